@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the reference's headline metric on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 `value` (BASELINE.json configs[1] at N = 1): synthetic Zipf(1.0)-distributed bytes in independent 1 MiB blocks,
 cudppCompress (BWT -> MTF -> Huffman) encode, inputs resident in HBM before the timed region.  A "step" is one pass
@@ -13,7 +13,13 @@ exact-length streams gathered on rank 0 over RCCL -- runs after the timed region
 rank 0 then checks that what it gathered equals what a single process produces for sampled blocks of every rank and
 DECODES gathered blocks of every rank back to their input.
 
-The same JSON line carries, measured in the same run on rank 0 at N = 1:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs) and prints the line: it
+carries `value` and `ms_per_step` (one timed step in milliseconds) and what the timed steps give for free (compression ratio,
+flagged-block counts).  Everything else takes runs of its own and needs --full: the per-kernel pass and `roofline`, the
+decode leg and its round-trip check, the parity of sampled blocks against the oracle, the multi-GPU gather leg, and the
+figures below.
+
+With --full the same JSON line carries, measured in the same run on rank 0 at N = 1:
     single_call                  what a drop-in caller of the reference API gets: cudppCompress, one 1 MiB block
     culzss                       configs[2]: 4 GiB log-style ASCII through the CULZSS path, device resident
     hd_decode                    configs[4] (one GPU's share): CUHD-shaped Huffman-only decode
@@ -852,9 +858,50 @@ def leg_hd(torch, glc, dev, mib, iters=5):
                          "sample": "%d MiB bit-serial oracle decode" % (ns >> 20)}}
 
 
-def compact_line(res, details_path):
-    """the ONE line the driver keeps (it retains the last 8 KB of output): every headline figure, `roofline` and `cpu_baseline`
-    as the contract asks; the per-kernel tables and every leg's sub-figures go to the details file"""
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs writes at most this much
+DUMP_WORD_BLOCKS = 16              # blocks whose compressed words are written (a seeded sample)
+DUMP_TABLE_BLOCKS = 4096           # blocks whose histograms and sub-block offsets are written (all of them up to this count)
+
+
+def dump_outputs(dirname, out, words_of_block, block_off, nblocks, nsub, seed=0x5EED00D0):
+    """--dump-outputs: what the timed encode's last step handed its caller, as DIR/<name>.npy.  Every value is exact in the
+    float type it is written in (float32 for values below 2^24, float64 for the 32-bit stream words):
+        size, bwt_index        per block: stream length in 32-bit words, BWT index             (all blocks, float64)
+        stream_offset          per block + 1: where each block's stream starts in the one compact array  (float64)
+        table_blocks           which blocks hist / sub_offsets hold (all up to 4096, else a seeded sample)
+        hist, sub_offsets      [blocks, 256] symbol histograms and Huffman sub-block word offsets  (float32)
+        word_blocks            a seeded sample of 16 blocks ...
+        words                  ... and their compressed streams back to back, size[word_blocks] words each (float64)
+    The samples depend on the block count only, so two runs with the same arguments write the same arrays."""
+    import numpy as np
+    import torch
+    rng = np.random.default_rng(seed)
+    size = out["size"][:nblocks].cpu().numpy().astype(np.int64)
+    arrays = {"size": size.astype(np.float64),
+              "bwt_index": out["bwt_index"][:nblocks].cpu().numpy().astype(np.float64),
+              "stream_offset": block_off[:nblocks + 1].cpu().numpy().astype(np.float64)}
+    tb = np.arange(nblocks) if nblocks <= DUMP_TABLE_BLOCKS else np.sort(rng.choice(nblocks, DUMP_TABLE_BLOCKS, replace=False))
+    arrays["table_blocks"] = tb.astype(np.float64)
+    hist = out["hist"].view(-1, 256)
+    subo = out["offsets"].view(-1, nsub)
+    idx = torch.from_numpy(tb.astype(np.int64)).to(hist.device)
+    arrays["hist"] = hist.index_select(0, idx).cpu().numpy().astype(np.float32)
+    arrays["sub_offsets"] = subo.index_select(0, idx).cpu().numpy().astype(np.float32)
+    wb = np.sort(rng.choice(nblocks, min(DUMP_WORD_BLOCKS, nblocks), replace=False))
+    used = sum(a.nbytes for a in arrays.values()) + 8 * wb.size
+    while wb.size > 1 and used + 8 * int(size[wb].sum()) > DUMP_LIMIT_BYTES:
+        wb = wb[:-1]
+    arrays["word_blocks"] = wb.astype(np.float64)
+    arrays["words"] = np.concatenate([words_of_block(int(b), int(size[b])).cpu().numpy().view(np.uint32).astype(np.float64) for b in wb])
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sum(a.nbytes for a in arrays.values())
+
+
+def compact_line(res, details_path, full=True):
+    """the ONE line the driver keeps (it retains the last 8 KB of output): every headline figure and, with --full, `roofline` and
+    `cpu_baseline` as the contract asks; the per-kernel tables and every leg's sub-figures go to the details file"""
     def pick(d, keys):
         return {k: d[k] for k in keys if isinstance(d, dict) and k in d and d[k] is not None}
     line = pick(res, ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
@@ -869,20 +916,22 @@ def compact_line(res, details_path):
                            "decode_one_plan_pipelined_GBps",
                            "frac_of_hbm_read_roofline", "frac_of_hbm_roofline_algorithmic_1_plus_rho", "encode_hbm_bytes_per_input_byte",
                            "stream_read_ceiling_GBps", "parity", "roundtrip", "value_with_gather", "gather_ms", "rccl_ranks_seen"]))
-    rf = res.get("roofline") or {}
-    line["roofline"] = pick(rf, ["kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "avg_launch_ms",
-                                 "launches", "kernel_design_frac", "hbm_busy_frac", "valu_issue_frac", "salu_issue_frac", "lds_busy_frac", "timing"])
-    line["roofline"]["traffic"] = rf.get("traffic")
-    kt = res.get("kernels") or {}
-    line["kernel_ms_per_launch"] = {k: v["avg_launch_ms"] for k, v in kt.items()}
+    if full:                                                  # (a plain run has no per-kernel pass and no legs: --full)
+        rf = res.get("roofline") or {}
+        line["roofline"] = pick(rf, ["kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch", "avg_launch_ms",
+                                     "launches", "kernel_design_frac", "hbm_busy_frac", "valu_issue_frac", "salu_issue_frac", "lds_busy_frac", "timing"])
+        line["roofline"]["traffic"] = rf.get("traffic")
+        kt = res.get("kernels") or {}
+        line["kernel_ms_per_launch"] = {k: v["avg_launch_ms"] for k, v in kt.items()}
     dec = res.get("decode") or {}
     if dec.get("roofline"):
         line["decode_roofline"] = pick(dec["roofline"], ["kernel", "bound", "frac", "kernel_design_frac", "traffic", "avg_launch_ms", "hbm_busy_frac"])
     sc = res.get("single_call") or {}
     tl = res.get("text_like") or {}
-    line["single_call"] = {"zipf_ms": sc.get("ms_per_call_median"), "zipf_host_ms_in_call": sc.get("ms_host_in_call"),
-                           "loop_GBps": sc.get("loop_GBps"), "text_loop_GBps": (tl.get("single_call_text") or {}).get("loop_GBps"),
-                           "text_ms": (tl.get("single_call_text") or {}).get("ms_per_call_median"), "host_syncs_in_call": sc.get("host_syncs_per_call")}
+    if full:
+        line["single_call"] = {"zipf_ms": sc.get("ms_per_call_median"), "zipf_host_ms_in_call": sc.get("ms_host_in_call"),
+                               "loop_GBps": sc.get("loop_GBps"), "text_loop_GBps": (tl.get("single_call_text") or {}).get("loop_GBps"),
+                               "text_ms": (tl.get("single_call_text") or {}).get("ms_per_call_median"), "host_syncs_in_call": sc.get("host_syncs_per_call")}
     if tl:
         line["text_like"] = {k: pick(tl[k], ["GBps", "GBps_rows2048", "ratio", "distinct_blocks", "blocks_left_by_sample_sorter", "round_trip_ok"]) for k in ("text", "log") if k in tl}
         if tl.get("deep_repeats"):
@@ -926,7 +975,7 @@ def emit(res, args):
             shown = os.path.relpath(path, ROOT)
         except OSError:
             shown = None
-    print(json.dumps(compact_line(res, shown)), flush=True)
+    print(json.dumps(compact_line(res, shown, full=args.full)), flush=True)
 
 
 def main():
@@ -966,6 +1015,14 @@ def main():
     ap.add_argument("--with-gather", action="store_true",
                     help="N>1: include the RCCL gather of records + streams to rank 0 in the timed region")
     ap.add_argument("--sorter", type=int, default=0, help="0 bucket sorter (default), 1 general sorter only (A/B)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: the per-kernel pass (`roofline`, `kernels`, "
+                         "`value_no_stage_overlap_GBps`), the decode leg and its round-trip check, the parity of sampled blocks against "
+                         "the oracle, the multi-GPU gather leg and, at N = 1, the single_call / culzss / hd_decode / text_like / ceiling / "
+                         "cpu_baseline legs.  Off: set up, warm up, time the steps, dump, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, at most 64 MB: all per-block "
+                         "records, a seeded sample of the streams; rank 0's blocks when N > 1; see dump_outputs)")
     args = ap.parse_args()
 
     import numpy as np
@@ -1213,8 +1270,11 @@ def main():
     keep_queued[0] = False
     barrier()
     t1 = time.perf_counter()
+    # what the timed path computed in its last step, before anything else runs on the GPU
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, words_of_block, compact_off, nblocks, nsub)
     no_overlap_gbps = None
-    if not profile_in_timed:
+    if args.full and not profile_in_timed:
         for pl in plans:
             pl.synchronize()
             pl.set_pipelining(False)
@@ -1230,14 +1290,15 @@ def main():
         if world > 1:
             dist.all_reduce(tno, op=dist.ReduceOp.MAX)
         no_overlap_gbps = float(nblocks) * n * world / float(tno.item()) / 1e9
-    kernels = {}
-    for pl in plans:
-        pl.synchronize()
-        for name, k in pl.kernel_profiles().items():
-            a = kernels.setdefault(name, dict(ms=0.0, launches=0, units=0.0))
-            for key in a:
-                a[key] += k[key]
-    stage_ms = plan.last_timing()
+    kernels, stage_ms = {}, None
+    if args.full:
+        for pl in plans:
+            pl.synchronize()
+            for name, k in pl.kernel_profiles().items():
+                a = kernels.setdefault(name, dict(ms=0.0, launches=0, units=0.0))
+                for key in a:
+                    a[key] += k[key]
+        stage_ms = plan.last_timing()
     for pl in plans:
         pl.enable_timing(0)
         pl.set_pipelining(False)
@@ -1340,71 +1401,72 @@ def main():
         del gathered
         return gather_info
 
-    # decode leg (not part of `value`): every block back through the HIP decoder, then the
-    # full-size property check decode(encode(x)) == x on all bytes
-    d_back = torch.empty_like(d_in)
+    if args.full:
+        # decode leg (not part of `value`): every block back through the HIP decoder, then the
+        # full-size property check decode(encode(x)) == x on all bytes
+        d_back = torch.empty_like(d_in)
 
-    def dec_worker(t, nt):
-        torch.cuda.set_device(dev)
-        pl = plans[t]
-        for b0 in batches[t::nt]:
-            nb = min(rows, nblocks - b0)
-            rc = dec_batch(pl, b0, nb, d_back.data_ptr() + b0 * n)
-            if rc != 0:
-                raise RuntimeError("glcDecompressBatch -> %d" % rc)
-        pl.synchronize()
+        def dec_worker(t, nt):
+            torch.cuda.set_device(dev)
+            pl = plans[t]
+            for b0 in batches[t::nt]:
+                nb = min(rows, nblocks - b0)
+                rc = dec_batch(pl, b0, nb, d_back.data_ptr() + b0 * n)
+                if rc != 0:
+                    raise RuntimeError("glcDecompressBatch -> %d" % rc)
+            pl.synchronize()
 
-    def decode_all():
-        run_threads(dec_worker, args.dec_threads)
+        def decode_all():
+            run_threads(dec_worker, args.dec_threads)
 
-    for pl in plans:                                          # second half of a call overlaps the first half of the next
-        pl.set_pipelining(not args.no_dec_pipeline)
-    decode_all()
-    barrier()
-    td0 = time.perf_counter()
-    decode_all()
-    barrier()
-    td1 = time.perf_counter()
-    if not bool(torch.equal(d_back, d_in)):
-        raise RuntimeError("round trip failed: decode(encode(x)) != x")
-    del d_back
-    # one plan, stages back to back: the decoder as a single caller sees it
-    for pl in plans:
-        pl.set_pipelining(False)
-    # (1024-block calls, whatever the encoder's batches are: the decoder's per-kernel table and its pipelined mode -- four calls,
-    #  each one's inverse BWT under the next one's Huffman + inverse MTF -- are quoted on them since round 3)
-    drows = min(rows, 1024)
-    dbatches = list(range(0, nblocks, drows))[:4]
-    d_back1 = torch.empty(drows * n, dtype=torch.uint8, device=dev)
-    plan.synchronize()
-    plan.enable_timing(3)                                     # per-kernel hipEvent pairs for the decoder's roofline block
-    t0d = time.perf_counter()
-    for b0 in dbatches:
-        dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
-    plan.synchronize()
-    dec1 = sum(min(drows, nblocks - b0) for b0 in dbatches) * n / (time.perf_counter() - t0d) / 1e9
-    dec_prof = plan.kernel_profiles()
-    plan.enable_timing(0)
-    # ... and the same plan with its stage pipelining on (glcPlanSetPipelining: inverse BWT of call k on the plan's side stream
-    # under Huffman + inverse MTF of call k + 1): ONE plan, one caller thread -- the figure a single caller gets
-    plan.set_pipelining(True)
-    for b0 in dbatches:
-        dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
-    plan.synchronize()
-    t0p = time.perf_counter()
-    for b0 in dbatches:
-        dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
-    plan.synchronize()
-    dec1_pipe = sum(min(drows, nblocks - b0) for b0 in dbatches) * n / (time.perf_counter() - t0p) / 1e9
-    last_b0 = dbatches[-1]
-    if not bool(torch.equal(d_back1[:min(drows, nblocks - last_b0) * n], d_in[last_b0 * n:(last_b0 + min(drows, nblocks - last_b0)) * n])):
-        raise RuntimeError("round trip failed in the pipelined one-plan decode")
-    plan.set_pipelining(False)
-    del d_back1
-    dec_elapsed = torch.tensor([td1 - td0], dtype=torch.float64, device=dev)
-    if world > 1:
-        dist.all_reduce(dec_elapsed, op=dist.ReduceOp.MAX)
-    decode_gbps = float(nblocks) * n * world / float(dec_elapsed.item()) / 1e9
+        for pl in plans:                                          # second half of a call overlaps the first half of the next
+            pl.set_pipelining(not args.no_dec_pipeline)
+        decode_all()
+        barrier()
+        td0 = time.perf_counter()
+        decode_all()
+        barrier()
+        td1 = time.perf_counter()
+        if not bool(torch.equal(d_back, d_in)):
+            raise RuntimeError("round trip failed: decode(encode(x)) != x")
+        del d_back
+        # one plan, stages back to back: the decoder as a single caller sees it
+        for pl in plans:
+            pl.set_pipelining(False)
+        # (1024-block calls, whatever the encoder's batches are: the decoder's per-kernel table and its pipelined mode -- four calls,
+        #  each one's inverse BWT under the next one's Huffman + inverse MTF -- are quoted on them since round 3)
+        drows = min(rows, 1024)
+        dbatches = list(range(0, nblocks, drows))[:4]
+        d_back1 = torch.empty(drows * n, dtype=torch.uint8, device=dev)
+        plan.synchronize()
+        plan.enable_timing(3)                                     # per-kernel hipEvent pairs for the decoder's roofline block
+        t0d = time.perf_counter()
+        for b0 in dbatches:
+            dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
+        plan.synchronize()
+        dec1 = sum(min(drows, nblocks - b0) for b0 in dbatches) * n / (time.perf_counter() - t0d) / 1e9
+        dec_prof = plan.kernel_profiles()
+        plan.enable_timing(0)
+        # ... and the same plan with its stage pipelining on (glcPlanSetPipelining: inverse BWT of call k on the plan's side stream
+        # under Huffman + inverse MTF of call k + 1): ONE plan, one caller thread -- the figure a single caller gets
+        plan.set_pipelining(True)
+        for b0 in dbatches:
+            dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
+        plan.synchronize()
+        t0p = time.perf_counter()
+        for b0 in dbatches:
+            dec_batch(plan, b0, min(drows, nblocks - b0), d_back1.data_ptr())
+        plan.synchronize()
+        dec1_pipe = sum(min(drows, nblocks - b0) for b0 in dbatches) * n / (time.perf_counter() - t0p) / 1e9
+        last_b0 = dbatches[-1]
+        if not bool(torch.equal(d_back1[:min(drows, nblocks - last_b0) * n], d_in[last_b0 * n:(last_b0 + min(drows, nblocks - last_b0)) * n])):
+            raise RuntimeError("round trip failed in the pipelined one-plan decode")
+        plan.set_pipelining(False)
+        del d_back1
+        dec_elapsed = torch.tensor([td1 - td0], dtype=torch.float64, device=dev)
+        if world > 1:
+            dist.all_reduce(dec_elapsed, op=dist.ReduceOp.MAX)
+        decode_gbps = float(nblocks) * n * world / float(dec_elapsed.item()) / 1e9
 
     my_elapsed = t1 - t0
     elapsed = torch.tensor([my_elapsed], dtype=torch.float64, device=dev)
@@ -1418,11 +1480,11 @@ def main():
     total_bytes = float(nblocks) * n * world * args.steps
     value = total_bytes / elapsed / 1e9
 
-    # compression ratio + parity of 64 sampled blocks against the oracle (after the timed region)
+    # compression ratio; with --full, parity of 64 sampled blocks against the oracle (after the timed region)
     sizes = out["size"].cpu().numpy().astype(np.int64)
     ratio = float(nblocks * n) / float(sizes.sum() * 4)
     verify, sample_host = None, []
-    if rank == 0:
+    if rank == 0 and args.full:
         nver = min(nblocks, 64)
         pick = sorted(set(int(x) for x in np.linspace(0, nblocks - 1, nver).astype(int)))
         sample_host = [d_in[b * n:(b + 1) * n].cpu().numpy() for b in pick]
@@ -1444,60 +1506,6 @@ def main():
     res = None
     if rank == 0:
         rho = 1.0 / ratio
-        ktab = {}
-        pmc_per64, issue, valu_src = load_pmc_insts()
-        census = load_census()
-        ttab_all, tblocks_all, tcollected_all = load_traffic()
-        for name, k in kernels.items():
-            avg = k["ms"] / max(1, k["launches"])
-            per_launch_units = k["units"] / max(1, k["launches"])
-            ab = ALG_BYTES.get(name)
-            if name == "k_huff_pack":
-                ab = 1.0 + rho
-            ach = per_launch_units * ab / (avg * 1e-3) / 1e9 if (ab and avg > 0) else None
-            e = {"avg_launch_ms": round(avg, 4), "launches": k["launches"], "input_bytes_per_launch": int(per_launch_units),
-                 # the bytes an encoder cannot avoid are 1 read + rho written per input byte
-                 "frac_8d": round(per_launch_units * (1.0 + rho) / (avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if avg > 0 else None,
-                 # the kernel's OWN design traffic (e.g. 8-byte suffix words in and out of HBM): what its formulation asks of HBM
-                 "design_bytes_per_input_byte": ab, "design_GBps": round(ach, 1) if ach else None,
-                 "kernel_design_frac": round(ach / HBM_PEAK_GBPS, 4) if ach else None}
-            t = sum(ttab_all.get(key, 0) for key in name.split("+"))
-            if t and avg > 0:
-                tb = t * (per_launch_units / float(n)) / tblocks_all          # counted per launch of tblocks_all blocks, scaled
-                e["traffic"] = int(round(tb))
-                e["hbm_busy_frac"] = round(tb / (avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 3)
-            e.update(issue_fractions(name, pmc_per64, census, issue, per_launch_units, avg))
-            e["bound"] = bound_of(e)
-            ktab[name] = e
-        # decoder: per-kernel table of the one-plan pass (stages back to back) and its dominant kernel
-        dec_names = [k for k in dec_prof if k.startswith(("k_dec", "k_imtf", "k_ibwt"))]
-        dec_alg = {"k_dec_prepare+k_dec_huff": rho + 1.0, "k_imtf_pos": 2.0, "k_imtf_scan+k_imtf_apply": 2.0,
-                   "k_ibwt_hist+k_rs_scan+k_ibwt_lf": 2.0 + 4.0, "k_ibwt_walk": 4.0 + 1.0, "k_ibwt_rank+k_ibwt_emit": 2.0}
-
-        def dec_get(i):
-            if i >= len(dec_names):
-                return None
-            k = dec_prof[dec_names[i]]
-            return dec_names[i], k["ms"], k["launches"], k["units"]
-        dec_pmc = dict(pmc_per64)
-        dec_pmc["k_dec_huff"] = pmc_per64.get("k_dec_huff_lanes", {})
-        ttab = dict(ttab_all)
-        ttab.setdefault("k_dec_huff", 0)
-        dtab = kernel_table(dec_get, dec_alg, dec_pmc, issue, traffic_tab=ttab, blocks_in_traffic=tblocks_all, census=census, rho=rho)
-        # one_plan_GBps keeps rounds 1-4's meaning (ONE plan, stages back to back: the pass the kernel table and hbm_frac below
-        # come from); the plan's pipelined mode has its own key (round 5 printed it under the first one: ADVICE r5)
-        decode_block = {"one_plan_GBps": round(dec1, 4), "one_plan_pipelined_GBps": round(dec1_pipe, 4),
-                        "one_plan_stages_back_to_back_GBps": round(dec1, 4),
-                        "pipelined_plans_GBps": round(decode_gbps, 4),
-                        "hbm_frac_algorithmic_rho_plus_1": round((1 + rho) * dec1 / HBM_PEAK_GBPS, 6),
-                        "roofline": roofline_of(dtab, "one plan, stages back to back; frac = (rho + 1) x decoded bytes of a launch / its time / 8 TB/s (SURVEY.md 8(d)); "
-                                                      "kernel_design_frac counts the kernel's own design traffic"),
-                        "traffic_source": "profiles/pmc_traffic.json (%s)" % tcollected_all,
-                        "kernels": dtab}
-        dom = max(kernels, key=lambda kname: kernels[kname]["ms"]) if kernels else None
-        d = ktab.get(dom, {})
-        enc_traffic = sum(ttab_all.get(k2, 0) for k2 in ("k_fs_hist", "k_fs_part", "k_fs_sort", "k_fs_ties", "k_mtf_chunk_lists", "k_mtf_scan_lists",
-                                                       "k_mtf_encode", "k_huff_build", "k_huff_pack")) / (tblocks_all * float(n)) if ttab_all else None
         res = {
             "metric": "encode+decode GB/s (input bytes) per GPU and whole-node; compression ratio parity",
             "value": round(value, 4), "unit": "GB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1528,40 +1536,97 @@ def main():
             "per_rank_GBps": [round(v, 3) for v in per_rank_gbps],
             "compression_ratio": round(ratio, 4),
             "value_no_stage_overlap_GBps": round(no_overlap_gbps, 4) if no_overlap_gbps else (round(value, 4) if not use_pipe else None),
-            "decode_GBps": round(decode_gbps, 4),
-            "decode_one_plan_GBps": round(dec1, 4),
-            "decode_one_plan_pipelined_GBps": round(dec1_pipe, 4),
-            "decode_one_plan_stages_back_to_back_GBps": round(dec1, 4),
-            "decode": decode_block,
-            "roundtrip": "decode(encode(x)) == x on all %d blocks per GPU" % nblocks,
             "frac_of_hbm_read_roofline": round(value / world / HBM_PEAK_GBPS, 6),
             "frac_of_hbm_roofline_algorithmic_1_plus_rho": round((1 + rho) * value / world / HBM_PEAK_GBPS, 6),
-            "encode_hbm_bytes_per_input_byte": round(enc_traffic, 2) if enc_traffic else None,
-            "stage_ms_last_batch": {"bwt": round(stage_ms[0], 3), "mtf": round(stage_ms[1], 3),
-                                    "huffman": round(stage_ms[2], 3), "total": round(stage_ms[3], 3)},
-            "roofline": {"kernel": "glc::" + dom if dom else None, "bound": d.get("bound"),
-                         # algorithmic bytes = (1 read + rho written) per input byte x the input bytes of one launch
-                         "achieved": round(d["frac_8d"] * HBM_PEAK_GBPS, 1) if d.get("frac_8d") else None,
-                         "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": d.get("frac_8d"), "traffic": d.get("traffic"),
-                         "algorithmic_bytes_per_launch": int(round(d["input_bytes_per_launch"] * (1.0 + rho))) if d else None,
-                         "avg_launch_ms": d.get("avg_launch_ms"), "launches": d.get("launches"),
-                         "kernel_design_frac": d.get("kernel_design_frac"), "kernel_design_bytes_per_input_byte": d.get("design_bytes_per_input_byte"),
-                         "hbm_busy_frac": d.get("hbm_busy_frac"), "valu_issue_frac": d.get("valu_issue_frac"),
-                         "salu_issue_frac": d.get("salu_issue_frac"), "lds_busy_frac": d.get("lds_busy_frac"),
-                         "traffic_source": "profiles/pmc_traffic.json (%s), scaled to this run's launch size" % tcollected_all,
-                         "valu_source": valu_src,
-                         "timing": ("hipEvent pairs on the launch stream around every launch" +
-                                    (" inside the timed region" if profile_in_timed else
-                                     " of one more pass of the same encode WITHOUT stage overlap (each time is the kernel's own)")),
-                         "note": "dominant = largest summed launch time of the encode pipeline; frac follows SURVEY.md 8(d) (1 + rho algorithmic bytes per "
-                                 "input byte); bound = the busiest of {HBM traffic / 8 TB/s, VALU issue (per-class cycles: static census x PMC count), "
-                                 "scalar issue, LDS busy}, 'latency' when none reaches 0.6"},
-            "kernels": ktab,
-            "parity": verify,
         }
+        if args.full:
+            ktab = {}
+            pmc_per64, issue, valu_src = load_pmc_insts()
+            census = load_census()
+            ttab_all, tblocks_all, tcollected_all = load_traffic()
+            for name, k in kernels.items():
+                avg = k["ms"] / max(1, k["launches"])
+                per_launch_units = k["units"] / max(1, k["launches"])
+                ab = ALG_BYTES.get(name)
+                if name == "k_huff_pack":
+                    ab = 1.0 + rho
+                ach = per_launch_units * ab / (avg * 1e-3) / 1e9 if (ab and avg > 0) else None
+                e = {"avg_launch_ms": round(avg, 4), "launches": k["launches"], "input_bytes_per_launch": int(per_launch_units),
+                     # the bytes an encoder cannot avoid are 1 read + rho written per input byte
+                     "frac_8d": round(per_launch_units * (1.0 + rho) / (avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4) if avg > 0 else None,
+                     # the kernel's OWN design traffic (e.g. 8-byte suffix words in and out of HBM): what its formulation asks of HBM
+                     "design_bytes_per_input_byte": ab, "design_GBps": round(ach, 1) if ach else None,
+                     "kernel_design_frac": round(ach / HBM_PEAK_GBPS, 4) if ach else None}
+                t = sum(ttab_all.get(key, 0) for key in name.split("+"))
+                if t and avg > 0:
+                    tb = t * (per_launch_units / float(n)) / tblocks_all          # counted per launch of tblocks_all blocks, scaled
+                    e["traffic"] = int(round(tb))
+                    e["hbm_busy_frac"] = round(tb / (avg * 1e-3) / 1e9 / HBM_PEAK_GBPS, 3)
+                e.update(issue_fractions(name, pmc_per64, census, issue, per_launch_units, avg))
+                e["bound"] = bound_of(e)
+                ktab[name] = e
+            # decoder: per-kernel table of the one-plan pass (stages back to back) and its dominant kernel
+            dec_names = [k for k in dec_prof if k.startswith(("k_dec", "k_imtf", "k_ibwt"))]
+            dec_alg = {"k_dec_prepare+k_dec_huff": rho + 1.0, "k_imtf_pos": 2.0, "k_imtf_scan+k_imtf_apply": 2.0,
+                       "k_ibwt_hist+k_rs_scan+k_ibwt_lf": 2.0 + 4.0, "k_ibwt_walk": 4.0 + 1.0, "k_ibwt_rank+k_ibwt_emit": 2.0}
 
-    # the other configs' single-GPU figures, same run (rank 0, N = 1 only)
-    if rank == 0 and world == 1 and not args.main_only:
+            def dec_get(i):
+                if i >= len(dec_names):
+                    return None
+                k = dec_prof[dec_names[i]]
+                return dec_names[i], k["ms"], k["launches"], k["units"]
+            dec_pmc = dict(pmc_per64)
+            dec_pmc["k_dec_huff"] = pmc_per64.get("k_dec_huff_lanes", {})
+            ttab = dict(ttab_all)
+            ttab.setdefault("k_dec_huff", 0)
+            dtab = kernel_table(dec_get, dec_alg, dec_pmc, issue, traffic_tab=ttab, blocks_in_traffic=tblocks_all, census=census, rho=rho)
+            # one_plan_GBps keeps rounds 1-4's meaning (ONE plan, stages back to back: the pass the kernel table and hbm_frac below
+            # come from); the plan's pipelined mode has its own key (round 5 printed it under the first one: ADVICE r5)
+            decode_block = {"one_plan_GBps": round(dec1, 4), "one_plan_pipelined_GBps": round(dec1_pipe, 4),
+                            "one_plan_stages_back_to_back_GBps": round(dec1, 4),
+                            "pipelined_plans_GBps": round(decode_gbps, 4),
+                            "hbm_frac_algorithmic_rho_plus_1": round((1 + rho) * dec1 / HBM_PEAK_GBPS, 6),
+                            "roofline": roofline_of(dtab, "one plan, stages back to back; frac = (rho + 1) x decoded bytes of a launch / its time / 8 TB/s (SURVEY.md 8(d)); "
+                                                          "kernel_design_frac counts the kernel's own design traffic"),
+                            "traffic_source": "profiles/pmc_traffic.json (%s)" % tcollected_all,
+                            "kernels": dtab}
+            dom = max(kernels, key=lambda kname: kernels[kname]["ms"]) if kernels else None
+            d = ktab.get(dom, {})
+            enc_traffic = sum(ttab_all.get(k2, 0) for k2 in ("k_fs_hist", "k_fs_part", "k_fs_sort", "k_fs_ties", "k_mtf_chunk_lists", "k_mtf_scan_lists",
+                                                           "k_mtf_encode", "k_huff_build", "k_huff_pack")) / (tblocks_all * float(n)) if ttab_all else None
+            res.update({
+                "decode_GBps": round(decode_gbps, 4),
+                "decode_one_plan_GBps": round(dec1, 4),
+                "decode_one_plan_pipelined_GBps": round(dec1_pipe, 4),
+                "decode_one_plan_stages_back_to_back_GBps": round(dec1, 4),
+                "decode": decode_block,
+                "roundtrip": "decode(encode(x)) == x on all %d blocks per GPU" % nblocks,
+                "encode_hbm_bytes_per_input_byte": round(enc_traffic, 2) if enc_traffic else None,
+                "stage_ms_last_batch": {"bwt": round(stage_ms[0], 3), "mtf": round(stage_ms[1], 3),
+                                        "huffman": round(stage_ms[2], 3), "total": round(stage_ms[3], 3)},
+                "roofline": {"kernel": "glc::" + dom if dom else None, "bound": d.get("bound"),
+                             # algorithmic bytes = (1 read + rho written) per input byte x the input bytes of one launch
+                             "achieved": round(d["frac_8d"] * HBM_PEAK_GBPS, 1) if d.get("frac_8d") else None,
+                             "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": d.get("frac_8d"), "traffic": d.get("traffic"),
+                             "algorithmic_bytes_per_launch": int(round(d["input_bytes_per_launch"] * (1.0 + rho))) if d else None,
+                             "avg_launch_ms": d.get("avg_launch_ms"), "launches": d.get("launches"),
+                             "kernel_design_frac": d.get("kernel_design_frac"), "kernel_design_bytes_per_input_byte": d.get("design_bytes_per_input_byte"),
+                             "hbm_busy_frac": d.get("hbm_busy_frac"), "valu_issue_frac": d.get("valu_issue_frac"),
+                             "salu_issue_frac": d.get("salu_issue_frac"), "lds_busy_frac": d.get("lds_busy_frac"),
+                             "traffic_source": "profiles/pmc_traffic.json (%s), scaled to this run's launch size" % tcollected_all,
+                             "valu_source": valu_src,
+                             "timing": ("hipEvent pairs on the launch stream around every launch" +
+                                        (" inside the timed region" if profile_in_timed else
+                                         " of one more pass of the same encode WITHOUT stage overlap (each time is the kernel's own)")),
+                             "note": "dominant = largest summed launch time of the encode pipeline; frac follows SURVEY.md 8(d) (1 + rho algorithmic bytes per "
+                                     "input byte); bound = the busiest of {HBM traffic / 8 TB/s, VALU issue (per-class cycles: static census x PMC count), "
+                                     "scalar issue, LDS busy}, 'latency' when none reaches 0.6"},
+                "kernels": ktab,
+                "parity": verify,
+            })
+
+    # the other configs' single-GPU figures, same run (rank 0, N = 1 only; --full)
+    if args.full and rank == 0 and world == 1 and not args.main_only:
         for pl in plans[1:]:
             pl.close()
         plans = plans[:1]
@@ -1582,10 +1647,10 @@ def main():
         res["text_like"] = leg_text_like(torch, glc, dev)
         if not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(sample_host, log_sample, kind)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+    elif args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(sample_host, None, kind)
     gather_failed = False
-    if world > 1:
+    if world > 1 and args.full:
         # the gather leg last, under a watchdog: a rank that waits for a peer that is gone still lets the line out
         import threading
 

@@ -13,6 +13,12 @@ import datagen
 import oracle_lib as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+sys.path.insert(0, GOLD)
+import make_ref_live_gold as LG  # noqa: E402  (the inputs of ref_live_gold.npz)
+
+# what the reference's own CPU routines produced on LG's inputs (tests/golden/make_ref_live_gold.py): the "live" tests below
+# check the oracle against it everywhere, and run the routines again where oracle/_ref was built
+LIVE = np.load(os.path.join(GOLD, "ref_live_gold.npz"))
 
 
 @pytest.fixture(scope="module")
@@ -70,11 +76,13 @@ def test_reference_1m_vectors_known_answers():
     assert np.array_equal(O.decompress(r["bwt_index"], r["hist"], r["offsets"], r["words"], x.size), x)
 
 
-@pytest.mark.skipif(not O.have_ref_gold(), reason="oracle/_ref not built (no /root/reference on this box)")
 def test_oracle_vs_live_reference_gold():
-    for n, mod in ((1 << 20, 255), (500001, 128), (1048577, 255)):
+    for n, mod in LG.SA_CASES:
         x = O.glibc_rand_bytes(n, mod)
-        assert np.array_equal(O.suffix_array(x), O.ref_sa_gold(x))
+        sa = O.suffix_array(x)
+        assert sa.size == n and O.crc32(sa.view(np.uint8)) == int(LIVE["sa_crc_%d_%d" % (n, mod)])
+        if O.have_ref_gold():
+            assert np.array_equal(sa, O.ref_sa_gold(x))
 
 
 def test_stream_kats_do_not_drift(kats):
@@ -277,25 +285,34 @@ def test_oracle_compress_vs_reference_gold_chain(name):
     assert np.array_equal(r["hist"], HUFF["e_%s_hist" % name])
 
 
-@pytest.mark.skipif(not O.have_ref_compress_gold(), reason="oracle/_ref/libcompressgold.so not built (no /root/reference)")
 def test_reference_gold_live_against_oracle():
-    """where the reference's lines are compiled: trees, MTF, BWT and the gold decoder against the oracle, live"""
-    rng = np.random.default_rng(3)
-    for _ in range(40):
-        k = int(rng.integers(1, 257))
-        hist = np.zeros(256, dtype=np.uint32)
-        hist[rng.choice(256, k, replace=False)] = rng.integers(1, 50, k) if rng.random() < 0.5 else rng.integers(1, 100000, k)
-        _, lens = O.ref_codes_from_tree(O.ref_huffman_tree(hist))
+    """trees, MTF, BWT and the gold decoder of the reference against the oracle: as ref_live_gold.npz keeps them, and live
+    where the reference's lines are compiled"""
+    live = O.have_ref_compress_gold()
+    for i, hist in enumerate(LG.huff_hists()):
+        lens = LIVE["huff_lens"][i]
+        if live:
+            assert np.array_equal(O.ref_codes_from_tree(O.ref_huffman_tree(hist))[1], lens)
         assert np.array_equal(lens.astype(np.uint8), O.huff_codes(hist)[1])
-    x = datagen.text_bytes(20000, seed=8)
-    b, idx = O.ref_bwt_gold(x)
+    x, y = LG.compress_gold_inputs()
+    b, idx = LIVE["bwt_out"], int(LIVE["bwt_idx"])
+    if live:
+        rb, ridx = O.ref_bwt_gold(x)
+        assert ridx == idx and np.array_equal(rb, b)
+        assert np.array_equal(O.ref_mtf_gold(b), LIVE["mtf_out"])
     ob, oidx = O.bwt(x)
     assert idx == oidx and np.array_equal(b, ob)
-    assert np.array_equal(O.ref_mtf_gold(b), O.mtf(b))
-    y = datagen.zipf_bytes(1 << 20, seed=77)
+    assert np.array_equal(LIVE["mtf_out"], O.mtf(b))
     r = O.compress(y)
-    sym, byt = O.ref_compress_gold_decode(r["hist"], r["offsets"], r["words"], y.size)
-    assert np.array_equal(byt, O.bwt(y)[0])                  # gold Huffman decode + inverse MTF reads the oracle's stream
+    want = O.bwt(y)[0]
+    # the stream the gold decoder read back when ref_live_gold.npz was made
+    assert r["size"] == int(LIVE["stream_size"]) and r["bwt_index"] == int(LIVE["stream_bwt_index"])
+    for k in ("words", "offsets", "hist"):
+        assert O.crc32(r[k].view(np.uint8)) == int(LIVE["stream_crc_" + k]), k
+    if live:
+        sym, byt = O.ref_compress_gold_decode(r["hist"], r["offsets"], r["words"], y.size)
+        assert np.array_equal(byt, want)                      # gold Huffman decode + inverse MTF reads the oracle's stream
+    assert O.crc32(want) == int(LIVE["decode_crc"])
 
 
 # ------------------------------------------------ CULZSS packer vs the reference's own aftercomp (row a13) ----
@@ -341,47 +358,39 @@ def test_oracle_lzss_pack_vs_reference_aftercomp(name):
             assert np.array_equal(O.lzss_decode(ref_bytes), x), "oracle decoder on reference-packed bytes"
 
 
-@pytest.mark.skipif(not O.have_ref_aftercomp(), reason="oracle/_ref/libaftercomp.so not built (needs /root/reference)")
 def test_reference_aftercomp_live_against_fixture_and_oracle():
-    """in the build container: the reference's packer run now == the committed fixture == the oracle, on fresh
-    candidate streams too (random mixtures the fixture does not hold)"""
-    import ctypes
+    """the reference's packer == the committed fixture == the oracle, on fresh candidate streams too (random mixtures the
+    fixture does not hold; what the reference made of them is in ref_live_gold.npz); where oracle/_ref was built, the
+    reference's packer runs again now"""
     import zlib
-    L = O.ref_aftercomp_lib()
-
-    def ref(cand, n):
-        buf = np.zeros(n + 8192, dtype=np.uint8)
-        m = ctypes.c_int(-1)
-        c = cand.copy()
-        rc = L.aftercompression_wrapper(buf.ctypes.data, n, c.ctypes.data, ctypes.byref(m))
-        return buf[: m.value].copy() if rc == 1 else None
-
+    live = O.have_ref_aftercomp()
     for name in ("log_4pkt", "spaces_then_text", "syn_random_mix", "one_packet_random"):
         n, _, cand = lzss_gold_candidates(name)
-        r = ref(cand, n)
-        if int(LZSS_GOLD[name + "/rc"]) == 0:
-            assert r is None
-        else:
-            assert (zlib.crc32(r.tobytes()) & 0xFFFFFFFF) == int(LZSS_GOLD[name + "/crc"])
-    rng = np.random.default_rng(5)
-    for trial in range(6):
-        x = np.concatenate([datagen.log_bytes(8192, seed=100 + trial), rng.integers(97, 101, 4096, dtype=np.uint8),
-                            datagen.text_bytes(4096, seed=trial)])
+        for r in [O.lzss_pack(cand, n)] + ([LG.ref_aftercomp(cand, n)] if live else []):
+            if int(LZSS_GOLD[name + "/rc"]) == 0:
+                assert r is None
+            else:
+                assert (zlib.crc32(r.tobytes()) & 0xFFFFFFFF) == int(LZSS_GOLD[name + "/crc"])
+    for trial, x in enumerate(LG.aftercomp_inputs()):
         cand = O.lzss_candidates(x)
-        r, o = ref(cand, x.size), O.lzss_pack(cand, x.size)
-        assert (r is None) == (o is None) and (r is None or np.array_equal(r, o)), trial
+        o = O.lzss_pack(cand, x.size)
+        if int(LIVE["ac_%d_rc" % trial]) == 0:
+            assert o is None, trial
+        else:
+            assert o is not None and o.size == int(LIVE["ac_%d_size" % trial]), trial
+            assert (zlib.crc32(o.tobytes()) & 0xFFFFFFFF) == int(LIVE["ac_%d_crc" % trial]), trial
+        if live:
+            r = LG.ref_aftercomp(cand, x.size)
+            assert (r is None) == (o is None) and (r is None or np.array_equal(r, o)), trial
 
 
-PG1661 = "/root/reference/cuda-lzss-unknown/pg1661.txt"
-
-
-@pytest.mark.skipif(not os.path.exists(PG1661), reason="in-container only: the text lives under /root/reference")
 def test_survey_kat_on_pg1661():
     """the survey's INDEPENDENT lock-step restatement of EncodeKernel / aftercomp on pg1661.txt
     zero-padded to one 1 MiB buffer gave candidates CRC 799b54ef and 569 823 packed bytes, CRC 15c4edd7.  The only
-    pin rows a11 / a14 can have (EncodeKernel and DecodeKernel are CUDA only, no CPU twin, no test in the reference)."""
+    pin rows a11 / a14 can have (EncodeKernel and DecodeKernel are CUDA only, no CPU twin, no test in the reference).
+    The text is the reference's pg1661.txt, kept as tests/golden/pg1661.txt.bz2."""
     import zlib
-    raw = np.fromfile(PG1661, dtype=np.uint8)
+    raw = LG.pg1661_text()
     x = np.zeros(1 << 20, dtype=np.uint8)
     x[: raw.size] = raw[: 1 << 20]
     cand = O.lzss_candidates(x)
@@ -420,15 +429,15 @@ def test_oracle_lzss_candidates_vs_reference_findmatch(name):
     assert int(np.count_nonzero(cand[0::2] > 1)) == int(FM_GOLD[name + "/matches"])
 
 
-@pytest.mark.skipif(not O.have_ref_findmatch(), reason="oracle/_ref/libfindmatch.so not built (needs /root/reference)")
 def test_reference_findmatch_live_on_fresh_packets():
-    """the reference's FindMatch, run HERE on packets that are not in the fixture, against the oracle"""
-    sys.path.insert(0, GOLD)
+    """the reference's FindMatch on packets that are not in the fixture (its candidates kept in ref_live_gold.npz, and run
+    HERE where oracle/_ref was built) against the oracle"""
     import make_findmatch_gold as M
-    rng = np.random.default_rng(20260929)
-    for x in (datagen.log_bytes(8192, seed=123), datagen.text_bytes(4096, seed=321),
-              rng.integers(0, 3, 4096, dtype=np.uint8), np.repeat(rng.integers(0, 256, 64, dtype=np.uint8), 64)):
-        assert np.array_equal(M.ref_candidates(x), O.lzss_candidates(x))
+    for i, x in enumerate(LG.findmatch_inputs()):
+        want = LIVE["fm_%d" % i]
+        if O.have_ref_findmatch():
+            assert np.array_equal(M.ref_candidates(x), want)
+        assert np.array_equal(want, O.lzss_candidates(x))
 
 
 # ------------------------------------------------ the config-2 generator (SURVEY.md 8(d)) ----

@@ -2,7 +2,7 @@
 # Per-kernel instruction counters of the encode / decode pipelines (runs ON the GPU box through gpurun):
 #   bash tools/exp/pmc_insts.sh <tag>
 # Three rocprofv3 --pmc passes with --kernel-trace only (counters never share a run with other trace domains), over
-#   python bench.py --gib 0.25 --rows 256 --steps 1 --warmup 0 --no-cpu-baseline --no-verify --main-only --no-overlap-pass
+#   python bench.py --gib 0.25 --rows 256 --steps 1 --warmup 0 --no-cpu-baseline --no-verify --main-only --no-overlap-pass --full
 # -> gpurun_out/<tag>_pmc_insts.json: for every kernel the counter sums per launch, the launch count and the average
 # duration under the counters.  profiles/make_pmc_insts.py <tag> turns it into the tracked summary bench.py reads.
 set -u
@@ -12,7 +12,7 @@ OUT=$REPO/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-CMD="python $REPO/bench.py --gib 0.25 --rows 256 --steps 1 --warmup 0 --no-cpu-baseline --no-verify --main-only --no-overlap-pass"
+CMD="python $REPO/bench.py --gib 0.25 --rows 256 --steps 1 --warmup 0 --no-cpu-baseline --no-verify --main-only --no-overlap-pass --full"
 i=0
 for SET in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SMEM" \
            "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA" \

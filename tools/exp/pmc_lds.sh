@@ -1,6 +1,7 @@
 # LDS health of every kernel of the bench run: unaligned stalls, bank conflicts (one rocprofv3 --pmc pass, --kernel-trace only)
+REPO=$(cd "$(dirname "$0")/../.." && pwd)
 cd /tmp; export TMPDIR=/tmp
-rm -rf /tmp/pm; timeout 400 rocprofv3 --pmc SQ_LDS_UNALIGNED_STALL SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --kernel-trace -d /tmp/pm -o p -- python $GRAFT_REPO_ROOT/bench.py --main-only --no-overlap-pass --steps 2 --warmup 1 > /tmp/l.txt 2>&1
+rm -rf /tmp/pm; timeout 400 rocprofv3 --pmc SQ_LDS_UNALIGNED_STALL SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_LDS --kernel-trace -d /tmp/pm -o p -- python $REPO/bench.py --main-only --no-overlap-pass --full --steps 2 --warmup 1 > /tmp/l.txt 2>&1
 python - <<PY
 import sqlite3,glob,collections
 db=glob.glob("/tmp/pm/**/*.db",recursive=True)
