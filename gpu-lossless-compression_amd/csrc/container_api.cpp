@@ -1,0 +1,602 @@
+// container_api.cpp -- the C ABI of include/glc_container.h: the BWT container over a COMPRESS plan.
+// Encode: one hooked glcCompressBatchCompact per frame writes the Huffman records straight into the container; the kernels of
+// container.hip decide the record kinds before the payload offsets are scanned, copy the raw records, CRC everything and
+// write the frame's tables behind the packer.  Frames chain on the device (a cursor word): no host read inside or between
+// frames, one at the end.  Decode: per frame the host reads the 32-byte frame header, the device checks the tables and records
+// (one verdict read back), then raw records are copied out, runs of Huffman blocks go to glcDecompressBatchCompact reading
+// the tables in place, and the decoded bytes are checked against the blocks' CRCs.
+#include "../../include/glc_container.h"
+#include "container_internal.h"
+
+#include <mutex>
+#include <map>
+#include <new>
+#include <stdio.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <vector>
+
+using namespace glc;
+
+namespace glc {
+static const CrcTables h_crc = crc_make_tables();
+uint32_t crc32_host(const void *data, size_t len, uint32_t crc)
+{
+    const uint8_t *p = static_cast<const uint8_t *>(data);
+    uint32_t r = ~crc;
+    for (size_t i = 0; i < len; i++) r = h_crc.t[0][(r ^ p[i]) & 255] ^ (r >> 8);
+    return ~r;
+}
+} // namespace glc
+
+namespace {
+
+struct LastError { unsigned long long v[3] = {0, ~0ull, ~0ull}; };
+std::mutex g_err_mu;
+std::map<CUDPPHandle, LastError> g_err;
+
+void set_error(CUDPPHandle plan, unsigned long long what, unsigned long long frame = ~0ull, unsigned long long block = ~0ull)
+{
+    std::lock_guard<std::mutex> g(g_err_mu);
+    LastError &e = g_err[plan];
+    e.v[0] = what; e.v[1] = frame; e.v[2] = block;
+}
+
+CUDPPResult fail(CUDPPHandle plan, unsigned long long what, unsigned long long frame = ~0ull, unsigned long long block = ~0ull)
+{
+    set_error(plan, what, frame, block);
+    return what == CT_CAPACITY ? CUDPP_ERROR_ILLEGAL_CONFIGURATION : CUDPP_ERROR_UNKNOWN;
+}
+
+CUDPPResult hip_res(hipError_t e)
+{
+    if (e == hipSuccess) return CUDPP_SUCCESS;
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? CUDPP_ERROR_INSUFFICIENT_RESOURCES : CUDPP_ERROR_UNKNOWN;
+}
+
+#define CT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_res(e_); } while (0)
+
+struct Plan {
+    CUDPPHandle h = 0;
+    uint32_t n = 0, rows = 0, parity = 0;
+    hipStream_t st = nullptr;
+    bool ok(CUDPPHandle plan) { h = plan; return plan != 0 && plan != CUDPP_INVALID_HANDLE && plan_info(plan, &n, &rows, &st, &parity); }
+};
+
+unsigned long long frame_bytes(uint32_t nb, uint32_t blk_len, unsigned long long payload_words)
+{
+    return CT_FRAME_HDR + 4 * ct_tables(nb, blk_len).words + 4 * (payload_words + (payload_words & 1));
+}
+
+// worst case of one frame of nb blocks of blk_len (raw records)
+unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
+{
+    return frame_bytes(nb, blk_len, (unsigned long long)nb * ct_raw_words(blk_len) + nb);
+}
+
+void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total)
+{
+    h[0] = CT_MAGIC_STREAM; h[1] = CT_VERSION; h[2] = block_len; h[3] = 0;
+    h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
+    h[6] = crc32_host(h, 24); h[7] = 0;
+}
+
+// -------------------------------------------------------------------------------------------------------------------------
+// encoder: device scratch for two frames (the plan's call parity) of up to `rows` blocks, and the running state
+// -------------------------------------------------------------------------------------------------------------------------
+struct Encoder {
+    Plan P;
+    void *mem = nullptr;
+    CtEncState *state = nullptr;
+    uint32_t *status = nullptr;
+    unsigned long long *d_len = nullptr;
+    CtEncFrame fr[2] = {};
+
+    hipError_t init()
+    {
+        const size_t R = P.rows, nsub = (P.n + HUFF_BLOCK - 1) / HUFF_BLOCK;
+        const size_t per = (8 * (5 * R + 6) + 4 * (262 * R + R * nsub + 4) + 255) & ~(size_t)255;
+        hipError_t e = hipMalloc(&mem, 256 + 2 * per);
+        if (e != hipSuccess) { mem = nullptr; return e; }
+        uint8_t *q = static_cast<uint8_t *>(mem);
+        state = reinterpret_cast<CtEncState *>(q);
+        status = reinterpret_cast<uint32_t *>(q + 64);
+        d_len = reinterpret_cast<unsigned long long *>(q + 128);
+        q += 256;
+        for (auto &f : fr) {
+            unsigned long long *u = reinterpret_cast<unsigned long long *>(q);
+            f.boff = u; u += R + 1;
+            f.seg_off = u; u += 2 * R + 2;
+            f.seg_len = u; u += 2 * R + 2;
+            f.start = u; u += 1;
+            uint32_t *w = reinterpret_cast<uint32_t *>(u);
+            f.kind = w; w += R;
+            f.size = w; w += R;
+            f.only = w; w += R;
+            f.hist = w; w += 256 * R;
+            f.enc_off = w; w += R * nsub;
+            f.crc = w; w += 2 * R + 2;
+            f.bwt = reinterpret_cast<int *>(w); w += R;
+            f.tcrc = w; w += 2;
+            q += per;
+        }
+        return hipSuccess;
+    }
+    ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
+
+    // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes)
+    CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
+    {
+        (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
+        const CtEncFrame &f = fr[P.parity];
+        const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
+        ContainerHooks hk;
+        hk.status = status;
+        hk.pack_only = f.only;
+        hk.before_offsets = [&](hipStream_t s2) { return ct_enc_kind(s2, f, nb, blk_len, state); };
+        hk.after_pack = [&](hipStream_t s2) { return ct_enc_after_pack(s2, f, d_in, nb, blk_len, out, cap, state); };
+        return plan_compress_hooked(P.h, d_in, f.bwt, f.hist, f.enc_off, nsub, f.size, reinterpret_cast<unsigned int *>(out),
+                                    (size_t)(cap / 4), f.boff, f.start, blk_len, nb, hk);
+    }
+
+    // every frame of [d_in, + len) with the plan's n and rows, starting at input byte `done` of the whole stream
+    template <class PerFrame>
+    CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap, PerFrame per_frame)
+    {
+        unsigned long long pos = 0;
+        while (pos < len) {
+            const unsigned long long left = len - pos;
+            const uint32_t nb = left >= P.n ? (uint32_t)std::min<unsigned long long>(P.rows, left / P.n) : 1u;
+            const uint32_t bl = left >= P.n ? P.n : (uint32_t)left;
+            CUDPPResult r = frame(d_in + pos, nb, bl, out, cap);
+            if (r != CUDPP_SUCCESS) return r;
+            r = per_frame((unsigned long long)nb * bl);
+            if (r != CUDPP_SUCCESS) return r;
+            pos += (unsigned long long)nb * bl;
+        }
+        return CUDPP_SUCCESS;
+    }
+};
+
+// -------------------------------------------------------------------------------------------------------------------------
+// decoder
+// -------------------------------------------------------------------------------------------------------------------------
+struct Decoder {
+    Plan P;
+    void *mem = nullptr;
+    size_t cap_nb = 0;
+    CtDecFrame f = {};
+    CtDecState *state = nullptr;
+    unsigned long long *h_verdict = nullptr;                  // pinned
+
+    ~Decoder()
+    {
+        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); }
+        if (state) { (void)hipStreamSynchronize(P.st); (void)hipFree(state); }
+        if (h_verdict) (void)hipHostFree(h_verdict);
+    }
+    hipError_t reserve(uint32_t nb)
+    {
+        if (nb <= cap_nb && mem) return hipSuccess;
+        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); mem = nullptr; }
+        if (h_verdict) { (void)hipHostFree(h_verdict); h_verdict = nullptr; }
+        const size_t n2 = nb + 2, vw = 2 + (nb + 1) / 2;
+        hipError_t e = hipMalloc(&mem, 8 * (2 * n2) + 8 * vw + 4 * n2);
+        if (e != hipSuccess) { mem = nullptr; return e; }
+        e = hipHostMalloc((void **)&h_verdict, 8 * vw, hipHostMallocDefault);
+        if (e != hipSuccess) { h_verdict = nullptr; return e; }
+        uint8_t *q = static_cast<uint8_t *>(mem);
+        f.seg_off = reinterpret_cast<unsigned long long *>(q); q += 8 * n2;
+        f.seg_len = reinterpret_cast<unsigned long long *>(q); q += 8 * n2;
+        f.verdict = reinterpret_cast<unsigned long long *>(q); q += 8 * vw;
+        f.crc = reinterpret_cast<uint32_t *>(q);
+        cap_nb = nb;
+        return hipSuccess;
+    }
+    hipError_t begin()
+    {
+        hipError_t e = hipMalloc((void **)&state, sizeof(CtDecState));
+        if (e != hipSuccess) { state = nullptr; return e; }
+        e = hipMemsetAsync(state, 0, sizeof(CtDecState), P.st);
+        if (e == hipSuccess) e = hipMemsetAsync(&state->err, 0xFF, 8, P.st);
+        return e;
+    }
+
+    // a frame in device memory whose header (nb, blk_len, payload words) the host has range-checked; decoded to out
+    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *out, uint32_t fi)
+    {
+        CT_TRY(reserve(nb));
+        CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw));
+        CT_TRY(hipMemcpyAsync(h_verdict, f.verdict, 8 * (2 + (nb + 1) / 2), hipMemcpyDeviceToHost, P.st));
+        CT_TRY(hipStreamSynchronize(P.st));
+        if (h_verdict[0]) return fail(P.h, CT_FRAME_TABLE, fi);
+        if (h_verdict[1] != ~0ull) return fail(P.h, h_verdict[1] >> 32, fi, h_verdict[1] & 0xFFFFFFFFu);
+        const uint32_t *kind = reinterpret_cast<const uint32_t *>(h_verdict + 2);
+        CT_TRY(ct_dec_raw(P.st, f, fr, nb, blk_len, out));
+        const CtTables T = ct_tables(nb, blk_len);
+        const uint32_t *W = reinterpret_cast<const uint32_t *>(fr + CT_FRAME_HDR);
+        const unsigned int *pay = reinterpret_cast<const unsigned int *>(fr + CT_FRAME_HDR + 4 * T.words);
+        for (uint32_t a = 0; a < nb;) {
+            if (kind[a] != CT_KIND_HUFF) { a++; continue; }
+            uint32_t b = a;
+            while (b < nb && kind[b] == CT_KIND_HUFF && b - a < P.rows) b++;
+            const CUDPPResult r = glcDecompressBatchCompact(
+                P.h, reinterpret_cast<const int *>(W + T.bwt) + a, W + T.hist + 256ull * a, W + T.enc_off + (size_t)T.nsub * a,
+                T.nsub, pay, pw, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, out + (size_t)a * blk_len,
+                blk_len, b - a);
+            if (r != CUDPP_SUCCESS) return r;
+            a = b;
+        }
+        plan_join(P.h);
+        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state));
+        return CUDPP_SUCCESS;
+    }
+
+    // after the last frame: the decoded-bytes verdict and the whole output's CRC against the trailer's
+    CUDPPResult end(uint32_t trailer_crc)
+    {
+        CtDecState s;
+        CT_TRY(hipMemcpyAsync(&s, state, sizeof(s), hipMemcpyDeviceToHost, P.st));
+        CT_TRY(hipStreamSynchronize(P.st));
+        if (s.err != ~0ull) return fail(P.h, CT_DECODED_CRC, (s.err - 1) >> 32, (s.err - 1) & 0xFFFFFFFFu);
+        if (s.crc_all != trailer_crc) return fail(P.h, CT_DECODED_CRC);
+        return CUDPP_SUCCESS;
+    }
+};
+
+// the checks on a stream header; returns block_len (0 = refused)
+uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total)
+{
+    if (h[0] != CT_MAGIC_STREAM || h[1] != CT_VERSION || h[3] != 0 || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
+    if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return 0;
+    *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
+    return h[2];
+}
+
+// the host's range checks on a frame header; 0 = refused
+bool check_frame_header(const uint32_t h[8], uint32_t block_len, unsigned long long left, unsigned long long *pw)
+{
+    const uint32_t nb = h[1], bl = h[2];
+    *pw = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
+    if (h[0] != CT_MAGIC_FRAME || h[3] != 0 || h[7] != 0 || nb == 0 || bl == 0 || bl > block_len) return false;
+    if ((nb > 1 && bl != block_len) || (unsigned long long)nb * bl > left) return false;
+    return *pw <= (unsigned long long)nb * ct_raw_words(bl);
+}
+
+bool check_trailer(const uint32_t t[4], uint32_t frames)
+{
+    return t[0] == CT_MAGIC_END && t[1] == frames && t[3] == crc32_host(t, 12);
+}
+
+// -------------------------------------------------------------------------------------------------------------------------
+// streamed forms: a source of input bytes and a sink of output bytes (host buffers or files), one frame at a time
+// -------------------------------------------------------------------------------------------------------------------------
+struct Source {
+    virtual ~Source() {}
+    virtual bool read(void *dst, size_t n) = 0;                  // exactly n bytes or false
+};
+struct Sink {
+    virtual ~Sink() {}
+    virtual bool write(const void *src, size_t n) = 0;           // false: no room (capacity) or an I/O error
+};
+struct MemSource : Source {
+    const uint8_t *p; unsigned long long left;
+    MemSource(const void *q, unsigned long long n) : p(static_cast<const uint8_t *>(q)), left(n) {}
+    bool read(void *dst, size_t n) override { if (n > left) return false; memcpy(dst, p, n); p += n; left -= n; return true; }
+};
+struct MemSink : Sink {
+    uint8_t *p; unsigned long long cap, used = 0;
+    MemSink(void *q, unsigned long long c) : p(static_cast<uint8_t *>(q)), cap(c) {}
+    bool write(const void *src, size_t n) override { if (n > cap - used) return false; memcpy(p + used, src, n); used += n; return true; }
+};
+struct FileSource : Source {
+    FILE *f;
+    explicit FileSource(FILE *g) : f(g) {}
+    bool read(void *dst, size_t n) override { return fread(dst, 1, n, f) == n; }
+};
+struct FileSink : Sink {
+    FILE *f;
+    explicit FileSink(FILE *g) : f(g) {}
+    bool write(const void *src, size_t n) override { return fwrite(src, 1, n, f) == n; }
+};
+
+struct Pinned {
+    void *p = nullptr; size_t n = 0;
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    hipError_t reserve(size_t m)
+    {
+        if (m <= n) return hipSuccess;
+        if (p) (void)hipHostFree(p);
+        p = nullptr; n = 0;
+        hipError_t e = hipHostMalloc(&p, m, hipHostMallocDefault);
+        if (e == hipSuccess) n = m;
+        return e;
+    }
+};
+struct DevBuf {
+    void *p = nullptr; size_t n = 0;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t reserve(size_t m)
+    {
+        if (m <= n) return hipSuccess;
+        if (p) (void)hipFree(p);
+        p = nullptr; n = 0;
+        hipError_t e = hipMalloc(&p, m);
+        if (e == hipSuccess) n = m;
+        return e;
+    }
+};
+
+// Input staging is double-buffered: the copy of frame i + 1 into pinned memory and onto the device runs while frame i encodes;
+// a frame's container bytes come back through pinned memory once the device cursor says how many there are.
+CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long len, Sink &out, unsigned long long *outLen)
+{
+    Encoder E;
+    if (!E.P.ok(plan)) return CUDPP_ERROR_INVALID_PLAN;
+    CT_TRY(E.init());
+    const unsigned long long fmax = (unsigned long long)E.P.n * E.P.rows;
+    Pinned hin[2], hout;
+    DevBuf din[2], dout;
+    const size_t inb = (size_t)std::min(fmax, std::max(len, 1ull));
+    for (int i = 0; i < 2; i++) { CT_TRY(hin[i].reserve(inb)); CT_TRY(din[i].reserve(inb)); }
+    const unsigned long long ocap = frame_bound(E.P.rows, E.P.n) + frame_bound(1, E.P.n) + CT_TRAILER;   // (a last chunk: blocks + tail)
+    CT_TRY(dout.reserve(ocap));
+    CT_TRY(hout.reserve(ocap));
+    uint32_t hdr[8];
+    make_header(hdr, E.P.n, len);
+    if (!out.write(hdr, CT_HDR)) return fail(plan, CT_CAPACITY);
+    unsigned long long total = CT_HDR;
+    hipStream_t cs = nullptr;
+    CT_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{cs};
+    hipEvent_t copied[2] = {nullptr, nullptr}, used[2] = {nullptr, nullptr};
+    struct EvGuard { hipEvent_t *e; int n; ~EvGuard() { for (int i = 0; i < n; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } eg1{copied, 2}, eg2{used, 2};
+    for (int i = 0; i < 2; i++) {
+        CT_TRY(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
+        CT_TRY(hipEventCreateWithFlags(&used[i], hipEventDisableTiming));
+    }
+    // chunk i: input bytes [i * fmax, ...) -- a frame of `rows` blocks, or the last blocks and the tail
+    const unsigned long long nchunk = (len + fmax - 1) / fmax;
+    auto stage = [&](unsigned long long i) -> CUDPPResult {
+        const int k = (int)(i & 1);
+        const size_t m = (size_t)std::min(fmax, len - i * fmax);
+        CT_TRY(hipEventSynchronize(used[k]));                 // (an unrecorded event is complete)
+        if (!src.read(hin[k].p, m)) return fail(plan, CT_TRUNCATED);
+        CT_TRY(hipMemcpyAsync(din[k].p, hin[k].p, m, hipMemcpyHostToDevice, cs));
+        CT_TRY(hipEventRecord(copied[k], cs));
+        return CUDPP_SUCCESS;
+    };
+    CT_TRY(ct_enc_header(E.P.st, static_cast<uint8_t *>(dout.p), 0, hdr, E.state));   // (cap 0: state only)
+    if (nchunk) { CUDPPResult r = stage(0); if (r != CUDPP_SUCCESS) return r; }
+    for (unsigned long long i = 0; i < nchunk; i++) {
+        const int k = (int)(i & 1);
+        const unsigned long long m = std::min(fmax, len - i * fmax);
+        CT_TRY(hipStreamWaitEvent(E.P.st, copied[k], 0));
+        CT_TRY(hipMemsetAsync(&E.state->cursor, 0, 8, E.P.st));
+        CUDPPResult r = E.frames(static_cast<const uint8_t *>(din[k].p), m, static_cast<uint8_t *>(dout.p), ocap,
+                                 [](unsigned long long) { return CUDPP_SUCCESS; });
+        if (r != CUDPP_SUCCESS) return r;
+        plan_join(plan);
+        CT_TRY(hipEventRecord(used[k], E.P.st));
+        if (i + 1 < nchunk) { r = stage(i + 1); if (r != CUDPP_SUCCESS) return r; }
+        unsigned long long fb = 0;
+        CT_TRY(hipMemcpyAsync(&fb, &E.state->cursor, 8, hipMemcpyDeviceToHost, E.P.st));
+        CT_TRY(hipStreamSynchronize(E.P.st));
+        if (fb > ocap) return fail(plan, CT_CAPACITY);
+        CT_TRY(hipMemcpy(hout.p, dout.p, fb, hipMemcpyDeviceToHost));
+        if (!out.write(hout.p, fb)) return fail(plan, CT_CAPACITY);
+        total += fb;
+    }
+    CT_TRY(hipMemsetAsync(&E.state->cursor, 0, 8, E.P.st));
+    CT_TRY(ct_enc_trailer(E.P.st, static_cast<uint8_t *>(dout.p), ocap, E.state, E.d_len));
+    CT_TRY(hipMemcpyAsync(hout.p, dout.p, CT_TRAILER, hipMemcpyDeviceToHost, E.P.st));
+    CT_TRY(hipStreamSynchronize(E.P.st));
+    if (!out.write(hout.p, CT_TRAILER)) return fail(plan, CT_CAPACITY);
+    total += CT_TRAILER;
+    if (outLen) *outLen = total;
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult decompress_stream(CUDPPHandle plan, Source &src, unsigned long long len, Sink &out, unsigned long long cap,
+                              unsigned long long *outLen)
+{
+    Decoder D;
+    if (!D.P.ok(plan)) return CUDPP_ERROR_INVALID_PLAN;
+    uint32_t hdr[8];
+    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
+    if (!src.read(hdr, CT_HDR)) return fail(plan, CT_TRUNCATED);
+    unsigned long long total = 0;
+    const uint32_t block_len = check_stream_header(hdr, &total);
+    if (!block_len) return fail(plan, CT_STREAM_HEADER);
+    if (total > cap) return fail(plan, CT_CAPACITY);
+    CT_TRY(D.begin());
+    Pinned hf, ho;
+    DevBuf df, dob;
+    unsigned long long pos = CT_HDR, done = 0;
+    uint32_t fi = 0;
+    while (done < total) {
+        uint32_t fh[8];
+        if (pos + CT_FRAME_HDR + CT_TRAILER > len || !src.read(fh, CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
+        unsigned long long pw = 0;
+        if (!check_frame_header(fh, block_len, total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
+        const uint32_t nb = fh[1], bl = fh[2];
+        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+        const unsigned long long fb = frame_bytes(nb, bl, pw);
+        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+        CT_TRY(hf.reserve(fb)); CT_TRY(df.reserve(fb));
+        const size_t ob = (size_t)nb * bl;
+        CT_TRY(ho.reserve(ob)); CT_TRY(dob.reserve(ob));
+        memcpy(hf.p, fh, CT_FRAME_HDR);
+        if (!src.read(static_cast<uint8_t *>(hf.p) + CT_FRAME_HDR, fb - CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
+        CT_TRY(hipMemcpyAsync(df.p, hf.p, fb, hipMemcpyHostToDevice, D.P.st));
+        CUDPPResult r = D.frame(static_cast<const uint8_t *>(df.p), nb, bl, pw, static_cast<uint8_t *>(dob.p), fi);
+        if (r != CUDPP_SUCCESS) return r;
+        CT_TRY(hipMemcpyAsync(ho.p, dob.p, ob, hipMemcpyDeviceToHost, D.P.st));
+        CT_TRY(hipStreamSynchronize(D.P.st));
+        if (!out.write(ho.p, ob)) return fail(plan, CT_CAPACITY);
+        pos += fb; done += ob; fi++;
+    }
+    uint32_t tr[4];
+    if (pos + CT_TRAILER > len || !src.read(tr, CT_TRAILER)) return fail(plan, CT_TRUNCATED, fi);
+    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
+    CUDPPResult r = D.end(tr[2]);
+    if (r != CUDPP_SUCCESS) return r;
+    if (outLen) *outLen = total;
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
+} // namespace
+
+extern "C" {
+
+unsigned long long glcContainerBound(unsigned long long len, size_t blockLen)
+{
+    if (blockLen == 0 || blockLen > MAX_BLOCK_ELEMS) return 0;
+    const unsigned long long frames = (len + blockLen - 1) / blockLen;
+    return CT_HDR + CT_TRAILER + len + frames * (CT_FRAME_HDR + 4 * ct_tables(1, (uint32_t)blockLen).words + 7);
+}
+
+CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, void *d_out,
+                                       unsigned long long cap, unsigned long long *d_outLen)
+{
+    Encoder E;
+    if (!E.P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if ((len && !d_in) || !d_out || !d_outLen || (reinterpret_cast<uintptr_t>(d_out) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(E.init());
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+    uint32_t hdr[8];
+    make_header(hdr, E.P.n, len);
+    CT_TRY(ct_enc_header(E.P.st, out, cap, hdr, E.state));
+    CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap, [](unsigned long long) { return CUDPP_SUCCESS; });
+    if (r != CUDPP_SUCCESS) return r;
+    plan_join(plan);
+    CT_TRY(ct_enc_trailer(E.P.st, out, cap, E.state, d_outLen));
+    unsigned long long total = 0;
+    CT_TRY(hipMemcpyAsync(&total, d_outLen, 8, hipMemcpyDeviceToHost, E.P.st));
+    CT_TRY(hipStreamSynchronize(E.P.st));
+    if (total > cap) return fail(plan, CT_CAPACITY);
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, void *d_out,
+                                         unsigned long long cap, unsigned long long *d_outLen)
+{
+    Decoder D;
+    if (!D.P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (!d_in || !d_outLen || (reinterpret_cast<uintptr_t>(d_in) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const uint8_t *in = static_cast<const uint8_t *>(d_in);
+    uint8_t *out = static_cast<uint8_t *>(d_out);
+    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
+    uint32_t hdr[8];
+    CT_TRY(hipMemcpyAsync(hdr, in, CT_HDR, hipMemcpyDeviceToHost, D.P.st));
+    CT_TRY(hipStreamSynchronize(D.P.st));
+    unsigned long long total = 0;
+    const uint32_t block_len = check_stream_header(hdr, &total);
+    if (!block_len) return fail(plan, CT_STREAM_HEADER);
+    if (total > cap || (total && !d_out)) return fail(plan, CT_CAPACITY);
+    CT_TRY(D.begin());
+    unsigned long long pos = CT_HDR, done = 0;
+    uint32_t fi = 0;
+    while (done < total) {
+        if (pos + CT_FRAME_HDR + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+        uint32_t fh[8];
+        CT_TRY(hipMemcpyAsync(fh, in + pos, CT_FRAME_HDR, hipMemcpyDeviceToHost, D.P.st));
+        CT_TRY(hipStreamSynchronize(D.P.st));
+        unsigned long long pw = 0;
+        if (!check_frame_header(fh, block_len, total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
+        const uint32_t nb = fh[1], bl = fh[2];
+        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+        const unsigned long long fb = frame_bytes(nb, bl, pw);
+        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+        CUDPPResult r = D.frame(in + pos, nb, bl, pw, out + done, fi);
+        if (r != CUDPP_SUCCESS) return r;
+        pos += fb; done += (unsigned long long)nb * bl; fi++;
+    }
+    uint32_t tr[4];
+    CT_TRY(hipMemcpyAsync(tr, in + pos, CT_TRAILER, hipMemcpyDeviceToHost, D.P.st));
+    CT_TRY(hipStreamSynchronize(D.P.st));
+    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
+    CUDPPResult r = D.end(tr[2]);
+    if (r != CUDPP_SUCCESS) return r;
+    CT_TRY(ct_put_u64(D.P.st, d_outLen, total));
+    CT_TRY(hipStreamSynchronize(D.P.st));
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerCompress(CUDPPHandle plan, const void *in, unsigned long long len, void *out, unsigned long long cap,
+                                 unsigned long long *outLen)
+{
+    if ((len && !in) || !out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    MemSource s(in, len);
+    MemSink k(out, cap);
+    return compress_stream(plan, s, len, k, outLen);
+}
+
+CUDPPResult glcContainerDecompress(CUDPPHandle plan, const void *in, unsigned long long len, void *out, unsigned long long cap,
+                                   unsigned long long *outLen)
+{
+    if (!in || (cap && !out)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    MemSource s(in, len);
+    MemSink k(out, cap);
+    return decompress_stream(plan, s, len, k, cap, outLen);
+}
+
+CUDPPResult glcContainerCompressFile(CUDPPHandle plan, const char *inPath, const char *outPath)
+{
+    if (!inPath || !outPath) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    struct stat sb;
+    if (stat(inPath, &sb) != 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fi = fopen(inPath, "rb");
+    if (!fi) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fo = fopen(outPath, "wb");
+    if (!fo) { fclose(fi); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+    FileSource s(fi);
+    FileSink k(fo);
+    CUDPPResult r = compress_stream(plan, s, (unsigned long long)sb.st_size, k, nullptr);
+    fclose(fi);
+    if (fclose(fo) != 0 && r == CUDPP_SUCCESS) r = CUDPP_ERROR_UNKNOWN;
+    return r;
+}
+
+CUDPPResult glcContainerDecompressFile(CUDPPHandle plan, const char *inPath, const char *outPath)
+{
+    if (!inPath || !outPath) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    struct stat sb;
+    if (stat(inPath, &sb) != 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fi = fopen(inPath, "rb");
+    if (!fi) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fo = fopen(outPath, "wb");
+    if (!fo) { fclose(fi); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+    FileSource s(fi);
+    FileSink k(fo);
+    CUDPPResult r = decompress_stream(plan, s, (unsigned long long)sb.st_size, k, ~0ull, nullptr);
+    fclose(fi);
+    if (fclose(fo) != 0 && r == CUDPP_SUCCESS) r = CUDPP_ERROR_UNKNOWN;
+    return r;
+}
+
+CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                             size_t count, unsigned int *d_crc, void *stream)
+{
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_offsets || !d_lengths || !d_crc || count > 0xFFFFFFFFull) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_res(crc32_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_base), d_offsets,
+                                  d_lengths, (uint32_t)count, d_crc));
+}
+
+CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3])
+{
+    if (plan == 0 || plan == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    std::lock_guard<std::mutex> g(g_err_mu);
+    const LastError e = g_err.count(plan) ? g_err[plan] : LastError();
+    for (int i = 0; i < 3; i++) out[i] = e.v[i];
+    return CUDPP_SUCCESS;
+}
+
+} // extern "C"

@@ -1,0 +1,163 @@
+// container_internal.h -- shared by container.hip (kernels) and container_api.cpp (host side of include/glc_container.h):
+// the CRC-32 algebra, the BWT container's layout and the plan hooks cudpp_api.cpp exports to it.
+#pragma once
+#include "../../include/cudpp.h"
+#include "glc_internal.h"
+
+#include <functional>
+
+namespace glc {
+
+// ---------------------------------------------------------------------------
+// CRC-32/IEEE, reflected (zlib.crc32).  A register r is a polynomial with x^0 in bit 31; "raw" CRCs below start from 0
+// and are not complemented, so they are linear: raw(A || B) = shift(raw(A), |B|) ^ raw(B), where shift(r, k) = r * x^(8k)
+// mod P is what feeding k zero bytes does.  The standard CRC is raw(M) ^ shift(~0, |M|) ^ ~0, and two standard CRCs
+// combine as crc(A || B) = shift(crc(A), |B|) ^ crc(B) (zlib's crc32_combine).
+// ---------------------------------------------------------------------------
+constexpr uint32_t CRC_POLY = 0xEDB88320u;
+
+__host__ __device__ constexpr uint32_t crc_multmodp(uint32_t a, uint32_t b)
+{   // a * b mod P, branch-free: 32 steps whatever a is
+    uint32_t p = 0;
+    for (int i = 0; i < 32; i++) {
+        p ^= (0u - ((a >> (31 - i)) & 1u)) & b;
+        b = (b >> 1) ^ ((0u - (b & 1u)) & CRC_POLY);
+    }
+    return p;
+}
+
+struct CrcX2n { uint32_t v[32]; };                             // x^(2^k) mod P
+constexpr CrcX2n crc_make_x2n()
+{
+    CrcX2n t{};
+    uint32_t p = 1u << 30;                                     // x^1
+    for (int k = 0; k < 32; k++) { t.v[k] = p; p = crc_multmodp(p, p); }
+    return t;
+}
+
+// x^(8 n) mod P for a byte count n (zlib's x2nmodp(n, 3)); X2N is the table above, wherever it lives
+template <class Tab>
+__host__ __device__ constexpr uint32_t crc_x8n(unsigned long long n, const Tab &X2N)
+{
+    uint32_t p = 1u << 31;
+    unsigned k = 3;
+    while (n) {
+        if (n & 1) p = crc_multmodp(X2N.v[k & 31], p);
+        n >>= 1;
+        k++;
+    }
+    return p;
+}
+
+// slice-by-16 tables of the raw register (T[0] = the bytewise table) and the four byte tables of "shift by 1024 bytes",
+// one 64-lane row of 16-byte granules (k_crc_rows)
+constexpr uint32_t CRC_ROW = 1024, CRC_TILE_ROWS = 16;
+struct CrcTables { uint32_t t[16][256]; uint32_t row[4][256]; };
+constexpr CrcTables crc_make_tables()
+{
+    CrcTables T{};
+    for (uint32_t i = 0; i < 256; i++) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; k++) c = (c >> 1) ^ ((0u - (c & 1u)) & CRC_POLY);
+        T.t[0][i] = c;
+    }
+    for (int j = 1; j < 16; j++)
+        for (uint32_t i = 0; i < 256; i++) T.t[j][i] = (T.t[j - 1][i] >> 8) ^ T.t[0][T.t[j - 1][i] & 0xFF];
+    const CrcX2n X = crc_make_x2n();
+    const uint32_t sh = crc_x8n(CRC_ROW, X);
+    for (int k = 0; k < 4; k++)
+        for (uint32_t i = 0; i < 256; i++) T.row[k][i] = crc_multmodp(sh, i << (8 * k));
+    return T;
+}
+
+uint32_t crc32_host(const void *data, size_t len, uint32_t crc = 0);     // standard CRC, continuing from `crc`
+
+// CRC of `count` device segments [base + off[i], + len[i]) into d_crc[i].  base may be null with absolute addresses in off.
+hipError_t crc32_segments(hipStream_t st, const uint8_t *base, const unsigned long long *d_off,
+                          const unsigned long long *d_len, uint32_t count, uint32_t *d_crc);
+
+// ---------------------------------------------------------------------------
+// layout (little-endian; every section 8-byte aligned)
+// ---------------------------------------------------------------------------
+constexpr uint32_t CT_MAGIC_STREAM = 0x42434C47u;   // "GLCB"
+constexpr uint32_t CT_MAGIC_FRAME  = 0x46434C47u;   // "GLCF"
+constexpr uint32_t CT_MAGIC_END    = 0x45434C47u;   // "GLCE"
+constexpr uint32_t CT_VERSION = 1;
+constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
+constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
+
+// failure classes of glcContainerLastError (out[0])
+enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
+                         CT_TRUNCATED = 5, CT_CAPACITY = 6 };
+
+struct CtTables {                                    // word offsets of the sections of a frame's tables (from the tables' start)
+    uint32_t nb, nsub;
+    unsigned long long kind, bwt, crc_raw, crc_rec, hist, enc_off, pay_off, words;
+};
+__host__ __device__ inline CtTables ct_tables(uint32_t nb, uint32_t blk_len)
+{
+    CtTables t{};
+    t.nb = nb;
+    t.nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
+    const unsigned long long a = nb + (nb & 1u), e = (unsigned long long)nb * t.nsub + (((unsigned long long)nb * t.nsub) & 1u);
+    t.kind = 0; t.bwt = a; t.crc_raw = 2 * a; t.crc_rec = 3 * a; t.hist = 4 * a;
+    t.enc_off = t.hist + 256ull * nb; t.pay_off = t.enc_off + e; t.words = t.pay_off + 2ull * (nb + 1);
+    return t;
+}
+__host__ __device__ inline uint32_t ct_raw_words(uint32_t blk_len) { return (blk_len + 3) / 4; }
+
+// ---------------------------------------------------------------------------
+// plan hooks (cudpp_api.cpp): the container path drives a COMPRESS plan through its internals
+// ---------------------------------------------------------------------------
+struct ContainerHooks {
+    uint32_t *status = nullptr;                              // replaces the plan's status word for this call's encode
+    const uint32_t *pack_only = nullptr;                     // blocks the packer writes (the Huffman ones)
+    std::function<hipError_t(hipStream_t)> before_offsets;   // after the last k_huff_build, before the payload offsets
+    std::function<hipError_t(hipStream_t)> after_pack;       // behind the packer, on the same stream
+};
+// glcCompressBatchCompact with the hooks above
+CUDPPResult plan_compress_hooked(CUDPPHandle plan, const unsigned char *d_in, int *d_bwtIndex, unsigned int *d_hist,
+                                 unsigned int *d_encodeOffset, size_t offsetStride, unsigned int *d_size,
+                                 unsigned int *d_compact, size_t capacityWords, unsigned long long *d_blockOffsets,
+                                 const unsigned long long *d_startOffset, size_t numElements, size_t numBlocks,
+                                 ContainerHooks &hk);
+// 1 = a COMPRESS plan; n, rows, its stream, and the parity of its next compress call (which half of double-buffered scratch
+// that call may reuse once the plan's own ordering lets it)
+bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
+void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
+
+// ---------------------------------------------------------------------------
+// kernels of container.hip
+// ---------------------------------------------------------------------------
+struct CtEncState {                                        // device: the running state of one container encode
+    unsigned long long cursor;                             // bytes written (or that would have been) so far
+    uint32_t crc_all, frames;
+    uint32_t frame_acc, pad;                               // the frame's CRC, summed from its blocks' terms
+};
+struct CtEncFrame {                                        // device scratch of one frame (double-buffered by call parity)
+    uint32_t *kind, *size, *only, *hist, *enc_off, *crc;   // crc: [2 nb] raw bytes, then records
+    int *bwt;
+    unsigned long long *boff, *seg_off, *seg_len, *start;  // boff: nb + 1 absolute word offsets; segs: 2 nb + 2
+    uint32_t *tcrc;                                        // [2]
+};
+hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
+hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, uint32_t nb, uint32_t blk_len,
+                             uint8_t *out, unsigned long long cap, CtEncState *state);
+hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, CtEncState *state, unsigned long long *d_len);
+
+struct CtDecFrame {                                        // device scratch of one frame's checks
+    unsigned long long *seg_off, *seg_len;                 // [nb + 2]
+    uint32_t *crc;                                         // [nb + 2]
+    unsigned long long *verdict;                           // [2 + ceil(nb / 2)]: table verdict, block verdict, kinds (u32)
+};
+struct CtDecState { uint32_t crc_all, frame_acc; unsigned long long err; };   // err: (frame << 32 | block) + 1 of the first decoded-CRC miss
+hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
+                         unsigned long long payload_words);
+hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out);
+hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
+                        const uint8_t *out, uint32_t frame_index, CtDecState *state);
+
+hipError_t ct_put_u64(hipStream_t st, unsigned long long *p, unsigned long long v);
+
+} // namespace glc

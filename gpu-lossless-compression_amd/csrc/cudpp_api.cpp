@@ -10,6 +10,7 @@
 // (compress_app.cu:257,263; sa_app.cu:73-100), HIP failures are returned as
 // CUDPP_ERROR_UNKNOWN instead of exit() (cuda_util.h:13-21).
 #include "../../include/cudpp.h"
+#include "container_internal.h"
 #include "glc_internal.h"
 
 #include <new>
@@ -261,8 +262,11 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
                                   unsigned int *d_compressedSize, unsigned int *d_compressed,
                                   size_t compressedStrideWords, size_t numElements, size_t numBlocks,
                                   unsigned long long *d_blockOffsets, const unsigned long long *d_startOffset,
-                                  size_t capacityWords)
+                                  size_t capacityWords, ContainerHooks *hk = nullptr)
 {
+    // hk (the container path, compact layout only): a status word of its own -- a block whose sub-block overflows becomes a raw
+    // record there instead of failing the call --, its kernels before the payload offsets and behind the packer, and the
+    // packer's block mask
     const bool compact = d_blockOffsets != nullptr;
     CompressPlan *p = plan_from<CompressPlan>(planHandle);
     if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
@@ -276,6 +280,7 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
     hipStream_t st = p->stream;
     StageTimer tm(p);
     hipError_t e = hipSuccess;
+    uint32_t *const status = hk ? hk->status : p->d_status;
     uint8_t *bwt = p->d_bwt;
     const uint32_t k = p->calls++ & 1u;
     hipStream_t s2 = st;                                       // stream of the MTF + Huffman stages
@@ -306,7 +311,7 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
         if (p->timing) (void)hipEventRecord(p->ev[2], s2);
         // (compact layout: a block has no slot of its own to overflow -- the array's capacity is checked with the offsets)
         if (e == hipSuccess) e = huff_build(s2, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                                            compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, p->d_status,
+                                            compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status,
                                             redo_flag, only);
         if (e == hipSuccess && !compact) e = huff_pack(s2, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride,
                                                        d_compressed, compressedStrideWords, only);
@@ -324,7 +329,7 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
         p->sa.stage_partial = [&](hipStream_t aux, const uint32_t *only) -> hipError_t {
             hipError_t e2 = mtf_forward(aux, bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, p->huff.sub_hist, only, true);
             if (e2 == hipSuccess) e2 = huff_build(aux, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                                                  compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, p->d_status, nullptr, only);
+                                                  compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status, nullptr, only);
             if (e2 == hipSuccess && !compact) e2 = huff_pack(aux, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride, d_compressed,
                                                              compressedStrideWords, only);
             return e2;
@@ -339,9 +344,11 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
         after_sort(nullptr, p->sa.partial_used ? p->sa.ss_mask[1] : (speculate && tiers ? p->sa.fs_redo[k] : nullptr), true);   // (the blocks of the other tiers: text-like)
     }
     if (e == hipSuccess && compact) {
-        e = huff_block_offsets(s2, d_compressedSize, nb, d_blockOffsets, d_startOffset, capacityWords, p->d_status);
+        if (hk && hk->before_offsets) e = hk->before_offsets(s2);
+        if (e == hipSuccess) e = huff_block_offsets(s2, d_compressedSize, nb, d_blockOffsets, d_startOffset, capacityWords, status);
         if (e == hipSuccess) e = huff_pack(s2, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride, d_compressed, 0,
-                                           nullptr, d_blockOffsets, capacityWords);
+                                           hk ? hk->pack_only : nullptr, d_blockOffsets, capacityWords);
+        if (e == hipSuccess && hk && hk->after_pack) e = hk->after_pack(s2);
         if (p->timing) (void)hipEventRecord(p->ev[3], s2);
     }
     tm.done();
@@ -788,3 +795,30 @@ CUDPPResult glcPlanLastTiming(CUDPPHandle planHandle, float *ms4)
 }
 
 } // extern "C"
+
+// internal: the container path (container_api.cpp) drives a plan through these
+namespace glc {
+CUDPPResult plan_compress_hooked(CUDPPHandle planHandle, const unsigned char *d_in, int *d_bwtIndex, unsigned int *d_hist,
+                                 unsigned int *d_encodeOffset, size_t offsetStride, unsigned int *d_size,
+                                 unsigned int *d_compact, size_t capacityWords, unsigned long long *d_blockOffsets,
+                                 const unsigned long long *d_startOffset, size_t numElements, size_t numBlocks,
+                                 ContainerHooks &hk)
+{
+    return compress_batch(planHandle, d_in, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_size, d_compact, 0, numElements,
+                          numBlocks, d_blockOffsets, d_startOffset, capacityWords, &hk);
+}
+
+bool plan_info(CUDPPHandle planHandle, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (!p || planHandle == CUDPP_INVALID_HANDLE || p->config.algorithm != CUDPP_COMPRESS || p->config.datatype != CUDPP_UCHAR)
+        return false;
+    if (n) *n = p->n;
+    if (rows) *rows = p->rows;
+    if (st) *st = p->stream;
+    if (next_parity) *next_parity = p->calls & 1u;
+    return true;
+}
+
+void plan_join(CUDPPHandle planHandle) { plan_from<CompressPlan>(planHandle)->join_side(); }
+} // namespace glc

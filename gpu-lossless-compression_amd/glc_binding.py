@@ -488,3 +488,128 @@ def hd_decode_device(d_units, lens, codes, nsym, stream=None):
     if not ok:
         raise HdError("glcHdDecodeDevice failed")
     return out[:nsym]
+
+
+# --------------------------------------------------------------------------------------------------------------------------
+# include/glc_container.h: the CRC-checked container of the BWT codec
+# --------------------------------------------------------------------------------------------------------------------------
+CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcContainerDecompressDevice", "glcContainerCompress",
+                     "glcContainerDecompress", "glcContainerCompressFile", "glcContainerDecompressFile", "glcCrc32Segments",
+                     "glcContainerLastError"]
+CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
+CONTAINER_HEADER_BYTES = 32
+
+
+def _ct():
+    L = lib()
+    if not getattr(L, "_ct_ready", False):
+        vp, sz, ull = C.c_void_p, C.c_size_t, C.c_ulonglong
+        ullp = C.POINTER(ull)
+        L.glcContainerBound.argtypes = [ull, sz]
+        L.glcContainerBound.restype = ull
+        for nm in ("glcContainerCompressDevice", "glcContainerDecompressDevice"):
+            getattr(L, nm).argtypes = [sz, vp, ull, vp, ull, vp]
+        for nm in ("glcContainerCompress", "glcContainerDecompress"):
+            getattr(L, nm).argtypes = [sz, vp, ull, vp, ull, ullp]
+        for nm in ("glcContainerCompressFile", "glcContainerDecompressFile"):
+            getattr(L, nm).argtypes = [sz, C.c_char_p, C.c_char_p]
+        L.glcCrc32Segments.argtypes = [vp, vp, vp, sz, vp, vp]
+        L.glcContainerLastError.argtypes = [sz, ullp]
+        for nm in CONTAINER_SYMBOLS[1:]:
+            getattr(L, nm).restype = C.c_int
+        L._ct_ready = True
+    return L
+
+
+def container_bound(length, block_len):
+    """worst-case container bytes for `length` input bytes in blocks of `block_len`"""
+    return int(_ct().glcContainerBound(int(length), int(block_len)))
+
+
+def container_compress(plan, d_in, cap=None):
+    """device uint8 tensor -> device uint8 tensor holding the container (a view of a buffer of `cap` bytes, default the bound)"""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    cap = container_bound(x.numel(), plan.n) if cap is None else int(cap)
+    out = torch.empty(max(cap, 8), dtype=torch.uint8, device=x.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=x.device)
+    _chk("glcContainerCompressDevice", _ct().glcContainerCompressDevice(plan.handle, x.data_ptr() if x.numel() else None,
+                                                                         x.numel(), out.data_ptr(), cap, d_len.data_ptr()))
+    return out[:int(d_len.item())]
+
+
+def container_total_len(header):
+    """the input length a container's stream header records (bytes 16..23)"""
+    import numpy as np
+    h = np.frombuffer(bytes(header[:CONTAINER_HEADER_BYTES]), dtype=np.uint8)
+    return int(h[16:24].view(np.uint64)[0])
+
+
+def container_decompress(plan, d_cont, cap=None):
+    """device container (uint8 tensor, 8-byte aligned) -> device uint8 tensor of the decoded bytes"""
+    import torch
+    c = d_cont.reshape(-1)
+    if cap is None:
+        cap = container_total_len(c[:CONTAINER_HEADER_BYTES].cpu().numpy().tobytes()) if c.numel() >= CONTAINER_HEADER_BYTES else 0
+    out = torch.empty(int(cap), dtype=torch.uint8, device=c.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=c.device)
+    _chk("glcContainerDecompressDevice", _ct().glcContainerDecompressDevice(
+        plan.handle, c.data_ptr(), c.numel(), out.data_ptr() if out.numel() else None, int(cap), d_len.data_ptr()))
+    return out[:int(d_len.item())]
+
+
+def container_compress_host(plan, data, cap=None):
+    """host bytes / uint8 array -> numpy uint8 container"""
+    import numpy as np
+    a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                             dtype=np.uint8)
+    cap = container_bound(a.size, plan.n) if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    n = C.c_ulonglong(0)
+    _chk("glcContainerCompress", _ct().glcContainerCompress(plan.handle, a.ctypes.data if a.size else None, a.size,
+                                                            out.ctypes.data, cap, C.byref(n)))
+    return out[:n.value]
+
+
+def container_decompress_host(plan, data, cap=None):
+    """host container -> numpy uint8 array of the decoded bytes"""
+    import numpy as np
+    a = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data,
+                             dtype=np.uint8)
+    if cap is None:
+        cap = container_total_len(a) if a.size >= CONTAINER_HEADER_BYTES else 0
+    out = np.zeros(max(int(cap), 1), dtype=np.uint8)
+    n = C.c_ulonglong(0)
+    _chk("glcContainerDecompress", _ct().glcContainerDecompress(plan.handle, a.ctypes.data if a.size else None, a.size,
+                                                                out.ctypes.data, int(cap), C.byref(n)))
+    return out[:n.value]
+
+
+def container_compress_file(plan, src, dst):
+    _chk("glcContainerCompressFile", _ct().glcContainerCompressFile(plan.handle, os.fsencode(src), os.fsencode(dst)))
+
+
+def container_decompress_file(plan, src, dst):
+    _chk("glcContainerDecompressFile", _ct().glcContainerDecompressFile(plan.handle, os.fsencode(src), os.fsencode(dst)))
+
+
+def crc32_segments(d_base, offsets, lengths, stream=None):
+    """CRC-32 (zlib.crc32) of segments [offsets[i], + lengths[i]) of the device uint8 tensor d_base; returns a list of ints"""
+    import torch
+    dev = d_base.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    out = torch.zeros(max(1, off.numel()), dtype=torch.int32, device=dev)
+    _chk("glcCrc32Segments", _ct().glcCrc32Segments(d_base.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(),
+                                                    out.data_ptr(), stream))
+    torch.cuda.synchronize(dev)
+    return [int(v) & 0xFFFFFFFF for v in out[:off.numel()].cpu().tolist()]
+
+
+def container_last_error(plan):
+    """(what, frame, block) of the plan's last container failure; frame / block -1 where the failure is not tied to one"""
+    a = (C.c_ulonglong * 3)()
+    _chk("glcContainerLastError", _ct().glcContainerLastError(plan.handle, a))
+    return tuple(-1 if v == (1 << 64) - 1 else int(v) for v in a)

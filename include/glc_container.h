@@ -1,0 +1,73 @@
+/*
+ * glc_container.h -- a CRC-checked, self-describing container around the BWT codec (cudppCompress path): any length in,
+ * one stream out, read back bit-exactly or refused.  Format: INTEGRATION.md section 4b.
+ *
+ * The input is cut into blocks of the plan's n bytes; up to `rows` of them make a frame, one batched encode; a ragged tail is
+ * a frame of one block.  A block whose Huffman record would not fit the format (a 4096-symbol sub-block needing more than 1536
+ * words) or would not save a quarter (4 * words >= block bytes) is stored raw.  Every block carries the CRC-32 of its bytes
+ * and of its record, every frame the CRC of its tables, the stream the CRC of the whole input (CRC-32/IEEE, = zlib.crc32).
+ *
+ * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
+ * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
+ * whose n is smaller than the container's blocks), CUDPP_ERROR_UNKNOWN (a container that fails a check, or a failed HIP
+ * call); glcContainerLastError says which check.
+ */
+#ifndef GLC_CONTAINER_H
+#define GLC_CONTAINER_H
+
+#include <stddef.h>
+
+#include "cudpp.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* what glcContainerLastError reports in out[0] */
+enum GlcContainerError
+{
+    GLC_CONTAINER_OK = 0,
+    GLC_CONTAINER_STREAM_HEADER = 1,    /* stream header or trailer (magic, version, CRC, frame count, stray bytes) */
+    GLC_CONTAINER_FRAME_TABLE = 2,      /* a frame header or its tables: table CRC or a field out of range */
+    GLC_CONTAINER_RECORD_CRC = 3,       /* a block's payload record */
+    GLC_CONTAINER_DECODED_CRC = 4,      /* the bytes a block decoded to, or the whole output against the trailer */
+    GLC_CONTAINER_TRUNCATED = 5,        /* the container ends inside a frame or before its trailer */
+    GLC_CONTAINER_CAPACITY = 6          /* the output does not fit `cap` */
+};
+
+/* Worst-case container size for `len` input bytes in blocks of `blockLen` (<= 1048576; 0 for a bad blockLen).  Depends
+ * on its arguments only; about len + 1.1 KB per block. */
+unsigned long long glcContainerBound(unsigned long long len, size_t blockLen);
+
+/* Device buffers.  d_out (and the container d_in of the decoder) must be 8-byte aligned.  *d_outLen is a DEVICE word that
+ * receives the container's (decoded) length; after a capacity failure of the encoder it holds the length that was needed.
+ * The decoder takes any COMPRESS plan whose n is at least the container's block length, whatever its rows. */
+CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, void *d_out,
+                                       unsigned long long cap, unsigned long long *d_outLen);
+CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, void *d_out,
+                                         unsigned long long cap, unsigned long long *d_outLen);
+
+/* Host buffers (any alignment), staged frame by frame through pinned memory; *outLen is a host word. */
+CUDPPResult glcContainerCompress(CUDPPHandle plan, const void *in, unsigned long long len, void *out,
+                                 unsigned long long cap, unsigned long long *outLen);
+CUDPPResult glcContainerDecompress(CUDPPHandle plan, const void *in, unsigned long long len, void *out,
+                                   unsigned long long cap, unsigned long long *outLen);
+
+/* Files, streamed: host and device memory stay proportional to one frame, not to the file. */
+CUDPPResult glcContainerCompressFile(CUDPPHandle plan, const char *inPath, const char *outPath);
+CUDPPResult glcContainerDecompressFile(CUDPPHandle plan, const char *inPath, const char *outPath);
+
+/* CRC-32/IEEE of `count` device segments [d_base + d_offsets[i], + d_lengths[i]) into d_crc[i], queued on `stream` (a
+ * hipStream_t; NULL = default).  Any length and byte alignment.  d_base may be NULL when the offsets are addresses. */
+CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                             size_t count, unsigned int *d_crc, void *stream);
+
+/* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
+ * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */
+CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* GLC_CONTAINER_H */

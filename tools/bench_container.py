@@ -1,0 +1,125 @@
+"""The BWT container against the codec it wraps, in one process and run (one JSON line on stdout):
+
+  crc        glcCrc32Segments over one device buffer of --gib GiB, against glcProbeStreamRead on the same buffer
+  encode     glcContainerCompressDevice of configs[1] (Philox Zipf(1.0) bytes, 1 MiB blocks, --rows-row plan, as bench.py
+             generates it), against glcCompressBatchCompact batches chained into one array on the same plan
+  decode     glcContainerDecompressDevice of that container, against glcDecompressBatchCompact of the compact array
+  size       container bytes against the sum of the compact sizes
+
+python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+MiB = 1 << 20
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=4.0)
+    ap.add_argument("--rows", type=int, default=2048)
+    ap.add_argument("--iters", type=int, default=2)
+    ap.add_argument("--pipelining", type=int, default=1)
+    args = ap.parse_args()
+    import importlib.util
+    import numpy as np
+    import torch
+
+    spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
+    glc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(glc)
+    sys.modules["glc_binding"] = glc
+    import datagen
+    L = glc.lib()
+    dev = torch.device("cuda:0")
+    n = MiB
+    nblocks = int(args.gib * 1024)
+    total = nblocks * n
+    d_in = torch.empty(total, dtype=torch.uint8, device=dev)
+    thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
+    assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+    torch.cuda.synchronize()
+
+    def timed(fn):
+        fn()                                                   # warm-up
+        torch.cuda.synchronize()
+        best = 1e30
+        for _ in range(args.iters):
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            best = min(best, time.perf_counter() - t)
+        return best
+
+    res = {"workload": "configs[1]: %d x 1 MiB Philox Zipf(1.0) blocks, plan rows %d, pipelining %s" % (nblocks, args.rows, bool(args.pipelining))}
+    # --- CRC against the read probe
+    off = torch.zeros(1, dtype=torch.int64, device=dev)
+    ln = torch.full((1,), total, dtype=torch.int64, device=dev)
+    crc = torch.zeros(1, dtype=torch.int32, device=dev)
+    t_crc = timed(lambda: glc._chk("glcCrc32Segments", glc._ct().glcCrc32Segments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), 1,
+                                                                                 crc.data_ptr(), None)))
+    import ctypes as C
+    ms = C.c_float(0)
+    assert L.glcProbeStreamRead(d_in.data_ptr(), total, 5, C.byref(ms), None) == 1
+    res["crc_GBps"] = total / t_crc / 1e9
+    res["probe_read_GBps"] = total / (ms.value * 1e-3) / 1e9
+    res["crc_vs_probe"] = res["crc_GBps"] / res["probe_read_GBps"]
+
+    with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+        plan.set_pipelining(bool(args.pipelining))
+        nsub = n // 4096
+        bwt = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        hist = torch.empty(nblocks * 256, dtype=torch.int32, device=dev)
+        offs = torch.empty(nblocks * nsub, dtype=torch.int32, device=dev)
+        size = torch.empty(nblocks, dtype=torch.int32, device=dev)
+        compact = torch.empty(nblocks * (n // 4 + nsub + 1), dtype=torch.int32, device=dev)   # (Zipf(1.0) bytes shrink: a word per 4 input bytes is room)
+        coff = torch.empty(nblocks + 1, dtype=torch.int64, device=dev)
+
+        def enc_compact():
+            for b0 in range(0, nblocks, args.rows):
+                nb = min(args.rows, nblocks - b0)
+                rc = L.glcCompressBatchCompact(plan.handle, d_in.data_ptr() + b0 * n, bwt.data_ptr() + 4 * b0, hist.data_ptr() + 1024 * b0,
+                                               offs.data_ptr() + 4 * nsub * b0, nsub, size.data_ptr() + 4 * b0, compact.data_ptr(),
+                                               compact.numel(), coff.data_ptr() + 8 * b0, (coff.data_ptr() + 8 * b0) if b0 else None, n, nb)
+                assert rc == 0, rc
+            plan.synchronize()
+
+        t_enc = timed(enc_compact)
+        compact_bytes = 4 * int(coff[nblocks].item())
+        cap = glc.container_bound(total, n)
+        cont = torch.empty(cap, dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+        t_cenc = timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+            plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+        clen = int(d_len.item())
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+
+        def dec_compact():
+            for b0 in range(0, nblocks, args.rows):
+                nb = min(args.rows, nblocks - b0)
+                rc = L.glcDecompressBatchCompact(plan.handle, bwt.data_ptr() + 4 * b0, hist.data_ptr() + 1024 * b0,
+                                                 offs.data_ptr() + 4 * nsub * b0, nsub, compact.data_ptr(), compact.numel(),
+                                                 coff.data_ptr() + 8 * b0, out.data_ptr() + b0 * n, n, nb)
+                assert rc == 0, rc
+            plan.synchronize()
+
+        t_dec = timed(dec_compact)
+        assert torch.equal(out, d_in)
+        out.zero_()
+        t_cdec = timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+        assert torch.equal(out, d_in) and int(d_len.item()) == total
+    res.update({"compact_encode_GBps": total / t_enc / 1e9, "container_encode_GBps": total / t_cenc / 1e9,
+                "encode_ratio": t_enc / t_cenc,
+                "compact_decode_GBps": total / t_dec / 1e9, "container_decode_GBps": total / t_cdec / 1e9,
+                "decode_ratio": t_dec / t_cdec,
+                "compact_bytes": compact_bytes, "container_bytes": clen, "size_overhead": clen / compact_bytes - 1})
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
