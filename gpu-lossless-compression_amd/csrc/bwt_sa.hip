@@ -846,7 +846,7 @@ __global__ __launch_bounds__(SA_THREADS) void k_chain_minmax(const uint64_t *__r
 
 __global__ __launch_bounds__(SA_THREADS) void k_chain_decide(const uint64_t *__restrict__ key, const uint32_t *__restrict__ pos,
                                                              const uint32_t *__restrict__ cnt, const uint2 *__restrict__ rec,
-                                                             uint32_t *__restrict__ info, uint32_t nmax)
+                                                             uint32_t *__restrict__ info, uint32_t nmax, uint32_t *__restrict__ tally)
 {
     const uint32_t b = blockIdx.y, m = cnt[b];
     const uint64_t *K = key + (size_t)b * nmax;
@@ -859,7 +859,7 @@ __global__ __launch_bounds__(SA_THREADS) void k_chain_decide(const uint64_t *__r
         const uint32_t mn = r.x, mx = ~r.y;
         if (L >= 2 && mx > mn && (mx - mn) % (L - 1) == 0) {
             const uint32_t d = (mx - mn) / (L - 1);
-            if (d <= CHAIN_DMAX) info[(size_t)b * nmax + g - 1] = d | CHAIN_CAND;
+            if (d <= CHAIN_DMAX) { info[(size_t)b * nmax + g - 1] = d | CHAIN_CAND; atomicAdd(tally, 1u); }   // (tally[0]: candidates)
         }
     }
 }
@@ -912,7 +912,8 @@ __global__ __launch_bounds__(SA_THREADS) void k_chain_verify(const uint64_t *__r
 
 __global__ __launch_bounds__(SA_THREADS) void k_chain_dir(const uint64_t *__restrict__ key, const uint32_t *__restrict__ cnt,
                                                           const uint2 *__restrict__ rec, uint32_t *__restrict__ info, uint32_t nmax,
-                                                          const uint8_t *__restrict__ text, size_t text_stride, uint32_t n, uint32_t h)
+                                                          const uint8_t *__restrict__ text, size_t text_stride, uint32_t n, uint32_t h,
+                                                          uint32_t *__restrict__ tally)
 {
     const uint32_t b = blockIdx.y, m = cnt[b];
     const uint64_t *K = key + (size_t)b * nmax;
@@ -942,6 +943,7 @@ __global__ __launch_bounds__(SA_THREADS) void k_chain_dir(const uint64_t *__rest
         }
         if (less < 0) { *I = 0u; continue; }                   // (cannot happen: see above; the group is left to the doubling)
         *I = d | CHAIN_OK | (less ? CHAIN_DESC : 0u);
+        atomicAdd(tally + 1, 1u);                              // (tally[1]: chains taken)
     }
 }
 
@@ -1163,10 +1165,11 @@ hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows)
     GLC_TRY(A((void **)&s.ghist, (size_t)rows * RS_MAXPASS * SA_MAXRADIX * 4));
     GLC_TRY(A((void **)&s.ticket, (size_t)rows * 4));
     GLC_TRY(A((void **)&s.cntA, (size_t)rows * 4)); GLC_TRY(A((void **)&s.cntB, (size_t)rows * 4));
-    GLC_TRY(A((void **)&s.d_max_cnt, 16));
+    GLC_TRY(A((void **)&s.d_max_cnt, 24));
     GLC_TRY(A((void **)&s.rl_flag, (size_t)rows * 4));
     GLC_TRY(A((void **)&s.rl_cnt, (size_t)rows * 4));
-    GLC_TRY(hipHostMalloc((void **)&s.h_max_cnt, 32, hipHostMallocDefault));
+    GLC_TRY(hipHostMalloc((void **)&s.h_max_cnt, 64, hipHostMallocDefault));
+    sa_chain_defaults(&s.chain_min, &s.chain_rounds);
     s.bytes = total;
     return hipSuccess;
 }
@@ -1284,7 +1287,7 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
     uint32_t tiles = (n + SA_TILE - 1) / SA_TILE;
     uint64_t *cur = s.keyA, *alt = s.keyB;
     double live_total = (double)n * nsorted;
-    GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, 16, st));          // [2] doubles as the device error word of the sort
+    GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, 24, st));          // [2] doubles as the device error word of the sort, [4..5] count chain groups
     if (!resume_depth) {   // 41 key bits at [20, 61): 8+8+8+8+9
         PassPlan pp = {5, {VAL_BITS, VAL_BITS + 8, VAL_BITS + 16, VAL_BITS + 24, VAL_BITS + 32}, {8, 8, 8, 8, 9}};
         const TextSrc src{text, text_stride, n};               // pass 0 and the histograms read the text itself
@@ -1322,13 +1325,19 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
                                s.d_max_cnt, s.nmax, s.max_tiles, mode, text, text_stride, n, depth, bwt_out, bwt_stride,
                                d_index, s.d_max_cnt + 2);
         GLC_TRY(hipGetLastError());
-        GLC_TRY(hipMemcpyAsync(s.h_max_cnt, s.d_max_cnt, 16, hipMemcpyDeviceToHost, st));
+        // (hc[4..5]: the chain tallies of every round so far -- candidates, taken -- ride along on the round's one readback)
+        uint32_t *hc = s.h_max_cnt + 8;
+        GLC_TRY(hipMemcpyAsync(hc, s.d_max_cnt, 24, hipMemcpyDeviceToHost, st));
         GLC_TRY(hipStreamSynchronize(st));
         rounds++;
-        const uint32_t maxc = s.h_max_cnt[0];
-        live_total = (double)s.h_max_cnt[1];
-        if (s.h_max_cnt[2]) return hipErrorUnknown;               // a look-back spin hit its bound
-        if (maxc == 0) break;
+        const uint32_t maxc = hc[0];
+        live_total = (double)hc[1];
+        if (hc[2]) return hipErrorUnknown;                        // a look-back spin hit its bound
+        if (maxc == 0) {
+            s.last_chains[0] += hc[5];
+            s.last_chains[1] += hc[4] - hc[5];
+            break;
+        }
         if (depth >= 2u * n + 16u) return hipErrorUnknown;        // cannot happen: depth >= n resolves everything
         // next round works on the compacted list that k_sa_rank<true> wrote into `alt`
         { uint64_t *x = cur; cur = alt; alt = x; }
@@ -1358,14 +1367,14 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
             text_rounds++;
         } else {
             // chain groups (one residue class of a periodic stretch each) get their final order this round; worth its five light
-            // passes over the list only where a lot is still live (GLC_CHAIN_MIN: tests lower it, 0 switches it off)
-            static const long chain_min = getenv("GLC_CHAIN_MIN") ? atol(getenv("GLC_CHAIN_MIN")) : 16384;
+            // passes over the list only where a lot is still live (s.chain_min, glcPlanSetChains: tests lower it, 0 switches it off)
+            const long chain_min = s.chain_min;
             // ... in the FIRST doubling round (a periodic stretch over a large alphabet is all chains at once), and again in rounds
             // 2 and 4 where more than half of everything is still live: over a small alphabet the period's 5-grams repeat, a group of
             // the first round holds several residue classes and only becomes chains once the depth tells them apart (two periodic
             // halves over {0, 1}: 50.1 ms per 32 blocks with the first round alone, 15.6 with all three; blocks with something deep
             // INSIDE have a few per cent live and are spared the later attempts' launches: 9.2 against 9.6 ms per 64)
-            static const long chain_every = getenv("GLC_CHAIN_ROUNDS") ? atol(getenv("GLC_CHAIN_ROUNDS")) : 0x15;   // bit r: try in doubling round r
+            const uint32_t chain_every = s.chain_rounds;             // bit r: try in doubling round r
             const bool mostly_live = live_total >= 0.5 * (double)n * nsorted;
             const bool chains = chain_min > 0 && live_total >= (double)chain_min && pos_cur != nullptr && isa_rounds < 32 &&
                                 ((chain_every >> isa_rounds) & 1) && (isa_rounds == 0 || mostly_live);
@@ -1375,12 +1384,13 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
                 dim3 cg(fill_blocks, nblk), ct(SA_THREADS);
                 hipLaunchKernelGGL(k_chain_init, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax);
                 hipLaunchKernelGGL(k_chain_minmax, cg, ct, 0, st, cur, cnt_cur, rec, s.nmax);
-                hipLaunchKernelGGL(k_chain_decide, cg, ct, 0, st, cur, pos_cur, cnt_cur, rec, s.hdA, s.nmax);
+                hipLaunchKernelGGL(k_chain_decide, cg, ct, 0, st, cur, pos_cur, cnt_cur, rec, s.hdA, s.nmax, s.d_max_cnt + 4);
                 // (the verification's cache, n / 16 halfwords at the head of every block's part of pos_next -- which the NEXT rank pass writes)
                 GLC_TRY(hipMemset2DAsync(pos_next, (size_t)s.nmax * 4, 0, ((size_t)n / 16 + 1) * 2, nblk, st));
                 hipLaunchKernelGGL(k_chain_verify, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax, text, text_stride,
                                    reinterpret_cast<uint16_t *>(pos_next));
-                hipLaunchKernelGGL(k_chain_dir, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax, text, text_stride, n, depth);
+                hipLaunchKernelGGL(k_chain_dir, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax, text, text_stride, n, depth,
+                                   s.d_max_cnt + 4);
             }
             hipLaunchKernelGGL(k_sa_fill_rank2, dim3(fill_blocks, nblk), dim3(SA_THREADS), 0, st, cur, cnt_cur, s.isa,
                                n, depth, s.nmax, rec, chains ? s.hdA : (const uint32_t *)nullptr);
@@ -1407,6 +1417,7 @@ hipError_t sa_build_begin(hipStream_t st, const uint8_t *text, size_t text_strid
     if (n == 0 || n > s.nmax || n > MAX_BLOCK_ELEMS || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
     s.last_flagged = nblk;
     s.last_general = nblk;
+    s.last_chains[0] = s.last_chains[1] = 0;
     s.pending = false;
     if (s.sorter == 1 || s.sorter == 2) {
         const bool isa = s.force_isa;

@@ -681,6 +681,33 @@ CUDPPResult glcPlanLastSortPeriodic(CUDPPHandle planHandle, unsigned int *out)
     return CUDPP_SUCCESS;
 }
 
+// chain groups of the doubling rounds: the plan's attempt schedule (minLive < 0 / roundMask == ~0u restore the defaults)
+CUDPPResult glcPlanSetChains(CUDPPHandle planHandle, long minLive, unsigned int roundMask)
+{
+    PlanBase *p = plan_from<PlanBase>(planHandle);
+    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = sa_of(p);
+    if (!s) return CUDPP_ERROR_INVALID_PLAN;
+    long dmin;
+    uint32_t dmask;
+    sa_chain_defaults(&dmin, &dmask);
+    s->chain_min = minLive < 0 ? dmin : minLive;
+    s->chain_rounds = roundMask == ~0u ? dmask : roundMask;
+    return CUDPP_SUCCESS;
+}
+
+// out2[0] = chain groups the plan's last call ordered by the rule, out2[1] = candidates the verification or the direction refused
+CUDPPResult glcPlanLastSortChains(CUDPPHandle planHandle, unsigned int *out2)
+{
+    PlanBase *p = plan_from<PlanBase>(planHandle);
+    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out2) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = sa_of(p);
+    if (!s) return CUDPP_ERROR_INVALID_PLAN;
+    out2[0] = s->last_chains[0];
+    out2[1] = s->last_chains[1];
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult glcPlanLastSortResumed(CUDPPHandle planHandle, unsigned int *out)
 {
     PlanBase *p = plan_from<PlanBase>(planHandle);

@@ -164,10 +164,15 @@ struct SaScratch {
     uint32_t *hdA = nullptr, *hdB = nullptr;     // [rows][nmax] SA slot of the group head of each unresolved entry
     uint32_t *cntA = nullptr, *cntB = nullptr;   // [rows] unresolved counts
     uint32_t *rl_flag = nullptr, *rl_cnt = nullptr;   // [rows] tile-local refinement: block needs the global sort / its count
-    uint32_t *d_max_cnt = nullptr;               // [2] max and sum of the unresolved counts
-    uint32_t *h_max_cnt = nullptr;               // pinned [2]
+    uint32_t *d_max_cnt = nullptr;               // [6] max and sum of the unresolved counts, error word, refinement count, chain tallies
+    uint32_t *h_max_cnt = nullptr;               // pinned [16]: [0..7] the tiers' readbacks, [8..13] the doubling round's copy of d_max_cnt
     size_t    bytes = 0;
     bool      force_isa = false;                 // tests: skip text refinement, prefix doubling from round 1
+    // chain groups of the doubling rounds (bwt_sa.hip k_chain_*): attempted in doubling round r where bit r of chain_rounds is
+    // set and at least chain_min suffixes of the call are live (0: never); glcPlanSetChains, defaults from sa_chain_defaults
+    long      chain_min = 16384;
+    uint32_t  chain_rounds = 0x15;
+    uint32_t  last_chains[2] = {0, 0};           // the plan's last call: chain groups ordered by the rule, candidates refused
     // fast path (bwt_bucket.hip); its words live in keyA/keyB (one allocation, fs_kstride words per block)
     int       sorter = 0;                        // 0 = bucket sorter, then sample sorter, then general sorter for what each flags;
                                                  // 1 = general sorter only; 2 = general sorter, prefix doubling only;
@@ -245,6 +250,13 @@ inline bool sa_skips_tier1(const SaScratch &s, uint32_t nblk)
     return s.sorter == 4 || (s.sorter == 0 && nblk <= TEXT_SKIP_MAX && s.textlike_streak >= TEXT_STREAK);
 }
 hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows);
+// what a plan starts with: GLC_CHAIN_MIN / GLC_CHAIN_ROUNDS (decimal) where set, else 16384 live suffixes, doubling rounds 0, 2, 4
+inline void sa_chain_defaults(long *min_live, uint32_t *round_mask)
+{
+    const char *m = getenv("GLC_CHAIN_MIN"), *r = getenv("GLC_CHAIN_ROUNDS");
+    *min_live = m ? atol(m) : 16384;
+    *round_mask = r ? (uint32_t)atol(r) : 0x15u;
+}
 hipError_t sa_general_reserve(SaScratch &s, bool only_sa);
 void       sa_scratch_free(SaScratch &s);
 

@@ -25,6 +25,7 @@ CUDPP_COMPRESS = 10
 CUDPP_BWT = 12
 CUDPP_MTF = 13
 CUDPP_SA = 14
+CHAIN_ALL_ROUNDS = 0x7FFFFFFF                           # glcPlanSetChains: a chain attempt in every doubling round
 CUDPP_INVALID_HANDLE = 0xC0DABAD1
 CUDPP_OPTION_FORWARD = 0x1
 CUDPP_OPTION_BACKWARD = 0x2
@@ -38,7 +39,7 @@ CUDPP_SYMBOLS = [
     "cudppBurrowsWheelerTransform", "cudppMoveToFrontTransform", "cudppSuffixArray",
     "glcCompressBatch", "glcBwtBatch", "glcMtfBatch", "glcDecompressBatch", "glcPlanSetStream",
     "glcPlanSynchronize", "glcPlanEnableTiming", "glcPlanLastTiming", "glcPlanKernelProfile",
-    "glcCompactStreams", "glcPlanSetPipelining", "glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanLastSortStatsEx", "glcPlanLastSortRetries", "glcPlanLastSortResumed", "glcPlanLastSortPeriodic", "glcPlanLastSortSkipped", "glcPlanDebugSortFlags", "glcPlanDebugBucketFill", "glcHuffmanEncodeBatch", "glcExpandStreams", "glcPlanKernelProfileEx", "glcProbeStreamRead", "glcGenZipfPhilox", "glcGenFloatPhilox", "glcPlanKernelProfileLost",
+    "glcCompactStreams", "glcPlanSetPipelining", "glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanLastSortStatsEx", "glcPlanLastSortRetries", "glcPlanLastSortResumed", "glcPlanLastSortPeriodic", "glcPlanSetChains", "glcPlanLastSortChains", "glcPlanLastSortSkipped", "glcPlanDebugSortFlags", "glcPlanDebugBucketFill", "glcHuffmanEncodeBatch", "glcExpandStreams", "glcPlanKernelProfileEx", "glcProbeStreamRead", "glcGenZipfPhilox", "glcGenFloatPhilox", "glcPlanKernelProfileLost",
     "glcCompressBatchCompact", "glcDecompressBatchCompact",
 ]
 CULZSS_SYMBOLS = [
@@ -107,6 +108,8 @@ def lib():
     L.glcPlanLastSortRetries.argtypes = [sz, C.POINTER(C.c_uint)]
     L.glcPlanLastSortResumed.argtypes = [sz, C.POINTER(C.c_uint)]
     L.glcPlanLastSortPeriodic.argtypes = [sz, C.POINTER(C.c_uint)]
+    L.glcPlanSetChains.argtypes = [sz, C.c_long, C.c_uint]
+    L.glcPlanLastSortChains.argtypes = [sz, C.POINTER(C.c_uint)]
     L.glcPlanLastSortSkipped.argtypes = [sz, C.POINTER(C.c_uint)]
     L.glcPlanDebugSortFlags.argtypes = [sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint), sz]
     L.glcPlanDebugBucketFill.argtypes = [sz, sz, C.POINTER(C.c_uint)]
@@ -309,6 +312,22 @@ class Plan:
         a = (C.c_uint * 1)()
         _chk("glcPlanLastSortPeriodic", lib().glcPlanLastSortPeriodic(self.handle, a))
         return a[0]
+
+    def set_chains(self, min_live=None, round_mask=None):
+        """chain groups of the doubling rounds: attempted in doubling round r where bit r of round_mask is set and at least
+        min_live suffixes of the call are live (0: never); None restores the default (GLC_CHAIN_MIN / GLC_CHAIN_ROUNDS, else
+        16384 / 0x15).  round_mask=CHAIN_ALL_ROUNDS: every round"""
+        m = -1 if min_live is None else int(min_live)
+        r = 0xFFFFFFFF if round_mask is None else int(round_mask)
+        if not 0 <= r <= 0xFFFFFFFF:
+            raise ValueError("round_mask is a 32-bit mask")
+        _chk("glcPlanSetChains", lib().glcPlanSetChains(self.handle, m, r))
+
+    def last_sort_chains(self):
+        """(chain groups ordered by the rule, candidates refused) of the last call, summed over rounds and blocks"""
+        a = (C.c_uint * 2)()
+        _chk("glcPlanLastSortChains", lib().glcPlanLastSortChains(self.handle, a))
+        return int(a[0]), int(a[1])
 
     def last_sort_skipped(self):
         """(skipped, streak): did the plan's last call go straight to the sample sorter, and the streak of all-text-like calls"""

@@ -273,6 +273,17 @@ CUDPPResult glcPlanLastSortRetries(CUDPPHandle planHandle, unsigned int *out);
 CUDPPResult glcPlanLastSortResumed(CUDPPHandle planHandle, unsigned int *out);
 /* out[0] = how many of the blocks the sample sorter gave up on were finished by the periodic tier (see glcPlanSetSorter) */
 CUDPPResult glcPlanLastSortPeriodic(CUDPPHandle planHandle, unsigned int *out);
+/* Chain groups of the general sorter's doubling rounds (a group of tied suffixes i, i + d, ... on a d-periodic stretch, given its
+ * final order from one text comparison).  The attempt is made in doubling round r where bit r of roundMask is set and at least
+ * minLive suffixes of the call are still live; minLive = 0 switches chains off.  A plan starts with GLC_CHAIN_MIN /
+ * GLC_CHAIN_ROUNDS (decimal) where set, else 16384 and 0x15 (rounds 0, 2 and 4; rounds past 0 only while half of the call is
+ * live); minLive < 0 restores the default minimum, roundMask = ~0u the default mask (every round: GLC_CHAIN_ALL_ROUNDS).
+ * Produces the same bytes either way; the knob exists for tests and A/B timing. */
+#define GLC_CHAIN_ALL_ROUNDS 0x7FFFFFFFu
+CUDPPResult glcPlanSetChains(CUDPPHandle planHandle, long minLive, unsigned int roundMask);
+/* out2[0] = chain groups the plan's last call ordered by the rule, summed over rounds and blocks; out2[1] = candidate groups
+ * (an arithmetic progression with a stride of at most 4096) that the verification or the direction walk refused */
+CUDPPResult glcPlanLastSortChains(CUDPPHandle planHandle, unsigned int *out2);
 /* out2[0] = 1 if the plan's last call went straight to the sample sorter (sorter mode 4, or adaptively: a call of up to 4 blocks
    behind eight calls in a row whose every block the text-likeness probe flagged -- the reference's callers hand over one block per
    call, test_compress.cpp:744, and a text block's call spent a fifth of its time on launches that found the block flagged);
