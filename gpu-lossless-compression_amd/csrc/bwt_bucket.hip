@@ -554,6 +554,24 @@ __device__ __forceinline__ void lds_only_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// block_excl_add_lds over the first FS_MAXNB threads only (one per bucket; the others pass through the barrier and get a
+// value nobody uses), with the wave number read as a uniform value: the "waves below mine" test is scalar instead of
+// sixteen lane masks kept in SGPRs across the tile loop
+template <int NT>
+__device__ __forceinline__ uint32_t bucket_excl_add_lds(uint32_t x, uint32_t *s_tmp)
+{
+    constexpr uint32_t NW = (NT < (int)FS_MAXNB ? NT : FS_MAXNB) / WAVE;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t inc = wave_incl_add(x);
+    if ((threadIdx.x & 63) == 63 && w < NW) s_tmp[w] = inc;
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    uint32_t base = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < NW; i++)
+        if (i < w) base += s_tmp[i];
+    return base + inc - x;
+}
+
 template <int NT, int ITEMS, int WPE>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_fs_part2(const uint8_t *__restrict__ text, size_t stride, uint32_t n, uint32_t nbl,
                                                      const uint2 *__restrict__ tab, uint64_t *__restrict__ keys, size_t kstride,
@@ -561,12 +579,21 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
                                                      uint32_t *__restrict__ zero_bucket, uint32_t tiles_per_wg)
 {
     constexpr uint32_t TILE = NT * ITEMS;                      // suffixes per tile
-    __shared__ uint32_t s_cnt[FS_MAXNB];
-    __shared__ uint16_t s_start[FS_MAXNB], s_gbase[FS_MAXNB];
-    __shared__ uint64_t s_w[NT * ITEMS];
-    __shared__ uint2 s_tab[256];
-    __shared__ uint32_t s_tmp[NT / 64 + 1];
-    __shared__ uint32_t s_flagged;
+    // one block of LDS with the tile's words LAST: everything else sits below 64 KB, where a per-thread or zero address
+    // register plus the instruction's 16-bit offset reaches it (no address register per array held across the tile loop)
+    __shared__ struct {
+        uint32_t cnt[FS_MAXNB];
+        uint16_t start[FS_MAXNB], gbase[FS_MAXNB];
+        uint2 tab[256];
+        uint32_t tmp[NT / 64 + 1];
+        uint32_t flagged;
+        uint64_t w[NT * ITEMS];
+    } sh;
+    uint32_t *s_cnt = sh.cnt, *s_tmp = sh.tmp;
+    uint16_t *s_start = sh.start, *s_gbase = sh.gbase;
+    uint2 *s_tab = sh.tab;
+    uint64_t *s_w = sh.w;
+    uint32_t &s_flagged = sh.flagged;
     uint8_t *s_txt = reinterpret_cast<uint8_t *>(s_w);         // s_txt[k] = T[base - 1 + k]: dead before the first word is bucketed
     uint32_t bx, by;
     xcd_order(bx, by);                                         // a block's tiles on ONE XCD, back to back
@@ -596,6 +623,117 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     bool have = false;                                         // stg holds the text of the tile about to be processed
     if (inner(tile0)) { request(tile0); have = true; }
     uint64_t *K = keys + (size_t)b * kstride;
+    static_assert(TILE <= (1u << 20), "a rank inside (tile, bucket) rides in the index field of the word until the scatter");
+    constexpr uint32_t LOW = (uint32_t)FS_LOW_MASK;            // the word's low dword: [4 code bits | index : 20 | bwt : 8]
+    // bucket of a word = its top nbl bits, from the high dword (nbl <= 9; a field of width 0 is 0)
+    auto bucket_of = [&](uint32_t hi) { return __builtin_amdgcn_ubfe(hi, 32u - nbl, nbl); };
+    // One tile: codes -> ranks inside (tile, bucket) -> scan + global atomics -> LDS scatter -> stores.  false: the block is
+    // flagged.  EDGE: the tile holds suffixes past n or its 16 bytes behind reach past the block (its last tile, or its only
+    // one): the per-suffix guards below exist in this instance only.
+    auto tile_body = [&](auto edge_t, uint32_t base, bool next_inner) __attribute__((always_inline)) -> bool {
+        constexpr bool EDGE = decltype(edge_t)::value;
+        // thread = 8 consecutive suffixes gi0 .. gi0+7; byte j of its 16 staged bytes is T[gi0 - 1 + j]
+        const uint32_t k0 = tid * ITEMS, gi0 = base + k0;
+        constexpr int NBY = (ITEMS + FS_DEPTH + 3) / 4;       // dwords that hold the thread's ITEMS + FS_DEPTH staged bytes (k0 is a multiple of ITEMS)
+        uint32_t by4[NBY];
+        if (ITEMS % 8 == 0) {
+#pragma unroll
+            for (int q = 0; q < NBY; q += 2) {
+                const uint2 v = *reinterpret_cast<const uint2 *>(s_txt + k0 + 4 * q);
+                by4[q] = v.x;
+                if (q + 1 < NBY) by4[q + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < NBY; q++) by4[q] = *reinterpret_cast<const uint32_t *>(s_txt + k0 + 4 * q);
+        }
+#define FS_BYTE(j) ((by4[(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu)
+        // table entry of the symbol at byte 1 + k (past the end of the block: C = p = 0); entry k is dead behind code k, so
+        // the entries come in as the codes need them (a window of FS_DEPTH in registers rather than all ITEMS + FS_DEPTH - 1)
+        uint2 e[ITEMS + FS_DEPTH - 1];
+        auto entry = [&](int k) {
+            const uint2 t = s_tab[FS_BYTE(1 + k)];
+            if constexpr (EDGE) return gi0 + k >= n ? make_uint2(0u, 0u) : t;
+            else return t;
+        };
+#pragma unroll
+        for (int k = 0; k < FS_DEPTH - 1; k++) e[k] = entry(k);
+        // the words leave this phase as [high dword | low dword with the RANK inside (tile, bucket) in the index field]: the
+        // bucket is the high dword's top bits and the index is gi0 + j, both re-derived at the scatter
+        uint32_t xh[ITEMS], xl[ITEMS];
+#pragma unroll
+        for (int j = 0; j < ITEMS; j++) {
+            e[j + FS_DEPTH - 1] = entry(j + FS_DEPTH - 1);
+            uint32_t y = e[j + FS_DEPTH - 1].x;
+#pragma unroll
+            for (int d = FS_DEPTH - 2; d >= 1; d--) y = e[j + d].x + __umulhi(e[j + d].y, y);
+            const uint64_t X = ((uint64_t)e[j].x << 32) + (uint64_t)e[j].y * y;
+            const uint32_t hi = (uint32_t)(X >> 32), bk = bucket_of(hi);
+            uint32_t r = 0;
+            if (!EDGE || gi0 + j < n) r = atomicAdd(&s_cnt[bk], 1u);
+            xh[j] = hi;
+            xl[j] = ((uint32_t)X & ~LOW) | (r << 8);
+            if (j == 0 && gi0 == 0) zero_bucket[b] = bk;        // where the word of suffix 0 goes: k_fs_sort_bwt looks for the BWT index there only
+        }
+        lds_only_barrier();
+        uint32_t g = 0, c = 0;
+        {
+            c = tid < FS_MAXNB ? s_cnt[tid] : 0u;
+            const uint32_t start = bucket_excl_add_lds<NT>(c, s_tmp);
+            if (c) g = atomicAdd(&fill[(size_t)b * FS_MAXNB + tid], c);     // issued here, looked at behind the scatter
+            if (tid < FS_MAXNB) s_start[tid] = (uint16_t)start;
+        }
+        // the BWT bytes go in from the staged text, read again here rather than kept through the code phase
+        {
+            const uint2 v = *reinterpret_cast<const uint2 *>(s_txt + k0);
+            by4[0] = v.x;
+            by4[1] = v.y;
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) xl[j] |= FS_BYTE(j);
+        }
+#undef FS_BYTE
+        lds_only_barrier();                                    // (the staged text and the table reads are done: s_w takes the words)
+#pragma unroll
+        for (int j = 0; j < ITEMS; j++) {
+            asm volatile("" : "+v"(xh[j]), "+v"(xl[j]));        // two registers per word across the scan, not the code phase's bucket, rank and index
+            if (!EDGE || gi0 + j < n) {
+                const uint32_t lo = (xl[j] & ~(LOW ^ 0xFFu)) | ((gi0 + j) << 8);
+                s_w[s_start[bucket_of(xh[j])] + ((xl[j] >> 8) & 0xFFFFFu)] = ((uint64_t)xh[j] << 32) | lo;
+            }
+        }
+        if (c && g + c > FS_FILLMAX) { atomicOr(&flag[b], 1u); s_flagged = 1; }
+        if (tid < FS_MAXNB) s_gbase[tid] = (uint16_t)(g < FS_CAP ? g : FS_CAP);
+        if (next_inner) {                                      // the next tile's text has arrived before this tile's stores are issued
+#pragma unroll                                                 // (loads and stores share one in-order counter)
+            for (int r = 0; r < NSTG; r++) asm volatile("" : "+v"(stg[r]));
+        }
+        lds_only_barrier();
+        if constexpr (EDGE) {
+            const uint32_t tile_n = min((uint32_t)TILE, n - base);
+#pragma unroll
+            for (int r = 0; r < ITEMS; r++) {
+                const uint32_t p = r * NT + tid;
+                if (p < tile_n) {
+                    const uint64_t ww = s_w[p];
+                    const uint32_t d = bucket_of((uint32_t)(ww >> 32));
+                    const uint32_t off = (uint32_t)s_gbase[d] + (p - (uint32_t)s_start[d]);
+                    if (off < FS_CAP) K[(size_t)d * FS_CAP + off] = ww;
+                }
+            }
+        } else {
+            // A bucket this tile's words would carry past FS_CAP has set s_flagged above (g + c > FS_FILLMAX): a tile that is not
+            // flagged stores every word inside its bucket's slot, and a flagged block's slots are read by nobody
+            if (__builtin_amdgcn_readfirstlane(s_flagged)) return false;
+#pragma unroll
+            for (int r = 0; r < ITEMS; r++) {
+                const uint32_t p = r * NT + tid;
+                const uint64_t ww = s_w[p];
+                const uint32_t d = bucket_of((uint32_t)(ww >> 32));
+                K[d * FS_CAP + (uint32_t)s_gbase[d] + (p - (uint32_t)s_start[d])] = ww;
+            }
+        }
+        return true;
+    };
 #pragma clang loop unroll(disable)
     for (uint32_t tile = tile0; tile < tend; tile++) {
         const uint32_t base = tile * TILE;
@@ -617,75 +755,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         const bool next_inner = tile + 1 < tend && inner(tile + 1);
         if (next_inner) request(tile + 1);                     // in flight until this tile's words are in LDS
         if (s_flagged) return;
-        // thread = 8 consecutive suffixes gi0 .. gi0+7; byte j of its 16 staged bytes is T[gi0 - 1 + j]
-        const uint32_t k0 = tid * ITEMS, gi0 = base + k0;
-        constexpr int NBY = (ITEMS + FS_DEPTH + 3) / 4;       // dwords that hold the thread's ITEMS + FS_DEPTH staged bytes (k0 is a multiple of ITEMS)
-        uint32_t by4[NBY];
-        if (ITEMS % 8 == 0) {
-#pragma unroll
-            for (int q = 0; q < NBY; q += 2) {
-                const uint2 v = *reinterpret_cast<const uint2 *>(s_txt + k0 + 4 * q);
-                by4[q] = v.x;
-                if (q + 1 < NBY) by4[q + 1] = v.y;
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < NBY; q++) by4[q] = *reinterpret_cast<const uint32_t *>(s_txt + k0 + 4 * q);
-        }
-#define FS_BYTE(j) ((by4[(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu)
-        uint2 e[ITEMS + FS_DEPTH - 1];                     // table entries of the symbols the 8 codes share
-#pragma unroll
-        for (int k = 0; k < ITEMS + FS_DEPTH - 1; k++) {
-            const uint2 t = s_tab[FS_BYTE(1 + k)];
-            e[k] = (edge && gi0 + k >= n) ? make_uint2(0u, 0u) : t;
-        }
-        uint64_t w[ITEMS];
-        uint32_t br[ITEMS];                                // bucket << 16 | rank inside (tile, bucket)
-#pragma unroll
-        for (int j = 0; j < ITEMS; j++) {
-            uint32_t y = e[j + FS_DEPTH - 1].x;
-#pragma unroll
-            for (int d = FS_DEPTH - 2; d >= 1; d--) y = e[j + d].x + __umulhi(e[j + d].y, y);
-            const uint64_t X = ((uint64_t)e[j].x << 32) + (uint64_t)e[j].y * y;
-            const uint32_t gi = gi0 + j;
-            w[j] = (X & ~FS_LOW_MASK) | ((uint64_t)gi << 8) | FS_BYTE(j);
-            const uint32_t bk = nbl ? (uint32_t)(X >> (64 - nbl)) : 0u;
-            br[j] = (bk << 16) | (gi < n ? atomicAdd(&s_cnt[bk], 1u) : 0u);
-            if (j == 0 && gi == 0) zero_bucket[b] = bk;        // where the word of suffix 0 goes: k_fs_sort_bwt looks for the BWT index there only
-        }
-#undef FS_BYTE
-        lds_only_barrier();
-        uint32_t g = 0, c = 0;
-        {
-            c = tid < FS_MAXNB ? s_cnt[tid] : 0u;
-            const uint32_t start = block_excl_add_lds<NT>(c, s_tmp);
-            if (c) g = atomicAdd(&fill[(size_t)b * FS_MAXNB + tid], c);     // issued here, looked at behind the scatter
-            if (tid < FS_MAXNB) s_start[tid] = (uint16_t)start;
-        }
-        lds_only_barrier();                                    // (the staged text and the table reads are done: s_w takes the words)
-#pragma unroll
-        for (int j = 0; j < ITEMS; j++)
-            if (gi0 + j < n) s_w[s_start[br[j] >> 16] + (br[j] & 0xFFFFu)] = w[j];
-        if (c && g + c > FS_FILLMAX) { atomicOr(&flag[b], 1u); s_flagged = 1; }
-        if (tid < FS_MAXNB) s_gbase[tid] = (uint16_t)(g < FS_CAP ? g : FS_CAP);
-        if (next_inner) {                                      // the next tile's text has arrived before this tile's stores are issued
-#pragma unroll                                                 // (loads and stores share one in-order counter)
-            for (int r = 0; r < NSTG; r++) asm volatile("" : "+v"(stg[r]));
-        }
+        // The tile proper, in two instances: an INNER tile (every suffix of it and the 16 bytes behind it inside the block: all
+        // but the first and last tile of a block, and the first as well when the block is long) takes no per-suffix guard at
+        // all; an edge tile (suffixes past n, symbols past the end contributing C = p = 0) keeps them.
+        const bool go = edge ? tile_body(std::true_type{}, base, next_inner) : tile_body(std::false_type{}, base, next_inner);
+        if (!go) return;
         have = next_inner;
-        lds_only_barrier();
-        const uint32_t tile_n = min((uint32_t)TILE, n - base);
-#pragma unroll
-        for (int r = 0; r < ITEMS; r++) {
-            const uint32_t p = r * NT + tid;
-            if (p < tile_n) {
-                const uint64_t ww = s_w[p];
-                const uint32_t d = nbl ? (uint32_t)(ww >> (64 - nbl)) : 0u;
-                const uint32_t off = (uint32_t)s_gbase[d] + (p - (uint32_t)s_start[d]);
-                if (off < FS_CAP) K[(size_t)d * FS_CAP + off] = ww;
-            }
-        }
-        lds_only_barrier();                                    // s_w is free for the next tile's text
+        lds_only_barrier();                                   // s_w is free for the next tile's text
     }
 }
 
@@ -2702,7 +2778,9 @@ hipError_t fs_build(hipStream_t st, const uint8_t *text, size_t text_stride, uin
             static const int per_env = getenv("GLC_FSP2_PER") ? atoi(getenv("GLC_FSP2_PER")) : 0;    // A/B: tiles per workgroup
             static const bool small_tiles = getenv("GLC_FSP2_SMALL") != nullptr;                     // A/B: 4096-suffix tiles for batches too
             // Batches of 16 blocks or more: tiles of 8192 suffixes, 1024 threads (runs of ~128 bytes leave for a bucket's slot, half the
-            // global atomics; 64 KB of LDS, two workgroups per CU), 16 tiles per workgroup.  Until the MTF kernel was re-based this
+            // global atomics), 16 tiles per workgroup.  70 KB of LDS would let two workgroups share a CU, but the registers (78 VGPRs:
+            // six waves per SIMD) hold it to ONE.  Squeezed to 64 VGPRs with amdgpu_waves_per_eu(8, 8) (4 spilled) for two per CU, it
+            // gave bench.py `value` 105.7-106.5 GB/s against 108.5-109.3 on one box, alternating.  Until the MTF kernel was re-based this
             // shape ran 2.7 ms and gave the same `value` (the stages of the batch before rarely left half a CU free at once); since:
             // alternating on one box, 6 steps: 100.2 / 101.7 / 102.0 GB/s as it was, 102.3 / 102.9 / 103.0 so (8 tiles per workgroup:
             // 102.3 / 102.5 / 102.7); stages back to back 97.8-99.8 -> 101.2-101.7; the kernel 2.91-3.10 -> 2.67-2.73 ms per GiB.
