@@ -55,7 +55,8 @@ EXCHANGE_SYMBOLS = ["glcCommGetUniqueId", "glcCommInitRank", "glcCommAdopt", "gl
                     "glcUnpackRecords", "glcGatherCounts", "glcGatherCountsBegin", "glcGatherCountsReady", "glcGatherCountsEnd",
                     "glcGatherStreams", "glcScatterStreams"]
 HD_SYMBOLS = ["glcHdBuildTable", "glcHdEncodeHost", "glcHdWorkBytes", "glcHdDecodeDevice", "glcHdDecodeDeviceTable", "glcHdDecodeDeviceTableOnDevice", "glcHdEnableProfile",
-              "glcHdKernelProfile"]
+              "glcHdKernelProfile", "glcHdEncodeBound", "glcHdEncodeWorkBytes", "glcHdHistogramDevice", "glcHdBuildTableDevice",
+              "glcHdEncodeDevice"]
 
 
 class CUDPPConfiguration(C.Structure):
@@ -195,6 +196,17 @@ def lib():
         L.glcHdEnableProfile.restype = C.c_int
         L.glcHdKernelProfile.argtypes = [C.c_int, C.c_char_p, sz, C.POINTER(C.c_double)]
         L.glcHdKernelProfile.restype = C.c_int
+    if hasattr(L, "glcHdEncodeDevice"):
+        L.glcHdEncodeBound.argtypes = [sz]
+        L.glcHdEncodeBound.restype = sz
+        L.glcHdEncodeWorkBytes.argtypes = [sz]
+        L.glcHdEncodeWorkBytes.restype = sz
+        L.glcHdHistogramDevice.argtypes = [vp, sz, vp, vp]
+        L.glcHdHistogramDevice.restype = C.c_int
+        L.glcHdBuildTableDevice.argtypes = [vp, vp, vp, vp, vp]
+        L.glcHdBuildTableDevice.restype = C.c_int
+        L.glcHdEncodeDevice.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
+        L.glcHdEncodeDevice.restype = C.c_int
     if hasattr(L, "glcGatherStreams"):                             # include/glc_exchange.h
         ullp = C.POINTER(C.c_ulonglong)
         L.glcCommGetUniqueId.argtypes = [vp]
@@ -507,6 +519,61 @@ def hd_decode_device(d_units, lens, codes, nsym, stream=None):
     if not ok:
         raise HdError("glcHdDecodeDevice failed")
     return out[:nsym]
+
+
+def _stream_ptr(stream):
+    """None (the null stream), a raw hipStream_t value, or a torch.cuda.Stream"""
+    return getattr(stream, "cuda_stream", stream)
+
+
+def hd_histogram_device(d_in, stream=None, d_hist=None):
+    """d_in: uint8 cuda tensor (any offset).  Returns an int64 cuda tensor of 256 byte counts; enqueued only."""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if d_hist is None:
+        d_hist = torch.empty(256, dtype=torch.int64, device=x.device)
+    if not lib().glcHdHistogramDevice(x.data_ptr() if x.numel() else None, x.numel(), d_hist.data_ptr(), _stream_ptr(stream)):
+        raise HdError("glcHdHistogramDevice failed")
+    return d_hist
+
+
+def hd_build_table_device(d_hist, table=True, stream=None):
+    """d_hist: 256 u64 counts in an int64 cuda tensor.  Returns (d_lens uint8[256], d_codes int16[256] holding the u16 codes,
+    d_table uint8[4096] -- the reference's {num_bits, symbol}[2048] decoder table -- or None); enqueued only."""
+    import torch
+    dev = d_hist.device
+    lens = torch.empty(256, dtype=torch.uint8, device=dev)
+    codes = torch.empty(256, dtype=torch.int16, device=dev)
+    tab = torch.empty(4096, dtype=torch.uint8, device=dev) if table else None
+    if not lib().glcHdBuildTableDevice(d_hist.data_ptr(), lens.data_ptr(), codes.data_ptr(), tab.data_ptr() if table else None,
+                                       _stream_ptr(stream)):
+        raise HdError("glcHdBuildTableDevice failed")
+    return lens, codes, tab
+
+
+def hd_encode_device(d_in, d_lens, d_codes, cap_units=None, stream=None, work=None, d_units=None):
+    """Device encode of the uint8 cuda tensor d_in with a device table.  Returns (d_units int32[cap_units], d_nunits int64[1]):
+    the stream is d_units[:d_nunits] (0 units: a symbol without a usable code, or cap_units too small).  Enqueued only."""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    dev = x.device
+    n = x.numel()
+    if cap_units is None:
+        cap_units = d_units.numel() if d_units is not None else int(lib().glcHdEncodeBound(n))
+    if d_units is None:
+        d_units = torch.empty(max(1, cap_units), dtype=torch.int32, device=dev)
+    if work is None:
+        work = torch.empty(int(lib().glcHdEncodeWorkBytes(n)), dtype=torch.uint8, device=dev)
+    nunits = torch.empty(1, dtype=torch.int64, device=dev)
+    if not lib().glcHdEncodeDevice(x.data_ptr() if n else None, n, d_lens.data_ptr(), d_codes.data_ptr(), d_units.data_ptr(),
+                                   cap_units, nunits.data_ptr(), work.data_ptr(), _stream_ptr(stream)):
+        raise HdError("glcHdEncodeDevice failed")
+    if isinstance(stream, torch.cuda.Stream):                  # allocated on the current stream, used on `stream`
+        for t in (work, d_units, nunits):
+            t.record_stream(stream)
+    return d_units, nunits
 
 
 # --------------------------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 /*
- * glc_hd.h -- C ABI of the CUHD-style Huffman-only decoder (BASELINE.json configs[4],
+ * glc_hd.h -- C ABI of the CUHD-style Huffman-only encoder and decoder (BASELINE.json configs[4],
  * SURVEY.md 8(f)3).
  *
  * Replaces, for the same stream shape, the C++ interface of the reference
@@ -20,6 +20,13 @@
  * span is summarised as a function {start offset 0..10} -> {offset into the next span,
  * symbols decoded}; those 11-entry functions compose associatively, so a scan gives the
  * exact start offset and output index of every span in a fixed number of passes.
+ *
+ * The reference encodes on the host (llhuffman_encoder.cc:200-238), as glcHdEncodeHost does.  glcHdHistogramDevice,
+ * glcHdBuildTableDevice and glcHdEncodeDevice do the same work on the device: histogram -> table -> encode ->
+ * glcHdDecodeDeviceTableOnDevice is a round trip that never leaves the device.  These calls only enqueue on `stream`
+ * (a hipStream_t, or NULL), never wait on the host and keep no global state: encodes on different streams with
+ * separate work buffers may overlap.  Each returns 1 when its arguments are valid and the work was enqueued, else 0,
+ * and then nothing was launched.
  */
 #ifndef GLC_HD_H
 #define GLC_HD_H
@@ -40,6 +47,32 @@ int glcHdBuildTable(const unsigned long long hist[256], unsigned char lens[256],
  * zero pad unit, or 0 if out_units (capacity cap_units) is too small. */
 size_t glcHdEncodeHost(const unsigned char *in, size_t nsym, const unsigned char lens[256],
                        const unsigned short codes[256], unsigned int *out_units, size_t cap_units);
+
+/* Units a stream of nsym symbols can need, pad unit included: ceil(11 * nsym / 32) + 1. */
+size_t glcHdEncodeBound(size_t nsym);
+
+/* Device scratch glcHdEncodeDevice needs for nsym symbols. */
+size_t glcHdEncodeWorkBytes(size_t nsym);
+
+/* d_hist[256] (u64, device) = byte counts of d_in[0 .. nsym).  Overwrites d_hist; d_in may have any alignment.
+ * nsym < 2^40. */
+int glcHdHistogramDevice(const unsigned char *d_in, size_t nsym, unsigned long long *d_hist, void *stream);
+
+/* glcHdBuildTable on the device: d_lens[256] / d_codes[256] bit-identical to the host builder's for the same histogram
+ * (histogram total below 2^56).  d_table2048 (optional, may be NULL; 4-byte aligned): the reference's decoder table,
+ * {num_bits, symbol} byte pairs indexed by the next 11 stream bits (cuhd_codetable.h:20-23); entries no codeword
+ * reaches are {0, 0}.  An empty histogram gives all-zero lens, codes and table. */
+int glcHdBuildTableDevice(const unsigned long long *d_hist, unsigned char *d_lens, unsigned short *d_codes,
+                          unsigned char *d_table2048, void *stream);
+
+/* The stream glcHdEncodeHost writes, word for word (MSB-first 32-bit units, zero bits after the last code, one zero pad
+ * unit), from a table in device memory (codes[s] holds lens[s] bits; higher bits are ignored).  *d_nunits (device u64)
+ * = units written, pad included; 0 when a symbol of the input has lens == 0 or lens > 11, or when the stream needs more
+ * than cap_units units -- and then NOTHING is written to d_units.  d_units must be 4-byte aligned; nsym < 2^40;
+ * nsym == 0 writes the pad unit alone.  d_work: glcHdEncodeWorkBytes(nsym) bytes, one per encode in flight.
+ * The decoders above take at most 2^31 units, i.e. streams of up to 2^36 bits. */
+int glcHdEncodeDevice(const unsigned char *d_in, size_t nsym, const unsigned char *d_lens, const unsigned short *d_codes,
+                      unsigned int *d_units, size_t cap_units, unsigned long long *d_nunits, void *d_work, void *stream);
 
 /* Device scratch needed by glcHdDecodeDevice for a stream of `nunits` units. */
 size_t glcHdWorkBytes(size_t nunits);
