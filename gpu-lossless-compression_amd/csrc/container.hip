@@ -317,8 +317,18 @@ hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_
     return hipGetLastError();
 }
 
-hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, uint32_t nb, uint32_t blk_len,
-                             uint8_t *out, unsigned long long cap, CtEncState *state)
+// blocks of blk_len bytes from `bytes` on as CRC segments [0, nb)
+__global__ __launch_bounds__(256) void k_ct_block_segs(unsigned long long *seg_off, unsigned long long *seg_len, const uint8_t *bytes,
+                                                       uint32_t nb, uint32_t blk_len)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= nb) return;
+    seg_off[b] = (unsigned long long)(uintptr_t)(bytes + (size_t)b * blk_len);
+    seg_len[b] = blk_len;
+}
+
+hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
+                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state)
 {
     const uint32_t rw = ct_raw_words(blk_len);
     hipLaunchKernelGGL(k_ct_raw_records, dim3(min(8u, (rw + 255) / 256), nb), dim3(256), 0, st, in, blk_len, f.kind,
@@ -329,6 +339,11 @@ hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t 
     hipLaunchKernelGGL(k_ct_tables, dim3(nb), dim3(256), 0, st, f, nb, blk_len, out, cap, (const CtEncState *)state);
     e = crc32_segments(st, nullptr, f.seg_off + 2 * nb, f.seg_len + 2 * nb, 2, f.tcrc);
     if (e != hipSuccess) return e;
+    if (orig) {                                                // the tables have the shuffled blocks' CRCs: their slots are free again
+        hipLaunchKernelGGL(k_ct_block_segs, dim3((nb + 255) / 256), dim3(256), 0, st, f.seg_off, f.seg_len, orig, nb, blk_len);
+        e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb, f.crc);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_fold_terms, dim3((nb + 255) / 256), dim3(256), 0, st, (const uint32_t *)f.crc, nb, blk_len, &state->frame_acc);
     hipLaunchKernelGGL(k_ct_end, dim3(1), dim3(1), 0, st, f, nb, blk_len, out, cap, state);
     return hipGetLastError();
@@ -443,12 +458,23 @@ hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame,
 }
 
 hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                        const uint8_t *out, uint32_t frame_index, CtDecState *state)
+                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold)
 {
     (void)out;                                                 // (k_cd_raw put the output ranges in f.seg_*)
     hipError_t e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb, f.crc);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_cd_check, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, frame_index, state);
+    if (!fold) return hipGetLastError();
+    hipLaunchKernelGGL(k_fold_terms, dim3((nb + 255) / 256), dim3(256), 0, st, (const uint32_t *)f.crc, nb, blk_len, &state->frame_acc);
+    hipLaunchKernelGGL(k_cd_end, dim3(1), dim3(1), 0, st, nb, blk_len, state);
+    return hipGetLastError();
+}
+
+hipError_t ct_dec_fold(hipStream_t st, const CtDecFrame &f, const uint8_t *bytes, uint32_t nb, uint32_t blk_len, CtDecState *state)
+{
+    hipLaunchKernelGGL(k_ct_block_segs, dim3((nb + 255) / 256), dim3(256), 0, st, f.seg_off, f.seg_len, bytes, nb, blk_len);
+    hipError_t e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb, f.crc);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fold_terms, dim3((nb + 255) / 256), dim3(256), 0, st, (const uint32_t *)f.crc, nb, blk_len, &state->frame_acc);
     hipLaunchKernelGGL(k_cd_end, dim3(1), dim3(1), 0, st, nb, blk_len, state);
     return hipGetLastError();

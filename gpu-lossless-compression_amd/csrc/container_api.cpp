@@ -5,6 +5,9 @@
 // frames, one at the end.  Decode: per frame the host reads the 32-byte frame header, the device checks the tables and records
 // (one verdict read back), then raw records are copied out, runs of Huffman blocks go to glcDecompressBatchCompact reading
 // the tables in place, and the decoded bytes are checked against the blocks' CRCs.
+// The shuffle filter (format version 2, shuffle.hip): with an element size set on the plan the encoder shuffles each frame as one
+// segment into staging kept with the plan and encodes from there; the decoder decodes a version-2 frame into staging, checks its
+// blocks there and unshuffles it into the output.  crc_all is taken over the original bytes on both sides.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 
@@ -75,9 +78,12 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
     return frame_bytes(nb, blk_len, (unsigned long long)nb * ct_raw_words(blk_len) + nb);
 }
 
-void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total)
+bool shuffle_elem_ok(uint32_t elem) { return elem == 2 || elem == 4 || elem == 8; }
+
+// elem: the shuffle's element size, 0 = no filter (version 1, as ever)
+void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem)
 {
-    h[0] = CT_MAGIC_STREAM; h[1] = CT_VERSION; h[2] = block_len; h[3] = 0;
+    h[0] = CT_MAGIC_STREAM; h[1] = elem ? CT_VERSION_SHUFFLE : CT_VERSION; h[2] = block_len; h[3] = elem;
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
     h[6] = crc32_host(h, 24); h[7] = 0;
 }
@@ -92,9 +98,20 @@ struct Encoder {
     uint32_t *status = nullptr;
     unsigned long long *d_len = nullptr;
     CtEncFrame fr[2] = {};
+    uint32_t elem = 0;                                        // the plan's shuffle filter (0 = off)
+    uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     hipError_t init()
     {
+        elem = plan_container_shuffle(P.h);
+        if (elem) {
+            const int nstage = plan_pipelined(P.h) ? 2 : 1;
+            for (int i = 0; i < nstage; i++) {
+                const hipError_t e = plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]);
+                if (e != hipSuccess) return e;
+            }
+            if (nstage == 1) stage[1] = stage[0];
+        }
         const size_t R = P.rows, nsub = (P.n + HUFF_BLOCK - 1) / HUFF_BLOCK;
         const size_t per = (8 * (5 * R + 6) + 4 * (262 * R + R * nsub + 4) + 255) & ~(size_t)255;
         hipError_t e = hipMalloc(&mem, 256 + 2 * per);
@@ -125,17 +142,25 @@ struct Encoder {
     }
     ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
 
-    // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes)
+    // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With the filter on the
+    // frame is shuffled as one segment into staging and its blocks are cut from there; the input's own bytes still make crc_all.
     CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
     {
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
         const CtEncFrame &f = fr[P.parity];
+        const uint8_t *orig = nullptr;
+        if (elem) {
+            plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
+            CT_TRY(shuffle_device(P.st, d_in, stage[P.parity], (unsigned long long)nb * blk_len, elem, false));
+            orig = d_in;
+            d_in = stage[P.parity];
+        }
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
         hk.status = status;
         hk.pack_only = f.only;
         hk.before_offsets = [&](hipStream_t s2) { return ct_enc_kind(s2, f, nb, blk_len, state); };
-        hk.after_pack = [&](hipStream_t s2) { return ct_enc_after_pack(s2, f, d_in, nb, blk_len, out, cap, state); };
+        hk.after_pack = [&](hipStream_t s2) { return ct_enc_after_pack(s2, f, d_in, orig, nb, blk_len, out, cap, state); };
         return plan_compress_hooked(P.h, d_in, f.bwt, f.hist, f.enc_off, nsub, f.size, reinterpret_cast<unsigned int *>(out),
                                     (size_t)(cap / 4), f.boff, f.start, blk_len, nb, hk);
     }
@@ -169,6 +194,7 @@ struct Decoder {
     CtDecFrame f = {};
     CtDecState *state = nullptr;
     unsigned long long *h_verdict = nullptr;                  // pinned
+    uint32_t elem = 0;                                        // the stream header's shuffle filter (0 = none)
 
     ~Decoder()
     {
@@ -203,10 +229,13 @@ struct Decoder {
         return e;
     }
 
-    // a frame in device memory whose header (nb, blk_len, payload words) the host has range-checked; decoded to out
-    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *out, uint32_t fi)
+    // a frame in device memory whose header (nb, blk_len, payload words) the host has range-checked; decoded to out.  A
+    // shuffled frame is decoded into the plan's staging, checked block by block there and unshuffled into out in one launch.
+    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi)
     {
         CT_TRY(reserve(nb));
+        uint8_t *out = final_out;
+        if (elem) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
         CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw));
         CT_TRY(hipMemcpyAsync(h_verdict, f.verdict, 8 * (2 + (nb + 1) / 2), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
@@ -229,7 +258,11 @@ struct Decoder {
             a = b;
         }
         plan_join(P.h);
-        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state));
+        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, elem == 0));
+        if (elem) {
+            CT_TRY(shuffle_device(P.st, out, final_out, (unsigned long long)nb * blk_len, elem, true));
+            CT_TRY(ct_dec_fold(P.st, f, final_out, nb, blk_len, state));
+        }
         return CUDPP_SUCCESS;
     }
 
@@ -245,10 +278,12 @@ struct Decoder {
     }
 };
 
-// the checks on a stream header; returns block_len (0 = refused)
-uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total)
+// the checks on a stream header; returns block_len (0 = refused) and the shuffle's element size (0 = version 1, no filter)
+uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[1] != CT_VERSION || h[3] != 0 || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
+    if (!(h[1] == CT_VERSION && h[3] == 0) && !(h[1] == CT_VERSION_SHUFFLE && shuffle_elem_ok(h[3]))) return 0;
+    *elem = h[3];
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return 0;
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
     return h[2];
@@ -344,7 +379,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     CT_TRY(dout.reserve(ocap));
     CT_TRY(hout.reserve(ocap));
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len);
+    make_header(hdr, E.P.n, len, E.elem);
     if (!out.write(hdr, CT_HDR)) return fail(plan, CT_CAPACITY);
     unsigned long long total = CT_HDR;
     hipStream_t cs = nullptr;
@@ -408,7 +443,7 @@ CUDPPResult decompress_stream(CUDPPHandle plan, Source &src, unsigned long long 
     if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
     if (!src.read(hdr, CT_HDR)) return fail(plan, CT_TRUNCATED);
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -468,7 +503,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(E.init());
     uint8_t *out = static_cast<uint8_t *>(d_out);
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len);
+    make_header(hdr, E.P.n, len, E.elem);
     CT_TRY(ct_enc_header(E.P.st, out, cap, hdr, E.state));
     CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap, [](unsigned long long) { return CUDPP_SUCCESS; });
     if (r != CUDPP_SUCCESS) return r;
@@ -495,7 +530,7 @@ CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, uns
     CT_TRY(hipMemcpyAsync(hdr, in, CT_HDR, hipMemcpyDeviceToHost, D.P.st));
     CT_TRY(hipStreamSynchronize(D.P.st));
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap || (total && !d_out)) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -587,6 +622,67 @@ CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_off
     if (!d_offsets || !d_lengths || !d_crc || count > 0xFFFFFFFFull) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     return hip_res(crc32_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_base), d_offsets,
                                   d_lengths, (uint32_t)count, d_crc));
+}
+
+static CUDPPResult shuffle_segments_api(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
+                                        const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream, bool inverse)
+{
+    // (one offset serves both bases, so equal bases are the in-place call; what else might overlap is in device memory)
+    if (!shuffle_elem_ok(elem) || count > 0xFFFFFFFFull) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_inBase || !d_outBase || d_inBase == d_outBase || !d_offsets || !d_lengths) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_res(shuffle_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase),
+                                    static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, (uint32_t)count, elem, inverse));
+}
+
+static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse)
+{
+    if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (len == 0) return CUDPP_SUCCESS;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (a < b ? b - a : a - b) < len) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_res(shuffle_device(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out),
+                                  len, elem, inverse));
+}
+
+CUDPPResult glcShuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
+                               const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream)
+{
+    return shuffle_segments_api(d_inBase, d_outBase, d_offsets, d_lengths, count, elem, stream, false);
+}
+
+CUDPPResult glcUnshuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
+                                 const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream)
+{
+    return shuffle_segments_api(d_inBase, d_outBase, d_offsets, d_lengths, count, elem, stream, true);
+}
+
+CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, false);
+}
+
+CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, true);
+}
+
+CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (elem > 1 && !shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    plan_set_container_shuffle(plan, elem > 1 ? elem : 0);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (!elem) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *elem = plan_container_shuffle(plan);
+    return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3])

@@ -76,13 +76,20 @@ uint32_t crc32_host(const void *data, size_t len, uint32_t crc = 0);     // stan
 hipError_t crc32_segments(hipStream_t st, const uint8_t *base, const unsigned long long *d_off,
                           const unsigned long long *d_len, uint32_t count, uint32_t *d_crc);
 
+// byte-plane shuffle (shuffle.hip): out[j q + i] = in[i elem + j] over the q = len / elem whole elements of a segment, the
+// last len % elem bytes in place; elem 2, 4 or 8; in and out must not overlap.  The batched form takes one offset per
+// segment for both bases.
+hipError_t shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, bool inverse);
+hipError_t shuffle_segments(hipStream_t st, const uint8_t *inBase, uint8_t *outBase, const unsigned long long *d_off,
+                            const unsigned long long *d_len, uint32_t count, uint32_t elem, bool inverse);
+
 // ---------------------------------------------------------------------------
 // layout (little-endian; every section 8-byte aligned)
 // ---------------------------------------------------------------------------
 constexpr uint32_t CT_MAGIC_STREAM = 0x42434C47u;   // "GLCB"
 constexpr uint32_t CT_MAGIC_FRAME  = 0x46434C47u;   // "GLCF"
 constexpr uint32_t CT_MAGIC_END    = 0x45434C47u;   // "GLCE"
-constexpr uint32_t CT_VERSION = 1;
+constexpr uint32_t CT_VERSION = 1, CT_VERSION_SHUFFLE = 2;   // 2: header word 3 = the shuffle's element size (2, 4, 8)
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 
@@ -125,6 +132,15 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, const unsigned char *d_in, in
 // that call may reuse once the plan's own ordering lets it)
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
+// the shuffle filter of a COMPRESS plan: the encoder's element size (0 = off), and the plan's two frame staging buffers
+// (grown on demand, never shrunk, freed with the plan; encoder: one per call parity, decoder: buffer 0)
+bool plan_pipelined(CUDPPHandle plan);
+uint32_t plan_container_shuffle(CUDPPHandle plan);
+void plan_set_container_shuffle(CUDPPHandle plan, uint32_t elem);
+hipError_t plan_stage(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
+// the plan's stream waits until the encode call that last used the next call's parity has released its input (pipelining:
+// that call's Huffman stages and container kernels read their input from the side stream)
+void plan_wait_released(CUDPPHandle plan);
 
 // ---------------------------------------------------------------------------
 // kernels of container.hip
@@ -142,8 +158,10 @@ struct CtEncFrame {                                        // device scratch of 
 };
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_t blk_len, const CtEncState *state);
-hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, uint32_t nb, uint32_t blk_len,
-                             uint8_t *out, unsigned long long cap, CtEncState *state);
+// in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
+// they differ from `in` (else null) -- the stream's crc_all is theirs
+hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
+                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state);
 hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, CtEncState *state, unsigned long long *d_len);
 
 struct CtDecFrame {                                        // device scratch of one frame's checks
@@ -155,8 +173,11 @@ struct CtDecState { uint32_t crc_all, frame_acc; unsigned long long err; };   //
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
                          unsigned long long payload_words);
 hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out);
+// fold = false: the blocks are checked but the stream's crc_all is left to ct_dec_fold (the filter's frames)
 hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                        const uint8_t *out, uint32_t frame_index, CtDecState *state);
+                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold = true);
+// the frame's nb * blk_len bytes at `bytes` (the unshuffled output) enter the stream's crc_all
+hipError_t ct_dec_fold(hipStream_t st, const CtDecFrame &f, const uint8_t *bytes, uint32_t nb, uint32_t blk_len, CtDecState *state);
 
 hipError_t ct_put_u64(hipStream_t st, unsigned long long *p, unsigned long long v);
 

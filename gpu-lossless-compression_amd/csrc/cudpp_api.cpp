@@ -83,6 +83,10 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     bool dec_released_valid[2] = {false, false};
     uint32_t dec_calls = 0;
     bool side_busy = false;                      // side-stream work issued since the last join
+    // container filter (glcPlanSetContainerShuffle): the encoder's element size and the frame staging both directions share
+    uint32_t ct_shuffle = 0;
+    void *ct_stage[2] = {nullptr, nullptr};
+    size_t ct_stage_bytes[2] = {0, 0};
     void join_side()                             // make the plan's stream wait for everything on the side stream
     {
         if (!side || !side_busy) return;
@@ -120,6 +124,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
         if (d_bwt) (void)hipFree(d_bwt);
         if (d_bwt2) (void)hipFree(d_bwt2);
         if (d_mtf) (void)hipFree(d_mtf);
+        for (auto q : ct_stage) if (q) (void)hipFree(q);
     }
 };
 
@@ -848,4 +853,33 @@ bool plan_info(CUDPPHandle planHandle, uint32_t *n, uint32_t *rows, hipStream_t 
 }
 
 void plan_join(CUDPPHandle planHandle) { plan_from<CompressPlan>(planHandle)->join_side(); }
+
+bool plan_pipelined(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->pipelined; }
+uint32_t plan_container_shuffle(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_shuffle; }
+void plan_set_container_shuffle(CUDPPHandle planHandle, uint32_t elem) { plan_from<CompressPlan>(planHandle)->ct_shuffle = elem; }
+
+hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (bytes > p->ct_stage_bytes[which]) {
+        if (p->ct_stage[which]) {                              // (growing: whatever still reads the old one finishes first)
+            p->join_side();
+            (void)hipStreamSynchronize(p->stream);
+            (void)hipFree(p->ct_stage[which]);
+            p->ct_stage[which] = nullptr; p->ct_stage_bytes[which] = 0;
+        }
+        const hipError_t e = hipMalloc(&p->ct_stage[which], bytes);
+        if (e != hipSuccess) { p->ct_stage[which] = nullptr; return e; }
+        p->ct_stage_bytes[which] = bytes;
+    }
+    *out = static_cast<uint8_t *>(p->ct_stage[which]);
+    return hipSuccess;
+}
+
+void plan_wait_released(CUDPPHandle planHandle)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    const uint32_t k = p->calls & 1u;
+    if (p->pipelined && p->released_valid[k]) (void)hipStreamWaitEvent(p->stream, p->ev_released[k], 0);
+}
 } // namespace glc

@@ -581,7 +581,8 @@ def hd_encode_device(d_in, d_lens, d_codes, cap_units=None, stream=None, work=No
 # --------------------------------------------------------------------------------------------------------------------------
 CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcContainerDecompressDevice", "glcContainerCompress",
                      "glcContainerDecompress", "glcContainerCompressFile", "glcContainerDecompressFile", "glcCrc32Segments",
-                     "glcContainerLastError"]
+                     "glcContainerLastError", "glcShuffleSegments", "glcUnshuffleSegments", "glcShuffleDevice", "glcUnshuffleDevice",
+                     "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle"]
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
 
@@ -601,6 +602,12 @@ def _ct():
             getattr(L, nm).argtypes = [sz, C.c_char_p, C.c_char_p]
         L.glcCrc32Segments.argtypes = [vp, vp, vp, sz, vp, vp]
         L.glcContainerLastError.argtypes = [sz, ullp]
+        for nm in ("glcShuffleSegments", "glcUnshuffleSegments"):
+            getattr(L, nm).argtypes = [vp, vp, vp, vp, sz, C.c_uint, vp]
+        for nm in ("glcShuffleDevice", "glcUnshuffleDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, vp]
+        L.glcPlanSetContainerShuffle.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerShuffle.argtypes = [sz, C.POINTER(C.c_uint)]
         for nm in CONTAINER_SYMBOLS[1:]:
             getattr(L, nm).restype = C.c_int
         L._ct_ready = True
@@ -678,6 +685,53 @@ def container_compress_file(plan, src, dst):
 
 def container_decompress_file(plan, src, dst):
     _chk("glcContainerDecompressFile", _ct().glcContainerDecompressFile(plan.handle, os.fsencode(src), os.fsencode(dst)))
+
+
+def container_set_shuffle(plan, elem):
+    """the byte-plane shuffle filter of the plan's container ENCODER: elem 2, 4 or 8 (format version 2), 0 or 1 = off (the
+    default: version 1).  The decoder reads the element size from the stream and ignores this setting."""
+    _chk("glcPlanSetContainerShuffle", _ct().glcPlanSetContainerShuffle(plan.handle, int(elem)))
+
+
+def container_get_shuffle(plan):
+    e = C.c_uint(0)
+    _chk("glcPlanGetContainerShuffle", _ct().glcPlanGetContainerShuffle(plan.handle, C.byref(e)))
+    return int(e.value)
+
+
+def _shuffle(fn, d_in, elem, out, stream):
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), stream))
+    return out
+
+
+def shuffle(d_in, elem, out=None, stream=None):
+    """byte-plane shuffle of a device uint8 tensor (elem 2, 4 or 8): byte j of every element gathered into plane j, the last
+    numel % elem bytes in place; into `out` (same size, not overlapping) or a new tensor.  Queued on `stream` (None = default)."""
+    return _shuffle("glcShuffleDevice", d_in, elem, out, stream)
+
+
+def unshuffle(d_in, elem, out=None, stream=None):
+    """the inverse of shuffle"""
+    return _shuffle("glcUnshuffleDevice", d_in, elem, out, stream)
+
+
+def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):
+    """shuffle (or unshuffle) the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in into the same ranges of d_out"""
+    import torch
+    dev = d_in.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    fn = "glcUnshuffleSegments" if inverse else "glcShuffleSegments"
+    _chk(fn, getattr(_ct(), fn)(d_in.data_ptr(), d_out.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), int(elem), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return d_out
 
 
 def crc32_segments(d_base, offsets, lengths, stream=None):

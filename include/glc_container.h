@@ -7,6 +7,13 @@
  * words) or would not save a quarter (4 * words >= block bytes) is stored raw.  Every block carries the CRC-32 of its bytes
  * and of its record, every frame the CRC of its tables, the stream the CRC of the whole input (CRC-32/IEEE, = zlib.crc32).
  *
+ * Typed data (float32, float64, 16-bit codes): an optional byte-plane shuffle filter, off by default.  With an element size of
+ * 2, 4 or 8 set on the encoding plan, every frame is shuffled as one segment on the device before its blocks are cut -- byte j of
+ * every element gathered into plane j -- and the stream is written as format version 2, whose header names the element size; the
+ * decoder reads it there, whatever its own plan's setting, and hands back the original bytes.  A block's CRC is then that of
+ * the shuffled block, the stream's still that of the original input.  With the filter off the container is version 1, byte for
+ * byte what it always was.  Choose rows as a multiple of the element size so that blocks and planes coincide.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -62,6 +69,26 @@ CUDPPResult glcContainerDecompressFile(CUDPPHandle plan, const char *inPath, con
  * hipStream_t; NULL = default).  Any length and byte alignment.  d_base may be NULL when the offsets are addresses. */
 CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                              size_t count, unsigned int *d_crc, void *stream);
+
+/* Byte-plane shuffle of device memory, queued on `stream` (a hipStream_t; NULL = default): with q = len / elem whole elements,
+ * out[j * q + i] = in[i * elem + j] for 0 <= j < elem, 0 <= i < q, and the last len % elem bytes copied in place; the Unshuffle
+ * forms are the inverse.  elem is 2, 4 or 8; any length and byte alignment; out of place only.  The single-segment forms
+ * refuse overlapping buffers.  The batched forms take `count` segments [base + d_offsets[i], + d_lengths[i]) with ONE offset
+ * array for both bases (offsets and lengths are device arrays); equal bases are refused, and segments must not overlap each
+ * other.  A refused call (CUDPP_ERROR_ILLEGAL_CONFIGURATION) has written nothing. */
+CUDPPResult glcShuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
+                               const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream);
+CUDPPResult glcUnshuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
+                                 const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream);
+CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
+CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
+
+/* The element size the container ENCODER of this plan shuffles by: 0 or 1 = off (the default), 2, 4, 8; anything else is
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it; the decoder
+ * ignores it (the stream header says what was done).  The first filtered call allocates device staging of one frame (rows * n
+ * bytes; two with pipelining on), the first filtered decode staging of the largest frame seen; both live as long as the plan. */
+CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem);
+CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -1,0 +1,67 @@
+/* A plain-C caller of the shuffle filter in include/glc_container.h (gcc, not hipcc): float32 samples of a smooth signal through
+ * one COMPRESS plan with the filter off and with element size 4, a device round trip of the filtered container, and
+ * glcShuffleDevice / glcUnshuffleDevice on their own.  Prints the two container lengths, the version and element-size fields of
+ * the filtered header, and whether the decoded and the unshuffled bytes equal the input. */
+#define __HIP_PLATFORM_AMD__ 1
+#include <hip/hip_runtime_api.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "glc_container.h"
+
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
+#define CR(x) do { CUDPPResult r_ = (x); if (r_ != CUDPP_SUCCESS) { fprintf(stderr, "CUDPPResult %d at line %d\n", (int)r_, __LINE__); return 3; } } while (0)
+
+int main(void)
+{
+    const size_t n = 65536, count = 9 * n / 4 + 300, len = 4 * count + 3;     /* a ragged tail that is no whole element */
+    unsigned char *h_in = (unsigned char *)malloc(len), *h_back = (unsigned char *)malloc(len), *h_shuf = (unsigned char *)malloc(len);
+    float walk = 0.0f;
+    srand(11);
+    for (size_t i = 0; i < count; i++) {
+        walk += 0.01f * (float)(rand() % 201 - 100) / 100.0f;
+        const float v = 100.0f * sinf((float)i * 0.00125f) + walk;
+        memcpy(h_in + 4 * i, &v, 4);
+    }
+    h_in[len - 3] = 1; h_in[len - 2] = 2; h_in[len - 1] = 3;
+    const unsigned long long cap = glcContainerBound(len, n);
+    unsigned char *d_in, *d_out, *d_back, *d_shuf, hdr[32];
+    unsigned long long *d_len, off_len = 0, on_len = 0, blen = 0;
+    unsigned int elem = 99;
+    CK(hipMalloc((void **)&d_in, len)); CK(hipMalloc((void **)&d_out, cap)); CK(hipMalloc((void **)&d_back, len));
+    CK(hipMalloc((void **)&d_shuf, len)); CK(hipMalloc((void **)&d_len, 8));
+    CK(hipMemcpy(d_in, h_in, len, hipMemcpyHostToDevice));
+    CUDPPHandle lib, plan;
+    CUDPPConfiguration cfg = {CUDPP_COMPRESS, CUDPP_ADD, CUDPP_UCHAR, 0, CUDPP_DEFAULT_BUCKET_MAPPER};
+    CR(cudppCreate(&lib));
+    CR(cudppPlan(lib, &plan, cfg, n, 4, 0));
+    CR(glcPlanGetContainerShuffle(plan, &elem));
+    if (elem != 0) return 4;                                    /* off by default */
+    CR(glcContainerCompressDevice(plan, d_in, len, d_out, cap, d_len));
+    CK(hipMemcpy(&off_len, d_len, 8, hipMemcpyDeviceToHost));
+    if (glcPlanSetContainerShuffle(plan, 3) != CUDPP_ERROR_ILLEGAL_CONFIGURATION) return 5;
+    CR(glcPlanSetContainerShuffle(plan, 4));
+    CR(glcContainerCompressDevice(plan, d_in, len, d_out, cap, d_len));
+    CK(hipMemcpy(&on_len, d_len, 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(hdr, d_out, 32, hipMemcpyDeviceToHost));
+    CR(glcPlanSetContainerShuffle(plan, 0));                    /* the decoder reads the element size from the stream */
+    CR(glcContainerDecompressDevice(plan, d_out, on_len, d_back, len, d_len));
+    CK(hipMemcpy(&blen, d_len, 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(h_back, d_back, len, hipMemcpyDeviceToHost));
+    const int equal = blen == len && memcmp(h_in, h_back, len) == 0;
+    CR(glcShuffleDevice(d_in, d_shuf, len, 4, NULL));
+    CR(glcUnshuffleDevice(d_shuf, d_back, len, 4, NULL));
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(h_shuf, d_shuf, len, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(h_back, d_back, len, hipMemcpyDeviceToHost));
+    int planes = 1;
+    for (size_t i = 0; i < count && planes; i++)
+        for (int j = 0; j < 4; j++) planes &= h_shuf[(size_t)j * count + i] == h_in[4 * i + j];
+    planes &= memcmp(h_shuf + 4 * count, h_in + 4 * count, 3) == 0;
+    printf("off_len=%llu on_len=%llu version=%d elem=%d decoded_len=%llu equal=%d planes=%d unshuffled=%d\n", off_len, on_len,
+           hdr[4] | (hdr[5] << 8), hdr[12], blen, equal, planes, memcmp(h_in, h_back, len) == 0);
+    CR(cudppDestroyPlan(plan));
+    CR(cudppDestroy(lib));
+    return 0;
+}

@@ -5,8 +5,15 @@
              generates it), against glcCompressBatchCompact batches chained into one array on the same plan
   decode     glcContainerDecompressDevice of that container, against glcDecompressBatchCompact of the compact array
   size       container bytes against the sum of the compact sizes
+  filter     with --shuffle ELEM: glcContainerCompressDevice / glcContainerDecompressDevice with the byte-plane shuffle filter
+             off and on (glcPlanSetContainerShuffle), alternating, on the same plan and input: ratio (input bytes / container
+             bytes) and GB/s for both settings, the plan's per-kernel profile and the sorter tiers its last frame went through
 
-python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0]"""
+--data picks the input: zipf (the default, configs[1]), or typed arrays generated on the device -- float32 (configs[3]: Philox
+N(0,1), as bench.py generates it), smooth32 / smooth64 (a sine plus a random walk) and quant16 (uint16 Laplace codes around
+512).  The comparison with the compact array needs input that shrinks: it runs for zipf only.
+
+python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM]"""
 import argparse
 import json
 import os
@@ -16,6 +23,68 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
+DATA_ELEM = {"zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2}
+
+
+def typed_on_device(torch, L, dev, kind, total):
+    """`total` bytes of typed data, generated on the device (seeded); the kinds of tests/typed_datagen.py at benchmark sizes"""
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED0010)
+    if kind == "float32":
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        assert L.glcGenFloatPhilox(out.data_ptr(), total, 0, 0x5EED0004, None) == 1
+        return out
+    if kind in ("smooth32", "smooth64"):
+        elem = DATA_ELEM[kind]
+        count = total // elem
+        x = torch.randn(count, dtype=torch.float64, device=dev, generator=g).mul_(0.01).cumsum_(0)
+        x.add_(torch.arange(count, dtype=torch.float64, device=dev).mul_(2.0 * 3.141592653589793 / 5000.0).sin_().mul_(100.0))
+        return (x if elem == 8 else x.to(torch.float32)).view(torch.uint8)
+    u = torch.rand(total // 2, dtype=torch.float32, device=dev, generator=g).sub_(0.5)
+    lap = u.sign() * torch.log1p(-2.0 * u.abs()).mul_(-6.0)
+    return (512.0 + lap).round_().clamp_(0, 65535).to(torch.int32).to(torch.int16).view(torch.uint8)
+
+
+def filter_section(torch, glc, plan, d_in, total, elem, timed):
+    """the container with the shuffle filter off and on, on one plan: sizes, rates, kernel profile and sorter tiers"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    res = {}
+
+    def enc():
+        glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+            plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr()))
+
+    for setting in (0, elem):
+        glc.container_set_shuffle(plan, setting)
+        t_enc = timed(enc)
+        clen = int(d_len.item())
+        stats = dict(flagged_general=list(plan.last_sort_stats()), retries=plan.last_sort_retries(), resumed=plan.last_sort_resumed(),
+                     periodic=plan.last_sort_periodic(), chains=list(plan.last_sort_chains()), skipped=plan.last_sort_skipped())
+        out.zero_()
+        t_dec = timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+        assert torch.equal(out, d_in) and int(d_len.item()) == total
+        plan.enable_timing(3)                                  # one more pass of each for the per-kernel profile
+        enc()
+        plan.synchronize()
+        prof_enc = plan.kernel_profiles()
+        plan.enable_timing(3)
+        glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr()))
+        plan.synchronize()
+        prof_dec = plan.kernel_profiles()
+        plan.enable_timing(0)
+        res["off" if not setting else "elem%d" % setting] = {
+            "container_bytes": clen, "ratio": total / clen, "encode_GBps": total / t_enc / 1e9, "decode_GBps": total / t_dec / 1e9,
+            "last_frame_sort": stats,
+            "encode_kernels_ms": {k: round(v["ms"], 3) for k, v in sorted(prof_enc.items(), key=lambda kv: -kv[1]["ms"])},
+            "decode_kernels_ms": {k: round(v["ms"], 3) for k, v in sorted(prof_dec.items(), key=lambda kv: -kv[1]["ms"])}}
+    glc.container_set_shuffle(plan, 0)
+    return res
 
 
 def main():
@@ -24,6 +93,8 @@ def main():
     ap.add_argument("--rows", type=int, default=2048)
     ap.add_argument("--iters", type=int, default=2)
     ap.add_argument("--pipelining", type=int, default=1)
+    ap.add_argument("--data", choices=sorted(DATA_ELEM), default="zipf")
+    ap.add_argument("--shuffle", type=int, default=0, choices=[0, 2, 4, 8], metavar="ELEM")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -39,9 +110,12 @@ def main():
     n = MiB
     nblocks = int(args.gib * 1024)
     total = nblocks * n
-    d_in = torch.empty(total, dtype=torch.uint8, device=dev)
-    thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
-    assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+    if args.data == "zipf":
+        d_in = torch.empty(total, dtype=torch.uint8, device=dev)
+        thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
+        assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+    else:
+        d_in = typed_on_device(torch, L, dev, args.data, total)
     torch.cuda.synchronize()
 
     def timed(fn):
@@ -55,7 +129,14 @@ def main():
             best = min(best, time.perf_counter() - t)
         return best
 
-    res = {"workload": "configs[1]: %d x 1 MiB Philox Zipf(1.0) blocks, plan rows %d, pipelining %s" % (nblocks, args.rows, bool(args.pipelining))}
+    res = {"workload": "%s: %d x 1 MiB blocks, plan rows %d, pipelining %s"
+                       % ("configs[1] Philox Zipf(1.0)" if args.data == "zipf" else args.data, nblocks, args.rows, bool(args.pipelining))}
+    if args.data != "zipf":
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed)
+        print(json.dumps(res))
+        return
     # --- CRC against the read probe
     off = torch.zeros(1, dtype=torch.int64, device=dev)
     ln = torch.full((1,), total, dtype=torch.int64, device=dev)
@@ -113,6 +194,9 @@ def main():
         t_cdec = timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
             plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
         assert torch.equal(out, d_in) and int(d_len.item()) == total
+        if args.shuffle:
+            del compact, out
+            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle, timed)
     res.update({"compact_encode_GBps": total / t_enc / 1e9, "container_encode_GBps": total / t_cenc / 1e9,
                 "encode_ratio": t_enc / t_cenc,
                 "compact_decode_GBps": total / t_dec / 1e9, "container_decode_GBps": total / t_cdec / 1e9,

@@ -1,0 +1,111 @@
+"""The byte-plane shuffle kernels alone against a device-to-device copy of the same bytes, in one process and interleaved:
+
+  copy       hipMemcpyAsync, device to device, of the buffer: one read and one write per byte, the yardstick
+  shuffle N  glcShuffleDevice with element size N = 2, 4, 8 on the same buffers
+  unshuf N   glcUnshuffleDevice
+
+Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each run is bracketed by device events.  The
+table gives the median, the fastest and the slowest run of every variant, as GB/s of input bytes (the traffic is twice that)
+and relative to the copy's median.  The buffer (--gib, default 1) is larger than the 256 MiB Infinity Cache on purpose.
+--offset A B misaligns source and destination by A and B bytes.  One JSON line on stdout, the table on stderr or in --md FILE.
+
+python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--md FILE]"""
+import argparse
+import ctypes as C
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def hip_runtime():
+    """the HIP runtime this process already has loaded (torch's and the library's are one and the same object)"""
+    for line in open("/proc/self/maps"):
+        path = line.split()[-1]
+        if "libamdhip64" in os.path.basename(path):
+            return C.CDLL(path)
+    raise RuntimeError("no HIP runtime is loaded")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--offset", type=int, nargs=2, default=[0, 0])
+    ap.add_argument("--md", default=None)
+    args = ap.parse_args()
+    assert args.reps >= 20, "at least 20 timed repetitions"
+    import torch
+
+    spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
+    glc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(glc)
+    L = glc._ct()
+    dev = torch.device("cuda:0")
+    n = int(args.gib * (1 << 30))
+    so, do = args.offset
+    src_buf = torch.randint(0, 256, (n + 256,), dtype=torch.uint8, device=dev)
+    dst_buf = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+    src, dst = src_buf[so:so + n], dst_buf[do:do + n]
+    hip = hip_runtime()
+    hip.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    hip.hipMemcpyAsync.restype = C.c_int
+    D2D = 3                                                    # hipMemcpyDeviceToDevice
+
+    def copy():
+        assert hip.hipMemcpyAsync(dst.data_ptr(), src.data_ptr(), n, D2D, None) == 0
+
+    def kernel(fn, elem):
+        return lambda: glc._chk("shuffle", fn(src.data_ptr(), dst.data_ptr(), n, elem, None))
+
+    variants = [("copy", copy)]
+    for elem in (2, 4, 8):
+        variants.append(("shuffle %d" % elem, kernel(L.glcShuffleDevice, elem)))
+        variants.append(("unshuf %d" % elem, kernel(L.glcUnshuffleDevice, elem)))
+    # correctness of what is timed, once, at this size and alignment
+    for elem in (2, 4, 8):
+        kernel(L.glcShuffleDevice, elem)()
+        q = n // elem
+        want = src[:q * elem].view(q, elem).t().contiguous().view(-1)
+        assert torch.equal(dst[:q * elem], want) and torch.equal(dst[q * elem:], src[q * elem:]), elem
+        back = torch.empty_like(src)
+        glc._chk("unshuffle", L.glcUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, None))
+        assert torch.equal(back, src), elem
+        del back, want
+    times = {name: [] for name, _ in variants}
+    events = []
+    for r in range(args.warmup + args.reps):
+        for name, fn in variants:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            if r >= args.warmup:
+                events.append((name, e0, e1))
+    torch.cuda.synchronize()
+    for name, e0, e1 in events:
+        times[name].append(e0.elapsed_time(e1) * 1e-3)
+    base = statistics.median(times["copy"])
+    res = {"bytes": n, "reps": args.reps, "offset": [so, do], "variants": {}}
+    rows = ["| variant | median GB/s | fastest | slowest | time / copy |", "|---|---|---|---|---|"]
+    for name, _ in variants:
+        t = sorted(times[name])
+        med = statistics.median(t)
+        res["variants"][name] = {"median_ms": med * 1e3, "min_ms": t[0] * 1e3, "max_ms": t[-1] * 1e3,
+                                 "median_GBps": n / med / 1e9, "vs_copy": med / base}
+        rows.append("| %s | %.0f | %.0f | %.0f | %.2f |" % (name, n / med / 1e9, n / t[0] / 1e9, n / t[-1] / 1e9, med / base))
+    table = "\n".join(rows) + "\n"
+    if args.md:
+        with open(args.md, "w") as f:
+            f.write(table)
+    else:
+        sys.stderr.write(table)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
