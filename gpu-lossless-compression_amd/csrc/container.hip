@@ -201,6 +201,28 @@ __global__ __launch_bounds__(256) void k_ct_kind(CtEncFrame f, uint32_t nb, uint
     }
 }
 
+// the order-0 codec's kinds (one thread per block), from the units each block's table asks for: raw when 4 * words >=
+// blk_len.  f.only becomes the batched encoder's skip mask.
+__global__ __launch_bounds__(256) void k_ct_kind0(CtEncFrame f, CtEncHuff0 h, uint32_t nb, uint32_t blk_len,
+                                                  unsigned long long table_bytes, const CtEncState *state)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
+    if (b >= nb) return;
+    const unsigned long long words = h.nun[b];
+    const bool raw = 4ull * words >= blk_len;
+    f.kind[b] = raw ? CT_KIND_RAW : CT_KIND_HUFF0;
+    f.only[b] = raw ? 1u : 0u;
+    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
+    f.bwt[b] = 0;
+}
+
+__global__ __launch_bounds__(256) void k_ct_block_offsets(unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len)
+{
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b < nb) { off[b] = (unsigned long long)b * blk_len; len[b] = blk_len; }
+}
+
 // a raw block's record: its bytes, zero-padded to a whole word (skipped when it would pass the capacity)
 __global__ __launch_bounds__(256) void k_ct_raw_records(const uint8_t *__restrict__ in, uint32_t blk_len, const uint32_t *__restrict__ kind,
                                                         const unsigned long long *__restrict__ boff, uint8_t *out,
@@ -266,7 +288,8 @@ __global__ __launch_bounds__(256) void k_ct_tables(CtEncFrame f, uint32_t nb, ui
         reinterpret_cast<unsigned long long *>(W + T.pay_off)[b] = f.boff[b] - f.boff[0];
     }
     for (uint32_t i = tid; i < 256; i += 256) W[T.hist + (size_t)b * 256 + i] = raw ? 0u : f.hist[(size_t)b * 256 + i];
-    for (uint32_t i = tid; i < T.nsub; i += 256) W[T.enc_off + (size_t)b * T.nsub + i] = raw ? 0u : f.enc_off[(size_t)b * T.nsub + i];
+    const bool bwt = f.kind[b] == CT_KIND_HUFF;                // (an order-0 record has no sub-block offsets)
+    for (uint32_t i = tid; i < T.nsub; i += 256) W[T.enc_off + (size_t)b * T.nsub + i] = bwt ? f.enc_off[(size_t)b * T.nsub + i] : 0u;
     if (b == 0 && tid == 0) {
         H[0] = CT_MAGIC_FRAME; H[1] = nb; H[2] = blk_len; H[3] = 0;
         H[4] = (uint32_t)P; H[5] = (uint32_t)(P >> 32); H[6] = 0; H[7] = 0;
@@ -317,6 +340,19 @@ hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_
     return hipGetLastError();
 }
 
+hipError_t ct_enc_kind0(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, uint32_t nb, uint32_t blk_len, const CtEncState *state)
+{
+    const CtTables T = ct_tables(nb, blk_len);
+    hipLaunchKernelGGL(k_ct_kind0, dim3((nb + 255) / 256), dim3(256), 0, st, f, h, nb, blk_len, 4 * T.words, state);
+    return hipGetLastError();
+}
+
+hipError_t ct_block_offsets(hipStream_t st, unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len)
+{
+    hipLaunchKernelGGL(k_ct_block_offsets, dim3((nb + 255) / 256), dim3(256), 0, st, off, len, nb, blk_len);
+    return hipGetLastError();
+}
+
 // blocks of blk_len bytes from `bytes` on as CRC segments [0, nb)
 __global__ __launch_bounds__(256) void k_ct_block_segs(unsigned long long *seg_off, unsigned long long *seg_len, const uint8_t *bytes,
                                                        uint32_t nb, uint32_t blk_len)
@@ -360,7 +396,7 @@ hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, 
 // tables themselves are unverified until k_cd_verdict, so everything read from them is clamped first
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                 unsigned long long P)
+                                                 unsigned long long P, uint32_t *skip0)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *W = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR);
@@ -369,6 +405,7 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b == 0) { f.verdict[0] = 0; f.verdict[1] = ~0ull; }
     if (b < nb) {
+        if (skip0) skip0[b] = W[T.kind + b] == CT_KIND_HUFF0 ? 0u : 1u;    // (version 3: whose tables are built next)
         const unsigned long long lo = po[b], hi = po[b + 1];
         const bool ok = lo <= hi && hi <= P;
         f.seg_off[b] = (unsigned long long)(uintptr_t)pay + (ok ? 4 * lo : 0);
@@ -380,8 +417,9 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     }
 }
 
+// nun0 (version 3, else null): the units the histogram of each kind-2 block asks for
 __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                    unsigned long long P)
+                                                    unsigned long long P, const unsigned long long *nun0)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *H = reinterpret_cast<const uint32_t *>(frame);
@@ -393,11 +431,20 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
     const uint32_t kind = W[T.kind + b];
     reinterpret_cast<uint32_t *>(f.verdict + 2)[b] = kind;
     const unsigned long long lo = po[b], hi = po[b + 1];
-    bool bad = kind > CT_KIND_RAW || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
+    bool bad = kind > (nun0 ? CT_KIND_HUFF0 : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
     if (!bad) {
         const unsigned long long w = hi - lo;
         if (kind == CT_KIND_RAW) bad = w != ct_raw_words(blk_len);
-        else {
+        else if (kind == CT_KIND_HUFF0) {
+            // an order-0 record: the counts are the block's, nothing else is set, and the record has exactly the units the
+            // table of those counts asks for -- so decoding blk_len symbols consumes it exactly
+            unsigned long long sum = 0;
+            const uint32_t *h = W + T.hist + 256ull * b;
+            for (uint32_t s = 0; s < 256; s++) sum += h[s];
+            bad = W[T.bwt + b] != 0 || sum != blk_len || w != nun0[b];
+            const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
+            for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] != 0;
+        } else {
             bad = W[T.bwt + b] >= blk_len || w > (unsigned long long)T.nsub * (HUFF_MAX_WORDS + 1);
             const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
             for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] >= w || (s > 0 && eo[s] <= eo[s - 1]);
@@ -442,12 +489,22 @@ __global__ void k_cd_end(uint32_t nb, uint32_t blk_len, CtDecState *state)
 }
 
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                         unsigned long long payload_words)
+                         unsigned long long payload_words, const CtDecHuff0 *h0, KernelProf *prof)
 {
-    hipLaunchKernelGGL(k_cd_segs, dim3((nb + 2 + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words);
-    hipError_t e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb + 2, f.crc);
+    hipLaunchKernelGGL(k_cd_segs, dim3((nb + 2 + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
+                       h0 ? h0->skip : nullptr);
+    hipError_t e = hipSuccess;
+    if (h0) {
+        const CtTables T = ct_tables(nb, blk_len);
+        uint32_t *hist = const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR) + T.hist);   // (read only)
+        const HdbSegs g{nullptr, nullptr, nullptr, nb, blk_len};
+        e = hdb_tables(st, g, false, hist, nullptr, nullptr, h0->lut, h0->nun, h0->skip, prof);
+        if (e != hipSuccess) return e;
+    }
+    e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb + 2, f.crc);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cd_verdict, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words);
+    hipLaunchKernelGGL(k_cd_verdict, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
+                       h0 ? (const unsigned long long *)h0->nun : nullptr);
     return hipGetLastError();
 }
 

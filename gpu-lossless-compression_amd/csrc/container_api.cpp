@@ -8,6 +8,10 @@
 // The shuffle filter (format version 2, shuffle.hip): with an element size set on the plan the encoder shuffles each frame as one
 // segment into staging kept with the plan and encodes from there; the decoder decodes a version-2 frame into staging, checks its
 // blocks there and unshuffles it into the output.  crc_all is taken over the original bytes on both sides.
+// The order-0 codec (format version 3, hd_batch.hip): with GLC_CONTAINER_CODEC_HUFF0 set on the plan a frame does not go through
+// the plan's compress call at all: batched histograms and tables give every block's record size, the same kind / offset / raw /
+// CRC / table kernels follow, and the batched encoder writes the kind-2 records straight into the container, all on the plan's
+// stream.  The decoder accepts kinds 0, 1 and 2 in a version-3 frame and sends runs of kind 2 to the batched decoder.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 
@@ -80,10 +84,11 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 
 bool shuffle_elem_ok(uint32_t elem) { return elem == 2 || elem == 4 || elem == 8; }
 
-// elem: the shuffle's element size, 0 = no filter (version 1, as ever)
-void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem)
+// elem: the shuffle's element size, 0 = no filter (version 1, as ever); codec: CT_CODEC_HUFF0 writes version 3
+void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem, uint32_t codec)
 {
-    h[0] = CT_MAGIC_STREAM; h[1] = elem ? CT_VERSION_SHUFFLE : CT_VERSION; h[2] = block_len; h[3] = elem;
+    h[0] = CT_MAGIC_STREAM; h[1] = codec == CT_CODEC_HUFF0 ? CT_VERSION_CODEC : (elem ? CT_VERSION_SHUFFLE : CT_VERSION);
+    h[2] = block_len; h[3] = elem;
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
     h[6] = crc32_host(h, 24); h[7] = 0;
 }
@@ -99,11 +104,26 @@ struct Encoder {
     unsigned long long *d_len = nullptr;
     CtEncFrame fr[2] = {};
     uint32_t elem = 0;                                        // the plan's shuffle filter (0 = off)
+    uint32_t codec = CT_CODEC_BWT;                            // the plan's container codec
+    CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     hipError_t init()
     {
         elem = plan_container_shuffle(P.h);
+        codec = plan_container_codec(P.h);
+        if (codec == CT_CODEC_HUFF0) {
+            const size_t R = P.rows, wb = hdb_encode_work_bytes(R);
+            uint8_t *q = nullptr;
+            const hipError_t e = plan_codec_scratch(P.h, 0, 24 * R + 256 * R + 512 * R + 256 + wb, &q);
+            if (e != hipSuccess) return e;
+            h0.nun = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
+            h0.in_off = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
+            h0.in_len = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
+            h0.codes = reinterpret_cast<uint16_t *>(q); q += 512 * R;
+            h0.lens = q; q += 256 * R;
+            h0.work = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(q) + 255) & ~(uintptr_t)255);
+        }
         if (elem) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) {
@@ -155,6 +175,7 @@ struct Encoder {
             orig = d_in;
             d_in = stage[P.parity];
         }
+        if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
         hk.status = status;
@@ -163,6 +184,26 @@ struct Encoder {
         hk.after_pack = [&](hipStream_t s2) { return ct_enc_after_pack(s2, f, d_in, orig, nb, blk_len, out, cap, state); };
         return plan_compress_hooked(P.h, d_in, f.bwt, f.hist, f.enc_off, nsub, f.size, reinterpret_cast<unsigned int *>(out),
                                     (size_t)(cap / 4), f.boff, f.start, blk_len, nb, hk);
+    }
+
+    // the order-0 codec's frame, wholly on the plan's stream: tables (and with them every record's size) -> kinds -> payload
+    // offsets -> the batched encoder, then the same stage behind the packer as ever
+    CUDPPResult frame_huff0(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
+                            uint8_t *out, unsigned long long cap)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        plan_stage_mark(P.h, 0);
+        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));   // (the blocks as segments of the frame)
+        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
+        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_kind0(P.st, f, h0, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
+        CT_TRY(hdb_encode(P.st, g, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4, f.only, h0.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
     }
 
     // every frame of [d_in, + len) with the plan's n and rows, starting at input byte `done` of the whole stream
@@ -195,6 +236,26 @@ struct Decoder {
     CtDecState *state = nullptr;
     unsigned long long *h_verdict = nullptr;                  // pinned
     uint32_t elem = 0;                                        // the stream header's shuffle filter (0 = none)
+    uint32_t version = CT_VERSION;                            // the stream header's
+    CtDecHuff0 h0 = {};
+
+    // a version-3 frame's scratch, kept with the plan: tables for nb blocks, span-function prefixes for `chunk` of them at a
+    // time (at most the plan's rows, and at most 256 MiB of prefixes)
+    hipError_t reserve_huff0(uint32_t nb, uint32_t blk_len)
+    {
+        const size_t per = hdb_decode_work_bytes(1, blk_len) + 512;
+        const size_t chunk = std::min<size_t>(std::min<size_t>(P.rows, nb), std::max<size_t>(1, ((size_t)256 << 20) / per));
+        const size_t wb = hdb_decode_work_bytes(chunk, blk_len), n4 = ((size_t)nb + 63) & ~(size_t)63;
+        uint8_t *q = nullptr;
+        const hipError_t e = plan_codec_scratch(P.h, 1, 8 * n4 + 4 * n4 + 4096 * (size_t)nb + 256 + wb, &q);
+        if (e != hipSuccess) return e;
+        h0.nun = reinterpret_cast<unsigned long long *>(q); q += 8 * n4;
+        h0.skip = reinterpret_cast<uint32_t *>(q); q += 4 * n4;
+        h0.lut = reinterpret_cast<uint16_t *>(q); q += 4096 * (size_t)nb;
+        h0.work = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(q) + 255) & ~(uintptr_t)255);
+        h0.chunk = (uint32_t)chunk;
+        return hipSuccess;
+    }
 
     ~Decoder()
     {
@@ -236,7 +297,10 @@ struct Decoder {
         CT_TRY(reserve(nb));
         uint8_t *out = final_out;
         if (elem) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
-        CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw));
+        const bool v3 = version == CT_VERSION_CODEC;
+        KernelProf *prof = plan_prof(P.h);
+        if (v3) CT_TRY(reserve_huff0(nb, blk_len));
+        CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw, v3 ? &h0 : nullptr, prof));
         CT_TRY(hipMemcpyAsync(h_verdict, f.verdict, 8 * (2 + (nb + 1) / 2), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
         if (h_verdict[0]) return fail(P.h, CT_FRAME_TABLE, fi);
@@ -255,6 +319,16 @@ struct Decoder {
                 T.nsub, pay, pw, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, out + (size_t)a * blk_len,
                 blk_len, b - a);
             if (r != CUDPP_SUCCESS) return r;
+            a = b;
+        }
+        for (uint32_t a = 0; v3 && a < nb;) {                   // runs of order-0 blocks, a chunk of the plan's rows at a time
+            if (kind[a] != CT_KIND_HUFF0) { a++; continue; }
+            uint32_t b = a;
+            while (b < nb && kind[b] == CT_KIND_HUFF0 && b - a < h0.chunk) b++;
+            // (k_cd_raw has put every block's output range into f.seg_*: absolute addresses, so the base is null)
+            const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, b - a, blk_len};
+            CT_TRY(hdb_decode(P.st, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, h0.nun + a,
+                              h0.lut + 2048ull * a, g, nullptr, h0.work, prof));
             a = b;
         }
         plan_join(P.h);
@@ -278,12 +352,14 @@ struct Decoder {
     }
 };
 
-// the checks on a stream header; returns block_len (0 = refused) and the shuffle's element size (0 = version 1, no filter)
-uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem)
+// the checks on a stream header; returns block_len (0 = refused), the shuffle's element size (0 = no filter) and the version
+uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem, uint32_t *version)
 {
     if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
-    if (!(h[1] == CT_VERSION && h[3] == 0) && !(h[1] == CT_VERSION_SHUFFLE && shuffle_elem_ok(h[3]))) return 0;
+    if (!(h[1] == CT_VERSION && h[3] == 0) && !(h[1] == CT_VERSION_SHUFFLE && shuffle_elem_ok(h[3])) &&
+        !(h[1] == CT_VERSION_CODEC && (h[3] == 0 || shuffle_elem_ok(h[3])))) return 0;
     *elem = h[3];
+    *version = h[1];
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return 0;
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
     return h[2];
@@ -379,7 +455,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     CT_TRY(dout.reserve(ocap));
     CT_TRY(hout.reserve(ocap));
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem);
+    make_header(hdr, E.P.n, len, E.elem, E.codec);
     if (!out.write(hdr, CT_HDR)) return fail(plan, CT_CAPACITY);
     unsigned long long total = CT_HDR;
     hipStream_t cs = nullptr;
@@ -443,7 +519,7 @@ CUDPPResult decompress_stream(CUDPPHandle plan, Source &src, unsigned long long 
     if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
     if (!src.read(hdr, CT_HDR)) return fail(plan, CT_TRUNCATED);
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -503,7 +579,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(E.init());
     uint8_t *out = static_cast<uint8_t *>(d_out);
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem);
+    make_header(hdr, E.P.n, len, E.elem, E.codec);
     CT_TRY(ct_enc_header(E.P.st, out, cap, hdr, E.state));
     CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap, [](unsigned long long) { return CUDPP_SUCCESS; });
     if (r != CUDPP_SUCCESS) return r;
@@ -530,7 +606,7 @@ CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, uns
     CT_TRY(hipMemcpyAsync(hdr, in, CT_HDR, hipMemcpyDeviceToHost, D.P.st));
     CT_TRY(hipStreamSynchronize(D.P.st));
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap || (total && !d_out)) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -673,6 +749,24 @@ CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
     if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
     if (elem > 1 && !shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     plan_set_container_shuffle(plan, elem > 1 ? elem : 0);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    plan_set_container_codec(plan, codec);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *codec = plan_container_codec(plan);
     return CUDPP_SUCCESS;
 }
 

@@ -90,8 +90,11 @@ constexpr uint32_t CT_MAGIC_STREAM = 0x42434C47u;   // "GLCB"
 constexpr uint32_t CT_MAGIC_FRAME  = 0x46434C47u;   // "GLCF"
 constexpr uint32_t CT_MAGIC_END    = 0x45434C47u;   // "GLCE"
 constexpr uint32_t CT_VERSION = 1, CT_VERSION_SHUFFLE = 2;   // 2: header word 3 = the shuffle's element size (2, 4, 8)
+constexpr uint32_t CT_VERSION_CODEC = 3;                     // 3: kind 2 is legal; header word 3 = element size or 0 (no filter)
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
+constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), version 3 only
+constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
 
 // failure classes of glcContainerLastError (out[0])
 enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
@@ -141,6 +144,15 @@ hipError_t plan_stage(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **
 // the plan's stream waits until the encode call that last used the next call's parity has released its input (pipelining:
 // that call's Huffman stages and container kernels read their input from the side stream)
 void plan_wait_released(CUDPPHandle plan);
+// the container codec of a COMPRESS plan's encoder (CT_CODEC_*), and what the order-0 codec keeps with the plan: device
+// scratch (which = 0 the encoder's, 1 the decoder's; grown on demand, never shrunk, freed with the plan, never allocated
+// by a plan that only uses the BWT codec), the plan's live kernel profile, and its stage events (i = 0 .. 3: the marks of
+// glcPlanLastTiming's four spans, recorded on the plan's stream; a no-op while timing is off)
+uint32_t plan_container_codec(CUDPPHandle plan);
+void plan_set_container_codec(CUDPPHandle plan, uint32_t codec);
+hipError_t plan_codec_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
+KernelProf *plan_prof(CUDPPHandle plan);
+void plan_stage_mark(CUDPPHandle plan, int i);
 
 // ---------------------------------------------------------------------------
 // kernels of container.hip
@@ -156,7 +168,17 @@ struct CtEncFrame {                                        // device scratch of 
     unsigned long long *boff, *seg_off, *seg_len, *start;  // boff: nb + 1 absolute word offsets; segs: 2 nb + 2
     uint32_t *tcrc;                                        // [2]
 };
+struct CtEncHuff0 {                                        // device scratch of the order-0 codec's frame (plan_codec_scratch 0)
+    unsigned long long *nun, *in_off, *in_len;             // [rows] units of each block's stream; the blocks as segments of the frame
+    uint8_t *lens;                                         // [rows][256]
+    uint16_t *codes;                                       // [rows][256]
+    void *work;                                            // hdb_encode_work_bytes(rows)
+};
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
+// the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
+// mask (1 = raw) and f.bwt zeros
+hipError_t ct_block_offsets(hipStream_t st, unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len);   // off[b] = b * blk_len
+hipError_t ct_enc_kind0(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
@@ -170,8 +192,17 @@ struct CtDecFrame {                                        // device scratch of 
     unsigned long long *verdict;                           // [2 + ceil(nb / 2)]: table verdict, block verdict, kinds (u32)
 };
 struct CtDecState { uint32_t crc_all, frame_acc; unsigned long long err; };   // err: (frame << 32 | block) + 1 of the first decoded-CRC miss
+struct CtDecHuff0 {                                        // device scratch of a version-3 frame (plan_codec_scratch 1)
+    uint32_t *skip;                                        // [nb] 1 = not kind 2
+    unsigned long long *nun;                               // [nb] units the block's hist asks for (kind 2)
+    uint16_t *lut;                                         // [nb][2048]
+    void *work;                                            // hdb_decode_work_bytes(chunk, blk_len)
+    uint32_t chunk;                                        // blocks one hdb_decode call may take
+};
+// h0 (version 3, else null): kind 2 is legal; its blocks' tables are built from the unverified histograms first, and the
+// units they ask for are one of the block's field checks
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                         unsigned long long payload_words);
+                         unsigned long long payload_words, const CtDecHuff0 *h0 = nullptr, KernelProf *prof = nullptr);
 hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out);
 // fold = false: the blocks are checked but the stream's crc_all is left to ct_dec_fold (the filter's frames)
 hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,

@@ -87,6 +87,10 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     uint32_t ct_shuffle = 0;
     void *ct_stage[2] = {nullptr, nullptr};
     size_t ct_stage_bytes[2] = {0, 0};
+    // container codec (glcPlanSetContainerCodec) and the order-0 codec's scratch: [0] the encoder's, [1] the decoder's
+    uint32_t ct_codec = 0;
+    void *ct_codec_mem[2] = {nullptr, nullptr};
+    size_t ct_codec_bytes[2] = {0, 0};
     void join_side()                             // make the plan's stream wait for everything on the side stream
     {
         if (!side || !side_busy) return;
@@ -125,6 +129,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
         if (d_bwt2) (void)hipFree(d_bwt2);
         if (d_mtf) (void)hipFree(d_mtf);
         for (auto q : ct_stage) if (q) (void)hipFree(q);
+        for (auto q : ct_codec_mem) if (q) (void)hipFree(q);
     }
 };
 
@@ -874,6 +879,39 @@ hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint
     }
     *out = static_cast<uint8_t *>(p->ct_stage[which]);
     return hipSuccess;
+}
+
+uint32_t plan_container_codec(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_codec; }
+void plan_set_container_codec(CUDPPHandle planHandle, uint32_t codec) { plan_from<CompressPlan>(planHandle)->ct_codec = codec; }
+
+hipError_t plan_codec_scratch(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (bytes > p->ct_codec_bytes[which]) {
+        if (p->ct_codec_mem[which]) {                          // (growing: whatever still uses the old one finishes first)
+            p->join_side();
+            (void)hipStreamSynchronize(p->stream);
+            (void)hipFree(p->ct_codec_mem[which]);
+            p->ct_codec_mem[which] = nullptr; p->ct_codec_bytes[which] = 0;
+        }
+        const hipError_t e = hipMalloc(&p->ct_codec_mem[which], bytes);
+        if (e != hipSuccess) { p->ct_codec_mem[which] = nullptr; return e; }
+        p->ct_codec_bytes[which] = bytes;
+    }
+    *out = static_cast<uint8_t *>(p->ct_codec_mem[which]);
+    return hipSuccess;
+}
+
+KernelProf *plan_prof(CUDPPHandle planHandle) { return &plan_from<CompressPlan>(planHandle)->prof; }
+
+void plan_stage_mark(CUDPPHandle planHandle, int i)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (!p->timing) return;
+    StageTimer tm(p);
+    tm.mark(i);
+    if (i == 1 && p->pipelined && p->ev_s2) (void)hipEventRecord(p->ev_s2, p->stream);   // (glcPlanSynchronize reads the second span from it)
+    if (i == 3) tm.done();
 }
 
 void plan_wait_released(CUDPPHandle planHandle)

@@ -69,6 +69,8 @@ enum ProfSlot { PROF_FS_PART = 0, PROF_FS_SORT, PROF_MTF_ENCODE, PROF_HUFF_PACK,
                 PROF_MTF_LISTS, PROF_HUFF_BUILD,
                 // decoder (decode.hip)
                 PROF_DEC_HUFF, PROF_IMTF_POS, PROF_IMTF_REST, PROF_IBWT_LF, PROF_IBWT_WALK, PROF_IBWT_EMIT,
+                // batched order-0 Huffman (hd_batch.hip): the container's HUFF0 codec
+                PROF_HDB_HIST, PROF_HDB_TABLE, PROF_HDB_COUNT, PROF_HDB_SCAN, PROF_HDB_PACK, PROF_HDB_SPANS, PROF_HDB_EMIT,
                 PROF_NSLOT };
 struct KernelProf {
     static constexpr int NPAIR = 4096;
@@ -76,7 +78,9 @@ struct KernelProf {
     const char *name[PROF_NSLOT] = {"k_fs_part", "k_fs_sort", "k_mtf_encode", "k_huff_pack", "k_rs_onesweep<8,false>",
                                     "k_fs_hist", "k_mtf_chunk_lists+k_mtf_scan_lists", "k_huff_build",
                                     "k_dec_prepare+k_dec_huff", "k_imtf_pos", "k_imtf_scan+k_imtf_apply",
-                                    "k_ibwt_hist+k_rs_scan+k_ibwt_lf", "k_ibwt_walk", "k_ibwt_rank+k_ibwt_emit"};
+                                    "k_ibwt_hist+k_rs_scan+k_ibwt_lf", "k_ibwt_walk", "k_ibwt_rank+k_ibwt_emit",
+                                    "k_hdb_hist", "k_hdb_table", "k_hdb_enc_count", "k_hdb_enc_scan", "k_hdb_enc_pack",
+                                    "k_hdb_span_functions", "k_hdb_emit"};
     double     ms[PROF_NSLOT] = {}, units[PROF_NSLOT] = {};
     long       launches[PROF_NSLOT] = {};
     // event pairs and what they bracket: allocated when profiling is switched on (a plan that never profiles carries
@@ -364,6 +368,36 @@ hipError_t compact_streams(hipStream_t st, const uint32_t *d_comp, size_t stride
 
 hipError_t expand_streams(hipStream_t st, const uint32_t *d_in, const unsigned long long *d_off, uint32_t nblk,
                           uint32_t *d_comp, size_t stride, uint32_t *d_sizes, uint32_t *d_status);
+
+// ---------------------------------------------------------------------------
+// batched order-0 Huffman (hd_batch.hip; the public form is glcHdSegments* in include/glc_hd.h): one table per segment,
+// thousands of segments per launch.  Segment i is [base + off[i], + min(len[i], max_len)), max_len <= HDB_MAX_LEN, any
+// byte alignment; off / len are device arrays.  Everything only enqueues on `st`.  skip (optional): segments whose entry
+// is non-zero are left alone.  prof (optional): the live per-kernel profile the launches are bracketed for.
+// ---------------------------------------------------------------------------
+constexpr uint32_t HDB_MAX_LEN = 1u << 20;
+struct HdbSegs { const uint8_t *base; const unsigned long long *off, *len; uint32_t count, max_len; };
+// segment i's bytes: base may be null with absolute addresses in off, so the sum is taken on integers
+__host__ __device__ inline const uint8_t *hdb_seg(const HdbSegs &g, uint32_t i) { return reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(g.base) + g.off[i]); }
+struct HdbOut { uint8_t *base; const unsigned long long *off, *len; uint32_t count, max_len; };   // the decoder's side: written
+constexpr size_t HDB_MAX_COUNT = (size_t)1 << 22;            // segments per call: one workgroup of up to 512 lanes each, grid.x * 512 < 2^32
+size_t hdb_encode_work_bytes(size_t count);
+size_t hdb_decode_work_bytes(size_t count, size_t max_len);          // (without the tables: 4096 bytes of LUT per segment)
+// hist[i][256] (u32) = the segment's byte counts (make_hist; else hist is the input and g.base / g.off / g.len are not
+// read); from it the table glcHdBuildTable gives -- lens[i][256], codes[i][256], lut[i][2048] (the decode kernels' u16
+// form), each optional -- and nunits[i] = ceil(sum hist * lens / 32) + 1, the units of the segment's stream, pad included
+hipError_t hdb_tables(hipStream_t st, const HdbSegs &g, bool make_hist, uint32_t *hist, uint8_t *lens, uint16_t *codes,
+                      uint16_t *lut, unsigned long long *nunits, const uint32_t *skip, KernelProf *prof);
+// segment i's stream, word for word glcHdEncodeHost's, at units_base + unit_off[i]; a segment whose nunits[i] units would
+// end past cap_units (counted from units_base), or whose bytes no longer give nunits[i], is not written at all
+hipError_t hdb_encode(hipStream_t st, const HdbSegs &g, const uint8_t *lens, const uint16_t *codes,
+                      const unsigned long long *nunits, uint32_t *units_base, const unsigned long long *unit_off,
+                      unsigned long long cap_units, const uint32_t *skip, void *work, KernelProf *prof);
+// g.len[i] symbols of the stream of nunits[i] units at units_base + unit_off[i] to g.base + g.off[i] (g.base may be null with addresses in g.off),
+// with the tables in lut.  Reads stay inside the stream's units, writes inside the segment, whatever the units hold.
+hipError_t hdb_decode(hipStream_t st, const uint32_t *units_base, const unsigned long long *unit_off,
+                      const unsigned long long *nunits, const uint16_t *lut, const HdbOut &g, const uint32_t *skip,
+                      void *work, KernelProf *prof);
 
 // ---------------------------------------------------------------------------
 // decoder (round-trip parity only; the reference has no GPU decoder)

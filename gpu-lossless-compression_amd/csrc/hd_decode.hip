@@ -19,9 +19,8 @@
 //   No data-dependent iteration count and no device->host convergence flag (the
 //   reference re-launches phase 2 until a flag copied back to the host says "synced",
 //   cuhd_gpu_decoder.cu:459-495).
-#include "glc_device.h"
+#include "hd_device.h"
 #include "glc_internal.h"
-#include "../../include/glc_hd.h"
 
 #include <algorithm>
 #include <string.h>
@@ -29,110 +28,7 @@
 
 namespace glc {
 
-constexpr int HD_SPAN   = 32;                    // units per lane
-constexpr int HD_PITCH  = HD_SPAN + 1;           // LDS pitch (bank-conflict-free) + look-ahead unit
-constexpr int HD_LANES  = 256;
-constexpr int HD_WG_UNITS = HD_SPAN * HD_LANES;  // 8192 units = 32 KiB per workgroup
-constexpr int HD_NOFF   = 11;                    // start offsets 0..10
-constexpr int HD_TSTRIDE = 12;                   // words per stored table
 constexpr int HD_CHUNK  = 512;                   // workgroup functions per walk chunk
-constexpr int HD_SPAN_BITS = HD_SPAN * 32;
-
-__device__ __forceinline__ void hd_stage(const uint32_t *__restrict__ units, size_t nunits, size_t base_unit,
-                                         uint32_t *s_u, const uint16_t *__restrict__ lut, uint16_t *s_lut)
-{
-    const uint32_t tid = threadIdx.x;
-    {   // batches of 8 independent loads, then the LDS stores (a load->store loop is one latency per trip)
-        uint32_t q[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) q[r] = lut[r * HD_LANES + tid];        // two 16-bit entries per word are not
-#pragma unroll                                                            // worth it: the table is read once
-        for (int r = 0; r < 8; r++) s_lut[r * HD_LANES + tid] = (uint16_t)q[r];
-        const bool full = base_unit + HD_WG_UNITS <= nunits;
-#pragma unroll 1
-        for (uint32_t i0 = 0; i0 < HD_WG_UNITS; i0 += 8 * HD_LANES) {
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const uint32_t i = i0 + r * HD_LANES + tid;
-                const size_t gu = base_unit + i;
-                q[r] = units[full || gu < nunits ? gu : 0];
-                if (!full && gu >= nunits) q[r] = 0u;
-            }
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                const uint32_t i = i0 + r * HD_LANES + tid;
-                s_u[(i >> 5) * HD_PITCH + (i & 31)] = q[r];
-            }
-        }
-    }
-    __syncthreads();
-    {   // look-ahead unit of every lane = first unit of the next lane / next workgroup
-        const size_t gu = base_unit + HD_WG_UNITS;
-        const uint32_t nxt = (tid + 1 < HD_LANES) ? s_u[(tid + 1) * HD_PITCH] : (gu < nunits ? units[gu] : 0u);
-        s_u[tid * HD_PITCH + HD_SPAN] = nxt;
-    }
-    __syncthreads();
-}
-
-// decode one span from bit `o`; EMIT: write symbols to out[base + k] (k-th symbol) while < nsym
-template <bool EMIT>
-__device__ __forceinline__ uint32_t hd_decode_span(const uint32_t *U, const uint16_t *s_lut, uint32_t o,
-                                                   uint8_t *__restrict__ out, size_t base, size_t nsym)
-{
-    uint32_t pos = o, cnt = 0;
-    uint64_t w = (((uint64_t)U[0] << 32) | U[1]) << o;
-    uint32_t valid = 64 - o, next = 2;
-    while (pos < HD_SPAN_BITS) {
-        const uint32_t e = s_lut[(uint32_t)(w >> (64 - GLC_HD_MAX_LEN))];
-        const uint32_t len = e >> 8;
-        if (EMIT) { if (base + cnt < nsym) out[base + cnt] = (uint8_t)e; }
-        w <<= len; pos += len; valid -= len; cnt++;
-        if (valid <= 32 && next <= HD_SPAN) { w |= (uint64_t)U[next] << (32 - valid); valid += 32; next++; }
-    }
-    return (cnt << 4) | (pos - HD_SPAN_BITS);
-}
-
-// Path from offset 0, recording for every unit the first codeword boundary inside it (every 32-bit
-// unit holds at least two boundaries: codewords are <= 11 bits): chk[u] = symbols before it << 5 | bit.
-__device__ __forceinline__ uint32_t hd_decode_ref(const uint32_t *U, const uint16_t *s_lut, uint16_t *chk)
-{
-    uint32_t pos = 0, cnt = 0, last_u = 0xFFFFFFFFu;
-    uint64_t w = ((uint64_t)U[0] << 32) | U[1];
-    uint32_t valid = 64, next = 2;
-    while (pos < HD_SPAN_BITS) {
-        const uint32_t u = pos >> 5;
-        if (u != last_u) { chk[u] = (uint16_t)((cnt << 5) | (pos & 31)); last_u = u; }
-        const uint32_t len = s_lut[(uint32_t)(w >> (64 - GLC_HD_MAX_LEN))] >> 8;
-        w <<= len; pos += len; valid -= len; cnt++;
-        if (valid <= 32 && next <= HD_SPAN) { w |= (uint64_t)U[next] << (32 - valid); valid += 32; next++; }
-    }
-    return (cnt << 4) | (pos - HD_SPAN_BITS);
-}
-
-// Path from offset o > 0: Huffman codes self-synchronise, so it usually falls onto the reference
-// path within a few codewords; from there on the two are identical, and the result is the
-// reference's (end offset, count) corrected by the symbols decoded so far.  Checked once per unit.
-__device__ __forceinline__ uint32_t hd_decode_merge(const uint32_t *U, const uint16_t *s_lut, const uint16_t *chk,
-                                                    uint32_t ref, uint32_t o)
-{
-    uint32_t pos = o, cnt = 0, last_u = 0;                     // unit 0 holds the start itself: no check there
-    uint64_t w = (((uint64_t)U[0] << 32) | U[1]) << o;
-    uint32_t valid = 64 - o, next = 2;
-    while (pos < HD_SPAN_BITS) {
-        const uint32_t u = pos >> 5;
-        if (u != last_u) {
-            const uint32_t c = chk[u];
-            if ((c & 31u) == (pos & 31u)) return (((ref >> 4) - (c >> 5) + cnt) << 4) | (ref & 15u);
-            last_u = u;
-        }
-        const uint32_t len = s_lut[(uint32_t)(w >> (64 - GLC_HD_MAX_LEN))] >> 8;
-        w <<= len; pos += len; valid -= len; cnt++;
-        if (valid <= 32 && next <= HD_SPAN) { w |= (uint64_t)U[next] << (32 - valid); valid += 32; next++; }
-    }
-    return (cnt << 4) | (pos - HD_SPAN_BITS);
-}
-
-constexpr int HD_CHK_PITCH = 34;                                // u16 per lane (17 words: odd, conflict-free)
 
 __global__ __launch_bounds__(HD_LANES) void k_hd_span_functions(const uint32_t *__restrict__ units, size_t nunits,
                                                                 const uint16_t *__restrict__ lut,
@@ -146,28 +42,7 @@ __global__ __launch_bounds__(HD_LANES) void k_hd_span_functions(const uint32_t *
     const uint32_t tid = threadIdx.x;
     const size_t wg = blockIdx.x;
     hd_stage(units, nunits, wg * (size_t)HD_WG_UNITS, s_u, lut, s_lut);
-    const uint32_t *U = s_u + tid * HD_PITCH;
-    uint16_t *chk = s_chk + tid * HD_CHK_PITCH;
-    const uint32_t ref = hd_decode_ref(U, s_lut, chk);
-    s_tab[0][tid][0] = ref;
-#pragma unroll 1
-    for (uint32_t o = 1; o < HD_NOFF; o++) s_tab[0][tid][o] = hd_decode_merge(U, s_lut, chk, ref, o);
-    // inclusive scan of the span functions across the 256 lanes (Hillis-Steele, composition B(A(.)))
-    int src = 0;
-    for (uint32_t d = 1; d < HD_LANES; d <<= 1) {
-        __syncthreads();
-        for (uint32_t o = 0; o < HD_NOFF; o++) {
-            uint32_t r = s_tab[src][tid][o];
-            if (tid >= d) {
-                const uint32_t a = s_tab[src][tid - d][o];            // earlier part, applied first
-                const uint32_t bb = s_tab[src][tid][a & 15];
-                r = (((a >> 4) + (bb >> 4)) << 4) | (bb & 15);
-            }
-            s_tab[src ^ 1][tid][o] = r;
-        }
-        src ^= 1;
-    }
-    __syncthreads();
+    const int src = hd_span_scan(s_u, s_lut, s_chk, s_tab);
     uint32_t *P = pexcl + (wg * HD_LANES + tid) * HD_TSTRIDE;
     for (uint32_t o = 0; o < HD_NOFF; o++) P[o] = tid ? s_tab[src][tid - 1][o] : o;   // exclusive; identity for lane 0
     if (tid < HD_NOFF) fwg[wg * HD_TSTRIDE + tid] = s_tab[src][HD_LANES - 1][tid];
@@ -225,33 +100,7 @@ __global__ __launch_bounds__(HD_LANES) void k_hd_emit(const uint32_t *__restrict
     const uint32_t p = pexcl[(wg * HD_LANES + tid) * HD_TSTRIDE + ow];
     const size_t base = (size_t)start_base[wg] + (p >> 4);
     if (base >= nsym) return;
-    // decode and write: four symbols per dword store once the output index is 4-aligned (the bytes
-    // before that belong to the previous lane's dword and go out one by one, as does the tail)
-    const uint32_t *U = s_u + tid * HD_PITCH;
-    const uint32_t o = p & 15;
-    uint32_t pos = o;
-    uint64_t w = (((uint64_t)U[0] << 32) | U[1]) << o;
-    uint32_t valid = 64 - o, next = 2, acc = 0;
-    size_t idx = base;
-    const bool al = (reinterpret_cast<size_t>(out) & 3) == 0;
-    while (pos < HD_SPAN_BITS && idx < nsym) {
-        const uint32_t e = s_lut[(uint32_t)(w >> (64 - GLC_HD_MAX_LEN))];
-        const uint32_t len = e >> 8, k = (uint32_t)idx & 3u;
-        acc |= (e & 0xFFu) << (8 * k);
-        if (k == 3) {
-            if (al && idx - base >= 3) *reinterpret_cast<uint32_t *>(out + idx - 3) = acc;
-            else for (uint32_t q = (idx - base >= 3) ? 0u : 3u - (uint32_t)(idx - base); q < 4; q++) out[idx - 3 + q] = (uint8_t)(acc >> (8 * q));
-            acc = 0;
-        }
-        idx++;
-        w <<= len; pos += len; valid -= len;
-        if (valid <= 32 && next <= HD_SPAN) { w |= (uint64_t)U[next] << (32 - valid); valid += 32; next++; }
-    }
-    {   // tail: the bytes of an unfinished dword
-        const uint32_t k = (uint32_t)idx & 3u;                 // bytes [idx - k, idx) pending, but not before `base`
-        const uint32_t have = (uint32_t)((idx - base) < k ? (idx - base) : k);
-        for (uint32_t q = k - have; q < k; q++) out[idx - k + q] = (uint8_t)(acc >> (8 * q));
-    }
+    hd_emit_span(s_u + tid * HD_PITCH, s_lut, p & 15, out, base, nsym);
 }
 
 // ---------------------------------------------------------------------------

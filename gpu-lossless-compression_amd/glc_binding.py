@@ -56,7 +56,8 @@ EXCHANGE_SYMBOLS = ["glcCommGetUniqueId", "glcCommInitRank", "glcCommAdopt", "gl
                     "glcGatherStreams", "glcScatterStreams"]
 HD_SYMBOLS = ["glcHdBuildTable", "glcHdEncodeHost", "glcHdWorkBytes", "glcHdDecodeDevice", "glcHdDecodeDeviceTable", "glcHdDecodeDeviceTableOnDevice", "glcHdEnableProfile",
               "glcHdKernelProfile", "glcHdEncodeBound", "glcHdEncodeWorkBytes", "glcHdHistogramDevice", "glcHdBuildTableDevice",
-              "glcHdEncodeDevice"]
+              "glcHdEncodeDevice", "glcHdSegmentsWorkBytes", "glcHdSegmentsTablesDevice", "glcHdSegmentsEncodeDevice",
+              "glcHdSegmentsDecodeDevice"]
 
 
 class CUDPPConfiguration(C.Structure):
@@ -207,6 +208,16 @@ def lib():
         L.glcHdBuildTableDevice.restype = C.c_int
         L.glcHdEncodeDevice.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp, vp]
         L.glcHdEncodeDevice.restype = C.c_int
+    if hasattr(L, "glcHdSegmentsEncodeDevice"):
+        ull = C.c_ulonglong
+        L.glcHdSegmentsWorkBytes.argtypes = [sz, sz]
+        L.glcHdSegmentsWorkBytes.restype = sz
+        L.glcHdSegmentsTablesDevice.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.glcHdSegmentsTablesDevice.restype = C.c_int
+        L.glcHdSegmentsEncodeDevice.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, ull, vp, vp, vp]
+        L.glcHdSegmentsEncodeDevice.restype = C.c_int
+        L.glcHdSegmentsDecodeDevice.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, vp]
+        L.glcHdSegmentsDecodeDevice.restype = C.c_int
     if hasattr(L, "glcGatherStreams"):                             # include/glc_exchange.h
         ullp = C.POINTER(C.c_ulonglong)
         L.glcCommGetUniqueId.argtypes = [vp]
@@ -576,13 +587,74 @@ def hd_encode_device(d_in, d_lens, d_codes, cap_units=None, stream=None, work=No
     return d_units, nunits
 
 
+HD_SEGMENT_MAX = 1 << 20
+
+
+def _i64(dev, values):
+    import torch
+    return torch.as_tensor(values, dtype=torch.int64).reshape(-1).to(dev)
+
+
+def hd_segments_tables(d_base, d_offsets, d_lengths, max_len, stream=None):
+    """The batched histogram + table builder: segments [d_offsets[i], + d_lengths[i]) of the uint8 cuda tensor d_base (offsets and
+    lengths: int64 cuda tensors).  Returns (d_hist int32[count, 256], d_lens uint8[count, 256], d_codes int16[count, 256] holding the
+    u16 codes, d_nunits int64[count]); enqueued only."""
+    import torch
+    dev, count = d_base.device, d_offsets.numel()
+    hist = torch.empty((max(count, 1), 256), dtype=torch.int32, device=dev)
+    lens = torch.empty((max(count, 1), 256), dtype=torch.uint8, device=dev)
+    codes = torch.empty((max(count, 1), 256), dtype=torch.int16, device=dev)
+    nunits = torch.empty(max(count, 1), dtype=torch.int64, device=dev)
+    if not lib().glcHdSegmentsTablesDevice(d_base.data_ptr(), d_offsets.data_ptr(), d_lengths.data_ptr(), count, int(max_len),
+                                           hist.data_ptr(), lens.data_ptr(), codes.data_ptr(), nunits.data_ptr(), _stream_ptr(stream)):
+        raise HdError("glcHdSegmentsTablesDevice failed")
+    if isinstance(stream, torch.cuda.Stream):
+        for t in (hist, lens, codes, nunits):
+            t.record_stream(stream)
+    return hist[:count], lens[:count], codes[:count], nunits[:count]
+
+
+def hd_segments_work(count, max_len, device):
+    import torch
+    return torch.empty(max(1, int(lib().glcHdSegmentsWorkBytes(int(count), int(max_len)))), dtype=torch.uint8, device=device)
+
+
+def hd_segments_encode(d_base, d_offsets, d_lengths, max_len, d_lens, d_codes, d_nunits, d_units, d_unit_offsets, cap_units=None,
+                       d_skip=None, work=None, stream=None):
+    """Every segment's stream into the int32 cuda tensor d_units at d_unit_offsets[i] (int64, in units); enqueued only."""
+    count = d_offsets.numel()
+    if work is None:
+        work = hd_segments_work(count, max_len, d_base.device)
+    cap = d_units.numel() if cap_units is None else int(cap_units)
+    if not lib().glcHdSegmentsEncodeDevice(d_base.data_ptr(), d_offsets.data_ptr(), d_lengths.data_ptr(), count, int(max_len),
+                                           d_lens.data_ptr(), d_codes.data_ptr(), d_nunits.data_ptr(), d_units.data_ptr(),
+                                           d_unit_offsets.data_ptr(), cap, d_skip.data_ptr() if d_skip is not None else None,
+                                           work.data_ptr(), _stream_ptr(stream)):
+        raise HdError("glcHdSegmentsEncodeDevice failed")
+    return work
+
+
+def hd_segments_decode(d_units, d_unit_offsets, d_nunits, d_hist, d_out, d_out_offsets, d_lengths, max_len, d_skip=None, work=None,
+                       stream=None):
+    """The inverse: d_lengths[i] symbols of every stream into the uint8 cuda tensor d_out at d_out_offsets[i]; enqueued only."""
+    count = d_out_offsets.numel()
+    if work is None:
+        work = hd_segments_work(count, max_len, d_out.device)
+    if not lib().glcHdSegmentsDecodeDevice(d_units.data_ptr(), d_unit_offsets.data_ptr(), d_nunits.data_ptr(), d_hist.data_ptr(),
+                                           d_out.data_ptr(), d_out_offsets.data_ptr(), d_lengths.data_ptr(), count, int(max_len),
+                                           d_skip.data_ptr() if d_skip is not None else None, work.data_ptr(), _stream_ptr(stream)):
+        raise HdError("glcHdSegmentsDecodeDevice failed")
+    return work
+
+
 # --------------------------------------------------------------------------------------------------------------------------
 # include/glc_container.h: the CRC-checked container of the BWT codec (INTEGRATION.md 4b)
 # --------------------------------------------------------------------------------------------------------------------------
 CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcContainerDecompressDevice", "glcContainerCompress",
                      "glcContainerDecompress", "glcContainerCompressFile", "glcContainerDecompressFile", "glcCrc32Segments",
                      "glcContainerLastError", "glcShuffleSegments", "glcUnshuffleSegments", "glcShuffleDevice", "glcUnshuffleDevice",
-                     "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle"]
+                     "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec"]
+CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0 = 0, 1
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
 
@@ -608,6 +680,8 @@ def _ct():
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, vp]
         L.glcPlanSetContainerShuffle.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerShuffle.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcPlanSetContainerCodec.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerCodec.argtypes = [sz, C.POINTER(C.c_uint)]
         for nm in CONTAINER_SYMBOLS[1:]:
             getattr(L, nm).restype = C.c_int
         L._ct_ready = True
@@ -697,6 +771,18 @@ def container_get_shuffle(plan):
     e = C.c_uint(0)
     _chk("glcPlanGetContainerShuffle", _ct().glcPlanGetContainerShuffle(plan.handle, C.byref(e)))
     return int(e.value)
+
+
+def container_set_codec(plan, codec):
+    """the codec of the plan's container ENCODER: CONTAINER_CODEC_BWT (the default: format version 1 / 2) or CONTAINER_CODEC_HUFF0
+    (order-0 Huffman records, format version 3).  The decoder reads what was done from the stream and ignores this setting."""
+    _chk("glcPlanSetContainerCodec", _ct().glcPlanSetContainerCodec(plan.handle, int(codec)))
+
+
+def container_get_codec(plan):
+    c = C.c_uint(0)
+    _chk("glcPlanGetContainerCodec", _ct().glcPlanGetContainerCodec(plan.handle, C.byref(c)))
+    return int(c.value)
 
 
 def _shuffle(fn, d_in, elem, out, stream):

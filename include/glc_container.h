@@ -14,6 +14,13 @@
  * the shuffled block, the stream's still that of the original input.  With the filter off the container is version 1, byte for
  * byte what it always was.  Choose rows as a multiple of the element size so that blocks and planes coincide.
  *
+ * A second codec, chosen by the caller: GLC_CONTAINER_CODEC_HUFF0 codes every block with an order-0 canonical Huffman table of
+ * its own (at most 11 bits, the CUHD-shaped stream of include/glc_hd.h) instead of suffix sort + move-to-front + Huffman.  It does
+ * no sort, and is smaller on data without context structure (i.i.d. symbols, quantised or shuffled numeric data); text and logs
+ * want the BWT codec.  Measured on one MI355X on 4 GiB of Zipf(1.0) bytes in 1 MiB blocks (profiles/container_codec.md): ratio
+ * 1.275 against 1.121, encode 533 against 103 GB/s, decode 100 against 45 GB/s; sizes for other inputs in INTEGRATION.md 4b.
+ * Such a stream is format version 3, with or without the filter.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -89,6 +96,22 @@ CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long
  * bytes; two with pipelining on), the first filtered decode staging of the largest frame seen; both live as long as the plan. */
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem);
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem);
+
+/* The codec the container ENCODER of this plan uses.  GLC_CONTAINER_CODEC_BWT (the default) writes format version 1, or 2 with
+ * the shuffle filter on, byte for byte as ever.  GLC_CONTAINER_CODEC_HUFF0 writes version 3: a block is an order-0 Huffman
+ * record (its histogram in the tables, the table rebuilt from it) or, when 4 * words >= block bytes, raw.  Any other value is
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it, with
+ * pipelining on or off; the decoder ignores it (the stream says what was done) and reads all three versions.  The first HUFF0
+ * encode allocates about 3 KiB of device scratch per row, the first version-3 decode 4 KiB per block of the largest frame plus
+ * up to 256 MiB of span-function prefixes; both live as long as the plan, and a plan that only uses the BWT codec has neither.
+ * The order-0 path never touches the sorter's scratch or statistics. */
+enum GlcContainerCodec
+{
+    GLC_CONTAINER_CODEC_BWT = 0,
+    GLC_CONTAINER_CODEC_HUFF0 = 1
+};
+CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec);
+CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -96,6 +96,47 @@ int glcHdDecodeDeviceTable(const unsigned int *d_units, size_t nunits, const uns
 int glcHdDecodeDeviceTableOnDevice(const unsigned int *d_units, size_t nunits, const unsigned char *d_table2048,
                                    unsigned char *d_out, size_t nsym, void *d_work, void *stream);
 
+/* The batched form of the device calls above: `count` segments [d_inBase + d_offsets[i], + d_lengths[i]) with ONE TABLE
+ * EACH, thousands per launch (the container's order-0 codec, include/glc_container.h, is built from these).  Any byte
+ * alignment; offsets, lengths and unit offsets are u64 arrays in DEVICE memory; no segment is longer than maxLen, and
+ * maxLen <= 1048576 (a larger maxLen is refused; a longer d_lengths[i] is read as maxLen); count <= 4194304 per call.  Like the calls above they
+ * only enqueue on `stream`, never wait on the host, keep no global state and return 1 when the arguments are valid and the
+ * work was enqueued, else 0 with nothing launched; count == 0 is a success that does nothing.
+ *
+ * d_work: glcHdSegmentsWorkBytes(count, maxLen) bytes, one per call in flight; it serves either direction.  The encoder
+ * needs 2 KiB of it per segment.  The decoder needs 4 KiB of tables per segment plus the span-function prefixes of every
+ * stream at its longest -- 48 bytes per 128 bytes of 11-bit stream, 541 KiB per segment at maxLen = 1 MiB -- so for
+ * thousands of large segments decode in chunks of segments rather than in one call.  The encoder loads a tile's symbols 16
+ * bytes per lane when the segment starts on a 16-byte boundary and byte by byte when it does not (rate not measured). */
+size_t glcHdSegmentsWorkBytes(size_t count, size_t maxLen);
+
+/* Per segment: d_hist[i][256] (u32) = its byte counts; d_lens[i][256] / d_codes[i][256] = the table glcHdBuildTable gives
+ * for them (all zero for an empty segment); d_nunits[i] = the units its stream needs, pad unit included:
+ * ceil(sum hist * lens / 32) + 1, so 1 for an empty segment.  No pass over the data is needed for that number, which is
+ * what lets a caller lay the streams out (d_unitOffsets below) before anything is encoded. */
+int glcHdSegmentsTablesDevice(const unsigned char *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                              size_t count, size_t maxLen, unsigned int *d_hist, unsigned char *d_lens, unsigned short *d_codes,
+                              unsigned long long *d_nunits, void *stream);
+
+/* Segment i's stream, word for word what glcHdEncodeHost writes for it with table i, at d_unitsBase + d_unitOffsets[i]
+ * (d_unitsBase 4-byte aligned; units, not bytes): d_nunits[i] units, every one of them written -- the destination need not
+ * be zeroed -- and none outside them, whatever order the workgroups run in.  d_skip (may be NULL): a segment whose
+ * d_skip[i] != 0 is left alone.  A segment whose stream would end past capUnits (counted from d_unitsBase), or whose bytes
+ * no longer give d_nunits[i] units with its table, is not written at all. */
+int glcHdSegmentsEncodeDevice(const unsigned char *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                              size_t count, size_t maxLen, const unsigned char *d_lens, const unsigned short *d_codes,
+                              const unsigned long long *d_nunits, unsigned int *d_unitsBase, const unsigned long long *d_unitOffsets,
+                              unsigned long long capUnits, const unsigned int *d_skip, void *d_work, void *stream);
+
+/* The inverse: the tables are rebuilt on the device from d_hist[i][256] (u32; what glcHdSegmentsTablesDevice wrote), and
+ * d_lengths[i] symbols of the stream of d_nunits[i] units at d_unitsBase + d_unitOffsets[i] are written to
+ * d_outBase + d_outOffsets[i].  Whatever the units hold, nothing is read outside a segment's d_nunits[i] units and nothing
+ * written outside its d_lengths[i] bytes.  d_skip as above. */
+int glcHdSegmentsDecodeDevice(const unsigned int *d_unitsBase, const unsigned long long *d_unitOffsets, const unsigned long long *d_nunits,
+                              const unsigned int *d_hist, unsigned char *d_outBase, const unsigned long long *d_outOffsets,
+                              const unsigned long long *d_lengths, size_t count, size_t maxLen, const unsigned int *d_skip,
+                              void *d_work, void *stream);
+
 /* Measurement aid: live per-kernel profile of the two decode entry points (hipEvent pairs on the call's stream around
  * k_hd_span_functions / the three k_hd_walk launches / k_hd_emit).  glcHdEnableProfile(1) switches it on and resets it;
  * glcHdKernelProfile(i, name, cap, out3) waits for the device and returns 1 with the slot's name and
