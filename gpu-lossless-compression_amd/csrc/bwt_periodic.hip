@@ -229,8 +229,6 @@ __global__ __launch_bounds__(256) void k_per_rows(const uint8_t *__restrict__ te
     else for (uint32_t k = 0; k < rows; k++) O[row0 + k] = (uint8_t)(v[k >> 2] >> (8 * (k & 3)));
 }
 
-#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t per_reserve(SaScratch &s)
 {
     if (s.per_text) return hipSuccess;

@@ -979,7 +979,7 @@ __global__ void k_sa_export(const uint32_t *__restrict__ sa, uint32_t n, uint32_
 }
 
 // ---------------------------------------------------------------------------
-// Resuming from the sample sorter's tolerant form (bwt_bucket.hip ss_build, attempt 2): s.sa holds the suffixes of a block
+// Resuming from the sample sorter's tolerant form (bwt_sample.hip ss_build, attempt 2): s.sa holds the suffixes of a block
 // ordered by their first SS_TOL_CAP symbols -- exact everywhere except that suffixes which agree in more than that come in
 // no particular order.  The GROUPS the doubling rounds have to order are the maximal ranges of neighbouring rows whose
 // suffixes share SS_TOL_CAP symbols, found by looking (not taken from the sample sorter's own bookkeeping: its buckets are
@@ -1117,8 +1117,6 @@ __global__ __launch_bounds__(GRP_NT) void k_grp_keys(uint32_t n, uint32_t *__res
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_tiles = (nmax + SA_TILE - 1) / SA_TILE;

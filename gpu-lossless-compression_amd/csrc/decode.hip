@@ -362,147 +362,23 @@ __global__ __launch_bounds__(DL_NT) void k_dec_huff_lanes(const uint32_t *__rest
 // 3. inverse MTF
 // ---------------------------------------------------------------------------
 
-// Pass 1 (k_imtf_pos): one LANE per chunk.  The lane keeps a 256-entry list of POSITIONS (identity at the chunk start)
-// in LDS and, for every MTF index r, reads entry r and moves it to the front.  Output: the position byte of every
+// Pass 1 (k_imtf_pos_deque): one LANE per chunk.  The lane keeps a 256-entry list of POSITIONS (identity at the chunk
+// start) in LDS and, for every MTF index r, reads entry r and moves it to the front.  Output: the position byte of every
 // symbol (symbol = start_list[pos]) and the chunk's final list = its position permutation.
 // Pass 2 (k_imtf_scan) composes the permutations; pass 3 (k_imtf_apply) is a 256-byte LUT lookup per chunk -- the
 // sequential work is done once, not twice.
-// The list is 16 GROUPS of 16 entries, [group][lane] x 16 bytes.  Moving entry r = 16 g + o to the front shifts the
-// r entries below it up by one; done word by word that is 2 g + 3 sixteen-byte LDS accesses per symbol FOR THE LANE
-// WITH THE LARGEST r of the wave (PMC: LDS data path saturated, VALU at 38 %, 9.9 ms per GiB).  Here every group is a
-// RING (its tail position is a nibble of tlo / thi): pushing an entry in at the front of group k < g and its last
-// entry out is one byte read + one byte write at the ring's tail, which becomes the new head -- the 16 bytes stay
-// where they are, and all the tails of a symbol step back in one nibble-wise addition.  Only group g itself is rewritten (rotated to its logical order, the o entries below the hit shifted,
-// stored back with head 0).  Bytes moved per symbol: ~2 g + 48 instead of 32 g + 48.  Measured: 9.9 -> 9.0 ms per GiB
-// -- the LDS data path is no longer the limit (active 105 -> 64 quad-cycles per 64 symbols, FIFO-full 40 -> 0.6), the
-// kernel now runs at ~62 % of the VALU issue rate (~210 instructions per 64 symbols: a read, a write and a nested EXEC
-// level per group) with 2.25 waves per SIMD (16.6 KB of LDS per wave) to cover three dependent LDS round trips per symbol.
 #ifndef GLC_IMTF_CHUNK
 #define GLC_IMTF_CHUNK 4096
 #endif
 constexpr uint32_t IMTF_CHUNK = GLC_IMTF_CHUNK;              // symbols per lane of pass 1 (4096 against 2048: permutation scan 251 -> 125, apply 535 -> 413 us per 1024 blocks)
 static_assert(IMTF_CHUNK % 2048 == 0, "k_imtf_apply works in pieces of 2048 symbols");
 
-// w rotated right by h bytes: byte i of the result = byte (i + h) & 15 of w
-__device__ __forceinline__ uint4 imtf_rotr(uint4 w, uint32_t h)
-{
-    const bool q1 = (h & 4u) != 0, q2 = (h & 8u) != 0;
-    uint32_t x = q1 ? w.y : w.x, y = q1 ? w.z : w.y, z = q1 ? w.w : w.z, v = q1 ? w.x : w.w;
-    const uint32_t x2 = q2 ? z : x, y2 = q2 ? v : y, z2 = q2 ? x : z, v2 = q2 ? y : v;
-    const uint32_t b = h & 3u;
-    uint4 r;
-    r.x = __builtin_amdgcn_alignbyte(y2, x2, b);
-    r.y = __builtin_amdgcn_alignbyte(z2, y2, b);
-    r.z = __builtin_amdgcn_alignbyte(v2, z2, b);
-    r.w = __builtin_amdgcn_alignbyte(x2, v2, b);
-    return r;
-}
-
-__global__ __launch_bounds__(64) void k_imtf_pos(const uint8_t *__restrict__ in, size_t in_stride, uint32_t n,
-                                                 uint8_t *__restrict__ lists, uint32_t max_chunks,
-                                                 uint8_t *__restrict__ pos_out, size_t out_stride)
-{
-    __shared__ uint4 s_list[16 * 64];
-    __shared__ uint4 s_mask[17];                              // s_mask[c]: the low c bytes
-    const uint32_t b = blockIdx.y, l = threadIdx.x;
-    const uint32_t nchunks = (n + IMTF_CHUNK - 1) / IMTF_CHUNK;
-    const uint32_t chunk = blockIdx.x * 64 + l;
-    const bool live = chunk < nchunks;
-    const uint32_t lo = chunk * IMTF_CHUNK;
-    const uint32_t cnt = live ? min(IMTF_CHUNK, n - lo) : 0u;
-    const uint8_t *src = in + (size_t)b * in_stride + lo;
-    uint8_t *dst = pos_out + (size_t)b * out_stride + lo;
-    uint8_t *s_bytes = reinterpret_cast<uint8_t *>(s_list);
-    const bool vec_ok = ((reinterpret_cast<size_t>(src) | reinterpret_cast<size_t>(dst)) & 15) == 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; k++) {
-        const uint32_t v = 0x03020100u + 0x10101010u * k;
-        s_list[k * 64 + l] = make_uint4(v, v + 0x04040404u, v + 0x08080808u, v + 0x0C0C0C0Cu);
-    }
-    if (l < 17) {
-        auto m = [&](int c) { return c >= 4 ? 0xFFFFFFFFu : (c <= 0 ? 0u : ((1u << (8 * c)) - 1u)); };
-        s_mask[l] = make_uint4(m((int)l), m((int)l - 4), m((int)l - 8), m((int)l - 12));
-    }
-    __builtin_amdgcn_wave_barrier();
-    auto load16 = [&](uint32_t j, uint32_t *rv) {
-        rv[0] = rv[1] = rv[2] = rv[3] = 0;
-        if (vec_ok && j + 16 <= cnt) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(src + j);
-            rv[0] = q.x; rv[1] = q.y; rv[2] = q.z; rv[3] = q.w;
-        } else if (j < cnt) {
-            for (uint32_t t = 0; t < min(16u, cnt - j); t++) rv[t >> 2] |= (uint32_t)src[j + t] << (8 * (t & 3));
-        }
-    };
-    uint32_t tlo = 0xFFFFFFFFu, thi = 0xFFFFFFFFu;           // ring TAILS (position of a group's last entry), groups 0..7 / 8..15, a nibble each
-    const uint32_t lbase = l * 16;
-    // nibble-wise x + y mod 16 (y = 15 in the nibbles that step back by one, 0 elsewhere)
-    auto nib_add = [](uint32_t x, uint32_t y) { return ((x & 0x77777777u) + (y & 0x77777777u)) ^ ((x ^ y) & 0x88888888u); };
-    uint32_t nx[4];
-    load16(0, nx);
-    for (uint32_t j = 0; j < IMTF_CHUNK; j += 16) {
-        if (__ballot(j < cnt) == 0) break;
-        uint32_t rv[4] = {nx[0], nx[1], nx[2], nx[3]}, ov[4] = {0, 0, 0, 0};
-        load16(j + 16, nx);                                   // in flight while these 16 are processed
-#pragma unroll
-        for (uint32_t t = 0; t < 16; t++) {
-            // past the end of the chunk: index 0, which changes nothing
-            const uint32_t r = (j + t < cnt) ? (rv[t >> 2] >> (8 * (t & 3))) & 0xFFu : 0u;
-            const uint32_t g = r >> 4, o = r & 15u, sh = (g & 7u) * 4u;
-            const uint32_t h = ((((g >= 8 ? thi : tlo) >> sh) & 15u) + 1u) & 15u;      // head of group g
-            const uint32_t gbase = g * 1024u + lbase;
-            const uint32_t sym = s_bytes[gbase + ((h + o) & 15u)];
-            // groups below g: the entry pushed out at the tail makes room for the one pushed in; the slot becomes the
-            // head.  A lane leaves the loop at its own g (the wave's EXEC shrinks); the next group's tail entry is
-            // read one trip ahead.
-            uint32_t carry = sym;
-            {
-                uint32_t acur = lbase + (tlo & 15u);
-                uint32_t tcur = s_bytes[acur];
-#pragma unroll
-                for (uint32_t k = 0; k < 15; k++) {
-                    if (k >= g) break;
-                    const uint32_t k1 = k + 1;
-                    const uint32_t anext = k1 * 1024u + lbase + (((k1 < 8 ? tlo : thi) >> (4 * (k1 & 7))) & 15u);
-                    const uint32_t tnext = s_bytes[anext];
-                    s_bytes[acur] = (uint8_t)carry;
-                    carry = tcur; tcur = tnext; acur = anext;
-                }
-            }
-            tlo = nib_add(tlo, g >= 8 ? 0xFFFFFFFFu : (1u << ((4 * g) & 31u)) - 1u);
-            thi = nib_add(thi, g <= 8 ? 0u : (1u << ((4 * g) & 31u)) - 1u);
-            {   // group g: logical order, entries 0..o-1 move up by one, the carry goes to the front, head = 0 (tail = 15)
-                const uint4 w = imtf_rotr(s_list[g * 64 + l], h);
-                const uint4 m = s_mask[o + 1];
-                uint4 nw;
-                nw.x = (w.x & ~m.x) | (((w.x << 8) | carry) & m.x);
-                nw.y = (w.y & ~m.y) | (__builtin_amdgcn_alignbit(w.y, w.x, 24) & m.y);
-                nw.z = (w.z & ~m.z) | (__builtin_amdgcn_alignbit(w.z, w.y, 24) & m.z);
-                nw.w = (w.w & ~m.w) | (__builtin_amdgcn_alignbit(w.w, w.z, 24) & m.w);
-                s_list[g * 64 + l] = nw;
-                const uint32_t set = 15u << sh;
-                if (g >= 8) thi |= set; else tlo |= set;
-            }
-            ov[t >> 2] |= sym << (8 * (t & 3));
-        }
-        if (vec_ok && j + 16 <= cnt) {
-            *reinterpret_cast<uint4 *>(dst + j) = make_uint4(ov[0], ov[1], ov[2], ov[3]);
-        } else if (j < cnt) {
-            for (uint32_t t = 0; t < min(16u, cnt - j); t++) dst[j + t] = (uint8_t)(ov[t >> 2] >> (8 * (t & 3)));
-        }
-    }
-    if (live && chunk + 1 < nchunks) {                           // nobody needs the last permutation
-        uint4 *LW = reinterpret_cast<uint4 *>(lists + ((size_t)b * max_chunks + chunk) * 256);
-#pragma unroll
-        for (uint32_t k = 0; k < 16; k++)
-            LW[k] = imtf_rotr(s_list[k * 64 + l], ((((k < 8 ? tlo : thi) >> (4 * (k & 7))) & 15u) + 1u) & 15u);
-    }
-}
-
 // ---------------------------------------------------------------------------
-// Pass 1, second form (the default): the list as a DEQUE WITH HOLES.  Moving entry r to the front of an array shifts r
-// entries; the ring form above cuts that to one byte per 16-entry group below the hit, and still spends ~135 of its 212
-// wave instructions per step in the loop over those groups -- executed as often as the LARGEST index of the wave asks
-// for, and MTF indices of near-incompressible data are large.  Here nothing is shifted at all.  A lane's list lives in
+// Pass 1: the list as a DEQUE WITH HOLES.  Moving entry r to the front of an array shifts r entries: as an array of 16
+// groups of 16 entries that was 2 g + 3 sixteen-byte LDS accesses per symbol for the lane with the largest r of the wave
+// (9.9 ms per GiB, the LDS data path saturated); with every group a ring (round 2: one byte per group below the hit) 9.0 ms,
+// and still ~135 of 212 wave instructions per step in the loop over those groups -- executed as often as the LARGEST index
+// of the wave asks for, and MTF indices of near-incompressible data are large.  Here nothing is shifted at all.  A lane's list lives in
 // 512 POSITIONS (lower = nearer the front): a 512-byte array A and a 512-bit bitmap V of the positions in use, exactly
 // 256 of them.  A step with index r
 //     finds the r-th position in use, p   -- SELECT on the bitmap: a 3-level tree of counts kept in registers names the
@@ -514,7 +390,7 @@ __global__ __launch_bounds__(64) void k_imtf_pos(const uint8_t *__restrict__ in,
 // a 16-entry selector table, no divergence: every lane holds exactly 256 entries).  ~75 VALU + 6 LDS instructions per
 // step instead of 212 + 41; 36 KB of LDS per wave (one wave per SIMD), so a step is the latency of its chain
 // (tree descent -> word -> byte -> bit: three LDS round trips), ~420 cycles.
-// Same outputs as the ring form: the position byte of every symbol and the chunk's final list (its permutation).
+// Outputs: the position byte of every symbol and the chunk's final list (its permutation).
 // ---------------------------------------------------------------------------
 #ifndef GLC_IMD_POS
 #define GLC_IMD_POS 512
@@ -1063,8 +939,8 @@ __global__ __launch_bounds__(256) void k_ibwt_emit(const uint8_t *__restrict__ t
 }
 
 // ---------------------------------------------------------------------------
-#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
+// host side
+// ---------------------------------------------------------------------------
 hipError_t decode_scratch_alloc(DecodeScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows;
@@ -1120,13 +996,8 @@ hipError_t decode_stage_a(hipStream_t st, const uint32_t *d_hist, const uint32_t
                            d_offsets, offset_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, d_block_off);
     if (pi >= 0) s.prof->end(pi, units, st);
     pi = s.prof ? s.prof->begin(PROF_IMTF_POS, st) : -1;
-    static const bool rings = getenv("GLC_IMTF_RINGS") != nullptr;   // A/B: the ring form of pass 1
-    if (rings)
-        hipLaunchKernelGGL(k_imtf_pos, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
-                           s.max_chunks, bwt, (size_t)s.nmax);
-    else
-        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
-                           s.max_chunks, bwt, (size_t)s.nmax);
+    hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
+                       s.max_chunks, bwt, (size_t)s.nmax);
     if (pi >= 0) s.prof->end(pi, units, st);
     pi = s.prof ? s.prof->begin(PROF_IMTF_REST, st) : -1;
     hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);

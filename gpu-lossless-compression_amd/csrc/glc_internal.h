@@ -10,10 +10,12 @@
 // Diagnostic switches change what a kernel does (extra stores, cycle stamps, debug counters): a library built with one is an
 // experiment, never the product.  They compile only with -DGLC_EXPERIMENT_BUILD, and build.py writes such a library (any
 // library built with GLC_CXXFLAGS) to GLC_LIB_OUT only -- libglc_amd.so is always the plain build.
-#if (defined(GLC_DEBUG_CAND) || defined(GLC_SS_CLOCKS) || defined(GLC_HB_TIMING) || defined(GLC_FS2_CLOCKS) || defined(GLC_EXP_PART) || \
-     defined(GLC_EXP_PART2) || defined(GLC_EXP_SORT) || defined(GLC_EXP_MTF)) && !defined(GLC_EXPERIMENT_BUILD)
-#error "diagnostic / timing-experiment switches need -DGLC_EXPERIMENT_BUILD (and GLC_LIB_OUT: build.py never writes libglc_amd.so from such a build)"
+#if (defined(GLC_DEBUG_CAND) || defined(GLC_SS_CLOCKS) || defined(GLC_HB_TIMING)) && !defined(GLC_EXPERIMENT_BUILD)
+#error "diagnostic switches need -DGLC_EXPERIMENT_BUILD (and GLC_LIB_OUT: build.py never writes libglc_amd.so from such a build)"
 #endif
+
+// in a launcher that returns hipError_t: pass a failed call's error on
+#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 namespace glc {
 
@@ -23,7 +25,7 @@ constexpr uint32_t HUFF_SYMS       = 257;        // HUFF_NUM_CHARS (cudpp_global
 constexpr uint32_t HUFF_MAX_WORDS  = 1536;       // HUFF_CODE_BYTES (cudpp_globals.h:66)
 constexpr uint32_t MTF_CHUNK       = 4096;       // bytes of BWT output per wave in the MTF kernels
 
-// fast suffix sorter (bwt_bucket.hip): buckets of FS_AVG suffixes on average, FS_CAP words of slot each
+// fast suffix sorters (bwt_bucket.hip, bwt_sample.hip): buckets of FS_AVG suffixes on average, FS_CAP words of slot each
 constexpr uint32_t FS_AVG   = 2048;
 constexpr uint32_t FS_CAP   = 4096;             // slot size in the word array
 constexpr uint32_t FS_FILLMAX = 4032;            // fullest bucket the in-LDS sort takes (a fuller one flags its block)
@@ -177,7 +179,7 @@ struct SaScratch {
     long      chain_min = 16384;
     uint32_t  chain_rounds = 0x15;
     uint32_t  last_chains[2] = {0, 0};           // the plan's last call: chain groups ordered by the rule, candidates refused
-    // fast path (bwt_bucket.hip); its words live in keyA/keyB (one allocation, fs_kstride words per block)
+    // fast path (bwt_bucket.hip, bwt_sample.hip); its words live in keyA/keyB (one allocation, fs_kstride words per block)
     int       sorter = 0;                        // 0 = bucket sorter, then sample sorter, then general sorter for what each flags;
                                                  // 1 = general sorter only; 2 = general sorter, prefix doubling only;
                                                  // 3 = bucket sorter, then general sorter (no sample sorter);
@@ -191,9 +193,11 @@ struct SaScratch {
     uint32_t *fs_redo[2] = {nullptr, nullptr};   // [rows] copies of fs_lcnt, one per call parity (read by the speculative Huffman pass)
     uint32_t *fs_keep[2] = {nullptr, nullptr};   // [rows] 1 = the bucket sorter finished the block (the speculative stages' `only` mask)
     uint32_t *fs_dup = nullptr;                  // [rows] repeated 6-grams among the samples k_fs_hist looks at (text-likeness probe)
-    uint32_t *fs_zero = nullptr;                 // [rows] bucket that holds the word of suffix 0 (k_fs_part -> k_fs_sort_bwt: the BWT index is looked for there only)
+    uint32_t *fs_zero = nullptr;                 // [rows] bucket that holds the word of suffix 0 (k_fs_part2 -> k_fs_sort_bwt: the BWT index is looked for there only)
     uint32_t  parity = 0;                        // set by the caller before sa_build_begin
-    uint32_t *fs_nflag = nullptr;                // [8] blocks flagged by the bucket sorter; given up on by the sample sorter; listed for its second attempt; ticket of the finishing kernel; blocks the probe did not call text-like
+    uint32_t *fs_nflag = nullptr;                // 32 bytes, cleared by k_fs_clear: [0] blocks flagged by the bucket sorter; [1] given up on by the sample sorter;
+                                                 // [2] listed for its second attempt / the tolerant form; [3] ticket of k_fs_finish's workgroups; [4] blocks the probe
+                                                 // did not call text-like; [5 .. 7] unused
     uint4    *fs_wl = nullptr;                   // [rows][fs_wl_cap] runs of equal codes: {index << 8 | bwt, first row, first entry, size}
     uint32_t *fs_wlcnt = nullptr;                // [rows] entries in use
     uint32_t  fs_wl_cap = 0;
@@ -207,7 +211,7 @@ struct SaScratch {
     bool      periodic = true;                   // glcPlanSetSorter 7 switches it off
     uint4    *per_info = nullptr;                // [rows] {period, first break, exit smaller?, slot}
     uint32_t *per_list = nullptr, *per_ok = nullptr;   // [rows] taken blocks by slot; whose rows were written
-    uint32_t *per_count = nullptr;               // [4] taken, bytes of the longest text of representatives, finished
+    uint32_t *per_count = nullptr;               // 16 bytes: [0] blocks taken, [1] bytes of the longest text of representatives, [2] blocks finished, [3] unused
     uint32_t *per_base = nullptr;                // [min(rows, PER_TAKE)][PER_NU + 1] first row of every representative
     uint8_t  *per_text = nullptr;                // [min(rows, PER_TAKE)][PER_NU] the texts of representatives
     uint32_t  last_periodic = 0;                 // blocks of the last sa_build this tier finished
@@ -222,7 +226,7 @@ struct SaScratch {
     // ends the streak.  A wrong guess costs time (that one call's blocks take the sample sorter), never correctness.
     uint32_t  textlike_streak = 0;
     bool      last_skipped = false;              // the plan's last sa_build skipped the bucket sorter's attempt
-    // second tier (bwt_bucket.hip, string sample sort): the blocks the bucket sorter flagged
+    // second tier (bwt_sample.hip, string sample sort): the blocks the bucket sorter flagged
     uint32_t *ss_list = nullptr;                 // [3 rows] their block numbers; behind them the ones that get a second attempt; then the ones for the tolerant form
     uint64_t *ss_split = nullptr;                // [rows][FS_MAXNB] first suffix of every bucket as a word [code : 36 | index : 20 | 0 : 8]
     uint32_t *ss_flag = nullptr;                 // [rows] this tier's give-up flags
@@ -282,6 +286,8 @@ hipError_t sa_build_finish(hipStream_t st, const uint8_t *text, size_t text_stri
 hipError_t fs_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk, SaScratch &s,
                     uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *sa_out);
 uint32_t   fs_bucket_log2(uint32_t n);
+// k_fs_scan (bwt_bucket.hip) for the nlisted blocks of `list`: fbase = exclusive scan of a block's bucket fills, a bucket past its slot flags the block
+hipError_t fs_scan(hipStream_t st, uint32_t nlisted, const uint32_t *fill, uint32_t *fbase, uint32_t *flag, const uint32_t *list);
 // second tier for the nflag blocks listed in s.ss_list: enqueues only; blocks it gives up on keep n in s.fs_lcnt
 // (the others get 0) and are counted in s.fs_nflag[1]
 hipError_t ss_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nflag, SaScratch &s,

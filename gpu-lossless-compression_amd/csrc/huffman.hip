@@ -369,8 +369,8 @@ hipError_t expand_streams(hipStream_t st, const uint32_t *d_in, const unsigned l
 }
 
 // ---------------------------------------------------------------------------
-#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
+// host side
+// ---------------------------------------------------------------------------
 hipError_t huff_scratch_alloc(HuffScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_sub = (nmax + HUFF_BLOCK - 1) / HUFF_BLOCK;

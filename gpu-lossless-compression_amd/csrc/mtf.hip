@@ -491,8 +491,8 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
 }
 
 // ---------------------------------------------------------------------------
-#define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
+// host side
+// ---------------------------------------------------------------------------
 hipError_t mtf_scratch_alloc(MtfScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_chunks = (nmax + MTF_CHUNK - 1) / MTF_CHUNK;

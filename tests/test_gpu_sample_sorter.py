@@ -1,4 +1,4 @@
-"""The second sorter tier (string sample sort, bwt_bucket.hip k_ss_*): the blocks the bucket sorter flags -- text, logs,
+"""The second sorter tier (string sample sort, bwt_sample.hip k_ss_*): the blocks the bucket sorter flags -- text, logs,
 heavy repeated phrases, low-entropy sources -- must come out bit-exact, on this tier where its design says so
 (glcPlanLastSortStatsEx: how many blocks each tier gave up on), and on the general sorter beyond its depth cap.
 Every case is checked against the oracle and against the other sorter modes (glcPlanSetSorter)."""

@@ -3,7 +3,7 @@
 `rows` Zipf blocks: stages back to back (pipelining off) against stage B of call k (inverse BWT: LF + walk + emit, side
 stream) under stage A of call k + 1 (Huffman + inverse MTF, the plan's stream).  The per-kernel profile of the serial pass
 says what stage A and stage B cost on their own, i.e. what perfect overlap would give.
-usage: dec_overlap_probe.py [rows] [calls]     env: GLC_LIB (variant build, e.g. -DGLC_WALK_PAD=86), GLC_SIDE_PRIO=least|same|greatest"""
+usage: dec_overlap_probe.py [rows] [calls]     env: GLC_LIB (variant build, e.g. -DGLC_WALK_PAD=86)"""
 import importlib.util, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)

@@ -1,7 +1,7 @@
 # where the decoder kernels' cycles go: instruction counts, busy cycles, LDS activity (rocprofv3 --pmc passes, --kernel-trace only)
-# usage: pmc_dec.sh [kernel-name-substring]   (default k_imtf_pos)
+# usage: pmc_dec.sh [kernel-name-substring]   (default k_imtf_pos_deque)
 cd /tmp; export TMPDIR=/tmp
-K=${1:-k_imtf_pos}
+K=${1:-k_imtf_pos_deque}
 run() {
   rm -rf /tmp/pm; timeout 200 rocprofv3 --pmc $1 --kernel-trace -d /tmp/pm -o p -- python $GRAFT_REPO_ROOT/tools/probe_dec.py 1024 1 > /tmp/l.txt 2>&1
   python - <<PY

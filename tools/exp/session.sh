@@ -2,7 +2,7 @@
 # One parameterised GPU-box session (replaces the 28 one-off session<N>.sh of rounds 4-5; those are in the history up to
 # commit 1a2090e): for every variant library tag, optionally the tests that cover what the variant touches, then `bench.py`
 # A/B against the in-tree library, alternating, twice.
-#   bash tools/exp/session.sh [-t "tests/test_gpu_bucket_sorter.py tests/test_gpu_bench_inputs.py"] [-k k_fs_part] [-e "GLC_FSP2_PER=8"] main tagA tagB ...
+#   bash tools/exp/session.sh [-t "tests/test_gpu_bucket_sorter.py tests/test_gpu_bench_inputs.py"] [-k k_fs_part] [-e "GLC_CHAIN_MIN=0"] main tagA tagB ...
 # Variants: GLC_CXXFLAGS="-D..." GLC_LIB_OUT=$PWD/gpu-lossless-compression_amd/variants/libglc_<tag>.so python gpu-lossless-compression_amd/build.py
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}" || exit 1
 V=$PWD/gpu-lossless-compression_amd/variants
