@@ -12,6 +12,9 @@
 // the plan's compress call at all: batched histograms and tables give every block's record size, the same kind / offset / raw /
 // CRC / table kernels follow, and the batched encoder writes the kind-2 records straight into the container, all on the plan's
 // stream.  The decoder accepts kinds 0, 1 and 2 in a version-3 frame and sends runs of kind 2 to the batched decoder.
+// The filter's delta mode (format version 4, delta.hip): with glcPlanSetContainerDelta on, the encoder stages a frame through the
+// fused delta + shuffle kernel instead of the shuffle and writes version 4 with flags = 1, whichever the codec; the decoder
+// treats such a frame as a version-3 one and inverts it with the fused inverse kernel.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 
@@ -84,10 +87,12 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 
 bool shuffle_elem_ok(uint32_t elem) { return elem == 2 || elem == 4 || elem == 8; }
 
-// elem: the shuffle's element size, 0 = no filter (version 1, as ever); codec: CT_CODEC_HUFF0 writes version 3
-void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem, uint32_t codec)
+// elem: the shuffle's element size, 0 = no filter (version 1, as ever); codec: CT_CODEC_HUFF0 writes version 3; delta (elem != 0
+// only): version 4 with the delta flag, whichever the codec
+void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem, uint32_t codec, bool delta)
 {
     h[0] = CT_MAGIC_STREAM; h[1] = codec == CT_CODEC_HUFF0 ? CT_VERSION_CODEC : (elem ? CT_VERSION_SHUFFLE : CT_VERSION);
+    if (delta) h[1] = CT_VERSION_DELTA | (CT_FLAG_DELTA << 16);
     h[2] = block_len; h[3] = elem;
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
     h[6] = crc32_host(h, 24); h[7] = 0;
@@ -104,6 +109,7 @@ struct Encoder {
     unsigned long long *d_len = nullptr;
     CtEncFrame fr[2] = {};
     uint32_t elem = 0;                                        // the plan's shuffle filter (0 = off)
+    bool delta = false;                                       // ... in delta mode
     uint32_t codec = CT_CODEC_BWT;                            // the plan's container codec
     CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
@@ -111,6 +117,7 @@ struct Encoder {
     hipError_t init()
     {
         elem = plan_container_shuffle(P.h);
+        delta = elem && plan_container_delta(P.h);
         codec = plan_container_codec(P.h);
         if (codec == CT_CODEC_HUFF0) {
             const size_t R = P.rows, wb = hdb_encode_work_bytes(R);
@@ -163,7 +170,8 @@ struct Encoder {
     ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
 
     // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With the filter on the
-    // frame is shuffled as one segment into staging and its blocks are cut from there; the input's own bytes still make crc_all.
+    // frame is shuffled (in delta mode: delta + shuffled) as one segment into staging and its blocks are cut from there; the
+    // input's own bytes still make crc_all.
     CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
     {
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
@@ -171,7 +179,7 @@ struct Encoder {
         const uint8_t *orig = nullptr;
         if (elem) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
-            CT_TRY(shuffle_device(P.st, d_in, stage[P.parity], (unsigned long long)nb * blk_len, elem, false));
+            CT_TRY((delta ? delta_shuffle_device : shuffle_device)(P.st, d_in, stage[P.parity], (unsigned long long)nb * blk_len, elem, false));
             orig = d_in;
             d_in = stage[P.parity];
         }
@@ -237,6 +245,7 @@ struct Decoder {
     unsigned long long *h_verdict = nullptr;                  // pinned
     uint32_t elem = 0;                                        // the stream header's shuffle filter (0 = none)
     uint32_t version = CT_VERSION;                            // the stream header's
+    bool delta = false;                                       // the stream header's flags, bit 0 (version 4)
     CtDecHuff0 h0 = {};
 
     // a version-3 frame's scratch, kept with the plan: tables for nb blocks, span-function prefixes for `chunk` of them at a
@@ -297,7 +306,7 @@ struct Decoder {
         CT_TRY(reserve(nb));
         uint8_t *out = final_out;
         if (elem) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
-        const bool v3 = version == CT_VERSION_CODEC;
+        const bool v3 = version >= CT_VERSION_CODEC;            // (version 4 is version 3 with another filter)
         KernelProf *prof = plan_prof(P.h);
         if (v3) CT_TRY(reserve_huff0(nb, blk_len));
         CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw, v3 ? &h0 : nullptr, prof));
@@ -334,7 +343,7 @@ struct Decoder {
         plan_join(P.h);
         CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, elem == 0));
         if (elem) {
-            CT_TRY(shuffle_device(P.st, out, final_out, (unsigned long long)nb * blk_len, elem, true));
+            CT_TRY((delta ? delta_shuffle_device : shuffle_device)(P.st, out, final_out, (unsigned long long)nb * blk_len, elem, true));
             CT_TRY(ct_dec_fold(P.st, f, final_out, nb, blk_len, state));
         }
         return CUDPP_SUCCESS;
@@ -352,14 +361,17 @@ struct Decoder {
     }
 };
 
-// the checks on a stream header; returns block_len (0 = refused), the shuffle's element size (0 = no filter) and the version
-uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem, uint32_t *version)
+// the checks on a stream header; returns block_len (0 = refused), the shuffle's element size (0 = no filter), the version and
+// whether the filter is in delta mode (version 4, whose only legal flags value is 1)
+uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem, uint32_t *version, bool *delta)
 {
     if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
+    const bool v4 = h[1] == (CT_VERSION_DELTA | (CT_FLAG_DELTA << 16)) && shuffle_elem_ok(h[3]);
     if (!(h[1] == CT_VERSION && h[3] == 0) && !(h[1] == CT_VERSION_SHUFFLE && shuffle_elem_ok(h[3])) &&
-        !(h[1] == CT_VERSION_CODEC && (h[3] == 0 || shuffle_elem_ok(h[3])))) return 0;
+        !(h[1] == CT_VERSION_CODEC && (h[3] == 0 || shuffle_elem_ok(h[3]))) && !v4) return 0;
     *elem = h[3];
-    *version = h[1];
+    *version = h[1] & 0xFFFFu;
+    *delta = v4;
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return 0;
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
     return h[2];
@@ -455,7 +467,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     CT_TRY(dout.reserve(ocap));
     CT_TRY(hout.reserve(ocap));
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem, E.codec);
+    make_header(hdr, E.P.n, len, E.elem, E.codec, E.delta);
     if (!out.write(hdr, CT_HDR)) return fail(plan, CT_CAPACITY);
     unsigned long long total = CT_HDR;
     hipStream_t cs = nullptr;
@@ -519,7 +531,7 @@ CUDPPResult decompress_stream(CUDPPHandle plan, Source &src, unsigned long long 
     if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
     if (!src.read(hdr, CT_HDR)) return fail(plan, CT_TRUNCATED);
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version, &D.delta);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -579,7 +591,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(E.init());
     uint8_t *out = static_cast<uint8_t *>(d_out);
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem, E.codec);
+    make_header(hdr, E.P.n, len, E.elem, E.codec, E.delta);
     CT_TRY(ct_enc_header(E.P.st, out, cap, hdr, E.state));
     CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap, [](unsigned long long) { return CUDPP_SUCCESS; });
     if (r != CUDPP_SUCCESS) return r;
@@ -606,7 +618,7 @@ CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, uns
     CT_TRY(hipMemcpyAsync(hdr, in, CT_HDR, hipMemcpyDeviceToHost, D.P.st));
     CT_TRY(hipStreamSynchronize(D.P.st));
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version);
+    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version, &D.delta);
     if (!block_len) return fail(plan, CT_STREAM_HEADER);
     if (total > cap || (total && !d_out)) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
@@ -711,14 +723,15 @@ static CUDPPResult shuffle_segments_api(const void *d_inBase, void *d_outBase, c
                                     static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, (uint32_t)count, elem, inverse));
 }
 
-static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse)
+static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse,
+                                      bool delta = false)
 {
     if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     if (len == 0) return CUDPP_SUCCESS;
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
     if (!d_in || !d_out || (a < b ? b - a : a - b) < len) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res(shuffle_device(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out),
-                                  len, elem, inverse));
+    return hip_res((delta ? delta_shuffle_device : shuffle_device)(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in),
+                                                                   static_cast<uint8_t *>(d_out), len, elem, inverse));
 }
 
 CUDPPResult glcShuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
@@ -743,12 +756,41 @@ CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long
     return shuffle_device_api(d_in, d_out, len, elem, stream, true);
 }
 
+CUDPPResult glcDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, false, true);
+}
+
+CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, true, true);
+}
+
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     Plan P;
     if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
     if (elem > 1 && !shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     plan_set_container_shuffle(plan, elem > 1 ? elem : 0);
+    if (elem <= 1) plan_set_container_delta(plan, false);      // (no delta without the shuffle)
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (on > 1 || (on && !plan_container_shuffle(plan))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    plan_set_container_delta(plan, on != 0);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_delta(plan) ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -82,6 +82,9 @@ hipError_t crc32_segments(hipStream_t st, const uint8_t *base, const unsigned lo
 hipError_t shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, bool inverse);
 hipError_t shuffle_segments(hipStream_t st, const uint8_t *inBase, uint8_t *outBase, const unsigned long long *d_off,
                             const unsigned long long *d_len, uint32_t count, uint32_t elem, bool inverse);
+// the shuffle of the differences of neighbouring elements, restarting every 2048 elements, and its inverse (delta.hip); one
+// segment, the same rules
+hipError_t delta_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, bool inverse);
 
 // ---------------------------------------------------------------------------
 // layout (little-endian; every section 8-byte aligned)
@@ -91,9 +94,11 @@ constexpr uint32_t CT_MAGIC_FRAME  = 0x46434C47u;   // "GLCF"
 constexpr uint32_t CT_MAGIC_END    = 0x45434C47u;   // "GLCE"
 constexpr uint32_t CT_VERSION = 1, CT_VERSION_SHUFFLE = 2;   // 2: header word 3 = the shuffle's element size (2, 4, 8)
 constexpr uint32_t CT_VERSION_CODEC = 3;                     // 3: kind 2 is legal; header word 3 = element size or 0 (no filter)
+constexpr uint32_t CT_VERSION_DELTA = 4;                     // 4: version 3 with flags in the upper half of the version dword
+constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the only one): the filter is delta + shuffle; elem 2, 4 or 8
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
-constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), version 3 only
+constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
 
 // failure classes of glcContainerLastError (out[0])
@@ -140,6 +145,8 @@ void plan_join(CUDPPHandle plan);                          // the plan's stream 
 bool plan_pipelined(CUDPPHandle plan);
 uint32_t plan_container_shuffle(CUDPPHandle plan);
 void plan_set_container_shuffle(CUDPPHandle plan, uint32_t elem);
+bool plan_container_delta(CUDPPHandle plan);               // the filter's delta mode (only ever on with the shuffle on)
+void plan_set_container_delta(CUDPPHandle plan, bool on);
 hipError_t plan_stage(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
 // the plan's stream waits until the encode call that last used the next call's parity has released its input (pipelining:
 // that call's Huffman stages and container kernels read their input from the side stream)

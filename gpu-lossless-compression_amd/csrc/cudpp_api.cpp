@@ -85,6 +85,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     bool side_busy = false;                      // side-stream work issued since the last join
     // container filter (glcPlanSetContainerShuffle): the encoder's element size and the frame staging both directions share
     uint32_t ct_shuffle = 0;
+    bool ct_delta = false;                       // (glcPlanSetContainerDelta: the filter's delta mode, format version 4)
     void *ct_stage[2] = {nullptr, nullptr};
     size_t ct_stage_bytes[2] = {0, 0};
     // container codec (glcPlanSetContainerCodec) and the order-0 codec's scratch: [0] the encoder's, [1] the decoder's
@@ -878,6 +879,8 @@ hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint
     return hipSuccess;
 }
 
+bool plan_container_delta(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_delta; }
+void plan_set_container_delta(CUDPPHandle planHandle, bool on) { plan_from<CompressPlan>(planHandle)->ct_delta = on; }
 uint32_t plan_container_codec(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_codec; }
 void plan_set_container_codec(CUDPPHandle planHandle, uint32_t codec) { plan_from<CompressPlan>(planHandle)->ct_codec = codec; }
 

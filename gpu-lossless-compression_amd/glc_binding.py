@@ -653,7 +653,8 @@ def hd_segments_decode(d_units, d_unit_offsets, d_nunits, d_hist, d_out, d_out_o
 CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcContainerDecompressDevice", "glcContainerCompress",
                      "glcContainerDecompress", "glcContainerCompressFile", "glcContainerDecompressFile", "glcCrc32Segments",
                      "glcContainerLastError", "glcShuffleSegments", "glcUnshuffleSegments", "glcShuffleDevice", "glcUnshuffleDevice",
-                     "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec"]
+                     "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec",
+                     "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta"]
 CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0 = 0, 1
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
@@ -676,12 +677,14 @@ def _ct():
         L.glcContainerLastError.argtypes = [sz, ullp]
         for nm in ("glcShuffleSegments", "glcUnshuffleSegments"):
             getattr(L, nm).argtypes = [vp, vp, vp, vp, sz, C.c_uint, vp]
-        for nm in ("glcShuffleDevice", "glcUnshuffleDevice"):
+        for nm in ("glcShuffleDevice", "glcUnshuffleDevice", "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, vp]
         L.glcPlanSetContainerShuffle.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerShuffle.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcPlanSetContainerCodec.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerCodec.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcPlanSetContainerDelta.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerDelta.argtypes = [sz, C.POINTER(C.c_uint)]
         for nm in CONTAINER_SYMBOLS[1:]:
             getattr(L, nm).restype = C.c_int
         L._ct_ready = True
@@ -785,6 +788,18 @@ def container_get_codec(plan):
     return int(c.value)
 
 
+def container_set_delta(plan, on):
+    """the delta mode of the plan's container ENCODER filter (format version 4): True / 1 needs the shuffle on (elem 2, 4 or 8);
+    container_set_shuffle(plan, 0) also switches it off.  The decoder reads what was done from the stream."""
+    _chk("glcPlanSetContainerDelta", _ct().glcPlanSetContainerDelta(plan.handle, int(on)))
+
+
+def container_get_delta(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerDelta", _ct().glcPlanGetContainerDelta(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
 def _shuffle(fn, d_in, elem, out, stream):
     import torch
     x = d_in.reshape(-1)
@@ -805,6 +820,17 @@ def shuffle(d_in, elem, out=None, stream=None):
 def unshuffle(d_in, elem, out=None, stream=None):
     """the inverse of shuffle"""
     return _shuffle("glcUnshuffleDevice", d_in, elem, out, stream)
+
+
+def delta_shuffle(d_in, elem, out=None, stream=None):
+    """shuffle of the differences of neighbouring elements (little-endian unsigned, modulo 2^(8 elem), restarting every 2048
+    elements) in one pass; the rules of shuffle"""
+    return _shuffle("glcDeltaShuffleDevice", d_in, elem, out, stream)
+
+
+def undelta_unshuffle(d_in, elem, out=None, stream=None):
+    """the inverse of delta_shuffle"""
+    return _shuffle("glcUndeltaUnshuffleDevice", d_in, elem, out, stream)
 
 
 def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):

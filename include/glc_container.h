@@ -21,6 +21,13 @@
  * 1.275 against 1.121, encode 533 against 103 GB/s, decode 100 against 45 GB/s; sizes for other inputs in INTEGRATION.md 4b.
  * Such a stream is format version 3, with or without the filter.
  *
+ * Integer series (timestamps, sorted ids, offsets, counters, ADC samples): the filter's delta mode, off by default.  With
+ * glcPlanSetContainerDelta on, a frame's elements are replaced by their differences to the element in front (modulo 2^(8 elem),
+ * restarting every 2048 elements of the frame) before the planes are gathered, in the same single pass over the frame; the stream
+ * is format version 4 with either codec.  Slowly varying integers have flat byte histograms after the shuffle alone and peaked ones
+ * after the delta, which is what the order-0 codec needs: the model's sizes are in INTEGRATION.md 4b.  It hurts
+ * noise-like data.  The decoder reads what was done from the stream header.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -90,12 +97,28 @@ CUDPPResult glcUnshuffleSegments(const void *d_inBase, void *d_outBase, const un
 CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 
+/* Delta + shuffle in one pass, and its inverse: with x[i] element i of the segment as a little-endian unsigned integer of `elem`
+ * bytes, d[i] = x[i] where i is a multiple of 2048 and x[i] - x[i - 1] modulo 2^(8 elem) elsewhere; out[j * q + i] = byte j of
+ * d[i]; the last len % elem bytes copied in place.  The inverse gathers d and sums it from the last multiple of 2048 up to i.
+ * The rules of glcShuffleDevice: elem 2, 4 or 8, any length and byte alignment, out of place, overlapping buffers and a bad elem
+ * refused (CUDPP_ERROR_ILLEGAL_CONFIGURATION) with nothing written.  Single segment only. */
+CUDPPResult glcDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
+CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
+
 /* The element size the container ENCODER of this plan shuffles by: 0 or 1 = off (the default), 2, 4, 8; anything else is
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it; the decoder
  * ignores it (the stream header says what was done).  The first filtered call allocates device staging of one frame (rows * n
  * bytes; two with pipelining on), the first filtered decode staging of the largest frame seen; both live as long as the plan. */
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem);
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem);
+
+/* The delta mode of the ENCODER's filter: on = 1 stages every frame through delta + shuffle instead of the shuffle and writes
+ * format version 4 (flags = 1), with either codec; 0 (the default) writes versions 1 to 3 byte for byte as ever.  on = 1 while
+ * the plan's shuffle is off, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.
+ * glcPlanSetContainerShuffle(plan, 0 or 1) also switches the delta off; a change among 2, 4 and 8 keeps it.  The decoder
+ * ignores the setting and reads all four versions. */
+CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on);
 
 /* The codec the container ENCODER of this plan uses.  GLC_CONTAINER_CODEC_BWT (the default) writes format version 1, or 2 with
  * the shuffle filter on, byte for byte as ever.  GLC_CONTAINER_CODEC_HUFF0 writes version 3: a block is an order-0 Huffman

@@ -13,7 +13,12 @@
 N(0,1), as bench.py generates it), smooth32 / smooth64 (a sine plus a random walk) and quant16 (uint16 Laplace codes around
 512).  The comparison with the compact array needs input that shrinks: it runs for zipf only.
 
-python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM]"""
+Integer series, also generated on the device, after tests/series_datagen.py: ts64 (int64 timestamps, steps uniform in [900, 1100)),
+ids32 (sorted uint32 ids below 2^31), ctr32 (uint32 counters, Poisson(3) increments) and adc16 (12-bit sine plus N(0, 3) noise in
+uint16).  --delta switches the filter's delta mode on for the filtered setting (glcPlanSetContainerDelta, format version 4), --codec 1
+the order-0 codec for both settings.
+
+python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]"""
 import argparse
 import json
 import os
@@ -23,7 +28,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2}
+DATA_ELEM = {"zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2}
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -40,13 +45,25 @@ def typed_on_device(torch, L, dev, kind, total):
         x = torch.randn(count, dtype=torch.float64, device=dev, generator=g).mul_(0.01).cumsum_(0)
         x.add_(torch.arange(count, dtype=torch.float64, device=dev).mul_(2.0 * 3.141592653589793 / 5000.0).sin_().mul_(100.0))
         return (x if elem == 8 else x.to(torch.float32)).view(torch.uint8)
+    if kind == "ts64":
+        return torch.randint(900, 1100, (total // 8,), dtype=torch.int64, device=dev, generator=g).cumsum_(0).view(torch.uint8)
+    if kind == "ids32":
+        return torch.randint(0, 2 ** 31, (total // 4,), dtype=torch.int64, device=dev, generator=g).sort().values.to(torch.int32).view(torch.uint8)
+    if kind == "ctr32":
+        inc = torch.poisson(torch.full((total // 4,), 3.0, dtype=torch.float32, device=dev), generator=g).to(torch.int64)
+        return inc.cumsum_(0).to(torch.int32).view(torch.uint8)
+    if kind == "adc16":
+        t = torch.arange(total // 2, dtype=torch.float64, device=dev).mul_(2.0 * 3.141592653589793 / 700.0).sin_().mul_(1500.0).add_(2048.0)
+        t.add_(torch.randn(total // 2, dtype=torch.float64, device=dev, generator=g).mul_(3.0))
+        return t.round_().clamp_(0, 4095).to(torch.int32).to(torch.int16).view(torch.uint8)
     u = torch.rand(total // 2, dtype=torch.float32, device=dev, generator=g).sub_(0.5)
     lap = u.sign() * torch.log1p(-2.0 * u.abs()).mul_(-6.0)
     return (512.0 + lap).round_().clamp_(0, 65535).to(torch.int32).to(torch.int16).view(torch.uint8)
 
 
-def filter_section(torch, glc, plan, d_in, total, elem, timed):
-    """the container with the shuffle filter off and on, on one plan: sizes, rates, kernel profile and sorter tiers"""
+def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
+    """the container with the shuffle filter off and on (with `delta`: in delta mode), on one plan: sizes, rates, kernel profile
+    and sorter tiers"""
     n = plan.n
     cap = glc.container_bound(total, n)
     cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
@@ -60,6 +77,8 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed):
 
     for setting in (0, elem):
         glc.container_set_shuffle(plan, setting)
+        if setting and delta:
+            glc.container_set_delta(plan, 1)
         t_enc = timed(enc)
         clen = int(d_len.item())
         stats = dict(flagged_general=list(plan.last_sort_stats()), retries=plan.last_sort_retries(), resumed=plan.last_sort_resumed(),
@@ -78,7 +97,7 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed):
         plan.synchronize()
         prof_dec = plan.kernel_profiles()
         plan.enable_timing(0)
-        res["off" if not setting else "elem%d" % setting] = {
+        res["off" if not setting else ("delta%d" if delta else "elem%d") % setting] = {
             "container_bytes": clen, "ratio": total / clen, "encode_GBps": total / t_enc / 1e9, "decode_GBps": total / t_dec / 1e9,
             "last_frame_sort": stats,
             "encode_kernels_ms": {k: round(v["ms"], 3) for k, v in sorted(prof_enc.items(), key=lambda kv: -kv[1]["ms"])},
@@ -95,6 +114,8 @@ def main():
     ap.add_argument("--pipelining", type=int, default=1)
     ap.add_argument("--data", choices=sorted(DATA_ELEM), default="zipf")
     ap.add_argument("--shuffle", type=int, default=0, choices=[0, 2, 4, 8], metavar="ELEM")
+    ap.add_argument("--delta", action="store_true", help="the filtered setting uses the filter's delta mode (format version 4)")
+    ap.add_argument("--codec", type=int, default=0, choices=[0, 1], help="the filter section's container codec: 0 BWT, 1 order-0")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -134,7 +155,9 @@ def main():
     if args.data != "zipf":
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
-            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed)
+            glc.container_set_codec(plan, args.codec)
+            res["codec"] = args.codec
+            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
         print(json.dumps(res))
         return
     # --- CRC against the read probe
@@ -196,7 +219,10 @@ def main():
         assert torch.equal(out, d_in) and int(d_len.item()) == total
         if args.shuffle:
             del compact, out
-            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle, timed)
+            glc.container_set_codec(plan, args.codec)
+            res["codec"] = args.codec
+            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle, timed, args.delta)
+            glc.container_set_codec(plan, 0)
     res.update({"compact_encode_GBps": total / t_enc / 1e9, "container_encode_GBps": total / t_cenc / 1e9,
                 "encode_ratio": t_enc / t_cenc,
                 "compact_decode_GBps": total / t_dec / 1e9, "container_decode_GBps": total / t_cdec / 1e9,

@@ -3,6 +3,8 @@
   copy       hipMemcpyAsync, device to device, of the buffer: one read and one write per byte, the yardstick
   shuffle N  glcShuffleDevice with element size N = 2, 4, 8 on the same buffers
   unshuf N   glcUnshuffleDevice
+  delta-shuffle N / undelta-unshuffle N
+             glcDeltaShuffleDevice / glcUndeltaUnshuffleDevice, the fused kernels of the filter's delta mode
 
 Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each run is bracketed by device events.  The
 table gives the median, the fastest and the slowest run of every variant, as GB/s of input bytes (the traffic is twice that)
@@ -66,6 +68,8 @@ def main():
     for elem in (2, 4, 8):
         variants.append(("shuffle %d" % elem, kernel(L.glcShuffleDevice, elem)))
         variants.append(("unshuf %d" % elem, kernel(L.glcUnshuffleDevice, elem)))
+        variants.append(("delta-shuffle %d" % elem, kernel(L.glcDeltaShuffleDevice, elem)))
+        variants.append(("undelta-unshuffle %d" % elem, kernel(L.glcUndeltaUnshuffleDevice, elem)))
     # correctness of what is timed, once, at this size and alignment
     for elem in (2, 4, 8):
         kernel(L.glcShuffleDevice, elem)()
@@ -75,7 +79,17 @@ def main():
         back = torch.empty_like(src)
         glc._chk("unshuffle", L.glcUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, None))
         assert torch.equal(back, src), elem
-        del back, want
+        # delta + shuffle: the differences within runs of 2048 elements, then the same planes
+        x = src[:q * elem].clone().view({2: torch.int16, 4: torch.int32, 8: torch.int64}[elem])     # (a copy: aligned for the view)
+        d = x.clone()
+        d[1:] -= x[:-1]
+        d[::2048] = x[::2048]
+        want = d.view(torch.uint8).view(q, elem).t().contiguous().view(-1)
+        kernel(L.glcDeltaShuffleDevice, elem)()
+        assert torch.equal(dst[:q * elem], want) and torch.equal(dst[q * elem:], src[q * elem:]), elem
+        glc._chk("undelta", L.glcUndeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, None))
+        assert torch.equal(back, src), elem
+        del back, want, d, x
     times = {name: [] for name, _ in variants}
     events = []
     for r in range(args.warmup + args.reps):
