@@ -654,12 +654,25 @@ __global__ __launch_bounds__(FSS_NT) void k_fs_sort(uint32_t n, uint32_t nbl, co
 //     per wave with ONE ballot and handled behind a wave-uniform branch (k_fs_sort: three nested divergent branches per
 //     item, executed or not);
 //   * the row of suffix 0 (the BWT index) is looked for in the ONE bucket k_fs_part2 saw it go to (zero_bucket), not in
-//     every word of every bucket.
-// Same LDS layout and access pattern (a word is ranked AT ITS POSITION of the bin-sorted array: bin bounds, neighbours and
-// the staged row of neighbouring lanes share banks -- the owner-ranked form measured in round 4 lost more to LDS bank
-// conflicts than it saved in instructions, tools/exp/attic), same work list, entry for entry.
+//     every word of every bucket -- behind a branch the compiler cannot fold into the words' own conditions (it did: the
+//     compares ran for every slot of every workgroup and the bucket test was ANDed in last);
+//   * the bin of a word is a field of its HIGH dword (bshift = 52 - nbl >= 43): one 32-bit shift, no 64-bit temporaries.
+// Instances by the number of FULL rounds.  A bucket of an i.i.d.-like block holds 2048 +- 7 % words: c / 512 is 3 or 4, and
+// eight slots per thread (a slot may hold 4032 words) meant three to four slots initialised, tested per lane in every loop
+// and guarded in every phase for nothing.  After the common prologue -- the flag exit, the counters cleared, three rounds
+// of words requested before the fill is known -- ONE wave-uniform branch picks
+//   * rounds<3> / rounds<4>: FULL + 1 slots, slots 1 .. FULL unconditional, slot 0 under `tid < part`, nothing else; and
+//     PHASE-MAJOR: every slot's LDS requests of a step are issued before the first answer is waited for (all counting
+//     atomics, all bin starts, and in the rank step all words, then all bin bounds, then all keys), the rare case is ORed
+//     over the thread's slots into ONE ballot and ONE branch per wave.  Item-major, a thread walked ~25 dependent LDS round
+//     trips where the data ask for ~5.  (`pos == ~0` comes with s_deep = 1 only, and the kernel leaves on s_deep before
+//     anything is staged: the staging and work-list loops test no position.)
+//   * everything else (small and skewed blocks, c / 512 in {0, 1, 2, 5, 6, 7}): the eight-slot guarded body.
+// Same LDS layout and access pattern in all of them (a word is ranked AT ITS POSITION of the bin-sorted array: bin bounds,
+// neighbours and the staged row of neighbouring lanes share banks -- the owner-ranked form measured in round 4 lost more to
+// LDS bank conflicts than it saved in instructions, tools/exp/attic), same rank rule, same work list, entry for entry.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(FSS_NT) void k_fs_sort_bwt(uint32_t nbl, const uint64_t *__restrict__ keys, size_t kstride,
+__global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_fs_sort_bwt(uint32_t nbl, const uint64_t *__restrict__ keys, size_t kstride,
                                                         const uint32_t *__restrict__ fill, const uint32_t *__restrict__ fbase,
                                                         uint32_t *__restrict__ flag, uint8_t *__restrict__ bwt_out,
                                                         size_t bwt_stride, int *__restrict__ d_index, uint4 *__restrict__ wl,
@@ -683,48 +696,31 @@ __global__ __launch_bounds__(FSS_NT) void k_fs_sort_bwt(uint32_t nbl, const uint
     if (tid == 0) { s_deep = flag[b]; s_wl = 0; }              // (one read: another bucket may flag the block meanwhile)
     for (uint32_t i = tid; i < FS_BINS / 2; i += FSS_NT) s_cp[i] = 0;
     const uint64_t *K = keys + (size_t)b * kstride + (size_t)bk * FS_CAP;
-    uint64_t w[FSS_ITEMS];
-#pragma unroll
-    for (int r = 0; r < FSS_ITEMS; r++) w[r] = ~0ull;
     // The first FSS_SPEC full rounds are requested BEFORE the bucket's fill is known: a bucket of an i.i.d.-like block holds
     // 2048 +- 7 % words, so words 0 .. 1535 are (nearly) always there, and fill -> words was two memory latencies in a row at
     // the head of every workgroup's chain.  A slot has FS_CAP words whatever its fill: reading past the fill is harmless, and
     // such a round is never looked at (r <= full guards every use).
     constexpr int FSS_SPEC = 3;
+    uint64_t ws[FSS_SPEC + 1];
 #pragma unroll
-    for (int r = 1; r <= FSS_SPEC; r++) w[r] = K[(r - 1) * FSS_NT + tid];
+    for (int r = 1; r <= FSS_SPEC; r++) ws[r] = K[(r - 1) * FSS_NT + tid];
     const uint32_t c = fill[(size_t)b * FS_MAXNB + bk];
     const uint32_t R0 = fbase[(size_t)b * FS_MAXNB + bk];
+    const bool zb = zero_bucket[b] == bk;                      // (uniform) suffix 0 is one of this bucket's words
     const uint32_t cc = c <= FS_FILLMAX ? c : 0u;              // (a fuller bucket has flagged its block in k_fs_scan)
     // item r of a thread: r = 0 -> word full * 512 + tid of the partial round (lanes tid < part), r >= 1 -> word
     // (r - 1) * 512 + tid of a full round (all lanes, r <= full)
     const uint32_t full = cc / FSS_NT, part = cc % FSS_NT;
     const bool v0 = tid < part;
     const uint32_t i0 = full * FSS_NT + tid;
-    if (v0) w[0] = K[i0];
-#pragma unroll
-    for (int r = FSS_SPEC + 1; r < FSS_ITEMS; r++)
-        if ((uint32_t)r <= full) w[r] = K[(r - 1) * FSS_NT + tid];
-    if (tid < FSS_LOOK && cc) s_w[cc + tid] = ~0ull;                  // what the rank step reads past the last bin compares as larger
-    __syncthreads();
-    if (s_deep || cc == 0) return;                             // flagged: the block is another sorter's
-    // 1. counting sort on the 12 bits below the bucket number (arrival order inside a bin: any order will do)
-    const uint32_t bshift = 64 - nbl - FS_BIN_BITS;
-    uint32_t rk[FSS_ITEMS];
-#pragma unroll
-    for (int r = 0; r < FSS_ITEMS; r++) rk[r] = 0;
-    {
-        auto count = [&](int r) {
-            const uint32_t bin = (uint32_t)(w[r] >> bshift) & (FS_BINS - 1), sh = 16 * (bin & 1);
-            rk[r] = (atomicAdd(&s_cp[bin >> 1], 1u << sh) >> sh) & 0xFFFFu;
-        };
-        if (v0) count(0);
-#pragma unroll
-        for (int r = 1; r < FSS_ITEMS; r++)
-            if ((uint32_t)r <= full) count(r);
-    }
-    __syncthreads();
-    {
+    const uint32_t bshift = 64 - nbl - FS_BIN_BITS;            // >= 43: the bin lies in a word's high dword
+    const uint32_t hshift = bshift - 32, kshift = bshift - 28; // ... at hshift there, at kshift in a sorted word's key
+    // rows R0 .. R0 + c of the block's BWT are staged so that aligned dwords of LDS are aligned dwords of the output
+    uint8_t *O = bwt_out + (size_t)b * bwt_stride + R0;
+    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(O) & 3u);
+
+    // bin counters -> bin starts (both 16-bit pairs), between the count and the scatter step of every instance
+    auto bin_starts = [&]() __attribute__((always_inline)) {
         constexpr int PW = FS_BINS / 2 / FSS_NT;               // packed words per thread
         uint32_t v[PW], sum = 0;
 #pragma unroll
@@ -737,94 +733,38 @@ __global__ __launch_bounds__(FSS_NT) void k_fs_sort_bwt(uint32_t nbl, const uint
             run = hi + (v[k] >> 16);
         }
         if (tid == FSS_NT - 1) s_cp[FS_BINS / 2] = c;          // end of the last bin
-    }
-    __syncthreads();
-    {
-        // in LDS a word is [code bits 28..59 : 32 | the word's low dword (code bits 28..31, index, BWT byte) : 32]: the rank step
-        // compares HIGH DWORDS only -- four 4-byte reads where the whole words were four 8-byte reads and a funnel shift each
-        auto scatter = [&](int r) {
-            const uint32_t lo = (uint32_t)w[r], hi = (uint32_t)(w[r] >> 32);
-            s_w[s16[(uint32_t)(w[r] >> bshift) & (FS_BINS - 1)] + rk[r]] =
-                ((uint64_t)__builtin_amdgcn_alignbit(hi, lo, 28) << 32) | lo;
-        };
-        if (v0) scatter(0);
-#pragma unroll
-        for (int r = 1; r < FSS_ITEMS; r++)
-            if ((uint32_t)r <= full) scatter(r);
-    }
-    __syncthreads();
-    // 2. final position = bin start + number of smaller codes in the bin (thread = the words at positions i0 / (r - 1) NT +
-    //    tid of the bin-sorted array).  The four words from the bin start are compared in straight-line code with no bounds
-    //    at all -- what lies behind the bin's end is a larger code or a sentinel; a bin of more than four, or a second word
-    //    with my code among the four, is the rare case: detected per wave, redone exactly over the whole bin.
-    const bool zb = zero_bucket[b] == bk;                       // (uniform) suffix 0 is one of this bucket's words
-    uint32_t pos[FSS_ITEMS], grp[FSS_ITEMS];                   // grp = group start << 16 | group size (0: not tied)
-#pragma unroll
-    for (int r = 0; r < FSS_ITEMS; r++) { pos[r] = 0xFFFFFFFFu; grp[r] = 0; }
-    {
-        auto rank = [&](int r, uint32_t p) {
-            const uint64_t wv = s_w[p];
-            w[r] = wv;
-            const uint32_t key = (uint32_t)(wv >> 32);         // inside a bin only the low 32 bits of the code can differ
-            const uint32_t bin = (key >> (bshift - 28)) & (FS_BINS - 1);
-            const uint32_t gs = s16[bin], ge = s16[bin + 1];
-            uint32_t less = 0, eqt = 0;
-            const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs + 1;
-#pragma unroll
-            for (uint32_t t = 0; t < FSS_LOOK; t++) {
-                const uint32_t kq = B[2 * t];
-                less += kq < key ? 1u : 0u;
-                eqt += kq == key ? 1u : 0u;
-            }
-            uint32_t at = gs + less;
-            const bool rare = (ge - gs > FSS_LOOK) | (eqt > 1);
-            if (__builtin_amdgcn_ballot_w64(rare) != 0) {      // (wave-uniform)
-                if (rare) {
-                    if (ge - gs > FS_MAX_GROUP) { s_deep = 1; at = 0xFFFFFFFFu; }
-                    else {
-                        uint32_t ls = 0, eq = 0, eqb = 0;
+    };
+    // in LDS a word is [code bits 28..59 : 32 | the word's low dword (code bits 28..31, index, BWT byte) : 32]: the rank step
+    // compares HIGH DWORDS only -- four 4-byte reads where the whole words were four 8-byte reads and a funnel shift each
+    auto sorted_word = [](uint64_t wv) -> uint64_t {
+        const uint32_t lo = (uint32_t)wv, hi = (uint32_t)(wv >> 32);
+        return ((uint64_t)__builtin_amdgcn_alignbit(hi, lo, 28) << 32) | lo;
+    };
+    // the rank step's rare case, exact over the whole bin [gs, ge) for the word at position p: its row, and its group if
+    // other words share its code
+    auto rank_rare = [&](uint32_t key, uint32_t p, uint32_t gs, uint32_t ge, uint32_t &at, uint32_t &grp) __attribute__((always_inline)) {
+        if (ge - gs > FS_MAX_GROUP) { s_deep = 1; at = 0xFFFFFFFFu; }
+        else {
+            uint32_t ls = 0, eq = 0, eqb = 0;
 #pragma clang loop unroll(disable)
-                        for (uint32_t q = gs; q < ge; q++) {
-                            const uint32_t kq = reinterpret_cast<const uint32_t *>(s_w)[2 * q + 1];
-                            ls += kq < key; eq += kq == key; eqb += (kq == key) & (q < p);
-                        }
-                        at = gs + ls;
-                        if (eq > 1) { grp[r] = (at << 16) | eq; at += eqb; }
-                    }
-                }
+            for (uint32_t q = gs; q < ge; q++) {
+                const uint32_t kq = reinterpret_cast<const uint32_t *>(s_w)[2 * q + 1];
+                ls += kq < key; eq += kq == key; eqb += (kq == key) & (q < p);
             }
-            pos[r] = at;
-        };
-        if (v0) rank(0, i0);
-#pragma unroll
-        for (int r = 1; r < FSS_ITEMS; r++)
-            if ((uint32_t)r <= full) rank(r, (r - 1) * FSS_NT + tid);
-        if (zb) {
-#pragma unroll
-            for (int r = 0; r < FSS_ITEMS; r++)
-                if (pos[r] != 0xFFFFFFFFu && ((uint32_t)w[r] & 0x0FFFFF00u) == 0 && !grp[r]) d_index[b] = (int)(R0 + pos[r]);
+            at = gs + ls;
+            if (eq > 1) { grp = (at << 16) | eq; at += eqb; }
         }
-    }
-    __syncthreads();                                           // s_cp (bin starts) is dead from here: it takes the BWT bytes
-    if (s_deep) { if (tid == 0) atomicOr(&flag[b], 2u); return; }
-    // rows R0 .. R0 + c of the block's BWT are staged so that aligned dwords of LDS are aligned dwords of the output
-    uint8_t *O = bwt_out + (size_t)b * bwt_stride + R0;
-    const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(O) & 3u);
-    // 3. tied groups -> the block's work list.  Entries are reserved with ONE global atomic per workgroup.  (Round 5: the
-    //    ~1.5 us a workgroup sits out for its return are NOT on the kernel's critical path -- with entries of the bucket's own
-    //    and no atomic at all the kernel ran 3.50 against 3.47 ms per GiB, and k_fs_ties, which then has to walk 512 short
-    //    lists per block, 0.32 against 0.18.)
-    bool any = false;
-#pragma unroll
-    for (int r = 0; r < FSS_ITEMS; r++) {
-        if (pos[r] != 0xFFFFFFFFu) s_cb[shift + pos[r]] = (uint8_t)w[r];      // (rows of tied groups are rewritten by k_fs_ties)
-        if (grp[r]) {
-            any = true;
-            const uint32_t gp = grp[r] >> 16, gs = grp[r] & 0xFFFFu;
-            if (pos[r] == gp) reinterpret_cast<uint32_t *>(s_w)[2 * gp + 1] = atomicAdd(&s_wl, gs);   // (the codes are dead)
-        }
-    }
-    if (__syncthreads_or((int)any)) {
+    };
+    // 3. (every instance) tied groups -> the block's work list.  Entries are reserved with ONE global atomic per workgroup.
+    //    (Round 5: the ~1.5 us a workgroup sits out for its return are NOT on the kernel's critical path -- with entries of the
+    //    bucket's own and no atomic at all the kernel ran 3.50 against 3.47 ms per GiB, and k_fs_ties, which then has to walk
+    //    512 short lists per block, 0.32 against 0.18.)
+    auto wl_reserve = [&](uint32_t pos, uint32_t grp) __attribute__((always_inline)) {
+        const uint32_t gp = grp >> 16, gs = grp & 0xFFFFu;
+        if (pos == gp) reinterpret_cast<uint32_t *>(s_w)[2 * gp + 1] = atomicAdd(&s_wl, gs);   // (the codes are dead)
+    };
+    auto wl_base = [&](bool any) __attribute__((always_inline)) -> uint32_t {   // 0xFFFFFFFF: nothing to write
+        if (!__syncthreads_or((int)any)) return 0xFFFFFFFFu;
         if (tid == 0) {
             const uint32_t tot = s_wl;
             uint32_t base = atomicAdd(&wl_count[b], tot);
@@ -832,18 +772,218 @@ __global__ __launch_bounds__(FSS_NT) void k_fs_sort_bwt(uint32_t nbl, const uint
             s_deep = base;
         }
         __syncthreads();
-        const uint32_t base = s_deep;
+        return s_deep;
+    };
+    auto wl_entry = [&](uint32_t base, uint64_t wv, uint32_t pos, uint32_t grp) __attribute__((always_inline)) {
         uint4 *WL = wl + (size_t)b * wl_cap;
-        if (base != 0xFFFFFFFFu) {
+        const uint32_t gp = grp >> 16, gs = grp & 0xFFFFu, slot0 = base + reinterpret_cast<const uint32_t *>(s_w)[2 * gp + 1];
+        WL[slot0 + (pos - gp)] = make_uint4((uint32_t)(wv & FS_LOW_MASK), R0 + gp, slot0, gs);
+    };
+
+    // ---- FULL full rounds, FULL + 1 slots, phase-major ----
+    auto rounds = [&](auto full_t) __attribute__((always_inline)) -> bool {
+        constexpr int FULL = decltype(full_t)::value, NS = FULL + 1;
+        static_assert(FULL >= FSS_SPEC && NS <= FSS_ITEMS, "the requested rounds are all full ones");
+        uint64_t w[NS];
+        w[0] = ~0ull;
+        if (v0) w[0] = K[i0];
 #pragma unroll
-            for (int r = 0; r < FSS_ITEMS; r++) {
-                if (grp[r]) {
-                    const uint32_t gp = grp[r] >> 16, gs = grp[r] & 0xFFFFu, slot0 = base + reinterpret_cast<const uint32_t *>(s_w)[2 * gp + 1];
-                    WL[slot0 + (pos[r] - gp)] = make_uint4((uint32_t)(w[r] & FS_LOW_MASK), R0 + gp, slot0, gs);
+        for (int r = 1; r <= FULL; r++) w[r] = r <= FSS_SPEC ? ws[r <= FSS_SPEC ? r : 0] : K[(r - 1) * FSS_NT + tid];
+        if (tid < FSS_LOOK) s_w[cc + tid] = ~0ull;             // what the rank step reads past the last bin compares as larger
+        __syncthreads();
+        if (s_deep) return false;                              // flagged: the block is another sorter's
+        // 1. counting sort on the 12 bits below the bucket number (arrival order inside a bin: any order will do)
+        uint32_t bin[NS], rk[NS];
+#pragma unroll
+        for (int r = 0; r < NS; r++) bin[r] = ((uint32_t)(w[r] >> 32) >> hshift) & (FS_BINS - 1);
+        rk[0] = 0;
+        if (v0) rk[0] = atomicAdd(&s_cp[bin[0] >> 1], 1u << (16 * (bin[0] & 1)));
+#pragma unroll
+        for (int r = 1; r < NS; r++) rk[r] = atomicAdd(&s_cp[bin[r] >> 1], 1u << (16 * (bin[r] & 1)));
+#pragma unroll
+        for (int r = 0; r < NS; r++) rk[r] = (rk[r] >> (16 * (bin[r] & 1))) & 0xFFFFu;
+        __syncthreads();
+        bin_starts();
+        __syncthreads();
+#pragma unroll
+        for (int r = 1; r < NS; r++) rk[r] += s16[bin[r]];
+        if (v0) s_w[s16[bin[0]] + rk[0]] = sorted_word(w[0]);
+#pragma unroll
+        for (int r = 1; r < NS; r++) s_w[rk[r]] = sorted_word(w[r]);
+        __syncthreads();
+        // 2. final position = bin start + number of smaller codes in the bin (thread = the words at positions i0 / (r - 1) NT +
+        //    tid of the bin-sorted array).  The four words from the bin start are compared in straight-line code with no bounds
+        //    at all -- what lies behind the bin's end is a larger code or a sentinel; a bin of more than four, or a second word
+        //    with my code among the four, is the rare case: detected per wave, redone exactly over the whole bin.
+        uint32_t pos[NS], grp[NS], gs[NS], ge[NS];             // grp = group start << 16 | group size (0: not tied)
+        if (v0) w[0] = s_w[i0];
+#pragma unroll
+        for (int r = 1; r < NS; r++) w[r] = s_w[(r - 1) * FSS_NT + tid];
+        gs[0] = ge[0] = 0;
+        if (v0) {
+            const uint32_t bn = ((uint32_t)(w[0] >> 32) >> kshift) & (FS_BINS - 1);
+            gs[0] = s16[bn]; ge[0] = s16[bn + 1];
+        }
+#pragma unroll
+        for (int r = 1; r < NS; r++) {
+            const uint32_t bn = ((uint32_t)(w[r] >> 32) >> kshift) & (FS_BINS - 1);
+            gs[r] = s16[bn]; ge[r] = s16[bn + 1];
+        }
+        uint32_t kq[NS][FSS_LOOK];
+        if (v0) {
+            const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs[0] + 1;
+#pragma unroll
+            for (uint32_t t = 0; t < FSS_LOOK; t++) kq[0][t] = B[2 * t];
+        }
+#pragma unroll
+        for (int r = 1; r < NS; r++) {
+            const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs[r] + 1;
+#pragma unroll
+            for (uint32_t t = 0; t < FSS_LOOK; t++) kq[r][t] = B[2 * t];
+        }
+        bool rare[NS], rare_any = false;
+#pragma unroll
+        for (int r = 0; r < NS; r++) {
+            const uint32_t key = (uint32_t)(w[r] >> 32);       // inside a bin only the low 32 bits of the code can differ
+            uint32_t less = 0, eqt = 0;
+#pragma unroll
+            for (uint32_t t = 0; t < FSS_LOOK; t++) {
+                less += kq[r][t] < key ? 1u : 0u;
+                eqt += kq[r][t] == key ? 1u : 0u;
+            }
+            pos[r] = gs[r] + less; grp[r] = 0;
+            rare[r] = ((ge[r] - gs[r] > FSS_LOOK) | (eqt > 1)) & (r > 0 || v0);
+            rare_any |= rare[r];
+        }
+        if (__builtin_amdgcn_ballot_w64(rare_any) != 0) {      // (wave-uniform)
+#pragma unroll
+            for (int r = 0; r < NS; r++)
+                if (rare[r]) rank_rare((uint32_t)(w[r] >> 32), r ? (r - 1) * FSS_NT + tid : i0, gs[r], ge[r], pos[r], grp[r]);
+        }
+        if (zb) {
+            asm volatile("" ::: "memory");                     // (keeps the search behind the branch: see the header)
+#pragma unroll
+            for (int r = 0; r < NS; r++)
+                if ((r > 0 || v0) && pos[r] != 0xFFFFFFFFu && ((uint32_t)w[r] & 0x0FFFFF00u) == 0 && !grp[r]) d_index[b] = (int)(R0 + pos[r]);
+        }
+        __syncthreads();                                       // s_cp (bin starts) is dead from here: it takes the BWT bytes
+        if (s_deep) { if (tid == 0) atomicOr(&flag[b], 2u); return false; }
+        if (v0) s_cb[shift + pos[0]] = (uint8_t)w[0];          // (rows of tied groups are rewritten by k_fs_ties)
+#pragma unroll
+        for (int r = 1; r < NS; r++) s_cb[shift + pos[r]] = (uint8_t)w[r];
+        uint32_t tied = 0;
+#pragma unroll
+        for (int r = 0; r < NS; r++) tied |= grp[r];
+        if (tied) {
+#pragma unroll
+            for (int r = 0; r < NS; r++)
+                if (grp[r]) wl_reserve(pos[r], grp[r]);
+        }
+        const uint32_t base = wl_base(tied != 0);
+        if (base != 0xFFFFFFFFu && tied) {
+#pragma unroll
+            for (int r = 0; r < NS; r++)
+                if (grp[r]) wl_entry(base, w[r], pos[r], grp[r]);
+        }
+        return true;
+    };
+
+    // ---- any fill: eight slots, every one of them guarded ----
+    auto guarded = [&]() __attribute__((always_inline)) -> bool {
+        uint64_t w[FSS_ITEMS];
+#pragma unroll
+        for (int r = 0; r < FSS_ITEMS; r++) w[r] = r >= 1 && r <= FSS_SPEC ? ws[r >= 1 && r <= FSS_SPEC ? r : 0] : ~0ull;
+        if (v0) w[0] = K[i0];
+#pragma unroll
+        for (int r = FSS_SPEC + 1; r < FSS_ITEMS; r++)
+            if ((uint32_t)r <= full) w[r] = K[(r - 1) * FSS_NT + tid];
+        if (tid < FSS_LOOK && cc) s_w[cc + tid] = ~0ull;       // what the rank step reads past the last bin compares as larger
+        __syncthreads();
+        if (s_deep || cc == 0) return false;                   // flagged: the block is another sorter's
+        // 1. counting sort
+        uint32_t rk[FSS_ITEMS];
+#pragma unroll
+        for (int r = 0; r < FSS_ITEMS; r++) rk[r] = 0;
+        {
+            auto count = [&](int r) {
+                const uint32_t bin = ((uint32_t)(w[r] >> 32) >> hshift) & (FS_BINS - 1), sh = 16 * (bin & 1);
+                rk[r] = (atomicAdd(&s_cp[bin >> 1], 1u << sh) >> sh) & 0xFFFFu;
+            };
+            if (v0) count(0);
+#pragma unroll
+            for (int r = 1; r < FSS_ITEMS; r++)
+                if ((uint32_t)r <= full) count(r);
+        }
+        __syncthreads();
+        bin_starts();
+        __syncthreads();
+        {
+            auto scatter = [&](int r) {
+                s_w[s16[((uint32_t)(w[r] >> 32) >> hshift) & (FS_BINS - 1)] + rk[r]] = sorted_word(w[r]);
+            };
+            if (v0) scatter(0);
+#pragma unroll
+            for (int r = 1; r < FSS_ITEMS; r++)
+                if ((uint32_t)r <= full) scatter(r);
+        }
+        __syncthreads();
+        // 2. final position, item by item
+        uint32_t pos[FSS_ITEMS], grp[FSS_ITEMS];               // grp = group start << 16 | group size (0: not tied)
+#pragma unroll
+        for (int r = 0; r < FSS_ITEMS; r++) { pos[r] = 0xFFFFFFFFu; grp[r] = 0; }
+        {
+            auto rank = [&](int r, uint32_t p) {
+                const uint64_t wv = s_w[p];
+                w[r] = wv;
+                const uint32_t key = (uint32_t)(wv >> 32);     // inside a bin only the low 32 bits of the code can differ
+                const uint32_t bin = (key >> kshift) & (FS_BINS - 1);
+                const uint32_t gs = s16[bin], ge = s16[bin + 1];
+                uint32_t less = 0, eqt = 0;
+                const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs + 1;
+#pragma unroll
+                for (uint32_t t = 0; t < FSS_LOOK; t++) {
+                    const uint32_t kq = B[2 * t];
+                    less += kq < key ? 1u : 0u;
+                    eqt += kq == key ? 1u : 0u;
                 }
+                uint32_t at = gs + less;
+                const bool rare = (ge - gs > FSS_LOOK) | (eqt > 1);
+                if (__builtin_amdgcn_ballot_w64(rare) != 0) {  // (wave-uniform)
+                    if (rare) rank_rare(key, p, gs, ge, at, grp[r]);
+                }
+                pos[r] = at;
+            };
+            if (v0) rank(0, i0);
+#pragma unroll
+            for (int r = 1; r < FSS_ITEMS; r++)
+                if ((uint32_t)r <= full) rank(r, (r - 1) * FSS_NT + tid);
+            if (zb) {
+                asm volatile("" ::: "memory");                 // (keeps the search behind the branch: see the header)
+#pragma unroll
+                for (int r = 0; r < FSS_ITEMS; r++)
+                    if (pos[r] != 0xFFFFFFFFu && ((uint32_t)w[r] & 0x0FFFFF00u) == 0 && !grp[r]) d_index[b] = (int)(R0 + pos[r]);
             }
         }
-    }
+        __syncthreads();                                       // s_cp (bin starts) is dead from here: it takes the BWT bytes
+        if (s_deep) { if (tid == 0) atomicOr(&flag[b], 2u); return false; }
+        bool any = false;
+#pragma unroll
+        for (int r = 0; r < FSS_ITEMS; r++) {
+            if (pos[r] != 0xFFFFFFFFu) s_cb[shift + pos[r]] = (uint8_t)w[r];      // (rows of tied groups are rewritten by k_fs_ties)
+            if (grp[r]) { any = true; wl_reserve(pos[r], grp[r]); }
+        }
+        const uint32_t base = wl_base(any);
+        if (base != 0xFFFFFFFFu) {
+#pragma unroll
+            for (int r = 0; r < FSS_ITEMS; r++)
+                if (grp[r]) wl_entry(base, w[r], pos[r], grp[r]);
+        }
+        return true;
+    };
+
+    // (wave-uniform; neighbouring workgroups of a Zipf block take different instances about half the time)
+    const bool go = full == 3 ? rounds(std::integral_constant<int, 3>{}) : full == 4 ? rounds(std::integral_constant<int, 4>{}) : guarded();
+    if (!go) return;
     // 4. the rows
     {
         const uint32_t end = shift + c;                        // staged bytes [shift, end)
