@@ -1,20 +1,20 @@
 // container_api.cpp -- the C ABI of include/glc_container.h: the BWT container over a COMPRESS plan.
-// Encode: one hooked glcCompressBatchCompact per frame writes the Huffman records straight into the container; the kernels of
-// container.hip decide the record kinds before the payload offsets are scanned, copy the raw records, CRC everything and
-// write the frame's tables behind the packer.  Frames chain on the device (a cursor word): no host read inside or between
-// frames, one at the end.  Decode: per frame the host reads the 32-byte frame header, the device checks the tables and records
-// (one verdict read back), then raw records are copied out, runs of Huffman blocks go to glcDecompressBatchCompact reading
-// the tables in place, and the decoded bytes are checked against the blocks' CRCs.
-// The shuffle filter (format version 2, shuffle.hip): with an element size set on the plan the encoder shuffles each frame as one
-// segment into staging kept with the plan and encodes from there; the decoder decodes a version-2 frame into staging, checks its
-// blocks there and unshuffles it into the output.  crc_all is taken over the original bytes on both sides.
-// The order-0 codec (format version 3, hd_batch.hip): with GLC_CONTAINER_CODEC_HUFF0 set on the plan a frame does not go through
-// the plan's compress call at all: batched histograms and tables give every block's record size, the same kind / offset / raw /
-// CRC / table kernels follow, and the batched encoder writes the kind-2 records straight into the container, all on the plan's
-// stream.  The decoder accepts kinds 0, 1 and 2 in a version-3 frame and sends runs of kind 2 to the batched decoder.
-// The filter's delta mode (format version 4, delta.hip): with glcPlanSetContainerDelta on, the encoder stages a frame through the
-// fused delta + shuffle kernel instead of the shuffle and writes version 4 with flags = 1, whichever the codec; the decoder
-// treats such a frame as a version-3 one and inverts it with the fused inverse kernel.
+// A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says two
+// things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
+// shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
+// 1 raw always, 2 order-0 Huffman where kind2_legal()).  CT_LEGAL below is the one table of legal triples: format_of() picks the
+// writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's.
+// Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
+// taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
+// straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
+// and the batched encoder writes the kind-2 records.  Either way the kernels of container.hip decide the record kinds before the
+// payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
+// chain on the device (a cursor word): no host read inside or between frames, one at the end.
+// Decode: decode_walk() is the one loop over a stream's frames, fed either from the caller's device buffers or from a Source
+// through staging.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
+// verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
+// place, runs of kind 2 to the batched order-0 decoder, and the decoded bytes are checked against the blocks' CRCs; a filtered
+// frame is decoded into staging, checked there and inverted into the output by filter_device().
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 
@@ -72,6 +72,12 @@ struct Plan {
     uint32_t n = 0, rows = 0, parity = 0;
     hipStream_t st = nullptr;
     bool ok(CUDPPHandle plan) { h = plan; return plan != 0 && plan != CUDPP_INVALID_HANDLE && plan_info(plan, &n, &rows, &st, &parity); }
+    // what the entry points that tell a bad handle from a plan of another kind return
+    CUDPPResult check(CUDPPHandle plan)
+    {
+        if (ok(plan)) return CUDPP_SUCCESS;
+        return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    }
 };
 
 unsigned long long frame_bytes(uint32_t nb, uint32_t blk_len, unsigned long long payload_words)
@@ -85,18 +91,70 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
     return frame_bytes(nb, blk_len, (unsigned long long)nb * ct_raw_words(blk_len) + nb);
 }
 
-bool shuffle_elem_ok(uint32_t elem) { return elem == 2 || elem == 4 || elem == 8; }
+// -------------------------------------------------------------------------------------------------------------------------
+// the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
+// -------------------------------------------------------------------------------------------------------------------------
+constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
+constexpr struct { uint32_t version, flags, elems; } CT_LEGAL[] = {
+    {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
+    {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}};
 
-// elem: the shuffle's element size, 0 = no filter (version 1, as ever); codec: CT_CODEC_HUFF0 writes version 3; delta (elem != 0
-// only): version 4 with the delta flag, whichever the codec
-void make_header(uint32_t h[8], uint32_t block_len, unsigned long long total, uint32_t elem, uint32_t codec, bool delta)
+bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
+
+bool format_legal(const CtFormat &f)
 {
-    h[0] = CT_MAGIC_STREAM; h[1] = codec == CT_CODEC_HUFF0 ? CT_VERSION_CODEC : (elem ? CT_VERSION_SHUFFLE : CT_VERSION);
-    if (delta) h[1] = CT_VERSION_DELTA | (CT_FLAG_DELTA << 16);
-    h[2] = block_len; h[3] = elem;
+    for (const auto &l : CT_LEGAL)
+        if (l.version == f.version && l.flags == f.flags && f.elem <= 8 && (l.elems >> f.elem & 1)) return true;
+    return false;
+}
+
+// the writer's format: the lowest version that can say the plan's settings
+CtFormat format_of(const CtSettings &s)
+{
+    CtFormat f;
+    f.elem = s.shuffle;
+    f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
+    for (const auto &l : CT_LEGAL) {
+        f.version = l.version;
+        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal())) break;
+    }
+    return f;                                                 // (the setters accept only what some row takes)
+}
+
+// the reader's: header words 1 (version, flags in the upper half) and 3 (elem)
+bool parse_format(const uint32_t h[8], CtFormat *f)
+{
+    f->version = h[1] & 0xFFFFu; f->flags = h[1] >> 16; f->elem = h[3];
+    return format_legal(*f);
+}
+
+hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
+{
+    return (f.delta() ? delta_shuffle_device : shuffle_device)(st, in, out, len, f.elem, inverse);
+}
+
+void make_header(uint32_t h[8], const CtFormat &f, uint32_t block_len, unsigned long long total)
+{
+    h[0] = CT_MAGIC_STREAM; h[1] = f.version | (f.flags << 16);
+    h[2] = block_len; h[3] = f.elem;
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
     h[6] = crc32_host(h, 24); h[7] = 0;
 }
+
+// Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
+// the allocation it places, so the size and the pointers cannot disagree.
+struct Carver {
+    uint8_t *base;
+    size_t off = 0;
+    explicit Carver(void *b = nullptr) : base(static_cast<uint8_t *>(b)) {}
+    template <class T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + off); off += count * sizeof(T); return base ? p : nullptr; }
+    void round(size_t a) { off = (off + a - 1) & ~(a - 1); }      // the offset (the base is at least as aligned)
+    void align(size_t a)                                          // the address; measuring counts the worst case
+    {
+        off = base ? (size_t)(((reinterpret_cast<uintptr_t>(base) + off + a - 1) & ~(uintptr_t)(a - 1)) - reinterpret_cast<uintptr_t>(base)) : off + a;
+    }
+    size_t bytes() const { return off; }
+};
 
 // -------------------------------------------------------------------------------------------------------------------------
 // encoder: device scratch for two frames (the plan's call parity) of up to `rows` blocks, and the running state
@@ -108,30 +166,60 @@ struct Encoder {
     uint32_t *status = nullptr;
     unsigned long long *d_len = nullptr;
     CtEncFrame fr[2] = {};
-    uint32_t elem = 0;                                        // the plan's shuffle filter (0 = off)
-    bool delta = false;                                       // ... in delta mode
+    CtFormat fmt;                                             // what the plan's settings write
     uint32_t codec = CT_CODEC_BWT;                            // the plan's container codec
     CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
+    void carve_huff0(Carver &c)
+    {
+        const size_t R = P.rows;
+        h0.nun = c.take<unsigned long long>(R);
+        h0.in_off = c.take<unsigned long long>(R);
+        h0.in_len = c.take<unsigned long long>(R);
+        h0.codes = c.take<uint16_t>(256 * R);
+        h0.lens = c.take<uint8_t>(256 * R);
+        c.align(256);
+        h0.work = c.take<uint8_t>(hdb_encode_work_bytes(R));
+    }
+    void carve(Carver &c)
+    {
+        const size_t R = P.rows, nsub = (P.n + HUFF_BLOCK - 1) / HUFF_BLOCK;
+        state = c.take<CtEncState>(1); c.round(64);
+        status = c.take<uint32_t>(1); c.round(64);
+        d_len = c.take<unsigned long long>(1); c.round(256);
+        for (auto &f : fr) {
+            f.boff = c.take<unsigned long long>(R + 1);
+            f.seg_off = c.take<unsigned long long>(2 * R + 2);
+            f.seg_len = c.take<unsigned long long>(2 * R + 2);
+            f.start = c.take<unsigned long long>(1);
+            f.kind = c.take<uint32_t>(R);
+            f.size = c.take<uint32_t>(R);
+            f.only = c.take<uint32_t>(R);
+            f.hist = c.take<uint32_t>(256 * R);
+            f.enc_off = c.take<uint32_t>(R * nsub);
+            f.crc = c.take<uint32_t>(2 * R + 2);
+            f.bwt = c.take<int>(R);
+            f.tcrc = c.take<uint32_t>(2);
+            c.round(256);
+        }
+    }
+
     hipError_t init()
     {
-        elem = plan_container_shuffle(P.h);
-        delta = elem && plan_container_delta(P.h);
-        codec = plan_container_codec(P.h);
+        const CtSettings &s = plan_container_settings(P.h);
+        fmt = format_of(s);
+        codec = s.codec;
         if (codec == CT_CODEC_HUFF0) {
-            const size_t R = P.rows, wb = hdb_encode_work_bytes(R);
+            Carver measure;
+            carve_huff0(measure);
             uint8_t *q = nullptr;
-            const hipError_t e = plan_codec_scratch(P.h, 0, 24 * R + 256 * R + 512 * R + 256 + wb, &q);
+            const hipError_t e = plan_codec_scratch(P.h, 0, measure.bytes(), &q);
             if (e != hipSuccess) return e;
-            h0.nun = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
-            h0.in_off = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
-            h0.in_len = reinterpret_cast<unsigned long long *>(q); q += 8 * R;
-            h0.codes = reinterpret_cast<uint16_t *>(q); q += 512 * R;
-            h0.lens = q; q += 256 * R;
-            h0.work = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(q) + 255) & ~(uintptr_t)255);
+            Carver place(q);
+            carve_huff0(place);
         }
-        if (elem) {
+        if (fmt.filtered()) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) {
                 const hipError_t e = plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]);
@@ -139,47 +227,26 @@ struct Encoder {
             }
             if (nstage == 1) stage[1] = stage[0];
         }
-        const size_t R = P.rows, nsub = (P.n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-        const size_t per = (8 * (5 * R + 6) + 4 * (262 * R + R * nsub + 4) + 255) & ~(size_t)255;
-        hipError_t e = hipMalloc(&mem, 256 + 2 * per);
+        Carver measure;
+        carve(measure);
+        const hipError_t e = hipMalloc(&mem, measure.bytes());
         if (e != hipSuccess) { mem = nullptr; return e; }
-        uint8_t *q = static_cast<uint8_t *>(mem);
-        state = reinterpret_cast<CtEncState *>(q);
-        status = reinterpret_cast<uint32_t *>(q + 64);
-        d_len = reinterpret_cast<unsigned long long *>(q + 128);
-        q += 256;
-        for (auto &f : fr) {
-            unsigned long long *u = reinterpret_cast<unsigned long long *>(q);
-            f.boff = u; u += R + 1;
-            f.seg_off = u; u += 2 * R + 2;
-            f.seg_len = u; u += 2 * R + 2;
-            f.start = u; u += 1;
-            uint32_t *w = reinterpret_cast<uint32_t *>(u);
-            f.kind = w; w += R;
-            f.size = w; w += R;
-            f.only = w; w += R;
-            f.hist = w; w += 256 * R;
-            f.enc_off = w; w += R * nsub;
-            f.crc = w; w += 2 * R + 2;
-            f.bwt = reinterpret_cast<int *>(w); w += R;
-            f.tcrc = w; w += 2;
-            q += per;
-        }
+        Carver place(mem);
+        carve(place);
         return hipSuccess;
     }
     ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
 
-    // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With the filter on the
-    // frame is shuffled (in delta mode: delta + shuffled) as one segment into staging and its blocks are cut from there; the
-    // input's own bytes still make crc_all.
+    // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With a filter the frame
+    // goes through it as one segment into staging and its blocks are cut from there; the input's own bytes still make crc_all.
     CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
     {
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
         const CtEncFrame &f = fr[P.parity];
         const uint8_t *orig = nullptr;
-        if (elem) {
+        if (fmt.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
-            CT_TRY((delta ? delta_shuffle_device : shuffle_device)(P.st, d_in, stage[P.parity], (unsigned long long)nb * blk_len, elem, false));
+            CT_TRY(filter_device(P.st, fmt, d_in, stage[P.parity], (unsigned long long)nb * blk_len, false));
             orig = d_in;
             d_in = stage[P.parity];
         }
@@ -214,18 +281,15 @@ struct Encoder {
         return CUDPP_SUCCESS;
     }
 
-    // every frame of [d_in, + len) with the plan's n and rows, starting at input byte `done` of the whole stream
-    template <class PerFrame>
-    CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap, PerFrame per_frame)
+    // every frame of [d_in, + len) with the plan's n and rows
+    CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap)
     {
         unsigned long long pos = 0;
         while (pos < len) {
             const unsigned long long left = len - pos;
             const uint32_t nb = left >= P.n ? (uint32_t)std::min<unsigned long long>(P.rows, left / P.n) : 1u;
             const uint32_t bl = left >= P.n ? P.n : (uint32_t)left;
-            CUDPPResult r = frame(d_in + pos, nb, bl, out, cap);
-            if (r != CUDPP_SUCCESS) return r;
-            r = per_frame((unsigned long long)nb * bl);
+            const CUDPPResult r = frame(d_in + pos, nb, bl, out, cap);
             if (r != CUDPP_SUCCESS) return r;
             pos += (unsigned long long)nb * bl;
         }
@@ -243,26 +307,31 @@ struct Decoder {
     CtDecFrame f = {};
     CtDecState *state = nullptr;
     unsigned long long *h_verdict = nullptr;                  // pinned
-    uint32_t elem = 0;                                        // the stream header's shuffle filter (0 = none)
-    uint32_t version = CT_VERSION;                            // the stream header's
-    bool delta = false;                                       // the stream header's flags, bit 0 (version 4)
+    CtFormat fmt;                                             // the stream header's
     CtDecHuff0 h0 = {};
 
-    // a version-3 frame's scratch, kept with the plan: tables for nb blocks, span-function prefixes for `chunk` of them at a
-    // time (at most the plan's rows, and at most 256 MiB of prefixes)
+    // the scratch of a frame that may hold kind 2, kept with the plan: tables for nb blocks, span-function prefixes for `chunk`
+    // of them at a time (at most the plan's rows, and at most 256 MiB of prefixes)
+    void carve_huff0(Carver &c, uint32_t nb, uint32_t blk_len)
+    {
+        const size_t n4 = ((size_t)nb + 63) & ~(size_t)63;
+        h0.nun = c.take<unsigned long long>(n4);
+        h0.skip = c.take<uint32_t>(n4);
+        h0.lut = c.take<uint16_t>(2048 * (size_t)nb);
+        c.align(256);
+        h0.work = c.take<uint8_t>(hdb_decode_work_bytes(h0.chunk, blk_len));
+    }
     hipError_t reserve_huff0(uint32_t nb, uint32_t blk_len)
     {
         const size_t per = hdb_decode_work_bytes(1, blk_len) + 512;
-        const size_t chunk = std::min<size_t>(std::min<size_t>(P.rows, nb), std::max<size_t>(1, ((size_t)256 << 20) / per));
-        const size_t wb = hdb_decode_work_bytes(chunk, blk_len), n4 = ((size_t)nb + 63) & ~(size_t)63;
+        h0.chunk = (uint32_t)std::min<size_t>(std::min<size_t>(P.rows, nb), std::max<size_t>(1, ((size_t)256 << 20) / per));
+        Carver measure;
+        carve_huff0(measure, nb, blk_len);
         uint8_t *q = nullptr;
-        const hipError_t e = plan_codec_scratch(P.h, 1, 8 * n4 + 4 * n4 + 4096 * (size_t)nb + 256 + wb, &q);
+        const hipError_t e = plan_codec_scratch(P.h, 1, measure.bytes(), &q);
         if (e != hipSuccess) return e;
-        h0.nun = reinterpret_cast<unsigned long long *>(q); q += 8 * n4;
-        h0.skip = reinterpret_cast<uint32_t *>(q); q += 4 * n4;
-        h0.lut = reinterpret_cast<uint16_t *>(q); q += 4096 * (size_t)nb;
-        h0.work = reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(q) + 255) & ~(uintptr_t)255);
-        h0.chunk = (uint32_t)chunk;
+        Carver place(q);
+        carve_huff0(place, nb, blk_len);
         return hipSuccess;
     }
 
@@ -272,21 +341,28 @@ struct Decoder {
         if (state) { (void)hipStreamSynchronize(P.st); (void)hipFree(state); }
         if (h_verdict) (void)hipHostFree(h_verdict);
     }
+    static size_t verdict_words(uint32_t nb) { return 2 + ((size_t)nb + 1) / 2; }
+    void carve(Carver &c, uint32_t nb)
+    {
+        const size_t n2 = (size_t)nb + 2;
+        f.seg_off = c.take<unsigned long long>(n2);
+        f.seg_len = c.take<unsigned long long>(n2);
+        f.verdict = c.take<unsigned long long>(verdict_words(nb));
+        f.crc = c.take<uint32_t>(n2);
+    }
     hipError_t reserve(uint32_t nb)
     {
         if (nb <= cap_nb && mem) return hipSuccess;
         if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); mem = nullptr; }
         if (h_verdict) { (void)hipHostFree(h_verdict); h_verdict = nullptr; }
-        const size_t n2 = nb + 2, vw = 2 + (nb + 1) / 2;
-        hipError_t e = hipMalloc(&mem, 8 * (2 * n2) + 8 * vw + 4 * n2);
+        Carver measure;
+        carve(measure, nb);
+        hipError_t e = hipMalloc(&mem, measure.bytes());
         if (e != hipSuccess) { mem = nullptr; return e; }
-        e = hipHostMalloc((void **)&h_verdict, 8 * vw, hipHostMallocDefault);
+        e = hipHostMalloc((void **)&h_verdict, 8 * verdict_words(nb), hipHostMallocDefault);
         if (e != hipSuccess) { h_verdict = nullptr; return e; }
-        uint8_t *q = static_cast<uint8_t *>(mem);
-        f.seg_off = reinterpret_cast<unsigned long long *>(q); q += 8 * n2;
-        f.seg_len = reinterpret_cast<unsigned long long *>(q); q += 8 * n2;
-        f.verdict = reinterpret_cast<unsigned long long *>(q); q += 8 * vw;
-        f.crc = reinterpret_cast<uint32_t *>(q);
+        Carver place(mem);
+        carve(place, nb);
         cap_nb = nb;
         return hipSuccess;
     }
@@ -300,17 +376,17 @@ struct Decoder {
     }
 
     // a frame in device memory whose header (nb, blk_len, payload words) the host has range-checked; decoded to out.  A
-    // shuffled frame is decoded into the plan's staging, checked block by block there and unshuffled into out in one launch.
+    // filtered frame is decoded into the plan's staging, checked block by block there and inverted into out in one launch.
     CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi)
     {
         CT_TRY(reserve(nb));
         uint8_t *out = final_out;
-        if (elem) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
-        const bool v3 = version >= CT_VERSION_CODEC;            // (version 4 is version 3 with another filter)
+        if (fmt.filtered()) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
+        const bool k2 = fmt.kind2_legal();
         KernelProf *prof = plan_prof(P.h);
-        if (v3) CT_TRY(reserve_huff0(nb, blk_len));
-        CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw, v3 ? &h0 : nullptr, prof));
-        CT_TRY(hipMemcpyAsync(h_verdict, f.verdict, 8 * (2 + (nb + 1) / 2), hipMemcpyDeviceToHost, P.st));
+        if (k2) CT_TRY(reserve_huff0(nb, blk_len));
+        CT_TRY(ct_dec_verify(P.st, f, fr, nb, blk_len, pw, k2 ? &h0 : nullptr, prof));
+        CT_TRY(hipMemcpyAsync(h_verdict, f.verdict, 8 * verdict_words(nb), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
         if (h_verdict[0]) return fail(P.h, CT_FRAME_TABLE, fi);
         if (h_verdict[1] != ~0ull) return fail(P.h, h_verdict[1] >> 32, fi, h_verdict[1] & 0xFFFFFFFFu);
@@ -330,7 +406,7 @@ struct Decoder {
             if (r != CUDPP_SUCCESS) return r;
             a = b;
         }
-        for (uint32_t a = 0; v3 && a < nb;) {                   // runs of order-0 blocks, a chunk of the plan's rows at a time
+        for (uint32_t a = 0; k2 && a < nb;) {                   // runs of order-0 blocks, a chunk of the plan's rows at a time
             if (kind[a] != CT_KIND_HUFF0) { a++; continue; }
             uint32_t b = a;
             while (b < nb && kind[b] == CT_KIND_HUFF0 && b - a < h0.chunk) b++;
@@ -341,9 +417,9 @@ struct Decoder {
             a = b;
         }
         plan_join(P.h);
-        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, elem == 0));
-        if (elem) {
-            CT_TRY((delta ? delta_shuffle_device : shuffle_device)(P.st, out, final_out, (unsigned long long)nb * blk_len, elem, true));
+        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !fmt.filtered()));
+        if (fmt.filtered()) {
+            CT_TRY(filter_device(P.st, fmt, out, final_out, (unsigned long long)nb * blk_len, true));
             CT_TRY(ct_dec_fold(P.st, f, final_out, nb, blk_len, state));
         }
         return CUDPP_SUCCESS;
@@ -361,20 +437,14 @@ struct Decoder {
     }
 };
 
-// the checks on a stream header; returns block_len (0 = refused), the shuffle's element size (0 = no filter), the version and
-// whether the filter is in delta mode (version 4, whose only legal flags value is 1)
-uint32_t check_stream_header(const uint32_t h[8], unsigned long long *total, uint32_t *elem, uint32_t *version, bool *delta)
+// the checks on a stream header; false = refused
+bool check_stream_header(const uint32_t h[8], CtFormat *fmt, uint32_t *block_len, unsigned long long *total)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24)) return 0;
-    const bool v4 = h[1] == (CT_VERSION_DELTA | (CT_FLAG_DELTA << 16)) && shuffle_elem_ok(h[3]);
-    if (!(h[1] == CT_VERSION && h[3] == 0) && !(h[1] == CT_VERSION_SHUFFLE && shuffle_elem_ok(h[3])) &&
-        !(h[1] == CT_VERSION_CODEC && (h[3] == 0 || shuffle_elem_ok(h[3]))) && !v4) return 0;
-    *elem = h[3];
-    *version = h[1] & 0xFFFFu;
-    *delta = v4;
-    if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return 0;
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24) || !parse_format(h, fmt)) return false;
+    if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
+    *block_len = h[2];
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
-    return h[2];
+    return true;
 }
 
 // the host's range checks on a frame header; 0 = refused
@@ -467,7 +537,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     CT_TRY(dout.reserve(ocap));
     CT_TRY(hout.reserve(ocap));
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem, E.codec, E.delta);
+    make_header(hdr, E.fmt, E.P.n, len);
     if (!out.write(hdr, CT_HDR)) return fail(plan, CT_CAPACITY);
     unsigned long long total = CT_HDR;
     hipStream_t cs = nullptr;
@@ -497,8 +567,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
         const unsigned long long m = std::min(fmax, len - i * fmax);
         CT_TRY(hipStreamWaitEvent(E.P.st, copied[k], 0));
         CT_TRY(hipMemsetAsync(&E.state->cursor, 0, 8, E.P.st));
-        CUDPPResult r = E.frames(static_cast<const uint8_t *>(din[k].p), m, static_cast<uint8_t *>(dout.p), ocap,
-                                 [](unsigned long long) { return CUDPP_SUCCESS; });
+        CUDPPResult r = E.frames(static_cast<const uint8_t *>(din[k].p), m, static_cast<uint8_t *>(dout.p), ocap);
         if (r != CUDPP_SUCCESS) return r;
         plan_join(plan);
         CT_TRY(hipEventRecord(used[k], E.P.st));
@@ -522,53 +591,142 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     return CUDPP_SUCCESS;
 }
 
+// -------------------------------------------------------------------------------------------------------------------------
+// decode: one walk over a stream's frames, fed from device memory or from a Source
+// -------------------------------------------------------------------------------------------------------------------------
+struct Feed {
+    virtual ~Feed() {}
+    // n = 32 or 16 header bytes at stream position pos, into host memory (frame: the index a failure names, ~0 = none)
+    virtual CUDPPResult header(void *dst, unsigned long long pos, size_t n, unsigned long long frame) = 0;
+    // the device pointers of the fb-byte frame at pos, whose header fh has been fetched, and of its ob output bytes, which
+    // follow `done` decoded ones
+    virtual CUDPPResult frame(const uint32_t fh[8], unsigned long long pos, unsigned long long fb, unsigned long long done, size_t ob,
+                              uint32_t fi, const uint8_t **fr, uint8_t **out) = 0;
+    virtual CUDPPResult taken(size_t ob) = 0;                    // the frame's output is complete on the plan's stream
+};
+
+// stream header -> frames -> trailer -> the decoded bytes' verdict; cap: the room for output.  Returns the stream's total.
+CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned long long cap, unsigned long long *total)
+{
+    const CUDPPHandle plan = D.P.h;
+    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
+    uint32_t hdr[8], block_len = 0;
+    CUDPPResult r = feed.header(hdr, 0, CT_HDR, ~0ull);
+    if (r != CUDPP_SUCCESS) return r;
+    if (!check_stream_header(hdr, &D.fmt, &block_len, total)) return fail(plan, CT_STREAM_HEADER);
+    if (*total > cap) return fail(plan, CT_CAPACITY);
+    CT_TRY(D.begin());
+    unsigned long long pos = CT_HDR, done = 0;
+    uint32_t fi = 0;
+    while (done < *total) {
+        if (pos + CT_FRAME_HDR + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+        uint32_t fh[8];
+        if ((r = feed.header(fh, pos, CT_FRAME_HDR, fi)) != CUDPP_SUCCESS) return r;
+        unsigned long long pw = 0;
+        if (!check_frame_header(fh, block_len, *total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
+        const uint32_t nb = fh[1], bl = fh[2];
+        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+        const unsigned long long fb = frame_bytes(nb, bl, pw);
+        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+        const size_t ob = (size_t)nb * bl;
+        const uint8_t *fr = nullptr;
+        uint8_t *out = nullptr;
+        if ((r = feed.frame(fh, pos, fb, done, ob, fi, &fr, &out)) != CUDPP_SUCCESS) return r;
+        if ((r = D.frame(fr, nb, bl, pw, out, fi)) != CUDPP_SUCCESS) return r;
+        if ((r = feed.taken(ob)) != CUDPP_SUCCESS) return r;
+        pos += fb; done += ob; fi++;
+    }
+    uint32_t tr[4];
+    if (pos + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
+    if ((r = feed.header(tr, pos, CT_TRAILER, fi)) != CUDPP_SUCCESS) return r;
+    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
+    if ((r = D.end(tr[2])) != CUDPP_SUCCESS) return r;
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
+// the caller's device buffers: headers come by a device-to-host copy, frames are decoded where they lie
+struct DeviceFeed : Feed {
+    hipStream_t st;
+    const uint8_t *in;
+    uint8_t *out;
+    DeviceFeed(hipStream_t s, const void *i, void *o) : st(s), in(static_cast<const uint8_t *>(i)), out(static_cast<uint8_t *>(o)) {}
+    CUDPPResult header(void *dst, unsigned long long pos, size_t n, unsigned long long) override
+    {
+        CT_TRY(hipMemcpyAsync(dst, in + pos, n, hipMemcpyDeviceToHost, st));
+        CT_TRY(hipStreamSynchronize(st));
+        return CUDPP_SUCCESS;
+    }
+    CUDPPResult frame(const uint32_t *, unsigned long long pos, unsigned long long, unsigned long long done, size_t, uint32_t,
+                      const uint8_t **fr, uint8_t **o) override
+    {
+        *fr = in + pos; *o = out + done;
+        return CUDPP_SUCCESS;
+    }
+    CUDPPResult taken(size_t) override { return CUDPP_SUCCESS; }
+};
+
+// a Source read in order and a Sink: a frame goes through pinned memory onto the device, its output back the same way
+struct StreamFeed : Feed {
+    CUDPPHandle plan;
+    hipStream_t st;
+    Source &src;
+    Sink &sink;
+    Pinned hf, ho;
+    DevBuf df, dob;
+    StreamFeed(CUDPPHandle p, hipStream_t s, Source &i, Sink &o) : plan(p), st(s), src(i), sink(o) {}
+    CUDPPResult header(void *dst, unsigned long long, size_t n, unsigned long long frame) override
+    {
+        return src.read(dst, n) ? CUDPP_SUCCESS : fail(plan, CT_TRUNCATED, frame);
+    }
+    CUDPPResult frame(const uint32_t fh[8], unsigned long long, unsigned long long fb, unsigned long long, size_t ob, uint32_t fi,
+                      const uint8_t **fr, uint8_t **o) override
+    {
+        CT_TRY(hf.reserve(fb)); CT_TRY(df.reserve(fb));
+        CT_TRY(ho.reserve(ob)); CT_TRY(dob.reserve(ob));
+        memcpy(hf.p, fh, CT_FRAME_HDR);
+        if (!src.read(static_cast<uint8_t *>(hf.p) + CT_FRAME_HDR, fb - CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
+        CT_TRY(hipMemcpyAsync(df.p, hf.p, fb, hipMemcpyHostToDevice, st));
+        *fr = static_cast<const uint8_t *>(df.p); *o = static_cast<uint8_t *>(dob.p);
+        return CUDPP_SUCCESS;
+    }
+    CUDPPResult taken(size_t ob) override
+    {
+        CT_TRY(hipMemcpyAsync(ho.p, dob.p, ob, hipMemcpyDeviceToHost, st));
+        CT_TRY(hipStreamSynchronize(st));
+        return sink.write(ho.p, ob) ? CUDPP_SUCCESS : fail(plan, CT_CAPACITY);
+    }
+};
+
 CUDPPResult decompress_stream(CUDPPHandle plan, Source &src, unsigned long long len, Sink &out, unsigned long long cap,
                               unsigned long long *outLen)
 {
     Decoder D;
     if (!D.P.ok(plan)) return CUDPP_ERROR_INVALID_PLAN;
-    uint32_t hdr[8];
-    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
-    if (!src.read(hdr, CT_HDR)) return fail(plan, CT_TRUNCATED);
+    StreamFeed feed(plan, D.P.st, src, out);
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version, &D.delta);
-    if (!block_len) return fail(plan, CT_STREAM_HEADER);
-    if (total > cap) return fail(plan, CT_CAPACITY);
-    CT_TRY(D.begin());
-    Pinned hf, ho;
-    DevBuf df, dob;
-    unsigned long long pos = CT_HDR, done = 0;
-    uint32_t fi = 0;
-    while (done < total) {
-        uint32_t fh[8];
-        if (pos + CT_FRAME_HDR + CT_TRAILER > len || !src.read(fh, CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
-        unsigned long long pw = 0;
-        if (!check_frame_header(fh, block_len, total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
-        const uint32_t nb = fh[1], bl = fh[2];
-        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
-        const unsigned long long fb = frame_bytes(nb, bl, pw);
-        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-        CT_TRY(hf.reserve(fb)); CT_TRY(df.reserve(fb));
-        const size_t ob = (size_t)nb * bl;
-        CT_TRY(ho.reserve(ob)); CT_TRY(dob.reserve(ob));
-        memcpy(hf.p, fh, CT_FRAME_HDR);
-        if (!src.read(static_cast<uint8_t *>(hf.p) + CT_FRAME_HDR, fb - CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
-        CT_TRY(hipMemcpyAsync(df.p, hf.p, fb, hipMemcpyHostToDevice, D.P.st));
-        CUDPPResult r = D.frame(static_cast<const uint8_t *>(df.p), nb, bl, pw, static_cast<uint8_t *>(dob.p), fi);
-        if (r != CUDPP_SUCCESS) return r;
-        CT_TRY(hipMemcpyAsync(ho.p, dob.p, ob, hipMemcpyDeviceToHost, D.P.st));
-        CT_TRY(hipStreamSynchronize(D.P.st));
-        if (!out.write(ho.p, ob)) return fail(plan, CT_CAPACITY);
-        pos += fb; done += ob; fi++;
-    }
-    uint32_t tr[4];
-    if (pos + CT_TRAILER > len || !src.read(tr, CT_TRAILER)) return fail(plan, CT_TRUNCATED, fi);
-    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
-    CUDPPResult r = D.end(tr[2]);
-    if (r != CUDPP_SUCCESS) return r;
-    if (outLen) *outLen = total;
-    set_error(plan, CT_OK);
-    return CUDPP_SUCCESS;
+    const CUDPPResult r = decode_walk(D, feed, len, cap, &total);
+    if (r == CUDPP_SUCCESS && outLen) *outLen = total;
+    return r;
+}
+
+// the two file entry points: stat and open, the streamed call, close; a failing close of the output fails a call that had not
+template <class Call>
+CUDPPResult with_files(const char *inPath, const char *outPath, Call call)
+{
+    if (!inPath || !outPath) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    struct stat sb;
+    if (stat(inPath, &sb) != 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fi = fopen(inPath, "rb");
+    if (!fi) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    FILE *fo = fopen(outPath, "wb");
+    if (!fo) { fclose(fi); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+    FileSource s(fi);
+    FileSink k(fo);
+    CUDPPResult r = call(s, (unsigned long long)sb.st_size, k);
+    fclose(fi);
+    if (fclose(fo) != 0 && r == CUDPP_SUCCESS) r = CUDPP_ERROR_UNKNOWN;
+    return r;
 }
 
 } // namespace
@@ -586,14 +744,14 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
                                        unsigned long long cap, unsigned long long *d_outLen)
 {
     Encoder E;
-    if (!E.P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (const CUDPPResult bad = E.P.check(plan)) return bad;
     if ((len && !d_in) || !d_out || !d_outLen || (reinterpret_cast<uintptr_t>(d_out) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CT_TRY(E.init());
     uint8_t *out = static_cast<uint8_t *>(d_out);
     uint32_t hdr[8];
-    make_header(hdr, E.P.n, len, E.elem, E.codec, E.delta);
+    make_header(hdr, E.fmt, E.P.n, len);
     CT_TRY(ct_enc_header(E.P.st, out, cap, hdr, E.state));
-    CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap, [](unsigned long long) { return CUDPP_SUCCESS; });
+    CUDPPResult r = E.frames(static_cast<const uint8_t *>(d_in), len, out, cap);
     if (r != CUDPP_SUCCESS) return r;
     plan_join(plan);
     CT_TRY(ct_enc_trailer(E.P.st, out, cap, E.state, d_outLen));
@@ -609,45 +767,14 @@ CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, uns
                                          unsigned long long cap, unsigned long long *d_outLen)
 {
     Decoder D;
-    if (!D.P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (const CUDPPResult bad = D.P.check(plan)) return bad;
     if (!d_in || !d_outLen || (reinterpret_cast<uintptr_t>(d_in) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const uint8_t *in = static_cast<const uint8_t *>(d_in);
-    uint8_t *out = static_cast<uint8_t *>(d_out);
-    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
-    uint32_t hdr[8];
-    CT_TRY(hipMemcpyAsync(hdr, in, CT_HDR, hipMemcpyDeviceToHost, D.P.st));
-    CT_TRY(hipStreamSynchronize(D.P.st));
+    DeviceFeed feed(D.P.st, d_in, d_out);
     unsigned long long total = 0;
-    const uint32_t block_len = check_stream_header(hdr, &total, &D.elem, &D.version, &D.delta);
-    if (!block_len) return fail(plan, CT_STREAM_HEADER);
-    if (total > cap || (total && !d_out)) return fail(plan, CT_CAPACITY);
-    CT_TRY(D.begin());
-    unsigned long long pos = CT_HDR, done = 0;
-    uint32_t fi = 0;
-    while (done < total) {
-        if (pos + CT_FRAME_HDR + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-        uint32_t fh[8];
-        CT_TRY(hipMemcpyAsync(fh, in + pos, CT_FRAME_HDR, hipMemcpyDeviceToHost, D.P.st));
-        CT_TRY(hipStreamSynchronize(D.P.st));
-        unsigned long long pw = 0;
-        if (!check_frame_header(fh, block_len, total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
-        const uint32_t nb = fh[1], bl = fh[2];
-        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
-        const unsigned long long fb = frame_bytes(nb, bl, pw);
-        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-        CUDPPResult r = D.frame(in + pos, nb, bl, pw, out + done, fi);
-        if (r != CUDPP_SUCCESS) return r;
-        pos += fb; done += (unsigned long long)nb * bl; fi++;
-    }
-    uint32_t tr[4];
-    CT_TRY(hipMemcpyAsync(tr, in + pos, CT_TRAILER, hipMemcpyDeviceToHost, D.P.st));
-    CT_TRY(hipStreamSynchronize(D.P.st));
-    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
-    CUDPPResult r = D.end(tr[2]);
+    const CUDPPResult r = decode_walk(D, feed, len, d_out ? cap : 0, &total);     // (without an output buffer only an empty stream fits)
     if (r != CUDPP_SUCCESS) return r;
     CT_TRY(ct_put_u64(D.P.st, d_outLen, total));
     CT_TRY(hipStreamSynchronize(D.P.st));
-    set_error(plan, CT_OK);
     return CUDPP_SUCCESS;
 }
 
@@ -671,36 +798,12 @@ CUDPPResult glcContainerDecompress(CUDPPHandle plan, const void *in, unsigned lo
 
 CUDPPResult glcContainerCompressFile(CUDPPHandle plan, const char *inPath, const char *outPath)
 {
-    if (!inPath || !outPath) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    struct stat sb;
-    if (stat(inPath, &sb) != 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    FILE *fi = fopen(inPath, "rb");
-    if (!fi) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    FILE *fo = fopen(outPath, "wb");
-    if (!fo) { fclose(fi); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
-    FileSource s(fi);
-    FileSink k(fo);
-    CUDPPResult r = compress_stream(plan, s, (unsigned long long)sb.st_size, k, nullptr);
-    fclose(fi);
-    if (fclose(fo) != 0 && r == CUDPP_SUCCESS) r = CUDPP_ERROR_UNKNOWN;
-    return r;
+    return with_files(inPath, outPath, [&](Source &s, unsigned long long len, Sink &k) { return compress_stream(plan, s, len, k, nullptr); });
 }
 
 CUDPPResult glcContainerDecompressFile(CUDPPHandle plan, const char *inPath, const char *outPath)
 {
-    if (!inPath || !outPath) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    struct stat sb;
-    if (stat(inPath, &sb) != 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    FILE *fi = fopen(inPath, "rb");
-    if (!fi) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    FILE *fo = fopen(outPath, "wb");
-    if (!fo) { fclose(fi); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
-    FileSource s(fi);
-    FileSink k(fo);
-    CUDPPResult r = decompress_stream(plan, s, (unsigned long long)sb.st_size, k, ~0ull, nullptr);
-    fclose(fi);
-    if (fclose(fo) != 0 && r == CUDPP_SUCCESS) r = CUDPP_ERROR_UNKNOWN;
-    return r;
+    return with_files(inPath, outPath, [&](Source &s, unsigned long long len, Sink &k) { return decompress_stream(plan, s, len, k, ~0ull, nullptr); });
 }
 
 CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
@@ -726,12 +829,14 @@ static CUDPPResult shuffle_segments_api(const void *d_inBase, void *d_outBase, c
 static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse,
                                       bool delta = false)
 {
+    CtFormat f;                                               // (only its filter matters here)
+    f.flags = delta ? CT_FLAG_DELTA : 0; f.elem = elem;
     if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     if (len == 0) return CUDPP_SUCCESS;
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
     if (!d_in || !d_out || (a < b ? b - a : a - b) < len) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res((delta ? delta_shuffle_device : shuffle_device)(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in),
-                                                                   static_cast<uint8_t *>(d_out), len, elem, inverse));
+    return hip_res(filter_device(reinterpret_cast<hipStream_t>(stream), f, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out),
+                                 len, inverse));
 }
 
 CUDPPResult glcShuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
@@ -769,55 +874,57 @@ CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned lo
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
     if (elem > 1 && !shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    plan_set_container_shuffle(plan, elem > 1 ? elem : 0);
-    if (elem <= 1) plan_set_container_delta(plan, false);      // (no delta without the shuffle)
+    CtSettings &s = plan_container_settings(plan);
+    s.shuffle = elem > 1 ? elem : 0;
+    if (elem <= 1) s.delta = false;                           // (no delta without the shuffle)
     return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
-    if (on > 1 || (on && !plan_container_shuffle(plan))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    plan_set_container_delta(plan, on != 0);
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_delta(plan) ? 1u : 0u;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    CtSettings &s = plan_container_settings(plan);
+    if (on > 1 || (on && !s.shuffle)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    s.delta = on != 0;
     return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
 {
     Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
     if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    plan_set_container_codec(plan, codec);
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
-{
-    Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
-    if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *codec = plan_container_codec(plan);
+    plan_container_settings(plan).codec = codec;
     return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
 {
     Plan P;
-    if (!P.ok(plan)) return plan == 0 || plan == CUDPP_INVALID_HANDLE ? CUDPP_ERROR_INVALID_HANDLE : CUDPP_ERROR_INVALID_PLAN;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!elem) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *elem = plan_container_shuffle(plan);
+    *elem = plan_container_settings(plan).shuffle;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).delta ? 1u : 0u;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *codec = plan_container_settings(plan).codec;
     return CUDPP_SUCCESS;
 }
 

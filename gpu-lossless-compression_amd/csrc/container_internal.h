@@ -96,6 +96,15 @@ constexpr uint32_t CT_VERSION = 1, CT_VERSION_SHUFFLE = 2;   // 2: header word 3
 constexpr uint32_t CT_VERSION_CODEC = 3;                     // 3: kind 2 is legal; header word 3 = element size or 0 (no filter)
 constexpr uint32_t CT_VERSION_DELTA = 4;                     // 4: version 3 with flags in the upper half of the version dword
 constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the only one): the filter is delta + shuffle; elem 2, 4 or 8
+// A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
+// went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
+// kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
+struct CtFormat {
+    uint32_t version = CT_VERSION, flags = 0, elem = 0;
+    bool filtered() const { return elem != 0; }
+    bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
+    bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
+};
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
@@ -140,23 +149,21 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, const unsigned char *d_in, in
 // that call may reuse once the plan's own ordering lets it)
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
-// the shuffle filter of a COMPRESS plan: the encoder's element size (0 = off), and the plan's two frame staging buffers
-// (grown on demand, never shrunk, freed with the plan; encoder: one per call parity, decoder: buffer 0)
+// the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
+// mode (only ever on with the shuffle on) and the codec (CT_CODEC_*)
+struct CtSettings { uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; };
+CtSettings &plan_container_settings(CUDPPHandle plan);
+// the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
+// call parity, decoder: buffer 0)
 bool plan_pipelined(CUDPPHandle plan);
-uint32_t plan_container_shuffle(CUDPPHandle plan);
-void plan_set_container_shuffle(CUDPPHandle plan, uint32_t elem);
-bool plan_container_delta(CUDPPHandle plan);               // the filter's delta mode (only ever on with the shuffle on)
-void plan_set_container_delta(CUDPPHandle plan, bool on);
 hipError_t plan_stage(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
 // the plan's stream waits until the encode call that last used the next call's parity has released its input (pipelining:
 // that call's Huffman stages and container kernels read their input from the side stream)
 void plan_wait_released(CUDPPHandle plan);
-// the container codec of a COMPRESS plan's encoder (CT_CODEC_*), and what the order-0 codec keeps with the plan: device
+// what the order-0 codec keeps with the plan: device
 // scratch (which = 0 the encoder's, 1 the decoder's; grown on demand, never shrunk, freed with the plan, never allocated
 // by a plan that only uses the BWT codec), the plan's live kernel profile, and its stage events (i = 0 .. 3: the marks of
 // glcPlanLastTiming's four spans, recorded on the plan's stream; a no-op while timing is off)
-uint32_t plan_container_codec(CUDPPHandle plan);
-void plan_set_container_codec(CUDPPHandle plan, uint32_t codec);
 hipError_t plan_codec_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
 KernelProf *plan_prof(CUDPPHandle plan);
 void plan_stage_mark(CUDPPHandle plan, int i);

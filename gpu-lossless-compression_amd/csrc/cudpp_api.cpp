@@ -83,13 +83,11 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     bool dec_released_valid[2] = {false, false};
     uint32_t dec_calls = 0;
     bool side_busy = false;                      // side-stream work issued since the last join
-    // container filter (glcPlanSetContainerShuffle): the encoder's element size and the frame staging both directions share
-    uint32_t ct_shuffle = 0;
-    bool ct_delta = false;                       // (glcPlanSetContainerDelta: the filter's delta mode, format version 4)
+    // container settings (glcPlanSetContainerShuffle / Delta / Codec) and the filter's frame staging both directions share
+    CtSettings ct;
     void *ct_stage[2] = {nullptr, nullptr};
     size_t ct_stage_bytes[2] = {0, 0};
-    // container codec (glcPlanSetContainerCodec) and the order-0 codec's scratch: [0] the encoder's, [1] the decoder's
-    uint32_t ct_codec = 0;
+    // the order-0 container codec's scratch: [0] the encoder's, [1] the decoder's
     void *ct_codec_mem[2] = {nullptr, nullptr};
     size_t ct_codec_bytes[2] = {0, 0};
     void join_side()                             // make the plan's stream wait for everything on the side stream
@@ -858,8 +856,7 @@ bool plan_info(CUDPPHandle planHandle, uint32_t *n, uint32_t *rows, hipStream_t 
 void plan_join(CUDPPHandle planHandle) { plan_from<CompressPlan>(planHandle)->join_side(); }
 
 bool plan_pipelined(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->pipelined; }
-uint32_t plan_container_shuffle(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_shuffle; }
-void plan_set_container_shuffle(CUDPPHandle planHandle, uint32_t elem) { plan_from<CompressPlan>(planHandle)->ct_shuffle = elem; }
+CtSettings &plan_container_settings(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct; }
 
 hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {
@@ -878,11 +875,6 @@ hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint
     *out = static_cast<uint8_t *>(p->ct_stage[which]);
     return hipSuccess;
 }
-
-bool plan_container_delta(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_delta; }
-void plan_set_container_delta(CUDPPHandle planHandle, bool on) { plan_from<CompressPlan>(planHandle)->ct_delta = on; }
-uint32_t plan_container_codec(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_codec; }
-void plan_set_container_codec(CUDPPHandle planHandle, uint32_t codec) { plan_from<CompressPlan>(planHandle)->ct_codec = codec; }
 
 hipError_t plan_codec_scratch(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {

@@ -11,7 +11,18 @@
 #include "glc_container.h"
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define CR(x) do { CUDPPResult r_ = (x); if (r_ != CUDPP_SUCCESS) { fprintf(stderr, "CUDPPResult %d at line %d\n", (int)r_, __LINE__); return 3; } } while (0)
+/* a failing call also says what the container's last error was (what, frame, block) and HIP's, once there is a plan */
+static CUDPPHandle plan = 0;
+static int refused(CUDPPResult r, int line)
+{
+    unsigned long long e[3] = {0, 0, 0};
+    fprintf(stderr, "CUDPPResult %d at line %d", (int)r, line);
+    if (plan && glcContainerLastError(plan, e) == CUDPP_SUCCESS)
+        fprintf(stderr, ", container last error (%llu, %lld, %lld), hip last error %d", e[0], (long long)e[1], (long long)e[2], (int)hipGetLastError());
+    fprintf(stderr, "\n");
+    return 3;
+}
+#define CR(x) do { CUDPPResult r_ = (x); if (r_ != CUDPP_SUCCESS) return refused(r_, __LINE__); } while (0)
 
 int main(void)
 {
@@ -32,7 +43,7 @@ int main(void)
     CK(hipMalloc((void **)&d_in, len)); CK(hipMalloc((void **)&d_out, cap)); CK(hipMalloc((void **)&d_back, len));
     CK(hipMalloc((void **)&d_shuf, len)); CK(hipMalloc((void **)&d_len, 8));
     CK(hipMemcpy(d_in, h_in, len, hipMemcpyHostToDevice));
-    CUDPPHandle lib, plan;
+    CUDPPHandle lib;
     CUDPPConfiguration cfg = {CUDPP_COMPRESS, CUDPP_ADD, CUDPP_UCHAR, 0, CUDPP_DEFAULT_BUCKET_MAPPER};
     CR(cudppCreate(&lib));
     CR(cudppPlan(lib, &plan, cfg, n, 4, 0));

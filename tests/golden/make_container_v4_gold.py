@@ -1,5 +1,5 @@
 """Writes tests/golden/container_v4_series.bin: a version-4 container (the filter's delta mode) made by the
-Python model, tests/container_delta_model.py, with all three record kinds in it: two frames of 8 and 2 blocks of 4096 bytes and a
+Python model, tests/container_model.py, with all three record kinds in it: two frames of 8 and 2 blocks of 4096 bytes and a
 ragged tail frame of 1235 bytes (not a multiple of 8), writer plan n = 4096, rows = 8, elem = 8, of int64 timestamps
 (tests/series_datagen.py) with a stretch of noise, the codec of each block forced in the cycle BWT, order-0, raw, order-0,
 BWT.  python tests/golden/make_container_v4_gold.py"""
@@ -11,7 +11,7 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
-import container_delta_model as D  # noqa: E402
+import container_model as M  # noqa: E402
 import series_datagen  # noqa: E402
 
 BLOCK, ROWS, ELEM = 4096, 8, 8
@@ -27,7 +27,7 @@ def gold_input():
 
 
 def make():
-    return D.write(gold_input(), BLOCK, ROWS, ELEM, delta=True, kinds=KINDS)
+    return M.write(gold_input(), BLOCK, ROWS, ELEM, delta=True, kinds=KINDS)
 
 
 if __name__ == "__main__":

@@ -1,9 +1,10 @@
 """The container's order-0 Huffman codec without a GPU: the library exports the new container and glc_hd.h entry points and
-validates their arguments before touching a device; the Python model of format version 3 (tests/container_codec_model.py)
+validates their arguments before touching a device; the Python model of format version 3 (tests/container_model.py)
 writes versions 1 / 2 unchanged with the BWT codec, round-trips with the order-0 one, writes records that equal the library's
 host encoder word for word, is refused by the older readers, refuses what the format forbids, and reproduces the golden
 fixture; the kinds and sizes the codec is for, counted on the model."""
 import ctypes as C
+import functools
 import importlib.util
 import os
 import struct
@@ -12,13 +13,12 @@ import zlib
 import numpy as np
 import pytest
 
-import container_codec_model as K
-import container_filter_model as F
 import container_model as M
 import datagen
 import hd_table_model as H
 import typed_datagen
 
+READ1, READ2, READ3 = (functools.partial(M.read, max_version=k) for k in (1, 2, 3))   # the readers of the older versions
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "container_v3_mixed.bin")
 NEW_CONTAINER = ["glcPlanSetContainerCodec", "glcPlanGetContainerCodec"]
@@ -94,17 +94,17 @@ def _record_inputs():
 
 def test_model_record_equals_the_host_encoder_word_for_word(glc):
     for name, x in _record_inputs():
-        hist, words = K.h0_encode(x)
+        hist, words = M.h0_encode(x)
         lens, codes = glc.hd_build_table(hist)
         assert np.array_equal(glc.hd_encode_host(x, lens, codes), words), name
         mlens, _ = H.build_table(hist)
         bits = int((hist.astype(np.int64) * mlens).sum())
-        assert words.size == (bits + 31) // 32 + 1 == K.h0_words(hist) and words[-1] == 0, name
+        assert words.size == (bits + 31) // 32 + 1 == M.h0_words(hist) and words[-1] == 0, name
         if bits % 32:
             assert words[-2] & ((1 << (32 - bits % 32)) - 1) == 0, name             # zero bits after the last code
-        back, used = K.h0_decode(hist, words, x.size)
+        back, used = M.h0_decode(hist, words, x.size)
         assert np.array_equal(back, x) and used == bits, name
-    h, w = K.h0_encode(np.full(5000, 7, np.uint8))
+    h, w = M.h0_encode(np.full(5000, 7, np.uint8))
     assert w.size == (5000 + 31) // 32 + 1                      # a one-symbol block: length 1, blk_len bits
 
 
@@ -118,13 +118,26 @@ def _data(n, seed, elem):
     return typed_datagen.typed_bytes(kind, n, seed=seed)
 
 
+def _pins():
+    """the pins generator (its grid and inputs) and the committed pins"""
+    spec = importlib.util.spec_from_file_location("make_container_model_pins",
+                                                  os.path.join(ROOT, "tests", "golden", "make_container_model_pins.py"))
+    g = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(g)
+    return g, g.committed()
+
+
 def test_codec_bwt_is_version_1_and_2_byte_for_byte():
+    g, pins = _pins()
     for n, bl, rows in ((0, 4096, 2), (5, 4096, 1), (3 * 4096 + 77, 4096, 2), (70000, 65536, 4)):
         x = _data(n, 3, 4)
         for elem in (0, 1, 2, 4, 8):
-            assert K.write(x, bl, rows, elem, 0) == F.write(x, bl, rows, elem)
-            assert np.array_equal(K.read(F.write(x, bl, rows, elem)), x)
-        assert K.write(x, bl, rows) == M.write(x, bl, rows)
+            c = M.write(x, bl, rows, elem, 0)
+            assert struct.unpack("<HHII", c[4:16]) == ((2, 0, bl, elem) if elem > 1 else (1, 0, bl, 0))
+            assert np.array_equal(READ3(c), x) and np.array_equal(READ2(c), x)
+            # ... and is what the models of versions 1 and 2 wrote
+            assert g.pin(M.write(g.grid_input(n, elem, False), bl, rows, elem, 0)) == pins["written"][g.grid_name(n, bl, rows, elem, 0, False)]
+        assert M.write(x, bl, rows, 1) == M.write(x, bl, rows, 0) == M.write(x, bl, rows)
 
 
 @pytest.mark.parametrize("bl", [1000, 4096, 65536])
@@ -134,21 +147,21 @@ def test_model_round_trip(bl, elem):
     for rows in (1, 3, 4):
         for i, n in enumerate((0, e1 - 1, bl, 2 * rows * bl, rows * bl + bl + 1 + e1, 2 * bl + 3 * e1)):
             x = _data(n, 10 * rows + i, elem)
-            c = K.write(x, bl, rows, elem, 1)
+            c = M.write(x, bl, rows, elem, 1)
             assert len(c) % 8 == 0 and len(c) <= M.bound(n, bl)
             assert struct.unpack("<HHII", c[4:16]) == (3, 0, bl, elem)
             assert struct.unpack("<I", c[-8:-4])[0] == zlib.crc32(x.tobytes())       # crc_all: the ORIGINAL input
-            data, kinds = K.read(c, with_kinds=True)
+            data, kinds = READ3(c, with_kinds=True)
             assert np.array_equal(data, x), (bl, rows, elem, n)
-            assert set(kinds) <= {M.RAW, K.HUFF0}
-    assert K.write(b"", bl, 2, elem, 1)[32:36] == M.MAGIC_END      # an empty input: header + trailer
+            assert set(kinds) <= {M.RAW, M.HUFF0}
+    assert M.write(b"", bl, 2, elem, 1)[32:36] == M.MAGIC_END      # an empty input: header + trailer
 
 
 def test_mixed_kinds_in_one_frame_round_trip():
     x = np.concatenate([datagen.text_bytes(3 * 4096, seed=1), datagen.zipf_bytes(4 * 4096 + 100, seed=2)])
     for elem in (0, 4):
-        c = K.write(x, 4096, 4, elem, kinds=[0, 2, 1, 2, 0, 1])
-        data, kinds = K.read(c, with_kinds=True)
+        c = M.write(x, 4096, 4, elem, kinds=[0, 2, 1, 2, 0, 1])
+        data, kinds = READ3(c, with_kinds=True)
         assert np.array_equal(data, x) and {0, 1, 2} <= set(kinds[:4])
 
 
@@ -161,19 +174,19 @@ def _refused(reader, c):
 def test_older_readers_refuse_version_3_and_the_version_3_reader_refuses_what_the_format_forbids():
     n, rows, elem = 4096, 3, 4
     x = np.concatenate([typed_datagen.typed_bytes("smooth32", 5 * n, seed=4), datagen.zipf_bytes(2 * n + 123, seed=4)])
-    c = K.write(x, n, rows, elem, 1)
-    assert _refused(M.read, c) == (M.STREAM_HEADER, -1, -1)
-    assert _refused(F.read, c) == (M.STREAM_HEADER, -1, -1)
-    assert _refused(F.read, K.write(x, n, rows, 0, 1)) == (M.STREAM_HEADER, -1, -1)
-    cases, lay = K.corrupted_cases(c, x, n, rows, elem)
+    c = M.write(x, n, rows, elem, 1)
+    assert _refused(READ1, c) == (M.STREAM_HEADER, -1, -1)
+    assert _refused(READ2, c) == (M.STREAM_HEADER, -1, -1)
+    assert _refused(READ2, M.write(x, n, rows, 0, 1)) == (M.STREAM_HEADER, -1, -1)
+    cases, lay = M.corrupted_cases(c, x, n, rows, elem)
     whats = set()
     for cont, want in cases:
-        assert _refused(K.read, cont) == want
+        assert _refused(READ3, cont) == want
         whats.add(want[0])
     assert whats == {1, 2, 3, 4} and len(cases) >= 13            # one word short and one word long are among them
-    assert _refused(K.read, c[:lay["frames"][1]["start"] + 40])[0] == M.TRUNCATED
-    assert _refused(K.read, c[:-1])[0] == M.TRUNCATED
-    assert np.array_equal(K.read(c), x)
+    assert _refused(READ3, c[:lay["frames"][1]["start"] + 40])[0] == M.TRUNCATED
+    assert _refused(READ3, c[:-1])[0] == M.TRUNCATED
+    assert np.array_equal(READ3(c), x)
 
 
 def test_golden_fixture_is_what_its_generator_makes():
@@ -187,10 +200,10 @@ def test_golden_fixture_is_what_its_generator_makes():
     assert len(gold) < 64 << 10
     assert g.make() == gold
     assert struct.unpack("<HHII", gold[4:16]) == (3, 0, g.BLOCK, g.ELEM)
-    data, kinds = K.read(gold, with_kinds=True)
+    data, kinds = READ3(gold, with_kinds=True)
     assert np.array_equal(data, x)
-    assert {M.HUFF, M.RAW, K.HUFF0} <= set(kinds) and len(kinds) == 10
-    assert _refused(F.read, gold) == (M.STREAM_HEADER, -1, -1)
+    assert {M.HUFF, M.RAW, M.HUFF0} <= set(kinds) and len(kinds) == 10
+    assert _refused(READ2, gold) == (M.STREAM_HEADER, -1, -1)
 
 
 # --- what the codec is for ---------------------------------------------------------------------------------------------------
@@ -198,7 +211,7 @@ MiB = 1 << 20
 
 
 def _kinds(x, elem, codec=1):
-    c = K.write(x, 65536, 4, elem, codec)
+    c = M.write(x, 65536, 4, elem, codec)
     return [k for f in M.layout(c)["frames"] for _, _, k in f["records"]], len(c)
 
 
@@ -209,11 +222,11 @@ def test_kinds_are_what_the_inputs_were_chosen_for():
                           ("quant16", typed_datagen.typed_bytes("quant16", MiB, seed=1), 2),
                           ("quant16 unfiltered", typed_datagen.typed_bytes("quant16", MiB, seed=1), 0)):
         kinds, _ = _kinds(x, elem)
-        assert kinds.count(K.HUFF0) == 16 and kinds.count(M.RAW) == 0, name
+        assert kinds.count(M.HUFF0) == 16 and kinds.count(M.RAW) == 0, name
     kinds, _ = _kinds(np.random.default_rng(1).integers(0, 256, MiB, dtype=np.uint8), 0)
     assert kinds.count(M.RAW) == 16                              # uniform bytes: every block raw
     kinds, _ = _kinds(typed_datagen.typed_bytes("float32", MiB, seed=1), 4)
-    assert kinds.count(M.RAW) == 8 and kinds.count(K.HUFF0) == 8   # float32 N(0,1): the mantissa planes raw, the high planes coded
+    assert kinds.count(M.RAW) == 8 and kinds.count(M.HUFF0) == 8   # float32 N(0,1): the mantissa planes raw, the high planes coded
 
 
 def test_order0_is_smaller_on_zipf_and_larger_on_text():

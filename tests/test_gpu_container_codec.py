@@ -1,5 +1,5 @@
 """The container's order-0 Huffman codec on the MI355X (-m gpu): codec BWT is version 1 / 2 byte for byte; codec HUFF0 is
-byte-identical to the Python model of version 3 (tests/container_codec_model.py) through the device, host-pointer and file
+byte-identical to the Python model of version 3 (tests/container_model.py) through the device, host-pointer and file
 entry points, with pipelining on and off, and from plain C; decoding by plans of other shapes and settings, of the golden
 fixture with all three kinds and of the version-1 / 2 fixtures; refusals with their glcContainerLastError triples; capacity;
 the plan's timing and profile interfaces with the codec on."""
@@ -10,8 +10,6 @@ import subprocess
 import numpy as np
 import pytest
 
-import container_codec_model as K
-import container_filter_model as F
 import container_model as M
 import datagen
 import typed_datagen
@@ -81,7 +79,7 @@ def _lengths(n, rows, elem):
 
 
 def _frames_with_both(c):
-    return sum(1 for f in M.layout(c)["frames"] if {k for _, _, k in f["records"]} >= {M.RAW, K.HUFF0})
+    return sum(1 for f in M.layout(c)["frames"] if {k for _, _, k in f["records"]} >= {M.RAW, M.HUFF0})
 
 
 def _plan(glc, ctx, n, rows, elem=0, codec=1, pipelined=False):
@@ -102,7 +100,7 @@ def test_codec_bwt_default_and_after_a_reset_is_version_1_or_2(glc, ctx, cuda):
         glc.container_set_codec(plan, glc.CONTAINER_CODEC_HUFF0)
         assert glc.container_get_codec(plan) == 1
         c = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-        assert c == K.write(x, n, rows, 0, 1) and struct.unpack("<H", c[4:6])[0] == 3
+        assert c == M.write(x, n, rows, 0, 1) and struct.unpack("<H", c[4:6])[0] == 3
         for bad in (2, 3, 255, 1 << 31):
             with pytest.raises(glc.CudppError) as e:
                 glc.container_set_codec(plan, bad)
@@ -110,7 +108,7 @@ def test_codec_bwt_default_and_after_a_reset_is_version_1_or_2(glc, ctx, cuda):
         glc.container_set_codec(plan, glc.CONTAINER_CODEC_BWT)
         for elem in (0, 4):
             glc.container_set_shuffle(plan, elem)
-            want = F.write(x, n, rows, elem)
+            want = M.write(x, n, rows, elem)
             assert struct.unpack("<H", want[4:6])[0] == (2 if elem else 1)
             assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == want
             assert glc.container_compress_host(plan, x).tobytes() == want
@@ -128,7 +126,7 @@ def test_device_container_equals_the_model(glc, ctx, cuda, n, rows, elem, pipeli
         for i, L in enumerate(_lengths(n, rows, elem)):
             x = _mixed(elem, L, n, 10 * rows + i + 1)
             c = glc.container_compress(plan, _gpu(x))
-            want = K.write(x, n, rows, elem, 1)
+            want = M.write(x, n, rows, elem, 1)
             assert _host(c).tobytes() == want, (n, rows, elem, L)
             assert struct.unpack("<HHII", want[4:16]) == (3, 0, n, elem)
             assert c.numel() <= glc.container_bound(L, n)
@@ -145,7 +143,7 @@ def test_host_and_file_forms_equal_the_model(glc, ctx, cuda, tmp_path, n, rows, 
     with _plan(glc, ctx, n, rows, elem, 1, pipelined) as plan:
         for i, L in enumerate(_lengths(n, rows, elem)):
             x = _mixed(elem, L, n, 50 + i)
-            want = K.write(x, n, rows, elem, 1)
+            want = M.write(x, n, rows, elem, 1)
             c = glc.container_compress_host(plan, x)
             assert c.tobytes() == want, (n, rows, elem, L)
             assert np.array_equal(glc.container_decompress_host(plan, c), x)
@@ -163,7 +161,7 @@ def test_other_plans_decode_and_the_decoder_ignores_its_own_settings(glc, ctx, c
     x = _mixed(elem, 19 * n + 1235, n, 7)
     with _plan(glc, ctx, n, rows, elem, 1) as w:
         c = glc.container_compress(w, _gpu(x))
-    assert np.array_equal(K.read(_host(c).tobytes()), x)
+    assert np.array_equal(M.read(_host(c).tobytes()), x)
     assert _frames_with_both(_host(c).tobytes()) > 0
     for m, r, own_codec, own_elem, pipe in ((n, 3, 0, 0, False), (n, 1, 1, 2, True), (3 * n + 5, 2, 0, 8, False), (1 << 20, 2, 1, 4, True)):
         with _plan(glc, ctx, m, r, own_elem, own_codec, pipe) as p:
@@ -178,7 +176,7 @@ def test_other_plans_decode_and_the_decoder_ignores_its_own_settings(glc, ctx, c
 
 def test_gpu_reads_the_fixtures_of_all_three_versions(glc, ctx, cuda):
     gold = open(os.path.join(GOLDEN, "container_v3_mixed.bin"), "rb").read()
-    x, kinds = K.read(gold, with_kinds=True)
+    x, kinds = M.read(gold, with_kinds=True)
     assert {0, 1, 2} <= set(kinds)
     for n, rows, codec in ((4096, 4, 1), (4096, 1, 0), (70000, 2, 1)):
         with _plan(glc, ctx, n, rows, 0, codec) as plan:
@@ -186,7 +184,7 @@ def test_gpu_reads_the_fixtures_of_all_three_versions(glc, ctx, cuda):
             assert np.array_equal(glc.container_decompress_host(plan, np.frombuffer(gold, np.uint8)), x)
             for name in ("container_v1.bin", "container_v2_f32.bin"):    # ... and the older ones on a HUFF0 plan
                 old = open(os.path.join(GOLDEN, name), "rb").read()
-                assert np.array_equal(_host(glc.container_decompress(plan, _gpu(np.frombuffer(old, np.uint8)))), F.read(old))
+                assert np.array_equal(_host(glc.container_decompress(plan, _gpu(np.frombuffer(old, np.uint8)))), M.read(old))
 
 
 # --- 4. refusals ---------------------------------------------------------------------------------------------------------
@@ -204,13 +202,13 @@ def test_corrupted_version_3_containers_are_refused(glc, ctx, cuda):
     x = _mixed(elem, 7 * n + 123, n, 4)
     with _plan(glc, ctx, n, rows, elem, 1) as plan:
         c = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-        assert c == K.write(x, n, rows, elem, 1)
-        cases, lay = K.corrupted_cases(c, x, n, rows, elem)
+        assert c == M.write(x, n, rows, elem, 1)
+        cases, lay = M.corrupted_cases(c, x, n, rows, elem)
         assert len(cases) >= 12
         guard = 64
         for cont, want in cases:
             with pytest.raises(M.ContainerError) as merr:          # the model
-                K.read(cont)
+                M.read(cont)
             assert (merr.value.what, merr.value.frame, merr.value.block) == want
             out = torch.full((x.size + guard,), 0xAB, dtype=torch.uint8, device=cuda)
             with pytest.raises(glc.CudppError) as err:
@@ -236,7 +234,7 @@ def test_capacity_with_the_codec_on(glc, ctx, cuda):
     n, rows, elem = 70000, 2, 8
     x = _mixed(elem, 2 * n + 999, n, 9)
     with _plan(glc, ctx, n, rows, elem, 1) as plan:
-        need = len(K.write(x, n, rows, elem, 1))
+        need = len(M.write(x, n, rows, elem, 1))
         for cap in (need - 1, need - 20, need // 2, 100):
             out = torch.full((cap + 256,), 0xCD, dtype=torch.uint8, device=cuda)
             d_len = torch.zeros(1, dtype=torch.int64, device=cuda)
@@ -256,7 +254,7 @@ def test_capacity_with_the_codec_on(glc, ctx, cuda):
 def test_timing_and_kernel_profile_with_the_codec_on(glc, ctx, cuda, pipelined):
     n, rows, elem = 65536, 4, 4
     x = _mixed(elem, 9 * n + 777, n, 3)
-    want = K.write(x, n, rows, elem, 1)
+    want = M.write(x, n, rows, elem, 1)
     with _plan(glc, ctx, n, rows, elem, 1, pipelined) as plan:
         for mode in (1, 3):
             plan.enable_timing(mode)

@@ -1,5 +1,5 @@
 """The delta mode of the container's filter on the MI355X (-m gpu): delta on is byte-identical to the Python model of format
-version 4 (tests/container_delta_model.py) for every element size, both codecs and pipelining on and off, through the device,
+version 4 (tests/container_model.py) for every element size, both codecs and pipelining on and off, through the device,
 host-pointer and file entry points, and from plain C; the golden fixture decodes; a plan's own delta setting does not matter to
 its decoder; the setters' rules; refusals with their glcContainerLastError triples; capacity."""
 import os
@@ -9,9 +9,6 @@ import subprocess
 import numpy as np
 import pytest
 
-import container_codec_model as K
-import container_delta_model as D
-import container_filter_model as F
 import container_model as M
 import series_datagen
 
@@ -62,7 +59,7 @@ def _input(elem):
 
 def _want(elem, codec):
     if (elem, codec) not in _WANT:
-        _WANT[elem, codec] = D.write(_input(elem), N, _rows(elem), elem, codec, delta=True)
+        _WANT[elem, codec] = M.write(_input(elem), N, _rows(elem), elem, codec, delta=True)
     return _WANT[elem, codec]
 
 
@@ -85,7 +82,7 @@ def test_all_entry_points_equal_the_model_and_round_trip(glc, ctx, cuda, tmp_pat
     assert struct.unpack("<I", want[4:8])[0] == 0x00010004 and struct.unpack("<II", want[8:16]) == (N, elem)
     frames = M.layout(want)["frames"]
     assert [f["nb"] for f in frames] == [_rows(elem), _rows(elem), 2, 1]
-    assert {k for f in frames for _, _, k in f["records"]} == {M.RAW, K.HUFF0 if codec else M.HUFF}
+    assert {k for f in frames for _, _, k in f["records"]} == {M.RAW, M.HUFF0 if codec else M.HUFF}
     with _plan(glc, ctx, elem, codec, pipelined) as plan:
         assert glc.container_get_delta(plan) == 1
         c = glc.container_compress(plan, _gpu(x))
@@ -105,14 +102,14 @@ def test_all_entry_points_equal_the_model_and_round_trip(glc, ctx, cuda, tmp_pat
         for L in (0, elem - 1):                                 # nothing; less than an element
             y = x[:L]
             c = glc.container_compress(plan, _gpu(y))
-            assert _host(c).tobytes() == D.write(y, N, _rows(elem), elem, codec, delta=True)
+            assert _host(c).tobytes() == M.write(y, N, _rows(elem), elem, codec, delta=True)
             assert np.array_equal(_host(glc.container_decompress(plan, c)), y)
 
 
 # --- 2. decoding -----------------------------------------------------------------------------------------------------------
 def test_gpu_reads_the_golden_fixture(glc, ctx, cuda):
     gold = open(os.path.join(GOLDEN, "container_v4_series.bin"), "rb").read()
-    x, kinds = D.read(gold, with_kinds=True)
+    x, kinds = M.read(gold, with_kinds=True)
     assert {0, 1, 2} <= set(kinds)
     g = np.frombuffer(gold, np.uint8)
     for n, rows, elem, codec, delta in ((4096, 8, 8, 1, True), (4096, 1, 0, 0, False), (70000, 2, 4, 1, True)):
@@ -124,7 +121,7 @@ def test_gpu_reads_the_golden_fixture(glc, ctx, cuda):
 def test_the_decoder_ignores_its_plans_delta_setting(glc, ctx, cuda):
     elem = 4
     x, v4 = _input(elem), _want(elem, 1)
-    older = [M.write(x, N, 4), F.write(x, N, 4, elem), K.write(x, N, 4, elem, 1), K.write(x, N, 4, 0, 1)]
+    older = [M.write(x, N, 4), M.write(x, N, 4, elem), M.write(x, N, 4, elem, 1), M.write(x, N, 4, 0, 1)]
     with _plan(glc, ctx, 0, 0, delta=False) as off:            # delta (and shuffle) off: decodes version 4
         assert glc.container_get_delta(off) == 0
         assert np.array_equal(_host(glc.container_decompress(off, _gpu(np.frombuffer(v4, np.uint8)))), x)
@@ -164,7 +161,7 @@ def test_setters_and_what_a_cleared_shuffle_writes(glc, ctx, cuda):
         assert glc.container_get_delta(plan) == 1 and glc.container_get_shuffle(plan) == elem
         assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == _want(elem, 0)
         glc.container_set_delta(plan, 0)                        # delta off: version 2 byte for byte
-        assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == F.write(x, N, 4, elem)
+        assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == M.write(x, N, 4, elem)
         for codec, clear in ((0, 0), (1, 1)):                   # delta set, then the shuffle cleared: version 1 or 3
             glc.container_set_codec(plan, codec)
             glc.container_set_shuffle(plan, elem)
@@ -172,10 +169,10 @@ def test_setters_and_what_a_cleared_shuffle_writes(glc, ctx, cuda):
             glc.container_set_shuffle(plan, clear)
             assert glc.container_get_delta(plan) == 0 and glc.container_get_shuffle(plan) == 0
             c = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-            assert c == K.write(x, N, 4, 0, codec) and struct.unpack("<HH", c[4:8]) == (3 if codec else 1, 0)
+            assert c == M.write(x, N, 4, 0, codec) and struct.unpack("<HH", c[4:8]) == (3 if codec else 1, 0)
             glc.container_set_shuffle(plan, elem)               # ... and the shuffle back on does not bring it back
             assert glc.container_get_delta(plan) == 0
-            assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == K.write(x, N, 4, elem, codec)
+            assert _host(glc.container_compress(plan, _gpu(x))).tobytes() == M.write(x, N, 4, elem, codec)
 
 
 # --- 4. refusals ---------------------------------------------------------------------------------------------------------
@@ -198,13 +195,13 @@ def test_refusal_matrix_of_version_4(glc, ctx, cuda, codec):
         glc.container_set_delta(plan, 0)
         glc.container_set_codec(plan, 1)
         c3 = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-        assert c3 == K.write(x, N, 4, elem, 1)
-        cases, lay = D.refusal_cases(c4, c3, elem)
-        assert len(cases) >= 17 and (D.with_header(c4, 4, 0, elem), (1, -1, -1)) in cases
+        assert c3 == M.write(x, N, 4, elem, 1)
+        cases, lay = M.refusal_cases(c4, c3, elem)
+        assert len(cases) >= 17 and (M.with_header(c4, 4, 0, elem), (1, -1, -1)) in cases
         guard = 64
         for cont, want in cases:
             with pytest.raises(M.ContainerError) as merr:          # the model
-                D.read(cont)
+                M.read(cont)
             assert (merr.value.what, merr.value.frame, merr.value.block) == want
             out = torch.full((x.size + guard,), 0xAB, dtype=torch.uint8, device=cuda)
             with pytest.raises(glc.CudppError) as err:

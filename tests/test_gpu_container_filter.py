@@ -1,5 +1,5 @@
 """The container's byte-plane shuffle filter on the MI355X (-m gpu): filter off is version 1 byte for byte; filter on is
-byte-identical to the Python model of version 2 (tests/container_filter_model.py) through the device, host-pointer and file
+byte-identical to the Python model of version 2 (tests/container_model.py) through the device, host-pointer and file
 entry points, with pipelining on and off, and from plain C; decoding by plans of other shapes and settings, of the golden
 fixture and of version-1 containers; refusals with their glcContainerLastError triples; the effect on float32 data; the
 plan's timing and profile interfaces with the filter on."""
@@ -11,7 +11,6 @@ import zlib
 import numpy as np
 import pytest
 
-import container_filter_model as F
 import container_model as M
 import datagen
 import typed_datagen
@@ -68,7 +67,7 @@ def test_filter_off_or_reset_is_version_1(glc, ctx, cuda):
         glc.container_set_shuffle(plan, 4)
         assert glc.container_get_shuffle(plan) == 4
         c = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-        assert c != want and c == F.write(x, n, rows, 4)
+        assert c != want and c == M.write(x, n, rows, 4)
         for bad in (3, 5, 16, 64):
             with pytest.raises(glc.CudppError) as e:
                 glc.container_set_shuffle(plan, bad)
@@ -95,7 +94,7 @@ def test_device_container_equals_the_model(glc, ctx, cuda, n, rows, elem, pipeli
         for i, L in enumerate(_lengths(n, rows, elem)):
             x = _typed(elem, L, 10 * rows + i + 1)
             c = glc.container_compress(plan, _gpu(x))
-            want = F.write(x, n, rows, elem)
+            want = M.write(x, n, rows, elem)
             assert _host(c).tobytes() == want, (n, rows, elem, L)
             assert c.numel() <= glc.container_bound(L, n)
             back = glc.container_decompress(plan, c)
@@ -111,7 +110,7 @@ def test_host_and_file_forms_equal_the_model(glc, ctx, cuda, tmp_path, n, rows, 
         glc.container_set_shuffle(plan, elem)
         for i, L in enumerate(_lengths(n, rows, elem)):
             x = _typed(elem, L, 50 + i)
-            want = F.write(x, n, rows, elem)
+            want = M.write(x, n, rows, elem)
             c = glc.container_compress_host(plan, x)
             assert c.tobytes() == want, (n, rows, elem, L)
             assert np.array_equal(glc.container_decompress_host(plan, c), x)
@@ -132,7 +131,7 @@ def test_other_plans_decode_and_the_decoder_ignores_its_own_setting(glc, ctx, cu
         c = glc.container_compress(w, _gpu(x))
         v1 = M.write(x, n, rows)
         assert np.array_equal(_host(glc.container_decompress(w, _gpu(np.frombuffer(v1, np.uint8)))), x)   # version 1, filter on
-    assert np.array_equal(F.read(_host(c).tobytes()), x)
+    assert np.array_equal(M.read(_host(c).tobytes()), x)
     for m, r, own, pipe in ((n, 3, 0, False), (n, 1, 2, True), (3 * n + 5, 2, 8, False), (1 << 20, 2, 4, True)):
         with glc.Plan(ctx, glc.CUDPP_COMPRESS, m, rows=r) as p:
             p.set_pipelining(pipe)
@@ -148,7 +147,7 @@ def test_other_plans_decode_and_the_decoder_ignores_its_own_setting(glc, ctx, cu
 
 def test_gpu_reads_the_golden_fixture_and_writes_it(glc, ctx, cuda):
     gold = open(os.path.join(ROOT, "tests", "golden", "container_v2_f32.bin"), "rb").read()
-    x = F.read(gold)
+    x = M.read(gold)
     for n, rows in ((4096, 4), (4096, 1), (70000, 2)):
         with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as plan:
             assert np.array_equal(_host(glc.container_decompress(plan, _gpu(np.frombuffer(gold, np.uint8)))), x)
@@ -178,7 +177,7 @@ def test_corrupted_version_2_containers_are_refused(glc, ctx, cuda):
     with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as plan:
         glc.container_set_shuffle(plan, elem)
         c = _host(glc.container_compress(plan, _gpu(x))).tobytes()
-        assert c == F.write(x, n, rows, elem)
+        assert c == M.write(x, n, rows, elem)
         v1 = M.write(x, n, rows)
         lay = M.layout(c)
         s, e, _ = lay["frames"][1]["records"][1]
@@ -196,7 +195,7 @@ def test_corrupted_version_2_containers_are_refused(glc, ctx, cuda):
             assert err.value.code == UNKNOWN
             assert glc.container_last_error(plan) == want
             with pytest.raises(M.ContainerError) as merr:          # the model agrees
-                F.read(cont)
+                M.read(cont)
             assert (merr.value.what, merr.value.frame, merr.value.block) == want
             assert bool((out[x.size:] == 0xAB).all())
             with pytest.raises(glc.CudppError):
@@ -218,7 +217,7 @@ def test_capacity_with_the_filter_on(glc, ctx, cuda):
     x = _typed(elem, 2 * n + 999, 9)
     with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as plan:
         glc.container_set_shuffle(plan, elem)
-        need = len(F.write(x, n, rows, elem))
+        need = len(M.write(x, n, rows, elem))
         for cap in (need - 1, 100):
             out = torch.full((cap + 256,), 0xCD, dtype=torch.uint8, device=cuda)
             d_len = torch.zeros(1, dtype=torch.int64, device=cuda)
@@ -254,7 +253,7 @@ def test_float32_is_smaller_with_the_filter(glc, ctx, cuda):
 def test_timing_and_kernel_profile_with_the_filter_on(glc, ctx, cuda, pipelined):
     n, rows, elem = 65536, 4, 4
     x = _typed(elem, 9 * n + 777, 3)
-    want = F.write(x, n, rows, elem)
+    want = M.write(x, n, rows, elem)
     with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as plan:
         plan.set_pipelining(pipelined)
         glc.container_set_shuffle(plan, elem)

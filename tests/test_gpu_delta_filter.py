@@ -1,12 +1,12 @@
 """The fused delta + shuffle kernels alone on the MI355X (-m gpu): glcDeltaShuffleDevice and glcUndeltaUnshuffleDevice against the
-numpy definition of tests/container_delta_model.py for element sizes 2, 4 and 8 -- lengths around an element, a run (2048
+numpy definition of tests/container_model.py for element sizes 2, 4 and 8 -- lengths around an element, a run (2048
 elements) and a 16 KiB tile, several tiles and more than 2^20 bytes; every pairing of input and output misalignments; series that
 wrap, carries across the dword boundary of 8-byte elements, a run boundary inside a last partial tile; guard bytes on both sides
 of the output; refusals that leave the output untouched."""
 import numpy as np
 import pytest
 
-import container_delta_model as D
+import container_model as M
 
 pytestmark = pytest.mark.gpu
 
@@ -41,8 +41,8 @@ def _series(e, n, seed):
 def _check_both(glc, torch, cuda, e, x, offsets):
     """forward and inverse of x at every (input offset, output offset) of `offsets`, against the model, guards included"""
     n = x.size
-    want = D.delta_shuffle(x, e)
-    assert np.array_equal(D.undelta_unshuffle(want, e), x)
+    want = M.delta_shuffle(x, e)
+    assert np.array_equal(M.undelta_unshuffle(want, e), x)
     d_x, d_want = torch.from_numpy(x.copy()).to(cuda), torch.from_numpy(want.copy()).to(cuda)
     src = _aligned(torch, n + 16, cuda)
     for fn, a, b in ((glc.delta_shuffle, d_x, d_want), (glc.undelta_unshuffle, d_want, d_x)):
@@ -120,4 +120,4 @@ def test_refusals_leave_the_output_untouched(glc, cuda):
     both = torch.zeros(2 * n, dtype=torch.uint8, device=cuda)
     both[:n] = src
     fn(both[:n], 4, out=both[n:])
-    assert np.array_equal(both[n:].cpu().numpy(), D.delta_shuffle(src.cpu().numpy(), 4))
+    assert np.array_equal(both[n:].cpu().numpy(), M.delta_shuffle(src.cpu().numpy(), 4))

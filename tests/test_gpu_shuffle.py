@@ -4,7 +4,7 @@ batched form against the per-segment results; refusals that write nothing."""
 import numpy as np
 import pytest
 
-import container_filter_model as F
+import container_model as M
 
 pytestmark = pytest.mark.gpu
 
@@ -23,8 +23,8 @@ def test_forward_and_inverse_equal_numpy_at_every_alignment(glc, cuda, elem):
     rng = np.random.default_rng(elem)
     for n in _lengths(elem):
         x = rng.integers(0, 256, n, dtype=np.uint8)
-        y = F.shuffle(x, elem)                                 # numpy: the reference for every alignment of this length
-        assert np.array_equal(F.unshuffle(y, elem), x)
+        y = M.shuffle(x, elem)                                 # numpy: the reference for every alignment of this length
+        assert np.array_equal(M.unshuffle(y, elem), x)
         d_x, d_y = torch.from_numpy(x).to(cuda), torch.from_numpy(y).to(cuda)
         src = torch.empty(n + 64, dtype=torch.uint8, device=cuda)
         dst = torch.empty(n + 64 + 2 * GUARD, dtype=torch.uint8, device=cuda)
@@ -58,7 +58,7 @@ def test_batched_form_equals_the_per_segment_results(glc, cuda, elem, count):
     x = rng.integers(0, 256, total, dtype=np.uint8)
     want_f = np.full(total, 0x5A, np.uint8)
     for o, n in zip(offs, lens):
-        want_f[o:o + n] = F.shuffle(x[o:o + n], elem)
+        want_f[o:o + n] = M.shuffle(x[o:o + n], elem)
     d_x = torch.from_numpy(x).to(cuda)
     out = torch.full((total,), 0x5A, dtype=torch.uint8, device=cuda)
     glc.shuffle_segments(d_x, out, offs, lens, elem)
