@@ -254,13 +254,180 @@ constexpr uint32_t MTF_SEG = 1024;                          // positions per seg
 #endif
 constexpr uint32_t MTF_QUARTERS_MAX_CHUNKS = GLC_MTF_QUARTERS_MAX;   // up to this many chunks in a launch: one wave per chunk
 
+// The pieces that the ragged and the FULL form of k_mtf_encode share (the kernel's comment says what they are for).
+//
+// re-base at a segment's end: the live timestamp of symbol c, t, becomes (live timestamps below t) = t - (killed below t);
+// every lane takes 16 symbols of its row's table, the prefix counts are those of the segment's last batch.  The ragged
+// form's loop holds a copy of this body (a call from there changes that form's machine code): change both together.
+__device__ __forceinline__ void mtf_rebase(uint32_t *tab, unsigned long long *bm, uint16_t *cum, uint32_t lr)
+{
+#pragma unroll 4
+    for (int k = 0; k < 16; k++) {
+        const uint32_t c = 16u * (uint32_t)k + lr;         // (lane-consecutive symbols: consecutive banks)
+        const uint32_t t = tab[c] >> 16, wd = t >> 6;
+        const uint32_t kb = cum[wd] + (uint32_t)__popcll(bm[wd] << (63u - (t & 63u)));   // (bit t itself is live: not set)
+        tab[c] = (t - kb) << 16;
+    }
+    __builtin_amdgcn_wave_barrier();
+    bm[2 * lr] = 0; bm[2 * lr + 1] = 0;
+    reinterpret_cast<uint32_t *>(cum)[lr] = 0;
+    __builtin_amdgcn_wave_barrier();
+}
+
+// G = 15 - lr + #{k < lr : P[k] < P[lr]}: lane lr meets P[lr-1], ... P[0] through DPP row_shr:1..15; each step is
+// (shifted P) - P with the borrow added up, and the 15 - lr steps that have no source lane read 0 < Pb
+__device__ __forceinline__ uint32_t mtf_slide(uint32_t Pb)
+{
+    uint32_t G = 0, t0;
+#define GLC_SLIDE(K)                                                                                    \
+    "v_sub_co_u32_dpp %1, vcc, %2, %2 row_shr:" #K " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"            \
+    "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n\t"
+    asm volatile(GLC_SLIDE(1) GLC_SLIDE(2) GLC_SLIDE(3) GLC_SLIDE(4) GLC_SLIDE(5) GLC_SLIDE(6) GLC_SLIDE(7) GLC_SLIDE(8)
+                 GLC_SLIDE(9) GLC_SLIDE(10) GLC_SLIDE(11) GLC_SLIDE(12) GLC_SLIDE(13) GLC_SLIDE(14) GLC_SLIDE(15)
+                 : "+v"(G), "=&v"(t0) : "v"(Pb) : "vcc");
+#undef GLC_SLIDE
+    return G;
+}
+
+// prefix counts of the killed-timestamp bitmap: 2 words per lane, scan across the row
+__device__ __forceinline__ void mtf_recount(const unsigned long long *bm, uint16_t *cum, uint32_t lr)
+{
+    const uint4 v = *reinterpret_cast<const uint4 *>(bm + 2 * lr);
+    const uint32_t c0 = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
+    const uint32_t sum = c0 + (uint32_t)__builtin_popcount(v.z) + (uint32_t)__builtin_popcount(v.w);
+    uint32_t inc = sum;
+    inc += GLC_DPP(inc, 0x111, 0xf);
+    inc += GLC_DPP(inc, 0x112, 0xf);
+    inc += GLC_DPP(inc, 0x114, 0xf);
+    inc += GLC_DPP(inc, 0x118, 0xf);
+    const uint32_t r0 = inc - sum;
+    reinterpret_cast<uint32_t *>(cum)[lr] = r0 | ((r0 + c0) << 16);
+}
+
+
+// --- FULL form of k_mtf_encode: see the kernel ---
+// A/B switches (build.py: GLC_CXXFLAGS=-D... with GLC_LIB_OUT): the request distance and the batches per group, measured
+// in profiles/mtf_full_rows.md.  GLC_MTF_FULL_GROUP=1 is the fixed-trip body alone, without the unroll and its immediates.
+#ifndef GLC_MTF_REQ_DIST
+#define GLC_MTF_REQ_DIST 1
+#endif
+constexpr int MTF_REQ = GLC_MTF_REQ_DIST;                  // batches between a byte's request and its use
+#ifndef GLC_MTF_FULL_GROUP
+#define GLC_MTF_FULL_GROUP 4
+#endif
+constexpr int MTF_GROUP = GLC_MTF_FULL_GROUP;               // batches per unrolled group
+static_assert(MTF_REQ >= 1 && MTF_GROUP % MTF_REQ == 0 && MTF_SEG % (16 * MTF_GROUP) == 0 && MTF_CHUNK % MTF_SEG == 0, "group shape");
+
+// One group of MTF_GROUP batches, the first at position lbg of its segment; voff = the lane's offset from sb / db.
+// LASTG: the chunk's last group, whose last MTF_REQ batches request nothing (no address at or past the row's end is formed).
+template <bool WITH_HIST, bool ZEROS, bool LASTG>
+__device__ __forceinline__ void mtf_full_group(const uint8_t *__restrict__ sb, uint8_t *__restrict__ db, uint32_t voff,
+                                               uint32_t lbg, uint32_t (&q)[MTF_REQ], uint32_t *tab, unsigned long long *bm,
+                                               uint16_t *cum, uint32_t *hist, uint32_t lr, uint32_t row)
+{
+    const uint32_t mybit = 1u << lr, below = mybit - 1u;
+    const uint8_t *sp = sb + voff;
+    uint8_t *dp = db + voff;
+    uint16_t *killp = reinterpret_cast<uint16_t *>(bm) + ((lbg + 256u) >> 4);
+#pragma unroll
+    for (int j = 0; j < MTF_GROUP; j++) {
+        const uint32_t lb = lbg + 16u * j;
+        const uint32_t sym = q[0];
+#pragma unroll
+        for (int d = 0; d + 1 < MTF_REQ; d++) q[d] = q[d + 1];
+        if (!LASTG || j + MTF_REQ < MTF_GROUP) q[MTF_REQ - 1] = sp[16 * (j + MTF_REQ)];   // in flight during MTF_REQ batches
+        atomicOr(&tab[sym], mybit);
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t e = tab[sym];
+        const uint32_t before = e & below;
+        const bool hasprev = before != 0;
+        const uint32_t p = 31u - (uint32_t)__builtin_clz(before | 1u);
+        const bool last_in_batch = ((e & 0xFFFFu) >> lr) == 1u;
+        uint32_t Pb = hasprev ? lb + p + 257u : (e >> 16) + 1u;
+        // The slide's first instruction reads Pb through DPP, which needs two wait states behind the VALU write of Pb.  The
+        // compiler's hazard pass does not see the DPP read inside the asm: in the chunk's last group, which is straight-line
+        // code, it put the v_cndmask that selects Pb one wait state ahead of the slide, and every output of those four
+        // batches was one too small.  Tied to Pb so that it cannot move ahead of the write.  (The ragged form shares
+        // mtf_slide without this: there both arms of the select are exec-masked and an s_or exec + the move that clears G
+        // stand between the write and the slide.  That is the schedule's doing, not a guarantee; its code is left as the
+        // parent's here.)
+        asm volatile("s_nop 1" : "+v"(Pb));
+        const uint32_t T = mtf_slide(Pb) + lr - 15u;
+        const uint32_t bitx = Pb - 1u;
+        uint32_t o;
+        if (hasprev) o = T - (p + 1u);
+        else {
+            const uint32_t wd = bitx >> 6, r = bitx & 63;
+            const uint32_t kb = cum[wd] + (uint32_t)__popcll(bm[wd] << (63u - r));
+            o = T + kb + 255u - bitx;
+        }
+        __builtin_amdgcn_wave_barrier();
+        {
+            const uint64_t nl = __ballot(!last_in_batch);
+            if (lr == 0) killp[j] = (uint16_t)(nl >> (16u * row));
+        }
+        if (WITH_HIST && ZEROS) {
+            const uint64_t zb = __ballot(o == 0);
+            const uint32_t zrow = (uint32_t)(zb >> (16u * row)) & 0xFFFFu;
+            if (lr == 0 && zrow) atomicAdd(&hist[0], (uint32_t)__builtin_popcount(zrow));
+        }
+        dp[16 * j] = (uint8_t)o;
+        if (WITH_HIST && !(ZEROS && o == 0)) atomicAdd(&hist[o & 127], 1u << ((o >> 3) & 16));
+        if (!hasprev) atomicOr(&reinterpret_cast<uint32_t *>(bm)[bitx >> 5], 1u << (bitx & 31));
+        if (last_in_batch) tab[sym] = (lb + lr + 256u) << 16;
+        __builtin_amdgcn_wave_barrier();
+        mtf_recount(bm, cum, lr);
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// The row's whole chunk: sb / db = the block's input and output (wave-uniform), lo = the chunk's offset in the block.
+template <bool WITH_HIST, bool ZEROS>
+__device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ sb, uint8_t *__restrict__ db, uint32_t lo,
+                                                    const uint8_t *__restrict__ list, uint32_t *tab, unsigned long long *bm,
+                                                    uint16_t *cum, uint32_t *hist, uint32_t *__restrict__ H, uint32_t lr,
+                                                    uint32_t row)
+{
+    {
+        const uint4 lw = reinterpret_cast<const uint4 *>(list)[lr];
+        const uint32_t q[4] = {lw.x, lw.y, lw.z, lw.w};
+#pragma unroll
+        for (int j = 0; j < 16; j++) tab[(q[j >> 2] >> (8 * (j & 3))) & 0xFF] = (255u - (16 * lr + j)) << 16;   // time -1-q, biased by 256
+        bm[2 * lr] = 0; bm[2 * lr + 1] = 0;
+        reinterpret_cast<uint32_t *>(cum)[lr] = 0;
+        if (WITH_HIST) for (int i = lr; i < 128; i += 16) hist[i] = 0;
+        __builtin_amdgcn_wave_barrier();
+    }
+    uint32_t voff = lo + lr;
+    uint32_t q[MTF_REQ];
+#pragma unroll
+    for (int d = 0; d < MTF_REQ; d++) q[d] = sb[voff + 16u * d];
+    constexpr uint32_t NSEG = MTF_CHUNK / MTF_SEG, NGRP = MTF_SEG / (16 * MTF_GROUP);
+    for (uint32_t seg = 0; seg < NSEG; seg++) {
+        if (seg) mtf_rebase(tab, bm, cum, lr);
+        const uint32_t ng = seg + 1 < NSEG ? NGRP : NGRP - 1;      // the chunk's last group follows the loops
+        for (uint32_t g = 0; g < ng; g++, voff += 16 * MTF_GROUP)
+            mtf_full_group<WITH_HIST, ZEROS, false>(sb, db, voff, 16 * MTF_GROUP * g, q, tab, bm, cum, hist, lr, row);
+    }
+    mtf_full_group<WITH_HIST, ZEROS, true>(sb, db, voff, 16 * MTF_GROUP * (NGRP - 1), q, tab, bm, cum, hist, lr, row);
+    if (WITH_HIST) {
+        __builtin_amdgcn_wave_barrier();
+        for (int i = lr; i < 256; i += 16) H[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+    }
+}
+
 //
 // QUARTERS (small batches): the rows of a wave are the four QUARTERS of one chunk instead of four chunks, so a block on
 // its own is 256 waves of 64 batches, not 64 waves of 256 (0.145 -> ~0.05 ms with the rest of the machine idle; the
 // batch loop is a chain of LDS round trips, ~1400 cycles per batch for a wave alone on its SIMD).  The start lists of
 // quarters 1..3 are made here: recency list of the quarter before (as k_mtf_chunk_lists does for a chunk) folded into
 // its start list (the operator of k_mtf_scan_lists), three times, by the whole wave.
-template <bool WITH_HIST, bool QUARTERS, bool ZEROS = false>
+//
+// FULL (n a multiple of MTF_ROWS * MTF_CHUNK: every row of every wave is a whole chunk -- the 1 MiB blocks of the hot path):
+// nothing in the batch depends on a length.  The segment and batch loops count on a scalar, the batches come four to a
+// group, and the row's bytes are addressed as block pointer (scalar) + 32-bit lane offset + immediate, so a group advances
+// one offset where a batch advanced two 64-bit pointers.
+template <bool WITH_HIST, bool QUARTERS, bool ZEROS = false, bool FULL = false>
 __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__restrict__ in,
                                                               size_t in_stride, uint32_t n,
                                                               const uint8_t *__restrict__ lists,
@@ -291,6 +458,13 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
     const uint32_t chunk0 = QUARTERS ? blockIdx.x * MTF_WAVES + w : (blockIdx.x * MTF_WAVES + w) * MTF_ROWS;
     if (chunk0 >= nchunks) return;                                           // whole wave exits together
     const uint32_t chunk = QUARTERS ? chunk0 : chunk0 + row;
+    if constexpr (FULL) {
+        static_assert(!QUARTERS, "the rows of the FULL form are whole chunks");
+        mtf_encode_full_row<WITH_HIST, ZEROS>(in + (size_t)b * in_stride, out + (size_t)b * out_stride, chunk * MTF_CHUNK,
+                                              lists + ((size_t)b * max_chunks + chunk) * 256, s_tab[slot], s_bm[slot], s_cum[slot],
+                                              s_hist[WITH_HIST ? slot : 0], sub_hist + ((size_t)b * max_chunks + chunk) * 256, lr, row);
+        return;
+    }
     const uint32_t Cc0 = min(n, chunk0 * MTF_CHUNK + MTF_CHUNK) - chunk0 * MTF_CHUNK;   // length of the wave's first chunk
     bool live;
     uint32_t lo, C, Cmax;
@@ -381,6 +555,7 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
     for (uint32_t seg0 = 0; seg0 < Cmax; seg0 += MTF_SEG) {
         if (seg0) {
             // ---- re-base: the live timestamp of symbol c, t, becomes (live timestamps below t) = t - (killed below t) ----
+            // (a copy of mtf_rebase, which the FULL form calls: change both together)
             // (every lane takes 16 symbols of its row's table; the prefix counts are those of the segment's last batch)
 #pragma unroll 4
             for (int k = 0; k < 16; k++) {
@@ -413,15 +588,7 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
             const uint32_t Pb = hasprev ? lb + p + 257u : (e >> 16) + 1u;
             // T = #{k < lr : P[k] < P[lr]}: lane lr meets P[lr-1], ... P[0] through DPP row_shr:1..15; each step is
             // (shifted P) - P with the borrow added up, and the 15 - lr steps that have no source lane read 0 < Pb
-            uint32_t G = 0, t0;
-#define GLC_SLIDE(K)                                                                                                \
-            "v_sub_co_u32_dpp %1, vcc, %2, %2 row_shr:" #K " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"            \
-            "v_addc_co_u32_e32 %0, vcc, 0, %0, vcc\n\t"
-            asm volatile(GLC_SLIDE(1) GLC_SLIDE(2) GLC_SLIDE(3) GLC_SLIDE(4) GLC_SLIDE(5) GLC_SLIDE(6) GLC_SLIDE(7) GLC_SLIDE(8)
-                         GLC_SLIDE(9) GLC_SLIDE(10) GLC_SLIDE(11) GLC_SLIDE(12) GLC_SLIDE(13) GLC_SLIDE(14) GLC_SLIDE(15)
-                         : "+v"(G), "=&v"(t0) : "v"(Pb) : "vcc");
-#undef GLC_SLIDE
-            const uint32_t T = G + lr - 15u;
+            const uint32_t T = mtf_slide(Pb) + lr - 15u;
             const uint32_t bitx = Pb - 1u;                           // index into the killed-timestamp bitmap
             uint32_t o;
             if (hasprev) o = T - (p + 1u);
@@ -459,18 +626,7 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
             }
             __builtin_amdgcn_wave_barrier();
             // prefix counts of the killed-timestamp bitmap: 2 words per lane, scan across the row
-            {
-                const uint4 v = *reinterpret_cast<const uint4 *>(bm + 2 * lr);
-                const uint32_t c0 = (uint32_t)__builtin_popcount(v.x) + (uint32_t)__builtin_popcount(v.y);
-                const uint32_t sum = c0 + (uint32_t)__builtin_popcount(v.z) + (uint32_t)__builtin_popcount(v.w);
-                uint32_t inc = sum;
-                inc += GLC_DPP(inc, 0x111, 0xf);
-                inc += GLC_DPP(inc, 0x112, 0xf);
-                inc += GLC_DPP(inc, 0x114, 0xf);
-                inc += GLC_DPP(inc, 0x118, 0xf);
-                const uint32_t r0 = inc - sum;
-                reinterpret_cast<uint32_t *>(cum)[lr] = r0 | ((r0 + c0) << 16);
-            }
+            mtf_recount(bm, cum, lr);
             __builtin_amdgcn_wave_barrier();
         }
     }
@@ -535,6 +691,15 @@ hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint
                            out_stride, sub_hist, only);
     else if (quarters)
         hipLaunchKernelGGL((k_mtf_encode<false, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                           out_stride, sub_hist, only);
+    else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist && skewed)             // whole chunks in every row: the FULL form
+        hipLaunchKernelGGL((k_mtf_encode<true, false, true, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                           out_stride, sub_hist, only);
+    else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist)
+        hipLaunchKernelGGL((k_mtf_encode<true, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                           out_stride, sub_hist, only);
+    else if (n % (MTF_ROWS * MTF_CHUNK) == 0)
+        hipLaunchKernelGGL((k_mtf_encode<false, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
                            out_stride, sub_hist, only);
     else if (sub_hist && skewed)
         hipLaunchKernelGGL((k_mtf_encode<true, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
