@@ -1118,9 +1118,15 @@ hipError_t fs_scan(hipStream_t st, uint32_t nlisted, const uint32_t *fill, uint3
     return hipGetLastError();
 }
 
-hipError_t fs_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk, SaScratch &s,
-                    uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *sa_out)
+hipError_t fs_build(const SortCall &c, SaScratch &s)
 {
+    const hipStream_t st = c.st;
+    const uint8_t *const text = c.text;
+    const size_t text_stride = c.text_stride, bwt_stride = c.bwt_stride;
+    const uint32_t n = c.n, nblk = c.nblk;
+    uint8_t *const bwt_out = c.bwt_out;
+    int *const d_index = c.d_index;
+    uint32_t *const sa_out = c.sa_out(s);
     const uint32_t nbl = fs_bucket_log2(n), nb = 1u << nbl;
     {
         const uint32_t words = nblk * (256u + FS_MAXNB + 3u) + 8u, g = (words + 1023) / 1024;
@@ -1128,7 +1134,7 @@ hipError_t fs_build(hipStream_t st, const uint8_t *text, size_t text_stride, uin
         hipLaunchKernelGGL(k_fs_clear, dim3(g < 2048 ? g : 2048), dim3(256), 0, st, nblk, s.fs_hist, s.fs_fill, s.fs_flag,
                            s.skip_tier1 ? 1u : 0u, s.fs_wlcnt, s.fs_dup, s.fs_nflag);
     }
-    uint32_t *h_nflag = s.h_max_cnt + 4;                       // pinned, device-mapped: written by the kernel that finishes the pass
+    uint32_t *h_nflag = s.h_max_cnt + HW_FLAGGED;              // pinned, device-mapped: written (with HW_NOT_TEXTLIKE behind it) by the kernel that finishes the pass
     const double units = (double)n * nblk;
     int pi = s.prof ? s.prof->begin(PROF_FS_HIST, st) : -1;
     // statistics from every 4th 32 KB slice of a block of 512 KiB or more (the pass reads a quarter of the input: 0.27 -> 0.07 ms

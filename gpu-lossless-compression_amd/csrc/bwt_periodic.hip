@@ -243,35 +243,34 @@ hipError_t per_reserve(SaScratch &s)
     return hipSuccess;
 }
 
-hipError_t per_detect(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nlisted, SaScratch &s)
+hipError_t per_detect(const SortCall &c, SaScratch &s, uint32_t nlisted)
 {
-    GLC_TRY(hipMemsetAsync(s.per_count, 0, 16, st));
-    hipLaunchKernelGGL(k_per_detect, dim3(nlisted), dim3(PER_NT), 0, st, text, text_stride, n, s.ss_list, s.ss_flag, s.per_info,
+    GLC_TRY(hipMemsetAsync(s.per_count, 0, 16, c.st));
+    hipLaunchKernelGGL(k_per_detect, dim3(nlisted), dim3(PER_NT), 0, c.st, c.text, c.text_stride, c.n, s.ss_list, s.ss_flag, s.per_info,
                        s.per_list, s.per_count, s.rows < PER_TAKE ? s.rows : PER_TAKE, false);
     return hipGetLastError();
 }
 
-hipError_t per_probe(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nlisted, SaScratch &s)
+hipError_t per_probe(const SortCall &c, SaScratch &s, uint32_t nlisted)
 {
-    if (n < 16 * PER_PMAX) return hipSuccess;
-    hipLaunchKernelGGL(k_per_detect, dim3(nlisted), dim3(PER_NT), 0, st, text, text_stride, n, s.ss_list, s.ss_flag, (uint4 *)nullptr,
+    if (c.n < 16 * PER_PMAX) return hipSuccess;
+    hipLaunchKernelGGL(k_per_detect, dim3(nlisted), dim3(PER_NT), 0, c.st, c.text, c.text_stride, c.n, s.ss_list, s.ss_flag, (uint4 *)nullptr,
                        (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, true);
     return hipGetLastError();
 }
 
-hipError_t per_text(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nper, uint32_t nu, SaScratch &s)
+hipError_t per_text(const SortCall &c, SaScratch &s, uint32_t nper, uint32_t nu)
 {
-    hipLaunchKernelGGL(k_per_text, dim3((nu + 255) / 256 < 16 ? (nu + 255) / 256 : 16, nper), dim3(256), 0, st, text, text_stride, n,
+    hipLaunchKernelGGL(k_per_text, dim3((nu + 255) / 256 < 16 ? (nu + 255) / 256 : 16, nper), dim3(256), 0, c.st, c.text, c.text_stride, c.n,
                        s.per_list, s.per_info, s.per_text, nu);
     return hipGetLastError();
 }
 
-hipError_t per_expand(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nper, uint32_t nu, SaScratch &s,
-                      uint8_t *bwt_out, size_t bwt_stride, int *d_index)
+hipError_t per_expand(const SortCall &c, SaScratch &s, uint32_t nper, uint32_t nu)
 {
-    hipLaunchKernelGGL(k_per_bases, dim3(nper), dim3(PER_NT), 0, st, n, s.per_list, s.per_info, s.sa, s.nmax, nu, s.per_base, s.per_ok);
-    hipLaunchKernelGGL(k_per_rows, dim3((n + 4095) / 4096, nper), dim3(256), 0, st, text, text_stride, n, s.per_list, s.per_info, s.sa,
-                       s.nmax, nu, s.per_base, s.per_ok, bwt_out, bwt_stride, d_index, s.ss_flag, s.fs_lcnt, s.per_count + 2);
+    hipLaunchKernelGGL(k_per_bases, dim3(nper), dim3(PER_NT), 0, c.st, c.n, s.per_list, s.per_info, s.sa, s.nmax, nu, s.per_base, s.per_ok);
+    hipLaunchKernelGGL(k_per_rows, dim3((c.n + 4095) / 4096, nper), dim3(256), 0, c.st, c.text, c.text_stride, c.n, s.per_list, s.per_info, s.sa,
+                       s.nmax, nu, s.per_base, s.per_ok, c.bwt_out, c.bwt_stride, c.d_index, s.ss_flag, s.fs_lcnt, s.per_count + 2);
     return hipGetLastError();
 }
 

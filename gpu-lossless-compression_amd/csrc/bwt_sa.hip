@@ -1,7 +1,7 @@
 // bwt_sa.hip -- the GENERAL suffix sorter (any data, any LCP depth): suffix array + BWT for blocks of
-// <= 2^20 bytes, many blocks per launch (blockIdx.y = block).  gfx950 / wave64.  sa_build() at the end of this
-// file runs the bucket sorter of bwt_bucket.hip first and sends only the blocks that one flags (deep common
-// prefixes: text, logs, long repeats) through the kernels below.
+// <= 2^20 bytes, many blocks per launch (blockIdx.y = block).  gfx950 / wave64.  sa_build() (bwt_tiers.cpp) runs the
+// bucket sorter of bwt_bucket.hip first and sends only the blocks that one and the tiers behind it give up on (deep
+// common prefixes: text, logs, long repeats) through the kernels below.
 //
 // Replaces, result-for-result, the reference's
 //   cudppSuffixArrayDispatch / ComputeSA     (cudpp-inpar/src/cudpp/app/sa_app.cu:125-298,365-391)
@@ -1114,6 +1114,20 @@ __global__ __launch_bounds__(GRP_NT) void k_grp_keys(uint32_t n, uint32_t *__res
     if (blockIdx.x == 0 && tid == 0) cnt[b] = n;
 }
 
+// (host) the three passes above for the ndeep blocks listed for the sample sorter's tolerant form: the resumed doubling's words
+hipError_t grp_keys(const SortCall &c, SaScratch &s, uint32_t ndeep)
+{
+    const uint32_t *list3 = s.ss_list + 2 * (size_t)s.rows;
+    const uint32_t gt = (c.n + GRP_NT - 1) / GRP_NT, max_gt = (s.nmax + GRP_NT - 1) / GRP_NT;
+    GLC_TRY(hipMemsetAsync(s.ss_cnt2, 0, (size_t)s.rows * 4, c.st));
+    hipLaunchKernelGGL(k_grp_flags, dim3(gt, ndeep), dim3(GRP_NT), 0, c.st, c.text, c.text_stride, c.n, s.sa, s.nmax, list3,
+                       s.ss_flag, s.ss_gtile, max_gt, SS_TOL_CAP);
+    hipLaunchKernelGGL(k_grp_scan, dim3(ndeep), dim3(1024), 0, c.st, s.ss_gtile, max_gt, gt, list3, s.ss_flag);
+    hipLaunchKernelGGL(k_grp_keys, dim3(gt, ndeep), dim3(GRP_NT), 0, c.st, c.n, s.sa, s.nmax, list3, s.ss_flag,
+                       s.ss_gtile, max_gt, s.keyA, s.ss_cnt2);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
@@ -1163,10 +1177,10 @@ hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows)
     GLC_TRY(A((void **)&s.ghist, (size_t)rows * RS_MAXPASS * SA_MAXRADIX * 4));
     GLC_TRY(A((void **)&s.ticket, (size_t)rows * 4));
     GLC_TRY(A((void **)&s.cntA, (size_t)rows * 4)); GLC_TRY(A((void **)&s.cntB, (size_t)rows * 4));
-    GLC_TRY(A((void **)&s.d_max_cnt, 24));
+    GLC_TRY(A((void **)&s.d_max_cnt, RD_WORDS * 4));
     GLC_TRY(A((void **)&s.rl_flag, (size_t)rows * 4));
     GLC_TRY(A((void **)&s.rl_cnt, (size_t)rows * 4));
-    GLC_TRY(hipHostMalloc((void **)&s.h_max_cnt, 64, hipHostMallocDefault));
+    GLC_TRY(hipHostMalloc((void **)&s.h_max_cnt, 64, hipHostMallocDefault));   // (16 words >= HW_WORDS)
     sa_chain_defaults(&s.chain_min, &s.chain_rounds);
     s.bytes = total;
     return hipSuccess;
@@ -1238,15 +1252,15 @@ static hipError_t radix_sort(hipStream_t st, uint64_t *&cur, uint64_t *&alt, con
         if (pp.bits[p] == 8 && p == 0 && src)
             hipLaunchKernelGGL((k_rs_onesweep<8, true>), g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p],
                                s.tile_hist, s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX,
-                               (uint32_t)(RS_MAXPASS * SA_MAXRADIX), s.nmax, s.rs_tiles, s.d_max_cnt + 2, *src);
+                               (uint32_t)(RS_MAXPASS * SA_MAXRADIX), s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR, *src);
         else if (pp.bits[p] == 8)
             hipLaunchKernelGGL(k_rs_onesweep<8>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
                                s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
-                               s.nmax, s.rs_tiles, s.d_max_cnt + 2);
+                               s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
         else
             hipLaunchKernelGGL(k_rs_onesweep<9>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
                                s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
-                               s.nmax, s.rs_tiles, s.d_max_cnt + 2);
+                               s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
         if (pi >= 0) s.prof->end(pi, live_total, st);
         uint64_t *x = cur; cur = alt; alt = x;
     }
@@ -1262,30 +1276,30 @@ static hipError_t refine_sort(hipStream_t st, uint64_t *&cur, uint64_t *&alt, co
     GLC_TRY(hipMemsetAsync(s.rl_flag, 0, (size_t)nblk * 4, st));
     hipLaunchKernelGGL(k_refine_local, dim3((maxc + RL_T - 1) / RL_T, nblk), dim3(RL_NT), 0, st, cur, alt, cnt, s.nmax,
                        gshift, s.rl_flag);
-    GLC_TRY(hipMemsetAsync(s.d_max_cnt + 3, 0, 4, st));
+    GLC_TRY(hipMemsetAsync(s.d_max_cnt + RD_REFINE_LIVE, 0, 4, st));
     hipLaunchKernelGGL(k_refine_counts, dim3((nblk + 255) / 256), dim3(256), 0, st, cnt, s.rl_flag, s.rl_cnt, nblk,
-                       s.d_max_cnt + 3);
-    GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 3, s.d_max_cnt + 3, 4, hipMemcpyDeviceToHost, st));
-    GLC_TRY(hipStreamSynchronize(st));                         // one more host round trip per refinement round
+                       s.d_max_cnt + RD_REFINE_LIVE);
+    const uint32_t *hw;
+    GLC_TRY(sa_read(st, s, hw, HW_REFINE_LIVE, s.d_max_cnt + RD_REFINE_LIVE, 1, true));   // one more host round trip per refinement round
     (void)live_total;
-    const uint32_t flagged_live = s.h_max_cnt[3];
+    const uint32_t flagged_live = hw[0];
     if (flagged_live == 0) { uint64_t *x = cur; cur = alt; alt = x; return hipSuccess; }   // every group was local
     // npass is odd: the radix sort leaves its result in what is `alt` now -- where the tile-local kernel wrote
     return radix_sort(st, cur, alt, s.rl_cnt, 0, pp, tiles, nblk, s, (double)flagged_live);
 }
 
-// the general sorter; cnt0 (optional) = per-block element counts: n for the blocks to sort, 0 for the others
-// resume_depth != 0: s.keyA already holds, for the blocks of cnt0, the words [group : 44 | suffix : 20] of an order that is
-// exact for the first resume_depth symbols (k_grp_keys): no sort from the text, prefix doubling from that depth on
-static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                                   SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, int *rounds_out,
-                                   const uint32_t *cnt0, uint32_t nsorted, uint32_t resume_depth = 0)
+// the general sorter (cnt0, nsorted, resume_depth: glc_internal.h)
+hipError_t sa_build_general(const SortCall &c, SaScratch &s, const uint32_t *cnt0, uint32_t nsorted, uint32_t resume_depth)
 {
+    const hipStream_t st = c.st;
+    const uint8_t *const text = c.text;
+    const size_t text_stride = c.text_stride;
+    const uint32_t n = c.n, nblk = c.nblk;                     // (the outputs, c.bwt_out / c.d_index, are k_sa_rank1's alone)
     GLC_TRY(sa_general_reserve(s, false));
     uint32_t tiles = (n + SA_TILE - 1) / SA_TILE;
     uint64_t *cur = s.keyA, *alt = s.keyB;
     double live_total = (double)n * nsorted;
-    GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, 24, st));          // [2] doubles as the device error word of the sort, [4..5] count chain groups
+    GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, RD_WORDS * 4, st));   // (RD_ERROR is the device error word of the sorts too; the chain tallies count from here)
     if (!resume_depth) {   // 41 key bits at [20, 61): 8+8+8+8+9
         PassPlan pp = {5, {VAL_BITS, VAL_BITS + 8, VAL_BITS + 16, VAL_BITS + 24, VAL_BITS + 32}, {8, 8, 8, 8, 9}};
         const TextSrc src{text, text_stride, n};               // pass 0 and the histograms read the text itself
@@ -1307,7 +1321,7 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
     }
     for (;;) {
         dim3 g(tiles, nblk);
-        GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, 8, st));
+        GLC_TRY(hipMemsetAsync(s.d_max_cnt, 0, 8, st));      // RD_MAX, RD_SUM
         hipLaunchKernelGGL(k_rank_pre, g, dim3(SA_THREADS), 0, st, cur, cnt_cur, live, (unsigned long long *)s.tile_state,
                            s.nmax, s.max_tiles);
         hipLaunchKernelGGL(k_rank_scan, dim3(nblk), dim3(256), 0, st, (unsigned long long *)s.tile_state, cnt_cur, live,
@@ -1315,25 +1329,24 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
         if (!pos_cur)
             hipLaunchKernelGGL(k_sa_rank1<true>, g, dim3(SA_THREADS), 0, st, cur, pos_cur, cnt_cur, live,
                                (unsigned long long *)s.tile_state, s.isa, s.sa, alt, pos_next, hd_next, cnt_next,
-                               s.d_max_cnt, s.nmax, s.max_tiles, mode, text, text_stride, n, depth, bwt_out, bwt_stride,
-                               d_index, s.d_max_cnt + 2);
+                               s.d_max_cnt, s.nmax, s.max_tiles, mode, text, text_stride, n, depth, c.bwt_out, c.bwt_stride,
+                               c.d_index, s.d_max_cnt + RD_ERROR);
         else
             hipLaunchKernelGGL(k_sa_rank1<false>, g, dim3(SA_THREADS), 0, st, cur, pos_cur, cnt_cur, live,
                                (unsigned long long *)s.tile_state, s.isa, s.sa, alt, pos_next, hd_next, cnt_next,
-                               s.d_max_cnt, s.nmax, s.max_tiles, mode, text, text_stride, n, depth, bwt_out, bwt_stride,
-                               d_index, s.d_max_cnt + 2);
+                               s.d_max_cnt, s.nmax, s.max_tiles, mode, text, text_stride, n, depth, c.bwt_out, c.bwt_stride,
+                               c.d_index, s.d_max_cnt + RD_ERROR);
         GLC_TRY(hipGetLastError());
-        // (hc[4..5]: the chain tallies of every round so far -- candidates, taken -- ride along on the round's one readback)
-        uint32_t *hc = s.h_max_cnt + 8;
-        GLC_TRY(hipMemcpyAsync(hc, s.d_max_cnt, 24, hipMemcpyDeviceToHost, st));
-        GLC_TRY(hipStreamSynchronize(st));
+        // (the chain tallies of every round so far -- candidates, taken -- ride along on the round's one readback)
+        const uint32_t *hc;
+        GLC_TRY(sa_read(st, s, hc, HW_ROUND, s.d_max_cnt, RD_WORDS, true));
         rounds++;
-        const uint32_t maxc = hc[0];
-        live_total = (double)hc[1];
-        if (hc[2]) return hipErrorUnknown;                        // a look-back spin hit its bound
+        const uint32_t maxc = hc[RD_MAX];
+        live_total = (double)hc[RD_SUM];
+        if (hc[RD_ERROR]) return hipErrorUnknown;                 // a look-back spin hit its bound
         if (maxc == 0) {
-            s.last_chains[0] += hc[5];
-            s.last_chains[1] += hc[4] - hc[5];
+            s.stats.chains[0] += hc[RD_CHAIN_TAKEN];
+            s.stats.chains[1] += hc[RD_CHAIN_CAND] - hc[RD_CHAIN_TAKEN];
             break;
         }
         if (depth >= 2u * n + 16u) return hipErrorUnknown;        // cannot happen: depth >= n resolves everything
@@ -1382,13 +1395,13 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
                 dim3 cg(fill_blocks, nblk), ct(SA_THREADS);
                 hipLaunchKernelGGL(k_chain_init, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax);
                 hipLaunchKernelGGL(k_chain_minmax, cg, ct, 0, st, cur, cnt_cur, rec, s.nmax);
-                hipLaunchKernelGGL(k_chain_decide, cg, ct, 0, st, cur, pos_cur, cnt_cur, rec, s.hdA, s.nmax, s.d_max_cnt + 4);
+                hipLaunchKernelGGL(k_chain_decide, cg, ct, 0, st, cur, pos_cur, cnt_cur, rec, s.hdA, s.nmax, s.d_max_cnt + RD_CHAIN_CAND);
                 // (the verification's cache, n / 16 halfwords at the head of every block's part of pos_next -- which the NEXT rank pass writes)
                 GLC_TRY(hipMemset2DAsync(pos_next, (size_t)s.nmax * 4, 0, ((size_t)n / 16 + 1) * 2, nblk, st));
                 hipLaunchKernelGGL(k_chain_verify, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax, text, text_stride,
                                    reinterpret_cast<uint16_t *>(pos_next));
                 hipLaunchKernelGGL(k_chain_dir, cg, ct, 0, st, cur, cnt_cur, rec, s.hdA, s.nmax, text, text_stride, n, depth,
-                                   s.d_max_cnt + 4);
+                                   s.d_max_cnt + RD_CHAIN_CAND);
             }
             hipLaunchKernelGGL(k_sa_fill_rank2, dim3(fill_blocks, nblk), dim3(SA_THREADS), 0, st, cur, cnt_cur, s.isa,
                                n, depth, s.nmax, rec, chains ? s.hdA : (const uint32_t *)nullptr);
@@ -1398,208 +1411,7 @@ static hipError_t sa_build_general(hipStream_t st, const uint8_t *text, size_t t
             depth *= 2;
         }
     }
-    if (rounds_out) *rounds_out = rounds;
     return hipSuccess;
-}
-
-// Two-phase form, so that a caller can queue the stages that FOLLOW the sort before the host waits for the sorter's
-// one readback (cudpp_api.cpp queues MTF + Huffman speculatively: the GPU never idles behind the wait, and the
-// rare batch with flagged blocks re-runs them):
-//   sa_build_begin   enqueues the bucket sorter and the readback of the flagged-block count (an event marks it);
-//                    with s.sorter != 0 it runs the whole general sort instead (which blocks per round).
-//   sa_build_finish  waits for that event only; if blocks were flagged, enqueues the general sorter for them.
-//                    *nflagged > 0 tells the caller that bwt_out / d_index of those blocks were rewritten.
-hipError_t sa_build_begin(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                          SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index)
-{
-    if (n == 0 || n > s.nmax || n > MAX_BLOCK_ELEMS || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
-    s.last_flagged = nblk;
-    s.last_general = nblk;
-    s.last_chains[0] = s.last_chains[1] = 0;
-    s.pending = false;
-    if (s.sorter == 1 || s.sorter == 2) {
-        const bool isa = s.force_isa;
-        s.force_isa = isa || s.sorter == 2;
-        const hipError_t e = sa_build_general(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, nullptr,
-                                              nullptr, nblk);
-        s.force_isa = isa;
-        return e;
-    }
-    // bucket sorter first; the suffix array itself is only written when it is the result asked for
-    if (!bwt_out) GLC_TRY(sa_general_reserve(s, true));
-    s.skip_tier1 = sa_skips_tier1(s, nblk);                  // the caller knows its data is text-like (sorter 4), or the plan's last calls say so
-    GLC_TRY(fs_build(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, bwt_out ? nullptr : s.sa));
-    // (the flagged-block count is in s.h_max_cnt[4] when the pass's last kernel is through: it writes it there itself --
-    //  k_fs_finish / k_fs_ties -- where a copy command behind the pass was one more ~5 us link in a single call's chain)
-    if (!s.ev_flag) GLC_TRY(hipEventCreateWithFlags(&s.ev_flag, hipEventDisableTiming));
-    GLC_TRY(hipEventRecord(s.ev_flag, st));
-    s.pending = true;
-    return hipSuccess;
-}
-
-static hipError_t sa_build_finish_tiers(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                                        SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *nflagged);
-
-hipError_t sa_build_finish(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                           SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *nflagged)
-{
-    s.partial_used = false;
-    const hipError_t e = sa_build_finish_tiers(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, nflagged);
-    // whatever the tiers did, the side stream's stages (if any were queued) are joined into st here
-    if (s.partial_used) { const hipError_t j = hipStreamWaitEvent(st, s.ev_join, 0); if (e == hipSuccess && j != hipSuccess) return j; }
-    return e;
-}
-
-static hipError_t sa_build_finish_tiers(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                                        SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *nflagged)
-{
-    if (nflagged) *nflagged = 0;
-    if (!s.pending) return hipSuccess;                       // general sorter only: nothing was deferred
-    s.pending = false;
-    GLC_TRY(hipEventSynchronize(s.ev_flag));
-    uint32_t nflag = s.h_max_cnt[4];
-    // the streak of calls whose every block the probe called text-like (k_fs_finish counts the others, in skipped calls too)
-    s.last_skipped = s.skip_tier1;
-    s.textlike_streak = (nflag == nblk && s.h_max_cnt[5] == 0) ? (s.textlike_streak < 1000u ? s.textlike_streak + 1 : 1000u) : 0u;
-    s.last_flagged = nflag;
-    s.last_general = 0;
-    s.last_retried = 0;
-    s.last_resumed = 0;
-    if (nflag == 0) return hipSuccess;
-    if (nflagged) *nflagged = nflag;
-    if (s.sorter != 3) {
-        // second tier: string sample sort of the flagged blocks; what it gives up on (very deep repeats) is counted again
-        GLC_TRY(ss_build(st, text, text_stride, n, nflag, s, bwt_out, bwt_stride, d_index, bwt_out ? nullptr : s.sa));
-        GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 5, s.fs_nflag + 1, 4, hipMemcpyDeviceToHost, st));
-        GLC_TRY(hipEventRecord(s.ev_flag, st));
-        GLC_TRY(hipEventSynchronize(s.ev_flag));
-        uint32_t left = s.h_max_cnt[5];
-        if (left) {
-            // some blocks were given up on.  Those whose only trouble was a bucket past its slot get ONE more attempt with
-            // other samples (a bucket of 4033-4200 words where 4032 fit: ~1 % of log-style blocks; the general sorter
-            // costs ten times the sample sorter, and its rounds hold the host)
-            if (s.stage_partial) GLC_TRY(ss_split_masks(st, nblk, s));
-            GLC_TRY(ss_retry_prepare(st, nflag, s));
-            GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 6, s.fs_nflag + 2, 4, hipMemcpyDeviceToHost, st));
-            GLC_TRY(hipEventRecord(s.ev_flag, st));
-            GLC_TRY(hipEventSynchronize(s.ev_flag));
-            const uint32_t again = s.h_max_cnt[6];
-            s.last_retried = again;
-            if (again && s.stage_partial && left < nflag) {
-                // the stages behind the sort for the blocks the first attempt finished, on a side stream BESIDE the second attempt
-                // (ss_mask was written before ss_retry_prepare touched anything: see above)
-                if (!s.aux) {
-                    // (lowest priority: the side stream's kernels fill the chip, the second attempt's small launches on `st` are a
-                    //  chain of latencies -- with equal priorities its bucketing pass took 614 us beside k_mtf_encode instead of 27)
-                    int least = 0, greatest = 0;
-                    (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-                    GLC_TRY(hipStreamCreateWithPriority(&s.aux, hipStreamNonBlocking, least));
-                    GLC_TRY(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
-                    GLC_TRY(hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
-                }
-                GLC_TRY(hipEventRecord(s.ev_fork, st));
-                GLC_TRY(hipStreamWaitEvent(s.aux, s.ev_fork, 0));
-                GLC_TRY(s.stage_partial(s.aux, s.ss_mask[0]));
-                GLC_TRY(hipEventRecord(s.ev_join, s.aux));
-                s.partial_used = true;
-            }
-            if (again) {
-                s.h_max_cnt[7] = left - again;                 // the others stay given up on; the second attempt adds its own
-                GLC_TRY(hipMemcpyAsync(s.fs_nflag + 1, s.h_max_cnt + 7, 4, hipMemcpyHostToDevice, st));
-                GLC_TRY(ss_build(st, text, text_stride, n, again, s, bwt_out, bwt_stride, d_index, bwt_out ? nullptr : s.sa, 1));
-                GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 5, s.fs_nflag + 1, 4, hipMemcpyDeviceToHost, st));
-                GLC_TRY(hipEventRecord(s.ev_flag, st));
-                GLC_TRY(hipEventSynchronize(s.ev_flag));
-                left = s.h_max_cnt[5];
-            }
-        }
-        s.last_general = left;                                 // what the sample sorter (both attempts) gave up on
-        s.last_resumed = 0;
-        s.last_periodic = 0;
-        if (left && s.periodic && bwt_out && d_index && n >= 16 * PER_PMAX && s.nmax >= PER_NU) {
-            // Blocks that are ONE periodic stretch (a page repeated, a short pattern, one byte up to a different last one):
-            // every suffix ties with the one a period further on for nearly the whole block -- ~18 doubling rounds over a
-            // million live suffixes.  Their suffix array has a closed form over the sorted rotations of the period and the
-            // few suffixes around the break (bwt_periodic.hip); only those -- a text of <= 7 p + 2 bytes per block -- are
-            // sorted, by the general sorter, whatever the block's size.
-            GLC_TRY(per_reserve(s));
-            GLC_TRY(per_detect(st, text, text_stride, n, nflag, s));
-            GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 6, s.per_count, 8, hipMemcpyDeviceToHost, st));   // {blocks taken, longest text of representatives}
-            GLC_TRY(hipEventRecord(s.ev_flag, st));
-            GLC_TRY(hipEventSynchronize(s.ev_flag));
-            const uint32_t nper = s.h_max_cnt[6] < PER_TAKE ? s.h_max_cnt[6] : PER_TAKE;   // (k_per_detect takes no more than its scratch holds)
-            if (nper) {
-                // (the longest text of representatives among the taken blocks -- they are sorted as one batch of equal length -- comes
-                //  with the count: round 5 copied every block's info to the host and waited a second time for it: ADVICE r5)
-                uint32_t nu = s.h_max_cnt[7] < 64 ? 64 : s.h_max_cnt[7];
-                nu = (nu + 15u) & ~15u;
-                if (nu > PER_NU) nu = PER_NU;
-                GLC_TRY(per_text(st, text, text_stride, n, nper, nu, s));
-                GLC_TRY(sa_build_general(st, s.per_text, PER_NU, nu, nper, s, nullptr, 0, nullptr, nullptr, nullptr, nper));
-                GLC_TRY(per_expand(st, text, text_stride, n, nper, nu, s, bwt_out, bwt_stride, d_index));
-                GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 6, s.per_count + 2, 4, hipMemcpyDeviceToHost, st));
-                GLC_TRY(hipEventRecord(s.ev_flag, st));
-                GLC_TRY(hipEventSynchronize(s.ev_flag));
-                const uint32_t done = s.h_max_cnt[6];
-                s.last_periodic = done;
-                left -= done < left ? done : left;
-                s.h_max_cnt[7] = left;                         // the device-side count of blocks still given up on follows
-                GLC_TRY(hipMemcpyAsync(s.fs_nflag + 1, s.h_max_cnt + 7, 4, hipMemcpyHostToDevice, st));
-            }
-        }
-        if (left && s.resume_min) {
-            // Blocks whose only trouble was a repeat deeper than the cap (zero pages, a duplicated region, long periodic
-            // stretches inside otherwise ordinary data): the sample sorter once more, in its TOLERANT form and writing the
-            // suffix array -- everything it can order it orders, suffixes that agree in more than the cap stay as they come
-            // -- then prefix doubling from that depth on, over the groups of rows that still share the cap (a few thousand
-            // suffixes of such a block for ~11 rounds, where the general sorter from scratch takes a million through ~20).
-            // counted first, without touching anything: below resume_min the blocks go on as they are (their flags and fills
-            // stay what glcPlanDebugSortFlags / BucketFill report)
-            GLC_TRY(ss_retry_prepare(st, nflag, s, 2, true));
-            GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 6, s.fs_nflag + 2, 4, hipMemcpyDeviceToHost, st));
-            GLC_TRY(hipEventRecord(s.ev_flag, st));
-            GLC_TRY(hipEventSynchronize(s.ev_flag));
-            const uint32_t deep2 = s.h_max_cnt[6];
-            // (a few blocks: the extra pass and its launches cost what the shorter doubling saves -- 2.6 against 2.2-2.7 ms for
-            //  one block, 3.5 against 4.4 for eight)
-            if (deep2 >= s.resume_min) {
-                GLC_TRY(ss_retry_prepare(st, nflag, s, 2));    // listed, flags and fills cleared for the tolerant pass
-                GLC_TRY(sa_general_reserve(s, false));
-                s.h_max_cnt[7] = left - deep2;                 // the others stay given up on; this attempt adds its own
-                GLC_TRY(hipMemcpyAsync(s.fs_nflag + 1, s.h_max_cnt + 7, 4, hipMemcpyHostToDevice, st));
-                GLC_TRY(ss_build(st, text, text_stride, n, deep2, s, nullptr, 0, nullptr, s.sa, 2));
-                GLC_TRY(hipMemcpyAsync(s.h_max_cnt + 5, s.fs_nflag + 1, 4, hipMemcpyDeviceToHost, st));
-                const uint32_t *list3 = s.ss_list + 2 * (size_t)s.rows;
-                const uint32_t gt = (n + GRP_NT - 1) / GRP_NT, max_gt = (s.nmax + GRP_NT - 1) / GRP_NT;
-                GLC_TRY(hipMemsetAsync(s.ss_cnt2, 0, (size_t)s.rows * 4, st));
-                hipLaunchKernelGGL(k_grp_flags, dim3(gt, deep2), dim3(GRP_NT), 0, st, text, text_stride, n, s.sa, s.nmax, list3,
-                                   s.ss_flag, s.ss_gtile, max_gt, SS_TOL_CAP);
-                hipLaunchKernelGGL(k_grp_scan, dim3(deep2), dim3(1024), 0, st, s.ss_gtile, max_gt, gt, list3, s.ss_flag);
-                hipLaunchKernelGGL(k_grp_keys, dim3(gt, deep2), dim3(GRP_NT), 0, st, n, s.sa, s.nmax, list3, s.ss_flag,
-                                   s.ss_gtile, max_gt, s.keyA, s.ss_cnt2);
-                GLC_TRY(hipEventRecord(s.ev_flag, st));
-                GLC_TRY(hipEventSynchronize(s.ev_flag));
-                const uint32_t left2 = s.h_max_cnt[5];          // = left - deep2 + what the tolerant form gave up on (a bucket past its slot)
-                const uint32_t resumed = left - left2;
-                if (resumed)
-                    GLC_TRY(sa_build_general(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, nullptr, s.ss_cnt2,
-                                             resumed, SS_TOL_CAP));
-                s.last_resumed = resumed;
-                left = left2;
-            }
-        }
-        nflag = left;
-        if (nflag == 0) return hipSuccess;
-    } else s.last_general = nflag;
-    return sa_build_general(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, nullptr, s.fs_lcnt, nflag);
-}
-
-hipError_t sa_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                    SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, int *rounds_out)
-{
-    if (rounds_out) *rounds_out = 0;
-    GLC_TRY(sa_build_begin(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index));
-    return sa_build_finish(st, text, text_stride, n, nblk, s, bwt_out, bwt_stride, d_index, nullptr);
 }
 
 // per-block exclusive scan of [tile][512] histograms (used by the decoder's LF construction)

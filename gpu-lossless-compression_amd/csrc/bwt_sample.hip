@@ -1695,9 +1695,15 @@ __global__ void k_ss_split_masks(const uint32_t *__restrict__ redo, const uint32
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-hipError_t ss_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nflag, SaScratch &s,
-                    uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *sa_out, uint32_t attempt)
+hipError_t ss_build(const SortCall &c, SaScratch &s, uint32_t nflag, uint32_t attempt)
 {
+    const hipStream_t st = c.st;
+    const uint8_t *const text = c.text;
+    const size_t text_stride = c.text_stride, bwt_stride = c.bwt_stride;
+    const uint32_t n = c.n;
+    uint8_t *const bwt_out = c.bwt_out;
+    int *const d_index = c.d_index;
+    uint32_t *const sa_out = c.sa_out(s);
     const uint32_t nbl = fs_bucket_log2(n), nb = 1u << nbl;
     // attempt 0: the blocks k_fs_finish listed in ss_list; attempt 1: the ones k_ss_retry_list listed behind them (a bucket
     // past its slot: other samples); attempt 2: the ones listed behind those (a repeat deeper than the cap), in the TOLERANT
@@ -1709,7 +1715,7 @@ hipError_t ss_build(hipStream_t st, const uint8_t *text, size_t text_stride, uin
     if (attempt == 0) {
         GLC_TRY(hipMemsetAsync(s.ss_flag, 0, (size_t)s.rows * 4, st));
         GLC_TRY(hipMemsetAsync(s.fs_fill, 0, (size_t)s.rows * FS_MAXNB * 4, st));
-        GLC_TRY(per_probe(st, text, text_stride, n, nflag, s));   // (blocks that are mostly one periodic stretch: not this sorter's)
+        GLC_TRY(per_probe(c, s, nflag));   // (blocks that are mostly one periodic stretch: not this sorter's)
     }
     if (tol)
         hipLaunchKernelGGL(k_ss_sample<true>, dim3(nflag), dim3(SSA_NT), 0, st, text, text_stride, n, nbl, s.fs_tab, list,

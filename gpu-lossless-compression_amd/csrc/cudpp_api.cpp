@@ -158,6 +158,28 @@ struct StageTimer {
     void done() { if (p->timing) p->ev_valid = true; }
 };
 
+SaScratch *sa_of(PlanBase *p)
+{
+    switch (p->config.algorithm) {
+    case CUDPP_COMPRESS: return &static_cast<CompressPlan *>(p)->sa;
+    case CUDPP_BWT: return &static_cast<BwtPlan *>(p)->sa;
+    case CUDPP_SA: return &static_cast<SaPlan *>(p)->sa;
+    default: return nullptr;
+    }
+}
+
+// the stats getters and glcPlanSetChains: handle, output pointer and plan type checked in one place (a null output is
+// reported as an invalid handle, as it always was), then f on the plan's sorter scratch
+template <class F> CUDPPResult with_sorter(CUDPPHandle planHandle, bool has_out, F f)
+{
+    PlanBase *p = plan_from<PlanBase>(planHandle);
+    if (!p || planHandle == CUDPP_INVALID_HANDLE || !has_out) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = sa_of(p);
+    if (!s) return CUDPP_ERROR_INVALID_PLAN;
+    f(*s);
+    return CUDPP_SUCCESS;
+}
+
 } // namespace
 
 extern "C" {
@@ -305,22 +327,28 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
     // the next call.  In the rare batch with flagged blocks they run again on the corrected BWT.
     tm.mark(0);
     p->sa.parity = k;
-    e = sa_build_begin(st, d_uncompressed, n, n, nb, p->sa, bwt, p->n, d_bwtIndex);
+    const SortCall sort{st, d_uncompressed, n, n, nb, bwt, p->n, d_bwtIndex};
+    e = sa_build_begin(sort, p->sa);
     tm.mark(1);
+    // MTF + Huffman of the blocks of `only` (all if null) on `stream`, behind whatever error `err` already holds
+    auto run_stages = [&](hipStream_t stream, hipError_t err, const uint32_t *redo_flag, const uint32_t *only, bool skewed) {
+        if (err == hipSuccess) err = mtf_forward(stream, bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, p->huff.sub_hist, only, skewed);
+        if (p->timing) (void)hipEventRecord(p->ev[2], stream);
+        // (compact layout: a block has no slot of its own to overflow -- the array's capacity is checked with the offsets)
+        if (err == hipSuccess) err = huff_build(stream, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
+                                                compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status,
+                                                redo_flag, only);
+        if (err == hipSuccess && !compact) err = huff_pack(stream, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride,
+                                                           d_compressed, compressedStrideWords, only);
+        return err;
+    };
     auto after_sort = [&](const uint32_t *redo_flag, const uint32_t *only, bool skewed) {
         if (p->pipelined) {
             (void)hipEventRecord(p->ev_sorted[k], st);
             (void)hipStreamWaitEvent(s2, p->ev_sorted[k], 0);
             if (p->timing) (void)hipEventRecord(p->ev_s2, s2);
         }
-        if (e == hipSuccess) e = mtf_forward(s2, bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, p->huff.sub_hist, only, skewed);
-        if (p->timing) (void)hipEventRecord(p->ev[2], s2);
-        // (compact layout: a block has no slot of its own to overflow -- the array's capacity is checked with the offsets)
-        if (e == hipSuccess) e = huff_build(s2, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                                            compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status,
-                                            redo_flag, only);
-        if (e == hipSuccess && !compact) e = huff_pack(s2, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride,
-                                                       d_compressed, compressedStrideWords, only);
+        e = run_stages(s2, e, redo_flag, only, skewed);
         if (p->timing) (void)hipEventRecord(p->ev[3], s2);
     };
     // Blocks the bucket sorter has given up on (flagged up front as text-like, or after its attempt) are skipped by this
@@ -332,15 +360,8 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
     // (not in the pipelined mode, whose stages have a stream of their own already, nor under the stage timer, whose events sit on
     //  the plan's stream: the blocks the sample sorter's first attempt finished get their MTF + Huffman beside its second attempt)
     if (speculate && tiers && !p->pipelined && !p->timing)
-        p->sa.stage_partial = [&](hipStream_t aux, const uint32_t *only) -> hipError_t {
-            hipError_t e2 = mtf_forward(aux, bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, p->huff.sub_hist, only, true);
-            if (e2 == hipSuccess) e2 = huff_build(aux, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                                                  compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status, nullptr, only);
-            if (e2 == hipSuccess && !compact) e2 = huff_pack(aux, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride, d_compressed,
-                                                             compressedStrideWords, only);
-            return e2;
-        };
-    if (e == hipSuccess) e = sa_build_finish(st, d_uncompressed, n, n, nb, p->sa, bwt, p->n, d_bwtIndex, &nflag);
+        p->sa.stage_partial = [&](hipStream_t aux, const uint32_t *only) { return run_stages(aux, hipSuccess, nullptr, only, true); };
+    if (e == hipSuccess) e = sa_build_finish(sort, p->sa, &nflag);
     p->sa.stage_partial = nullptr;                             // (it refers to this call's arguments)
     if (e == hipSuccess && (nflag || !speculate)) {
         // sa_build_finish has queued the other sorters for the flagged blocks on st; this pass is ordered after the
@@ -429,8 +450,7 @@ CUDPPResult glcBwtBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsig
     if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const uint32_t n = (uint32_t)numElements, nb = (uint32_t)numBlocks;
-    hipError_t e = sa_build(p->stream, d_in, n, n, nb, p->sa, d_out, n, d_index);
-    return hip_result(e);
+    return hip_result(sa_build(SortCall{p->stream, d_in, n, n, nb, d_out, n, d_index}, p->sa));
 }
 
 CUDPPResult glcMtfBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsigned char *d_out,
@@ -543,7 +563,7 @@ CUDPPResult cudppSuffixArray(CUDPPHandle planHandle, unsigned char *d_str, unsig
     if (p->config.datatype != CUDPP_UCHAR) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     if (numElements == 0 || numElements > p->n) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const uint32_t n = (uint32_t)numElements;
-    hipError_t e = sa_build(p->stream, d_str, n, n, 1, p->sa);
+    hipError_t e = sa_build(SortCall{p->stream, d_str, n, n, 1, nullptr, 0, nullptr}, p->sa);
     if (e == hipSuccess) e = sa_export(p->stream, p->sa.sa, n, d_keys_sa);
     return hip_result(e);
 }
@@ -592,16 +612,6 @@ CUDPPResult glcPlanSynchronize(CUDPPHandle planHandle)
     return *p->h_status ? CUDPP_ERROR_UNKNOWN : CUDPP_SUCCESS;
 }
 
-static SaScratch *sa_of(PlanBase *p)
-{
-    switch (p->config.algorithm) {
-    case CUDPP_COMPRESS: return &static_cast<CompressPlan *>(p)->sa;
-    case CUDPP_BWT: return &static_cast<BwtPlan *>(p)->sa;
-    case CUDPP_SA: return &static_cast<SaPlan *>(p)->sa;
-    default: return nullptr;
-    }
-}
-
 CUDPPResult glcPlanEnableTiming(CUDPPHandle planHandle, int enable)
 {
     PlanBase *p = plan_from<PlanBase>(planHandle);
@@ -633,95 +643,55 @@ CUDPPResult glcPlanSetSorter(CUDPPHandle planHandle, int mode)
 
 CUDPPResult glcPlanLastSortStats(CUDPPHandle planHandle, unsigned int *flaggedBlocks)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !flaggedBlocks) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    *flaggedBlocks = s->last_flagged;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, flaggedBlocks, [&](SaScratch &s) { *flaggedBlocks = s.stats.flagged; });
 }
 
 CUDPPResult glcPlanLastSortStatsEx(CUDPPHandle planHandle, unsigned int *out2)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out2) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out2[0] = s->last_flagged;
-    out2[1] = s->last_general;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, out2, [&](SaScratch &s) { out2[0] = s.stats.flagged; out2[1] = s.stats.general; });
 }
 
-// out[0] = blocks of the plan's last call that the sample sorter finished only in its second attempt (other samples)
+// out[0] = blocks of the plan's last call that the sample sorter took in a second attempt (other samples)
 CUDPPResult glcPlanLastSortRetries(CUDPPHandle planHandle, unsigned int *out)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out[0] = s->last_retried;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, out, [&](SaScratch &s) { out[0] = s.stats.retried; });
 }
 
 // out[0] = 1 if the plan's last call skipped the bucket sorter's attempt (sorter mode 4, or a small call behind a streak of calls
 // whose every block the text-likeness probe flagged), out[1] = the streak
 CUDPPResult glcPlanLastSortSkipped(CUDPPHandle planHandle, unsigned int *out2)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out2) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out2[0] = s->last_skipped ? 1u : 0u;
-    out2[1] = s->textlike_streak;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, out2, [&](SaScratch &s) { out2[0] = s.stats.skipped ? 1u : 0u; out2[1] = s.textlike_streak; });
+}
+
+// out[0] = blocks of the plan's last call that the periodic tier finished
+CUDPPResult glcPlanLastSortPeriodic(CUDPPHandle planHandle, unsigned int *out)
+{
+    return with_sorter(planHandle, out, [&](SaScratch &s) { out[0] = s.stats.periodic; });
 }
 
 // out[0] = blocks of the plan's last call whose doubling rounds resumed from the sample sorter's tolerant form
-CUDPPResult glcPlanLastSortPeriodic(CUDPPHandle planHandle, unsigned int *out)
+CUDPPResult glcPlanLastSortResumed(CUDPPHandle planHandle, unsigned int *out)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out[0] = s->last_periodic;
-    return CUDPP_SUCCESS;
-}
-
-// chain groups of the doubling rounds: the plan's attempt schedule (minLive < 0 / roundMask == ~0u restore the defaults)
-CUDPPResult glcPlanSetChains(CUDPPHandle planHandle, long minLive, unsigned int roundMask)
-{
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    long dmin;
-    uint32_t dmask;
-    sa_chain_defaults(&dmin, &dmask);
-    s->chain_min = minLive < 0 ? dmin : minLive;
-    s->chain_rounds = roundMask == ~0u ? dmask : roundMask;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, out, [&](SaScratch &s) { out[0] = s.stats.resumed; });
 }
 
 // out2[0] = chain groups the plan's last call ordered by the rule, out2[1] = candidates the verification or the direction refused
 CUDPPResult glcPlanLastSortChains(CUDPPHandle planHandle, unsigned int *out2)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out2) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out2[0] = s->last_chains[0];
-    out2[1] = s->last_chains[1];
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, out2, [&](SaScratch &s) { out2[0] = s.stats.chains[0]; out2[1] = s.stats.chains[1]; });
 }
 
-CUDPPResult glcPlanLastSortResumed(CUDPPHandle planHandle, unsigned int *out)
+// chain groups of the doubling rounds: the plan's attempt schedule (minLive < 0 / roundMask == ~0u restore the defaults)
+CUDPPResult glcPlanSetChains(CUDPPHandle planHandle, long minLive, unsigned int roundMask)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
-    if (!s) return CUDPP_ERROR_INVALID_PLAN;
-    out[0] = s->last_resumed;
-    return CUDPP_SUCCESS;
+    return with_sorter(planHandle, true, [&](SaScratch &s) {
+        long dmin;
+        uint32_t dmask;
+        sa_chain_defaults(&dmin, &dmask);
+        s.chain_min = minLive < 0 ? dmin : minLive;
+        s.chain_rounds = roundMask == ~0u ? dmask : roundMask;
+    });
 }
 
 // diagnostic: the give-up flags of the plan's last sort, per block (waits for the plan's stream).  out_fs[b]: bucket sorter

@@ -155,6 +155,37 @@ inline int global_prof_get(KernelProf &pr, int nslot, int index, char *name, siz
 // ---------------------------------------------------------------------------
 // suffix array scratch: everything for `rows` blocks of up to nmax elements
 // ---------------------------------------------------------------------------
+// SaScratch::d_max_cnt, the general sorter's device counters, and the copy of them a doubling round reads back
+enum RoundWord : uint32_t { RD_MAX = 0, RD_SUM,              // most and sum of the blocks' unresolved counts
+                            RD_ERROR,                        // a look-back spin hit its bound
+                            RD_REFINE_LIVE,                  // live suffixes of the blocks a refinement's tile-local sort could not finish
+                            RD_CHAIN_CAND, RD_CHAIN_TAKEN,   // chain groups: candidates / ordered by the rule, every round so far
+                            RD_WORDS };
+// SaScratch::h_max_cnt, the pinned words: one name per meaning
+enum HostWord : uint32_t {
+    HW_ROUND = 0,                                // [RD_WORDS] a doubling round's copy of d_max_cnt
+    HW_REFINE_LIVE = HW_ROUND + RD_WORDS,        // refine_sort: d_max_cnt[RD_REFINE_LIVE]
+    HW_FLAGGED, HW_NOT_TEXTLIKE,                 // blocks the bucket sorter flagged / the probe did not call text-like: written by the pass's
+                                                 // last kernel itself (k_fs_finish, through one pointer: the two stay neighbours)
+    HW_GIVEN_UP,                                 // fs_nflag[1]: blocks the sample sorter has given up on so far
+    HW_LISTED,                                   // fs_nflag[2]: blocks ss_retry_prepare listed or counted (second attempt, tolerant form)
+    HW_PER_TAKEN, HW_PER_LONGEST,                // per_count[0 .. 1], one copy: blocks the periodic tier takes, bytes of their longest text of representatives
+    HW_PER_DONE,                                 // per_count[2]: blocks the periodic tier finished
+    HW_LEFT,                                     // host -> device: the staging word of sa_set_left
+    HW_WORDS };
+static_assert(HW_WORDS <= 16, "h_max_cnt is 16 words");
+
+// the plan's last sa_build, for the glcPlanLastSort* getters
+struct SortStats {
+    uint32_t flagged = 0;                        // blocks the bucket sorter gave up on (all of them where it made no attempt)
+    uint32_t retried = 0;                        // ... of which the sample sorter took in a second attempt (a bucket past its slot in the first)
+    uint32_t general = 0;                        // ... of which the sample sorter gave up on too
+    uint32_t periodic = 0;                       // ... of which the periodic tier finished
+    uint32_t resumed = 0;                        // ... of which the doubling rounds RESUMED from the sample sorter's tolerant form
+    uint32_t chains[2] = {0, 0};                 // chain groups ordered by the rule, candidates refused
+    bool     skipped = false;                    // the call skipped the bucket sorter's attempt
+};
+
 struct SaScratch {
     uint32_t  nmax = 0, rows = 0, max_tiles = 0, rs_tiles = 0;
     uint64_t *keyA = nullptr, *keyB = nullptr;   // [rows][nmax]
@@ -170,15 +201,14 @@ struct SaScratch {
     uint32_t *hdA = nullptr, *hdB = nullptr;     // [rows][nmax] SA slot of the group head of each unresolved entry
     uint32_t *cntA = nullptr, *cntB = nullptr;   // [rows] unresolved counts
     uint32_t *rl_flag = nullptr, *rl_cnt = nullptr;   // [rows] tile-local refinement: block needs the global sort / its count
-    uint32_t *d_max_cnt = nullptr;               // [6] max and sum of the unresolved counts, error word, refinement count, chain tallies
-    uint32_t *h_max_cnt = nullptr;               // pinned [16]: [0..7] the tiers' readbacks, [8..13] the doubling round's copy of d_max_cnt
+    uint32_t *d_max_cnt = nullptr;               // [RD_WORDS] the general sorter's counters, by RoundWord
+    uint32_t *h_max_cnt = nullptr;               // pinned [HW_WORDS]: what the host reads back (sa_read) or stages, by HostWord
     size_t    bytes = 0;
     bool      force_isa = false;                 // tests: skip text refinement, prefix doubling from round 1
     // chain groups of the doubling rounds (bwt_sa.hip k_chain_*): attempted in doubling round r where bit r of chain_rounds is
     // set and at least chain_min suffixes of the call are live (0: never); glcPlanSetChains, defaults from sa_chain_defaults
     long      chain_min = 16384;
     uint32_t  chain_rounds = 0x15;
-    uint32_t  last_chains[2] = {0, 0};           // the plan's last call: chain groups ordered by the rule, candidates refused
     // fast path (bwt_bucket.hip, bwt_sample.hip); its words live in keyA/keyB (one allocation, fs_kstride words per block)
     int       sorter = 0;                        // 0 = bucket sorter, then sample sorter, then general sorter for what each flags;
                                                  // 1 = general sorter only; 2 = general sorter, prefix doubling only;
@@ -194,17 +224,12 @@ struct SaScratch {
     uint32_t *fs_keep[2] = {nullptr, nullptr};   // [rows] 1 = the bucket sorter finished the block (the speculative stages' `only` mask)
     uint32_t *fs_dup = nullptr;                  // [rows] repeated 6-grams among the samples k_fs_hist looks at (text-likeness probe)
     uint32_t *fs_zero = nullptr;                 // [rows] bucket that holds the word of suffix 0 (k_fs_part2 -> k_fs_sort_bwt: the BWT index is looked for there only)
-    uint32_t  parity = 0;                        // set by the caller before sa_build_begin
     uint32_t *fs_nflag = nullptr;                // 32 bytes, cleared by k_fs_clear: [0] blocks flagged by the bucket sorter; [1] given up on by the sample sorter;
                                                  // [2] listed for its second attempt / the tolerant form; [3] ticket of k_fs_finish's workgroups; [4] blocks the probe
                                                  // did not call text-like; [5 .. 7] unused
     uint4    *fs_wl = nullptr;                   // [rows][fs_wl_cap] runs of equal codes: {index << 8 | bwt, first row, first entry, size}
     uint32_t *fs_wlcnt = nullptr;                // [rows] entries in use
     uint32_t  fs_wl_cap = 0;
-    uint32_t  last_flagged = 0;                  // blocks of the last sa_build the bucket sorter gave up on
-    uint32_t  last_retried = 0;                  // ... the sample sorter took in a second attempt (a bucket past its slot in the first)
-    uint32_t  last_general = 0;                  // ... of which the sample sorter gave up on too (general sorter)
-    uint32_t  last_resumed = 0;                  // ... of which the doubling rounds RESUMED from the sample sorter's tolerant form
     uint32_t *ss_gtile = nullptr;                // [rows][ceil(nmax / 256)] group heads per tile of rows (k_grp_*)
     uint32_t *ss_cnt2 = nullptr;                 // [rows] n for the blocks the resumed doubling works on, else 0
     // periodic tier: blocks every other tier gave up on that turn out to be ONE periodic stretch (allocated on first use)
@@ -214,18 +239,16 @@ struct SaScratch {
     uint32_t *per_count = nullptr;               // 16 bytes: [0] blocks taken, [1] bytes of the longest text of representatives, [2] blocks finished, [3] unused
     uint32_t *per_base = nullptr;                // [min(rows, PER_TAKE)][PER_NU + 1] first row of every representative
     uint8_t  *per_text = nullptr;                // [min(rows, PER_TAKE)][PER_NU] the texts of representatives
-    uint32_t  last_periodic = 0;                 // blocks of the last sa_build this tier finished
     uint32_t  resume_min = 2;                    // fewest blocks given up on for depth that are worth the tolerant pass (0: never; sorter modes 5 / 6).  4 until round 6;
                                                  // with chain groups and the tolerant cap at 64: 2 blocks 2.1-2.6 -> 1.6-2.1 ms per call, 3 blocks 2.4-2.9 -> 1.7-2.2; a lone
                                                  // block 1.8-2.3 against 1.6-2.7 (three kinds of four gain, log lines with runs lose: left as it was)
-    bool      skip_tier1 = false;                // sorter 4: no bucket-sorter attempt, every block goes to the sample sorter
+    // A call makes no bucket-sorter attempt (skip_tier1: every block goes to the sample sorter) under sorter 4
     // ... and, adaptively, for SMALL calls (sa_skips_tier1): the reference's callers hand over one block per call, and a text
     // block's call spent 0.13 of its 0.69 ms on the bucket sorter's fourteen launches that find the block flagged.  After
     // TEXT_STREAK calls in a row in which the probe called every block text-like, a call of up to TEXT_SKIP_MAX blocks goes
     // straight to the sample sorter; the first block the probe does not call text-like (it is evaluated in skipped calls too)
     // ends the streak.  A wrong guess costs time (that one call's blocks take the sample sorter), never correctness.
     uint32_t  textlike_streak = 0;
-    bool      last_skipped = false;              // the plan's last sa_build skipped the bucket sorter's attempt
     // second tier (bwt_sample.hip, string sample sort): the blocks the bucket sorter flagged
     uint32_t *ss_list = nullptr;                 // [3 rows] their block numbers; behind them the ones that get a second attempt; then the ones for the tolerant form
     uint64_t *ss_split = nullptr;                // [rows][FS_MAXNB] first suffix of every bucket as a word [code : 36 | index : 20 | 0 : 8]
@@ -234,7 +257,13 @@ struct SaScratch {
     uint2    *ss_long = nullptr;                 // [rows * FS_MAXNB * (SSL_PER_BUCKET + SSL_BIG_PER_BUCKET)] long bins of the sample sorter's first cut
     unsigned long long *ss_long_count = nullptr; // their number: small ones in the low half, big ones in the high half
     uint16_t *ss_cell = nullptr;                 // [rows][4098] first splitter of every cell of the code space
-    hipEvent_t ev_flag = nullptr;                // marks the readback of fs_nflag (sa_build_begin / sa_build_finish)
+    hipEvent_t ev_flag = nullptr;                // marks a readback: the bucket sorter's (sa_build_begin / sa_build_finish), then every sa_read of the tiers
+    // what the glcPlanLastSort* getters report of the plan's last call: assigned whole by sa_build_begin, the tiers only add to it
+    SortStats stats;
+    // per-call plumbing between sa_build_begin, sa_build_finish and their caller
+    uint32_t  parity = 0;                        // set by the caller before sa_build_begin
+    bool      skip_tier1 = false;                // this call makes no bucket-sorter attempt (sa_skips_tier1)
+    bool      pending = false;                   // sa_build_begin left the tiers to sa_build_finish
     // The sample sorter's SECOND attempt (a block in a few hundred, whose first samples left a bucket past its slot) is a chain
     // of small launches on one block -- 0.54 of a 256-text-block call's 11.3 ms with the chip idle.  A caller that has stages
     // behind the sort (cudpp_api.cpp: MTF + Huffman) sets stage_partial: sa_build_finish calls it ONCE, with a side stream
@@ -245,7 +274,6 @@ struct SaScratch {
     uint32_t *ss_mask[2] = {nullptr, nullptr};   // [rows] 1 = flagged block finished by the sample sorter's first attempt / n = still open then
     hipStream_t aux = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    bool      pending = false;
     KernelProf *prof = nullptr;                  // owned by the plan
 };
 
@@ -268,30 +296,64 @@ inline void sa_chain_defaults(long *min_live, uint32_t *round_mask)
 hipError_t sa_general_reserve(SaScratch &s, bool only_sa);
 void       sa_scratch_free(SaScratch &s);
 
-// Suffix arrays of `nblk` blocks of n bytes (block b at text + b*text_stride).
-// Result in s.sa[b*nmax ..].  Synchronises the stream once per doubling round.
-// If bwt_out != nullptr the BWT bytes (L[i] = SA[i]==0 ? T[n-1] : T[SA[i]-1]) and d_index[b] are
-// produced on the way (bwt_compute_final_kernel, compress_kernel.cuh:55-74) -- no separate gather.
-hipError_t sa_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                    SaScratch &s, uint8_t *bwt_out = nullptr, size_t bwt_stride = 0, int *d_index = nullptr,
-                    int *rounds_out = nullptr);
+// One call of the suffix sorter: `nblk` blocks of n bytes (block b at text + b * text_stride) on stream st.  With bwt_out
+// the BWT bytes (L[i] = SA[i]==0 ? T[n-1] : T[SA[i]-1]) and d_index[b] are produced on the way (bwt_compute_final_kernel,
+// compress_kernel.cuh:55-74) -- no separate gather; without it the suffix arrays themselves are the result, in s.sa[b * nmax ..].
+struct SortCall {
+    hipStream_t st; const uint8_t *text; size_t text_stride; uint32_t n, nblk; uint8_t *bwt_out; size_t bwt_stride; int *d_index;
+    uint32_t *sa_out(const SaScratch &s) const { return bwt_out ? nullptr : s.sa; }   // where a tier writes suffix-array rows
+};
 
-// two-phase form of sa_build (see bwt_sa.hip): stages that follow the sort can be queued between the two calls
-hipError_t sa_build_begin(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                          SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index);
-hipError_t sa_build_finish(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk,
-                           SaScratch &s, uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *nflagged);
+// Host readbacks: nwords device words to the pinned words from `slot` on, then the host waits -- for ev_flag, recorded behind
+// the copy, or (the general sorter's rounds, which also run where no bucket sorter created the event) for the whole stream.
+// sa_read_queue and sa_read_wait are its two halves, for the one place that queues work between them.
+inline hipError_t sa_read_queue(hipStream_t st, SaScratch &s, HostWord slot, const uint32_t *d_src, uint32_t nwords = 1)
+{
+    return hipMemcpyAsync(s.h_max_cnt + slot, d_src, 4 * (size_t)nwords, hipMemcpyDeviceToHost, st);
+}
+inline hipError_t sa_read_wait(hipStream_t st, SaScratch &s, bool whole_stream = false)
+{
+    if (whole_stream) return hipStreamSynchronize(st);
+    GLC_TRY(hipEventRecord(s.ev_flag, st));
+    return hipEventSynchronize(s.ev_flag);
+}
+inline hipError_t sa_read(hipStream_t st, SaScratch &s, const uint32_t *&words, HostWord slot, const uint32_t *d_src, uint32_t nwords = 1,
+                          bool whole_stream = false)
+{
+    words = s.h_max_cnt + slot;
+    GLC_TRY(sa_read_queue(st, s, slot, d_src, nwords));
+    return sa_read_wait(st, s, whole_stream);
+}
+// the device's count of blocks still given up on (fs_nflag[1]) := left.  The staging word is the copy's alone: nothing else
+// writes it, and every later call of this sits behind a host wait on the same stream.
+inline hipError_t sa_set_left(hipStream_t st, SaScratch &s, uint32_t left)
+{
+    s.h_max_cnt[HW_LEFT] = left;
+    return hipMemcpyAsync(s.fs_nflag + 1, s.h_max_cnt + HW_LEFT, 4, hipMemcpyHostToDevice, st);
+}
+
+// the tiers in sequence (bwt_tiers.cpp).  Synchronises the stream once per doubling round of the general sorter.
+hipError_t sa_build(const SortCall &c, SaScratch &s);
+// two-phase form of sa_build (see bwt_tiers.cpp): stages that follow the sort can be queued between the two calls
+hipError_t sa_build_begin(const SortCall &c, SaScratch &s);
+hipError_t sa_build_finish(const SortCall &c, SaScratch &s, uint32_t *nflagged);
+
+// the general sorter (bwt_sa.hip); cnt0 (optional) = per-block element counts: n for the nsorted blocks to sort, 0 for the others
+// resume_depth != 0: s.keyA already holds, for the blocks of cnt0, the words [group : 44 | suffix : 20] of an order that is
+// exact for the first resume_depth symbols (grp_keys): no sort from the text, prefix doubling from that depth on
+hipError_t sa_build_general(const SortCall &c, SaScratch &s, const uint32_t *cnt0, uint32_t nsorted, uint32_t resume_depth = 0);
+// (bwt_sa.hip) the rows of s.sa that the sample sorter's tolerant form left for the ndeep blocks listed for it -> those words
+// in s.keyA, s.ss_cnt2[b] = n for the blocks it did not give up on (0 for every other block of the plan); enqueues only
+hipError_t grp_keys(const SortCall &c, SaScratch &s, uint32_t ndeep);
 
 // the fast path alone (bwt_bucket.hip): enqueues only; flagged blocks are reported in s.fs_lcnt / s.fs_nflag
-hipError_t fs_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nblk, SaScratch &s,
-                    uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *sa_out);
+hipError_t fs_build(const SortCall &c, SaScratch &s);
 uint32_t   fs_bucket_log2(uint32_t n);
 // k_fs_scan (bwt_bucket.hip) for the nlisted blocks of `list`: fbase = exclusive scan of a block's bucket fills, a bucket past its slot flags the block
 hipError_t fs_scan(hipStream_t st, uint32_t nlisted, const uint32_t *fill, uint32_t *fbase, uint32_t *flag, const uint32_t *list);
-// second tier for the nflag blocks listed in s.ss_list: enqueues only; blocks it gives up on keep n in s.fs_lcnt
-// (the others get 0) and are counted in s.fs_nflag[1]
-hipError_t ss_build(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nflag, SaScratch &s,
-                    uint8_t *bwt_out, size_t bwt_stride, int *d_index, uint32_t *sa_out, uint32_t attempt = 0);
+// second tier for the nflag blocks listed in s.ss_list (c.nblk is not looked at): enqueues only; blocks it gives up on keep
+// n in s.fs_lcnt (the others get 0) and are counted in s.fs_nflag[1]
+hipError_t ss_build(const SortCall &c, SaScratch &s, uint32_t nflag, uint32_t attempt = 0);
 // blocks of the first attempt whose only trouble was a bucket past its slot -> listed behind ss_list, count in s.fs_nflag[2]
 // (count_only: nothing is listed or cleared -- how many there are decides whether the attempt is worth making)
 hipError_t ss_retry_prepare(hipStream_t st, uint32_t nflag, SaScratch &s, uint32_t to = 1, bool count_only = false);
@@ -304,12 +366,11 @@ hipError_t ss_split_masks(hipStream_t st, uint32_t nblk, SaScratch &s);
 // turns the suffix arrays of those texts (s.sa, rows 0 .. nper) into the blocks' BWT rows and indices, clears ss_flag /
 // fs_lcnt of every block it finishes and counts them in s.per_count[2]
 hipError_t per_reserve(SaScratch &s);
-hipError_t per_detect(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nlisted, SaScratch &s);
+hipError_t per_detect(const SortCall &c, SaScratch &s, uint32_t nlisted);
 // before the sample sorter's first attempt: listed blocks whose beginning is periodic for 3/8 of the block or more get ss_flag = 3
-hipError_t per_probe(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nlisted, SaScratch &s);
-hipError_t per_text(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nper, uint32_t nu, SaScratch &s);
-hipError_t per_expand(hipStream_t st, const uint8_t *text, size_t text_stride, uint32_t n, uint32_t nper, uint32_t nu, SaScratch &s,
-                      uint8_t *bwt_out, size_t bwt_stride, int *d_index);
+hipError_t per_probe(const SortCall &c, SaScratch &s, uint32_t nlisted);
+hipError_t per_text(const SortCall &c, SaScratch &s, uint32_t nper, uint32_t nu);
+hipError_t per_expand(const SortCall &c, SaScratch &s, uint32_t nper, uint32_t nu);
 
 // copy SA to the cudppSuffixArray layout (out[0]=n, out[1..n]=SA)
 hipError_t sa_export(hipStream_t st, const uint32_t *sa, uint32_t n, uint32_t *out);

@@ -88,6 +88,43 @@ def test_random_periods_tails_and_alphabets(glc, cuda, seed):
     assert nper >= len(blocks) // 2, (nper, f1, f2)            # (random words of few symbols may have a smaller period or sort early)
 
 
+def test_the_stats_of_a_call_do_not_outlive_it(glc, cuda):
+    """three calls on ONE plan: periodic blocks, then Zipf blocks no tier behind the sample sorter sees, then the periodic blocks
+    again under sorter mode 3 (bucket sorter, then general sorter: no periodic tier).  What glcPlanLastSort* report is the last
+    call's alone.  n = 64 KiB = 16 * PER_PMAX, the smallest block the periodic tier takes: that bound decides -- the tier's other
+    one, nmax >= PER_NU = 7 * 4096 + 32 bytes, is below it."""
+    import torch
+    import datagen
+    L = glc.lib()
+    n, nb = 1 << 16, 2
+    assert n == 16 * 4096 and n >= 7 * 4096 + 32
+    rng = np.random.default_rng(21)
+    periodic = [np.tile(np.frombuffer(b"ab", dtype=np.uint8), n // 2), _periodic(n, 3, 2, rng, [0, 1, 2])]
+    zipf = [datagen.zipf_bytes(n, seed=31), datagen.zipf_bytes(n, seed=32)]
+    want = {id(blocks): [O.bwt(x) for x in blocks] for blocks in (periodic, zipf)}
+
+    def call(plan, blocks):
+        d_in = torch.from_numpy(np.concatenate(blocks)).to(cuda)
+        d_out = torch.zeros_like(d_in)
+        d_idx = torch.full((nb,), -1, dtype=torch.int32, device=cuda)
+        assert L.glcBwtBatch(plan.handle, d_in.data_ptr(), d_out.data_ptr(), d_idx.data_ptr(), n, nb) == 0
+        plan.synchronize()
+        got, idx = d_out.cpu().numpy().reshape(nb, n), d_idx.cpu().numpy()
+        for k, (w, widx) in enumerate(want[id(blocks)]):
+            assert int(idx[k]) == widx, k
+            assert np.array_equal(got[k], w), k
+
+    with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_BWT, n, rows=nb) as plan:
+        call(plan, periodic)
+        assert plan.last_sort_periodic() == 2, plan.last_sort_stats()
+        call(plan, zipf)
+        assert plan.last_sort_periodic() == 0
+        assert plan.last_sort_retries() == 0 and plan.last_sort_resumed() == 0 and plan.last_sort_chains() == (0, 0)
+        plan.set_sorter(3)
+        call(plan, periodic)
+        assert plan.last_sort_periodic() == 0
+
+
 def test_blocks_the_tier_must_leave_alone(glc, cuda):
     """a period longer than the tier takes, a tail longer than it takes, a break in the middle, a word that is itself periodic
     (its smallest period has a tail too long for it): same bytes by the other tiers"""

@@ -1,7 +1,7 @@
 """Blocks with repeats deeper than the sample sorter's cap INSIDE otherwise ordinary data (zero pages, a duplicated region,
 a long phrase, long runs in log lines): the sample sorter runs once more in its tolerant form (suffixes that agree in more
 than SS_TOL_CAP symbols stay as they come), the groups of rows that still tie are found by looking, and prefix doubling
-RESUMES from that depth (bwt_sa.hip sa_build_finish, k_grp_*).  Same bytes as the oracle and as the general sorter from
+RESUMES from that depth (bwt_tiers.cpp tier_resume, bwt_sa.hip k_grp_*).  Same bytes as the oracle and as the general sorter from
 scratch (glcPlanSetSorter 5); glcPlanLastSortResumed says which way a call's blocks went."""
 import numpy as np
 import pytest
