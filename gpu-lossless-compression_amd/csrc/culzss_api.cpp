@@ -4,7 +4,7 @@
 // 569-670; gpu_decompress.cu:98-118,247-358): same symbols, argument meaning and
 // return values, called from the reference's pthread pipeline (culzss.c:85-86,108,
 // 133-134,170,176; deculzss.c:78-79,98,119-120) on different threads ("launch on
-// thread A, wait on thread B"), so all shared state sits behind one mutex.
+// thread A, wait on thread B"), so all shared state sits behind the locks tabulated above State.
 //
 // Differences, all deliberate: token selection/packing runs on the GPU inside the
 // compression stream instead of on a CPU thread (aftercomp, gpu_compress.cu:462-566);
@@ -16,11 +16,27 @@
 #include "glc_internal.h"
 
 #include <algorithm>
+#include <array>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
+
+// host clock around the four phases of compression_kernel_wrapper: nothing without the switch
+#ifdef GLC_LZ_HOSTTRACE
 #include <time.h>
+namespace {
+struct HostTrace {
+    double t[5];
+    int n = 0;
+    void mark() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); t[n++] = ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3; }
+    void print(int index) const { fprintf(stderr, "wrapper slot %d: H2D %.0f us, kernels %.0f us, D2H cand %.0f us, D2H size %.0f us\n", index, t[1] - t[0], t[2] - t[1], t[3] - t[2], t[4] - t[3]); }
+};
+} // namespace
+#else
+namespace { struct HostTrace { void mark() {} void print(int) const {} }; }
+#endif
 
 using namespace glc;
 
@@ -28,8 +44,44 @@ namespace {
 
 constexpr int NSLOTS = 4;                       // ring slots of the reference queue (culzss.c:273-346)
 
+bool ok(hipError_t e, const char *what)
+{
+    if (e == hipSuccess) return true;
+    fprintf(stderr, "culzss (hip): %s: %s\n", what, hipGetErrorString(e));
+    return false;
+}
+
+// One row per buffer of a slot, a group or the decode scratch.  The owner's list is walked to allocate (rows of 0 bytes are
+// left out) and walked again to release, so what is freed is what was allocated.
+struct Mem { void **p; size_t bytes; bool pinned; const char *what; };
+
+template <class List> void mem_release(const List &list)
+{
+    for (const Mem &m : list) {
+        if (*m.p) (void)(m.pinned ? hipHostFree(*m.p) : hipFree(*m.p));
+        *m.p = nullptr;
+    }
+}
+
+template <class List> bool mem_alloc(const List &list)
+{
+    for (const Mem &m : list)
+        if (m.bytes && !ok(m.pinned ? hipHostMalloc(m.p, m.bytes, hipHostMallocDefault) : hipMalloc(m.p, m.bytes), m.what)) return false;
+    return true;
+}
+
+// grow-only scratch: `list` sized for `want`, `cap` what it holds now (0 after a failure: the next call starts over)
+template <class List> bool mem_ensure(int &cap, int want, const List &list)
+{
+    if (cap >= want) return true;
+    mem_release(list);
+    cap = mem_alloc(list) ? want : 0;
+    return cap != 0;
+}
+
 struct Slot {
     hipStream_t stream = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
     int cap = 0;                                // buf_length the scratch below was sized for
     uint8_t *d_packed = nullptr;
     uint8_t *d_in = nullptr, *d_cand = nullptr; // the slot's own input / candidate buffers (see compression_kernel_wrapper)
@@ -40,72 +92,106 @@ struct Slot {
     const unsigned char *key = nullptr;         // host candidate buffer of the in-flight call
     int len = 0;
     bool valid = false;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     // One lock per ring slot: the reference's callers run a producer, a GPU thread and a CPU thread on DIFFERENT slots
     // at the same time (culzss.c:85-176); under one global lock the launch of slot k + 1 (a dozen HIP calls) waited for
-    // the copy-out of slot k.  Order: g.mu (slot lookup, init) is never held while a slot lock is taken for long work.
+    // the copy-out of slot k.
     std::mutex mu;
 };
 
+// the scratch of a slot sized for buf_length (the sizes do not matter to a release)
+std::array<Mem, 7> slot_mem(Slot &s, int buf_length)
+{
+    const size_t stride = lzss_pack_stride(buf_length);
+    return {{{(void **)&s.d_packed, stride, false, "slot packed"},
+             {(void **)&s.d_in, (size_t)buf_length, false, "slot in"},
+             {(void **)&s.d_cand, (size_t)2 * buf_length, false, "slot candidates"},
+             {(void **)&s.d_size, 16, false, "slot size"},                      // (leaves as one 16-byte piece: lzss_copy_to_host)
+             {&s.d_work, lzss_work_bytes(buf_length, 1), false, "slot work"},
+             {(void **)&s.h_packed, stride, true, "slot pinned"},
+             {(void **)&s.h_size, 16, true, "slot pinned size"}}};
+}
+
+// (the tracking entry {valid, key, len} is read and written under g.mu only: the teardown clears it, the wrapper drops it
+//  before it reuses a slot)
+void slot_release(Slot &s) { mem_release(slot_mem(s, 0)); s.cap = 0; }
+bool slot_ensure(Slot &s, int buf_length) { return mem_ensure(s.cap, buf_length, slot_mem(s, buf_length)); }
+
+bool slot_create(Slot &s)
+{
+    return ok(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking), "slot stream") &&
+           ok(hipEventCreate(&s.e0), "slot event") && ok(hipEventCreate(&s.e1), "slot event");
+}
+
+void slot_destroy(Slot &s, bool wait)
+{
+    if (wait && s.stream) (void)hipStreamSynchronize(s.stream);
+    slot_release(s);
+    if (s.stream) (void)hipStreamDestroy(s.stream);
+    if (s.e0) (void)hipEventDestroy(s.e0);
+    if (s.e1) (void)hipEventDestroy(s.e1);
+    s.stream = nullptr; s.e0 = s.e1 = nullptr; s.key = nullptr; s.len = 0; s.valid = false;
+}
+
+// what decompression_kernel_wrapper decodes in: one packed buffer in, one buffer out, {size, error word}
+struct LzDecodeScratch {
+    uint8_t *in = nullptr, *out = nullptr;
+    int *size = nullptr;
+    int cap = 0;                                // the original length this was sized for
+
+    std::array<Mem, 3> mem(int orig)
+    {
+        return {{{(void **)&in, lzss_pack_stride(orig), false, "decode in"},
+                 {(void **)&out, (size_t)orig, false, "decode out"},
+                 {(void **)&size, 2 * sizeof(int), false, "decode size"}}};
+    }
+    bool ensure(int orig) { return mem_ensure(cap, orig, mem(orig)); }
+    void release() { mem_release(mem(0)); cap = 0; }
+};
+
+// Which lock an entry point holds while it does what.  g.mu guards `inited`, the choice of a slot and every slot's tracking
+// entry {valid, key, len}; a slot's mu guards that slot's stream, events and scratch.  No cycle: a RING slot's mu is never
+// taken under g.mu (the wrapper takes g.mu under it, to publish three words); the SCRATCH slot's mu is, and takes nothing.
+//   compression_kernel_wrapper             g.mu for the slot lookup (init; drops the tracking entry) and again to publish the
+//                                          new entry; the ring slot's mu across the work: wait, regrow, copies, kernels
+//   onestream_finish_GPU                   g.mu for the slot lookup (init); waits on the stream under no lock
+//   aftercompression_wrapper               g.mu for the lookup of the entry (init); then the tracked slot's mu (wait, copy
+//                                          out) or, untracked, the scratch slot's mu (the whole packing) -- not g.mu
+//   decompression_kernel_wrapper,          g.mu across the whole call, the scratch slot's mu inside it (culzss_decompress:
+//   culzss_compress                        inside the wrapper it calls)
+//   culzss_container_compress/_decompress  g.mu across the whole call; streams of their own, no slot
+//   initGPU, glcLzssLastKernelMs           g.mu across the whole call
+//   deleteGPUStreams, resetGPU             g.mu only: the caller must have quiesced every thread that uses a slot
 struct State {
     std::mutex mu;
     bool inited = false;
     Slot slot[NSLOTS + 1];                      // +1: scratch slot for stand-alone packing / conveniences
-    // decode scratch
-    uint8_t *dd_in = nullptr, *dd_out = nullptr;
-    int *dd_size = nullptr;
-    int dd_cap = 0;
-    float last_ms = 0.f;
+    LzDecodeScratch dd;                           // runs on the scratch slot's stream
 } g;
 
-bool ok(hipError_t e, const char *what)
+// All streams and events, or none: after a failed creation nothing is left behind and `inited` stays false, so every entry
+// point fails (0) until a later call gets them all.
+bool init_locked()
 {
-    if (e == hipSuccess) return true;
-    fprintf(stderr, "culzss (hip): %s: %s\n", what, hipGetErrorString(e));
-    return false;
-}
-
-void init_locked()
-{
-    if (g.inited) return;
+    if (g.inited) return true;
     // the reference pins device 0 (gpu_compress.cu:395); here the streams belong to whatever device is current
     // in the calling thread, so one process per GPU (rank r on device r) works without HIP_VISIBLE_DEVICES
-    for (auto &s : g.slot) {
-        (void)hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
-        (void)hipEventCreate(&s.e0);
-        (void)hipEventCreate(&s.e1);
-    }
+    for (auto &s : g.slot)
+        if (!slot_create(s)) {
+            for (auto &t : g.slot) slot_destroy(t, false);
+            return false;
+        }
     g.inited = true;
-}
-
-void free_slot(Slot &s)
-{
-    if (s.d_packed) (void)hipFree(s.d_packed);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_cand) (void)hipFree(s.d_cand);
-    if (s.d_size) (void)hipFree(s.d_size);
-    if (s.d_work) (void)hipFree(s.d_work);
-    if (s.h_packed) (void)hipHostFree(s.h_packed);
-    if (s.h_size) (void)hipHostFree(s.h_size);
-    s.d_packed = nullptr; s.d_in = nullptr; s.d_cand = nullptr; s.d_size = nullptr; s.d_work = nullptr; s.h_packed = nullptr; s.h_size = nullptr;
-    s.cap = 0;                                                 // (the tracking entry {valid, key, len} is read and written under g.mu only:
-}                                                              //  the callers that hold it clear it; the wrapper drops it before reusing a slot)
-
-bool ensure_slot(Slot &s, int buf_length)
-{
-    if (s.cap >= buf_length) return true;
-    free_slot(s);
-    const size_t stride = lzss_pack_stride(buf_length);
-    if (!ok(hipMalloc((void **)&s.d_packed, stride), "slot packed")) return false;
-    if (!ok(hipMalloc((void **)&s.d_in, (size_t)buf_length), "slot in")) return false;
-    if (!ok(hipMalloc((void **)&s.d_cand, (size_t)2 * buf_length), "slot candidates")) return false;
-    if (!ok(hipMalloc((void **)&s.d_size, 16), "slot size")) return false;          // (leaves as one 16-byte piece: lzss_copy_to_host)
-    if (!ok(hipMalloc(&s.d_work, lzss_work_bytes(buf_length, 1)), "slot work")) return false;
-    if (!ok(hipHostMalloc((void **)&s.h_packed, stride, hipHostMallocDefault), "slot pinned")) return false;
-    if (!ok(hipHostMalloc((void **)&s.h_size, 16, hipHostMallocDefault), "slot pinned size")) return false;
-    s.cap = buf_length;
     return true;
 }
+
+void teardown_locked(bool wait)
+{
+    for (auto &s : g.slot) slot_destroy(s, wait);
+    g.dd.release();
+    g.inited = false;
+}
+
+Slot &slot_at(int index) { return g.slot[((index % NSLOTS) + NSLOTS) % NSLOTS]; }
 
 // is [p, p + bytes) pinned host memory the device can write (hipHostMalloc / initCPUmem) and 16-byte aligned?
 bool host_mapped(const void *p, size_t bytes)
@@ -124,6 +210,45 @@ bool host_mapped(const void *p, size_t bytes)
 
 bool valid_len(int n) { return n > 0 && n % GLC_LZSS_PACKET == 0 && n <= GLC_LZSS_MAX_BUF; }
 
+// The trailer of a packed buffer (gpu_decompress.cu:257-270): the original length, big-endian, in bytes -6..-3 and the
+// padding in -2..-1.  Only the layout is read here; what lengths a caller accepts is the caller's rule.
+bool parse_trailer(const unsigned char *p, size_t len, int *orig, int *pad)
+{
+    if (len < 6) return false;
+    const unsigned char *t = p + len - 6;
+    *orig = (int)(((unsigned)t[0] << 24) | ((unsigned)t[1] << 16) | ((unsigned)t[2] << 8) | (unsigned)t[3]);
+    *pad = (int)(((unsigned)t[4] << 8) | (unsigned)t[5]);
+    return true;
+}
+
+// Host bytes in -> lzss_encode (a buffer) or lzss_pack (its 2 B/B candidate stream) on the scratch slot -> packed bytes in
+// dst and their count in *size.  0: a HIP call failed; 2: the packed form "took more", dst and *size are untouched and the
+// caller stores the buffer raw; 1 otherwise.
+int scratch_pack(const unsigned char *src, int buf_length, bool candidates, unsigned char *dst, int *size)
+{
+    Slot &s = g.slot[NSLOTS];
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!slot_ensure(s, buf_length)) return 0;
+    const size_t bytes = candidates ? (size_t)2 * buf_length : (size_t)buf_length;
+    uint8_t *d_src = nullptr;
+    if (!ok(hipMalloc((void **)&d_src, bytes), "scratch upload")) return 0;
+    const bool good = ok(hipMemcpyAsync(d_src, src, bytes, hipMemcpyHostToDevice, s.stream), "H2D")
+                   && (candidates ? ok(lzss_pack(s.stream, d_src, buf_length, 1, s.d_packed, s.d_size, s.d_work), "pack")
+                                  : ok(lzss_encode(s.stream, d_src, buf_length, 1, nullptr, s.d_packed, s.d_size, s.d_work), "encode"))
+                   && ok(hipMemcpyAsync(s.h_packed, s.d_packed, lzss_pack_stride(buf_length), hipMemcpyDeviceToHost, s.stream), "D2H")
+                   && ok(hipMemcpyAsync(s.h_size, s.d_size, sizeof(int), hipMemcpyDeviceToHost, s.stream), "D2H size")
+                   && ok(hipStreamSynchronize(s.stream), "sync");
+    (void)hipFree(d_src);
+    if (!good) return 0;
+    if (*s.h_size <= 0) return 2;
+    memcpy(dst, s.h_packed, (size_t)*s.h_size);
+    *size = *s.h_size;
+    return 1;
+}
+
+using Bytes = std::unique_ptr<unsigned char[]>;
+Bytes bytes_new(size_t n) { return Bytes(new (std::nothrow) unsigned char[n ? n : 1]); }
+
 } // namespace
 
 extern "C" {
@@ -131,25 +256,13 @@ extern "C" {
 void initGPU(void)
 {
     std::lock_guard<std::mutex> lk(g.mu);
-    init_locked();
+    (void)init_locked();
 }
 
 void resetGPU(void)
 {
     std::lock_guard<std::mutex> lk(g.mu);
-    for (auto &s : g.slot) {
-        free_slot(s);
-        s.valid = false;
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        if (s.e0) (void)hipEventDestroy(s.e0);
-        if (s.e1) (void)hipEventDestroy(s.e1);
-        s.stream = nullptr; s.e0 = s.e1 = nullptr; s.key = nullptr; s.len = 0;
-    }
-    if (g.dd_in) (void)hipFree(g.dd_in);
-    if (g.dd_out) (void)hipFree(g.dd_out);
-    if (g.dd_size) (void)hipFree(g.dd_size);
-    g.dd_in = g.dd_out = nullptr; g.dd_size = nullptr; g.dd_cap = 0;
-    g.inited = false;
+    teardown_locked(false);
     (void)hipDeviceReset();
 }
 
@@ -158,16 +271,7 @@ int streams_in_GPU(void) { return 1; }
 void deleteGPUStreams(void)
 {
     std::lock_guard<std::mutex> lk(g.mu);
-    for (auto &s : g.slot) {
-        if (s.stream) { (void)hipStreamSynchronize(s.stream); }
-        free_slot(s);
-        s.valid = false;
-        if (s.stream) (void)hipStreamDestroy(s.stream);
-        if (s.e0) (void)hipEventDestroy(s.e0);
-        if (s.e1) (void)hipEventDestroy(s.e1);
-        s.stream = nullptr; s.e0 = s.e1 = nullptr; s.key = nullptr; s.len = 0;
-    }
-    g.inited = false;
+    teardown_locked(true);
 }
 
 void signalExitThreads(void) {}
@@ -200,34 +304,28 @@ int compression_kernel_wrapper(unsigned char *buffer, int buf_length, unsigned c
     Slot *sp;
     {
         std::lock_guard<std::mutex> lk(g.mu);
-        init_locked();
-        sp = &g.slot[((index % NSLOTS) + NSLOTS) % NSLOTS];
+        if (!init_locked()) return 0;
+        sp = &slot_at(index);
         sp->valid = false;                         // the slot is taken again: what it tracked is gone (written under g.mu, as it is read)
     }
     Slot &s = *sp;
     std::lock_guard<std::mutex> lk(s.mu);
     (void)hipStreamSynchronize(s.stream);          // slot reuse: previous call on this slot must be done
-    if (!ensure_slot(s, buf_length)) return 0;
+    if (!slot_ensure(s, buf_length)) return 0;
     hipStream_t st = s.stream;
     // The reference's pipeline hands EVERY ring slot the same in_d / out_d (culzss.c:85-86,108) and queues the slots
     // on different streams without waiting (gpu_compress.cu:426-460): slot s+1's copy-in can overwrite what slot
     // s's kernel is still reading.  The caller's device buffers are therefore accepted but not used: each slot
     // stages through buffers of its own.
     (void)in_d; (void)out_d;
-#ifdef GLC_LZ_HOSTTRACE
-    auto tnow = [] { timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec * 1e6 + t.tv_nsec * 1e-3; };
-    const double t_0 = tnow();
-#endif
+    HostTrace trace;
+    trace.mark();
     if (!ok(hipMemcpyAsync(s.d_in, buffer, (size_t)buf_length, hipMemcpyHostToDevice, st), "H2D")) return 0;
-#ifdef GLC_LZ_HOSTTRACE
-    const double t_1 = tnow();
-#endif
+    trace.mark();
     (void)hipEventRecord(s.e0, st);
     if (!ok(lzss_encode(st, s.d_in, buf_length, 1, s.d_cand, s.d_packed, s.d_size, s.d_work), "encode")) return 0;
     (void)hipEventRecord(s.e1, st);
-#ifdef GLC_LZ_HOSTTRACE
-    const double t_2 = tnow();
-#endif
+    trace.mark();
     // what leaves the device here: the candidate stream (the interface's compressed_buffer: 2 B per input byte) and the
     // packed size.  The packed bytes stay in the slot until aftercompression_wrapper knows how many there are and copies
     // exactly those, straight into the caller's buffer (a whole-slot copy into pinned staging + a host memcpy were
@@ -236,13 +334,10 @@ int compression_kernel_wrapper(unsigned char *buffer, int buf_length, unsigned c
         // pinned (initCPUmem, as the reference's callers allocate it): written by a kernel -- see k_lzss_to_host
         if (!ok(lzss_copy_to_host(st, s.d_cand, compressed_buffer, (size_t)2 * buf_length), "candidates to host")) return 0;
     } else if (!ok(hipMemcpyAsync(compressed_buffer, s.d_cand, (size_t)2 * buf_length, hipMemcpyDeviceToHost, st), "D2H cand")) return 0;
-#ifdef GLC_LZ_HOSTTRACE
-    const double t_3 = tnow();
-#endif
+    trace.mark();
     if (!ok(lzss_copy_to_host(st, s.d_size, s.h_size, 16), "size to host")) return 0;
-#ifdef GLC_LZ_HOSTTRACE
-    fprintf(stderr, "wrapper slot %d: H2D %.0f us, kernels %.0f us, D2H cand %.0f us, D2H size %.0f us\n", index, t_1 - t_0, t_2 - t_1, t_3 - t_2, tnow() - t_3);
-#endif
+    trace.mark();
+    trace.print(index);
     {
         std::lock_guard<std::mutex> lg(g.mu);
         s.key = compressed_buffer; s.len = buf_length; s.valid = true;
@@ -255,8 +350,8 @@ int onestream_finish_GPU(int index)
     hipStream_t st;
     {
         std::lock_guard<std::mutex> lk(g.mu);
-        init_locked();
-        st = g.slot[((index % NSLOTS) + NSLOTS) % NSLOTS].stream;
+        if (!init_locked()) return 0;
+        st = slot_at(index).stream;
     }
     return ok(hipStreamSynchronize(st), "stream sync") ? 1 : 0;
 }
@@ -267,30 +362,12 @@ int aftercompression_wrapper(unsigned char *buffer, int buf_length, unsigned cha
     Slot *hit = nullptr;
     {
         std::lock_guard<std::mutex> lk(g.mu);
-        init_locked();
+        if (!init_locked()) return 0;
         for (int i = 0; i < NSLOTS; i++)
             if (g.slot[i].valid && g.slot[i].key == bufferout && g.slot[i].len == buf_length) { hit = &g.slot[i]; hit->valid = false; }
     }
-    if (!hit) {
-        // candidates that did not come from a tracked call: pack them on the GPU now
-        Slot &s = g.slot[NSLOTS];
-        std::lock_guard<std::mutex> lk(s.mu);
-        if (!ensure_slot(s, buf_length)) return 0;
-        uint8_t *d_cand = nullptr;
-        if (!ok(hipMalloc((void **)&d_cand, (size_t)2 * buf_length), "cand upload")) return 0;
-        bool good = ok(hipMemcpyAsync(d_cand, bufferout, (size_t)2 * buf_length, hipMemcpyHostToDevice, s.stream), "H2D cand")
-                 && ok(lzss_pack(s.stream, d_cand, buf_length, 1, s.d_packed, s.d_size, s.d_work), "pack")
-                 && ok(hipMemcpyAsync(s.h_packed, s.d_packed, lzss_pack_stride(buf_length), hipMemcpyDeviceToHost, s.stream), "D2H")
-                 && ok(hipMemcpyAsync(s.h_size, s.d_size, sizeof(int), hipMemcpyDeviceToHost, s.stream), "D2H size")
-                 && ok(hipStreamSynchronize(s.stream), "sync");
-        (void)hipFree(d_cand);
-        if (!good) return 0;
-        const int size = *s.h_size;
-        if (size <= 0) return 0;                    // "compression took more": caller stores the buffer raw
-        memcpy(buffer, s.h_packed, (size_t)size);
-        *comp_length = size;
-        return 1;
-    }
+    // candidates that did not come from a tracked call: pack them on the GPU now ("took more": the caller stores the buffer raw)
+    if (!hit) return scratch_pack(bufferout, buf_length, true, buffer, comp_length) == 1 ? 1 : 0;
     std::lock_guard<std::mutex> lk(hit->mu);
     if (!ok(hipStreamSynchronize(hit->stream), "sync")) return 0;
     const int size = *hit->h_size;
@@ -305,35 +382,25 @@ int decompression_kernel_wrapper(unsigned char *buffer, int buf_length, int *dec
                                  int /*compression_type*/, int /*wsize*/, int /*numthre*/)
 {
     if (!buffer || !decomp_length || buf_length < 8) return 0;
-    // trailer (gpu_decompress.cu:257-270)
-    const int orig = (int)(((unsigned)buffer[buf_length - 6] << 24) ^ ((unsigned)buffer[buf_length - 5] << 16) ^
-                           ((unsigned)buffer[buf_length - 4] << 8) ^ (unsigned)buffer[buf_length - 3]);
-    const int pad = (int)(((unsigned)buffer[buf_length - 2] << 8) ^ (unsigned)buffer[buf_length - 1]);
+    int orig, pad;
+    if (!parse_trailer(buffer, (size_t)buf_length, &orig, &pad)) return 0;
     if (!valid_len(orig) || pad < 0 || pad > orig || buf_length < 2 * (orig / GLC_LZSS_PACKET) + 6) return 0;
     std::lock_guard<std::mutex> lk(g.mu);
-    init_locked();
+    if (!init_locked()) return 0;
     std::lock_guard<std::mutex> ls(g.slot[NSLOTS].mu);        // (the scratch slot's stream: shared with the untracked packing path)
-    if (g.dd_cap < orig) {
-        if (g.dd_in) (void)hipFree(g.dd_in);
-        if (g.dd_out) (void)hipFree(g.dd_out);
-        if (g.dd_size) (void)hipFree(g.dd_size);
-        g.dd_in = g.dd_out = nullptr; g.dd_size = nullptr; g.dd_cap = 0;
-        if (!ok(hipMalloc((void **)&g.dd_in, lzss_pack_stride(orig)), "decode in")) return 0;
-        if (!ok(hipMalloc((void **)&g.dd_out, (size_t)orig), "decode out")) return 0;
-        if (!ok(hipMalloc((void **)&g.dd_size, 2 * sizeof(int)), "decode size")) return 0;   // {size, error word}
-        g.dd_cap = orig;
-    }
+    LzDecodeScratch &dd = g.dd;
+    if (!dd.ensure(orig)) return 0;
     if ((size_t)buf_length > lzss_pack_stride(orig)) return 0;
     hipStream_t st = g.slot[NSLOTS].stream;
-    int hdr[2] = {buf_length, 0}, err = 0;
-    bool good = ok(hipMemcpyAsync(g.dd_in, buffer, (size_t)buf_length, hipMemcpyHostToDevice, st), "H2D")
-             && ok(hipMemcpyAsync(g.dd_size, hdr, sizeof hdr, hipMemcpyHostToDevice, st), "H2D size")
+    int hdr[2] = {buf_length, 0}, err = 0;                     // {size, error word}
+    bool good = ok(hipMemcpyAsync(dd.in, buffer, (size_t)buf_length, hipMemcpyHostToDevice, st), "H2D")
+             && ok(hipMemcpyAsync(dd.size, hdr, sizeof hdr, hipMemcpyHostToDevice, st), "H2D size")
              && ok(hipStreamSynchronize(st), "sync")       // hdr is a stack variable
-             && ok(lzss_decode(st, g.dd_in, g.dd_size, orig, 1, g.dd_out, g.dd_size + 1), "decode")
-             && ok(hipMemcpyAsync(&err, g.dd_size + 1, sizeof(int), hipMemcpyDeviceToHost, st), "D2H err")
+             && ok(lzss_decode(st, dd.in, dd.size, orig, 1, dd.out, dd.size + 1), "decode")
+             && ok(hipMemcpyAsync(&err, dd.size + 1, sizeof(int), hipMemcpyDeviceToHost, st), "D2H err")
              && ok(hipStreamSynchronize(st), "sync");
     if (!good || err) return 0;                             // malformed stream: nothing is written back
-    good = ok(hipMemcpyAsync(buffer, g.dd_out, (size_t)(orig - pad), hipMemcpyDeviceToHost, st), "D2H")
+    good = ok(hipMemcpyAsync(buffer, dd.out, (size_t)(orig - pad), hipMemcpyDeviceToHost, st), "D2H")
         && ok(hipStreamSynchronize(st), "sync");
     if (!good) return 0;
     *decomp_length = orig - pad;
@@ -347,39 +414,24 @@ int culzss_compress(const unsigned char *in, int len, unsigned char *out, int *o
 {
     if (!in || !out || !out_len || !valid_len(len)) return 0;
     std::lock_guard<std::mutex> lk(g.mu);
-    init_locked();
-    Slot &s = g.slot[NSLOTS];
-    std::lock_guard<std::mutex> ls(s.mu);
-    if (!ensure_slot(s, len)) return 0;
-    uint8_t *d_in = nullptr;
-    if (!ok(hipMalloc((void **)&d_in, (size_t)len), "culzss_compress in")) return 0;
-    bool good = ok(hipMemcpyAsync(d_in, in, (size_t)len, hipMemcpyHostToDevice, s.stream), "H2D")
-             && ok(lzss_encode(s.stream, d_in, len, 1, nullptr, s.d_packed, s.d_size, s.d_work), "encode")
-             && ok(hipMemcpyAsync(s.h_packed, s.d_packed, lzss_pack_stride(len), hipMemcpyDeviceToHost, s.stream), "D2H")
-             && ok(hipMemcpyAsync(s.h_size, s.d_size, sizeof(int), hipMemcpyDeviceToHost, s.stream), "D2H size")
-             && ok(hipStreamSynchronize(s.stream), "sync");
-    (void)hipFree(d_in);
-    if (!good) return 0;
-    const int size = *s.h_size;
-    if (size <= 0) { memcpy(out, in, (size_t)len); *out_len = len; return 2; }
-    memcpy(out, s.h_packed, (size_t)size);
-    *out_len = size;
-    return 1;
+    if (!init_locked()) return 0;
+    const int rc = scratch_pack(in, len, false, out, out_len);
+    if (rc == 2) { memcpy(out, in, (size_t)len); *out_len = len; }
+    return rc;
 }
 
 int culzss_decompress(const unsigned char *in, int len, unsigned char *out, int *out_len)
 {
     if (!in || !out || !out_len || len < 8) return 0;
-    const int orig = (int)(((unsigned)in[len - 6] << 24) ^ ((unsigned)in[len - 5] << 16) ^
-                           ((unsigned)in[len - 4] << 8) ^ (unsigned)in[len - 3]);
+    int orig, pad;
+    if (!parse_trailer(in, (size_t)len, &orig, &pad)) return 0;
     if (!valid_len(orig) || (size_t)len > lzss_pack_stride(orig)) return 0;
-    unsigned char *tmp = (unsigned char *)malloc(lzss_pack_stride(orig) > (size_t)orig ? lzss_pack_stride(orig) : (size_t)orig);
+    Bytes tmp = bytes_new(std::max(lzss_pack_stride(orig), (size_t)orig));   // the wrapper decodes in place
     if (!tmp) return 0;
-    memcpy(tmp, in, (size_t)len);
+    memcpy(tmp.get(), in, (size_t)len);
     int n = 0;
-    const int rc = decompression_kernel_wrapper(tmp, len, &n, 0, 1, 1);
-    if (rc == 1) { memcpy(out, tmp, (size_t)n); *out_len = n; }
-    free(tmp);
+    const int rc = decompression_kernel_wrapper(tmp.get(), len, &n, 0, 1, 1);
+    if (rc == 1) { memcpy(out, tmp.get(), (size_t)n); *out_len = n; }
     return rc;
 }
 
@@ -473,33 +525,78 @@ struct Group {
     size_t first = 0;
 };
 
-bool group_alloc(Group &g, bool decode)
+// a group's buffers; the rows of the other direction have 0 bytes (the sizes do not matter to a release)
+std::array<Mem, 9> group_mem(Group &G, bool decode)
 {
-    const size_t stride = lzss_pack_stride(CBUF);
-    if (!ok(hipStreamCreateWithFlags(&g.st, hipStreamNonBlocking), "group stream")) return false;
-    if (!ok(hipMalloc((void **)&g.d_packed, stride * GROUP), "group packed")) return false;
-    if (!ok(hipMalloc((void **)&g.d_sizes, sizeof(int) * (GROUP + 1)), "group sizes")) return false;
-    if (!ok(hipHostMalloc((void **)&g.h_packed, stride * GROUP, hipHostMallocDefault), "group h_packed")) return false;
-    if (!ok(hipHostMalloc((void **)&g.h_sizes, sizeof(int) * (GROUP + 1), hipHostMallocDefault), "group h_sizes")) return false;
-    if (!decode) {
-        if (!ok(hipMalloc((void **)&g.d_in, (size_t)CBUF * GROUP), "group in")) return false;
-        if (!ok(hipHostMalloc((void **)&g.h_in, (size_t)CBUF * GROUP, hipHostMallocDefault), "group h_in")) return false;
-        if (!ok(hipMalloc(&g.d_work, lzss_work_bytes(CBUF, GROUP)), "group work")) return false;
-    } else {
-        if (!ok(hipMalloc((void **)&g.d_out, (size_t)CBUF * GROUP), "group out")) return false;
-        if (!ok(hipHostMalloc((void **)&g.h_out, (size_t)CBUF * GROUP, hipHostMallocDefault), "group h_out")) return false;
-    }
-    return true;
+    const size_t stride = lzss_pack_stride(CBUF), enc = decode ? 0 : 1, dec = decode ? 1 : 0;
+    return {{{(void **)&G.d_packed, stride * GROUP, false, "group packed"},
+             {(void **)&G.d_sizes, sizeof(int) * (GROUP + 1), false, "group sizes"},
+             {(void **)&G.h_packed, stride * GROUP, true, "group h_packed"},
+             {(void **)&G.h_sizes, sizeof(int) * (GROUP + 1), true, "group h_sizes"},
+             {(void **)&G.d_in, enc * CBUF * GROUP, false, "group in"},
+             {(void **)&G.h_in, enc * CBUF * GROUP, true, "group h_in"},
+             {&G.d_work, enc * lzss_work_bytes(CBUF, GROUP), false, "group work"},
+             {(void **)&G.d_out, dec * CBUF * GROUP, false, "group out"},
+             {(void **)&G.h_out, dec * CBUF * GROUP, true, "group h_out"}}};
 }
 
-void group_free(Group &g)
+bool group_alloc(Group &G, bool decode)
 {
-    if (g.st) { (void)hipStreamSynchronize(g.st); (void)hipStreamDestroy(g.st); }
-    void *dp[] = {g.d_in, g.d_packed, g.d_sizes, g.d_work, g.d_out};
-    for (void *p : dp) if (p) (void)hipFree(p);
-    void *hp[] = {g.h_in, g.h_packed, g.h_sizes, g.h_out};
-    for (void *p : hp) if (p) (void)hipHostFree(p);
-    g = Group();
+    return ok(hipStreamCreateWithFlags(&G.st, hipStreamNonBlocking), "group stream") && mem_alloc(group_mem(G, decode));
+}
+
+void group_free(Group &G)
+{
+    if (G.st) { (void)hipStreamSynchronize(G.st); (void)hipStreamDestroy(G.st); }
+    mem_release(group_mem(G, false));
+    G.st = nullptr;
+}
+
+// The double-buffered loop of both container directions over nb buffers: group g + 1 is submitted (its copies and kernels
+// queued on its own stream) before group g is collected, so the device works while the host assembles.  submit(G) and
+// collect(G) return false to stop; the two groups are released on every way out.
+template <class Submit, class Collect> bool run_groups(size_t nb, bool decode, Submit submit, Collect collect)
+{
+    Group grp[2];
+    auto start = [&](Group &G, size_t first) {
+        G.first = first; G.nbuf = (int)std::min((size_t)GROUP, nb - first);
+        return submit(G);
+    };
+    bool good = group_alloc(grp[0], decode) && group_alloc(grp[1], decode) && start(grp[0], 0);
+    size_t next = GROUP;
+    int cur = 0;
+    while (good) {
+        const bool more = next < nb;
+        if (more) { good = start(grp[cur ^ 1], next); next += GROUP; }
+        good = good && collect(grp[cur]);
+        if (!more) break;
+        cur ^= 1;
+    }
+    group_free(grp[0]); group_free(grp[1]);
+    return good;
+}
+
+// the whole file, or nothing (pipes, FIFOs, directories: not seekable)
+Bytes slurp(const char *path, unsigned long long *len)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) return nullptr;
+    Bytes p;
+    long sz = -1;
+    if (fseek(f, 0, SEEK_END) == 0 && (sz = ftell(f)) >= 0 && fseek(f, 0, SEEK_SET) == 0) p = bytes_new((size_t)sz);
+    if (p && fread(p.get(), 1, (size_t)sz, f) != (size_t)sz) p.reset();
+    fclose(f);
+    *len = p ? (unsigned long long)sz : 0;
+    return p;
+}
+
+bool spill(const char *path, const unsigned char *data, size_t len)
+{
+    FILE *f = fopen(path, "wb");
+    if (!f) return false;
+    const bool all = fwrite(data, 1, len, f) == len;
+    fclose(f);
+    return all;
 }
 
 } // namespace
@@ -519,56 +616,40 @@ int culzss_container_compress(const unsigned char *in, unsigned long long len, u
     if (len < (unsigned long long)CBUF) return 0;            // "too small to benefit from GPU" (main.c:228-232)
     const size_t nb = (size_t)((len + CBUF - 1) / CBUF);
     if (nb > 0x3FFFFFFFu || out_cap < culzss_container_bound(len)) return 0;
-    const uint32_t padding = (uint32_t)(nb * (size_t)CBUF - len);
-    uint32_t *hdr = reinterpret_cast<uint32_t *>(out);       // out comes from malloc/numpy: aligned
-    uint32_t w0 = (uint32_t)nb; memcpy(out, &w0, 4); memcpy(out + 4, &padding, 4);
+    const uint32_t nb32 = (uint32_t)nb, padding = (uint32_t)(nb * (size_t)CBUF - len);
+    memcpy(out, &nb32, 4); memcpy(out + 4, &padding, 4);
     size_t wpos = 8 + 4 * nb, cum = 0;
-    (void)hdr;
     std::lock_guard<std::mutex> lk(g.mu);
-    init_locked();
-    Group grp[2];
-    if (!group_alloc(grp[0], false) || !group_alloc(grp[1], false)) { group_free(grp[0]); group_free(grp[1]); return 0; }
+    if (!init_locked()) return 0;
     const size_t stride = lzss_pack_stride(CBUF);
-    bool good = true;
-    auto submit = [&](Group &G, size_t first) {
-        G.first = first; G.nbuf = (int)std::min((size_t)GROUP, nb - first);
+    auto submit = [&](Group &G) {
         for (int i = 0; i < G.nbuf; i++) {
-            const size_t off = (first + i) * (size_t)CBUF;
+            const size_t off = (G.first + i) * (size_t)CBUF;
             const size_t take = std::min((size_t)CBUF, (size_t)len - off);
             memcpy(G.h_in + (size_t)i * CBUF, in + off, take);
             if (take < (size_t)CBUF) memset(G.h_in + (size_t)i * CBUF + take, 0, CBUF - take);   // zero-filled tail
         }
-        good = good && ok(hipMemcpyAsync(G.d_in, G.h_in, (size_t)G.nbuf * CBUF, hipMemcpyHostToDevice, G.st), "H2D")
+        return ok(hipMemcpyAsync(G.d_in, G.h_in, (size_t)G.nbuf * CBUF, hipMemcpyHostToDevice, G.st), "H2D")
             && ok(lzss_encode(G.st, G.d_in, CBUF, G.nbuf, nullptr, G.d_packed, G.d_sizes, G.d_work), "encode")
             && ok(hipMemcpyAsync(G.h_sizes, G.d_sizes, sizeof(int) * G.nbuf, hipMemcpyDeviceToHost, G.st), "D2H sizes")
             && ok(hipMemcpyAsync(G.h_packed, G.d_packed, stride * G.nbuf, hipMemcpyDeviceToHost, G.st), "D2H packed");
     };
     auto collect = [&](Group &G) {
-        good = good && ok(hipStreamSynchronize(G.st), "sync");
-        for (int i = 0; good && i < G.nbuf; i++) {
+        if (!ok(hipStreamSynchronize(G.st), "sync")) return false;
+        for (int i = 0; i < G.nbuf; i++) {
             int sz = G.h_sizes[i];
             if (sz >= CBUF) sz = 0;                                           // never packed to >= BUFSIZE: a payload of exactly
                                                                               // BUFSIZE bytes MEANS raw (deculzss.c:94-95)
             const size_t bytes = sz > 0 ? (size_t)sz : (size_t)CBUF;          // 0 => stored raw (culzss.c:241-242)
-            if (wpos + bytes > out_cap || cum + bytes > 0xFFFFFFFFull) { good = false; break; }   // u32 offsets: format limit
+            if (wpos + bytes > out_cap || cum + bytes > 0xFFFFFFFFull) return false;              // u32 offsets: format limit
             memcpy(out + wpos, sz > 0 ? G.h_packed + (size_t)i * stride : G.h_in + (size_t)i * CBUF, bytes);
             wpos += bytes; cum += bytes;
             const uint32_t c32 = (uint32_t)cum;
             memcpy(out + 8 + 4 * (G.first + i), &c32, 4);
         }
+        return true;
     };
-    size_t next = 0;
-    int cur = 0;
-    submit(grp[cur], next); next += GROUP;
-    while (good) {
-        const bool more = next < nb;
-        if (more) { submit(grp[cur ^ 1], next); next += GROUP; }
-        collect(grp[cur]);
-        if (!more) break;
-        cur ^= 1;
-    }
-    group_free(grp[0]); group_free(grp[1]);
-    if (!good) return 0;
+    if (!run_groups(nb, false, submit, collect)) return 0;
     *out_len = wpos;
     return 1;
 }
@@ -584,105 +665,71 @@ int culzss_container_decompress(const unsigned char *in, unsigned long long len,
     const unsigned long long total = (unsigned long long)nb * CBUF - padding;
     if (out_cap < total) return 0;
     std::lock_guard<std::mutex> lk(g.mu);
-    init_locked();
-    Group grp[2];
-    if (!group_alloc(grp[0], true) || !group_alloc(grp[1], true)) { group_free(grp[0]); group_free(grp[1]); return 0; }
+    if (!init_locked()) return 0;
     const size_t stride = lzss_pack_stride(CBUF);
     const size_t payload = 8 + 4 * nb;
-    bool good = true;
     auto cumat = [&](size_t i) -> size_t { if (i == 0) return 0; uint32_t c; memcpy(&c, in + 8 + 4 * (i - 1), 4); return c; };
-    auto submit = [&](Group &G, size_t first) {
-        G.first = first; G.nbuf = (int)std::min((size_t)GROUP, nb - first);
-        for (int i = 0; good && i < G.nbuf; i++) {
-            const size_t a = cumat(first + i), b = cumat(first + i + 1);
+    auto submit = [&](Group &G) {
+        for (int i = 0; i < G.nbuf; i++) {
+            const size_t a = cumat(G.first + i), b = cumat(G.first + i + 1);
             const size_t sz = b - a;
             // (a packed chunk may be LONGER than the buffer: the reference's packer only gives up when the bytes flushed
             //  before the last group outgrow it, so up to BUFSIZE + 535 bytes reach the file -- include/culzss.h -- and
             //  its decoder takes everything that is not exactly BUFSIZE as packed, deculzss.c:92-98)
-            if (b < a || sz > stride || payload + b > len) { good = false; break; }
+            if (b < a || sz > stride || payload + b > len) return false;
             const uint8_t *src = in + payload + a;
             if (sz != (size_t)CBUF) {                                          // packed: must hold its trailer, and the trailer
                 constexpr size_t TR = 2 * (CBUF / GLC_LZSS_PACKET) + 6;        // must describe a 1 MiB buffer without padding
-                if (sz < TR) { good = false; break; }
-                const uint32_t orig = ((uint32_t)src[sz - 6] << 24) | ((uint32_t)src[sz - 5] << 16) |
-                                      ((uint32_t)src[sz - 4] << 8) | (uint32_t)src[sz - 3];
-                if (orig != (uint32_t)CBUF || src[sz - 2] || src[sz - 1]) { good = false; break; }
+                int orig, pad;
+                if (sz < TR || !parse_trailer(src, sz, &orig, &pad) || orig != CBUF || pad != 0) return false;
             }
             memcpy(G.h_packed + (size_t)i * stride, src, sz);
             G.h_sizes[i] = (sz == (size_t)CBUF) ? 0 : (int)sz;             // raw buffers: deculzss.c:94-95
         }
         G.h_sizes[GROUP] = 0;                                              // error word
-        good = good && ok(hipMemcpyAsync(G.d_packed, G.h_packed, stride * G.nbuf, hipMemcpyHostToDevice, G.st), "H2D")
+        return ok(hipMemcpyAsync(G.d_packed, G.h_packed, stride * G.nbuf, hipMemcpyHostToDevice, G.st), "H2D")
             && ok(hipMemcpyAsync(G.d_sizes, G.h_sizes, sizeof(int) * (GROUP + 1), hipMemcpyHostToDevice, G.st), "H2D sizes")
             && ok(lzss_decode(G.st, G.d_packed, G.d_sizes, CBUF, G.nbuf, G.d_out, G.d_sizes + GROUP), "decode")
             && ok(hipMemcpyAsync(G.h_sizes + GROUP, G.d_sizes + GROUP, sizeof(int), hipMemcpyDeviceToHost, G.st), "D2H err")
             && ok(hipMemcpyAsync(G.h_out, G.d_out, (size_t)G.nbuf * CBUF, hipMemcpyDeviceToHost, G.st), "D2H");
     };
     auto collect = [&](Group &G) {
-        good = good && ok(hipStreamSynchronize(G.st), "sync");
-        if (good && G.h_sizes[GROUP]) good = false;                        // a packet table that does not add up
-        for (int i = 0; good && i < G.nbuf; i++) {
+        if (!ok(hipStreamSynchronize(G.st), "sync") || G.h_sizes[GROUP]) return false;   // (a packet table that does not add up)
+        for (int i = 0; i < G.nbuf; i++) {
             const size_t off = (G.first + i) * (size_t)CBUF;
             const size_t take = std::min((size_t)CBUF, (size_t)total - off);  // last buffer loses the padding (deculzss.c:156-159)
             memcpy(out + off, G.h_out + (size_t)i * CBUF, take);
         }
+        return true;
     };
-    size_t next = 0;
-    int cur = 0;
-    submit(grp[cur], next); next += GROUP;
-    while (good) {
-        const bool more = next < nb;
-        if (more) { submit(grp[cur ^ 1], next); next += GROUP; }
-        collect(grp[cur]);
-        if (!more) break;
-        cur ^= 1;
-    }
-    group_free(grp[0]); group_free(grp[1]);
-    if (!good) return 0;
+    if (!run_groups(nb, true, submit, collect)) return 0;
     *out_len = total;
-    return 1;
-}
-
-static int slurp(const char *path, unsigned char **data, unsigned long long *len)
-{
-    FILE *f = fopen(path, "rb");
-    if (!f) return 0;
-    if (fseek(f, 0, SEEK_END) != 0) { fclose(f); return 0; }          // pipes, FIFOs, directories: not seekable
-    const long sz = ftell(f);
-    if (sz < 0 || fseek(f, 0, SEEK_SET) != 0) { fclose(f); return 0; }
-    unsigned char *p = (unsigned char *)malloc(sz > 0 ? (size_t)sz : 1);
-    if (!p) { fclose(f); return 0; }
-    const size_t got = fread(p, 1, (size_t)sz, f);
-    fclose(f);
-    if (got != (size_t)sz) { free(p); return 0; }
-    *data = p; *len = (unsigned long long)sz;
     return 1;
 }
 
 /* ./main -i in -o out   (main.c:160-186, compress branch) */
 int culzss_compress_file(const char *in_path, const char *out_path)
 {
-    unsigned char *in = nullptr; unsigned long long len = 0, olen = 0;
-    if (!in_path || !out_path || !slurp(in_path, &in, &len)) return 0;
-    unsigned char *out = (unsigned char *)malloc((size_t)culzss_container_bound(len) + 16);
-    int rc = out ? culzss_container_compress(in, len, out, culzss_container_bound(len), &olen) : 0;
-    if (rc) { FILE *f = fopen(out_path, "wb"); rc = f && fwrite(out, 1, (size_t)olen, f) == (size_t)olen; if (f) fclose(f); }
-    free(in); free(out);
-    return rc;
+    unsigned long long len = 0, olen = 0;
+    if (!in_path || !out_path) return 0;
+    const Bytes in = slurp(in_path, &len);
+    if (!in) return 0;
+    const Bytes out = bytes_new((size_t)culzss_container_bound(len) + 16);
+    return out && culzss_container_compress(in.get(), len, out.get(), culzss_container_bound(len), &olen) &&
+           spill(out_path, out.get(), (size_t)olen);
 }
 
 /* ./main -d 1 -i in -o out   (main.c:207-222) */
 int culzss_decompress_file(const char *in_path, const char *out_path)
 {
-    unsigned char *in = nullptr; unsigned long long len = 0, olen = 0;
-    if (!in_path || !out_path || !slurp(in_path, &in, &len) || len < 8) { free(in); return 0; }
-    uint32_t nb; memcpy(&nb, in, 4);
+    unsigned long long len = 0, olen = 0;
+    if (!in_path || !out_path) return 0;
+    const Bytes in = slurp(in_path, &len);
+    if (!in || len < 8) return 0;
+    uint32_t nb; memcpy(&nb, in.get(), 4);
     const unsigned long long cap = (unsigned long long)nb * CBUF;
-    unsigned char *out = (unsigned char *)malloc(cap ? (size_t)cap : 1);
-    int rc = out ? culzss_container_decompress(in, len, out, cap, &olen) : 0;
-    if (rc) { FILE *f = fopen(out_path, "wb"); rc = f && fwrite(out, 1, (size_t)olen, f) == (size_t)olen; if (f) fclose(f); }
-    free(in); free(out);
-    return rc;
+    const Bytes out = bytes_new((size_t)cap);
+    return out && culzss_container_decompress(in.get(), len, out.get(), cap, &olen) && spill(out_path, out.get(), (size_t)olen);
 }
 
 } // extern "C"

@@ -397,3 +397,151 @@ def test_container_with_a_packed_chunk_longer_than_the_buffer(glc, cuda):
     too_long = np.concatenate([np.array([1, 0, int(L.glcLzssPackStride(MiB)) + 1], dtype=np.uint32).view(np.uint8),
                                np.zeros(int(L.glcLzssPackStride(MiB)) + 1, dtype=np.uint8)])
     assert L.culzss_container_decompress(too_long.ctypes.data, too_long.size, back.ctypes.data, back.size, C.byref(k)) == 0
+
+
+# --------------------------------------------------------------------------
+# The host layer of culzss_api.cpp: group boundaries of the container loop, regrowth of the cached scratch, the ring index,
+# the tracking entry and the file functions' refusals.  References are computed once and shared.
+# --------------------------------------------------------------------------
+_REF = {}
+
+
+def _tile3():
+    """3 MiB of log lines: tiled, so buffer i of an input holds the bytes of buffer i % 3"""
+    if "tile" not in _REF:
+        _REF["tile"] = datagen.log_bytes(3 * MiB, seed=77)
+    return _REF["tile"]
+
+
+def _ref_packed(key, make):
+    """(bytes, candidates, packed form) of a buffer by the oracle, once per key"""
+    if key not in _REF:
+        x = np.ascontiguousarray(make())
+        cand = O.lzss_candidates(x)
+        _REF[key] = (x, cand, O.lzss_pack(cand, x.size))
+    return _REF[key]
+
+
+def _tile_block(i, take=MiB):
+    def make():
+        blk = np.zeros(MiB, dtype=np.uint8)
+        blk[:take] = _tile3()[(i % 3) * MiB:(i % 3) * MiB + take]
+        return blk
+    return _ref_packed(("tile", i % 3, take), make)
+
+
+def _small(seed):
+    return _ref_packed(("small", seed), lambda: datagen.log_bytes(4 * 4096, seed=seed))
+
+
+def _as_u8(ptr, n):
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n,))
+
+
+@pytest.mark.parametrize("nbufs,tail", [(1, 0), (16, 0), (17, 777), (32, 0)])
+def test_container_group_boundaries(glc, cuda, nbufs, tail):
+    """the double-buffered loop at its edges (16 buffers per group): one partial group, one full group with nothing after
+    it, a second group of one (ragged) buffer, two full groups"""
+    L = glc.lib()
+    size = nbufs * MiB if not tail else (nbufs - 1) * MiB + tail
+    x = np.tile(_tile3(), (nbufs + 2) // 3)[:size].copy()
+    cap = L.culzss_container_bound(x.size)
+    out = np.zeros(cap, dtype=np.uint8)
+    n = C.c_ulonglong(0)
+    assert L.culzss_container_compress(x.ctypes.data, x.size, out.ctypes.data, cap, C.byref(n)) == 1
+    hdr = out[:8].view(np.uint32)
+    assert hdr[0] == nbufs and hdr[1] == nbufs * MiB - size
+    body = 8 + 4 * nbufs
+    cum = np.concatenate([[0], out[8:body].view(np.uint32).astype(np.int64)])
+    assert np.all(np.diff(cum) > 0) and cum[-1] == n.value - body
+    for i in sorted({0, nbufs - 1}):
+        want = _tile_block(i, tail if tail and i == nbufs - 1 else MiB)[2]
+        got = out[body + cum[i]: body + cum[i + 1]]
+        assert np.array_equal(got, want), "buffer %d " % i + _first_diff(got, want)
+    back = np.zeros(nbufs * MiB, dtype=np.uint8)
+    m = C.c_ulonglong(0)
+    assert L.culzss_container_decompress(out.ctypes.data, n.value, back.ctypes.data, back.size, C.byref(m)) == 1
+    assert m.value == size and np.array_equal(back[:size], x)
+
+
+def test_slot_scratch_regrows_and_ring_index_wraps(glc, cuda):
+    """one ring slot through a small buffer, a 1 MiB one (its scratch grows) and the small one again (it does not shrink);
+    index -1 and index 7 are slot 3 (the reference's callers pass index % 4, the ABI takes any int)"""
+    L = glc.lib()
+    L.deleteGPUStreams()                                           # the slots start without scratch
+    L.initGPU()
+    buf, bufout = L.initCPUmem(MiB), L.initCPUmem(2 * MiB)
+    in_d, out_d = L.initGPUmem(MiB), L.initGPUmem(2 * MiB)
+    assert buf and bufout and in_d and out_d
+    for (x, want_cand, want), launch, wait in ((_small(51), -1, 3), (_tile_block(0), 7, -1), (_small(52), 3, 7)):
+        C.memmove(buf, x.ctypes.data, x.size)
+        assert L.compression_kernel_wrapper(buf, x.size, bufout, 0, 0, 128, 0, launch, in_d, out_d) == 1
+        assert L.onestream_finish_GPU(wait) == 1
+        cand = _as_u8(bufout, 2 * x.size).copy()
+        assert np.array_equal(cand, want_cand), _first_diff(cand, want_cand)
+        n = C.c_int(0)
+        assert L.aftercompression_wrapper(buf, x.size, bufout, C.byref(n)) == 1
+        got = _as_u8(buf, MiB)[:n.value].copy()
+        assert np.array_equal(got, want), _first_diff(got, want)
+    L.deleteCPUmem(buf); L.deleteCPUmem(bufout); L.deleteGPUmem(in_d); L.deleteGPUmem(out_d)
+    L.deleteGPUStreams()
+
+
+def test_tracking_entry_is_dropped_when_its_slot_is_reused(glc, cuda):
+    """a second launch on slot 0 forgets the first: the first call's candidates are then packed as untracked ones (uploaded
+    and packed again), the second call's come from the slot -- each with its own bytes"""
+    L = glc.lib()
+    L.initGPU()
+    n = 4 * 4096
+    a, b = _small(51), _small(52)
+    buf, bufout_a, bufout_b = L.initCPUmem(n), L.initCPUmem(2 * n), L.initCPUmem(2 * n)
+    in_d, out_d = L.initGPUmem(n), L.initGPUmem(2 * n)
+    assert buf and bufout_a and bufout_b and in_d and out_d
+    for (x, _, _), bufout in ((a, bufout_a), (b, bufout_b)):
+        C.memmove(buf, x.ctypes.data, n)
+        assert L.compression_kernel_wrapper(buf, n, bufout, 0, 0, 128, 0, 0, in_d, out_d) == 1
+        assert L.onestream_finish_GPU(0) == 1
+    for (_, want_cand, want), bufout in ((a, bufout_a), (b, bufout_b)):
+        assert np.array_equal(_as_u8(bufout, 2 * n), want_cand)
+        m = C.c_int(0)
+        assert L.aftercompression_wrapper(buf, n, bufout, C.byref(m)) == 1
+        got = _as_u8(buf, n)[:m.value].copy()
+        assert np.array_equal(got, want), _first_diff(got, want)
+    for p in (buf, bufout_a, bufout_b):
+        L.deleteCPUmem(p)
+    L.deleteGPUmem(in_d); L.deleteGPUmem(out_d)
+    L.deleteGPUStreams()
+
+
+def test_decode_scratch_regrows(glc, cuda):
+    """decompression_kernel_wrapper's cached scratch: a small packed buffer, a 1 MiB one (it grows), the small one again"""
+    L = glc.lib()
+    L.deleteGPUStreams()
+    for x, _, packed in (_small(51), _tile_block(1), _small(51)):
+        buf = np.zeros(L.glcLzssPackStride(x.size), dtype=np.uint8)
+        buf[:packed.size] = packed
+        m = C.c_int(0)
+        assert L.decompression_kernel_wrapper(buf.ctypes.data, packed.size, C.byref(m), 0, 1, 1) == 1
+        assert m.value == x.size and np.array_equal(buf[:x.size], x)
+    L.deleteGPUStreams()
+
+
+def test_file_functions_refuse_cleanly(glc, cuda, tmp_path):
+    """a missing input, a file shorter than a header, a container cut by one byte and an input shorter than one buffer:
+    0, and no output file"""
+    L = glc.lib()
+    x = _tile_block(0)[0]
+    cap = L.culzss_container_bound(MiB)
+    cont = np.zeros(cap, dtype=np.uint8)
+    n = C.c_ulonglong(0)
+    assert L.culzss_container_compress(x.ctypes.data, MiB, cont.ctypes.data, cap, C.byref(n)) == 1
+    (tmp_path / "five.bin").write_bytes(b"12345")
+    (tmp_path / "cut.bin").write_bytes(cont[: n.value - 1].tobytes())
+    (tmp_path / "short.bin").write_bytes(x[: MiB - 1].tobytes())
+    out = tmp_path / "out.bin"
+    path = lambda name: str(tmp_path / name).encode()
+    for fn, name in ((L.culzss_compress_file, "missing.bin"), (L.culzss_decompress_file, "missing.bin"),
+                     (L.culzss_decompress_file, "five.bin"), (L.culzss_decompress_file, "cut.bin"),
+                     (L.culzss_compress_file, "short.bin")):
+        assert fn(path(name), str(out).encode()) == 0, name
+        assert not out.exists(), name
