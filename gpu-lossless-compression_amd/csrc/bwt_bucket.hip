@@ -1136,14 +1136,15 @@ hipError_t fs_build(const SortCall &c, SaScratch &s)
     }
     uint32_t *h_nflag = s.h_max_cnt + HW_FLAGGED;              // pinned, device-mapped: written (with HW_NOT_TEXTLIKE behind it) by the kernel that finishes the pass
     const double units = (double)n * nblk;
-    int pi = s.prof ? s.prof->begin(PROF_FS_HIST, st) : -1;
     // statistics from every 4th 32 KB slice of a block of 512 KiB or more (the pass reads a quarter of the input: 0.27 -> 0.07 ms
     // per GiB)
     const uint32_t nslices = (n + FSH_SLICE - 1) / FSH_SLICE;
     const uint32_t hstep = nslices >= 16 ? 4u : 1u;
-    hipLaunchKernelGGL(k_fs_hist, dim3((nslices + hstep - 1) / hstep, nblk), dim3(256), 0, st, text, text_stride, n,
-                       s.fs_hist, s.fs_dup, hstep);
-    if (pi >= 0) s.prof->end(pi, units, st);
+    {
+        ProfScope ps(s.prof, PROF_FS_HIST, st, units);
+        hipLaunchKernelGGL(k_fs_hist, dim3((nslices + hstep - 1) / hstep, nblk), dim3(256), 0, st, text, text_stride, n,
+                           s.fs_hist, s.fs_dup, hstep);
+    }
     hipLaunchKernelGGL(k_fs_tables, dim3(nblk), dim3(256), 0, st, s.fs_hist, n, s.fs_tab, s.fs_dup, s.fs_flag, text, text_stride,
                        bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax, hstep);
     if (s.skip_tier1) {
@@ -1155,7 +1156,6 @@ hipError_t fs_build(const SortCall &c, SaScratch &s)
     // (The 8-byte suffix words of a block make one round trip through memory between k_fs_part2 and k_fs_sort -- 16 of the
     // encoder's 26 bytes of HBM traffic per input byte when a call's words, 8 MiB per block, are far more than the 256 MB
     // Infinity Cache holds.  The whole call is bucketed, then sorted.)
-    pi = s.prof ? s.prof->begin(PROF_FS_PART, st) : -1;
     // tiles of 4096 suffixes, per workgroup: 4 for a few blocks, 1 for one to three (more workgroups for a block on its own).  Round 5, bench.py
     // `value` on one box, 1024-block batches, stage overlap on: 4 / 8 / 12 / 16 / 24 / 32 / 64 tiles -> 93.1 / 95.1 / 94.7 /
     // 95.1 / 95.6 / 93.8 / 87-94 GB/s (16 and 24 fall into two modes from run to run: 94.3-96.5); the kernel itself 3.0 ->
@@ -1170,32 +1170,35 @@ hipError_t fs_build(const SortCall &c, SaScratch &s)
     // alternating on one box, 6 steps: 100.2 / 101.7 / 102.0 GB/s as it was, 102.3 / 102.9 / 103.0 so (8 tiles per workgroup:
     // 102.3 / 102.5 / 102.7); stages back to back 97.8-99.8 -> 101.2-101.7; the kernel 2.91-3.10 -> 2.67-2.73 ms per GiB.
     // (512 threads x 16 suffixes for the same tile: 3.3 ms.)
-    if (nblk >= 16) {
+    {
+        ProfScope ps(s.prof, PROF_FS_PART, st, units);
+        if (nblk >= 16) {
 #ifndef GLC_FSP2_BT
 #define GLC_FSP2_BT 8192
 #endif
-        constexpr int BT = GLC_FSP2_BT, BN = 1024;
-        const uint32_t tiles = (n + BT - 1) / BT, per = 16;
-        hipLaunchKernelGGL((k_fs_part2<BN, BT / BN, 4>), dim3((tiles + per - 1) / per, nblk), dim3(BN), 0, st, text, text_stride, n, nbl,
-                           s.fs_tab, s.keyA, s.fs_kstride, s.fs_fill, s.fs_flag, s.fs_zero, per);
-    } else {
-        const uint32_t tiles = (n + FSP2_TILE - 1) / FSP2_TILE;
-        // (a call of one to three blocks: ONE tile per workgroup -- 256 workgroups for a block on its own: 17.3 -> 12.0 us of
-        //  a single cudppCompress call's chain, 0.190 -> 0.182 ms per call)
-        const uint32_t per = nblk >= 4 ? FSP2_T : 1u;
-        hipLaunchKernelGGL((k_fs_part2<FSP2_NT, FSP2_TILE / FSP2_NT, GLC_FSP2_WAVES>), dim3((tiles + per - 1) / per, nblk), dim3(FSP2_NT), 0, st,
-                           text, text_stride, n, nbl, s.fs_tab, s.keyA, s.fs_kstride, s.fs_fill, s.fs_flag, s.fs_zero, per);
+            constexpr int BT = GLC_FSP2_BT, BN = 1024;
+            const uint32_t tiles = (n + BT - 1) / BT, per = 16;
+            hipLaunchKernelGGL((k_fs_part2<BN, BT / BN, 4>), dim3((tiles + per - 1) / per, nblk), dim3(BN), 0, st, text, text_stride, n, nbl,
+                               s.fs_tab, s.keyA, s.fs_kstride, s.fs_fill, s.fs_flag, s.fs_zero, per);
+        } else {
+            const uint32_t tiles = (n + FSP2_TILE - 1) / FSP2_TILE;
+            // (a call of one to three blocks: ONE tile per workgroup -- 256 workgroups for a block on its own: 17.3 -> 12.0 us of
+            //  a single cudppCompress call's chain, 0.190 -> 0.182 ms per call)
+            const uint32_t per = nblk >= 4 ? FSP2_T : 1u;
+            hipLaunchKernelGGL((k_fs_part2<FSP2_NT, FSP2_TILE / FSP2_NT, GLC_FSP2_WAVES>), dim3((tiles + per - 1) / per, nblk), dim3(FSP2_NT), 0, st,
+                               text, text_stride, n, nbl, s.fs_tab, s.keyA, s.fs_kstride, s.fs_fill, s.fs_flag, s.fs_zero, per);
+        }
     }
-    if (pi >= 0) s.prof->end(pi, units, st);
     hipLaunchKernelGGL(k_fs_scan, dim3(nblk), dim3(FS_MAXNB), 0, st, s.fs_fill, s.fs_base, s.fs_flag, (const uint32_t *)nullptr);
-    pi = s.prof ? s.prof->begin(PROF_FS_SORT, st) : -1;
-    if (sa_out || !bwt_out || !d_index)                        // the suffix array itself is asked for: the kernel that writes it
-        hipLaunchKernelGGL(k_fs_sort, dim3(nb, nblk), dim3(FSS_NT), 0, st, n, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
-                           bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt);
-    else
-        hipLaunchKernelGGL(k_fs_sort_bwt, dim3(nb, nblk), dim3(FSS_NT), 0, st, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
-                           bwt_out, bwt_stride, d_index, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt, s.fs_zero);
-    if (pi >= 0) s.prof->end(pi, units, st);
+    {
+        ProfScope ps(s.prof, PROF_FS_SORT, st, units);
+        if (sa_out || !bwt_out || !d_index)                    // the suffix array itself is asked for: the kernel that writes it
+            hipLaunchKernelGGL(k_fs_sort, dim3(nb, nblk), dim3(FSS_NT), 0, st, n, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
+                               bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt);
+        else
+            hipLaunchKernelGGL(k_fs_sort_bwt, dim3(nb, nblk), dim3(FSS_NT), 0, st, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
+                               bwt_out, bwt_stride, d_index, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt, s.fs_zero);
+    }
     hipLaunchKernelGGL(k_fs_ties, dim3(24, nblk), dim3(256), 0, st, text, text_stride, n, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt,
                        s.fs_flag, bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax);
     hipLaunchKernelGGL(k_fs_finish, dim3((nblk + 255) / 256), dim3(256), 0, st, s.fs_flag, n, nblk, s.fs_lcnt, s.fs_nflag,

@@ -1247,21 +1247,22 @@ static hipError_t radix_sort(hipStream_t st, uint64_t *&cur, uint64_t *&alt, con
         GLC_TRY(hipMemsetAsync(s.ticket, 0, (size_t)nblk * 4, st));
         // profiled kernel = k_rs_onesweep<8,false> (16 algorithmic bytes per live suffix); the text-sourced
         // first pass of round 0 is a different kernel (1 R + 8 W) and is left out
-        const int pi = (profile && s.prof && pp.bits[p] == 8 && !(p == 0 && src)) ? s.prof->begin(PROF_RS_ONESWEEP8, st) : -1;
-        dim3 g(nblk, rs_tiles);
-        if (pp.bits[p] == 8 && p == 0 && src)
-            hipLaunchKernelGGL((k_rs_onesweep<8, true>), g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p],
-                               s.tile_hist, s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX,
-                               (uint32_t)(RS_MAXPASS * SA_MAXRADIX), s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR, *src);
-        else if (pp.bits[p] == 8)
-            hipLaunchKernelGGL(k_rs_onesweep<8>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
-                               s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
-                               s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
-        else
-            hipLaunchKernelGGL(k_rs_onesweep<9>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
-                               s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
-                               s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
-        if (pi >= 0) s.prof->end(pi, live_total, st);
+        {
+            ProfScope ps(profile && pp.bits[p] == 8 && !(p == 0 && src) ? s.prof : nullptr, PROF_RS_ONESWEEP8, st, live_total);
+            dim3 g(nblk, rs_tiles);
+            if (pp.bits[p] == 8 && p == 0 && src)
+                hipLaunchKernelGGL((k_rs_onesweep<8, true>), g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p],
+                                   s.tile_hist, s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX,
+                                   (uint32_t)(RS_MAXPASS * SA_MAXRADIX), s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR, *src);
+            else if (pp.bits[p] == 8)
+                hipLaunchKernelGGL(k_rs_onesweep<8>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
+                                   s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
+                                   s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
+            else
+                hipLaunchKernelGGL(k_rs_onesweep<9>, g, dim3(RS_NT), 0, st, cur, alt, cnt, nfixed, pp.shift[p], s.tile_hist,
+                                   s.ticket, s.epoch, s.digit_base + p * SA_MAXRADIX, (uint32_t)(RS_MAXPASS * SA_MAXRADIX),
+                                   s.nmax, s.rs_tiles, s.d_max_cnt + RD_ERROR);
+        }
         uint64_t *x = cur; cur = alt; alt = x;
     }
     return hipGetLastError();

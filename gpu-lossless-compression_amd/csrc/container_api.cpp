@@ -257,8 +257,8 @@ struct Encoder {
         hk.pack_only = f.only;
         hk.before_offsets = [&](hipStream_t s2) { return ct_enc_kind(s2, f, nb, blk_len, state); };
         hk.after_pack = [&](hipStream_t s2) { return ct_enc_after_pack(s2, f, d_in, orig, nb, blk_len, out, cap, state); };
-        return plan_compress_hooked(P.h, d_in, f.bwt, f.hist, f.enc_off, nsub, f.size, reinterpret_cast<unsigned int *>(out),
-                                    (size_t)(cap / 4), f.boff, f.start, blk_len, nb, hk);
+        return plan_compress_hooked(P.h, CompressCall{d_in, f.bwt, f.hist, f.enc_off, nsub, f.size, reinterpret_cast<uint32_t *>(out), 0,
+                                                      blk_len, nb, f.boff, f.start, (size_t)(cap / 4)}, hk);
     }
 
     // the order-0 codec's frame, wholly on the plan's stream: tables (and with them every record's size) -> kinds -> payload

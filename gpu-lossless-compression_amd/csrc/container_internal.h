@@ -140,11 +140,7 @@ struct ContainerHooks {
     std::function<hipError_t(hipStream_t)> after_pack;       // behind the packer, on the same stream
 };
 // glcCompressBatchCompact with the hooks above
-CUDPPResult plan_compress_hooked(CUDPPHandle plan, const unsigned char *d_in, int *d_bwtIndex, unsigned int *d_hist,
-                                 unsigned int *d_encodeOffset, size_t offsetStride, unsigned int *d_size,
-                                 unsigned int *d_compact, size_t capacityWords, unsigned long long *d_blockOffsets,
-                                 const unsigned long long *d_startOffset, size_t numElements, size_t numBlocks,
-                                 ContainerHooks &hk);
+CUDPPResult plan_compress_hooked(CUDPPHandle plan, CompressCall c, ContainerHooks &hk);
 // 1 = a COMPRESS plan; n, rows, its stream, and the parity of its next compress call (which half of double-buffered scratch
 // that call may reuse once the plan's own ordering lets it)
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);

@@ -51,20 +51,61 @@ struct PlanBase {
         if (h_status) (void)hipHostFree(h_status);
         for (auto &e : ev) if (e) (void)hipEventDestroy(e);
     }
+    // what the entry points ask of a plan whatever its algorithm
+    virtual SaScratch *sorter() { return nullptr; }            // the suffix sorter's scratch (MTF plans have none)
+    virtual void join_side() {}                                // the plan's stream waits for everything on its side stream (COMPRESS)
+    virtual void wire_prof() = 0;                              // point the stage scratches at the plan's live profile
+    virtual hipEvent_t side_span_start() { return nullptr; }   // stages on two streams: the event their second span starts at
 };
 
-struct SaPlan : PlanBase {                       // CUDPPSaPlan (cudpp_plan.h:289-305)
+struct SortPlan : PlanBase {                     // CUDPPSaPlan and CUDPPBwtPlan (cudpp_plan.h:289-305, 343-356)
     SaScratch sa;
-    ~SaPlan() override { sa_scratch_free(sa); }
-};
-struct BwtPlan : PlanBase {                      // CUDPPBwtPlan (cudpp_plan.h:343-356)
-    SaScratch sa;
-    ~BwtPlan() override { sa_scratch_free(sa); }
+    ~SortPlan() override { sa_scratch_free(sa); }
+    SaScratch *sorter() override { return &sa; }
+    void wire_prof() override { sa.prof = &prof; }
 };
 struct MtfPlan : PlanBase {                      // CUDPPMtfPlan (cudpp_plan.h:358-369)
     MtfScratch mtf;
     ~MtfPlan() override { mtf_scratch_free(mtf); }
+    void wire_prof() override { mtf.prof = &prof; }
 };
+
+// A double-buffered half changing hands between the calls of one direction: call i works on half i & 1, and may start on
+// it once call i - 2 has released it.  (The count runs on when the mode changes; only the releases are forgotten.)
+struct HandOver {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool valid[2] = {false, false};
+    uint32_t calls = 0;
+    uint32_t next() const { return calls & 1u; }               // the half the next call takes
+    uint32_t take() { return calls++ & 1u; }
+    void wait_free(uint32_t k, hipStream_t s) const { if (valid[k]) (void)hipStreamWaitEvent(s, ev[k], 0); }
+    void release(uint32_t k, hipStream_t s) { (void)hipEventRecord(ev[k], s); valid[k] = true; }
+    void reset() { valid[0] = valid[1] = false; }
+};
+
+// Device memory a plan keeps for its container path: grown on demand, never shrunk, freed with the plan
+struct GrowBuf {
+    void *mem = nullptr;
+    size_t bytes = 0;
+    hipError_t grow(PlanBase &p, size_t want, uint8_t **out)
+    {
+        if (want > bytes) {
+            if (mem) {                                         // (growing: whatever still uses the old one finishes first)
+                p.join_side();
+                (void)hipStreamSynchronize(p.stream);
+                (void)hipFree(mem);
+                mem = nullptr; bytes = 0;
+            }
+            const hipError_t e = hipMalloc(&mem, want);
+            if (e != hipSuccess) { mem = nullptr; return e; }
+            bytes = want;
+        }
+        *out = static_cast<uint8_t *>(mem);
+        return hipSuccess;
+    }
+    ~GrowBuf() { if (mem) (void)hipFree(mem); }
+};
+
 struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_plan.h:307-341)
     SaScratch sa;
     MtfScratch mtf;
@@ -76,21 +117,21 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     bool pipelined = false;
     uint8_t *d_bwt2 = nullptr;
     hipStream_t side = nullptr;
-    hipEvent_t ev_in = nullptr, ev_sorted[2] = {nullptr, nullptr}, ev_released[2] = {nullptr, nullptr}, ev_s2 = nullptr;
-    bool released_valid[2] = {false, false};
-    uint32_t calls = 0;
-    hipEvent_t ev_dec_a[2] = {nullptr, nullptr}, ev_dec_released[2] = {nullptr, nullptr};
-    bool dec_released_valid[2] = {false, false};
-    uint32_t dec_calls = 0;
+    hipEvent_t ev_in = nullptr, ev_sorted[2] = {nullptr, nullptr}, ev_dec_a[2] = {nullptr, nullptr}, ev_s2 = nullptr;
+    HandOver enc_half, dec_half;                 // d_bwt / d_bwt2 between compress calls, dec.bwt / dec.bwt2 between decompress calls
+    // every event of the side stream: pipeline_init creates them in this order, the destructor destroys them (ev_s2, the
+    // last, is the one that is read for a time)
+    hipEvent_t *const side_events[10] = {&ev_in, &ev_sorted[0], &ev_sorted[1], &enc_half.ev[0], &enc_half.ev[1],
+                                         &ev_dec_a[0], &ev_dec_a[1], &dec_half.ev[0], &dec_half.ev[1], &ev_s2};
     bool side_busy = false;                      // side-stream work issued since the last join
     // container settings (glcPlanSetContainerShuffle / Delta / Codec) and the filter's frame staging both directions share
     CtSettings ct;
-    void *ct_stage[2] = {nullptr, nullptr};
-    size_t ct_stage_bytes[2] = {0, 0};
-    // the order-0 container codec's scratch: [0] the encoder's, [1] the decoder's
-    void *ct_codec_mem[2] = {nullptr, nullptr};
-    size_t ct_codec_bytes[2] = {0, 0};
-    void join_side()                             // make the plan's stream wait for everything on the side stream
+    GrowBuf ct_stage[2];
+    GrowBuf ct_codec[2];                         // the order-0 container codec's scratch: [0] the encoder's, [1] the decoder's
+    SaScratch *sorter() override { return &sa; }
+    void wire_prof() override { sa.prof = &prof; mtf.prof = &prof; huff.prof = &prof; dec.prof = &prof; }
+    hipEvent_t side_span_start() override { return pipelined ? ev_s2 : nullptr; }
+    void join_side() override
     {
         if (!side || !side_busy) return;
         (void)hipEventRecord(ev_in, side);
@@ -108,24 +149,18 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
             e = hipStreamCreateWithPriority(&side, hipStreamNonBlocking, least);
         }
-        hipEvent_t *evs[] = {&ev_in, &ev_sorted[0], &ev_sorted[1], &ev_released[0], &ev_released[1],
-                             &ev_dec_a[0], &ev_dec_a[1], &ev_dec_released[0], &ev_dec_released[1]};
-        for (auto pe : evs) if (e == hipSuccess) e = hipEventCreateWithFlags(pe, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreate(&ev_s2);
+        for (hipEvent_t *pe : side_events)
+            if (e == hipSuccess) e = pe == &ev_s2 ? hipEventCreate(pe) : hipEventCreateWithFlags(pe, hipEventDisableTiming);
         return e;
     }
     ~CompressPlan() override
     {
         if (side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
-        hipEvent_t evs[] = {ev_in, ev_sorted[0], ev_sorted[1], ev_released[0], ev_released[1], ev_s2,
-                            ev_dec_a[0], ev_dec_a[1], ev_dec_released[0], ev_dec_released[1]};
-        for (auto e : evs) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t *pe : side_events) if (*pe) (void)hipEventDestroy(*pe);
         sa_scratch_free(sa); mtf_scratch_free(mtf); huff_scratch_free(huff); decode_scratch_free(dec);
         if (d_bwt) (void)hipFree(d_bwt);
         if (d_bwt2) (void)hipFree(d_bwt2);
         if (d_mtf) (void)hipFree(d_mtf);
-        for (auto q : ct_stage) if (q) (void)hipFree(q);
-        for (auto q : ct_codec_mem) if (q) (void)hipFree(q);
     }
 };
 
@@ -158,23 +193,46 @@ struct StageTimer {
     void done() { if (p->timing) p->ev_valid = true; }
 };
 
-SaScratch *sa_of(PlanBase *p)
+// glcPlanLastTiming's four spans, read from the stage events once the plan's streams are idle.  Stages that ran on two
+// streams report their own spans: the second starts at the side stream's event, and the total is the sum of the three.
+void read_spans(PlanBase *p)
 {
-    switch (p->config.algorithm) {
-    case CUDPP_COMPRESS: return &static_cast<CompressPlan *>(p)->sa;
-    case CUDPP_BWT: return &static_cast<BwtPlan *>(p)->sa;
-    case CUDPP_SA: return &static_cast<SaPlan *>(p)->sa;
-    default: return nullptr;
-    }
+    const hipEvent_t s2 = p->side_span_start();
+    (void)hipEventElapsedTime(&p->last_ms[0], p->ev[0], p->ev[1]);
+    (void)hipEventElapsedTime(&p->last_ms[1], s2 ? s2 : p->ev[1], p->ev[2]);
+    (void)hipEventElapsedTime(&p->last_ms[2], p->ev[2], p->ev[3]);
+    if (s2) p->last_ms[3] = p->last_ms[0] + p->last_ms[1] + p->last_ms[2];
+    else (void)hipEventElapsedTime(&p->last_ms[3], p->ev[0], p->ev[3]);
 }
 
-// the stats getters and glcPlanSetChains: handle, output pointer and plan type checked in one place (a null output is
-// reported as an invalid handle, as it always was), then f on the plan's sorter scratch
+// Entry check of the plan utilities: the handle and, where the entry has one, its output pointer (a null output is
+// reported as an invalid handle, as it always was).  Null: the entry answers CUDPP_ERROR_INVALID_HANDLE.
+PlanBase *plan_of(CUDPPHandle planHandle, bool has_out = true)
+{
+    return planHandle == 0 || planHandle == CUDPP_INVALID_HANDLE || !has_out ? nullptr : plan_from<PlanBase>(planHandle);
+}
+
+// Entry check of the batch entries, in the order the codes are documented in: handle, algorithm, datatype (ANY_DATATYPE: the
+// entry does not look at it -- glcHuffmanEncodeBatch and the two decompress entries, which take their symbols as bytes
+// whatever the plan was made for), then the call's sizes against the plan's.  Null: the entry answers `why`.
+enum DatatypeCheck { ANY_DATATYPE, UCHAR_ONLY };
+template <class T>
+T *batch_plan(CUDPPHandle planHandle, CUDPPAlgorithm algorithm, DatatypeCheck dt, size_t numElements, size_t numBlocks, CUDPPResult &why)
+{
+    PlanBase *p = plan_of(planHandle);
+    why = !p ? CUDPP_ERROR_INVALID_HANDLE
+        : p->config.algorithm != algorithm ? CUDPP_ERROR_INVALID_PLAN
+        : (dt == UCHAR_ONLY && p->config.datatype != CUDPP_UCHAR) || numElements == 0 || numElements > p->n || numBlocks == 0 ||
+          numBlocks > p->rows ? CUDPP_ERROR_ILLEGAL_CONFIGURATION : CUDPP_SUCCESS;
+    return why == CUDPP_SUCCESS ? static_cast<T *>(p) : nullptr;
+}
+
+// the stats getters and glcPlanSetChains: the utilities' check, then the plan type, then f on the plan's sorter scratch
 template <class F> CUDPPResult with_sorter(CUDPPHandle planHandle, bool has_out, F f)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !has_out) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
+    PlanBase *p = plan_of(planHandle, has_out);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = p->sorter();
     if (!s) return CUDPP_ERROR_INVALID_PLAN;
     f(*s);
     return CUDPP_SUCCESS;
@@ -227,17 +285,9 @@ CUDPPResult cudppPlan(const CUDPPHandle cudppHandle, CUDPPHandle *planHandle, CU
         if (e == hipSuccess) e = hipMalloc((void **)&p->d_mtf, n * rows);
         break;
     }
-    case CUDPP_BWT: {
+    case CUDPP_BWT: case CUDPP_SA: {
         if (n > MAX_BLOCK_ELEMS) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-        BwtPlan *p = new (std::nothrow) BwtPlan();
-        if (!p) return CUDPP_ERROR_UNKNOWN;
-        plan = p;
-        e = sa_scratch_alloc(p->sa, (uint32_t)n, (uint32_t)rows);
-        break;
-    }
-    case CUDPP_SA: {
-        if (n > MAX_BLOCK_ELEMS) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-        SaPlan *p = new (std::nothrow) SaPlan();
+        SortPlan *p = new (std::nothrow) SortPlan();
         if (!p) return CUDPP_ERROR_UNKNOWN;
         plan = p;
         e = sa_scratch_alloc(p->sa, (uint32_t)n, (uint32_t)rows);
@@ -280,37 +330,30 @@ CUDPPResult cudppDestroyPlan(CUDPPHandle planHandle)
 // --------------------------------------------------------------------------
 // batched entry points
 // --------------------------------------------------------------------------
-// One body for the two output layouts.  Strided (d_blockOffsets == nullptr): block b's words at d_compressed +
-// b * compressedStrideWords, the reference's layout per block.  Compact: block b's words at d_compressed +
-// d_blockOffsets[b], the blocks back to back from *d_startOffset on -- the sizes are known before anything is packed
+// One body for the two output layouts of a CompressCall.  Strided (c.block_off == nullptr): block b's words at c.out +
+// b * c.out_stride, the reference's layout per block.  Compact: block b's words at c.out +
+// c.block_off[b], the blocks back to back from *c.start on -- the sizes are known before anything is packed
 // (k_huff_build), so the packer writes every block where it ends up and no copy pass follows.  In that mode the packer
 // runs once, after the host knows that no block's size can still change (the sorter's tiers are through).
-static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d_uncompressed, int *d_bwtIndex,
-                                  unsigned int *d_hist, unsigned int *d_encodeOffset, size_t offsetStride,
-                                  unsigned int *d_compressedSize, unsigned int *d_compressed,
-                                  size_t compressedStrideWords, size_t numElements, size_t numBlocks,
-                                  unsigned long long *d_blockOffsets, const unsigned long long *d_startOffset,
-                                  size_t capacityWords, ContainerHooks *hk = nullptr)
+static CUDPPResult compress_batch(CUDPPHandle planHandle, const CompressCall &c)
 {
-    // hk (the container path, compact layout only): a status word of its own -- a block whose sub-block overflows becomes a raw
+    // c.hooks (the container path, compact layout only): a status word of its own -- a block whose sub-block overflows becomes a raw
     // record there instead of failing the call --, its kernels before the payload offsets and behind the packer, and the
     // packer's block mask
-    const bool compact = d_blockOffsets != nullptr;
-    CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
-    if (p->config.datatype != CUDPP_UCHAR) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const uint32_t n = (uint32_t)numElements, nb = (uint32_t)numBlocks;
+    const ContainerHooks *const hk = c.hooks;
+    const bool compact = c.compact();
+    CUDPPResult why;
+    CompressPlan *p = batch_plan<CompressPlan>(planHandle, CUDPP_COMPRESS, UCHAR_ONLY, c.n, c.nblk, why);
+    if (!p) return why;
+    const uint32_t n = (uint32_t)c.n, nb = (uint32_t)c.nblk;
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    if (offsetStride < nsub) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (c.off_stride < nsub) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     hipStream_t st = p->stream;
     StageTimer tm(p);
     hipError_t e = hipSuccess;
     uint32_t *const status = hk ? hk->status : p->d_status;
     uint8_t *bwt = p->d_bwt;
-    const uint32_t k = p->calls++ & 1u;
+    const uint32_t k = p->enc_half.take();
     hipStream_t s2 = st;                                       // stream of the MTF + Huffman stages
     if (p->pipelined) {
         // The sort stays on the plan's stream (inputs keep their stream order).  MTF + Huffman move to the side
@@ -319,7 +362,7 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
         e = p->pipeline_init();
         if (e != hipSuccess) return hip_result(e);
         bwt = k ? p->d_bwt2 : p->d_bwt;
-        if (p->released_valid[k]) (void)hipStreamWaitEvent(st, p->ev_released[k], 0);   // this BWT half is free again
+        p->enc_half.wait_free(k, st);                          // this BWT half is free again
         s2 = p->side;
     }
     // The stages after the sort are queued BEFORE the host waits for the sorter's one readback (how many blocks the
@@ -327,7 +370,7 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
     // the next call.  In the rare batch with flagged blocks they run again on the corrected BWT.
     tm.mark(0);
     p->sa.parity = k;
-    const SortCall sort{st, d_uncompressed, n, n, nb, bwt, p->n, d_bwtIndex};
+    const SortCall sort{st, c.in, n, n, nb, bwt, p->n, c.bwt_index};
     e = sa_build_begin(sort, p->sa);
     tm.mark(1);
     // MTF + Huffman of the blocks of `only` (all if null) on `stream`, behind whatever error `err` already holds
@@ -335,11 +378,11 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
         if (err == hipSuccess) err = mtf_forward(stream, bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, p->huff.sub_hist, only, skewed);
         if (p->timing) (void)hipEventRecord(p->ev[2], stream);
         // (compact layout: a block has no slot of its own to overflow -- the array's capacity is checked with the offsets)
-        if (err == hipSuccess) err = huff_build(stream, n, nb, p->huff, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                                                compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : compressedStrideWords, status,
+        if (err == hipSuccess) err = huff_build(stream, n, nb, p->huff, c.hist, c.enc_off, c.off_stride, c.size,
+                                                compact ? (size_t)(HUFF_MAX_WORDS + 1) * nsub : c.out_stride, status,
                                                 redo_flag, only);
-        if (err == hipSuccess && !compact) err = huff_pack(stream, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride,
-                                                           d_compressed, compressedStrideWords, only);
+        if (err == hipSuccess && !compact) err = huff_pack(stream, p->d_mtf, p->n, n, nb, p->huff, c.enc_off, c.off_stride,
+                                                           c.out, c.out_stride, only);
         return err;
     };
     auto after_sort = [&](const uint32_t *redo_flag, const uint32_t *only, bool skewed) {
@@ -372,14 +415,14 @@ static CUDPPResult compress_batch(CUDPPHandle planHandle, const unsigned char *d
     }
     if (e == hipSuccess && compact) {
         if (hk && hk->before_offsets) e = hk->before_offsets(s2);
-        if (e == hipSuccess) e = huff_block_offsets(s2, d_compressedSize, nb, d_blockOffsets, d_startOffset, capacityWords, status);
-        if (e == hipSuccess) e = huff_pack(s2, p->d_mtf, p->n, n, nb, p->huff, d_encodeOffset, offsetStride, d_compressed, 0,
-                                           hk ? hk->pack_only : nullptr, d_blockOffsets, capacityWords);
+        if (e == hipSuccess) e = huff_block_offsets(s2, c.size, nb, c.block_off, c.start, c.capacity, status);
+        if (e == hipSuccess) e = huff_pack(s2, p->d_mtf, p->n, n, nb, p->huff, c.enc_off, c.off_stride, c.out, 0,
+                                           hk ? hk->pack_only : nullptr, c.block_off, c.capacity);
         if (e == hipSuccess && hk && hk->after_pack) e = hk->after_pack(s2);
         if (p->timing) (void)hipEventRecord(p->ev[3], s2);
     }
     tm.done();
-    if (p->pipelined) { (void)hipEventRecord(p->ev_released[k], s2); p->released_valid[k] = true; p->side_busy = true; }
+    if (p->pipelined) { p->enc_half.release(k, s2); p->side_busy = true; }
     return hip_result(e);
 }
 
@@ -388,8 +431,8 @@ CUDPPResult glcCompressBatch(CUDPPHandle planHandle, const unsigned char *d_unco
                              unsigned int *d_compressedSize, unsigned int *d_compressed,
                              size_t compressedStrideWords, size_t numElements, size_t numBlocks)
 {
-    return compress_batch(planHandle, d_uncompressed, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                          d_compressed, compressedStrideWords, numElements, numBlocks, nullptr, nullptr, 0);
+    return compress_batch(planHandle, CompressCall{d_uncompressed, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
+                                                   d_compressed, compressedStrideWords, numElements, numBlocks});
 }
 
 CUDPPResult glcCompressBatchCompact(CUDPPHandle planHandle, const unsigned char *d_uncompressed, int *d_bwtIndex,
@@ -399,8 +442,8 @@ CUDPPResult glcCompressBatchCompact(CUDPPHandle planHandle, const unsigned char 
                                     size_t numElements, size_t numBlocks)
 {
     if (!d_blockOffsets || !d_compact) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return compress_batch(planHandle, d_uncompressed, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
-                          d_compact, 0, numElements, numBlocks, d_blockOffsets, d_startOffset, capacityWords);
+    return compress_batch(planHandle, CompressCall{d_uncompressed, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressedSize,
+                                                   d_compact, 0, numElements, numBlocks, d_blockOffsets, d_startOffset, capacityWords});
 }
 
 // the Huffman half of cudppCompress on its own (histogram, tree + codes, bit packer, offsets: rows a5-a8)
@@ -409,11 +452,9 @@ CUDPPResult glcHuffmanEncodeBatch(CUDPPHandle planHandle, const unsigned char *d
                                   unsigned int *d_compressed, size_t compressedStrideWords, size_t numElements,
                                   size_t numBlocks)
 {
-    CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
-    if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CUDPPResult why;
+    CompressPlan *p = batch_plan<CompressPlan>(planHandle, CUDPP_COMPRESS, ANY_DATATYPE, numElements, numBlocks, why);
+    if (!p) return why;
     const uint32_t n = (uint32_t)numElements, nb = (uint32_t)numBlocks;
     if (offsetStride < (n + HUFF_BLOCK - 1) / HUFF_BLOCK) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     p->join_side();
@@ -428,27 +469,25 @@ CUDPPResult glcHuffmanEncodeBatch(CUDPPHandle planHandle, const unsigned char *d
 
 CUDPPResult glcPlanSetPipelining(CUDPPHandle planHandle, int on)
 {
-    CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
+    PlanBase *base = plan_of(planHandle);
+    if (!base) return CUDPP_ERROR_INVALID_HANDLE;
+    if (base->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
+    CompressPlan *p = static_cast<CompressPlan *>(base);
     p->join_side();
     if (p->side) (void)hipStreamSynchronize(p->side);
     (void)hipStreamSynchronize(p->stream);
     p->pipelined = on != 0;
-    p->released_valid[0] = p->released_valid[1] = false;
-    p->dec_released_valid[0] = p->dec_released_valid[1] = false;
+    p->enc_half.reset();
+    p->dec_half.reset();
     return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcBwtBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsigned char *d_out, int *d_index,
                         size_t numElements, size_t numBlocks)
 {
-    BwtPlan *p = plan_from<BwtPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_BWT) return CUDPP_ERROR_INVALID_PLAN;
-    if (p->config.datatype != CUDPP_UCHAR) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CUDPPResult why;
+    SortPlan *p = batch_plan<SortPlan>(planHandle, CUDPP_BWT, UCHAR_ONLY, numElements, numBlocks, why);
+    if (!p) return why;
     const uint32_t n = (uint32_t)numElements, nb = (uint32_t)numBlocks;
     return hip_result(sa_build(SortCall{p->stream, d_in, n, n, nb, d_out, n, d_index}, p->sa));
 }
@@ -456,51 +495,37 @@ CUDPPResult glcBwtBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsig
 CUDPPResult glcMtfBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsigned char *d_out,
                         size_t numElements, size_t numBlocks)
 {
-    MtfPlan *p = plan_from<MtfPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_MTF) return CUDPP_ERROR_INVALID_PLAN;
-    if (p->config.datatype != CUDPP_UCHAR) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CUDPPResult why;
+    MtfPlan *p = batch_plan<MtfPlan>(planHandle, CUDPP_MTF, UCHAR_ONLY, numElements, numBlocks, why);
+    if (!p) return why;
     const uint32_t n = (uint32_t)numElements, nb = (uint32_t)numBlocks;
     return hip_result(mtf_forward(p->stream, d_in, n, n, nb, d_out, n, p->mtf, nullptr));
 }
 
-static CUDPPResult decompress_batch(CUDPPHandle planHandle, const int *d_bwtIndex, const unsigned int *d_hist,
-                                    const unsigned int *d_encodeOffset, size_t offsetStride,
-                                    const unsigned int *d_compressed, size_t compressedStrideWords,
-                                    unsigned char *d_out, size_t numElements, size_t numBlocks,
-                                    const unsigned long long *d_blockOffsets)
+static CUDPPResult decompress_batch(CUDPPHandle planHandle, const DecodeCall &c)
 {
-    CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
-    if (numElements == 0 || numElements > p->n || numBlocks == 0 || numBlocks > p->rows)
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CUDPPResult why;
+    CompressPlan *p = batch_plan<CompressPlan>(planHandle, CUDPP_COMPRESS, ANY_DATATYPE, c.n, c.nblk, why);
+    if (!p) return why;
     if (!p->dec.lf) {
         hipError_t e = decode_scratch_alloc(p->dec, p->n, p->rows);
         if (e != hipSuccess) return hip_result(e);
     }
-    if (!p->pipelined)
-        return hip_result(decode_blocks(p->stream, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressed,
-                                        compressedStrideWords, d_out, (uint32_t)numElements, (uint32_t)numBlocks,
-                                        p->dec, p->mtf, p->d_status, d_blockOffsets));
+    if (!p->pipelined) return hip_result(decode_blocks(p->stream, c, p->dec, p->d_status));
     // pipelined: Huffman + inverse MTF on the plan's stream (inputs keep their stream order), the inverse
     // BWT -- a memory-latency-bound walk -- on the side stream, where it overlaps stage A of the next call.
     // d_out is complete after glcPlanSynchronize / a device synchronize.
     hipError_t e = p->pipeline_init();
     if (e != hipSuccess) return hip_result(e);
     hipStream_t st = p->stream;
-    const uint32_t k = p->dec_calls++ & 1u;
+    const uint32_t k = p->dec_half.take();
     uint8_t *bwt = k ? p->dec.bwt2 : p->dec.bwt;
-    if (p->dec_released_valid[k]) (void)hipStreamWaitEvent(st, p->ev_dec_released[k], 0);
-    e = decode_stage_a(st, d_hist, d_encodeOffset, offsetStride, d_compressed, compressedStrideWords,
-                       (uint32_t)numElements, (uint32_t)numBlocks, p->dec, bwt, p->d_status, d_blockOffsets);
+    p->dec_half.wait_free(k, st);
+    e = decode_stage_a(st, c, p->dec, bwt, p->d_status);
     (void)hipEventRecord(p->ev_dec_a[k], st);
     (void)hipStreamWaitEvent(p->side, p->ev_dec_a[k], 0);
-    if (e == hipSuccess) e = decode_stage_b(p->side, d_bwtIndex, bwt, d_out, (uint32_t)numElements, (uint32_t)numBlocks, p->dec, p->d_status);
-    (void)hipEventRecord(p->ev_dec_released[k], p->side);
-    p->dec_released_valid[k] = true;
+    if (e == hipSuccess) e = decode_stage_b(p->side, c, bwt, p->dec, p->d_status);
+    p->dec_half.release(k, p->side);
     p->side_busy = true;
     return hip_result(e);
 }
@@ -510,8 +535,8 @@ CUDPPResult glcDecompressBatch(CUDPPHandle planHandle, const int *d_bwtIndex, co
                                const unsigned int *d_compressed, size_t compressedStrideWords,
                                unsigned char *d_out, size_t numElements, size_t numBlocks)
 {
-    return decompress_batch(planHandle, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressed,
-                            compressedStrideWords, d_out, numElements, numBlocks, nullptr);
+    return decompress_batch(planHandle, DecodeCall{d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compressed,
+                                                   compressedStrideWords, d_out, numElements, numBlocks});
 }
 
 CUDPPResult glcDecompressBatchCompact(CUDPPHandle planHandle, const int *d_bwtIndex, const unsigned int *d_hist,
@@ -521,8 +546,8 @@ CUDPPResult glcDecompressBatchCompact(CUDPPHandle planHandle, const int *d_bwtIn
                                       size_t numElements, size_t numBlocks)
 {
     if (!d_blockOffsets) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return decompress_batch(planHandle, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compact, compactWords, d_out,
-                            numElements, numBlocks, d_blockOffsets);
+    return decompress_batch(planHandle, DecodeCall{d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compact, compactWords, d_out,
+                                                   numElements, numBlocks, d_blockOffsets});
 }
 
 // --------------------------------------------------------------------------
@@ -557,11 +582,9 @@ CUDPPResult cudppMoveToFrontTransform(CUDPPHandle planHandle, unsigned char *d_i
 CUDPPResult cudppSuffixArray(CUDPPHandle planHandle, unsigned char *d_str, unsigned int *d_keys_sa,
                              size_t numElements)
 {
-    SaPlan *p = plan_from<SaPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm != CUDPP_SA) return CUDPP_ERROR_INVALID_PLAN;
-    if (p->config.datatype != CUDPP_UCHAR) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (numElements == 0 || numElements > p->n) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CUDPPResult why;
+    SortPlan *p = batch_plan<SortPlan>(planHandle, CUDPP_SA, UCHAR_ONLY, numElements, 1, why);   // (one block: a plan has a row at least)
+    if (!p) return why;
     const uint32_t n = (uint32_t)numElements;
     hipError_t e = sa_build(SortCall{p->stream, d_str, n, n, 1, nullptr, 0, nullptr}, p->sa);
     if (e == hipSuccess) e = sa_export(p->stream, p->sa.sa, n, d_keys_sa);
@@ -573,8 +596,8 @@ CUDPPResult cudppSuffixArray(CUDPPHandle planHandle, unsigned char *d_str, unsig
 // --------------------------------------------------------------------------
 CUDPPResult glcPlanSetStream(CUDPPHandle planHandle, void *hipStream)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     p->stream = reinterpret_cast<hipStream_t>(hipStream);
     return CUDPP_SUCCESS;
 }
@@ -587,52 +610,36 @@ __global__ void k_status_fetch(uint32_t *__restrict__ d_status, uint32_t *__rest
 
 CUDPPResult glcPlanSynchronize(CUDPPHandle planHandle)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (p->config.algorithm == CUDPP_COMPRESS) static_cast<CompressPlan *>(p)->join_side();
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
+    p->join_side();
     // status word: fetched into pinned memory and cleared by ONE small kernel (a copy command + a fill command were two more
     // ~5 us links in the chain a cudppCompress caller waits for)
     hipLaunchKernelGGL(k_status_fetch, dim3(1), dim3(1), 0, p->stream, p->d_status, p->h_status);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
     if (e != hipSuccess) return CUDPP_ERROR_UNKNOWN;
-    if (p->timing && p->ev_valid) {
-        (void)hipEventElapsedTime(&p->last_ms[0], p->ev[0], p->ev[1]);
-        CompressPlan *cp = p->config.algorithm == CUDPP_COMPRESS ? static_cast<CompressPlan *>(p) : nullptr;
-        if (cp && cp->pipelined && cp->ev_s2) {                 // stages ran on two streams: report their own spans
-            (void)hipEventElapsedTime(&p->last_ms[1], cp->ev_s2, p->ev[2]);
-            (void)hipEventElapsedTime(&p->last_ms[2], p->ev[2], p->ev[3]);
-            p->last_ms[3] = p->last_ms[0] + p->last_ms[1] + p->last_ms[2];
-        } else {
-            (void)hipEventElapsedTime(&p->last_ms[1], p->ev[1], p->ev[2]);
-            (void)hipEventElapsedTime(&p->last_ms[2], p->ev[2], p->ev[3]);
-            (void)hipEventElapsedTime(&p->last_ms[3], p->ev[0], p->ev[3]);
-        }
-    }
+    if (p->timing && p->ev_valid) read_spans(p);
     return *p->h_status ? CUDPP_ERROR_UNKNOWN : CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanEnableTiming(CUDPPHandle planHandle, int enable)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     p->timing = enable != 0;
     p->ev_valid = false;
     if (!p->prof.enable((enable & 2) != 0)) return CUDPP_ERROR_INSUFFICIENT_RESOURCES;
     p->prof.reset();
-    if (SaScratch *s = sa_of(p)) s->prof = &p->prof;
-    if (p->config.algorithm == CUDPP_COMPRESS) {
-        CompressPlan *cp = static_cast<CompressPlan *>(p);
-        cp->mtf.prof = &p->prof; cp->huff.prof = &p->prof; cp->dec.prof = &p->prof;
-    } else if (p->config.algorithm == CUDPP_MTF) static_cast<MtfPlan *>(p)->mtf.prof = &p->prof;
+    p->wire_prof();
     return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanSetSorter(CUDPPHandle planHandle, int mode)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = p->sorter();
     if (!s) return CUDPP_ERROR_INVALID_PLAN;
     if (mode < 0 || mode > 7) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     s->sorter = mode >= 5 ? 0 : mode;
@@ -699,9 +706,9 @@ CUDPPResult glcPlanSetChains(CUDPPHandle planHandle, long minLive, unsigned int 
 // out_ss[b]: sample sorter (1 = a bucket overflowed, 2 = deeper than its cap / a run no window holds)
 CUDPPResult glcPlanDebugSortFlags(CUDPPHandle planHandle, unsigned int *out_fs, unsigned int *out_ss, size_t numBlocks)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = p->sorter();
     if (!s || numBlocks > s->rows) return CUDPP_ERROR_INVALID_PLAN;
     if (hipStreamSynchronize(p->stream) != hipSuccess) return CUDPP_ERROR_UNKNOWN;
     if (out_fs && hipMemcpy(out_fs, s->fs_flag, numBlocks * 4, hipMemcpyDeviceToHost) != hipSuccess) return CUDPP_ERROR_UNKNOWN;
@@ -712,9 +719,9 @@ CUDPPResult glcPlanDebugSortFlags(CUDPPHandle planHandle, unsigned int *out_fs, 
 // diagnostic: bucket fills of block `block` as the last bucketing pass left them (FS_MAXNB = 512 entries)
 CUDPPResult glcPlanDebugBucketFill(CUDPPHandle planHandle, size_t block, unsigned int *out512)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out512) return CUDPP_ERROR_INVALID_HANDLE;
-    SaScratch *s = sa_of(p);
+    PlanBase *p = plan_of(planHandle, out512);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
+    SaScratch *s = p->sorter();
     if (!s || block >= s->rows) return CUDPP_ERROR_INVALID_PLAN;
     if (hipStreamSynchronize(p->stream) != hipSuccess) return CUDPP_ERROR_UNKNOWN;
     return hipMemcpy(out512, s->fs_fill + block * FS_MAXNB, FS_MAXNB * 4, hipMemcpyDeviceToHost) == hipSuccess ? CUDPP_SUCCESS : CUDPP_ERROR_UNKNOWN;
@@ -724,15 +731,15 @@ CUDPPResult glcPlanDebugBucketFill(CUDPPHandle planHandle, size_t block, unsigne
 static void prof_collect(PlanBase *p)
 {
     if (p->prof.npend == 0) return;
-    if (p->config.algorithm == CUDPP_COMPRESS) static_cast<CompressPlan *>(p)->join_side();
+    p->join_side();
     (void)hipStreamSynchronize(p->stream);
     p->prof.collect();
 }
 
 CUDPPResult glcPlanKernelProfileEx(CUDPPHandle planHandle, int index, char *name, size_t nameCap, double *out3)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out3) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle, out3);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     if (index < 0 || index >= PROF_NSLOT) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     prof_collect(p);
     out3[0] = p->prof.ms[index]; out3[1] = (double)p->prof.launches[index]; out3[2] = p->prof.units[index];
@@ -743,8 +750,8 @@ CUDPPResult glcPlanKernelProfileEx(CUDPPHandle planHandle, int index, char *name
 // the kernel with the largest accumulated launch time: {ms, launches, input bytes processed}; resets the profile
 CUDPPResult glcPlanKernelProfile(CUDPPHandle planHandle, double *out3)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out3) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle, out3);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     prof_collect(p);
     int best = 0;
     for (int k = 1; k < PROF_NSLOT; k++) if (p->prof.ms[k] > p->prof.ms[best]) best = k;
@@ -757,8 +764,8 @@ CUDPPResult glcPlanKernelProfile(CUDPPHandle planHandle, double *out3)
 // reads), out2[1] = bracketed but unreadable
 CUDPPResult glcPlanKernelProfileLost(CUDPPHandle planHandle, unsigned long long *out2)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !out2) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle, out2);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     out2[0] = (unsigned long long)p->prof.dropped; out2[1] = (unsigned long long)p->prof.unread;
     return CUDPP_SUCCESS;
 }
@@ -767,11 +774,11 @@ CUDPPResult glcCompactStreams(CUDPPHandle planHandle, const unsigned int *d_comp
                               size_t compressedStrideWords, const unsigned int *d_compressedSize,
                               size_t numBlocks, unsigned int *d_out, unsigned long long *d_outOffsets)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     if (!d_compressed || !d_compressedSize || !d_out || !d_outOffsets || numBlocks == 0)
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (p->config.algorithm == CUDPP_COMPRESS) static_cast<CompressPlan *>(p)->join_side();
+    p->join_side();
     return hip_result(compact_streams(p->stream, d_compressed, compressedStrideWords, d_compressedSize,
                                       (uint32_t)numBlocks, d_out, d_outOffsets));
 }
@@ -780,19 +787,19 @@ CUDPPResult glcExpandStreams(CUDPPHandle planHandle, const unsigned int *d_in, c
                              size_t numBlocks, unsigned int *d_compressed, size_t compressedStrideWords,
                              unsigned int *d_compressedSize)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     if (!d_in || !d_inOffsets || !d_compressed || numBlocks == 0 || compressedStrideWords == 0)
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (p->config.algorithm == CUDPP_COMPRESS) static_cast<CompressPlan *>(p)->join_side();
+    p->join_side();
     return hip_result(expand_streams(p->stream, d_in, d_inOffsets, (uint32_t)numBlocks, d_compressed,
                                      compressedStrideWords, d_compressedSize, p->d_status));
 }
 
 CUDPPResult glcPlanLastTiming(CUDPPHandle planHandle, float *ms4)
 {
-    PlanBase *p = plan_from<PlanBase>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || !ms4) return CUDPP_ERROR_INVALID_HANDLE;
+    PlanBase *p = plan_of(planHandle, ms4);
+    if (!p) return CUDPP_ERROR_INVALID_HANDLE;
     for (int i = 0; i < 4; i++) ms4[i] = p->last_ms[i];
     return CUDPP_SUCCESS;
 }
@@ -801,25 +808,20 @@ CUDPPResult glcPlanLastTiming(CUDPPHandle planHandle, float *ms4)
 
 // internal: the container path (container_api.cpp) drives a plan through these
 namespace glc {
-CUDPPResult plan_compress_hooked(CUDPPHandle planHandle, const unsigned char *d_in, int *d_bwtIndex, unsigned int *d_hist,
-                                 unsigned int *d_encodeOffset, size_t offsetStride, unsigned int *d_size,
-                                 unsigned int *d_compact, size_t capacityWords, unsigned long long *d_blockOffsets,
-                                 const unsigned long long *d_startOffset, size_t numElements, size_t numBlocks,
-                                 ContainerHooks &hk)
+CUDPPResult plan_compress_hooked(CUDPPHandle planHandle, CompressCall c, ContainerHooks &hk)
 {
-    return compress_batch(planHandle, d_in, d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_size, d_compact, 0, numElements,
-                          numBlocks, d_blockOffsets, d_startOffset, capacityWords, &hk);
+    c.hooks = &hk;
+    return compress_batch(planHandle, c);
 }
 
 bool plan_info(CUDPPHandle planHandle, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity)
 {
-    CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (!p || planHandle == CUDPP_INVALID_HANDLE || p->config.algorithm != CUDPP_COMPRESS || p->config.datatype != CUDPP_UCHAR)
-        return false;
+    PlanBase *p = plan_of(planHandle);
+    if (!p || p->config.algorithm != CUDPP_COMPRESS || p->config.datatype != CUDPP_UCHAR) return false;
     if (n) *n = p->n;
     if (rows) *rows = p->rows;
     if (st) *st = p->stream;
-    if (next_parity) *next_parity = p->calls & 1u;
+    if (next_parity) *next_parity = static_cast<CompressPlan *>(p)->enc_half.next();
     return true;
 }
 
@@ -831,37 +833,13 @@ CtSettings &plan_container_settings(CUDPPHandle planHandle) { return plan_from<C
 hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {
     CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (bytes > p->ct_stage_bytes[which]) {
-        if (p->ct_stage[which]) {                              // (growing: whatever still reads the old one finishes first)
-            p->join_side();
-            (void)hipStreamSynchronize(p->stream);
-            (void)hipFree(p->ct_stage[which]);
-            p->ct_stage[which] = nullptr; p->ct_stage_bytes[which] = 0;
-        }
-        const hipError_t e = hipMalloc(&p->ct_stage[which], bytes);
-        if (e != hipSuccess) { p->ct_stage[which] = nullptr; return e; }
-        p->ct_stage_bytes[which] = bytes;
-    }
-    *out = static_cast<uint8_t *>(p->ct_stage[which]);
-    return hipSuccess;
+    return p->ct_stage[which].grow(*p, bytes, out);
 }
 
 hipError_t plan_codec_scratch(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {
     CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    if (bytes > p->ct_codec_bytes[which]) {
-        if (p->ct_codec_mem[which]) {                          // (growing: whatever still uses the old one finishes first)
-            p->join_side();
-            (void)hipStreamSynchronize(p->stream);
-            (void)hipFree(p->ct_codec_mem[which]);
-            p->ct_codec_mem[which] = nullptr; p->ct_codec_bytes[which] = 0;
-        }
-        const hipError_t e = hipMalloc(&p->ct_codec_mem[which], bytes);
-        if (e != hipSuccess) { p->ct_codec_mem[which] = nullptr; return e; }
-        p->ct_codec_bytes[which] = bytes;
-    }
-    *out = static_cast<uint8_t *>(p->ct_codec_mem[which]);
-    return hipSuccess;
+    return p->ct_codec[which].grow(*p, bytes, out);
 }
 
 KernelProf *plan_prof(CUDPPHandle planHandle) { return &plan_from<CompressPlan>(planHandle)->prof; }
@@ -879,7 +857,6 @@ void plan_stage_mark(CUDPPHandle planHandle, int i)
 void plan_wait_released(CUDPPHandle planHandle)
 {
     CompressPlan *p = plan_from<CompressPlan>(planHandle);
-    const uint32_t k = p->calls & 1u;
-    if (p->pipelined && p->released_valid[k]) (void)hipStreamWaitEvent(p->stream, p->ev_released[k], 0);
+    if (p->pipelined) p->enc_half.wait_free(p->enc_half.next(), p->stream);
 }
 } // namespace glc

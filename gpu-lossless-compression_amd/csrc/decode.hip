@@ -978,70 +978,72 @@ void decode_scratch_free(DecodeScratch &s)
 // Stage B: inverse BWT of `bwt` -> d_out.  The two stages use disjoint scratch apart from `bwt`, so
 // stage A of the next batch can run on another stream while stage B of this one walks its LF cycles
 // (glcPlanSetPipelining): A is LDS/VALU work, B is a memory-latency-bound pointer chase.
-hipError_t decode_stage_a(hipStream_t st, const uint32_t *d_hist, const uint32_t *d_offsets, size_t offset_stride,
-                          const uint32_t *d_comp, size_t comp_stride_words, uint32_t n, uint32_t nblk, DecodeScratch &s,
-                          uint8_t *bwt, uint32_t *d_status, const unsigned long long *d_block_off)
+hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status)
 {
-    if (n == 0 || n > s.nmax || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
+    if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
+    const uint32_t n = (uint32_t)c.n, nblk = (uint32_t)c.nblk;
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
     const uint32_t nchunks = (n + IMTF_CHUNK - 1) / IMTF_CHUNK;
     const double units = (double)n * nblk;
-    int pi = s.prof ? s.prof->begin(PROF_DEC_HUFF, st) : -1;
-    hipLaunchKernelGGL(k_dec_prepare, dim3(nblk), dim3(256), 0, st, d_hist, s.lut, s.nodes, n, d_status);
-    if ((uint64_t)nsub * nblk >= DL_MIN_SUBS)
-        hipLaunchKernelGGL(k_dec_huff_lanes, dim3((nsub + DL_NT - 1) / DL_NT, nblk), dim3(DL_NT), 0, st, d_comp, comp_stride_words,
-                           d_offsets, offset_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, d_block_off);
-    else
-        hipLaunchKernelGGL(k_dec_huff, dim3((nsub + DH_WAVES - 1) / DH_WAVES, nblk), dim3(DH_WAVES * 64), 0, st, d_comp, comp_stride_words,
-                           d_offsets, offset_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, d_block_off);
-    if (pi >= 0) s.prof->end(pi, units, st);
-    pi = s.prof ? s.prof->begin(PROF_IMTF_POS, st) : -1;
-    hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
-                       s.max_chunks, bwt, (size_t)s.nmax);
-    if (pi >= 0) s.prof->end(pi, units, st);
-    pi = s.prof ? s.prof->begin(PROF_IMTF_REST, st) : -1;
-    hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);
-    hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, n, s.ilists,
-                       s.max_chunks);
-    if (pi >= 0) s.prof->end(pi, units, st);
+    {
+        ProfScope ps(s.prof, PROF_DEC_HUFF, st, units);
+        hipLaunchKernelGGL(k_dec_prepare, dim3(nblk), dim3(256), 0, st, c.hist, s.lut, s.nodes, n, d_status);
+        if ((uint64_t)nsub * nblk >= DL_MIN_SUBS)
+            hipLaunchKernelGGL(k_dec_huff_lanes, dim3((nsub + DL_NT - 1) / DL_NT, nblk), dim3(DL_NT), 0, st, c.comp, c.comp_stride,
+                               c.enc_off, c.off_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, c.block_off);
+        else
+            hipLaunchKernelGGL(k_dec_huff, dim3((nsub + DH_WAVES - 1) / DH_WAVES, nblk), dim3(DH_WAVES * 64), 0, st, c.comp, c.comp_stride,
+                               c.enc_off, c.off_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, c.block_off);
+    }
+    {
+        ProfScope ps(s.prof, PROF_IMTF_POS, st, units);
+        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
+                           s.max_chunks, bwt, (size_t)s.nmax);
+    }
+    {
+        ProfScope ps(s.prof, PROF_IMTF_REST, st, units);
+        hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);
+        hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, n, s.ilists,
+                           s.max_chunks);
+    }
     return hipGetLastError();
 }
 
-hipError_t decode_stage_b(hipStream_t st, const int *d_bwt_index, const uint8_t *bwt, uint8_t *d_out, uint32_t n,
-                          uint32_t nblk, DecodeScratch &s, uint32_t *d_status)
+hipError_t decode_stage_b(hipStream_t st, const DecodeCall &c, const uint8_t *bwt, DecodeScratch &s, uint32_t *d_status)
 {
-    if (n == 0 || n > s.nmax || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
+    if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
+    const uint32_t n = (uint32_t)c.n, nblk = (uint32_t)c.nblk;
     const uint32_t rows = n + 1, tiles = (rows + LF_TILE - 1) / LF_TILE, nsplit = (rows + SPLIT - 1) / SPLIT;
     const size_t lf_stride = (size_t)s.nmax + 4;
     const double units = (double)n * nblk;
-    int pi = s.prof ? s.prof->begin(PROF_IBWT_LF, st) : -1;
-    hipLaunchKernelGGL(k_ibwt_hist, dim3(tiles, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, d_bwt_index, n,
-                       s.tile_hist, s.max_tiles, d_status);
-    GLC_TRY(tile_hist_scan9(st, s.tile_hist, rows, s.digit_base, s.max_tiles, nblk, LF_TILE));
-    hipLaunchKernelGGL(k_ibwt_lf, dim3(tiles, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, d_bwt_index, n,
-                       s.tile_hist, s.digit_base, s.max_tiles, s.lf, lf_stride);
-    hipLaunchKernelGGL(k_ibwt_seg_init, dim3((nblk + 255) / 256), dim3(256), 0, st, s.seg_count, n, nblk);
-    if (pi >= 0) s.prof->end(pi, units, st);
-    pi = s.prof ? s.prof->begin(PROF_IBWT_WALK, st) : -1;
-    hipLaunchKernelGGL(k_ibwt_walk<GLC_WALK_PAD>, dim3((nsplit + 255) / 256, nblk), dim3(256), 0, st, s.lf, lf_stride, n, s.seg,
-                       s.max_seg, s.seg_count, s.slots);
-    if (pi >= 0) s.prof->end(pi, units, st);
-    pi = s.prof ? s.prof->begin(PROF_IBWT_EMIT, st) : -1;
-    hipLaunchKernelGGL(k_ibwt_rank, dim3(nblk), dim3(RANK_NT), 0, st, s.seg, s.max_seg, s.seg_count, s.seg_pos);
-    const uint32_t seg_bound = nsplit + rows / SLOT + 1;
-    hipLaunchKernelGGL(k_ibwt_emit, dim3((seg_bound + 4 * EMIT_SEGS - 1) / (4 * EMIT_SEGS), nblk), dim3(256), 0, st,
-                       s.slots, s.seg, s.seg_pos, s.max_seg, s.seg_count, n, d_out, (size_t)n);
-    if (pi >= 0) s.prof->end(pi, units, st);
+    {
+        ProfScope ps(s.prof, PROF_IBWT_LF, st, units);
+        hipLaunchKernelGGL(k_ibwt_hist, dim3(tiles, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, c.bwt_index, n,
+                           s.tile_hist, s.max_tiles, d_status);
+        GLC_TRY(tile_hist_scan9(st, s.tile_hist, rows, s.digit_base, s.max_tiles, nblk, LF_TILE));
+        hipLaunchKernelGGL(k_ibwt_lf, dim3(tiles, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, c.bwt_index, n,
+                           s.tile_hist, s.digit_base, s.max_tiles, s.lf, lf_stride);
+        hipLaunchKernelGGL(k_ibwt_seg_init, dim3((nblk + 255) / 256), dim3(256), 0, st, s.seg_count, n, nblk);
+    }
+    {
+        ProfScope ps(s.prof, PROF_IBWT_WALK, st, units);
+        hipLaunchKernelGGL(k_ibwt_walk<GLC_WALK_PAD>, dim3((nsplit + 255) / 256, nblk), dim3(256), 0, st, s.lf, lf_stride, n, s.seg,
+                           s.max_seg, s.seg_count, s.slots);
+    }
+    {
+        ProfScope ps(s.prof, PROF_IBWT_EMIT, st, units);
+        hipLaunchKernelGGL(k_ibwt_rank, dim3(nblk), dim3(RANK_NT), 0, st, s.seg, s.max_seg, s.seg_count, s.seg_pos);
+        const uint32_t seg_bound = nsplit + rows / SLOT + 1;
+        hipLaunchKernelGGL(k_ibwt_emit, dim3((seg_bound + 4 * EMIT_SEGS - 1) / (4 * EMIT_SEGS), nblk), dim3(256), 0, st,
+                           s.slots, s.seg, s.seg_pos, s.max_seg, s.seg_count, n, c.out, (size_t)n);
+    }
     return hipGetLastError();
 }
 
-hipError_t decode_blocks(hipStream_t st, const int *d_bwt_index, const uint32_t *d_hist, const uint32_t *d_offsets,
-                         size_t offset_stride, const uint32_t *d_comp, size_t comp_stride_words, uint8_t *d_out,
-                         uint32_t n, uint32_t nblk, DecodeScratch &s, MtfScratch & /*ms*/, uint32_t *d_status,
-                         const unsigned long long *d_block_off)
+hipError_t decode_blocks(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint32_t *d_status)
 {
-    GLC_TRY(decode_stage_a(st, d_hist, d_offsets, offset_stride, d_comp, comp_stride_words, n, nblk, s, s.bwt, d_status, d_block_off));
-    return decode_stage_b(st, d_bwt_index, s.bwt, d_out, n, nblk, s, d_status);
+    GLC_TRY(decode_stage_a(st, c, s, s.bwt, d_status));
+    return decode_stage_b(st, c, s.bwt, s, d_status);
 }
 
 } // namespace glc

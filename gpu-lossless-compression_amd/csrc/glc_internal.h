@@ -140,6 +140,17 @@ struct KernelProf {
     }
 };
 
+// The bracket around the launches of one slot: begins where it is declared, ends where its block does -- braces of their own
+// where that must be before the next launch.  KernelProf::begin does not reserve its pair until end: two scopes must never be
+// open at once on one profile.  A scope left early (a failed call inside it) still closes its pair.  pr may be null.
+struct ProfScope {
+    KernelProf *pr; hipStream_t st; double units; int i;
+    ProfScope(KernelProf *p, int slot, hipStream_t s, double u) : pr(p), st(s), units(u), i(p ? p->begin(slot, s) : -1) {}
+    ~ProfScope() { if (pr) pr->end(i, units, st); }
+    ProfScope(const ProfScope &) = delete;
+    ProfScope &operator=(const ProfScope &) = delete;
+};
+
 // C-ABI helper for the stateless device entry points (CULZSS, CUHD-shaped decoder), which have no plan to hang a profile
 // on: a process-wide KernelProf with its own slot names.  out3 = {sum of launch ms, launches, units}; returns 0 past the
 // last named slot.  Measurement aid: not thread-safe against concurrent launches.
@@ -302,6 +313,25 @@ void       sa_scratch_free(SaScratch &s);
 struct SortCall {
     hipStream_t st; const uint8_t *text; size_t text_stride; uint32_t n, nblk; uint8_t *bwt_out; size_t bwt_stride; int *d_index;
     uint32_t *sa_out(const SaScratch &s) const { return bwt_out ? nullptr : s.sa; }   // where a tier writes suffix-array rows
+};
+
+// One encode call of a COMPRESS plan (cudpp_api.cpp), as the entry points and the container hand it over.  n and nblk are the
+// caller's numbers: nothing narrows them before they are checked against the plan.  Strided layout: block b's words at out +
+// b * out_stride.  Compact layout (block_off given): at out + block_off[b], back to back from *start on, capacity words in all.
+struct ContainerHooks;                                         // container_internal.h
+struct CompressCall {
+    const uint8_t *in; int *bwt_index; uint32_t *hist, *enc_off; size_t off_stride; uint32_t *size, *out; size_t out_stride;
+    size_t n, nblk;
+    unsigned long long *block_off = nullptr; const unsigned long long *start = nullptr; size_t capacity = 0;
+    ContainerHooks *hooks = nullptr;
+    bool compact() const { return block_off != nullptr; }
+};
+// One decode call, the same way (block_off: the compact layout, nblk + 1 entries: block b's words are comp[block_off[b] ..
+// block_off[b + 1]))
+struct DecodeCall {
+    const int *bwt_index; const uint32_t *hist, *enc_off; size_t off_stride; const uint32_t *comp; size_t comp_stride; uint8_t *out;
+    size_t n, nblk;
+    const unsigned long long *block_off = nullptr;
 };
 
 // Host readbacks: nwords device words to the pinned words from `slot` on, then the host waits -- for ev_flag, recorded behind
@@ -491,16 +521,9 @@ hipError_t tile_hist_scan9(hipStream_t st, uint32_t *tile_hist, uint32_t count, 
                            uint32_t max_tiles, uint32_t nblk, uint32_t tile_elems);
 hipError_t decode_scratch_alloc(DecodeScratch &s, uint32_t nmax, uint32_t rows);
 void       decode_scratch_free(DecodeScratch &s);
-// d_block_off (compact layout, nblk + 1 entries): block b's words are d_comp[d_block_off[b] .. d_block_off[b + 1])
-hipError_t decode_stage_a(hipStream_t st, const uint32_t *d_hist, const uint32_t *d_offsets, size_t offset_stride,
-                          const uint32_t *d_comp, size_t comp_stride_words, uint32_t n, uint32_t nblk, DecodeScratch &s,
-                          uint8_t *bwt, uint32_t *d_status, const unsigned long long *d_block_off = nullptr);
-hipError_t decode_stage_b(hipStream_t st, const int *d_bwt_index, const uint8_t *bwt, uint8_t *d_out, uint32_t n,
-                          uint32_t nblk, DecodeScratch &s, uint32_t *d_status);
-hipError_t decode_blocks(hipStream_t st, const int *d_bwt_index, const uint32_t *d_hist,
-                         const uint32_t *d_offsets, size_t offset_stride, const uint32_t *d_comp,
-                         size_t comp_stride_words, uint8_t *d_out, uint32_t n, uint32_t nblk,
-                         DecodeScratch &s, MtfScratch &ms, uint32_t *d_status,
-                         const unsigned long long *d_block_off = nullptr);
+// stage A: the call's streams -> BWT bytes in `bwt`; stage B: `bwt` -> c.out; decode_blocks: both, through s.bwt
+hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status);
+hipError_t decode_stage_b(hipStream_t st, const DecodeCall &c, const uint8_t *bwt, DecodeScratch &s, uint32_t *d_status);
+hipError_t decode_blocks(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint32_t *d_status);
 
 } // namespace glc

@@ -253,12 +253,6 @@ size_t hdb_decode_work_bytes(size_t count, size_t max_len)
     return up256(w * HD_LANES * HD_TSTRIDE * 4) + up256(w * HD_TSTRIDE * 4);
 }
 
-struct ProfScope {
-    KernelProf *pr; hipStream_t st; double units; int i;
-    ProfScope(KernelProf *p, int slot, hipStream_t s, double u) : pr(p), st(s), units(u), i(p ? p->begin(slot, s) : -1) {}
-    ~ProfScope() { if (pr) pr->end(i, units, st); }
-};
-
 hipError_t hdb_tables(hipStream_t st, const HdbSegs &g, bool make_hist, uint32_t *hist, uint8_t *lens, uint16_t *codes,
                       uint16_t *lut, unsigned long long *nunits, const uint32_t *skip, KernelProf *prof)
 {

@@ -424,14 +424,15 @@ hipError_t huff_build(hipStream_t st, uint32_t n, uint32_t nblk, HuffScratch &s,
                       uint32_t *d_status, const uint32_t *redo_flag, const uint32_t *only)
 {
     if (n == 0 || n > s.nmax || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
-    const int pi = s.prof ? s.prof->begin(PROF_HUFF_BUILD, st) : -1;
-    if (nblk <= 512)                                           // resident either way: more threads, shorter passes
-        hipLaunchKernelGGL(k_huff_build<1024>, dim3(nblk), dim3(1024), 0, st, s.sub_hist, s.max_sub, n, d_hist, s.codes,
-                           s.lens, d_offsets, offset_stride, d_size, (uint64_t)capacity_words, d_status, redo_flag, only);
-    else
-        hipLaunchKernelGGL(k_huff_build<512>, dim3(nblk), dim3(512), 0, st, s.sub_hist, s.max_sub, n, d_hist, s.codes,
-                           s.lens, d_offsets, offset_stride, d_size, (uint64_t)capacity_words, d_status, redo_flag, only);
-    if (pi >= 0) s.prof->end(pi, (double)n * nblk, st);
+    {
+        ProfScope ps(s.prof, PROF_HUFF_BUILD, st, (double)n * nblk);
+        if (nblk <= 512)                                       // resident either way: more threads, shorter passes
+            hipLaunchKernelGGL(k_huff_build<1024>, dim3(nblk), dim3(1024), 0, st, s.sub_hist, s.max_sub, n, d_hist, s.codes,
+                               s.lens, d_offsets, offset_stride, d_size, (uint64_t)capacity_words, d_status, redo_flag, only);
+        else
+            hipLaunchKernelGGL(k_huff_build<512>, dim3(nblk), dim3(512), 0, st, s.sub_hist, s.max_sub, n, d_hist, s.codes,
+                               s.lens, d_offsets, offset_stride, d_size, (uint64_t)capacity_words, d_status, redo_flag, only);
+    }
     return hipGetLastError();
 }
 
@@ -449,11 +450,12 @@ hipError_t huff_pack(hipStream_t st, const uint8_t *mtf, size_t mtf_stride, uint
                      size_t capacity_words)
 {
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    const int pi = s.prof ? s.prof->begin(PROF_HUFF_PACK, st) : -1;
-    hipLaunchKernelGGL(k_huff_pack, dim3((nsub + HP_SUBS - 1) / HP_SUBS, nblk), dim3(256), 0, st, mtf, mtf_stride, n, s.codes, s.lens,
-                       d_offsets, offset_stride, d_compressed, comp_stride_words,
-                       (uint64_t)(d_block_off ? capacity_words : comp_stride_words), only, d_block_off);
-    if (pi >= 0) s.prof->end(pi, (double)n * nblk, st);
+    {
+        ProfScope ps(s.prof, PROF_HUFF_PACK, st, (double)n * nblk);
+        hipLaunchKernelGGL(k_huff_pack, dim3((nsub + HP_SUBS - 1) / HP_SUBS, nblk), dim3(256), 0, st, mtf, mtf_stride, n, s.codes, s.lens,
+                           d_offsets, offset_stride, d_compressed, comp_stride_words,
+                           (uint64_t)(d_block_off ? capacity_words : comp_stride_words), only, d_block_off);
+    }
     return hipGetLastError();
 }
 

@@ -674,43 +674,45 @@ hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint
     dim3 g((nchunks + MTF_WAVES - 1) / MTF_WAVES, nblk), t(MTF_WAVES * 64);
     dim3 ge((nchunks + MTF_WAVES * MTF_ROWS - 1) / (MTF_WAVES * MTF_ROWS), nblk);      // encode: 4 chunks per wave
     const double units = (double)n * nblk;
-    int pi = s.prof ? s.prof->begin(PROF_MTF_LISTS, st) : -1;
-    hipLaunchKernelGGL(k_mtf_chunk_lists, g, t, 0, st, in, in_stride, n, s.lists, s.lens, s.max_chunks, only);
-    // 16 waves of 16 chunks: the shortest chain of folds (48) for a block on its own; 8 waves of 32 (72 folds): four
-    // workgroups per CU, so a batch of 1024 blocks is resident at once instead of in two rounds (0.156 -> 0.126 ms)
-    if (nblk <= 512)
-        hipLaunchKernelGGL(k_mtf_scan_lists<16>, dim3(nblk), dim3(16 * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
-    else
-        hipLaunchKernelGGL(k_mtf_scan_lists<8>, dim3(nblk), dim3(8 * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
-    if (pi >= 0) s.prof->end(pi, units, st);
-    pi = s.prof ? s.prof->begin(PROF_MTF_ENCODE, st) : -1;
-    // few chunks in all (a cudppCompress call, small batches): a wave per chunk, its rows the chunk's quarters
-    const bool quarters = (uint64_t)nchunks * nblk <= MTF_QUARTERS_MAX_CHUNKS;
-    if (quarters && sub_hist)
-        hipLaunchKernelGGL((k_mtf_encode<true, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (quarters)
-        hipLaunchKernelGGL((k_mtf_encode<false, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist && skewed)             // whole chunks in every row: the FULL form
-        hipLaunchKernelGGL((k_mtf_encode<true, false, true, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist)
-        hipLaunchKernelGGL((k_mtf_encode<true, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (n % (MTF_ROWS * MTF_CHUNK) == 0)
-        hipLaunchKernelGGL((k_mtf_encode<false, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (sub_hist && skewed)
-        hipLaunchKernelGGL((k_mtf_encode<true, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else if (sub_hist)
-        hipLaunchKernelGGL((k_mtf_encode<true, false>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    else
-        hipLaunchKernelGGL((k_mtf_encode<false, false>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
-                           out_stride, sub_hist, only);
-    if (pi >= 0) s.prof->end(pi, units, st);
+    {
+        ProfScope ps(s.prof, PROF_MTF_LISTS, st, units);
+        hipLaunchKernelGGL(k_mtf_chunk_lists, g, t, 0, st, in, in_stride, n, s.lists, s.lens, s.max_chunks, only);
+        // 16 waves of 16 chunks: the shortest chain of folds (48) for a block on its own; 8 waves of 32 (72 folds): four
+        // workgroups per CU, so a batch of 1024 blocks is resident at once instead of in two rounds (0.156 -> 0.126 ms)
+        if (nblk <= 512)
+            hipLaunchKernelGGL(k_mtf_scan_lists<16>, dim3(nblk), dim3(16 * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
+        else
+            hipLaunchKernelGGL(k_mtf_scan_lists<8>, dim3(nblk), dim3(8 * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
+    }
+    {
+        ProfScope ps(s.prof, PROF_MTF_ENCODE, st, units);
+        // few chunks in all (a cudppCompress call, small batches): a wave per chunk, its rows the chunk's quarters
+        const bool quarters = (uint64_t)nchunks * nblk <= MTF_QUARTERS_MAX_CHUNKS;
+        if (quarters && sub_hist)
+            hipLaunchKernelGGL((k_mtf_encode<true, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (quarters)
+            hipLaunchKernelGGL((k_mtf_encode<false, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist && skewed)             // whole chunks in every row: the FULL form
+            hipLaunchKernelGGL((k_mtf_encode<true, false, true, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (n % (MTF_ROWS * MTF_CHUNK) == 0 && sub_hist)
+            hipLaunchKernelGGL((k_mtf_encode<true, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (n % (MTF_ROWS * MTF_CHUNK) == 0)
+            hipLaunchKernelGGL((k_mtf_encode<false, false, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (sub_hist && skewed)
+            hipLaunchKernelGGL((k_mtf_encode<true, false, true>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (sub_hist)
+            hipLaunchKernelGGL((k_mtf_encode<true, false>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else
+            hipLaunchKernelGGL((k_mtf_encode<false, false>), ge, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+    }
     return hipGetLastError();
 }
 

@@ -248,6 +248,25 @@ def test_float32_is_smaller_with_the_filter(glc, ctx, cuda):
         assert torch.equal(glc.container_decompress(plan, c), d)
 
 
+def test_decoder_staging_grows_and_is_kept(glc, ctx, cuda):
+    """a one-row plan decodes a stream of one-block frames, then one of three-block frames (its staging, and the order-0
+    codec's scratch, grow), then the first again (they stay)"""
+    n, elem = 4096, 4
+    x = _typed(elem, 3 * n + 5, 11)
+    conts = {}
+    for rows, codec in ((1, glc.CONTAINER_CODEC_BWT), (3, glc.CONTAINER_CODEC_HUFF0)):
+        with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as w:
+            glc.container_set_shuffle(w, elem)
+            glc.container_set_codec(w, codec)
+            conts[rows] = glc.container_compress(w, _gpu(x))
+            assert glc.container_last_error(w) == (0, -1, -1)
+    with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=1) as r:
+        for rows in (1, 3, 1):
+            assert np.array_equal(_host(glc.container_decompress(r, conts[rows])), x), rows
+            assert glc.container_last_error(r) == (0, -1, -1)
+            assert glc.CONTAINER_WHAT[glc.container_last_error(r)[0]] == "ok"
+
+
 # --- 6. timing and profile interfaces ----------------------------------------------------------------------------------------
 @pytest.mark.parametrize("pipelined", [False, True])
 def test_timing_and_kernel_profile_with_the_filter_on(glc, ctx, cuda, pipelined):

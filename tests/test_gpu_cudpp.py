@@ -324,6 +324,186 @@ def test_error_codes(glc, ctx, cuda):
         assert L.cudppBurrowsWheelerTransform(mtf_plan.handle, d.data_ptr(), d.data_ptr(), o.data_ptr(), 4096) == glc.CUDPP_ERROR_INVALID_PLAN
         assert L.cudppMoveToFrontTransform(mtf_plan.handle, d.data_ptr(), d.data_ptr(), 8192) == glc.CUDPP_ERROR_ILLEGAL_CONFIGURATION
     assert L.cudppDestroyPlan(glc.CUDPP_INVALID_HANDLE) == glc.CUDPP_ERROR_INVALID_HANDLE
+    _error_table(glc, ctx, cuda)
+
+
+PROF_NSLOT = 21                                            # csrc/glc_internal.h
+
+
+def _error_table(glc, ctx, cuda):
+    """Every batch entry and plan utility against every kind of bad argument, the exact code each time.  Handle -> 1, plan
+    type -> 3, everything else -> 2; a null output pointer answers like a bad handle; the checks that run before the handle
+    is looked at (null offsets / null array of the Compact entries) win over it."""
+    import ctypes as C
+    import torch
+    L = glc.lib()
+    HANDLE, CONFIG, PLAN = glc.CUDPP_ERROR_INVALID_HANDLE, glc.CUDPP_ERROR_ILLEGAL_CONFIGURATION, glc.CUDPP_ERROR_INVALID_PLAN
+    N, R = 4096, 2
+    STRIDE = glc.compressed_stride_words(N)
+    x = np.concatenate([datagen.zipf_bytes(N, seed=501), datagen.text_bytes(N, seed=502)])
+    d_in = torch.from_numpy(x).cuda()
+    d_out = torch.zeros(N * R, dtype=torch.uint8, device=cuda)
+    scratch = torch.zeros(STRIDE * R + 4096, dtype=torch.int32, device=cuda)    # (no call of the table gets as far as using it)
+    d, d2, o = d_in.data_ptr(), d_out.data_ptr(), scratch.data_ptr()
+    one, two, three = (C.c_uint * 1)(), (C.c_ulonglong * 2)(), (C.c_double * 3)()
+    ms4, name = (C.c_float * 4)(), C.create_string_buffer(96)
+    # the batch entries as f(handle, numElements, numBlocks, offsetStride)
+    batch = {
+        "glcCompressBatch": lambda h, n=N, nb=R, st=1: L.glcCompressBatch(h, d, o, o, o, st, o, o, STRIDE, n, nb),
+        "glcCompressBatchCompact": lambda h, n=N, nb=R, st=1: L.glcCompressBatchCompact(h, d, o, o, o, st, o, o, STRIDE * R, o, None, n, nb),
+        "glcHuffmanEncodeBatch": lambda h, n=N, nb=R, st=1: L.glcHuffmanEncodeBatch(h, d, o, o, st, o, o, STRIDE, n, nb),
+        "glcDecompressBatch": lambda h, n=N, nb=R, st=1: L.glcDecompressBatch(h, o, o, o, st, o, STRIDE, d2, n, nb),
+        "glcDecompressBatchCompact": lambda h, n=N, nb=R, st=1: L.glcDecompressBatchCompact(h, o, o, o, st, o, STRIDE * R, o, d2, n, nb),
+        "glcBwtBatch": lambda h, n=N, nb=R, st=1: L.glcBwtBatch(h, d, d2, o, n, nb),
+        "glcMtfBatch": lambda h, n=N, nb=R, st=1: L.glcMtfBatch(h, d, d2, n, nb),
+        "cudppSuffixArray": lambda h, n=N, nb=R, st=1: L.cudppSuffixArray(h, d, o, n),
+    }
+    own = {"glcCompressBatch": "compress", "glcCompressBatchCompact": "compress", "glcHuffmanEncodeBatch": "compress",
+           "glcDecompressBatch": "compress", "glcDecompressBatchCompact": "compress", "glcBwtBatch": "bwt", "glcMtfBatch": "mtf",
+           "cudppSuffixArray": "sa"}
+    checks_datatype = {"glcCompressBatch", "glcCompressBatchCompact", "glcBwtBatch"}      # ... of those a CUDPP_UINT plan exists for here
+    checks_offset_stride = {"glcCompressBatch", "glcCompressBatchCompact", "glcHuffmanEncodeBatch"}
+    # the plan utilities as f(handle, with an output pointer?)
+    util = {
+        "glcPlanSetSorter": lambda h, out=True: L.glcPlanSetSorter(h, 0),
+        "glcPlanLastSortStats": lambda h, out=True: L.glcPlanLastSortStats(h, one if out else None),
+        "glcPlanSetChains": lambda h, out=True: L.glcPlanSetChains(h, -1, 0xFFFFFFFF),
+        "glcPlanLastTiming": lambda h, out=True: L.glcPlanLastTiming(h, ms4 if out else None),
+        "glcPlanKernelProfileEx": lambda h, out=True: L.glcPlanKernelProfileEx(h, 0, name, 96, three if out else None),
+        "glcCompactStreams": lambda h, out=True: L.glcCompactStreams(h, o, STRIDE, o, R, o if out else None, o),
+    }
+    needs_sorter = {"glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanSetChains"}
+    has_out = {"glcPlanLastSortStats": HANDLE, "glcPlanLastTiming": HANDLE, "glcPlanKernelProfileEx": HANDLE,
+               "glcCompactStreams": CONFIG}                # (glcCompactStreams' arrays are arguments, not the getter's output)
+    algs = dict(compress=glc.CUDPP_COMPRESS, bwt=glc.CUDPP_BWT, mtf=glc.CUDPP_MTF, sa=glc.CUDPP_SA)
+    plans = {k: glc.Plan(ctx, a, N, rows=R) for k, a in algs.items()}
+    uint = {k: glc.Plan(ctx, algs[k], N, rows=R, datatype=glc.CUDPP_UINT) for k in ("compress", "bwt")}
+    got, want = {}, {}
+
+    def expect(tag, rc, code):
+        got[tag], want[tag] = rc, code
+
+    try:
+        for nm, f in batch.items():
+            good = plans[own[nm]].handle
+            expect((nm, "handle 0"), f(0), HANDLE)
+            expect((nm, "invalid handle"), f(glc.CUDPP_INVALID_HANDLE), HANDLE)
+            for k, pl in plans.items():
+                if k != own[nm]:
+                    expect((nm, "plan of " + k), f(pl.handle), PLAN)
+            for k, pl in uint.items():
+                if k != own[nm]:
+                    expect((nm, "UINT plan of " + k), f(pl.handle), PLAN)
+                elif nm in checks_datatype:
+                    expect((nm, "UINT plan"), f(pl.handle), CONFIG)
+                    expect((nm, "UINT plan, numElements 0"), f(pl.handle, n=0), CONFIG)
+                else:                                           # accepted up to the size checks (a good call: below)
+                    expect((nm, "UINT plan, numElements 0"), f(pl.handle, n=0), CONFIG)
+                    expect((nm, "UINT plan, numBlocks rows + 1"), f(pl.handle, nb=R + 1), CONFIG)
+            expect((nm, "numElements 0"), f(good, n=0), CONFIG)
+            expect((nm, "numElements n + 1"), f(good, n=N + 1), CONFIG)
+            if nm != "cudppSuffixArray":                        # (it has no numBlocks)
+                expect((nm, "numBlocks 0"), f(good, nb=0), CONFIG)
+                expect((nm, "numBlocks rows + 1"), f(good, nb=R + 1), CONFIG)
+            if nm in checks_offset_stride:                      # (the decoder takes the stride as it comes)
+                expect((nm, "offsetStride 0"), f(good, st=0), CONFIG)
+                expect((nm, "offsetStride 0, plan of mtf"), f(plans["mtf"].handle, st=0), PLAN)
+        # the pre-checks that run before the handle is looked at
+        expect("compact encode: null offsets, handle 0", L.glcCompressBatchCompact(0, d, o, o, o, 1, o, o, STRIDE * R, None, None, N, R), CONFIG)
+        expect("compact encode: null array, handle 0", L.glcCompressBatchCompact(0, d, o, o, o, 1, o, None, STRIDE * R, o, None, N, R), CONFIG)
+        expect("compact encode: null offsets, invalid handle",
+               L.glcCompressBatchCompact(glc.CUDPP_INVALID_HANDLE, d, o, o, o, 1, o, o, STRIDE * R, None, None, N, R), CONFIG)
+        expect("compact decode: null offsets, handle 0", L.glcDecompressBatchCompact(0, o, o, o, 1, o, STRIDE * R, None, d2, N, R), CONFIG)
+        expect("compact decode: null offsets, plan of mtf",
+               L.glcDecompressBatchCompact(plans["mtf"].handle, o, o, o, 1, o, STRIDE * R, None, d2, N, R), CONFIG)
+        for h, tag in ((0, "handle 0"), (glc.CUDPP_INVALID_HANDLE, "invalid handle")):
+            expect(("cudppCompress", tag), L.cudppCompress(h, d, o, None, o, o, o, o, N), HANDLE)
+            expect(("cudppBurrowsWheelerTransform", tag), L.cudppBurrowsWheelerTransform(h, d, d2, o, N), HANDLE)
+            expect(("cudppMoveToFrontTransform", tag), L.cudppMoveToFrontTransform(h, d, d2, N), HANDLE)
+            expect(("cudppSuffixArray", tag), L.cudppSuffixArray(h, d, o, N), HANDLE)
+        for nm, f in util.items():
+            expect((nm, "handle 0"), f(0), HANDLE)
+            expect((nm, "invalid handle"), f(glc.CUDPP_INVALID_HANDLE), HANDLE)
+            if nm in has_out:
+                expect((nm, "null output"), f(plans["compress"].handle, out=False), has_out[nm])
+                expect((nm, "null output, plan of mtf"), f(plans["mtf"].handle, out=False), has_out[nm])
+                expect((nm, "null output, handle 0"), f(0, out=False), HANDLE)
+            for k, pl in plans.items():
+                if nm in needs_sorter and k == "mtf":
+                    expect((nm, "plan of mtf"), f(pl.handle), PLAN)
+                elif nm != "glcCompactStreams":                 # (takes any plan, and would run)
+                    expect((nm, "plan of " + k), f(pl.handle), glc.CUDPP_SUCCESS)
+        for mode in (-1, 8):
+            expect(("glcPlanSetSorter", "mode %d" % mode), L.glcPlanSetSorter(plans["bwt"].handle, mode), CONFIG)
+            expect(("glcPlanSetSorter", "mode %d, plan of mtf" % mode), L.glcPlanSetSorter(plans["mtf"].handle, mode), PLAN)
+        for index in (-1, PROF_NSLOT):
+            expect(("glcPlanKernelProfileEx", "index %d" % index),
+                   L.glcPlanKernelProfileEx(plans["sa"].handle, index, name, 96, three), CONFIG)
+            expect(("glcPlanKernelProfileEx", "index %d, null output" % index),
+                   L.glcPlanKernelProfileEx(plans["sa"].handle, index, name, 96, None), HANDLE)
+        expect(("glcPlanKernelProfileEx", "last index"), L.glcPlanKernelProfileEx(plans["sa"].handle, PROF_NSLOT - 1, name, 96, three), 0)
+        expect(("glcPlanKernelProfileLost", "null output"), L.glcPlanKernelProfileLost(plans["mtf"].handle, None), HANDLE)
+        expect(("glcPlanKernelProfileLost", "handle 0"), L.glcPlanKernelProfileLost(0, two), HANDLE)
+        expect(("glcCompactStreams", "numBlocks 0"), L.glcCompactStreams(plans["mtf"].handle, o, STRIDE, o, 0, o, o), CONFIG)
+        expect(("glcCompactStreams", "null sizes, handle 0"), L.glcCompactStreams(0, o, STRIDE, None, R, o, o), HANDLE)
+        bad = {t: (got[t], want[t]) for t in got if got[t] != want[t]}
+        assert not bad, "(got, want) where they differ: %r" % bad
+        # the CUDPP_UINT COMPRESS plan where the datatype is not looked at: the Huffman stage alone and both decoders work on it
+        p8, p32 = plans["compress"], uint["compress"]
+        ref, ref_c = glc.compress_batch(p8, d_in, N, R), glc.compress_batch_compact(p8, d_in, N, R)
+        sym = glc.huffman_encode_batch(p8, d_in, N, R)
+        p8.synchronize()
+        sym32 = glc.huffman_encode_batch(p32, d_in, N, R)
+        back, back_c = glc.decompress_batch(p32, ref, N, R), glc.decompress_batch_compact(p32, ref_c, N, R)
+        p32.synchronize()
+        assert torch.equal(back, d_in) and torch.equal(back_c, d_in)
+        for k in ("hist", "offsets", "size"):
+            assert torch.equal(sym32[k], sym[k]), k
+        sizes = sym["size"].cpu().numpy()
+        for b in range(R):
+            assert torch.equal(sym32["words"][b * STRIDE:b * STRIDE + int(sizes[b])], sym["words"][b * STRIDE:b * STRIDE + int(sizes[b])])
+    finally:
+        for pl in list(plans.values()) + list(uint.values()):
+            pl.close()
+
+
+def _streams(r, nb):
+    """a compress_batch result as host arrays: indices, sizes, histograms, offsets and every block's words"""
+    sizes = r["size"].cpu().numpy()
+    return (r["bwt_index"].cpu().numpy().copy(), sizes.copy(), r["hist"].cpu().numpy().copy(), r["offsets"].cpu().numpy().copy(),
+            [r["words"][b * r["stride"]: b * r["stride"] + int(sizes[b])].cpu().numpy().copy() for b in range(nb)])
+
+
+def test_halves_change_hands_in_both_directions_of_one_plan(glc, ctx, cuda):
+    """One plan, pipelining on: five compress calls back to back, then five decompress calls back to back (three is the
+    fewest that reuse a half; the odd count leaves a half released in each direction), then the mode goes off and one more
+    of each follows.  Every stream is the plain plan's, word for word, and every decode its input."""
+    import torch
+    n, nb, calls = 12305, 3, 5                                   # three sub-blocks, the last one ragged
+    batches = [np.concatenate([datagen.zipf_bytes(n, seed=7000 + 10 * c + b) if (b + c) % 2 else
+                               datagen.text_bytes(n, seed=8000 + 10 * c + b) for b in range(nb)]) for c in range(calls + 1)]
+    d_in = [torch.from_numpy(x).cuda() for x in batches]
+    with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=nb) as plain:
+        res = [glc.compress_batch(plain, x, n, nb) for x in d_in]
+        plain.synchronize()
+        want = [_streams(r, nb) for r in res]
+    with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=nb) as plan:
+        plan.set_pipelining(True)
+        res = [glc.compress_batch(plan, d_in[c], n, nb) for c in range(calls)]          # no synchronise in between
+        plan.synchronize()                                                            # (the streams are complete behind it: include/cudpp.h)
+        outs = [glc.decompress_batch(plan, r, n, nb) for r in res]                      # nor here
+        plan.synchronize()
+        plan.set_pipelining(False)
+        res.append(glc.compress_batch(plan, d_in[calls], n, nb))
+        outs.append(glc.decompress_batch(plan, res[calls], n, nb))
+        plan.synchronize()
+        for c in range(calls + 1):
+            got = _streams(res[c], nb)
+            for k in range(4):
+                assert np.array_equal(got[k], want[c][k]), "call %d, array %d" % (c, k)
+            for b in range(nb):
+                assert np.array_equal(got[4][b], want[c][4][b]), "call %d block %d %s" % (c, b, _first_diff(got[4][b], want[c][4][b]))
+            assert torch.equal(outs[c], d_in[c]), "decode of call %d" % c
 
 
 def test_pipelined_calls_match_plain_calls(glc, ctx, cuda):

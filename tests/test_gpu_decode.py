@@ -144,3 +144,43 @@ def test_corrupt_stream_is_reported_not_followed(glc, cuda):
         back = glc.decompress_batch(plan, comp, n, 1)           # the plan is still usable
         plan.synchronize()
         assert np.array_equal(back.cpu().numpy(), x)
+
+
+# the live profile of one compress and one decompress call of two 8192-byte Zipf blocks (none flagged: no tier behind the
+# bucket sorter runs): every bracket once, n * rows units each.  Counts from a run of this test on commit 7cea40a's library.
+PROFILE_UNITS = 8192.0 * 2
+PROFILE_LAUNCHES = {
+    "k_fs_hist": 1, "k_fs_part": 1, "k_fs_sort": 1, "k_mtf_chunk_lists+k_mtf_scan_lists": 1, "k_mtf_encode": 1,
+    "k_huff_build": 1, "k_huff_pack": 1,
+    "k_dec_prepare+k_dec_huff": 1, "k_imtf_pos": 1, "k_imtf_scan+k_imtf_apply": 1, "k_ibwt_hist+k_rs_scan+k_ibwt_lf": 1,
+    "k_ibwt_walk": 1, "k_ibwt_rank+k_ibwt_emit": 1,
+}
+
+
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_profile_counts_of_one_call_each_way(glc, cuda, pipelined):
+    import ctypes as C
+    import torch
+    n, nb = 8192, 2
+    x = np.concatenate([datagen.zipf_bytes(n, seed=61), datagen.zipf_bytes(n, seed=62)])
+    d_in = torch.from_numpy(x).cuda()
+    with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=nb) as plan:
+        comp = glc.compress_batch(plan, d_in, n, nb)              # a finished stream for the decode call to read
+        plan.synchronize()
+        assert plan.last_flagged_blocks() == 0
+        plan.set_pipelining(pipelined)
+        plan.enable_timing(3)
+        again = glc.compress_batch(plan, d_in, n, nb)
+        back = glc.decompress_batch(plan, comp, n, nb)
+        plan.synchronize()
+        assert torch.equal(back, d_in) and torch.equal(again["size"], comp["size"])
+        prof = plan.kernel_profiles()
+        lost = (C.c_ulonglong * 2)()
+        assert glc.lib().glcPlanKernelProfileLost(plan.handle, lost) == glc.CUDPP_SUCCESS
+        ms = plan.last_timing()
+        assert {k: v["launches"] for k, v in prof.items()} == PROFILE_LAUNCHES
+        assert all(v["units"] == PROFILE_UNITS * v["launches"] for v in prof.values())
+        assert tuple(lost) == (0, 0)
+        assert len(ms) == 4 and all(np.isfinite(v) and v >= 0 for v in ms)
+        if pipelined:                                             # the total is the sum of the three spans, in float32 as the library adds them
+            assert ms[3] == float(np.float32(np.float32(np.float32(ms[0]) + np.float32(ms[1])) + np.float32(ms[2])))
