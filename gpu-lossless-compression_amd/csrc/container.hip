@@ -396,7 +396,7 @@ hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, 
 // tables themselves are unverified until k_cd_verdict, so everything read from them is clamped first
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                 unsigned long long P, uint32_t *skip0)
+                                                 unsigned long long P, uint32_t *skip0, uint32_t max_kind)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *W = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR);
@@ -405,7 +405,10 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
     if (b == 0) { f.verdict[0] = 0; f.verdict[1] = ~0ull; }
     if (b < nb) {
-        if (skip0) skip0[b] = W[T.kind + b] == CT_KIND_HUFF0 ? 0u : 1u;    // (version 3: whose tables are built next)
+        if (skip0) {                                           // (version 3 and later: whose tables are built next)
+            const uint32_t kind = W[T.kind + b];
+            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind >= CT_KIND_SPARSE) ? 0u : 1u;
+        }
         const unsigned long long lo = po[b], hi = po[b + 1];
         const bool ok = lo <= hi && hi <= P;
         f.seg_off[b] = (unsigned long long)(uintptr_t)pay + (ok ? 4 * lo : 0);
@@ -417,9 +420,10 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     }
 }
 
-// nun0 (version 3, else null): the units the histogram of each kind-2 block asks for
+// nun0 (version 3 and later, else null): the units the histogram of each kind-2 or kind-3 block asks for; h0: where the
+// verdict leaves what the decoder of the kind-3 blocks needs
 __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                    unsigned long long P, const unsigned long long *nun0)
+                                                    unsigned long long P, const unsigned long long *nun0, CtDecHuff0 h0)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *H = reinterpret_cast<const uint32_t *>(frame);
@@ -431,11 +435,32 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
     const uint32_t kind = W[T.kind + b];
     reinterpret_cast<uint32_t *>(f.verdict + 2)[b] = kind;
     const unsigned long long lo = po[b], hi = po[b + 1];
-    bool bad = kind > (nun0 ? CT_KIND_HUFF0 : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
+    bool bad = kind > (nun0 ? h0.max_kind : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
+    unsigned long long klen = 0;
     if (!bad) {
         const unsigned long long w = hi - lo;
         if (kind == CT_KIND_RAW) bad = w != ct_raw_words(blk_len);
-        else if (kind == CT_KIND_HUFF0) {
+        else if (kind == CT_KIND_SPARSE) {
+            // a sparse record: a fill byte, nothing else set, a whole mask with its unused bits zero (read only once the record
+            // is known to hold it), the counts those of the kept bytes, and behind the mask exactly the units their table asks
+            // for -- so decoding klen symbols consumes the record exactly and the expansion reads exactly klen bytes
+            const uint32_t nch = (blk_len + SP_CHUNK - 1) / SP_CHUNK, mw = sp_mask_words(blk_len);
+            bad = W[T.bwt + b] > 255u;
+            const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
+            for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] != 0;
+            bad = bad || w < mw;
+            if (!bad) {
+                const uint32_t *mask = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR + 4 * T.words) + lo;
+                unsigned long long kept = 0, sum = 0;
+                for (uint32_t i = 0; i < mw; i++) kept += __popc(mask[i]);
+                bad = (nch & 31u) && (mask[mw - 1] >> (nch & 31u)) != 0;
+                const uint32_t last = (mask[(nch - 1) >> 5] >> ((nch - 1) & 31u)) & 1u;
+                klen = bad ? 0 : SP_CHUNK * kept - (last ? SP_CHUNK * nch - blk_len : 0u);
+                const uint32_t *h = W + T.hist + 256ull * b;
+                for (uint32_t s = 0; s < 256; s++) sum += h[s];
+                bad = bad || sum != klen || w != mw + (klen ? nun0[b] : 0ull);
+            }
+        } else if (kind == CT_KIND_HUFF0) {
             // an order-0 record: the counts are the block's, nothing else is set, and the record has exactly the units the
             // table of those counts asks for -- so decoding blk_len symbols consumes it exactly
             unsigned long long sum = 0;
@@ -449,6 +474,13 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
             const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
             for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] >= w || (s > 0 && eo[s] <= eo[s - 1]);
         }
+    }
+    if (nun0 && h0.max_kind >= CT_KIND_SPARSE) {
+        const bool k3 = !bad && kind == CT_KIND_SPARSE;
+        h0.k_off[b] = (unsigned long long)(uintptr_t)(h0.kept + (size_t)(b % h0.chunk) * h0.kept_stride);
+        h0.k_len[b] = k3 ? klen : 0;
+        h0.u_off[b] = k3 ? lo + sp_mask_words(blk_len) : 0;
+        h0.skip3[b] = k3 && klen ? 0u : 1u;
     }
     if (bad) atomicMin(&f.verdict[1], ((unsigned long long)CT_FRAME_TABLE << 32) | b);
     else if (f.crc[b] != W[T.crc_rec + b]) atomicMin(&f.verdict[1], ((unsigned long long)CT_RECORD_CRC << 32) | b);
@@ -492,7 +524,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
                          unsigned long long payload_words, const CtDecHuff0 *h0, KernelProf *prof)
 {
     hipLaunchKernelGGL(k_cd_segs, dim3((nb + 2 + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
-                       h0 ? h0->skip : nullptr);
+                       h0 ? h0->skip : nullptr, h0 ? h0->max_kind : CT_KIND_RAW);
     hipError_t e = hipSuccess;
     if (h0) {
         const CtTables T = ct_tables(nb, blk_len);
@@ -504,7 +536,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
     e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb + 2, f.crc);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_cd_verdict, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
-                       h0 ? (const unsigned long long *)h0->nun : nullptr);
+                       h0 ? (const unsigned long long *)h0->nun : nullptr, h0 ? *h0 : CtDecHuff0{});
     return hipGetLastError();
 }
 

@@ -2,18 +2,19 @@
 // A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says two
 // things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
-// 1 raw always, 2 order-0 Huffman where kind2_legal()).  CT_LEGAL below is the one table of legal triples: format_of() picks the
+// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal()).  CT_LEGAL below is the one table of legal triples: format_of() picks the
 // writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's.
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
-// and the batched encoder writes the kind-2 records.  Either way the kernels of container.hip decide the record kinds before the
+// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3).  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
 // Decode: decode_walk() is the one loop over a stream's frames, fed either from the caller's device buffers or from a Source
 // through staging.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
 // verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
-// place, runs of kind 2 to the batched order-0 decoder, and the decoded bytes are checked against the blocks' CRCs; a filtered
+// place, runs of kind 2 to the batched order-0 decoder, runs of kind 3 to it as well (the kept bytes into scratch, then expanded
+// under the record's mask), and the decoded bytes are checked against the blocks' CRCs; a filtered
 // frame is decoded into staging, checked there and inverted into the output by filter_device().
 #include "../../include/glc_container.h"
 #include "container_internal.h"
@@ -97,7 +98,8 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 constexpr struct { uint32_t version, flags, elems; } CT_LEGAL[] = {
     {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
-    {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}};
+    {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
+    {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}};
 
 bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
 
@@ -116,7 +118,7 @@ CtFormat format_of(const CtSettings &s)
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
     for (const auto &l : CT_LEGAL) {
         f.version = l.version;
-        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal())) break;
+        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal())) break;
     }
     return f;                                                 // (the setters accept only what some row takes)
 }
@@ -169,6 +171,8 @@ struct Encoder {
     CtFormat fmt;                                             // what the plan's settings write
     uint32_t codec = CT_CODEC_BWT;                            // the plan's container codec
     CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
+    bool sparse = false;                                      // the codec's sparse mode
+    CtEncSparse sp = {};                                      // its scratch, behind h0's; a plan that never has it on has none
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     void carve_huff0(Carver &c)
@@ -181,6 +185,22 @@ struct Encoder {
         h0.lens = c.take<uint8_t>(256 * R);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_encode_work_bytes(R));
+        if (!sparse) return;
+        // everything of a frame runs on the plan's stream in order, so one compaction space serves pipelined calls as well
+        sp.mask_stride = sp_mask_words(P.n);
+        sp.kept_stride = (P.n + 15u) & ~15u;
+        sp.klen = c.take<unsigned long long>(R);
+        sp.kept_off = c.take<unsigned long long>(R);
+        sp.unit_off = c.take<unsigned long long>(R);
+        sp.blk_off = c.take<unsigned long long>(R);
+        sp.blk_len = c.take<unsigned long long>(R);
+        sp.mask = c.take<uint32_t>(R * sp.mask_stride);
+        sp.fill = c.take<uint32_t>(R);
+        sp.is3 = c.take<uint32_t>(R);
+        sp.skip_move = c.take<uint32_t>(R);
+        sp.skip_table = c.take<uint32_t>(R);
+        c.align(256);
+        sp.kept = c.take<uint8_t>(R * sp.kept_stride);
     }
     void carve(Carver &c)
     {
@@ -210,6 +230,7 @@ struct Encoder {
         const CtSettings &s = plan_container_settings(P.h);
         fmt = format_of(s);
         codec = s.codec;
+        sparse = s.sparse && codec == CT_CODEC_HUFF0;
         if (codec == CT_CODEC_HUFF0) {
             Carver measure;
             carve_huff0(measure);
@@ -250,6 +271,7 @@ struct Encoder {
             orig = d_in;
             d_in = stage[P.parity];
         }
+        if (sparse) return frame_sparse(f, d_in, orig, nb, blk_len, out, cap);
         if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
@@ -275,6 +297,39 @@ struct Encoder {
         CT_TRY(ct_enc_kind0(P.st, f, h0, nb, blk_len, state));
         CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
         CT_TRY(hdb_encode(P.st, g, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4, f.only, h0.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
+    }
+
+    // frame_huff0 with the sparse mode on: tables of the whole blocks -> fill bytes -> masks -> kind 3 or 2 (histograms corrected)
+    // -> compaction of the kind-3 blocks -> their tables, of K -> record sizes and the raw rule -> payload offsets -> masks into
+    // the records and every stream encoded behind its mask (kind 2 from the frame, kind 3 from the compaction space)
+    CUDPPResult frame_sparse(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
+                             uint8_t *out, unsigned long long cap)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        plan_stage_mark(P.h, 0);
+        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));
+        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
+        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+        CT_TRY(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
+        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));        // (klen itself comes two steps on)
+        CT_TRY(ct_block_offsets(P.st, sp.blk_off, sp.blk_len, nb, blk_len));
+        SpSegs s{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr, sp.mask_stride,
+                 nullptr, nb, blk_len};
+        CT_TRY(sparse_mask(P.st, s));
+        CT_TRY(ct_enc_sparse_decide(P.st, s, sp, f.hist, h0.in_off, h0.in_len));
+        s.skip = sp.skip_move;
+        CT_TRY(sparse_compact(P.st, s));
+        const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
+        CT_TRY(hdb_tables(P.st, g2, false, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_sparse_kind(P.st, f, h0, sp, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
+        CT_TRY(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, reinterpret_cast<uint32_t *>(out), cap / 4));
+        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), sp.unit_off, cap / 4, f.only, h0.work, prof));
         plan_stage_mark(P.h, 2);
         CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
         plan_stage_mark(P.h, 3);
@@ -320,6 +375,15 @@ struct Decoder {
         h0.lut = c.take<uint16_t>(2048 * (size_t)nb);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_decode_work_bytes(h0.chunk, blk_len));
+        h0.max_kind = fmt.max_kind();
+        if (!fmt.kind3_legal()) return;
+        h0.k_off = c.take<unsigned long long>(n4);
+        h0.k_len = c.take<unsigned long long>(n4);
+        h0.u_off = c.take<unsigned long long>(n4);
+        h0.skip3 = c.take<uint32_t>(n4);
+        c.align(256);
+        h0.kept_stride = (blk_len + 15u) & ~15u;
+        h0.kept = c.take<uint8_t>((size_t)h0.chunk * h0.kept_stride);
     }
     hipError_t reserve_huff0(uint32_t nb, uint32_t blk_len)
     {
@@ -414,6 +478,17 @@ struct Decoder {
             const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, b - a, blk_len};
             CT_TRY(hdb_decode(P.st, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, h0.nun + a,
                               h0.lut + 2048ull * a, g, nullptr, h0.work, prof));
+            a = b;
+        }
+        for (uint32_t a = 0; fmt.kind3_legal() && a < nb;) {    // runs of sparse blocks: K decoded into scratch, then expanded
+            if (kind[a] != CT_KIND_SPARSE) { a++; continue; }
+            uint32_t b = a;
+            while (b < nb && kind[b] == CT_KIND_SPARSE && b - a < h0.chunk) b++;
+            const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, b - a, blk_len};
+            CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
+            const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
+                           reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, 0, nullptr, b - a, blk_len};
+            CT_TRY(sparse_join(P.st, s));
             a = b;
         }
         plan_join(P.h);
@@ -614,6 +689,8 @@ CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned
     CUDPPResult r = feed.header(hdr, 0, CT_HDR, ~0ull);
     if (r != CUDPP_SUCCESS) return r;
     if (!check_stream_header(hdr, &D.fmt, &block_len, total)) return fail(plan, CT_STREAM_HEADER);
+    if (D.fmt.kind3_legal() && !plan_container_settings(plan).sparse)   // a plan with the sparse mode off is a version-4 reader
+        return fail(plan, CT_STREAM_HEADER);
     if (*total > cap) return fail(plan, CT_CAPACITY);
     CT_TRY(D.begin());
     unsigned long long pos = CT_HDR, done = 0;
@@ -851,6 +928,44 @@ CUDPPResult glcUnshuffleSegments(const void *d_inBase, void *d_outBase, const un
     return shuffle_segments_api(d_inBase, d_outBase, d_offsets, d_lengths, count, elem, stream, true);
 }
 
+// the two sparse calls: a bad argument is refused before anything is enqueued
+static bool sparse_args_ok(const void *a, const void *b, const void *c, const void *d, const void *e, const void *f, size_t count, size_t maxLen)
+{
+    return count <= 0xFFFFFFFFull && maxLen <= GLC_SPARSE_MAX_LEN && (count == 0 || (a && b && c && d && e && f));
+}
+
+CUDPPResult glcSparseSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, const unsigned int *d_fill, unsigned int *d_mask, void *d_keptBase,
+                                   unsigned long long *d_keptLen, void *stream)
+{
+    if (!sparse_args_ok(d_inBase, d_offsets, d_lengths, d_fill, d_mask, d_keptBase, count, maxLen) || (count && !d_keptLen) ||
+        (count && d_inBase == d_keptBase) || (reinterpret_cast<uintptr_t>(d_mask) & 3))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const SpSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, static_cast<uint8_t *>(d_keptBase), d_offsets,
+                   d_fill, d_mask, nullptr, sp_mask_words((uint32_t)maxLen), nullptr, (uint32_t)count, (uint32_t)maxLen};
+    CT_TRY(sparse_mask(st, g));
+    CT_TRY(sparse_count(st, g, d_keptLen));
+    CT_TRY(sparse_compact(st, g));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_fill, const unsigned int *d_mask, void *d_outBase,
+                                  void *stream)
+{
+    if (!sparse_args_ok(d_keptBase, d_offsets, d_lengths, d_fill, d_mask, d_outBase, count, maxLen) || (count && d_keptBase == d_outBase) ||
+        (reinterpret_cast<uintptr_t>(d_mask) & 3))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    const SpSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, static_cast<uint8_t *>(const_cast<void *>(d_keptBase)), d_offsets,
+                   d_fill, const_cast<unsigned int *>(d_mask), nullptr, sp_mask_words((uint32_t)maxLen), nullptr, (uint32_t)count,
+                   (uint32_t)maxLen};
+    CT_TRY(sparse_join(reinterpret_cast<hipStream_t>(stream), g));
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
 {
     return shuffle_device_api(d_in, d_out, len, elem, stream, false);
@@ -897,7 +1012,19 @@ CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    plan_container_settings(plan).codec = codec;
+    CtSettings &s = plan_container_settings(plan);
+    s.codec = codec;
+    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = false;   // (no sparse mode without the order-0 codec)
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    CtSettings &s = plan_container_settings(plan);
+    if (on > 1 || (on && s.codec != GLC_CONTAINER_CODEC_HUFF0)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    s.sparse = on != 0;
     return CUDPP_SUCCESS;
 }
 
@@ -925,6 +1052,15 @@ CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     *codec = plan_container_settings(plan).codec;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerSparse(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).sparse ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

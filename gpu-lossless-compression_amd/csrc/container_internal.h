@@ -86,6 +86,25 @@ hipError_t shuffle_segments(hipStream_t st, const uint8_t *inBase, uint8_t *outB
 // segment, the same rules
 hipError_t delta_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, bool inverse);
 
+// the sparse passes (sparse.hip).  Segment i is `data` + data_off[i], min(data_len[i], max_len) bytes, cut into chunks of 64; its
+// mask (bit c % 32 of word c / 32 = chunk c is kept, i.e. not all fill[i] & 255) is at mask + (mask_off ? mask_off[i] : i *
+// mask_stride) words, its kept chunks K at kept + kept_off[i].  Either base may be null with absolute addresses in the offsets.
+// skip (optional): segments whose entry is non-zero are left alone.  Everything only enqueues on `st`.
+constexpr uint32_t SP_CHUNK = 64;
+__host__ __device__ inline uint32_t sp_mask_words(uint32_t len) { return ((len + SP_CHUNK - 1) / SP_CHUNK + 31) / 32; }
+struct SpSegs {
+    uint8_t *data; const unsigned long long *data_off, *data_len;
+    uint8_t *kept; const unsigned long long *kept_off;
+    const uint32_t *fill;
+    uint32_t *mask; const unsigned long long *mask_off; uint32_t mask_stride;
+    const uint32_t *skip;
+    uint32_t count, max_len;
+};
+hipError_t sparse_mask(hipStream_t st, const SpSegs &g);                                  // data -> mask
+hipError_t sparse_count(hipStream_t st, const SpSegs &g, unsigned long long *d_klen);     // mask -> bytes of K
+hipError_t sparse_compact(hipStream_t st, const SpSegs &g);                               // data, mask -> K
+hipError_t sparse_join(hipStream_t st, const SpSegs &g);                                  // K, mask, fill -> data
+
 // ---------------------------------------------------------------------------
 // layout (little-endian; every section 8-byte aligned)
 // ---------------------------------------------------------------------------
@@ -96,6 +115,7 @@ constexpr uint32_t CT_VERSION = 1, CT_VERSION_SHUFFLE = 2;   // 2: header word 3
 constexpr uint32_t CT_VERSION_CODEC = 3;                     // 3: kind 2 is legal; header word 3 = element size or 0 (no filter)
 constexpr uint32_t CT_VERSION_DELTA = 4;                     // 4: version 3 with flags in the upper half of the version dword
 constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the only one): the filter is delta + shuffle; elem 2, 4 or 8
+constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is legal; flags 0 (elem 0, 2, 4, 8) or the delta flag (elem 2, 4, 8)
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
@@ -104,10 +124,13 @@ struct CtFormat {
     bool filtered() const { return elem != 0; }
     bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
+    bool kind3_legal() const { return version >= CT_VERSION_SPARSE; }
+    uint32_t max_kind() const { return kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
+constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 record (sparse.hip): mask, then the kind-2 stream of the kept chunks; version 5
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
 
 // failure classes of glcContainerLastError (out[0])
@@ -146,8 +169,8 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, CompressCall c, ContainerHook
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
-// mode (only ever on with the shuffle on) and the codec (CT_CODEC_*)
-struct CtSettings { uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; };
+// mode (only ever on with the shuffle on), the codec (CT_CODEC_*) and its sparse mode (only ever on with the order-0 codec)
+struct CtSettings { uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false; };
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
@@ -184,12 +207,30 @@ struct CtEncHuff0 {                                        // device scratch of 
     uint16_t *codes;                                       // [rows][256]
     void *work;                                            // hdb_encode_work_bytes(rows)
 };
+struct CtEncSparse {                                       // device scratch of the sparse mode, behind CtEncHuff0's (allocated once it is on)
+    uint32_t *mask; uint32_t mask_stride;                  // [rows][mask_stride] words
+    uint32_t *fill, *is3, *skip_move, *skip_table;         // [rows]: fill byte; kind 3 chosen; 1 = not compacted; 1 = no table of K
+    unsigned long long *klen, *kept_off, *unit_off;        // [rows]: bytes of K; K's place in `kept`; where the block's stream starts
+    unsigned long long *blk_off, *blk_len;                 // [rows]: the blocks as segments of the frame
+    uint8_t *kept; uint32_t kept_stride;                   // [rows][kept_stride] bytes: the compaction space
+};
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 // the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
 // mask (1 = raw) and f.bwt zeros
 hipError_t ct_block_offsets(hipStream_t st, unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len);   // off[b] = b * blk_len
 hipError_t ct_enc_kind0(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+// the sparse mode's steps (sparse.hip), in order: the fill byte of every block from its histogram; kind 3 or 2 from the mask,
+// with the histogram corrected to K's and (in_off, in_len) turned into what the tables and the encoder read (absolute
+// addresses); ct_enc_kind0's sibling (record sizes, raw rule, skip mask, the fill into f.bwt); and behind the payload offsets
+// the masks into the records and sp.unit_off = where each block's stream starts
+hipError_t ct_enc_sparse_fill(hipStream_t st, const uint32_t *hist, uint32_t nb, uint32_t *fill);
+hipError_t ct_enc_sparse_decide(hipStream_t st, const SpSegs &g, const CtEncSparse &sp, uint32_t *hist, unsigned long long *in_off,
+                                unsigned long long *in_len);
+hipError_t ct_enc_sparse_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, uint32_t nb,
+                              uint32_t blk_len, const CtEncState *state);
+hipError_t ct_enc_sparse_place(hipStream_t st, const CtEncFrame &f, const CtEncSparse &sp, uint32_t nb, uint32_t blk_len, uint32_t *out,
+                               unsigned long long cap_words);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
@@ -208,8 +249,14 @@ struct CtDecHuff0 {                                        // device scratch of 
     uint16_t *lut;                                         // [nb][2048]
     void *work;                                            // hdb_decode_work_bytes(chunk, blk_len)
     uint32_t chunk;                                        // blocks one hdb_decode call may take
+    // version 5 (max_kind 3): what the verdict leaves for the kind-3 blocks -- K's place in `kept` (block b in slot b % chunk)
+    // and length, where the stream starts behind the mask, and 1 = nothing to decode (not kind 3, or nothing kept)
+    uint32_t max_kind;
+    unsigned long long *k_off, *k_len, *u_off;             // [nb]
+    uint32_t *skip3;                                       // [nb]
+    uint8_t *kept; uint32_t kept_stride;                   // [chunk][kept_stride]
 };
-// h0 (version 3, else null): kind 2 is legal; its blocks' tables are built from the unverified histograms first, and the
+// h0 (version 3 and later, else null): kind 2 is legal, and kind 3 where h0->max_kind says so; its blocks' tables are built from the unverified histograms first, and the
 // units they ask for are one of the block's field checks
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
                          unsigned long long payload_words, const CtDecHuff0 *h0 = nullptr, KernelProf *prof = nullptr);

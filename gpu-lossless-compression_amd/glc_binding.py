@@ -654,7 +654,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcContainerDecompress", "glcContainerCompressFile", "glcContainerDecompressFile", "glcCrc32Segments",
                      "glcContainerLastError", "glcShuffleSegments", "glcUnshuffleSegments", "glcShuffleDevice", "glcUnshuffleDevice",
                      "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec",
-                     "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta"]
+                     "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta",
+                     "glcSparseSplitSegments", "glcSparseJoinSegments", "glcPlanSetContainerSparse", "glcPlanGetContainerSparse"]
 CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0 = 0, 1
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
@@ -685,6 +686,10 @@ def _ct():
         L.glcPlanGetContainerCodec.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcPlanSetContainerDelta.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerDelta.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcPlanSetContainerSparse.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerSparse.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcSparseSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.glcSparseJoinSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
         for nm in CONTAINER_SYMBOLS[1:]:
             getattr(L, nm).restype = C.c_int
         L._ct_ready = True
@@ -798,6 +803,61 @@ def container_get_delta(plan):
     d = C.c_uint(0)
     _chk("glcPlanGetContainerDelta", _ct().glcPlanGetContainerDelta(plan.handle, C.byref(d)))
     return int(d.value)
+
+
+def container_set_sparse(plan, on):
+    """the sparse mode of the plan's container ENCODER (format version 5): True / 1 needs the order-0 codec;
+    container_set_codec(plan, CONTAINER_CODEC_BWT) also switches it off.  It is also the version the plan reads: on, versions 1
+    to 5; off, versions 1 to 4, and a version-5 stream is a stream-header failure as it always was."""
+    _chk("glcPlanSetContainerSparse", _ct().glcPlanSetContainerSparse(plan.handle, int(on)))
+
+
+def container_get_sparse(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerSparse", _ct().glcPlanGetContainerSparse(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def sparse_mask_words(max_len):
+    return ((int(max_len) + 63) // 64 + 31) // 32
+
+
+def _sparse_args(d_base, offsets, lengths, fill):
+    import torch
+    dev = d_base.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    fl = torch.as_tensor(fill, dtype=torch.int32).to(dev)
+    assert off.numel() == ln.numel() == fl.numel()
+    return off, ln, fl
+
+
+def sparse_split_segments(d_in, d_kept, offsets, lengths, fill, max_len=None, stream=None):
+    """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in, cut into 64-byte chunks: the chunks that are not
+    all fill[i] go, in order, to d_kept at offsets[i].  Returns (mask int32 tensor [count, sparse_mask_words(max_len)], kept
+    lengths int64 tensor [count])"""
+    import torch
+    off, ln, fl = _sparse_args(d_in, offsets, lengths, fill)
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    mask = torch.zeros((off.numel(), max(1, sparse_mask_words(max_len))), dtype=torch.int32, device=d_in.device)
+    klen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
+    _chk("glcSparseSplitSegments", _ct().glcSparseSplitSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
+                                                                 fl.data_ptr(), mask.data_ptr(), d_kept.data_ptr(), klen.data_ptr(), stream))
+    torch.cuda.synchronize(d_in.device)                        # (off / ln / fl are temporaries of this call)
+    return mask[:, :sparse_mask_words(max_len)], klen[:off.numel()]
+
+
+def sparse_join_segments(d_kept, d_out, offsets, lengths, fill, mask, max_len=None, stream=None):
+    """the inverse of sparse_split_segments: `mask` is its mask tensor (rows of sparse_mask_words(max_len) words)"""
+    import torch
+    off, ln, fl = _sparse_args(d_kept, offsets, lengths, fill)
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    m = mask.contiguous()
+    assert m.numel() == off.numel() * sparse_mask_words(max_len) or sparse_mask_words(max_len) == 0
+    _chk("glcSparseJoinSegments", _ct().glcSparseJoinSegments(d_kept.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
+                                                               fl.data_ptr(), m.data_ptr(), d_out.data_ptr(), stream))
+    torch.cuda.synchronize(d_kept.device)
+    return d_out
 
 
 def _shuffle(fn, d_in, elem, out, stream):

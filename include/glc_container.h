@@ -28,6 +28,15 @@
  * after the delta, which is what the order-0 codec needs: the model's sizes are in INTEGRATION.md 4b.  It hurts
  * noise-like data.  The decoder reads what was done from the stream header.
  *
+ * Sparse data (zero pages, masks, tensors with few non-zeros, the all-zero byte planes of a shuffled integer series): the sparse
+ * mode of the order-0 codec, off by default.  A Huffman code spends at least one bit per byte, so a block of one repeated byte
+ * still costs an eighth of its size.  With glcPlanSetContainerSparse on, a block is cut into chunks of 64 bytes, the chunks that
+ * consist of the block's most frequent byte are left out, a mask of one bit per chunk says which, and only the kept chunks are
+ * Huffman-coded (record kind 3); a block with fewer than one such chunk in 32 stays an ordinary order-0 record.  The stream is
+ * format version 5.  The model's sizes are in INTEGRATION.md 4b ("sparse: when").  Measured on one MI355X on 1 GiB of int64
+ * timestamps in 1 MiB blocks with delta + shuffle 8 (profiles/sparse_mode.md): ratio 6.771 against 4.192 with the mode off, encode
+ * 460 against 417 GB/s, decode 174 against 134 GB/s; uint32 counters 9.999 against 5.280, 468 against 424 and 199 against 146.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -105,6 +114,23 @@ CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long
 CUDPPResult glcDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 
+/* The two passes of the sparse mode as batched calls (csrc/sparse.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of
+ * its base, cut into chunks of 64 bytes (the last may be short); d_fill[i] & 255 is its fill byte, given by the caller; its mask is
+ * row i of d_mask, rows of ceil(ceil(maxLen / 64) / 32) words: bit c % 32 of word c / 32 is 1 when chunk c is kept, 0 when every
+ * byte of it equals the fill, and 0 past the last chunk.  Split writes the mask words of every segment, its kept chunks in order
+ * at d_keptBase + d_offsets[i] (at most the segment's length) and their byte count to d_keptLen[i].  Join takes the mask, the fill
+ * and the kept bytes (exactly the bytes the mask asks for: 64 per kept chunk, fewer for a kept short last chunk) and writes
+ * d_lengths[i] bytes at d_outBase + d_offsets[i].  Any length up to GLC_SPARSE_MAX_LEN, any byte alignment, out of place; the calls
+ * only enqueue on `stream`.  A bad argument (a null pointer with count > 0, equal bases, a mask not 4-byte aligned, a maxLen
+ * or count too large) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_SPARSE_MAX_LEN ((size_t)1 << 28)
+CUDPPResult glcSparseSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, const unsigned int *d_fill, unsigned int *d_mask, void *d_keptBase,
+                                   unsigned long long *d_keptLen, void *stream);
+CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_fill, const unsigned int *d_mask, void *d_outBase,
+                                  void *stream);
+
 /* The element size the container ENCODER of this plan shuffles by: 0 or 1 = off (the default), 2, 4, 8; anything else is
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it; the decoder
  * ignores it (the stream header says what was done).  The first filtered call allocates device staging of one frame (rows * n
@@ -116,7 +142,7 @@ CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem);
  * format version 4 (flags = 1), with either codec; 0 (the default) writes versions 1 to 3 byte for byte as ever.  on = 1 while
  * the plan's shuffle is off, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.
  * glcPlanSetContainerShuffle(plan, 0 or 1) also switches the delta off; a change among 2, 4 and 8 keeps it.  The decoder
- * ignores the setting and reads all four versions. */
+ * ignores the setting and reads every version. */
 CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on);
 
@@ -124,7 +150,7 @@ CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on);
  * the shuffle filter on, byte for byte as ever.  GLC_CONTAINER_CODEC_HUFF0 writes version 3: a block is an order-0 Huffman
  * record (its histogram in the tables, the table rebuilt from it) or, when 4 * words >= block bytes, raw.  Any other value is
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it, with
- * pipelining on or off; the decoder ignores it (the stream says what was done) and reads all three versions.  The first HUFF0
+ * pipelining on or off; the decoder ignores it (the stream says what was done) and reads every version.  The first HUFF0
  * encode allocates about 3 KiB of device scratch per row, the first version-3 decode 4 KiB per block of the largest frame plus
  * up to 256 MiB of span-function prefixes; both live as long as the plan, and a plan that only uses the BWT codec has neither.
  * The order-0 path never touches the sorter's scratch or statistics. */
@@ -135,6 +161,19 @@ enum GlcContainerCodec
 };
 CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec);
 CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec);
+
+/* The sparse mode of the ENCODER's order-0 codec: on = 1 writes format version 5, where a block whose most frequent byte fills
+ * at least one 64-byte chunk in 32 becomes a sparse record (kind 3: fill byte, chunk mask, the order-0 stream of the kept
+ * chunks) and every other block an order-0 or raw record as in version 3 / 4; 0 (the default) writes versions 1 to 4 byte for
+ * byte as ever.  on = 1 while the plan's codec is not GLC_CONTAINER_CODEC_HUFF0, and any other value, are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; glcPlanSetContainerCodec(plan, GLC_CONTAINER_CODEC_BWT) also
+ * switches it off.  All six container entry points honour it, with pipelining on or off and with any filter setting.  The setting
+ * is also the version the plan speaks: a plan with it on reads versions 1 to 5, a plan with it off is a version-4 reader to which a
+ * version-5 stream is a stream-header failure, as it was before version 5 existed (so a reader of sparse streams sets the
+ * HUFF0 codec and the mode on; its other settings stay ignored).  The first sparse encode allocates rows * n bytes of compaction space and the masks, the
+ * first version-5 decode as much for the blocks of one decoder chunk; both are kept with the plan and freed with it. */
+CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerSparse(CUDPPHandle plan, unsigned int *on);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -18,7 +18,13 @@ ids32 (sorted uint32 ids below 2^31), ctr32 (uint32 counters, Poisson(3) increme
 uint16).  --delta switches the filter's delta mode on for the filtered setting (glcPlanSetContainerDelta, format version 4), --codec 1
 the order-0 codec for both settings.
 
-python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]"""
+--rounds R (typed data, --codec 1) replaces the filter section by the sparse section: the filter on (with --delta: in delta mode), the
+order-0 codec, and R interleaved rounds of encode and decode timed with device events -- with --sparse each round runs the sparse
+mode off and then on (glcPlanSetContainerSparse, format version 5), without it only off, which is also what a build without the
+mode can run.  Every round's rates are reported, with their median and spread (max - min) per setting.
+
+python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]
+                                [--rounds R] [--sparse]"""
 import argparse
 import json
 import os
@@ -106,6 +112,52 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
     return res
 
 
+def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse):
+    """the order-0 container with the sparse mode off and (with_sparse) on, interleaved: `rounds` rounds of one encode and one
+    decode per setting after one untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    glc.container_set_shuffle(plan, elem)
+    if elem and delta:
+        glc.container_set_delta(plan, 1)
+    settings = ["off", "sparse"] if with_sparse else ["off"]
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            if with_sparse:
+                glc.container_set_sparse(plan, 1 if s == "sparse" else 0)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -116,6 +168,8 @@ def main():
     ap.add_argument("--shuffle", type=int, default=0, choices=[0, 2, 4, 8], metavar="ELEM")
     ap.add_argument("--delta", action="store_true", help="the filtered setting uses the filter's delta mode (format version 4)")
     ap.add_argument("--codec", type=int, default=0, choices=[0, 1], help="the filter section's container codec: 0 BWT, 1 order-0")
+    ap.add_argument("--rounds", type=int, default=0, help="typed data: the sparse section, this many interleaved rounds timed with device events")
+    ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -157,7 +211,12 @@ def main():
             plan.set_pipelining(bool(args.pipelining))
             glc.container_set_codec(plan, args.codec)
             res["codec"] = args.codec
-            res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
+            if args.rounds:
+                assert args.codec == 1, "the sparse section is the order-0 codec's"
+                res["sparse"] = sparse_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.delta, args.rounds,
+                                               args.sparse)
+            else:
+                res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
         print(json.dumps(res))
         return
     # --- CRC against the read probe
