@@ -487,11 +487,12 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
 }
 
 // raw records out (verified); every block's output range becomes a segment for the decoded-bytes check
-__global__ __launch_bounds__(256) void k_cd_raw(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out)
+__global__ __launch_bounds__(256) void k_cd_raw(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out,
+                                                uint32_t first)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *W = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR);
-    const uint32_t b = blockIdx.y;
+    const uint32_t b = first + blockIdx.y;
     uint8_t *dst = out + (size_t)b * blk_len;
     if (blockIdx.x == 0 && threadIdx.x == 0) { f.seg_off[b] = (unsigned long long)(uintptr_t)dst; f.seg_len[b] = blk_len; }
     if (W[T.kind + b] != CT_KIND_RAW) return;
@@ -506,12 +507,12 @@ __global__ __launch_bounds__(256) void k_cd_raw(CtDecFrame f, const uint8_t *fra
 }
 
 __global__ __launch_bounds__(256) void k_cd_check(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                  uint32_t frame_index, CtDecState *state)
+                                                  uint32_t frame_index, CtDecState *state, uint32_t first, uint32_t end)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *W = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR);
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b < nb && f.crc[b] != W[T.crc_raw + b]) atomicMin(&state->err, (((unsigned long long)frame_index << 32) | b) + 1);
+    const uint32_t b = first + blockIdx.x * 256 + threadIdx.x;
+    if (b < end && f.crc[b] != W[T.crc_raw + b]) atomicMin(&state->err, (((unsigned long long)frame_index << 32) | b) + 1);
 }
 
 __global__ void k_cd_end(uint32_t nb, uint32_t blk_len, CtDecState *state)
@@ -540,20 +541,27 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
     return hipGetLastError();
 }
 
-hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out)
+hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out,
+                      uint32_t first, uint32_t count)
 {
-    hipLaunchKernelGGL(k_cd_raw, dim3(min(8u, (ct_raw_words(blk_len) + 255) / 256), nb), dim3(256), 0, st, f, frame, nb, blk_len, out);
+    if (first >= nb) return hipSuccess;
+    if (count == 0 || count > nb - first) count = nb - first;
+    hipLaunchKernelGGL(k_cd_raw, dim3(min(8u, (ct_raw_words(blk_len) + 255) / 256), count), dim3(256), 0, st, f, frame, nb, blk_len, out,
+                       first);
     return hipGetLastError();
 }
 
 hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold)
+                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold, uint32_t first, uint32_t count)
 {
     (void)out;                                                 // (k_cd_raw put the output ranges in f.seg_*)
-    hipError_t e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb, f.crc);
+    if (first >= nb) return hipSuccess;
+    if (count == 0 || count > nb - first) count = nb - first;
+    hipError_t e = crc32_segments(st, nullptr, f.seg_off + first, f.seg_len + first, count, f.crc + first);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_cd_check, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, frame_index, state);
-    if (!fold) return hipGetLastError();
+    hipLaunchKernelGGL(k_cd_check, dim3((count + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, frame_index, state, first,
+                       first + count);
+    if (!fold || count != nb) return hipGetLastError();
     hipLaunchKernelGGL(k_fold_terms, dim3((nb + 255) / 256), dim3(256), 0, st, (const uint32_t *)f.crc, nb, blk_len, &state->frame_acc);
     hipLaunchKernelGGL(k_cd_end, dim3(1), dim3(1), 0, st, nb, blk_len, state);
     return hipGetLastError();
@@ -566,6 +574,50 @@ hipError_t ct_dec_fold(hipStream_t st, const CtDecFrame &f, const uint8_t *bytes
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fold_terms, dim3((nb + 255) / 256), dim3(256), 0, st, (const uint32_t *)f.crc, nb, blk_len, &state->frame_acc);
     hipLaunchKernelGGL(k_cd_end, dim3(1), dim3(1), 0, st, nb, blk_len, state);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// the frame index of a container in device memory: ct_walk, the walk every reader makes, run by one thread.  The chain is
+// serial by nature -- a frame's size is in its header and the next header lies behind it -- so there is nothing for a second
+// lane to do: one dependent 32-byte read per frame.  Every read lies inside [in, in + len): the walk tests the position of a
+// header against len before it fetches it.  Entry fi is written only while fi < cap.
+// ---------------------------------------------------------------------------
+__global__ void k_ct_index(const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t sparse_reader, CtIndexHead *head,
+                           CtFrameRef *entries, unsigned long long cap)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    CtIndexHead h = {};
+    const CtWalkEnd end = ct_walk(
+        g_crc, len, plan_n, sparse_reader != 0,
+        [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long) {
+            const uint32_t *src = reinterpret_cast<const uint32_t *>(in + pos);       // (pos is a multiple of 8, as is `in`)
+            for (uint32_t i = 0; i < bytes / 4; i++) dst[i] = src[i];
+            return true;
+        },
+        [&](const uint32_t *hdr, const CtFormat &, uint32_t, unsigned long long) {
+            for (int i = 0; i < 8; i++) h.hdr[i] = hdr[i];
+            return true;
+        },
+        [&](uint32_t fi, const uint32_t *, const CtFrameRef &ref) {
+            if (fi >= cap) return false;
+            entries[fi] = ref;
+            h.frames = fi + 1;
+            return true;
+        },
+        [&](const uint32_t *tr, uint32_t) {
+            for (int i = 0; i < 4; i++) h.trailer[i] = tr[i];
+            return true;
+        });
+    h.what = end.what;
+    h.frame = end.frame;
+    *head = h;
+}
+
+hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, bool sparse_reader,
+                           CtIndexHead *head, CtFrameRef *entries, unsigned long long cap)
+{
+    hipLaunchKernelGGL(k_ct_index, dim3(1), dim3(64), 0, st, in, len, plan_n, sparse_reader ? 1u : 0u, head, entries, cap);
     return hipGetLastError();
 }
 

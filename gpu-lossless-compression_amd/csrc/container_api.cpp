@@ -2,16 +2,17 @@
 // A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says two
 // things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
-// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal()).  CT_LEGAL below is the one table of legal triples: format_of() picks the
-// writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's.
+// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
+// writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's (both read ct_legal()).
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
 // and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3).  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
-// Decode: decode_walk() is the one loop over a stream's frames, fed either from the caller's device buffers or from a Source
-// through staging.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
+// Decode: decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from the caller's
+// device buffers or from a Source through staging; the frame index (glcContainerIndex*) is the same walk without the decoding,
+// and a range read (glcContainerReadRange*) decodes a subset of the blocks of the frames its range overlaps.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
 // verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
 // place, runs of kind 2 to the batched order-0 decoder, runs of kind 3 to it as well (the kept bytes into scratch, then expanded
 // under the record's mask), and the decoded bytes are checked against the blocks' CRCs; a filtered
@@ -19,15 +20,27 @@
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 
+#include <fcntl.h>
+#include <memory>
 #include <mutex>
 #include <map>
 #include <new>
 #include <stdio.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <unistd.h>
 #include <vector>
 
 using namespace glc;
+
+// the frame index of one container (glcContainerIndex*): what the walk over its headers found, kept on the host
+struct GlcContainerIndex {
+    uint32_t hdr[8] = {}, trailer[4] = {};                    // copies of the stream header and of the trailer
+    unsigned long long len = 0, total = 0;                    // container bytes; input bytes
+    uint32_t block_len = 0;
+    CtFormat fmt;
+    std::vector<CtFrameRef> frames;
+};
 
 namespace glc {
 static const CrcTables h_crc = crc_make_tables();
@@ -81,11 +94,6 @@ struct Plan {
     }
 };
 
-unsigned long long frame_bytes(uint32_t nb, uint32_t blk_len, unsigned long long payload_words)
-{
-    return CT_FRAME_HDR + 4 * ct_tables(nb, blk_len).words + 4 * (payload_words + (payload_words & 1));
-}
-
 // worst case of one frame of nb blocks of blk_len (raw records)
 unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 {
@@ -93,22 +101,9 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 }
 
 // -------------------------------------------------------------------------------------------------------------------------
-// the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
+// the format rule (ct_legal() of container_internal.h: the table the device's walk reads as well)
 // -------------------------------------------------------------------------------------------------------------------------
-constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
-constexpr struct { uint32_t version, flags, elems; } CT_LEGAL[] = {
-    {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
-    {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
-    {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}};
-
 bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
-
-bool format_legal(const CtFormat &f)
-{
-    for (const auto &l : CT_LEGAL)
-        if (l.version == f.version && l.flags == f.flags && f.elem <= 8 && (l.elems >> f.elem & 1)) return true;
-    return false;
-}
 
 // the writer's format: the lowest version that can say the plan's settings
 CtFormat format_of(const CtSettings &s)
@@ -116,18 +111,11 @@ CtFormat format_of(const CtSettings &s)
     CtFormat f;
     f.elem = s.shuffle;
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
-    for (const auto &l : CT_LEGAL) {
-        f.version = l.version;
+    for (uint32_t i = 0; i < CT_NLEGAL; i++) {
+        f.version = ct_legal(i).version;
         if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal())) break;
     }
     return f;                                                 // (the setters accept only what some row takes)
-}
-
-// the reader's: header words 1 (version, flags in the upper half) and 3 (elem)
-bool parse_format(const uint32_t h[8], CtFormat *f)
-{
-    f->version = h[1] & 0xFFFFu; f->flags = h[1] >> 16; f->elem = h[3];
-    return format_legal(*f);
 }
 
 hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
@@ -441,11 +429,29 @@ struct Decoder {
 
     // a frame in device memory whose header (nb, blk_len, payload words) the host has range-checked; decoded to out.  A
     // filtered frame is decoded into the plan's staging, checked block by block there and inverted into out in one launch.
-    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi)
+    // With a subset (a range read: need[b] != 0 = block b is wanted) the frame gets every check of its tables and records as
+    // ever, but only the wanted blocks are decoded, into the plan's staging at their own places whatever the format, and
+    // checked there; *staged is the staging and final_out is not touched (the inverse filter of a range is the caller's).
+    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi,
+                      const uint8_t *need = nullptr, uint8_t **staged = nullptr)
     {
         CT_TRY(reserve(nb));
         uint8_t *out = final_out;
-        if (fmt.filtered()) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
+        if (fmt.filtered() || need) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
+        if (staged) *staged = out;
+        auto want = [&](uint32_t b) { return !need || need[b] != 0; };
+        // over the runs of wanted blocks (all of them: one run)
+        auto runs = [&](auto call) -> hipError_t {
+            for (uint32_t a = 0; a < nb;) {
+                if (!want(a)) { a++; continue; }
+                uint32_t b = a;
+                while (b < nb && want(b)) b++;
+                const hipError_t e = call(a, b - a);
+                if (e != hipSuccess) return e;
+                a = b;
+            }
+            return hipSuccess;
+        };
         const bool k2 = fmt.kind2_legal();
         KernelProf *prof = plan_prof(P.h);
         if (k2) CT_TRY(reserve_huff0(nb, blk_len));
@@ -455,14 +461,14 @@ struct Decoder {
         if (h_verdict[0]) return fail(P.h, CT_FRAME_TABLE, fi);
         if (h_verdict[1] != ~0ull) return fail(P.h, h_verdict[1] >> 32, fi, h_verdict[1] & 0xFFFFFFFFu);
         const uint32_t *kind = reinterpret_cast<const uint32_t *>(h_verdict + 2);
-        CT_TRY(ct_dec_raw(P.st, f, fr, nb, blk_len, out));
+        CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_raw(P.st, f, fr, nb, blk_len, out, a, cnt); }));
         const CtTables T = ct_tables(nb, blk_len);
         const uint32_t *W = reinterpret_cast<const uint32_t *>(fr + CT_FRAME_HDR);
         const unsigned int *pay = reinterpret_cast<const unsigned int *>(fr + CT_FRAME_HDR + 4 * T.words);
         for (uint32_t a = 0; a < nb;) {
-            if (kind[a] != CT_KIND_HUFF) { a++; continue; }
+            if (kind[a] != CT_KIND_HUFF || !want(a)) { a++; continue; }
             uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_HUFF && b - a < P.rows) b++;
+            while (b < nb && kind[b] == CT_KIND_HUFF && want(b) && b - a < P.rows) b++;
             const CUDPPResult r = glcDecompressBatchCompact(
                 P.h, reinterpret_cast<const int *>(W + T.bwt) + a, W + T.hist + 256ull * a, W + T.enc_off + (size_t)T.nsub * a,
                 T.nsub, pay, pw, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, out + (size_t)a * blk_len,
@@ -471,9 +477,9 @@ struct Decoder {
             a = b;
         }
         for (uint32_t a = 0; k2 && a < nb;) {                   // runs of order-0 blocks, a chunk of the plan's rows at a time
-            if (kind[a] != CT_KIND_HUFF0) { a++; continue; }
+            if (kind[a] != CT_KIND_HUFF0 || !want(a)) { a++; continue; }
             uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_HUFF0 && b - a < h0.chunk) b++;
+            while (b < nb && kind[b] == CT_KIND_HUFF0 && want(b) && b - a < h0.chunk) b++;
             // (k_cd_raw has put every block's output range into f.seg_*: absolute addresses, so the base is null)
             const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, b - a, blk_len};
             CT_TRY(hdb_decode(P.st, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, h0.nun + a,
@@ -481,9 +487,9 @@ struct Decoder {
             a = b;
         }
         for (uint32_t a = 0; fmt.kind3_legal() && a < nb;) {    // runs of sparse blocks: K decoded into scratch, then expanded
-            if (kind[a] != CT_KIND_SPARSE) { a++; continue; }
+            if (kind[a] != CT_KIND_SPARSE || !want(a)) { a++; continue; }
             uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_SPARSE && b - a < h0.chunk) b++;
+            while (b < nb && kind[b] == CT_KIND_SPARSE && want(b) && b - a < h0.chunk) b++;
             const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, b - a, blk_len};
             CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
             const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
@@ -492,6 +498,10 @@ struct Decoder {
             a = b;
         }
         plan_join(P.h);
+        if (need) {
+            CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
+            return CUDPP_SUCCESS;
+        }
         CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !fmt.filtered()));
         if (fmt.filtered()) {
             CT_TRY(filter_device(P.st, fmt, out, final_out, (unsigned long long)nb * blk_len, true));
@@ -500,42 +510,18 @@ struct Decoder {
         return CUDPP_SUCCESS;
     }
 
-    // after the last frame: the decoded-bytes verdict and the whole output's CRC against the trailer's
-    CUDPPResult end(uint32_t trailer_crc)
+    // after the last frame: the decoded-bytes verdict and the whole output's CRC against the trailer's (a range read has no
+    // whole output: it stops at the blocks' verdict)
+    CUDPPResult end(uint32_t trailer_crc, bool whole = true)
     {
         CtDecState s;
         CT_TRY(hipMemcpyAsync(&s, state, sizeof(s), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
         if (s.err != ~0ull) return fail(P.h, CT_DECODED_CRC, (s.err - 1) >> 32, (s.err - 1) & 0xFFFFFFFFu);
-        if (s.crc_all != trailer_crc) return fail(P.h, CT_DECODED_CRC);
+        if (whole && s.crc_all != trailer_crc) return fail(P.h, CT_DECODED_CRC);
         return CUDPP_SUCCESS;
     }
 };
-
-// the checks on a stream header; false = refused
-bool check_stream_header(const uint32_t h[8], CtFormat *fmt, uint32_t *block_len, unsigned long long *total)
-{
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_host(h, 24) || !parse_format(h, fmt)) return false;
-    if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
-    *block_len = h[2];
-    *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
-    return true;
-}
-
-// the host's range checks on a frame header; 0 = refused
-bool check_frame_header(const uint32_t h[8], uint32_t block_len, unsigned long long left, unsigned long long *pw)
-{
-    const uint32_t nb = h[1], bl = h[2];
-    *pw = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
-    if (h[0] != CT_MAGIC_FRAME || h[3] != 0 || h[7] != 0 || nb == 0 || bl == 0 || bl > block_len) return false;
-    if ((nb > 1 && bl != block_len) || (unsigned long long)nb * bl > left) return false;
-    return *pw <= (unsigned long long)nb * ct_raw_words(bl);
-}
-
-bool check_trailer(const uint32_t t[4], uint32_t frames)
-{
-    return t[0] == CT_MAGIC_END && t[1] == frames && t[3] == crc32_host(t, 12);
-}
 
 // -------------------------------------------------------------------------------------------------------------------------
 // streamed forms: a source of input bytes and a sink of output bytes (host buffers or files), one frame at a time
@@ -680,46 +666,43 @@ struct Feed {
     virtual CUDPPResult taken(size_t ob) = 0;                    // the frame's output is complete on the plan's stream
 };
 
-// stream header -> frames -> trailer -> the decoded bytes' verdict; cap: the room for output.  Returns the stream's total.
+// stream header -> frames -> trailer -> the decoded bytes' verdict over ct_walk(), the walk the frame index makes as well;
+// cap: the room for output.  Returns the stream's total.
+CUDPPResult walk_result(CUDPPHandle plan, const CtWalkEnd &end, CUDPPResult stopped)
+{
+    if (end.what == CT_WALK_STOPPED) return stopped;
+    if (end.what == CT_WALK_CONFIG) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+    if (end.what != CT_OK) return fail(plan, end.what, end.frame);
+    set_error(plan, CT_OK);
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned long long cap, unsigned long long *total)
 {
     const CUDPPHandle plan = D.P.h;
-    if (len < CT_HDR + CT_TRAILER) return fail(plan, CT_TRUNCATED);
-    uint32_t hdr[8], block_len = 0;
-    CUDPPResult r = feed.header(hdr, 0, CT_HDR, ~0ull);
-    if (r != CUDPP_SUCCESS) return r;
-    if (!check_stream_header(hdr, &D.fmt, &block_len, total)) return fail(plan, CT_STREAM_HEADER);
-    if (D.fmt.kind3_legal() && !plan_container_settings(plan).sparse)   // a plan with the sparse mode off is a version-4 reader
-        return fail(plan, CT_STREAM_HEADER);
-    if (*total > cap) return fail(plan, CT_CAPACITY);
-    CT_TRY(D.begin());
-    unsigned long long pos = CT_HDR, done = 0;
-    uint32_t fi = 0;
-    while (done < *total) {
-        if (pos + CT_FRAME_HDR + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-        uint32_t fh[8];
-        if ((r = feed.header(fh, pos, CT_FRAME_HDR, fi)) != CUDPP_SUCCESS) return r;
-        unsigned long long pw = 0;
-        if (!check_frame_header(fh, block_len, *total - done, &pw)) return fail(plan, CT_FRAME_TABLE, fi);
-        const uint32_t nb = fh[1], bl = fh[2];
-        if (bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
-        const unsigned long long fb = frame_bytes(nb, bl, pw);
-        if (pos + fb + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-        const size_t ob = (size_t)nb * bl;
-        const uint8_t *fr = nullptr;
-        uint8_t *out = nullptr;
-        if ((r = feed.frame(fh, pos, fb, done, ob, fi, &fr, &out)) != CUDPP_SUCCESS) return r;
-        if ((r = D.frame(fr, nb, bl, pw, out, fi)) != CUDPP_SUCCESS) return r;
-        if ((r = feed.taken(ob)) != CUDPP_SUCCESS) return r;
-        pos += fb; done += ob; fi++;
-    }
-    uint32_t tr[4];
-    if (pos + CT_TRAILER > len) return fail(plan, CT_TRUNCATED, fi);
-    if ((r = feed.header(tr, pos, CT_TRAILER, fi)) != CUDPP_SUCCESS) return r;
-    if (!check_trailer(tr, fi) || pos + CT_TRAILER != len) return fail(plan, CT_STREAM_HEADER, fi);
-    if ((r = D.end(tr[2])) != CUDPP_SUCCESS) return r;
-    set_error(plan, CT_OK);
-    return CUDPP_SUCCESS;
+    CUDPPResult r = CUDPP_SUCCESS;                              // why a callback stopped the walk
+    const CtWalkEnd end = ct_walk(
+        h_crc, len, D.P.n, plan_container_settings(plan).sparse,   // a plan with the sparse mode off is a version-4 reader
+        [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long frame) {
+            return (r = feed.header(dst, pos, bytes, frame)) == CUDPP_SUCCESS;
+        },
+        [&](const uint32_t *, const CtFormat &fmt, uint32_t, unsigned long long tot) {
+            D.fmt = fmt;
+            *total = tot;
+            if (tot > cap) r = fail(plan, CT_CAPACITY);
+            else r = hip_res(D.begin());
+            return r == CUDPP_SUCCESS;
+        },
+        [&](uint32_t fi, const uint32_t *fh, const CtFrameRef &F) {
+            const size_t ob = (size_t)F.nb * F.bl;
+            const uint8_t *fr = nullptr;
+            uint8_t *out = nullptr;
+            if ((r = feed.frame(fh, F.pos, frame_bytes(F.nb, F.bl, F.pw), F.out_off, ob, fi, &fr, &out)) != CUDPP_SUCCESS) return false;
+            if ((r = D.frame(fr, F.nb, F.bl, F.pw, out, fi)) != CUDPP_SUCCESS) return false;
+            return (r = feed.taken(ob)) == CUDPP_SUCCESS;
+        },
+        [&](const uint32_t *tr, uint32_t) { return (r = D.end(tr[2])) == CUDPP_SUCCESS; });
+    return walk_result(plan, end, r);
 }
 
 // the caller's device buffers: headers come by a device-to-host copy, frames are decoded where they lie
@@ -806,9 +789,374 @@ CUDPPResult with_files(const char *inPath, const char *outPath, Call call)
     return r;
 }
 
+// -------------------------------------------------------------------------------------------------------------------------
+// the frame index and range reads.  An index is ct_walk() over a container's headers and nothing else: 32 bytes per frame
+// from a host buffer or a file, one launch of k_ct_index and one readback for device memory.  A range read takes the frames
+// the range overlaps from the index, fetches each of them whole, gives it the checks of the full decode (Decoder::frame with
+// a block subset), decodes the blocks the range needs into the plan's staging and delivers the range's bytes from there.
+// -------------------------------------------------------------------------------------------------------------------------
+struct RandomSource {                                            // container bytes by position: a host buffer or a file
+    virtual ~RandomSource() {}
+    virtual bool at(void *dst, unsigned long long pos, size_t n) = 0;            // exactly n bytes or false
+};
+struct MemRandom : RandomSource {
+    const uint8_t *p; unsigned long long len;
+    MemRandom(const void *q, unsigned long long n) : p(static_cast<const uint8_t *>(q)), len(n) {}
+    bool at(void *dst, unsigned long long pos, size_t n) override
+    {
+        if (pos > len || n > len - pos) return false;
+        memcpy(dst, p + pos, n);
+        return true;
+    }
+};
+struct FileRandom : RandomSource {
+    int fd = -1;
+    unsigned long long len = 0;
+    explicit FileRandom(const char *path)
+    {
+        struct stat sb;
+        if (path && (fd = open(path, O_RDONLY)) >= 0) {
+            if (fstat(fd, &sb) == 0) len = (unsigned long long)sb.st_size;
+            else { close(fd); fd = -1; }
+        }
+    }
+    ~FileRandom() { if (fd >= 0) close(fd); }
+    bool at(void *dst, unsigned long long pos, size_t n) override
+    {
+        uint8_t *d = static_cast<uint8_t *>(dst);
+        while (n) {
+            const ssize_t k = pread(fd, d, n, (off_t)pos);
+            if (k <= 0) return false;
+            d += k; pos += (unsigned long long)k; n -= (size_t)k;
+        }
+        return true;
+    }
+};
+
+CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &ix, const CtWalkEnd &end, CUDPPResult stopped,
+                         GlcContainerIndex **index)
+{
+    const CUDPPResult r = walk_result(plan, end, stopped);
+    if (r != CUDPP_SUCCESS) return r;
+    ix->fmt = CtFormat();
+    (void)parse_format(ix->hdr, &ix->fmt);
+    ix->block_len = ix->hdr[2];
+    ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
+    *index = ix.release();
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult index_host(CUDPPHandle plan, RandomSource &src, unsigned long long len, GlcContainerIndex **index)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!index) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    std::unique_ptr<GlcContainerIndex> ix(new (std::nothrow) GlcContainerIndex);
+    if (!ix) return CUDPP_ERROR_INSUFFICIENT_RESOURCES;
+    ix->len = len;
+    CUDPPResult r = CUDPP_SUCCESS;
+    const CtWalkEnd end = ct_walk(
+        h_crc, len, P.n, plan_container_settings(plan).sparse,
+        [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long frame) {
+            if (src.at(dst, pos, bytes)) return true;
+            r = fail(plan, CT_TRUNCATED, frame);
+            return false;
+        },
+        [&](const uint32_t *h, const CtFormat &, uint32_t, unsigned long long) { memcpy(ix->hdr, h, CT_HDR); return true; },
+        [&](uint32_t, const uint32_t *, const CtFrameRef &ref) {
+            try { ix->frames.push_back(ref); } catch (const std::bad_alloc &) { r = CUDPP_ERROR_INSUFFICIENT_RESOURCES; return false; }
+            return true;
+        },
+        [&](const uint32_t *tr, uint32_t) { memcpy(ix->trailer, tr, CT_TRAILER); return true; });
+    return index_result(plan, ix, end, r, index);
+}
+
+// where a range read's container bytes come from and where its output goes
+struct RangeIO {
+    virtual ~RangeIO() {}
+    virtual CUDPPResult small(void *dst, unsigned long long pos, size_t n) = 0;           // a few bytes into host memory
+    // the fb-byte frame at pos in device memory, ordered on the plan's stream, and its 32-byte header in host memory
+    virtual CUDPPResult frame(unsigned long long pos, unsigned long long fb, const uint8_t **fr, uint32_t fh[8]) = 0;
+    // n decoded bytes in device memory (ready on the plan's stream) are bytes [out_pos, + n) of the range
+    virtual CUDPPResult deliver(const uint8_t *d_src, size_t n, unsigned long long out_pos) = 0;
+};
+struct DeviceRangeIO : RangeIO {
+    hipStream_t st;
+    const uint8_t *in;
+    uint8_t *out;
+    DeviceRangeIO(hipStream_t s, const void *i, void *o) : st(s), in(static_cast<const uint8_t *>(i)), out(static_cast<uint8_t *>(o)) {}
+    CUDPPResult small(void *dst, unsigned long long pos, size_t n) override
+    {
+        CT_TRY(hipMemcpyAsync(dst, in + pos, n, hipMemcpyDeviceToHost, st));
+        CT_TRY(hipStreamSynchronize(st));
+        return CUDPP_SUCCESS;
+    }
+    CUDPPResult frame(unsigned long long pos, unsigned long long, const uint8_t **fr, uint32_t fh[8]) override
+    {
+        *fr = in + pos;
+        return small(fh, pos, CT_FRAME_HDR);
+    }
+    CUDPPResult deliver(const uint8_t *d_src, size_t n, unsigned long long out_pos) override
+    {
+        CT_TRY(hipMemcpyAsync(out + out_pos, d_src, n, hipMemcpyDeviceToDevice, st));
+        return CUDPP_SUCCESS;
+    }
+};
+// a host buffer or a file, one frame at a time through pinned memory; the output goes back the same way
+struct HostRangeIO : RangeIO {
+    hipStream_t st;
+    RandomSource &src;
+    uint8_t *out;
+    Pinned hf, ho;
+    DevBuf df;
+    HostRangeIO(hipStream_t s, RandomSource &i, void *o) : st(s), src(i), out(static_cast<uint8_t *>(o)) {}
+    CUDPPResult small(void *dst, unsigned long long pos, size_t n) override { return src.at(dst, pos, n) ? CUDPP_SUCCESS : CUDPP_ERROR_UNKNOWN; }
+    CUDPPResult frame(unsigned long long pos, unsigned long long fb, const uint8_t **fr, uint32_t fh[8]) override
+    {
+        CT_TRY(hf.reserve(fb)); CT_TRY(df.reserve(fb));
+        if (!src.at(hf.p, pos, fb)) return CUDPP_ERROR_UNKNOWN;
+        memcpy(fh, hf.p, CT_FRAME_HDR);
+        CT_TRY(hipMemcpyAsync(df.p, hf.p, fb, hipMemcpyHostToDevice, st));
+        *fr = static_cast<const uint8_t *>(df.p);
+        return CUDPP_SUCCESS;
+    }
+    CUDPPResult deliver(const uint8_t *d_src, size_t n, unsigned long long out_pos) override
+    {
+        CT_TRY(ho.reserve(n));
+        CT_TRY(hipMemcpyAsync(ho.p, d_src, n, hipMemcpyDeviceToHost, st));
+        CT_TRY(hipStreamSynchronize(st));
+        memcpy(out + out_pos, ho.p, n);
+        return CUDPP_SUCCESS;
+    }
+};
+
+// The blocks of a frame of nb blocks of bl bytes that bytes [a, b) of it need (need[blk] = 1), and with a filter the
+// elements [*i0, *i1) the range form of the inverse has to produce: whole elements, from the start of the delta's run.
+std::vector<uint8_t> needed_blocks(const CtFormat &fmt, uint32_t nb, uint32_t bl, unsigned long long a, unsigned long long b,
+                                   unsigned long long *i0, unsigned long long *i1)
+{
+    std::vector<uint8_t> need(nb, 0);
+    const unsigned long long F = (unsigned long long)nb * bl;
+    auto mark = [&](unsigned long long lo, unsigned long long hi) {
+        for (unsigned long long k = lo / bl; lo < hi && k <= (hi - 1) / bl; k++) need[k] = 1;
+    };
+    *i0 = *i1 = 0;
+    if (!fmt.filtered()) { mark(a, b); return need; }
+    const unsigned long long e = fmt.elem, q = F / e;
+    const unsigned long long lo = a / e, hi = std::min(q, (b + e - 1) / e);
+    if (lo < hi) {                                              // (a range inside the len % elem tail needs no element)
+        *i0 = fmt.delta() ? lo & ~2047ull : lo;
+        *i1 = hi;
+        for (unsigned long long j = 0; j < e; j++) mark(j * q + *i0, j * q + *i1);
+    }
+    if (b > q * e) mark(q * e, F);
+    return need;
+}
+
+struct RangeStats { unsigned long long v[3] = {0, 0, 0}; };
+std::map<CUDPPHandle, RangeStats> g_range_stats;               // (under g_err_mu)
+
+CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, unsigned long long len, unsigned long long offset,
+                       unsigned long long count)
+{
+    const CUDPPHandle plan = D.P.h;
+    if (!ix || len != ix->len || offset > ix->total || count > ix->total - offset) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    RangeStats stats;
+    auto done = [&]() {
+        set_error(plan, CT_OK);
+        std::lock_guard<std::mutex> g(g_err_mu);
+        g_range_stats[plan] = stats;
+        return CUDPP_SUCCESS;
+    };
+    if (count == 0) return done();
+    uint32_t hdr[8];
+    if (io.small(hdr, 0, CT_HDR) != CUDPP_SUCCESS) return fail(plan, CT_TRUNCATED);
+    if (memcmp(hdr, ix->hdr, CT_HDR) != 0) return fail(plan, CT_STREAM_HEADER);           // another container than the index's
+    if (ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) return fail(plan, CT_STREAM_HEADER);
+    stats.v[2] = CT_HDR;
+    D.fmt = ix->fmt;
+    CT_TRY(D.begin());
+    const unsigned long long end = offset + count;
+    size_t fi = 0, hi = ix->frames.size();                      // the last frame that starts at or before `offset`
+    while (hi - fi > 1) {
+        const size_t mid = fi + (hi - fi) / 2;
+        if (ix->frames[mid].out_off <= offset) fi = mid; else hi = mid;
+    }
+    for (; fi < ix->frames.size() && ix->frames[fi].out_off < end; fi++) {
+        const CtFrameRef &F = ix->frames[fi];
+        const unsigned long long fbytes = (unsigned long long)F.nb * F.bl, fb = frame_bytes(F.nb, F.bl, F.pw);
+        if (F.bl > D.P.n) { set_error(plan, CT_OK); return CUDPP_ERROR_ILLEGAL_CONFIGURATION; }
+        const unsigned long long a = std::max(offset, F.out_off) - F.out_off, b = std::min(end, F.out_off + fbytes) - F.out_off;
+        const uint8_t *fr = nullptr;
+        uint32_t fh[8];
+        unsigned long long pw = 0;
+        CUDPPResult r = io.frame(F.pos, fb, &fr, fh);
+        if (r == CUDPP_ERROR_UNKNOWN) return fail(plan, CT_TRUNCATED, fi);
+        if (r != CUDPP_SUCCESS) return r;
+        // the header's range check, on the bytes that are there now: it has to say what the index says
+        if (!check_frame_header(fh, ix->block_len, ix->total - F.out_off, &pw) || fh[1] != F.nb || fh[2] != F.bl || pw != F.pw)
+            return fail(plan, CT_FRAME_TABLE, fi);
+        unsigned long long i0 = 0, i1 = 0;
+        const std::vector<uint8_t> need = needed_blocks(ix->fmt, F.nb, F.bl, a, b, &i0, &i1);
+        uint8_t *stage = nullptr;
+        if ((r = D.frame(fr, F.nb, F.bl, F.pw, nullptr, (uint32_t)fi, need.data(), &stage)) != CUDPP_SUCCESS) return r;
+        stats.v[0] += 1;
+        for (uint8_t w : need) stats.v[1] += w;
+        stats.v[2] += fb;
+        const unsigned long long at = F.out_off - offset;       // (+ a frame byte = its place in the range; never negative there)
+        if (!ix->fmt.filtered()) {
+            if ((r = io.deliver(stage + a, b - a, at + a)) != CUDPP_SUCCESS) return r;
+            continue;
+        }
+        const unsigned long long e = ix->fmt.elem, q = fbytes / e;
+        if (i0 < i1) {                                          // elements [i0, i1) into the second staging, [a, min(b, q e)) out of them
+            uint8_t *el = nullptr;
+            CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
+            CT_TRY((ix->fmt.delta() ? undelta_unshuffle_range_device : unshuffle_range_device)(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
+            const unsigned long long top = std::min(b, q * e);
+            if ((r = io.deliver(el + (a - i0 * e), top - a, at + a)) != CUDPP_SUCCESS) return r;
+        }
+        if (b > q * e) {                                        // the len % elem tail lies in the filtered frame as it is
+            const unsigned long long lo = std::max(a, q * e);
+            if ((r = io.deliver(stage + lo, b - lo, at + lo)) != CUDPP_SUCCESS) return r;
+        }
+    }
+    const CUDPPResult r = D.end(0, false);
+    if (r != CUDPP_SUCCESS) return r;
+    return done();
+}
+
+CUDPPResult range_filter_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
+                             unsigned long long count, void *stream, bool delta)
+{
+    if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const unsigned long long q = len / elem;
+    if (first > q || count > q - first || (delta && first % 2048)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (a < b + count * elem && b < a + len)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_res((delta ? undelta_unshuffle_range_device : unshuffle_range_device)(
+        reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), q, elem, first, count));
+}
+
 } // namespace
 
 extern "C" {
+
+CUDPPResult glcContainerIndexDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, GlcContainerIndex **index)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!d_in || !index || (reinterpret_cast<uintptr_t>(d_in) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    std::unique_ptr<GlcContainerIndex> ix(new (std::nothrow) GlcContainerIndex);
+    if (!ix) return CUDPP_ERROR_INSUFFICIENT_RESOURCES;
+    ix->len = len;
+    // no frame is smaller than one block of one byte with an empty payload, so len bounds the entries before the header is read
+    const unsigned long long cap = len / frame_bytes(1, 1, 0) + 1;
+    uint8_t *scratch = nullptr;
+    CT_TRY(plan_codec_scratch(plan, 2, sizeof(CtIndexHead) + cap * sizeof(CtFrameRef), &scratch));
+    CtIndexHead *d_head = reinterpret_cast<CtIndexHead *>(scratch);
+    CtFrameRef *d_ent = reinterpret_cast<CtFrameRef *>(scratch + sizeof(CtIndexHead));
+    CT_TRY(ct_index_device(P.st, static_cast<const uint8_t *>(d_in), len, P.n, plan_container_settings(plan).sparse, d_head, d_ent, cap));
+    // one readback: the head and the first entries; a container of more frames than that fetches the rest
+    const size_t first = (size_t)std::min<unsigned long long>(cap, CT_INDEX_FIRST);
+    std::vector<uint8_t> back(sizeof(CtIndexHead) + first * sizeof(CtFrameRef));
+    CT_TRY(hipMemcpyAsync(back.data(), scratch, back.size(), hipMemcpyDeviceToHost, P.st));
+    CT_TRY(hipStreamSynchronize(P.st));
+    CtIndexHead head;
+    memcpy(&head, back.data(), sizeof(head));
+    if (head.what == CT_OK) {
+        if (head.frames > cap) return CUDPP_ERROR_UNKNOWN;
+        ix->frames.resize(head.frames);
+        const size_t got = std::min<size_t>(head.frames, first);
+        if (got) memcpy(ix->frames.data(), back.data() + sizeof(CtIndexHead), got * sizeof(CtFrameRef));
+        if (head.frames > got) {
+            CT_TRY(hipMemcpyAsync(ix->frames.data() + got, d_ent + got, (head.frames - got) * sizeof(CtFrameRef), hipMemcpyDeviceToHost, P.st));
+            CT_TRY(hipStreamSynchronize(P.st));
+        }
+        memcpy(ix->hdr, head.hdr, CT_HDR);
+        memcpy(ix->trailer, head.trailer, CT_TRAILER);
+    }
+    return index_result(plan, ix, CtWalkEnd{head.what, head.frame}, CUDPP_ERROR_UNKNOWN, index);
+}
+
+CUDPPResult glcContainerIndex(CUDPPHandle plan, const void *in, unsigned long long len, GlcContainerIndex **index)
+{
+    if (!in) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    MemRandom src(in, len);
+    return index_host(plan, src, len, index);
+}
+
+CUDPPResult glcContainerIndexFile(CUDPPHandle plan, const char *path, GlcContainerIndex **index)
+{
+    FileRandom src(path);
+    if (src.fd < 0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return index_host(plan, src, src.len, index);
+}
+
+void glcContainerIndexFree(GlcContainerIndex *index) { delete index; }
+
+CUDPPResult glcContainerIndexInfo(const GlcContainerIndex *index, unsigned long long out[4])
+{
+    if (!index || !out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    out[0] = index->total; out[1] = index->block_len; out[2] = index->frames.size();
+    out[3] = index->fmt.version | ((unsigned long long)index->fmt.flags << 16) | ((unsigned long long)index->fmt.elem << 32);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerReadRangeDevice(CUDPPHandle plan, const GlcContainerIndex *index, const void *d_in, unsigned long long len,
+                                        unsigned long long offset, unsigned long long count, void *d_out)
+{
+    Decoder D;
+    if (const CUDPPResult bad = D.P.check(plan)) return bad;
+    if (!d_in || (count && !d_out) || (reinterpret_cast<uintptr_t>(d_in) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    DeviceRangeIO io(D.P.st, d_in, d_out);
+    return read_range(D, index, io, len, offset, count);
+}
+
+CUDPPResult glcContainerReadRange(CUDPPHandle plan, const GlcContainerIndex *index, const void *in, unsigned long long len,
+                                  unsigned long long offset, unsigned long long count, void *out)
+{
+    Decoder D;
+    if (const CUDPPResult bad = D.P.check(plan)) return bad;
+    if (!in || (count && !out)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    MemRandom src(in, len);
+    HostRangeIO io(D.P.st, src, out);
+    return read_range(D, index, io, len, offset, count);
+}
+
+CUDPPResult glcContainerReadRangeFile(CUDPPHandle plan, const GlcContainerIndex *index, const char *path, unsigned long long offset,
+                                      unsigned long long count, void *out)
+{
+    Decoder D;
+    if (const CUDPPResult bad = D.P.check(plan)) return bad;
+    FileRandom src(path);
+    if (src.fd < 0 || (count && !out)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    HostRangeIO io(D.P.st, src, out);
+    return read_range(D, index, io, src.len, offset, count);
+}
+
+CUDPPResult glcContainerLastRangeStats(CUDPPHandle plan, unsigned long long out[3])
+{
+    if (plan == 0 || plan == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    std::lock_guard<std::mutex> g(g_err_mu);
+    const RangeStats s = g_range_stats.count(plan) ? g_range_stats[plan] : RangeStats();
+    for (int i = 0; i < 3; i++) out[i] = s.v[i];
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
+                                    unsigned long long count, void *stream)
+{
+    return range_filter_api(d_in, d_out, len, elem, first, count, stream, false);
+}
+
+CUDPPResult glcUndeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                           unsigned long long first, unsigned long long count, void *stream)
+{
+    return range_filter_api(d_in, d_out, len, elem, first, count, stream, true);
+}
 
 unsigned long long glcContainerBound(unsigned long long len, size_t blockLen)
 {

@@ -85,6 +85,13 @@ hipError_t shuffle_segments(hipStream_t st, const uint8_t *inBase, uint8_t *outB
 // the shuffle of the differences of neighbouring elements, restarting every 2048 elements, and its inverse (delta.hip); one
 // segment, the same rules
 hipError_t delta_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, bool inverse);
+// range forms of the two inverses: `in` is a filtered segment with plane stride q; elements [first, first + count) of what the
+// whole-segment inverse would produce go to out[0 .. count * elem).  first + count <= q; the delta form wants first % 2048 == 0.
+// Loads touch only the aligned 16-byte granules that hold a byte of one of the elem plane runs [j q + first, + count).
+hipError_t unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                  unsigned long long first, unsigned long long count);
+hipError_t undelta_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                          unsigned long long first, unsigned long long count);
 
 // the sparse passes (sparse.hip).  Segment i is `data` + data_off[i], min(data_len[i], max_len) bytes, cut into chunks of 64; its
 // mask (bit c % 32 of word c / 32 = chunk c is kept, i.e. not all fill[i] & 255) is at mask + (mask_off ? mask_off[i] : i *
@@ -121,13 +128,33 @@ constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is leg
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
-    bool filtered() const { return elem != 0; }
-    bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
-    bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
-    bool kind3_legal() const { return version >= CT_VERSION_SPARSE; }
-    uint32_t max_kind() const { return kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
+    __host__ __device__ bool filtered() const { return elem != 0; }
+    __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
+    __host__ __device__ bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
+    __host__ __device__ bool kind3_legal() const { return version >= CT_VERSION_SPARSE; }
+    __host__ __device__ uint32_t max_kind() const { return kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
+// the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
+constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
+struct CtLegal { uint32_t version, flags, elems; };
+constexpr uint32_t CT_NLEGAL = 6;
+__host__ __device__ inline CtLegal ct_legal(uint32_t i)
+{
+    constexpr CtLegal L[CT_NLEGAL] = {
+        {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}};
+    return L[i];
+}
+__host__ __device__ inline bool format_legal(const CtFormat &f)
+{
+    for (uint32_t i = 0; i < CT_NLEGAL; i++) {
+        const CtLegal l = ct_legal(i);
+        if (l.version == f.version && l.flags == f.flags && f.elem <= 8 && (l.elems >> f.elem & 1)) return true;
+    }
+    return false;
+}
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
 constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 record (sparse.hip): mask, then the kind-2 stream of the kept chunks; version 5
@@ -152,6 +179,113 @@ __host__ __device__ inline CtTables ct_tables(uint32_t nb, uint32_t blk_len)
     return t;
 }
 __host__ __device__ inline uint32_t ct_raw_words(uint32_t blk_len) { return (blk_len + 3) / 4; }
+__host__ __device__ inline unsigned long long frame_bytes(uint32_t nb, uint32_t blk_len, unsigned long long payload_words)
+{
+    return CT_FRAME_HDR + 4 * ct_tables(nb, blk_len).words + 4 * (payload_words + (payload_words & 1));
+}
+
+// ---------------------------------------------------------------------------
+// The walk over a stream's headers: stream header -> frame header -> frame_bytes(nb, bl, pw) -> next frame header -> trailer.
+// One function for the host (the decoder's walk and the index of a host buffer or a file) and for the device (k_ct_index), so
+// that all of them refuse the same streams with the same class and the same frame.  C: the CRC tables of the side that runs.
+// ---------------------------------------------------------------------------
+__host__ __device__ inline uint32_t crc32_bytes(const CrcTables &C, const void *data, size_t len)
+{
+    const uint8_t *p = static_cast<const uint8_t *>(data);
+    uint32_t r = ~0u;
+    for (size_t i = 0; i < len; i++) r = C.t[0][(r ^ p[i]) & 255] ^ (r >> 8);
+    return ~r;
+}
+
+// the reader's format: header words 1 (version, flags in the upper half) and 3 (elem)
+__host__ __device__ inline bool parse_format(const uint32_t h[8], CtFormat *f)
+{
+    f->version = h[1] & 0xFFFFu; f->flags = h[1] >> 16; f->elem = h[3];
+    return format_legal(*f);
+}
+
+// the checks on a stream header; false = refused
+__host__ __device__ inline bool check_stream_header(const CrcTables &C, const uint32_t h[8], CtFormat *fmt, uint32_t *block_len,
+                                                    unsigned long long *total)
+{
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_format(h, fmt)) return false;
+    if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
+    *block_len = h[2];
+    *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
+    return true;
+}
+
+// the range checks on a frame header, `left` output bytes still to come; false = refused
+__host__ __device__ inline bool check_frame_header(const uint32_t h[8], uint32_t block_len, unsigned long long left, unsigned long long *pw)
+{
+    const uint32_t nb = h[1], bl = h[2];
+    *pw = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
+    if (h[0] != CT_MAGIC_FRAME || h[3] != 0 || h[7] != 0 || nb == 0 || bl == 0 || bl > block_len) return false;
+    if ((nb > 1 && bl != block_len) || (unsigned long long)nb * bl > left) return false;
+    return *pw <= (unsigned long long)nb * ct_raw_words(bl);
+}
+
+__host__ __device__ inline bool check_trailer(const CrcTables &C, const uint32_t t[4], uint32_t frames)
+{
+    return t[0] == CT_MAGIC_END && t[1] == frames && t[3] == crc32_bytes(C, t, 12);
+}
+
+struct CtFrameRef {                                        // a frame whose header has passed the walk's checks
+    unsigned long long pos, out_off, pw;                   // where it starts in the stream; the output offset of its first byte
+    uint32_t nb, bl;
+};
+// what a walk ends with beyond CtWhat: the plan's n is below a frame's blk_len; a callback stopped it (the reason is the caller's)
+constexpr uint32_t CT_WALK_CONFIG = 0x100, CT_WALK_STOPPED = 0x101;
+struct CtWalkEnd { uint32_t what; unsigned long long frame; };            // frame: the index a failure names (~0 = none)
+
+// fetch(dst, pos, bytes, frame) -> bool brings 32 or 16 header bytes into dst; on_header(h, fmt, block_len, total),
+// on_frame(fi, fh, ref) and on_trailer(tr, frames) -> bool see what has passed its checks.  `sparse_reader` is the plan's sparse
+// mode (a plan with it off is a version-4 reader), plan_n its block length.
+template <class Fetch, class OnHeader, class OnFrame, class OnTrailer>
+__host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long long len, uint32_t plan_n, bool sparse_reader, Fetch fetch,
+                                             OnHeader on_header, OnFrame on_frame, OnTrailer on_trailer)
+{
+    const unsigned long long none = ~0ull;
+    if (len < CT_HDR + CT_TRAILER) return {CT_TRUNCATED, none};
+    uint32_t hdr[8], block_len = 0;
+    unsigned long long total = 0;
+    CtFormat fmt;
+    if (!fetch(hdr, 0ull, CT_HDR, none)) return {CT_WALK_STOPPED, none};
+    if (!check_stream_header(C, hdr, &fmt, &block_len, &total)) return {CT_STREAM_HEADER, none};
+    if (fmt.kind3_legal() && !sparse_reader) return {CT_STREAM_HEADER, none};
+    if (!on_header(hdr, fmt, block_len, total)) return {CT_WALK_STOPPED, none};
+    unsigned long long pos = CT_HDR, done = 0;
+    uint32_t fi = 0;
+    while (done < total) {
+        if (pos + CT_FRAME_HDR + CT_TRAILER > len) return {CT_TRUNCATED, fi};
+        uint32_t fh[8];
+        if (!fetch(fh, pos, CT_FRAME_HDR, (unsigned long long)fi)) return {CT_WALK_STOPPED, fi};
+        CtFrameRef ref{pos, done, 0, fh[1], fh[2]};
+        if (!check_frame_header(fh, block_len, total - done, &ref.pw)) return {CT_FRAME_TABLE, fi};
+        if (ref.bl > plan_n) return {CT_WALK_CONFIG, fi};
+        const unsigned long long fb = frame_bytes(ref.nb, ref.bl, ref.pw);
+        if (pos + fb + CT_TRAILER > len) return {CT_TRUNCATED, fi};
+        if (!on_frame(fi, fh, ref)) return {CT_WALK_STOPPED, fi};
+        pos += fb; done += (unsigned long long)ref.nb * ref.bl; fi++;
+    }
+    uint32_t tr[4];
+    if (pos + CT_TRAILER > len) return {CT_TRUNCATED, fi};
+    if (!fetch(tr, pos, CT_TRAILER, (unsigned long long)fi)) return {CT_WALK_STOPPED, fi};
+    if (!check_trailer(C, tr, fi) || pos + CT_TRAILER != len) return {CT_STREAM_HEADER, fi};
+    if (!on_trailer(tr, fi)) return {CT_WALK_STOPPED, fi};
+    return {CT_OK, none};
+}
+
+// what k_ct_index leaves in front of its entries: how the walk ended, the frames it passed, the header and the trailer
+struct CtIndexHead {
+    uint32_t what, frames;
+    unsigned long long frame;
+    uint32_t hdr[8], trailer[4];
+};
+constexpr uint32_t CT_INDEX_FIRST = 1022;                  // entries the one readback brings along with the head (32 KiB in all)
+// the walk over a container in device memory (8-byte aligned), one launch: head and up to `cap` entries into `scratch`
+hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, bool sparse_reader,
+                           CtIndexHead *head, CtFrameRef *entries, unsigned long long cap);
 
 // ---------------------------------------------------------------------------
 // plan hooks (cudpp_api.cpp): the container path drives a COMPRESS plan through its internals
@@ -180,7 +314,7 @@ hipError_t plan_stage(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **
 // that call's Huffman stages and container kernels read their input from the side stream)
 void plan_wait_released(CUDPPHandle plan);
 // what the order-0 codec keeps with the plan: device
-// scratch (which = 0 the encoder's, 1 the decoder's; grown on demand, never shrunk, freed with the plan, never allocated
+// scratch (which = 0 the encoder's, 1 the decoder's, 2 the entries of the frame index walk; grown on demand, never shrunk, freed with the plan, never allocated
 // by a plan that only uses the BWT codec), the plan's live kernel profile, and its stage events (i = 0 .. 3: the marks of
 // glcPlanLastTiming's four spans, recorded on the plan's stream; a no-op while timing is off)
 hipError_t plan_codec_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
@@ -260,10 +394,14 @@ struct CtDecHuff0 {                                        // device scratch of 
 // units they ask for are one of the block's field checks
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
                          unsigned long long payload_words, const CtDecHuff0 *h0 = nullptr, KernelProf *prof = nullptr);
-hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out);
-// fold = false: the blocks are checked but the stream's crc_all is left to ct_dec_fold (the filter's frames)
+// blocks [first, first + count) of the frame (count 0: all of them from `first` on)
+hipError_t ct_dec_raw(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint8_t *out,
+                      uint32_t first = 0, uint32_t count = 0);
+// fold = false: the blocks are checked but the stream's crc_all is left to ct_dec_fold (the filter's frames); a subset of
+// the blocks (first, count as above) is never folded
 hipError_t ct_dec_check(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold = true);
+                        const uint8_t *out, uint32_t frame_index, CtDecState *state, bool fold = true, uint32_t first = 0,
+                        uint32_t count = 0);
 // the frame's nb * blk_len bytes at `bytes` (the unshuffled output) enter the stream's crc_all
 hipError_t ct_dec_fold(hipStream_t st, const CtDecFrame &f, const uint8_t *bytes, uint32_t nb, uint32_t blk_len, CtDecState *state);
 

@@ -127,7 +127,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse) and the filter's frame staging both directions share
     CtSettings ct;
     GrowBuf ct_stage[2];
-    GrowBuf ct_codec[2];                         // the order-0 container codec's scratch, its sparse mode's included: [0] the encoder's, [1] the decoder's
+    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
     SaScratch *sorter() override { return &sa; }
     void wire_prof() override { sa.prof = &prof; mtf.prof = &prof; huff.prof = &prof; dec.prof = &prof; }
     hipEvent_t side_span_start() override { return pipelined ? ev_s2 : nullptr; }

@@ -291,4 +291,40 @@ hipError_t delta_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out,
     }
 }
 
+// the range form of the inverse (see k_unshuffle_range): `first` is a multiple of RUN, so every tile still starts a run, and
+// the sums of a tile never depended on anything in front of it
+template <uint32_t ELEM>
+__global__ __launch_bounds__(SH_THREADS) void k_undelta_unshuffle_range(const uint8_t *in, uint8_t *out, unsigned long long q,
+                                                                        unsigned long long first, unsigned long long count)
+{
+    using G = ShGeom<ELEM>;
+    __shared__ __attribute__((aligned(16))) uint32_t reg[DL_REGION_WORDS];
+    __shared__ __attribute__((aligned(16))) uint32_t flat[DL_FLAT_WORDS];
+    __shared__ typename DlAcc<ELEM>::T wt[4 * DL_PASSES];
+    uint8_t *base = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(out) - first * ELEM);
+    const unsigned long long nt = (count + G::TQ - 1) / G::TQ;
+    for (unsigned long long t = blockIdx.x; t < nt; t += gridDim.x) {
+        const unsigned long long i0 = first + t * G::TQ;
+        const uint32_t cnt = (uint32_t)min((unsigned long long)G::TQ, first + count - i0);
+        dl_tile_inverse<ELEM>(in, base, q, i0, cnt, reg, flat, wt);
+        __syncthreads();                                       // (the next tile of this workgroup reuses the LDS images)
+    }
+}
+
+hipError_t undelta_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                          unsigned long long first, unsigned long long count)
+{
+    if (count == 0) return hipSuccess;
+    if (first % DL_RUN) return hipErrorInvalidValue;
+    const unsigned long long tq = SH_TILE / elem, nt = (count + tq - 1) / tq;
+    const dim3 grid((uint32_t)std::min<unsigned long long>(nt, 1u << 24)), block(SH_THREADS);
+    switch (elem) {
+    case 2: hipLaunchKernelGGL(k_undelta_unshuffle_range<2>, grid, block, 0, st, in, out, q, first, count); break;
+    case 4: hipLaunchKernelGGL(k_undelta_unshuffle_range<4>, grid, block, 0, st, in, out, q, first, count); break;
+    case 8: hipLaunchKernelGGL(k_undelta_unshuffle_range<8>, grid, block, 0, st, in, out, q, first, count); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 } // namespace glc

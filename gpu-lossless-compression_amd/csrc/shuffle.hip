@@ -192,6 +192,43 @@ hipError_t shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsig
     return sh_dispatch(st, inverse, elem, grid, in, out, nullptr, nullptr, 1, len);
 }
 
+// ---------------------------------------------------------------------------
+// the range form of the inverse: elements [first, first + count) of a segment with plane stride q, to out[0 .. count ELEM).
+// The inverse tile takes any i0 (a plane run starts where it starts), so tile t is simply elements first + t TQ ..; it
+// addresses its output as base + i0 ELEM, which makes the base out - first ELEM.  Nothing of the tile function changes: the
+// loads are the aligned granules that cover the ELEM plane runs of the tile, the stores exactly the tile's output bytes.
+// ---------------------------------------------------------------------------
+template <uint32_t ELEM>
+__global__ __launch_bounds__(SH_THREADS) void k_unshuffle_range(const uint8_t *in, uint8_t *out, unsigned long long q,
+                                                                unsigned long long first, unsigned long long count)
+{
+    using G = ShGeom<ELEM>;
+    __shared__ __attribute__((aligned(16))) uint32_t lds[SH_LDS_WORDS];
+    uint8_t *base = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(out) - first * ELEM);
+    const unsigned long long nt = (count + G::TQ - 1) / G::TQ;
+    for (unsigned long long t = blockIdx.x; t < nt; t += gridDim.x) {
+        const unsigned long long i0 = first + t * G::TQ;
+        const uint32_t cnt = (uint32_t)min((unsigned long long)G::TQ, first + count - i0);
+        sh_tile_inverse<ELEM>(in, base, q, i0, cnt, lds);
+        __syncthreads();                                       // (the next tile of this workgroup reuses the LDS image)
+    }
+}
+
+hipError_t unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                  unsigned long long first, unsigned long long count)
+{
+    if (count == 0) return hipSuccess;
+    const unsigned long long tq = SH_TILE / elem, nt = (count + tq - 1) / tq;
+    const dim3 grid((uint32_t)std::min<unsigned long long>(nt, 1u << 24)), block(SH_THREADS);
+    switch (elem) {
+    case 2: hipLaunchKernelGGL(k_unshuffle_range<2>, grid, block, 0, st, in, out, q, first, count); break;
+    case 4: hipLaunchKernelGGL(k_unshuffle_range<4>, grid, block, 0, st, in, out, q, first, count); break;
+    case 8: hipLaunchKernelGGL(k_unshuffle_range<8>, grid, block, 0, st, in, out, q, first, count); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 hipError_t shuffle_segments(hipStream_t st, const uint8_t *inBase, uint8_t *outBase, const unsigned long long *d_off,
                             const unsigned long long *d_len, uint32_t count, uint32_t elem, bool inverse)
 {

@@ -655,7 +655,11 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcContainerLastError", "glcShuffleSegments", "glcUnshuffleSegments", "glcShuffleDevice", "glcUnshuffleDevice",
                      "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec",
                      "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta",
-                     "glcSparseSplitSegments", "glcSparseJoinSegments", "glcPlanSetContainerSparse", "glcPlanGetContainerSparse"]
+                     "glcSparseSplitSegments", "glcSparseJoinSegments", "glcPlanSetContainerSparse", "glcPlanGetContainerSparse",
+                     "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
+                     "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
+                     "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
+RANGE_SYMBOLS = CONTAINER_SYMBOLS[-11:]                         # the frame index and the range reads
 CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0 = 0, 1
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
@@ -690,8 +694,20 @@ def _ct():
         L.glcPlanGetContainerSparse.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcSparseSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         L.glcSparseJoinSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
-        for nm in CONTAINER_SYMBOLS[1:]:
+        for nm in ("glcContainerIndexDevice", "glcContainerIndex"):
+            getattr(L, nm).argtypes = [sz, vp, ull, C.POINTER(vp)]
+        L.glcContainerIndexFile.argtypes = [sz, C.c_char_p, C.POINTER(vp)]
+        L.glcContainerIndexFree.argtypes = [vp]
+        L.glcContainerIndexInfo.argtypes = [vp, ullp]
+        for nm in ("glcContainerReadRangeDevice", "glcContainerReadRange"):
+            getattr(L, nm).argtypes = [sz, vp, vp, ull, ull, ull, vp]
+        L.glcContainerReadRangeFile.argtypes = [sz, vp, C.c_char_p, ull, ull, vp]
+        L.glcContainerLastRangeStats.argtypes = [sz, ullp]
+        for nm in ("glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, ull, ull, vp]
+        for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
+        L.glcContainerIndexFree.restype = None
         L._ct_ready = True
     return L
 
@@ -925,3 +941,115 @@ def container_last_error(plan):
     a = (C.c_ulonglong * 3)()
     _chk("glcContainerLastError", _ct().glcContainerLastError(plan.handle, a))
     return tuple(-1 if v == (1 << 64) - 1 else int(v) for v in a)
+
+
+# --- the frame index and range reads ------------------------------------------------------------------------------------
+class ContainerIndex:
+    """the frame index of one container (glcContainerIndex*): freed by close() or the with statement"""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def info(self):
+        """(total_len, block_len, frames, version, flags, elem)"""
+        a = (C.c_ulonglong * 4)()
+        _chk("glcContainerIndexInfo", _ct().glcContainerIndexInfo(self.ptr, a))
+        return int(a[0]), int(a[1]), int(a[2]), int(a[3]) & 0xFFFF, (int(a[3]) >> 16) & 0xFFFF, int(a[3]) >> 32
+
+    def close(self):
+        if self.ptr:
+            _ct().glcContainerIndexFree(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _host_u8(data):
+    import numpy as np
+    return np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else data, dtype=np.uint8)
+
+
+def container_index(plan, d_cont):
+    """the index of a container in device memory (uint8 tensor, 8-byte aligned): the walk runs on the GPU"""
+    c = d_cont.reshape(-1)
+    p = C.c_void_p(None)
+    _chk("glcContainerIndexDevice", _ct().glcContainerIndexDevice(plan.handle, c.data_ptr(), c.numel(), C.byref(p)))
+    return ContainerIndex(p)
+
+
+def container_index_host(plan, data):
+    a = _host_u8(data)
+    p = C.c_void_p(None)
+    _chk("glcContainerIndex", _ct().glcContainerIndex(plan.handle, a.ctypes.data, a.size, C.byref(p)))
+    return ContainerIndex(p)
+
+
+def container_index_file(plan, path):
+    p = C.c_void_p(None)
+    _chk("glcContainerIndexFile", _ct().glcContainerIndexFile(plan.handle, os.fsencode(path), C.byref(p)))
+    return ContainerIndex(p)
+
+
+def container_read_range(plan, index, d_cont, offset, count, out=None):
+    """bytes [offset, offset + count) of the input of the device container d_cont, into `out` (a device uint8 tensor of at least
+    `count` bytes, any alignment) or a new tensor"""
+    import torch
+    c = d_cont.reshape(-1)
+    if out is None:
+        out = torch.empty(int(count), dtype=torch.uint8, device=c.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= count
+    _chk("glcContainerReadRangeDevice", _ct().glcContainerReadRangeDevice(
+        plan.handle, index.ptr if index is not None else None, c.data_ptr(), c.numel(), int(offset), int(count),
+        out.data_ptr() if out.numel() else None))
+    return out[:int(count)]
+
+
+def container_read_range_host(plan, index, data, offset, count, out=None):
+    import numpy as np
+    a = _host_u8(data)
+    if out is None:
+        out = np.zeros(max(int(count), 1), dtype=np.uint8)
+    _chk("glcContainerReadRange", _ct().glcContainerReadRange(plan.handle, index.ptr if index is not None else None, a.ctypes.data, a.size,
+                                                              int(offset), int(count), out.ctypes.data))
+    return out[:int(count)]
+
+
+def container_read_range_file(plan, index, path, offset, count, out=None):
+    import numpy as np
+    if out is None:
+        out = np.zeros(max(int(count), 1), dtype=np.uint8)
+    _chk("glcContainerReadRangeFile", _ct().glcContainerReadRangeFile(plan.handle, index.ptr if index is not None else None,
+                                                                      os.fsencode(path), int(offset), int(count), out.ctypes.data))
+    return out[:int(count)]
+
+
+def container_last_range_stats(plan):
+    """(frames fetched, blocks decoded, container bytes fetched) of the plan's last successful range read"""
+    a = (C.c_ulonglong * 3)()
+    _chk("glcContainerLastRangeStats", _ct().glcContainerLastRangeStats(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
+def _unshuffle_range(fn, d_in, elem, first, count, out, stream):
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(first), int(count), stream))
+    return out
+
+
+def unshuffle_range(d_in, elem, first, count, out=None, stream=None):
+    """elements [first, first + count) of unshuffle(d_in, elem), reading only the plane runs they come from"""
+    return _unshuffle_range("glcUnshuffleRangeDevice", d_in, elem, first, count, out, stream)
+
+
+def undelta_unshuffle_range(d_in, elem, first, count, out=None, stream=None):
+    """elements [first, first + count) of undelta_unshuffle(d_in, elem); first a multiple of 2048"""
+    return _unshuffle_range("glcUndeltaUnshuffleRangeDevice", d_in, elem, first, count, out, stream)

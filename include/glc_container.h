@@ -175,6 +175,67 @@ CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec);
 CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerSparse(CUDPPHandle plan, unsigned int *on);
 
+/* Range reads: bytes [offset, offset + count) of the original input out of a container, decoding only the blocks they need.
+ * No format change: every frame header gives the size of its frame, so a walk over the headers alone -- 32 bytes per frame --
+ * yields a FRAME INDEX: per frame its position in the stream, nb, blk_len, payload words and the output offset of its first byte,
+ * with copies of the stream header and the trailer.  The index is an opaque host object, built once per container and freed with
+ * glcContainerIndexFree (NULL is fine).  Building it makes exactly the checks the full decode makes before it touches a frame's
+ * tables -- stream header (a plan with the sparse mode off is a version-4 reader), every frame header's range check, truncation,
+ * the trailer and stray bytes behind it, a plan whose n is below the blocks' length -- and fails with the same result and the same
+ * glcContainerLastError triple as glcContainerDecompress* on the same bytes; table CRCs, table fields and records are left to
+ * reading.  An empty input's container gives an index of zero frames.  The host and file forms fetch the headers and nothing else
+ * (the file form by pread); the device form walks the chain on the GPU in one launch (d_in 8-byte aligned) and reads the result
+ * back once, twice for a container of more than 1022 frames.
+ *
+ * A read takes the index and the container it was built from (`len`, and the stream header now at position 0, must be the
+ * index's: a different len is CUDPP_ERROR_ILLEGAL_CONFIGURATION, a different header CUDPP_ERROR_UNKNOWN with
+ * {GLC_CONTAINER_STREAM_HEADER, ~0, ~0}).  count == 0 succeeds and writes nothing; offset + count beyond the input's length and a
+ * NULL index are CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written.  d_out / out receive exactly `count` bytes, at any
+ * alignment, and the call returns with them complete.
+ * WHAT A RANGE READ CHECKS.  A frame the range does not overlap is not read at all.  A frame it overlaps is fetched whole and gets
+ * the full decode's checks in the full decode's order -- the header's range check (it must still say what the index says), the
+ * table CRC, every field check, the CRC of EVERY record of the frame -- with the same failure triples; then only the blocks the
+ * range needs are decoded, each checked against its CRC in the tables.  With a filter of element size e over a frame of F bytes,
+ * q = F / e, the needed blocks of bytes [a, b) of the frame are those that hold a byte of one of the e plane runs [j q + i0,
+ * j q + i1), i0 = a / e (rounded down to a multiple of 2048 with the delta on), i1 = min(q, ceil(b / e)), and those of the last
+ * F % e bytes when b reaches into them; without a filter the blocks that intersect [a, b).
+ * WHAT IT DOES NOT CHECK.  The trailer's crc_all is the CRC of the whole input and cannot be checked by a partial read; frames
+ * outside the range are not looked at, so damage there goes unnoticed until a read that touches it.
+ * The host and file forms keep host and device memory proportional to one frame.  A range read decodes into the plan's frame
+ * staging (one frame, allocated on the first read and kept with the plan), a filtered one also into the second staging.
+ * glcContainerLastRangeStats: for the plan's last successful range read, {frames fetched, blocks decoded, container bytes fetched
+ * (the 32-byte stream header and the frames)}.  Measured on one MI355X on 1 GiB in 1 MiB blocks, rows 512, so two frames
+ * (tools/bench_range.py, profiles/range_read.md; medians): a read inside one frame costs the frame's checks whatever its size --
+ * BWT codec 2.2 ms for 4 KiB or 1 MiB and 3.8 ms for 64 MiB against 25.5 ms for the full decode; int64 timestamps with the order-0
+ * codec, delta + shuffle 8 and the sparse mode 2.1-2.4 ms and 2.6 ms against 6.2 ms -- a read across the frame edge twice that, and
+ * the index of the device container 0.07 ms. */
+typedef struct GlcContainerIndex GlcContainerIndex;
+CUDPPResult glcContainerIndexDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, GlcContainerIndex **index);
+CUDPPResult glcContainerIndex(CUDPPHandle plan, const void *in, unsigned long long len, GlcContainerIndex **index);
+CUDPPResult glcContainerIndexFile(CUDPPHandle plan, const char *path, GlcContainerIndex **index);
+void glcContainerIndexFree(GlcContainerIndex *index);
+/* out: total_len, block_len, frame count, version | flags << 16 | elem << 32 */
+CUDPPResult glcContainerIndexInfo(const GlcContainerIndex *index, unsigned long long out[4]);
+CUDPPResult glcContainerReadRangeDevice(CUDPPHandle plan, const GlcContainerIndex *index, const void *d_in, unsigned long long len,
+                                        unsigned long long offset, unsigned long long count, void *d_out);
+CUDPPResult glcContainerReadRange(CUDPPHandle plan, const GlcContainerIndex *index, const void *in, unsigned long long len,
+                                  unsigned long long offset, unsigned long long count, void *out);
+CUDPPResult glcContainerReadRangeFile(CUDPPHandle plan, const GlcContainerIndex *index, const char *path, unsigned long long offset,
+                                      unsigned long long count, void *out);
+CUDPPResult glcContainerLastRangeStats(CUDPPHandle plan, unsigned long long out[3]);
+
+/* Range forms of the two inverse filters, queued on `stream`: d_in is a filtered segment of `len` bytes (plane stride q = len /
+ * elem); d_out receives count * elem bytes, elements first .. first + count - 1 as glcUnshuffleDevice / glcUndeltaUnshuffleDevice
+ * over the whole segment would have produced them.  first + count <= q; the delta form wants `first` a multiple of 2048 (a run
+ * start); any other `first`, any count and any byte alignment of either buffer are fine.  Only the aligned 16-byte granules that
+ * hold a byte of one of the elem plane runs [j q + first, + count) are read, and exactly the output bytes are written.  elem 2, 4
+ * or 8; a bad elem, a range past q, a delta `first` off a run start, a NULL buffer and an output that overlaps the segment are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+CUDPPResult glcUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
+                                    unsigned long long count, void *stream);
+CUDPPResult glcUndeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                           unsigned long long first, unsigned long long count, void *stream);
+
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */
 CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3]);

@@ -1,0 +1,137 @@
+"""Range reads of a container against the full decode of the same container on the same plan, in one process and interleaved.
+
+Two containers of --gib (default 1) GiB of input in blocks of 1 MiB, rows 512:
+  bwt      skewed bytes (the product of two uniform bytes, high half) through the BWT codec
+  ts64     int64 timestamps (tests/series_datagen.py) through the order-0 codec with delta + shuffle 8 and the sparse mode
+For each: glcContainerReadRangeDevice of 4 KiB, 1 MiB and 64 MiB at the start, in the middle and at the end of the input, and
+glcContainerDecompressDevice of all of it.  Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each
+run is bracketed by device events (every call returns with its output complete).  The index (glcContainerIndexDevice) is built once
+per round as a variant of its own and is NOT part of a read's time.  The table gives the median, fastest and slowest time of every
+variant, the median relative to the full decode's, and what glcContainerLastRangeStats reports for the read.  Every read is compared
+with the input once before anything is timed.  One JSON line on stdout; the table goes to --md FILE (default
+profiles/range_read.md).
+
+python tools/bench_range.py [--gib 1] [--reps 20] [--warmup 3] [--md FILE]"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BLOCK, ROWS = 1 << 20, 512
+SIZES = [("4 KiB", 4 << 10), ("1 MiB", 1 << 20), ("64 MiB", 64 << 20)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "range_read.md"))
+    args = ap.parse_args()
+    assert args.reps >= 20, "at least 20 timed repetitions"
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import series_datagen
+    spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
+    glc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(glc)
+    dev = torch.device("cuda:0")
+    n = int(args.gib * (1 << 30))
+    assert n >= 2 * SIZES[-1][1]
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED0030)
+
+    def skewed():
+        a = torch.randint(0, 256, (n,), dtype=torch.int32, device=dev, generator=g)
+        b = torch.randint(0, 256, (n,), dtype=torch.int32, device=dev, generator=g)
+        return ((a * b) >> 8).to(torch.uint8)
+
+    inputs = [("bwt", skewed, dict(codec=0, elem=0, delta=False, sparse=False)),
+              ("ts64", lambda: torch.from_numpy(np.array(series_datagen.series_bytes("ts64", n), copy=True)).to(dev),
+               dict(codec=1, elem=8, delta=True, sparse=True))]
+    res = {"bytes": n, "block": BLOCK, "rows": ROWS, "reps": args.reps, "containers": {}}
+    rows = ["| container | read | at | median ms | fastest | slowest | time / full decode | frames | blocks | container bytes fetched |",
+            "|---|---|---|---|---|---|---|---|---|---|"]
+    with glc.Cudpp() as ctx:
+        for name, make, st in inputs:
+            x = make()
+            assert x.numel() == n
+            with glc.Plan(ctx, glc.CUDPP_COMPRESS, BLOCK, rows=ROWS) as plan:
+                glc.container_set_shuffle(plan, st["elem"])
+                glc.container_set_codec(plan, st["codec"])
+                if st["delta"]:
+                    glc.container_set_delta(plan, 1)
+                if st["sparse"]:
+                    glc.container_set_sparse(plan, 1)
+                c = glc.container_compress(plan, x).clone()
+                full_out = torch.empty(n, dtype=torch.uint8, device=dev)
+                d_len = torch.zeros(1, dtype=torch.int64, device=dev)
+                range_out = torch.empty(SIZES[-1][1], dtype=torch.uint8, device=dev)
+                L = glc._ct()
+
+                def full():
+                    glc._chk("full", L.glcContainerDecompressDevice(plan.handle, c.data_ptr(), c.numel(), full_out.data_ptr(), n, d_len.data_ptr()))
+
+                ix = glc.container_index(plan, c)
+                reads = []
+                for label, size in SIZES:
+                    for at, off in (("start", 0), ("middle", (n - size) // 2 // 8 * 8 + 3), ("end", n - size)):
+                        reads.append((label, at, off, size))
+                stats = {}
+                full()
+                assert torch.equal(full_out, x)
+                for label, at, off, size in reads:               # correctness of what is timed, once
+                    out = glc.container_read_range(plan, ix, c, off, size, out=range_out)
+                    assert torch.equal(out, x[off:off + size]), (name, label, at)
+                    stats[label, at] = glc.container_last_range_stats(plan)
+
+                def read(off, size):
+                    return lambda: glc.container_read_range(plan, ix, c, off, size, out=range_out)
+
+                def index():
+                    glc.container_index(plan, c).close()
+
+                variants = [("full", "decode", full), ("index", "build", index)]
+                variants += [(label, at, read(off, size)) for label, at, off, size in reads]
+                times = {(a, b): [] for a, b, _ in variants}
+                events = []
+                for r in range(args.warmup + args.reps):
+                    for a, b, fn in variants:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        fn()
+                        e1.record()
+                        if r >= args.warmup:
+                            events.append(((a, b), e0, e1))
+                torch.cuda.synchronize()
+                for key, e0, e1 in events:
+                    times[key].append(e0.elapsed_time(e1))
+                ix.close()
+                base = statistics.median(times["full", "decode"])
+                out = res["containers"][name] = {"container_bytes": int(c.numel()), "frames": (n + BLOCK * ROWS - 1) // (BLOCK * ROWS),
+                                                 "variants": {}}
+                for a, b, _ in variants:
+                    t = sorted(times[a, b])
+                    med = statistics.median(t)
+                    s = stats.get((a, b), ("", "", ""))
+                    out["variants"]["%s %s" % (a, b)] = {"median_ms": med, "min_ms": t[0], "max_ms": t[-1], "vs_full": med / base,
+                                                         "stats": list(s) if s[0] != "" else None}
+                    rows.append("| %s | %s | %s | %.3f | %.3f | %.3f | %.3f | %s | %s | %s |" % (name, a, b, med, t[0], t[-1], med / base, *s))
+            del x, c, full_out
+    head = ("Range reads against the full decode, %d bytes of input per container in blocks of %d, rows %d (%d frames), %d timed rounds "
+            "after %d, device events, one process, variants interleaved (tools/bench_range.py).  `index build` is "
+            "glcContainerIndexDevice alone and is not part of a read's time.  Where the middle of the input is the edge between two "
+            "frames, a `middle` read overlaps both and fetches both; `start` and `end` reads overlap one.\n\n"
+            % (n, BLOCK, ROWS, (n + BLOCK * ROWS - 1) // (BLOCK * ROWS), args.reps, args.warmup))
+    with open(args.md, "w") as f:
+        f.write(head + "\n".join(rows) + "\n")
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
