@@ -407,7 +407,8 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     if (b < nb) {
         if (skip0) {                                           // (version 3 and later: whose tables are built next)
             const uint32_t kind = W[T.kind + b];
-            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind >= CT_KIND_SPARSE) ? 0u : 1u;
+            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind >= CT_KIND_SPARSE) ||
+                       (kind == CT_KIND_RUNS && max_kind >= CT_KIND_RUNS) ? 0u : 1u;
         }
         const unsigned long long lo = po[b], hi = po[b + 1];
         const bool ok = lo <= hi && hi <= P;
@@ -436,11 +437,37 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
     reinterpret_cast<uint32_t *>(f.verdict + 2)[b] = kind;
     const unsigned long long lo = po[b], hi = po[b + 1];
     bool bad = kind > (nun0 ? h0.max_kind : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
-    unsigned long long klen = 0;
+    const bool runs = nun0 && h0.max_kind >= CT_KIND_RUNS;       // (version 6: kind 3 is not legal)
+    bad = bad || (runs && kind == CT_KIND_SPARSE);
+    unsigned long long klen = 0, nB = 0, nzw = 0;
     if (!bad) {
         const unsigned long long w = hi - lo;
         if (kind == CT_KIND_RAW) bad = w != ct_raw_words(blk_len);
-        else if (kind == CT_KIND_SPARSE) {
+        else if (kind == CT_KIND_RUNS) {
+            // a zero-run record, the checks in the order of INTEGRATION.md 4b: the BWT index inside the block, nothing else set,
+            // counts of a non-empty A; nz and the pairs read only once the record is known to hold them; the pairs ascending
+            // with counts of their own that sum to A's zeros and, with A's other bytes, expand to exactly blk_len; and behind
+            // the pairs exactly the units the two tables ask for -- so decoding nA and nB symbols consumes the record exactly
+            // and the join of what they decode to fills the block exactly
+            const uint32_t *h = W + T.hist + 256ull * b;
+            const uint32_t *rec = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR + 4 * T.words) + lo;
+            bad = W[T.bwt + b] >= blk_len;
+            const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
+            for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] != 0;
+            unsigned long long sum = 0, cnt = 0, expand = 0;
+            for (uint32_t s = 0; s < 256; s++) sum += h[s];
+            bad = bad || sum < 1 || w < 1;
+            nzw = bad ? 0 : rec[0];
+            bad = bad || nzw > 256 || w < 1 + nzw;
+            for (uint32_t s = 0; s < nzw && !bad; s++) {
+                const unsigned long long v = rec[1 + s] >> 24, c = rec[1 + s] & 0xFFFFFFu;
+                bad = c < 1 || (s > 0 && (rec[s] >> 24) >= v);
+                cnt += c; expand += c * (v + 1);
+            }
+            bad = bad || cnt != h[0] || (sum - h[0]) + expand != blk_len;
+            klen = sum; nB = cnt;
+            bad = bad || w != 1 + nzw + nun0[b] + (nB ? h0.nun_b[b] : 0ull);
+        } else if (kind == CT_KIND_SPARSE) {
             // a sparse record: a fill byte, nothing else set, a whole mask with its unused bits zero (read only once the record
             // is known to hold it), the counts those of the kept bytes, and behind the mask exactly the units their table asks
             // for -- so decoding klen symbols consumes the record exactly and the expansion reads exactly klen bytes
@@ -475,7 +502,20 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
             for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] >= w || (s > 0 && eo[s] <= eo[s - 1]);
         }
     }
-    if (nun0 && h0.max_kind >= CT_KIND_SPARSE) {
+    if (runs) {                                                  // A into the kept space, B beside it, the join into the MTF rows
+        const bool k4 = !bad && kind == CT_KIND_RUNS;
+        const size_t slot = b % h0.chunk;
+        h0.k_off[b] = (unsigned long long)(uintptr_t)(h0.kept + slot * h0.kept_stride);
+        h0.k_len[b] = k4 ? klen : 0;
+        h0.u_off[b] = k4 ? lo + 1 + nzw : 0;
+        h0.skip3[b] = k4 ? 0u : 1u;
+        h0.b_off[b] = (unsigned long long)(uintptr_t)(h0.kept_b + slot * h0.kept_stride);
+        h0.b_len[b] = k4 ? nB : 0;
+        h0.ub_off[b] = k4 ? lo + 1 + nzw + nun0[b] : 0;
+        h0.skip_b[b] = k4 && nB ? 0u : 1u;
+        h0.m_off[b] = (unsigned long long)(uintptr_t)(h0.mtf + slot * h0.mtf_stride);
+        h0.m_len[b] = blk_len;
+    } else if (nun0 && h0.max_kind >= CT_KIND_SPARSE) {
         const bool k3 = !bad && kind == CT_KIND_SPARSE;
         h0.k_off[b] = (unsigned long long)(uintptr_t)(h0.kept + (size_t)(b % h0.chunk) * h0.kept_stride);
         h0.k_len[b] = k3 ? klen : 0;
@@ -533,6 +573,12 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
         const HdbSegs g{nullptr, nullptr, nullptr, nb, blk_len};
         e = hdb_tables(st, g, false, hist, nullptr, nullptr, h0->lut, h0->nun, h0->skip, prof);
         if (e != hipSuccess) return e;
+        if (h0->max_kind >= CT_KIND_RUNS) {                    // (version 6: the tables of B, from the counts in the records)
+            e = ct_dec_runs_hist(st, frame, nb, blk_len, payload_words, *h0);
+            if (e != hipSuccess) return e;
+            e = hdb_tables(st, g, false, h0->hist_b, nullptr, nullptr, h0->lut_b, h0->nun_b, h0->skip_tb, prof);
+            if (e != hipSuccess) return e;
+        }
     }
     e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb + 2, f.crc);
     if (e != hipSuccess) return e;
@@ -583,13 +629,13 @@ hipError_t ct_dec_fold(hipStream_t st, const CtDecFrame &f, const uint8_t *bytes
 // lane to do: one dependent 32-byte read per frame.  Every read lies inside [in, in + len): the walk tests the position of a
 // header against len before it fetches it.  Entry fi is written only while fi < cap.
 // ---------------------------------------------------------------------------
-__global__ void k_ct_index(const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t sparse_reader, CtIndexHead *head,
+__global__ void k_ct_index(const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t reader, CtIndexHead *head,
                            CtFrameRef *entries, unsigned long long cap)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     CtIndexHead h = {};
     const CtWalkEnd end = ct_walk(
-        g_crc, len, plan_n, sparse_reader != 0,
+        g_crc, len, plan_n, reader,
         [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long) {
             const uint32_t *src = reinterpret_cast<const uint32_t *>(in + pos);       // (pos is a multiple of 8, as is `in`)
             for (uint32_t i = 0; i < bytes / 4; i++) dst[i] = src[i];
@@ -614,10 +660,10 @@ __global__ void k_ct_index(const uint8_t *in, unsigned long long len, uint32_t p
     *head = h;
 }
 
-hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, bool sparse_reader,
+hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t reader,
                            CtIndexHead *head, CtFrameRef *entries, unsigned long long cap)
 {
-    hipLaunchKernelGGL(k_ct_index, dim3(1), dim3(64), 0, st, in, len, plan_n, sparse_reader ? 1u : 0u, head, entries, cap);
+    hipLaunchKernelGGL(k_ct_index, dim3(1), dim3(64), 0, st, in, len, plan_n, reader, head, entries, cap);
     return hipGetLastError();
 }
 

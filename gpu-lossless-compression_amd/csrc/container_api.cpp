@@ -2,12 +2,14 @@
 // A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says two
 // things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
-// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
+// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal(), 4 the BWT codec's
+// zero-run form (zrun.hip) where kind4_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
 // writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's (both read ct_legal()).
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
-// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3).  Either way the kernels of container.hip decide the record kinds before the
+// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3).  With the BWT codec's
+// runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
 // Decode: decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from the caller's
@@ -15,7 +17,8 @@
 // and a range read (glcContainerReadRange*) decodes a subset of the blocks of the frames its range overlaps.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
 // verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
 // place, runs of kind 2 to the batched order-0 decoder, runs of kind 3 to it as well (the kept bytes into scratch, then expanded
-// under the record's mask), and the decoded bytes are checked against the blocks' CRCs; a filtered
+// under the record's mask), runs of kind 4 to it too (A and B into scratch, joined into the BWT decoder's MTF rows, then its
+// inverse MTF and inverse BWT), and the decoded bytes are checked against the blocks' CRCs; a filtered
 // frame is decoded into staging, checked there and inverted into the output by filter_device().
 #include "../../include/glc_container.h"
 #include "container_internal.h"
@@ -80,6 +83,7 @@ CUDPPResult hip_res(hipError_t e)
 }
 
 #define CT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_res(e_); } while (0)
+#define CT_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 struct Plan {
     CUDPPHandle h = 0;
@@ -113,7 +117,8 @@ CtFormat format_of(const CtSettings &s)
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         f.version = ct_legal(i).version;
-        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal())) break;
+        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal()) &&
+            (!s.runs || f.kind4_legal())) break;
     }
     return f;                                                 // (the setters accept only what some row takes)
 }
@@ -161,8 +166,33 @@ struct Encoder {
     CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
     bool sparse = false;                                      // the codec's sparse mode
     CtEncSparse sp = {};                                      // its scratch, behind h0's; a plan that never has it on has none
+    bool runs = false;                                        // the BWT codec's runs mode
+    CtEncRuns zr = {};                                        // its scratch, kept with the plan; a plan that never has it on has none
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
+    // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
+    void carve_runs(Carver &c)
+    {
+        const size_t R = P.rows;
+        zr.x_off = c.take<unsigned long long>(R);
+        zr.x_len = c.take<unsigned long long>(R);
+        zr.seg_off = c.take<unsigned long long>(2 * R);
+        zr.seg_len = c.take<unsigned long long>(2 * R);
+        zr.nun = c.take<unsigned long long>(2 * R);
+        zr.unit_off = c.take<unsigned long long>(2 * R);
+        zr.skip_enc = c.take<uint32_t>(2 * R);
+        zr.skip_b = c.take<uint32_t>(R);
+        zr.nz = c.take<uint32_t>(R);
+        zr.hist_b = c.take<uint32_t>(256 * R);
+        zr.codes = c.take<uint16_t>(256 * 2 * R);
+        zr.lens = c.take<uint8_t>(256 * 2 * R);
+        c.align(256);
+        zr.work = c.take<uint8_t>(hdb_encode_work_bytes(2 * R));
+        c.align(256);
+        zr.stride = (P.n + 15u) & ~15u;
+        zr.a = c.take<uint8_t>(R * zr.stride);
+        zr.b = c.take<uint8_t>(R * zr.stride);
+    }
     void carve_huff0(Carver &c)
     {
         const size_t R = P.rows;
@@ -219,6 +249,16 @@ struct Encoder {
         fmt = format_of(s);
         codec = s.codec;
         sparse = s.sparse && codec == CT_CODEC_HUFF0;
+        runs = s.runs && codec == CT_CODEC_BWT;
+        if (runs) {
+            Carver measure;
+            carve_runs(measure);
+            uint8_t *q = nullptr;
+            const hipError_t e = plan_codec_scratch(P.h, 0, measure.bytes(), &q);
+            if (e != hipSuccess) return e;
+            Carver place(q);
+            carve_runs(place);
+        }
         if (codec == CT_CODEC_HUFF0) {
             Carver measure;
             carve_huff0(measure);
@@ -260,6 +300,7 @@ struct Encoder {
             d_in = stage[P.parity];
         }
         if (sparse) return frame_sparse(f, d_in, orig, nb, blk_len, out, cap);
+        if (runs) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
         if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
@@ -324,6 +365,38 @@ struct Encoder {
         return CUDPP_SUCCESS;
     }
 
+    // the BWT codec's frame with the runs mode on, wholly on the plan's stream: BWT and MTF of the blocks by the plan's sorter
+    // and MTF stage -> the split into A and B -> tables of the A's (their counts are the record's hist) and of the B's -> nz,
+    // record sizes and the raw rule -> payload offsets -> nz and the pairs into the records -> every stream encoded at its
+    // place, A's and B's in one launch -> the same stage behind the packer as ever
+    CUDPPResult frame_runs(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
+                           uint8_t *out, unsigned long long cap)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        plan_stage_mark(P.h, 0);
+        const uint8_t *mtf = nullptr;
+        size_t mtf_stride = 0;
+        CT_TRY(plan_bwt_mtf(P.h, d_in, blk_len, nb, f.bwt, &mtf, &mtf_stride));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_runs_segs(P.st, zr, mtf, mtf_stride, nb, blk_len));
+        const ZrSegs z{nullptr, zr.x_off, zr.x_len, nullptr, zr.seg_off, zr.seg_len, nullptr, zr.seg_off + nb, zr.seg_len + nb, nullptr,
+                       nb, blk_len};
+        CT_TRY(zrun_split(P.st, z));
+        CT_TRY(ct_enc_runs_empty(P.st, zr, nb));
+        const HdbSegs ga{nullptr, zr.seg_off, zr.seg_len, nb, blk_len}, gb{nullptr, zr.seg_off + nb, zr.seg_len + nb, nb, blk_len};
+        CT_TRY(hdb_tables(P.st, ga, true, f.hist, zr.lens, zr.codes, nullptr, zr.nun, nullptr, prof));
+        CT_TRY(hdb_tables(P.st, gb, true, zr.hist_b, zr.lens + 256ull * nb, zr.codes + 256ull * nb, nullptr, zr.nun + nb, zr.skip_b, prof));
+        CT_TRY(ct_enc_runs_kind(P.st, f, zr, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
+        CT_TRY(ct_enc_runs_place(P.st, f, zr, nb, reinterpret_cast<uint32_t *>(out), cap / 4));
+        const HdbSegs gab{nullptr, zr.seg_off, zr.seg_len, 2 * nb, blk_len};
+        CT_TRY(hdb_encode(P.st, gab, zr.lens, zr.codes, zr.nun, reinterpret_cast<uint32_t *>(out), zr.unit_off, cap / 4, zr.skip_enc, zr.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
+    }
+
     // every frame of [d_in, + len) with the plan's n and rows
     CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap)
     {
@@ -364,7 +437,7 @@ struct Decoder {
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_decode_work_bytes(h0.chunk, blk_len));
         h0.max_kind = fmt.max_kind();
-        if (!fmt.kind3_legal()) return;
+        if (!fmt.kind3_legal() && !fmt.kind4_legal()) return;
         h0.k_off = c.take<unsigned long long>(n4);
         h0.k_len = c.take<unsigned long long>(n4);
         h0.u_off = c.take<unsigned long long>(n4);
@@ -372,11 +445,24 @@ struct Decoder {
         c.align(256);
         h0.kept_stride = (blk_len + 15u) & ~15u;
         h0.kept = c.take<uint8_t>((size_t)h0.chunk * h0.kept_stride);
+        if (!fmt.kind4_legal()) return;
+        h0.kept_b = c.take<uint8_t>((size_t)h0.chunk * h0.kept_stride);
+        h0.b_off = c.take<unsigned long long>(n4);
+        h0.b_len = c.take<unsigned long long>(n4);
+        h0.ub_off = c.take<unsigned long long>(n4);
+        h0.nun_b = c.take<unsigned long long>(n4);
+        h0.m_off = c.take<unsigned long long>(n4);
+        h0.m_len = c.take<unsigned long long>(n4);
+        h0.skip_b = c.take<uint32_t>(n4);
+        h0.skip_tb = c.take<uint32_t>(n4);
+        h0.hist_b = c.take<uint32_t>(256 * (size_t)nb);
+        h0.lut_b = c.take<uint16_t>(2048 * (size_t)nb);
     }
     hipError_t reserve_huff0(uint32_t nb, uint32_t blk_len)
     {
         const size_t per = hdb_decode_work_bytes(1, blk_len) + 512;
         h0.chunk = (uint32_t)std::min<size_t>(std::min<size_t>(P.rows, nb), std::max<size_t>(1, ((size_t)256 << 20) / per));
+        if (fmt.kind4_legal()) CT_HIP(plan_decode_rows(P.h, &h0.mtf, &h0.mtf_stride));   // (where the join leaves the MTF bytes)
         Carver measure;
         carve_huff0(measure, nb, blk_len);
         uint8_t *q = nullptr;
@@ -495,6 +581,21 @@ struct Decoder {
             const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
                            reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, 0, nullptr, b - a, blk_len};
             CT_TRY(sparse_join(P.st, s));
+            a = b;
+        }
+        // runs of zero-run blocks inside one chunk of the decoder: A and B decoded into scratch, joined into the rows b % chunk of
+        // the decoder's MTF bytes, and from there the BWT codec's own inverse MTF and inverse BWT
+        for (uint32_t a = 0; fmt.kind4_legal() && a < nb;) {
+            if (kind[a] != CT_KIND_RUNS || !want(a)) { a++; continue; }
+            uint32_t b = a;
+            while (b < nb && kind[b] == CT_KIND_RUNS && want(b) && b / h0.chunk == a / h0.chunk) b++;
+            const HdbOut ga{nullptr, h0.k_off + a, h0.k_len + a, b - a, blk_len}, gb{nullptr, h0.b_off + a, h0.b_len + a, b - a, blk_len};
+            CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, ga, h0.skip3 + a, h0.work, prof));
+            CT_TRY(hdb_decode(P.st, pay, h0.ub_off + a, h0.nun_b + a, h0.lut_b + 2048ull * a, gb, h0.skip_b + a, h0.work, prof));
+            const ZrSegs z{nullptr, h0.m_off + a, h0.m_len + a, nullptr, h0.k_off + a, h0.k_len + a, nullptr, h0.b_off + a, h0.b_len + a,
+                           nullptr, b - a, blk_len};
+            CT_TRY(zrun_join(P.st, z));
+            CT_TRY(plan_decode_from_mtf(P.h, a % h0.chunk, reinterpret_cast<const int *>(W + T.bwt) + a, out + (size_t)a * blk_len, blk_len, b - a));
             a = b;
         }
         plan_join(P.h);
@@ -682,7 +783,7 @@ CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned
     const CUDPPHandle plan = D.P.h;
     CUDPPResult r = CUDPP_SUCCESS;                              // why a callback stopped the walk
     const CtWalkEnd end = ct_walk(
-        h_crc, len, D.P.n, plan_container_settings(plan).sparse,   // a plan with the sparse mode off is a version-4 reader
+        h_crc, len, D.P.n, plan_container_settings(plan).reader(),   // a plan with the sparse and runs modes off is a version-4 reader
         [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long frame) {
             return (r = feed.header(dst, pos, bytes, frame)) == CUDPP_SUCCESS;
         },
@@ -856,7 +957,7 @@ CUDPPResult index_host(CUDPPHandle plan, RandomSource &src, unsigned long long l
     ix->len = len;
     CUDPPResult r = CUDPP_SUCCESS;
     const CtWalkEnd end = ct_walk(
-        h_crc, len, P.n, plan_container_settings(plan).sparse,
+        h_crc, len, P.n, plan_container_settings(plan).reader(),
         [&](uint32_t *dst, unsigned long long pos, uint32_t bytes, unsigned long long frame) {
             if (src.at(dst, pos, bytes)) return true;
             r = fail(plan, CT_TRUNCATED, frame);
@@ -972,7 +1073,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
     uint32_t hdr[8];
     if (io.small(hdr, 0, CT_HDR) != CUDPP_SUCCESS) return fail(plan, CT_TRUNCATED);
     if (memcmp(hdr, ix->hdr, CT_HDR) != 0) return fail(plan, CT_STREAM_HEADER);           // another container than the index's
-    if (ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) return fail(plan, CT_STREAM_HEADER);
+    if ((ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) || (ix->fmt.kind4_legal() && !plan_container_settings(plan).runs))
+        return fail(plan, CT_STREAM_HEADER);
     stats.v[2] = CT_HDR;
     D.fmt = ix->fmt;
     CT_TRY(D.begin());
@@ -1057,7 +1159,7 @@ CUDPPResult glcContainerIndexDevice(CUDPPHandle plan, const void *d_in, unsigned
     CT_TRY(plan_codec_scratch(plan, 2, sizeof(CtIndexHead) + cap * sizeof(CtFrameRef), &scratch));
     CtIndexHead *d_head = reinterpret_cast<CtIndexHead *>(scratch);
     CtFrameRef *d_ent = reinterpret_cast<CtFrameRef *>(scratch + sizeof(CtIndexHead));
-    CT_TRY(ct_index_device(P.st, static_cast<const uint8_t *>(d_in), len, P.n, plan_container_settings(plan).sparse, d_head, d_ent, cap));
+    CT_TRY(ct_index_device(P.st, static_cast<const uint8_t *>(d_in), len, P.n, plan_container_settings(plan).reader(), d_head, d_ent, cap));
     // one readback: the head and the first entries; a container of more frames than that fetches the rest
     const size_t first = (size_t)std::min<unsigned long long>(cap, CT_INDEX_FIRST);
     std::vector<uint8_t> back(sizeof(CtIndexHead) + first * sizeof(CtFrameRef));
@@ -1314,6 +1416,39 @@ CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long lo
     return CUDPP_SUCCESS;
 }
 
+// the two zero-run calls: a bad argument is refused before anything is enqueued
+static bool zrun_args_ok(const void *x, const void *off, const void *len, const void *a, const void *b, const void *alen, const void *blen,
+                         size_t count, size_t maxLen)
+{
+    return count <= 0xFFFFFFFFull && maxLen <= GLC_ZERORUN_MAX_LEN && (count == 0 || (x && off && len && a && b && alen && blen)) &&
+           (count == 0 || (x != a && x != b && a != b));
+}
+
+CUDPPResult glcZeroRunSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                    size_t count, size_t maxLen, void *d_aBase, void *d_bBase, unsigned long long *d_aLen,
+                                    unsigned long long *d_bLen, void *stream)
+{
+    if (!zrun_args_ok(d_inBase, d_offsets, d_lengths, d_aBase, d_bBase, d_aLen, d_bLen, count, maxLen)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    const ZrSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, static_cast<uint8_t *>(d_aBase), d_offsets, d_aLen,
+                   static_cast<uint8_t *>(d_bBase), d_offsets, d_bLen, nullptr, (uint32_t)count, (uint32_t)maxLen};
+    CT_TRY(zrun_split(reinterpret_cast<hipStream_t>(stream), g));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcZeroRunJoinSegments(const void *d_aBase, const void *d_bBase, const unsigned long long *d_offsets,
+                                   const unsigned long long *d_aLen, const unsigned long long *d_bLen, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, void *d_outBase, void *stream)
+{
+    if (!zrun_args_ok(d_outBase, d_offsets, d_lengths, d_aBase, d_bBase, d_aLen, d_bLen, count, maxLen)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    const ZrSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, static_cast<uint8_t *>(const_cast<void *>(d_aBase)), d_offsets,
+                   const_cast<unsigned long long *>(d_aLen), static_cast<uint8_t *>(const_cast<void *>(d_bBase)), d_offsets,
+                   const_cast<unsigned long long *>(d_bLen), nullptr, (uint32_t)count, (uint32_t)maxLen};
+    CT_TRY(zrun_join(reinterpret_cast<hipStream_t>(stream), g));
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
 {
     return shuffle_device_api(d_in, d_out, len, elem, stream, false);
@@ -1363,6 +1498,7 @@ CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
     CtSettings &s = plan_container_settings(plan);
     s.codec = codec;
     if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = false;   // (no sparse mode without the order-0 codec)
+    if (codec != GLC_CONTAINER_CODEC_BWT) s.runs = false;       // (no runs mode without the BWT codec)
     return CUDPP_SUCCESS;
 }
 
@@ -1400,6 +1536,25 @@ CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     *codec = plan_container_settings(plan).codec;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerRuns(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    CtSettings &s = plan_container_settings(plan);
+    if (on > 1 || (on && s.codec != GLC_CONTAINER_CODEC_BWT)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    s.runs = on != 0;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).runs ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -112,6 +112,23 @@ hipError_t sparse_count(hipStream_t st, const SpSegs &g, unsigned long long *d_k
 hipError_t sparse_compact(hipStream_t st, const SpSegs &g);                               // data, mask -> K
 hipError_t sparse_join(hipStream_t st, const SpSegs &g);                                  // K, mask, fill -> data
 
+// the zero-run passes (zrun.hip; the split is defined in INTEGRATION.md 4b).  Segment i is x + x_off[i], min(x_len[i], max_len)
+// bytes, cut into tiles of 256; A (the non-zero bytes and one 0 per run of zeros, a run ending at a tile edge) is at a + a_off[i],
+// B (run length - 1 per run) at b + b_off[i], their byte counts in a_len[i] / b_len[i].  Any base may be null with absolute
+// addresses in the offsets.  skip (optional): segments whose entry is non-zero are left alone.  Everything only enqueues on `st`.
+constexpr uint32_t ZR_TILE = 256, ZR_MAX_LEN = 1u << 20;
+struct ZrSegs {
+    uint8_t *x; const unsigned long long *x_off, *x_len;
+    uint8_t *a; const unsigned long long *a_off; unsigned long long *a_len;
+    uint8_t *b; const unsigned long long *b_off; unsigned long long *b_len;
+    const uint32_t *skip;
+    uint32_t count, max_len;
+};
+hipError_t zrun_split(hipStream_t st, const ZrSegs &g);      // x -> A, B, a_len, b_len
+// A, B (a_len / b_len are read, clamped to max_len) -> x.  Tolerant: a zero of A beyond B's end is a run of one, nothing is read
+// outside A or B and nothing written outside the segment, whatever the streams hold
+hipError_t zrun_join(hipStream_t st, const ZrSegs &g);
+
 // ---------------------------------------------------------------------------
 // layout (little-endian; every section 8-byte aligned)
 // ---------------------------------------------------------------------------
@@ -123,6 +140,7 @@ constexpr uint32_t CT_VERSION_CODEC = 3;                     // 3: kind 2 is leg
 constexpr uint32_t CT_VERSION_DELTA = 4;                     // 4: version 3 with flags in the upper half of the version dword
 constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the only one): the filter is delta + shuffle; elem 2, 4 or 8
 constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is legal; flags 0 (elem 0, 2, 4, 8) or the delta flag (elem 2, 4, 8)
+constexpr uint32_t CT_VERSION_RUNS = 6;                      // 6: kinds 0, 1, 2 and 4 are legal (not 3); the same triples as version 5
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
@@ -131,20 +149,22 @@ struct CtFormat {
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     __host__ __device__ bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
-    __host__ __device__ bool kind3_legal() const { return version >= CT_VERSION_SPARSE; }
-    __host__ __device__ uint32_t max_kind() const { return kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
+    __host__ __device__ bool kind3_legal() const { return version == CT_VERSION_SPARSE; }
+    __host__ __device__ bool kind4_legal() const { return version == CT_VERSION_RUNS; }
+    __host__ __device__ uint32_t max_kind() const { return kind4_legal() ? 4u : kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }   // (version 6: all but 3)
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 struct CtLegal { uint32_t version, flags, elems; };
-constexpr uint32_t CT_NLEGAL = 6;
+constexpr uint32_t CT_NLEGAL = 8;
 __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 {
     constexpr CtLegal L[CT_NLEGAL] = {
         {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
-        {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}};
+        {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_RUNS, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}};
     return L[i];
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
@@ -158,7 +178,10 @@ __host__ __device__ inline bool format_legal(const CtFormat &f)
 constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
 constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 record (sparse.hip): mask, then the kind-2 stream of the kept chunks; version 5
+constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
+// what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6
+constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2;
 
 // failure classes of glcContainerLastError (out[0])
 enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
@@ -239,10 +262,10 @@ constexpr uint32_t CT_WALK_CONFIG = 0x100, CT_WALK_STOPPED = 0x101;
 struct CtWalkEnd { uint32_t what; unsigned long long frame; };            // frame: the index a failure names (~0 = none)
 
 // fetch(dst, pos, bytes, frame) -> bool brings 32 or 16 header bytes into dst; on_header(h, fmt, block_len, total),
-// on_frame(fi, fh, ref) and on_trailer(tr, frames) -> bool see what has passed its checks.  `sparse_reader` is the plan's sparse
-// mode (a plan with it off is a version-4 reader), plan_n its block length.
+// on_frame(fi, fh, ref) and on_trailer(tr, frames) -> bool see what has passed its checks.  `reader` (CT_READS_*) is the plan's
+// sparse and runs modes (a plan with both off is a version-4 reader), plan_n its block length.
 template <class Fetch, class OnHeader, class OnFrame, class OnTrailer>
-__host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long long len, uint32_t plan_n, bool sparse_reader, Fetch fetch,
+__host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long long len, uint32_t plan_n, uint32_t reader, Fetch fetch,
                                              OnHeader on_header, OnFrame on_frame, OnTrailer on_trailer)
 {
     const unsigned long long none = ~0ull;
@@ -252,7 +275,7 @@ __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long l
     CtFormat fmt;
     if (!fetch(hdr, 0ull, CT_HDR, none)) return {CT_WALK_STOPPED, none};
     if (!check_stream_header(C, hdr, &fmt, &block_len, &total)) return {CT_STREAM_HEADER, none};
-    if (fmt.kind3_legal() && !sparse_reader) return {CT_STREAM_HEADER, none};
+    if ((fmt.kind3_legal() && !(reader & CT_READS_SPARSE)) || (fmt.kind4_legal() && !(reader & CT_READS_RUNS))) return {CT_STREAM_HEADER, none};
     if (!on_header(hdr, fmt, block_len, total)) return {CT_WALK_STOPPED, none};
     unsigned long long pos = CT_HDR, done = 0;
     uint32_t fi = 0;
@@ -284,7 +307,7 @@ struct CtIndexHead {
 };
 constexpr uint32_t CT_INDEX_FIRST = 1022;                  // entries the one readback brings along with the head (32 KiB in all)
 // the walk over a container in device memory (8-byte aligned), one launch: head and up to `cap` entries into `scratch`
-hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, bool sparse_reader,
+hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t reader,
                            CtIndexHead *head, CtFrameRef *entries, unsigned long long cap);
 
 // ---------------------------------------------------------------------------
@@ -303,8 +326,12 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, CompressCall c, ContainerHook
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
-// mode (only ever on with the shuffle on), the codec (CT_CODEC_*) and its sparse mode (only ever on with the order-0 codec)
-struct CtSettings { uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false; };
+// mode (only ever on with the shuffle on), the codec (CT_CODEC_*), its sparse mode (only ever on with the order-0 codec) and its
+// runs mode (only ever on with the BWT codec)
+struct CtSettings {
+    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false;
+    uint32_t reader() const { return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u); }
+};
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
@@ -320,6 +347,13 @@ void plan_wait_released(CUDPPHandle plan);
 hipError_t plan_codec_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
 KernelProf *plan_prof(CUDPPHandle plan);
 void plan_stage_mark(CUDPPHandle plan, int i);
+// the runs mode's two ends of the plan's BWT codec, wholly on the plan's stream (the side stream is joined first).  Encode: the
+// suffix sort and the MTF of nb blocks of n bytes at `in` -- bwt_index[b] and the MTF bytes, block b at *mtf + b * *stride.
+// Decode: *mtf / *stride are the decoder's MTF rows (allocated on first use); rows [first_row, + nblk) of them -> inverse MTF ->
+// inverse BWT with bwt_index[0 .. nblk) -> out, blocks of n bytes back to back
+hipError_t plan_bwt_mtf(CUDPPHandle plan, const uint8_t *in, uint32_t n, uint32_t nb, int *bwt_index, const uint8_t **mtf, size_t *stride);
+hipError_t plan_decode_rows(CUDPPHandle plan, uint8_t **mtf, size_t *stride);
+hipError_t plan_decode_from_mtf(CUDPPHandle plan, uint32_t first_row, const int *bwt_index, uint8_t *out, uint32_t n, uint32_t nblk);
 
 // ---------------------------------------------------------------------------
 // kernels of container.hip
@@ -348,6 +382,17 @@ struct CtEncSparse {                                       // device scratch of 
     unsigned long long *blk_off, *blk_len;                 // [rows]: the blocks as segments of the frame
     uint8_t *kept; uint32_t kept_stride;                   // [rows][kept_stride] bytes: the compaction space
 };
+struct CtEncRuns {                                         // device scratch of the runs mode (plan_codec_scratch 0; allocated once it is on)
+    unsigned long long *x_off, *x_len;                     // [rows] the MTF rows as segments
+    unsigned long long *seg_off, *seg_len;                 // [2 rows] A of the frame's nb blocks, then B of them: addresses, byte counts
+    unsigned long long *nun, *unit_off;                    // [2 rows] units of each stream; where it starts in the payload
+    uint32_t *skip_enc;                                    // [2 rows] 1 = not encoded (a raw block; an empty B)
+    uint32_t *skip_b, *nz;                                 // [rows] 1 = B is empty (no table); non-zero counts of B
+    uint32_t *hist_b;                                      // [rows][256] B's counts
+    uint8_t *lens; uint16_t *codes;                        // [2 rows][256]
+    void *work;                                            // hdb_encode_work_bytes(2 rows)
+    uint8_t *a, *b; uint32_t stride;                       // [rows][stride] each
+};
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 // the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
 // mask (1 = raw) and f.bwt zeros
@@ -365,6 +410,13 @@ hipError_t ct_enc_sparse_kind(hipStream_t st, const CtEncFrame &f, const CtEncHu
                               uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_sparse_place(hipStream_t st, const CtEncFrame &f, const CtEncSparse &sp, uint32_t nb, uint32_t blk_len, uint32_t *out,
                                unsigned long long cap_words);
+// the runs mode's steps (zrun.hip), in order: the MTF rows and the A / B spaces as segments; behind the split, which B is empty;
+// ct_enc_kind0's sibling (nz, record sizes, raw rule, skip masks); and behind the payload offsets nz and the pairs into the
+// records and r.unit_off = where each stream starts
+hipError_t ct_enc_runs_segs(hipStream_t st, const CtEncRuns &r, const uint8_t *mtf, size_t mtf_stride, uint32_t nb, uint32_t blk_len);
+hipError_t ct_enc_runs_empty(hipStream_t st, const CtEncRuns &r, uint32_t nb);
+hipError_t ct_enc_runs_kind(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+hipError_t ct_enc_runs_place(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t *out, unsigned long long cap_words);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
@@ -389,7 +441,21 @@ struct CtDecHuff0 {                                        // device scratch of 
     unsigned long long *k_off, *k_len, *u_off;             // [nb]
     uint32_t *skip3;                                       // [nb]
     uint8_t *kept; uint32_t kept_stride;                   // [chunk][kept_stride]
+    // version 6 (max_kind 4): the fields above serve A of the kind-4 blocks (k_off / k_len / u_off / skip3 / kept: A's place,
+    // length, stream start, 1 = not kind 4); these are B's, the tables of B (built from the counts in the record before the
+    // verdict: hist_b, skip_tb) and the decoder's MTF rows the join writes (block b in row b % chunk)
+    unsigned long long *b_off, *b_len, *ub_off, *nun_b;    // [nb]
+    uint32_t *skip_b, *skip_tb;                            // [nb] 1 = no B to decode; 1 = no table of B to build
+    uint32_t *hist_b;                                      // [nb][256]
+    uint16_t *lut_b;                                       // [nb][2048]
+    uint8_t *kept_b;                                       // [chunk][kept_stride]
+    unsigned long long *m_off, *m_len;                     // [nb]
+    uint8_t *mtf; size_t mtf_stride;
 };
+// the counts of B of every kind-4 block from its record's pairs (zeros where the record does not hold well-formed pairs), and
+// whose table is built from them
+hipError_t ct_dec_runs_hist(hipStream_t st, const uint8_t *frame, uint32_t nb, uint32_t blk_len, unsigned long long payload_words,
+                            const CtDecHuff0 &h0);
 // h0 (version 3 and later, else null): kind 2 is legal, and kind 3 where h0->max_kind says so; its blocks' tables are built from the unverified histograms first, and the
 // units they ask for are one of the block's field checks
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,

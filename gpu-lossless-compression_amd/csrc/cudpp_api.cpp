@@ -124,10 +124,10 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     hipEvent_t *const side_events[10] = {&ev_in, &ev_sorted[0], &ev_sorted[1], &enc_half.ev[0], &enc_half.ev[1],
                                          &ev_dec_a[0], &ev_dec_a[1], &dec_half.ev[0], &dec_half.ev[1], &ev_s2};
     bool side_busy = false;                      // side-stream work issued since the last join
-    // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse) and the filter's frame staging both directions share
+    // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse / Runs) and the filter's frame staging both directions share
     CtSettings ct;
     GrowBuf ct_stage[2];
-    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
+    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse mode's and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
     SaScratch *sorter() override { return &sa; }
     void wire_prof() override { sa.prof = &prof; mtf.prof = &prof; huff.prof = &prof; dec.prof = &prof; }
     hipEvent_t side_span_start() override { return pipelined ? ev_s2 : nullptr; }
@@ -852,6 +852,37 @@ void plan_stage_mark(CUDPPHandle planHandle, int i)
     tm.mark(i);
     if (i == 1 && p->pipelined && p->ev_s2) (void)hipEventRecord(p->ev_s2, p->stream);   // (glcPlanSynchronize reads the second span from it)
     if (i == 3) tm.done();
+}
+
+hipError_t plan_bwt_mtf(CUDPPHandle planHandle, const uint8_t *in, uint32_t n, uint32_t nb, int *bwt_index, const uint8_t **mtf, size_t *stride)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    p->join_side();                                            // (an earlier pipelined call may still read d_bwt / d_mtf there)
+    p->sa.parity = p->enc_half.next();
+    hipError_t e = sa_build(SortCall{p->stream, in, n, n, nb, p->d_bwt, p->n, bwt_index}, p->sa);
+    if (e == hipSuccess) e = mtf_forward(p->stream, p->d_bwt, p->n, n, nb, p->d_mtf, p->n, p->mtf, nullptr);
+    *mtf = p->d_mtf; *stride = p->n;
+    return e;
+}
+
+hipError_t plan_decode_rows(CUDPPHandle planHandle, uint8_t **mtf, size_t *stride)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (!p->dec.lf) {
+        const hipError_t e = decode_scratch_alloc(p->dec, p->n, p->rows);
+        if (e != hipSuccess) return e;
+    }
+    *mtf = p->dec.mtf; *stride = p->dec.nmax;
+    return hipSuccess;
+}
+
+hipError_t plan_decode_from_mtf(CUDPPHandle planHandle, uint32_t first_row, const int *bwt_index, uint8_t *out, uint32_t n, uint32_t nblk)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    if (!p->dec.lf || first_row + nblk > p->dec.rows) return hipErrorInvalidValue;
+    p->join_side();                                            // (stage B of an earlier pipelined call uses the same scratch)
+    return decode_mtf_blocks(p->stream, DecodeCall{bwt_index, nullptr, nullptr, 0, nullptr, 0, out, n, nblk},
+                             p->dec.mtf + (size_t)first_row * p->dec.nmax, p->dec, p->d_status);
 }
 
 void plan_wait_released(CUDPPHandle planHandle)

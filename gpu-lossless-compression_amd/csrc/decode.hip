@@ -978,12 +978,30 @@ void decode_scratch_free(DecodeScratch &s)
 // Stage B: inverse BWT of `bwt` -> d_out.  The two stages use disjoint scratch apart from `bwt`, so
 // stage A of the next batch can run on another stream while stage B of this one walks its LF cycles
 // (glcPlanSetPipelining): A is LDS/VALU work, B is a memory-latency-bound pointer chase.
+// the second half of stage A: nblk rows of MTF bytes (stride s.nmax) -> BWT bytes in `bwt`
+static hipError_t imtf_rows(hipStream_t st, uint32_t n, uint32_t nblk, DecodeScratch &s, const uint8_t *mtf, uint8_t *bwt)
+{
+    const uint32_t nchunks = (n + IMTF_CHUNK - 1) / IMTF_CHUNK;
+    const double units = (double)n * nblk;
+    {
+        ProfScope ps(s.prof, PROF_IMTF_POS, st, units);
+        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, mtf, (size_t)s.nmax, n, s.ilists,
+                           s.max_chunks, bwt, (size_t)s.nmax);
+    }
+    {
+        ProfScope ps(s.prof, PROF_IMTF_REST, st, units);
+        hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);
+        hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, n, s.ilists,
+                           s.max_chunks);
+    }
+    return hipGetLastError();
+}
+
 hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status)
 {
     if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
     const uint32_t n = (uint32_t)c.n, nblk = (uint32_t)c.nblk;
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    const uint32_t nchunks = (n + IMTF_CHUNK - 1) / IMTF_CHUNK;
     const double units = (double)n * nblk;
     {
         ProfScope ps(s.prof, PROF_DEC_HUFF, st, units);
@@ -995,18 +1013,14 @@ hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s,
             hipLaunchKernelGGL(k_dec_huff, dim3((nsub + DH_WAVES - 1) / DH_WAVES, nblk), dim3(DH_WAVES * 64), 0, st, c.comp, c.comp_stride,
                                c.enc_off, c.off_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, c.block_off);
     }
-    {
-        ProfScope ps(s.prof, PROF_IMTF_POS, st, units);
-        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, s.mtf, (size_t)s.nmax, n, s.ilists,
-                           s.max_chunks, bwt, (size_t)s.nmax);
-    }
-    {
-        ProfScope ps(s.prof, PROF_IMTF_REST, st, units);
-        hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);
-        hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, n, s.ilists,
-                           s.max_chunks);
-    }
-    return hipGetLastError();
+    return imtf_rows(st, n, nblk, s, s.mtf, bwt);
+}
+
+hipError_t decode_mtf_blocks(hipStream_t st, const DecodeCall &c, const uint8_t *mtf, DecodeScratch &s, uint32_t *d_status)
+{
+    if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
+    GLC_TRY(imtf_rows(st, (uint32_t)c.n, (uint32_t)c.nblk, s, mtf, s.bwt));
+    return decode_stage_b(st, c, s.bwt, s, d_status);
 }
 
 hipError_t decode_stage_b(hipStream_t st, const DecodeCall &c, const uint8_t *bwt, DecodeScratch &s, uint32_t *d_status)

@@ -525,5 +525,8 @@ void       decode_scratch_free(DecodeScratch &s);
 hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status);
 hipError_t decode_stage_b(hipStream_t st, const DecodeCall &c, const uint8_t *bwt, DecodeScratch &s, uint32_t *d_status);
 hipError_t decode_blocks(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint32_t *d_status);
+// stage A without its Huffman step, then stage B: c.nblk rows of MTF bytes at `mtf` (stride s.nmax; the container's zero-run
+// records are joined into s.mtf) -> c.out.  Of c only bwt_index, out, n and nblk are read.
+hipError_t decode_mtf_blocks(hipStream_t st, const DecodeCall &c, const uint8_t *mtf, DecodeScratch &s, uint32_t *d_status);
 
 } // namespace glc

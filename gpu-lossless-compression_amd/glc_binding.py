@@ -656,6 +656,7 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerShuffle", "glcPlanGetContainerShuffle", "glcPlanSetContainerCodec", "glcPlanGetContainerCodec",
                      "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta",
                      "glcSparseSplitSegments", "glcSparseJoinSegments", "glcPlanSetContainerSparse", "glcPlanGetContainerSparse",
+                     "glcZeroRunSplitSegments", "glcZeroRunJoinSegments", "glcPlanSetContainerRuns", "glcPlanGetContainerRuns",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -694,6 +695,10 @@ def _ct():
         L.glcPlanGetContainerSparse.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcSparseSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         L.glcSparseJoinSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.glcPlanSetContainerRuns.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerRuns.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcZeroRunSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
+        L.glcZeroRunJoinSegments.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]
         for nm in ("glcContainerIndexDevice", "glcContainerIndex"):
             getattr(L, nm).argtypes = [sz, vp, ull, C.POINTER(vp)]
         L.glcContainerIndexFile.argtypes = [sz, C.c_char_p, C.POINTER(vp)]
@@ -832,6 +837,56 @@ def container_get_sparse(plan):
     d = C.c_uint(0)
     _chk("glcPlanGetContainerSparse", _ct().glcPlanGetContainerSparse(plan.handle, C.byref(d)))
     return int(d.value)
+
+
+def container_set_runs(plan, on):
+    """the runs mode of the plan's container ENCODER (format version 6): True / 1 needs the BWT codec;
+    container_set_codec(plan, CONTAINER_CODEC_HUFF0) also switches it off.  It is also the version the plan reads: on, versions 1
+    to 4 and 6; off, a version-6 stream is a stream-header failure as it always was."""
+    _chk("glcPlanSetContainerRuns", _ct().glcPlanSetContainerRuns(plan.handle, int(on)))
+
+
+def container_get_runs(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerRuns", _ct().glcPlanGetContainerRuns(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def _zerorun_args(d_base, offsets, lengths):
+    import torch
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(d_base.device)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(d_base.device)
+    assert off.numel() == ln.numel()
+    return off, ln
+
+
+def zerorun_split_segments(d_in, d_a, d_b, offsets, lengths, max_len=None, stream=None):
+    """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in split into A (non-zero bytes and one zero per run
+    of zeros, a run ending at a 256-byte tile edge) at d_a + offsets[i] and B (run lengths minus one) at d_b + offsets[i].
+    Returns (A lengths, B lengths), int64 tensors [count]"""
+    import torch
+    off, ln = _zerorun_args(d_in, offsets, lengths)
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    alen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
+    blen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
+    _chk("glcZeroRunSplitSegments", _ct().glcZeroRunSplitSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
+                                                                   d_a.data_ptr(), d_b.data_ptr(), alen.data_ptr(), blen.data_ptr(), stream))
+    torch.cuda.synchronize(d_in.device)                        # (off / ln are temporaries of this call)
+    return alen[:off.numel()], blen[:off.numel()]
+
+
+def zerorun_join_segments(d_a, d_b, d_out, offsets, a_lengths, b_lengths, lengths, max_len=None, stream=None):
+    """the inverse of zerorun_split_segments; tolerant of streams that do not fit each other (see include/glc_container.h)"""
+    import torch
+    off, ln = _zerorun_args(d_out, offsets, lengths)
+    al = torch.as_tensor(a_lengths, dtype=torch.int64).to(d_out.device)
+    bl = torch.as_tensor(b_lengths, dtype=torch.int64).to(d_out.device)
+    assert al.numel() == bl.numel() == off.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    _chk("glcZeroRunJoinSegments", _ct().glcZeroRunJoinSegments(d_a.data_ptr(), d_b.data_ptr(), off.data_ptr(), al.data_ptr(), bl.data_ptr(),
+                                                                 ln.data_ptr(), off.numel(), max_len, d_out.data_ptr(), stream))
+    torch.cuda.synchronize(d_out.device)
+    return d_out
 
 
 def sparse_mask_words(max_len):

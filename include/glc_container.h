@@ -37,6 +37,20 @@
  * timestamps in 1 MiB blocks with delta + shuffle 8 (profiles/sparse_mode.md): ratio 6.771 against 4.192 with the mode off, encode
  * 460 against 417 GB/s, decode 174 against 134 GB/s; uint32 counters 9.999 against 5.280, 468 against 424 and 199 against 146.
  *
+ * Text and logs, further: the runs mode of the BWT codec, off by default.  The move-to-front output of text is mostly zeros, a
+ * Huffman code spends at least a bit on each, and the reference's stream has a new table every 4096 symbols, so the BWT codec
+ * stopped at 8 : 1 on anything.  With glcPlanSetContainerRuns on, a block's move-to-front bytes are split into A (the non-zero
+ * bytes and one zero per run of zeros) and B (the run lengths; a run ends at a 256-byte tile edge), and each is coded with one
+ * order-0 table of its own (record kind 4).  The stream is format version 6.  The model's sizes are in INTEGRATION.md 4b
+ * ("runs: when"): 1 MiB blocks of text 4.687 against 3.715, of logs 6.622 against 4.187, a repeated page 287.1 against 7.816.
+ * A plan reads version 6 only with the mode on, and version 5 only with the sparse mode on, which needs the other codec: no
+ * single plan reads both.  Measured on one MI355X on 1 GiB of device-generated data in 1 MiB blocks, rows 512
+ * (profiles/runs_mode.md; ratio / encode / decode GB/s, medians of 5 interleaved rounds): text-like, mode off 3.715 / 24.7 /
+ * 41.2, on 4.872 / 23.1 / 29.4; log-like, off 3.916 / 17.3 / 41.9, on 5.867 / 16.6 / 29.9. With the mode off the rates equal
+ * the parent commit's within the spread of the rounds. Decode is slower with the mode on: the batched order-0 decoder's
+ * k_hdb_span_functions takes 5 ms per GiB where the kind-0 record's sub-block offsets let k_dec_huff take 1.7. The split alone
+ * moves 316 GB/s and the join 638-820, a device-to-device copy 2542.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -130,6 +144,24 @@ CUDPPResult glcSparseSplitSegments(const void *d_inBase, const unsigned long lon
 CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                                   size_t count, size_t maxLen, const unsigned int *d_fill, const unsigned int *d_mask, void *d_outBase,
                                   void *stream);
+
+/* The two passes of the runs mode as batched calls (csrc/zrun.hip; the split is defined in INTEGRATION.md 4b).  Segment i is
+ * x = [d_offsets[i], + n) of its base, n = min(d_lengths[i], maxLen), cut into tiles of 256 bytes.  Position p is a run start
+ * when x[p] = 0 and (p % 256 = 0 or x[p - 1] != 0).  A is x at the positions that are non-zero or run starts, in order; B has one
+ * byte per run start: the zeros from there up to the next non-zero byte, tile edge or n, minus one.  Split writes A and B of
+ * segment i at d_offsets[i] of their bases (at most n bytes each) and their byte counts to d_aLen[i] and d_bLen[i].  Join walks A:
+ * a non-zero byte is copied, the z-th zero becomes B[z] + 1 zeros; it writes n bytes at d_outBase + d_offsets[i].  It is
+ * tolerant: it does not ask for the tile rule, a zero of A beyond d_bLen[i] is a run of one, output beyond n is dropped and the
+ * rest of a short output is zeros, so it never reads outside A or B and never writes outside the segment.  Any length up to
+ * GLC_ZERORUN_MAX_LEN, any byte alignment, out of place; the calls only enqueue on `stream`.  A bad argument (a null pointer with
+ * count > 0, two equal bases, a maxLen or count too large) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_ZERORUN_MAX_LEN ((size_t)1 << 20)
+CUDPPResult glcZeroRunSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                    size_t count, size_t maxLen, void *d_aBase, void *d_bBase, unsigned long long *d_aLen,
+                                    unsigned long long *d_bLen, void *stream);
+CUDPPResult glcZeroRunJoinSegments(const void *d_aBase, const void *d_bBase, const unsigned long long *d_offsets,
+                                   const unsigned long long *d_aLen, const unsigned long long *d_bLen, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, void *d_outBase, void *stream);
 
 /* The element size the container ENCODER of this plan shuffles by: 0 or 1 = off (the default), 2, 4, 8; anything else is
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it; the decoder
@@ -235,6 +267,19 @@ CUDPPResult glcUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long
                                     unsigned long long count, void *stream);
 CUDPPResult glcUndeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
                                            unsigned long long first, unsigned long long count, void *stream);
+
+/* The runs mode of the ENCODER's BWT codec: on = 1 writes format version 6, where every block is a zero-run record (kind 4: the
+ * BWT index, the byte counts of A, the non-zero counts of B, the order-0 streams of A and B) or, when 4 * words >= block bytes,
+ * raw; 0 (the default) writes versions 1 to 5 byte for byte as ever.  on = 1 while the plan's codec is not
+ * GLC_CONTAINER_CODEC_BWT, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; setting
+ * the codec to GLC_CONTAINER_CODEC_HUFF0 also switches it off.  All six container entry points and the range reads honour it,
+ * with pipelining on or off (a runs frame is queued on the plan's stream alone) and with any filter setting.  The setting is also
+ * the version the plan speaks: a plan with it on reads versions 1 to 4 and 6, every other plan refuses version 6 as a
+ * stream-header failure, as it was before version 6 existed.  Version 5 needs the sparse mode and with it the other codec, so no
+ * single plan reads both 5 and 6.  The first runs encode allocates 2 * rows * n bytes for A and B, the first version-6 decode as
+ * much for the blocks of one decoder chunk plus the BWT decoder's scratch; both are kept with the plan and freed with it. */
+CUDPPResult glcPlanSetContainerRuns(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

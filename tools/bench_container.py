@@ -23,8 +23,15 @@ order-0 codec, and R interleaved rounds of encode and decode timed with device e
 mode off and then on (glcPlanSetContainerSparse, format version 5), without it only off, which is also what a build without the
 mode can run.  Every round's rates are reported, with their median and spread (max - min) per setting.
 
+--runs (with --data textlike or loglike, generated on the device; --rounds R, at least 1) is the runs section: the BWT codec with its
+runs mode off and then on (glcPlanSetContainerRuns, format version 6), R interleaved rounds of encode and decode timed with device
+events, their medians and spreads, the ratio of both settings, the plan's per-kernel profile of one encode and one decode per
+setting, and the split and the join alone (glcZeroRunSplitSegments / glcZeroRunJoinSegments over the input's blocks) against a
+device-to-device copy.  --runs-off-only runs the same section without ever touching the mode, which is also what a build without
+it can run.
+
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]
-                                [--rounds R] [--sparse]"""
+                                [--rounds R] [--sparse] [--runs | --runs-off-only]"""
 import argparse
 import json
 import os
@@ -34,7 +41,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2}
+DATA_ELEM = {"textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2}
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -65,6 +72,137 @@ def typed_on_device(torch, L, dev, kind, total):
     u = torch.rand(total // 2, dtype=torch.float32, device=dev, generator=g).sub_(0.5)
     lap = u.sign() * torch.log1p(-2.0 * u.abs()).mul_(-6.0)
     return (512.0 + lap).round_().clamp_(0, 65535).to(torch.int32).to(torch.int16).view(torch.uint8)
+
+
+def text_on_device(torch, dev, kind, total):
+    """`total` bytes of text-like (words of a 4096-word vocabulary, Zipf-weighted, a third of them determined by the word in
+    front) or log-like data (fixed-width lines: a rising timestamp, one of five levels, one of 64 sources and messages, three
+    numeric fields), generated on the device (seeded)"""
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED0020)
+    if kind == "loglike":
+        W = 96
+        lines = (total + W - 1) // W
+        tmpl = torch.full((64, W), 32, dtype=torch.uint8, device=dev)
+        letters = torch.randint(97, 123, (64, W), dtype=torch.uint8, device=dev, generator=g)
+        tmpl[:, 30:44] = letters[:, 30:44]                         # source
+        tmpl[:, 45:80] = letters[:, 45:80]                         # message
+        tmpl[:, 52] = 32; tmpl[:, 60] = 32; tmpl[:, 67] = 61
+        out = tmpl[torch.randint(0, 64, (lines,), device=dev, generator=g)]
+        levels = torch.tensor([list(b"INFO "), list(b"WARN "), list(b"DEBUG"), list(b"ERROR"), list(b"TRACE")], dtype=torch.uint8, device=dev)
+        out[:, 24:29] = levels[torch.multinomial(torch.tensor([0.7, 0.1, 0.15, 0.03, 0.02], device=dev), lines, replacement=True, generator=g)]
+        t = torch.randint(1, 40, (lines,), dtype=torch.int64, device=dev, generator=g).cumsum_(0).add_(1_700_000_000_000)
+        for col in range(13):                                      # the timestamp, 13 decimal digits
+            out[:, 12 - col] = (t % 10 + 48).to(torch.uint8)
+            t //= 10
+        for lo, width, top in ((14, 8, 10 ** 8), (80, 5, 3000), (88, 6, 10 ** 6)):
+            v = torch.randint(0, top, (lines,), dtype=torch.int64, device=dev, generator=g)
+            for col in range(width):
+                out[:, lo + width - 1 - col] = (v % 10 + 48).to(torch.uint8)
+                v //= 10
+        out[:, W - 1] = 10
+        return out.reshape(-1)[:total].contiguous()
+    V, WMAX = 4096, 12
+    wl = torch.randint(2, WMAX - 1, (V,), device=dev, generator=g)
+    lw = torch.tensor([8.2, 1.5, 2.8, 4.3, 12.7, 2.2, 2.0, 6.1, 7.0, 0.2, 0.8, 4.0, 2.4, 6.7, 7.5, 1.9, 0.1, 6.0, 6.3, 9.1, 2.8, 1.0, 2.4, 0.2, 2.0, 0.1],
+                      device=dev)
+    vocab = (torch.multinomial(lw, V * WMAX, replacement=True, generator=g) + 97).to(torch.uint8).reshape(V, WMAX)
+    col = torch.arange(WMAX, device=dev)
+    vocab[col[None, :] == wl[:, None]] = 32                        # the space behind the word
+    pw = 1.0 / torch.arange(1, V + 1, dtype=torch.float32, device=dev)
+    parts, have = [], 0
+    while have < total:                                            # 8 Mi words a piece
+        w = torch.multinomial(pw, 1 << 23, replacement=True, generator=g)
+        dep = torch.rand(w.numel(), device=dev, generator=g) < 0.35
+        w[1:] = torch.where(dep[1:], (31 * w[:-1] + 7) % V, w[1:])
+        keep = col[None, :] <= wl[w][:, None]
+        parts.append(vocab[w][keep])
+        have += parts[-1].numel()
+    return torch.cat(parts)[:total].contiguous()
+
+
+def runs_section(torch, glc, plan, d_in, total, rounds, with_runs):
+    """the BWT container with the runs mode off and (with_runs) on, interleaved as sparse_section does it; then one profiled
+    encode and decode per setting, and the two passes alone against a copy"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["off", "runs"] if with_runs else ["off"]
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def enc():
+        glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+            plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr()))
+
+    def dec(clen):
+        glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr()))
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            if with_runs:
+                glc.container_set_runs(plan, 1 if s == "runs" else 0)
+            t_enc = event_timed(enc)
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: dec(clen))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+        if with_runs:
+            glc.container_set_runs(plan, 1 if s == "runs" else 0)
+        plan.enable_timing(3)
+        enc()
+        plan.synchronize()
+        prof_enc = plan.kernel_profiles()
+        clen = int(d_len.item())
+        plan.enable_timing(3)
+        dec(clen)
+        plan.synchronize()
+        prof_dec = plan.kernel_profiles()
+        plan.enable_timing(0)
+        res[s]["encode_kernels_ms"] = {k: round(v["ms"], 3) for k, v in sorted(prof_enc.items(), key=lambda kv: -kv[1]["ms"])[:8]}
+        res[s]["decode_kernels_ms"] = {k: round(v["ms"], 3) for k, v in sorted(prof_dec.items(), key=lambda kv: -kv[1]["ms"])[:8]}
+    if with_runs:
+        # the passes alone, on MTF-like bytes of the same zero density as a text block's: the input's bytes below 0x70 made zero
+        nseg = min(total // n, 512)
+        x = d_in[:nseg * n].clone()
+        x[x < 0x70] = 0
+        a, b = torch.empty_like(x), torch.empty_like(x)
+        offs, lens = [i * n for i in range(nseg)], [n] * nseg
+        off = torch.tensor(offs, dtype=torch.int64, device=x.device)
+        ln = torch.tensor(lens, dtype=torch.int64, device=x.device)
+        al, bl = torch.zeros_like(off), torch.zeros_like(off)
+        L = glc._ct()
+        split = lambda: glc._chk("glcZeroRunSplitSegments", L.glcZeroRunSplitSegments(x.data_ptr(), off.data_ptr(), ln.data_ptr(), nseg, n,
+                                                                                       a.data_ptr(), b.data_ptr(), al.data_ptr(), bl.data_ptr(), None))
+        y = torch.empty_like(x)
+        join = lambda: glc._chk("glcZeroRunJoinSegments", L.glcZeroRunJoinSegments(a.data_ptr(), b.data_ptr(), off.data_ptr(), al.data_ptr(),
+                                                                                    bl.data_ptr(), ln.data_ptr(), nseg, n, y.data_ptr(), None))
+        split(); join()
+        assert torch.equal(x, y)
+        best = lambda fn: min(event_timed(fn) for _ in range(5))
+        res["passes"] = {"bytes": x.numel(), "zero_fraction": float((x == 0).float().mean().item()),
+                         "split_GBps": round(x.numel() / best(split) / 1e9, 1), "join_GBps": round(x.numel() / best(join) / 1e9, 1),
+                         "copy_GBps": round(x.numel() / best(lambda: y.copy_(x)) / 1e9, 1)}
+    return res
 
 
 def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
@@ -170,6 +308,8 @@ def main():
     ap.add_argument("--codec", type=int, default=0, choices=[0, 1], help="the filter section's container codec: 0 BWT, 1 order-0")
     ap.add_argument("--rounds", type=int, default=0, help="typed data: the sparse section, this many interleaved rounds timed with device events")
     ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
+    ap.add_argument("--runs", action="store_true", help="text-like data: the runs section, the BWT codec's runs mode off and on (format version 6)")
+    ap.add_argument("--runs-off-only", action="store_true", help="the runs section without the mode (what a build without it can run)")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -189,6 +329,9 @@ def main():
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
         thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
         assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+    elif args.data in ("textlike", "loglike"):
+        assert args.runs or args.runs_off_only, "text-like data is the runs section's"
+        d_in = text_on_device(torch, dev, args.data, total)
     else:
         d_in = typed_on_device(torch, L, dev, args.data, total)
     torch.cuda.synchronize()
@@ -206,6 +349,12 @@ def main():
 
     res = {"workload": "%s: %d x 1 MiB blocks, plan rows %d, pipelining %s"
                        % ("configs[1] Philox Zipf(1.0)" if args.data == "zipf" else args.data, nblocks, args.rows, bool(args.pipelining))}
+    if args.runs or args.runs_off_only:
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
     if args.data != "zipf":
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
