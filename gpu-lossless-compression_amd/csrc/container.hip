@@ -407,8 +407,8 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     if (b < nb) {
         if (skip0) {                                           // (version 3 and later: whose tables are built next)
             const uint32_t kind = W[T.kind + b];
-            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind >= CT_KIND_SPARSE) ||
-                       (kind == CT_KIND_RUNS && max_kind >= CT_KIND_RUNS) ? 0u : 1u;
+            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind == CT_KIND_SPARSE) ||
+                       (kind == CT_KIND_RUNS && max_kind == CT_KIND_RUNS) ? 0u : 1u;   // (a kind-5 block has no Huffman table)
         }
         const unsigned long long lo = po[b], hi = po[b + 1];
         const bool ok = lo <= hi && hi <= P;
@@ -437,13 +437,33 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
     reinterpret_cast<uint32_t *>(f.verdict + 2)[b] = kind;
     const unsigned long long lo = po[b], hi = po[b + 1];
     bool bad = kind > (nun0 ? h0.max_kind : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
-    const bool runs = nun0 && h0.max_kind >= CT_KIND_RUNS;       // (version 6: kind 3 is not legal)
-    bad = bad || (runs && kind == CT_KIND_SPARSE);
+    const bool runs = nun0 && h0.max_kind == CT_KIND_RUNS;       // (version 6: kind 3 is not legal)
+    const bool ans = nun0 && h0.max_kind == CT_KIND_ANS;         // (version 7: neither are kinds 3 and 4)
+    bad = bad || (runs && kind == CT_KIND_SPARSE) || (ans && (kind == CT_KIND_SPARSE || kind == CT_KIND_RUNS));
     unsigned long long klen = 0, nB = 0, nzw = 0;
     if (!bad) {
         const unsigned long long w = hi - lo;
         if (kind == CT_KIND_RAW) bad = w != ct_raw_words(blk_len);
-        else if (kind == CT_KIND_RUNS) {
+        else if (kind == CT_KIND_ANS) {
+            // an rANS record, the checks in the order of INTEGRATION.md 4b: the counts are the block's, nothing else is set, the
+            // record holds its chunk counts (read only once it is known to), no chunk has more units than symbols, and the
+            // record is exactly the counts, every chunk's 64 states and its units -- so the decoder's offsets stay inside it
+            const uint32_t *h = W + T.hist + 256ull * b;
+            const uint32_t nch = ans_chunks(blk_len);
+            unsigned long long sum = 0, need = nch;
+            for (uint32_t s = 0; s < 256; s++) sum += h[s];
+            bad = sum != blk_len || W[T.bwt + b] != 0;
+            const uint32_t *eo = W + T.enc_off + (size_t)b * T.nsub;
+            for (uint32_t s = 0; s < T.nsub && !bad; s++) bad = eo[s] != 0;
+            bad = bad || w < nch;
+            const uint32_t *rec = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR + 4 * T.words) + lo;
+            for (uint32_t c = 0; c < nch && !bad; c++) {
+                const uint32_t u = rec[c];
+                bad = u > min(ANS_CHUNK, blk_len - c * ANS_CHUNK);
+                need += ANS_LANES + (u + 1ull) / 2;
+            }
+            bad = bad || need != w;
+        } else if (kind == CT_KIND_RUNS) {
             // a zero-run record, the checks in the order of INTEGRATION.md 4b: the BWT index inside the block, nothing else set,
             // counts of a non-empty A; nz and the pairs read only once the record is known to hold them; the pairs ascending
             // with counts of their own that sum to A's zeros and, with A's other bytes, expand to exactly blk_len; and behind
@@ -515,7 +535,7 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
         h0.skip_b[b] = k4 && nB ? 0u : 1u;
         h0.m_off[b] = (unsigned long long)(uintptr_t)(h0.mtf + slot * h0.mtf_stride);
         h0.m_len[b] = blk_len;
-    } else if (nun0 && h0.max_kind >= CT_KIND_SPARSE) {
+    } else if (nun0 && h0.max_kind == CT_KIND_SPARSE) {
         const bool k3 = !bad && kind == CT_KIND_SPARSE;
         h0.k_off[b] = (unsigned long long)(uintptr_t)(h0.kept + (size_t)(b % h0.chunk) * h0.kept_stride);
         h0.k_len[b] = k3 ? klen : 0;
@@ -573,7 +593,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
         const HdbSegs g{nullptr, nullptr, nullptr, nb, blk_len};
         e = hdb_tables(st, g, false, hist, nullptr, nullptr, h0->lut, h0->nun, h0->skip, prof);
         if (e != hipSuccess) return e;
-        if (h0->max_kind >= CT_KIND_RUNS) {                    // (version 6: the tables of B, from the counts in the records)
+        if (h0->max_kind == CT_KIND_RUNS) {                    // (version 6: the tables of B, from the counts in the records)
             e = ct_dec_runs_hist(st, frame, nb, blk_len, payload_words, *h0);
             if (e != hipSuccess) return e;
             e = hdb_tables(st, g, false, h0->hist_b, nullptr, nullptr, h0->lut_b, h0->nun_b, h0->skip_tb, prof);

@@ -3,12 +3,13 @@
 // things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal(), 4 the BWT codec's
-// zero-run form (zrun.hip) where kind4_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
+// zero-run form (zrun.hip) where kind4_legal(), 5 the order-0 codec's rANS form (ans.hip) where kind5_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
 // writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's (both read ct_legal()).
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
-// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3).  With the BWT codec's
+// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3; with the rANS mode on: frame_ans, kind 5, the histograms alone and the
+// kernels of ans.hip).  With the BWT codec's
 // runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
@@ -18,7 +19,7 @@
 // verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
 // place, runs of kind 2 to the batched order-0 decoder, runs of kind 3 to it as well (the kept bytes into scratch, then expanded
 // under the record's mask), runs of kind 4 to it too (A and B into scratch, joined into the BWT decoder's MTF rows, then its
-// inverse MTF and inverse BWT), and the decoded bytes are checked against the blocks' CRCs; a filtered
+// inverse MTF and inverse BWT), runs of kind 5 to the rANS decoder (tables from the verified histograms, then one pass), and the decoded bytes are checked against the blocks' CRCs; a filtered
 // frame is decoded into staging, checked there and inverted into the output by filter_device().
 #include "../../include/glc_container.h"
 #include "container_internal.h"
@@ -118,7 +119,7 @@ CtFormat format_of(const CtSettings &s)
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         f.version = ct_legal(i).version;
         if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal()) &&
-            (!s.runs || f.kind4_legal())) break;
+            (!s.runs || f.kind4_legal()) && (!s.ans || f.kind5_legal())) break;
     }
     return f;                                                 // (the setters accept only what some row takes)
 }
@@ -168,6 +169,8 @@ struct Encoder {
     CtEncSparse sp = {};                                      // its scratch, behind h0's; a plan that never has it on has none
     bool runs = false;                                        // the BWT codec's runs mode
     CtEncRuns zr = {};                                        // its scratch, kept with the plan; a plan that never has it on has none
+    bool ans = false;                                         // the order-0 codec's rANS mode
+    CtEncAns an = {};                                         // its scratch, behind h0's; a plan that never has it on has none
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -203,6 +206,18 @@ struct Encoder {
         h0.lens = c.take<uint8_t>(256 * R);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_encode_work_bytes(R));
+        if (ans) {
+            // everything of a frame runs on the plan's stream in order, so one set of chunk slots serves pipelined calls as well
+            const size_t slots = R * ans_chunks(P.n);
+            an.sc.nch_max = ans_chunks(P.n);
+            an.blk_off = c.take<unsigned long long>(R);
+            an.blk_len = c.take<unsigned long long>(R);
+            an.sc.states = c.take<uint32_t>(slots * ANS_LANES);
+            an.sc.counts = c.take<uint32_t>(slots);
+            c.align(256);
+            an.tab = c.take<uint8_t>(R * ANS_TAB_BYTES);
+            an.sc.units = c.take<uint16_t>(slots * ANS_CHUNK);
+        }
         if (!sparse) return;
         // everything of a frame runs on the plan's stream in order, so one compaction space serves pipelined calls as well
         sp.mask_stride = sp_mask_words(P.n);
@@ -250,6 +265,7 @@ struct Encoder {
         codec = s.codec;
         sparse = s.sparse && codec == CT_CODEC_HUFF0;
         runs = s.runs && codec == CT_CODEC_BWT;
+        ans = s.ans && codec == CT_CODEC_HUFF0 && !sparse;
         if (runs) {
             Carver measure;
             carve_runs(measure);
@@ -301,6 +317,7 @@ struct Encoder {
         }
         if (sparse) return frame_sparse(f, d_in, orig, nb, blk_len, out, cap);
         if (runs) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
+        if (ans) return frame_ans(f, d_in, orig, nb, blk_len, out, cap);
         if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
@@ -359,6 +376,33 @@ struct Encoder {
         CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
         CT_TRY(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, reinterpret_cast<uint32_t *>(out), cap / 4));
         CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), sp.unit_off, cap / 4, f.only, h0.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
+    }
+
+    // frame_huff0 with the rANS mode on: histograms (the Huffman tables that come with them are not used) -> the blocks' rANS
+    // tables -> every chunk coded into its scratch slot -> record sizes and the raw rule -> payload offsets -> counts, states and
+    // units into the records
+    CUDPPResult frame_ans(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
+                          uint8_t *out, unsigned long long cap)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        plan_stage_mark(P.h, 0);
+        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));
+        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
+        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+        CT_TRY(ct_block_offsets(P.st, an.blk_off, an.blk_len, nb, blk_len));
+        const AnsSegs a{const_cast<uint8_t *>(d_in), an.blk_off, an.blk_len, f.hist, an.tab, nullptr, nb, blk_len};
+        CT_TRY(ans_tables(P.st, a));
+        CT_TRY(ans_encode(P.st, a, an.sc));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_ans_kind(P.st, f, an.sc, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
+        AnsSegs ap = a;
+        ap.skip = f.only;
+        CT_TRY(ans_place(P.st, ap, an.sc, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4));
         plan_stage_mark(P.h, 2);
         CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
         plan_stage_mark(P.h, 3);
@@ -437,6 +481,10 @@ struct Decoder {
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_decode_work_bytes(h0.chunk, blk_len));
         h0.max_kind = fmt.max_kind();
+        if (fmt.kind5_legal()) {
+            c.align(256);
+            h0.ans_tab = c.take<uint8_t>((size_t)h0.chunk * ANS_TAB_BYTES);
+        }
         if (!fmt.kind3_legal() && !fmt.kind4_legal()) return;
         h0.k_off = c.take<unsigned long long>(n4);
         h0.k_len = c.take<unsigned long long>(n4);
@@ -581,6 +629,15 @@ struct Decoder {
             const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
                            reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, 0, nullptr, b - a, blk_len};
             CT_TRY(sparse_join(P.st, s));
+            a = b;
+        }
+        for (uint32_t a = 0; fmt.kind5_legal() && a < nb;) {    // runs of rANS blocks: their tables from the histograms, then one pass
+            if (kind[a] != CT_KIND_ANS || !want(a)) { a++; continue; }
+            uint32_t b = a;
+            while (b < nb && kind[b] == CT_KIND_ANS && want(b) && b - a < h0.chunk) b++;
+            const AnsSegs g{nullptr, f.seg_off + a, f.seg_len + a, W + T.hist + 256ull * a, h0.ans_tab, nullptr, b - a, blk_len};
+            CT_TRY(ans_tables(P.st, g));
+            CT_TRY(ans_decode(P.st, g, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, nullptr));
             a = b;
         }
         // runs of zero-run blocks inside one chunk of the decoder: A and B decoded into scratch, joined into the rows b % chunk of
@@ -1073,7 +1130,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
     uint32_t hdr[8];
     if (io.small(hdr, 0, CT_HDR) != CUDPP_SUCCESS) return fail(plan, CT_TRUNCATED);
     if (memcmp(hdr, ix->hdr, CT_HDR) != 0) return fail(plan, CT_STREAM_HEADER);           // another container than the index's
-    if ((ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) || (ix->fmt.kind4_legal() && !plan_container_settings(plan).runs))
+    if ((ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) || (ix->fmt.kind4_legal() && !plan_container_settings(plan).runs) ||
+        (ix->fmt.kind5_legal() && !plan_container_settings(plan).ans))
         return fail(plan, CT_STREAM_HEADER);
     stats.v[2] = CT_HDR;
     D.fmt = ix->fmt;
@@ -1449,6 +1507,84 @@ CUDPPResult glcZeroRunJoinSegments(const void *d_aBase, const void *d_bBase, con
     return CUDPP_SUCCESS;
 }
 
+// the two rANS calls: a bad argument is refused before anything is enqueued.  The work space: the tables, what the batched
+// histogram kernel's table step writes beside them, and the encoder's chunk slots
+struct AnsWork {
+    uint8_t *tab, *lens; uint16_t *codes; unsigned long long *nun; AnsScratch sc;
+    size_t carve(void *base, size_t count, size_t maxLen)
+    {
+        Carver c(base);
+        const size_t nch = ans_chunks((uint32_t)maxLen), slots = count * nch;
+        c.align(256);
+        tab = c.take<uint8_t>(count * ANS_TAB_BYTES);
+        nun = c.take<unsigned long long>(count);
+        sc.states = c.take<uint32_t>(slots * ANS_LANES);
+        sc.counts = c.take<uint32_t>(slots);
+        codes = c.take<uint16_t>(256 * count);
+        lens = c.take<uint8_t>(256 * count);
+        c.align(256);
+        sc.units = c.take<uint16_t>(slots * ANS_CHUNK);
+        sc.nch_max = (uint32_t)nch;
+        return c.bytes();
+    }
+};
+
+size_t glcAnsBoundWords(size_t len) { return len > GLC_ANS_MAX_LEN ? 0 : (size_t)ans_bound_words((uint32_t)len); }
+
+size_t glcAnsSegmentsWorkBytes(size_t count, size_t maxLen)
+{
+    if (count > GLC_ANS_MAX_COUNT || maxLen > GLC_ANS_MAX_LEN) return 0;
+    AnsWork w;
+    return w.carve(nullptr, count, maxLen);
+}
+
+static bool ans_args_ok(const void *data, const void *off, const void *len, const void *hist, const void *rec, const void *recOff,
+                        const void *recWords, const void *work, size_t workBytes, size_t count, size_t maxLen)
+{
+    if (count > GLC_ANS_MAX_COUNT || maxLen > GLC_ANS_MAX_LEN) return false;
+    if (count == 0) return true;
+    return data && off && len && hist && rec && recOff && recWords && work && data != rec && (reinterpret_cast<uintptr_t>(rec) & 3) == 0 &&
+           (reinterpret_cast<uintptr_t>(hist) & 3) == 0 && workBytes >= glcAnsSegmentsWorkBytes(count, maxLen);
+}
+
+CUDPPResult glcAnsEncodeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_recBase,
+                                 const unsigned long long *d_recOffsets, unsigned long long *d_recWords, void *d_work, size_t workBytes,
+                                 void *stream)
+{
+    if (!ans_args_ok(d_inBase, d_offsets, d_lengths, d_hist, d_recBase, d_recOffsets, d_recWords, d_work, workBytes, count, maxLen))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AnsWork w;
+    (void)w.carve(d_work, count, maxLen);
+    const HdbSegs h{static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count, (uint32_t)maxLen};
+    CT_TRY(hdb_tables(st, h, true, d_hist, w.lens, w.codes, nullptr, w.nun, nullptr, nullptr));
+    const AnsSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, d_hist, w.tab, nullptr, (uint32_t)count,
+                    (uint32_t)maxLen};
+    CT_TRY(ans_tables(st, g));
+    CT_TRY(ans_encode(st, g, w.sc));
+    CT_TRY(ans_words(st, g, w.sc, d_recWords));
+    CT_TRY(ans_place(st, g, w.sc, d_recBase, d_recOffsets, ~0ull));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcAnsDecodeSegments(const unsigned int *d_recBase, const unsigned long long *d_recOffsets, const unsigned long long *d_recWords,
+                                 const unsigned int *d_hist, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, void *d_outBase, void *d_work, size_t workBytes, void *stream)
+{
+    if (!ans_args_ok(d_outBase, d_offsets, d_lengths, d_hist, d_recBase, d_recOffsets, d_recWords, d_work, workBytes, count, maxLen))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    AnsWork w;
+    (void)w.carve(d_work, count, maxLen);
+    const AnsSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, d_hist, w.tab, nullptr, (uint32_t)count, (uint32_t)maxLen};
+    CT_TRY(ans_tables(st, g));
+    CT_TRY(ans_decode(st, g, d_recBase, d_recOffsets, d_recWords));
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
 {
     return shuffle_device_api(d_in, d_out, len, elem, stream, false);
@@ -1497,7 +1633,7 @@ CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
     if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CtSettings &s = plan_container_settings(plan);
     s.codec = codec;
-    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = false;   // (no sparse mode without the order-0 codec)
+    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = s.ans = false;   // (no sparse or rANS mode without the order-0 codec)
     if (codec != GLC_CONTAINER_CODEC_BWT) s.runs = false;       // (no runs mode without the BWT codec)
     return CUDPP_SUCCESS;
 }
@@ -1507,8 +1643,27 @@ CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && s.codec != GLC_CONTAINER_CODEC_HUFF0)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.ans))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;   // (the two modes exclude each other)
     s.sparse = on != 0;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    CtSettings &s = plan_container_settings(plan);
+    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    s.ans = on != 0;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).ans ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -3,6 +3,7 @@
 #pragma once
 #include "../../include/cudpp.h"
 #include "glc_internal.h"
+#include "ans_coder.h"
 
 #include <functional>
 
@@ -129,6 +130,34 @@ hipError_t zrun_split(hipStream_t st, const ZrSegs &g);      // x -> A, B, a_len
 // outside A or B and nothing written outside the segment, whatever the streams hold
 hipError_t zrun_join(hipStream_t st, const ZrSegs &g);
 
+// the rANS passes (ans.hip; the coder is defined in INTEGRATION.md 4b).  Segment i is data + data_off[i], min(data_len[i], max_len)
+// bytes (max_len <= ANS_MAX_LEN), cut into chunks of ANS_CHUNK; its byte counts are hist[i][256], its table (ans_tables makes it
+// from the counts: 256 packed (q, cum, divisor shift), 256 divisor multipliers, 4096 slot -> symbol bytes) the ANS_TAB_BYTES at
+// tab + i * ANS_TAB_BYTES, 16-byte aligned.  data may be null with absolute addresses in data_off.  skip (optional): segments
+// whose entry is non-zero are left alone.  Everything only enqueues on `st`.
+constexpr uint32_t ANS_TAB_BYTES = 2048 + ANS_M;
+struct AnsSegs {
+    uint8_t *data; const unsigned long long *data_off, *data_len;
+    const uint32_t *hist; uint8_t *tab;
+    const uint32_t *skip;
+    uint32_t count, max_len;
+};
+struct AnsScratch {                                        // the encoder's: chunk c of segment i is slot i * nch_max + c
+    uint16_t *units;                                       // [slots][ANS_CHUNK], a slot filled from its back
+    uint32_t *states, *counts;                             // [slots][64]; [slots] units of the chunk
+    uint32_t nch_max;                                      // ans_chunks(max_len)
+};
+hipError_t ans_tables(hipStream_t st, const AnsSegs &g);                                   // hist -> tab
+hipError_t ans_encode(hipStream_t st, const AnsSegs &g, const AnsScratch &sc);             // data, tab -> scratch
+hipError_t ans_words(hipStream_t st, const AnsSegs &g, const AnsScratch &sc, unsigned long long *words);   // scratch -> record words
+// scratch -> the record of segment i at rec_base + rec_off[i] (words); a record that would end past cap_words is not written
+hipError_t ans_place(hipStream_t st, const AnsSegs &g, const AnsScratch &sc, uint32_t *rec_base, const unsigned long long *rec_off,
+                     unsigned long long cap_words);
+// records (rec_len[i] words each; null: rec_off[i + 1] - rec_off[i]), tab -> data.  Tolerant: a unit beyond a chunk's count or the
+// record's end is 0, nothing is read outside the record and nothing written outside the segment, whatever the record holds
+hipError_t ans_decode(hipStream_t st, const AnsSegs &g, const uint32_t *rec_base, const unsigned long long *rec_off,
+                      const unsigned long long *rec_len);
+
 // ---------------------------------------------------------------------------
 // layout (little-endian; every section 8-byte aligned)
 // ---------------------------------------------------------------------------
@@ -141,6 +170,7 @@ constexpr uint32_t CT_VERSION_DELTA = 4;                     // 4: version 3 wit
 constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the only one): the filter is delta + shuffle; elem 2, 4 or 8
 constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is legal; flags 0 (elem 0, 2, 4, 8) or the delta flag (elem 2, 4, 8)
 constexpr uint32_t CT_VERSION_RUNS = 6;                      // 6: kinds 0, 1, 2 and 4 are legal (not 3); the same triples as version 5
+constexpr uint32_t CT_VERSION_ANS = 7;                       // 7: kinds 0, 1, 2 and 5 are legal (not 3, not 4); the same triples as version 5
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
@@ -151,20 +181,23 @@ struct CtFormat {
     __host__ __device__ bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
     __host__ __device__ bool kind3_legal() const { return version == CT_VERSION_SPARSE; }
     __host__ __device__ bool kind4_legal() const { return version == CT_VERSION_RUNS; }
-    __host__ __device__ uint32_t max_kind() const { return kind4_legal() ? 4u : kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }   // (version 6: all but 3)
+    __host__ __device__ bool kind5_legal() const { return version == CT_VERSION_ANS; }
+    // (version 6: all but 3; version 7: all but 3 and 4)
+    __host__ __device__ uint32_t max_kind() const { return kind5_legal() ? 5u : kind4_legal() ? 4u : kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 struct CtLegal { uint32_t version, flags, elems; };
-constexpr uint32_t CT_NLEGAL = 8;
+constexpr uint32_t CT_NLEGAL = 10;
 __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 {
     constexpr CtLegal L[CT_NLEGAL] = {
         {CT_VERSION, 0, CT_NO_FILTER}, {CT_VERSION_SHUFFLE, 0, CT_ELEMS}, {CT_VERSION_CODEC, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_RUNS, 0, CT_NO_FILTER | CT_ELEMS},
-        {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}};
+        {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_ANS, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_ANS, CT_FLAG_DELTA, CT_ELEMS}};
     return L[i];
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
@@ -179,9 +212,11 @@ constexpr uint32_t CT_KIND_HUFF = 0, CT_KIND_RAW = 1;
 constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman record (hd_batch.hip), versions 3 and 4
 constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 record (sparse.hip): mask, then the kind-2 stream of the kept chunks; version 5
 constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
+constexpr uint32_t CT_KIND_ANS = 5;                          // rANS order-0 record (ans.hip): chunk unit counts, then every chunk's 64 states and units; version 7
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
-// what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6
-constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2;
+// what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
+// its rANS mode version 7
+constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4;
 
 // failure classes of glcContainerLastError (out[0])
 enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
@@ -263,7 +298,7 @@ struct CtWalkEnd { uint32_t what; unsigned long long frame; };            // fra
 
 // fetch(dst, pos, bytes, frame) -> bool brings 32 or 16 header bytes into dst; on_header(h, fmt, block_len, total),
 // on_frame(fi, fh, ref) and on_trailer(tr, frames) -> bool see what has passed its checks.  `reader` (CT_READS_*) is the plan's
-// sparse and runs modes (a plan with both off is a version-4 reader), plan_n its block length.
+// sparse, runs and rANS modes (a plan with all off is a version-4 reader), plan_n its block length.
 template <class Fetch, class OnHeader, class OnFrame, class OnTrailer>
 __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long long len, uint32_t plan_n, uint32_t reader, Fetch fetch,
                                              OnHeader on_header, OnFrame on_frame, OnTrailer on_trailer)
@@ -275,7 +310,8 @@ __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long l
     CtFormat fmt;
     if (!fetch(hdr, 0ull, CT_HDR, none)) return {CT_WALK_STOPPED, none};
     if (!check_stream_header(C, hdr, &fmt, &block_len, &total)) return {CT_STREAM_HEADER, none};
-    if ((fmt.kind3_legal() && !(reader & CT_READS_SPARSE)) || (fmt.kind4_legal() && !(reader & CT_READS_RUNS))) return {CT_STREAM_HEADER, none};
+    if ((fmt.kind3_legal() && !(reader & CT_READS_SPARSE)) || (fmt.kind4_legal() && !(reader & CT_READS_RUNS)) ||
+        (fmt.kind5_legal() && !(reader & CT_READS_ANS))) return {CT_STREAM_HEADER, none};
     if (!on_header(hdr, fmt, block_len, total)) return {CT_WALK_STOPPED, none};
     unsigned long long pos = CT_HDR, done = 0;
     uint32_t fi = 0;
@@ -326,11 +362,11 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, CompressCall c, ContainerHook
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
-// mode (only ever on with the shuffle on), the codec (CT_CODEC_*), its sparse mode (only ever on with the order-0 codec) and its
-// runs mode (only ever on with the BWT codec)
+// mode (only ever on with the shuffle on), the codec (CT_CODEC_*), its sparse mode (only ever on with the order-0 codec), its
+// runs mode (only ever on with the BWT codec) and its rANS mode (only ever on with the order-0 codec and the sparse mode off)
 struct CtSettings {
-    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false;
-    uint32_t reader() const { return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u); }
+    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false, ans = false;
+    uint32_t reader() const { return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u) | (ans ? CT_READS_ANS : 0u); }
 };
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
@@ -393,6 +429,11 @@ struct CtEncRuns {                                         // device scratch of 
     void *work;                                            // hdb_encode_work_bytes(2 rows)
     uint8_t *a, *b; uint32_t stride;                       // [rows][stride] each
 };
+struct CtEncAns {                                          // device scratch of the rANS mode, behind CtEncHuff0's (allocated once it is on)
+    unsigned long long *blk_off, *blk_len;                 // [rows] the blocks as segments of the frame
+    uint8_t *tab;                                          // [rows] ANS_TAB_BYTES
+    AnsScratch sc;                                         // [rows * ans_chunks(n)] slots: about 2 * rows * n bytes
+};
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 // the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
 // mask (1 = raw) and f.bwt zeros
@@ -417,6 +458,9 @@ hipError_t ct_enc_runs_segs(hipStream_t st, const CtEncRuns &r, const uint8_t *m
 hipError_t ct_enc_runs_empty(hipStream_t st, const CtEncRuns &r, uint32_t nb);
 hipError_t ct_enc_runs_kind(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_runs_place(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t *out, unsigned long long cap_words);
+// the rANS mode's ct_enc_kind0 (ans.hip), behind ans_encode: record sizes from the chunks' unit counts, kind 5 or raw when
+// 4 * words >= blk_len; f.only becomes ans_place's skip mask (1 = raw) and f.bwt zeros
+hipError_t ct_enc_ans_kind(hipStream_t st, const CtEncFrame &f, const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
@@ -451,6 +495,9 @@ struct CtDecHuff0 {                                        // device scratch of 
     uint8_t *kept_b;                                       // [chunk][kept_stride]
     unsigned long long *m_off, *m_len;                     // [nb]
     uint8_t *mtf; size_t mtf_stride;
+    // version 7 (max_kind 5): the tables of the kind-5 blocks of one decoder chunk (block b in slot b % chunk), built from the
+    // verified histograms behind the verdict
+    uint8_t *ans_tab;                                      // [chunk] ANS_TAB_BYTES
 };
 // the counts of B of every kind-4 block from its record's pairs (zeros where the record does not hold well-formed pairs), and
 // whose table is built from them

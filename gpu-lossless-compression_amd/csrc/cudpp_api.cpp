@@ -124,10 +124,10 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     hipEvent_t *const side_events[10] = {&ev_in, &ev_sorted[0], &ev_sorted[1], &enc_half.ev[0], &enc_half.ev[1],
                                          &ev_dec_a[0], &ev_dec_a[1], &dec_half.ev[0], &dec_half.ev[1], &ev_s2};
     bool side_busy = false;                      // side-stream work issued since the last join
-    // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse / Runs) and the filter's frame staging both directions share
+    // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse / Runs / Ans) and the filter's frame staging both directions share
     CtSettings ct;
     GrowBuf ct_stage[2];
-    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse mode's and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
+    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse and rANS modes' and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
     SaScratch *sorter() override { return &sa; }
     void wire_prof() override { sa.prof = &prof; mtf.prof = &prof; huff.prof = &prof; dec.prof = &prof; }
     hipEvent_t side_span_start() override { return pipelined ? ev_s2 : nullptr; }

@@ -657,6 +657,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice", "glcPlanSetContainerDelta", "glcPlanGetContainerDelta",
                      "glcSparseSplitSegments", "glcSparseJoinSegments", "glcPlanSetContainerSparse", "glcPlanGetContainerSparse",
                      "glcZeroRunSplitSegments", "glcZeroRunJoinSegments", "glcPlanSetContainerRuns", "glcPlanGetContainerRuns",
+                     "glcAnsEncodeSegments", "glcAnsDecodeSegments", "glcAnsSegmentsWorkBytes", "glcAnsBoundWords",
+                     "glcPlanSetContainerAns", "glcPlanGetContainerAns",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -713,6 +715,14 @@ def _ct():
         for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
         L.glcContainerIndexFree.restype = None
+        L.glcPlanSetContainerAns.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerAns.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcAnsEncodeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
+        L.glcAnsDecodeSegments.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, sz, vp]
+        L.glcAnsSegmentsWorkBytes.argtypes = [sz, sz]
+        L.glcAnsSegmentsWorkBytes.restype = sz
+        L.glcAnsBoundWords.argtypes = [sz]
+        L.glcAnsBoundWords.restype = sz
         L._ct_ready = True
     return L
 
@@ -850,6 +860,76 @@ def container_get_runs(plan):
     d = C.c_uint(0)
     _chk("glcPlanGetContainerRuns", _ct().glcPlanGetContainerRuns(plan.handle, C.byref(d)))
     return int(d.value)
+
+
+def container_set_ans(plan, on):
+    """the rANS mode of the plan's container ENCODER (format version 7): True / 1 needs the order-0 codec and the sparse mode off;
+    container_set_codec(plan, CONTAINER_CODEC_BWT) also switches it off.  It is also the version the plan reads: on, versions 1
+    to 4 and 7; off, a version-7 stream is a stream-header failure as it always was."""
+    _chk("glcPlanSetContainerAns", _ct().glcPlanSetContainerAns(plan.handle, int(on)))
+
+
+def container_get_ans(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerAns", _ct().glcPlanGetContainerAns(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def ans_bound_words(length):
+    """words of room the record of a segment of `length` bytes may need"""
+    return int(_ct().glcAnsBoundWords(int(length)))
+
+
+def ans_work_bytes(count, max_len):
+    return int(_ct().glcAnsSegmentsWorkBytes(int(count), int(max_len)))
+
+
+def _ans_args(d_base, offsets, lengths, max_len):
+    import torch
+    dev = d_base.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    work = torch.empty(max(16, ans_work_bytes(off.numel(), max_len)), dtype=torch.uint8, device=dev)
+    return off, ln, max_len, work
+
+
+def ans_encode_segments(d_in, offsets, lengths, max_len=None, stream=None):
+    """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in as rANS records (format version 7, kind 5).
+    Returns (hist int32 tensor [count, 256], records int32 tensor, record word offsets (list), record words int64 tensor
+    [count]); record i is records[rec_off[i] : rec_off[i] + words[i]]"""
+    import torch
+    off, ln, max_len, work = _ans_args(d_in, offsets, lengths, max_len)
+    n = off.numel()
+    rec_off, total = [], 0
+    for l in lengths:
+        rec_off.append(total)
+        total += ans_bound_words(min(int(l), max_len))
+    ro = torch.as_tensor(rec_off, dtype=torch.int64).to(d_in.device)
+    hist = torch.zeros((max(1, n), 256), dtype=torch.int32, device=d_in.device)
+    rec = torch.zeros(max(1, total), dtype=torch.int32, device=d_in.device)
+    words = torch.zeros(max(1, n), dtype=torch.int64, device=d_in.device)
+    _chk("glcAnsEncodeSegments", _ct().glcAnsEncodeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, hist.data_ptr(),
+                                                             rec.data_ptr(), ro.data_ptr(), words.data_ptr(), work.data_ptr(),
+                                                             work.numel(), stream))
+    torch.cuda.synchronize(d_in.device)                        # (off / ln / ro / work are temporaries of this call)
+    return hist[:n], rec, rec_off, words[:n]
+
+
+def ans_decode_segments(rec, rec_off, words, hist, d_out, offsets, lengths, max_len=None, stream=None):
+    """the inverse of ans_encode_segments into the device uint8 tensor d_out; tolerant of whatever rec and words hold"""
+    import torch
+    off, ln, max_len, work = _ans_args(d_out, offsets, lengths, max_len)
+    ro = torch.as_tensor(rec_off, dtype=torch.int64).to(d_out.device)
+    wd = torch.as_tensor(words, dtype=torch.int64).to(d_out.device)
+    h = hist.contiguous()
+    assert ro.numel() == wd.numel() == off.numel() and h.numel() == 256 * off.numel()
+    _chk("glcAnsDecodeSegments", _ct().glcAnsDecodeSegments(rec.data_ptr(), ro.data_ptr(), wd.data_ptr(), h.data_ptr(), off.data_ptr(),
+                                                             ln.data_ptr(), off.numel(), max_len, d_out.data_ptr(), work.data_ptr(),
+                                                             work.numel(), stream))
+    torch.cuda.synchronize(d_out.device)
+    return d_out
 
 
 def _zerorun_args(d_base, offsets, lengths):

@@ -51,6 +51,24 @@
  * k_hdb_span_functions takes 5 ms per GiB where the kind-0 record's sub-block offsets let k_dec_huff take 1.7. The split alone
  * moves 316 GB/s and the join 638-820, a device-to-device copy 2542.
  *
+ * Scattered skew (quantised gradients and activations, delta'd planes that are mostly 0 and +-1, masks with isolated set bytes):
+ * the rANS mode of the order-0 codec, off by default.  No 64-byte chunk of such data is one byte, so the sparse mode elides
+ * nothing and the stream stays at Huffman's one bit per byte at best.  With glcPlanSetContainerAns on, a block is coded by
+ * interleaved range-ANS against 12-bit probabilities derived from its byte counts (record kind 5): chunks of 32768 bytes, 64
+ * interleaved 32-bit states a chunk, 16-bit units, the states stored -- so a symbol of probability q / 4096 costs log2(4096 / q)
+ * bits and one wave decodes one chunk straight through, with no synchronisation pass.  The stream is format version 7.  The
+ * model's sizes are in INTEGRATION.md 4b ("ans: when"): 1 MiB of bytes that are 90 % zeros, scattered, 7.648 against 5.223 with
+ * the mode off or the sparse mode on; the integer series within 3 % of the sparse mode; data that is one byte over whole
+ * regions stays the sparse mode's (38.96 against 44.30 on regular-step timestamps); Zipf bytes gain nothing.
+ * Measured on one MI355X on 1 GiB of device-generated data in 1 MiB blocks, rows 512 (profiles/ans_mode.md; ratio / encode /
+ * decode GB/s, medians of 5 interleaved rounds): scattered 90 % zeros, mode off 5.677 / 552 / 171, on 8.670 / 501 / 450; int64
+ * timestamps with delta + shuffle 8, off 4.192 / 415 / 134, sparse 6.771 / 456 / 173, rANS 6.809 / 385 / 359; uint32 counters with
+ * delta + shuffle 4, off 5.280 / 418 / 145, sparse 9.999 / 459 / 200, rANS 9.835 / 394 / 365.  Decode with the mode on is 2.5 to
+ * 2.7 times faster than the order-0 path with the mode off: k_ans_table + k_ans_decode take about 1.1 ms per GiB where
+ * k_hdb_span_functions + k_hdb_emit take about 6.5.  Encode is 6 to 9 % slower: the coder and its placing pass stand where
+ * k_hdb_enc_* stood.  With the mode off the rates equal the parent commit's within the spread of the rounds.  The kernels alone:
+ * encode 782 GB/s, decode 968, a device-to-device copy 2674.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -162,6 +180,29 @@ CUDPPResult glcZeroRunSplitSegments(const void *d_inBase, const unsigned long lo
 CUDPPResult glcZeroRunJoinSegments(const void *d_aBase, const void *d_bBase, const unsigned long long *d_offsets,
                                    const unsigned long long *d_aLen, const unsigned long long *d_bLen, const unsigned long long *d_lengths,
                                    size_t count, size_t maxLen, void *d_outBase, void *stream);
+
+/* The rANS coder of the order-0 codec's rANS mode as batched calls (csrc/ans.hip; the record is INTEGRATION.md 4b's kind 5).  Segment
+ * i is [d_offsets[i], + min(d_lengths[i], maxLen)) of its base, at most GLC_ANS_MAX_LEN bytes at any byte alignment, cut into chunks
+ * of 32768 bytes that 64 interleaved states code.  Encode writes row i of d_hist (256 byte counts), the record at d_recBase +
+ * d_recOffsets[i] WORDS (the caller leaves glcAnsBoundWords(length) words of room: chunk unit counts, then every chunk's 64 states
+ * and its 16-bit units) and its size to d_recWords[i].  Decode takes the counts, the records and their sizes and writes the
+ * segments; it is tolerant -- whatever a record or d_recWords holds, nothing is read outside [record, + d_recWords[i]) and nothing
+ * written outside the segment; a segment whose counts are not its own decodes to garbage.  d_work: glcAnsSegmentsWorkBytes(count,
+ * maxLen) bytes of device memory for the duration of the call's work (the tables, 6 KiB a segment; the encoder's chunk slots,
+ * 64 KiB per chunk of maxLen per segment); the calls only enqueue on `stream`.  A bad argument (a null pointer with count > 0, equal
+ * data and record bases, records or counts not 4-byte aligned, a work space too small, a maxLen or count too large) is
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written; the two size functions return 0 for such a maxLen or count. */
+#define GLC_ANS_MAX_LEN ((size_t)1 << 20)
+#define GLC_ANS_MAX_COUNT ((size_t)1 << 22)
+size_t glcAnsBoundWords(size_t len);
+size_t glcAnsSegmentsWorkBytes(size_t count, size_t maxLen);
+CUDPPResult glcAnsEncodeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_recBase,
+                                 const unsigned long long *d_recOffsets, unsigned long long *d_recWords, void *d_work, size_t workBytes,
+                                 void *stream);
+CUDPPResult glcAnsDecodeSegments(const unsigned int *d_recBase, const unsigned long long *d_recOffsets, const unsigned long long *d_recWords,
+                                 const unsigned int *d_hist, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, void *d_outBase, void *d_work, size_t workBytes, void *stream);
 
 /* The element size the container ENCODER of this plan shuffles by: 0 or 1 = off (the default), 2, 4, 8; anything else is
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leaves the setting as it was.  All six container entry points honour it; the decoder
@@ -280,6 +321,24 @@ CUDPPResult glcUndeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsign
  * much for the blocks of one decoder chunk plus the BWT decoder's scratch; both are kept with the plan and freed with it. */
 CUDPPResult glcPlanSetContainerRuns(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on);
+
+/* The rANS mode of the ENCODER's order-0 codec: on = 1 writes format version 7, where every block is an rANS record (kind 5: the
+ * block's byte counts in the tables, the 12-bit probabilities derived from them, and per chunk of 32768 bytes 64 interleaved
+ * 32-bit states with their 16-bit units) or, when 4 * words >= block bytes, raw; 0 (the default) writes versions 1 to 6 byte for
+ * byte as ever.  A Huffman code spends at least one bit per byte; this coder spends log2(4096 / q) bits on a symbol of quantised
+ * probability q / 4096, so scattered skew (quantised gradients, delta'd planes of 0 and +-1) that no fill-byte chunk and no table
+ * can shorten codes below one bit.  on = 1 needs the codec GLC_CONTAINER_CODEC_HUFF0 and the sparse mode off: on = 1 without them,
+ * and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; glcPlanSetContainerCodec(plan,
+ * GLC_CONTAINER_CODEC_BWT) also switches it off, and glcPlanSetContainerSparse(plan, 1) is refused while it is on.  All six
+ * container entry points and the range reads honour it, with pipelining on or off and with any filter setting.  The setting is
+ * also the version the plan speaks: a plan with it on reads versions 1 to 4 and 7, every other plan refuses a version-7 stream as
+ * a stream-header failure, as it did before version 7 existed.  The first rANS encode allocates about 2 * rows * n bytes of chunk
+ * slots and 6 KiB of tables per row, the first version-7 decode 6 KiB of tables per block of one decoder chunk beside what a
+ * version-3 decode allocates (a version-7 frame may hold kind 2); the kind-5 blocks themselves use the tables alone -- a chunk starts
+ * from stored states, so one wave decodes it straight through and no span-function prefixes are computed.  Both are kept with the
+ * plan and freed with it.  The new kernels have no slot in the plan's kernel profile. */
+CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

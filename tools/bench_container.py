@@ -21,7 +21,9 @@ the order-0 codec for both settings.
 --rounds R (typed data, --codec 1) replaces the filter section by the sparse section: the filter on (with --delta: in delta mode), the
 order-0 codec, and R interleaved rounds of encode and decode timed with device events -- with --sparse each round runs the sparse
 mode off and then on (glcPlanSetContainerSparse, format version 5), without it only off, which is also what a build without the
-mode can run.  Every round's rates are reported, with their median and spread (max - min) per setting.
+mode can run; with --ans each round also runs the rANS mode (glcPlanSetContainerAns, format version 7), so that one run interleaves
+the settings off, sparse and ans.  --data skew90 is the scattered-skew input (90 % zeros, the rest uniform in 1 .. 15, no filter).
+Every round's rates are reported, with their median and spread (max - min) per setting.
 
 --runs (with --data textlike or loglike, generated on the device; --rounds R, at least 1) is the runs section: the BWT codec with its
 runs mode off and then on (glcPlanSetContainerRuns, format version 6), R interleaved rounds of encode and decode timed with device
@@ -31,7 +33,7 @@ device-to-device copy.  --runs-off-only runs the same section without ever touch
 it can run.
 
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]
-                                [--rounds R] [--sparse] [--runs | --runs-off-only]"""
+                                [--rounds R] [--sparse] [--ans] [--runs | --runs-off-only]"""
 import argparse
 import json
 import os
@@ -41,7 +43,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2}
+DATA_ELEM = {"textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0}
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -58,6 +60,9 @@ def typed_on_device(torch, L, dev, kind, total):
         x = torch.randn(count, dtype=torch.float64, device=dev, generator=g).mul_(0.01).cumsum_(0)
         x.add_(torch.arange(count, dtype=torch.float64, device=dev).mul_(2.0 * 3.141592653589793 / 5000.0).sin_().mul_(100.0))
         return (x if elem == 8 else x.to(torch.float32)).view(torch.uint8)
+    if kind == "skew90":                                       # scattered skew: 90 % zeros, the rest uniform in 1 .. 15
+        v = torch.randint(1, 16, (total,), dtype=torch.uint8, device=dev, generator=g)
+        return v.mul_(torch.rand(total, dtype=torch.float32, device=dev, generator=g) >= 0.9)
     if kind == "ts64":
         return torch.randint(900, 1100, (total // 8,), dtype=torch.int64, device=dev, generator=g).cumsum_(0).view(torch.uint8)
     if kind == "ids32":
@@ -250,9 +255,10 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
     return res
 
 
-def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse):
-    """the order-0 container with the sparse mode off and (with_sparse) on, interleaved: `rounds` rounds of one encode and one
-    decode per setting after one untimed round, each timed with device events on the plan's (the default) stream"""
+def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse, with_ans=False):
+    """the order-0 container with its modes off, (with_sparse) the sparse mode on and (with_ans) the rANS mode on, interleaved:
+    `rounds` rounds of one encode and one decode per setting after one untimed round, each timed with device events on the plan's
+    (the default) stream"""
     n = plan.n
     cap = glc.container_bound(total, n)
     cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
@@ -261,7 +267,7 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
     glc.container_set_shuffle(plan, elem)
     if elem and delta:
         glc.container_set_delta(plan, 1)
-    settings = ["off", "sparse"] if with_sparse else ["off"]
+    settings = ["off"] + (["sparse"] if with_sparse else []) + (["ans"] if with_ans else [])
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
 
     def event_timed(fn):
@@ -275,8 +281,12 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
 
     for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
         for s in settings:
+            if with_ans:
+                glc.container_set_ans(plan, 0)                 # (the two modes exclude each other: off before the other goes on)
             if with_sparse:
                 glc.container_set_sparse(plan, 1 if s == "sparse" else 0)
+            if with_ans:
+                glc.container_set_ans(plan, 1 if s == "ans" else 0)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -308,6 +318,7 @@ def main():
     ap.add_argument("--codec", type=int, default=0, choices=[0, 1], help="the filter section's container codec: 0 BWT, 1 order-0")
     ap.add_argument("--rounds", type=int, default=0, help="typed data: the sparse section, this many interleaved rounds timed with device events")
     ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
+    ap.add_argument("--ans", action="store_true", help="the sparse section also runs the order-0 codec's rANS mode (format version 7)")
     ap.add_argument("--runs", action="store_true", help="text-like data: the runs section, the BWT codec's runs mode off and on (format version 6)")
     ap.add_argument("--runs-off-only", action="store_true", help="the runs section without the mode (what a build without it can run)")
     args = ap.parse_args()
@@ -363,7 +374,7 @@ def main():
             if args.rounds:
                 assert args.codec == 1, "the sparse section is the order-0 codec's"
                 res["sparse"] = sparse_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.delta, args.rounds,
-                                               args.sparse)
+                                               args.sparse, args.ans)
             else:
                 res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
         print(json.dumps(res))
