@@ -154,14 +154,6 @@ __global__ __launch_bounds__(ANS_THREADS) void k_ans_encode(AnsSegs g, AnsScratc
     if (lane == 0) sc.counts[slot] = ANS_CHUNK - ptr;
 }
 
-// the words of a segment's record from its chunks' counts (every lane of a wave; counts clamped to a chunk's symbols)
-__device__ __forceinline__ unsigned long long ans_words_of(const uint32_t *counts, uint32_t nch)
-{
-    unsigned long long w = nch;
-    for (uint32_t c = 0; c < nch; c++) w += ANS_LANES + (min(counts[c], ANS_CHUNK) + 1) / 2;
-    return w;
-}
-
 __global__ __launch_bounds__(256) void k_ans_words(AnsSegs g, AnsScratch sc, unsigned long long *words)
 {
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;

@@ -396,7 +396,7 @@ hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, 
 // tables themselves are unverified until k_cd_verdict, so everything read from them is clamped first
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
-                                                 unsigned long long P, uint32_t *skip0, uint32_t max_kind)
+                                                 unsigned long long P, uint32_t *skip0, uint32_t kinds)
 {
     const CtTables T = ct_tables(nb, blk_len);
     const uint32_t *W = reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR);
@@ -407,8 +407,7 @@ __global__ __launch_bounds__(256) void k_cd_segs(CtDecFrame f, const uint8_t *fr
     if (b < nb) {
         if (skip0) {                                           // (version 3 and later: whose tables are built next)
             const uint32_t kind = W[T.kind + b];
-            skip0[b] = kind == CT_KIND_HUFF0 || (kind == CT_KIND_SPARSE && max_kind == CT_KIND_SPARSE) ||
-                       (kind == CT_KIND_RUNS && max_kind == CT_KIND_RUNS) ? 0u : 1u;   // (a kind-5 block has no Huffman table)
+            skip0[b] = (kind == CT_KIND_HUFF0 || kind == CT_KIND_SPARSE || kind == CT_KIND_RUNS) && (kinds >> kind & 1u) ? 0u : 1u;   // (a kind-5 block has no Huffman table)
         }
         const unsigned long long lo = po[b], hi = po[b + 1];
         const bool ok = lo <= hi && hi <= P;
@@ -436,10 +435,9 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
     const uint32_t kind = W[T.kind + b];
     reinterpret_cast<uint32_t *>(f.verdict + 2)[b] = kind;
     const unsigned long long lo = po[b], hi = po[b + 1];
-    bool bad = kind > (nun0 ? h0.max_kind : CT_KIND_RAW) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
-    const bool runs = nun0 && h0.max_kind == CT_KIND_RUNS;       // (version 6: kind 3 is not legal)
-    const bool ans = nun0 && h0.max_kind == CT_KIND_ANS;         // (version 7: neither are kinds 3 and 4)
-    bad = bad || (runs && kind == CT_KIND_SPARSE) || (ans && (kind == CT_KIND_SPARSE || kind == CT_KIND_RUNS));
+    const uint32_t legal = nun0 ? h0.kinds : ct_kinds(CT_VERSION);   // (version 6: not kind 3; 7: neither 3 nor 4; 8: not 4)
+    bool bad = kind > 31u || !(legal >> kind & 1u) || lo > hi || hi > P || (b == 0 && lo != 0) || (b + 1 == nb && hi != P);
+    const bool runs = nun0 && (legal >> CT_KIND_RUNS & 1u);
     unsigned long long klen = 0, nB = 0, nzw = 0;
     if (!bad) {
         const unsigned long long w = hi - lo;
@@ -535,7 +533,7 @@ __global__ __launch_bounds__(256) void k_cd_verdict(CtDecFrame f, const uint8_t 
         h0.skip_b[b] = k4 && nB ? 0u : 1u;
         h0.m_off[b] = (unsigned long long)(uintptr_t)(h0.mtf + slot * h0.mtf_stride);
         h0.m_len[b] = blk_len;
-    } else if (nun0 && h0.max_kind == CT_KIND_SPARSE) {
+    } else if (nun0 && (legal >> CT_KIND_SPARSE & 1u)) {
         const bool k3 = !bad && kind == CT_KIND_SPARSE;
         h0.k_off[b] = (unsigned long long)(uintptr_t)(h0.kept + (size_t)(b % h0.chunk) * h0.kept_stride);
         h0.k_len[b] = k3 ? klen : 0;
@@ -585,7 +583,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
                          unsigned long long payload_words, const CtDecHuff0 *h0, KernelProf *prof)
 {
     hipLaunchKernelGGL(k_cd_segs, dim3((nb + 2 + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
-                       h0 ? h0->skip : nullptr, h0 ? h0->max_kind : CT_KIND_RAW);
+                       h0 ? h0->skip : nullptr, h0 ? h0->kinds : ct_kinds(CT_VERSION));
     hipError_t e = hipSuccess;
     if (h0) {
         const CtTables T = ct_tables(nb, blk_len);
@@ -593,7 +591,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
         const HdbSegs g{nullptr, nullptr, nullptr, nb, blk_len};
         e = hdb_tables(st, g, false, hist, nullptr, nullptr, h0->lut, h0->nun, h0->skip, prof);
         if (e != hipSuccess) return e;
-        if (h0->max_kind == CT_KIND_RUNS) {                    // (version 6: the tables of B, from the counts in the records)
+        if (h0->kinds >> CT_KIND_RUNS & 1u) {                  // (version 6: the tables of B, from the counts in the records)
             e = ct_dec_runs_hist(st, frame, nb, blk_len, payload_words, *h0);
             if (e != hipSuccess) return e;
             e = hdb_tables(st, g, false, h0->hist_b, nullptr, nullptr, h0->lut_b, h0->nun_b, h0->skip_tb, prof);

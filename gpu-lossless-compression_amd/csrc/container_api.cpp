@@ -9,7 +9,7 @@
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
 // and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3; with the rANS mode on: frame_ans, kind 5, the histograms alone and the
-// kernels of ans.hip).  With the BWT codec's
+// kernels of ans.hip; with the auto mode on: frame_auto, the probe of auto.hip and a kind per block out of 2, 3 and 5).  With the BWT codec's
 // runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
@@ -119,7 +119,7 @@ CtFormat format_of(const CtSettings &s)
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         f.version = ct_legal(i).version;
         if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal()) &&
-            (!s.runs || f.kind4_legal()) && (!s.ans || f.kind5_legal())) break;
+            (!s.runs || f.kind4_legal()) && (!s.ans || f.kind5_legal()) && (!s.autom || f.version == CT_VERSION_AUTO)) break;
     }
     return f;                                                 // (the setters accept only what some row takes)
 }
@@ -171,6 +171,8 @@ struct Encoder {
     CtEncRuns zr = {};                                        // its scratch, kept with the plan; a plan that never has it on has none
     bool ans = false;                                         // the order-0 codec's rANS mode
     CtEncAns an = {};                                         // its scratch, behind h0's; a plan that never has it on has none
+    bool autom = false;                                       // the order-0 codec's auto mode: both scratches above and its own
+    CtEncAuto au = {};
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -206,7 +208,7 @@ struct Encoder {
         h0.lens = c.take<uint8_t>(256 * R);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_encode_work_bytes(R));
-        if (ans) {
+        if (ans || autom) {
             // everything of a frame runs on the plan's stream in order, so one set of chunk slots serves pipelined calls as well
             const size_t slots = R * ans_chunks(P.n);
             an.sc.nch_max = ans_chunks(P.n);
@@ -218,7 +220,14 @@ struct Encoder {
             an.tab = c.take<uint8_t>(R * ANS_TAB_BYTES);
             an.sc.units = c.take<uint16_t>(slots * ANS_CHUNK);
         }
-        if (!sparse) return;
+        if (autom) {
+            au.uniform = c.take<uint32_t>(256 * R);
+            au.hist_s = c.take<uint32_t>(256 * R);
+            au.wa = c.take<uint32_t>(R);
+            au.pick5 = c.take<uint32_t>(R);
+            au.skip_ans = c.take<uint32_t>(R);
+        }
+        if (!sparse && !autom) return;
         // everything of a frame runs on the plan's stream in order, so one compaction space serves pipelined calls as well
         sp.mask_stride = sp_mask_words(P.n);
         sp.kept_stride = (P.n + 15u) & ~15u;
@@ -266,6 +275,7 @@ struct Encoder {
         sparse = s.sparse && codec == CT_CODEC_HUFF0;
         runs = s.runs && codec == CT_CODEC_BWT;
         ans = s.ans && codec == CT_CODEC_HUFF0 && !sparse;
+        autom = s.autom && codec == CT_CODEC_HUFF0 && !sparse && !ans;
         if (runs) {
             Carver measure;
             carve_runs(measure);
@@ -318,6 +328,7 @@ struct Encoder {
         if (sparse) return frame_sparse(f, d_in, orig, nb, blk_len, out, cap);
         if (runs) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
         if (ans) return frame_ans(f, d_in, orig, nb, blk_len, out, cap);
+        if (autom) return frame_auto(f, d_in, orig, nb, blk_len, out, cap);
         if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
@@ -409,6 +420,46 @@ struct Encoder {
         return CUDPP_SUCCESS;
     }
 
+    // frame_huff0 with the auto mode on: one probe of the blocks (counts and uniform chunks) -> fill bytes and the blocks' rANS
+    // tables (their q) -> candidate S of every block and the estimate wA, from the statistics alone -> the Huffman tables of
+    // candidate S's counts, and with them wS -> the choice per block -> masks and compaction of the blocks that stay kind 3, the
+    // rANS coder on the blocks chosen as kind 5 -> actual sizes and the raw rule -> payload offsets -> masks and rANS records
+    // placed, kind 2 and K encoded behind them
+    CUDPPResult frame_auto(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
+                           uint8_t *out, unsigned long long cap)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        plan_stage_mark(P.h, 0);
+        CT_TRY(ct_block_offsets(P.st, sp.blk_off, sp.blk_len, nb, blk_len));
+        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));        // (klen itself comes two steps on)
+        CT_TRY(probe_segments(P.st, d_in, sp.blk_off, sp.blk_len, nb, blk_len, f.hist, au.uniform));
+        CT_TRY(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
+        const AnsSegs a{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, f.hist, an.tab, nullptr, nb, blk_len};
+        CT_TRY(ans_tables(P.st, a));
+        SpSegs s{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr, sp.mask_stride,
+                 nullptr, nb, blk_len};
+        CT_TRY(ct_enc_auto_candidates(P.st, s, sp, au, f.hist, an.tab, h0.in_off, h0.in_len));
+        const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
+        CT_TRY(hdb_tables(P.st, g2, false, au.hist_s, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
+        CT_TRY(ct_enc_auto_choose(P.st, f, h0, sp, au, nb, blk_len));
+        s.skip = sp.skip_move;
+        CT_TRY(sparse_mask(P.st, s));
+        CT_TRY(sparse_compact(P.st, s));
+        AnsSegs ae = a;
+        ae.skip = au.skip_ans;
+        CT_TRY(ans_encode(P.st, ae, an.sc));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_auto_kind(P.st, f, h0, sp, au, an.sc, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
+        CT_TRY(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, reinterpret_cast<uint32_t *>(out), cap / 4));
+        CT_TRY(ans_place(P.st, ae, an.sc, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4));
+        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), sp.unit_off, cap / 4, f.only, h0.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
+    }
+
     // the BWT codec's frame with the runs mode on, wholly on the plan's stream: BWT and MTF of the blocks by the plan's sorter
     // and MTF stage -> the split into A and B -> tables of the A's (their counts are the record's hist) and of the B's -> nz,
     // record sizes and the raw rule -> payload offsets -> nz and the pairs into the records -> every stream encoded at its
@@ -480,7 +531,7 @@ struct Decoder {
         h0.lut = c.take<uint16_t>(2048 * (size_t)nb);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_decode_work_bytes(h0.chunk, blk_len));
-        h0.max_kind = fmt.max_kind();
+        h0.kinds = fmt.kinds();
         if (fmt.kind5_legal()) {
             c.align(256);
             h0.ans_tab = c.take<uint8_t>((size_t)h0.chunk * ANS_TAB_BYTES);
@@ -1130,9 +1181,7 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
     uint32_t hdr[8];
     if (io.small(hdr, 0, CT_HDR) != CUDPP_SUCCESS) return fail(plan, CT_TRUNCATED);
     if (memcmp(hdr, ix->hdr, CT_HDR) != 0) return fail(plan, CT_STREAM_HEADER);           // another container than the index's
-    if ((ix->fmt.kind3_legal() && !plan_container_settings(plan).sparse) || (ix->fmt.kind4_legal() && !plan_container_settings(plan).runs) ||
-        (ix->fmt.kind5_legal() && !plan_container_settings(plan).ans))
-        return fail(plan, CT_STREAM_HEADER);
+    if (ix->fmt.reads() && !(plan_container_settings(plan).reader() & ix->fmt.reads())) return fail(plan, CT_STREAM_HEADER);
     stats.v[2] = CT_HDR;
     D.fmt = ix->fmt;
     CT_TRY(D.begin());
@@ -1585,6 +1634,19 @@ CUDPPResult glcAnsDecodeSegments(const unsigned int *d_recBase, const unsigned l
     return CUDPP_SUCCESS;
 }
 
+// the probe: a bad argument is refused before anything is enqueued
+CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                             size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_uniform, void *stream)
+{
+    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_inBase || !d_offsets || !d_lengths || !d_hist || !d_uniform || d_hist == d_uniform || (reinterpret_cast<uintptr_t>(d_hist) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_uniform) & 3)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                          (uint32_t)maxLen, d_hist, d_uniform));
+    return CUDPP_SUCCESS;
+}
+
 CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
 {
     return shuffle_device_api(d_in, d_out, len, elem, stream, false);
@@ -1633,7 +1695,7 @@ CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
     if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CtSettings &s = plan_container_settings(plan);
     s.codec = codec;
-    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = s.ans = false;   // (no sparse or rANS mode without the order-0 codec)
+    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = s.ans = s.autom = false;   // (no sparse, rANS or auto mode without the order-0 codec)
     if (codec != GLC_CONTAINER_CODEC_BWT) s.runs = false;       // (no runs mode without the BWT codec)
     return CUDPP_SUCCESS;
 }
@@ -1643,7 +1705,7 @@ CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.ans))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;   // (the two modes exclude each other)
+    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.ans || s.autom))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;   // (the modes exclude each other)
     s.sparse = on != 0;
     return CUDPP_SUCCESS;
 }
@@ -1653,8 +1715,27 @@ CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse || s.autom))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     s.ans = on != 0;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    CtSettings &s = plan_container_settings(plan);
+    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse || s.ans))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    s.autom = on != 0;
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).autom ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -4,6 +4,7 @@
 #include "../../include/cudpp.h"
 #include "glc_internal.h"
 #include "ans_coder.h"
+#include "auto_rule.h"
 
 #include <functional>
 
@@ -147,6 +148,13 @@ struct AnsScratch {                                        // the encoder's: chu
     uint32_t *states, *counts;                             // [slots][64]; [slots] units of the chunk
     uint32_t nch_max;                                      // ans_chunks(max_len)
 };
+// the words of a segment's record from its chunks' counts (counts clamped to a chunk's symbols)
+__host__ __device__ inline unsigned long long ans_words_of(const uint32_t *counts, uint32_t nch)
+{
+    unsigned long long w = nch;
+    for (uint32_t c = 0; c < nch; c++) w += ANS_LANES + ((counts[c] < ANS_CHUNK ? counts[c] : ANS_CHUNK) + 1) / 2;
+    return w;
+}
 hipError_t ans_tables(hipStream_t st, const AnsSegs &g);                                   // hist -> tab
 hipError_t ans_encode(hipStream_t st, const AnsSegs &g, const AnsScratch &sc);             // data, tab -> scratch
 hipError_t ans_words(hipStream_t st, const AnsSegs &g, const AnsScratch &sc, unsigned long long *words);   // scratch -> record words
@@ -171,6 +179,16 @@ constexpr uint32_t CT_FLAG_DELTA = 1;                        //    bit 0 (the on
 constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is legal; flags 0 (elem 0, 2, 4, 8) or the delta flag (elem 2, 4, 8)
 constexpr uint32_t CT_VERSION_RUNS = 6;                      // 6: kinds 0, 1, 2 and 4 are legal (not 3); the same triples as version 5
 constexpr uint32_t CT_VERSION_ANS = 7;                       // 7: kinds 0, 1, 2 and 5 are legal (not 3, not 4); the same triples as version 5
+constexpr uint32_t CT_VERSION_AUTO = 8;                      // 8: kinds 0, 1, 2, 3 and 5 are legal (not 4); the same triples as version 5
+// what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
+// its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7)
+constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8;
+// the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
+__host__ __device__ inline uint32_t ct_kinds(uint32_t version)
+{
+    constexpr uint32_t K[CT_VERSION_AUTO + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F};
+    return version <= CT_VERSION_AUTO ? K[version] : 0u;
+}
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
@@ -178,18 +196,23 @@ struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
-    __host__ __device__ bool kind2_legal() const { return version >= CT_VERSION_CODEC; }
-    __host__ __device__ bool kind3_legal() const { return version == CT_VERSION_SPARSE; }
-    __host__ __device__ bool kind4_legal() const { return version == CT_VERSION_RUNS; }
-    __host__ __device__ bool kind5_legal() const { return version == CT_VERSION_ANS; }
-    // (version 6: all but 3; version 7: all but 3 and 4)
-    __host__ __device__ uint32_t max_kind() const { return kind5_legal() ? 5u : kind4_legal() ? 4u : kind3_legal() ? 3u : kind2_legal() ? 2u : 1u; }
+    __host__ __device__ uint32_t kinds() const { return ct_kinds(version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4)
+    __host__ __device__ bool kind2_legal() const { return (kinds() >> 2 & 1u) != 0; }
+    __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
+    __host__ __device__ bool kind4_legal() const { return (kinds() >> 4 & 1u) != 0; }
+    __host__ __device__ bool kind5_legal() const { return (kinds() >> 5 & 1u) != 0; }
+    // the CT_READS_* bit a plan must have to speak this version (0: every plan does)
+    __host__ __device__ uint32_t reads() const
+    {
+        return version == CT_VERSION_SPARSE ? CT_READS_SPARSE : version == CT_VERSION_RUNS ? CT_READS_RUNS :
+               version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO : 0u;
+    }
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 struct CtLegal { uint32_t version, flags, elems; };
-constexpr uint32_t CT_NLEGAL = 10;
+constexpr uint32_t CT_NLEGAL = 12;
 __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 {
     constexpr CtLegal L[CT_NLEGAL] = {
@@ -197,7 +220,8 @@ __host__ __device__ inline CtLegal ct_legal(uint32_t i)
         {CT_VERSION_DELTA, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_SPARSE, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_RUNS, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_ANS, 0, CT_NO_FILTER | CT_ELEMS},
-        {CT_VERSION_ANS, CT_FLAG_DELTA, CT_ELEMS}};
+        {CT_VERSION_ANS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_AUTO, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_AUTO, CT_FLAG_DELTA, CT_ELEMS}};
     return L[i];
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
@@ -214,9 +238,6 @@ constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 r
 constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
 constexpr uint32_t CT_KIND_ANS = 5;                          // rANS order-0 record (ans.hip): chunk unit counts, then every chunk's 64 states and units; version 7
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
-// what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
-// its rANS mode version 7
-constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4;
 
 // failure classes of glcContainerLastError (out[0])
 enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
@@ -298,7 +319,7 @@ struct CtWalkEnd { uint32_t what; unsigned long long frame; };            // fra
 
 // fetch(dst, pos, bytes, frame) -> bool brings 32 or 16 header bytes into dst; on_header(h, fmt, block_len, total),
 // on_frame(fi, fh, ref) and on_trailer(tr, frames) -> bool see what has passed its checks.  `reader` (CT_READS_*) is the plan's
-// sparse, runs and rANS modes (a plan with all off is a version-4 reader), plan_n its block length.
+// sparse, runs, rANS and auto modes (a plan with all off is a version-4 reader), plan_n its block length.
 template <class Fetch, class OnHeader, class OnFrame, class OnTrailer>
 __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long long len, uint32_t plan_n, uint32_t reader, Fetch fetch,
                                              OnHeader on_header, OnFrame on_frame, OnTrailer on_trailer)
@@ -310,8 +331,7 @@ __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long l
     CtFormat fmt;
     if (!fetch(hdr, 0ull, CT_HDR, none)) return {CT_WALK_STOPPED, none};
     if (!check_stream_header(C, hdr, &fmt, &block_len, &total)) return {CT_STREAM_HEADER, none};
-    if ((fmt.kind3_legal() && !(reader & CT_READS_SPARSE)) || (fmt.kind4_legal() && !(reader & CT_READS_RUNS)) ||
-        (fmt.kind5_legal() && !(reader & CT_READS_ANS))) return {CT_STREAM_HEADER, none};
+    if (fmt.reads() && !(reader & fmt.reads())) return {CT_STREAM_HEADER, none};
     if (!on_header(hdr, fmt, block_len, total)) return {CT_WALK_STOPPED, none};
     unsigned long long pos = CT_HDR, done = 0;
     uint32_t fi = 0;
@@ -363,10 +383,15 @@ bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, u
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
 // mode (only ever on with the shuffle on), the codec (CT_CODEC_*), its sparse mode (only ever on with the order-0 codec), its
-// runs mode (only ever on with the BWT codec) and its rANS mode (only ever on with the order-0 codec and the sparse mode off)
+// runs mode (only ever on with the BWT codec), its rANS mode (only ever on with the order-0 codec and the sparse mode off) and
+// its auto mode (only ever on with the order-0 codec and both of those off; as a reader it implies them)
 struct CtSettings {
-    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false, ans = false;
-    uint32_t reader() const { return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u) | (ans ? CT_READS_ANS : 0u); }
+    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false, ans = false, autom = false;
+    uint32_t reader() const
+    {
+        return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u) | (ans ? CT_READS_ANS : 0u) |
+               (autom ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : 0u);
+    }
 };
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
@@ -434,6 +459,12 @@ struct CtEncAns {                                          // device scratch of 
     uint8_t *tab;                                          // [rows] ANS_TAB_BYTES
     AnsScratch sc;                                         // [rows * ans_chunks(n)] slots: about 2 * rows * n bytes
 };
+struct CtEncAuto {                                         // device scratch of the auto mode, behind CtEncSparse's and CtEncAns's (allocated once it is on)
+    uint32_t *uniform;                                     // [rows][256] the probe's chunk counts
+    uint32_t *hist_s;                                      // [rows][256] candidate S's counts: the block's, or K's where S is kind 3
+    uint32_t *wa, *pick5;                                  // [rows] the estimate wA; 1 = the block is coded as kind 5
+    uint32_t *skip_ans;                                    // [rows] 1 = not rANS-coded; behind the kinds: 1 = no kind-5 record to place
+};
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 // the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
 // mask (1 = raw) and f.bwt zeros
@@ -461,6 +492,23 @@ hipError_t ct_enc_runs_place(hipStream_t st, const CtEncFrame &f, const CtEncRun
 // the rANS mode's ct_enc_kind0 (ans.hip), behind ans_encode: record sizes from the chunks' unit counts, kind 5 or raw when
 // 4 * words >= blk_len; f.only becomes ans_place's skip mask (1 = raw) and f.bwt zeros
 hipError_t ct_enc_ans_kind(hipStream_t st, const CtEncFrame &f, const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+// the probe (auto.hip): hist[i][256] and uniform[i][256] of segment i = data + data_off[i], min(data_len[i], max_len) bytes
+// (max_len <= 2^20), uniform[i][v] = its 64-byte chunks, counted from the segment's start, that hold byte v alone (the short last
+// chunk included when it does).  The rows need not be zeroed.  Everything only enqueues on `st`.
+hipError_t probe_segments(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                          uint32_t count, uint32_t max_len, uint32_t *hist, uint32_t *uniform);
+// the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
+// block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
+// read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the
+// skip masks of the mask / compaction passes (sp.skip_move) and of the rANS coder (au.skip_ans), and f.hist made K's where a
+// block stays kind 3 (sp.is3 stays the candidate's: a block is kind 3 when it is set and au.pick5 is not).  Behind the passes: ct_enc_sparse_kind's and ct_enc_ans_kind's sibling (actual sizes, the raw
+// rule, f.only = the Huffman encoder's skip mask, au.skip_ans = the placing kernel's)
+hipError_t ct_enc_auto_candidates(hipStream_t st, const SpSegs &g, const CtEncSparse &sp, const CtEncAuto &au, const uint32_t *hist,
+                                  const uint8_t *ans_tab, unsigned long long *in_off, unsigned long long *in_len);
+hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
+                              uint32_t nb, uint32_t blk_len);
+hipError_t ct_enc_auto_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
+                            const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
@@ -479,13 +527,13 @@ struct CtDecHuff0 {                                        // device scratch of 
     uint16_t *lut;                                         // [nb][2048]
     void *work;                                            // hdb_decode_work_bytes(chunk, blk_len)
     uint32_t chunk;                                        // blocks one hdb_decode call may take
-    // version 5 (max_kind 3): what the verdict leaves for the kind-3 blocks -- K's place in `kept` (block b in slot b % chunk)
+    // version 5 (kind 3 legal; version 8 as well): what the verdict leaves for the kind-3 blocks -- K's place in `kept` (block b in slot b % chunk)
     // and length, where the stream starts behind the mask, and 1 = nothing to decode (not kind 3, or nothing kept)
-    uint32_t max_kind;
+    uint32_t kinds;                                        // the format's legal kinds (ct_kinds)
     unsigned long long *k_off, *k_len, *u_off;             // [nb]
     uint32_t *skip3;                                       // [nb]
     uint8_t *kept; uint32_t kept_stride;                   // [chunk][kept_stride]
-    // version 6 (max_kind 4): the fields above serve A of the kind-4 blocks (k_off / k_len / u_off / skip3 / kept: A's place,
+    // version 6 (kind 4 legal): the fields above serve A of the kind-4 blocks (k_off / k_len / u_off / skip3 / kept: A's place,
     // length, stream start, 1 = not kind 4); these are B's, the tables of B (built from the counts in the record before the
     // verdict: hist_b, skip_tb) and the decoder's MTF rows the join writes (block b in row b % chunk)
     unsigned long long *b_off, *b_len, *ub_off, *nun_b;    // [nb]
@@ -495,7 +543,7 @@ struct CtDecHuff0 {                                        // device scratch of 
     uint8_t *kept_b;                                       // [chunk][kept_stride]
     unsigned long long *m_off, *m_len;                     // [nb]
     uint8_t *mtf; size_t mtf_stride;
-    // version 7 (max_kind 5): the tables of the kind-5 blocks of one decoder chunk (block b in slot b % chunk), built from the
+    // version 7 (kind 5 legal; version 8 as well): the tables of the kind-5 blocks of one decoder chunk (block b in slot b % chunk), built from the
     // verified histograms behind the verdict
     uint8_t *ans_tab;                                      // [chunk] ANS_TAB_BYTES
 };
@@ -503,7 +551,7 @@ struct CtDecHuff0 {                                        // device scratch of 
 // whose table is built from them
 hipError_t ct_dec_runs_hist(hipStream_t st, const uint8_t *frame, uint32_t nb, uint32_t blk_len, unsigned long long payload_words,
                             const CtDecHuff0 &h0);
-// h0 (version 3 and later, else null): kind 2 is legal, and kind 3 where h0->max_kind says so; its blocks' tables are built from the unverified histograms first, and the
+// h0 (version 3 and later, else null): kind 2 is legal, and kinds 3 to 5 where h0->kinds says so; its blocks' tables are built from the unverified histograms first, and the
 // units they ask for are one of the block's field checks
 hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
                          unsigned long long payload_words, const CtDecHuff0 *h0 = nullptr, KernelProf *prof = nullptr);

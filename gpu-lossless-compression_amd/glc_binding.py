@@ -659,6 +659,7 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcZeroRunSplitSegments", "glcZeroRunJoinSegments", "glcPlanSetContainerRuns", "glcPlanGetContainerRuns",
                      "glcAnsEncodeSegments", "glcAnsDecodeSegments", "glcAnsSegmentsWorkBytes", "glcAnsBoundWords",
                      "glcPlanSetContainerAns", "glcPlanGetContainerAns",
+                     "glcProbeSegments", "glcPlanSetContainerAuto", "glcPlanGetContainerAuto",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -723,6 +724,9 @@ def _ct():
         L.glcAnsSegmentsWorkBytes.restype = sz
         L.glcAnsBoundWords.argtypes = [sz]
         L.glcAnsBoundWords.restype = sz
+        L.glcPlanSetContainerAuto.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerAuto.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L._ct_ready = True
     return L
 
@@ -873,6 +877,40 @@ def container_get_ans(plan):
     d = C.c_uint(0)
     _chk("glcPlanGetContainerAns", _ct().glcPlanGetContainerAns(plan.handle, C.byref(d)))
     return int(d.value)
+
+
+def container_set_auto(plan, on):
+    """the auto mode of the plan's container ENCODER (format version 8: a kind per block out of 2, 3 and 5, from one probe pass):
+    True / 1 needs the order-0 codec and the sparse and rANS modes off; container_set_codec(plan, CONTAINER_CODEC_BWT) also
+    switches it off.  It is also the version the plan reads: on, versions 1 to 5, 7 and 8; off, a version-8 stream is a
+    stream-header failure as it always was."""
+    _chk("glcPlanSetContainerAuto", _ct().glcPlanSetContainerAuto(plan.handle, int(on)))
+
+
+def container_get_auto(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerAuto", _ct().glcPlanGetContainerAuto(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None, stream=None):
+    """the probe of the auto mode over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in:
+    (hist, uniform), int32 tensors [count, 256] -- the byte counts, and per byte value the 64-byte chunks (cut from the segment's
+    start) made of that byte alone.  hist / uniform: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev = d_in.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    n = off.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    hist = torch.empty((max(1, n), 256), dtype=torch.int32, device=dev) if hist is None else hist
+    uniform = torch.empty((max(1, n), 256), dtype=torch.int32, device=dev) if uniform is None else uniform
+    assert hist.is_contiguous() and uniform.is_contiguous() and hist.numel() >= 256 * n and uniform.numel() >= 256 * n
+    _chk("glcProbeSegments", _ct().glcProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, hist.data_ptr(),
+                                                     uniform.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return hist[:n], uniform[:n]
 
 
 def ans_bound_words(length):

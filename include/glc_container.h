@@ -69,6 +69,23 @@
  * k_hdb_enc_* stood.  With the mode off the rates equal the parent commit's within the spread of the rounds.  The kernels alone:
  * encode 782 GB/s, decode 968, a device-to-device copy 2674.
  *
+ * Mixtures, and callers who do not know their data: the auto mode of the order-0 codec, off by default.  The sparse mode stops at
+ * 5.223 on scattered skew where rANS reaches 7.648, rANS gets 38.96 on regular-step timestamps where the sparse mode gets 44.30, and
+ * a frame of typed data behind delta + shuffle holds planes of both sorts and planes of noise.  With glcPlanSetContainerAuto on, one
+ * probe pass over a frame (glcProbeSegments) gives every block's byte counts and its 64-byte chunks of one byte, and each block
+ * is coded as the smaller of what the sparse mode's writer would make of it (kinds 3, 2, 1; size known exactly from the counts)
+ * and an rANS record (kind 5; size estimated from the counts by integer arithmetic); the mask, compaction and rANS passes run only on
+ * the blocks that chose them.  The stream is format version 8, whose frames may mix kinds 0, 1, 2, 3 and 5; no record changes.  The
+ * model's sizes are in INTEGRATION.md 4b ("auto: when"): never below the better of the two modes on nine inputs, above both on
+ * mixed frames (int64 timestamps 6.412 against 6.188 and 6.261).  A plan with the mode on reads versions 1 to 5, 7 and 8: it is the
+ * one reader for everything the order-0 codec has written.  Measured on one MI355X on 1 GiB of device-generated data in 1 MiB
+ * blocks, rows 512 (profiles/auto_mode.md; ratio / encode / decode GB/s, medians of 5 interleaved rounds): int64 timestamps with
+ * delta + shuffle 8, sparse 6.771 / 449 / 172, rANS 6.809 / 383 / 353, auto 7.008 / 396 / 291; uint32 counters with delta +
+ * shuffle 4, sparse 9.999 / 450 / 198, rANS 9.835 / 387 / 360, auto 10.218 / 401 / 301; scattered 90 % zeros, sparse 5.677 / 470 /
+ * 169, rANS 8.670 / 489 / 441, auto 8.670 / 472 / 443.  With the mode off the sizes equal the parent commit's and the rates differ
+ * from it by no more than two runs of one build do.  The probe alone: 4864 GB/s on zeros, 3356 on scattered skew, 4038 on noise, where
+ * the call that holds the histogram pass alone moves 4081, 3070 and 3724; a device-to-device copy 2584.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -339,6 +356,40 @@ CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on);
  * plan and freed with it.  The new kernels have no slot in the plan's kernel profile. */
 CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on);
+
+/* The probe of the auto mode as a batched call (csrc/auto.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of its
+ * base, at most GLC_PROBE_MAX_LEN bytes at any byte alignment.  One pass over it writes row i of d_hist, its 256 byte counts, and
+ * row i of d_uniform: d_uniform[256 i + v] is the number of its 64-byte chunks -- cut from the segment's start, not by address;
+ * the last may be short -- whose bytes all equal v.  The rows (256 words each) need not be zeroed by the caller.  The call only
+ * enqueues on `stream`.  A bad argument (a null pointer with count > 0, rows not 4-byte aligned, the two row arrays equal, a
+ * maxLen or count too large) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_PROBE_MAX_LEN ((size_t)1 << 20)
+#define GLC_PROBE_MAX_COUNT ((size_t)1 << 22)
+CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                             size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_uniform, void *stream);
+
+/* The auto mode of the ENCODER's order-0 codec: on = 1 writes format version 8, whose frames may hold kinds 0, 1, 2, 3 and 5 in any
+ * mix (not 4), and picks a kind per block from the block's statistics alone ("the auto mode's rule").  One probe
+ * pass gives every block's byte counts H and, per byte value, its 64-byte chunks of that byte alone.  Candidate S is what the sparse
+ * mode's writer would make (kind 3, 2 or 1) and wS its exact words, known from the counts and the Huffman tables' code lengths;
+ * candidate A is kind 5 and wA = 65 * ceil(n / 32768) + ceil(sum H[s] * (12 - log2 q[s]) / 32) an estimate of its words, with the
+ * logarithm in 1/256 bit rounded up by exact integer arithmetic (csrc/auto_rule.h).  The block is coded as kind 5 when wA < wS and
+ * then falls under kind 5's raw rule on its actual words; otherwise it is candidate S.  Every record and every reader check is
+ * that of the version that introduced its kind.  The mask and compaction passes then run on the kind-3 blocks only, the rANS
+ * coder on the kind-5 blocks only, the Huffman encoder on kind 2 and on the kept bytes of kind 3.  0 (the default) writes versions
+ * 1 to 7 byte for byte as ever.  on = 1 needs the codec GLC_CONTAINER_CODEC_HUFF0 with the sparse and the rANS mode off: on = 1
+ * without that, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was;
+ * glcPlanSetContainerCodec(plan, GLC_CONTAINER_CODEC_BWT) also switches it off, and glcPlanSetContainerSparse(plan, 1) and
+ * glcPlanSetContainerAns(plan, 1) are refused while it is on.  All six container entry points, the index and the range reads
+ * honour it, with pipelining on or off and with any filter setting.  The setting is also the version the plan speaks: a plan with
+ * it on reads versions 1 to 5, 7 and 8 -- everything the order-0 codec has ever written -- and refuses version 6; every other
+ * plan refuses a version-8 stream as a stream-header failure, as it did before version 8 existed.  The first auto encode allocates
+ * the scratch of the sparse and of the rANS mode together -- about 3 * rows * n bytes (rows * n of compaction space, 2 * rows * n
+ * of chunk slots) plus the masks and 6 KiB of rANS tables and 2 KiB of probe counts per row -- and the first version-8 decode what
+ * a version-5 and a version-7 decode allocate; both are kept with the plan and freed with it.  The new kernels have no slot in the
+ * plan's kernel profile. */
+CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -22,7 +22,8 @@ the order-0 codec for both settings.
 order-0 codec, and R interleaved rounds of encode and decode timed with device events -- with --sparse each round runs the sparse
 mode off and then on (glcPlanSetContainerSparse, format version 5), without it only off, which is also what a build without the
 mode can run; with --ans each round also runs the rANS mode (glcPlanSetContainerAns, format version 7), so that one run interleaves
-the settings off, sparse and ans.  --data skew90 is the scattered-skew input (90 % zeros, the rest uniform in 1 .. 15, no filter).
+the settings off, sparse and ans; with --auto each round also runs the auto mode (glcPlanSetContainerAuto, format version 8),
+interleaved with the others.  --data skew90 is the scattered-skew input (90 % zeros, the rest uniform in 1 .. 15, no filter).
 Every round's rates are reported, with their median and spread (max - min) per setting.
 
 --runs (with --data textlike or loglike, generated on the device; --rounds R, at least 1) is the runs section: the BWT codec with its
@@ -33,7 +34,7 @@ device-to-device copy.  --runs-off-only runs the same section without ever touch
 it can run.
 
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]
-                                [--rounds R] [--sparse] [--ans] [--runs | --runs-off-only]"""
+                                [--rounds R] [--sparse] [--ans] [--auto] [--runs | --runs-off-only]"""
 import argparse
 import json
 import os
@@ -255,8 +256,9 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
     return res
 
 
-def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse, with_ans=False):
-    """the order-0 container with its modes off, (with_sparse) the sparse mode on and (with_ans) the rANS mode on, interleaved:
+def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse, with_ans=False, with_auto=False):
+    """the order-0 container with its modes off, (with_sparse) the sparse mode on, (with_ans) the rANS mode on and (with_auto) the
+    auto mode on, interleaved:
     `rounds` rounds of one encode and one decode per setting after one untimed round, each timed with device events on the plan's
     (the default) stream"""
     n = plan.n
@@ -267,7 +269,7 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
     glc.container_set_shuffle(plan, elem)
     if elem and delta:
         glc.container_set_delta(plan, 1)
-    settings = ["off"] + (["sparse"] if with_sparse else []) + (["ans"] if with_ans else [])
+    settings = ["off"] + (["sparse"] if with_sparse else []) + (["ans"] if with_ans else []) + (["auto"] if with_auto else [])
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
 
     def event_timed(fn):
@@ -281,12 +283,16 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
 
     for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
         for s in settings:
+            if with_auto:
+                glc.container_set_auto(plan, 0)                # (the modes exclude each other: off before another goes on)
             if with_ans:
-                glc.container_set_ans(plan, 0)                 # (the two modes exclude each other: off before the other goes on)
+                glc.container_set_ans(plan, 0)
             if with_sparse:
                 glc.container_set_sparse(plan, 1 if s == "sparse" else 0)
             if with_ans:
                 glc.container_set_ans(plan, 1 if s == "ans" else 0)
+            if with_auto:
+                glc.container_set_auto(plan, 1 if s == "auto" else 0)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -319,6 +325,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=0, help="typed data: the sparse section, this many interleaved rounds timed with device events")
     ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
     ap.add_argument("--ans", action="store_true", help="the sparse section also runs the order-0 codec's rANS mode (format version 7)")
+    ap.add_argument("--auto", action="store_true", help="the sparse section also runs the order-0 codec's auto mode (format version 8)")
     ap.add_argument("--runs", action="store_true", help="text-like data: the runs section, the BWT codec's runs mode off and on (format version 6)")
     ap.add_argument("--runs-off-only", action="store_true", help="the runs section without the mode (what a build without it can run)")
     args = ap.parse_args()
@@ -374,7 +381,7 @@ def main():
             if args.rounds:
                 assert args.codec == 1, "the sparse section is the order-0 codec's"
                 res["sparse"] = sparse_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.delta, args.rounds,
-                                               args.sparse, args.ans)
+                                               args.sparse, args.ans, args.auto)
             else:
                 res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
         print(json.dumps(res))
