@@ -24,6 +24,15 @@ constexpr uint32_t HUFF_BLOCK      = 4096;       // HUFF_THREADS_PER_BLOCK*HUFF_
 constexpr uint32_t HUFF_SYMS       = 257;        // HUFF_NUM_CHARS (cudpp_globals.h:62)
 constexpr uint32_t HUFF_MAX_WORDS  = 1536;       // HUFF_CODE_BYTES (cudpp_globals.h:66)
 constexpr uint32_t MTF_CHUNK       = 4096;       // bytes of BWT output per wave in the MTF kernels
+// Histogram of a 4096-symbol sub-block (HuffScratch::sub_hist): no count passes 4096, so a count is a 16-bit half.  Dword j
+// holds rank j in its low half and rank j + 128 in its high half (the layout of k_mtf_encode's LDS counters, which leave as
+// they stand).  A block's total reaches 2^20: k_huff_build unpacks before it adds.  (GLC_SUBHIST_WIDE: A/B, a dword per count)
+#ifdef GLC_SUBHIST_WIDE
+constexpr uint32_t SUBHIST_DWORDS  = 256;
+#else
+constexpr uint32_t SUBHIST_DWORDS  = 128;
+#endif
+constexpr bool     SUBHIST_PACKED  = SUBHIST_DWORDS == 128;
 
 // fast suffix sorters (bwt_bucket.hip, bwt_sample.hip): buckets of FS_AVG suffixes on average, FS_CAP words of slot each
 constexpr uint32_t FS_AVG   = 2048;
@@ -419,7 +428,7 @@ hipError_t mtf_scratch_alloc(MtfScratch &s, uint32_t nmax, uint32_t rows);
 void       mtf_scratch_free(MtfScratch &s);
 
 // out = MTF(in) per block; if sub_hist != nullptr also writes the histogram of
-// each 4096-symbol chunk of the output: sub_hist[b][chunk][256].
+// each 4096-symbol chunk of the output: sub_hist[b][chunk][SUBHIST_DWORDS].
 hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint32_t n, uint32_t nblk,
                        uint8_t *out, size_t out_stride, MtfScratch &s, uint32_t *sub_hist, const uint32_t *only = nullptr,
                        bool skewed = false);
@@ -433,7 +442,7 @@ hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint
 struct HuffScratch {
     KernelProf *prof = nullptr;
     uint32_t nmax = 0, rows = 0, max_sub = 0;
-    uint32_t *sub_hist = nullptr;    // [rows][max_sub][256]
+    uint32_t *sub_hist = nullptr;    // [rows][max_sub][SUBHIST_DWORDS]
     uint32_t *codes = nullptr;       // [rows][257]
     uint32_t *lens = nullptr;        // [rows][257]  (one word each for aligned LDS staging)
     size_t    bytes = 0;

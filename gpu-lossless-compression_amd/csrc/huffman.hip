@@ -55,7 +55,7 @@ __global__ __launch_bounds__(HB_NT) void k_huff_build(const uint32_t *__restrict
                                                     const uint32_t *__restrict__ only)
 {
     static_assert(HB_NT == 256 || HB_NT == 512 || HB_NT == 1024, "k_huff_build: 256, 512 or 1024 threads");
-    constexpr int HB_PARTS = HB_NT / 256, HB_NW = HB_NT / 64;
+    constexpr int HB_PARTS = HB_NT / SUBHIST_DWORDS, HB_NW = HB_NT / 64;
     __shared__ uint32_t s_hist[257];
     __shared__ uint32_t s_part[HB_PARTS][256];
     __shared__ HuffTreeLds T;
@@ -67,23 +67,28 @@ __global__ __launch_bounds__(HB_NT) void k_huff_build(const uint32_t *__restrict
     if (only && !only[b]) return;                              // (second pass over the blocks a later sorter tier rewrote)
     const uint32_t w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    const uint32_t *SH = sub_hist + (size_t)b * max_sub * 256;
+    const uint32_t *SH = sub_hist + (size_t)b * max_sub * SUBHIST_DWORDS;
     HB_STAMP(0);
 
     // ---- total histogram (huffman_build_tree_kernel merges partial histograms,
     //      compress_kernel.cuh:2284-2299; EOF gets count 1, :2250) ----
     {
-        // thread = (symbol, part of the sub-blocks), 16 loads in flight
-        const uint32_t sym = tid & 255, qt = tid >> 8;
-        uint32_t c = 0;
+        // thread = (dword of the sub-histograms, part of the sub-blocks), 16 loads in flight.  Packed: a dword's halves are
+        // two symbols' counts, added up apart (sixteen sub-blocks of one symbol already pass 16 bits)
+        const uint32_t j = tid % SUBHIST_DWORDS, qt = tid / SUBHIST_DWORDS;
+        uint32_t c = 0, ch = 0;
         for (uint32_t s = qt * 16; s < nsub; s += 16 * HB_PARTS) {
             uint32_t v[16];
 #pragma unroll
-            for (int k = 0; k < 16; k++) v[k] = s + k < nsub ? SH[(size_t)(s + k) * 256 + sym] : 0u;
+            for (int k = 0; k < 16; k++) v[k] = s + k < nsub ? SH[(size_t)(s + k) * SUBHIST_DWORDS + j] : 0u;
 #pragma unroll
-            for (int k = 0; k < 16; k++) c += v[k];
+            for (int k = 0; k < 16; k++) {
+                if constexpr (SUBHIST_PACKED) { c += v[k] & 0xFFFFu; ch += v[k] >> 16; }
+                else c += v[k];
+            }
         }
-        s_part[qt][sym] = c;
+        s_part[qt][j] = c;
+        if constexpr (SUBHIST_PACKED) s_part[qt][j + 128] = ch;
     }
     __syncthreads();
     if (tid < 256) {
@@ -132,18 +137,25 @@ __global__ __launch_bounds__(HB_NT) void k_huff_build(const uint32_t *__restrict
         uint32_t ln[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) ln[r] = s_len[r * 64 + l];
-        for (uint32_t s0 = w; s0 < 256; s0 += 4 * HB_NW) {     // four sub-blocks of this wave at a time: 16 loads in flight
-            uint32_t h[4][4];
+        // four (packed: eight) sub-blocks of this wave at a time: 16 loads in flight.  Packed: dword r * 64 + l holds ranks
+        // r * 64 + l and r * 64 + l + 128
+        constexpr int HB_SB = 16 * 64 / SUBHIST_DWORDS, HB_DW = SUBHIST_DWORDS / 64;
+        for (uint32_t s0 = w; s0 < 256; s0 += HB_SB * HB_NW) {
+            uint32_t h[HB_SB][HB_DW];
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
+            for (int k = 0; k < HB_SB; k++) {
                 const uint32_t sb = s0 + HB_NW * k;
 #pragma unroll
-                for (int r = 0; r < 4; r++) h[k][r] = sb < nsub ? SH[(size_t)sb * 256 + r * 64 + l] : 0u;
+                for (int r = 0; r < HB_DW; r++) h[k][r] = sb < nsub ? SH[(size_t)sb * SUBHIST_DWORDS + r * 64 + l] : 0u;
             }
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
+            for (int k = 0; k < HB_SB; k++) {
                 const uint32_t sb = s0 + HB_NW * k;
-                uint32_t bits = h[k][0] * ln[0] + h[k][1] * ln[1] + h[k][2] * ln[2] + h[k][3] * ln[3];
+                uint32_t bits;
+                if constexpr (SUBHIST_PACKED)
+                    bits = (h[k][0] & 0xFFFFu) * ln[0] + (h[k][1] & 0xFFFFu) * ln[1] + (h[k][0] >> 16) * ln[2] + (h[k][1] >> 16) * ln[3];
+                else
+                    bits = h[k][0] * ln[0] + h[k][1] * ln[1] + h[k][2 % HB_DW] * ln[2] + h[k][3 % HB_DW] * ln[3];
                 bits = wave_sum(bits);
                 if (l == 0) s_words[sb] = (sb < nsub) ? (bits + 31) / 32 : 0u;
             }
@@ -175,6 +187,11 @@ __global__ __launch_bounds__(HB_NT) void k_huff_build(const uint32_t *__restrict
 // table per 4 KB of symbols, was most of what the kernel did).
 constexpr uint32_t HP_SUBS = 4;
 
+// FULLBLK (chosen by huff_pack when n is a multiple of HP_SUBS * HUFF_BLOCK and every sub-block starts 16-byte aligned -- the
+// 1 MiB blocks of the hot path): every workgroup has HP_SUBS whole sub-blocks, so there is no symbol count, no per-symbol
+// guard and no byte-loop arm, the sub-block loop has a fixed trip count and the table look-ups take their byte straight from
+// the four loaded dwords.  Every other n or base runs the guarded instance.  (GLC_HP_NO_FULL: A/B, the guarded one always)
+template <bool FULLBLK>
 __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ mtf, size_t mtf_stride, uint32_t n,
                                                    const uint32_t *__restrict__ codes,
                                                    const uint32_t *__restrict__ lens,
@@ -192,7 +209,7 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ m
     __shared__ uint32_t s_tmp[8];
     const uint32_t b = blockIdx.y, tid = threadIdx.x;
     if (only && !only[b]) return;
-    if (blockIdx.x * HP_SUBS * HUFF_BLOCK >= n) return;
+    if (!FULLBLK && blockIdx.x * HP_SUBS * HUFF_BLOCK >= n) return;
     bool mylong = false;
     for (uint32_t i = tid; i < 257; i += 256) {
         const uint2 cl1 = make_uint2(codes[(size_t)b * 257 + i], lens[(size_t)b * 257 + i]);
@@ -208,31 +225,42 @@ __global__ __launch_bounds__(256) void k_huff_pack(const uint8_t *__restrict__ m
     const bool pairs = __syncthreads_or((int)mylong) == 0;     // (uniform)
 #endif
     const uint64_t base = block_off ? block_off[b] : 0ull;
-    for (uint32_t sub = blockIdx.x * HP_SUBS; sub < (blockIdx.x + 1) * HP_SUBS; sub++) {
+    const uint32_t sub0 = blockIdx.x * HP_SUBS;
+    for (uint32_t sub = sub0; FULLBLK ? sub != sub0 + HP_SUBS : sub < (blockIdx.x + 1) * HP_SUBS; sub++) {
         const uint32_t lo = sub * HUFF_BLOCK;
-        if (lo >= n) break;
-        const uint32_t cntb = min((uint32_t)HUFF_BLOCK, n - lo);
+        if (!FULLBLK && lo >= n) break;
+        const uint32_t cntb = min((uint32_t)HUFF_BLOCK, n - lo);   // (FULLBLK: not used)
         __syncthreads();                                       // the table is in place / the previous sub-block's words have been read
 
         const uint8_t *src = mtf + (size_t)b * mtf_stride + lo;
-        uint8_t sym[SPT];
         const uint32_t i0 = tid * SPT;
-        if (i0 + SPT <= cntb && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+        uint2 cl[SPT];                                         // read once, used by the bit count and by the merge
+        uint32_t mybits = 0;
+        if constexpr (FULLBLK) {
             const uint4 q = *reinterpret_cast<const uint4 *>(src + i0);
             const uint32_t qq[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-            for (int j = 0; j < SPT; j++) sym[j] = (uint8_t)(qq[j >> 2] >> (8 * (j & 3)));
+            for (int j = 0; j < SPT; j++) {
+                cl[j] = s_cl[(qq[j >> 2] >> (8 * (j & 3))) & 0xFFu];
+                mybits += cl[j].y;
+            }
         } else {
+            uint8_t sym[SPT];
+            if (i0 + SPT <= cntb && ((reinterpret_cast<uintptr_t>(src) & 15) == 0)) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(src + i0);
+                const uint32_t qq[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-            for (int j = 0; j < SPT; j++) sym[j] = (i0 + j < cntb) ? src[i0 + j] : 0;
-        }
-        uint2 cl[SPT];                                         // read once, used by the bit count and by the merge
-        uint32_t mybits = 0;
+                for (int j = 0; j < SPT; j++) sym[j] = (uint8_t)(qq[j >> 2] >> (8 * (j & 3)));
+            } else {
 #pragma unroll
-        for (int j = 0; j < SPT; j++) {
-            cl[j] = s_cl[sym[j]];
-            if (i0 + j >= cntb) cl[j] = make_uint2(0u, 0u);
-            mybits += cl[j].y;
+                for (int j = 0; j < SPT; j++) sym[j] = (i0 + j < cntb) ? src[i0 + j] : 0;
+            }
+#pragma unroll
+            for (int j = 0; j < SPT; j++) {
+                cl[j] = s_cl[sym[j]];
+                if (i0 + j >= cntb) cl[j] = make_uint2(0u, 0u);
+                mybits += cl[j].y;
+            }
         }
         uint32_t total = 0;
         const uint32_t start = block_excl_add<256>(mybits, s_tmp, &total);
@@ -374,7 +402,7 @@ hipError_t expand_streams(hipStream_t st, const uint32_t *d_in, const unsigned l
 hipError_t huff_scratch_alloc(HuffScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_sub = (nmax + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    size_t a = (size_t)rows * s.max_sub * 256 * 4, c = (size_t)rows * 257 * 4;
+    size_t a = (size_t)rows * s.max_sub * SUBHIST_DWORDS * 4, c = (size_t)rows * 257 * 4;
     GLC_TRY(hipMalloc((void **)&s.sub_hist, a));
     GLC_TRY(hipMalloc((void **)&s.codes, c));
     GLC_TRY(hipMalloc((void **)&s.lens, c));
@@ -407,8 +435,9 @@ __global__ __launch_bounds__(256) void k_sub_hist(const uint8_t *__restrict__ sy
     uint32_t *H = s_h[w] + (l & 3) * 257;
     for (uint32_t i = lo + l; i < hi; i += 64) atomicAdd(&H[S[i]], 1u);
     __builtin_amdgcn_wave_barrier();
-    uint32_t *O = sub_hist + ((size_t)b * max_sub + sub) * 256;
-    for (uint32_t i = l; i < 256; i += 64) O[i] = s_h[w][i] + s_h[w][257 + i] + s_h[w][514 + i] + s_h[w][771 + i];
+    uint32_t *O = sub_hist + ((size_t)b * max_sub + sub) * SUBHIST_DWORDS;
+    auto count = [&](uint32_t i) { return s_h[w][i] + s_h[w][257 + i] + s_h[w][514 + i] + s_h[w][771 + i]; };
+    for (uint32_t i = l; i < SUBHIST_DWORDS; i += 64) O[i] = SUBHIST_PACKED ? count(i) | (count(i + 128) << 16) : count(i);
 }
 
 hipError_t huff_histogram(hipStream_t st, const uint8_t *sym, size_t stride, uint32_t n, uint32_t nblk, HuffScratch &s)
@@ -450,11 +479,22 @@ hipError_t huff_pack(hipStream_t st, const uint8_t *mtf, size_t mtf_stride, uint
                      size_t capacity_words)
 {
     const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
+    const dim3 grid((nsub + HP_SUBS - 1) / HP_SUBS, nblk);
+    const uint64_t cap = d_block_off ? capacity_words : comp_stride_words;
+    // whole sub-blocks in every workgroup, each starting 16-byte aligned (the base is the caller's in glcHuffmanEncodeBatch)
+#ifdef GLC_HP_NO_FULL
+    const bool full = false;
+#else
+    const bool full = n % (HP_SUBS * HUFF_BLOCK) == 0 && (reinterpret_cast<uintptr_t>(mtf) & 15) == 0 && (mtf_stride & 15) == 0;
+#endif
     {
         ProfScope ps(s.prof, PROF_HUFF_PACK, st, (double)n * nblk);
-        hipLaunchKernelGGL(k_huff_pack, dim3((nsub + HP_SUBS - 1) / HP_SUBS, nblk), dim3(256), 0, st, mtf, mtf_stride, n, s.codes, s.lens,
-                           d_offsets, offset_stride, d_compressed, comp_stride_words,
-                           (uint64_t)(d_block_off ? capacity_words : comp_stride_words), only, d_block_off);
+        if (full)
+            hipLaunchKernelGGL(k_huff_pack<true>, grid, dim3(256), 0, st, mtf, mtf_stride, n, s.codes, s.lens, d_offsets,
+                               offset_stride, d_compressed, comp_stride_words, cap, only, d_block_off);
+        else
+            hipLaunchKernelGGL(k_huff_pack<false>, grid, dim3(256), 0, st, mtf, mtf_stride, n, s.codes, s.lens, d_offsets,
+                               offset_stride, d_compressed, comp_stride_words, cap, only, d_block_off);
     }
     return hipGetLastError();
 }

@@ -412,7 +412,9 @@ __device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ 
     mtf_full_group<WITH_HIST, ZEROS, true>(sb, db, voff, 16 * MTF_GROUP * (NGRP - 1), q, tab, bm, cum, hist, lr, row);
     if (WITH_HIST) {
         __builtin_amdgcn_wave_barrier();
-        for (int i = lr; i < 256; i += 16) H[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+        // (packed: the row's 16-bit counter pairs leave as they stand)
+        if constexpr (SUBHIST_PACKED) for (int i = lr; i < 128; i += 16) H[i] = hist[i];
+        else for (int i = lr; i < 256; i += 16) H[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
     }
 }
 
@@ -462,7 +464,7 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
         static_assert(!QUARTERS, "the rows of the FULL form are whole chunks");
         mtf_encode_full_row<WITH_HIST, ZEROS>(in + (size_t)b * in_stride, out + (size_t)b * out_stride, chunk * MTF_CHUNK,
                                               lists + ((size_t)b * max_chunks + chunk) * 256, s_tab[slot], s_bm[slot], s_cum[slot],
-                                              s_hist[WITH_HIST ? slot : 0], sub_hist + ((size_t)b * max_chunks + chunk) * 256, lr, row);
+                                              s_hist[WITH_HIST ? slot : 0], sub_hist + ((size_t)b * max_chunks + chunk) * SUBHIST_DWORDS, lr, row);
         return;
     }
     const uint32_t Cc0 = min(n, chunk0 * MTF_CHUNK + MTF_CHUNK) - chunk0 * MTF_CHUNK;   // length of the wave's first chunk
@@ -632,17 +634,20 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
     }
     if (WITH_HIST && QUARTERS) {
         __builtin_amdgcn_wave_barrier();
-        uint32_t *H = sub_hist + ((size_t)b * max_chunks + chunk0) * 256;
-        for (int i = l; i < 256; i += 64) {
+        uint32_t *H = sub_hist + ((size_t)b * max_chunks + chunk0) * SUBHIST_DWORDS;
+        for (int i = l; i < (int)SUBHIST_DWORDS; i += 64) {
             uint32_t c = 0;
+            // (packed: the four quarters' counter pairs add up as words -- a half's total is at most 4096, nothing carries)
 #pragma unroll
-            for (int r = 0; r < MTF_ROWS; r++) c += (s_hist[w * MTF_ROWS + r][i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+            for (int r = 0; r < MTF_ROWS; r++)
+                c += SUBHIST_PACKED ? s_hist[w * MTF_ROWS + r][i] : (s_hist[w * MTF_ROWS + r][i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
             H[i] = c;
         }
     } else if (WITH_HIST && live) {
         __builtin_amdgcn_wave_barrier();
-        uint32_t *H = sub_hist + ((size_t)b * max_chunks + chunk) * 256;
-        for (int i = lr; i < 256; i += 16) H[i] = (s_hist[slot][i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+        uint32_t *H = sub_hist + ((size_t)b * max_chunks + chunk) * SUBHIST_DWORDS;
+        if constexpr (SUBHIST_PACKED) for (int i = lr; i < 128; i += 16) H[i] = s_hist[slot][i];
+        else for (int i = lr; i < 256; i += 16) H[i] = (s_hist[slot][i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
     }
 }
 
