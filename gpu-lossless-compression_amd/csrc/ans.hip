@@ -15,7 +15,7 @@
 //                 beyond the chunk's count (or the record's end) reads as 0, nothing is read outside the record's words and
 //                 nothing written outside the segment.
 // Any length up to 2^20, any byte alignment of the segments; records are word-aligned.  The container's own step (record sizes,
-// raw rule) is the small kernel at the end.
+// the record rule) is k_ct_kind0 of container.hip.
 #include "container_internal.h"
 #include "glc_device.h"
 
@@ -260,22 +260,6 @@ __global__ __launch_bounds__(ANS_THREADS) void k_ans_decode(AnsSegs g, const uin
     }
 }
 
-// the rANS mode's ct_enc_kind0: record sizes from the chunks' counts, kind 5 or raw when 4 * words >= blk_len; f.only becomes
-// the placing kernel's skip mask (1 = raw) and f.bwt zeros
-__global__ __launch_bounds__(256) void k_ct_kind_ans(CtEncFrame f, AnsScratch sc, uint32_t nb, uint32_t blk_len, unsigned long long table_bytes,
-                                                     const CtEncState *state)
-{
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
-    if (b >= nb) return;
-    const unsigned long long words = ans_words_of(sc.counts + (size_t)b * sc.nch_max, ans_chunks(blk_len));
-    const bool raw = 4ull * words >= blk_len;
-    f.kind[b] = raw ? CT_KIND_RAW : CT_KIND_ANS;
-    f.only[b] = raw ? 1u : 0u;
-    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
-    f.bwt[b] = 0;
-}
-
 hipError_t ans_tables(hipStream_t st, const AnsSegs &g)
 {
     if (g.count == 0) return hipSuccess;
@@ -312,13 +296,6 @@ hipError_t ans_decode(hipStream_t st, const AnsSegs &g, const uint32_t *rec_base
 {
     if (g.count == 0 || g.max_len == 0) return hipSuccess;
     hipLaunchKernelGGL(k_ans_decode, ans_grid(g), dim3(ANS_THREADS), 0, st, g, rec_base, rec_off, rec_len);
-    return hipGetLastError();
-}
-
-hipError_t ct_enc_ans_kind(hipStream_t st, const CtEncFrame &f, const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state)
-{
-    const CtTables T = ct_tables(nb, blk_len);
-    hipLaunchKernelGGL(k_ct_kind_ans, dim3((nb + 255) / 256), dim3(256), 0, st, f, sc, nb, blk_len, 4 * T.words, state);
     return hipGetLastError();
 }
 

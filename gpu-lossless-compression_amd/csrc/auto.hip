@@ -12,7 +12,7 @@
 //                 E = uniform[fill], else kind 2) with K's counts and length from the statistics, and the estimate wA of the
 //                 block's rANS record from its counts and the q of its rANS table (auto_rule.h)
 //   k_au_choose   behind the Huffman tables of candidate S's counts: wS, the choice, the skip masks of the passes that follow
-//   k_au_kind     behind those passes: the actual record sizes, the raw rule, the encoders' skip masks
+// Behind those passes k_ct_kind0<auto> (container.hip) gives the actual record sizes and the encoders' skip masks.
 // Any segment length up to 2^20, any byte alignment.
 #include "container_internal.h"
 #include "glc_device.h"
@@ -164,14 +164,15 @@ __global__ __launch_bounds__(256) void k_au_cand(SpSegs g, CtEncSparse sp, CtEnc
     in_len[b] = is3 ? klen : L;
 }
 
-__global__ __launch_bounds__(256) void k_au_choose(CtEncFrame f, CtEncHuff0 h, CtEncSparse sp, CtEncAuto au, uint32_t nb, uint32_t blk_len)
+__global__ __launch_bounds__(256) void k_au_choose(CtEncFrame f, CtEncHuff0 h, CtEncSparse sp, CtEncAns an, CtEncAuto au, uint32_t nb,
+                                                   uint32_t blk_len)
 {
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= nb) return;
     const bool is3 = sp.is3[b] != 0;
     const unsigned long long klen = sp.klen[b];
     unsigned long long wS = is3 ? sp_mask_words(blk_len) + (klen ? h.nun[b] : 0ull) : h.nun[b];
-    if (4ull * wS >= blk_len) wS = ct_raw_words(blk_len);
+    if (ct_stored_raw(wS, blk_len)) wS = ct_raw_words(blk_len);
     const bool pick5 = auto_pick5(au.wa[b], wS);
     if (!pick5 && is3) {                                       // the block stays kind 3: its table counts are K's
 #pragma unroll
@@ -179,29 +180,8 @@ __global__ __launch_bounds__(256) void k_au_choose(CtEncFrame f, CtEncHuff0 h, C
     }
     if (lane) return;
     au.pick5[b] = pick5 ? 1u : 0u;
-    au.skip_ans[b] = pick5 ? 0u : 1u;
+    an.skip_ans[b] = pick5 ? 0u : 1u;
     sp.skip_move[b] = !pick5 && is3 ? 0u : 1u;
-}
-
-// ct_enc_sparse_kind and ct_enc_ans_kind in one: a block coded as kind 5 has the size its chunks' counts give, a block of
-// candidate S the size its table gave; the raw rule applies to whichever it is.  f.only = 1 where the Huffman encoder has nothing
-// to write (raw, kind 5, a kind-3 block with nothing kept), au.skip_ans = 1 where the rANS placing has not
-__global__ __launch_bounds__(256) void k_au_kind(CtEncFrame f, CtEncHuff0 h, CtEncSparse sp, CtEncAuto au, AnsScratch sc, uint32_t nb,
-                                                 uint32_t blk_len, unsigned long long table_bytes, const CtEncState *state)
-{
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
-    if (b >= nb) return;
-    const bool pick5 = au.pick5[b] != 0, is3 = !pick5 && sp.is3[b] != 0;
-    const unsigned long long klen = sp.klen[b];
-    const unsigned long long words = pick5 ? ans_words_of(sc.counts + (size_t)b * sc.nch_max, ans_chunks(blk_len))
-                                   : is3 ? sp_mask_words(blk_len) + (klen ? h.nun[b] : 0ull) : h.nun[b];
-    const bool raw = 4ull * words >= blk_len;
-    f.kind[b] = raw ? CT_KIND_RAW : pick5 ? CT_KIND_ANS : is3 ? CT_KIND_SPARSE : CT_KIND_HUFF0;
-    f.only[b] = raw || pick5 || (is3 && klen == 0) ? 1u : 0u;
-    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
-    f.bwt[b] = !raw && is3 ? (int)(sp.fill[b] & 255u) : 0;
-    au.skip_ans[b] = pick5 && !raw ? 0u : 1u;
 }
 
 hipError_t ct_enc_auto_candidates(hipStream_t st, const SpSegs &g, const CtEncSparse &sp, const CtEncAuto &au, const uint32_t *hist,
@@ -211,18 +191,10 @@ hipError_t ct_enc_auto_candidates(hipStream_t st, const SpSegs &g, const CtEncSp
     return hipGetLastError();
 }
 
-hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
-                              uint32_t nb, uint32_t blk_len)
+hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAns &an,
+                              const CtEncAuto &au, uint32_t nb, uint32_t blk_len)
 {
-    hipLaunchKernelGGL(k_au_choose, dim3((nb + 3) / 4), dim3(256), 0, st, f, h, sp, au, nb, blk_len);
-    return hipGetLastError();
-}
-
-hipError_t ct_enc_auto_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
-                            const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state)
-{
-    const CtTables T = ct_tables(nb, blk_len);
-    hipLaunchKernelGGL(k_au_kind, dim3((nb + 255) / 256), dim3(256), 0, st, f, h, sp, au, sc, nb, blk_len, 4 * T.words, state);
+    hipLaunchKernelGGL(k_au_choose, dim3((nb + 3) / 4), dim3(256), 0, st, f, h, sp, an, au, nb, blk_len);
     return hipGetLastError();
 }
 

@@ -177,12 +177,11 @@ __global__ void k_ct_header(uint8_t *out, unsigned long long cap, CtHdrWords h, 
     if (threadIdx.x == 0) { state->cursor = CT_HDR; state->crc_all = 0; state->frames = 0; state->frame_acc = 0; }
 }
 
-// per block (one wave each): raw when a sub-block needs more than HUFF_MAX_WORDS words or 4 * words >= blk_len; the record's
+// per block (one wave each): raw when a sub-block needs more than HUFF_MAX_WORDS words or under the record rule; the record's
 // words go to f.size (what the payload offsets are scanned from) and the packer's mask to f.only
 __global__ __launch_bounds__(256) void k_ct_kind(CtEncFrame f, uint32_t nb, uint32_t blk_len, unsigned long long table_bytes,
                                                  const CtEncState *state)
 {
-    if (blockIdx.x == 0 && threadIdx.x == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
     const uint32_t b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (b >= nb) return;
     const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
@@ -193,28 +192,29 @@ __global__ __launch_bounds__(256) void k_ct_kind(CtEncFrame f, uint32_t nb, uint
         const uint32_t nx = s + 1 < nsub ? eo[s + 1] : size;
         over |= nx - eo[s] - 1 > HUFF_MAX_WORDS;
     }
-    const bool raw = __any((int)over) || 4ull * size >= blk_len;
-    if (lane == 0) {
-        f.kind[b] = raw ? CT_KIND_RAW : CT_KIND_HUFF;
-        f.only[b] = raw ? 0u : 1u;
-        if (raw) f.size[b] = ct_raw_words(blk_len);
-    }
+    const bool any_over = __any((int)over);
+    if (lane) return;
+    const bool raw = ct_put_record(f, b, CT_KIND_HUFF, size, blk_len, table_bytes, state, any_over);
+    f.only[b] = raw ? 0u : 1u;
 }
 
-// the order-0 codec's kinds (one thread per block), from the units each block's table asks for: raw when 4 * words >=
-// blk_len.  f.only becomes the batched encoder's skip mask.
-__global__ __launch_bounds__(256) void k_ct_kind0(CtEncFrame f, CtEncHuff0 h, uint32_t nb, uint32_t blk_len,
-                                                  unsigned long long table_bytes, const CtEncState *state)
+// the order-0 codec's kinds in each of its modes (one thread per block; the rule is at ct_enc_kind0's declaration).  MODE says
+// which scratch exists: nothing of a mode that is off is read.
+template <uint32_t MODE>                                       // a CtMode
+__global__ __launch_bounds__(256) void k_ct_kind0(CtEncFrame f, CtEncHuff0 h, CtEncSparse sp, CtEncAns an, CtEncAuto au, uint32_t nb,
+                                                  uint32_t blk_len, unsigned long long table_bytes, const CtEncState *state)
 {
+    constexpr bool SPARSE = MODE == CT_MODE_SPARSE || MODE == CT_MODE_AUTO, ANS = MODE == CT_MODE_ANS || MODE == CT_MODE_AUTO;
     const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
     if (b >= nb) return;
-    const unsigned long long words = h.nun[b];
-    const bool raw = 4ull * words >= blk_len;
-    f.kind[b] = raw ? CT_KIND_RAW : CT_KIND_HUFF0;
-    f.only[b] = raw ? 1u : 0u;
-    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
-    f.bwt[b] = 0;
+    const bool pick5 = MODE == CT_MODE_ANS || (MODE == CT_MODE_AUTO && au.pick5[b] != 0), is3 = SPARSE && !pick5 && sp.is3[b] != 0;
+    const unsigned long long klen = is3 ? sp.klen[b] : 0ull;
+    const unsigned long long words = pick5 ? ans_words_of(an.sc.counts + (size_t)b * an.sc.nch_max, ans_chunks(blk_len))
+                                   : is3 ? sp_mask_words(blk_len) + (klen ? h.nun[b] : 0ull) : h.nun[b];
+    const bool raw = ct_put_record(f, b, pick5 ? CT_KIND_ANS : is3 ? CT_KIND_SPARSE : CT_KIND_HUFF0, words, blk_len, table_bytes, state);
+    f.only[b] = raw || pick5 || (is3 && klen == 0) ? 1u : 0u;
+    f.bwt[b] = !raw && is3 ? (int)(sp.fill[b] & 255u) : 0;
+    if (ANS) an.skip_ans[b] = pick5 && !raw ? 0u : 1u;
 }
 
 __global__ __launch_bounds__(256) void k_ct_block_offsets(unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len)
@@ -340,10 +340,13 @@ hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_
     return hipGetLastError();
 }
 
-hipError_t ct_enc_kind0(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, uint32_t nb, uint32_t blk_len, const CtEncState *state)
+hipError_t ct_enc_kind0(hipStream_t st, CtMode mode, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAns &an,
+                        const CtEncAuto &au, uint32_t nb, uint32_t blk_len, const CtEncState *state)
 {
     const CtTables T = ct_tables(nb, blk_len);
-    hipLaunchKernelGGL(k_ct_kind0, dim3((nb + 255) / 256), dim3(256), 0, st, f, h, nb, blk_len, 4 * T.words, state);
+    const auto k = mode == CT_MODE_SPARSE ? k_ct_kind0<CT_MODE_SPARSE> : mode == CT_MODE_ANS ? k_ct_kind0<CT_MODE_ANS> :
+                   mode == CT_MODE_AUTO ? k_ct_kind0<CT_MODE_AUTO> : k_ct_kind0<CT_MODE_PLAIN>;
+    hipLaunchKernelGGL(k, dim3((nb + 255) / 256), dim3(256), 0, st, f, h, sp, an, au, nb, blk_len, 4 * T.words, state);
     return hipGetLastError();
 }
 

@@ -4,12 +4,12 @@
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal(), 4 the BWT codec's
 // zero-run form (zrun.hip) where kind4_legal(), 5 the order-0 codec's rANS form (ans.hip) where kind5_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
-// writer's from the plan's settings (the lowest version that can say them), parse_format() accepts a reader's (both read ct_legal()).
+// writer's from the plan's settings (the lowest version whose kinds hold every kind they may write), parse_format() accepts a reader's (both read ct_legal()).
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
-// and the batched encoder writes the kind-2 records (with the sparse mode on: frame_sparse, kinds 2 and 3; with the rANS mode on: frame_ans, kind 5, the histograms alone and the
-// kernels of ans.hip; with the auto mode on: frame_auto, the probe of auto.hip and a kind per block out of 2, 3 and 5).  With the BWT codec's
+// and the batched encoder writes the kind-2 records (frame_order0 is the one path; with the sparse mode on its parts are frame_sparse's, kinds 2 and 3; with the rANS mode on
+// frame_ans's, kind 5, the histograms alone and the kernels of ans.hip; with the auto mode on frame_auto's, the probe of auto.hip and a kind per block out of 2, 3 and 5).  With the BWT codec's
 // runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.
@@ -106,24 +106,8 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 }
 
 // -------------------------------------------------------------------------------------------------------------------------
-// the format rule (ct_legal() of container_internal.h: the table the device's walk reads as well)
+// the format rule (ct_legal() and format_of() of container_internal.h: the table the device's walk reads as well)
 // -------------------------------------------------------------------------------------------------------------------------
-bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
-
-// the writer's format: the lowest version that can say the plan's settings
-CtFormat format_of(const CtSettings &s)
-{
-    CtFormat f;
-    f.elem = s.shuffle;
-    f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
-    for (uint32_t i = 0; i < CT_NLEGAL; i++) {
-        f.version = ct_legal(i).version;
-        if (format_legal(f) && (s.codec != CT_CODEC_HUFF0 || f.kind2_legal()) && (!s.sparse || f.kind3_legal()) &&
-            (!s.runs || f.kind4_legal()) && (!s.ans || f.kind5_legal()) && (!s.autom || f.version == CT_VERSION_AUTO)) break;
-    }
-    return f;                                                 // (the setters accept only what some row takes)
-}
-
 hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
 {
     return (f.delta() ? delta_shuffle_device : shuffle_device)(st, in, out, len, f.elem, inverse);
@@ -151,6 +135,23 @@ struct Carver {
     }
     size_t bytes() const { return off; }
 };
+// measure with a null Carver, allocate (alloc(bytes, &base) -> hipError_t), carve again on the allocation
+template <class Alloc, class Carve>
+hipError_t carve_on(Alloc alloc, Carve carve)
+{
+    Carver measure;
+    carve(measure);
+    void *base = nullptr;
+    CT_HIP(alloc(measure.bytes(), &base));
+    Carver place(base);
+    carve(place);
+    return hipSuccess;
+}
+// alloc for carve_on: the plan's codec scratch `which` (plan_codec_scratch)
+auto codec_scratch(CUDPPHandle plan, uint32_t which)
+{
+    return [=](size_t bytes, void **base) { return plan_codec_scratch(plan, which, bytes, reinterpret_cast<uint8_t **>(base)); };
+}
 
 // -------------------------------------------------------------------------------------------------------------------------
 // encoder: device scratch for two frames (the plan's call parity) of up to `rows` blocks, and the running state
@@ -164,15 +165,12 @@ struct Encoder {
     CtEncFrame fr[2] = {};
     CtFormat fmt;                                             // what the plan's settings write
     uint32_t codec = CT_CODEC_BWT;                            // the plan's container codec
+    CtMode mode = CT_MODE_PLAIN;                              // and its mode (one that fits the codec: CtSettings keeps that)
     CtEncHuff0 h0 = {};                                       // the order-0 codec's scratch, kept with the plan
-    bool sparse = false;                                      // the codec's sparse mode
-    CtEncSparse sp = {};                                      // its scratch, behind h0's; a plan that never has it on has none
-    bool runs = false;                                        // the BWT codec's runs mode
-    CtEncRuns zr = {};                                        // its scratch, kept with the plan; a plan that never has it on has none
-    bool ans = false;                                         // the order-0 codec's rANS mode
-    CtEncAns an = {};                                         // its scratch, behind h0's; a plan that never has it on has none
-    bool autom = false;                                       // the order-0 codec's auto mode: both scratches above and its own
-    CtEncAuto au = {};
+    CtEncSparse sp = {};                                      // the sparse mode's, behind h0's; a plan that never has it on has none
+    CtEncRuns zr = {};                                        // the runs mode's, kept with the plan; a plan that never has it on has none
+    CtEncAns an = {};                                         // the rANS mode's, behind h0's; a plan that never has it on has none
+    CtEncAuto au = {};                                        // the auto mode's: both scratches above and its own
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -201,41 +199,40 @@ struct Encoder {
     void carve_huff0(Carver &c)
     {
         const size_t R = P.rows;
+        const bool sparse = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, ans = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
         h0.nun = c.take<unsigned long long>(R);
-        h0.in_off = c.take<unsigned long long>(R);
-        h0.in_len = c.take<unsigned long long>(R);
+        h0.blk_off = c.take<unsigned long long>(R);
+        h0.blk_len = c.take<unsigned long long>(R);
         h0.codes = c.take<uint16_t>(256 * R);
         h0.lens = c.take<uint8_t>(256 * R);
         c.align(256);
         h0.work = c.take<uint8_t>(hdb_encode_work_bytes(R));
-        if (ans || autom) {
+        if (ans) {
             // everything of a frame runs on the plan's stream in order, so one set of chunk slots serves pipelined calls as well
             const size_t slots = R * ans_chunks(P.n);
             an.sc.nch_max = ans_chunks(P.n);
-            an.blk_off = c.take<unsigned long long>(R);
-            an.blk_len = c.take<unsigned long long>(R);
             an.sc.states = c.take<uint32_t>(slots * ANS_LANES);
             an.sc.counts = c.take<uint32_t>(slots);
+            an.skip_ans = c.take<uint32_t>(R);
             c.align(256);
             an.tab = c.take<uint8_t>(R * ANS_TAB_BYTES);
             an.sc.units = c.take<uint16_t>(slots * ANS_CHUNK);
         }
-        if (autom) {
+        if (mode == CT_MODE_AUTO) {
             au.uniform = c.take<uint32_t>(256 * R);
             au.hist_s = c.take<uint32_t>(256 * R);
             au.wa = c.take<uint32_t>(R);
             au.pick5 = c.take<uint32_t>(R);
-            au.skip_ans = c.take<uint32_t>(R);
         }
-        if (!sparse && !autom) return;
+        if (!sparse) return;
         // everything of a frame runs on the plan's stream in order, so one compaction space serves pipelined calls as well
         sp.mask_stride = sp_mask_words(P.n);
         sp.kept_stride = (P.n + 15u) & ~15u;
         sp.klen = c.take<unsigned long long>(R);
         sp.kept_off = c.take<unsigned long long>(R);
         sp.unit_off = c.take<unsigned long long>(R);
-        sp.blk_off = c.take<unsigned long long>(R);
-        sp.blk_len = c.take<unsigned long long>(R);
+        h0.in_off = c.take<unsigned long long>(R);
+        h0.in_len = c.take<unsigned long long>(R);
         sp.mask = c.take<uint32_t>(R * sp.mask_stride);
         sp.fill = c.take<uint32_t>(R);
         sp.is3 = c.take<uint32_t>(R);
@@ -272,43 +269,22 @@ struct Encoder {
         const CtSettings &s = plan_container_settings(P.h);
         fmt = format_of(s);
         codec = s.codec;
-        sparse = s.sparse && codec == CT_CODEC_HUFF0;
-        runs = s.runs && codec == CT_CODEC_BWT;
-        ans = s.ans && codec == CT_CODEC_HUFF0 && !sparse;
-        autom = s.autom && codec == CT_CODEC_HUFF0 && !sparse && !ans;
-        if (runs) {
-            Carver measure;
-            carve_runs(measure);
-            uint8_t *q = nullptr;
-            const hipError_t e = plan_codec_scratch(P.h, 0, measure.bytes(), &q);
-            if (e != hipSuccess) return e;
-            Carver place(q);
-            carve_runs(place);
-        }
-        if (codec == CT_CODEC_HUFF0) {
-            Carver measure;
-            carve_huff0(measure);
-            uint8_t *q = nullptr;
-            const hipError_t e = plan_codec_scratch(P.h, 0, measure.bytes(), &q);
-            if (e != hipSuccess) return e;
-            Carver place(q);
-            carve_huff0(place);
-        }
+        mode = s.mode;
+        if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
+        if (codec == CT_CODEC_HUFF0) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
         if (fmt.filtered()) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
-            for (int i = 0; i < nstage; i++) {
-                const hipError_t e = plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]);
-                if (e != hipSuccess) return e;
-            }
+            for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
             if (nstage == 1) stage[1] = stage[0];
         }
-        Carver measure;
-        carve(measure);
-        const hipError_t e = hipMalloc(&mem, measure.bytes());
-        if (e != hipSuccess) { mem = nullptr; return e; }
-        Carver place(mem);
-        carve(place);
-        return hipSuccess;
+        return carve_on(
+            [&](size_t bytes, void **base) {
+                const hipError_t e = hipMalloc(&mem, bytes);
+                if (e != hipSuccess) mem = nullptr;
+                *base = mem;
+                return e;
+            },
+            [&](Carver &c) { carve(c); });
     }
     ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
 
@@ -325,11 +301,12 @@ struct Encoder {
             orig = d_in;
             d_in = stage[P.parity];
         }
-        if (sparse) return frame_sparse(f, d_in, orig, nb, blk_len, out, cap);
-        if (runs) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
-        if (ans) return frame_ans(f, d_in, orig, nb, blk_len, out, cap);
-        if (autom) return frame_auto(f, d_in, orig, nb, blk_len, out, cap);
-        if (codec == CT_CODEC_HUFF0) return frame_huff0(f, d_in, orig, nb, blk_len, out, cap);
+        if (mode == CT_MODE_RUNS) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
+        if (codec == CT_CODEC_HUFF0) {
+            const Frame0 F{f, d_in, orig, nb, blk_len, out, cap};
+            return mode == CT_MODE_SPARSE ? frame_sparse(F) : mode == CT_MODE_ANS ? frame_ans(F) : mode == CT_MODE_AUTO ? frame_auto(F) :
+                                            frame_plain(F);
+        }
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
         hk.status = status;
@@ -340,129 +317,134 @@ struct Encoder {
                                                       blk_len, nb, f.boff, f.start, (size_t)(cap / 4)}, hk);
     }
 
-    // the order-0 codec's frame, wholly on the plan's stream: tables (and with them every record's size) -> kinds -> payload
-    // offsets -> the batched encoder, then the same stage behind the packer as ever
-    CUDPPResult frame_huff0(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
-                            uint8_t *out, unsigned long long cap)
+    // The order-0 codec's frame in every mode, wholly on the plan's stream: the blocks as segments of the frame -> sizes(), the
+    // mode's passes up to everything the kinds need -> kinds (ct_enc_kind0) -> payload offsets -> place(out as words, its
+    // capacity in words), the mode's records written behind the offsets -> the same stage behind the packer as ever.  The four
+    // functions below are the modes: each says its two parts and what they share.
+    struct Frame0 {
+        const CtEncFrame &f; const uint8_t *d_in, *orig; uint32_t nb, blk_len; uint8_t *out; unsigned long long cap;
+    };
+    template <class Sizes, class Place>
+    CUDPPResult frame_order0(const Frame0 &F, Sizes sizes, Place place)
     {
-        KernelProf *prof = plan_prof(P.h);
+        uint32_t *out_words = reinterpret_cast<uint32_t *>(F.out);
+        const unsigned long long cap_words = F.cap / 4;
         plan_stage_mark(P.h, 0);
-        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));   // (the blocks as segments of the frame)
-        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
-        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+        CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, F.nb, F.blk_len));
+        CT_TRY(sizes());
         plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_kind0(P.st, f, h0, nb, blk_len, state));
-        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
-        CT_TRY(hdb_encode(P.st, g, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4, f.only, h0.work, prof));
+        CT_TRY(ct_enc_kind0(P.st, mode, F.f, h0, sp, an, au, F.nb, F.blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, F.f.size, F.nb, F.f.boff, F.f.start, (size_t)cap_words, status));
+        CT_TRY(place(out_words, cap_words));
         plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
+        CT_TRY(ct_enc_after_pack(P.st, F.f, F.d_in, F.orig, F.nb, F.blk_len, F.out, F.cap, state));
         plan_stage_mark(P.h, 3);
         return CUDPP_SUCCESS;
     }
 
-    // frame_huff0 with the sparse mode on: tables of the whole blocks -> fill bytes -> masks -> kind 3 or 2 (histograms corrected)
-    // -> compaction of the kind-3 blocks -> their tables, of K -> record sizes and the raw rule -> payload offsets -> masks into
-    // the records and every stream encoded behind its mask (kind 2 from the frame, kind 3 from the compaction space)
-    CUDPPResult frame_sparse(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
-                             uint8_t *out, unsigned long long cap)
+    // tables (and with them every record's size) -> kinds -> the batched encoder
+    CUDPPResult frame_plain(const Frame0 &F)
     {
         KernelProf *prof = plan_prof(P.h);
-        plan_stage_mark(P.h, 0);
-        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));
-        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
-        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
-        CT_TRY(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
-        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));        // (klen itself comes two steps on)
-        CT_TRY(ct_block_offsets(P.st, sp.blk_off, sp.blk_len, nb, blk_len));
-        SpSegs s{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr, sp.mask_stride,
-                 nullptr, nb, blk_len};
-        CT_TRY(sparse_mask(P.st, s));
-        CT_TRY(ct_enc_sparse_decide(P.st, s, sp, f.hist, h0.in_off, h0.in_len));
-        s.skip = sp.skip_move;
-        CT_TRY(sparse_compact(P.st, s));
+        const CtEncFrame &f = F.f;
+        const HdbSegs g{F.d_in, h0.blk_off, h0.blk_len, F.nb, F.blk_len};
+        return frame_order0(
+            F, [&] { return hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof); },
+            [&](uint32_t *out, unsigned long long cap) { return hdb_encode(P.st, g, h0.lens, h0.codes, h0.nun, out, f.boff, cap, f.only, h0.work, prof); });
+    }
+
+    // the sparse mode: tables of the whole blocks -> fill bytes -> masks -> kind 3 or 2 (histograms corrected) -> compaction of
+    // the kind-3 blocks -> their tables, of K -> record sizes and the record rule -> payload offsets -> masks into the records
+    // and every stream encoded behind its mask (kind 2 from the frame, kind 3 from the compaction space)
+    CUDPPResult frame_sparse(const Frame0 &F)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        const CtEncFrame &f = F.f;
+        const uint32_t nb = F.nb, blk_len = F.blk_len;
         const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
-        CT_TRY(hdb_tables(P.st, g2, false, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
-        plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_sparse_kind(P.st, f, h0, sp, nb, blk_len, state));
-        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
-        CT_TRY(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, reinterpret_cast<uint32_t *>(out), cap / 4));
-        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), sp.unit_off, cap / 4, f.only, h0.work, prof));
-        plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
-        plan_stage_mark(P.h, 3);
-        return CUDPP_SUCCESS;
+        return frame_order0(
+            F,
+            [&]() -> hipError_t {
+                const HdbSegs g{F.d_in, h0.blk_off, h0.blk_len, nb, blk_len};
+                CT_HIP(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+                CT_HIP(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
+                CT_HIP(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));    // (klen itself comes two steps on)
+                SpSegs s{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr,
+                         sp.mask_stride, nullptr, nb, blk_len};
+                CT_HIP(sparse_mask(P.st, s));
+                CT_HIP(ct_enc_sparse_decide(P.st, s, sp, f.hist, h0.in_off, h0.in_len));
+                s.skip = sp.skip_move;
+                CT_HIP(sparse_compact(P.st, s));
+                return hdb_tables(P.st, g2, false, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof);
+            },
+            [&](uint32_t *out, unsigned long long cap) -> hipError_t {
+                CT_HIP(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, out, cap));
+                return hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, out, sp.unit_off, cap, f.only, h0.work, prof);
+            });
     }
 
-    // frame_huff0 with the rANS mode on: histograms (the Huffman tables that come with them are not used) -> the blocks' rANS
-    // tables -> every chunk coded into its scratch slot -> record sizes and the raw rule -> payload offsets -> counts, states and
-    // units into the records
-    CUDPPResult frame_ans(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
-                          uint8_t *out, unsigned long long cap)
+    // the rANS mode: histograms (the Huffman tables that come with them are not used) -> the blocks' rANS tables -> every chunk
+    // coded into its scratch slot -> record sizes and the record rule -> payload offsets -> counts, states and units into the
+    // records
+    CUDPPResult frame_ans(const Frame0 &F)
     {
         KernelProf *prof = plan_prof(P.h);
-        plan_stage_mark(P.h, 0);
-        CT_TRY(ct_block_offsets(P.st, h0.in_off, h0.in_len, nb, blk_len));
-        const HdbSegs g{d_in, h0.in_off, h0.in_len, nb, blk_len};
-        CT_TRY(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
-        CT_TRY(ct_block_offsets(P.st, an.blk_off, an.blk_len, nb, blk_len));
-        const AnsSegs a{const_cast<uint8_t *>(d_in), an.blk_off, an.blk_len, f.hist, an.tab, nullptr, nb, blk_len};
-        CT_TRY(ans_tables(P.st, a));
-        CT_TRY(ans_encode(P.st, a, an.sc));
-        plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_ans_kind(P.st, f, an.sc, nb, blk_len, state));
-        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
-        AnsSegs ap = a;
-        ap.skip = f.only;
-        CT_TRY(ans_place(P.st, ap, an.sc, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4));
-        plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
-        plan_stage_mark(P.h, 3);
-        return CUDPP_SUCCESS;
+        const CtEncFrame &f = F.f;
+        AnsSegs a{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, f.hist, an.tab, nullptr, F.nb, F.blk_len};
+        return frame_order0(
+            F,
+            [&]() -> hipError_t {
+                const HdbSegs g{F.d_in, h0.blk_off, h0.blk_len, F.nb, F.blk_len};
+                CT_HIP(hdb_tables(P.st, g, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, nullptr, prof));
+                CT_HIP(ans_tables(P.st, a));
+                return ans_encode(P.st, a, an.sc);
+            },
+            [&](uint32_t *out, unsigned long long cap) {
+                a.skip = an.skip_ans;
+                return ans_place(P.st, a, an.sc, out, f.boff, cap);
+            });
     }
 
-    // frame_huff0 with the auto mode on: one probe of the blocks (counts and uniform chunks) -> fill bytes and the blocks' rANS
-    // tables (their q) -> candidate S of every block and the estimate wA, from the statistics alone -> the Huffman tables of
-    // candidate S's counts, and with them wS -> the choice per block -> masks and compaction of the blocks that stay kind 3, the
-    // rANS coder on the blocks chosen as kind 5 -> actual sizes and the raw rule -> payload offsets -> masks and rANS records
-    // placed, kind 2 and K encoded behind them
-    CUDPPResult frame_auto(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
-                           uint8_t *out, unsigned long long cap)
+    // the auto mode: one probe of the blocks (counts and uniform chunks) -> fill bytes and the blocks' rANS tables (their q) ->
+    // candidate S of every block and the estimate wA, from the statistics alone -> the Huffman tables of candidate S's counts,
+    // and with them wS -> the choice per block -> masks and compaction of the blocks that stay kind 3, the rANS coder on the
+    // blocks chosen as kind 5 -> actual sizes and the record rule -> payload offsets -> masks and rANS records placed, kind 2 and
+    // K encoded behind them
+    CUDPPResult frame_auto(const Frame0 &F)
     {
         KernelProf *prof = plan_prof(P.h);
-        plan_stage_mark(P.h, 0);
-        CT_TRY(ct_block_offsets(P.st, sp.blk_off, sp.blk_len, nb, blk_len));
-        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));        // (klen itself comes two steps on)
-        CT_TRY(probe_segments(P.st, d_in, sp.blk_off, sp.blk_len, nb, blk_len, f.hist, au.uniform));
-        CT_TRY(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
-        const AnsSegs a{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, f.hist, an.tab, nullptr, nb, blk_len};
-        CT_TRY(ans_tables(P.st, a));
-        SpSegs s{const_cast<uint8_t *>(d_in), sp.blk_off, sp.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr, sp.mask_stride,
-                 nullptr, nb, blk_len};
-        CT_TRY(ct_enc_auto_candidates(P.st, s, sp, au, f.hist, an.tab, h0.in_off, h0.in_len));
+        const CtEncFrame &f = F.f;
+        const uint32_t nb = F.nb, blk_len = F.blk_len;
         const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
-        CT_TRY(hdb_tables(P.st, g2, false, au.hist_s, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
-        CT_TRY(ct_enc_auto_choose(P.st, f, h0, sp, au, nb, blk_len));
-        s.skip = sp.skip_move;
-        CT_TRY(sparse_mask(P.st, s));
-        CT_TRY(sparse_compact(P.st, s));
-        AnsSegs ae = a;
-        ae.skip = au.skip_ans;
-        CT_TRY(ans_encode(P.st, ae, an.sc));
-        plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_auto_kind(P.st, f, h0, sp, au, an.sc, nb, blk_len, state));
-        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)(cap / 4), status));
-        CT_TRY(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, reinterpret_cast<uint32_t *>(out), cap / 4));
-        CT_TRY(ans_place(P.st, ae, an.sc, reinterpret_cast<uint32_t *>(out), f.boff, cap / 4));
-        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, reinterpret_cast<uint32_t *>(out), sp.unit_off, cap / 4, f.only, h0.work, prof));
-        plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, f, d_in, orig, nb, blk_len, out, cap, state));
-        plan_stage_mark(P.h, 3);
-        return CUDPP_SUCCESS;
+        AnsSegs a{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, f.hist, an.tab, nullptr, nb, blk_len};
+        return frame_order0(
+            F,
+            [&]() -> hipError_t {
+                CT_HIP(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));    // (klen itself comes two steps on)
+                CT_HIP(probe_segments(P.st, F.d_in, h0.blk_off, h0.blk_len, nb, blk_len, f.hist, au.uniform));
+                CT_HIP(ct_enc_sparse_fill(P.st, f.hist, nb, sp.fill));
+                CT_HIP(ans_tables(P.st, a));
+                SpSegs s{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr,
+                         sp.mask_stride, nullptr, nb, blk_len};
+                CT_HIP(ct_enc_auto_candidates(P.st, s, sp, au, f.hist, an.tab, h0.in_off, h0.in_len));
+                CT_HIP(hdb_tables(P.st, g2, false, au.hist_s, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
+                CT_HIP(ct_enc_auto_choose(P.st, f, h0, sp, an, au, nb, blk_len));
+                s.skip = sp.skip_move;
+                CT_HIP(sparse_mask(P.st, s));
+                CT_HIP(sparse_compact(P.st, s));
+                a.skip = an.skip_ans;                         // (1 = not rANS-coded; behind the kinds: no kind-5 record to place)
+                return ans_encode(P.st, a, an.sc);
+            },
+            [&](uint32_t *out, unsigned long long cap) -> hipError_t {
+                CT_HIP(ct_enc_sparse_place(P.st, f, sp, nb, blk_len, out, cap));
+                CT_HIP(ans_place(P.st, a, an.sc, out, f.boff, cap));
+                return hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, out, sp.unit_off, cap, f.only, h0.work, prof);
+            });
     }
 
     // the BWT codec's frame with the runs mode on, wholly on the plan's stream: BWT and MTF of the blocks by the plan's sorter
     // and MTF stage -> the split into A and B -> tables of the A's (their counts are the record's hist) and of the B's -> nz,
-    // record sizes and the raw rule -> payload offsets -> nz and the pairs into the records -> every stream encoded at its
+    // record sizes and the record rule -> payload offsets -> nz and the pairs into the records -> every stream encoded at its
     // place, A's and B's in one launch -> the same stage behind the packer as ever
     CUDPPResult frame_runs(const CtEncFrame &f, const uint8_t *d_in, const uint8_t *orig, uint32_t nb, uint32_t blk_len,
                            uint8_t *out, unsigned long long cap)
@@ -562,14 +544,7 @@ struct Decoder {
         const size_t per = hdb_decode_work_bytes(1, blk_len) + 512;
         h0.chunk = (uint32_t)std::min<size_t>(std::min<size_t>(P.rows, nb), std::max<size_t>(1, ((size_t)256 << 20) / per));
         if (fmt.kind4_legal()) CT_HIP(plan_decode_rows(P.h, &h0.mtf, &h0.mtf_stride));   // (where the join leaves the MTF bytes)
-        Carver measure;
-        carve_huff0(measure, nb, blk_len);
-        uint8_t *q = nullptr;
-        const hipError_t e = plan_codec_scratch(P.h, 1, measure.bytes(), &q);
-        if (e != hipSuccess) return e;
-        Carver place(q);
-        carve_huff0(place, nb, blk_len);
-        return hipSuccess;
+        return carve_on(codec_scratch(P.h, 1), [&](Carver &c) { carve_huff0(c, nb, blk_len); });
     }
 
     ~Decoder()
@@ -592,14 +567,16 @@ struct Decoder {
         if (nb <= cap_nb && mem) return hipSuccess;
         if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); mem = nullptr; }
         if (h_verdict) { (void)hipHostFree(h_verdict); h_verdict = nullptr; }
-        Carver measure;
-        carve(measure, nb);
-        hipError_t e = hipMalloc(&mem, measure.bytes());
-        if (e != hipSuccess) { mem = nullptr; return e; }
-        e = hipHostMalloc((void **)&h_verdict, 8 * verdict_words(nb), hipHostMallocDefault);
-        if (e != hipSuccess) { h_verdict = nullptr; return e; }
-        Carver place(mem);
-        carve(place, nb);
+        CT_HIP(carve_on(
+            [&](size_t bytes, void **base) {
+                hipError_t e = hipMalloc(&mem, bytes);
+                if (e != hipSuccess) { mem = nullptr; return e; }
+                e = hipHostMalloc((void **)&h_verdict, 8 * verdict_words(nb), hipHostMallocDefault);
+                if (e != hipSuccess) h_verdict = nullptr;
+                *base = mem;
+                return e;
+            },
+            [&](Carver &c) { carve(c, nb); }));
         cap_nb = nb;
         return hipSuccess;
     }
@@ -650,62 +627,66 @@ struct Decoder {
         const CtTables T = ct_tables(nb, blk_len);
         const uint32_t *W = reinterpret_cast<const uint32_t *>(fr + CT_FRAME_HDR);
         const unsigned int *pay = reinterpret_cast<const unsigned int *>(fr + CT_FRAME_HDR + 4 * T.words);
-        for (uint32_t a = 0; a < nb;) {
-            if (kind[a] != CT_KIND_HUFF || !want(a)) { a++; continue; }
-            uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_HUFF && want(b) && b - a < P.rows) b++;
-            const CUDPPResult r = glcDecompressBatchCompact(
-                P.h, reinterpret_cast<const int *>(W + T.bwt) + a, W + T.hist + 256ull * a, W + T.enc_off + (size_t)T.nsub * a,
-                T.nsub, pay, pw, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, out + (size_t)a * blk_len,
-                blk_len, b - a);
-            if (r != CUDPP_SUCCESS) return r;
-            a = b;
-        }
-        for (uint32_t a = 0; k2 && a < nb;) {                   // runs of order-0 blocks, a chunk of the plan's rows at a time
-            if (kind[a] != CT_KIND_HUFF0 || !want(a)) { a++; continue; }
-            uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_HUFF0 && want(b) && b - a < h0.chunk) b++;
+        // over the maximal runs [a, b) of wanted blocks of kind K: more(a, b) = block b may still join the run that starts at a
+        auto runs_of = [&](uint32_t K, auto more, auto body) -> CUDPPResult {
+            for (uint32_t a = 0; a < nb;) {
+                if (kind[a] != K || !want(a)) { a++; continue; }
+                uint32_t b = a;
+                while (b < nb && kind[b] == K && want(b) && more(a, b)) b++;
+                const CUDPPResult r = body(a, b - a);
+                if (r != CUDPP_SUCCESS) return r;
+                a = b;
+            }
+            return CUDPP_SUCCESS;
+        };
+        auto in_rows = [&](uint32_t a, uint32_t b) { return b - a < P.rows; };
+        auto in_chunk = [&](uint32_t a, uint32_t b) { return b - a < h0.chunk; };        // a chunk of the plan's rows at a time
+        auto same_chunk = [&](uint32_t a, uint32_t b) { return b / h0.chunk == a / h0.chunk; };
+        const unsigned long long *pay_off = reinterpret_cast<const unsigned long long *>(W + T.pay_off);
+        CUDPPResult r = runs_of(CT_KIND_HUFF, in_rows, [&](uint32_t a, uint32_t cnt) {
+            return glcDecompressBatchCompact(P.h, reinterpret_cast<const int *>(W + T.bwt) + a, W + T.hist + 256ull * a,
+                                             W + T.enc_off + (size_t)T.nsub * a, T.nsub, pay, pw, pay_off + a, out + (size_t)a * blk_len,
+                                             blk_len, cnt);
+        });
+        if (r != CUDPP_SUCCESS) return r;
+        if (k2) r = runs_of(CT_KIND_HUFF0, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
             // (k_cd_raw has put every block's output range into f.seg_*: absolute addresses, so the base is null)
-            const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, b - a, blk_len};
-            CT_TRY(hdb_decode(P.st, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, h0.nun + a,
-                              h0.lut + 2048ull * a, g, nullptr, h0.work, prof));
-            a = b;
-        }
-        for (uint32_t a = 0; fmt.kind3_legal() && a < nb;) {    // runs of sparse blocks: K decoded into scratch, then expanded
-            if (kind[a] != CT_KIND_SPARSE || !want(a)) { a++; continue; }
-            uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_SPARSE && want(b) && b - a < h0.chunk) b++;
-            const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, b - a, blk_len};
+            const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, cnt, blk_len};
+            CT_TRY(hdb_decode(P.st, pay, pay_off + a, h0.nun + a, h0.lut + 2048ull * a, g, nullptr, h0.work, prof));
+            return CUDPP_SUCCESS;
+        });
+        if (r != CUDPP_SUCCESS) return r;
+        // sparse blocks: K decoded into scratch, then expanded
+        if (fmt.kind3_legal()) r = runs_of(CT_KIND_SPARSE, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+            const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len};
             CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
             const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
-                           reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, 0, nullptr, b - a, blk_len};
+                           pay_off + a, 0, nullptr, cnt, blk_len};
             CT_TRY(sparse_join(P.st, s));
-            a = b;
-        }
-        for (uint32_t a = 0; fmt.kind5_legal() && a < nb;) {    // runs of rANS blocks: their tables from the histograms, then one pass
-            if (kind[a] != CT_KIND_ANS || !want(a)) { a++; continue; }
-            uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_ANS && want(b) && b - a < h0.chunk) b++;
-            const AnsSegs g{nullptr, f.seg_off + a, f.seg_len + a, W + T.hist + 256ull * a, h0.ans_tab, nullptr, b - a, blk_len};
+            return CUDPP_SUCCESS;
+        });
+        if (r != CUDPP_SUCCESS) return r;
+        // rANS blocks: their tables from the histograms, then one pass
+        if (fmt.kind5_legal()) r = runs_of(CT_KIND_ANS, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+            const AnsSegs g{nullptr, f.seg_off + a, f.seg_len + a, W + T.hist + 256ull * a, h0.ans_tab, nullptr, cnt, blk_len};
             CT_TRY(ans_tables(P.st, g));
-            CT_TRY(ans_decode(P.st, g, pay, reinterpret_cast<const unsigned long long *>(W + T.pay_off) + a, nullptr));
-            a = b;
-        }
-        // runs of zero-run blocks inside one chunk of the decoder: A and B decoded into scratch, joined into the rows b % chunk of
-        // the decoder's MTF bytes, and from there the BWT codec's own inverse MTF and inverse BWT
-        for (uint32_t a = 0; fmt.kind4_legal() && a < nb;) {
-            if (kind[a] != CT_KIND_RUNS || !want(a)) { a++; continue; }
-            uint32_t b = a;
-            while (b < nb && kind[b] == CT_KIND_RUNS && want(b) && b / h0.chunk == a / h0.chunk) b++;
-            const HdbOut ga{nullptr, h0.k_off + a, h0.k_len + a, b - a, blk_len}, gb{nullptr, h0.b_off + a, h0.b_len + a, b - a, blk_len};
+            CT_TRY(ans_decode(P.st, g, pay, pay_off + a, nullptr));
+            return CUDPP_SUCCESS;
+        });
+        if (r != CUDPP_SUCCESS) return r;
+        // zero-run blocks inside one chunk of the decoder: A and B decoded into scratch, joined into the rows b % chunk of the
+        // decoder's MTF bytes, and from there the BWT codec's own inverse MTF and inverse BWT
+        if (fmt.kind4_legal()) r = runs_of(CT_KIND_RUNS, same_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+            const HdbOut ga{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len}, gb{nullptr, h0.b_off + a, h0.b_len + a, cnt, blk_len};
             CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, ga, h0.skip3 + a, h0.work, prof));
             CT_TRY(hdb_decode(P.st, pay, h0.ub_off + a, h0.nun_b + a, h0.lut_b + 2048ull * a, gb, h0.skip_b + a, h0.work, prof));
             const ZrSegs z{nullptr, h0.m_off + a, h0.m_len + a, nullptr, h0.k_off + a, h0.k_len + a, nullptr, h0.b_off + a, h0.b_len + a,
-                           nullptr, b - a, blk_len};
+                           nullptr, cnt, blk_len};
             CT_TRY(zrun_join(P.st, z));
-            CT_TRY(plan_decode_from_mtf(P.h, a % h0.chunk, reinterpret_cast<const int *>(W + T.bwt) + a, out + (size_t)a * blk_len, blk_len, b - a));
-            a = b;
-        }
+            CT_TRY(plan_decode_from_mtf(P.h, a % h0.chunk, reinterpret_cast<const int *>(W + T.bwt) + a, out + (size_t)a * blk_len, blk_len, cnt));
+            return CUDPP_SUCCESS;
+        });
+        if (r != CUDPP_SUCCESS) return r;
         plan_join(P.h);
         if (need) {
             CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
@@ -1671,63 +1652,42 @@ CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (elem > 1 && !shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    CtSettings &s = plan_container_settings(plan);
-    s.shuffle = elem > 1 ? elem : 0;
-    if (elem <= 1) s.delta = false;                           // (no delta without the shuffle)
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_shuffle(elem) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && !s.shuffle)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    s.delta = on != 0;
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_delta(on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (codec != GLC_CONTAINER_CODEC_BWT && codec != GLC_CONTAINER_CODEC_HUFF0) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    CtSettings &s = plan_container_settings(plan);
-    s.codec = codec;
-    if (codec != GLC_CONTAINER_CODEC_HUFF0) s.sparse = s.ans = s.autom = false;   // (no sparse, rANS or auto mode without the order-0 codec)
-    if (codec != GLC_CONTAINER_CODEC_BWT) s.runs = false;       // (no runs mode without the BWT codec)
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_codec(codec) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.ans || s.autom))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;   // (the modes exclude each other)
-    s.sparse = on != 0;
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_mode(CT_MODE_SPARSE, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse || s.autom))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    s.ans = on != 0;
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_mode(CT_MODE_ANS, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && (s.codec != GLC_CONTAINER_CODEC_HUFF0 || s.sparse || s.ans))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    s.autom = on != 0;
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_mode(CT_MODE_AUTO, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on)
@@ -1735,7 +1695,7 @@ CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).autom ? 1u : 0u;
+    *on = plan_container_settings(plan).mode == CT_MODE_AUTO ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 
@@ -1744,7 +1704,7 @@ CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).ans ? 1u : 0u;
+    *on = plan_container_settings(plan).mode == CT_MODE_ANS ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 
@@ -1779,10 +1739,7 @@ CUDPPResult glcPlanSetContainerRuns(CUDPPHandle plan, unsigned int on)
 {
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
-    CtSettings &s = plan_container_settings(plan);
-    if (on > 1 || (on && s.codec != GLC_CONTAINER_CODEC_BWT)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    s.runs = on != 0;
-    return CUDPP_SUCCESS;
+    return plan_container_settings(plan).set_mode(CT_MODE_RUNS, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
 }
 
 CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on)
@@ -1790,7 +1747,7 @@ CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).runs ? 1u : 0u;
+    *on = plan_container_settings(plan).mode == CT_MODE_RUNS ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 
@@ -1799,7 +1756,7 @@ CUDPPResult glcPlanGetContainerSparse(CUDPPHandle plan, unsigned int *on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).sparse ? 1u : 0u;
+    *on = plan_container_settings(plan).mode == CT_MODE_SPARSE ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -238,6 +238,13 @@ constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 r
 constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
 constexpr uint32_t CT_KIND_ANS = 5;                          // rANS order-0 record (ans.hip): chunk unit counts, then every chunk's 64 states and units; version 7
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
+// the writer's mode: which record kinds beyond its codec's plain ones it may emit (3; 4; 5; 3 and 5).  At most one is on, and
+// each belongs to one codec: runs to the BWT codec, sparse, rANS and auto to the order-0 codec
+enum CtMode : uint32_t { CT_MODE_PLAIN = 0, CT_MODE_SPARSE, CT_MODE_RUNS, CT_MODE_ANS, CT_MODE_AUTO };
+__host__ __device__ inline bool ct_mode_fits(CtMode mode, uint32_t codec)
+{
+    return mode == CT_MODE_PLAIN || codec == (mode == CT_MODE_RUNS ? CT_CODEC_BWT : CT_CODEC_HUFF0);
+}
 
 // failure classes of glcContainerLastError (out[0])
 enum CtWhat : uint32_t { CT_OK = 0, CT_STREAM_HEADER = 1, CT_FRAME_TABLE = 2, CT_RECORD_CRC = 3, CT_DECODED_CRC = 4,
@@ -258,6 +265,8 @@ __host__ __device__ inline CtTables ct_tables(uint32_t nb, uint32_t blk_len)
     return t;
 }
 __host__ __device__ inline uint32_t ct_raw_words(uint32_t blk_len) { return (blk_len + 3) / 4; }
+// the record rule: a block whose coded record of `words` words would not be smaller than its bytes is stored raw
+__host__ __device__ inline bool ct_stored_raw(unsigned long long words, uint32_t blk_len) { return 4 * words >= blk_len; }
 __host__ __device__ inline unsigned long long frame_bytes(uint32_t nb, uint32_t blk_len, unsigned long long payload_words)
 {
     return CT_FRAME_HDR + 4 * ct_tables(nb, blk_len).words + 4 * (payload_words + (payload_words & 1));
@@ -382,17 +391,66 @@ CUDPPResult plan_compress_hooked(CUDPPHandle plan, CompressCall c, ContainerHook
 bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, uint32_t *next_parity);
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
-// mode (only ever on with the shuffle on), the codec (CT_CODEC_*), its sparse mode (only ever on with the order-0 codec), its
-// runs mode (only ever on with the BWT codec), its rANS mode (only ever on with the order-0 codec and the sparse mode off) and
-// its auto mode (only ever on with the order-0 codec and both of those off; as a reader it implies them)
+// mode (only ever on with the shuffle on), the codec (CT_CODEC_*) and the mode (only ever one that ct_mode_fits() the codec).
+// The set_*() are the whole rule of the public setters: false = refused, nothing changed.
+inline bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
 struct CtSettings {
-    uint32_t shuffle = 0; bool delta = false; uint32_t codec = 0; bool sparse = false, runs = false, ans = false, autom = false;
+    uint32_t shuffle = 0; bool delta = false; uint32_t codec = CT_CODEC_BWT; CtMode mode = CT_MODE_PLAIN;
+    bool set_shuffle(uint32_t elem)
+    {
+        if (elem > 1 && !shuffle_elem_ok(elem)) return false;
+        shuffle = elem > 1 ? elem : 0;
+        if (elem <= 1) delta = false;                         // (no delta without the shuffle)
+        return true;
+    }
+    bool set_delta(uint32_t on)
+    {
+        if (on > 1 || (on && !shuffle)) return false;
+        delta = on != 0;
+        return true;
+    }
+    bool set_codec(uint32_t c)
+    {
+        if (c != CT_CODEC_BWT && c != CT_CODEC_HUFF0) return false;
+        codec = c;
+        if (!ct_mode_fits(mode, codec)) mode = CT_MODE_PLAIN;  // (no mode without its codec)
+        return true;
+    }
+    // on: refused when the mode does not fit the codec or another mode is on (the modes exclude each other); off: clears the
+    // mode if it is the one that is on
+    bool set_mode(CtMode m, uint32_t on)
+    {
+        if (on > 1 || (on && (!ct_mode_fits(m, codec) || (mode != CT_MODE_PLAIN && mode != m)))) return false;
+        if (on) mode = m;
+        else if (mode == m) mode = CT_MODE_PLAIN;
+        return true;
+    }
+    // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
-        return (sparse ? CT_READS_SPARSE : 0u) | (runs ? CT_READS_RUNS : 0u) | (ans ? CT_READS_ANS : 0u) |
-               (autom ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : 0u);
+        return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : 0u;
+    }
+    // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
+    uint32_t kinds() const
+    {
+        const bool k3 = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, k5 = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
+        return 1u << CT_KIND_RAW | 1u << (codec == CT_CODEC_HUFF0 ? CT_KIND_HUFF0 : CT_KIND_HUFF) | (k3 ? 1u << CT_KIND_SPARSE : 0u) |
+               (mode == CT_MODE_RUNS ? 1u << CT_KIND_RUNS : 0u) | (k5 ? 1u << CT_KIND_ANS : 0u);
     }
 };
+// the writer's format: the lowest legal version whose kinds include every kind the settings may write
+inline CtFormat format_of(const CtSettings &s)
+{
+    CtFormat f;
+    f.elem = s.shuffle;
+    f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
+    for (uint32_t i = 0; i < CT_NLEGAL; i++) {
+        f.version = ct_legal(i).version;
+        if (format_legal(f) && (f.kinds() & s.kinds()) == s.kinds()) break;
+    }
+    return f;                                                 // (the setters accept only what some row takes)
+}
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
@@ -430,8 +488,23 @@ struct CtEncFrame {                                        // device scratch of 
     unsigned long long *boff, *seg_off, *seg_len, *start;  // boff: nb + 1 absolute word offsets; segs: 2 nb + 2
     uint32_t *tcrc;                                        // [2]
 };
+// what every kind kernel ends with: block b's kind and record words under the record rule (also_raw: the kernel's own further
+// reason to store it raw), and from block 0's thread where the frame's payload starts; true = stored raw
+__device__ inline bool ct_put_record(const CtEncFrame &f, uint32_t b, uint32_t kind, unsigned long long words, uint32_t blk_len,
+                                     unsigned long long table_bytes, const CtEncState *state, bool also_raw = false)
+{
+    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
+    const bool raw = also_raw || ct_stored_raw(words, blk_len);
+    f.kind[b] = raw ? CT_KIND_RAW : kind;
+    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
+    return raw;
+}
 struct CtEncHuff0 {                                        // device scratch of the order-0 codec's frame (plan_codec_scratch 0)
-    unsigned long long *nun, *in_off, *in_len;             // [rows] units of each block's stream; the blocks as segments of the frame
+    unsigned long long *nun;                               // [rows] units of each block's stream
+    unsigned long long *blk_off, *blk_len;                 // [rows] the blocks as segments of the frame
+    // [rows] what the tables and the Huffman encoder read where that is not the block itself (absolute addresses: the block
+    // or its kept bytes); the sparse and the auto mode's, with their scratch
+    unsigned long long *in_off, *in_len;
     uint8_t *lens;                                         // [rows][256]
     uint16_t *codes;                                       // [rows][256]
     void *work;                                            // hdb_encode_work_bytes(rows)
@@ -440,7 +513,6 @@ struct CtEncSparse {                                       // device scratch of 
     uint32_t *mask; uint32_t mask_stride;                  // [rows][mask_stride] words
     uint32_t *fill, *is3, *skip_move, *skip_table;         // [rows]: fill byte; kind 3 chosen; 1 = not compacted; 1 = no table of K
     unsigned long long *klen, *kept_off, *unit_off;        // [rows]: bytes of K; K's place in `kept`; where the block's stream starts
-    unsigned long long *blk_off, *blk_len;                 // [rows]: the blocks as segments of the frame
     uint8_t *kept; uint32_t kept_stride;                   // [rows][kept_stride] bytes: the compaction space
 };
 struct CtEncRuns {                                         // device scratch of the runs mode (plan_codec_scratch 0; allocated once it is on)
@@ -455,43 +527,41 @@ struct CtEncRuns {                                         // device scratch of 
     uint8_t *a, *b; uint32_t stride;                       // [rows][stride] each
 };
 struct CtEncAns {                                          // device scratch of the rANS mode, behind CtEncHuff0's (allocated once it is on)
-    unsigned long long *blk_off, *blk_len;                 // [rows] the blocks as segments of the frame
     uint8_t *tab;                                          // [rows] ANS_TAB_BYTES
     AnsScratch sc;                                         // [rows * ans_chunks(n)] slots: about 2 * rows * n bytes
+    // [rows] behind the kinds: 1 = no kind-5 record to place (not kind 5, or raw); in the auto mode before them: 1 = not rANS-coded
+    uint32_t *skip_ans;
 };
 struct CtEncAuto {                                         // device scratch of the auto mode, behind CtEncSparse's and CtEncAns's (allocated once it is on)
     uint32_t *uniform;                                     // [rows][256] the probe's chunk counts
     uint32_t *hist_s;                                      // [rows][256] candidate S's counts: the block's, or K's where S is kind 3
     uint32_t *wa, *pick5;                                  // [rows] the estimate wA; 1 = the block is coded as kind 5
-    uint32_t *skip_ans;                                    // [rows] 1 = not rANS-coded; behind the kinds: 1 = no kind-5 record to place
 };
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
-// the order-0 codec's ct_enc_kind, from h.nun: kind 2, or raw when 4 * words >= blk_len; f.only becomes the encoder's SKIP
-// mask (1 = raw) and f.bwt zeros
 hipError_t ct_block_offsets(hipStream_t st, unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len);   // off[b] = b * blk_len
-hipError_t ct_enc_kind0(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+// the order-0 codec's ct_enc_kind in every mode of that codec (the scratch of a mode that is off is not touched).  A block is
+// kind 5 in the rANS mode and where au.pick5 says so in the auto mode, its words from the chunks' unit counts; else kind 3 where
+// sp.is3 says so in the sparse and auto modes (the mask and, when anything is kept, the stream h.nun counts; the fill into f.bwt);
+// else kind 2 (h.nun); and raw under the record rule whichever it was.  f.only = 1 where the Huffman encoder has nothing to write
+// (raw, kind 5, kind 3 with nothing kept); an.skip_ans (rANS and auto modes) = 1 where ans_place has not (not kind 5, or raw)
+hipError_t ct_enc_kind0(hipStream_t st, CtMode mode, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAns &an,
+                        const CtEncAuto &au, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_kind(hipStream_t st, const CtEncFrame &f, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 // the sparse mode's steps (sparse.hip), in order: the fill byte of every block from its histogram; kind 3 or 2 from the mask,
-// with the histogram corrected to K's and (in_off, in_len) turned into what the tables and the encoder read (absolute
-// addresses); ct_enc_kind0's sibling (record sizes, raw rule, skip mask, the fill into f.bwt); and behind the payload offsets
-// the masks into the records and sp.unit_off = where each block's stream starts
+// with the histogram corrected to K's and (in_off, in_len) made what the tables and the encoder read; and behind the payload
+// offsets the masks into the records and sp.unit_off = where each block's stream starts
 hipError_t ct_enc_sparse_fill(hipStream_t st, const uint32_t *hist, uint32_t nb, uint32_t *fill);
 hipError_t ct_enc_sparse_decide(hipStream_t st, const SpSegs &g, const CtEncSparse &sp, uint32_t *hist, unsigned long long *in_off,
                                 unsigned long long *in_len);
-hipError_t ct_enc_sparse_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, uint32_t nb,
-                              uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_sparse_place(hipStream_t st, const CtEncFrame &f, const CtEncSparse &sp, uint32_t nb, uint32_t blk_len, uint32_t *out,
                                unsigned long long cap_words);
 // the runs mode's steps (zrun.hip), in order: the MTF rows and the A / B spaces as segments; behind the split, which B is empty;
-// ct_enc_kind0's sibling (nz, record sizes, raw rule, skip masks); and behind the payload offsets nz and the pairs into the
-// records and r.unit_off = where each stream starts
+// the runs mode's ct_enc_kind (nz, record sizes under the record rule, skip masks); and behind the payload offsets nz and the
+// pairs into the records and r.unit_off = where each stream starts
 hipError_t ct_enc_runs_segs(hipStream_t st, const CtEncRuns &r, const uint8_t *mtf, size_t mtf_stride, uint32_t nb, uint32_t blk_len);
 hipError_t ct_enc_runs_empty(hipStream_t st, const CtEncRuns &r, uint32_t nb);
 hipError_t ct_enc_runs_kind(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 hipError_t ct_enc_runs_place(hipStream_t st, const CtEncFrame &f, const CtEncRuns &r, uint32_t nb, uint32_t *out, unsigned long long cap_words);
-// the rANS mode's ct_enc_kind0 (ans.hip), behind ans_encode: record sizes from the chunks' unit counts, kind 5 or raw when
-// 4 * words >= blk_len; f.only becomes ans_place's skip mask (1 = raw) and f.bwt zeros
-hipError_t ct_enc_ans_kind(hipStream_t st, const CtEncFrame &f, const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state);
 // the probe (auto.hip): hist[i][256] and uniform[i][256] of segment i = data + data_off[i], min(data_len[i], max_len) bytes
 // (max_len <= 2^20), uniform[i][v] = its 64-byte chunks, counted from the segment's start, that hold byte v alone (the short last
 // chunk included when it does).  The rows need not be zeroed.  Everything only enqueues on `st`.
@@ -500,15 +570,13 @@ hipError_t probe_segments(hipStream_t st, const uint8_t *data, const unsigned lo
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
 // block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
 // read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the
-// skip masks of the mask / compaction passes (sp.skip_move) and of the rANS coder (au.skip_ans), and f.hist made K's where a
-// block stays kind 3 (sp.is3 stays the candidate's: a block is kind 3 when it is set and au.pick5 is not).  Behind the passes: ct_enc_sparse_kind's and ct_enc_ans_kind's sibling (actual sizes, the raw
-// rule, f.only = the Huffman encoder's skip mask, au.skip_ans = the placing kernel's)
+// skip masks of the mask / compaction passes (sp.skip_move) and of the rANS coder (an.skip_ans), and f.hist made K's where a
+// block stays kind 3 (sp.is3 stays the candidate's: a block is kind 3 when it is set and au.pick5 is not).  Behind the passes,
+// ct_enc_kind0 gives the actual sizes
 hipError_t ct_enc_auto_candidates(hipStream_t st, const SpSegs &g, const CtEncSparse &sp, const CtEncAuto &au, const uint32_t *hist,
                                   const uint8_t *ans_tab, unsigned long long *in_off, unsigned long long *in_len);
-hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
-                              uint32_t nb, uint32_t blk_len);
-hipError_t ct_enc_auto_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAuto &au,
-                            const AnsScratch &sc, uint32_t nb, uint32_t blk_len, const CtEncState *state);
+hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncAns &an,
+                              const CtEncAuto &au, uint32_t nb, uint32_t blk_len);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,

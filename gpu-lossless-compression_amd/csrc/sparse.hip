@@ -187,7 +187,7 @@ hipError_t sparse_join(hipStream_t st, const SpSegs &g)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// the container encoder's steps around them (container_api.cpp, Encoder::frame_huff0 with the sparse mode on)
+// the container encoder's steps around them (container_api.cpp, Encoder::frame_sparse)
 // ---------------------------------------------------------------------------------------------------------------------
 // fill = the block's most frequent byte, the lowest value on a tie: one wave per block, four symbols a lane
 __global__ __launch_bounds__(256) void k_sp_fill(const uint32_t *__restrict__ hist, uint32_t nb, uint32_t *__restrict__ fill)
@@ -227,24 +227,6 @@ __global__ __launch_bounds__(SP_THREADS) void k_sp_decide(SpSegs g, CtEncSparse 
     in_len[b] = is3 ? klen : L;
 }
 
-// ct_enc_kind0 with the sparse mode on: a kind-3 record is its mask and, when anything is kept, the stream of K; the raw
-// rule applies to whichever kind was chosen.  f.only (the encoder's skip mask) also names the kind-3 blocks with nothing kept.
-__global__ __launch_bounds__(256) void k_sp_kind(CtEncFrame f, CtEncHuff0 h, CtEncSparse sp, uint32_t nb, uint32_t blk_len,
-                                                 unsigned long long table_bytes, const CtEncState *state)
-{
-    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
-    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
-    if (b >= nb) return;
-    const bool is3 = sp.is3[b] != 0;
-    const unsigned long long klen = sp.klen[b], mw = sp_mask_words(blk_len);
-    const unsigned long long words = is3 ? mw + (klen ? h.nun[b] : 0ull) : h.nun[b];
-    const bool raw = 4ull * words >= blk_len;
-    f.kind[b] = raw ? CT_KIND_RAW : is3 ? CT_KIND_SPARSE : CT_KIND_HUFF0;
-    f.only[b] = raw || (is3 && klen == 0) ? 1u : 0u;
-    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
-    f.bwt[b] = !raw && is3 ? (int)(sp.fill[b] & 255u) : 0;
-}
-
 // behind the payload offsets: the masks into the kind-3 records (those that end inside the capacity), and where every
 // block's stream starts
 __global__ __launch_bounds__(256) void k_sp_place(CtEncFrame f, CtEncSparse sp, uint32_t blk_len, uint32_t *out, unsigned long long cap_words)
@@ -268,14 +250,6 @@ hipError_t ct_enc_sparse_decide(hipStream_t st, const SpSegs &g, const CtEncSpar
 hipError_t ct_enc_sparse_fill(hipStream_t st, const uint32_t *hist, uint32_t nb, uint32_t *fill)
 {
     hipLaunchKernelGGL(k_sp_fill, dim3((nb + 3) / 4), dim3(256), 0, st, hist, nb, fill);
-    return hipGetLastError();
-}
-
-hipError_t ct_enc_sparse_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, uint32_t nb,
-                              uint32_t blk_len, const CtEncState *state)
-{
-    const CtTables T = ct_tables(nb, blk_len);
-    hipLaunchKernelGGL(k_sp_kind, dim3((nb + 255) / 256), dim3(256), 0, st, f, h, sp, nb, blk_len, 4 * T.words, state);
     return hipGetLastError();
 }
 

@@ -199,8 +199,8 @@ __global__ __launch_bounds__(256) void k_zr_empty(CtEncRuns r, uint32_t nb)
     if (b < nb) r.skip_b[b] = r.seg_len[nb + b] == 0 ? 1u : 0u;
 }
 
-// ct_enc_kind0 with the runs mode on (one workgroup per block): nz from B's counts; the record is nz, the pairs, the stream of
-// A and, when B is not empty, the stream of B; raw when 4 * words >= blk_len, and no other kind
+// ct_enc_kind with the runs mode on (one workgroup per block): nz from B's counts; the record is nz, the pairs, the stream of
+// A and, when B is not empty, the stream of B; raw under the record rule, and no other kind
 __global__ __launch_bounds__(256) void k_zr_kind(CtEncFrame f, CtEncRuns r, uint32_t nb, uint32_t blk_len, unsigned long long table_bytes,
                                                  const CtEncState *state)
 {
@@ -211,12 +211,9 @@ __global__ __launch_bounds__(256) void k_zr_kind(CtEncFrame f, CtEncRuns r, uint
     uint32_t nz = 0;
     (void)block_excl_add<256>(c ? 1u : 0u, s_tmp, &nz);
     if (tid) return;
-    if (b == 0) *f.start = (state->cursor + CT_FRAME_HDR + table_bytes) / 4;
     const unsigned long long words = 1ull + nz + r.nun[b] + (nB ? r.nun[nb + b] : 0ull);
-    const bool raw = 4ull * words >= blk_len;
-    f.kind[b] = raw ? CT_KIND_RAW : CT_KIND_RUNS;
+    const bool raw = ct_put_record(f, b, CT_KIND_RUNS, words, blk_len, table_bytes, state);
     f.only[b] = raw ? 1u : 0u;
-    f.size[b] = raw ? ct_raw_words(blk_len) : (uint32_t)words;
     r.nz[b] = nz;
     r.skip_enc[b] = raw ? 1u : 0u;
     r.skip_enc[nb + b] = raw || nB == 0 ? 1u : 0u;

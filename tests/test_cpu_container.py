@@ -140,3 +140,18 @@ def test_plain_c_caller_compiles_and_links_with_gcc(glc, tmp_path):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     assert os.path.exists(exe)
+
+
+def test_the_settings_checker_under_the_host_sanitizers(tmp_path):
+    """tools/ct_settings_check.cpp: the setters' rule, format_of() and reader() of csrc/container_internal.h against a
+    restatement of the rule they replaced, over every state setter calls can reach from the default; a host-only build with the
+    address and undefined-behaviour sanitizers, run on the CPU"""
+    hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    exe = str(tmp_path / "ct_settings_check")
+    flags = ["-x", "hip", "--cuda-host-only", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    r = subprocess.run([hipcc] + flags + [os.path.join(ROOT, "tools", "ct_settings_check.cpp"), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and "ct_settings_check: ok, 42 states, " in r.stdout, r.stdout + r.stderr
