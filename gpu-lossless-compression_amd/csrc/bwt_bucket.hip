@@ -55,6 +55,11 @@ constexpr uint32_t FS_BIN_BITS = GLC_FS_BIN_BITS, FS_BINS = 1u << FS_BIN_BITS;
 #endif
 constexpr uint32_t FSS_LOOK = GLC_FSS_LOOK;         // k_fs_sort_bwt's rank step: words from a bin's start compared in straight-line code
 constexpr uint32_t FS_MAX_GROUP = 512;              // longest run of equal codes ranked by direct count
+// k_fs_sort_bwt: a bin start is a 16-bit entry that holds at most FS_FILLMAX: the bits above FS_START_MASK are free, and the
+// top one says "this bin has more than FSS_LOOK words" (set by the words that arrived as its fifth and later)
+constexpr uint32_t FS_START_MASK = 0x0FFFu, FS_BIG_BIN = 0x8000u;
+static_assert(FS_FILLMAX <= FS_START_MASK, "a bin start and the end of the last bin fit below the big-bin flag");
+constexpr uint32_t FSS_SENT = 2 * FSS_LOOK;         // k_fs_sort_bwt: sentinels behind the last word (the rare case looks at 2 FSS_LOOK keys from a bin's start)
 
 // at least 16 buckets: k_fs_sort compares bits 28..59 of the words, so the four bits above must be bucket number
 uint32_t fs_bucket_log2(uint32_t n)
@@ -652,7 +657,13 @@ __global__ __launch_bounds__(FSS_NT) void k_fs_sort(uint32_t n, uint32_t nbl, co
 //     1 .. c / 512 are full and run under a uniform branch alone (k_fs_sort: `i < c` in every round of every loop);
 //   * the rare cases of the rank step -- a bin of more than four words, another word with the same code -- are found
 //     per wave with ONE ballot and handled behind a wave-uniform branch (k_fs_sort: three nested divergent branches per
-//     item, executed or not);
+//     item, executed or not).  "More than four words" is a flag in the bin's start entry, set by the words that arrived
+//     fifth and later (3e-4 of them), so the rank step reads a bin's start only; behind the branch a word reads the
+//     bin's end and the next four keys with one wait and finishes a bin of up to eight in straight-line code -- the
+//     serial walk of the bin, one dependent LDS read per member in front of the workgroup's barrier, is left to bins of
+//     nine and more (profiles/sort_rank_tail.md);
+//   * whether the workgroup has work-list entries to write is its own counter s_wl read behind the barrier that is
+//     there anyway, not a workgroup-wide OR;
 //   * the row of suffix 0 (the BWT index) is looked for in the ONE bucket k_fs_part2 saw it go to (zero_bucket), not in
 //     every word of every bucket -- behind a branch the compiler cannot fold into the words' own conditions (it did: the
 //     compares ran for every slot of every workgroup and the bucket test was ANDed in last);
@@ -679,7 +690,7 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                                                         uint32_t wl_cap, uint32_t *__restrict__ wl_count,
                                                         const uint32_t *__restrict__ zero_bucket)
 {
-    __shared__ uint64_t s_w[FS_FILLMAX + FSS_LOOK];            // + sentinels behind the last word
+    __shared__ uint64_t s_w[FS_FILLMAX + FSS_SENT];            // + sentinels behind the last word
     __shared__ uint32_t s_cp[FS_BINS / 2 + 1];                 // bin counters, then bin starts (two 16-bit values per word), then BWT bytes
     __shared__ uint32_t s_tmp[FSS_NT / 64 + 1];
     __shared__ uint32_t s_deep, s_wl;
@@ -755,6 +766,31 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             if (eq > 1) { grp = (at << 16) | eq; at += eqb; }
         }
     };
+    // ... with the bin's end and the keys at gs + FSS_LOOK .. gs + 2 FSS_LOOK - 1 read together (one wait; k1 = the keys at
+    // gs .. gs + FSS_LOOK - 1, which the rank step has in registers): a bin of up to 2 FSS_LOOK words is finished from the
+    // eight keys in straight-line code with no bounds -- what lies behind the bin's end is a larger code or a sentinel (a key
+    // of all ones could tie with a sentinel: it takes the loop, which stops at the bin's end).  Only a longer bin (6e-8 of
+    // the words of i.i.d. data) walks the loop otherwise.
+    auto rank_rare2 = [&](uint32_t key, uint32_t p, uint32_t gs, const uint32_t *k1, uint32_t &at, uint32_t &grp) __attribute__((always_inline)) {
+        const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * (gs + FSS_LOOK) + 1;
+        uint32_t k2[FSS_LOOK];
+#pragma unroll
+        for (uint32_t t = 0; t < FSS_LOOK; t++) k2[t] = B[2 * t];
+        const uint32_t ge = s16[((key >> kshift) & (FS_BINS - 1)) + 1] & FS_START_MASK;
+        if ((ge - gs > 2 * FSS_LOOK) | (key == 0xFFFFFFFFu)) rank_rare(key, p, gs, ge, at, grp);
+        else {
+            uint32_t ls = 0, em = 0;                           // em: bit t = the key at gs + t is mine
+#pragma unroll
+            for (uint32_t t = 0; t < 2 * FSS_LOOK; t++) {
+                const uint32_t kq = t < FSS_LOOK ? k1[t < FSS_LOOK ? t : 0] : k2[t < FSS_LOOK ? 0 : t - FSS_LOOK];
+                ls += kq < key ? 1u : 0u;
+                em |= kq == key ? 1u << t : 0u;
+            }
+            const uint32_t eq = __builtin_popcount(em);
+            at = gs + ls;
+            if (eq > 1) { grp = (at << 16) | eq; at += __builtin_popcount(em & ((1u << (p - gs)) - 1u)); }
+        }
+    };
     // 3. (every instance) tied groups -> the block's work list.  Entries are reserved with ONE global atomic per workgroup.
     //    (Round 5: the ~1.5 us a workgroup sits out for its return are NOT on the kernel's critical path -- with entries of the
     //    bucket's own and no atomic at all the kernel ran 3.50 against 3.47 ms per GiB, and k_fs_ties, which then has to walk
@@ -763,10 +799,14 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         const uint32_t gp = grp >> 16, gs = grp & 0xFFFFu;
         if (pos == gp) reinterpret_cast<uint32_t *>(s_w)[2 * gp + 1] = atomicAdd(&s_wl, gs);   // (the codes are dead)
     };
-    auto wl_base = [&](bool any) __attribute__((always_inline)) -> uint32_t {   // 0xFFFFFFFF: nothing to write
-        if (!__syncthreads_or((int)any)) return 0xFFFFFFFFu;
+    auto wl_base = [&]() __attribute__((always_inline)) -> uint32_t {   // 0xFFFFFFFF: nothing to write
+        // every tied group's size is in s_wl (wl_reserve) before this barrier, which is also the one between the staged
+        // bytes and the row stores: s_wl != 0 is "some thread of the workgroup has an entry to write" (a workgroup-wide OR
+        // of the threads' own flags -- a DPP reduce, an LDS exchange and two barriers -- cost 0.3 ms per 2048-block launch)
+        __syncthreads();
+        const uint32_t tot = s_wl;
+        if (tot == 0) return 0xFFFFFFFFu;                      // (uniform)
         if (tid == 0) {
-            const uint32_t tot = s_wl;
             uint32_t base = atomicAdd(&wl_count[b], tot);
             if (base + tot > wl_cap) { atomicOr(&flag[b], 4u); base = 0xFFFFFFFFu; }   // list full: block flagged
             s_deep = base;
@@ -789,7 +829,7 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         if (v0) w[0] = K[i0];
 #pragma unroll
         for (int r = 1; r <= FULL; r++) w[r] = r <= FSS_SPEC ? ws[r <= FSS_SPEC ? r : 0] : K[(r - 1) * FSS_NT + tid];
-        if (tid < FSS_LOOK) s_w[cc + tid] = ~0ull;             // what the rank step reads past the last bin compares as larger
+        if (tid < FSS_SENT) s_w[cc + tid] = ~0ull;             // what the rank step reads past the last bin compares as larger
         __syncthreads();
         if (s_deep) return false;                              // flagged: the block is another sorter's
         // 1. counting sort on the 12 bits below the bucket number (arrival order inside a bin: any order will do)
@@ -805,30 +845,45 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         __syncthreads();
         bin_starts();
         __syncthreads();
+        {
+            // the words that arrived fifth and later in their bin (3e-4 of them) flag it as big: the rank step then needs the
+            // bin's start only.  The starts are read masked: a flag may or may not be in yet.
+            uint32_t st[NS];
+            st[0] = 0;
+            if (v0) st[0] = s16[bin[0]];
 #pragma unroll
-        for (int r = 1; r < NS; r++) rk[r] += s16[bin[r]];
-        if (v0) s_w[s16[bin[0]] + rk[0]] = sorted_word(w[0]);
+            for (int r = 1; r < NS; r++) st[r] = s16[bin[r]];
+            bool late = false;
+#pragma unroll
+            for (int r = 0; r < NS; r++) late |= rk[r] >= FSS_LOOK;
+            if (late) {
+#pragma unroll
+                for (int r = 0; r < NS; r++)
+                    if (rk[r] >= FSS_LOOK) atomicOr(&s_cp[bin[r] >> 1], FS_BIG_BIN << (16 * (bin[r] & 1)));
+            }
+#pragma unroll
+            for (int r = 0; r < NS; r++) rk[r] += st[r] & FS_START_MASK;
+            if (v0) s_w[rk[0]] = sorted_word(w[0]);
+        }
 #pragma unroll
         for (int r = 1; r < NS; r++) s_w[rk[r]] = sorted_word(w[r]);
         __syncthreads();
         // 2. final position = bin start + number of smaller codes in the bin (thread = the words at positions i0 / (r - 1) NT +
         //    tid of the bin-sorted array).  The four words from the bin start are compared in straight-line code with no bounds
-        //    at all -- what lies behind the bin's end is a larger code or a sentinel; a bin of more than four, or a second word
-        //    with my code among the four, is the rare case: detected per wave, redone exactly over the whole bin.
-        uint32_t pos[NS], grp[NS], gs[NS], ge[NS];             // grp = group start << 16 | group size (0: not tied)
+        //    at all -- what lies behind the bin's end is a larger code or a sentinel; a bin of more than four (flagged in its
+        //    start entry: the bin's end is not read here), or a second word with my code among the four, is the rare case:
+        //    detected per wave, redone exactly with a second look at the next four keys (rank_rare2).
+        uint32_t pos[NS], grp[NS], gs[NS];                     // grp = group start << 16 | group size (0: not tied)
+        bool big[NS];                                          // the bin holds more than FSS_LOOK words
         if (v0) w[0] = s_w[i0];
 #pragma unroll
         for (int r = 1; r < NS; r++) w[r] = s_w[(r - 1) * FSS_NT + tid];
-        gs[0] = ge[0] = 0;
-        if (v0) {
-            const uint32_t bn = ((uint32_t)(w[0] >> 32) >> kshift) & (FS_BINS - 1);
-            gs[0] = s16[bn]; ge[0] = s16[bn + 1];
-        }
+        gs[0] = 0;
+        if (v0) gs[0] = s16[((uint32_t)(w[0] >> 32) >> kshift) & (FS_BINS - 1)];
 #pragma unroll
-        for (int r = 1; r < NS; r++) {
-            const uint32_t bn = ((uint32_t)(w[r] >> 32) >> kshift) & (FS_BINS - 1);
-            gs[r] = s16[bn]; ge[r] = s16[bn + 1];
-        }
+        for (int r = 1; r < NS; r++) gs[r] = s16[((uint32_t)(w[r] >> 32) >> kshift) & (FS_BINS - 1)];
+#pragma unroll
+        for (int r = 0; r < NS; r++) { big[r] = gs[r] > FS_START_MASK; gs[r] &= FS_START_MASK; }   // (the bin's end is read in the rare case only)
         uint32_t kq[NS][FSS_LOOK];
         if (v0) {
             const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs[0] + 1;
@@ -852,13 +907,13 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                 eqt += kq[r][t] == key ? 1u : 0u;
             }
             pos[r] = gs[r] + less; grp[r] = 0;
-            rare[r] = ((ge[r] - gs[r] > FSS_LOOK) | (eqt > 1)) & (r > 0 || v0);
+            rare[r] = (big[r] | (eqt > 1)) & (r > 0 || v0);
             rare_any |= rare[r];
         }
         if (__builtin_amdgcn_ballot_w64(rare_any) != 0) {      // (wave-uniform)
 #pragma unroll
             for (int r = 0; r < NS; r++)
-                if (rare[r]) rank_rare((uint32_t)(w[r] >> 32), r ? (r - 1) * FSS_NT + tid : i0, gs[r], ge[r], pos[r], grp[r]);
+                if (rare[r]) rank_rare2((uint32_t)(w[r] >> 32), r ? (r - 1) * FSS_NT + tid : i0, gs[r], kq[r], pos[r], grp[r]);
         }
         if (zb) {
             asm volatile("" ::: "memory");                     // (keeps the search behind the branch: see the header)
@@ -879,7 +934,7 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             for (int r = 0; r < NS; r++)
                 if (grp[r]) wl_reserve(pos[r], grp[r]);
         }
-        const uint32_t base = wl_base(tied != 0);
+        const uint32_t base = wl_base();
         if (base != 0xFFFFFFFFu && tied) {
 #pragma unroll
             for (int r = 0; r < NS; r++)
@@ -897,7 +952,7 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
 #pragma unroll
         for (int r = FSS_SPEC + 1; r < FSS_ITEMS; r++)
             if ((uint32_t)r <= full) w[r] = K[(r - 1) * FSS_NT + tid];
-        if (tid < FSS_LOOK && cc) s_w[cc + tid] = ~0ull;       // what the rank step reads past the last bin compares as larger
+        if (tid < FSS_SENT && cc) s_w[cc + tid] = ~0ull;       // what the rank step reads past the last bin compares as larger
         __syncthreads();
         if (s_deep || cc == 0) return false;                   // flagged: the block is another sorter's
         // 1. counting sort
@@ -919,7 +974,10 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         __syncthreads();
         {
             auto scatter = [&](int r) {
-                s_w[s16[((uint32_t)(w[r] >> 32) >> hshift) & (FS_BINS - 1)] + rk[r]] = sorted_word(w[r]);
+                const uint32_t bin = ((uint32_t)(w[r] >> 32) >> hshift) & (FS_BINS - 1);
+                const uint32_t st = s16[bin];
+                if (rk[r] >= FSS_LOOK) atomicOr(&s_cp[bin >> 1], FS_BIG_BIN << (16 * (bin & 1)));   // (see rounds<>)
+                s_w[(st & FS_START_MASK) + rk[r]] = sorted_word(w[r]);
             };
             if (v0) scatter(0);
 #pragma unroll
@@ -937,19 +995,19 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
                 w[r] = wv;
                 const uint32_t key = (uint32_t)(wv >> 32);     // inside a bin only the low 32 bits of the code can differ
                 const uint32_t bin = (key >> kshift) & (FS_BINS - 1);
-                const uint32_t gs = s16[bin], ge = s16[bin + 1];
-                uint32_t less = 0, eqt = 0;
+                const uint32_t gf = s16[bin], gs = gf & FS_START_MASK;
+                uint32_t less = 0, eqt = 0, kq[FSS_LOOK];
                 const uint32_t *B = reinterpret_cast<const uint32_t *>(s_w) + 2 * gs + 1;
 #pragma unroll
                 for (uint32_t t = 0; t < FSS_LOOK; t++) {
-                    const uint32_t kq = B[2 * t];
-                    less += kq < key ? 1u : 0u;
-                    eqt += kq == key ? 1u : 0u;
+                    kq[t] = B[2 * t];
+                    less += kq[t] < key ? 1u : 0u;
+                    eqt += kq[t] == key ? 1u : 0u;
                 }
                 uint32_t at = gs + less;
-                const bool rare = (ge - gs > FSS_LOOK) | (eqt > 1);
+                const bool rare = (gf > FS_START_MASK) | (eqt > 1);
                 if (__builtin_amdgcn_ballot_w64(rare) != 0) {  // (wave-uniform)
-                    if (rare) rank_rare(key, p, gs, ge, at, grp[r]);
+                    if (rare) rank_rare2(key, p, gs, kq, at, grp[r]);
                 }
                 pos[r] = at;
             };
@@ -966,13 +1024,12 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
         }
         __syncthreads();                                       // s_cp (bin starts) is dead from here: it takes the BWT bytes
         if (s_deep) { if (tid == 0) atomicOr(&flag[b], 2u); return false; }
-        bool any = false;
 #pragma unroll
         for (int r = 0; r < FSS_ITEMS; r++) {
             if (pos[r] != 0xFFFFFFFFu) s_cb[shift + pos[r]] = (uint8_t)w[r];      // (rows of tied groups are rewritten by k_fs_ties)
-            if (grp[r]) { any = true; wl_reserve(pos[r], grp[r]); }
+            if (grp[r]) wl_reserve(pos[r], grp[r]);
         }
-        const uint32_t base = wl_base(any);
+        const uint32_t base = wl_base();
         if (base != 0xFFFFFFFFu) {
 #pragma unroll
             for (int r = 0; r < FSS_ITEMS; r++)
