@@ -12,7 +12,10 @@
 // frame_ans's, kind 5, the histograms alone and the kernels of ans.hip; with the auto mode on frame_auto's, the probe of auto.hip and a kind per block out of 2, 3 and 5).  With the BWT codec's
 // runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
-// chain on the device (a cursor word): no host read inside or between frames, one at the end.
+// chain on the device (a cursor word): no host read inside or between frames, one at the end.  With the CHOOSE codec
+// (super_frame) the bigram probe of choose.hip runs over what is one frame otherwise, its stats rows are read back (the one host
+// read per such group), the rule of choose_rule.h picks the BWT or the order-0 codec per block, and every maximal run of blocks of
+// one choice becomes one frame by that codec's path above: format version 3, kinds 0, 1 and 2, no reader change.
 // Decode: decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from the caller's
 // device buffers or from a Source through staging; the frame index (glcContainerIndex*) is the same walk without the decoding,
 // and a range read (glcContainerReadRange*) decodes a subset of the blocks of the frames its range overlaps.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
@@ -74,6 +77,13 @@ CUDPPResult fail(CUDPPHandle plan, unsigned long long what, unsigned long long f
 {
     set_error(plan, what, frame, block);
     return what == CT_CAPACITY ? CUDPP_ERROR_ILLEGAL_CONFIGURATION : CUDPP_ERROR_UNKNOWN;
+}
+
+// what glcContainerLastChoice reports: the last successful compress of the plan, kept with it
+void set_choice(CUDPPHandle plan, const unsigned long long v[3])
+{
+    unsigned long long *c = plan_container_choice(plan);
+    for (int i = 0; i < 3; i++) c[i] = v[i];
 }
 
 CUDPPResult hip_res(hipError_t e)
@@ -172,6 +182,8 @@ struct Encoder {
     CtEncAns an = {};                                         // the rANS mode's, behind h0's; a plan that never has it on has none
     CtEncAuto au = {};                                        // the auto mode's: both scratches above and its own
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
+    unsigned long long *ch_stats = nullptr, *h_stats = nullptr;   // the CHOOSE codec's probe rows [rows][4]: device, pinned
+    unsigned long long choice[3] = {0, 0, 0};                 // blocks given to the BWT codec, to the order-0 codec; frames
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
     void carve_runs(Carver &c)
@@ -262,6 +274,7 @@ struct Encoder {
             f.tcrc = c.take<uint32_t>(2);
             c.round(256);
         }
+        if (codec == CT_CODEC_CHOOSE) ch_stats = c.take<unsigned long long>(CHOOSE_STATS * R);
     }
 
     hipError_t init()
@@ -271,7 +284,8 @@ struct Encoder {
         codec = s.codec;
         mode = s.mode;
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
-        if (codec == CT_CODEC_HUFF0) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
+        if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
+        if (codec == CT_CODEC_CHOOSE) CT_HIP(hipHostMalloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows, hipHostMallocDefault));
         if (fmt.filtered()) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
@@ -286,12 +300,19 @@ struct Encoder {
             },
             [&](Carver &c) { carve(c); });
     }
-    ~Encoder() { if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); } }
+    ~Encoder()
+    {
+        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); }
+        if (h_stats) (void)hipHostFree(h_stats);
+    }
 
     // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With a filter the frame
     // goes through it as one segment into staging and its blocks are cut from there; the input's own bytes still make crc_all.
-    CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
+    // `by`: the codec that writes this frame (the plan's, or what the CHOOSE codec picked for its blocks).
+    CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap, uint32_t by)
     {
+        choice[by == CT_CODEC_BWT ? 0 : 1] += nb;
+        choice[2]++;
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
         const CtEncFrame &f = fr[P.parity];
         const uint8_t *orig = nullptr;
@@ -302,7 +323,7 @@ struct Encoder {
             d_in = stage[P.parity];
         }
         if (mode == CT_MODE_RUNS) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
-        if (codec == CT_CODEC_HUFF0) {
+        if (by == CT_CODEC_HUFF0) {
             const Frame0 F{f, d_in, orig, nb, blk_len, out, cap};
             return mode == CT_MODE_SPARSE ? frame_sparse(F) : mode == CT_MODE_ANS ? frame_ans(F) : mode == CT_MODE_AUTO ? frame_auto(F) :
                                             frame_plain(F);
@@ -474,6 +495,29 @@ struct Encoder {
         return CUDPP_SUCCESS;
     }
 
+    // The CHOOSE codec's super-frame (what is one frame with the other codecs): the bigram probe of its blocks, their stats rows
+    // read back in one copy and one wait, the rule on the host (choose_rule.h), and one frame per maximal run of blocks of one
+    // choice, each by that codec's own path at the device cursor.  An order-0 frame is wholly on the plan's stream, so it waits
+    // for what a pipelined BWT frame in front of it still has on the side stream (the cursor and the running CRC chain there).
+    CUDPPResult super_frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap)
+    {
+        CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, nb, blk_len));
+        CT_TRY(bigram_probe_segments(P.st, d_in, h0.blk_off, h0.blk_len, nb, blk_len, ch_stats));
+        CT_TRY(hipMemcpyAsync(h_stats, ch_stats, 8 * CHOOSE_STATS * (size_t)nb, hipMemcpyDeviceToHost, P.st));
+        CT_TRY(hipStreamSynchronize(P.st));
+        auto by = [&](uint32_t b) { return choose_bwt(blk_len, h_stats + CHOOSE_STATS * (size_t)b) ? CT_CODEC_BWT : CT_CODEC_HUFF0; };
+        for (uint32_t a = 0; a < nb;) {
+            const uint32_t c = by(a);
+            uint32_t b = a + 1;
+            while (b < nb && by(b) == c) b++;
+            if (c == CT_CODEC_HUFF0) plan_join(P.h);
+            const CUDPPResult r = frame(d_in + (size_t)a * blk_len, b - a, blk_len, out, cap, c);
+            if (r != CUDPP_SUCCESS) return r;
+            a = b;
+        }
+        return CUDPP_SUCCESS;
+    }
+
     // every frame of [d_in, + len) with the plan's n and rows
     CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap)
     {
@@ -482,7 +526,7 @@ struct Encoder {
             const unsigned long long left = len - pos;
             const uint32_t nb = left >= P.n ? (uint32_t)std::min<unsigned long long>(P.rows, left / P.n) : 1u;
             const uint32_t bl = left >= P.n ? P.n : (uint32_t)left;
-            const CUDPPResult r = frame(d_in + pos, nb, bl, out, cap);
+            const CUDPPResult r = codec == CT_CODEC_CHOOSE ? super_frame(d_in + pos, nb, bl, out, cap) : frame(d_in + pos, nb, bl, out, cap, codec);
             if (r != CUDPP_SUCCESS) return r;
             pos += (unsigned long long)nb * bl;
         }
@@ -784,7 +828,8 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     DevBuf din[2], dout;
     const size_t inb = (size_t)std::min(fmax, std::max(len, 1ull));
     for (int i = 0; i < 2; i++) { CT_TRY(hin[i].reserve(inb)); CT_TRY(din[i].reserve(inb)); }
-    const unsigned long long ocap = frame_bound(E.P.rows, E.P.n) + frame_bound(1, E.P.n) + CT_TRAILER;   // (a last chunk: blocks + tail)
+    // (a last chunk: blocks + tail; with the CHOOSE codec a chunk may come out as one frame per block)
+    const unsigned long long ocap = (E.codec == CT_CODEC_CHOOSE ? E.P.rows * frame_bound(1, E.P.n) : frame_bound(E.P.rows, E.P.n) + frame_bound(1, E.P.n)) + CT_TRAILER;
     CT_TRY(dout.reserve(ocap));
     CT_TRY(hout.reserve(ocap));
     uint32_t hdr[8];
@@ -838,6 +883,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     if (!out.write(hout.p, CT_TRAILER)) return fail(plan, CT_CAPACITY);
     total += CT_TRAILER;
     if (outLen) *outLen = total;
+    set_choice(plan, E.choice);
     set_error(plan, CT_OK);
     return CUDPP_SUCCESS;
 }
@@ -1374,6 +1420,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(hipMemcpyAsync(&total, d_outLen, 8, hipMemcpyDeviceToHost, E.P.st));
     CT_TRY(hipStreamSynchronize(E.P.st));
     if (total > cap) return fail(plan, CT_CAPACITY);
+    set_choice(plan, E.choice);
     set_error(plan, CT_OK);
     return CUDPP_SUCCESS;
 }
@@ -1625,6 +1672,28 @@ CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_o
         (reinterpret_cast<uintptr_t>(d_uniform) & 3)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CT_TRY(probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
                           (uint32_t)maxLen, d_hist, d_uniform));
+    return CUDPP_SUCCESS;
+}
+
+// the bigram probe: a bad argument is refused before anything is enqueued
+CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, unsigned long long *d_stats, void *stream)
+{
+    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_inBase || !d_offsets || !d_lengths || !d_stats || (reinterpret_cast<uintptr_t>(d_stats) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(bigram_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
+                                 (uint32_t)count, (uint32_t)maxLen, d_stats));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerLastChoice(CUDPPHandle plan, unsigned long long out[3])
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const unsigned long long *c = plan_container_choice(plan);
+    for (int i = 0; i < 3; i++) out[i] = c[i];
     return CUDPP_SUCCESS;
 }
 

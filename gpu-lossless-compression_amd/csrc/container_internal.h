@@ -5,6 +5,7 @@
 #include "glc_internal.h"
 #include "ans_coder.h"
 #include "auto_rule.h"
+#include "choose_rule.h"
 
 #include <functional>
 
@@ -238,12 +239,15 @@ constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 r
 constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
 constexpr uint32_t CT_KIND_ANS = 5;                          // rANS order-0 record (ans.hip): chunk unit counts, then every chunk's 64 states and units; version 7
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
+// CHOOSE: the writer gives each block to one of the two codecs (choose_rule.h) and cuts a frame wherever the choice changes.  It
+// takes no mode (each belongs to one codec) and no filter (a filter is per frame, and the choice would be made on filtered bytes)
+constexpr uint32_t CT_CODEC_CHOOSE = 4;                      // (2 and 3 stay refused: callers and tests have long used them as the bad value)
 // the writer's mode: which record kinds beyond its codec's plain ones it may emit (3; 4; 5; 3 and 5).  At most one is on, and
 // each belongs to one codec: runs to the BWT codec, sparse, rANS and auto to the order-0 codec
 enum CtMode : uint32_t { CT_MODE_PLAIN = 0, CT_MODE_SPARSE, CT_MODE_RUNS, CT_MODE_ANS, CT_MODE_AUTO };
 __host__ __device__ inline bool ct_mode_fits(CtMode mode, uint32_t codec)
 {
-    return mode == CT_MODE_PLAIN || codec == (mode == CT_MODE_RUNS ? CT_CODEC_BWT : CT_CODEC_HUFF0);
+    return mode == CT_MODE_PLAIN || codec == (mode == CT_MODE_RUNS ? CT_CODEC_BWT : CT_CODEC_HUFF0);   // (none fits CHOOSE)
 }
 
 // failure classes of glcContainerLastError (out[0])
@@ -392,13 +396,14 @@ bool plan_info(CUDPPHandle plan, uint32_t *n, uint32_t *rows, hipStream_t *st, u
 void plan_join(CUDPPHandle plan);                          // the plan's stream waits for its internal one
 // the container settings of a COMPRESS plan's encoder (glcPlanSetContainer*): the filter's element size (0 = off), its delta
 // mode (only ever on with the shuffle on), the codec (CT_CODEC_*) and the mode (only ever one that ct_mode_fits() the codec).
-// The set_*() are the whole rule of the public setters: false = refused, nothing changed.
+// The CHOOSE codec is only ever on with the shuffle off.  The set_*() are the whole rule of the public setters: false = refused,
+// nothing changed.
 inline bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
 struct CtSettings {
     uint32_t shuffle = 0; bool delta = false; uint32_t codec = CT_CODEC_BWT; CtMode mode = CT_MODE_PLAIN;
     bool set_shuffle(uint32_t elem)
     {
-        if (elem > 1 && !shuffle_elem_ok(elem)) return false;
+        if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE)) return false;
         shuffle = elem > 1 ? elem : 0;
         if (elem <= 1) delta = false;                         // (no delta without the shuffle)
         return true;
@@ -411,7 +416,7 @@ struct CtSettings {
     }
     bool set_codec(uint32_t c)
     {
-        if (c != CT_CODEC_BWT && c != CT_CODEC_HUFF0) return false;
+        if (c != CT_CODEC_BWT && c != CT_CODEC_HUFF0 && (c != CT_CODEC_CHOOSE || shuffle)) return false;
         codec = c;
         if (!ct_mode_fits(mode, codec)) mode = CT_MODE_PLAIN;  // (no mode without its codec)
         return true;
@@ -435,7 +440,8 @@ struct CtSettings {
     uint32_t kinds() const
     {
         const bool k3 = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, k5 = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
-        return 1u << CT_KIND_RAW | 1u << (codec == CT_CODEC_HUFF0 ? CT_KIND_HUFF0 : CT_KIND_HUFF) | (k3 ? 1u << CT_KIND_SPARSE : 0u) |
+        return 1u << CT_KIND_RAW | (codec != CT_CODEC_HUFF0 ? 1u << CT_KIND_HUFF : 0u) | (codec != CT_CODEC_BWT ? 1u << CT_KIND_HUFF0 : 0u) |
+               (k3 ? 1u << CT_KIND_SPARSE : 0u) |
                (mode == CT_MODE_RUNS ? 1u << CT_KIND_RUNS : 0u) | (k5 ? 1u << CT_KIND_ANS : 0u);
     }
 };
@@ -452,6 +458,8 @@ inline CtFormat format_of(const CtSettings &s)
     return f;                                                 // (the setters accept only what some row takes)
 }
 CtSettings &plan_container_settings(CUDPPHandle plan);
+// {blocks given to the BWT codec, blocks given to the order-0 codec, frames} of the plan's last successful container compress
+unsigned long long *plan_container_choice(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
 bool plan_pipelined(CUDPPHandle plan);
@@ -567,6 +575,10 @@ hipError_t ct_enc_runs_place(hipStream_t st, const CtEncFrame &f, const CtEncRun
 // chunk included when it does).  The rows need not be zeroed.  Everything only enqueues on `st`.
 hipError_t probe_segments(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                           uint32_t count, uint32_t max_len, uint32_t *hist, uint32_t *uniform);
+// the bigram probe (choose.hip): row i of stats = {S2, SR, SC, M} of segment i (choose_rule.h), the segments as above.  Every row
+// is written whole.  Everything only enqueues on `st`.
+hipError_t bigram_probe_segments(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                                 uint32_t count, uint32_t max_len, unsigned long long *stats);
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
 // block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
 // read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the

@@ -660,11 +660,12 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcAnsEncodeSegments", "glcAnsDecodeSegments", "glcAnsSegmentsWorkBytes", "glcAnsBoundWords",
                      "glcPlanSetContainerAns", "glcPlanGetContainerAns",
                      "glcProbeSegments", "glcPlanSetContainerAuto", "glcPlanGetContainerAuto",
+                     "glcBigramProbeSegments", "glcContainerLastChoice",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
 RANGE_SYMBOLS = CONTAINER_SYMBOLS[-11:]                         # the frame index and the range reads
-CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0 = 0, 1
+CONTAINER_CODEC_BWT, CONTAINER_CODEC_HUFF0, CONTAINER_CODEC_CHOOSE = 0, 1, 4
 CONTAINER_WHAT = {0: "ok", 1: "stream header", 2: "frame table", 3: "record crc", 4: "decoded crc", 5: "truncated", 6: "capacity"}
 CONTAINER_HEADER_BYTES = 32
 
@@ -727,6 +728,8 @@ def _ct():
         L.glcPlanSetContainerAuto.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerAuto.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.glcBigramProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp]
+        L.glcContainerLastChoice.argtypes = [sz, ullp]
         L._ct_ready = True
     return L
 
@@ -818,7 +821,9 @@ def container_get_shuffle(plan):
 
 def container_set_codec(plan, codec):
     """the codec of the plan's container ENCODER: CONTAINER_CODEC_BWT (the default: format version 1 / 2) or CONTAINER_CODEC_HUFF0
-    (order-0 Huffman records, format version 3).  The decoder reads what was done from the stream and ignores this setting."""
+    (order-0 Huffman records, format version 3), or CONTAINER_CODEC_CHOOSE (one of the two per block, from the bigram probe; format
+    version 3 as well, frames cut where the choice changes; needs the filter off and takes no mode).  The decoder reads what was
+    done from the stream and ignores this setting."""
     _chk("glcPlanSetContainerCodec", _ct().glcPlanSetContainerCodec(plan.handle, int(codec)))
 
 
@@ -911,6 +916,24 @@ def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None
                                                      uniform.data_ptr(), stream))
     torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
     return hist[:n], uniform[:n]
+
+
+def bigram_probe_segments(d_in, offsets, lengths, max_len=None, stats=None, stream=None):
+    """the bigram probe of CONTAINER_CODEC_CHOOSE over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8
+    tensor d_in: an int64 tensor [count, 4] of rows {S2, SR, SC, M} (csrc/choose_rule.h).  stats: a tensor to write into."""
+    import torch
+    dev = d_in.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    n = off.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    stats = torch.empty((max(1, n), 4), dtype=torch.int64, device=dev) if stats is None else stats
+    assert stats.is_contiguous() and stats.dtype == torch.int64 and stats.numel() >= 4 * n
+    _chk("glcBigramProbeSegments", _ct().glcBigramProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
+                                                                 stats.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return stats[:n]
 
 
 def ans_bound_words(length):
@@ -1204,6 +1227,14 @@ def container_last_range_stats(plan):
     """(frames fetched, blocks decoded, container bytes fetched) of the plan's last successful range read"""
     a = (C.c_ulonglong * 3)()
     _chk("glcContainerLastRangeStats", _ct().glcContainerLastRangeStats(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
+def container_last_choice(plan):
+    """(blocks given to the BWT codec, blocks given to the order-0 codec, frames written) of the plan's last successful container
+    compress; with CONTAINER_CODEC_CHOOSE the rule's choices, counted before the record rule"""
+    a = (C.c_ulonglong * 3)()
+    _chk("glcContainerLastChoice", _ct().glcContainerLastChoice(plan.handle, a))
     return tuple(int(v) for v in a)
 
 

@@ -243,11 +243,31 @@ CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on);
  * pipelining on or off; the decoder ignores it (the stream says what was done) and reads every version.  The first HUFF0
  * encode allocates about 3 KiB of device scratch per row, the first version-3 decode 4 KiB per block of the largest frame plus
  * up to 256 MiB of span-function prefixes; both live as long as the plan, and a plan that only uses the BWT codec has neither.
- * The order-0 path never touches the sorter's scratch or statistics. */
+ * The order-0 path never touches the sorter's scratch or statistics.
+ *
+ * GLC_CONTAINER_CODEC_CHOOSE (value 4: 2 and 3 stay refused, the values callers have used to see a bad codec refused) picks one of
+ * the two per block ("choose"; csrc/choose_rule.h).  What is one frame
+ * with the other codecs -- up to `rows` blocks, the ragged tail on its own -- is probed first (glcBigramProbeSegments below), its
+ * stats rows are read back in one copy and one wait, and a block goes to the BWT codec exactly when it has at least 2048 bytes,
+ * SR > 0, SC > 0 and 2 * S2 * M * (M - 1) >= 3 * SR * SC (128-bit integers); every other block goes to the order-0 codec.  Each
+ * maximal run of blocks of one choice becomes one frame, written by that codec's own path, so a stream holds frames of any
+ * nb <= rows with kinds 0 and 1, or 2 and 1.  That is format version 3 as readers have accepted it since it exists: there is no
+ * new version, and any plan, a default one included, decodes, indexes and range-reads the stream.  The statistic sees local
+ * dependence only: a block that repeats a far-away region of noise stays order-0 (or raw).  CHOOSE needs the filter and every
+ * mode off: it is refused while the shuffle is on and otherwise clears the mode as every codec change does, and
+ * glcPlanSetContainerShuffle(plan, 2, 4 or 8) and every mode setter with on = 1 are refused while it is the codec (composing it
+ * with them is left open: a filter is per frame, a mode belongs to one codec).  All six container entry points honour it, with
+ * pipelining on or off, with the same bytes.  It allocates what both codecs allocate, 32 bytes per row for the probe, and for
+ * the host forms rows * (one block's worst frame) of output staging.  On one MI355X, 1 GiB in 1 MiB blocks, rows 512
+ * (profiles/choose_mode.md; ratio / encode / decode GB/s): text and Zipf bytes half and half in runs of 64 blocks 1.899 / 33.4 /
+ * 26.0 against BWT 1.723 / 35.8 / 41.5 and order-0 1.521 / 450.5 / 100.3 (BWT frames of 64 blocks decode slower than frames of
+ * 512); Zipf bytes alone the order-0 bytes at 291.7 GB/s against 434.9; text alone the BWT bytes at 24.1 against 25.0; the probe
+ * alone 1178 to 1199 GB/s. */
 enum GlcContainerCodec
 {
     GLC_CONTAINER_CODEC_BWT = 0,
-    GLC_CONTAINER_CODEC_HUFF0 = 1
+    GLC_CONTAINER_CODEC_HUFF0 = 1,
+    GLC_CONTAINER_CODEC_CHOOSE = 4                              /* (2 and 3 stay refused values, as callers have long relied on) */
 };
 CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec);
 CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec);
@@ -367,6 +387,21 @@ CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on);
 #define GLC_PROBE_MAX_COUNT ((size_t)1 << 22)
 CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                              size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_uniform, void *stream);
+
+/* The bigram probe of GLC_CONTAINER_CODEC_CHOOSE as a batched call (csrc/choose.hip).  The segments are those of glcProbeSegments.
+ * For 2 <= p < L the key of position p of a segment x of L bytes is the context (31 * x[p-2] + x[p-1]) & 255 and the symbol
+ * x[p]; N[a][b] counts the positions with context a and symbol b, R[a] and C[b] are its row and column sums.  Row i of d_stats is
+ * four 64-bit words {S2, SR, SC, M}: the sums of N (N - 1), R (R - 1) and C (C - 1), and the number of positions M = L - 2 (0 for
+ * L < 2), all exact.  S2 * M * (M - 1) / (SR * SC) is 1 for i.i.d. bytes at any length and grows with the dependence of a byte
+ * on the two before it.  Every row is written whole.  The call only enqueues on `stream`.  A bad argument (a null pointer with
+ * count > 0, rows not 8-byte aligned, a maxLen or count too large) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, unsigned long long *d_stats, void *stream);
+
+/* {blocks given to the BWT codec, blocks given to the order-0 codec, frames written} of the plan's last successful container
+ * compress, whatever its codec; with GLC_CONTAINER_CODEC_CHOOSE the first two are the rule's choices, counted before the record
+ * rule stores a block raw.  {0, 0, 0} before the first. */
+CUDPPResult glcContainerLastChoice(CUDPPHandle plan, unsigned long long out[3]);
 
 /* The auto mode of the ENCODER's order-0 codec: on = 1 writes format version 8, whose frames may hold kinds 0, 1, 2, 3 and 5 in any
  * mix (not 4), and picks a kind per block from the block's statistics alone ("the auto mode's rule").  One probe

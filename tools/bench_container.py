@@ -33,7 +33,12 @@ setting, and the split and the join alone (glcZeroRunSplitSegments / glcZeroRunJ
 device-to-device copy.  --runs-off-only runs the same section without ever touching the mode, which is also what a build without
 it can run.
 
-python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1]
+--codec 4 (with --data textlike, zipf or mix -- text-like and Zipf bytes half and half in runs of 64 blocks --; --rounds R, at least
+1) is the choose section: the BWT codec, the order-0 codec and the CHOOSE codec on the same bytes in R interleaved rounds timed with
+device events, ratio / encode / decode per codec and what glcContainerLastChoice reports, then the bigram probe alone against the
+auto mode's probe and a device-to-device copy.
+
+python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--runs | --runs-off-only]"""
 import argparse
 import json
@@ -44,7 +49,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0}
+DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0}
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -211,6 +216,71 @@ def runs_section(torch, glc, plan, d_in, total, rounds, with_runs):
     return res
 
 
+def choose_section(torch, glc, plan, d_in, total, rounds):
+    """the container with the BWT codec, the order-0 codec and the CHOOSE codec, interleaved as sparse_section does it; then the
+    bigram probe, the auto mode's probe and a copy over the same blocks"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = {"bwt": 0, "order0": 1, "choose": glc.CONTAINER_CODEC_CHOOSE}
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def enc():
+        glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+            plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr()))
+
+    def dec(clen):
+        glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr()))
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s, codec in settings.items():
+            glc.container_set_codec(plan, codec)
+            t_enc = event_timed(enc)
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: dec(clen))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["last_choice"] = list(glc.container_last_choice(plan))
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    glc.container_set_codec(plan, 0)
+    nseg = min(total // n, 512)
+    x = d_in[:nseg * n]
+    y = torch.empty_like(x)
+    off = torch.arange(nseg, dtype=torch.int64, device=x.device) * n
+    ln = torch.full((nseg,), n, dtype=torch.int64, device=x.device)
+    stats = torch.empty((nseg, 4), dtype=torch.int64, device=x.device)
+    hist, uni = (torch.empty((nseg, 256), dtype=torch.int32, device=x.device) for _ in range(2))
+    L = glc._ct()
+    bigram = lambda: glc._chk("glcBigramProbeSegments", L.glcBigramProbeSegments(x.data_ptr(), off.data_ptr(), ln.data_ptr(), nseg, n,
+                                                                                   stats.data_ptr(), None))
+    probe = lambda: glc._chk("glcProbeSegments", L.glcProbeSegments(x.data_ptr(), off.data_ptr(), ln.data_ptr(), nseg, n, hist.data_ptr(),
+                                                                      uni.data_ptr(), None))
+    bigram(); probe()
+    med = lambda fn: sorted(event_timed(fn) for _ in range(5))[2]
+    res["probe"] = {"bytes": x.numel(), "bigram_probe_GBps": round(x.numel() / med(bigram) / 1e9, 1),
+                    "auto_probe_GBps": round(x.numel() / med(probe) / 1e9, 1), "copy_GBps": round(x.numel() / med(lambda: y.copy_(x)) / 1e9, 1)}
+    return res
+
+
 def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
     """the container with the shuffle filter off and on (with `delta`: in delta mode), on one plan: sizes, rates, kernel profile
     and sorter tiers"""
@@ -321,7 +391,8 @@ def main():
     ap.add_argument("--data", choices=sorted(DATA_ELEM), default="zipf")
     ap.add_argument("--shuffle", type=int, default=0, choices=[0, 2, 4, 8], metavar="ELEM")
     ap.add_argument("--delta", action="store_true", help="the filtered setting uses the filter's delta mode (format version 4)")
-    ap.add_argument("--codec", type=int, default=0, choices=[0, 1], help="the filter section's container codec: 0 BWT, 1 order-0")
+    ap.add_argument("--codec", type=int, default=0, choices=[0, 1, 4],
+                    help="the filter section's container codec: 0 BWT, 1 order-0; 4: the choose section (all three codecs, no filter)")
     ap.add_argument("--rounds", type=int, default=0, help="typed data: the sparse section, this many interleaved rounds timed with device events")
     ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
     ap.add_argument("--ans", action="store_true", help="the sparse section also runs the order-0 codec's rANS mode (format version 7)")
@@ -343,12 +414,16 @@ def main():
     n = MiB
     nblocks = int(args.gib * 1024)
     total = nblocks * n
-    if args.data == "zipf":
+    if args.data in ("zipf", "mix"):
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
         thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
         assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+        if args.data == "mix":                                 # every other run of 64 blocks is text-like
+            assert args.codec == 4, "the mix is the choose section's"
+            runs = d_in[:total // (128 * n) * 128 * n].view(-1, 2, 64 * n)
+            runs[:, 1, :] = text_on_device(torch, dev, "textlike", runs.shape[0] * 64 * n).view(-1, 64 * n)
     elif args.data in ("textlike", "loglike"):
-        assert args.runs or args.runs_off_only, "text-like data is the runs section's"
+        assert args.runs or args.runs_off_only or args.codec == 4, "text-like data is the runs and the choose section's"
         d_in = text_on_device(torch, dev, args.data, total)
     else:
         d_in = typed_on_device(torch, L, dev, args.data, total)
@@ -367,6 +442,13 @@ def main():
 
     res = {"workload": "%s: %d x 1 MiB blocks, plan rows %d, pipelining %s"
                        % ("configs[1] Philox Zipf(1.0)" if args.data == "zipf" else args.data, nblocks, args.rows, bool(args.pipelining))}
+    if args.codec == 4:
+        assert args.data in ("zipf", "mix", "textlike", "loglike") and not args.shuffle, "the choose section takes untyped data and no filter"
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            res["choose"] = choose_section(torch, glc, plan, d_in, total, max(1, args.rounds))
+        print(json.dumps(res))
+        return
     if args.runs or args.runs_off_only:
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))

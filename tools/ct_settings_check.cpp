@@ -9,6 +9,12 @@
 // every call, the same return code, and in every state the same getter values, the same (version, flags, elem), the same reader
 // mask, and the encoder's derived booleans equal to the settings' own.  It prints
 //   ct_settings_check: ok, <states> states, <calls> calls
+// That walk stays inside what the old rule knew: the codecs 0 and 1.  The CHOOSE codec (4) came later and has no older rule to
+// be held against, so a second part states its rule outright and tries it from every state of the walk: accepted exactly with
+// the shuffle off, it clears the mode, writes (3, 0, 0) and reads what a plain plan reads; while it is the codec every filter
+// and every mode is refused with nothing changed, switching anything off is still accepted, and codec 0 or 1 leads back to
+// that codec's plain state.  It prints
+//   ct_settings_check: choose ok, <states> states
 #include "../gpu-lossless-compression_amd/csrc/container_internal.h"
 
 #include <stdio.h>
@@ -127,6 +133,7 @@ static bool same_state(const Both &s)
 int main()
 {
     const std::vector<uint32_t> elems = {0, 1, 2, 3, 4, 8, 16, 255}, flags = {0, 1, 2, 0xFFFFFFFFu};
+    std::vector<CtSettings> states;
     std::map<decltype(Old().key()), bool> seen;
     std::vector<Both> todo = {Both()};
     seen[todo[0].o.key()] = true;
@@ -135,6 +142,7 @@ int main()
         const Both from = todo.back();
         todo.pop_back();
         if (!same_state(from)) return 1;
+        states.push_back(from.n);
         for (int k = 0; k < 7; k++)
             for (uint32_t v : k == 0 ? elems : flags) {
                 Both s = from;
@@ -156,5 +164,46 @@ int main()
         }
     }
     printf("ct_settings_check: ok, %zu states, %llu calls\n", seen.size(), calls);
+    const CtMode modes[] = {CT_MODE_SPARSE, CT_MODE_RUNS, CT_MODE_ANS, CT_MODE_AUTO};
+    auto same = [](const CtSettings &a, const CtSettings &b) { return a.shuffle == b.shuffle && a.delta == b.delta && a.codec == b.codec && a.mode == b.mode; };
+    auto choose_state = [&](const CtSettings &c) {
+        CHECK(c.codec == CT_CODEC_CHOOSE && c.mode == CT_MODE_PLAIN && c.shuffle == 0 && !c.delta && c.reader() == 0);
+        const CtFormat f = format_of(c);
+        CHECK(f.version == CT_VERSION_CODEC && f.flags == 0 && f.elem == 0 && format_legal(f));
+        CHECK(c.kinds() == (1u << CT_KIND_HUFF | 1u << CT_KIND_RAW | 1u << CT_KIND_HUFF0));
+        return true;
+    };
+    for (const CtSettings &from : states) {
+        CtSettings c = from;
+        if (from.shuffle) {                                     // refused while the filter is on, nothing changed
+            if (c.set_codec(CT_CODEC_CHOOSE) || !same(c, from)) { fprintf(stderr, "ct_settings_check: CHOOSE accepted with the shuffle on\n"); return 1; }
+            continue;
+        }
+        if (!c.set_codec(CT_CODEC_CHOOSE) || !choose_state(c)) { fprintf(stderr, "ct_settings_check: CHOOSE refused or wrong with the shuffle off\n"); return 1; }
+        const CtSettings at = c;
+        for (uint32_t e : elems) {
+            CtSettings t = at;
+            const bool ok = t.set_shuffle(e);
+            if (ok != (e <= 1) || !same(t, at)) { fprintf(stderr, "ct_settings_check: shuffle %u under CHOOSE\n", e); return 1; }
+        }
+        for (uint32_t v : flags) {
+            CtSettings t = at;
+            if (t.set_delta(v) != (v == 0) || !same(t, at)) { fprintf(stderr, "ct_settings_check: delta %u under CHOOSE\n", v); return 1; }
+            for (CtMode m : modes) {
+                t = at;
+                if (t.set_mode(m, v) != (v == 0) || !same(t, at)) { fprintf(stderr, "ct_settings_check: mode %u = %u under CHOOSE\n", (uint32_t)m, v); return 1; }
+            }
+        }
+        for (uint32_t k : {CT_CODEC_BWT, CT_CODEC_HUFF0, CT_CODEC_CHOOSE}) {
+            CtSettings t = at, plain;
+            plain.codec = k;
+            if (!t.set_codec(k) || !same(t, plain)) { fprintf(stderr, "ct_settings_check: codec %u after CHOOSE\n", k); return 1; }
+        }
+        for (uint32_t k : {2u, 3u, 5u, 0xFFFFFFFFu}) {
+            CtSettings t = at;
+            if (t.set_codec(k) || !same(t, at)) { fprintf(stderr, "ct_settings_check: codec %u accepted\n", k); return 1; }
+        }
+    }
+    printf("ct_settings_check: choose ok, %zu states\n", states.size());
     return 0;
 }
