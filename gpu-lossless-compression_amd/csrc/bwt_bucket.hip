@@ -219,7 +219,14 @@ __global__ __launch_bounds__(256) void k_fs_hist(const uint8_t *__restrict__ tex
 //   * the global atomic of a (tile, bucket) be ISSUED before the words are scattered in LDS and CONSUMED after (the
 //     scatter needs the tile-local ranks only), with LDS-only barriers in between so that nobody waits for it early;
 //   * the stores of tile t retire under tile t + 1 (the prefetched text is taken out of its registers before they are issued:
-//     loads and stores share one counter, in order).
+//     loads and stores share one counter, in order).  That holds only where the compiler's counter model sees no load in
+//     flight at the loop's header: one loop over edge and inner tiles alike, entered with the first request pending and left
+//     by `return` behind a request (a return inside a loop is routed through its latch), had `s_waitcnt vmcnt(0)` at the
+//     latch and in front of the stg -> LDS writes, so every tile drained its 64 KB of scattered stores with all waves
+//     behind a barrier.  Hence the shape below: the run of inner tiles is a loop of its own, entered behind an explicit wait
+//     for its first tile's text, the block's flag is looked at BEFORE the next request is issued, and the edge tiles stay
+//     outside.  On the way round that loop the only wait on the memory counter is the vmcnt(0) that takes in the tile's
+//     own fill atomic, half a tile behind the stores of the tile before (profiles/part2_waits.md).
 #ifndef GLC_FSP2_T
 #define GLC_FSP2_T 4
 #endif
@@ -235,6 +242,9 @@ constexpr int FSP2_T = GLC_FSP2_T;
 #endif
 constexpr int FSP2_TILE = GLC_FSP2_TILE;                       // suffixes per tile of k_fs_part2
 constexpr int FSP2_NT = GLC_FSP2_NT;                           // threads per workgroup; a thread takes 4096 / FSP2_NT consecutive suffixes
+#ifndef GLC_FSP2_PHASES
+#define GLC_FSP2_PHASES 1                                      // (A/B: 0 = the batch instance's inner tile item-major like the others)
+#endif
 
 __device__ __forceinline__ void lds_only_barrier()
 {
@@ -309,8 +319,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         }
     };
     const uint32_t tend = min(ntiles, tile0 + tiles_per_wg);
-    bool have = false;                                         // stg holds the text of the tile about to be processed
-    if (inner(tile0)) { request(tile0); have = true; }
     uint64_t *K = keys + (size_t)b * kstride;
     static_assert(TILE <= (1u << 20), "a rank inside (tile, bucket) rides in the index field of the word until the scatter");
     constexpr uint32_t LOW = (uint32_t)FS_LOW_MASK;            // the word's low dword: [4 code bits | index : 20 | bwt : 8]
@@ -321,6 +329,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
     // one): the per-suffix guards below exist in this instance only.
     auto tile_body = [&](auto edge_t, uint32_t base, bool next_inner) __attribute__((always_inline)) -> bool {
         constexpr bool EDGE = decltype(edge_t)::value;
+        // the inner tile of the instance with four waves per SIMD (128 VGPRs to spend) keeps all of a thread's table entries,
+        // ranks and bucket starts in registers and asks LDS for each kind in one go
+        constexpr bool PHASES = !EDGE && WPE <= 4 && GLC_FSP2_PHASES;
         // thread = 8 consecutive suffixes gi0 .. gi0+7; byte j of its 16 staged bytes is T[gi0 - 1 + j]
         const uint32_t k0 = tid * ITEMS, gi0 = base + k0;
         constexpr int NBY = (ITEMS + FS_DEPTH + 3) / 4;       // dwords that hold the thread's ITEMS + FS_DEPTH staged bytes (k0 is a multiple of ITEMS)
@@ -337,32 +348,59 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
             for (int q = 0; q < NBY; q++) by4[q] = *reinterpret_cast<const uint32_t *>(s_txt + k0 + 4 * q);
         }
 #define FS_BYTE(j) ((by4[(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu)
-        // table entry of the symbol at byte 1 + k (past the end of the block: C = p = 0); entry k is dead behind code k, so
-        // the entries come in as the codes need them (a window of FS_DEPTH in registers rather than all ITEMS + FS_DEPTH - 1)
+        // table entry of the symbol at byte 1 + k (past the end of the block: C = p = 0)
         uint2 e[ITEMS + FS_DEPTH - 1];
         auto entry = [&](int k) {
             const uint2 t = s_tab[FS_BYTE(1 + k)];
             if constexpr (EDGE) return gi0 + k >= n ? make_uint2(0u, 0u) : t;
             else return t;
         };
-#pragma unroll
-        for (int k = 0; k < FS_DEPTH - 1; k++) e[k] = entry(k);
-        // the words leave this phase as [high dword | low dword with the RANK inside (tile, bucket) in the index field]: the
-        // bucket is the high dword's top bits and the index is gi0 + j, both re-derived at the scatter
-        uint32_t xh[ITEMS], xl[ITEMS];
-#pragma unroll
-        for (int j = 0; j < ITEMS; j++) {
-            e[j + FS_DEPTH - 1] = entry(j + FS_DEPTH - 1);
+        auto code = [&](int j) {
             uint32_t y = e[j + FS_DEPTH - 1].x;
 #pragma unroll
             for (int d = FS_DEPTH - 2; d >= 1; d--) y = e[j + d].x + __umulhi(e[j + d].y, y);
-            const uint64_t X = ((uint64_t)e[j].x << 32) + (uint64_t)e[j].y * y;
-            const uint32_t hi = (uint32_t)(X >> 32), bk = bucket_of(hi);
-            uint32_t r = 0;
-            if (!EDGE || gi0 + j < n) r = atomicAdd(&s_cnt[bk], 1u);
-            xh[j] = hi;
-            xl[j] = ((uint32_t)X & ~LOW) | (r << 8);
-            if (j == 0 && gi0 == 0) zero_bucket[b] = bk;        // where the word of suffix 0 goes: k_fs_sort_bwt looks for the BWT index there only
+            return ((uint64_t)e[j].x << 32) + (uint64_t)e[j].y * y;
+        };
+        // the words leave this phase as [high dword | low dword with the RANK inside (tile, bucket) in the index field]: the
+        // bucket is the high dword's top bits and the index is gi0 + j, both re-derived at the scatter
+        uint32_t xh[ITEMS], xl[ITEMS];
+        if constexpr (PHASES) {
+            // phase-major: every table read is in flight before the first code is computed, and the rank atomics leave as
+            // the codes complete -- the first returned rank is looked at behind the last atomic (item-major, each code sat
+            // behind its own table read AND the rank atomic of the code before: eight LDS round trips per thread)
+#pragma unroll
+            for (int k = 0; k < ITEMS + FS_DEPTH - 1; k++) e[k] = entry(k);
+            __builtin_amdgcn_sched_barrier(0);
+            uint32_t rk[ITEMS];
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) {
+                const uint64_t X = code(j);
+                xh[j] = (uint32_t)(X >> 32);
+                xl[j] = (uint32_t)X & ~LOW;
+                rk[j] = atomicAdd(&s_cnt[bucket_of(xh[j])], 1u);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) xl[j] |= rk[j] << 8;
+        } else {
+            // item-major: entry k is dead behind code k, so the entries come in as the codes need them (a window of FS_DEPTH in
+            // registers rather than all ITEMS + FS_DEPTH - 1)
+#pragma unroll
+            for (int k = 0; k < FS_DEPTH - 1; k++) e[k] = entry(k);
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) {
+                e[j + FS_DEPTH - 1] = entry(j + FS_DEPTH - 1);
+                // (the edge tile: a word's low half in ONE register from here, not the code bits and the rank apart until the scatter)
+                if constexpr (EDGE) if (j > 0) asm volatile("" : "+v"(xl[j - 1]));
+                const uint64_t X = code(j);
+                const uint32_t hi = (uint32_t)(X >> 32), bk = bucket_of(hi);
+                uint32_t r = 0;
+                if (!EDGE || gi0 + j < n) r = atomicAdd(&s_cnt[bk], 1u);
+                xh[j] = hi;
+                xl[j] = ((uint32_t)X & ~LOW) | (r << 8);
+                // where the word of suffix 0 goes: k_fs_sort_bwt looks for the BWT index there only (a block's first tile is an edge tile)
+                if constexpr (EDGE) if (j == 0 && gi0 == 0) zero_bucket[b] = bk;
+            }
         }
         lds_only_barrier();
         uint32_t g = 0, c = 0;
@@ -382,12 +420,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         }
 #undef FS_BYTE
         lds_only_barrier();                                    // (the staged text and the table reads are done: s_w takes the words)
+        if constexpr (PHASES) {
+            uint32_t at[ITEMS];                                 // the eight bucket starts asked for together, then the eight words written
 #pragma unroll
-        for (int j = 0; j < ITEMS; j++) {
-            asm volatile("" : "+v"(xh[j]), "+v"(xl[j]));        // two registers per word across the scan, not the code phase's bucket, rank and index
-            if (!EDGE || gi0 + j < n) {
+            for (int j = 0; j < ITEMS; j++) at[j] = s_start[bucket_of(xh[j])];
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) {
                 const uint32_t lo = (xl[j] & ~(LOW ^ 0xFFu)) | ((gi0 + j) << 8);
-                s_w[s_start[bucket_of(xh[j])] + ((xl[j] >> 8) & 0xFFFFFu)] = ((uint64_t)xh[j] << 32) | lo;
+                s_w[at[j] + ((xl[j] >> 8) & 0xFFFFFu)] = ((uint64_t)xh[j] << 32) | lo;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < ITEMS; j++) {
+                asm volatile("" : "+v"(xh[j]), "+v"(xl[j]));    // two registers per word across the scan, not the code phase's bucket, rank and index
+                if (!EDGE || gi0 + j < n) {
+                    const uint32_t lo = (xl[j] & ~(LOW ^ 0xFFu)) | ((gi0 + j) << 8);
+                    s_w[s_start[bucket_of(xh[j])] + ((xl[j] >> 8) & 0xFFFFFu)] = ((uint64_t)xh[j] << 32) | lo;
+                }
             }
         }
         if (c && g + c > FS_FILLMAX) { atomicOr(&flag[b], 1u); s_flagged = 1; }
@@ -423,34 +472,51 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
         }
         return true;
     };
+    // The tile proper comes in two instances: an INNER tile (every suffix of it and the 16 bytes behind it inside the block, and
+    // not the block's first) takes its text from stg and runs without a per-suffix guard; an edge tile (the first of a block:
+    // the byte in front of suffix 0 is the block's last; the last one or two: suffixes past n, symbols past the end
+    // contributing C = p = 0) fetches its text byte by byte and keeps the guards.  A workgroup's tiles are at most one edge
+    // tile, a run of inner tiles, and one or two edge tiles; the run is a loop of its own, entered with its first tile's text
+    // arrived, so that on the way round it no path brings a load in flight to its header.
+    uint32_t tile = tile0;
+    if (inner(tile)) request(tile);
 #pragma clang loop unroll(disable)
-    for (uint32_t tile = tile0; tile < tend; tile++) {
-        const uint32_t base = tile * TILE;
-        const bool edge = base + TILE + 16 > n;
-        if (tid < FS_MAXNB) s_cnt[tid] = 0;
-        if (have) {
+    while (tile < tend) {
+        if (!inner(tile)) {
+            const uint32_t base = tile * TILE;
+            if (tid < FS_MAXNB) s_cnt[tid] = 0;
+            for (uint32_t k = tid; k < TILE + 16; k += NT) {
+                const int64_t g = (int64_t)base - 1 + k;
+                s_txt[k] = g < 0 ? T[n - 1] : (g < (int64_t)n ? T[g] : (uint8_t)0);
+            }
+            lds_only_barrier();
+            if (s_flagged) return;
+            const bool next_inner = tile + 1 < tend && inner(tile + 1);
+            if (next_inner) request(tile + 1);                 // in flight until this tile's words are in LDS
+            tile_body(std::true_type{}, base, next_inner);
+            lds_only_barrier();                               // s_w is free for the next tile's text
+            tile++;
+            continue;
+        }
+#pragma unroll
+        for (int r = 0; r < NSTG; r++) asm volatile("" : "+v"(stg[r]));   // the run's first tile has arrived
+#pragma clang loop unroll(disable)
+        for (;;) {
+            if (tid < FS_MAXNB) s_cnt[tid] = 0;
 #pragma unroll
             for (int r = 0; r < NSTG; r++) {
                 const uint32_t q = r * NT + tid;
                 if (q < (TILE + 16) / 4) reinterpret_cast<uint32_t *>(s_txt)[q] = stg[r];
             }
-        } else {
-            for (uint32_t k = tid; k < TILE + 16; k += NT) {
-                const int64_t g = (int64_t)base - 1 + k;
-                s_txt[k] = g < 0 ? T[n - 1] : (g < (int64_t)n ? T[g] : (uint8_t)0);
-            }
+            lds_only_barrier();                                // (stg is in LDS: its registers take the next tile's request)
+            if (s_flagged) return;                             // (ahead of the request: no way out of the loop with a load in flight)
+            const bool more = tile + 1 < tend && inner(tile + 1);
+            if (more) request(tile + 1);                       // in flight until this tile's words are in LDS
+            if (!tile_body(std::false_type{}, tile * TILE, more)) return;
+            lds_only_barrier();                               // s_w is free for the next tile's text
+            tile++;
+            if (!more) break;
         }
-        lds_only_barrier();                                    // (stg is in LDS: its registers take the next tile's request)
-        const bool next_inner = tile + 1 < tend && inner(tile + 1);
-        if (next_inner) request(tile + 1);                     // in flight until this tile's words are in LDS
-        if (s_flagged) return;
-        // The tile proper, in two instances: an INNER tile (every suffix of it and the 16 bytes behind it inside the block: all
-        // but the first and last tile of a block, and the first as well when the block is long) takes no per-suffix guard at
-        // all; an edge tile (suffixes past n, symbols past the end contributing C = p = 0) keeps them.
-        const bool go = edge ? tile_body(std::true_type{}, base, next_inner) : tile_body(std::false_type{}, base, next_inner);
-        if (!go) return;
-        have = next_inner;
-        lds_only_barrier();                                   // s_w is free for the next tile's text
     }
 }
 
@@ -1220,7 +1286,7 @@ hipError_t fs_build(const SortCall &c, SaScratch &s)
     // the global atomics) run 2.7 ms -- and give the same `value` as 4 tiles of 4096: a 1024-thread workgroup needs half a CU
     // free AT ONCE, which the MTF and Huffman kernels of the batch before, sharing the chip under stage overlap, rarely leave.
     // Batches of 16 blocks or more: tiles of 8192 suffixes, 1024 threads (runs of ~128 bytes leave for a bucket's slot, half the
-    // global atomics), 16 tiles per workgroup.  70 KB of LDS would let two workgroups share a CU, but the registers (78 VGPRs:
+    // global atomics), 16 tiles per workgroup.  70 KB of LDS would let two workgroups share a CU, but the registers (76 VGPRs:
     // six waves per SIMD) hold it to ONE.  Squeezed to 64 VGPRs with amdgpu_waves_per_eu(8, 8) (4 spilled) for two per CU, it
     // gave bench.py `value` 105.7-106.5 GB/s against 108.5-109.3 on one box, alternating.  Until the MTF kernel was re-based this
     // shape ran 2.7 ms and gave the same `value` (the stages of the batch before rarely left half a CU free at once); since:
