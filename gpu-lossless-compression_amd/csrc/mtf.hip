@@ -17,6 +17,9 @@
 //   3. k_mtf_encode       MTF as dominance counting over previous-occurrence
 //      timestamps (see the kernel): four chunks per wave, one per 16-lane DPP row;
 //      no serial list, no per-byte dependency chain.
+// Where a call is many blocks of whole rows (n a multiple of MTF_SPAN * 4 * 4096) a row of 3 runs on through MTF_SPAN
+// consecutive chunks, and 1 and 2 make one list per span of MTF_SPAN chunks: the encoder's state at a chunk's end is the
+// next chunk's start list.
 #include "glc_device.h"
 #include "glc_internal.h"
 
@@ -33,47 +36,84 @@ constexpr int MTF_INP = 256 + 8;                   // membership bytes of mtf_fo
 // first[sym] with an LDS atomicMin only when a plain read says it would (most recent bytes first, so after the
 // first few dozen bytes almost nothing passes the test); the symbols are then ranked by first[] through a 4096-bit
 // occupancy bitmap + prefix popcounts.
+//
+// K > 1 (the span form of k_mtf_encode, whose rows run on through K consecutive chunks and need a start list only for the
+// first): the wave's unit is a SPAN of K chunks, lists and lens are indexed by span.  The span's chunks are taken most
+// recent first into the same first[], order indices going on from one chunk to the next, so in an older chunk only
+// the symbols not met so far pass the test.  Once all 256 have been met the older chunks cannot change anything and
+// are not read: after every chunk but the oldest the wave looks (mtf_all_met: wave-uniform, no atomics, no waiting).
+__device__ __forceinline__ bool mtf_all_met(const uint32_t *first, uint32_t l)
+{
+    bool all = true;
+#pragma unroll
+    for (int j = 0; j < 4; j++) all = all && first[4 * l + j] != 0xFFFFFFFFu;
+    return __ballot(all) == ~0ull;
+}
+
+template <int K>
 __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_chunk_lists(const uint8_t *__restrict__ in,
                                                                    size_t in_stride, uint32_t n,
                                                                    uint8_t *__restrict__ lists,
                                                                    uint16_t *__restrict__ lens,
                                                                    uint32_t max_chunks, const uint32_t *__restrict__ only)
 {
+    constexpr uint32_t SPAN = K * MTF_CHUNK;
     __shared__ uint32_t s_first[MTF_WAVES][256];
-    __shared__ unsigned long long s_bm[MTF_WAVES][64];
-    __shared__ uint32_t s_cum[MTF_WAVES][64];
+    __shared__ unsigned long long s_bm[MTF_WAVES][64 * K];     // one bit per order index; lane l owns words K l .. K l + K - 1
+    __shared__ uint32_t s_cum[MTF_WAVES][64 * K];
     const uint32_t b = blockIdx.y, l = threadIdx.x & 63;
     if (only && !only[b]) return;                              // (second pass over the blocks a later sorter tier rewrote)
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform
-    const uint32_t chunk = blockIdx.x * MTF_WAVES + w;
-    const uint32_t nchunks = (n + MTF_CHUNK - 1) / MTF_CHUNK;
+    const uint32_t chunk = blockIdx.x * MTF_WAVES + w;         // (K > 1: the span)
+    const uint32_t nchunks = (n + SPAN - 1) / SPAN;
     if (chunk >= nchunks) return;                           // whole wave exits together
-    const uint32_t lo = chunk * MTF_CHUNK, hi = min(n, lo + MTF_CHUNK), C = hi - lo;
+    const uint32_t lo = chunk * SPAN, hi = min(n, lo + SPAN), C = hi - lo;
     const uint8_t *src = in + (size_t)b * in_stride;
     uint8_t *L = lists + ((size_t)b * max_chunks + chunk) * 256;
     uint32_t *first = s_first[w];
     for (int i = l; i < 256; i += 64) first[i] = 0xFFFFFFFFu;
-    s_bm[w][l] = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) s_bm[w][K * l + k] = 0;
     __builtin_amdgcn_wave_barrier();
-    if (C == MTF_CHUNK && (reinterpret_cast<uintptr_t>(src + lo) & 15) == 0) {
-        // lane l of segment g holds order indices [1024 g + 16 l, +16): the 16 bytes at lo + 4096 - 1024 g - 16 (l + 1)
-        uint4 q[4];
+    if (C == SPAN && (reinterpret_cast<uintptr_t>(src + lo) & 15) == 0) {
 #pragma unroll
-        for (int g = 0; g < 4; g++)
-            q[g] = *reinterpret_cast<const uint4 *>(src + lo + MTF_CHUNK - 1024 * g - 16 * (l + 1));
+        for (int c = 0; c < K; c++) {                          // chunk K - 1 - c of the span: order indices [4096 c, +4096)
+            if (K > 1 && c) {
+                __builtin_amdgcn_wave_barrier();
+                if (mtf_all_met(first, l)) break;
+            }
+            // lane l of segment g holds order indices [4096 c + 1024 g + 16 l, +16): the 16 bytes that end 1024 g + 16 l
+            // before the chunk's end
+            uint4 q[4];
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const uint32_t d[4] = {q[g].x, q[g].y, q[g].z, q[g].w};
+            for (int g = 0; g < 4; g++)
+                q[g] = *reinterpret_cast<const uint4 *>(src + lo + (K - c) * MTF_CHUNK - 1024 * g - 16 * (l + 1));
 #pragma unroll
-            for (int k = 15; k >= 0; k--) {                   // byte k sits at order index 1024 g + 16 l + 15 - k
-                const uint32_t sym = (d[k >> 2] >> (8 * (k & 3))) & 0xFFu, o = 1024u * g + 16u * l + 15u - k;
-                if (o < first[sym]) atomicMin(&first[sym], o);
+            for (int g = 0; g < 4; g++) {
+                const uint32_t d[4] = {q[g].x, q[g].y, q[g].z, q[g].w};
+#pragma unroll
+                for (int k = 15; k >= 0; k--) {               // byte k sits at order index 4096 c + 1024 g + 16 l + 15 - k
+                    const uint32_t sym = (d[k >> 2] >> (8 * (k & 3))) & 0xFFu, o = 4096u * c + 1024u * g + 16u * l + 15u - k;
+                    if (o < first[sym]) atomicMin(&first[sym], o);
+                }
             }
         }
-    } else {
+    } else if constexpr (K == 1) {
         for (uint32_t o = l; o < C; o += 64) {
             const uint32_t sym = src[hi - 1 - o];
             if (o < first[sym]) atomicMin(&first[sym], o);
+        }
+    } else {
+        for (uint32_t c0 = 0; c0 < C; c0 += MTF_CHUNK) {
+            if (c0) {
+                __builtin_amdgcn_wave_barrier();
+                if (mtf_all_met(first, l)) break;
+            }
+            const uint32_t c1 = min(C, c0 + MTF_CHUNK);
+            for (uint32_t o = c0 + l; o < c1; o += 64) {
+                const uint32_t sym = src[hi - 1 - o];
+                if (o < first[sym]) atomicMin(&first[sym], o);
+            }
         }
     }
     __builtin_amdgcn_wave_barrier();
@@ -84,9 +124,13 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_chunk_lists(const uint8_
         if (f[j] != 0xFFFFFFFFu) atomicOr(&s_bm[w][f[j] >> 6], 1ull << (f[j] & 63));
     }
     __builtin_amdgcn_wave_barrier();
-    const uint32_t c = (uint32_t)__popcll(s_bm[w][l]);
+    uint32_t ck[K], c = 0;
+#pragma unroll
+    for (int k = 0; k < K; k++) { ck[k] = (uint32_t)__popcll(s_bm[w][K * l + k]); c += ck[k]; }
     const uint32_t inc = wave_incl_add(c);
-    s_cum[w][l] = inc - c;
+    uint32_t below = inc - c;
+#pragma unroll
+    for (int k = 0; k < K; k++) { s_cum[w][K * l + k] = below; below += ck[k]; }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -142,12 +186,13 @@ __device__ __forceinline__ uint32_t mtf_fold(const uint8_t *cur, uint8_t *next, 
     return m + (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
 }
 
-template <int MSC_WAVES>
+// K > 1: the entries are the lists of spans of K chunks (k_mtf_chunk_lists<K>), a 1 MiB block has 256 / K of them, and
+// MSC_GROUP is chosen with MSC_WAVES for the shortest chain of folds, 2 MSC_GROUP + MSC_WAVES (mtf_forward).
+template <int MSC_WAVES, int K = 1, int MSC_GROUP = 256 / MSC_WAVES>
 __global__ __launch_bounds__(MSC_WAVES * 64) void k_mtf_scan_lists(uint8_t *__restrict__ lists,
                                                                   const uint16_t *__restrict__ lens, uint32_t n,
                                                                   uint32_t max_chunks, const uint32_t *__restrict__ only)
 {
-    constexpr int MSC_GROUP = 256 / MSC_WAVES;
     __shared__ __attribute__((aligned(16))) uint8_t s_state[MSC_WAVES][2][256];
     __shared__ __attribute__((aligned(16))) uint8_t s_inp[MSC_WAVES][MTF_INP];
     __shared__ __attribute__((aligned(16))) uint8_t s_comb[MSC_WAVES][256];      // combined list of every group
@@ -157,7 +202,7 @@ __global__ __launch_bounds__(MSC_WAVES * 64) void k_mtf_scan_lists(uint8_t *__re
     const uint32_t b = blockIdx.x, l = threadIdx.x & 63;
     if (only && !only[b]) return;
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t nchunks = (n + MTF_CHUNK - 1) / MTF_CHUNK;
+    const uint32_t nchunks = (n + K * MTF_CHUNK - 1) / (K * MTF_CHUNK);        // (K > 1: spans)
     uint8_t *LB = lists + (size_t)b * max_chunks * 256;
     const uint16_t *NB = lens + (size_t)b * max_chunks;
     if (w == 0) for (int i = l; i < 256; i += 64) s_carry[i] = (uint8_t)i;      // identity list before the first chunk
@@ -306,17 +351,21 @@ __device__ __forceinline__ void mtf_recount(const unsigned long long *bm, uint16
 
 
 // --- FULL form of k_mtf_encode: see the kernel ---
-// A/B switches (build.py: GLC_CXXFLAGS=-D... with GLC_LIB_OUT): the request distance and the batches per group, measured
-// in profiles/mtf_full_rows.md.  GLC_MTF_FULL_GROUP=1 is the fixed-trip body alone, without the unroll and its immediates.
+// A/B switches (build.py: GLC_CXXFLAGS=-D... with GLC_LIB_OUT), measured in profiles/mtf_full_rows.md and
+// profiles/mtf_span_rows.md: the request distance (2: k_mtf_encode 4.90 -> 4.78 ms per 2048-block launch against 1) and the
+// chunks per row.  (The batches per group were a third: the fixed-trip body alone, a group of 1, is 5.27 ms; the switch is gone.)
 #ifndef GLC_MTF_REQ_DIST
-#define GLC_MTF_REQ_DIST 1
+#define GLC_MTF_REQ_DIST 2
 #endif
 constexpr int MTF_REQ = GLC_MTF_REQ_DIST;                  // batches between a byte's request and its use
-#ifndef GLC_MTF_FULL_GROUP
-#define GLC_MTF_FULL_GROUP 4
-#endif
-constexpr int MTF_GROUP = GLC_MTF_FULL_GROUP;               // batches per unrolled group
+constexpr int MTF_GROUP = 4;                                // batches per unrolled group
 static_assert(MTF_REQ >= 1 && MTF_GROUP % MTF_REQ == 0 && MTF_SEG % (16 * MTF_GROUP) == 0 && MTF_CHUNK % MTF_SEG == 0, "group shape");
+// chunks per row of the FULL form where n allows (1: every row one chunk), measured in profiles/mtf_span_rows.md
+#ifndef GLC_MTF_SPAN
+#define GLC_MTF_SPAN 4
+#endif
+constexpr int MTF_SPAN = GLC_MTF_SPAN;
+static_assert(MTF_SPAN == 1 || MTF_SPAN == 2 || MTF_SPAN == 4, "spans of 1, 2 or 4 chunks");
 
 // One group of MTF_GROUP batches, the first at position lbg of its segment; voff = the lane's offset from sb / db.
 // LASTG: the chunk's last group, whose last MTF_REQ batches request nothing (no address at or past the row's end is formed).
@@ -382,7 +431,12 @@ __device__ __forceinline__ void mtf_full_group(const uint8_t *__restrict__ sb, u
 }
 
 // The row's whole chunk: sb / db = the block's input and output (wave-uniform), lo = the chunk's offset in the block.
-template <bool WITH_HIST, bool ZEROS>
+// K > 1: the row runs on through K consecutive chunks.  The state at a chunk's end IS the next chunk's start state -- tab[]
+// holds every symbol's last timestamp and the re-base at the segment's end makes ranks 0..255 of them, as a start list
+// would -- so only the first chunk's list is read (k_mtf_chunk_lists<K> makes no other).  At a chunk's end inside the span
+// the row's counters leave for that chunk's sub_hist slot (H = the first chunk's) and start again from zero; the byte
+// requests run on across it, and the group that requests nothing is the span's last.
+template <bool WITH_HIST, bool ZEROS, int K>
 __device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ sb, uint8_t *__restrict__ db, uint32_t lo,
                                                     const uint8_t *__restrict__ list, uint32_t *tab, unsigned long long *bm,
                                                     uint16_t *cum, uint32_t *hist, uint32_t *__restrict__ H, uint32_t lr,
@@ -403,9 +457,19 @@ __device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ 
 #pragma unroll
     for (int d = 0; d < MTF_REQ; d++) q[d] = sb[voff + 16u * d];
     constexpr uint32_t NSEG = MTF_CHUNK / MTF_SEG, NGRP = MTF_SEG / (16 * MTF_GROUP);
-    for (uint32_t seg = 0; seg < NSEG; seg++) {
+    for (uint32_t seg = 0; seg < K * NSEG; seg++) {
         if (seg) mtf_rebase(tab, bm, cum, lr);
-        const uint32_t ng = seg + 1 < NSEG ? NGRP : NGRP - 1;      // the chunk's last group follows the loops
+        if constexpr (K > 1 && WITH_HIST) {
+            if (seg && seg % NSEG == 0) {                          // a chunk has ended inside the span (seg is wave-uniform)
+                __builtin_amdgcn_wave_barrier();
+                uint32_t *Hc = H + (size_t)(seg / NSEG - 1) * SUBHIST_DWORDS;
+                if constexpr (SUBHIST_PACKED) for (int i = lr; i < 128; i += 16) Hc[i] = hist[i];
+                else for (int i = lr; i < 256; i += 16) Hc[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+                for (int i = lr; i < 128; i += 16) hist[i] = 0;
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        const uint32_t ng = seg + 1 < K * NSEG ? NGRP : NGRP - 1;  // the row's last group follows the loops
         for (uint32_t g = 0; g < ng; g++, voff += 16 * MTF_GROUP)
             mtf_full_group<WITH_HIST, ZEROS, false>(sb, db, voff, 16 * MTF_GROUP * g, q, tab, bm, cum, hist, lr, row);
     }
@@ -413,8 +477,9 @@ __device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ 
     if (WITH_HIST) {
         __builtin_amdgcn_wave_barrier();
         // (packed: the row's 16-bit counter pairs leave as they stand)
-        if constexpr (SUBHIST_PACKED) for (int i = lr; i < 128; i += 16) H[i] = hist[i];
-        else for (int i = lr; i < 256; i += 16) H[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
+        uint32_t *Hl = H + (size_t)(K - 1) * SUBHIST_DWORDS;       // the row's last chunk
+        if constexpr (SUBHIST_PACKED) for (int i = lr; i < 128; i += 16) Hl[i] = hist[i];
+        else for (int i = lr; i < 256; i += 16) Hl[i] = (hist[i & 127] >> (16 * (i >> 7))) & 0xFFFFu;
     }
 }
 
@@ -429,7 +494,10 @@ __device__ __forceinline__ void mtf_encode_full_row(const uint8_t *__restrict__ 
 // nothing in the batch depends on a length.  The segment and batch loops count on a scalar, the batches come four to a
 // group, and the row's bytes are addressed as block pointer (scalar) + 32-bit lane offset + immediate, so a group advances
 // one offset where a batch advanced two 64-bit pointers.
-template <bool WITH_HIST, bool QUARTERS, bool ZEROS = false, bool FULL = false>
+//
+// FULL with K > 1 (the span form; n a multiple of K * MTF_ROWS * MTF_CHUNK): a row is K consecutive chunks, row r of wave w of
+// workgroup x takes chunks [((x MTF_WAVES + w) MTF_ROWS + r) K, +K), and `lists` is indexed by span (see mtf_encode_full_row).
+template <bool WITH_HIST, bool QUARTERS, bool ZEROS = false, bool FULL = false, int K = 1>
 __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__restrict__ in,
                                                               size_t in_stride, uint32_t n,
                                                               const uint8_t *__restrict__ lists,
@@ -458,13 +526,15 @@ __global__ __launch_bounds__(MTF_WAVES * 64) void k_mtf_encode(const uint8_t *__
     constexpr uint32_t QLEN = MTF_CHUNK / MTF_ROWS;                          // 1024
     // QUARTERS: chunk0 = the wave's chunk, row = quarter.  Otherwise chunk0 = first of the wave's four chunks.
     const uint32_t chunk0 = QUARTERS ? blockIdx.x * MTF_WAVES + w : (blockIdx.x * MTF_WAVES + w) * MTF_ROWS;
-    if (chunk0 >= nchunks) return;                                           // whole wave exits together
-    const uint32_t chunk = QUARTERS ? chunk0 : chunk0 + row;
+    static_assert(K == 1 || FULL, "only the FULL form has rows of K chunks");
+    if (chunk0 * K >= nchunks) return;                                       // whole wave exits together
+    const uint32_t chunk = QUARTERS ? chunk0 : chunk0 + row;                 // (K > 1: the row's span, of chunks K chunk ..)
     if constexpr (FULL) {
         static_assert(!QUARTERS, "the rows of the FULL form are whole chunks");
-        mtf_encode_full_row<WITH_HIST, ZEROS>(in + (size_t)b * in_stride, out + (size_t)b * out_stride, chunk * MTF_CHUNK,
-                                              lists + ((size_t)b * max_chunks + chunk) * 256, s_tab[slot], s_bm[slot], s_cum[slot],
-                                              s_hist[WITH_HIST ? slot : 0], sub_hist + ((size_t)b * max_chunks + chunk) * SUBHIST_DWORDS, lr, row);
+        mtf_encode_full_row<WITH_HIST, ZEROS, K>(in + (size_t)b * in_stride, out + (size_t)b * out_stride, chunk * (K * MTF_CHUNK),
+                                                 lists + ((size_t)b * max_chunks + chunk) * 256, s_tab[slot], s_bm[slot], s_cum[slot],
+                                                 s_hist[WITH_HIST ? slot : 0],
+                                                 sub_hist + ((size_t)b * max_chunks + chunk * K) * SUBHIST_DWORDS, lr, row);
         return;
     }
     const uint32_t Cc0 = min(n, chunk0 * MTF_CHUNK + MTF_CHUNK) - chunk0 * MTF_CHUNK;   // length of the wave's first chunk
@@ -671,6 +741,44 @@ void mtf_scratch_free(MtfScratch &s)
     s = MtfScratch();
 }
 
+// The span form of the three launches (K > 1): lists and start lists per span of K chunks, rows of K chunks.  A template so
+// that a build with K = 1 holds none of its kernels.
+template <int K>
+static hipError_t mtf_forward_span(hipStream_t st, const uint8_t *in, size_t in_stride, uint32_t n, uint32_t nblk, uint8_t *out,
+                                   size_t out_stride, MtfScratch &s, uint32_t *sub_hist, const uint32_t *only, bool skewed)
+{
+    if constexpr (K > 1) {
+        const uint32_t nspans = n / (K * MTF_CHUNK);
+        const dim3 t(MTF_WAVES * 64);
+        const double units = (double)n * nblk;
+        {
+            ProfScope ps(s.prof, PROF_MTF_LISTS, st, units);
+            hipLaunchKernelGGL(k_mtf_chunk_lists<K>, dim3((nspans + MTF_WAVES - 1) / MTF_WAVES, nblk), t, 0, st, in, in_stride, n, s.lists,
+                               s.lens, s.max_chunks, only);
+            // a 1 MiB block is 128 entries (spans of 2) or 64 (spans of 4); the chain is 2 x group + waves folds.  128: 16 waves
+            // of 8 (32 folds) for few blocks, 8 waves of 16 (40) where four workgroups per CU count, as for single chunks.
+            // 64: 8 waves of 8 (24 folds; 16 waves of 4 are 24 too)
+            constexpr int W_FEW = K == 2 ? 16 : 8;
+            if (nblk <= 512)
+                hipLaunchKernelGGL((k_mtf_scan_lists<W_FEW, K, 8>), dim3(nblk), dim3(W_FEW * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
+            else
+                hipLaunchKernelGGL((k_mtf_scan_lists<8, K, 32 / K>), dim3(nblk), dim3(8 * 64), 0, st, s.lists, s.lens, n, s.max_chunks, only);
+        }
+        ProfScope ps(s.prof, PROF_MTF_ENCODE, st, units);
+        const dim3 gs((nspans + MTF_WAVES * MTF_ROWS - 1) / (MTF_WAVES * MTF_ROWS), nblk);             // 4 spans per wave
+        if (sub_hist && skewed)
+            hipLaunchKernelGGL((k_mtf_encode<true, false, true, true, K>), gs, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else if (sub_hist)
+            hipLaunchKernelGGL((k_mtf_encode<true, false, false, true, K>), gs, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+        else
+            hipLaunchKernelGGL((k_mtf_encode<false, false, false, true, K>), gs, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
+                               out_stride, sub_hist, only);
+    }
+    return hipGetLastError();
+}
+
 hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint32_t n, uint32_t nblk,
                        uint8_t *out, size_t out_stride, MtfScratch &s, uint32_t *sub_hist, const uint32_t *only, bool skewed)
 {
@@ -679,9 +787,14 @@ hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint
     dim3 g((nchunks + MTF_WAVES - 1) / MTF_WAVES, nblk), t(MTF_WAVES * 64);
     dim3 ge((nchunks + MTF_WAVES * MTF_ROWS - 1) / (MTF_WAVES * MTF_ROWS), nblk);      // encode: 4 chunks per wave
     const double units = (double)n * nblk;
+    // few chunks in all (a cudppCompress call, small batches): a wave per chunk, its rows the chunk's quarters
+    const bool quarters = (uint64_t)nchunks * nblk <= MTF_QUARTERS_MAX_CHUNKS;
+    // the span form: what would take a FULL instance, when every row is MTF_SPAN whole chunks
+    if (MTF_SPAN > 1 && !quarters && n % (MTF_SPAN * MTF_ROWS * MTF_CHUNK) == 0)
+        return mtf_forward_span<MTF_SPAN>(st, in, in_stride, n, nblk, out, out_stride, s, sub_hist, only, skewed);
     {
         ProfScope ps(s.prof, PROF_MTF_LISTS, st, units);
-        hipLaunchKernelGGL(k_mtf_chunk_lists, g, t, 0, st, in, in_stride, n, s.lists, s.lens, s.max_chunks, only);
+        hipLaunchKernelGGL(k_mtf_chunk_lists<1>, g, t, 0, st, in, in_stride, n, s.lists, s.lens, s.max_chunks, only);
         // 16 waves of 16 chunks: the shortest chain of folds (48) for a block on its own; 8 waves of 32 (72 folds): four
         // workgroups per CU, so a batch of 1024 blocks is resident at once instead of in two rounds (0.156 -> 0.126 ms)
         if (nblk <= 512)
@@ -691,8 +804,6 @@ hipError_t mtf_forward(hipStream_t st, const uint8_t *in, size_t in_stride, uint
     }
     {
         ProfScope ps(s.prof, PROF_MTF_ENCODE, st, units);
-        // few chunks in all (a cudppCompress call, small batches): a wave per chunk, its rows the chunk's quarters
-        const bool quarters = (uint64_t)nchunks * nblk <= MTF_QUARTERS_MAX_CHUNKS;
         if (quarters && sub_hist)
             hipLaunchKernelGGL((k_mtf_encode<true, true>), g, t, 0, st, in, in_stride, n, s.lists, s.max_chunks, out,
                                out_stride, sub_hist, only);
