@@ -59,6 +59,13 @@ constexpr uint32_t FS_MAX_GROUP = 512;              // longest run of equal code
 // top one says "this bin has more than FSS_LOOK words" (set by the words that arrived as its fifth and later)
 constexpr uint32_t FS_START_MASK = 0x0FFFu, FS_BIG_BIN = 0x8000u;
 static_assert(FS_FILLMAX <= FS_START_MASK, "a bin start and the end of the last bin fit below the big-bin flag");
+// k_fs_sort_bwt, what a workgroup pays once (profiles/sort_entry.md; 0 builds the form before, for the A/B):
+#ifndef GLC_FSS_ENTRY
+#define GLC_FSS_ENTRY 1                              // the entry: workgroup order without a division, one batch of scalar loads
+#endif
+#ifndef GLC_FSS_SCAN
+#define GLC_FSS_SCAN 1                               // bin_starts(): packed halves, scalar wave number, one barrier
+#endif
 constexpr uint32_t FSS_SENT = 2 * FSS_LOOK;         // k_fs_sort_bwt: sentinels behind the last word (the rare case looks at 2 FSS_LOOK keys from a bin's start)
 
 // at least 16 buckets: k_fs_sort compares bits 28..59 of the words, so the four bits above must be bucket number
@@ -763,16 +770,56 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     uint16_t *s16 = reinterpret_cast<uint16_t *>(s_cp);
     uint8_t *s_cb = reinterpret_cast<uint8_t *>(s_cp);
     uint32_t gx, gy;
+#if GLC_FSS_ENTRY
+    xcd_order_pow2(gx, gy, nbl);                               // (the grid's x size is the bucket count, 1 << nbl)
+#else
     xcd_order(gx, gy);
+#endif
     const uint32_t b = gy, bk = gx, tid = threadIdx.x;
     // A block flagged BEFORE this kernel started -- text-like (k_fs_tables), a bucket past its slot (k_fs_part2), constant -- is
     // another sorter's: its 512 workgroups leave on a scalar load, before the table of counters is cleared and three rounds of
     // words are asked for (0.25 ms per batch of 256 text blocks were spent leaving).  Bits 1 and 8 only: nobody sets those while
     // this kernel runs, so every wave of the workgroup sees the same (what k_fs_sort_bwt itself sets, 2 and 4, goes through s_deep)
+#if GLC_FSS_ENTRY
+    // What a workgroup does once is spread over four or five words per thread, so the entry is kept short: one batch of
+    // arguments; the flag by a scalar load, and the exit; then the word requests, with nothing waited for in front of them
+    // but that flag.  The bucket's fill and rank base and the block's zero bucket -- like the flag's bits 1 and 8, nobody writes
+    // them while this kernel runs -- are scalar loads too (const_load_u32), which the compiler issues beside the word
+    // requests and waits for where the fill is first used.  The offsets into the per-block tables (b * FS_MAXNB + bk, one
+    // dword per bucket of a call) and into a block's slots (bk * FS_CAP <= 2^21) are 32-bit products; b * kstride, b * bwt_stride and b * wl_cap stay 64-bit: a block's words
+    // are 16 MiB, its work list entries 16 bytes, and neither the strides nor the number of blocks have a bound that keeps a
+    // byte offset below 2^32 (2048 blocks of words are 32 GiB).
+    // The flag's two uses want different things.  The exit wants bits 1 and 8, which are final before the launch: the scalar
+    // load gives them.  s_deep's initial value wants bits 2 and 4 as well, which OTHER workgroups of this launch set (a bin
+    // of more than FS_MAX_GROUP words, a full work list).  No result depends on seeing them: a block so flagged is sorted again
+    // by the next tier whatever this bucket writes, a full list refuses every later reservation by its count, and the flag is
+    // only ever ORed.  But a workgroup that sees them leaves behind the first barrier instead of sorting a bucket for nothing,
+    // and data with runs (zero pages in float data) flag most blocks of a call this way.  The scalar cache is not coherent with
+    // the other workgroups' atomics, so that value takes a second, vector read.  Wave 0 asks for it BEFORE the words and
+    // stores it behind them: the wait is for that one dword (vmcnt counts the word requests as still in flight), and no
+    // lane mask is held across the requests.
+    // (The empty statement wants every argument in a register HERE: the compiler otherwise fetches them where they are used,
+    // four batches with a wait each in front of the first word request.  A plain load of flag[b] under a uniform branch
+    // becomes a scalar load too, hence the atomic one: agent scope, so it is answered by the L2 the other workgroups' atomics
+    // went to.  Both are a compiler's choices, not the language's: after a toolchain change the entry's machine code is
+    // looked at again -- the list of what to find there is in profiles/sort_entry.md, "After a compiler change".)
+    asm volatile("" :: "s"(keys), "s"(kstride), "s"(fill), "s"(fbase), "s"(bwt_out), "s"(bwt_stride), "s"(d_index), "s"(wl),
+                 "s"(wl_cap), "s"(wl_count), "s"(zero_bucket));
+    const uint32_t bo = b * FS_MAXNB + bk;
+    const uint32_t f0 = const_load_u32(flag + b);
+    const uint32_t c = const_load_u32(fill + bo), R0 = const_load_u32(fbase + bo);
+    const bool zb = const_load_u32(zero_bucket + b) == bk;     // (uniform) suffix 0 is one of this bucket's words
+    if (f0 & (1u | FS_DONE)) return;
+    const bool wave0 = __builtin_amdgcn_readfirstlane(tid >> 6) == 0;
+    uint32_t f1 = 0;
+    if (wave0) f1 = __hip_atomic_load(flag + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const uint64_t *K = keys + (size_t)b * kstride + bk * FS_CAP;
+#else
     if (scalar_load_u32(flag + b) & (1u | FS_DONE)) return;
     if (tid == 0) { s_deep = flag[b]; s_wl = 0; }              // (one read: another bucket may flag the block meanwhile)
     for (uint32_t i = tid; i < FS_BINS / 2; i += FSS_NT) s_cp[i] = 0;
     const uint64_t *K = keys + (size_t)b * kstride + (size_t)bk * FS_CAP;
+#endif
     // The first FSS_SPEC full rounds are requested BEFORE the bucket's fill is known: a bucket of an i.i.d.-like block holds
     // 2048 +- 7 % words, so words 0 .. 1535 are (nearly) always there, and fill -> words was two memory latencies in a row at
     // the head of every workgroup's chain.  A slot has FS_CAP words whatever its fill: reading past the fill is harmless, and
@@ -781,9 +828,16 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     uint64_t ws[FSS_SPEC + 1];
 #pragma unroll
     for (int r = 1; r <= FSS_SPEC; r++) ws[r] = K[(r - 1) * FSS_NT + tid];
+#if GLC_FSS_ENTRY
+    static_assert(FS_BINS / 2 % FSS_NT == 0, "every thread clears the same number of counter words");
+#pragma unroll
+    for (uint32_t k = 0; k < FS_BINS / 2 / FSS_NT; k++) s_cp[k * FSS_NT + tid] = 0;
+    if (wave0) { s_deep = f1; s_wl = 0; }                      // (every lane of the wave writes the same two values)
+#else
     const uint32_t c = fill[(size_t)b * FS_MAXNB + bk];
     const uint32_t R0 = fbase[(size_t)b * FS_MAXNB + bk];
     const bool zb = zero_bucket[b] == bk;                      // (uniform) suffix 0 is one of this bucket's words
+#endif
     const uint32_t cc = c <= FS_FILLMAX ? c : 0u;              // (a fuller bucket has flagged its block in k_fs_scan)
     // item r of a thread: r = 0 -> word full * 512 + tid of the partial round (lanes tid < part), r >= 1 -> word
     // (r - 1) * 512 + tid of a full round (all lanes, r <= full)
@@ -799,6 +853,35 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     // bin counters -> bin starts (both 16-bit pairs), between the count and the scatter step of every instance
     auto bin_starts = [&]() __attribute__((always_inline)) {
         constexpr int PW = FS_BINS / 2 / FSS_NT;               // packed words per thread
+#if GLC_FSS_SCAN
+        // On packed halves: a bucket holds at most FS_FILLMAX < 2^16 words, so any sum of its counters fits one half and no
+        // carry crosses into the other.  P = [run : 16 | run : 16] walks the thread's words: the starts of word k are
+        // P + (v[k] << 16) (low bin at run, high bin at run + low count) and P moves on by v[k] + rot16(v[k]), the word's
+        // total in both halves.  Across the waves, as in bucket_excl_add_lds: the wave's number is uniform and s_tmp is
+        // written here only, once per workgroup, so ONE barrier; the "waves below mine" sum is three row shifts over the
+        // eight totals, one lane each, not eight lane-mask selects per thread.
+        static_assert(FSS_NT / WAVE == 8 && FS_FILLMAX < 0x10000u, "eight wave totals in lanes 0 .. 7 of a row; sums stay inside a half");
+        const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6), l8 = tid & 7u;
+        uint32_t v[PW], t = 0;
+#pragma unroll
+        for (int k = 0; k < PW; k++) { v[k] = s_cp[tid * PW + k]; t += v[k]; }
+        const uint32_t sum = (t & 0xFFFFu) + (t >> 16);
+        const uint32_t inc = wave_incl_add(sum);
+        if ((tid & 63u) == 63u) s_tmp[wv] = inc;
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        uint32_t x = s_tmp[l8];
+        x = l8 < wv ? x : 0u;
+        x += GLC_DPP(x, 0x111, 0xf);       // row_shr:1
+        x += GLC_DPP(x, 0x112, 0xf);       // row_shr:2
+        x += GLC_DPP(x, 0x114, 0xf);       // row_shr:4: lane 7 = the totals of the waves below mine
+        const uint32_t run = (uint32_t)__builtin_amdgcn_readlane((int)x, 7) + inc - sum;
+        uint32_t P = run | (run << 16);
+#pragma unroll
+        for (int k = 0; k < PW; k++) {
+            s_cp[tid * PW + k] = P + (v[k] << 16);
+            P += v[k] + __builtin_amdgcn_alignbit(v[k], v[k], 16);
+        }
+#else
         uint32_t v[PW], sum = 0;
 #pragma unroll
         for (int k = 0; k < PW; k++) { v[k] = s_cp[tid * PW + k]; sum += (v[k] & 0xFFFFu) + (v[k] >> 16); }
@@ -809,6 +892,7 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
             s_cp[tid * PW + k] = lo | (hi << 16);
             run = hi + (v[k] >> 16);
         }
+#endif
         if (tid == FSS_NT - 1) s_cp[FS_BINS / 2] = c;          // end of the last bin
     };
     // in LDS a word is [code bits 28..59 : 32 | the word's low dword (code bits 28..31, index, BWT byte) : 32]: the rank step
@@ -1108,6 +1192,8 @@ __global__ __launch_bounds__(FSS_NT) __attribute__((amdgpu_waves_per_eu(8, 8))) 
     const bool go = full == 3 ? rounds(std::integral_constant<int, 3>{}) : full == 4 ? rounds(std::integral_constant<int, 4>{}) : guarded();
     if (!go) return;
     // 4. the rows
+    // (Whole dwords in straight-line code, two per thread at most, and the ragged ends by eight lanes: measured, 5.04-5.11 ms
+    // per launch against this loop's 4.95-5.02, profiles/sort_entry.md.)
     {
         const uint32_t end = shift + c;                        // staged bytes [shift, end)
         for (uint32_t q = tid; 4 * q < end; q += FSS_NT) {
@@ -1318,9 +1404,13 @@ hipError_t fs_build(const SortCall &c, SaScratch &s)
         if (sa_out || !bwt_out || !d_index)                    // the suffix array itself is asked for: the kernel that writes it
             hipLaunchKernelGGL(k_fs_sort, dim3(nb, nblk), dim3(FSS_NT), 0, st, n, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
                                bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt);
-        else
+        else {
+            // the kernel finds its bucket and block by shift and mask (xcd_order_pow2): right only for a grid x of exactly
+            // 1 << nbl with nbl >= 3.  fs_bucket_log2 gives 4 .. 9 today; a rule that gives less fails here, not in the rows
+            if (nbl < 3 || nb != 1u << nbl) return hipErrorInvalidValue;
             hipLaunchKernelGGL(k_fs_sort_bwt, dim3(nb, nblk), dim3(FSS_NT), 0, st, nbl, s.keyA, s.fs_kstride, s.fs_fill, s.fs_base, s.fs_flag,
                                bwt_out, bwt_stride, d_index, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt, s.fs_zero);
+        }
     }
     hipLaunchKernelGGL(k_fs_ties, dim3(24, nblk), dim3(256), 0, st, text, text_stride, n, s.fs_wl, s.fs_wl_cap, s.fs_wlcnt,
                        s.fs_flag, bwt_out, bwt_stride, d_index, sa_out, (size_t)s.nmax);

@@ -127,8 +127,6 @@ __device__ __forceinline__ uint32_t block_excl_max(uint32_t x, uint32_t *s_tmp)
     return base > prev ? base : prev;
 }
 
-// XCD-aware order of a (x, y) grid: physical workgroup p runs on XCD p & 7; the logical workgroups are dealt out so that
-// every XCD takes one contiguous run of them (everything of a block on one XCD: what its workgroups share stays in one L2)
 // a dword every lane of the workgroup wants, through the scalar cache (a fraction of a vector load's latency, and a hit for
 // every later workgroup of the CU that asks for the same word).  Only for words nobody writes while this kernel runs: the scalar
 // cache is not coherent with stores of other workgroups.
@@ -142,12 +140,34 @@ __device__ __forceinline__ uint32_t scalar_load_u32(const uint32_t *p)
     return v;
 }
 
+// XCD-aware order of a (x, y) grid: physical workgroup p runs on XCD p & 7; the logical workgroups are dealt out so that
+// every XCD takes one contiguous run of them (everything of a block on one XCD: what its workgroups share stays in one L2)
 __device__ __forceinline__ void xcd_order(uint32_t &bx, uint32_t &by)
 {
     const uint32_t nx = gridDim.x, total = nx * gridDim.y, p = blockIdx.y * nx + blockIdx.x;
     const uint32_t q = total >> 3, r = total & 7u, x = p & 7u;
     const uint32_t lg = x * q + min(x, r) + (p >> 3);
     by = lg / nx; bx = lg % nx;
+}
+
+// xcd_order for a grid whose x size is 2^nxl, 3 <= nxl: the same mapping, workgroup for workgroup, without the run-time
+// division (a float reciprocal, two s_mul_hi and two correction steps, a serial chain in front of a workgroup's first
+// address).  total = gridDim.y << nxl is a multiple of 8, so the remainder term min(x, r) is zero and q = gridDim.y << (nxl - 3).
+// BOTH conditions are the caller's: nxl < 3 shifts by a negative count, a grid x other than 1 << nxl gives another mapping
+// (workgroups without a bucket, buckets without a workgroup).  The launch site checks them on the host.
+__device__ __forceinline__ void xcd_order_pow2(uint32_t &bx, uint32_t &by, uint32_t nxl)
+{
+    const uint32_t p = (blockIdx.y << nxl) + blockIdx.x;
+    const uint32_t lg = (p & 7u) * (gridDim.y << (nxl - 3)) + (p >> 3);
+    by = lg >> nxl; bx = lg & ((1u << nxl) - 1u);
+}
+
+// a dword at a workgroup-uniform address that NOBODY writes while the kernel runs, as a load from the constant address
+// space: the compiler picks a scalar load and places the wait for it itself, at the first use (scalar_load_u32 waits on
+// the spot)
+__device__ __forceinline__ uint32_t const_load_u32(const uint32_t *p)
+{
+    return *(const __attribute__((address_space(4))) uint32_t *)(reinterpret_cast<uintptr_t>(p));
 }
 
 
