@@ -591,6 +591,10 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
     if (h0) {
         const CtTables T = ct_tables(nb, blk_len);
         uint32_t *hist = const_cast<uint32_t *>(reinterpret_cast<const uint32_t *>(frame + CT_FRAME_HDR) + T.hist);   // (read only)
+        if (h0->kinds >> CT_KIND_DEDUP & 1u) {                 // (version 9: a kind-6 block has a table like a kind-2 block's)
+            e = ct_dec_dedup_skip(st, frame, nb, h0->skip);
+            if (e != hipSuccess) return e;
+        }
         const HdbSegs g{nullptr, nullptr, nullptr, nb, blk_len};
         e = hdb_tables(st, g, false, hist, nullptr, nullptr, h0->lut, h0->nun, h0->skip, prof);
         if (e != hipSuccess) return e;
@@ -603,6 +607,7 @@ hipError_t ct_dec_verify(hipStream_t st, const CtDecFrame &f, const uint8_t *fra
     }
     e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, nb + 2, f.crc);
     if (e != hipSuccess) return e;
+    if (h0 && (h0->kinds >> CT_KIND_DEDUP & 1u)) return ct_dec_dedup_verdict(st, f, frame, nb, blk_len, payload_words, *h0);
     hipLaunchKernelGGL(k_cd_verdict, dim3((nb + 255) / 256), dim3(256), 0, st, f, frame, nb, blk_len, payload_words,
                        h0 ? (const unsigned long long *)h0->nun : nullptr, h0 ? *h0 : CtDecHuff0{});
     return hipGetLastError();

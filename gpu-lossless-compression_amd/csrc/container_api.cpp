@@ -9,8 +9,11 @@
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
 // and the batched encoder writes the kind-2 records (frame_order0 is the one path; with the sparse mode on its parts are frame_sparse's, kinds 2 and 3; with the rANS mode on
-// frame_ans's, kind 5, the histograms alone and the kernels of ans.hip; with the auto mode on frame_auto's, the probe of auto.hip and a kind per block out of 2, 3 and 5).  With the BWT codec's
-// runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
+// frame_ans's, kind 5, the histograms alone and the kernels of ans.hip; with the auto mode on frame_auto's, the probe of auto.hip and a kind per block out of 2, 3 and 5).
+// With the order-0 codec's dedup mode on (frame_dedup, kind 6, format version 9; dedup.hip) the map of the frame's 512-byte chunks
+// runs first, the chunks that repeat an earlier chunk of the frame are elided, and the sparse mode's compaction and the batched
+// encoder work on what is kept; the decoder puts the kept chunks back and one fill pass copies the elided ones from their sources.
+// With the BWT codec's runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
 // payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
 // chain on the device (a cursor word): no host read inside or between frames, one at the end.  With the CHOOSE codec
 // (super_frame) the bigram probe of choose.hip runs over what is one frame otherwise, its stats rows are read back (the one host
@@ -26,6 +29,7 @@
 // frame is decoded into staging, checked there and inverted into the output by filter_device().
 #include "../../include/glc_container.h"
 #include "container_internal.h"
+#include "dedup_rule.h"
 
 #include <fcntl.h>
 #include <memory>
@@ -181,6 +185,7 @@ struct Encoder {
     CtEncRuns zr = {};                                        // the runs mode's, kept with the plan; a plan that never has it on has none
     CtEncAns an = {};                                         // the rANS mode's, behind h0's; a plan that never has it on has none
     CtEncAuto au = {};                                        // the auto mode's: both scratches above and its own
+    CtEncDedup dd = {};                                       // the dedup mode's: the sparse mode's scratch (masks, compaction space) and its own
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
     unsigned long long *ch_stats = nullptr, *h_stats = nullptr;   // the CHOOSE codec's probe rows [rows][4]: device, pinned
     unsigned long long choice[3] = {0, 0, 0};                 // blocks given to the BWT codec, to the order-0 codec; frames
@@ -211,7 +216,7 @@ struct Encoder {
     void carve_huff0(Carver &c)
     {
         const size_t R = P.rows;
-        const bool sparse = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, ans = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
+        const bool sparse = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO || mode == CT_MODE_DEDUP, ans = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
         h0.nun = c.take<unsigned long long>(R);
         h0.blk_off = c.take<unsigned long long>(R);
         h0.blk_len = c.take<unsigned long long>(R);
@@ -252,6 +257,21 @@ struct Encoder {
         sp.skip_table = c.take<uint32_t>(R);
         c.align(256);
         sp.kept = c.take<uint8_t>(R * sp.kept_stride);
+        if (mode != CT_MODE_DEDUP) return;
+        // the map's table and hashes, the map itself and what the records take from it: ONE set whether pipelining is on or off,
+        // like the compaction space -- everything of a dedup frame runs on the plan's stream in order, so a second set would never
+        // be in use.  It grows with the plan's codec scratch, whose growth joins the side stream first (GrowBuf).
+        dd.nch = (P.n + DD_CHUNK - 1) / DD_CHUNK;
+        dd.mask_stride = (dd.nch + 31) / 32;
+        dd.slots = (uint32_t)dedup_slots(R * dd.nch);
+        dd.src = c.take<uint32_t>(R * dd.nch);
+        dd.refs = c.take<uint32_t>(R * dd.nch);
+        dd.mask = c.take<uint32_t>(R * dd.mask_stride);
+        dd.E = c.take<uint32_t>(R);
+        dd.lo = c.take<uint32_t>(R);
+        c.align(16);
+        dd.table = c.take<DdSlot>((size_t)dd.slots + 1);
+        dd.hash = c.take<uint64_t>(R * dd.nch);
     }
     void carve(Carver &c)
     {
@@ -326,7 +346,7 @@ struct Encoder {
         if (by == CT_CODEC_HUFF0) {
             const Frame0 F{f, d_in, orig, nb, blk_len, out, cap};
             return mode == CT_MODE_SPARSE ? frame_sparse(F) : mode == CT_MODE_ANS ? frame_ans(F) : mode == CT_MODE_AUTO ? frame_auto(F) :
-                                            frame_plain(F);
+                   mode == CT_MODE_DEDUP ? frame_dedup(F) : frame_plain(F);
         }
         const uint32_t nsub = (blk_len + HUFF_BLOCK - 1) / HUFF_BLOCK;
         ContainerHooks hk;
@@ -463,6 +483,44 @@ struct Encoder {
             });
     }
 
+    // the dedup mode, wholly on the plan's stream: the map of the frame's chunks (hash, insert, verify) -> per block the mask, the
+    // refs, the lowest source block and kind 6 or 2 -> compaction of the kind-6 blocks (the sparse mode's mover under the mask
+    // widened to 64-byte chunks) -> counts and tables, of K or of the whole block -> record sizes and the record rule -> payload
+    // offsets -> masks and refs into the records and every stream encoded behind them.  Its kinds kernel is its own, so the
+    // sequence is frame_order0's with that one step exchanged.
+    CUDPPResult frame_dedup(const Frame0 &F)
+    {
+        KernelProf *prof = plan_prof(P.h);
+        const CtEncFrame &f = F.f;
+        const uint32_t nb = F.nb, blk_len = F.blk_len;
+        uint32_t *out_words = reinterpret_cast<uint32_t *>(F.out);
+        const unsigned long long cap_words = F.cap / 4;
+        const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
+        plan_stage_mark(P.h, 0);
+        CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, nb, blk_len));
+        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));          // (klen itself comes two steps on)
+        DdSegs m{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, dd.hash, dd.table, dd.slots, dd.src, nb, blk_len, dd.nch};
+        m.nch = (blk_len + DD_CHUNK - 1) / DD_CHUNK;                                       // (the frame's: the tail frame's blocks are shorter)
+        m.slots = (uint32_t)dedup_slots((size_t)nb * m.nch);
+        CtEncDedup d = dd;
+        d.nch = m.nch;
+        CT_TRY(dedup_map(P.st, m));
+        CT_TRY(ct_enc_dedup_decide(P.st, d, sp, h0.blk_off, F.d_in, nb, blk_len, f.hist, h0.in_off, h0.in_len));
+        const SpSegs s{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr,
+                       sp.mask_stride, sp.skip_move, nb, blk_len};
+        CT_TRY(sparse_compact(P.st, s));
+        CT_TRY(hdb_tables(P.st, g2, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
+        plan_stage_mark(P.h, 1);
+        CT_TRY(ct_enc_dedup_kind(P.st, f, h0, sp, d, nb, blk_len, state));
+        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)cap_words, status));
+        CT_TRY(ct_enc_dedup_place(P.st, f, sp, d, nb, blk_len, out_words, cap_words));
+        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, out_words, sp.unit_off, cap_words, f.only, h0.work, prof));
+        plan_stage_mark(P.h, 2);
+        CT_TRY(ct_enc_after_pack(P.st, f, F.d_in, F.orig, nb, blk_len, F.out, F.cap, state));
+        plan_stage_mark(P.h, 3);
+        return CUDPP_SUCCESS;
+    }
+
     // the BWT codec's frame with the runs mode on, wholly on the plan's stream: BWT and MTF of the blocks by the plan's sorter
     // and MTF stage -> the split into A and B -> tables of the A's (their counts are the record's hist) and of the B's -> nz,
     // record sizes and the record rule -> payload offsets -> nz and the pairs into the records -> every stream encoded at its
@@ -546,6 +604,7 @@ struct Decoder {
     unsigned long long *h_verdict = nullptr;                  // pinned
     CtFormat fmt;                                             // the stream header's
     CtDecHuff0 h0 = {};
+    CtDecDedup dd = {};                                       // a version-9 frame's map and widened masks, behind h0's
 
     // the scratch of a frame that may hold kind 2, kept with the plan: tables for nb blocks, span-function prefixes for `chunk`
     // of them at a time (at most the plan's rows, and at most 256 MiB of prefixes)
@@ -562,7 +621,7 @@ struct Decoder {
             c.align(256);
             h0.ans_tab = c.take<uint8_t>((size_t)h0.chunk * ANS_TAB_BYTES);
         }
-        if (!fmt.kind3_legal() && !fmt.kind4_legal()) return;
+        if (!fmt.kind3_legal() && !fmt.kind4_legal() && !fmt.kind6_legal()) return;
         h0.k_off = c.take<unsigned long long>(n4);
         h0.k_len = c.take<unsigned long long>(n4);
         h0.u_off = c.take<unsigned long long>(n4);
@@ -570,6 +629,12 @@ struct Decoder {
         c.align(256);
         h0.kept_stride = (blk_len + 15u) & ~15u;
         h0.kept = c.take<uint8_t>((size_t)h0.chunk * h0.kept_stride);
+        if (fmt.kind6_legal()) {
+            dd.chunk = h0.chunk;
+            dd.stride64 = sp_mask_words(blk_len);
+            dd.src = c.take<uint32_t>((size_t)nb * ((blk_len + DD_CHUNK - 1) / DD_CHUNK));
+            dd.mask64 = c.take<uint32_t>((size_t)h0.chunk * dd.stride64);
+        }
         if (!fmt.kind4_legal()) return;
         h0.kept_b = c.take<uint8_t>((size_t)h0.chunk * h0.kept_stride);
         h0.b_off = c.take<unsigned long long>(n4);
@@ -638,14 +703,18 @@ struct Decoder {
     // With a subset (a range read: need[b] != 0 = block b is wanted) the frame gets every check of its tables and records as
     // ever, but only the wanted blocks are decoded, into the plan's staging at their own places whatever the format, and
     // checked there; *staged is the staging and final_out is not touched (the inverse filter of a range is the caller's).
+    // In a version-9 frame a wanted kind-6 block b needs the blocks [bwt_index[b], b) as sources (dedup_rule.h): they are decoded
+    // and joined as well, but neither filled nor compared with their crc_raw; *decoded counts them with the wanted ones.
     CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi,
-                      const uint8_t *need = nullptr, uint8_t **staged = nullptr)
+                      const uint8_t *need = nullptr, uint8_t **staged = nullptr, unsigned long long *decoded = nullptr)
     {
         CT_TRY(reserve(nb));
         uint8_t *out = final_out;
         if (fmt.filtered() || need) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
         if (staged) *staged = out;
+        std::vector<uint8_t> need9;                               // version 9: need[] with the source-only blocks marked 2
         auto want = [&](uint32_t b) { return !need || need[b] != 0; };
+        auto checked = [&](uint32_t b) { return !need || need[b] == DEDUP_NEEDED; };
         // over the runs of wanted blocks (all of them: one run)
         auto runs = [&](auto call) -> hipError_t {
             for (uint32_t a = 0; a < nb;) {
@@ -667,6 +736,16 @@ struct Decoder {
         if (h_verdict[0]) return fail(P.h, CT_FRAME_TABLE, fi);
         if (h_verdict[1] != ~0ull) return fail(P.h, h_verdict[1] >> 32, fi, h_verdict[1] & 0xFFFFFFFFu);
         const uint32_t *kind = reinterpret_cast<const uint32_t *>(h_verdict + 2);
+        if (need && fmt.kind6_legal()) {
+            const CtTables T9 = ct_tables(nb, blk_len);
+            std::vector<uint32_t> idx(nb);
+            CT_TRY(hipMemcpyAsync(idx.data(), fr + CT_FRAME_HDR + 4 * T9.bwt, 4ull * nb, hipMemcpyDeviceToHost, P.st));
+            CT_TRY(hipStreamSynchronize(P.st));
+            need9.assign(need, need + nb);
+            (void)dedup_mark_sources(kind, idx.data(), nb, need9.data());   // (every run of needed blocks asks for its sources)
+            need = need9.data();
+        }
+        if (decoded) for (uint32_t b = 0; b < nb; b++) *decoded += want(b) ? 1 : 0;
         CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_raw(P.st, f, fr, nb, blk_len, out, a, cnt); }));
         const CtTables T = ct_tables(nb, blk_len);
         const uint32_t *W = reinterpret_cast<const uint32_t *>(fr + CT_FRAME_HDR);
@@ -731,9 +810,41 @@ struct Decoder {
             return CUDPP_SUCCESS;
         });
         if (r != CUDPP_SUCCESS) return r;
+        // dedup blocks inside one chunk of the decoder: K decoded into scratch and put back under the mask (widened to 64-byte
+        // chunks for the sparse mode's join, which leaves its fill byte in the elided chunks until the fill pass)
+        if (fmt.kind6_legal()) {
+            CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_dedup_expand(P.st, fr, nb, blk_len, a, cnt, dd, false); }));
+            r = runs_of(CT_KIND_DEDUP, same_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+                const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len};
+                CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
+                CT_TRY(ct_dec_dedup_expand(P.st, fr, nb, blk_len, a, cnt, dd, true));
+                const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a,
+                               dd.mask64 + (size_t)(a % dd.chunk) * dd.stride64, nullptr, dd.stride64, nullptr, cnt, blk_len};
+                CT_TRY(sparse_join(P.st, s));
+                return CUDPP_SUCCESS;
+            });
+            if (r != CUDPP_SUCCESS) return r;
+        }
         plan_join(P.h);
+        // the fill: behind every join of the frame, in front of the decoded-CRC pass; sources are kept chunks, so one pass completes
+        // the frame.  Only the blocks that are checked are filled.
+        auto runs_checked = [&](auto call) -> hipError_t {
+            for (uint32_t a = 0; a < nb;) {
+                if (!checked(a)) { a++; continue; }
+                uint32_t b = a;
+                while (b < nb && checked(b)) b++;
+                const hipError_t e = call(a, b - a);
+                if (e != hipSuccess) return e;
+                a = b;
+            }
+            return hipSuccess;
+        };
+        if (fmt.kind6_legal()) {
+            const DdSegs g{nullptr, f.seg_off, f.seg_len, nullptr, nullptr, 0, dd.src, nb, blk_len, (blk_len + DD_CHUNK - 1) / DD_CHUNK};
+            CT_TRY(runs_checked([&](uint32_t a, uint32_t cnt) { return dedup_fill(P.st, g, a, cnt); }));
+        }
         if (need) {
-            CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
+            CT_TRY(runs_checked([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
             return CUDPP_SUCCESS;
         }
         CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !fmt.filtered()));
@@ -1235,9 +1346,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         unsigned long long i0 = 0, i1 = 0;
         const std::vector<uint8_t> need = needed_blocks(ix->fmt, F.nb, F.bl, a, b, &i0, &i1);
         uint8_t *stage = nullptr;
-        if ((r = D.frame(fr, F.nb, F.bl, F.pw, nullptr, (uint32_t)fi, need.data(), &stage)) != CUDPP_SUCCESS) return r;
+        if ((r = D.frame(fr, F.nb, F.bl, F.pw, nullptr, (uint32_t)fi, need.data(), &stage, &stats.v[1])) != CUDPP_SUCCESS) return r;
         stats.v[0] += 1;
-        for (uint8_t w : need) stats.v[1] += w;
         stats.v[2] += fb;
         const unsigned long long at = F.out_off - offset;       // (+ a frame byte = its place in the range; never negative there)
         if (!ix->fmt.filtered()) {
@@ -1551,6 +1661,51 @@ CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long lo
     return CUDPP_SUCCESS;
 }
 
+// the dedup calls: a bad argument is refused before anything is enqueued
+static size_t dedup_chunks(size_t count, size_t maxLen)
+{
+    if (count > GLC_DEDUP_MAX_COUNT || maxLen > GLC_DEDUP_MAX_LEN) return (size_t)-1;
+    const size_t chunks = count * ((maxLen + DD_CHUNK - 1) / DD_CHUNK);
+    return chunks > DD_MAX_CHUNKS ? (size_t)-1 : chunks;
+}
+
+size_t glcDedupWorkBytes(size_t count, size_t maxLen)
+{
+    const size_t chunks = dedup_chunks(count, maxLen);
+    if (chunks == (size_t)-1 || chunks == 0) return 0;
+    return (dedup_slots(chunks) + 1) * sizeof(DdSlot) + chunks * sizeof(uint64_t);
+}
+
+CUDPPResult glcDedupMapSegments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
+                                size_t maxLen, unsigned int *d_src, void *d_work, size_t workBytes, void *stream)
+{
+    const size_t chunks = dedup_chunks(count, maxLen);
+    if (chunks == (size_t)-1) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (chunks == 0) return CUDPP_SUCCESS;
+    if (!d_base || !d_offsets || !d_lengths || !d_src || !d_work || (reinterpret_cast<uintptr_t>(d_src) & 3) ||
+        (reinterpret_cast<uintptr_t>(d_work) & 15) || workBytes < glcDedupWorkBytes(count, maxLen))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const size_t slots = dedup_slots(chunks);
+    DdSlot *table = static_cast<DdSlot *>(d_work);
+    const DdSegs g{static_cast<uint8_t *>(const_cast<void *>(d_base)), d_offsets, d_lengths, reinterpret_cast<uint64_t *>(table + slots + 1),
+                   table, (uint32_t)slots, d_src, (uint32_t)count, (uint32_t)maxLen, (uint32_t)((maxLen + DD_CHUNK - 1) / DD_CHUNK)};
+    CT_TRY(dedup_map(reinterpret_cast<hipStream_t>(stream), g));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcDedupFillSegments(void *d_outBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
+                                 size_t maxLen, const unsigned int *d_src, void *stream)
+{
+    const size_t chunks = dedup_chunks(count, maxLen);
+    if (chunks == (size_t)-1) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (chunks == 0) return CUDPP_SUCCESS;
+    if (!d_outBase || !d_offsets || !d_lengths || !d_src || (reinterpret_cast<uintptr_t>(d_src) & 3)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const DdSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, nullptr, nullptr, 0, const_cast<unsigned int *>(d_src),
+                   (uint32_t)count, (uint32_t)maxLen, (uint32_t)((maxLen + DD_CHUNK - 1) / DD_CHUNK)};
+    CT_TRY(dedup_fill(reinterpret_cast<hipStream_t>(stream), g));
+    return CUDPP_SUCCESS;
+}
+
 // the two zero-run calls: a bad argument is refused before anything is enqueued
 static bool zrun_args_ok(const void *x, const void *off, const void *len, const void *a, const void *b, const void *alen, const void *blen,
                          size_t count, size_t maxLen)
@@ -1743,6 +1898,22 @@ CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
     Plan P;
     if (const CUDPPResult bad = P.check(plan)) return bad;
     return plan_container_settings(plan).set_mode(CT_MODE_SPARSE, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+}
+
+CUDPPResult glcPlanSetContainerDedup(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    return plan_container_settings(plan).set_mode(CT_MODE_DEDUP, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+}
+
+CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).mode == CT_MODE_DEDUP ? 1u : 0u;
+    return CUDPP_SUCCESS;
 }
 
 CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)

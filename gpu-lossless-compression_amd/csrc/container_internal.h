@@ -115,6 +115,27 @@ hipError_t sparse_count(hipStream_t st, const SpSegs &g, unsigned long long *d_k
 hipError_t sparse_compact(hipStream_t st, const SpSegs &g);                               // data, mask -> K
 hipError_t sparse_join(hipStream_t st, const SpSegs &g);                                  // K, mask, fill -> data
 
+// the dedup passes (dedup.hip; the hash and the rule are defined in INTEGRATION.md 4b).  The segments are the blocks of one frame
+// in order: segment i is data + data_off[i], min(data_len[i], max_len) bytes, cut into chunks of 512; chunk c of it has the id
+// i * nch + c, nch = ceil(max_len / 512).  hash[id] and the table (slots, a power of two >= 2 * count * nch, plus one slot for the
+// key that equals the empty mark) are scratch of dedup_map; src[id] = the id of the chunk's source, or id itself for a kept chunk.
+// data may be null with absolute addresses in data_off.  Everything only enqueues on `st`.
+constexpr uint32_t DD_CHUNK = 512, DD_MAX_LEN = 1u << 20;
+constexpr size_t DD_MAX_CHUNKS = (size_t)1 << 30;
+struct DdSlot { uint64_t key; uint32_t id, pad; };
+struct DdSegs {
+    uint8_t *data; const unsigned long long *data_off, *data_len;
+    uint64_t *hash; DdSlot *table; uint32_t slots;
+    uint32_t *src;
+    uint32_t count, max_len, nch;
+};
+size_t dedup_slots(size_t chunks);
+hipError_t dedup_map(hipStream_t st, const DdSegs &g);       // data -> src (the writer's rule: the smallest id with equal hash, verified)
+// src -> data, in place: a chunk whose entry is smaller than its id and names a chunk of its own length is copied from there;
+// every other entry is skipped.  Nothing is read or written outside the segments.
+// segments [first, first + count) only (count 0: all of them from `first` on); sources may lie in any segment
+hipError_t dedup_fill(hipStream_t st, const DdSegs &g, uint32_t first = 0, uint32_t count = 0);
+
 // the zero-run passes (zrun.hip; the split is defined in INTEGRATION.md 4b).  Segment i is x + x_off[i], min(x_len[i], max_len)
 // bytes, cut into tiles of 256; A (the non-zero bytes and one 0 per run of zeros, a run ending at a tile edge) is at a + a_off[i],
 // B (run length - 1 per run) at b + b_off[i], their byte counts in a_len[i] / b_len[i].  Any base may be null with absolute
@@ -181,14 +202,15 @@ constexpr uint32_t CT_VERSION_SPARSE = 5;                    // 5: kind 3 is leg
 constexpr uint32_t CT_VERSION_RUNS = 6;                      // 6: kinds 0, 1, 2 and 4 are legal (not 3); the same triples as version 5
 constexpr uint32_t CT_VERSION_ANS = 7;                       // 7: kinds 0, 1, 2 and 5 are legal (not 3, not 4); the same triples as version 5
 constexpr uint32_t CT_VERSION_AUTO = 8;                      // 8: kinds 0, 1, 2, 3 and 5 are legal (not 4); the same triples as version 5
+constexpr uint32_t CT_VERSION_DEDUP = 9;                     // 9: kinds 0, 1, 2 and 6 are legal (not 3, 4, 5); the same triples as version 5
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
-// its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7)
-constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8;
+// its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9
+constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_AUTO + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F};
-    return version <= CT_VERSION_AUTO ? K[version] : 0u;
+    constexpr uint32_t K[CT_VERSION_DEDUP + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47};
+    return version <= CT_VERSION_DEDUP ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
@@ -202,18 +224,20 @@ struct CtFormat {
     __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
     __host__ __device__ bool kind4_legal() const { return (kinds() >> 4 & 1u) != 0; }
     __host__ __device__ bool kind5_legal() const { return (kinds() >> 5 & 1u) != 0; }
+    __host__ __device__ bool kind6_legal() const { return (kinds() >> 6 & 1u) != 0; }
     // the CT_READS_* bit a plan must have to speak this version (0: every plan does)
     __host__ __device__ uint32_t reads() const
     {
         return version == CT_VERSION_SPARSE ? CT_READS_SPARSE : version == CT_VERSION_RUNS ? CT_READS_RUNS :
-               version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO : 0u;
+               version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
+               version == CT_VERSION_DEDUP ? CT_READS_DEDUP : 0u;
     }
 };
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 struct CtLegal { uint32_t version, flags, elems; };
-constexpr uint32_t CT_NLEGAL = 12;
+constexpr uint32_t CT_NLEGAL = 14;
 __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 {
     constexpr CtLegal L[CT_NLEGAL] = {
@@ -222,7 +246,8 @@ __host__ __device__ inline CtLegal ct_legal(uint32_t i)
         {CT_VERSION_SPARSE, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_RUNS, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_ANS, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_ANS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_AUTO, 0, CT_NO_FILTER | CT_ELEMS},
-        {CT_VERSION_AUTO, CT_FLAG_DELTA, CT_ELEMS}};
+        {CT_VERSION_AUTO, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_DEDUP, 0, CT_NO_FILTER | CT_ELEMS},
+        {CT_VERSION_DEDUP, CT_FLAG_DELTA, CT_ELEMS}};
     return L[i];
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
@@ -238,13 +263,14 @@ constexpr uint32_t CT_KIND_HUFF0 = 2;                        // order-0 Huffman 
 constexpr uint32_t CT_KIND_SPARSE = 3;                       // sparse order-0 record (sparse.hip): mask, then the kind-2 stream of the kept chunks; version 5
 constexpr uint32_t CT_KIND_RUNS = 4;                         // zero-run BWT record (zrun.hip): B's counts, then the kind-2 streams of A and B; version 6
 constexpr uint32_t CT_KIND_ANS = 5;                          // rANS order-0 record (ans.hip): chunk unit counts, then every chunk's 64 states and units; version 7
+constexpr uint32_t CT_KIND_DEDUP = 6;                        // dedup order-0 record (dedup.hip): mask, source ids of the elided chunks, then the kind-2 stream of the kept chunks; version 9
 constexpr uint32_t CT_CODEC_BWT = 0, CT_CODEC_HUFF0 = 1;     // GlcContainerCodec
 // CHOOSE: the writer gives each block to one of the two codecs (choose_rule.h) and cuts a frame wherever the choice changes.  It
 // takes no mode (each belongs to one codec) and no filter (a filter is per frame, and the choice would be made on filtered bytes)
 constexpr uint32_t CT_CODEC_CHOOSE = 4;                      // (2 and 3 stay refused: callers and tests have long used them as the bad value)
-// the writer's mode: which record kinds beyond its codec's plain ones it may emit (3; 4; 5; 3 and 5).  At most one is on, and
-// each belongs to one codec: runs to the BWT codec, sparse, rANS and auto to the order-0 codec
-enum CtMode : uint32_t { CT_MODE_PLAIN = 0, CT_MODE_SPARSE, CT_MODE_RUNS, CT_MODE_ANS, CT_MODE_AUTO };
+// the writer's mode: which record kinds beyond its codec's plain ones it may emit (3; 4; 5; 3 and 5; 6).  At most one is on, and
+// each belongs to one codec: runs to the BWT codec, sparse, rANS, auto and dedup to the order-0 codec
+enum CtMode : uint32_t { CT_MODE_PLAIN = 0, CT_MODE_SPARSE, CT_MODE_RUNS, CT_MODE_ANS, CT_MODE_AUTO, CT_MODE_DEDUP };
 __host__ __device__ inline bool ct_mode_fits(CtMode mode, uint32_t codec)
 {
     return mode == CT_MODE_PLAIN || codec == (mode == CT_MODE_RUNS ? CT_CODEC_BWT : CT_CODEC_HUFF0);   // (none fits CHOOSE)
@@ -434,7 +460,7 @@ struct CtSettings {
     uint32_t reader() const
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
-               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : 0u;
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
     uint32_t kinds() const
@@ -442,7 +468,8 @@ struct CtSettings {
         const bool k3 = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, k5 = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
         return 1u << CT_KIND_RAW | (codec != CT_CODEC_HUFF0 ? 1u << CT_KIND_HUFF : 0u) | (codec != CT_CODEC_BWT ? 1u << CT_KIND_HUFF0 : 0u) |
                (k3 ? 1u << CT_KIND_SPARSE : 0u) |
-               (mode == CT_MODE_RUNS ? 1u << CT_KIND_RUNS : 0u) | (k5 ? 1u << CT_KIND_ANS : 0u);
+               (mode == CT_MODE_RUNS ? 1u << CT_KIND_RUNS : 0u) | (k5 ? 1u << CT_KIND_ANS : 0u) |
+               (mode == CT_MODE_DEDUP ? 1u << CT_KIND_DEDUP : 0u);
     }
 };
 // the writer's format: the lowest legal version whose kinds include every kind the settings may write
@@ -545,6 +572,21 @@ struct CtEncAuto {                                         // device scratch of 
     uint32_t *hist_s;                                      // [rows][256] candidate S's counts: the block's, or K's where S is kind 3
     uint32_t *wa, *pick5;                                  // [rows] the estimate wA; 1 = the block is coded as kind 5
 };
+struct CtEncDedup {                                        // device scratch of the dedup mode, behind CtEncSparse's (allocated once it is on)
+    uint32_t *src, *refs; uint32_t nch;                    // [rows][nch]: the frame's map; each block's refs in chunk order
+    uint32_t *mask; uint32_t mask_stride;                  // [rows][mask_stride] words: the 512-byte-chunk masks (sp.mask holds them widened to 64-byte chunks)
+    uint32_t *E, *lo;                                      // [rows] elided chunks; the lowest block a source lies in
+    DdSlot *table; uint64_t *hash; uint32_t slots;         // the map's scratch: slots + 1 slots, rows * nch hashes
+};
+// the dedup mode's steps (dedup.hip), in order, behind dedup_map: kind 6 or 2 per block from its row of the map (mask, refs, E,
+// lo; for a kind-6 block sp's fields as the sparse mode leaves them, the mask widened for sparse_compact, and zero counts where
+// nothing is kept); the mode's ct_enc_kind; and behind the payload offsets mask and refs into the records and sp.unit_off
+hipError_t ct_enc_dedup_decide(hipStream_t st, const CtEncDedup &dd, const CtEncSparse &sp, const unsigned long long *blk_off, const uint8_t *d_in,
+                               uint32_t nb, uint32_t blk_len, uint32_t *hist, unsigned long long *in_off, unsigned long long *in_len);
+hipError_t ct_enc_dedup_kind(hipStream_t st, const CtEncFrame &f, const CtEncHuff0 &h, const CtEncSparse &sp, const CtEncDedup &dd, uint32_t nb,
+                             uint32_t blk_len, const CtEncState *state);
+hipError_t ct_enc_dedup_place(hipStream_t st, const CtEncFrame &f, const CtEncSparse &sp, const CtEncDedup &dd, uint32_t nb, uint32_t blk_len,
+                              uint32_t *out, unsigned long long cap_words);
 hipError_t ct_enc_header(hipStream_t st, uint8_t *out, unsigned long long cap, const uint32_t hdr[8], CtEncState *state);
 hipError_t ct_block_offsets(hipStream_t st, unsigned long long *off, unsigned long long *len, uint32_t nb, uint32_t blk_len);   // off[b] = b * blk_len
 // the order-0 codec's ct_enc_kind in every mode of that codec (the scratch of a mode that is off is not touched).  A block is
@@ -627,6 +669,18 @@ struct CtDecHuff0 {                                        // device scratch of 
     // verified histograms behind the verdict
     uint8_t *ans_tab;                                      // [chunk] ANS_TAB_BYTES
 };
+struct CtDecDedup {                                        // device scratch of a version-9 frame, beside CtDecHuff0's (k_off / k_len / u_off / skip3 / kept serve K)
+    uint32_t *src;                                         // [nb][nch] the frame's map: own ids, refs at the elided chunks of kind-6 blocks
+    uint32_t *mask64; uint32_t stride64, chunk;            // [chunk][stride64] a kind-6 block's mask widened to 64-byte chunks (block b in row b % chunk)
+};
+// version 9 (dedup.hip): the tables of the kind-6 blocks join those k_cd_segs asks for; the verdict of a frame of kinds 0, 1, 2
+// and 6 (ct_dec_verify calls both); src rows (masks = false) or widened masks (true) of blocks [first, first + count) of a
+// verified frame
+hipError_t ct_dec_dedup_skip(hipStream_t st, const uint8_t *frame, uint32_t nb, uint32_t *skip0);
+hipError_t ct_dec_dedup_verdict(hipStream_t st, const CtDecFrame &f, const uint8_t *frame, uint32_t nb, uint32_t blk_len,
+                                unsigned long long payload_words, const CtDecHuff0 &h0);
+hipError_t ct_dec_dedup_expand(hipStream_t st, const uint8_t *frame, uint32_t nb, uint32_t blk_len, uint32_t first, uint32_t count,
+                               const CtDecDedup &dd, bool masks);
 // the counts of B of every kind-4 block from its record's pairs (zeros where the record does not hold well-formed pairs), and
 // whose table is built from them
 hipError_t ct_dec_runs_hist(hipStream_t st, const uint8_t *frame, uint32_t nb, uint32_t blk_len, unsigned long long payload_words,

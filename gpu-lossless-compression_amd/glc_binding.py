@@ -661,6 +661,7 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerAns", "glcPlanGetContainerAns",
                      "glcProbeSegments", "glcPlanSetContainerAuto", "glcPlanGetContainerAuto",
                      "glcBigramProbeSegments", "glcContainerLastChoice",
+                     "glcDedupWorkBytes", "glcDedupMapSegments", "glcDedupFillSegments", "glcPlanSetContainerDedup", "glcPlanGetContainerDedup",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -730,6 +731,12 @@ def _ct():
         L.glcProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcBigramProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.glcContainerLastChoice.argtypes = [sz, ullp]
+        L.glcPlanSetContainerDedup.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerDedup.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcDedupWorkBytes.argtypes = [sz, sz]
+        L.glcDedupWorkBytes.restype = sz
+        L.glcDedupMapSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp]
+        L.glcDedupFillSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L._ct_ready = True
     return L
 
@@ -895,6 +902,20 @@ def container_set_auto(plan, on):
 def container_get_auto(plan):
     d = C.c_uint(0)
     _chk("glcPlanGetContainerAuto", _ct().glcPlanGetContainerAuto(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def container_set_dedup(plan, on):
+    """the dedup mode of the plan's container ENCODER (format version 9: 512-byte chunks that repeat an earlier chunk of their frame
+    are elided, kind 6): True / 1 needs the order-0 codec and the sparse, rANS and auto modes off; a codec change also switches it
+    off.  It is also the version the plan reads: on, versions 1 to 4 and 9; off, a version-9 stream is a stream-header failure as it
+    always was."""
+    _chk("glcPlanSetContainerDedup", _ct().glcPlanSetContainerDedup(plan.handle, int(on)))
+
+
+def container_get_dedup(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerDedup", _ct().glcPlanGetContainerDedup(plan.handle, C.byref(d)))
     return int(d.value)
 
 
@@ -1069,6 +1090,48 @@ def sparse_join_segments(d_kept, d_out, offsets, lengths, fill, mask, max_len=No
     _chk("glcSparseJoinSegments", _ct().glcSparseJoinSegments(d_kept.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
                                                                fl.data_ptr(), m.data_ptr(), d_out.data_ptr(), stream))
     torch.cuda.synchronize(d_kept.device)
+    return d_out
+
+
+DEDUP_CHUNK = 512
+
+
+def dedup_chunks(max_len):
+    return (int(max_len) + DEDUP_CHUNK - 1) // DEDUP_CHUNK
+
+
+def dedup_map_segments(d_base, offsets, lengths, max_len=None, stream=None):
+    """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_base as the blocks of one frame, cut into 512-byte
+    chunks: an int32 tensor [count * dedup_chunks(max_len)] with, for chunk c of segment i at i * nch + c, the id of the earlier
+    chunk it repeats under the writer's rule, or its own id"""
+    import torch
+    dev = d_base.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    L = _ct()
+    src = torch.zeros(max(1, off.numel() * dedup_chunks(max_len)), dtype=torch.int32, device=dev)
+    work = torch.empty(max(16, int(L.glcDedupWorkBytes(off.numel(), max_len))), dtype=torch.uint8, device=dev)
+    _chk("glcDedupMapSegments", L.glcDedupMapSegments(d_base.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len, src.data_ptr(),
+                                                      work.data_ptr(), work.numel(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln / work are temporaries of this call)
+    return src[:off.numel() * dedup_chunks(max_len)]
+
+
+def dedup_fill_segments(d_out, offsets, lengths, src, max_len=None, stream=None):
+    """the inverse of dedup_map_segments, in place: every chunk whose entry of `src` is not its own id is copied from the chunk the
+    entry names"""
+    import torch
+    dev = d_out.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    s = src.contiguous()
+    assert s.numel() == off.numel() * dedup_chunks(max_len)
+    _chk("glcDedupFillSegments", _ct().glcDedupFillSegments(d_out.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
+                                                             s.data_ptr() if s.numel() else None, stream))
+    torch.cuda.synchronize(dev)
     return d_out
 
 

@@ -78,7 +78,8 @@
  * the blocks that chose them.  The stream is format version 8, whose frames may mix kinds 0, 1, 2, 3 and 5; no record changes.  The
  * model's sizes are in INTEGRATION.md 4b ("auto: when"): never below the better of the two modes on nine inputs, above both on
  * mixed frames (int64 timestamps 6.412 against 6.188 and 6.261).  A plan with the mode on reads versions 1 to 5, 7 and 8: it is the
- * one reader for everything the order-0 codec has written.  Measured on one MI355X on 1 GiB of device-generated data in 1 MiB
+ * one reader for everything the order-0 codec has written in versions 1 to 8 (version 9, the dedup mode's, is read by a plan with
+ * that mode on).  Measured on one MI355X on 1 GiB of device-generated data in 1 MiB
  * blocks, rows 512 (profiles/auto_mode.md; ratio / encode / decode GB/s, medians of 5 interleaved rounds): int64 timestamps with
  * delta + shuffle 8, sparse 6.771 / 449 / 172, rANS 6.809 / 383 / 353, auto 7.008 / 396 / 291; uint32 counters with delta +
  * shuffle 4, sparse 9.999 / 450 / 198, rANS 9.835 / 387 / 360, auto 10.218 / 401 / 301; scattered 90 % zeros, sparse 5.677 / 470 /
@@ -179,6 +180,29 @@ CUDPPResult glcSparseSplitSegments(const void *d_inBase, const unsigned long lon
 CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                                   size_t count, size_t maxLen, const unsigned int *d_fill, const unsigned int *d_mask, void *d_outBase,
                                   void *stream);
+
+/* The two passes of frame-wide chunk dedup as batched calls (csrc/dedup.hip; the hash and the writer's rule are INTEGRATION.md 4b,
+ * "dedup").  The segments are the blocks of one frame, in order: segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of its
+ * base, cut into chunks of 512 bytes from its start (the last may be short); with nch = ceil(maxLen / 512), chunk c of segment i has
+ * the id i * nch + c.  Map writes d_src[id] for every id below count * nch: the id of the chunk's source under the writer's rule --
+ * the smallest id whose chunk has the same 64-bit hash, when that id is smaller and the two chunks agree in length and in every
+ * byte -- and the chunk's own id otherwise (a kept chunk; also the entry of an id past its segment's end).  A source is therefore
+ * always a kept chunk.  d_work: glcDedupWorkBytes(count, maxLen) bytes of device memory, 16-byte aligned, for the duration of the
+ * call's work (a hash table of 16 bytes a slot, at least two slots a chunk, and 8 bytes of hash per chunk).  Fill is the inverse, in
+ * place: every chunk whose entry is not its own id is copied from the chunk the entry names.  It is tolerant: an entry that is not
+ * smaller than the chunk's id, or whose source has another length, is skipped, so nothing is read or written outside the segments
+ * whatever d_src holds (an entry that names a chunk which is itself copied gives that chunk's bytes of before or after its copy).
+ * Any byte alignment of the segments; the calls only enqueue on `stream`.  A bad argument (a null pointer with work to do, d_src
+ * not 4-byte or d_work not 16-byte aligned, a work space too small, a maxLen above GLC_DEDUP_MAX_LEN, a count above
+ * GLC_DEDUP_MAX_COUNT, more than 2^30 chunks in all) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written; glcDedupWorkBytes
+ * returns 0 for such sizes. */
+#define GLC_DEDUP_MAX_LEN ((size_t)1 << 20)
+#define GLC_DEDUP_MAX_COUNT ((size_t)1 << 22)
+size_t glcDedupWorkBytes(size_t count, size_t maxLen);
+CUDPPResult glcDedupMapSegments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
+                                size_t maxLen, unsigned int *d_src, void *d_work, size_t workBytes, void *stream);
+CUDPPResult glcDedupFillSegments(void *d_outBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
+                                 size_t maxLen, const unsigned int *d_src, void *stream);
 
 /* The two passes of the runs mode as batched calls (csrc/zrun.hip; the split is defined in INTEGRATION.md 4b).  Segment i is
  * x = [d_offsets[i], + n) of its base, n = min(d_lengths[i], maxLen), cut into tiles of 256 bytes.  Position p is a run start
@@ -425,6 +449,32 @@ CUDPPResult glcContainerLastChoice(CUDPPHandle plan, unsigned long long out[3]);
  * plan's kernel profile. */
 CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on);
+
+/* The dedup mode of the ENCODER's order-0 codec: on = 1 writes format version 9, whose frames may hold kinds 0, 1, 2 and 6 (the
+ * writer makes 6, 2 or 1).  Every record kind before it looks no further than one block; here a block is cut into chunks of 512
+ * bytes and a chunk that repeats an EARLIER chunk of the same frame -- up to rows * n bytes away -- is elided: the record (kind 6)
+ * holds a chunk mask, one 32-bit source id per elided chunk and the order-0 stream of the kept chunks ("dedup";
+ * the passes are glcDedupMapSegments and glcDedupFillSegments above).  The writer's rule is deterministic: a 64-bit hash per chunk,
+ * the smallest chunk id of the frame with that hash as the candidate, a byte compare, so a source is always a kept chunk and one
+ * copy pass behind the blocks' decoders completes a frame.  A block with E elided chunks becomes kind 6 when 15 * E >= its mask
+ * words (then the record cannot be longer than the block's kind-2 record) and kind 2 otherwise, raw under the record rule either
+ * way.  It is for page- or sector-aligned repeats (snapshots, images, archives that hold a file twice, tied tensors); it finds
+ * nothing in data whose repeats are not 512-aligned, and a frame of zeros costs 128 : 1 of what the sparse mode makes of it (one
+ * ref per chunk).  0 (the default) writes versions 1 to 8 byte for byte as ever.  on = 1 needs the codec
+ * GLC_CONTAINER_CODEC_HUFF0 with the sparse, rANS and auto modes off: on = 1 without that, and any other value, are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; glcPlanSetContainerCodec(plan, GLC_CONTAINER_CODEC_BWT or
+ * _CHOOSE) also switches it off, and the three other order-0 mode setters with on = 1 are refused while it is on.  All six container
+ * entry points honour it, with pipelining on or off and with any filter setting, with the same bytes.  The setting is also the
+ * version the plan speaks: a plan with it on reads versions 1 to 4 and 9; to every other plan, the auto-mode plan included, a
+ * version-9 stream is a stream-header failure, as it always was.  A range read of a kind-6 block b also decodes the blocks
+ * [bwt_index[b], b) of its frame as sources (decoded, not compared with their own crc_raw; the block's own crc_raw covers what was
+ * copied); glcContainerLastRangeStats counts them among the blocks decoded.  The first dedup encode allocates, beside the sparse
+ * mode's rows * n bytes of compaction space, a hash table of 16 bytes a slot with at least two slots per chunk of a frame and 16
+ * bytes per chunk (about 40 MiB for rows 512, n 1 MiB; one set whether pipelining is on or off, since a dedup frame runs wholly on
+ * the plan's stream); the first version-9 decode the compaction space of one decoder chunk and 4
+ * bytes per chunk of the largest frame; both are kept with the plan and freed with it. */
+CUDPPResult glcPlanSetContainerDedup(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -24,7 +24,11 @@ mode off and then on (glcPlanSetContainerSparse, format version 5), without it o
 mode can run; with --ans each round also runs the rANS mode (glcPlanSetContainerAns, format version 7), so that one run interleaves
 the settings off, sparse and ans; with --auto each round also runs the auto mode (glcPlanSetContainerAuto, format version 8),
 interleaved with the others.  --data skew90 is the scattered-skew input (90 % zeros, the rest uniform in 1 .. 15, no filter).
-Every round's rates are reported, with their median and spread (max - min) per setting.
+Every round's rates are reported, with their median and spread (max - min) per setting.  With --dedup each round also runs the dedup
+mode (glcPlanSetContainerDedup, format version 9), interleaved with the others; --data pages / pages_noise are the inputs of
+tests/dedup_inputs.py (4 KiB pages of which about half repeat, compressible or not), made on the host by the generator the Python
+model reads, so that container_bytes can be held against tests/dedup_model.py's size(); with --dedup, --data zipf (data without a
+duplicate) runs through this section too.
 
 --runs (with --data textlike or loglike, generated on the device; --rounds R, at least 1) is the runs section: the BWT codec with its
 runs mode off and then on (glcPlanSetContainerRuns, format version 6), R interleaved rounds of encode and decode timed with device
@@ -39,7 +43,7 @@ device events, ratio / encode / decode per codec and what glcContainerLastChoice
 auto mode's probe and a device-to-device copy.
 
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
-                                [--rounds R] [--sparse] [--ans] [--auto] [--runs | --runs-off-only]"""
+                                [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]"""
 import argparse
 import json
 import os
@@ -49,7 +53,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0}
+DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0}
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -326,7 +330,7 @@ def filter_section(torch, glc, plan, d_in, total, elem, timed, delta=False):
     return res
 
 
-def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse, with_ans=False, with_auto=False):
+def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_sparse, with_ans=False, with_auto=False, with_dedup=False):
     """the order-0 container with its modes off, (with_sparse) the sparse mode on, (with_ans) the rANS mode on and (with_auto) the
     auto mode on, interleaved:
     `rounds` rounds of one encode and one decode per setting after one untimed round, each timed with device events on the plan's
@@ -339,7 +343,8 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
     glc.container_set_shuffle(plan, elem)
     if elem and delta:
         glc.container_set_delta(plan, 1)
-    settings = ["off"] + (["sparse"] if with_sparse else []) + (["ans"] if with_ans else []) + (["auto"] if with_auto else [])
+    settings = ["off"] + (["sparse"] if with_sparse else []) + (["ans"] if with_ans else []) + (["auto"] if with_auto else []) + \
+               (["dedup"] if with_dedup else [])
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
 
     def event_timed(fn):
@@ -353,8 +358,10 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
 
     for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
         for s in settings:
+            if with_dedup:
+                glc.container_set_dedup(plan, 0)               # (the modes exclude each other: off before another goes on)
             if with_auto:
-                glc.container_set_auto(plan, 0)                # (the modes exclude each other: off before another goes on)
+                glc.container_set_auto(plan, 0)
             if with_ans:
                 glc.container_set_ans(plan, 0)
             if with_sparse:
@@ -363,6 +370,8 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
                 glc.container_set_ans(plan, 1 if s == "ans" else 0)
             if with_auto:
                 glc.container_set_auto(plan, 1 if s == "auto" else 0)
+            if with_dedup:
+                glc.container_set_dedup(plan, 1 if s == "dedup" else 0)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -397,6 +406,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse section also runs the order-0 codec's sparse mode (format version 5)")
     ap.add_argument("--ans", action="store_true", help="the sparse section also runs the order-0 codec's rANS mode (format version 7)")
     ap.add_argument("--auto", action="store_true", help="the sparse section also runs the order-0 codec's auto mode (format version 8)")
+    ap.add_argument("--dedup", action="store_true", help="the sparse section also runs the order-0 codec's dedup mode (format version 9)")
     ap.add_argument("--runs", action="store_true", help="text-like data: the runs section, the BWT codec's runs mode off and on (format version 6)")
     ap.add_argument("--runs-off-only", action="store_true", help="the runs section without the mode (what a build without it can run)")
     args = ap.parse_args()
@@ -414,7 +424,10 @@ def main():
     n = MiB
     nblocks = int(args.gib * 1024)
     total = nblocks * n
-    if args.data in ("zipf", "mix"):
+    if args.data in ("pages", "pages_noise"):                  # the model's own generator, on the host
+        import dedup_inputs
+        d_in = torch.from_numpy(np.array(dedup_inputs.make(args.data, total), copy=True)).to(dev)
+    elif args.data in ("zipf", "mix"):
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
         thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
         assert L.glcGenZipfPhilox(d_in.data_ptr(), total, 0, 0x5EED0002, thr.data_ptr(), None) == 1
@@ -455,7 +468,7 @@ def main():
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
         print(json.dumps(res))
         return
-    if args.data != "zipf":
+    if args.data != "zipf" or args.dedup:
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             glc.container_set_codec(plan, args.codec)
@@ -463,7 +476,7 @@ def main():
             if args.rounds:
                 assert args.codec == 1, "the sparse section is the order-0 codec's"
                 res["sparse"] = sparse_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.delta, args.rounds,
-                                               args.sparse, args.ans, args.auto)
+                                               args.sparse, args.ans, args.auto, args.dedup)
             else:
                 res["filter"] = filter_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], timed, args.delta)
         print(json.dumps(res))

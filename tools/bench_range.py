@@ -11,7 +11,10 @@ variant, the median relative to the full decode's, and what glcContainerLastRang
 with the input once before anything is timed.  One JSON line on stdout; the table goes to --md FILE (default
 profiles/range_read.md).
 
-python tools/bench_range.py [--gib 1] [--reps 20] [--warmup 3] [--md FILE]"""
+--dedup runs one container instead: `pages` of tests/dedup_inputs.py (4 KiB pages of which about half repeat frame-wide) through the
+order-0 codec with the dedup mode, where a read inside a kind-6 block also decodes the blocks from its lowest source block on.
+
+python tools/bench_range.py [--gib 1] [--reps 20] [--warmup 3] [--md FILE] [--dedup]"""
 import argparse
 import importlib.util
 import json
@@ -29,9 +32,11 @@ def main():
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--md", default=os.path.join(ROOT, "profiles", "range_read.md"))
+    ap.add_argument("--md", default=None, help="default profiles/range_read.md, with --dedup profiles/range_read_dedup.md")
+    ap.add_argument("--dedup", action="store_true", help="the `pages` container of the dedup mode (format version 9) alone")
     args = ap.parse_args()
     assert args.reps >= 20, "at least 20 timed repetitions"
+    args.md = args.md or os.path.join(ROOT, "profiles", "range_read_dedup.md" if args.dedup else "range_read.md")
     import numpy as np
     import torch
 
@@ -54,6 +59,10 @@ def main():
     inputs = [("bwt", skewed, dict(codec=0, elem=0, delta=False, sparse=False)),
               ("ts64", lambda: torch.from_numpy(np.array(series_datagen.series_bytes("ts64", n), copy=True)).to(dev),
                dict(codec=1, elem=8, delta=True, sparse=True))]
+    if args.dedup:
+        import dedup_inputs
+        inputs = [("pages", lambda: torch.from_numpy(np.array(dedup_inputs.make("pages", n), copy=True)).to(dev),
+                   dict(codec=1, elem=0, delta=False, sparse=False, dedup=True))]
     res = {"bytes": n, "block": BLOCK, "rows": ROWS, "reps": args.reps, "containers": {}}
     rows = ["| container | read | at | median ms | fastest | slowest | time / full decode | frames | blocks | container bytes fetched |",
             "|---|---|---|---|---|---|---|---|---|---|"]
@@ -68,6 +77,8 @@ def main():
                     glc.container_set_delta(plan, 1)
                 if st["sparse"]:
                     glc.container_set_sparse(plan, 1)
+                if st.get("dedup"):
+                    glc.container_set_dedup(plan, 1)
                 c = glc.container_compress(plan, x).clone()
                 full_out = torch.empty(n, dtype=torch.uint8, device=dev)
                 d_len = torch.zeros(1, dtype=torch.int64, device=dev)
