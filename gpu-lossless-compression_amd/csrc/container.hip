@@ -366,8 +366,15 @@ __global__ __launch_bounds__(256) void k_ct_block_segs(unsigned long long *seg_o
     seg_len[b] = blk_len;
 }
 
+// format version 10: the frame's filter into word 3 of the header k_ct_tables has just written, in front of the header's CRC
+__global__ void k_ct_frame_word(uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap, const CtEncState *state, uint32_t word)
+{
+    const unsigned long long F = state->cursor;
+    if (F + CT_FRAME_HDR + 4 * ct_tables(nb, blk_len).words <= cap) reinterpret_cast<uint32_t *>(out + F)[3] = word;
+}
+
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
-                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state)
+                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state, uint32_t frame_word)
 {
     const uint32_t rw = ct_raw_words(blk_len);
     hipLaunchKernelGGL(k_ct_raw_records, dim3(min(8u, (rw + 255) / 256), nb), dim3(256), 0, st, in, blk_len, f.kind,
@@ -376,6 +383,7 @@ hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t 
     hipError_t e = crc32_segments(st, nullptr, f.seg_off, f.seg_len, 2 * nb, f.crc);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_ct_tables, dim3(nb), dim3(256), 0, st, f, nb, blk_len, out, cap, (const CtEncState *)state);
+    if (frame_word) hipLaunchKernelGGL(k_ct_frame_word, dim3(1), dim3(1), 0, st, nb, blk_len, out, cap, (const CtEncState *)state, frame_word);
     e = crc32_segments(st, nullptr, f.seg_off + 2 * nb, f.seg_len + 2 * nb, 2, f.tcrc);
     if (e != hipSuccess) return e;
     if (orig) {                                                // the tables have the shuffled blocks' CRCs: their slots are free again

@@ -5,6 +5,9 @@
 // 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal(), 4 the BWT codec's
 // zero-run form (zrun.hip) where kind4_legal(), 5 the order-0 codec's rANS form (ans.hip) where kind5_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
 // writer's from the plan's settings (the lowest version whose kinds hold every kind they may write), parse_format() accepts a reader's (both read ct_legal()).
+// Under format version 10 (filter-auto) the filter is each FRAME's: the stream's triple is (10, 0, 0), word 3 of a frame header names the
+// frame's filter, and ct_frame_format() gives the format a frame went through -- the writer picks it per frame from the filter probe
+// (filter_probe.hip, filter_rule.h; one host read of seven costs per frame), the readers take it from the frame.
 // Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
 // taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
 // straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
@@ -30,6 +33,7 @@
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 #include "dedup_rule.h"
+#include "filter_rule.h"
 
 #include <fcntl.h>
 #include <memory>
@@ -81,6 +85,14 @@ CUDPPResult fail(CUDPPHandle plan, unsigned long long what, unsigned long long f
 {
     set_error(plan, what, frame, block);
     return what == CT_CAPACITY ? CUDPP_ERROR_ILLEGAL_CONFIGURATION : CUDPP_ERROR_UNKNOWN;
+}
+
+// what glcContainerLastFilters reports: frames per candidate of filter_rule.h, then the frame count; kept with the plan
+struct LastFilters { unsigned long long v[FILTER_CANDS + 1] = {}; };
+void set_filters(CUDPPHandle plan, const LastFilters &f)
+{
+    unsigned long long *c = plan_container_filters(plan);
+    for (uint32_t i = 0; i <= FILTER_CANDS; i++) c[i] = f.v[i];
 }
 
 // what glcContainerLastChoice reports: the last successful compress of the plan, kept with it
@@ -189,6 +201,13 @@ struct Encoder {
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
     unsigned long long *ch_stats = nullptr, *h_stats = nullptr;   // the CHOOSE codec's probe rows [rows][4]: device, pinned
     unsigned long long choice[3] = {0, 0, 0};                 // blocks given to the BWT codec, to the order-0 codec; frames
+    // filter-auto (format version 10): the filter probe's rows and costs of one frame, the frame as its one segment {offset, length},
+    // the costs on the host (pinned), and the frames each candidate got (the plan's own filter's candidate with the setting off)
+    bool filter_auto = false;
+    uint32_t own_pick = 0;                                    // the candidate every frame counts for with the setting off
+    uint32_t *fp_planes = nullptr;
+    unsigned long long *fp_costs = nullptr, *fp_seg = nullptr, *h_costs = nullptr;
+    LastFilters filters;
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
     void carve_runs(Carver &c)
@@ -295,6 +314,11 @@ struct Encoder {
             c.round(256);
         }
         if (codec == CT_CODEC_CHOOSE) ch_stats = c.take<unsigned long long>(CHOOSE_STATS * R);
+        if (filter_auto) {
+            fp_planes = c.take<uint32_t>(FILTER_ROWS * 256);
+            fp_costs = c.take<unsigned long long>(FILTER_CANDS + 1);
+            fp_seg = c.take<unsigned long long>(2);
+        }
     }
 
     hipError_t init()
@@ -303,27 +327,48 @@ struct Encoder {
         fmt = format_of(s);
         codec = s.codec;
         mode = s.mode;
+        filter_auto = s.filter_auto;
+        for (uint32_t i = 0; i < FILTER_CANDS; i++) {             // the candidate that is the plan's own filter
+            const FilterCand c = filter_cand(i);
+            if (c.elem == (fmt.elem ? fmt.elem : 1u) && (c.delta != 0) == fmt.delta()) own_pick = i;
+        }
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
         if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
         if (codec == CT_CODEC_CHOOSE) CT_HIP(hipHostMalloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows, hipHostMallocDefault));
-        if (fmt.filtered()) {
+        if (filter_auto) CT_HIP(hipHostMalloc((void **)&h_costs, 8 * FILTER_CANDS, hipHostMallocDefault));
+        if (fmt.filtered() || filter_auto) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
             if (nstage == 1) stage[1] = stage[0];
         }
-        return carve_on(
+        CT_HIP(carve_on(
             [&](size_t bytes, void **base) {
                 const hipError_t e = hipMalloc(&mem, bytes);
                 if (e != hipSuccess) mem = nullptr;
                 *base = mem;
                 return e;
             },
-            [&](Carver &c) { carve(c); });
+            [&](Carver &c) { carve(c); }));
+        return filter_auto ? hipMemsetAsync(fp_seg, 0, 8, P.st) : hipSuccess;
     }
     ~Encoder()
     {
         if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); }
         if (h_stats) (void)hipHostFree(h_stats);
+        if (h_costs) (void)hipHostFree(h_costs);
+    }
+
+    // filter-auto: the probe of the frame where it lies, its seven costs read back with one wait (as the CHOOSE codec reads its
+    // stats), and the rule on the host.  A frame beyond the probe's 2^31 bytes is judged by its first 2^31.
+    CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick)
+    {
+        CT_TRY(ct_put_u64(P.st, fp_seg + 1, frame_len));     // (fp_seg[0], the segment's offset, is 0 from init() on)
+        CT_TRY(filter_probe_segments(P.st, d_in, fp_seg, fp_seg + 1, 1, (uint32_t)std::min<unsigned long long>(frame_len, GLC_FILTER_PROBE_MAX_LEN),
+                                     fp_planes, fp_costs));
+        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FILTER_CANDS, hipMemcpyDeviceToHost, P.st));
+        CT_TRY(hipStreamSynchronize(P.st));
+        *pick = filter_pick(h_costs);
+        return CUDPP_SUCCESS;
     }
 
     // one frame of nb blocks of blk_len from d_in, written at the device cursor into out (cap bytes).  With a filter the frame
@@ -336,15 +381,26 @@ struct Encoder {
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
         const CtEncFrame &f = fr[P.parity];
         const uint8_t *orig = nullptr;
-        if (fmt.filtered()) {
+        CtFormat ff = fmt;                                    // the format whose filter this frame goes through
+        uint32_t pick = own_pick;
+        if (filter_auto) {
+            const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick);
+            if (r != CUDPP_SUCCESS) return r;
+            const FilterCand c = filter_cand(pick);
+            ff.elem = c.elem > 1 ? c.elem : 0;
+            ff.flags = c.delta ? CT_FLAG_DELTA : 0;
+        }
+        filters.v[pick]++;
+        filters.v[FILTER_CANDS]++;
+        if (ff.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
-            CT_TRY(filter_device(P.st, fmt, d_in, stage[P.parity], (unsigned long long)nb * blk_len, false));
+            CT_TRY(filter_device(P.st, ff, d_in, stage[P.parity], (unsigned long long)nb * blk_len, false));
             orig = d_in;
             d_in = stage[P.parity];
         }
         if (mode == CT_MODE_RUNS) return frame_runs(f, d_in, orig, nb, blk_len, out, cap);
         if (by == CT_CODEC_HUFF0) {
-            const Frame0 F{f, d_in, orig, nb, blk_len, out, cap};
+            const Frame0 F{f, d_in, orig, nb, blk_len, out, cap, filter_auto ? ct_frame_word(ff) : 0u};
             return mode == CT_MODE_SPARSE ? frame_sparse(F) : mode == CT_MODE_ANS ? frame_ans(F) : mode == CT_MODE_AUTO ? frame_auto(F) :
                    mode == CT_MODE_DEDUP ? frame_dedup(F) : frame_plain(F);
         }
@@ -364,6 +420,7 @@ struct Encoder {
     // functions below are the modes: each says its two parts and what they share.
     struct Frame0 {
         const CtEncFrame &f; const uint8_t *d_in, *orig; uint32_t nb, blk_len; uint8_t *out; unsigned long long cap;
+        uint32_t word;                                        // the frame header's word 3: the frame's filter under version 10, else 0
     };
     template <class Sizes, class Place>
     CUDPPResult frame_order0(const Frame0 &F, Sizes sizes, Place place)
@@ -378,7 +435,7 @@ struct Encoder {
         CT_TRY(huff_block_offsets(P.st, F.f.size, F.nb, F.f.boff, F.f.start, (size_t)cap_words, status));
         CT_TRY(place(out_words, cap_words));
         plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, F.f, F.d_in, F.orig, F.nb, F.blk_len, F.out, F.cap, state));
+        CT_TRY(ct_enc_after_pack(P.st, F.f, F.d_in, F.orig, F.nb, F.blk_len, F.out, F.cap, state, F.word));
         plan_stage_mark(P.h, 3);
         return CUDPP_SUCCESS;
     }
@@ -705,12 +762,14 @@ struct Decoder {
     // checked there; *staged is the staging and final_out is not touched (the inverse filter of a range is the caller's).
     // In a version-9 frame a wanted kind-6 block b needs the blocks [bwt_index[b], b) as sources (dedup_rule.h): they are decoded
     // and joined as well, but neither filled nor compared with their crc_raw; *decoded counts them with the wanted ones.
-    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint8_t *final_out, uint32_t fi,
+    // word: the frame header's word 3, which under version 10 names the frame's filter (ct_frame_format)
+    CUDPPResult frame(const uint8_t *fr, uint32_t nb, uint32_t blk_len, unsigned long long pw, uint32_t word, uint8_t *final_out, uint32_t fi,
                       const uint8_t *need = nullptr, uint8_t **staged = nullptr, unsigned long long *decoded = nullptr)
     {
         CT_TRY(reserve(nb));
+        const CtFormat ff = ct_frame_format(fmt, word);
         uint8_t *out = final_out;
-        if (fmt.filtered() || need) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
+        if (ff.filtered() || need) CT_TRY(plan_stage(P.h, 0, (size_t)nb * blk_len, &out));
         if (staged) *staged = out;
         std::vector<uint8_t> need9;                               // version 9: need[] with the source-only blocks marked 2
         auto want = [&](uint32_t b) { return !need || need[b] != 0; };
@@ -847,9 +906,9 @@ struct Decoder {
             CT_TRY(runs_checked([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
             return CUDPP_SUCCESS;
         }
-        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !fmt.filtered()));
-        if (fmt.filtered()) {
-            CT_TRY(filter_device(P.st, fmt, out, final_out, (unsigned long long)nb * blk_len, true));
+        CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !ff.filtered()));
+        if (ff.filtered()) {
+            CT_TRY(filter_device(P.st, ff, out, final_out, (unsigned long long)nb * blk_len, true));
             CT_TRY(ct_dec_fold(P.st, f, final_out, nb, blk_len, state));
         }
         return CUDPP_SUCCESS;
@@ -995,6 +1054,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     total += CT_TRAILER;
     if (outLen) *outLen = total;
     set_choice(plan, E.choice);
+    set_filters(plan, E.filters);
     set_error(plan, CT_OK);
     return CUDPP_SUCCESS;
 }
@@ -1045,7 +1105,7 @@ CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned
             const uint8_t *fr = nullptr;
             uint8_t *out = nullptr;
             if ((r = feed.frame(fh, F.pos, frame_bytes(F.nb, F.bl, F.pw), F.out_off, ob, fi, &fr, &out)) != CUDPP_SUCCESS) return false;
-            if ((r = D.frame(fr, F.nb, F.bl, F.pw, out, fi)) != CUDPP_SUCCESS) return false;
+            if ((r = D.frame(fr, F.nb, F.bl, F.pw, F.filter, out, fi)) != CUDPP_SUCCESS) return false;
             return (r = feed.taken(ob)) == CUDPP_SUCCESS;
         },
         [&](const uint32_t *tr, uint32_t) { return (r = D.end(tr[2])) == CUDPP_SUCCESS; });
@@ -1341,24 +1401,26 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         if (r == CUDPP_ERROR_UNKNOWN) return fail(plan, CT_TRUNCATED, fi);
         if (r != CUDPP_SUCCESS) return r;
         // the header's range check, on the bytes that are there now: it has to say what the index says
-        if (!check_frame_header(fh, ix->block_len, ix->total - F.out_off, &pw) || fh[1] != F.nb || fh[2] != F.bl || pw != F.pw)
+        if (!check_frame_header(fh, ix->fmt, ix->block_len, ix->total - F.out_off, &pw) || fh[1] != F.nb || fh[2] != F.bl || pw != F.pw ||
+            fh[3] != F.filter)
             return fail(plan, CT_FRAME_TABLE, fi);
+        const CtFormat ff = ct_frame_format(ix->fmt, F.filter);   // the frame's own filter under version 10, else the stream's
         unsigned long long i0 = 0, i1 = 0;
-        const std::vector<uint8_t> need = needed_blocks(ix->fmt, F.nb, F.bl, a, b, &i0, &i1);
+        const std::vector<uint8_t> need = needed_blocks(ff, F.nb, F.bl, a, b, &i0, &i1);
         uint8_t *stage = nullptr;
-        if ((r = D.frame(fr, F.nb, F.bl, F.pw, nullptr, (uint32_t)fi, need.data(), &stage, &stats.v[1])) != CUDPP_SUCCESS) return r;
+        if ((r = D.frame(fr, F.nb, F.bl, F.pw, F.filter, nullptr, (uint32_t)fi, need.data(), &stage, &stats.v[1])) != CUDPP_SUCCESS) return r;
         stats.v[0] += 1;
         stats.v[2] += fb;
         const unsigned long long at = F.out_off - offset;       // (+ a frame byte = its place in the range; never negative there)
-        if (!ix->fmt.filtered()) {
+        if (!ff.filtered()) {
             if ((r = io.deliver(stage + a, b - a, at + a)) != CUDPP_SUCCESS) return r;
             continue;
         }
-        const unsigned long long e = ix->fmt.elem, q = fbytes / e;
+        const unsigned long long e = ff.elem, q = fbytes / e;
         if (i0 < i1) {                                          // elements [i0, i1) into the second staging, [a, min(b, q e)) out of them
             uint8_t *el = nullptr;
             CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
-            CT_TRY((ix->fmt.delta() ? undelta_unshuffle_range_device : unshuffle_range_device)(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
+            CT_TRY((ff.delta() ? undelta_unshuffle_range_device : unshuffle_range_device)(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
             const unsigned long long top = std::min(b, q * e);
             if ((r = io.deliver(el + (a - i0 * e), top - a, at + a)) != CUDPP_SUCCESS) return r;
         }
@@ -1531,6 +1593,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(hipStreamSynchronize(E.P.st));
     if (total > cap) return fail(plan, CT_CAPACITY);
     set_choice(plan, E.choice);
+    set_filters(plan, E.filters);
     set_error(plan, CT_OK);
     return CUDPP_SUCCESS;
 }
@@ -1839,6 +1902,46 @@ CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long lon
     if (!d_inBase || !d_offsets || !d_lengths || !d_stats || (reinterpret_cast<uintptr_t>(d_stats) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CT_TRY(bigram_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
                                  (uint32_t)count, (uint32_t)maxLen, d_stats));
+    return CUDPP_SUCCESS;
+}
+
+// the filter probe: a bad argument is refused before anything is enqueued
+CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, unsigned int *d_planes, unsigned long long *d_costs, void *stream)
+{
+    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_FILTER_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_inBase || !d_offsets || !d_lengths || !d_planes || !d_costs || (reinterpret_cast<uintptr_t>(d_planes) & 15) ||
+        (reinterpret_cast<uintptr_t>(d_costs) & 7) || static_cast<void *>(d_planes) == static_cast<void *>(d_costs))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(filter_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
+                                 (uint32_t)count, (uint32_t)maxLen, d_planes, d_costs));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8])
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const unsigned long long *c = plan_container_filters(plan);
+    for (uint32_t i = 0; i <= FILTER_CANDS; i++) out[i] = c[i];
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    return plan_container_settings(plan).set_filter_auto(on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+}
+
+CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *on = plan_container_settings(plan).filter_auto ? 1u : 0u;
     return CUDPP_SUCCESS;
 }
 

@@ -203,14 +203,18 @@ constexpr uint32_t CT_VERSION_RUNS = 6;                      // 6: kinds 0, 1, 2
 constexpr uint32_t CT_VERSION_ANS = 7;                       // 7: kinds 0, 1, 2 and 5 are legal (not 3, not 4); the same triples as version 5
 constexpr uint32_t CT_VERSION_AUTO = 8;                      // 8: kinds 0, 1, 2, 3 and 5 are legal (not 4); the same triples as version 5
 constexpr uint32_t CT_VERSION_DEDUP = 9;                     // 9: kinds 0, 1, 2 and 6 are legal (not 3, 4, 5); the same triples as version 5
+// 10: version 8's kinds; the stream header's triple is (10, 0, 0) and every FRAME header's word 3 names that frame's filter,
+// elem | flags << 16 (elem 0, 2, 4 or 8; flags 0 or the delta flag, which needs an elem)
+constexpr uint32_t CT_VERSION_FILTER = 10;
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
-// its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9
-constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16;
+// its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
+// its filter-auto setting version 10 (it is only ever on with the auto mode, so that mode's bits come with it)
+constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_DEDUP + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47};
-    return version <= CT_VERSION_DEDUP ? K[version] : 0u;
+    constexpr uint32_t K[CT_VERSION_FILTER + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F};
+    return version <= CT_VERSION_FILTER ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
@@ -230,14 +234,30 @@ struct CtFormat {
     {
         return version == CT_VERSION_SPARSE ? CT_READS_SPARSE : version == CT_VERSION_RUNS ? CT_READS_RUNS :
                version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
-               version == CT_VERSION_DEDUP ? CT_READS_DEDUP : 0u;
+               version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER : 0u;
     }
 };
+// a frame header's word 3.  Versions 1 to 9 keep it 0; under version 10 it is the frame's filter.  ct_frame_word_legal() is the
+// header's range check on it, ct_frame_format() the format whose filter a frame with a legal word went through: the stream's
+// below version 10, the word's under it
+__host__ __device__ inline uint32_t ct_frame_word(const CtFormat &f) { return f.elem | (f.flags << 16); }
+__host__ __device__ inline bool ct_frame_word_legal(const CtFormat &stream, uint32_t word)
+{
+    if (stream.version != CT_VERSION_FILTER) return word == 0;
+    const uint32_t elem = word & 0xFFFFu, flags = word >> 16;
+    return elem == 0 ? flags == 0 : (elem == 2 || elem == 4 || elem == 8) && flags <= CT_FLAG_DELTA;
+}
+__host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint32_t word)
+{
+    CtFormat f = stream;
+    if (stream.version == CT_VERSION_FILTER) { f.elem = word & 0xFFFFu; f.flags = word >> 16; }
+    return f;
+}
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
 constexpr uint32_t CT_NO_FILTER = 1u << 0, CT_ELEMS = 1u << 2 | 1u << 4 | 1u << 8;
 struct CtLegal { uint32_t version, flags, elems; };
-constexpr uint32_t CT_NLEGAL = 14;
+constexpr uint32_t CT_NLEGAL = 15;
 __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 {
     constexpr CtLegal L[CT_NLEGAL] = {
@@ -247,7 +267,7 @@ __host__ __device__ inline CtLegal ct_legal(uint32_t i)
         {CT_VERSION_RUNS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_ANS, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_ANS, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_AUTO, 0, CT_NO_FILTER | CT_ELEMS},
         {CT_VERSION_AUTO, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_DEDUP, 0, CT_NO_FILTER | CT_ELEMS},
-        {CT_VERSION_DEDUP, CT_FLAG_DELTA, CT_ELEMS}};
+        {CT_VERSION_DEDUP, CT_FLAG_DELTA, CT_ELEMS}, {CT_VERSION_FILTER, 0, CT_NO_FILTER}};
     return L[i];
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
@@ -334,11 +354,12 @@ __host__ __device__ inline bool check_stream_header(const CrcTables &C, const ui
 }
 
 // the range checks on a frame header, `left` output bytes still to come; false = refused
-__host__ __device__ inline bool check_frame_header(const uint32_t h[8], uint32_t block_len, unsigned long long left, unsigned long long *pw)
+__host__ __device__ inline bool check_frame_header(const uint32_t h[8], const CtFormat &fmt, uint32_t block_len, unsigned long long left,
+                                                   unsigned long long *pw)
 {
     const uint32_t nb = h[1], bl = h[2];
     *pw = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
-    if (h[0] != CT_MAGIC_FRAME || h[3] != 0 || h[7] != 0 || nb == 0 || bl == 0 || bl > block_len) return false;
+    if (h[0] != CT_MAGIC_FRAME || !ct_frame_word_legal(fmt, h[3]) || h[7] != 0 || nb == 0 || bl == 0 || bl > block_len) return false;
     if ((nb > 1 && bl != block_len) || (unsigned long long)nb * bl > left) return false;
     return *pw <= (unsigned long long)nb * ct_raw_words(bl);
 }
@@ -351,6 +372,7 @@ __host__ __device__ inline bool check_trailer(const CrcTables &C, const uint32_t
 struct CtFrameRef {                                        // a frame whose header has passed the walk's checks
     unsigned long long pos, out_off, pw;                   // where it starts in the stream; the output offset of its first byte
     uint32_t nb, bl;
+    uint32_t filter, pad;                                  // its header's word 3: 0 below version 10, the frame's filter under it
 };
 // what a walk ends with beyond CtWhat: the plan's n is below a frame's blk_len; a callback stopped it (the reason is the caller's)
 constexpr uint32_t CT_WALK_CONFIG = 0x100, CT_WALK_STOPPED = 0x101;
@@ -378,8 +400,8 @@ __host__ __device__ inline CtWalkEnd ct_walk(const CrcTables &C, unsigned long l
         if (pos + CT_FRAME_HDR + CT_TRAILER > len) return {CT_TRUNCATED, fi};
         uint32_t fh[8];
         if (!fetch(fh, pos, CT_FRAME_HDR, (unsigned long long)fi)) return {CT_WALK_STOPPED, fi};
-        CtFrameRef ref{pos, done, 0, fh[1], fh[2]};
-        if (!check_frame_header(fh, block_len, total - done, &ref.pw)) return {CT_FRAME_TABLE, fi};
+        CtFrameRef ref{pos, done, 0, fh[1], fh[2], fh[3], 0};
+        if (!check_frame_header(fh, fmt, block_len, total - done, &ref.pw)) return {CT_FRAME_TABLE, fi};
         if (ref.bl > plan_n) return {CT_WALK_CONFIG, fi};
         const unsigned long long fb = frame_bytes(ref.nb, ref.bl, ref.pw);
         if (pos + fb + CT_TRAILER > len) return {CT_TRUNCATED, fi};
@@ -400,7 +422,7 @@ struct CtIndexHead {
     unsigned long long frame;
     uint32_t hdr[8], trailer[4];
 };
-constexpr uint32_t CT_INDEX_FIRST = 1022;                  // entries the one readback brings along with the head (32 KiB in all)
+constexpr uint32_t CT_INDEX_FIRST = 1022;                  // entries the one readback brings along with the head (40 KiB in all)
 // the walk over a container in device memory (8-byte aligned), one launch: head and up to `cap` entries into `scratch`
 hipError_t ct_index_device(hipStream_t st, const uint8_t *in, unsigned long long len, uint32_t plan_n, uint32_t reader,
                            CtIndexHead *head, CtFrameRef *entries, unsigned long long cap);
@@ -427,9 +449,12 @@ void plan_join(CUDPPHandle plan);                          // the plan's stream 
 inline bool shuffle_elem_ok(uint32_t elem) { return elem <= 8 && (CT_ELEMS >> elem & 1); }
 struct CtSettings {
     uint32_t shuffle = 0; bool delta = false; uint32_t codec = CT_CODEC_BWT; CtMode mode = CT_MODE_PLAIN;
+    // filter-auto: the writer picks every frame's filter itself (filter_rule.h) and writes version 10.  Only ever on with the order-0
+    // codec, the auto mode on and the shuffle off; whatever ends one of the three switches it off
+    bool filter_auto = false;
     bool set_shuffle(uint32_t elem)
     {
-        if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE)) return false;
+        if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE || filter_auto)) return false;
         shuffle = elem > 1 ? elem : 0;
         if (elem <= 1) delta = false;                         // (no delta without the shuffle)
         return true;
@@ -445,6 +470,7 @@ struct CtSettings {
         if (c != CT_CODEC_BWT && c != CT_CODEC_HUFF0 && (c != CT_CODEC_CHOOSE || shuffle)) return false;
         codec = c;
         if (!ct_mode_fits(mode, codec)) mode = CT_MODE_PLAIN;  // (no mode without its codec)
+        if (mode != CT_MODE_AUTO) filter_auto = false;
         return true;
     }
     // on: refused when the mode does not fit the codec or another mode is on (the modes exclude each other); off: clears the
@@ -454,13 +480,21 @@ struct CtSettings {
         if (on > 1 || (on && (!ct_mode_fits(m, codec) || (mode != CT_MODE_PLAIN && mode != m)))) return false;
         if (on) mode = m;
         else if (mode == m) mode = CT_MODE_PLAIN;
+        if (mode != CT_MODE_AUTO) filter_auto = false;
+        return true;
+    }
+    bool set_filter_auto(uint32_t on)
+    {
+        if (on > 1 || (on && (codec != CT_CODEC_HUFF0 || mode != CT_MODE_AUTO || shuffle))) return false;
+        filter_auto = on != 0;
         return true;
     }
     // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
-               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS : mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) :
+               mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
     uint32_t kinds() const
@@ -476,6 +510,7 @@ struct CtSettings {
 inline CtFormat format_of(const CtSettings &s)
 {
     CtFormat f;
+    if (s.filter_auto) { f.version = CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
     f.elem = s.shuffle;
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
@@ -487,6 +522,8 @@ inline CtFormat format_of(const CtSettings &s)
 CtSettings &plan_container_settings(CUDPPHandle plan);
 // {blocks given to the BWT codec, blocks given to the order-0 codec, frames} of the plan's last successful container compress
 unsigned long long *plan_container_choice(CUDPPHandle plan);
+// frames per candidate of filter_rule.h (seven), then all frames, of the plan's last successful container compress
+unsigned long long *plan_container_filters(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
 bool plan_pipelined(CUDPPHandle plan);
@@ -621,6 +658,12 @@ hipError_t probe_segments(hipStream_t st, const uint8_t *data, const unsigned lo
 // is written whole.  Everything only enqueues on `st`.
 hipError_t bigram_probe_segments(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                                  uint32_t count, uint32_t max_len, unsigned long long *stats);
+// the filter probe (filter_probe.hip, filter_rule.h): row i of planes = the 22 histograms of the first L - L % 8 bytes of segment i
+// (L = min(data_len[i], max_len), max_len <= 2^31), row i of costs = the seven candidates' costs.  planes is 16-byte aligned and
+// need not be zeroed.  Everything only enqueues on `st`.
+hipError_t filter_probe_segments(hipStream_t st, const uint8_t *data, const unsigned long long *data_off,
+                                 const unsigned long long *data_len, uint32_t count, uint32_t max_len, uint32_t *planes,
+                                 unsigned long long *costs);
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
 // block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
 // read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the
@@ -633,8 +676,9 @@ hipError_t ct_enc_auto_choose(hipStream_t st, const CtEncFrame &f, const CtEncHu
                               const CtEncAuto &au, uint32_t nb, uint32_t blk_len);
 // in: the frame as the blocks are cut from it (the shuffled frame with the filter on); orig: the frame's input bytes where
 // they differ from `in` (else null) -- the stream's crc_all is theirs
+// frame_word: the frame header's word 3 (0 below version 10)
 hipError_t ct_enc_after_pack(hipStream_t st, const CtEncFrame &f, const uint8_t *in, const uint8_t *orig, uint32_t nb,
-                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state);
+                             uint32_t blk_len, uint8_t *out, unsigned long long cap, CtEncState *state, uint32_t frame_word = 0);
 hipError_t ct_enc_trailer(hipStream_t st, uint8_t *out, unsigned long long cap, CtEncState *state, unsigned long long *d_len);
 
 struct CtDecFrame {                                        // device scratch of one frame's checks

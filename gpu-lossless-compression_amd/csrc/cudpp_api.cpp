@@ -127,6 +127,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse / Runs / Ans) and the filter's frame staging both directions share
     CtSettings ct;
     unsigned long long ct_choice[3] = {0, 0, 0};                // glcContainerLastChoice: the last successful container compress
+    unsigned long long ct_filters[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // glcContainerLastFilters: frames per filter candidate, then all frames
     GrowBuf ct_stage[2];
     GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse and rANS modes' and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
     SaScratch *sorter() override { return &sa; }
@@ -831,6 +832,7 @@ void plan_join(CUDPPHandle planHandle) { plan_from<CompressPlan>(planHandle)->jo
 bool plan_pipelined(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->pipelined; }
 CtSettings &plan_container_settings(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct; }
 unsigned long long *plan_container_choice(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_choice; }
+unsigned long long *plan_container_filters(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_filters; }
 
 hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {

@@ -660,7 +660,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcAnsEncodeSegments", "glcAnsDecodeSegments", "glcAnsSegmentsWorkBytes", "glcAnsBoundWords",
                      "glcPlanSetContainerAns", "glcPlanGetContainerAns",
                      "glcProbeSegments", "glcPlanSetContainerAuto", "glcPlanGetContainerAuto",
-                     "glcBigramProbeSegments", "glcContainerLastChoice",
+                     "glcBigramProbeSegments", "glcContainerLastChoice", "glcFilterProbeSegments",
+                     "glcPlanSetContainerFilterAuto", "glcPlanGetContainerFilterAuto", "glcContainerLastFilters",
                      "glcDedupWorkBytes", "glcDedupMapSegments", "glcDedupFillSegments", "glcPlanSetContainerDedup", "glcPlanGetContainerDedup",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
@@ -731,6 +732,10 @@ def _ct():
         L.glcProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcBigramProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.glcContainerLastChoice.argtypes = [sz, ullp]
+        L.glcFilterProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.glcPlanSetContainerFilterAuto.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerFilterAuto.argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcContainerLastFilters.argtypes = [sz, ullp]
         L.glcPlanSetContainerDedup.argtypes = [sz, C.c_uint]
         L.glcPlanGetContainerDedup.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcDedupWorkBytes.argtypes = [sz, sz]
@@ -905,6 +910,27 @@ def container_get_auto(plan):
     return int(d.value)
 
 
+def container_set_filter_auto(plan, on):
+    """filter-auto of the plan's container ENCODER (format version 10: every frame's filter picked from the filter probe and
+    named in its frame header): True / 1 needs the order-0 codec, the auto mode on and the plan's shuffle off; while it is on
+    container_set_shuffle(plan, 2, 4 or 8) is refused, and container_set_auto(plan, 0) or a codec change switch it off.  It is also
+    the version the plan reads: on, versions 1 to 5, 7, 8 and 10; off, a version-10 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerFilterAuto", _ct().glcPlanSetContainerFilterAuto(plan.handle, int(on)))
+
+
+def container_get_filter_auto(plan):
+    d = C.c_uint(0)
+    _chk("glcPlanGetContainerFilterAuto", _ct().glcPlanGetContainerFilterAuto(plan.handle, C.byref(d)))
+    return int(d.value)
+
+
+def container_last_filters(plan):
+    """(frames per candidate of FILTER_CANDS ..., frames) of the plan's last successful container compress: eight integers"""
+    a = (C.c_ulonglong * 8)()
+    _chk("glcContainerLastFilters", _ct().glcContainerLastFilters(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
 def container_set_dedup(plan, on):
     """the dedup mode of the plan's container ENCODER (format version 9: 512-byte chunks that repeat an earlier chunk of their frame
     are elided, kind 6): True / 1 needs the order-0 codec and the sparse, rANS and auto modes off; a codec change also switches it
@@ -955,6 +981,32 @@ def bigram_probe_segments(d_in, offsets, lengths, max_len=None, stats=None, stre
                                                                  stats.data_ptr(), stream))
     torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
     return stats[:n]
+
+
+FILTER_PROBE_ROWS, FILTER_CANDIDATES, FILTER_PROBE_MAX_LEN = 22, 7, 1 << 31
+FILTER_CANDS = ((1, 0), (2, 0), (2, 1), (4, 0), (4, 1), (8, 0), (8, 1))     # (elem, delta) in the rule's order; (1, 0): no filter
+
+
+def filter_probe_segments(d_in, offsets, lengths, max_len=None, planes=None, costs=None, stream=None):
+    """the filter probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (planes,
+    costs) -- an int32 tensor [count, 22, 256] of the histograms A_0..7, D_2, D_4 and D_8 of each segment's first L - L % 8 bytes,
+    and an int64 tensor [count, 7] of the candidates' costs in the order of FILTER_CANDS (csrc/filter_rule.h).  planes / costs:
+    tensors to write into (they need not be zeroed)."""
+    import torch
+    dev = d_in.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    n = off.numel()
+    max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
+    planes = torch.empty((max(1, n), FILTER_PROBE_ROWS, 256), dtype=torch.int32, device=dev) if planes is None else planes
+    costs = torch.empty((max(1, n), FILTER_CANDIDATES), dtype=torch.int64, device=dev) if costs is None else costs
+    assert planes.is_contiguous() and costs.is_contiguous() and costs.dtype == torch.int64
+    assert planes.numel() >= FILTER_PROBE_ROWS * 256 * n and costs.numel() >= FILTER_CANDIDATES * n
+    _chk("glcFilterProbeSegments", _ct().glcFilterProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
+                                                                 planes.data_ptr(), costs.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return planes[:n], costs[:n]
 
 
 def ans_bound_words(length):

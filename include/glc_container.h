@@ -87,6 +87,18 @@
  * from it by no more than two runs of one build do.  The probe alone: 4864 GB/s on zeros, 3356 on scattered skew, 4038 on noise, where
  * the call that holds the histogram pass alone moves 4081, 3070 and 3724; a device-to-device copy 2584.
  *
+ * Callers who do not know their data's type either: filter-auto, off by default.  The filter above is one per stream and has to be
+ * known in advance, and a wrong guess costs up to 5 : 1.  With glcPlanSetContainerFilterAuto on (it needs the order-0 codec and the
+ * auto mode) one probe pass over every frame (glcFilterProbeSegments) counts the byte planes of all seven candidates -- no filter,
+ * the shuffle over 2, 4 or 8 bytes, each with or without the delta -- and the writer gives the frame the cheapest by a margin and
+ * names it in the frame header.  The stream is format version 10; nothing else changes.  Measured on one MI355X on 1 GiB of
+ * device-generated data in 1 MiB blocks, rows 512 (profiles/filter_auto.md; ratio / encode / decode GB/s, medians of 5 interleaved
+ * rounds): int64 timestamps 7.008 / 209 / 295 against 7.008 / 395 / 294 with delta + shuffle 8 set by hand and 1.548 / 435 / 113
+ * without a filter; uint32 counters 10.218 / 209 / 304 against 10.218 / 399 / 303; float32 1.198 / 199 / 118 against 1.198 / 362 / 118;
+ * text-like 1.884 / 221 / 127 against 1.884 / 441 / 127.  The probe alone moves 506 to 518 GB/s (1475 on zeros; a device-to-device
+ * copy 2544 to 2590).  With the setting off the bytes equal the parent commit's and the rates differ from it by no more than two runs
+ * of one build do.
+ *
  * Plans are CUDPP_COMPRESS plans (include/cudpp.h).  Work is queued on the plan's stream, with or without
  * glcPlanSetPipelining; every call below returns with its outputs complete.  Results: CUDPP_SUCCESS,
  * CUDPP_ERROR_ILLEGAL_CONFIGURATION (bad arguments, a capacity too small -- nothing is ever written past `cap` --, a plan
@@ -422,6 +434,29 @@ CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_o
 CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                                    size_t count, size_t maxLen, unsigned long long *d_stats, void *stream);
 
+/* The filter probe as a batched call (csrc/filter_probe.hip, csrc/filter_rule.h): which byte-plane filter -- element size 2, 4 or 8,
+ * with or without the delta of glcDeltaShuffleDevice, or none -- a segment wants, from one read of it.  The segments are those of
+ * glcProbeSegments, but up to GLC_FILTER_PROBE_MAX_LEN bytes each; with L = min(d_lengths[i], maxLen) only the first P = L - L % 8
+ * bytes x[0 .. P) of segment i are counted.  Row i of d_planes is 22 histograms of 256 words (GLC_FILTER_PROBE_ROWS):
+ *   rows 0..7    A_k[v]: the positions p < P with p % 8 == k and x[p] == v.  Plane j of the plain shuffle over elements of e bytes
+ *                is the sum of the A_k with k = j modulo e; the unfiltered bytes are the sum of all eight;
+ *   rows 8..9    D_2[j][v], rows 10..13 D_4[j][v], rows 14..21 D_8[j][v]: the elements i < P / e whose delta d_e[i] has byte j equal to
+ *                v, with d_e[i] = x_e[i] where i % 2048 == 0 and x_e[i] - x_e[i-1] modulo 2^(8 e) elsewhere, elements little-endian and
+ *                counted from the segment's start: the planes glcDeltaShuffleDevice makes of these bytes.
+ * Row i of d_costs is seven 64-bit words, the costs of the candidates (elem, delta) = (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1) in
+ * this order, (1,0) being no filter: the sum over the candidate's planes of sum_s H[s] * cost(q(s)) with H the plane's counts, N their
+ * sum, q(s) = clamp(floor(H[s] * 4096 / N), 1, 4096) and cost(q) = 12 - log2 q in 1/256 bit rounded up (the table of the auto mode,
+ * csrc/auto_rule.h) -- exact integers below 2^43.  The rule that reads them (csrc/filter_rule.h) walks the candidates in order from
+ * pick = 0 and lets candidate i replace the pick exactly when 33 * cost[i] < 32 * cost[pick]: more planes never raise an empirical
+ * entropy, so a later candidate has to win by a margin.  The rows need not be zeroed by the caller.  The call only enqueues on
+ * `stream`.  A bad argument (a null pointer with count > 0, d_planes not 16-byte or d_costs not 8-byte aligned, the two equal, a
+ * maxLen or count too large) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_FILTER_PROBE_MAX_LEN ((size_t)1 << 31)
+#define GLC_FILTER_PROBE_ROWS 22
+#define GLC_FILTER_CANDIDATES 7
+CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                   size_t count, size_t maxLen, unsigned int *d_planes, unsigned long long *d_costs, void *stream);
+
 /* {blocks given to the BWT codec, blocks given to the order-0 codec, frames written} of the plan's last successful container
  * compress, whatever its codec; with GLC_CONTAINER_CODEC_CHOOSE the first two are the rule's choices, counted before the record
  * rule stores a block raw.  {0, 0, 0} before the first. */
@@ -475,6 +510,35 @@ CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on);
  * bytes per chunk of the largest frame; both are kept with the plan and freed with it. */
 CUDPPResult glcPlanSetContainerDedup(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on);
+
+/* Filter-auto: the ENCODER picks every frame's filter itself.  on = 1 writes format version 10: the stream header's triple is
+ * (10, 0, 0), the record kinds are version 8's (0, 1, 2, 3 and 5), and word 3 of every FRAME header (byte 12; 0 in versions 1 to 9)
+ * names that frame's filter as elem | flags << 16 -- elem 0, 2, 4 or 8, flags 0 or 1 (the delta), flags 1 only with an elem.  The
+ * frame's bytes went through that filter as one segment before its blocks were cut, exactly as a stream-level filter does; crc_raw
+ * is of the filtered blocks, crc_all of the original input, table_crc covers the word, frames are cut as ever and tables, records,
+ * payload and trailer are unchanged: a version-10 stream has the size of the version-8 stream with the same filters.  Per frame
+ * (the ragged tail included) the writer probes the frame in place (glcFilterProbeSegments), reads the seven costs back with one
+ * wait -- the one host read per frame, as the CHOOSE codec reads its stats --, applies the rule of csrc/filter_rule.h, stages the
+ * frame through the chosen filter (not at all for no filter) and runs the auto mode's frame on it.  A frame longer than
+ * GLC_FILTER_PROBE_MAX_LEN is judged by its first 2^31 bytes.  A checkpoint shard, an archive or a column file that holds float32,
+ * int64 and text sections behind each other gets each frame's own filter; the sizes are in INTEGRATION.md 4b ("filter: when").
+ * 0 (the default) writes versions 1 to 9 byte for byte as ever.  on = 1 needs the codec GLC_CONTAINER_CODEC_HUFF0, the auto mode on
+ * and the plan's shuffle off: on = 1 without all three, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the
+ * setting as it was.  While it is on glcPlanSetContainerShuffle(plan, 2, 4 or 8) is refused; glcPlanSetContainerAuto(plan, 0) and a
+ * codec change that ends the auto mode switch it off.  All six container entry points write the same bytes, with pipelining on or
+ * off; the index keeps every frame's filter, and range reads use it for the blocks a range needs and for the range inverse filters
+ * (the delta's rounding to 2048 elements included); glcContainerIndexInfo's fourth word reports what the stream header says.  The
+ * setting is also the version the plan speaks: a plan with it on reads versions 1 to 5, 7, 8 and 10; every other plan refuses a
+ * version-10 stream as a stream-header failure.  A frame word that is none of the above is a frame-table failure naming the frame,
+ * found by the header's range check before the tables are touched.  Not combined with the BWT codec, the CHOOSE codec or the other
+ * order-0 modes; element sizes other than 2, 4 and 8, a sampled probe and a choice per block are not offered. */
+CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on);
+
+/* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
+ * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.
+ * With filter-auto off every frame counts for the plan's own filter.  Zeros before the first. */
+CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8]);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -42,13 +42,21 @@ it can run.
 device events, ratio / encode / decode per codec and what glcContainerLastChoice reports, then the bigram probe alone against the
 auto mode's probe and a device-to-device copy.
 
+--filter-auto (any --data but zipf's compact comparison; --rounds R, at least 1) is the filter-auto section: the order-0 codec with
+the auto mode on under no filter, under the filter named by --shuffle / --delta (default: the data's element size) and under
+filter-auto (glcPlanSetContainerFilterAuto, format version 10), R interleaved rounds of encode and decode timed with device events,
+ratio, the CRC-32 of the container and what glcContainerLastFilters reports per setting.  --filter-auto-off-only runs the first two
+settings alone, which is also what a build without the setting can run.
+
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
-                                [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]"""
+                                [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
+                                [--filter-auto | --filter-auto-off-only]"""
 import argparse
 import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -391,6 +399,60 @@ def sparse_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_spar
     return res
 
 
+def filter_auto_section(torch, glc, plan, d_in, total, elem, delta, rounds, with_filter_auto=True):
+    """the order-0 container with the auto mode on under three filter settings, interleaved: "none" (no filter), "fixed" (the
+    filter set by hand: elem, delta) and "filter_auto" (format version 10: a probe and a host wait per frame, the filter picked per
+    frame; left out without with_filter_auto, which is what a build without it can run).  `rounds` rounds of one encode and one
+    decode per setting after one untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["none", "fixed"] + (["filter_auto"] if with_filter_auto else [])
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+    glc.container_set_auto(plan, 1)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            if with_filter_auto:
+                glc.container_set_filter_auto(plan, 0)
+            glc.container_set_shuffle(plan, elem if s == "fixed" else 0)
+            if s == "fixed" and elem and delta:
+                glc.container_set_delta(plan, 1)
+            if s == "filter_auto":
+                glc.container_set_filter_auto(plan, 1)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["crc32"] = zlib.crc32(cont[:clen].cpu().numpy().tobytes())
+                if with_filter_auto:
+                    res[s]["frames_per_filter"] = list(glc.container_last_filters(plan))
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -409,6 +471,9 @@ def main():
     ap.add_argument("--dedup", action="store_true", help="the sparse section also runs the order-0 codec's dedup mode (format version 9)")
     ap.add_argument("--runs", action="store_true", help="text-like data: the runs section, the BWT codec's runs mode off and on (format version 6)")
     ap.add_argument("--runs-off-only", action="store_true", help="the runs section without the mode (what a build without it can run)")
+    ap.add_argument("--filter-auto", action="store_true",
+                    help="the filter-auto section (format version 10): the auto mode with no filter, with --shuffle / --delta set by hand and with filter-auto")
+    ap.add_argument("--filter-auto-off-only", action="store_true", help="the filter-auto section without the setting (what a build without it can run)")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -436,7 +501,8 @@ def main():
             runs = d_in[:total // (128 * n) * 128 * n].view(-1, 2, 64 * n)
             runs[:, 1, :] = text_on_device(torch, dev, "textlike", runs.shape[0] * 64 * n).view(-1, 64 * n)
     elif args.data in ("textlike", "loglike"):
-        assert args.runs or args.runs_off_only or args.codec == 4, "text-like data is the runs and the choose section's"
+        assert args.runs or args.runs_off_only or args.codec == 4 or args.filter_auto or args.filter_auto_off_only, \
+            "text-like data is the runs, the choose and the filter-auto section's"
         d_in = text_on_device(torch, dev, args.data, total)
     else:
         d_in = typed_on_device(torch, L, dev, args.data, total)
@@ -466,6 +532,14 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if args.filter_auto or args.filter_auto_off_only:
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["filter_auto"] = filter_auto_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM.get(args.data, 0), args.delta,
+                                                     max(1, args.rounds), args.filter_auto)
         print(json.dumps(res))
         return
     if args.data != "zipf" or args.dedup:

@@ -1,0 +1,99 @@
+"""The filter probe alone (csrc/filter_probe.hip, glcFilterProbeSegments) against a device-to-device copy of the same bytes:
+--gib GiB as ONE segment (a frame, as the container's writer probes it) and as segments of 1 MiB, of zeros, int64 timestamps
+(the running sum of steps uniform in [900, 1100): tests/series_datagen.py's ts64, made on the device), float32 ~ N(0, 1) and noise;
+--rounds interleaved rounds after one warm-up, each call timed with device events; medians and spreads (max - min) in one JSON line
+per input, with the candidate the rule picks from the costs.
+
+  frame    glcFilterProbeSegments over the whole buffer as one segment: a memset of the rows, k_fp_probe, k_fp_cost
+  blocks   the same call over segments of 1 MiB
+  copy     a device-to-device copy
+
+python tools/bench_filter_probe.py [--gib 1] [--rounds 5]"""
+import argparse
+import importlib.util
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+MiB = 1 << 20
+
+from filter_auto_model import CANDS, pick  # noqa: E402  (the rule and its margin are the model's)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--rounds", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
+    glc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(glc)
+    dev = torch.device("cuda:0")
+    count = int(args.gib * 1024)
+    total = count * MiB
+    assert total <= glc.FILTER_PROBE_MAX_LEN, "one segment holds at most 2 GiB"
+    g = torch.Generator(device=dev)
+    g.manual_seed(0x5EED0011)
+    off = torch.arange(count, dtype=torch.int64, device=dev) * MiB
+    ln = torch.full((count,), MiB, dtype=torch.int64, device=dev)
+    off1 = torch.zeros(1, dtype=torch.int64, device=dev)
+    ln1 = torch.full((1,), total, dtype=torch.int64, device=dev)
+    planes = torch.empty((count, 22, 256), dtype=torch.int32, device=dev)
+    costs = torch.empty((count, 7), dtype=torch.int64, device=dev)
+    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    L = glc._ct()
+
+    def timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for name in ("zeros", "ts64", "float32", "noise"):
+        if name == "zeros":
+            d_in = torch.zeros(total, dtype=torch.uint8, device=dev)
+        elif name == "ts64":
+            d_in = torch.cumsum(torch.randint(900, 1100, (total // 8,), dtype=torch.int64, device=dev, generator=g), 0).view(torch.uint8)
+        elif name == "float32":
+            d_in = torch.randn(total // 4, dtype=torch.float32, device=dev, generator=g).view(torch.uint8)
+        else:
+            d_in = torch.randint(0, 256, (total,), dtype=torch.uint8, device=dev, generator=g)
+
+        def frame():
+            glc._chk("glcFilterProbeSegments", L.glcFilterProbeSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total,
+                                                                         planes.data_ptr(), costs.data_ptr(), None))
+
+        def blocks():
+            glc._chk("glcFilterProbeSegments", L.glcFilterProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), count, MiB,
+                                                                         planes.data_ptr(), costs.data_ptr(), None))
+
+        def copy():
+            out.copy_(d_in)
+
+        res = {k: [] for k in ("frame_GBps", "blocks_GBps", "copy_GBps")}
+        for r in range(args.rounds + 1):                        # round 0 is the warm-up
+            for k, fn in (("frame_GBps", frame), ("blocks_GBps", blocks), ("copy_GBps", copy)):
+                t = timed(fn)
+                if r:
+                    res[k].append(round(total / t / 1e9, 2))
+        block_rows = planes.to(torch.int64).sum(dim=0)          # the segments of 1 MiB start on delta restarts: their rows add up
+        frame()
+        torch.cuda.synchronize()
+        assert torch.equal(planes[0].to(torch.int64), block_rows) and int(planes[0, :8].sum(dtype=torch.int64).item()) == total
+        c = [int(v) for v in costs[0].cpu().tolist()]
+        rep = {"workload": "%d MiB of %s" % (count, name), "costs_bytes": [v // 2048 for v in c], "pick": list(CANDS[pick(c)])}
+        for k, v in res.items():
+            s = sorted(v)
+            rep[k], rep[k + "_median"], rep[k + "_spread"] = v, s[len(s) // 2], round(s[-1] - s[0], 2)
+        print(json.dumps(rep))
+        del d_in
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -14,7 +14,11 @@ profiles/range_read.md).
 --dedup runs one container instead: `pages` of tests/dedup_inputs.py (4 KiB pages of which about half repeat frame-wide) through the
 order-0 codec with the dedup mode, where a read inside a kind-6 block also decodes the blocks from its lowest source block on.
 
-python tools/bench_range.py [--gib 1] [--reps 20] [--warmup 3] [--md FILE] [--dedup]"""
+--filter-auto runs one container instead: int64 timestamps and float32 values (tests/series_datagen.py, tests/typed_datagen.py) in
+alternating frames through the order-0 codec with the auto mode and filter-auto (format version 10), where every frame has its own
+filter and a read uses the frame's for the blocks it needs and for the range inverse.
+
+python tools/bench_range.py [--gib 1] [--reps 20] [--warmup 3] [--md FILE] [--dedup | --filter-auto]"""
 import argparse
 import importlib.util
 import json
@@ -34,9 +38,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--md", default=None, help="default profiles/range_read.md, with --dedup profiles/range_read_dedup.md")
     ap.add_argument("--dedup", action="store_true", help="the `pages` container of the dedup mode (format version 9) alone")
+    ap.add_argument("--filter-auto", action="store_true", help="a container of alternating int64 and float32 frames with filter-auto (format version 10) alone")
     args = ap.parse_args()
     assert args.reps >= 20, "at least 20 timed repetitions"
-    args.md = args.md or os.path.join(ROOT, "profiles", "range_read_dedup.md" if args.dedup else "range_read.md")
+    args.md = args.md or os.path.join(ROOT, "profiles", "range_read_dedup.md" if args.dedup else "range_read_filter_auto.md" if args.filter_auto
+                                      else "range_read.md")
     import numpy as np
     import torch
 
@@ -63,6 +69,17 @@ def main():
         import dedup_inputs
         inputs = [("pages", lambda: torch.from_numpy(np.array(dedup_inputs.make("pages", n), copy=True)).to(dev),
                    dict(codec=1, elem=0, delta=False, sparse=False, dedup=True))]
+    if args.filter_auto:
+        import typed_datagen
+
+        def mixed():                                              # frames of rows blocks: timestamps, floats, timestamps, ...
+            F = BLOCK * ROWS
+            ts = np.asarray(series_datagen.series_bytes("ts64", n))
+            fl = np.frombuffer(typed_datagen.typed_bytes("float32", n), np.uint8)
+            x = np.where((np.arange(n) // F) % 2 == 0, ts, fl)
+            return torch.from_numpy(np.array(x, dtype=np.uint8, copy=True)).to(dev)
+
+        inputs = [("ts64 / float32", mixed, dict(codec=1, elem=0, delta=False, sparse=False, filter_auto=True))]
     res = {"bytes": n, "block": BLOCK, "rows": ROWS, "reps": args.reps, "containers": {}}
     rows = ["| container | read | at | median ms | fastest | slowest | time / full decode | frames | blocks | container bytes fetched |",
             "|---|---|---|---|---|---|---|---|---|---|"]
@@ -79,6 +96,9 @@ def main():
                     glc.container_set_sparse(plan, 1)
                 if st.get("dedup"):
                     glc.container_set_dedup(plan, 1)
+                if st.get("filter_auto"):
+                    glc.container_set_auto(plan, 1)
+                    glc.container_set_filter_auto(plan, 1)
                 c = glc.container_compress(plan, x).clone()
                 full_out = torch.empty(n, dtype=torch.uint8, device=dev)
                 d_len = torch.zeros(1, dtype=torch.int64, device=dev)
