@@ -1,35 +1,49 @@
-// container_api.cpp -- the C ABI of include/glc_container.h: the BWT container over a COMPRESS plan.
-// A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says two
-// things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
+// container_api.cpp -- the C ABI of include/glc_container.h that works on a COMPRESS plan: the BWT container,
+// its frame index and range reads, what the plan reports of its last calls, and the plan's container settings.  (The plan-less
+// segment calls of that header -- CRC, filters, sparse, dedup, zero-run, rANS, the probes -- are segments_api.cpp.)
+//
+// Format.  A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says
+// two things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
-// 1 raw always, 2 order-0 Huffman where kind2_legal(), 3 its sparse form (sparse.hip) where kind3_legal(), 4 the BWT codec's
-// zero-run form (zrun.hip) where kind4_legal(), 5 the order-0 codec's rANS form (ans.hip) where kind5_legal()).  ct_legal() is the one table of legal triples: format_of() picks the
-// writer's from the plan's settings (the lowest version whose kinds hold every kind they may write), parse_format() accepts a reader's (both read ct_legal()).
-// Under format version 10 (filter-auto) the filter is each FRAME's: the stream's triple is (10, 0, 0), word 3 of a frame header names the
-// frame's filter, and ct_frame_format() gives the format a frame went through -- the writer picks it per frame from the filter probe
-// (filter_probe.hip, filter_rule.h; one host read of seven costs per frame), the readers take it from the frame.
-// Encode: a filtered frame is staged through filter_device() into staging kept with the plan and encoded from there; crc_all is
-// taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman records
-// straight into the container; with the order-0 codec (hd_batch.hip) batched histograms and tables give every block's record size
-// and the batched encoder writes the kind-2 records (frame_order0 is the one path; with the sparse mode on its parts are frame_sparse's, kinds 2 and 3; with the rANS mode on
-// frame_ans's, kind 5, the histograms alone and the kernels of ans.hip; with the auto mode on frame_auto's, the probe of auto.hip and a kind per block out of 2, 3 and 5).
-// With the order-0 codec's dedup mode on (frame_dedup, kind 6, format version 9; dedup.hip) the map of the frame's 512-byte chunks
-// runs first, the chunks that repeat an earlier chunk of the frame are elided, and the sparse mode's compaction and the batched
-// encoder work on what is kept; the decoder puts the kept chunks back and one fill pass copies the elided ones from their sources.
-// With the BWT codec's runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the zero-run split and the same batched encoder.  Either way the kernels of container.hip decide the record kinds before the
-// payload offsets are scanned, copy the raw records, CRC everything and write the frame's tables behind the packer.  Frames
-// chain on the device (a cursor word): no host read inside or between frames, one at the end.  With the CHOOSE codec
-// (super_frame) the bigram probe of choose.hip runs over what is one frame otherwise, its stats rows are read back (the one host
-// read per such group), the rule of choose_rule.h picks the BWT or the order-0 codec per block, and every maximal run of blocks of
-// one choice becomes one frame by that codec's path above: format version 3, kinds 0, 1 and 2, no reader change.
-// Decode: decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from the caller's
-// device buffers or from a Source through staging; the frame index (glcContainerIndex*) is the same walk without the decoding,
-// and a range read (glcContainerReadRange*) decodes a subset of the blocks of the frames its range overlaps.  Per frame the host range-checks the 32-byte frame header, the device checks the tables and records (one
-// verdict read back), then raw records are copied out, runs of kind 0 go to glcDecompressBatchCompact reading the tables in
-// place, runs of kind 2 to the batched order-0 decoder, runs of kind 3 to it as well (the kept bytes into scratch, then expanded
-// under the record's mask), runs of kind 4 to it too (A and B into scratch, joined into the BWT decoder's MTF rows, then its
-// inverse MTF and inverse BWT), runs of kind 5 to the rANS decoder (tables from the verified histograms, then one pass), and the decoded bytes are checked against the blocks' CRCs; a filtered
-// frame is decoded into staging, checked there and inverted into the output by filter_device().
+// 1 raw always; 2 order-0 Huffman, 3 its sparse form (sparse.hip), 4 the BWT codec's zero-run form (zrun.hip), 5 the order-0
+// codec's rANS form (ans.hip) and 6 its dedup form (dedup.hip) where kind2_legal() .. kind6_legal() say so).  ct_legal() is the
+// one table of legal triples: format_of() picks the writer's from the plan's settings (the lowest version whose kinds hold every
+// kind they may write), parse_format() accepts a reader's.  Under format version 10 (filter-auto) the filter is each FRAME's: the
+// stream's triple is (10, 0, 0), word 3 of a frame header names the frame's filter, and ct_frame_format() gives the format a frame
+// went through -- the writer picks it per frame from the filter probe (filter_probe.hip, filter_rule.h; one host read of seven
+// costs per frame), the readers take it from the frame.
+//
+// Encode (Encoder).  A filtered frame is staged through filter_device() into staging kept with the plan and encoded from there;
+// crc_all is taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman
+// records straight into the container; with its runs mode on (frame_runs, kind 4) the plan's sorter and MTF stage feed the
+// zero-run split and the batched order-0 encoder.  With the order-0 codec (hd_batch.hip) frame_order0 is the one path: a mode hands
+// it its parts -- what gives every block's record size, the kinds kernel where the mode has its own, and what writes the records
+// behind the payload offsets.  frame_plain: batched histograms and tables, kind 2.  frame_sparse: kinds 2 and 3.  frame_ans: kind
+// 5, the histograms alone and the kernels of ans.hip.  frame_auto: the probe of auto.hip and a kind per block out of 2, 3 and 5.
+// frame_dedup (kind 6, format version 9): the map of the frame's 512-byte chunks runs first, the chunks that repeat an earlier
+// chunk of the frame are elided, and the sparse mode's compaction and the batched encoder work on what is kept.  Either way the
+// kernels of container.hip decide the record kinds before the payload offsets are scanned, copy the raw records, CRC everything
+// and write the frame's tables behind the packer.  Frames chain on the device (a cursor word): no host read inside or between
+// frames, one at the end.  With the CHOOSE codec (super_frame) the bigram probe of choose.hip runs over what is one frame
+// otherwise, its stats rows are read back (the one host read per such group), the rule of choose_rule.h picks the BWT or the
+// order-0 codec per block, and every maximal run of blocks of one choice becomes one frame by that codec's path above: format
+// version 3, kinds 0, 1 and 2, no reader change.
+//
+// Decode (Decoder).  decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from
+// the caller's device buffers or from a Source through staging; the frame index (glcContainerIndex*) is the same walk without the
+// decoding, and a range read (glcContainerReadRange*) decodes a subset of the blocks of the frames its range overlaps.  Per frame
+// the host range-checks the 32-byte frame header, the device checks the tables and records (one verdict read back), then raw
+// records are copied out and for_runs() hands every maximal run of blocks of one kind to that kind's decoder: kind 0 to
+// glcDecompressBatchCompact reading the tables in place, kind 2 to the batched order-0 decoder, kind 3 to it as well (the kept
+// bytes into scratch, then expanded under the record's mask), kind 4 to it too (A and B into scratch, joined into the BWT
+// decoder's MTF rows, then its inverse MTF and inverse BWT), kind 5 to the rANS decoder (tables from the verified histograms, then
+// one pass), kind 6 to the order-0 decoder and the sparse join (the kept chunks put back; one fill pass then copies the elided
+// ones from their sources).  The decoded bytes are checked against the blocks' CRCs; a filtered frame is decoded into staging,
+// checked there and inverted into the output by filter_device().
+//
+// Reports and settings.  What glcContainerLastError, LastRangeStats, LastChoice and LastFilters answer is one CtReports kept in the
+// plan: it starts with the plan and goes with it, and two plans share nothing.  The glcPlanSet/GetContainer* entries are ct_set()
+// and ct_get() over the plan's CtSettings, whose set_*() are the whole rule.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 #include "dedup_rule.h"
@@ -37,8 +51,6 @@
 
 #include <fcntl.h>
 #include <memory>
-#include <mutex>
-#include <map>
 #include <new>
 #include <stdio.h>
 #include <string.h>
@@ -70,15 +82,11 @@ uint32_t crc32_host(const void *data, size_t len, uint32_t crc)
 
 namespace {
 
-struct LastError { unsigned long long v[3] = {0, ~0ull, ~0ull}; };
-std::mutex g_err_mu;
-std::map<CUDPPHandle, LastError> g_err;
-
+// what glcContainerLastError reports: kept with the plan (CtReports), like everything a plan's calls leave behind
 void set_error(CUDPPHandle plan, unsigned long long what, unsigned long long frame = ~0ull, unsigned long long block = ~0ull)
 {
-    std::lock_guard<std::mutex> g(g_err_mu);
-    LastError &e = g_err[plan];
-    e.v[0] = what; e.v[1] = frame; e.v[2] = block;
+    unsigned long long *e = plan_container_reports(plan).error;
+    e[0] = what; e[1] = frame; e[2] = block;
 }
 
 CUDPPResult fail(CUDPPHandle plan, unsigned long long what, unsigned long long frame = ~0ull, unsigned long long block = ~0ull)
@@ -87,29 +95,6 @@ CUDPPResult fail(CUDPPHandle plan, unsigned long long what, unsigned long long f
     return what == CT_CAPACITY ? CUDPP_ERROR_ILLEGAL_CONFIGURATION : CUDPP_ERROR_UNKNOWN;
 }
 
-// what glcContainerLastFilters reports: frames per candidate of filter_rule.h, then the frame count; kept with the plan
-struct LastFilters { unsigned long long v[FILTER_CANDS + 1] = {}; };
-void set_filters(CUDPPHandle plan, const LastFilters &f)
-{
-    unsigned long long *c = plan_container_filters(plan);
-    for (uint32_t i = 0; i <= FILTER_CANDS; i++) c[i] = f.v[i];
-}
-
-// what glcContainerLastChoice reports: the last successful compress of the plan, kept with it
-void set_choice(CUDPPHandle plan, const unsigned long long v[3])
-{
-    unsigned long long *c = plan_container_choice(plan);
-    for (int i = 0; i < 3; i++) c[i] = v[i];
-}
-
-CUDPPResult hip_res(hipError_t e)
-{
-    if (e == hipSuccess) return CUDPP_SUCCESS;
-    (void)hipGetLastError();
-    return e == hipErrorOutOfMemory ? CUDPP_ERROR_INSUFFICIENT_RESOURCES : CUDPP_ERROR_UNKNOWN;
-}
-
-#define CT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return hip_res(e_); } while (0)
 #define CT_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
 
 struct Plan {
@@ -134,11 +119,6 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 // -------------------------------------------------------------------------------------------------------------------------
 // the format rule (ct_legal() and format_of() of container_internal.h: the table the device's walk reads as well)
 // -------------------------------------------------------------------------------------------------------------------------
-hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
-{
-    return (f.delta() ? delta_shuffle_device : shuffle_device)(st, in, out, len, f.elem, inverse);
-}
-
 void make_header(uint32_t h[8], const CtFormat &f, uint32_t block_len, unsigned long long total)
 {
     h[0] = CT_MAGIC_STREAM; h[1] = f.version | (f.flags << 16);
@@ -147,20 +127,6 @@ void make_header(uint32_t h[8], const CtFormat &f, uint32_t block_len, unsigned 
     h[6] = crc32_host(h, 24); h[7] = 0;
 }
 
-// Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
-// the allocation it places, so the size and the pointers cannot disagree.
-struct Carver {
-    uint8_t *base;
-    size_t off = 0;
-    explicit Carver(void *b = nullptr) : base(static_cast<uint8_t *>(b)) {}
-    template <class T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + off); off += count * sizeof(T); return base ? p : nullptr; }
-    void round(size_t a) { off = (off + a - 1) & ~(a - 1); }      // the offset (the base is at least as aligned)
-    void align(size_t a)                                          // the address; measuring counts the worst case
-    {
-        off = base ? (size_t)(((reinterpret_cast<uintptr_t>(base) + off + a - 1) & ~(uintptr_t)(a - 1)) - reinterpret_cast<uintptr_t>(base)) : off + a;
-    }
-    size_t bytes() const { return off; }
-};
 // measure with a null Carver, allocate (alloc(bytes, &base) -> hipError_t), carve again on the allocation
 template <class Alloc, class Carve>
 hipError_t carve_on(Alloc alloc, Carve carve)
@@ -200,14 +166,14 @@ struct Encoder {
     CtEncDedup dd = {};                                       // the dedup mode's: the sparse mode's scratch (masks, compaction space) and its own
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
     unsigned long long *ch_stats = nullptr, *h_stats = nullptr;   // the CHOOSE codec's probe rows [rows][4]: device, pinned
-    unsigned long long choice[3] = {0, 0, 0};                 // blocks given to the BWT codec, to the order-0 codec; frames
+    CtReports rep;                                            // this call's choice and filters, committed when it succeeds
     // filter-auto (format version 10): the filter probe's rows and costs of one frame, the frame as its one segment {offset, length},
-    // the costs on the host (pinned), and the frames each candidate got (the plan's own filter's candidate with the setting off)
+    // the costs on the host (pinned); rep.filters counts the frames each candidate got (the plan's own filter's candidate with the
+    // setting off)
     bool filter_auto = false;
     uint32_t own_pick = 0;                                    // the candidate every frame counts for with the setting off
     uint32_t *fp_planes = nullptr;
     unsigned long long *fp_costs = nullptr, *fp_seg = nullptr, *h_costs = nullptr;
-    LastFilters filters;
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
     void carve_runs(Carver &c)
@@ -376,8 +342,8 @@ struct Encoder {
     // `by`: the codec that writes this frame (the plan's, or what the CHOOSE codec picked for its blocks).
     CUDPPResult frame(const uint8_t *d_in, uint32_t nb, uint32_t blk_len, uint8_t *out, unsigned long long cap, uint32_t by)
     {
-        choice[by == CT_CODEC_BWT ? 0 : 1] += nb;
-        choice[2]++;
+        rep.choice[by == CT_CODEC_BWT ? 0 : 1] += nb;
+        rep.choice[2]++;
         (void)plan_info(P.h, nullptr, nullptr, nullptr, &P.parity);
         const CtEncFrame &f = fr[P.parity];
         const uint8_t *orig = nullptr;
@@ -390,8 +356,8 @@ struct Encoder {
             ff.elem = c.elem > 1 ? c.elem : 0;
             ff.flags = c.delta ? CT_FLAG_DELTA : 0;
         }
-        filters.v[pick]++;
-        filters.v[FILTER_CANDS]++;
+        rep.filters[pick]++;
+        rep.filters[FILTER_CANDS]++;
         if (ff.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
             CT_TRY(filter_device(P.st, ff, d_in, stage[P.parity], (unsigned long long)nb * blk_len, false));
@@ -415,15 +381,15 @@ struct Encoder {
     }
 
     // The order-0 codec's frame in every mode, wholly on the plan's stream: the blocks as segments of the frame -> sizes(), the
-    // mode's passes up to everything the kinds need -> kinds (ct_enc_kind0) -> payload offsets -> place(out as words, its
-    // capacity in words), the mode's records written behind the offsets -> the same stage behind the packer as ever.  The four
-    // functions below are the modes: each says its two parts and what they share.
+    // mode's passes up to everything the kinds need -> kinds() (ct_enc_kind0 unless the mode brings its own) -> payload offsets ->
+    // place(out as words, its capacity in words), the mode's records written behind the offsets -> the same stage behind the packer
+    // as ever.  The five functions below are the modes: each says its parts and what they share.
     struct Frame0 {
         const CtEncFrame &f; const uint8_t *d_in, *orig; uint32_t nb, blk_len; uint8_t *out; unsigned long long cap;
         uint32_t word;                                        // the frame header's word 3: the frame's filter under version 10, else 0
     };
-    template <class Sizes, class Place>
-    CUDPPResult frame_order0(const Frame0 &F, Sizes sizes, Place place)
+    template <class Sizes, class Kinds, class Place>
+    CUDPPResult frame_order0(const Frame0 &F, Sizes sizes, Kinds kinds, Place place)
     {
         uint32_t *out_words = reinterpret_cast<uint32_t *>(F.out);
         const unsigned long long cap_words = F.cap / 4;
@@ -431,13 +397,18 @@ struct Encoder {
         CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, F.nb, F.blk_len));
         CT_TRY(sizes());
         plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_kind0(P.st, mode, F.f, h0, sp, an, au, F.nb, F.blk_len, state));
+        CT_TRY(kinds());
         CT_TRY(huff_block_offsets(P.st, F.f.size, F.nb, F.f.boff, F.f.start, (size_t)cap_words, status));
         CT_TRY(place(out_words, cap_words));
         plan_stage_mark(P.h, 2);
         CT_TRY(ct_enc_after_pack(P.st, F.f, F.d_in, F.orig, F.nb, F.blk_len, F.out, F.cap, state, F.word));
         plan_stage_mark(P.h, 3);
         return CUDPP_SUCCESS;
+    }
+    template <class Sizes, class Place>
+    CUDPPResult frame_order0(const Frame0 &F, Sizes sizes, Place place)
+    {
+        return frame_order0(F, sizes, [&] { return ct_enc_kind0(P.st, mode, F.f, h0, sp, an, au, F.nb, F.blk_len, state); }, place);
     }
 
     // tables (and with them every record's size) -> kinds -> the batched encoder
@@ -543,39 +514,35 @@ struct Encoder {
     // the dedup mode, wholly on the plan's stream: the map of the frame's chunks (hash, insert, verify) -> per block the mask, the
     // refs, the lowest source block and kind 6 or 2 -> compaction of the kind-6 blocks (the sparse mode's mover under the mask
     // widened to 64-byte chunks) -> counts and tables, of K or of the whole block -> record sizes and the record rule -> payload
-    // offsets -> masks and refs into the records and every stream encoded behind them.  Its kinds kernel is its own, so the
-    // sequence is frame_order0's with that one step exchanged.
+    // offsets -> masks and refs into the records and every stream encoded behind them.  Its kinds kernel is its own: the one
+    // mode that hands frame_order0 that part as well.
     CUDPPResult frame_dedup(const Frame0 &F)
     {
         KernelProf *prof = plan_prof(P.h);
         const CtEncFrame &f = F.f;
         const uint32_t nb = F.nb, blk_len = F.blk_len;
-        uint32_t *out_words = reinterpret_cast<uint32_t *>(F.out);
-        const unsigned long long cap_words = F.cap / 4;
         const HdbSegs g2{nullptr, h0.in_off, h0.in_len, nb, blk_len};                      // (absolute addresses: frame blocks and K's)
-        plan_stage_mark(P.h, 0);
-        CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, nb, blk_len));
-        CT_TRY(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));          // (klen itself comes two steps on)
         DdSegs m{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, dd.hash, dd.table, dd.slots, dd.src, nb, blk_len, dd.nch};
         m.nch = (blk_len + DD_CHUNK - 1) / DD_CHUNK;                                       // (the frame's: the tail frame's blocks are shorter)
         m.slots = (uint32_t)dedup_slots((size_t)nb * m.nch);
         CtEncDedup d = dd;
         d.nch = m.nch;
-        CT_TRY(dedup_map(P.st, m));
-        CT_TRY(ct_enc_dedup_decide(P.st, d, sp, h0.blk_off, F.d_in, nb, blk_len, f.hist, h0.in_off, h0.in_len));
-        const SpSegs s{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr,
-                       sp.mask_stride, sp.skip_move, nb, blk_len};
-        CT_TRY(sparse_compact(P.st, s));
-        CT_TRY(hdb_tables(P.st, g2, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof));
-        plan_stage_mark(P.h, 1);
-        CT_TRY(ct_enc_dedup_kind(P.st, f, h0, sp, d, nb, blk_len, state));
-        CT_TRY(huff_block_offsets(P.st, f.size, nb, f.boff, f.start, (size_t)cap_words, status));
-        CT_TRY(ct_enc_dedup_place(P.st, f, sp, d, nb, blk_len, out_words, cap_words));
-        CT_TRY(hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, out_words, sp.unit_off, cap_words, f.only, h0.work, prof));
-        plan_stage_mark(P.h, 2);
-        CT_TRY(ct_enc_after_pack(P.st, f, F.d_in, F.orig, nb, blk_len, F.out, F.cap, state));
-        plan_stage_mark(P.h, 3);
-        return CUDPP_SUCCESS;
+        return frame_order0(
+            F,
+            [&]() -> hipError_t {
+                CT_HIP(ct_block_offsets(P.st, sp.kept_off, sp.klen, nb, sp.kept_stride));    // (klen itself comes two steps on)
+                CT_HIP(dedup_map(P.st, m));
+                CT_HIP(ct_enc_dedup_decide(P.st, d, sp, h0.blk_off, F.d_in, nb, blk_len, f.hist, h0.in_off, h0.in_len));
+                const SpSegs s{const_cast<uint8_t *>(F.d_in), h0.blk_off, h0.blk_len, sp.kept, sp.kept_off, sp.fill, sp.mask, nullptr,
+                               sp.mask_stride, sp.skip_move, nb, blk_len};
+                CT_HIP(sparse_compact(P.st, s));
+                return hdb_tables(P.st, g2, true, f.hist, h0.lens, h0.codes, nullptr, h0.nun, sp.skip_table, prof);
+            },
+            [&] { return ct_enc_dedup_kind(P.st, f, h0, sp, d, nb, blk_len, state); },
+            [&](uint32_t *out, unsigned long long cap) -> hipError_t {
+                CT_HIP(ct_enc_dedup_place(P.st, f, sp, d, nb, blk_len, out, cap));
+                return hdb_encode(P.st, g2, h0.lens, h0.codes, h0.nun, out, sp.unit_off, cap, f.only, h0.work, prof);
+            });
     }
 
     // the BWT codec's frame with the runs mode on, wholly on the plan's stream: BWT and MTF of the blocks by the plan's sorter
@@ -633,6 +600,16 @@ struct Encoder {
         return CUDPP_SUCCESS;
     }
 
+    // the call is through: what glcContainerLastChoice and glcContainerLastFilters report is this call's from here on
+    CUDPPResult succeeded()
+    {
+        CtReports &r = plan_container_reports(P.h);
+        memcpy(r.choice, rep.choice, sizeof r.choice);
+        memcpy(r.filters, rep.filters, sizeof r.filters);
+        set_error(P.h, CT_OK);
+        return CUDPP_SUCCESS;
+    }
+
     // every frame of [d_in, + len) with the plan's n and rows
     CUDPPResult frames(const uint8_t *d_in, unsigned long long len, uint8_t *out, unsigned long long cap)
     {
@@ -652,6 +629,22 @@ struct Encoder {
 // -------------------------------------------------------------------------------------------------------------------------
 // decoder
 // -------------------------------------------------------------------------------------------------------------------------
+// body(a, count) -> CUDPPResult over the maximal runs [a, a + count) of the blocks 0 .. nb: in(a, a) = a run may start at block a,
+// in(a, b) = block b may join the run that starts at a.  Stops at the first body that fails.
+template <class In, class Body>
+CUDPPResult for_runs(uint32_t nb, In in, Body body)
+{
+    for (uint32_t a = 0; a < nb;) {
+        if (!in(a, a)) { a++; continue; }
+        uint32_t b = a + 1;
+        while (b < nb && in(a, b)) b++;
+        const CUDPPResult r = body(a, b - a);
+        if (r != CUDPP_SUCCESS) return r;
+        a = b;
+    }
+    return CUDPP_SUCCESS;
+}
+
 struct Decoder {
     Plan P;
     void *mem = nullptr;
@@ -774,18 +767,9 @@ struct Decoder {
         std::vector<uint8_t> need9;                               // version 9: need[] with the source-only blocks marked 2
         auto want = [&](uint32_t b) { return !need || need[b] != 0; };
         auto checked = [&](uint32_t b) { return !need || need[b] == DEDUP_NEEDED; };
-        // over the runs of wanted blocks (all of them: one run)
-        auto runs = [&](auto call) -> hipError_t {
-            for (uint32_t a = 0; a < nb;) {
-                if (!want(a)) { a++; continue; }
-                uint32_t b = a;
-                while (b < nb && want(b)) b++;
-                const hipError_t e = call(a, b - a);
-                if (e != hipSuccess) return e;
-                a = b;
-            }
-            return hipSuccess;
-        };
+        // what for_runs() walks: the runs of wanted blocks (all of them: one run), and of the blocks that are checked
+        auto wanted = [&](uint32_t, uint32_t b) { return want(b); };
+        auto to_check = [&](uint32_t, uint32_t b) { return checked(b); };
         const bool k2 = fmt.kind2_legal();
         KernelProf *prof = plan_prof(P.h);
         if (k2) CT_TRY(reserve_huff0(nb, blk_len));
@@ -805,33 +789,26 @@ struct Decoder {
             need = need9.data();
         }
         if (decoded) for (uint32_t b = 0; b < nb; b++) *decoded += want(b) ? 1 : 0;
-        CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_raw(P.st, f, fr, nb, blk_len, out, a, cnt); }));
+        CUDPPResult r = for_runs(nb, wanted, [&](uint32_t a, uint32_t cnt) { return hip_result(ct_dec_raw(P.st, f, fr, nb, blk_len, out, a, cnt)); });
+        if (r != CUDPP_SUCCESS) return r;
         const CtTables T = ct_tables(nb, blk_len);
         const uint32_t *W = reinterpret_cast<const uint32_t *>(fr + CT_FRAME_HDR);
         const unsigned int *pay = reinterpret_cast<const unsigned int *>(fr + CT_FRAME_HDR + 4 * T.words);
-        // over the maximal runs [a, b) of wanted blocks of kind K: more(a, b) = block b may still join the run that starts at a
-        auto runs_of = [&](uint32_t K, auto more, auto body) -> CUDPPResult {
-            for (uint32_t a = 0; a < nb;) {
-                if (kind[a] != K || !want(a)) { a++; continue; }
-                uint32_t b = a;
-                while (b < nb && kind[b] == K && want(b) && more(a, b)) b++;
-                const CUDPPResult r = body(a, b - a);
-                if (r != CUDPP_SUCCESS) return r;
-                a = b;
-            }
-            return CUDPP_SUCCESS;
+        // the maximal runs [a, b) of wanted blocks of kind K: more(a, b) = block b may still join the run that starts at a
+        auto of_kind = [&](uint32_t K, auto more) {
+            return [&want, kind, K, more](uint32_t a, uint32_t b) { return kind[b] == K && want(b) && more(a, b); };
         };
         auto in_rows = [&](uint32_t a, uint32_t b) { return b - a < P.rows; };
         auto in_chunk = [&](uint32_t a, uint32_t b) { return b - a < h0.chunk; };        // a chunk of the plan's rows at a time
         auto same_chunk = [&](uint32_t a, uint32_t b) { return b / h0.chunk == a / h0.chunk; };
         const unsigned long long *pay_off = reinterpret_cast<const unsigned long long *>(W + T.pay_off);
-        CUDPPResult r = runs_of(CT_KIND_HUFF, in_rows, [&](uint32_t a, uint32_t cnt) {
+        r = for_runs(nb, of_kind(CT_KIND_HUFF, in_rows), [&](uint32_t a, uint32_t cnt) {
             return glcDecompressBatchCompact(P.h, reinterpret_cast<const int *>(W + T.bwt) + a, W + T.hist + 256ull * a,
                                              W + T.enc_off + (size_t)T.nsub * a, T.nsub, pay, pw, pay_off + a, out + (size_t)a * blk_len,
                                              blk_len, cnt);
         });
         if (r != CUDPP_SUCCESS) return r;
-        if (k2) r = runs_of(CT_KIND_HUFF0, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+        if (k2) r = for_runs(nb, of_kind(CT_KIND_HUFF0, in_chunk), [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
             // (k_cd_raw has put every block's output range into f.seg_*: absolute addresses, so the base is null)
             const HdbOut g{nullptr, f.seg_off + a, f.seg_len + a, cnt, blk_len};
             CT_TRY(hdb_decode(P.st, pay, pay_off + a, h0.nun + a, h0.lut + 2048ull * a, g, nullptr, h0.work, prof));
@@ -839,7 +816,7 @@ struct Decoder {
         });
         if (r != CUDPP_SUCCESS) return r;
         // sparse blocks: K decoded into scratch, then expanded
-        if (fmt.kind3_legal()) r = runs_of(CT_KIND_SPARSE, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+        if (fmt.kind3_legal()) r = for_runs(nb, of_kind(CT_KIND_SPARSE, in_chunk), [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
             const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len};
             CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
             const SpSegs s{nullptr, f.seg_off + a, f.seg_len + a, nullptr, h0.k_off + a, W + T.bwt + a, const_cast<uint32_t *>(pay),
@@ -849,7 +826,7 @@ struct Decoder {
         });
         if (r != CUDPP_SUCCESS) return r;
         // rANS blocks: their tables from the histograms, then one pass
-        if (fmt.kind5_legal()) r = runs_of(CT_KIND_ANS, in_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+        if (fmt.kind5_legal()) r = for_runs(nb, of_kind(CT_KIND_ANS, in_chunk), [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
             const AnsSegs g{nullptr, f.seg_off + a, f.seg_len + a, W + T.hist + 256ull * a, h0.ans_tab, nullptr, cnt, blk_len};
             CT_TRY(ans_tables(P.st, g));
             CT_TRY(ans_decode(P.st, g, pay, pay_off + a, nullptr));
@@ -858,7 +835,7 @@ struct Decoder {
         if (r != CUDPP_SUCCESS) return r;
         // zero-run blocks inside one chunk of the decoder: A and B decoded into scratch, joined into the rows b % chunk of the
         // decoder's MTF bytes, and from there the BWT codec's own inverse MTF and inverse BWT
-        if (fmt.kind4_legal()) r = runs_of(CT_KIND_RUNS, same_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+        if (fmt.kind4_legal()) r = for_runs(nb, of_kind(CT_KIND_RUNS, same_chunk), [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
             const HdbOut ga{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len}, gb{nullptr, h0.b_off + a, h0.b_len + a, cnt, blk_len};
             CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, ga, h0.skip3 + a, h0.work, prof));
             CT_TRY(hdb_decode(P.st, pay, h0.ub_off + a, h0.nun_b + a, h0.lut_b + 2048ull * a, gb, h0.skip_b + a, h0.work, prof));
@@ -872,8 +849,9 @@ struct Decoder {
         // dedup blocks inside one chunk of the decoder: K decoded into scratch and put back under the mask (widened to 64-byte
         // chunks for the sparse mode's join, which leaves its fill byte in the elided chunks until the fill pass)
         if (fmt.kind6_legal()) {
-            CT_TRY(runs([&](uint32_t a, uint32_t cnt) { return ct_dec_dedup_expand(P.st, fr, nb, blk_len, a, cnt, dd, false); }));
-            r = runs_of(CT_KIND_DEDUP, same_chunk, [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
+            r = for_runs(nb, wanted, [&](uint32_t a, uint32_t cnt) { return hip_result(ct_dec_dedup_expand(P.st, fr, nb, blk_len, a, cnt, dd, false)); });
+            if (r != CUDPP_SUCCESS) return r;
+            r = for_runs(nb, of_kind(CT_KIND_DEDUP, same_chunk), [&](uint32_t a, uint32_t cnt) -> CUDPPResult {
                 const HdbOut g{nullptr, h0.k_off + a, h0.k_len + a, cnt, blk_len};
                 CT_TRY(hdb_decode(P.st, pay, h0.u_off + a, h0.nun + a, h0.lut + 2048ull * a, g, h0.skip3 + a, h0.work, prof));
                 CT_TRY(ct_dec_dedup_expand(P.st, fr, nb, blk_len, a, cnt, dd, true));
@@ -887,25 +865,15 @@ struct Decoder {
         plan_join(P.h);
         // the fill: behind every join of the frame, in front of the decoded-CRC pass; sources are kept chunks, so one pass completes
         // the frame.  Only the blocks that are checked are filled.
-        auto runs_checked = [&](auto call) -> hipError_t {
-            for (uint32_t a = 0; a < nb;) {
-                if (!checked(a)) { a++; continue; }
-                uint32_t b = a;
-                while (b < nb && checked(b)) b++;
-                const hipError_t e = call(a, b - a);
-                if (e != hipSuccess) return e;
-                a = b;
-            }
-            return hipSuccess;
-        };
         if (fmt.kind6_legal()) {
             const DdSegs g{nullptr, f.seg_off, f.seg_len, nullptr, nullptr, 0, dd.src, nb, blk_len, (blk_len + DD_CHUNK - 1) / DD_CHUNK};
-            CT_TRY(runs_checked([&](uint32_t a, uint32_t cnt) { return dedup_fill(P.st, g, a, cnt); }));
+            r = for_runs(nb, to_check, [&](uint32_t a, uint32_t cnt) { return hip_result(dedup_fill(P.st, g, a, cnt)); });
+            if (r != CUDPP_SUCCESS) return r;
         }
-        if (need) {
-            CT_TRY(runs_checked([&](uint32_t a, uint32_t cnt) { return ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt); }));
-            return CUDPP_SUCCESS;
-        }
+        if (need)
+            return for_runs(nb, to_check, [&](uint32_t a, uint32_t cnt) {
+                return hip_result(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, false, a, cnt));
+            });
         CT_TRY(ct_dec_check(P.st, f, fr, nb, blk_len, out, fi, state, !ff.filtered()));
         if (ff.filtered()) {
             CT_TRY(filter_device(P.st, ff, out, final_out, (unsigned long long)nb * blk_len, true));
@@ -1053,10 +1021,7 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     if (!out.write(hout.p, CT_TRAILER)) return fail(plan, CT_CAPACITY);
     total += CT_TRAILER;
     if (outLen) *outLen = total;
-    set_choice(plan, E.choice);
-    set_filters(plan, E.filters);
-    set_error(plan, CT_OK);
-    return CUDPP_SUCCESS;
+    return E.succeeded();
 }
 
 // -------------------------------------------------------------------------------------------------------------------------
@@ -1097,7 +1062,7 @@ CUDPPResult decode_walk(Decoder &D, Feed &feed, unsigned long long len, unsigned
             D.fmt = fmt;
             *total = tot;
             if (tot > cap) r = fail(plan, CT_CAPACITY);
-            else r = hip_res(D.begin());
+            else r = hip_result(D.begin());
             return r == CUDPP_SUCCESS;
         },
         [&](uint32_t fi, const uint32_t *fh, const CtFrameRef &F) {
@@ -1360,19 +1325,15 @@ std::vector<uint8_t> needed_blocks(const CtFormat &fmt, uint32_t nb, uint32_t bl
     return need;
 }
 
-struct RangeStats { unsigned long long v[3] = {0, 0, 0}; };
-std::map<CUDPPHandle, RangeStats> g_range_stats;               // (under g_err_mu)
-
 CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, unsigned long long len, unsigned long long offset,
                        unsigned long long count)
 {
     const CUDPPHandle plan = D.P.h;
     if (!ix || len != ix->len || offset > ix->total || count > ix->total - offset) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    RangeStats stats;
+    unsigned long long stats[3] = {0, 0, 0};                    // frames, blocks decoded, container bytes fetched
     auto done = [&]() {
         set_error(plan, CT_OK);
-        std::lock_guard<std::mutex> g(g_err_mu);
-        g_range_stats[plan] = stats;
+        memcpy(plan_container_reports(plan).range, stats, sizeof stats);
         return CUDPP_SUCCESS;
     };
     if (count == 0) return done();
@@ -1380,7 +1341,7 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
     if (io.small(hdr, 0, CT_HDR) != CUDPP_SUCCESS) return fail(plan, CT_TRUNCATED);
     if (memcmp(hdr, ix->hdr, CT_HDR) != 0) return fail(plan, CT_STREAM_HEADER);           // another container than the index's
     if (ix->fmt.reads() && !(plan_container_settings(plan).reader() & ix->fmt.reads())) return fail(plan, CT_STREAM_HEADER);
-    stats.v[2] = CT_HDR;
+    stats[2] = CT_HDR;
     D.fmt = ix->fmt;
     CT_TRY(D.begin());
     const unsigned long long end = offset + count;
@@ -1408,9 +1369,9 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         unsigned long long i0 = 0, i1 = 0;
         const std::vector<uint8_t> need = needed_blocks(ff, F.nb, F.bl, a, b, &i0, &i1);
         uint8_t *stage = nullptr;
-        if ((r = D.frame(fr, F.nb, F.bl, F.pw, F.filter, nullptr, (uint32_t)fi, need.data(), &stage, &stats.v[1])) != CUDPP_SUCCESS) return r;
-        stats.v[0] += 1;
-        stats.v[2] += fb;
+        if ((r = D.frame(fr, F.nb, F.bl, F.pw, F.filter, nullptr, (uint32_t)fi, need.data(), &stage, &stats[1])) != CUDPP_SUCCESS) return r;
+        stats[0] += 1;
+        stats[2] += fb;
         const unsigned long long at = F.out_off - offset;       // (+ a frame byte = its place in the range; never negative there)
         if (!ff.filtered()) {
             if ((r = io.deliver(stage + a, b - a, at + a)) != CUDPP_SUCCESS) return r;
@@ -1434,17 +1395,37 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
     return done();
 }
 
-CUDPPResult range_filter_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
-                             unsigned long long count, void *stream, bool delta)
+// the four glcContainerLast* entries: n values of the plan's reports.  Two of them (loose) tell only a bad handle: a live plan that
+// is not a COMPRESS plan has no container call behind it, so they answer it with the values no call has touched.
+template <class Pick>
+CUDPPResult last_report(CUDPPHandle plan, bool loose, unsigned long long *out, size_t n, Pick pick)
 {
-    if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const unsigned long long q = len / elem;
-    if (first > q || count > q - first || (delta && first % 2048)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
-    if (!d_in || !d_out || (a < b + count * elem && b < a + len)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res((delta ? undelta_unshuffle_range_device : unshuffle_range_device)(
-        reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out), q, elem, first, count));
+    Plan P;
+    const CUDPPResult bad = P.check(plan);
+    if (bad == CUDPP_ERROR_INVALID_HANDLE || (bad && !loose)) return bad;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const CtReports untouched;
+    memcpy(out, pick(bad ? untouched : plan_container_reports(plan)), n * sizeof *out);
+    return CUDPP_SUCCESS;
+}
+
+// the glcPlanSet/GetContainer* entries: the plan check, then the setter's own rule (CtSettings: false = refused, nothing changed);
+// the plan check, then the null-output check, then the read
+template <class Set>
+CUDPPResult ct_set(CUDPPHandle plan, Set set)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    return set(plan_container_settings(plan)) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+}
+template <class Get>
+CUDPPResult ct_get(CUDPPHandle plan, unsigned int *out, Get get)
+{
+    Plan P;
+    if (const CUDPPResult bad = P.check(plan)) return bad;
+    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *out = get(plan_container_settings(plan));
+    return CUDPP_SUCCESS;
 }
 
 } // namespace
@@ -1544,28 +1525,6 @@ CUDPPResult glcContainerReadRangeFile(CUDPPHandle plan, const GlcContainerIndex 
     return read_range(D, index, io, src.len, offset, count);
 }
 
-CUDPPResult glcContainerLastRangeStats(CUDPPHandle plan, unsigned long long out[3])
-{
-    if (plan == 0 || plan == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    std::lock_guard<std::mutex> g(g_err_mu);
-    const RangeStats s = g_range_stats.count(plan) ? g_range_stats[plan] : RangeStats();
-    for (int i = 0; i < 3; i++) out[i] = s.v[i];
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
-                                    unsigned long long count, void *stream)
-{
-    return range_filter_api(d_in, d_out, len, elem, first, count, stream, false);
-}
-
-CUDPPResult glcUndeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
-                                           unsigned long long first, unsigned long long count, void *stream)
-{
-    return range_filter_api(d_in, d_out, len, elem, first, count, stream, true);
-}
-
 unsigned long long glcContainerBound(unsigned long long len, size_t blockLen)
 {
     if (blockLen == 0 || blockLen > MAX_BLOCK_ELEMS) return 0;
@@ -1592,10 +1551,7 @@ CUDPPResult glcContainerCompressDevice(CUDPPHandle plan, const void *d_in, unsig
     CT_TRY(hipMemcpyAsync(&total, d_outLen, 8, hipMemcpyDeviceToHost, E.P.st));
     CT_TRY(hipStreamSynchronize(E.P.st));
     if (total > cap) return fail(plan, CT_CAPACITY);
-    set_choice(plan, E.choice);
-    set_filters(plan, E.filters);
-    set_error(plan, CT_OK);
-    return CUDPP_SUCCESS;
+    return E.succeeded();
 }
 
 CUDPPResult glcContainerDecompressDevice(CUDPPHandle plan, const void *d_in, unsigned long long len, void *d_out,
@@ -1641,476 +1597,114 @@ CUDPPResult glcContainerDecompressFile(CUDPPHandle plan, const char *inPath, con
     return with_files(inPath, outPath, [&](Source &s, unsigned long long len, Sink &k) { return decompress_stream(plan, s, len, k, ~0ull, nullptr); });
 }
 
-CUDPPResult glcCrc32Segments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                             size_t count, unsigned int *d_crc, void *stream)
+CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3])
 {
-    if (count == 0) return CUDPP_SUCCESS;
-    if (!d_offsets || !d_lengths || !d_crc || count > 0xFFFFFFFFull) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res(crc32_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_base), d_offsets,
-                                  d_lengths, (uint32_t)count, d_crc));
+    return last_report(plan, true, out, 3, [](const CtReports &r) { return r.error; });
 }
 
-static CUDPPResult shuffle_segments_api(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
-                                        const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream, bool inverse)
+CUDPPResult glcContainerLastRangeStats(CUDPPHandle plan, unsigned long long out[3])
 {
-    // (one offset serves both bases, so equal bases are the in-place call; what else might overlap is in device memory)
-    if (!shuffle_elem_ok(elem) || count > 0xFFFFFFFFull) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    if (!d_inBase || !d_outBase || d_inBase == d_outBase || !d_offsets || !d_lengths) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res(shuffle_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase),
-                                    static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, (uint32_t)count, elem, inverse));
-}
-
-static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse,
-                                      bool delta = false)
-{
-    CtFormat f;                                               // (only its filter matters here)
-    f.flags = delta ? CT_FLAG_DELTA : 0; f.elem = elem;
-    if (!shuffle_elem_ok(elem)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (len == 0) return CUDPP_SUCCESS;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
-    if (!d_in || !d_out || (a < b ? b - a : a - b) < len) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    return hip_res(filter_device(reinterpret_cast<hipStream_t>(stream), f, static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out),
-                                 len, inverse));
-}
-
-CUDPPResult glcShuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
-                               const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream)
-{
-    return shuffle_segments_api(d_inBase, d_outBase, d_offsets, d_lengths, count, elem, stream, false);
-}
-
-CUDPPResult glcUnshuffleSegments(const void *d_inBase, void *d_outBase, const unsigned long long *d_offsets,
-                                 const unsigned long long *d_lengths, size_t count, unsigned int elem, void *stream)
-{
-    return shuffle_segments_api(d_inBase, d_outBase, d_offsets, d_lengths, count, elem, stream, true);
-}
-
-// the two sparse calls: a bad argument is refused before anything is enqueued
-static bool sparse_args_ok(const void *a, const void *b, const void *c, const void *d, const void *e, const void *f, size_t count, size_t maxLen)
-{
-    return count <= 0xFFFFFFFFull && maxLen <= GLC_SPARSE_MAX_LEN && (count == 0 || (a && b && c && d && e && f));
-}
-
-CUDPPResult glcSparseSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                   size_t count, size_t maxLen, const unsigned int *d_fill, unsigned int *d_mask, void *d_keptBase,
-                                   unsigned long long *d_keptLen, void *stream)
-{
-    if (!sparse_args_ok(d_inBase, d_offsets, d_lengths, d_fill, d_mask, d_keptBase, count, maxLen) || (count && !d_keptLen) ||
-        (count && d_inBase == d_keptBase) || (reinterpret_cast<uintptr_t>(d_mask) & 3))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const SpSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, static_cast<uint8_t *>(d_keptBase), d_offsets,
-                   d_fill, d_mask, nullptr, sp_mask_words((uint32_t)maxLen), nullptr, (uint32_t)count, (uint32_t)maxLen};
-    CT_TRY(sparse_mask(st, g));
-    CT_TRY(sparse_count(st, g, d_keptLen));
-    CT_TRY(sparse_compact(st, g));
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcSparseJoinSegments(const void *d_keptBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                  size_t count, size_t maxLen, const unsigned int *d_fill, const unsigned int *d_mask, void *d_outBase,
-                                  void *stream)
-{
-    if (!sparse_args_ok(d_keptBase, d_offsets, d_lengths, d_fill, d_mask, d_outBase, count, maxLen) || (count && d_keptBase == d_outBase) ||
-        (reinterpret_cast<uintptr_t>(d_mask) & 3))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    const SpSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, static_cast<uint8_t *>(const_cast<void *>(d_keptBase)), d_offsets,
-                   d_fill, const_cast<unsigned int *>(d_mask), nullptr, sp_mask_words((uint32_t)maxLen), nullptr, (uint32_t)count,
-                   (uint32_t)maxLen};
-    CT_TRY(sparse_join(reinterpret_cast<hipStream_t>(stream), g));
-    return CUDPP_SUCCESS;
-}
-
-// the dedup calls: a bad argument is refused before anything is enqueued
-static size_t dedup_chunks(size_t count, size_t maxLen)
-{
-    if (count > GLC_DEDUP_MAX_COUNT || maxLen > GLC_DEDUP_MAX_LEN) return (size_t)-1;
-    const size_t chunks = count * ((maxLen + DD_CHUNK - 1) / DD_CHUNK);
-    return chunks > DD_MAX_CHUNKS ? (size_t)-1 : chunks;
-}
-
-size_t glcDedupWorkBytes(size_t count, size_t maxLen)
-{
-    const size_t chunks = dedup_chunks(count, maxLen);
-    if (chunks == (size_t)-1 || chunks == 0) return 0;
-    return (dedup_slots(chunks) + 1) * sizeof(DdSlot) + chunks * sizeof(uint64_t);
-}
-
-CUDPPResult glcDedupMapSegments(const void *d_base, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
-                                size_t maxLen, unsigned int *d_src, void *d_work, size_t workBytes, void *stream)
-{
-    const size_t chunks = dedup_chunks(count, maxLen);
-    if (chunks == (size_t)-1) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (chunks == 0) return CUDPP_SUCCESS;
-    if (!d_base || !d_offsets || !d_lengths || !d_src || !d_work || (reinterpret_cast<uintptr_t>(d_src) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_work) & 15) || workBytes < glcDedupWorkBytes(count, maxLen))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const size_t slots = dedup_slots(chunks);
-    DdSlot *table = static_cast<DdSlot *>(d_work);
-    const DdSegs g{static_cast<uint8_t *>(const_cast<void *>(d_base)), d_offsets, d_lengths, reinterpret_cast<uint64_t *>(table + slots + 1),
-                   table, (uint32_t)slots, d_src, (uint32_t)count, (uint32_t)maxLen, (uint32_t)((maxLen + DD_CHUNK - 1) / DD_CHUNK)};
-    CT_TRY(dedup_map(reinterpret_cast<hipStream_t>(stream), g));
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcDedupFillSegments(void *d_outBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths, size_t count,
-                                 size_t maxLen, const unsigned int *d_src, void *stream)
-{
-    const size_t chunks = dedup_chunks(count, maxLen);
-    if (chunks == (size_t)-1) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (chunks == 0) return CUDPP_SUCCESS;
-    if (!d_outBase || !d_offsets || !d_lengths || !d_src || (reinterpret_cast<uintptr_t>(d_src) & 3)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const DdSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, nullptr, nullptr, 0, const_cast<unsigned int *>(d_src),
-                   (uint32_t)count, (uint32_t)maxLen, (uint32_t)((maxLen + DD_CHUNK - 1) / DD_CHUNK)};
-    CT_TRY(dedup_fill(reinterpret_cast<hipStream_t>(stream), g));
-    return CUDPP_SUCCESS;
-}
-
-// the two zero-run calls: a bad argument is refused before anything is enqueued
-static bool zrun_args_ok(const void *x, const void *off, const void *len, const void *a, const void *b, const void *alen, const void *blen,
-                         size_t count, size_t maxLen)
-{
-    return count <= 0xFFFFFFFFull && maxLen <= GLC_ZERORUN_MAX_LEN && (count == 0 || (x && off && len && a && b && alen && blen)) &&
-           (count == 0 || (x != a && x != b && a != b));
-}
-
-CUDPPResult glcZeroRunSplitSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                    size_t count, size_t maxLen, void *d_aBase, void *d_bBase, unsigned long long *d_aLen,
-                                    unsigned long long *d_bLen, void *stream)
-{
-    if (!zrun_args_ok(d_inBase, d_offsets, d_lengths, d_aBase, d_bBase, d_aLen, d_bLen, count, maxLen)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    const ZrSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, static_cast<uint8_t *>(d_aBase), d_offsets, d_aLen,
-                   static_cast<uint8_t *>(d_bBase), d_offsets, d_bLen, nullptr, (uint32_t)count, (uint32_t)maxLen};
-    CT_TRY(zrun_split(reinterpret_cast<hipStream_t>(stream), g));
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcZeroRunJoinSegments(const void *d_aBase, const void *d_bBase, const unsigned long long *d_offsets,
-                                   const unsigned long long *d_aLen, const unsigned long long *d_bLen, const unsigned long long *d_lengths,
-                                   size_t count, size_t maxLen, void *d_outBase, void *stream)
-{
-    if (!zrun_args_ok(d_outBase, d_offsets, d_lengths, d_aBase, d_bBase, d_aLen, d_bLen, count, maxLen)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    const ZrSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, static_cast<uint8_t *>(const_cast<void *>(d_aBase)), d_offsets,
-                   const_cast<unsigned long long *>(d_aLen), static_cast<uint8_t *>(const_cast<void *>(d_bBase)), d_offsets,
-                   const_cast<unsigned long long *>(d_bLen), nullptr, (uint32_t)count, (uint32_t)maxLen};
-    CT_TRY(zrun_join(reinterpret_cast<hipStream_t>(stream), g));
-    return CUDPP_SUCCESS;
-}
-
-// the two rANS calls: a bad argument is refused before anything is enqueued.  The work space: the tables, what the batched
-// histogram kernel's table step writes beside them, and the encoder's chunk slots
-struct AnsWork {
-    uint8_t *tab, *lens; uint16_t *codes; unsigned long long *nun; AnsScratch sc;
-    size_t carve(void *base, size_t count, size_t maxLen)
-    {
-        Carver c(base);
-        const size_t nch = ans_chunks((uint32_t)maxLen), slots = count * nch;
-        c.align(256);
-        tab = c.take<uint8_t>(count * ANS_TAB_BYTES);
-        nun = c.take<unsigned long long>(count);
-        sc.states = c.take<uint32_t>(slots * ANS_LANES);
-        sc.counts = c.take<uint32_t>(slots);
-        codes = c.take<uint16_t>(256 * count);
-        lens = c.take<uint8_t>(256 * count);
-        c.align(256);
-        sc.units = c.take<uint16_t>(slots * ANS_CHUNK);
-        sc.nch_max = (uint32_t)nch;
-        return c.bytes();
-    }
-};
-
-size_t glcAnsBoundWords(size_t len) { return len > GLC_ANS_MAX_LEN ? 0 : (size_t)ans_bound_words((uint32_t)len); }
-
-size_t glcAnsSegmentsWorkBytes(size_t count, size_t maxLen)
-{
-    if (count > GLC_ANS_MAX_COUNT || maxLen > GLC_ANS_MAX_LEN) return 0;
-    AnsWork w;
-    return w.carve(nullptr, count, maxLen);
-}
-
-static bool ans_args_ok(const void *data, const void *off, const void *len, const void *hist, const void *rec, const void *recOff,
-                        const void *recWords, const void *work, size_t workBytes, size_t count, size_t maxLen)
-{
-    if (count > GLC_ANS_MAX_COUNT || maxLen > GLC_ANS_MAX_LEN) return false;
-    if (count == 0) return true;
-    return data && off && len && hist && rec && recOff && recWords && work && data != rec && (reinterpret_cast<uintptr_t>(rec) & 3) == 0 &&
-           (reinterpret_cast<uintptr_t>(hist) & 3) == 0 && workBytes >= glcAnsSegmentsWorkBytes(count, maxLen);
-}
-
-CUDPPResult glcAnsEncodeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                 size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_recBase,
-                                 const unsigned long long *d_recOffsets, unsigned long long *d_recWords, void *d_work, size_t workBytes,
-                                 void *stream)
-{
-    if (!ans_args_ok(d_inBase, d_offsets, d_lengths, d_hist, d_recBase, d_recOffsets, d_recWords, d_work, workBytes, count, maxLen))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    AnsWork w;
-    (void)w.carve(d_work, count, maxLen);
-    const HdbSegs h{static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count, (uint32_t)maxLen};
-    CT_TRY(hdb_tables(st, h, true, d_hist, w.lens, w.codes, nullptr, w.nun, nullptr, nullptr));
-    const AnsSegs g{static_cast<uint8_t *>(const_cast<void *>(d_inBase)), d_offsets, d_lengths, d_hist, w.tab, nullptr, (uint32_t)count,
-                    (uint32_t)maxLen};
-    CT_TRY(ans_tables(st, g));
-    CT_TRY(ans_encode(st, g, w.sc));
-    CT_TRY(ans_words(st, g, w.sc, d_recWords));
-    CT_TRY(ans_place(st, g, w.sc, d_recBase, d_recOffsets, ~0ull));
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcAnsDecodeSegments(const unsigned int *d_recBase, const unsigned long long *d_recOffsets, const unsigned long long *d_recWords,
-                                 const unsigned int *d_hist, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                 size_t count, size_t maxLen, void *d_outBase, void *d_work, size_t workBytes, void *stream)
-{
-    if (!ans_args_ok(d_outBase, d_offsets, d_lengths, d_hist, d_recBase, d_recOffsets, d_recWords, d_work, workBytes, count, maxLen))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    AnsWork w;
-    (void)w.carve(d_work, count, maxLen);
-    const AnsSegs g{static_cast<uint8_t *>(d_outBase), d_offsets, d_lengths, d_hist, w.tab, nullptr, (uint32_t)count, (uint32_t)maxLen};
-    CT_TRY(ans_tables(st, g));
-    CT_TRY(ans_decode(st, g, d_recBase, d_recOffsets, d_recWords));
-    return CUDPP_SUCCESS;
-}
-
-// the probe: a bad argument is refused before anything is enqueued
-CUDPPResult glcProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                             size_t count, size_t maxLen, unsigned int *d_hist, unsigned int *d_uniform, void *stream)
-{
-    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    if (!d_inBase || !d_offsets || !d_lengths || !d_hist || !d_uniform || d_hist == d_uniform || (reinterpret_cast<uintptr_t>(d_hist) & 3) ||
-        (reinterpret_cast<uintptr_t>(d_uniform) & 3)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    CT_TRY(probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
-                          (uint32_t)maxLen, d_hist, d_uniform));
-    return CUDPP_SUCCESS;
-}
-
-// the bigram probe: a bad argument is refused before anything is enqueued
-CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                   size_t count, size_t maxLen, unsigned long long *d_stats, void *stream)
-{
-    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    if (!d_inBase || !d_offsets || !d_lengths || !d_stats || (reinterpret_cast<uintptr_t>(d_stats) & 7)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    CT_TRY(bigram_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
-                                 (uint32_t)count, (uint32_t)maxLen, d_stats));
-    return CUDPP_SUCCESS;
-}
-
-// the filter probe: a bad argument is refused before anything is enqueued
-CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
-                                   size_t count, size_t maxLen, unsigned int *d_planes, unsigned long long *d_costs, void *stream)
-{
-    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_FILTER_PROBE_MAX_LEN) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (count == 0) return CUDPP_SUCCESS;
-    if (!d_inBase || !d_offsets || !d_lengths || !d_planes || !d_costs || (reinterpret_cast<uintptr_t>(d_planes) & 15) ||
-        (reinterpret_cast<uintptr_t>(d_costs) & 7) || static_cast<void *>(d_planes) == static_cast<void *>(d_costs))
-        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    CT_TRY(filter_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
-                                 (uint32_t)count, (uint32_t)maxLen, d_planes, d_costs));
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8])
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const unsigned long long *c = plan_container_filters(plan);
-    for (uint32_t i = 0; i <= FILTER_CANDS; i++) out[i] = c[i];
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_filter_auto(on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-}
-
-CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).filter_auto ? 1u : 0u;
-    return CUDPP_SUCCESS;
+    return last_report(plan, true, out, 3, [](const CtReports &r) { return r.range; });
 }
 
 CUDPPResult glcContainerLastChoice(CUDPPHandle plan, unsigned long long out[3])
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    const unsigned long long *c = plan_container_choice(plan);
-    for (int i = 0; i < 3; i++) out[i] = c[i];
-    return CUDPP_SUCCESS;
+    return last_report(plan, false, out, 3, [](const CtReports &r) { return r.choice; });
 }
 
-CUDPPResult glcShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
+CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8])
 {
-    return shuffle_device_api(d_in, d_out, len, elem, stream, false);
-}
-
-CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
-{
-    return shuffle_device_api(d_in, d_out, len, elem, stream, true);
-}
-
-CUDPPResult glcDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
-{
-    return shuffle_device_api(d_in, d_out, len, elem, stream, false, true);
-}
-
-CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream)
-{
-    return shuffle_device_api(d_in, d_out, len, elem, stream, true, true);
+    return last_report(plan, false, out, FILTER_CANDS + 1, [](const CtReports &r) { return r.filters; });
 }
 
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_shuffle(elem) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_shuffle(elem); });
 }
 
 CUDPPResult glcPlanSetContainerDelta(CUDPPHandle plan, unsigned int on)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_delta(on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_delta(on); });
 }
 
 CUDPPResult glcPlanSetContainerCodec(CUDPPHandle plan, unsigned int codec)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_codec(codec) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_codec(codec); });
 }
 
 CUDPPResult glcPlanSetContainerSparse(CUDPPHandle plan, unsigned int on)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_mode(CT_MODE_SPARSE, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-}
-
-CUDPPResult glcPlanSetContainerDedup(CUDPPHandle plan, unsigned int on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_mode(CT_MODE_DEDUP, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-}
-
-CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).mode == CT_MODE_DEDUP ? 1u : 0u;
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_mode(CT_MODE_ANS, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-}
-
-CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_mode(CT_MODE_AUTO, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-}
-
-CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).mode == CT_MODE_AUTO ? 1u : 0u;
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).mode == CT_MODE_ANS ? 1u : 0u;
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!elem) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *elem = plan_container_settings(plan).shuffle;
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).delta ? 1u : 0u;
-    return CUDPP_SUCCESS;
-}
-
-CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
-{
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!codec) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *codec = plan_container_settings(plan).codec;
-    return CUDPP_SUCCESS;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_mode(CT_MODE_SPARSE, on); });
 }
 
 CUDPPResult glcPlanSetContainerRuns(CUDPPHandle plan, unsigned int on)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    return plan_container_settings(plan).set_mode(CT_MODE_RUNS, on) ? CUDPP_SUCCESS : CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_mode(CT_MODE_RUNS, on); });
 }
 
-CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on)
+CUDPPResult glcPlanSetContainerAns(CUDPPHandle plan, unsigned int on)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).mode == CT_MODE_RUNS ? 1u : 0u;
-    return CUDPP_SUCCESS;
+    return ct_set(plan, [&](CtSettings &s) { return s.set_mode(CT_MODE_ANS, on); });
+}
+
+CUDPPResult glcPlanSetContainerAuto(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_mode(CT_MODE_AUTO, on); });
+}
+
+CUDPPResult glcPlanSetContainerDedup(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_mode(CT_MODE_DEDUP, on); });
+}
+
+CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_filter_auto(on); });
+}
+
+CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
+{
+    return ct_get(plan, elem, [](const CtSettings &s) { return s.shuffle; });
+}
+
+CUDPPResult glcPlanGetContainerDelta(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.delta ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerCodec(CUDPPHandle plan, unsigned int *codec)
+{
+    return ct_get(plan, codec, [](const CtSettings &s) { return s.codec; });
 }
 
 CUDPPResult glcPlanGetContainerSparse(CUDPPHandle plan, unsigned int *on)
 {
-    Plan P;
-    if (const CUDPPResult bad = P.check(plan)) return bad;
-    if (!on) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    *on = plan_container_settings(plan).mode == CT_MODE_SPARSE ? 1u : 0u;
-    return CUDPP_SUCCESS;
+    return ct_get(plan, on, [](const CtSettings &s) { return s.mode == CT_MODE_SPARSE ? 1u : 0u; });
 }
 
-CUDPPResult glcContainerLastError(CUDPPHandle plan, unsigned long long out[3])
+CUDPPResult glcPlanGetContainerRuns(CUDPPHandle plan, unsigned int *on)
 {
-    if (plan == 0 || plan == CUDPP_INVALID_HANDLE) return CUDPP_ERROR_INVALID_HANDLE;
-    if (!out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    std::lock_guard<std::mutex> g(g_err_mu);
-    const LastError e = g_err.count(plan) ? g_err[plan] : LastError();
-    for (int i = 0; i < 3; i++) out[i] = e.v[i];
-    return CUDPP_SUCCESS;
+    return ct_get(plan, on, [](const CtSettings &s) { return s.mode == CT_MODE_RUNS ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerAns(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.mode == CT_MODE_ANS ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerAuto(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.mode == CT_MODE_AUTO ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.mode == CT_MODE_DEDUP ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.filter_auto ? 1u : 0u; });
 }
 
 } // extern "C"

@@ -1,11 +1,13 @@
-// container_internal.h -- shared by container.hip (kernels) and container_api.cpp (host side of include/glc_container.h):
-// the CRC-32 algebra, the BWT container's layout and the plan hooks cudpp_api.cpp exports to it.
+// container_internal.h -- shared by container.hip (kernels), container_api.cpp and segments_api.cpp (host side of
+// include/glc_container.h: the container over a plan, and the plan-less segment calls): the CRC-32 algebra, the BWT container's
+// layout and the plan hooks cudpp_api.cpp exports to it.
 #pragma once
 #include "../../include/cudpp.h"
 #include "glc_internal.h"
 #include "ans_coder.h"
 #include "auto_rule.h"
 #include "choose_rule.h"
+#include "filter_rule.h"
 
 #include <functional>
 
@@ -95,6 +97,21 @@ hipError_t unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *ou
                                   unsigned long long first, unsigned long long count);
 hipError_t undelta_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
                                           unsigned long long first, unsigned long long count);
+
+// Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
+// the allocation it places, so the size and the pointers cannot disagree.
+struct Carver {
+    uint8_t *base;
+    size_t off = 0;
+    explicit Carver(void *b = nullptr) : base(static_cast<uint8_t *>(b)) {}
+    template <class T> T *take(size_t count) { T *p = reinterpret_cast<T *>(base + off); off += count * sizeof(T); return base ? p : nullptr; }
+    void round(size_t a) { off = (off + a - 1) & ~(a - 1); }      // the offset (the base is at least as aligned)
+    void align(size_t a)                                          // the address; measuring counts the worst case
+    {
+        off = base ? (size_t)(((reinterpret_cast<uintptr_t>(base) + off + a - 1) & ~(uintptr_t)(a - 1)) - reinterpret_cast<uintptr_t>(base)) : off + a;
+    }
+    size_t bytes() const { return off; }
+};
 
 // the sparse passes (sparse.hip).  Segment i is `data` + data_off[i], min(data_len[i], max_len) bytes, cut into chunks of 64; its
 // mask (bit c % 32 of word c / 32 = chunk c is kept, i.e. not all fill[i] & 255) is at mask + (mask_off ? mask_off[i] : i *
@@ -252,6 +269,11 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
     CtFormat f = stream;
     if (stream.version == CT_VERSION_FILTER) { f.elem = word & 0xFFFFu; f.flags = word >> 16; }
     return f;
+}
+// a format's filter over one segment, or its inverse
+inline hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
+{
+    return (f.delta() ? delta_shuffle_device : shuffle_device)(st, in, out, len, f.elem, inverse);
 }
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
@@ -520,10 +542,14 @@ inline CtFormat format_of(const CtSettings &s)
     return f;                                                 // (the setters accept only what some row takes)
 }
 CtSettings &plan_container_settings(CUDPPHandle plan);
-// {blocks given to the BWT codec, blocks given to the order-0 codec, frames} of the plan's last successful container compress
-unsigned long long *plan_container_choice(CUDPPHandle plan);
-// frames per candidate of filter_rule.h (seven), then all frames, of the plan's last successful container compress
-unsigned long long *plan_container_filters(CUDPPHandle plan);
+// what the glcContainerLast* entries report, kept with the plan and gone with it
+struct CtReports {
+    unsigned long long error[3] = {0, ~0ull, ~0ull};       // {CtWhat, frame, block} of the last container call (~0 = none)
+    unsigned long long range[3] = {};                      // {frames, blocks decoded, container bytes fetched} of the last successful range read
+    unsigned long long choice[3] = {};                     // {blocks given to the BWT codec, to the order-0 codec, frames} of the last successful compress
+    unsigned long long filters[FILTER_CANDS + 1] = {};     // frames per candidate of filter_rule.h, then all frames, of the last successful compress
+};
+CtReports &plan_container_reports(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
 // call parity, decoder: buffer 0)
 bool plan_pipelined(CUDPPHandle plan);

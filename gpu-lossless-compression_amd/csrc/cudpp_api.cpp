@@ -126,8 +126,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     bool side_busy = false;                      // side-stream work issued since the last join
     // container settings (glcPlanSetContainerShuffle / Delta / Codec / Sparse / Runs / Ans) and the filter's frame staging both directions share
     CtSettings ct;
-    unsigned long long ct_choice[3] = {0, 0, 0};                // glcContainerLastChoice: the last successful container compress
-    unsigned long long ct_filters[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // glcContainerLastFilters: frames per filter candidate, then all frames
+    CtReports ct_reports;                        // what the glcContainerLast* entries report
     GrowBuf ct_stage[2];
     GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse and rANS modes' and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
     SaScratch *sorter() override { return &sa; }
@@ -175,13 +174,6 @@ CUDPPResult validate_options(const CUDPPConfiguration &c)
     if ((c.options & CUDPP_OPTION_EXCLUSIVE) && (c.options & CUDPP_OPTION_INCLUSIVE))
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     return CUDPP_SUCCESS;
-}
-
-CUDPPResult hip_result(hipError_t e)
-{
-    if (e == hipSuccess) return CUDPP_SUCCESS;
-    if (e == hipErrorOutOfMemory) return CUDPP_ERROR_INSUFFICIENT_RESOURCES;
-    return CUDPP_ERROR_UNKNOWN;
 }
 
 struct StageTimer {
@@ -307,7 +299,7 @@ CUDPPResult cudppPlan(const CUDPPHandle cudppHandle, CUDPPHandle *planHandle, CU
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;   // not on the compression path
     }
     if (e == hipSuccess) e = plan->init_common();
-    if (e != hipSuccess) { delete plan; (void)hipGetLastError(); return hip_result(e); }
+    if (e != hipSuccess) { delete plan; return hip_result(e); }
     plan->config = config;
     plan->n = (uint32_t)n;
     plan->rows = (uint32_t)rows;
@@ -808,8 +800,16 @@ CUDPPResult glcPlanLastTiming(CUDPPHandle planHandle, float *ms4)
 
 } // extern "C"
 
-// internal: the container path (container_api.cpp) drives a plan through these
 namespace glc {
+// the one place a HIP error becomes a result code (glc_internal.h); the error is not left sticky for the caller's next HIP call
+CUDPPResult hip_result(hipError_t e)
+{
+    if (e == hipSuccess) return CUDPP_SUCCESS;
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? CUDPP_ERROR_INSUFFICIENT_RESOURCES : CUDPP_ERROR_UNKNOWN;
+}
+
+// internal: the container path (container_api.cpp) drives a plan through these
 CUDPPResult plan_compress_hooked(CUDPPHandle planHandle, CompressCall c, ContainerHooks &hk)
 {
     c.hooks = &hk;
@@ -831,8 +831,7 @@ void plan_join(CUDPPHandle planHandle) { plan_from<CompressPlan>(planHandle)->jo
 
 bool plan_pipelined(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->pipelined; }
 CtSettings &plan_container_settings(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct; }
-unsigned long long *plan_container_choice(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_choice; }
-unsigned long long *plan_container_filters(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_filters; }
+CtReports &plan_container_reports(CUDPPHandle planHandle) { return plan_from<CompressPlan>(planHandle)->ct_reports; }
 
 hipError_t plan_stage(CUDPPHandle planHandle, uint32_t which, size_t bytes, uint8_t **out)
 {

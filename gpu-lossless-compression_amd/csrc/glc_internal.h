@@ -1,6 +1,7 @@
 // glc_internal.h -- host-side interfaces between the C-ABI layer (cudpp_api.cpp,
 // culzss_api.cpp) and the stage launchers (*.hip).  Plain pointers + sizes.
 #pragma once
+#include "../../include/cudpp.h"
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -16,8 +17,13 @@
 
 // in a launcher that returns hipError_t: pass a failed call's error on
 #define GLC_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
+// in an entry point that returns CUDPPResult: a failed call's error as the result code
+#define CT_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return glc::hip_result(e_); } while (0)
 
 namespace glc {
+
+// what the C ABI answers for a HIP error (cudpp_api.cpp); a failure also clears HIP's sticky last error
+CUDPPResult hip_result(hipError_t e);
 
 constexpr uint32_t MAX_BLOCK_ELEMS = 1u << 20;   // cudppCompress/BWT limit (cudpp-inpar/README.md:96,99)
 constexpr uint32_t HUFF_BLOCK      = 4096;       // HUFF_THREADS_PER_BLOCK*HUFF_WORK_PER_THREAD (cudpp_globals.h:60-61)

@@ -691,18 +691,8 @@ def _ct():
             getattr(L, nm).argtypes = [vp, vp, vp, vp, sz, C.c_uint, vp]
         for nm in ("glcShuffleDevice", "glcUnshuffleDevice", "glcDeltaShuffleDevice", "glcUndeltaUnshuffleDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, vp]
-        L.glcPlanSetContainerShuffle.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerShuffle.argtypes = [sz, C.POINTER(C.c_uint)]
-        L.glcPlanSetContainerCodec.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerCodec.argtypes = [sz, C.POINTER(C.c_uint)]
-        L.glcPlanSetContainerDelta.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerDelta.argtypes = [sz, C.POINTER(C.c_uint)]
-        L.glcPlanSetContainerSparse.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerSparse.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcSparseSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         L.glcSparseJoinSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
-        L.glcPlanSetContainerRuns.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerRuns.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcZeroRunSplitSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp]
         L.glcZeroRunJoinSegments.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp]
         for nm in ("glcContainerIndexDevice", "glcContainerIndex"):
@@ -716,28 +706,25 @@ def _ct():
         L.glcContainerLastRangeStats.argtypes = [sz, ullp]
         for nm in ("glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, ull, ull, vp]
+        for nm in CONTAINER_SYMBOLS:                              # the plan's settings: Set takes the value, Get a pointer to it
+            if nm.startswith("glcPlanSetContainer"):
+                getattr(L, nm).argtypes = [sz, C.c_uint]
+            elif nm.startswith("glcPlanGetContainer"):
+                getattr(L, nm).argtypes = [sz, C.POINTER(C.c_uint)]
         for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
         L.glcContainerIndexFree.restype = None
-        L.glcPlanSetContainerAns.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerAns.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcAnsEncodeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp]
         L.glcAnsDecodeSegments.argtypes = [vp, vp, vp, vp, vp, vp, sz, sz, vp, vp, sz, vp]
         L.glcAnsSegmentsWorkBytes.argtypes = [sz, sz]
         L.glcAnsSegmentsWorkBytes.restype = sz
         L.glcAnsBoundWords.argtypes = [sz]
         L.glcAnsBoundWords.restype = sz
-        L.glcPlanSetContainerAuto.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerAuto.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcBigramProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp]
         L.glcContainerLastChoice.argtypes = [sz, ullp]
         L.glcFilterProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
-        L.glcPlanSetContainerFilterAuto.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerFilterAuto.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcContainerLastFilters.argtypes = [sz, ullp]
-        L.glcPlanSetContainerDedup.argtypes = [sz, C.c_uint]
-        L.glcPlanGetContainerDedup.argtypes = [sz, C.POINTER(C.c_uint)]
         L.glcDedupWorkBytes.argtypes = [sz, sz]
         L.glcDedupWorkBytes.restype = sz
         L.glcDedupMapSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp]
@@ -819,6 +806,13 @@ def container_decompress_file(plan, src, dst):
     _chk("glcContainerDecompressFile", _ct().glcContainerDecompressFile(plan.handle, os.fsencode(src), os.fsencode(dst)))
 
 
+def _get_uint(name, plan):
+    """a glcPlanGetContainer* entry: the setting as an int"""
+    v = C.c_uint(0)
+    _chk(name, getattr(_ct(), name)(plan.handle, C.byref(v)))
+    return int(v.value)
+
+
 def container_set_shuffle(plan, elem):
     """the byte-plane shuffle filter of the plan's container ENCODER: elem 2, 4 or 8 (format version 2), 0 or 1 = off (the
     default: version 1).  The decoder reads the element size from the stream and ignores this setting."""
@@ -826,9 +820,7 @@ def container_set_shuffle(plan, elem):
 
 
 def container_get_shuffle(plan):
-    e = C.c_uint(0)
-    _chk("glcPlanGetContainerShuffle", _ct().glcPlanGetContainerShuffle(plan.handle, C.byref(e)))
-    return int(e.value)
+    return _get_uint("glcPlanGetContainerShuffle", plan)
 
 
 def container_set_codec(plan, codec):
@@ -840,9 +832,7 @@ def container_set_codec(plan, codec):
 
 
 def container_get_codec(plan):
-    c = C.c_uint(0)
-    _chk("glcPlanGetContainerCodec", _ct().glcPlanGetContainerCodec(plan.handle, C.byref(c)))
-    return int(c.value)
+    return _get_uint("glcPlanGetContainerCodec", plan)
 
 
 def container_set_delta(plan, on):
@@ -852,9 +842,7 @@ def container_set_delta(plan, on):
 
 
 def container_get_delta(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerDelta", _ct().glcPlanGetContainerDelta(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerDelta", plan)
 
 
 def container_set_sparse(plan, on):
@@ -865,9 +853,7 @@ def container_set_sparse(plan, on):
 
 
 def container_get_sparse(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerSparse", _ct().glcPlanGetContainerSparse(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerSparse", plan)
 
 
 def container_set_runs(plan, on):
@@ -878,9 +864,7 @@ def container_set_runs(plan, on):
 
 
 def container_get_runs(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerRuns", _ct().glcPlanGetContainerRuns(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerRuns", plan)
 
 
 def container_set_ans(plan, on):
@@ -891,9 +875,7 @@ def container_set_ans(plan, on):
 
 
 def container_get_ans(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerAns", _ct().glcPlanGetContainerAns(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerAns", plan)
 
 
 def container_set_auto(plan, on):
@@ -905,9 +887,7 @@ def container_set_auto(plan, on):
 
 
 def container_get_auto(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerAuto", _ct().glcPlanGetContainerAuto(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerAuto", plan)
 
 
 def container_set_filter_auto(plan, on):
@@ -919,9 +899,7 @@ def container_set_filter_auto(plan, on):
 
 
 def container_get_filter_auto(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerFilterAuto", _ct().glcPlanGetContainerFilterAuto(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerFilterAuto", plan)
 
 
 def container_last_filters(plan):
@@ -940,9 +918,7 @@ def container_set_dedup(plan, on):
 
 
 def container_get_dedup(plan):
-    d = C.c_uint(0)
-    _chk("glcPlanGetContainerDedup", _ct().glcPlanGetContainerDedup(plan.handle, C.byref(d)))
-    return int(d.value)
+    return _get_uint("glcPlanGetContainerDedup", plan)
 
 
 def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None, stream=None):

@@ -253,6 +253,57 @@ def _decompress_into(glc, plan, cont, out, cap):
                                                                                    out.data_ptr(), cap, d_len.data_ptr()))
 
 
+# --- 7b. what a plan reports of its last calls lives and dies with it -------------------------------------------------------
+def _refused_header(glc, plan, c, size):
+    import torch
+    b = bytearray(c)
+    b[0] ^= 0x20                                                # the stream header's magic
+    with pytest.raises(glc.CudppError) as e:
+        _decompress_into(glc, plan, bytes(b), torch.empty(size, dtype=torch.uint8, device="cuda"), size)
+    assert e.value.code == UNKNOWN
+    assert glc.container_last_error(plan) == (1, -1, -1)
+
+
+def test_reports_die_with_their_plan(glc, ctx, cuda):
+    """A plan that has failed a decode and made a range read is closed; the next plans, which the allocator may put at its
+    address, start with the reports no call has touched."""
+    n, rows = 4096, 2
+    x = np.concatenate([_kind_data("text", 3 * n, 2), _kind_data("random", 3, 1)])
+    a = glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows)
+    d_c = glc.container_compress(a, _gpu(x))
+    c = _host(d_c).tobytes()
+    _refused_header(glc, a, c, x.size)
+    with glc.container_index(a, d_c) as ix:
+        assert np.array_equal(_host(glc.container_read_range(a, ix, d_c, n + 5, n)), x[n + 5:2 * n + 5])
+    stats = glc.container_last_range_stats(a)
+    assert all(v > 0 for v in stats)
+    _refused_header(glc, a, c, x.size)                          # (the range read has reset the triple: leave it non-zero again)
+    assert glc.container_last_range_stats(a) == stats
+    old = a.handle
+    a.close()
+    reused = 0
+    for _ in range(8):
+        with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as p:
+            reused += p.handle == old
+            assert glc.container_last_error(p) == (0, -1, -1)
+            assert glc.container_last_range_stats(p) == (0, 0, 0)
+    print("reports_die_with_their_plan: %d of 8 new plans took the closed plan's handle" % reused)   # (recorded, not asserted)
+
+
+def test_two_live_plans_do_not_share_reports(glc, ctx, cuda):
+    n, rows = 4096, 2
+    x = _kind_data("text", 2 * n + 7, 5)
+    with glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as a, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows) as b, \
+            glc.Plan(ctx, glc.CUDPP_BWT, n) as other:
+        c = _host(glc.container_compress(a, _gpu(x))).tobytes()
+        _refused_header(glc, a, c, x.size)
+        assert glc.container_last_error(b) == (0, -1, -1) and glc.container_last_range_stats(b) == (0, 0, 0)
+        assert glc.container_last_error(other) == (0, -1, -1)   # not a COMPRESS plan: no container call behind it, and no error
+        assert glc.container_last_range_stats(other) == (0, 0, 0)
+        assert np.array_equal(_host(glc.container_decompress(b, _gpu(np.frombuffer(c, np.uint8)))), x)
+        assert glc.container_last_error(a) == (1, -1, -1) and glc.container_last_error(b) == (0, -1, -1)
+
+
 # --- 8. capacity --------------------------------------------------------------------------------------------------------
 def test_capacity_is_checked_and_never_passed(glc, ctx, cuda):
     import torch

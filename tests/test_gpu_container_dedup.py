@@ -256,6 +256,23 @@ def test_capacity_with_the_dedup_mode_on(glc, ctx, cuda):
         assert c.numel() == need and _host(c).tobytes() == _want(elem, delta)
 
 
+def test_timing_with_the_dedup_mode_on(glc, ctx, cuda):
+    """the dedup frame is frame_order0's with its own kinds part: with the stage events on, the four marks come in order and the
+    bytes are the model's.  The input has kind-6 blocks (frame 0) and a ragged tail frame."""
+    x, want = I.container_input(0, False), _want(0, False)
+    frames = M.layout(want)["frames"]
+    assert 6 in [k for _, _, k in frames[0]["records"]] and frames[-1]["blk_len"] == I.TAIL < N
+    with _plan(glc, ctx, 0) as plan:
+        plan.enable_timing(1)
+        c = glc.container_compress(plan, _gpu(x))
+        plan.synchronize()
+        assert _host(c).tobytes() == want
+        ms = plan.last_timing()
+        assert len(ms) == 4 and all(np.isfinite(v) and v >= 0 for v in ms) and sum(ms) > 0
+        assert np.array_equal(_host(glc.container_decompress(plan, c)), x)
+        assert glc.container_last_error(plan) == (0, -1, -1)
+
+
 # --- 5. range reads ----------------------------------------------------------------------------------------------------------
 def _want_blocks(c, a, n):
     """(frames, blocks decoded) of a read of [a, a + n) of the unfiltered container c: the needed blocks of every frame and, in
