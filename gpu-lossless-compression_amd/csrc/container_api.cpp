@@ -4,7 +4,8 @@
 //
 // Format.  A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says
 // two things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
-// shuffle of shuffle.hip, or the fused delta + shuffle of delta.hip), and which record KINDS a frame may hold (0 BWT + Huffman and
+// shuffle of shuffle.hip, the fused delta + shuffle of delta.hip, or under version 11 that delta with the flags' lag and fold, lag.hip),
+// and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always; 2 order-0 Huffman, 3 its sparse form (sparse.hip), 4 the BWT codec's zero-run form (zrun.hip), 5 the order-0
 // codec's rANS form (ans.hip) and 6 its dedup form (dedup.hip) where kind2_legal() .. kind6_legal() say so).  ct_legal() is the
 // one table of legal triples: format_of() picks the writer's from the plan's settings (the lowest version whose kinds hold every
@@ -1381,7 +1382,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         if (i0 < i1) {                                          // elements [i0, i1) into the second staging, [a, min(b, q e)) out of them
             uint8_t *el = nullptr;
             CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
-            CT_TRY((ff.delta() ? undelta_unshuffle_range_device : unshuffle_range_device)(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
+            if (ff.delta()) CT_TRY(unlag_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.lag(), ff.fold(), i0, i1 - i0));
+            else CT_TRY(unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
             const unsigned long long top = std::min(b, q * e);
             if ((r = io.deliver(el + (a - i0 * e), top - a, at + a)) != CUDPP_SUCCESS) return r;
         }
@@ -1705,6 +1707,18 @@ CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on)
 CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
 {
     return ct_get(plan, on, [](const CtSettings &s) { return s.filter_auto ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_delta_lag(lag, fold); });
+}
+
+CUDPPResult glcPlanGetContainerDeltaLag(CUDPPHandle plan, unsigned int *lag, unsigned int *fold)
+{
+    if (!fold) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const CUDPPResult r = ct_get(plan, lag, [](const CtSettings &s) { return s.lag; });
+    return r != CUDPP_SUCCESS ? r : ct_get(plan, fold, [](const CtSettings &s) { return s.fold; });
 }
 
 } // extern "C"

@@ -97,6 +97,12 @@ hipError_t unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *ou
                                   unsigned long long first, unsigned long long count);
 hipError_t undelta_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
                                           unsigned long long first, unsigned long long count);
+// the lagged, folded delta + shuffle and its inverses (lag.hip): the predecessor is `lag` elements back (1..16), the difference's
+// sign folded into bit 0 where fold = 1; the rules of the delta forms, which (lag, fold) = (1, 0) is handed to
+hipError_t lag_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, uint32_t lag,
+                              uint32_t fold, bool inverse);
+hipError_t unlag_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                        uint32_t lag, uint32_t fold, unsigned long long first, unsigned long long count);
 
 // Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
 // the allocation it places, so the size and the pointers cannot disagree.
@@ -223,23 +229,37 @@ constexpr uint32_t CT_VERSION_DEDUP = 9;                     // 9: kinds 0, 1, 2
 // 10: version 8's kinds; the stream header's triple is (10, 0, 0) and every FRAME header's word 3 names that frame's filter,
 // elem | flags << 16 (elem 0, 2, 4 or 8; flags 0 or the delta flag, which needs an elem)
 constexpr uint32_t CT_VERSION_FILTER = 10;
+// 11: version 8's stream (its kinds, frame word 0) behind the lagged, folded delta of lag.hip: elem 2, 4 or 8 and flags
+// 1 | fold << 1 | (lag - 1) << 8 with the fold bit or the lag field non-zero (what flags 1 would say, version 8 says)
+constexpr uint32_t CT_VERSION_LAG = 11;
+constexpr uint32_t CT_FLAG_FOLD = 2, CT_LAG_SHIFT = 8, CT_LAG_MASK = 15u << CT_LAG_SHIFT;
+__host__ __device__ inline bool ct_lag_flags_legal(uint32_t flags)
+{
+    return (flags & CT_FLAG_DELTA) && !(flags & ~(CT_FLAG_DELTA | CT_FLAG_FOLD | CT_LAG_MASK)) && (flags & (CT_FLAG_FOLD | CT_LAG_MASK));
+}
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
-// its filter-auto setting version 10 (it is only ever on with the auto mode, so that mode's bits come with it)
+// its filter-auto setting version 10 and its delta-lag setting version 11 (either is only ever on with the auto mode, so that
+// mode's bits come with it)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
+constexpr uint32_t CT_READS_LAG = 64;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_FILTER + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F};
-    return version <= CT_VERSION_FILTER ? K[version] : 0u;
+    constexpr uint32_t K[CT_VERSION_LAG + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F};
+    return version <= CT_VERSION_LAG ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
-// kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike.
+// kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike (version 11's
+// are a family of flags over it: the delta's lag and fold).
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
+    // the delta's lag and fold: (1, 0) below version 11
+    __host__ __device__ uint32_t lag() const { return version == CT_VERSION_LAG ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
+    __host__ __device__ uint32_t fold() const { return version == CT_VERSION_LAG && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
     __host__ __device__ uint32_t kinds() const { return ct_kinds(version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4)
     __host__ __device__ bool kind2_legal() const { return (kinds() >> 2 & 1u) != 0; }
     __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
@@ -251,7 +271,8 @@ struct CtFormat {
     {
         return version == CT_VERSION_SPARSE ? CT_READS_SPARSE : version == CT_VERSION_RUNS ? CT_READS_RUNS :
                version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
-               version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER : 0u;
+               version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
+               version == CT_VERSION_LAG ? CT_READS_LAG : 0u;
     }
 };
 // a frame header's word 3.  Versions 1 to 9 keep it 0; under version 10 it is the frame's filter.  ct_frame_word_legal() is the
@@ -273,7 +294,8 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
 // a format's filter over one segment, or its inverse
 inline hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
 {
-    return (f.delta() ? delta_shuffle_device : shuffle_device)(st, in, out, len, f.elem, inverse);
+    if (f.delta()) return lag_shuffle_device(st, in, out, len, f.elem, f.lag(), f.fold(), inverse);   // ((1, 0): delta.hip's kernels)
+    return shuffle_device(st, in, out, len, f.elem, inverse);
 }
 constexpr uint32_t CT_HDR = 32, CT_FRAME_HDR = 32, CT_TRAILER = 16;
 // the format rule: the legal (version, flags) pairs, lowest version first, and the element sizes each takes (bit e = elem e)
@@ -294,6 +316,8 @@ __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 }
 __host__ __device__ inline bool format_legal(const CtFormat &f)
 {
+    // (version 11 is a family of flags, not rows: every lag and fold over the three element sizes)
+    if (f.version == CT_VERSION_LAG) return ct_lag_flags_legal(f.flags) && f.elem <= 8 && (CT_ELEMS >> f.elem & 1);
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         const CtLegal l = ct_legal(i);
         if (l.version == f.version && l.flags == f.flags && f.elem <= 8 && (l.elems >> f.elem & 1)) return true;
@@ -474,17 +498,32 @@ struct CtSettings {
     // filter-auto: the writer picks every frame's filter itself (filter_rule.h) and writes version 10.  Only ever on with the order-0
     // codec, the auto mode on and the shuffle off; whatever ends one of the three switches it off
     bool filter_auto = false;
+    // delta-lag: the delta's predecessor is `lag` elements back and its sign is folded where fold = 1 (lag.hip; the writer writes
+    // version 11).  Anything but (1, 0) is only ever on with the order-0 codec, the auto mode, the shuffle and the delta on and
+    // filter-auto off; whatever ends one of them puts it back to (1, 0)
+    uint32_t lag = 1, fold = 0;
+    bool lag_on() const { return lag != 1 || fold != 0; }
+    bool lag_fits() const { return codec == CT_CODEC_HUFF0 && mode == CT_MODE_AUTO && shuffle && delta && !filter_auto; }
+    void lag_keep() { if (!lag_fits()) { lag = 1; fold = 0; } }
     bool set_shuffle(uint32_t elem)
     {
         if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE || filter_auto)) return false;
         shuffle = elem > 1 ? elem : 0;
         if (elem <= 1) delta = false;                         // (no delta without the shuffle)
+        lag_keep();
         return true;
     }
     bool set_delta(uint32_t on)
     {
         if (on > 1 || (on && !shuffle)) return false;
         delta = on != 0;
+        lag_keep();
+        return true;
+    }
+    bool set_delta_lag(uint32_t l, uint32_t f)
+    {
+        if (l < 1 || l > 16 || f > 1 || ((l != 1 || f) && !lag_fits())) return false;
+        lag = l; fold = f;
         return true;
     }
     bool set_codec(uint32_t c)
@@ -493,6 +532,7 @@ struct CtSettings {
         codec = c;
         if (!ct_mode_fits(mode, codec)) mode = CT_MODE_PLAIN;  // (no mode without its codec)
         if (mode != CT_MODE_AUTO) filter_auto = false;
+        lag_keep();
         return true;
     }
     // on: refused when the mode does not fit the codec or another mode is on (the modes exclude each other); off: clears the
@@ -503,19 +543,22 @@ struct CtSettings {
         if (on) mode = m;
         else if (mode == m) mode = CT_MODE_PLAIN;
         if (mode != CT_MODE_AUTO) filter_auto = false;
+        lag_keep();
         return true;
     }
     bool set_filter_auto(uint32_t on)
     {
         if (on > 1 || (on && (codec != CT_CODEC_HUFF0 || mode != CT_MODE_AUTO || shuffle))) return false;
         filter_auto = on != 0;
+        lag_keep();                                           // (it needs the shuffle off and the lag needs it on: already (1, 0))
         return true;
     }
     // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
-               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) :
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) |
+                                      (lag_on() ? CT_READS_LAG : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
@@ -535,6 +578,11 @@ inline CtFormat format_of(const CtSettings &s)
     if (s.filter_auto) { f.version = CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
     f.elem = s.shuffle;
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
+    if (s.lag_on()) {                                         // (what (1, 0) does, version 8 says)
+        f.version = CT_VERSION_LAG;
+        f.flags |= (s.fold ? CT_FLAG_FOLD : 0u) | (s.lag - 1) << CT_LAG_SHIFT;
+        return f;
+    }
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         f.version = ct_legal(i).version;
         if (format_legal(f) && (f.kinds() & s.kinds()) == s.kinds()) break;

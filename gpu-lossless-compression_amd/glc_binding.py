@@ -663,6 +663,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcBigramProbeSegments", "glcContainerLastChoice", "glcFilterProbeSegments",
                      "glcPlanSetContainerFilterAuto", "glcPlanGetContainerFilterAuto", "glcContainerLastFilters",
                      "glcDedupWorkBytes", "glcDedupMapSegments", "glcDedupFillSegments", "glcPlanSetContainerDedup", "glcPlanGetContainerDedup",
+                     "glcLagDeltaShuffleDevice", "glcUnlagDeltaUnshuffleDevice", "glcUnlagDeltaUnshuffleRangeDevice",
+                     "glcPlanSetContainerDeltaLag", "glcPlanGetContainerDeltaLag",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -711,6 +713,11 @@ def _ct():
                 getattr(L, nm).argtypes = [sz, C.c_uint]
             elif nm.startswith("glcPlanGetContainer"):
                 getattr(L, nm).argtypes = [sz, C.POINTER(C.c_uint)]
+        L.glcPlanSetContainerDeltaLag.argtypes = [sz, C.c_uint, C.c_uint]
+        L.glcPlanGetContainerDeltaLag.argtypes = [sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        for nm in ("glcLagDeltaShuffleDevice", "glcUnlagDeltaUnshuffleDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, vp]
+        L.glcUnlagDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
         for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
         L.glcContainerIndexFree.restype = None
@@ -900,6 +907,20 @@ def container_set_filter_auto(plan, on):
 
 def container_get_filter_auto(plan):
     return _get_uint("glcPlanGetContainerFilterAuto", plan)
+
+
+def container_set_delta_lag(plan, lag, fold):
+    """the lag and fold of the delta of the plan's container ENCODER (format version 11: the predecessor `lag` elements back, the
+    sign folded into bit 0 where fold is 1); (1, 0) is off.  Anything else needs the order-0 codec, the auto mode, the shuffle
+    and the delta on and filter-auto off, and whatever ends one of them puts it back to (1, 0).  It is also the version the plan
+    reads: on, versions 1 to 5, 7, 8 and 11; off, a version-11 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerDeltaLag", _ct().glcPlanSetContainerDeltaLag(plan.handle, int(lag), int(fold)))
+
+
+def container_get_delta_lag(plan):
+    lag, fold = C.c_uint(0), C.c_uint(0)
+    _chk("glcPlanGetContainerDeltaLag", _ct().glcPlanGetContainerDeltaLag(plan.handle, C.byref(lag), C.byref(fold)))
+    return int(lag.value), int(fold.value)
 
 
 def container_last_filters(plan):
@@ -1196,6 +1217,29 @@ def undelta_unshuffle(d_in, elem, out=None, stream=None):
     return _shuffle("glcUndeltaUnshuffleDevice", d_in, elem, out, stream)
 
 
+def _lag_shuffle(fn, d_in, elem, lag, fold, out, stream):
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), int(lag),
+                                int(fold), stream))
+    return out
+
+
+def lag_delta_shuffle(d_in, elem, lag, fold, out=None, stream=None):
+    """delta_shuffle with the predecessor `lag` elements back (1 to 16: the channel count of interleaved data) and, where fold is
+    1, the difference's sign folded into bit 0; (1, 0) is delta_shuffle.  The rules of shuffle"""
+    return _lag_shuffle("glcLagDeltaShuffleDevice", d_in, elem, lag, fold, out, stream)
+
+
+def unlag_delta_unshuffle(d_in, elem, lag, fold, out=None, stream=None):
+    """the inverse of lag_delta_shuffle"""
+    return _lag_shuffle("glcUnlagDeltaUnshuffleDevice", d_in, elem, lag, fold, out, stream)
+
+
 def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):
     """shuffle (or unshuffle) the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in into the same ranges of d_out"""
     import torch
@@ -1348,3 +1392,16 @@ def unshuffle_range(d_in, elem, first, count, out=None, stream=None):
 def undelta_unshuffle_range(d_in, elem, first, count, out=None, stream=None):
     """elements [first, first + count) of undelta_unshuffle(d_in, elem); first a multiple of 2048"""
     return _unshuffle_range("glcUndeltaUnshuffleRangeDevice", d_in, elem, first, count, out, stream)
+
+
+def unlag_delta_unshuffle_range(d_in, elem, lag, fold, first, count, out=None, stream=None):
+    """elements [first, first + count) of unlag_delta_unshuffle(d_in, elem, lag, fold); first a multiple of 2048"""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
+    _chk("glcUnlagDeltaUnshuffleRangeDevice", _ct().glcUnlagDeltaUnshuffleRangeDevice(
+        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(lag), int(fold), int(first), int(count), stream))
+    return out

@@ -176,6 +176,21 @@ CUDPPResult glcUnshuffleDevice(const void *d_in, void *d_out, unsigned long long
 CUDPPResult glcDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 CUDPPResult glcUndeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream);
 
+/* The delta with a lag and a folded sign (csrc/lag.hip), for interleaved channels and for series whose differences change sign:
+ * with W = 8 elem and r = i mod 2048, d[i] = x[i] where r < lag and x[i] - x[i - lag] modulo 2^W elsewhere; f[i] = d[i], or with
+ * fold = 1 (d[i] << 1) ^ (0 - (d[i] >> (W - 1))) modulo 2^W (the sign in bit 0, so the upper planes of a small difference of
+ * either sign are zero); out[j * q + i] = byte j of f[i]; the last len % elem bytes copied in place.  The inverse gathers f, undoes
+ * the fold, d = (f >> 1) ^ (0 - (f & 1)), and sums every lag-th element back to the one with r < lag.  lag is the channel count,
+ * 1 to 16; (lag, fold) = (1, 0) is glcDeltaShuffleDevice, byte for byte.  The rules of glcDeltaShuffleDevice; a lag outside 1..16
+ * and a fold above 1 are refused like a bad elem.  The range form is glcUndeltaUnshuffleRangeDevice's: `first` a multiple of 2048. */
+CUDPPResult glcLagDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int lag,
+                                     unsigned int fold, void *stream);
+CUDPPResult glcUnlagDeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int lag,
+                                         unsigned int fold, void *stream);
+CUDPPResult glcUnlagDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                              unsigned int lag, unsigned int fold, unsigned long long first,
+                                              unsigned long long count, void *stream);
+
 /* The two passes of the sparse mode as batched calls (csrc/sparse.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of
  * its base, cut into chunks of 64 bytes (the last may be short); d_fill[i] & 255 is its fill byte, given by the caller; its mask is
  * row i of d_mask, rows of ceil(ceil(maxLen / 64) / 32) words: bit c % 32 of word c / 32 is 1 when chunk c is kept, 0 when every
@@ -534,6 +549,17 @@ CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on);
  * order-0 modes; element sizes other than 2, 4 and 8, a sampled probe and a choice per block are not offered. */
 CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on);
+
+/* The lag and fold of the ENCODER's delta (glcLagDeltaShuffleDevice), (1, 0) = off, the default.  Anything else needs the order-0
+ * codec, the auto mode on, the shuffle at 2, 4 or 8, the delta on and filter-auto off; any other state, a lag outside 1..16 and a
+ * fold above 1 are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.  Whatever ends one of those prerequisites
+ * puts it back to (1, 0); a change among elem 2, 4 and 8 keeps it.  The stream is format version 11: version 8's frames, the
+ * header's flags 1 | fold << 1 | (lag - 1) << 8.  (1, 0) writes version 8 byte for byte.  Decode, index and range reads take lag and
+ * fold from the stream header, never from the plan; glcContainerIndexInfo's fourth word carries the flags.  The setting is also the
+ * version the plan speaks: with it on the plan reads versions 1 to 5, 7, 8 and 11; every other plan refuses a version-11 stream as
+ * a stream-header failure.  Not combined with filter-auto, the BWT codec, the CHOOSE codec or the other order-0 modes. */
+CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold);
+CUDPPResult glcPlanGetContainerDeltaLag(CUDPPHandle plan, unsigned int *lag, unsigned int *fold);
 
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.

@@ -48,6 +48,10 @@ filter-auto (glcPlanSetContainerFilterAuto, format version 10), R interleaved ro
 ratio, the CRC-32 of the container and what glcContainerLastFilters reports per setting.  --filter-auto-off-only runs the first two
 settings alone, which is also what a build without the setting can run.
 
+--lag L [--fold] (with --data stereo16, adc16x8, xyz32, cplx64 or i32x4 of tests/lag_inputs.py -- 32 MiB generated on the host and
+repeated to the size asked for --, or any typed kind; --rounds R, at least 1) is the lag section: the order-0 codec with the auto
+mode on under the shuffle alone, the plain delta (both format version 8) and the delta with lag L and the fold (format version
+11), interleaved, with the same output as the filter-auto section; --lag 1 without --fold runs the first two only.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
                                 [--filter-auto | --filter-auto-off-only]"""
@@ -61,7 +65,9 @@ import zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
-DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0}
+DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0,
+             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4}
+LAG_PIECE = 32 * MiB                                           # what tests/lag_inputs.py generates on the host; repeated on the device
 
 
 def typed_on_device(torch, L, dev, kind, total):
@@ -453,6 +459,56 @@ def filter_auto_section(torch, glc, plan, d_in, total, elem, delta, rounds, with
     return res
 
 
+def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
+    """the order-0 container with the auto mode on under "shuffle" (the shuffle alone), "delta" (the plain delta) and "lag" (the
+    delta with `lag` and `fold`, format version 11; left out at (1, 0)), interleaved: `rounds` rounds of one encode and one decode
+    per setting after one untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["shuffle", "delta"] + (["lag"] if (lag, fold) != (1, 0) else [])
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+    glc.container_set_auto(plan, 1)
+    glc.container_set_shuffle(plan, elem)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            glc.container_set_delta(plan, 0 if s == "shuffle" else 1)      # (off: the lag goes back to (1, 0) with it)
+            if s == "lag":
+                glc.container_set_delta_lag(plan, lag, fold)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if s == "lag":
+                glc.container_set_delta_lag(plan, 1, 0)
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["version"] = int(cont[4].item()) | int(cont[5].item()) << 8
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -474,6 +530,8 @@ def main():
     ap.add_argument("--filter-auto", action="store_true",
                     help="the filter-auto section (format version 10): the auto mode with no filter, with --shuffle / --delta set by hand and with filter-auto")
     ap.add_argument("--filter-auto-off-only", action="store_true", help="the filter-auto section without the setting (what a build without it can run)")
+    ap.add_argument("--lag", type=int, default=0, metavar="L", help="the lag section (format version 11): the delta's lag, 1 to 16")
+    ap.add_argument("--fold", action="store_true", help="the lag section's delta folds its sign")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -492,6 +550,11 @@ def main():
     if args.data in ("pages", "pages_noise"):                  # the model's own generator, on the host
         import dedup_inputs
         d_in = torch.from_numpy(np.array(dedup_inputs.make(args.data, total), copy=True)).to(dev)
+    elif args.data in ("stereo16", "adc16x8", "xyz32", "cplx64", "i32x4"):
+        import lag_inputs
+        assert args.lag, "the interleaved kinds are the lag section's"
+        piece = torch.from_numpy(lag_inputs.lag_bytes(args.data, min(total, LAG_PIECE))).to(dev)
+        d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
     elif args.data in ("zipf", "mix"):
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
         thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
@@ -532,6 +595,13 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if args.lag:
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["lag"] = lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.lag, int(args.fold), max(1, args.rounds))
         print(json.dumps(res))
         return
     if args.filter_auto or args.filter_auto_off_only:

@@ -5,13 +5,15 @@
   unshuf N   glcUnshuffleDevice
   delta-shuffle N / undelta-unshuffle N
              glcDeltaShuffleDevice / glcUndeltaUnshuffleDevice, the fused kernels of the filter's delta mode
+  lag L[f] N / unlag L[f] N   (with --lag)
+             glcLagDeltaShuffleDevice / glcUnlagDeltaUnshuffleDevice (csrc/lag.hip) with lag L = 2, 3, 8, 16, f = the fold on
 
 Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each run is bracketed by device events.  The
 table gives the median, the fastest and the slowest run of every variant, as GB/s of input bytes (the traffic is twice that)
 and relative to the copy's median.  The buffer (--gib, default 1) is larger than the 256 MiB Infinity Cache on purpose.
 --offset A B misaligns source and destination by A and B bytes.  One JSON line on stdout, the table on stderr or in --md FILE.
 
-python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--md FILE]"""
+python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--md FILE]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -38,6 +40,7 @@ def main():
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--offset", type=int, nargs=2, default=[0, 0])
+    ap.add_argument("--lag", action="store_true", help="the lagged, folded delta kernels beside the others")
     ap.add_argument("--md", default=None)
     args = ap.parse_args()
     assert args.reps >= 20, "at least 20 timed repetitions"
@@ -70,6 +73,22 @@ def main():
         variants.append(("unshuf %d" % elem, kernel(L.glcUnshuffleDevice, elem)))
         variants.append(("delta-shuffle %d" % elem, kernel(L.glcDeltaShuffleDevice, elem)))
         variants.append(("undelta-unshuffle %d" % elem, kernel(L.glcUndeltaUnshuffleDevice, elem)))
+    def lagged(fn, elem, lag, fold):
+        return lambda: glc._chk("lag", fn(src.data_ptr(), dst.data_ptr(), n, elem, lag, fold, None))
+
+    if args.lag:
+        for elem in (2, 4, 8):
+            for lag in (2, 3, 8, 16):
+                for fold in (0, 1):
+                    tag = "%d%s %d" % (lag, "f" if fold else "", elem)
+                    variants.append(("lag " + tag, lagged(L.glcLagDeltaShuffleDevice, elem, lag, fold)))
+                    variants.append(("unlag " + tag, lagged(L.glcUnlagDeltaUnshuffleDevice, elem, lag, fold)))
+            back = torch.empty_like(src)                       # what is timed inverts itself, once per lag, with the fold
+            for lag in (2, 3, 8, 16):
+                lagged(L.glcLagDeltaShuffleDevice, elem, lag, 1)()
+                glc._chk("unlag", L.glcUnlagDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, lag, 1, None))
+                assert torch.equal(back, src), (elem, lag)
+            del back
     # correctness of what is timed, once, at this size and alignment
     for elem in (2, 4, 8):
         kernel(L.glcShuffleDevice, elem)()
