@@ -496,15 +496,22 @@ CUDPPResult glcMtfBatch(CUDPPHandle planHandle, const unsigned char *d_in, unsig
     return hip_result(mtf_forward(p->stream, d_in, n, n, nb, d_out, n, p->mtf, nullptr));
 }
 
+// the entry check of the decoder's entries, and the decoder's scratch on first use
+static CompressPlan *decode_plan(CUDPPHandle planHandle, size_t numElements, size_t numBlocks, CUDPPResult &why)
+{
+    CompressPlan *p = batch_plan<CompressPlan>(planHandle, CUDPP_COMPRESS, ANY_DATATYPE, numElements, numBlocks, why);
+    if (p && !p->dec.lf) {
+        why = hip_result(decode_scratch_alloc(p->dec, p->n, p->rows));
+        if (why != CUDPP_SUCCESS) return nullptr;
+    }
+    return p;
+}
+
 static CUDPPResult decompress_batch(CUDPPHandle planHandle, const DecodeCall &c)
 {
     CUDPPResult why;
-    CompressPlan *p = batch_plan<CompressPlan>(planHandle, CUDPP_COMPRESS, ANY_DATATYPE, c.n, c.nblk, why);
+    CompressPlan *p = decode_plan(planHandle, c.n, c.nblk, why);
     if (!p) return why;
-    if (!p->dec.lf) {
-        hipError_t e = decode_scratch_alloc(p->dec, p->n, p->rows);
-        if (e != hipSuccess) return hip_result(e);
-    }
     if (!p->pipelined) return hip_result(decode_blocks(p->stream, c, p->dec, p->d_status));
     // pipelined: Huffman + inverse MTF on the plan's stream (inputs keep their stream order), the inverse
     // BWT -- a memory-latency-bound walk -- on the side stream, where it overlaps stage A of the next call.
@@ -542,6 +549,43 @@ CUDPPResult glcDecompressBatchCompact(CUDPPHandle planHandle, const int *d_bwtIn
     if (!d_blockOffsets) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     return decompress_batch(planHandle, DecodeCall{d_bwtIndex, d_hist, d_encodeOffset, offsetStride, d_compact, compactWords, d_out,
                                                    numElements, numBlocks, d_blockOffsets});
+}
+
+// the decoder stage by stage (tests, A/B timing): the Huffman step alone, the inverse of glcHuffmanEncodeBatch ...
+CUDPPResult glcHuffmanDecodeBatch(CUDPPHandle planHandle, const unsigned int *d_hist, const unsigned int *d_encodeOffset,
+                                  size_t offsetStride, const unsigned int *d_compressed, size_t compressedStrideWords,
+                                  unsigned char *d_symbols, size_t numElements, size_t numBlocks)
+{
+    CUDPPResult why;
+    CompressPlan *p = decode_plan(planHandle, numElements, numBlocks, why);
+    if (!p) return why;
+    p->join_side();
+    return hip_result(decode_huff_rows(p->stream, DecodeCall{nullptr, d_hist, d_encodeOffset, offsetStride, d_compressed,
+                                                              compressedStrideWords, nullptr, numElements, numBlocks},
+                                       p->dec, d_symbols, numElements, p->d_status));
+}
+
+// ... and the inverse MTF alone, the inverse of glcMtfBatch
+CUDPPResult glcMtfInverseBatch(CUDPPHandle planHandle, const unsigned char *d_mtf, unsigned char *d_out, size_t numElements,
+                               size_t numBlocks)
+{
+    CUDPPResult why;
+    CompressPlan *p = decode_plan(planHandle, numElements, numBlocks, why);
+    if (!p) return why;
+    p->join_side();
+    return hip_result(decode_imtf_rows(p->stream, (uint32_t)numElements, (uint32_t)numBlocks, p->dec, d_mtf, numElements, d_out,
+                                       numElements));
+}
+
+// which Huffman decode kernel the plan's decoder uses: 0 by the call's size, 1 k_dec_huff, 2 k_dec_huff_lanes
+CUDPPResult glcPlanSetHuffDecoder(CUDPPHandle planHandle, int mode)
+{
+    PlanBase *base = plan_of(planHandle);
+    if (!base) return CUDPP_ERROR_INVALID_HANDLE;
+    if (base->config.algorithm != CUDPP_COMPRESS) return CUDPP_ERROR_INVALID_PLAN;
+    if (mode < 0 || mode > 2) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    static_cast<CompressPlan *>(base)->dec.huff_decoder = mode;
+    return CUDPP_SUCCESS;
 }
 
 // --------------------------------------------------------------------------

@@ -331,7 +331,9 @@ __global__ __launch_bounds__(DL_NT) void k_dec_huff_lanes(const uint32_t *__rest
     uint8_t *dst = mtf + (size_t)b * mtf_stride + lo;
     const bool vec = (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
     for (uint32_t i0 = 0; i0 < cnt; i0 += 16) {
-        if (have <= 16) refill();                               // 16 symbols take at most 14 words (codes <= 28 bits)
+        // 16 symbols take at most 14 words (codes <= 28 bits).  Both met at n = 2^20 (tests/dec_huff_inputs.py: a code of
+        // 28 bits; a group of 422 bits that takes 14 words): a threshold below 13 runs the ring dry, one above 16 overfills it
+        if (have <= 16) refill();
         uint32_t o4[4] = {0, 0, 0, 0};
 #pragma unroll
         for (uint32_t j = 0; j < 16; j++) {
@@ -978,48 +980,59 @@ void decode_scratch_free(DecodeScratch &s)
 // Stage B: inverse BWT of `bwt` -> d_out.  The two stages use disjoint scratch apart from `bwt`, so
 // stage A of the next batch can run on another stream while stage B of this one walks its LF cycles
 // (glcPlanSetPipelining): A is LDS/VALU work, B is a memory-latency-bound pointer chase.
-// the second half of stage A: nblk rows of MTF bytes (stride s.nmax) -> BWT bytes in `bwt`
-static hipError_t imtf_rows(hipStream_t st, uint32_t n, uint32_t nblk, DecodeScratch &s, const uint8_t *mtf, uint8_t *bwt)
+// the second half of stage A: nblk rows of MTF bytes at `mtf` (stride in_stride) -> BWT bytes in `bwt` (stride out_stride)
+hipError_t decode_imtf_rows(hipStream_t st, uint32_t n, uint32_t nblk, DecodeScratch &s, const uint8_t *mtf, size_t in_stride,
+                            uint8_t *bwt, size_t out_stride)
 {
+    if (n == 0 || n > s.nmax || nblk == 0 || nblk > s.rows) return hipErrorInvalidValue;
     const uint32_t nchunks = (n + IMTF_CHUNK - 1) / IMTF_CHUNK;
     const double units = (double)n * nblk;
     {
         ProfScope ps(s.prof, PROF_IMTF_POS, st, units);
-        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, mtf, (size_t)s.nmax, n, s.ilists,
-                           s.max_chunks, bwt, (size_t)s.nmax);
+        hipLaunchKernelGGL(k_imtf_pos_deque, dim3((nchunks + 63) / 64, nblk), dim3(64), 0, st, mtf, in_stride, n, s.ilists,
+                           s.max_chunks, bwt, out_stride);
     }
     {
         ProfScope ps(s.prof, PROF_IMTF_REST, st, units);
         hipLaunchKernelGGL(k_imtf_scan, dim3(nblk), dim3(64), 0, st, s.ilists, n, s.max_chunks);
-        hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, (size_t)s.nmax, n, s.ilists,
+        hipLaunchKernelGGL(k_imtf_apply, dim3(nchunks, nblk), dim3(256), 0, st, bwt, out_stride, n, s.ilists,
                            s.max_chunks);
+    }
+    return hipGetLastError();
+}
+
+// the first half of stage A: the call's streams -> nblk rows of symbols at `sym` (stride sym_stride).  Which kernel: by the
+// call's size, unless s.huff_decoder (glcPlanSetHuffDecoder) names one -- same bytes either way.
+hipError_t decode_huff_rows(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *sym, size_t sym_stride,
+                            uint32_t *d_status)
+{
+    if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
+    const uint32_t n = (uint32_t)c.n, nblk = (uint32_t)c.nblk;
+    const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
+    const bool lanes = s.huff_decoder == 0 ? (uint64_t)nsub * nblk >= DL_MIN_SUBS : s.huff_decoder == 2;
+    {
+        ProfScope ps(s.prof, PROF_DEC_HUFF, st, (double)n * nblk);
+        hipLaunchKernelGGL(k_dec_prepare, dim3(nblk), dim3(256), 0, st, c.hist, s.lut, s.nodes, n, d_status);
+        if (lanes)
+            hipLaunchKernelGGL(k_dec_huff_lanes, dim3((nsub + DL_NT - 1) / DL_NT, nblk), dim3(DL_NT), 0, st, c.comp, c.comp_stride,
+                               c.enc_off, c.off_stride, s.lut, s.nodes, n, sym, sym_stride, d_status, c.block_off);
+        else
+            hipLaunchKernelGGL(k_dec_huff, dim3((nsub + DH_WAVES - 1) / DH_WAVES, nblk), dim3(DH_WAVES * 64), 0, st, c.comp, c.comp_stride,
+                               c.enc_off, c.off_stride, s.lut, s.nodes, n, sym, sym_stride, d_status, c.block_off);
     }
     return hipGetLastError();
 }
 
 hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status)
 {
-    if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
-    const uint32_t n = (uint32_t)c.n, nblk = (uint32_t)c.nblk;
-    const uint32_t nsub = (n + HUFF_BLOCK - 1) / HUFF_BLOCK;
-    const double units = (double)n * nblk;
-    {
-        ProfScope ps(s.prof, PROF_DEC_HUFF, st, units);
-        hipLaunchKernelGGL(k_dec_prepare, dim3(nblk), dim3(256), 0, st, c.hist, s.lut, s.nodes, n, d_status);
-        if ((uint64_t)nsub * nblk >= DL_MIN_SUBS)
-            hipLaunchKernelGGL(k_dec_huff_lanes, dim3((nsub + DL_NT - 1) / DL_NT, nblk), dim3(DL_NT), 0, st, c.comp, c.comp_stride,
-                               c.enc_off, c.off_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, c.block_off);
-        else
-            hipLaunchKernelGGL(k_dec_huff, dim3((nsub + DH_WAVES - 1) / DH_WAVES, nblk), dim3(DH_WAVES * 64), 0, st, c.comp, c.comp_stride,
-                               c.enc_off, c.off_stride, s.lut, s.nodes, n, s.mtf, (size_t)s.nmax, d_status, c.block_off);
-    }
-    return imtf_rows(st, n, nblk, s, s.mtf, bwt);
+    GLC_TRY(decode_huff_rows(st, c, s, s.mtf, (size_t)s.nmax, d_status));
+    return decode_imtf_rows(st, (uint32_t)c.n, (uint32_t)c.nblk, s, s.mtf, (size_t)s.nmax, bwt, (size_t)s.nmax);
 }
 
 hipError_t decode_mtf_blocks(hipStream_t st, const DecodeCall &c, const uint8_t *mtf, DecodeScratch &s, uint32_t *d_status)
 {
     if (c.n == 0 || c.n > s.nmax || c.nblk == 0 || c.nblk > s.rows) return hipErrorInvalidValue;
-    GLC_TRY(imtf_rows(st, (uint32_t)c.n, (uint32_t)c.nblk, s, mtf, s.bwt));
+    GLC_TRY(decode_imtf_rows(st, (uint32_t)c.n, (uint32_t)c.nblk, s, mtf, (size_t)s.nmax, s.bwt, (size_t)s.nmax));
     return decode_stage_b(st, c, s.bwt, s, d_status);
 }
 

@@ -531,6 +531,7 @@ struct DecodeScratch {
     uint8_t  *slots = nullptr;                   // [rows][max_seg][256] symbols emitted by each segment
     uint32_t  max_seg = 0;
     size_t    bytes = 0;
+    int       huff_decoder = 0;                  // glcPlanSetHuffDecoder: 0 by the call's size, 1 k_dec_huff, 2 k_dec_huff_lanes
 };
 hipError_t tile_hist_scan9(hipStream_t st, uint32_t *tile_hist, uint32_t count, uint32_t *digit_base,
                            uint32_t max_tiles, uint32_t nblk, uint32_t tile_elems);
@@ -540,6 +541,12 @@ void       decode_scratch_free(DecodeScratch &s);
 hipError_t decode_stage_a(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *bwt, uint32_t *d_status);
 hipError_t decode_stage_b(hipStream_t st, const DecodeCall &c, const uint8_t *bwt, DecodeScratch &s, uint32_t *d_status);
 hipError_t decode_blocks(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint32_t *d_status);
+// the two halves of stage A on their own (glcHuffmanDecodeBatch, glcMtfInverseBatch): the call's streams -> c.nblk rows of
+// symbols at `sym`; nblk rows of MTF bytes at `mtf` -> BWT bytes at `bwt`.  Rows at the strides given.
+hipError_t decode_huff_rows(hipStream_t st, const DecodeCall &c, DecodeScratch &s, uint8_t *sym, size_t sym_stride,
+                            uint32_t *d_status);
+hipError_t decode_imtf_rows(hipStream_t st, uint32_t n, uint32_t nblk, DecodeScratch &s, const uint8_t *mtf, size_t in_stride,
+                            uint8_t *bwt, size_t out_stride);
 // stage A without its Huffman step, then stage B: c.nblk rows of MTF bytes at `mtf` (stride s.nmax; the container's zero-run
 // records are joined into s.mtf) -> c.out.  Of c only bwt_index, out, n and nblk are read.
 hipError_t decode_mtf_blocks(hipStream_t st, const DecodeCall &c, const uint8_t *mtf, DecodeScratch &s, uint32_t *d_status);

@@ -41,6 +41,7 @@ CUDPP_SYMBOLS = [
     "glcPlanSynchronize", "glcPlanEnableTiming", "glcPlanLastTiming", "glcPlanKernelProfile",
     "glcCompactStreams", "glcPlanSetPipelining", "glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanLastSortStatsEx", "glcPlanLastSortRetries", "glcPlanLastSortResumed", "glcPlanLastSortPeriodic", "glcPlanSetChains", "glcPlanLastSortChains", "glcPlanLastSortSkipped", "glcPlanDebugSortFlags", "glcPlanDebugBucketFill", "glcHuffmanEncodeBatch", "glcExpandStreams", "glcPlanKernelProfileEx", "glcProbeStreamRead", "glcGenZipfPhilox", "glcGenFloatPhilox", "glcPlanKernelProfileLost",
     "glcCompressBatchCompact", "glcDecompressBatchCompact",
+    "glcHuffmanDecodeBatch", "glcMtfInverseBatch", "glcPlanSetHuffDecoder",
 ]
 CULZSS_SYMBOLS = [
     "compression_kernel_wrapper", "aftercompression_wrapper", "decompression_kernel_wrapper",
@@ -104,6 +105,9 @@ def lib():
     L.glcPlanSynchronize.argtypes = [sz]
     L.glcPlanSetPipelining.argtypes = [sz, C.c_int]
     L.glcHuffmanEncodeBatch.argtypes = [sz, vp, vp, vp, sz, vp, vp, sz, sz, sz]
+    L.glcHuffmanDecodeBatch.argtypes = [sz, vp, vp, sz, vp, sz, vp, sz, sz]
+    L.glcMtfInverseBatch.argtypes = [sz, vp, vp, sz, sz]
+    L.glcPlanSetHuffDecoder.argtypes = [sz, C.c_int]
     L.glcPlanSetSorter.argtypes = [sz, C.c_int]
     L.glcPlanLastSortStats.argtypes = [sz, C.POINTER(C.c_uint)]
     L.glcPlanLastSortStatsEx.argtypes = [sz, C.POINTER(C.c_uint)]
@@ -307,6 +311,10 @@ class Plan:
         """0 bucket sorter + general sorter for flagged blocks (default), 1 general only, 2 general, prefix doubling only"""
         _chk("glcPlanSetSorter", lib().glcPlanSetSorter(self.handle, int(mode)))
 
+    def set_huff_decoder(self, mode):
+        """the decoder's Huffman kernel: 0 by the call's size (default), 1 always k_dec_huff, 2 always k_dec_huff_lanes"""
+        _chk("glcPlanSetHuffDecoder", lib().glcPlanSetHuffDecoder(self.handle, int(mode)))
+
     def last_flagged_blocks(self):
         a = C.c_uint(0)
         _chk("glcPlanLastSortStats", lib().glcPlanLastSortStats(self.handle, C.byref(a)))
@@ -433,6 +441,27 @@ def huffman_encode_batch(plan, d_sym, n, nblk):
                                      nsub, out["size"].data_ptr(), out["words"].data_ptr(), stride, n, nblk)
     _chk("glcHuffmanEncodeBatch", rc)
     return out
+
+
+def huffman_decode_batch(plan, comp, n, nblk, d_sym=None):
+    """glcHuffmanDecodeBatch on a dict of hist / offsets / words (+ nsub, stride) as huffman_encode_batch returns it: the
+    symbols, nblk rows of n bytes"""
+    import torch
+    if d_sym is None:
+        d_sym = torch.empty(nblk * n, dtype=torch.uint8, device=comp["words"].device)
+    rc = lib().glcHuffmanDecodeBatch(plan.handle, comp["hist"].data_ptr(), comp["offsets"].data_ptr(), comp["nsub"],
+                                     comp["words"].data_ptr(), comp["stride"], d_sym.data_ptr(), n, nblk)
+    _chk("glcHuffmanDecodeBatch", rc)
+    return d_sym
+
+
+def mtf_inverse_batch(plan, d_mtf, n, nblk, d_out=None):
+    """glcMtfInverseBatch (a COMPRESS plan): nblk rows of n MTF bytes -> the bytes they stand for"""
+    import torch
+    if d_out is None:
+        d_out = torch.empty(nblk * n, dtype=torch.uint8, device=d_mtf.device)
+    _chk("glcMtfInverseBatch", lib().glcMtfInverseBatch(plan.handle, d_mtf.data_ptr(), d_out.data_ptr(), n, nblk))
+    return d_out
 
 
 def compress_batch_into(plan, d_in, n, nblk, out):

@@ -203,6 +203,25 @@ CUDPPResult glcDecompressBatchCompact(CUDPPHandle planHandle, const int *d_bwtIn
                                       const unsigned long long *d_blockOffsets, unsigned char *d_out,
                                       size_t numElements, size_t numBlocks);
 
+/* The decoder stage by stage (plans of CUDPP_COMPRESS; entry checks as glcDecompressBatch, corrupt stream data reported
+ * by glcPlanSynchronize the same way).  They exist for tests and A/B timing: glcDecompressBatch runs the same kernels.
+ * glcHuffmanDecodeBatch is the inverse of glcHuffmanEncodeBatch -- the tree from d_hist, then the Huffman decode kernel
+ * alone: block b's numElements symbols go to d_symbols + b * numElements.
+ * glcMtfInverseBatch is the inverse of glcMtfBatch on a COMPRESS plan: rows of numElements MTF bytes at stride
+ * numElements in d_mtf -> the bytes they stand for in d_out, same layout (d_out must not overlap d_mtf). */
+CUDPPResult glcHuffmanDecodeBatch(CUDPPHandle planHandle, const unsigned int *d_hist,
+                                  const unsigned int *d_encodeOffset, size_t offsetStride,
+                                  const unsigned int *d_compressed, size_t compressedStrideWords,
+                                  unsigned char *d_symbols, size_t numElements, size_t numBlocks);
+CUDPPResult glcMtfInverseBatch(CUDPPHandle planHandle, const unsigned char *d_mtf, unsigned char *d_out,
+                               size_t numElements, size_t numBlocks);
+/* Which Huffman decode kernel the plan's decoder runs (glcDecompressBatch[Compact], pipelined or not, and
+ * glcHuffmanDecodeBatch).  0 (default): by the size of the call -- one wave per 4096-symbol sub-block (k_dec_huff), or,
+ * from 32768 sub-blocks in a call, one lane per sub-block (k_dec_huff_lanes); 1: always the first; 2: always the second.
+ * Any other mode: CUDPP_ERROR_ILLEGAL_CONFIGURATION, the setting stays.  Same bytes either way; exists for tests and
+ * A/B timing. */
+CUDPPResult glcPlanSetHuffDecoder(CUDPPHandle planHandle, int mode);
+
 /* Run a plan's work on `hipStream` (a hipStream_t cast to void*; NULL = the
  * default stream, which is what the reference uses). */
 CUDPPResult glcPlanSetStream(CUDPPHandle planHandle, void *hipStream);

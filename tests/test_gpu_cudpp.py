@@ -354,12 +354,15 @@ def _error_table(glc, ctx, cuda):
         "glcHuffmanEncodeBatch": lambda h, n=N, nb=R, st=1: L.glcHuffmanEncodeBatch(h, d, o, o, st, o, o, STRIDE, n, nb),
         "glcDecompressBatch": lambda h, n=N, nb=R, st=1: L.glcDecompressBatch(h, o, o, o, st, o, STRIDE, d2, n, nb),
         "glcDecompressBatchCompact": lambda h, n=N, nb=R, st=1: L.glcDecompressBatchCompact(h, o, o, o, st, o, STRIDE * R, o, d2, n, nb),
+        "glcHuffmanDecodeBatch": lambda h, n=N, nb=R, st=1: L.glcHuffmanDecodeBatch(h, o, o, st, o, STRIDE, d2, n, nb),
+        "glcMtfInverseBatch": lambda h, n=N, nb=R, st=1: L.glcMtfInverseBatch(h, d, d2, n, nb),
         "glcBwtBatch": lambda h, n=N, nb=R, st=1: L.glcBwtBatch(h, d, d2, o, n, nb),
         "glcMtfBatch": lambda h, n=N, nb=R, st=1: L.glcMtfBatch(h, d, d2, n, nb),
         "cudppSuffixArray": lambda h, n=N, nb=R, st=1: L.cudppSuffixArray(h, d, o, n),
     }
     own = {"glcCompressBatch": "compress", "glcCompressBatchCompact": "compress", "glcHuffmanEncodeBatch": "compress",
            "glcDecompressBatch": "compress", "glcDecompressBatchCompact": "compress", "glcBwtBatch": "bwt", "glcMtfBatch": "mtf",
+           "glcHuffmanDecodeBatch": "compress", "glcMtfInverseBatch": "compress",
            "cudppSuffixArray": "sa"}
     checks_datatype = {"glcCompressBatch", "glcCompressBatchCompact", "glcBwtBatch"}      # ... of those a CUDPP_UINT plan exists for here
     checks_offset_stride = {"glcCompressBatch", "glcCompressBatchCompact", "glcHuffmanEncodeBatch"}
@@ -368,11 +371,13 @@ def _error_table(glc, ctx, cuda):
         "glcPlanSetSorter": lambda h, out=True: L.glcPlanSetSorter(h, 0),
         "glcPlanLastSortStats": lambda h, out=True: L.glcPlanLastSortStats(h, one if out else None),
         "glcPlanSetChains": lambda h, out=True: L.glcPlanSetChains(h, -1, 0xFFFFFFFF),
+        "glcPlanSetHuffDecoder": lambda h, out=True: L.glcPlanSetHuffDecoder(h, 0),
         "glcPlanLastTiming": lambda h, out=True: L.glcPlanLastTiming(h, ms4 if out else None),
         "glcPlanKernelProfileEx": lambda h, out=True: L.glcPlanKernelProfileEx(h, 0, name, 96, three if out else None),
         "glcCompactStreams": lambda h, out=True: L.glcCompactStreams(h, o, STRIDE, o, R, o if out else None, o),
     }
     needs_sorter = {"glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanSetChains"}
+    needs_compress = {"glcPlanSetHuffDecoder"}
     has_out = {"glcPlanLastSortStats": HANDLE, "glcPlanLastTiming": HANDLE, "glcPlanKernelProfileEx": HANDLE,
                "glcCompactStreams": CONFIG}                # (glcCompactStreams' arrays are arguments, not the getter's output)
     algs = dict(compress=glc.CUDPP_COMPRESS, bwt=glc.CUDPP_BWT, mtf=glc.CUDPP_MTF, sa=glc.CUDPP_SA)
@@ -431,11 +436,16 @@ def _error_table(glc, ctx, cuda):
             for k, pl in plans.items():
                 if nm in needs_sorter and k == "mtf":
                     expect((nm, "plan of mtf"), f(pl.handle), PLAN)
+                elif nm in needs_compress and k != "compress":
+                    expect((nm, "plan of " + k), f(pl.handle), PLAN)
                 elif nm != "glcCompactStreams":                 # (takes any plan, and would run)
                     expect((nm, "plan of " + k), f(pl.handle), glc.CUDPP_SUCCESS)
         for mode in (-1, 8):
             expect(("glcPlanSetSorter", "mode %d" % mode), L.glcPlanSetSorter(plans["bwt"].handle, mode), CONFIG)
             expect(("glcPlanSetSorter", "mode %d, plan of mtf" % mode), L.glcPlanSetSorter(plans["mtf"].handle, mode), PLAN)
+        for mode in (-1, 3):
+            expect(("glcPlanSetHuffDecoder", "mode %d" % mode), L.glcPlanSetHuffDecoder(plans["compress"].handle, mode), CONFIG)
+            expect(("glcPlanSetHuffDecoder", "mode %d, plan of bwt" % mode), L.glcPlanSetHuffDecoder(plans["bwt"].handle, mode), PLAN)
         for index in (-1, PROF_NSLOT):
             expect(("glcPlanKernelProfileEx", "index %d" % index),
                    L.glcPlanKernelProfileEx(plans["sa"].handle, index, name, 96, three), CONFIG)
