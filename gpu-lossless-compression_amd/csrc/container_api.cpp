@@ -4,7 +4,8 @@
 //
 // Format.  A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says
 // two things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
-// shuffle of shuffle.hip, the fused delta + shuffle of delta.hip, or under version 11 that delta with the flags' lag and fold, lag.hip),
+// shuffle of shuffle.hip, the fused delta + shuffle of delta.hip, under version 11 that delta with the flags' lag and fold, lag.hip,
+// or under version 12 the 2-D predictor of grid.hip with the row width of the header's word 3),
 // and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always; 2 order-0 Huffman, 3 its sparse form (sparse.hip), 4 the BWT codec's zero-run form (zrun.hip), 5 the order-0
 // codec's rANS form (ans.hip) and 6 its dedup form (dedup.hip) where kind2_legal() .. kind6_legal() say so).  ct_legal() is the
@@ -123,7 +124,7 @@ unsigned long long frame_bound(uint32_t nb, uint32_t blk_len)
 void make_header(uint32_t h[8], const CtFormat &f, uint32_t block_len, unsigned long long total)
 {
     h[0] = CT_MAGIC_STREAM; h[1] = f.version | (f.flags << 16);
-    h[2] = block_len; h[3] = f.elem;
+    h[2] = block_len; h[3] = f.word3();
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
     h[6] = crc32_host(h, 24); h[7] = 0;
 }
@@ -1318,7 +1319,7 @@ std::vector<uint8_t> needed_blocks(const CtFormat &fmt, uint32_t nb, uint32_t bl
     const unsigned long long e = fmt.elem, q = F / e;
     const unsigned long long lo = a / e, hi = std::min(q, (b + e - 1) / e);
     if (lo < hi) {                                              // (a range inside the len % elem tail needs no element)
-        *i0 = fmt.delta() ? lo & ~2047ull : lo;
+        *i0 = fmt.grid() ? lo - lo % ct_grid_period(fmt.width) : fmt.delta() ? lo & ~2047ull : lo;   // (the band's, the run's start)
         *i1 = hi;
         for (unsigned long long j = 0; j < e; j++) mark(j * q + *i0, j * q + *i1);
     }
@@ -1382,7 +1383,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         if (i0 < i1) {                                          // elements [i0, i1) into the second staging, [a, min(b, q e)) out of them
             uint8_t *el = nullptr;
             CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
-            if (ff.delta()) CT_TRY(unlag_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.lag(), ff.fold(), i0, i1 - i0));
+            if (ff.grid()) CT_TRY(ungrid_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.width, ff.fold(), i0, i1 - i0));
+            else if (ff.delta()) CT_TRY(unlag_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.lag(), ff.fold(), i0, i1 - i0));
             else CT_TRY(unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
             const unsigned long long top = std::min(b, q * e);
             if ((r = io.deliver(el + (a - i0 * e), top - a, at + a)) != CUDPP_SUCCESS) return r;
@@ -1491,7 +1493,7 @@ CUDPPResult glcContainerIndexInfo(const GlcContainerIndex *index, unsigned long 
 {
     if (!index || !out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     out[0] = index->total; out[1] = index->block_len; out[2] = index->frames.size();
-    out[3] = index->fmt.version | ((unsigned long long)index->fmt.flags << 16) | ((unsigned long long)index->fmt.elem << 32);
+    out[3] = index->fmt.version | ((unsigned long long)index->fmt.flags << 16) | ((unsigned long long)index->fmt.word3() << 32);
     return CUDPP_SUCCESS;
 }
 
@@ -1719,6 +1721,18 @@ CUDPPResult glcPlanGetContainerDeltaLag(CUDPPHandle plan, unsigned int *lag, uns
     if (!fold) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const CUDPPResult r = ct_get(plan, lag, [](const CtSettings &s) { return s.lag; });
     return r != CUDPP_SUCCESS ? r : ct_get(plan, fold, [](const CtSettings &s) { return s.fold; });
+}
+
+CUDPPResult glcPlanSetContainerDeltaGrid(CUDPPHandle plan, unsigned int width, unsigned int fold)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_delta_grid(width, fold); });
+}
+
+CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, unsigned int *fold)
+{
+    if (!fold) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const CUDPPResult r = ct_get(plan, width, [](const CtSettings &s) { return s.grid_width; });
+    return r != CUDPP_SUCCESS ? r : ct_get(plan, fold, [](const CtSettings &s) { return s.grid_fold; });
 }
 
 } // extern "C"

@@ -103,6 +103,13 @@ hipError_t lag_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, u
                               uint32_t fold, bool inverse);
 hipError_t unlag_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
                                         uint32_t lag, uint32_t fold, unsigned long long first, unsigned long long count);
+// the 2-D predictor + shuffle and its inverses (grid.hip): the delta at (1, fold) over the differences to the element `width`
+// places back, the row above, within bands of ct_grid_period(width) elements; the rules of the delta forms, the range form's
+// `first` a multiple of the period
+hipError_t grid_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, uint32_t width,
+                               uint32_t fold, bool inverse);
+hipError_t ungrid_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                         uint32_t width, uint32_t fold, unsigned long long first, unsigned long long count);
 
 // Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
 // the allocation it places, so the size and the pointers cannot disagree.
@@ -237,29 +244,42 @@ __host__ __device__ inline bool ct_lag_flags_legal(uint32_t flags)
 {
     return (flags & CT_FLAG_DELTA) && !(flags & ~(CT_FLAG_DELTA | CT_FLAG_FOLD | CT_LAG_MASK)) && (flags & (CT_FLAG_FOLD | CT_LAG_MASK));
 }
+// 12: version 8's stream behind the 2-D predictor of grid.hip: flags 1 | fold << 1 | 4 (bit 2 the grid flag, the lag field 0, no
+// other bit) and the header's word 3 elem | width << 8 with elem 2, 4 or 8 and the row width 2..65536.  Word 3 is split under this
+// version only: under every other it is the element size, whole
+constexpr uint32_t CT_VERSION_GRID = 12;
+constexpr uint32_t CT_FLAG_GRID = 4, CT_GRID_MIN_WIDTH = 2, CT_GRID_MAX_WIDTH = 65536, CT_WIDTH_SHIFT = 8;
+__host__ __device__ inline bool ct_grid_width_ok(uint32_t width) { return width >= CT_GRID_MIN_WIDTH && width <= CT_GRID_MAX_WIDTH; }
+// the period of the predictor: the row above is subtracted only inside a band of this many elements (about 32 rows, whole runs)
+__host__ __device__ inline uint32_t ct_grid_period(uint32_t width) { return 2048u * ((width + 63) / 64); }
+__host__ __device__ inline bool ct_grid_flags_legal(uint32_t flags) { return (flags & ~CT_FLAG_FOLD) == (CT_FLAG_DELTA | CT_FLAG_GRID); }
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
-// its filter-auto setting version 10 and its delta-lag setting version 11 (either is only ever on with the auto mode, so that
-// mode's bits come with it)
+// its filter-auto setting version 10, its delta-lag setting version 11 and its grid setting version 12 (each is only ever on with
+// the auto mode, so that mode's bits come with it)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
-constexpr uint32_t CT_READS_LAG = 64;
+constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_LAG + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F};
-    return version <= CT_VERSION_LAG ? K[version] : 0u;
+    constexpr uint32_t K[CT_VERSION_GRID + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F, 0x2F};
+    return version <= CT_VERSION_GRID ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
 // went through before its blocks were cut (none / shuffle / delta + shuffle over elements of `elem` bytes) and whether record
 // kind 2 is legal.  The legal triples are one table in container_api.cpp, read by the writer and the reader alike (version 11's
-// are a family of flags over it: the delta's lag and fold).
+// are a family of flags over it: the delta's lag and fold; version 12's a family of row widths, which ride in the element word).
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
+    uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     // the delta's lag and fold: (1, 0) below version 11
     __host__ __device__ uint32_t lag() const { return version == CT_VERSION_LAG ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
-    __host__ __device__ uint32_t fold() const { return version == CT_VERSION_LAG && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
+    __host__ __device__ uint32_t fold() const { return (version == CT_VERSION_LAG || version == CT_VERSION_GRID) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
+    __host__ __device__ bool grid() const { return version == CT_VERSION_GRID; }
+    // the stream header's word 3: the element size, under version 12 with the row width above it
+    __host__ __device__ uint32_t word3() const { return elem | width << CT_WIDTH_SHIFT; }
     __host__ __device__ uint32_t kinds() const { return ct_kinds(version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4)
     __host__ __device__ bool kind2_legal() const { return (kinds() >> 2 & 1u) != 0; }
     __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
@@ -272,7 +292,7 @@ struct CtFormat {
         return version == CT_VERSION_SPARSE ? CT_READS_SPARSE : version == CT_VERSION_RUNS ? CT_READS_RUNS :
                version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
                version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
-               version == CT_VERSION_LAG ? CT_READS_LAG : 0u;
+               version == CT_VERSION_LAG ? CT_READS_LAG : version == CT_VERSION_GRID ? CT_READS_GRID : 0u;
     }
 };
 // a frame header's word 3.  Versions 1 to 9 keep it 0; under version 10 it is the frame's filter.  ct_frame_word_legal() is the
@@ -294,6 +314,7 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
 // a format's filter over one segment, or its inverse
 inline hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
 {
+    if (f.grid()) return grid_shuffle_device(st, in, out, len, f.elem, f.width, f.fold(), inverse);
     if (f.delta()) return lag_shuffle_device(st, in, out, len, f.elem, f.lag(), f.fold(), inverse);   // ((1, 0): delta.hip's kernels)
     return shuffle_device(st, in, out, len, f.elem, inverse);
 }
@@ -317,7 +338,10 @@ __host__ __device__ inline CtLegal ct_legal(uint32_t i)
 __host__ __device__ inline bool format_legal(const CtFormat &f)
 {
     // (version 11 is a family of flags, not rows: every lag and fold over the three element sizes)
-    if (f.version == CT_VERSION_LAG) return ct_lag_flags_legal(f.flags) && f.elem <= 8 && (CT_ELEMS >> f.elem & 1);
+    if (f.version == CT_VERSION_LAG) return ct_lag_flags_legal(f.flags) && f.elem <= 8 && (CT_ELEMS >> f.elem & 1) && !f.width;
+    // (so is version 12: either fold and every row width over the three element sizes)
+    if (f.version == CT_VERSION_GRID) return ct_grid_flags_legal(f.flags) && f.elem <= 8 && (CT_ELEMS >> f.elem & 1) && ct_grid_width_ok(f.width);
+    if (f.width) return false;
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {
         const CtLegal l = ct_legal(i);
         if (l.version == f.version && l.flags == f.flags && f.elem <= 8 && (l.elems >> f.elem & 1)) return true;
@@ -381,10 +405,11 @@ __host__ __device__ inline uint32_t crc32_bytes(const CrcTables &C, const void *
     return ~r;
 }
 
-// the reader's format: header words 1 (version, flags in the upper half) and 3 (elem)
+// the reader's format: header words 1 (version, flags in the upper half) and 3 (elem; under version 12 elem | width << 8)
 __host__ __device__ inline bool parse_format(const uint32_t h[8], CtFormat *f)
 {
-    f->version = h[1] & 0xFFFFu; f->flags = h[1] >> 16; f->elem = h[3];
+    f->version = h[1] & 0xFFFFu; f->flags = h[1] >> 16; f->elem = h[3]; f->width = 0;
+    if (f->version == CT_VERSION_GRID) { f->elem = h[3] & 0xFFu; f->width = h[3] >> CT_WIDTH_SHIFT; }
     return format_legal(*f);
 }
 
@@ -504,7 +529,15 @@ struct CtSettings {
     uint32_t lag = 1, fold = 0;
     bool lag_on() const { return lag != 1 || fold != 0; }
     bool lag_fits() const { return codec == CT_CODEC_HUFF0 && mode == CT_MODE_AUTO && shuffle && delta && !filter_auto; }
-    void lag_keep() { if (!lag_fits()) { lag = 1; fold = 0; } }
+    // grid: the delta is the 2-D predictor of row width grid_width (0 = off), its sign folded where grid_fold = 1 (grid.hip; the
+    // writer writes version 12).  Only ever on with the lag's prerequisites and the lag itself at (1, 0); whatever ends one of
+    // them puts it back to off
+    uint32_t grid_width = 0, grid_fold = 0;
+    bool grid_on() const { return grid_width != 0; }
+    void lag_keep()
+    {
+        if (!lag_fits()) { lag = 1; fold = 0; grid_width = 0; grid_fold = 0; }
+    }
     bool set_shuffle(uint32_t elem)
     {
         if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE || filter_auto)) return false;
@@ -522,8 +555,14 @@ struct CtSettings {
     }
     bool set_delta_lag(uint32_t l, uint32_t f)
     {
-        if (l < 1 || l > 16 || f > 1 || ((l != 1 || f) && !lag_fits())) return false;
+        if (l < 1 || l > 16 || f > 1 || ((l != 1 || f) && (!lag_fits() || grid_on()))) return false;
         lag = l; fold = f;
+        return true;
+    }
+    bool set_delta_grid(uint32_t w, uint32_t f)
+    {
+        if (f > 1 || (w && (!ct_grid_width_ok(w) || !lag_fits() || lag_on()))) return false;
+        grid_width = w; grid_fold = w ? f : 0;
         return true;
     }
     bool set_codec(uint32_t c)
@@ -558,7 +597,7 @@ struct CtSettings {
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
                mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) |
-                                      (lag_on() ? CT_READS_LAG : 0u) :
+                                      (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
@@ -581,6 +620,12 @@ inline CtFormat format_of(const CtSettings &s)
     if (s.lag_on()) {                                         // (what (1, 0) does, version 8 says)
         f.version = CT_VERSION_LAG;
         f.flags |= (s.fold ? CT_FLAG_FOLD : 0u) | (s.lag - 1) << CT_LAG_SHIFT;
+        return f;
+    }
+    if (s.grid_on()) {
+        f.version = CT_VERSION_GRID;
+        f.flags |= (s.grid_fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID;
+        f.width = s.grid_width;
         return f;
     }
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {

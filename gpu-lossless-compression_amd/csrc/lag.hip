@@ -12,7 +12,8 @@
 //
 // The geometry is delta.hip's: one workgroup of 256 lanes per 16 KiB tile, a tile holds whole runs, so nothing in front of a
 // tile is ever read and no workgroup waits for another; aligned 16-byte granule loads at any alignment of the buffers; the
-// plane build with its head / body / tail stores; single segment, 64-bit offsets.
+// plane build with its head / body / tail stores; single segment, 64-bit offsets.  The element-wise arithmetic on granules, the
+// LDS read at any byte and the plane build are lag_tile.h's, which grid.hip's forward shares.
 //
 // Forward, one tile: the raw image as in delta.hip, with 32 words in front of it: the predecessors of a granule are the 16 bytes
 // LAG ELEM <= 128 bytes in front of it, taken like the granule itself as five aligned dwords and v_alignbyte.  An element with
@@ -30,92 +31,19 @@
 // delta.hip.
 //
 // LDS: forward 34960 bytes (raw image 16528, padded image 18432), inverse 32928 bytes: four workgroups per CU each.
-#include "shuffle_tile.h"
+#include "lag_tile.h"
 
 namespace glc {
 
-constexpr uint32_t LG_RUN = 2048;                              // elements between two restarts (delta.hip's DL_RUN)
 constexpr uint32_t LG_MAX_LAG = 16;
 constexpr uint32_t LG_PASSES = SH_TILE / 16 / SH_THREADS;      // element-aligned granules of a tile per lane
 constexpr uint32_t LG_RAW_FRONT = LG_MAX_LAG * 8 / 4;          // forward: words in front of the raw image, the longest way back
 constexpr uint32_t LG_RAW_WORDS = LG_RAW_FRONT + 4 * SH_NGI;
-constexpr uint32_t LG_IMG_WORDS = SH_TILE / 4 + SH_TILE / 32;  // padded image at s = 0 (ELEM = 2 pads most)
 constexpr uint32_t LG_REGION_WORDS = SH_TILE / 4 + 4 * 8;      // inverse: ELEM plane regions of 16 NGP bytes; then the second image
 constexpr uint32_t LG_FRONT = 4;                               // inverse: words in front of an image (a masked read may start 15 bytes early)
 constexpr uint32_t LG_FLAT_WORDS = LG_FRONT + SH_TILE / 4 + 4; // and one granule of slack behind it for the output cut
 static_assert(LG_PASSES == 4, "four passes of 256 lanes cover a tile");
 static_assert(LG_REGION_WORDS >= LG_FLAT_WORDS, "the regions' space holds an image");
-
-typedef unsigned short lg_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ lg_us2 lg_halves(uint32_t v) { return __builtin_bit_cast(lg_us2, v); }
-__device__ __forceinline__ uint32_t lg_word(lg_us2 v) { return __builtin_bit_cast(uint32_t, v); }
-
-// p with every element zeroed whose run-relative byte, gb + its offset in the granule, is below dist
-template <uint32_t ELEM>
-__device__ __forceinline__ void lg_mask(uint32_t (&p)[4], uint32_t gb, uint32_t dist)
-{
-#pragma unroll
-    for (uint32_t m = 0; m < 4; m++) {
-        if constexpr (ELEM == 2) p[m] &= (gb + 4 * m >= dist ? 0xFFFFu : 0u) | (gb + 4 * m + 2 >= dist ? 0xFFFF0000u : 0u);
-        else p[m] = gb + (ELEM == 8 ? 8 * (m / 2) : 4 * m) >= dist ? p[m] : 0u;
-    }
-}
-
-// c +- p, element by element
-template <uint32_t ELEM, bool SUB>
-__device__ __forceinline__ void lg_combine(uint32_t (&c)[4], const uint32_t (&p)[4])
-{
-    if constexpr (ELEM == 8) {
-#pragma unroll
-        for (uint32_t i = 0; i < 2; i++) {
-            const unsigned long long a = c[2 * i] | ((unsigned long long)c[2 * i + 1] << 32), b = p[2 * i] | ((unsigned long long)p[2 * i + 1] << 32);
-            const unsigned long long r = SUB ? a - b : a + b;
-            c[2 * i] = (uint32_t)r; c[2 * i + 1] = (uint32_t)(r >> 32);
-        }
-    } else {
-#pragma unroll
-        for (uint32_t m = 0; m < 4; m++) {
-            if constexpr (ELEM == 4) c[m] = SUB ? c[m] - p[m] : c[m] + p[m];
-            else c[m] = lg_word(SUB ? lg_halves(c[m]) - lg_halves(p[m]) : lg_halves(c[m]) + lg_halves(p[m]));
-        }
-    }
-}
-
-// the fold (fold = 0: nothing) and its inverse, element by element
-template <uint32_t ELEM, bool INVERSE>
-__device__ __forceinline__ void lg_fold(uint32_t (&d)[4], uint32_t fold)
-{
-    if constexpr (ELEM == 8) {
-#pragma unroll
-        for (uint32_t i = 0; i < 2; i++) {
-            const unsigned long long v = d[2 * i] | ((unsigned long long)d[2 * i + 1] << 32);
-            const unsigned long long r = INVERSE ? (v >> fold) ^ (0ull - (v & fold)) : (v << fold) ^ (0ull - ((v >> 63) & fold));
-            d[2 * i] = (uint32_t)r; d[2 * i + 1] = (uint32_t)(r >> 32);
-        }
-    } else if constexpr (ELEM == 4) {
-#pragma unroll
-        for (uint32_t m = 0; m < 4; m++) d[m] = INVERSE ? (d[m] >> fold) ^ (0u - (d[m] & fold)) : (d[m] << fold) ^ (0u - ((d[m] >> 31) & fold));
-    } else {
-        const lg_us2 f = {(unsigned short)fold, (unsigned short)fold}, z = {0, 0}, s = {15, 15};
-#pragma unroll
-        for (uint32_t m = 0; m < 4; m++) {
-            const lg_us2 v = lg_halves(d[m]);
-            d[m] = lg_word(INVERSE ? (v >> f) ^ (z - (v & f)) : (v << f) ^ (z - ((v >> s) & f)));
-        }
-    }
-}
-
-// the 16 bytes at byte b (b >= -4 * front of the caller's slack) of an LDS image whose byte 0 is at words: five aligned dwords
-__device__ __forceinline__ void lg_read16(const uint32_t *words, int b, uint32_t (&o)[4])
-{
-    const uint32_t *p = words + (b >> 2);
-    const uint32_t sb = (uint32_t)b & 3;
-    uint32_t w[5];
-#pragma unroll
-    for (int m = 0; m < 5; m++) w[m] = p[m];
-#pragma unroll
-    for (int m = 0; m < 4; m++) o[m] = __builtin_amdgcn_alignbyte(w[m + 1], w[m], sb);
-}
 
 // ---------------------------------------------------------------------------
 // forward: elements [i0, i0 + cnt) of a segment whose q whole elements start at `in`; i0 is a multiple of RUN
@@ -124,8 +52,6 @@ template <uint32_t ELEM>
 __device__ __forceinline__ void lg_tile_forward(const uint8_t *in, uint8_t *out, unsigned long long q, unsigned long long i0,
                                                 uint32_t cnt, uint32_t lag, uint32_t fold, uint32_t *raw, uint32_t *img)
 {
-    using G = ShGeom<ELEM>;
-    constexpr uint32_t SH = 4 + G::LG;                         // log2 of the bytes between two pad dwords
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const unsigned long long A = (unsigned long long)(uintptr_t)in + i0 * ELEM, A0 = A & ~15ull;
     const uint32_t s = (uint32_t)(A - A0);
@@ -142,44 +68,10 @@ __device__ __forceinline__ void lg_tile_forward(const uint8_t *in, uint8_t *out,
         lg_mask<ELEM>(p, (16 * g) & (LG_RUN * ELEM - 1), dist);
         lg_combine<ELEM, true>(c, p);
         lg_fold<ELEM, false>(c, fold);
-        uint32_t *dst = img + 4 * g + (g >> G::LG);
-        dst[0] = c[0]; dst[1] = c[1]; dst[2] = c[2]; dst[3] = c[3];
+        lg_img_store<ELEM>(img, g, c);
     }
     __syncthreads();
-    // planes from the padded image, as delta.hip's forward tile: byte B = ELEM e + j lies at B + 4 * (B >> SH)
-    const uint8_t *ldsb = reinterpret_cast<const uint8_t *>(img);
-#pragma unroll
-    for (uint32_t pp = 0; pp < G::PPW; pp++) {
-        const uint32_t j = G::WPP > 1 ? wave % ELEM : wave + 4 * pp;
-        const uint32_t sub = G::WPP > 1 ? wave / ELEM : 0;
-        const unsigned long long O = (unsigned long long)(uintptr_t)out + j * q + i0;
-        const ShRun r = sh_run(O, cnt);
-        const uint32_t c = j + ELEM * r.head;
-        const uint32_t ru = c & ((16u << G::LG) - 1);
-        uint4 *dst = reinterpret_cast<uint4 *>(out + (j * q + i0 + r.head));
-        for (uint32_t h = sub * 64 + lane; h < r.nf; h += 64 * G::WPP) {
-            const uint32_t B0 = c + ((16 * h) << G::LG);
-            const uint32_t P0 = B0 + 4 * (B0 >> SH);
-            uint32_t b[16];
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++) b[k] = ldsb[P0 + ELEM * k + 4 * ((ru + ELEM * k) >> SH)];
-            dst[h] = sh_pack(b);
-        }
-    }
-    {
-        const uint32_t j = tid >> 5, x = tid & 31;
-        if (j < ELEM) {
-            const unsigned long long O = (unsigned long long)(uintptr_t)out + j * q + i0;
-            const ShRun r = sh_run(O, cnt);
-            const bool is_head = x < 16;
-            const uint32_t y = x & 15;
-            if (y < (is_head ? r.head : r.tail)) {
-                const uint32_t e = is_head ? y : r.head + 16 * r.nf + y;
-                const uint32_t B = j + ELEM * e;
-                out[j * q + i0 + e] = ldsb[B + 4 * (B >> SH)];
-            }
-        }
-    }
+    lg_planes<ELEM>(img, out, q, i0, cnt, tid, lane, wave);
 }
 
 // ---------------------------------------------------------------------------

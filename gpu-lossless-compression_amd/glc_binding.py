@@ -694,6 +694,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcDedupWorkBytes", "glcDedupMapSegments", "glcDedupFillSegments", "glcPlanSetContainerDedup", "glcPlanGetContainerDedup",
                      "glcLagDeltaShuffleDevice", "glcUnlagDeltaUnshuffleDevice", "glcUnlagDeltaUnshuffleRangeDevice",
                      "glcPlanSetContainerDeltaLag", "glcPlanGetContainerDeltaLag",
+                     "glcGridDeltaShuffleDevice", "glcUngridDeltaUnshuffleDevice", "glcUngridDeltaUnshuffleRangeDevice",
+                     "glcPlanSetContainerDeltaGrid", "glcPlanGetContainerDeltaGrid",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -747,6 +749,11 @@ def _ct():
         for nm in ("glcLagDeltaShuffleDevice", "glcUnlagDeltaUnshuffleDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, vp]
         L.glcUnlagDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
+        L.glcPlanSetContainerDeltaGrid.argtypes = [sz, C.c_uint, C.c_uint]
+        L.glcPlanGetContainerDeltaGrid.argtypes = [sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        for nm in ("glcGridDeltaShuffleDevice", "glcUngridDeltaUnshuffleDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, vp]
+        L.glcUngridDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
         for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
         L.glcContainerIndexFree.restype = None
@@ -950,6 +957,21 @@ def container_get_delta_lag(plan):
     lag, fold = C.c_uint(0), C.c_uint(0)
     _chk("glcPlanGetContainerDeltaLag", _ct().glcPlanGetContainerDeltaLag(plan.handle, C.byref(lag), C.byref(fold)))
     return int(lag.value), int(fold.value)
+
+
+def container_set_delta_grid(plan, width, fold):
+    """the row width and fold of the 2-D predictor of the plan's container ENCODER (format version 12: the delta over the
+    differences to the element `width` places back, the row above; the sign folded into bit 0 where fold is 1); width 0 is off.
+    Any other width (2 to 65536) needs the order-0 codec, the auto mode, the shuffle and the delta on, filter-auto off and the
+    delta-lag setting at (1, 0), and whatever ends one of them puts it back to off.  It is also the version the plan reads: on,
+    versions 1 to 5, 7, 8 and 12; off, a version-12 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerDeltaGrid", _ct().glcPlanSetContainerDeltaGrid(plan.handle, int(width), int(fold)))
+
+
+def container_get_delta_grid(plan):
+    width, fold = C.c_uint(0), C.c_uint(0)
+    _chk("glcPlanGetContainerDeltaGrid", _ct().glcPlanGetContainerDeltaGrid(plan.handle, C.byref(width), C.byref(fold)))
+    return int(width.value), int(fold.value)
 
 
 def container_last_filters(plan):
@@ -1269,6 +1291,18 @@ def unlag_delta_unshuffle(d_in, elem, lag, fold, out=None, stream=None):
     return _lag_shuffle("glcUnlagDeltaUnshuffleDevice", d_in, elem, lag, fold, out, stream)
 
 
+def grid_delta_shuffle(d_in, elem, width, fold, out=None, stream=None):
+    """delta_shuffle over the differences to the element `width` places back (the row above of row-major gridded data, 2 to 65536
+    elements wide) within bands of 2048 * ceil(width / 64) elements, the sign folded into bit 0 where fold is 1.  The rules of
+    shuffle"""
+    return _lag_shuffle("glcGridDeltaShuffleDevice", d_in, elem, width, fold, out, stream)
+
+
+def ungrid_delta_unshuffle(d_in, elem, width, fold, out=None, stream=None):
+    """the inverse of grid_delta_shuffle"""
+    return _lag_shuffle("glcUngridDeltaUnshuffleDevice", d_in, elem, width, fold, out, stream)
+
+
 def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):
     """shuffle (or unshuffle) the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in into the same ranges of d_out"""
     import torch
@@ -1311,7 +1345,7 @@ class ContainerIndex:
         self.ptr = ptr
 
     def info(self):
-        """(total_len, block_len, frames, version, flags, elem)"""
+        """(total_len, block_len, frames, version, flags, elem); under version 12 the last is the header's word 3, elem | width << 8"""
         a = (C.c_ulonglong * 4)()
         _chk("glcContainerIndexInfo", _ct().glcContainerIndexInfo(self.ptr, a))
         return int(a[0]), int(a[1]), int(a[2]), int(a[3]) & 0xFFFF, (int(a[3]) >> 16) & 0xFFFF, int(a[3]) >> 32
@@ -1433,4 +1467,18 @@ def unlag_delta_unshuffle_range(d_in, elem, lag, fold, first, count, out=None, s
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
     _chk("glcUnlagDeltaUnshuffleRangeDevice", _ct().glcUnlagDeltaUnshuffleRangeDevice(
         x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(lag), int(fold), int(first), int(count), stream))
+    return out
+
+
+def ungrid_delta_unshuffle_range(d_in, elem, width, fold, first, count, out=None, stream=None):
+    """elements [first, first + count) of ungrid_delta_unshuffle(d_in, elem, width, fold); first a multiple of the period,
+    2048 * ceil(width / 64)"""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
+    _chk("glcUngridDeltaUnshuffleRangeDevice", _ct().glcUngridDeltaUnshuffleRangeDevice(
+        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(fold), int(first), int(count), stream))
     return out

@@ -191,6 +191,23 @@ CUDPPResult glcUnlagDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, uns
                                               unsigned int lag, unsigned int fold, unsigned long long first,
                                               unsigned long long count, void *stream);
 
+/* The 2-D (row-stride) predictor (csrc/grid.hip), for row-major gridded data -- 16-bit images and depth maps, detector frames, 2-D
+ * slices of float32 or float64 fields, integer rasters: the delta with a folded sign over the differences to the element one row
+ * above.  With arithmetic modulo 2^(8 elem), `width` the row width in elements, 2..65536, and P = 2048 * ceil(width / 64):
+ * v[i] = x[i] where i mod P < width and x[i] - x[i - width] elsewhere; d[i] = v[i] where i mod 2048 == 0 and v[i] - v[i - 1]
+ * elsewhere; f[i] = d[i], or with fold = 1 (d[i] << 1) ^ (0 - (d[i] >> (8 elem - 1))); out[j * q + i] = byte j of f[i]; the last
+ * len % elem bytes copied in place.  The rule is linear in i: a segment needs no row alignment.  The inverse undoes the fold, sums
+ * d along every run of 2048 and then adds the row above up every band of P elements.  The rules of glcDeltaShuffleDevice; a width
+ * outside 2..65536 and a fold above 1 are refused like a bad elem.  The range form is glcUndeltaUnshuffleRangeDevice's with `first`
+ * a multiple of P. */
+CUDPPResult glcGridDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                      unsigned int fold, void *stream);
+CUDPPResult glcUngridDeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                          unsigned int fold, void *stream);
+CUDPPResult glcUngridDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                               unsigned int width, unsigned int fold, unsigned long long first,
+                                               unsigned long long count, void *stream);
+
 /* The two passes of the sparse mode as batched calls (csrc/sparse.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of
  * its base, cut into chunks of 64 bytes (the last may be short); d_fill[i] & 255 is its fill byte, given by the caller; its mask is
  * row i of d_mask, rows of ceil(ceil(maxLen / 64) / 32) words: bit c % 32 of word c / 32 is 1 when chunk c is kept, 0 when every
@@ -560,6 +577,19 @@ CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on);
  * a stream-header failure.  Not combined with filter-auto, the BWT codec, the CHOOSE codec or the other order-0 modes. */
 CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold);
 CUDPPResult glcPlanGetContainerDeltaLag(CUDPPHandle plan, unsigned int *lag, unsigned int *fold);
+
+/* The row width and fold of the ENCODER's 2-D predictor (glcGridDeltaShuffleDevice); width 0 = off, the default.  Any other width
+ * needs what glcPlanSetContainerDeltaLag needs -- the order-0 codec, the auto mode on, the shuffle at 2, 4 or 8, the delta on and
+ * filter-auto off -- and the delta-lag setting at (1, 0); any other state, a width outside 2..65536 and a fold above 1 are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.  While it is on, glcPlanSetContainerDeltaLag with anything but
+ * (1, 0) is refused.  Whatever ends one of the prerequisites puts it back to off; a change among elem 2, 4 and 8 keeps it.  The
+ * stream is format version 12: version 8's frames, the header's flags 1 | fold << 1 | 4 and its word 3 elem | width << 8.  Decode,
+ * index and range reads take width and fold from the stream header, never from the plan; glcContainerIndexInfo's fourth word
+ * carries word 3 as it stands.  The setting is also the version the plan speaks: with it on the plan reads versions 1 to 5, 7, 8
+ * and 12 (not 11); every other plan refuses a version-12 stream as a stream-header failure.  With it off every stream is written
+ * as before. */
+CUDPPResult glcPlanSetContainerDeltaGrid(CUDPPHandle plan, unsigned int width, unsigned int fold);
+CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, unsigned int *fold);
 
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.

@@ -52,9 +52,14 @@ settings alone, which is also what a build without the setting can run.
 repeated to the size asked for --, or any typed kind; --rounds R, at least 1) is the lag section: the order-0 codec with the auto
 mode on under the shuffle alone, the plain delta (both format version 8) and the delta with lag L and the fold (format version
 11), interleaved, with the same output as the filter-auto section; --lag 1 without --fold runs the first two only.
+
+--grid W [--fold] (with --data img16, field32 or walk32 of tests/grid_inputs.py at row width W -- about 32 MiB of whole rows
+generated on the host and repeated --, or any typed kind; --rounds R, at least 1) is the grid section: the lag section's settings at
+lag 1 -- the shuffle alone, the plain delta, with --fold the folded delta (format version 11) -- and the 2-D predictor of row width
+W (glcPlanSetContainerDeltaGrid, format version 12), interleaved, with the same output.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
-                                [--filter-auto | --filter-auto-off-only]"""
+                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] | --grid W [--fold]]"""
 import argparse
 import json
 import os
@@ -66,7 +71,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
 DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0,
-             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4}
+             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4, "img16": 2, "field32": 4, "walk32": 4}
 LAG_PIECE = 32 * MiB                                           # what tests/lag_inputs.py generates on the host; repeated on the device
 
 
@@ -459,16 +464,17 @@ def filter_auto_section(torch, glc, plan, d_in, total, elem, delta, rounds, with
     return res
 
 
-def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
-    """the order-0 container with the auto mode on under "shuffle" (the shuffle alone), "delta" (the plain delta) and "lag" (the
-    delta with `lag` and `fold`, format version 11; left out at (1, 0)), interleaved: `rounds` rounds of one encode and one decode
-    per setting after one untimed round, each timed with device events on the plan's (the default) stream"""
+def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
+    """the order-0 container with the auto mode on under "shuffle" (the shuffle alone), "delta" (the plain delta), "lag" (the
+    delta with `lag` and `fold`, format version 11; left out at (1, 0)) and, with a row width `grid`, "grid" (the 2-D predictor
+    with `fold`, format version 12), interleaved: `rounds` rounds of one encode and one decode per setting after one untimed
+    round, each timed with device events on the plan's (the default) stream"""
     n = plan.n
     cap = glc.container_bound(total, n)
     cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
     out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
     d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
-    settings = ["shuffle", "delta"] + (["lag"] if (lag, fold) != (1, 0) else [])
+    settings = ["shuffle", "delta"] + (["lag"] if (lag, fold) != (1, 0) else []) + (["grid"] if grid else [])
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
     glc.container_set_auto(plan, 1)
     glc.container_set_shuffle(plan, elem)
@@ -487,6 +493,8 @@ def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
             glc.container_set_delta(plan, 0 if s == "shuffle" else 1)      # (off: the lag goes back to (1, 0) with it)
             if s == "lag":
                 glc.container_set_delta_lag(plan, lag, fold)
+            if s == "grid":
+                glc.container_set_delta_grid(plan, grid, fold)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -494,6 +502,8 @@ def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
                 plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
             if s == "lag":
                 glc.container_set_delta_lag(plan, 1, 0)
+            if s == "grid":
+                glc.container_set_delta_grid(plan, 0, 0)
             if r == 0:
                 assert torch.equal(out, d_in) and int(d_len.item()) == total
                 res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
@@ -531,7 +541,8 @@ def main():
                     help="the filter-auto section (format version 10): the auto mode with no filter, with --shuffle / --delta set by hand and with filter-auto")
     ap.add_argument("--filter-auto-off-only", action="store_true", help="the filter-auto section without the setting (what a build without it can run)")
     ap.add_argument("--lag", type=int, default=0, metavar="L", help="the lag section (format version 11): the delta's lag, 1 to 16")
-    ap.add_argument("--fold", action="store_true", help="the lag section's delta folds its sign")
+    ap.add_argument("--fold", action="store_true", help="the lag or grid section's delta folds its sign")
+    ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
     args = ap.parse_args()
     import importlib.util
     import numpy as np
@@ -554,6 +565,12 @@ def main():
         import lag_inputs
         assert args.lag, "the interleaved kinds are the lag section's"
         piece = torch.from_numpy(lag_inputs.lag_bytes(args.data, min(total, LAG_PIECE))).to(dev)
+        d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
+    elif args.data in ("img16", "field32", "walk32"):
+        import grid_inputs
+        assert args.grid, "the grids are the grid section's"
+        row = args.grid * grid_inputs.KINDS[args.data]
+        piece = torch.from_numpy(grid_inputs.grid_bytes(args.data, max(row, min(total, LAG_PIECE) // row * row), args.grid)).to(dev)      # whole rows
         d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
     elif args.data in ("zipf", "mix"):
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -595,6 +612,13 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if args.grid:
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["grid"] = lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], 1, int(args.fold), max(1, args.rounds), args.grid)
         print(json.dumps(res))
         return
     if args.lag:

@@ -7,13 +7,17 @@
              glcDeltaShuffleDevice / glcUndeltaUnshuffleDevice, the fused kernels of the filter's delta mode
   lag L[f] N / unlag L[f] N   (with --lag)
              glcLagDeltaShuffleDevice / glcUnlagDeltaUnshuffleDevice (csrc/lag.hip) with lag L = 2, 3, 8, 16, f = the fold on
+  lag 1f N / unlag 1f N, grid Wf N / ungrid Wf N   (with --grid W, the fold on)
+             glcGridDeltaShuffleDevice / glcUngridDeltaUnshuffleDevice (csrc/grid.hip) at row width W beside the lag kernels at
+             (1, 1), which the grid's expectations are stated against; k_grid_vsum takes its 16-byte path when W * N and the
+             destination's address (--offset) are multiples of 16, else its element path
 
 Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each run is bracketed by device events.  The
 table gives the median, the fastest and the slowest run of every variant, as GB/s of input bytes (the traffic is twice that)
 and relative to the copy's median.  The buffer (--gib, default 1) is larger than the 256 MiB Infinity Cache on purpose.
 --offset A B misaligns source and destination by A and B bytes.  One JSON line on stdout, the table on stderr or in --md FILE.
 
-python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--md FILE]"""
+python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--grid W] [--md FILE]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -41,6 +45,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--offset", type=int, nargs=2, default=[0, 0])
     ap.add_argument("--lag", action="store_true", help="the lagged, folded delta kernels beside the others")
+    ap.add_argument("--grid", type=int, default=0, metavar="W", help="the 2-D predictor's kernels at row width W beside the lag kernels at (1, 1)")
     ap.add_argument("--md", default=None)
     args = ap.parse_args()
     assert args.reps >= 20, "at least 20 timed repetitions"
@@ -89,6 +94,17 @@ def main():
                 glc._chk("unlag", L.glcUnlagDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, lag, 1, None))
                 assert torch.equal(back, src), (elem, lag)
             del back
+    if args.grid:
+        back = torch.empty_like(src)                           # what is timed inverts itself
+        for elem in (2, 4, 8):
+            variants.append(("lag 1f %d" % elem, lagged(L.glcLagDeltaShuffleDevice, elem, 1, 1)))
+            variants.append(("unlag 1f %d" % elem, lagged(L.glcUnlagDeltaUnshuffleDevice, elem, 1, 1)))
+            variants.append(("grid %df %d" % (args.grid, elem), lagged(L.glcGridDeltaShuffleDevice, elem, args.grid, 1)))
+            variants.append(("ungrid %df %d" % (args.grid, elem), lagged(L.glcUngridDeltaUnshuffleDevice, elem, args.grid, 1)))
+            lagged(L.glcGridDeltaShuffleDevice, elem, args.grid, 1)()
+            glc._chk("ungrid", L.glcUngridDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, args.grid, 1, None))
+            assert torch.equal(back, src), (elem, args.grid)
+        del back
     # correctness of what is timed, once, at this size and alignment
     for elem in (2, 4, 8):
         kernel(L.glcShuffleDevice, elem)()
