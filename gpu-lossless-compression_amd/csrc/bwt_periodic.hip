@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void k_per_rows(const uint8_t *__restrict__ te
 hipError_t per_reserve(SaScratch &s)
 {
     if (s.per_text) return hipSuccess;
-    auto A = [&](void **p, size_t bytes) -> hipError_t { s.bytes += bytes; return hipMalloc(p, bytes); };
+    auto A = [&](void **p, size_t bytes) -> hipError_t { s.bytes += bytes; return glc_dev_alloc(p, bytes); };
     GLC_TRY(A((void **)&s.per_info, (size_t)s.rows * sizeof(uint4)));
     GLC_TRY(A((void **)&s.per_list, (size_t)s.rows * 4));
     GLC_TRY(A((void **)&s.per_ok, (size_t)s.rows * 4));

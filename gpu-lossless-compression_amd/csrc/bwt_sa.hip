@@ -1137,7 +1137,7 @@ hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows)
     s.rs_tiles = (nmax + RS_TILE - 1) / RS_TILE;
     const size_t ne = (size_t)nmax * rows;
     size_t total = 0;
-    auto A = [&](void **p, size_t bytes) -> hipError_t { total += bytes; return hipMalloc(p, bytes); };
+    auto A = [&](void **p, size_t bytes) -> hipError_t { total += bytes; return glc_dev_alloc(p, bytes); };
     {   // keyA | keyB in one allocation: the bucket sorter uses it as [rows][buckets][FS_CAP]
         s.fs_kstride = ((size_t)1 << fs_bucket_log2(nmax)) * FS_CAP;
         const size_t words = s.fs_kstride * rows > 2 * ne ? s.fs_kstride * rows : 2 * ne;
@@ -1180,7 +1180,7 @@ hipError_t sa_scratch_alloc(SaScratch &s, uint32_t nmax, uint32_t rows)
     GLC_TRY(A((void **)&s.d_max_cnt, RD_WORDS * 4));
     GLC_TRY(A((void **)&s.rl_flag, (size_t)rows * 4));
     GLC_TRY(A((void **)&s.rl_cnt, (size_t)rows * 4));
-    GLC_TRY(hipHostMalloc((void **)&s.h_max_cnt, 64, hipHostMallocDefault));   // (16 words >= HW_WORDS)
+    GLC_TRY(glc_host_alloc((void **)&s.h_max_cnt, 64));   // (16 words >= HW_WORDS)
     sa_chain_defaults(&s.chain_min, &s.chain_rounds);
     s.bytes = total;
     return hipSuccess;
@@ -1195,7 +1195,7 @@ hipError_t sa_general_reserve(SaScratch &s, bool only_sa)
     auto A = [&](void **p, size_t bytes) -> hipError_t {
         if (*p) return hipSuccess;
         s.bytes += bytes;
-        return hipMalloc(p, bytes);
+        return glc_dev_alloc(p, bytes);
     };
     GLC_TRY(A((void **)&s.sa, ne * 4));
     if (only_sa) return hipSuccess;

@@ -70,15 +70,17 @@ static hipError_t tier_sample_again(const SortCall &c, SaScratch &s, uint32_t &l
     if (s.stage_partial && left < nflag) {
         // the stages behind the sort for the blocks the first attempt finished, on a side stream BESIDE the second attempt
         // (ss_mask was written before ss_retry_prepare touched anything: see above)
+        // (each of the three is made where it is missing: a call that failed between them leaves the next one the rest to
+        //  make, not a stream without its events)
         if (!s.aux) {
             // (lowest priority: the side stream's kernels fill the chip, the second attempt's small launches on `st` are a
             //  chain of latencies -- with equal priorities its bucketing pass took 614 us beside k_mtf_encode instead of 27)
             int least = 0, greatest = 0;
             (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
             GLC_TRY(hipStreamCreateWithPriority(&s.aux, hipStreamNonBlocking, least));
-            GLC_TRY(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
-            GLC_TRY(hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
         }
+        if (!s.ev_fork) GLC_TRY(hipEventCreateWithFlags(&s.ev_fork, hipEventDisableTiming));
+        if (!s.ev_join) GLC_TRY(hipEventCreateWithFlags(&s.ev_join, hipEventDisableTiming));
         GLC_TRY(hipEventRecord(s.ev_fork, c.st));
         GLC_TRY(hipStreamWaitEvent(s.aux, s.ev_fork, 0));
         GLC_TRY(s.stage_partial(s.aux, s.ss_mask[0]));

@@ -148,7 +148,7 @@ hipError_t crc32_segments(hipStream_t st, const uint8_t *base, const unsigned lo
 {
     if (count == 0) return hipSuccess;
     uint32_t *ts = nullptr;
-    hipError_t e = hipMallocAsync((void **)&ts, ((size_t)count + 1) * 4, st);
+    hipError_t e = glc_dev_alloc_async((void **)&ts, ((size_t)count + 1) * 4, st);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_crc_scan, dim3(1), dim3(1024), 0, st, base, d_off, d_len, count, ts, d_crc);
     hipLaunchKernelGGL(k_crc_rows, dim3(CRC_GRID), dim3(256), 0, st, base, d_off, d_len, count, (const uint32_t *)ts, d_crc);

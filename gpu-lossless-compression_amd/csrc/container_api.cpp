@@ -302,8 +302,8 @@ struct Encoder {
         }
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
         if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
-        if (codec == CT_CODEC_CHOOSE) CT_HIP(hipHostMalloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows, hipHostMallocDefault));
-        if (filter_auto) CT_HIP(hipHostMalloc((void **)&h_costs, 8 * FILTER_CANDS, hipHostMallocDefault));
+        if (codec == CT_CODEC_CHOOSE) CT_HIP(glc_host_alloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows));
+        if (filter_auto) CT_HIP(glc_host_alloc((void **)&h_costs, 8 * FILTER_CANDS));
         if (fmt.filtered() || filter_auto) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
@@ -311,7 +311,7 @@ struct Encoder {
         }
         CT_HIP(carve_on(
             [&](size_t bytes, void **base) {
-                const hipError_t e = hipMalloc(&mem, bytes);
+                const hipError_t e = glc_dev_alloc(&mem, bytes);
                 if (e != hipSuccess) mem = nullptr;
                 *base = mem;
                 return e;
@@ -730,9 +730,9 @@ struct Decoder {
         if (h_verdict) { (void)hipHostFree(h_verdict); h_verdict = nullptr; }
         CT_HIP(carve_on(
             [&](size_t bytes, void **base) {
-                hipError_t e = hipMalloc(&mem, bytes);
+                hipError_t e = glc_dev_alloc(&mem, bytes);
                 if (e != hipSuccess) { mem = nullptr; return e; }
-                e = hipHostMalloc((void **)&h_verdict, 8 * verdict_words(nb), hipHostMallocDefault);
+                e = glc_host_alloc((void **)&h_verdict, 8 * verdict_words(nb));
                 if (e != hipSuccess) h_verdict = nullptr;
                 *base = mem;
                 return e;
@@ -743,7 +743,7 @@ struct Decoder {
     }
     hipError_t begin()
     {
-        hipError_t e = hipMalloc((void **)&state, sizeof(CtDecState));
+        hipError_t e = glc_dev_alloc((void **)&state, sizeof(CtDecState));
         if (e != hipSuccess) { state = nullptr; return e; }
         e = hipMemsetAsync(state, 0, sizeof(CtDecState), P.st);
         if (e == hipSuccess) e = hipMemsetAsync(&state->err, 0xFF, 8, P.st);
@@ -937,7 +937,7 @@ struct Pinned {
         if (m <= n) return hipSuccess;
         if (p) (void)hipHostFree(p);
         p = nullptr; n = 0;
-        hipError_t e = hipHostMalloc(&p, m, hipHostMallocDefault);
+        hipError_t e = glc_host_alloc(&p, m);
         if (e == hipSuccess) n = m;
         return e;
     }
@@ -950,7 +950,7 @@ struct DevBuf {
         if (m <= n) return hipSuccess;
         if (p) (void)hipFree(p);
         p = nullptr; n = 0;
-        hipError_t e = hipMalloc(&p, m);
+        hipError_t e = glc_dev_alloc(&p, m);
         if (e == hipSuccess) n = m;
         return e;
     }

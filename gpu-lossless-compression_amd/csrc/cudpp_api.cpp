@@ -19,6 +19,26 @@
 
 using namespace glc;
 
+// the fill seam of the scratch allocation helpers (glc_internal.h): the word repeated over the whole block, the last 1 to 3
+// bytes from the word's low bytes, complete on return (a stream-ordered block is filled on its stream, which is then waited for)
+ScratchFill glc::g_scratch_fill;
+hipError_t glc::scratch_fill(void *p, size_t bytes, bool pinned, hipStream_t st)
+{
+    const uint32_t w = g_scratch_fill.word;
+    const size_t words = bytes / 4, tail = bytes & 3;
+    if (pinned) {
+        for (size_t i = 0; i < words; i++) memcpy(static_cast<uint8_t *>(p) + 4 * i, &w, 4);
+        memcpy(static_cast<uint8_t *>(p) + 4 * words, &w, tail);
+    } else {
+        if (words) GLC_TRY(hipMemsetD32Async(static_cast<hipDeviceptr_t>(p), (int)w, words, st));
+        if (tail) GLC_TRY(hipMemcpyAsync(static_cast<uint8_t *>(p) + 4 * words, &w, tail, hipMemcpyHostToDevice, st));
+        GLC_TRY(hipStreamSynchronize(st));
+    }
+    g_scratch_fill.blocks++;
+    g_scratch_fill.bytes += bytes;
+    return hipSuccess;
+}
+
 namespace {
 
 struct Manager {
@@ -39,11 +59,11 @@ struct PlanBase {
 
     hipError_t init_common()
     {
-        hipError_t e = hipMalloc((void **)&d_status, 4);
+        hipError_t e = glc_dev_alloc((void **)&d_status, 4);
         if (e != hipSuccess) return e;
         e = hipMemset(d_status, 0, 4);
         if (e != hipSuccess) return e;
-        return hipHostMalloc((void **)&h_status, 4, hipHostMallocDefault);
+        return glc_host_alloc((void **)&h_status, 4);
     }
     virtual ~PlanBase()
     {
@@ -96,7 +116,7 @@ struct GrowBuf {
                 (void)hipFree(mem);
                 mem = nullptr; bytes = 0;
             }
-            const hipError_t e = hipMalloc(&mem, want);
+            const hipError_t e = glc_dev_alloc(&mem, want);
             if (e != hipSuccess) { mem = nullptr; return e; }
             bytes = want;
         }
@@ -142,7 +162,7 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     hipError_t pipeline_init()
     {
         if (side) return hipSuccess;
-        hipError_t e = hipMalloc((void **)&d_bwt2, (size_t)n * rows);
+        hipError_t e = glc_dev_alloc((void **)&d_bwt2, (size_t)n * rows);
         if (e == hipSuccess) {
             // lowest priority: the second halves fill the slots the first halves leave free.  Measured on the
             // 4 GiB bench: decode 26.6 (default priority) / 27.3 (lowest) / 25.9 GB/s (highest); encode unchanged.
@@ -275,8 +295,8 @@ CUDPPResult cudppPlan(const CUDPPHandle cudppHandle, CUDPPHandle *planHandle, CU
         e = sa_scratch_alloc(p->sa, (uint32_t)n, (uint32_t)rows);
         if (e == hipSuccess) e = mtf_scratch_alloc(p->mtf, (uint32_t)n, (uint32_t)rows);
         if (e == hipSuccess) e = huff_scratch_alloc(p->huff, (uint32_t)n, (uint32_t)rows);
-        if (e == hipSuccess) e = hipMalloc((void **)&p->d_bwt, n * rows);
-        if (e == hipSuccess) e = hipMalloc((void **)&p->d_mtf, n * rows);
+        if (e == hipSuccess) e = glc_dev_alloc((void **)&p->d_bwt, n * rows);
+        if (e == hipSuccess) e = glc_dev_alloc((void **)&p->d_mtf, n * rows);
         break;
     }
     case CUDPP_BWT: case CUDPP_SA: {
@@ -763,6 +783,19 @@ CUDPPResult glcPlanDebugBucketFill(CUDPPHandle planHandle, size_t block, unsigne
     if (!s || block >= s->rows) return CUDPP_ERROR_INVALID_PLAN;
     if (hipStreamSynchronize(p->stream) != hipSuccess) return CUDPP_ERROR_UNKNOWN;
     return hipMemcpy(out512, s->fs_fill + block * FS_MAXNB, FS_MAXNB * 4, hipMemcpyDeviceToHost) == hipSuccess ? CUDPP_SUCCESS : CUDPP_ERROR_UNKNOWN;
+}
+
+// diagnostic, process-wide: the fill seam of the scratch allocation helpers (glc_internal.h)
+void glcDebugSetScratchFill(unsigned int on, unsigned int word)
+{
+    g_scratch_fill = ScratchFill{on ? 1u : 0u, word, 0, 0};
+}
+
+void glcDebugScratchFillStats(unsigned long long out2[2])
+{
+    if (!out2) return;
+    out2[0] = g_scratch_fill.blocks;
+    out2[1] = g_scratch_fill.bytes;
 }
 
 // the event pairs are read when the plan's streams are idle: both getters wait for them first

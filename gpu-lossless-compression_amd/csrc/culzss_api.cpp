@@ -66,7 +66,7 @@ template <class List> void mem_release(const List &list)
 template <class List> bool mem_alloc(const List &list)
 {
     for (const Mem &m : list)
-        if (m.bytes && !ok(m.pinned ? hipHostMalloc(m.p, m.bytes, hipHostMallocDefault) : hipMalloc(m.p, m.bytes), m.what)) return false;
+        if (m.bytes && !ok(m.pinned ? glc_host_alloc(m.p, m.bytes) : glc_dev_alloc(m.p, m.bytes), m.what)) return false;
     return true;
 }
 
@@ -231,7 +231,7 @@ int scratch_pack(const unsigned char *src, int buf_length, bool candidates, unsi
     if (!slot_ensure(s, buf_length)) return 0;
     const size_t bytes = candidates ? (size_t)2 * buf_length : (size_t)buf_length;
     uint8_t *d_src = nullptr;
-    if (!ok(hipMalloc((void **)&d_src, bytes), "scratch upload")) return 0;
+    if (!ok(glc_dev_alloc((void **)&d_src, bytes), "scratch upload")) return 0;
     const bool good = ok(hipMemcpyAsync(d_src, src, bytes, hipMemcpyHostToDevice, s.stream), "H2D")
                    && (candidates ? ok(lzss_pack(s.stream, d_src, buf_length, 1, s.d_packed, s.d_size, s.d_work), "pack")
                                   : ok(lzss_encode(s.stream, d_src, buf_length, 1, nullptr, s.d_packed, s.d_size, s.d_work), "encode"))
@@ -279,14 +279,14 @@ void signalExitThreads(void) {}
 unsigned char *initGPUmem(int buf_length)
 {
     void *p = nullptr;
-    if (buf_length <= 0 || !ok(hipMalloc(&p, (size_t)buf_length), "initGPUmem")) return nullptr;
+    if (buf_length <= 0 || !ok(glc_dev_alloc(&p, (size_t)buf_length), "initGPUmem")) return nullptr;
     return (unsigned char *)p;
 }
 
 unsigned char *initCPUmem(int buf_length)
 {
     void *p = nullptr;
-    if (buf_length <= 0 || !ok(hipHostMalloc(&p, (size_t)buf_length, hipHostMallocDefault), "initCPUmem")) return nullptr;
+    if (buf_length <= 0 || !ok(glc_host_alloc(&p, (size_t)buf_length), "initCPUmem")) return nullptr;
     return (unsigned char *)p;
 }
 

@@ -1,5 +1,6 @@
 // culzss_internal.h -- constants + launchers shared by culzss.hip and culzss_api.cpp
 #pragma once
+#include "glc_internal.h"                // glc_dev_alloc / glc_host_alloc: the library's scratch comes from them
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>

@@ -950,7 +950,7 @@ hipError_t decode_scratch_alloc(DecodeScratch &s, uint32_t nmax, uint32_t rows)
     s.max_split = (nmax + 1 + SPLIT - 1) / SPLIT;
     s.max_chunks = (nmax + IMTF_CHUNK - 1) / IMTF_CHUNK;
     size_t total = 0;
-    auto A = [&](void **p, size_t bytes) -> hipError_t { total += bytes; return hipMalloc(p, bytes); };
+    auto A = [&](void **p, size_t bytes) -> hipError_t { total += bytes; return glc_dev_alloc(p, bytes); };
     GLC_TRY(A((void **)&s.mtf, (size_t)nmax * rows));
     GLC_TRY(A((void **)&s.bwt, (size_t)nmax * rows));
     GLC_TRY(A((void **)&s.bwt2, (size_t)nmax * rows));

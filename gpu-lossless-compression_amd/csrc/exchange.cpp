@@ -6,6 +6,7 @@
 // receives over its 7 links at once, no ring).
 #include "../../include/glc_exchange.h"
 #include "glc_device.h"
+#include "glc_internal.h"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -87,8 +88,8 @@ CUDPPResult finish_init(glcComm_st *c)
 {
     GLC_NCCL(ncclCommCount(c->comm, &c->nranks));
     GLC_NCCL(ncclCommUserRank(c->comm, &c->rank));
-    GLC_HIP(hipMalloc((void **)&c->d_counts, sizeof(unsigned long long) * c->slot_words() * GLC_COUNT_SLOTS));
-    GLC_HIP(hipHostMalloc((void **)&c->h_counts, sizeof(unsigned long long) * 2 * (size_t)c->nranks * GLC_COUNT_SLOTS, hipHostMallocDefault));
+    GLC_HIP(glc::glc_dev_alloc((void **)&c->d_counts, sizeof(unsigned long long) * c->slot_words() * GLC_COUNT_SLOTS));
+    GLC_HIP(glc::glc_host_alloc((void **)&c->h_counts, sizeof(unsigned long long) * 2 * (size_t)c->nranks * GLC_COUNT_SLOTS));
     for (int i = 0; i < GLC_COUNT_SLOTS; i++) GLC_HIP(hipEventCreateWithFlags(&c->done[i], hipEventDisableTiming));
     return CUDPP_SUCCESS;
 }

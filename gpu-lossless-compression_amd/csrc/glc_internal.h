@@ -25,6 +25,33 @@ namespace glc {
 // what the C ABI answers for a HIP error (cudpp_api.cpp); a failure also clears HIP's sticky last error
 CUDPPResult hip_result(hipError_t e);
 
+// ---------------------------------------------------------------------------
+// Scratch allocation.  Every device and pinned-host block the library allocates for itself comes from one of the three
+// helpers below (tests/test_cpu_alloc_sites.py holds csrc/ to that); buffers the caller owns are never touched.  What a block
+// holds when it arrives is whatever the allocator left there, and the library's results must not depend on it: the fill seam
+// (glcDebugSetScratchFill, cudpp.h) lets a test choose those contents.  While it is on, each block is filled whole
+// with a 32-bit word (tail bytes included) before the helper returns, and the fill has completed by then.  Off -- the
+// default -- costs the one branch below.  Process-wide, a debugging aid: not safe against concurrent allocation.
+// ---------------------------------------------------------------------------
+struct ScratchFill { unsigned on = 0, word = 0; unsigned long long blocks = 0, bytes = 0; };
+extern ScratchFill g_scratch_fill;               // cudpp_api.cpp
+hipError_t scratch_fill(void *p, size_t bytes, bool pinned, hipStream_t st);   // cudpp_api.cpp
+inline hipError_t glc_dev_alloc(void **p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess && g_scratch_fill.on ? scratch_fill(*p, bytes, false, nullptr) : e;
+}
+inline hipError_t glc_host_alloc(void **p, size_t bytes)   // pinned host memory (hipHostMallocDefault)
+{
+    const hipError_t e = hipHostMalloc(p, bytes, hipHostMallocDefault);
+    return e == hipSuccess && g_scratch_fill.on ? scratch_fill(*p, bytes, true, nullptr) : e;
+}
+inline hipError_t glc_dev_alloc_async(void **p, size_t bytes, hipStream_t st)   // stream-ordered; freed with hipFreeAsync
+{
+    const hipError_t e = hipMallocAsync(p, bytes, st);
+    return e == hipSuccess && g_scratch_fill.on ? scratch_fill(*p, bytes, false, st) : e;
+}
+
 constexpr uint32_t MAX_BLOCK_ELEMS = 1u << 20;   // cudppCompress/BWT limit (cudpp-inpar/README.md:96,99)
 constexpr uint32_t HUFF_BLOCK      = 4096;       // HUFF_THREADS_PER_BLOCK*HUFF_WORK_PER_THREAD (cudpp_globals.h:60-61)
 constexpr uint32_t HUFF_SYMS       = 257;        // HUFF_NUM_CHARS (cudpp_globals.h:62)

@@ -403,9 +403,9 @@ hipError_t huff_scratch_alloc(HuffScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_sub = (nmax + HUFF_BLOCK - 1) / HUFF_BLOCK;
     size_t a = (size_t)rows * s.max_sub * SUBHIST_DWORDS * 4, c = (size_t)rows * 257 * 4;
-    GLC_TRY(hipMalloc((void **)&s.sub_hist, a));
-    GLC_TRY(hipMalloc((void **)&s.codes, c));
-    GLC_TRY(hipMalloc((void **)&s.lens, c));
+    GLC_TRY(glc_dev_alloc((void **)&s.sub_hist, a));
+    GLC_TRY(glc_dev_alloc((void **)&s.codes, c));
+    GLC_TRY(glc_dev_alloc((void **)&s.lens, c));
     s.bytes = a + 2 * c;
     return hipSuccess;
 }

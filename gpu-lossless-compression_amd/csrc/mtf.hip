@@ -728,8 +728,8 @@ hipError_t mtf_scratch_alloc(MtfScratch &s, uint32_t nmax, uint32_t rows)
 {
     s.nmax = nmax; s.rows = rows; s.max_chunks = (nmax + MTF_CHUNK - 1) / MTF_CHUNK;
     size_t a = (size_t)rows * s.max_chunks * 256, c = (size_t)rows * s.max_chunks * sizeof(uint16_t);
-    GLC_TRY(hipMalloc((void **)&s.lists, a));
-    GLC_TRY(hipMalloc((void **)&s.lens, c));
+    GLC_TRY(glc_dev_alloc((void **)&s.lists, a));
+    GLC_TRY(glc_dev_alloc((void **)&s.lens, c));
     s.bytes = a + c;
     return hipSuccess;
 }

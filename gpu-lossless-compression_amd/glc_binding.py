@@ -42,6 +42,7 @@ CUDPP_SYMBOLS = [
     "glcCompactStreams", "glcPlanSetPipelining", "glcPlanSetSorter", "glcPlanLastSortStats", "glcPlanLastSortStatsEx", "glcPlanLastSortRetries", "glcPlanLastSortResumed", "glcPlanLastSortPeriodic", "glcPlanSetChains", "glcPlanLastSortChains", "glcPlanLastSortSkipped", "glcPlanDebugSortFlags", "glcPlanDebugBucketFill", "glcHuffmanEncodeBatch", "glcExpandStreams", "glcPlanKernelProfileEx", "glcProbeStreamRead", "glcGenZipfPhilox", "glcGenFloatPhilox", "glcPlanKernelProfileLost",
     "glcCompressBatchCompact", "glcDecompressBatchCompact",
     "glcHuffmanDecodeBatch", "glcMtfInverseBatch", "glcPlanSetHuffDecoder",
+    "glcDebugSetScratchFill", "glcDebugScratchFillStats",
 ]
 CULZSS_SYMBOLS = [
     "compression_kernel_wrapper", "aftercompression_wrapper", "decompression_kernel_wrapper",
@@ -128,6 +129,10 @@ def lib():
     L.glcExpandStreams.argtypes = [sz, vp, vp, sz, vp, sz, vp]
     for name in CUDPP_SYMBOLS:
         getattr(L, name).restype = C.c_int
+    L.glcDebugSetScratchFill.argtypes = [C.c_uint, C.c_uint]
+    L.glcDebugSetScratchFill.restype = None
+    L.glcDebugScratchFillStats.argtypes = [C.POINTER(C.c_ulonglong)]
+    L.glcDebugScratchFillStats.restype = None
     L.glcProbeStreamRead.argtypes = [vp, sz, C.c_int, C.POINTER(C.c_float), vp]
     L.glcProbeStreamRead.restype = C.c_int
     L.glcGenZipfPhilox.argtypes = [vp, sz, C.c_ulonglong, C.c_uint, vp, vp]
@@ -256,6 +261,25 @@ class CudppError(RuntimeError):
 def _chk(fn, code):
     if code != CUDPP_SUCCESS:
         raise CudppError(fn, code)
+
+
+def debug_set_scratch_fill(word):
+    """Process-wide test seam: while `word` is a 32-bit value, every block of device or pinned memory the library allocates
+    for itself is filled with it before use; None switches the fill off again (the default).  Either way the counters of
+    debug_scratch_fill_stats() start over."""
+    if word is None:
+        lib().glcDebugSetScratchFill(0, 0)
+    else:
+        if not 0 <= int(word) <= 0xFFFFFFFF:
+            raise ValueError("the fill is a 32-bit word")
+        lib().glcDebugSetScratchFill(1, int(word))
+
+
+def debug_scratch_fill_stats():
+    """(blocks, bytes) filled since the last debug_set_scratch_fill"""
+    a = (C.c_ulonglong * 2)()
+    lib().glcDebugScratchFillStats(a)
+    return int(a[0]), int(a[1])
 
 
 def config(algorithm, datatype=CUDPP_UCHAR, options=0, op=CUDPP_ADD):

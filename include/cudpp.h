@@ -313,6 +313,14 @@ CUDPPResult glcPlanLastSortSkipped(CUDPPHandle planHandle, unsigned int *out2);
  * 512 bucket fills of one block as the last bucketing pass left them.  Both wait for the plan's stream. */
 CUDPPResult glcPlanDebugSortFlags(CUDPPHandle planHandle, unsigned int *out_fs, unsigned int *out_ss, size_t numBlocks);
 CUDPPResult glcPlanDebugBucketFill(CUDPPHandle planHandle, size_t block, unsigned int *out512);
+/* diagnostics (tests), process-wide: what the library's own scratch memory holds when it is allocated.  No result may depend
+ * on it, and these two let a test vary it.  While on != 0, every device or pinned-host block the library allocates for itself
+ * -- by plans, by the container calls, by CULZSS and the exchange; never a buffer of the caller's -- is filled whole with the
+ * 32-bit `word` (a tail of 1 to 3 bytes gets the word's low bytes) before anything uses it; the fill is complete when the
+ * allocation returns.  Off (the default) it costs one branch per allocation.  Set also zeroes the two counters Stats reports:
+ * out2[0] = blocks filled, out2[1] = bytes filled since the last Set.  Not safe against allocation on another thread. */
+void glcDebugSetScratchFill(unsigned int on, unsigned int word);
+void glcDebugScratchFillStats(unsigned long long out2[2]);
 
 /* Result collection: packs the strided per-block streams of a batched compress
  * back to back.  d_outOffsets has numBlocks+1 entries (word offsets; the last is

@@ -1,6 +1,8 @@
 /* A plain-C caller of include/glc_container.h (gcc, not hipcc): a device round trip of a ragged input through one
  * COMPRESS plan, printing the container length, its CRC-32, the CRC-32 glcCrc32Segments reports for the input and whether
- * the decoded bytes equal the input. */
+ * the decoded bytes equal the input.  The container's length and CRC-32 are printed BEFORE it is decoded (the test compares
+ * them with the CPU model's), so that a failed decode says whether the encoder wrote wrong bytes or the decoder misread right
+ * ones. */
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -17,7 +19,18 @@ static unsigned crc32(const void *p, size_t n)
 }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "HIP error %d at line %d\n", (int)e_, __LINE__); return 2; } } while (0)
-#define CR(x) do { CUDPPResult r_ = (x); if (r_ != CUDPP_SUCCESS) { fprintf(stderr, "CUDPPResult %d at line %d\n", (int)r_, __LINE__); return 3; } } while (0)
+/* a failing call also says what the container's last error was (what, frame, block) and HIP's, once there is a plan */
+static CUDPPHandle plan = 0;
+static int refused(CUDPPResult r, int line)
+{
+    unsigned long long e[3] = {0, 0, 0};
+    fprintf(stderr, "CUDPPResult %d at line %d", (int)r, line);
+    if (plan && glcContainerLastError(plan, e) == CUDPP_SUCCESS)
+        fprintf(stderr, ", container last error (%llu, %lld, %lld), hip last error %d", e[0], (long long)e[1], (long long)e[2], (int)hipGetLastError());
+    fprintf(stderr, "\n");
+    return 3;
+}
+#define CR(x) do { CUDPPResult r_ = (x); if (r_ != CUDPP_SUCCESS) return refused(r_, __LINE__); } while (0)
 
 int main(void)
 {
@@ -32,7 +45,7 @@ int main(void)
     CK(hipMalloc((void **)&d_in, len)); CK(hipMalloc((void **)&d_out, cap)); CK(hipMalloc((void **)&d_back, len));
     CK(hipMalloc((void **)&d_len, 8)); CK(hipMalloc((void **)&d_off, 8)); CK(hipMalloc((void **)&d_ln, 8)); CK(hipMalloc((void **)&d_crc, 4));
     CK(hipMemcpy(d_in, h_in, len, hipMemcpyHostToDevice));
-    CUDPPHandle lib, plan;
+    CUDPPHandle lib;
     CUDPPConfiguration cfg = {CUDPP_COMPRESS, CUDPP_ADD, CUDPP_UCHAR, 0, CUDPP_DEFAULT_BUCKET_MAPPER};
     CR(cudppCreate(&lib));
     CR(cudppPlan(lib, &plan, cfg, n, 2, 0));
@@ -40,6 +53,9 @@ int main(void)
     CK(hipMemcpy(&clen, d_len, 8, hipMemcpyDeviceToHost));
     h_cont = (unsigned char *)malloc(clen);
     CK(hipMemcpy(h_cont, d_out, clen, hipMemcpyDeviceToHost));
+    const unsigned ccrc = crc32(h_cont, clen);
+    printf("container_len=%llu container_crc=%08x\n", clen, ccrc);
+    fflush(stdout);
     CR(glcContainerDecompressDevice(plan, d_out, clen, d_back, len, d_len));
     CK(hipMemcpy(&blen, d_len, 8, hipMemcpyDeviceToHost));
     CK(hipMemcpy(h_back, d_back, len, hipMemcpyDeviceToHost));
@@ -49,7 +65,7 @@ int main(void)
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(&gcrc, d_crc, 4, hipMemcpyDeviceToHost));
     printf("container_len=%llu container_crc=%08x input_crc=%08x gpu_crc=%08x decoded_len=%llu equal=%d\n", clen,
-           crc32(h_cont, clen), crc32(h_in, len), gcrc, blen, blen == len && memcmp(h_in, h_back, len) == 0);
+           ccrc, crc32(h_in, len), gcrc, blen, blen == len && memcmp(h_in, h_back, len) == 0);
     CR(cudppDestroyPlan(plan));
     CR(cudppDestroy(lib));
     return 0;

@@ -368,7 +368,25 @@ def test_plain_c_caller_round_trip(glc, tmp_path):
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    # first the line the rig prints BEFORE it decodes, whatever became of the decode: the container against the model's of
+    # the same input (the rig's srand(7) stream, restated).  Only then the return code: a refused decode of a container that
+    # equals the model's is the decoder's failure, one of a container that differs the encoder's
+    x, want = _rig_input_and_container()
+    lines = r.stdout.splitlines()
+    assert lines and lines[0].startswith("container_len="), "the rig got no container to report: rc %d\n%s" % (r.returncode, r.stdout + r.stderr)
+    pre = dict(kv.split("=") for kv in lines[0].split())
+    model = dict(container_len=str(len(want)), container_crc="%08x" % zlib.crc32(want))
+    assert pre == model, "the ENCODER wrote other bytes than the model (rig rc %d)\nrig:   %r\nmodel: %r\n%s" % (r.returncode, pre, model, r.stderr)
+    assert r.returncode == 0, "the container equals the model's byte for byte, so the DECODER failed on right bytes\n" + r.stdout + r.stderr
     out = dict(kv.split("=") for kv in r.stdout.split())
     assert out["equal"] == "1" and out["input_crc"] == out["gpu_crc"]
     assert int(out["decoded_len"]) == 3 * 65536 + 12345
+    assert out["input_crc"] == "%08x" % zlib.crc32(x.tobytes())
+
+
+def _rig_input_and_container():
+    import oracle_lib as O
+    n, length = 65536, 3 * 65536 + 12345
+    letters = np.frombuffer(b"abcabd, the cat sat on the mat. ", np.uint8)
+    x = letters[O.glibc_rand_bytes(length, 32, 7).astype(np.int64) - 1] ^ (np.arange(length) % 977 == 0).astype(np.uint8)
+    return x, M.write(x, n, 2)

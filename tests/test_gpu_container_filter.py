@@ -303,9 +303,32 @@ def test_plain_c_caller_of_the_filter(glc, tmp_path):
            "-lamdhip64", "-lm", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+    # the rig reads its input from a file written here (its own sinf and float accumulation are not reproduced bit for bit in
+    # numpy), so that the model's containers of the same bytes can be held beside the rig's
+    x, want_off, want_on = _rig_input_and_containers()
+    src = tmp_path / "filter_rig_input.bin"
+    x.tofile(src)
+    r = subprocess.run([exe, str(src)], capture_output=True, text=True, timeout=120)
+    # first the line the rig prints BEFORE it decodes, whatever became of the decode: both containers against the model's
+    lines = r.stdout.splitlines()
+    assert lines and lines[0].startswith("input_crc="), "the rig got no container to report: rc %d\n%s" % (r.returncode, r.stdout + r.stderr)
+    pre = dict(kv.split("=") for kv in lines[0].split())
+    model = dict(input_crc="%08x" % zlib.crc32(x.tobytes()), off_len=str(len(want_off)), off_crc="%08x" % zlib.crc32(want_off),
+                 on_len=str(len(want_on)), on_crc="%08x" % zlib.crc32(want_on))
+    assert pre == model, "the ENCODER wrote other bytes than the model (rig rc %d)\nrig:   %r\nmodel: %r\n%s" % (r.returncode, pre, model, r.stderr)
+    assert r.returncode == 0, "both containers equal the model's byte for byte, so the DECODER failed on right bytes\n" + r.stdout + r.stderr
     out = dict(kv.split("=") for kv in r.stdout.split())
     assert (out["version"], out["elem"], out["equal"], out["planes"], out["unshuffled"]) == ("2", "4", "1", "1", "1")
     assert int(out["decoded_len"]) == 4 * (9 * 65536 // 4 + 300) + 3
     assert int(out["on_len"]) < int(out["off_len"])             # smooth float32: the high planes code well
+
+
+def _rig_input_and_containers():
+    """float32 samples of a smooth signal -- a sine plus a small random walk, as the rig makes for itself without an argument --
+    and a ragged tail of three bytes; the model's containers of them with the filter off and with element size 4 (n 65536, rows 4)"""
+    n, count = 65536, 9 * 65536 // 4 + 300
+    rng = np.random.default_rng(11)
+    walk = np.cumsum(rng.integers(-100, 101, count).astype(np.float32) * np.float32(1e-4), dtype=np.float32)
+    v = (np.float32(100.0) * np.sin(np.arange(count, dtype=np.float32) * np.float32(0.00125)) + walk).astype(np.float32)
+    x = np.concatenate([v.view(np.uint8), np.array([1, 2, 3], np.uint8)])
+    return x, M.write(x, n, 4), M.write(x, n, 4, 4)

@@ -8,6 +8,7 @@ import pytest
 
 import datagen
 import oracle_lib as O
+import tier_batches as T
 
 pytestmark = pytest.mark.gpu
 N = 1 << 20
@@ -23,43 +24,8 @@ def _bwt(glc, plan, torch, x, rows):
     return d_out.cpu().numpy(), d_idx.cpu().numpy()
 
 
-def _zero_pages(n, seed):
-    x = datagen.zipf_bytes(n, seed=seed).copy()
-    for off in (n // 25, n // 3 + 123, n - n // 9):
-        x[off:off + 4096] = 0
-    return x
-
-
-def _duplicate(n, seed):
-    x = datagen.text_bytes(n, seed=seed).copy()
-    ln = n // 50
-    x[n // 2 + 77:n // 2 + 77 + ln] = x[n // 10:n // 10 + ln]
-    return x
-
-
-def _phrase(n, seed):
-    x = datagen.text_bytes(n, seed=seed).copy()
-    ph = np.random.default_rng(seed).integers(97, 123, 2000, dtype=np.uint8)
-    for off in range(5000, n - 2000, 16384):
-        x[off:off + 2000] = ph
-    return x
-
-
-def _log_runs(n, seed):
-    x = datagen.log_bytes(n, seed=seed).copy()
-    x[n // 5:n // 5 + 1500] = 32
-    x[n - n // 3:n - n // 3 + 9000] = 0
-    return x
-
-
-def _tail_run(n, seed):
-    """the deep part reaches the end of the block: suffixes shorter than the cap inside a run"""
-    x = datagen.text_bytes(n, seed=seed).copy()
-    x[n - 3000:] = 65
-    return x
-
-
-GENS = {"zero_pages": _zero_pages, "duplicate": _duplicate, "phrase": _phrase, "log_runs": _log_runs, "tail_run": _tail_run}
+# the generators live in tier_batches.py, which the scratch-fill and call-history tests share
+_zero_pages, _duplicate, _phrase, _log_runs, _tail_run, GENS = T.zero_pages, T.duplicate, T.phrase, T.log_runs, T.tail_run, T.GENS
 
 
 @pytest.fixture(scope="module")
@@ -89,9 +55,7 @@ def test_resume_in_a_mixed_batch(glc, ctx, cuda):
     """every way a block can go, in one call: bucket sorter, sample sorter, resumed doubling, general sorter from scratch
     (periodic data: the tolerant form gives it up at sampling), a block of one symbol"""
     import torch
-    blocks = [datagen.zipf_bytes(N, seed=1), _duplicate(N, 2), datagen.text_bytes(N, seed=3), _phrase(N, 4),
-              np.tile(np.frombuffer(b"xy", dtype=np.uint8), N // 2), _log_runs(N, 5), np.zeros(N, dtype=np.uint8),
-              _tail_run(N, 6), np.tile(np.random.default_rng(7).integers(0, 256, 4096, dtype=np.uint8), N // 4096)]
+    blocks = T.all_tiers_blocks(N)
     x = np.concatenate(blocks)
     with glc.Plan(ctx, glc.CUDPP_BWT, N, rows=len(blocks)) as plan:
         for rep in range(2):
