@@ -13,7 +13,9 @@
 // kind they may write), parse_format() accepts a reader's.  Under format version 10 (filter-auto) the filter is each FRAME's: the
 // stream's triple is (10, 0, 0), word 3 of a frame header names the frame's filter, and ct_frame_format() gives the format a frame
 // went through -- the writer picks it per frame from the filter probe (filter_probe.hip, filter_rule.h; one host read of seven
-// costs per frame), the readers take it from the frame.
+// costs per frame), the readers take it from the frame.  Format version 13 (filter-lag) is version 10 whose frame word may also
+// carry version 11's lag and fold: the writer enqueues the lag probe behind the filter probe (lag_probe.hip, lag_rule.h) and
+// reads ten costs and three lags with the same one wait; its triple (13, 0, 0) is parse_stream_format()'s.
 //
 // Encode (Encoder).  A filtered frame is staged through filter_device() into staging kept with the plan and encoded from there;
 // crc_all is taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman
@@ -50,6 +52,7 @@
 #include "container_internal.h"
 #include "dedup_rule.h"
 #include "filter_rule.h"
+#include "lag_rule.h"
 
 #include <fcntl.h>
 #include <memory>
@@ -175,6 +178,11 @@ struct Encoder {
     bool filter_auto = false;
     uint32_t own_pick = 0;                                    // the candidate every frame counts for with the setting off
     uint32_t *fp_planes = nullptr;
+    // filter-lag (format version 13): the lag probe's sums, winners and rows of the same frame; its three costs lie behind the filter
+    // probe's seven and its winners behind those, so that one copy brings all thirteen words to the host
+    bool filter_lag = false;
+    unsigned long long *lp_sums = nullptr;
+    uint32_t *lp_lags = nullptr, *lp_planes = nullptr;
     unsigned long long *fp_costs = nullptr, *fp_seg = nullptr, *h_costs = nullptr;
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -284,8 +292,14 @@ struct Encoder {
         if (codec == CT_CODEC_CHOOSE) ch_stats = c.take<unsigned long long>(CHOOSE_STATS * R);
         if (filter_auto) {
             fp_planes = c.take<uint32_t>(FILTER_ROWS * 256);
-            fp_costs = c.take<unsigned long long>(FILTER_CANDS + 1);
+            fp_costs = c.take<unsigned long long>(FP_HOST_WORDS);
+            lp_lags = reinterpret_cast<uint32_t *>(fp_costs + LAG_CANDS);
             fp_seg = c.take<unsigned long long>(2);
+            if (filter_lag) {
+                lp_sums = c.take<unsigned long long>(LAG_SUMS);
+                c.align(16);
+                lp_planes = c.take<uint32_t>(LAG_ROWS * 256);
+            }
         }
     }
 
@@ -296,6 +310,7 @@ struct Encoder {
         codec = s.codec;
         mode = s.mode;
         filter_auto = s.filter_auto;
+        filter_lag = s.filter_lag;
         for (uint32_t i = 0; i < FILTER_CANDS; i++) {             // the candidate that is the plan's own filter
             const FilterCand c = filter_cand(i);
             if (c.elem == (fmt.elem ? fmt.elem : 1u) && (c.delta != 0) == fmt.delta()) own_pick = i;
@@ -303,7 +318,7 @@ struct Encoder {
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
         if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
         if (codec == CT_CODEC_CHOOSE) CT_HIP(glc_host_alloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows));
-        if (filter_auto) CT_HIP(glc_host_alloc((void **)&h_costs, 8 * FILTER_CANDS));
+        if (filter_auto) CT_HIP(glc_host_alloc((void **)&h_costs, 8 * FP_HOST_WORDS));
         if (fmt.filtered() || filter_auto) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
@@ -327,15 +342,28 @@ struct Encoder {
     }
 
     // filter-auto: the probe of the frame where it lies, its seven costs read back with one wait (as the CHOOSE codec reads its
-    // stats), and the rule on the host.  A frame beyond the probe's 2^31 bytes is judged by its first 2^31.
-    CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick)
+    // stats), and the rule on the host.  A frame beyond the probe's 2^31 bytes is judged by its first 2^31.  With filter-lag the
+    // lag probe's sums, winners, rows and costs are enqueued behind it -- the winners never leave the device between them -- and
+    // the same wait brings ten costs and three lags; the walk is lag_rule.h's.  *pick: the candidate (below LAG_CANDS), *lag: its lag.
+    static constexpr size_t FP_HOST_WORDS = LAG_CANDS + 2;    // ten costs, then the three winners in two 64-bit words
+    CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick, uint32_t *lag)
     {
+        const uint32_t max_len = (uint32_t)std::min<unsigned long long>(frame_len, GLC_FILTER_PROBE_MAX_LEN);
         CT_TRY(ct_put_u64(P.st, fp_seg + 1, frame_len));     // (fp_seg[0], the segment's offset, is 0 from init() on)
-        CT_TRY(filter_probe_segments(P.st, d_in, fp_seg, fp_seg + 1, 1, (uint32_t)std::min<unsigned long long>(frame_len, GLC_FILTER_PROBE_MAX_LEN),
-                                     fp_planes, fp_costs));
-        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FILTER_CANDS, hipMemcpyDeviceToHost, P.st));
+        CT_TRY(filter_probe_segments(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, fp_planes, fp_costs));
+        *lag = 1;
+        if (!filter_lag) {
+            CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FILTER_CANDS, hipMemcpyDeviceToHost, P.st));
+            CT_TRY(hipStreamSynchronize(P.st));
+            *pick = filter_pick(h_costs);
+            return CUDPP_SUCCESS;
+        }
+        CT_TRY(lag_probe_sums(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, lp_sums, lp_lags));
+        CT_TRY(lag_probe_planes(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, lp_lags, lp_planes, fp_costs + FILTER_CANDS));
+        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FP_HOST_WORDS, hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
-        *pick = filter_pick(h_costs);
+        *pick = lag_pick(h_costs);
+        if (*pick >= FILTER_CANDS) *lag = lag_clamp(reinterpret_cast<const uint32_t *>(h_costs + LAG_CANDS)[*pick - FILTER_CANDS]);
         return CUDPP_SUCCESS;
     }
 
@@ -352,13 +380,16 @@ struct Encoder {
         CtFormat ff = fmt;                                    // the format whose filter this frame goes through
         uint32_t pick = own_pick;
         if (filter_auto) {
-            const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick);
+            uint32_t lag = 1;
+            const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick, &lag);
             if (r != CUDPP_SUCCESS) return r;
-            const FilterCand c = filter_cand(pick);
+            const uint32_t lags[LAG_ELEMS] = {lag, lag, lag};
+            const LagCand c = lag_cand(pick, lags);           // (below FILTER_CANDS: filter_rule.h's candidate, lag 1 and no fold)
             ff.elem = c.elem > 1 ? c.elem : 0;
-            ff.flags = c.delta ? CT_FLAG_DELTA : 0;
+            ff.flags = c.delta ? CT_FLAG_DELTA | (c.fold ? CT_FLAG_FOLD : 0u) | (c.lag - 1u) << CT_LAG_SHIFT : 0;
         }
-        rep.filters[pick]++;
+        if (pick < FILTER_CANDS) rep.filters[pick]++;         // (a frame that took a lag candidate counts among all frames only)
+        else { rep.lag_filters[pick - FILTER_CANDS]++; rep.lag_filters[LAG_ELEMS]++; }
         rep.filters[FILTER_CANDS]++;
         if (ff.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
@@ -608,6 +639,7 @@ struct Encoder {
         CtReports &r = plan_container_reports(P.h);
         memcpy(r.choice, rep.choice, sizeof r.choice);
         memcpy(r.filters, rep.filters, sizeof r.filters);
+        memcpy(r.lag_filters, rep.lag_filters, sizeof r.lag_filters);
         set_error(P.h, CT_OK);
         return CUDPP_SUCCESS;
     }
@@ -1213,7 +1245,7 @@ CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &i
     const CUDPPResult r = walk_result(plan, end, stopped);
     if (r != CUDPP_SUCCESS) return r;
     ix->fmt = CtFormat();
-    (void)parse_format(ix->hdr, &ix->fmt);
+    (void)parse_stream_format(ix->hdr, &ix->fmt);
     ix->block_len = ix->hdr[2];
     ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
     *index = ix.release();
@@ -1621,6 +1653,11 @@ CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8])
     return last_report(plan, false, out, FILTER_CANDS + 1, [](const CtReports &r) { return r.filters; });
 }
 
+CUDPPResult glcContainerLastLagFilters(CUDPPHandle plan, unsigned long long out[4])
+{
+    return last_report(plan, false, out, LAG_ELEMS + 1, [](const CtReports &r) { return r.lag_filters; });
+}
+
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     return ct_set(plan, [&](CtSettings &s) { return s.set_shuffle(elem); });
@@ -1666,6 +1703,11 @@ CUDPPResult glcPlanSetContainerFilterAuto(CUDPPHandle plan, unsigned int on)
     return ct_set(plan, [&](CtSettings &s) { return s.set_filter_auto(on); });
 }
 
+CUDPPResult glcPlanSetContainerFilterLag(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_filter_lag(on); });
+}
+
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
 {
     return ct_get(plan, elem, [](const CtSettings &s) { return s.shuffle; });
@@ -1709,6 +1751,11 @@ CUDPPResult glcPlanGetContainerDedup(CUDPPHandle plan, unsigned int *on)
 CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
 {
     return ct_get(plan, on, [](const CtSettings &s) { return s.filter_auto ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.filter_lag ? 1u : 0u; });
 }
 
 CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold)

@@ -3,7 +3,7 @@
 // CRC of segments (container.hip), the byte-plane shuffle, the delta + shuffle and its lagged, folded form with their range forms
 // (shuffle.hip, delta.hip, lag.hip) and the 2-D predictor over it (grid.hip),
 // the sparse split and join (sparse.hip), the dedup map and fill (dedup.hip), the zero-run split and join (zrun.hip), the rANS
-// coder (ans.hip) and the three probes (auto.hip, choose.hip, filter_probe.hip).  The container over a plan, which runs the same
+// coder (ans.hip) and the probes (auto.hip, choose.hip, filter_probe.hip, lag_probe.hip).  The container over a plan, which runs the same
 // passes inside its frames, is container_api.cpp.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
@@ -383,6 +383,39 @@ CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long lon
         return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CT_TRY(filter_probe_segments(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths,
                                  (uint32_t)count, (uint32_t)maxLen, d_planes, d_costs));
+    return CUDPP_SUCCESS;
+}
+
+// the two lag probes: a bad argument is refused before anything is enqueued
+static bool lag_probe_args_ok(const void *in, const void *off, const void *len, size_t count, size_t maxLen, const void *a, unsigned aAlign,
+                              const void *b, unsigned bAlign)
+{
+    if (count > GLC_PROBE_MAX_COUNT || maxLen > GLC_FILTER_PROBE_MAX_LEN) return false;
+    if (count == 0) return true;
+    return in && off && len && a && b && a != b && !(reinterpret_cast<uintptr_t>(a) & (aAlign - 1)) && !(reinterpret_cast<uintptr_t>(b) & (bAlign - 1));
+}
+
+CUDPPResult glcLagProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                size_t count, size_t maxLen, unsigned long long *d_sums, unsigned int *d_lags, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_sums, 8, d_lags, 4)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    CT_TRY(lag_probe_sums(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                          (uint32_t)maxLen, d_sums, d_lags));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcLagPlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, const unsigned int *d_lags, unsigned int *d_planes,
+                                 unsigned long long *d_costs, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_planes, 16, d_costs, 8)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    // (the lags are read while the outputs are written: neither output may be them)
+    if (!d_lags || (reinterpret_cast<uintptr_t>(d_lags) & 3) || static_cast<const void *>(d_lags) == d_planes ||
+        static_cast<const void *>(d_lags) == d_costs) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(lag_probe_planes(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                            (uint32_t)maxLen, d_lags, d_planes, d_costs));
     return CUDPP_SUCCESS;
 }
 

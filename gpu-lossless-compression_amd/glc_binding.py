@@ -720,6 +720,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerDeltaLag", "glcPlanGetContainerDeltaLag",
                      "glcGridDeltaShuffleDevice", "glcUngridDeltaUnshuffleDevice", "glcUngridDeltaUnshuffleRangeDevice",
                      "glcPlanSetContainerDeltaGrid", "glcPlanGetContainerDeltaGrid",
+                     "glcLagProbeSegments", "glcLagPlanesSegments",
+                     "glcPlanSetContainerFilterLag", "glcPlanGetContainerFilterLag", "glcContainerLastLagFilters",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -792,6 +794,9 @@ def _ct():
         L.glcContainerLastChoice.argtypes = [sz, ullp]
         L.glcFilterProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcContainerLastFilters.argtypes = [sz, ullp]
+        L.glcContainerLastLagFilters.argtypes = [sz, ullp]
+        L.glcLagProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.glcLagPlanesSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.glcDedupWorkBytes.argtypes = [sz, sz]
         L.glcDedupWorkBytes.restype = sz
         L.glcDedupMapSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp]
@@ -969,6 +974,24 @@ def container_get_filter_auto(plan):
     return _get_uint("glcPlanGetContainerFilterAuto", plan)
 
 
+def container_set_filter_lag(plan, on):
+    """filter-lag of the plan's container ENCODER (format version 13: filter-auto also weighs the lagged, folded delta at the lag
+    the lag probe finds per frame): True / 1 needs filter-auto on, and whatever switches filter-auto off switches it off.  It is
+    also the version the plan reads: on, versions 1 to 5, 7, 8, 10 and 13; off, a version-13 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerFilterLag", _ct().glcPlanSetContainerFilterLag(plan.handle, int(on)))
+
+
+def container_get_filter_lag(plan):
+    return _get_uint("glcPlanGetContainerFilterLag", plan)
+
+
+def container_last_lag_filters(plan):
+    """(frames that took the lag candidate of elem 2, of elem 4, of elem 8, their sum) of the plan's last successful compress"""
+    a = (C.c_ulonglong * 4)()
+    _chk("glcContainerLastLagFilters", _ct().glcContainerLastLagFilters(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
 def container_set_delta_lag(plan, lag, fold):
     """the lag and fold of the delta of the plan's container ENCODER (format version 11: the predecessor `lag` elements back, the
     sign folded into bit 0 where fold is 1); (1, 0) is off.  Anything else needs the order-0 codec, the auto mode, the shuffle
@@ -1077,6 +1100,52 @@ def filter_probe_segments(d_in, offsets, lengths, max_len=None, planes=None, cos
     assert planes.numel() >= FILTER_PROBE_ROWS * 256 * n and costs.numel() >= FILTER_CANDIDATES * n
     _chk("glcFilterProbeSegments", _ct().glcFilterProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
                                                                  planes.data_ptr(), costs.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return planes[:n], costs[:n]
+
+
+LAG_PROBE_SUMS, LAG_PROBE_ROWS, LAG_PROBE_MAX_LAG = 48, 14, 16
+
+
+def _lag_probe_args(d_in, offsets, lengths, max_len):
+    import torch
+    dev = d_in.device
+    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
+    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    assert off.numel() == ln.numel()
+    return dev, off, ln, off.numel(), int(max(lengths, default=0)) if max_len is None else int(max_len)
+
+
+def lag_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, lags=None, stream=None):
+    """the lag probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (sums, lags) --
+    an int64 tensor [count, 48] of the bit lengths S[e][l] of the folded differences at element size e = 2, 4, 8 and lag
+    l = 1 .. 16 (row (log2 e - 1) * 16 + l - 1) over each segment's first L - L % 8 bytes, and an int32 tensor [count, 3] of the
+    lag with the smallest sum per element size (csrc/lag_rule.h).  sums / lags: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    sums = torch.empty((max(1, n), LAG_PROBE_SUMS), dtype=torch.int64, device=dev) if sums is None else sums
+    lags = torch.empty((max(1, n), 3), dtype=torch.int32, device=dev) if lags is None else lags
+    assert sums.is_contiguous() and lags.is_contiguous() and sums.dtype == torch.int64 and lags.dtype == torch.int32
+    assert sums.numel() >= LAG_PROBE_SUMS * n and lags.numel() >= 3 * n
+    _chk("glcLagProbeSegments", _ct().glcLagProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
+                                                           sums.data_ptr(), lags.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return sums[:n], lags[:n]
+
+
+def lag_planes_segments(d_in, offsets, lengths, lags, max_len=None, planes=None, costs=None, stream=None):
+    """the plane probe of the lag rule over the same segments at the lags of the device int32 tensor `lags` [count, 3] (each word
+    used as ((v - 1) & 15) + 1): (planes, costs) -- an int32 tensor [count, 14, 256] of the histograms E_2, E_4 and E_8 and an
+    int64 tensor [count, 3] of their costs.  planes / costs: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    planes = torch.empty((max(1, n), LAG_PROBE_ROWS, 256), dtype=torch.int32, device=dev) if planes is None else planes
+    costs = torch.empty((max(1, n), 3), dtype=torch.int64, device=dev) if costs is None else costs
+    assert planes.is_contiguous() and costs.is_contiguous() and costs.dtype == torch.int64
+    assert lags.is_contiguous() and lags.dtype == torch.int32 and lags.numel() >= 3 * n
+    assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
+    _chk("glcLagPlanesSegments", _ct().glcLagPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, lags.data_ptr(),
+                                                             planes.data_ptr(), costs.data_ptr(), stream))
     torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
     return planes[:n], costs[:n]
 

@@ -489,6 +489,32 @@ CUDPPResult glcBigramProbeSegments(const void *d_inBase, const unsigned long lon
 CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
                                    size_t count, size_t maxLen, unsigned int *d_planes, unsigned long long *d_costs, void *stream);
 
+/* The lag probe as two batched calls (csrc/lag_probe.hip, csrc/lag_rule.h): which lag of glcLagDeltaShuffleDevice's lagged, folded
+ * delta a segment wants at each element size, and what the planes of that filter would cost.  The segments are those of
+ * glcFilterProbeSegments: with L = min(d_lengths[i], maxLen) only the first P = L - L % 8 bytes of segment i are counted.  With
+ * x_e[i] the elements of e = 2, 4 or 8 bytes and f_{e,l}[i] the folded difference at lag l = 1 .. 16 -- d = x_e[i] where
+ * i % 2048 < l, else x_e[i] - x_e[i - l] modulo 2^(8 e); f = (d << 1) ^ (0 - (d >> (8 e - 1))), run heads included: what
+ * glcLagDeltaShuffleDevice(e, l, fold = 1) builds its planes from --
+ *   glcLagProbeSegments   row i of d_sums is 48 64-bit words (GLC_LAG_PROBE_SUMS), S[e][l] = sum_i bitlen(f_{e,l}[i]) at word
+ *                         (log2 e - 1) * 16 + (l - 1), bitlen(0) = 0 and bitlen(v) = floor(log2 v) + 1, exact; row i of d_lags is
+ *                         three words, for e = 2, 4 and 8 the l with the smallest sum, ties to the smallest l (P = 0: 1, 1, 1).
+ *   glcLagPlanesSegments  row i of d_planes is 14 histograms of 256 words (GLC_LAG_PROBE_ROWS): rows 0..1 E_2[j][v], rows 2..5
+ *                         E_4[j][v], rows 6..13 E_8[j][v] = the elements whose f_{e,l_e}[i] has byte j equal to v, with l_e read from
+ *                         row i of d_lags in device memory and used as ((word - 1) & 15) + 1; row i of d_costs is three 64-bit
+ *                         words, the cost of glcFilterProbeSegments summed over the planes of E_2, of E_4 and of E_8.
+ * The second call takes the first's d_lags without the host between them.  The rule that reads the costs (csrc/lag_rule.h) is
+ * glcFilterProbeSegments' walk over ten candidates: its seven, then (2, l_2), (4, l_4) and (8, l_8) with the fold, under the same
+ * margin.  No output need be zeroed by the caller.  Both calls only enqueue on `stream`.  A bad argument (a null pointer with
+ * count > 0, d_sums or d_costs not 8-byte or d_planes not 16-byte aligned, two of a call's arrays equal, a maxLen above
+ * GLC_FILTER_PROBE_MAX_LEN or a count above GLC_PROBE_MAX_COUNT) is CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_LAG_PROBE_SUMS 48
+#define GLC_LAG_PROBE_ROWS 14
+CUDPPResult glcLagProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                size_t count, size_t maxLen, unsigned long long *d_sums, unsigned int *d_lags, void *stream);
+CUDPPResult glcLagPlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, const unsigned int *d_lags, unsigned int *d_planes,
+                                 unsigned long long *d_costs, void *stream);
+
 /* {blocks given to the BWT codec, blocks given to the order-0 codec, frames written} of the plan's last successful container
  * compress, whatever its codec; with GLC_CONTAINER_CODEC_CHOOSE the first two are the rule's choices, counted before the record
  * rule stores a block raw.  {0, 0, 0} before the first. */
@@ -591,10 +617,37 @@ CUDPPResult glcPlanGetContainerDeltaLag(CUDPPHandle plan, unsigned int *lag, uns
 CUDPPResult glcPlanSetContainerDeltaGrid(CUDPPHandle plan, unsigned int width, unsigned int fold);
 CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, unsigned int *fold);
 
+/* Filter-lag: filter-auto also picks the delta's lag per frame.  on = 1 writes format version 13: version 10 whose frame word
+ * (word 3 of every frame header, elem | flags << 16) may also carry flags 1 | fold << 1 | (lag - 1) << 8 with elem 2, 4 or 8, the
+ * flags of format version 11: that frame went through glcLagDeltaShuffleDevice(elem, lag, fold) as one segment.  The stream
+ * header's triple is (13, 0, 0), the kinds are version 8's, frames, tables, records and trailer version 10's; table_crc covers the
+ * word as ever.  Per frame the writer enqueues the filter probe and behind it the lag probe (glcLagProbeSegments and
+ * glcLagPlanesSegments, the winners staying in device memory between them), reads ten costs and three lags back with the one wait
+ * filter-auto has, and walks the ten candidates of csrc/lag_rule.h: filter-auto's seven in their order, then (2, l_2), (4, l_4)
+ * and (8, l_8) with the fold, under the same margin.  The writer makes only fold = 1 lag words; the reader takes the whole family,
+ * (lag > 1, fold 0) included.  A stream whose every pick is among the first seven differs from the version-10 stream only in the
+ * header's version and its CRC.  Interleaved channels -- stereo audio, an 8-channel ADC dump, xyz points -- get their channel
+ * count as the lag, and single series the fold, frame by frame ("filter-lag: when").  on = 1 needs filter-auto
+ * on: on = 1 without it, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; whatever
+ * switches filter-auto off switches this off.  0 (the default) writes every stream byte for byte as before.  All six container
+ * entry points write the same bytes, with pipelining on or off.  Range reads of a lag frame use the delta's rounding to 2048
+ * elements and glcUnlagDeltaUnshuffleRangeDevice with the frame's lag and fold.  The setting is also the version the plan speaks:
+ * with it on the plan reads versions 1 to 5, 7, 8, 10 and 13; every other plan, a filter-auto plan included, refuses a version-13
+ * stream as a stream-header failure.  A lag word under a version-10 header, and any word outside the family above, is a
+ * frame-table failure naming the frame.  The 2-D predictor's width, a lag above 16, the unfolded delta at lag > 1 as a candidate
+ * of its own, a choice per block and a sampled probe are not offered. */
+CUDPPResult glcPlanSetContainerFilterLag(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on);
+
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.
- * With filter-auto off every frame counts for the plan's own filter.  Zeros before the first. */
+ * With filter-auto off every frame counts for the plan's own filter; a frame that took a lag candidate of filter-lag counts in
+ * out[7] only.  Zeros before the first. */
 CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8]);
+
+/* Frames of the plan's last successful container compress that took the lag candidate of elem 2, of elem 4 and of elem 8
+ * (glcPlanSetContainerFilterLag), and their sum.  Zeros before the first and with the setting off. */
+CUDPPResult glcContainerLastLagFilters(CUDPPHandle plan, unsigned long long out[4]);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

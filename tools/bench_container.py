@@ -57,9 +57,14 @@ mode on under the shuffle alone, the plain delta (both format version 8) and the
 generated on the host and repeated --, or any typed kind; --rounds R, at least 1) is the grid section: the lag section's settings at
 lag 1 -- the shuffle alone, the plain delta, with --fold the folded delta (format version 11) -- and the 2-D predictor of row width
 W (glcPlanSetContainerDeltaGrid, format version 12), interleaved, with the same output.
+
+--filter-lag (with --lag L [--fold] and the data of the lag section; --rounds R, at least 1) is the filter-lag section: the order-0
+codec with the auto mode on under filter-auto (format version 10), under filter-auto with lag (glcPlanSetContainerFilterLag, format
+version 13: the lag probe per frame, the lag picked per frame) and under the plan set by hand to the data's element size, lag L and
+the fold (format version 11), interleaved, with the filter-auto section's output and what glcContainerLastLagFilters reports.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
-                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] | --grid W [--fold]]"""
+                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold]]"""
 import argparse
 import json
 import os
@@ -464,6 +469,62 @@ def filter_auto_section(torch, glc, plan, d_in, total, elem, delta, rounds, with
     return res
 
 
+def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
+    """the order-0 container with the auto mode on under "filter_auto" (format version 10), "filter_lag" (format version 13: the
+    filter probe and the lag probe per frame, one host wait, the filter and its lag picked per frame) and "hand" (format version 11:
+    elem, lag and fold set by hand, no probe), interleaved: `rounds` rounds of one encode and one decode per setting after one
+    untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["filter_auto", "filter_lag", "hand"]
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+    glc.container_set_auto(plan, 1)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            glc.container_set_filter_auto(plan, 0)             # (filter-lag goes off with it)
+            glc.container_set_shuffle(plan, 0)                 # (the delta and its lag go off with it)
+            if s == "hand":
+                glc.container_set_shuffle(plan, elem)
+                glc.container_set_delta(plan, 1)
+                glc.container_set_delta_lag(plan, lag, fold)
+            else:
+                glc.container_set_filter_auto(plan, 1)
+                glc.container_set_filter_lag(plan, 1 if s == "filter_lag" else 0)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["version"] = int(cont[4].item()) | int(cont[5].item()) << 8
+                res[s]["frames_per_filter"] = list(glc.container_last_filters(plan))
+                res[s]["frames_per_lag_filter"] = list(glc.container_last_lag_filters(plan))
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
     """the order-0 container with the auto mode on under "shuffle" (the shuffle alone), "delta" (the plain delta), "lag" (the
     delta with `lag` and `fold`, format version 11; left out at (1, 0)) and, with a row width `grid`, "grid" (the 2-D predictor
@@ -541,6 +602,8 @@ def main():
                     help="the filter-auto section (format version 10): the auto mode with no filter, with --shuffle / --delta set by hand and with filter-auto")
     ap.add_argument("--filter-auto-off-only", action="store_true", help="the filter-auto section without the setting (what a build without it can run)")
     ap.add_argument("--lag", type=int, default=0, metavar="L", help="the lag section (format version 11): the delta's lag, 1 to 16")
+    ap.add_argument("--filter-lag", action="store_true",
+                    help="the filter-lag section (format version 13): filter-auto, filter-auto with lag, and elem / --lag / --fold set by hand")
     ap.add_argument("--fold", action="store_true", help="the lag or grid section's delta folds its sign")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
     args = ap.parse_args()
@@ -619,6 +682,15 @@ def main():
             plan.set_pipelining(bool(args.pipelining))
             glc.container_set_codec(plan, 1)
             res["grid"] = lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], 1, int(args.fold), max(1, args.rounds), args.grid)
+        print(json.dumps(res))
+        return
+    if args.filter_lag:
+        assert args.lag, "--filter-lag compares with the plan set by hand: give its --lag (and --fold)"
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["filter_lag"] = filter_lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], args.lag, int(args.fold),
+                                                   max(1, args.rounds))
         print(json.dumps(res))
         return
     if args.lag:

@@ -8,7 +8,14 @@ per input, with the candidate the rule picks from the costs.
   blocks   the same call over segments of 1 MiB
   copy     a device-to-device copy
 
-python tools/bench_filter_probe.py [--gib 1] [--rounds 5]"""
+
+--lag adds the lag probe (csrc/lag_probe.hip) over the same buffer as one segment, in the same interleaved rounds, and two
+interleaved-channel inputs (adc16x8 and xyz32 of tests/lag_inputs.py, 32 MiB made on the host and repeated):
+  lag_sums    glcLagProbeSegments: a memset of the sums, k_lp_sums, k_lp_argmin
+  lag_planes  glcLagPlanesSegments at the winners: a memset of the rows, k_lp_planes, k_lp_cost
+with the winners and the candidate the ten-cost walk picks.
+
+python tools/bench_filter_probe.py [--gib 1] [--rounds 5] [--lag]"""
 import argparse
 import importlib.util
 import json
@@ -26,6 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--lag", action="store_true", help="also the lag probe, and the interleaved-channel inputs")
     args = ap.parse_args()
     import torch
     spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
@@ -44,6 +52,10 @@ def main():
     planes = torch.empty((count, 22, 256), dtype=torch.int32, device=dev)
     costs = torch.empty((count, 7), dtype=torch.int64, device=dev)
     out = torch.empty(total, dtype=torch.uint8, device=dev)
+    lp_sums = torch.empty((1, 48), dtype=torch.int64, device=dev)
+    lp_lags = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    lp_planes = torch.empty((1, 14, 256), dtype=torch.int32, device=dev)
+    lp_costs = torch.empty((1, 3), dtype=torch.int64, device=dev)
     L = glc._ct()
 
     def timed(fn):
@@ -55,11 +67,16 @@ def main():
         torch.cuda.synchronize()
         return a.elapsed_time(b) * 1e-3
 
-    for name in ("zeros", "ts64", "float32", "noise"):
+    for name in ("zeros", "ts64", "float32", "noise") + (("adc16x8", "xyz32") if args.lag else ()):
         if name == "zeros":
             d_in = torch.zeros(total, dtype=torch.uint8, device=dev)
         elif name == "ts64":
             d_in = torch.cumsum(torch.randint(900, 1100, (total // 8,), dtype=torch.int64, device=dev, generator=g), 0).view(torch.uint8)
+        elif name in ("adc16x8", "xyz32"):
+            import lag_inputs
+            import numpy as np
+            piece = torch.from_numpy(np.array(lag_inputs.lag_bytes(name, min(total, 32 * MiB)), copy=True)).to(dev)
+            d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
         elif name == "float32":
             d_in = torch.randn(total // 4, dtype=torch.float32, device=dev, generator=g).view(torch.uint8)
         else:
@@ -76,9 +93,19 @@ def main():
         def copy():
             out.copy_(d_in)
 
-        res = {k: [] for k in ("frame_GBps", "blocks_GBps", "copy_GBps")}
+        def lag_sums():
+            glc._chk("glcLagProbeSegments", L.glcLagProbeSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total,
+                                                                   lp_sums.data_ptr(), lp_lags.data_ptr(), None))
+
+        def lag_planes():
+            glc._chk("glcLagPlanesSegments", L.glcLagPlanesSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total, lp_lags.data_ptr(),
+                                                                     lp_planes.data_ptr(), lp_costs.data_ptr(), None))
+
+        calls = (("frame_GBps", frame), ("blocks_GBps", blocks), ("copy_GBps", copy)) + \
+                ((("lag_sums_GBps", lag_sums), ("lag_planes_GBps", lag_planes)) if args.lag else ())
+        res = {k: [] for k, _ in calls}
         for r in range(args.rounds + 1):                        # round 0 is the warm-up
-            for k, fn in (("frame_GBps", frame), ("blocks_GBps", blocks), ("copy_GBps", copy)):
+            for k, fn in calls:
                 t = timed(fn)
                 if r:
                     res[k].append(round(total / t / 1e9, 2))
@@ -88,6 +115,12 @@ def main():
         assert torch.equal(planes[0].to(torch.int64), block_rows) and int(planes[0, :8].sum(dtype=torch.int64).item()) == total
         c = [int(v) for v in costs[0].cpu().tolist()]
         rep = {"workload": "%d MiB of %s" % (count, name), "costs_bytes": [v // 2048 for v in c], "pick": list(CANDS[pick(c)])}
+        if args.lag:
+            import filter_lag_model as FL
+            lags = [int(v) for v in lp_lags[0].cpu().tolist()]
+            c10 = c + [int(v) for v in lp_costs[0].cpu().tolist()]
+            assert int(lp_planes.sum(dtype=torch.int64).item()) == 3 * total
+            rep.update({"lags": lags, "lag_costs_bytes": [v // 2048 for v in c10[7:]], "lag_pick": list(FL.cands(lags)[FL.pick(c10)])})
         for k, v in res.items():
             s = sorted(v)
             rep[k], rep[k + "_median"], rep[k + "_spread"] = v, s[len(s) // 2], round(s[-1] - s[0], 2)
