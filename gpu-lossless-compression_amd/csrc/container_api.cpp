@@ -15,7 +15,9 @@
 // went through -- the writer picks it per frame from the filter probe (filter_probe.hip, filter_rule.h; one host read of seven
 // costs per frame), the readers take it from the frame.  Format version 13 (filter-lag) is version 10 whose frame word may also
 // carry version 11's lag and fold: the writer enqueues the lag probe behind the filter probe (lag_probe.hip, lag_rule.h) and
-// reads ten costs and three lags with the same one wait; its triple (13, 0, 0) is parse_stream_format()'s.
+// reads ten costs and three lags with the same one wait; its triple (13, 0, 0) is parse_stream_format()'s.  Format version 14
+// (filter-grid) is version 13 whose frame word may also name the 2-D predictor of version 12: the grid probe (grid_probe.hip,
+// grid_rule.h) is enqueued behind the lag probe, and the one wait brings thirteen costs, three lags and three widths.
 //
 // Encode (Encoder).  A filtered frame is staged through filter_device() into staging kept with the plan and encoded from there;
 // crc_all is taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman
@@ -52,6 +54,7 @@
 #include "container_internal.h"
 #include "dedup_rule.h"
 #include "filter_rule.h"
+#include "grid_rule.h"
 #include "lag_rule.h"
 
 #include <fcntl.h>
@@ -183,6 +186,10 @@ struct Encoder {
     bool filter_lag = false;
     unsigned long long *lp_sums = nullptr;
     uint32_t *lp_lags = nullptr, *lp_planes = nullptr;
+    // filter-grid (format version 14): the grid probe's sums, winners and rows of the same frame; its three costs lie behind the lag
+    // probe's, the lags behind those and the widths behind the lags: one copy brings all of it
+    bool filter_grid = false;
+    uint32_t *gw_sums = nullptr, *gw_widths = nullptr, *gw_planes = nullptr;
     unsigned long long *fp_costs = nullptr, *fp_seg = nullptr, *h_costs = nullptr;
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -293,12 +300,18 @@ struct Encoder {
         if (filter_auto) {
             fp_planes = c.take<uint32_t>(FILTER_ROWS * 256);
             fp_costs = c.take<unsigned long long>(FP_HOST_WORDS);
-            lp_lags = reinterpret_cast<uint32_t *>(fp_costs + LAG_CANDS);
+            lp_lags = reinterpret_cast<uint32_t *>(fp_costs + ncosts());
+            gw_widths = lp_lags + 4;
             fp_seg = c.take<unsigned long long>(2);
             if (filter_lag) {
                 lp_sums = c.take<unsigned long long>(LAG_SUMS);
                 c.align(16);
                 lp_planes = c.take<uint32_t>(LAG_ROWS * 256);
+            }
+            if (filter_grid) {
+                c.align(16);
+                gw_planes = c.take<uint32_t>(LAG_ROWS * 256);
+                gw_sums = c.take<uint32_t>(GRID_SUMS);
             }
         }
     }
@@ -311,6 +324,7 @@ struct Encoder {
         mode = s.mode;
         filter_auto = s.filter_auto;
         filter_lag = s.filter_lag;
+        filter_grid = s.filter_grid;
         for (uint32_t i = 0; i < FILTER_CANDS; i++) {             // the candidate that is the plan's own filter
             const FilterCand c = filter_cand(i);
             if (c.elem == (fmt.elem ? fmt.elem : 1u) && (c.delta != 0) == fmt.delta()) own_pick = i;
@@ -344,14 +358,18 @@ struct Encoder {
     // filter-auto: the probe of the frame where it lies, its seven costs read back with one wait (as the CHOOSE codec reads its
     // stats), and the rule on the host.  A frame beyond the probe's 2^31 bytes is judged by its first 2^31.  With filter-lag the
     // lag probe's sums, winners, rows and costs are enqueued behind it -- the winners never leave the device between them -- and
-    // the same wait brings ten costs and three lags; the walk is lag_rule.h's.  *pick: the candidate (below LAG_CANDS), *lag: its lag.
-    static constexpr size_t FP_HOST_WORDS = LAG_CANDS + 2;    // ten costs, then the three winners in two 64-bit words
-    CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick, uint32_t *lag)
+    // the same wait brings ten costs and three lags; the walk is lag_rule.h's.  With filter-grid the grid probe follows in the same
+    // way, and the walk is grid_rule.h's over thirteen costs.  *pick: the candidate (below GRID_CANDS), *lag: its lag, *width: its
+    // row width (0 but for a grid candidate).
+    static constexpr size_t FP_HOST_WORDS = GRID_CANDS + 4;   // up to thirteen costs, then the three lags and the three widths in two 64-bit words each
+    size_t ncosts() const { return filter_grid ? GRID_CANDS : LAG_CANDS; }
+    CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick, uint32_t *lag, uint32_t *width)
     {
         const uint32_t max_len = (uint32_t)std::min<unsigned long long>(frame_len, GLC_FILTER_PROBE_MAX_LEN);
         CT_TRY(ct_put_u64(P.st, fp_seg + 1, frame_len));     // (fp_seg[0], the segment's offset, is 0 from init() on)
         CT_TRY(filter_probe_segments(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, fp_planes, fp_costs));
         *lag = 1;
+        *width = 0;
         if (!filter_lag) {
             CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FILTER_CANDS, hipMemcpyDeviceToHost, P.st));
             CT_TRY(hipStreamSynchronize(P.st));
@@ -360,10 +378,16 @@ struct Encoder {
         }
         CT_TRY(lag_probe_sums(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, lp_sums, lp_lags));
         CT_TRY(lag_probe_planes(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, lp_lags, lp_planes, fp_costs + FILTER_CANDS));
-        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * FP_HOST_WORDS, hipMemcpyDeviceToHost, P.st));
+        if (filter_grid) {
+            CT_TRY(grid_probe_sums(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, gw_sums, gw_widths));
+            CT_TRY(grid_probe_planes(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, gw_widths, gw_planes, fp_costs + LAG_CANDS));
+        }
+        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * (ncosts() + 4), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
-        *pick = lag_pick(h_costs);
-        if (*pick >= FILTER_CANDS) *lag = lag_clamp(reinterpret_cast<const uint32_t *>(h_costs + LAG_CANDS)[*pick - FILTER_CANDS]);
+        const uint32_t *words = reinterpret_cast<const uint32_t *>(h_costs + ncosts());      // three lags, a pad, three widths
+        *pick = filter_grid ? grid_pick(h_costs) : lag_pick(h_costs);
+        if (*pick >= LAG_CANDS) *width = grid_width_word(words[4 + *pick - LAG_CANDS]);      // (never 0: such a candidate costs GRID_NO_COST)
+        else if (*pick >= FILTER_CANDS) *lag = lag_clamp(words[*pick - FILTER_CANDS]);
         return CUDPP_SUCCESS;
     }
 
@@ -380,16 +404,18 @@ struct Encoder {
         CtFormat ff = fmt;                                    // the format whose filter this frame goes through
         uint32_t pick = own_pick;
         if (filter_auto) {
-            uint32_t lag = 1;
-            const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick, &lag);
+            uint32_t lag = 1, width = 0;
+            const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick, &lag, &width);
             if (r != CUDPP_SUCCESS) return r;
-            const uint32_t lags[LAG_ELEMS] = {lag, lag, lag};
-            const LagCand c = lag_cand(pick, lags);           // (below FILTER_CANDS: filter_rule.h's candidate, lag 1 and no fold)
+            const uint32_t lags[LAG_ELEMS] = {lag, lag, lag}, widths[LAG_ELEMS] = {width, width, width};
+            const GridCand c = grid_cand(pick, lags, widths); // (below FILTER_CANDS: filter_rule.h's candidate, lag 1 and no fold)
             ff.elem = c.elem > 1 ? c.elem : 0;
-            ff.flags = c.delta ? CT_FLAG_DELTA | (c.fold ? CT_FLAG_FOLD : 0u) | (c.lag - 1u) << CT_LAG_SHIFT : 0;
+            ff.flags = c.delta ? CT_FLAG_DELTA | (c.fold ? CT_FLAG_FOLD : 0u) | (c.lag - 1u) << CT_LAG_SHIFT | (c.width ? CT_FLAG_GRID : 0u) : 0;
+            ff.width = c.width;                               // (the frame's format: ct_frame_format()'s of the word written below)
         }
-        if (pick < FILTER_CANDS) rep.filters[pick]++;         // (a frame that took a lag candidate counts among all frames only)
-        else { rep.lag_filters[pick - FILTER_CANDS]++; rep.lag_filters[LAG_ELEMS]++; }
+        if (pick < FILTER_CANDS) rep.filters[pick]++;         // (a frame that took a lag or grid candidate counts among all frames only)
+        else if (pick < LAG_CANDS) { rep.lag_filters[pick - FILTER_CANDS]++; rep.lag_filters[LAG_ELEMS]++; }
+        else { rep.grid_filters[pick - LAG_CANDS]++; rep.grid_filters[LAG_ELEMS]++; }
         rep.filters[FILTER_CANDS]++;
         if (ff.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
@@ -640,6 +666,7 @@ struct Encoder {
         memcpy(r.choice, rep.choice, sizeof r.choice);
         memcpy(r.filters, rep.filters, sizeof r.filters);
         memcpy(r.lag_filters, rep.lag_filters, sizeof r.lag_filters);
+        memcpy(r.grid_filters, rep.grid_filters, sizeof r.grid_filters);
         set_error(P.h, CT_OK);
         return CUDPP_SUCCESS;
     }
@@ -1245,7 +1272,7 @@ CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &i
     const CUDPPResult r = walk_result(plan, end, stopped);
     if (r != CUDPP_SUCCESS) return r;
     ix->fmt = CtFormat();
-    (void)parse_stream_format(ix->hdr, &ix->fmt);
+    (void)parse_header_format(ix->hdr, &ix->fmt);
     ix->block_len = ix->hdr[2];
     ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
     *index = ix.release();
@@ -1658,6 +1685,11 @@ CUDPPResult glcContainerLastLagFilters(CUDPPHandle plan, unsigned long long out[
     return last_report(plan, false, out, LAG_ELEMS + 1, [](const CtReports &r) { return r.lag_filters; });
 }
 
+CUDPPResult glcContainerLastGridFilters(CUDPPHandle plan, unsigned long long out[4])
+{
+    return last_report(plan, false, out, LAG_ELEMS + 1, [](const CtReports &r) { return r.grid_filters; });
+}
+
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     return ct_set(plan, [&](CtSettings &s) { return s.set_shuffle(elem); });
@@ -1708,6 +1740,11 @@ CUDPPResult glcPlanSetContainerFilterLag(CUDPPHandle plan, unsigned int on)
     return ct_set(plan, [&](CtSettings &s) { return s.set_filter_lag(on); });
 }
 
+CUDPPResult glcPlanSetContainerFilterGrid(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_filter_grid(on); });
+}
+
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
 {
     return ct_get(plan, elem, [](const CtSettings &s) { return s.shuffle; });
@@ -1756,6 +1793,11 @@ CUDPPResult glcPlanGetContainerFilterAuto(CUDPPHandle plan, unsigned int *on)
 CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on)
 {
     return ct_get(plan, on, [](const CtSettings &s) { return s.filter_lag ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.filter_grid ? 1u : 0u; });
 }
 
 CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold)

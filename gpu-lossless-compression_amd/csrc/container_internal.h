@@ -256,17 +256,23 @@ __host__ __device__ inline bool ct_grid_flags_legal(uint32_t flags) { return (fl
 // 13: version 10 whose frame word may also name the lagged, folded delta: elem | flags << 16 with flags 0, 1, or a value that
 // ct_lag_flags_legal() accepts (1 | fold << 1 | (lag - 1) << 8) with elem 2, 4 or 8; the stream header's triple is (13, 0, 0)
 constexpr uint32_t CT_VERSION_FILTER_LAG = 13;
-constexpr uint32_t CT_VERSION_MAX = CT_VERSION_FILTER_LAG;
+// 14: version 13 whose frame word may also name the 2-D predictor: a word with bit 31 set is elem | width << 8 | fold << 30 | 1 << 31
+// (version 12's header word 3 with the fold in bit 30 -- elem 2, 4 or 8, width 2..65536, bits 25..29 zero); under version 13 every
+// such word is illegal, so the two families cannot collide.  The stream header's triple is (14, 0, 0)
+constexpr uint32_t CT_VERSION_FILTER_GRID = 14;
+constexpr uint32_t CT_WORD_GRID = 1u << 31, CT_WORD_GRID_FOLD = 1u << 30, CT_WORD_GRID_WIDTH = 0x1FFFFu << CT_WIDTH_SHIFT;
+constexpr uint32_t CT_VERSION_MAX = CT_VERSION_FILTER_GRID;
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
-// its filter-auto setting version 10, its delta-lag setting version 11, its grid setting version 12 and its filter-lag setting
-// version 13 (each is only ever on with the auto mode, so that mode's bits come with it; filter-lag only with filter-auto)
+// its filter-auto setting version 10, its delta-lag setting version 11, its grid setting version 12, its filter-lag setting
+// version 13 and its filter-grid setting version 14 (each is only ever on with the auto mode, so that mode's bits come with it;
+// filter-lag only with filter-auto, filter-grid only with filter-lag)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
-constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128, CT_READS_FILTER_LAG = 256;
+constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128, CT_READS_FILTER_LAG = 256, CT_READS_FILTER_GRID = 512;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_MAX + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F, 0x2F, 0x2F};
+    constexpr uint32_t K[CT_VERSION_MAX + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F, 0x2F, 0x2F, 0x2F};
     return version <= CT_VERSION_MAX ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
@@ -275,14 +281,16 @@ __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 // are a family of flags over it: the delta's lag and fold; version 12's a family of row widths, which ride in the element word).
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
-    uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12
+    uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12 and in a grid FRAME's format under version 14
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     // the delta's lag and fold: (1, 0) below version 11; under version 13 a FRAME's format (ct_frame_format) carries them
-    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG; }
+    __host__ __device__ bool frame_filters() const { return version == CT_VERSION_FILTER || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID; }
+    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID; }
     __host__ __device__ uint32_t lag() const { return lag_flags() ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
     __host__ __device__ uint32_t fold() const { return (lag_flags() || version == CT_VERSION_GRID) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
-    __host__ __device__ bool grid() const { return version == CT_VERSION_GRID; }
+    // the 2-D predictor: version 12's streams, and under version 14 the format of a frame whose word names it
+    __host__ __device__ bool grid() const { return version == CT_VERSION_GRID || (version == CT_VERSION_FILTER_GRID && width != 0); }
     // the stream header's word 3: the element size, under version 12 with the row width above it
     __host__ __device__ uint32_t word3() const { return elem | width << CT_WIDTH_SHIFT; }
     __host__ __device__ uint32_t kinds() const { return ct_kinds(version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4)
@@ -298,25 +306,41 @@ struct CtFormat {
                version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
                version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
                version == CT_VERSION_LAG ? CT_READS_LAG : version == CT_VERSION_GRID ? CT_READS_GRID :
-               version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : 0u;
+               version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : version == CT_VERSION_FILTER_GRID ? CT_READS_FILTER_GRID : 0u;
     }
 };
-// a frame header's word 3.  Versions 1 to 9, 11 and 12 keep it 0; under versions 10 and 13 it is the frame's filter.  ct_frame_word_legal() is the
+// a frame header's word 3.  Versions 1 to 9, 11 and 12 keep it 0; under versions 10, 13 and 14 it is the frame's filter.  ct_frame_word_legal() is the
 // header's range check on it, ct_frame_format() the format whose filter a frame with a legal word went through: the stream's
 // below version 10, the word's under it
-__host__ __device__ inline uint32_t ct_frame_word(const CtFormat &f) { return f.elem | (f.flags << 16); }
+__host__ __device__ inline uint32_t ct_frame_word(const CtFormat &f)
+{
+    if (f.width) return f.elem | f.width << CT_WIDTH_SHIFT | (f.fold() ? CT_WORD_GRID_FOLD : 0u) | CT_WORD_GRID;
+    return f.elem | (f.flags << 16);
+}
 __host__ __device__ inline bool ct_frame_word_legal(const CtFormat &stream, uint32_t word)
 {
-    if (stream.version != CT_VERSION_FILTER && stream.version != CT_VERSION_FILTER_LAG) return word == 0;
+    if (!stream.frame_filters()) return word == 0;
+    if (word & CT_WORD_GRID) {                                // version 14's grid word
+        const uint32_t e = word & 0xFFu;
+        return stream.version == CT_VERSION_FILTER_GRID && !(word & ~(0xFFu | CT_WORD_GRID_WIDTH | CT_WORD_GRID_FOLD | CT_WORD_GRID)) &&
+               (e == 2 || e == 4 || e == 8) && ct_grid_width_ok((word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT);
+    }
     const uint32_t elem = word & 0xFFFFu, flags = word >> 16;
     if (elem == 0) return flags == 0;
     if (elem != 2 && elem != 4 && elem != 8) return false;
-    return flags <= CT_FLAG_DELTA || (stream.version == CT_VERSION_FILTER_LAG && ct_lag_flags_legal(flags));
+    return flags <= CT_FLAG_DELTA || (stream.version != CT_VERSION_FILTER && ct_lag_flags_legal(flags));
 }
 __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint32_t word)
 {
     CtFormat f = stream;
-    if (stream.version == CT_VERSION_FILTER || stream.version == CT_VERSION_FILTER_LAG) { f.elem = word & 0xFFFFu; f.flags = word >> 16; }
+    if (!stream.frame_filters()) return f;
+    if (word & CT_WORD_GRID) {                                // (legal under version 14 alone: version 12's filter for this frame)
+        f.elem = word & 0xFFu;
+        f.width = (word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT;
+        f.flags = CT_FLAG_DELTA | CT_FLAG_GRID | (word & CT_WORD_GRID_FOLD ? CT_FLAG_FOLD : 0u);
+        return f;
+    }
+    f.elem = word & 0xFFFFu; f.flags = word >> 16;
     return f;
 }
 // a format's filter over one segment, or its inverse
@@ -429,12 +453,19 @@ __host__ __device__ inline bool parse_stream_format(const uint32_t h[8], CtForma
     if (parse_format(h, f)) return true;
     return f->version == CT_VERSION_FILTER_LAG && f->flags == 0 && f->elem == 0 && f->width == 0;
 }
+// version 14's one triple (14, 0, 0) beside it, accepted the way 13 was: parse_stream_format() is pinned up to version 15 by
+// tools/filter_lag_rule_check.cpp, so this is the function the readers call; tools/filter_grid_rule_check.cpp pins it
+__host__ __device__ inline bool parse_header_format(const uint32_t h[8], CtFormat *f)
+{
+    if (parse_stream_format(h, f)) return true;
+    return f->version == CT_VERSION_FILTER_GRID && f->flags == 0 && f->elem == 0 && f->width == 0;
+}
 
 // the checks on a stream header; false = refused
 __host__ __device__ inline bool check_stream_header(const CrcTables &C, const uint32_t h[8], CtFormat *fmt, uint32_t *block_len,
                                                     unsigned long long *total)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_stream_format(h, fmt)) return false;
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_header_format(h, fmt)) return false;
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
     *block_len = h[2];
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
@@ -543,10 +574,14 @@ struct CtSettings {
     // filter-lag: filter-auto also weighs the lagged, folded delta at the lag it finds per frame (lag_rule.h) and writes version
     // 13.  Only ever on with filter-auto on; whatever switches that off switches this off
     bool filter_lag = false;
+    // filter-grid: filter-lag also weighs the 2-D predictor at the row width it finds per frame (grid_rule.h) and writes version
+    // 14.  Only ever on with filter-lag on; whatever switches that off switches this off
+    bool filter_grid = false;
     void filter_keep()
     {
         if (mode != CT_MODE_AUTO) filter_auto = false;
         if (!filter_auto) filter_lag = false;
+        if (!filter_lag) filter_grid = false;
     }
     // delta-lag: the delta's predecessor is `lag` elements back and its sign is folded where fold = 1 (lag.hip; the writer writes
     // version 11).  Anything but (1, 0) is only ever on with the order-0 codec, the auto mode, the shuffle and the delta on and
@@ -622,13 +657,20 @@ struct CtSettings {
     {
         if (on > 1 || (on && !filter_auto)) return false;
         filter_lag = on != 0;
+        filter_keep();
+        return true;
+    }
+    bool set_filter_grid(uint32_t on)
+    {
+        if (on > 1 || (on && !filter_lag)) return false;
+        filter_grid = on != 0;
         return true;
     }
     // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
-               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) |
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) |
                                       (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
@@ -646,7 +688,7 @@ struct CtSettings {
 inline CtFormat format_of(const CtSettings &s)
 {
     CtFormat f;
-    if (s.filter_auto) { f.version = s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
+    if (s.filter_auto) { f.version = s.filter_grid ? CT_VERSION_FILTER_GRID : s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
     f.elem = s.shuffle;
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
     if (s.lag_on()) {                                         // (what (1, 0) does, version 8 says)
@@ -674,6 +716,7 @@ struct CtReports {
     unsigned long long choice[3] = {};                     // {blocks given to the BWT codec, to the order-0 codec, frames} of the last successful compress
     unsigned long long filters[FILTER_CANDS + 1] = {};     // frames per candidate of filter_rule.h, then all frames, of the last successful compress
     unsigned long long lag_filters[4] = {};                // frames that took the lag candidate of elem 2, 4, 8 (lag_rule.h) and their sum, of the same compress
+    unsigned long long grid_filters[4] = {};               // frames that took the grid candidate of elem 2, 4, 8 (grid_rule.h) and their sum, of the same compress
 };
 CtReports &plan_container_reports(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
@@ -824,6 +867,17 @@ hipError_t lag_probe_sums(hipStream_t st, const uint8_t *data, const unsigned lo
                           uint32_t count, uint32_t max_len, unsigned long long *sums, uint32_t *lags);
 hipError_t lag_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                             uint32_t count, uint32_t max_len, const uint32_t *lags, uint32_t *planes, unsigned long long *costs);
+// the costs alone, of `count` segments' 14 rows; widths: null, or three width words a segment (device memory): an element size whose
+// word is outside 2..65536 costs GRID_NO_COST
+hipError_t lag_probe_cost(hipStream_t st, const uint32_t *planes, uint32_t count, const uint32_t *widths, unsigned long long *costs);
+// the grid probe (grid_probe.hip, grid_rule.h), the segments as the filter probe's: row i of sums = the 3 * 65537 sums S_e[W] of
+// segment i (0xFFFFFFFF where W is no candidate) and row i of widths its three winners (0: no candidate); row i of planes = the 14
+// histograms of segment i at the widths of row i of `widths` (device memory; a word outside 2..65536 names no width: zero rows,
+// GRID_NO_COST), row i of costs their three costs.  planes is 16-byte aligned; nothing need be zeroed.  Everything only enqueues.
+hipError_t grid_probe_sums(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                           uint32_t count, uint32_t max_len, uint32_t *sums, uint32_t *widths);
+hipError_t grid_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                             uint32_t count, uint32_t max_len, const uint32_t *widths, uint32_t *planes, unsigned long long *costs);
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
 // block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
 // read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the

@@ -20,12 +20,15 @@
 //                16 bytes lag * e bytes in front of it (lag_tile.h's read, mask, subtract and fold).  The LDS counter copies
 //                and the uniform shortcut are k_fp_probe's: a wave whose lanes hold one value at a byte position adds 64 once
 //                -- the upper planes of a good lag are almost all zero, so without it every lane lands on one counter.
-//   k_lp_cost    the three costs of a segment from its 14 rows: one wave per plane, as k_fp_cost.
+//   k_lp_cost    the three costs of a segment from its 14 rows: one wave per plane, as k_fp_cost.  The grid probe
+//                (grid_probe.hip) runs it over its own rows, with the width words that say which element sizes have a candidate.
 // Any segment length up to 2^31, any byte alignment; only the first L - L % 8 bytes are counted.
 #include "container_internal.h"
 #include "glc_device.h"
+#include "grid_rule.h"
 #include "lag_rule.h"
 #include "lag_tile.h"
+#include "plane_hist.h"
 
 namespace glc {
 
@@ -174,18 +177,6 @@ __global__ __launch_bounds__(64) void k_lp_argmin(const unsigned long long *__re
     lags[(size_t)b * LAG_ELEMS + threadIdx.x] = lag_argmin(sums + (size_t)b * LAG_SUMS + threadIdx.x * LAG_MAX);
 }
 
-// the OR of x over the wave, in every lane's scalar (k_fp_probe's)
-__device__ __forceinline__ uint32_t lp_wave_or(uint32_t x)
-{
-    x |= GLC_DPP(x, 0x111, 0xf);
-    x |= GLC_DPP(x, 0x112, 0xf);
-    x |= GLC_DPP(x, 0x114, 0xf);
-    x |= GLC_DPP(x, 0x118, 0xf);
-    x |= GLC_DPP(x, 0x142, 0xa);
-    x |= GLC_DPP(x, 0x143, 0xc);
-    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
-}
-
 // the folded differences of the granule at tile byte o, its predecessors `lag` elements back
 template <uint32_t ELEM>
 __device__ __forceinline__ void lp_folded(const uint32_t *raw, uint32_t o, uint32_t lag, const uint32_t (&c)[4], uint32_t (&f)[4])
@@ -218,39 +209,6 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_planes(const uint8_t *data, c
     if (tid < LP_FRONT) raw[tid] = 0;
     for (uint32_t i = tid; i < LP_COPIES * LP_COPY_WORDS; i += LP_THREADS) s_h[i] = 0;
     uint32_t *H = s_h + (tid & (LP_COPIES - 1)) * LP_COPY_WORDS;
-    // one group of a pass: this lane's n (0, 8 or 16) bytes d of histograms row0 .. row0 + e - 1, byte k to row row0 + k % e
-    auto group = [&](const uint32_t d[4], uint32_t n, bool whole, uint32_t row0, uint32_t e) {
-        if (whole) {                                           // every lane holds 16 bytes: are they the first lane's?
-            uint32_t f[4];
-            bool same = true;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
-                f[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)d[k]);
-                same = same && d[k] == f[k];
-            }
-            if (__ballot(!same) == 0) {
-                if (lane < 16) {
-                    const uint32_t w = lane < 4 ? f[0] : lane < 8 ? f[1] : lane < 12 ? f[2] : f[3];
-                    atomicAdd(&H[(row0 + (lane & (e - 1))) * LP_PITCH + ((w >> (8 * (lane & 3))) & 0xFFu)], 64u);
-                }
-                return;
-            }
-            // the byte positions that hold one value in every lane (the high bytes of a small difference) cost one add of 64
-            uint32_t var[4];
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) var[k] = lp_wave_or(d[k] ^ f[k]);
-#pragma unroll
-            for (uint32_t k = 0; k < 16; k++) {
-                uint32_t *row = H + (row0 + (k & (e - 1))) * LP_PITCH;
-                if ((var[k >> 2] >> (8 * (k & 3))) & 0xFFu) atomicAdd(&row[(d[k >> 2] >> (8 * (k & 3))) & 0xFFu], 1u);
-                else if (lane == 0) atomicAdd(&row[(f[k >> 2] >> (8 * (k & 3))) & 0xFFu], 64u);
-            }
-            return;
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < 16; k++)
-            if (k < n) atomicAdd(&H[(row0 + (k & (e - 1))) * LP_PITCH + ((d[k >> 2] >> (8 * (k & 3))) & 0xFFu)], 1u);
-    };
     for (uint32_t t = t0; t < t1; t += LP_TILE) {
         const uint32_t n = min(LP_TILE, t1 - t);               // a multiple of 8
         __syncthreads();                                       // (the tile before has been read; the counters are zero)
@@ -268,9 +226,9 @@ __global__ __launch_bounds__(LP_THREADS) void k_lp_planes(const uint8_t *data, c
                 lp_folded<4>(raw, o, l4, c, f4);
                 lp_folded<8>(raw, o, l8, c, f8);
             }
-            group(f2, nn, whole, lag_plane_row(2), 2);
-            group(f4, nn, whole, lag_plane_row(4), 4);
-            group(f8, nn, whole, lag_plane_row(8), 8);
+            ph_group<LP_PITCH>(H, f2, nn, whole, lag_plane_row(2), 2, lane);
+            ph_group<LP_PITCH>(H, f4, nn, whole, lag_plane_row(4), 4, lane);
+            ph_group<LP_PITCH>(H, f8, nn, whole, lag_plane_row(8), 8, lane);
         }
     }
     __syncthreads();
@@ -290,8 +248,10 @@ __device__ __forceinline__ unsigned long long lp_wave_sum64(unsigned long long x
     return x;
 }
 
+// widths: null, or (the grid rule's use, grid_rule.h) three width words a segment: an element size whose word names no width has
+// no candidate, and its cost is GRID_NO_COST
 __global__ __launch_bounds__(LP_PLANE_WAVES * 64) void k_lp_cost(const uint32_t *__restrict__ planes, uint32_t count,
-                                                                 unsigned long long *__restrict__ costs)
+                                                                 const uint32_t *__restrict__ widths, unsigned long long *__restrict__ costs)
 {
     __shared__ unsigned long long s_plane[LAG_ROWS];
     const uint32_t b = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -312,6 +272,7 @@ __global__ __launch_bounds__(LP_PLANE_WAVES * 64) void k_lp_cost(const uint32_t 
         const uint32_t e = 2u << threadIdx.x;
         unsigned long long c = 0;
         for (uint32_t j = 0; j < e; j++) c += s_plane[lag_plane_row(e) + j];
+        if (widths && !grid_width_word(widths[(size_t)b * LAG_ELEMS + threadIdx.x])) c = GRID_NO_COST;
         costs[(size_t)b * LAG_ELEMS + threadIdx.x] = c;
     }
 }
@@ -354,7 +315,12 @@ hipError_t lag_probe_planes(hipStream_t st, const uint8_t *data, const unsigned 
         hipLaunchKernelGGL(k_lp_planes, grid, dim3(LP_THREADS), 0, st, data, data_off, data_len, max_len, span, lags, planes);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_lp_cost, dim3(count), dim3(LP_PLANE_WAVES * 64), 0, st, planes, count, costs);
+    return lag_probe_cost(st, planes, count, nullptr, costs);
+}
+
+hipError_t lag_probe_cost(hipStream_t st, const uint32_t *planes, uint32_t count, const uint32_t *widths, unsigned long long *costs)
+{
+    hipLaunchKernelGGL(k_lp_cost, dim3(count), dim3(LP_PLANE_WAVES * 64), 0, st, planes, count, widths, costs);
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 // CRC of segments (container.hip), the byte-plane shuffle, the delta + shuffle and its lagged, folded form with their range forms
 // (shuffle.hip, delta.hip, lag.hip) and the 2-D predictor over it (grid.hip),
 // the sparse split and join (sparse.hip), the dedup map and fill (dedup.hip), the zero-run split and join (zrun.hip), the rANS
-// coder (ans.hip) and the probes (auto.hip, choose.hip, filter_probe.hip, lag_probe.hip).  The container over a plan, which runs the same
+// coder (ans.hip) and the probes (auto.hip, choose.hip, filter_probe.hip, lag_probe.hip, grid_probe.hip).  The container over a plan, which runs the same
 // passes inside its frames, is container_api.cpp.
 #include "../../include/glc_container.h"
 #include "container_internal.h"
@@ -386,7 +386,7 @@ CUDPPResult glcFilterProbeSegments(const void *d_inBase, const unsigned long lon
     return CUDPP_SUCCESS;
 }
 
-// the two lag probes: a bad argument is refused before anything is enqueued
+// the two lag probes and the two grid probes: a bad argument is refused before anything is enqueued
 static bool lag_probe_args_ok(const void *in, const void *off, const void *len, size_t count, size_t maxLen, const void *a, unsigned aAlign,
                               const void *b, unsigned bAlign)
 {
@@ -416,6 +416,30 @@ CUDPPResult glcLagPlanesSegments(const void *d_inBase, const unsigned long long 
         static_cast<const void *>(d_lags) == d_costs) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     CT_TRY(lag_probe_planes(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
                             (uint32_t)maxLen, d_lags, d_planes, d_costs));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcGridProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned int *d_sums, unsigned int *d_widths, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_sums, 4, d_widths, 4)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    CT_TRY(grid_probe_sums(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                           (uint32_t)maxLen, d_sums, d_widths));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcGridPlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_widths, unsigned int *d_planes,
+                                  unsigned long long *d_costs, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_planes, 16, d_costs, 8)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    // (the widths are read while the outputs are written: neither output may be them)
+    if (!d_widths || (reinterpret_cast<uintptr_t>(d_widths) & 3) || static_cast<const void *>(d_widths) == d_planes ||
+        static_cast<const void *>(d_widths) == d_costs) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(grid_probe_planes(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                             (uint32_t)maxLen, d_widths, d_planes, d_costs));
     return CUDPP_SUCCESS;
 }
 

@@ -722,6 +722,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerDeltaGrid", "glcPlanGetContainerDeltaGrid",
                      "glcLagProbeSegments", "glcLagPlanesSegments",
                      "glcPlanSetContainerFilterLag", "glcPlanGetContainerFilterLag", "glcContainerLastLagFilters",
+                     "glcGridProbeSegments", "glcGridPlanesSegments",
+                     "glcPlanSetContainerFilterGrid", "glcPlanGetContainerFilterGrid", "glcContainerLastGridFilters",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -797,6 +799,9 @@ def _ct():
         L.glcContainerLastLagFilters.argtypes = [sz, ullp]
         L.glcLagProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcLagPlanesSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.glcContainerLastGridFilters.argtypes = [sz, ullp]
+        L.glcGridProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
+        L.glcGridPlanesSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.glcDedupWorkBytes.argtypes = [sz, sz]
         L.glcDedupWorkBytes.restype = sz
         L.glcDedupMapSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp]
@@ -992,6 +997,24 @@ def container_last_lag_filters(plan):
     return tuple(int(v) for v in a)
 
 
+def container_set_filter_grid(plan, on):
+    """filter-grid of the plan's container ENCODER (format version 14: filter-lag also weighs the 2-D predictor at the row width
+    the grid probe finds per frame): True / 1 needs filter-lag on, and whatever switches filter-lag off switches it off.  It is
+    also the version the plan reads: on, versions 1 to 5, 7, 8, 10, 13 and 14; off, a version-14 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerFilterGrid", _ct().glcPlanSetContainerFilterGrid(plan.handle, int(on)))
+
+
+def container_get_filter_grid(plan):
+    return _get_uint("glcPlanGetContainerFilterGrid", plan)
+
+
+def container_last_grid_filters(plan):
+    """(frames that took the grid candidate of elem 2, of elem 4, of elem 8, their sum) of the plan's last successful compress"""
+    a = (C.c_ulonglong * 4)()
+    _chk("glcContainerLastGridFilters", _ct().glcContainerLastGridFilters(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
 def container_set_delta_lag(plan, lag, fold):
     """the lag and fold of the delta of the plan's container ENCODER (format version 11: the predecessor `lag` elements back, the
     sign folded into bit 0 where fold is 1); (1, 0) is off.  Anything else needs the order-0 codec, the auto mode, the shuffle
@@ -1146,6 +1169,43 @@ def lag_planes_segments(d_in, offsets, lengths, lags, max_len=None, planes=None,
     assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
     _chk("glcLagPlanesSegments", _ct().glcLagPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, lags.data_ptr(),
                                                              planes.data_ptr(), costs.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return planes[:n], costs[:n]
+
+
+GRID_PROBE_ROW, GRID_PROBE_SUMS = 65537, 3 * 65537
+
+
+def grid_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, widths=None, stream=None):
+    """the grid probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (sums, widths) --
+    an int32 tensor [count, 3 * 65537] whose word k * 65537 + W is S_e[W] for e = 2 << k (the bit pattern 0xFFFFFFFF, so -1, where W
+    is no candidate), and an int32 tensor [count, 3] of the width with the smallest sum per element size, 0 where there is none
+    (csrc/grid_rule.h).  sums / widths: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    sums = torch.empty((max(1, n), GRID_PROBE_SUMS), dtype=torch.int32, device=dev) if sums is None else sums
+    widths = torch.empty((max(1, n), 3), dtype=torch.int32, device=dev) if widths is None else widths
+    assert sums.is_contiguous() and widths.is_contiguous() and sums.dtype == torch.int32 and widths.dtype == torch.int32
+    assert sums.numel() >= GRID_PROBE_SUMS * n and widths.numel() >= 3 * n
+    _chk("glcGridProbeSegments", _ct().glcGridProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
+                                                             sums.data_ptr(), widths.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return sums[:n], widths[:n]
+
+
+def grid_planes_segments(d_in, offsets, lengths, widths, max_len=None, planes=None, costs=None, stream=None):
+    """the plane probe of the grid rule over the same segments at the widths of the device int32 tensor `widths` [count, 3] (a
+    word outside 2..65536 names no width: zero rows and the cost 2^56): (planes, costs) -- an int32 tensor [count, 14, 256] and an
+    int64 tensor [count, 3].  planes / costs: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    planes = torch.empty((max(1, n), LAG_PROBE_ROWS, 256), dtype=torch.int32, device=dev) if planes is None else planes
+    costs = torch.empty((max(1, n), 3), dtype=torch.int64, device=dev) if costs is None else costs
+    assert planes.is_contiguous() and costs.is_contiguous() and costs.dtype == torch.int64
+    assert widths.is_contiguous() and widths.dtype == torch.int32 and widths.numel() >= 3 * n
+    assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
+    _chk("glcGridPlanesSegments", _ct().glcGridPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, widths.data_ptr(),
+                                                               planes.data_ptr(), costs.data_ptr(), stream))
     torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
     return planes[:n], costs[:n]
 

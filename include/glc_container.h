@@ -515,6 +515,36 @@ CUDPPResult glcLagPlanesSegments(const void *d_inBase, const unsigned long long 
                                  size_t count, size_t maxLen, const unsigned int *d_lags, unsigned int *d_planes,
                                  unsigned long long *d_costs, void *stream);
 
+/* The grid probe as two batched calls (csrc/grid_probe.hip, csrc/grid_rule.h): which row width of glcGridDeltaShuffleDevice's 2-D
+ * predictor a segment wants at each element size, and what the planes of that filter would cost.  The segments are those of
+ * glcFilterProbeSegments: with L = min(d_lengths[i], maxLen) only the first P = L - L % 8 bytes of segment i are counted.  With
+ * x_e[i] the N = P / e elements of e = 2, 4 or 8 bytes: an element size with N < 1024 has no candidate.  Otherwise
+ * Wmax = min(65536, N / 2), and the sample is 32 tiles of 256 target elements at b_t = Wmax + floor(t (N - Wmax - 256) / 31) --
+ *   glcGridProbeSegments   row i of d_sums is 3 * 65537 32-bit words (GLC_GRID_PROBE_SUMS): at word k * 65537 + W, k = log2 e - 1,
+ *                          S_e[W] = sum over t and j < 256 of bitlen(fold(x_e[b_t + j] - x_e[b_t + j - W])) for W = 2 .. Wmax, the
+ *                          difference modulo 2^(8 e), fold and bitlen those of glcLagProbeSegments, exact; 0xFFFFFFFF at W < 2, at
+ *                          W > Wmax and where there is no candidate.  Row i of d_widths is three words, for e = 2, 4 and 8 the W
+ *                          with the smallest sum, ties to the smallest W, or 0 where there is no candidate.
+ *   glcGridPlanesSegments  row i of d_planes is 14 histograms of 256 words in glcLagPlanesSegments' layout, over the bytes of what
+ *                          glcGridDeltaShuffleDevice(e, w_e, fold = 1) builds from the counted bytes, bands and run heads
+ *                          included, with w_e read from row i of d_widths in device memory; row i of d_costs is three 64-bit words,
+ *                          the cost of glcFilterProbeSegments summed over the planes of e.  A width word outside 2..65536 names no
+ *                          width: its rows are zero, its cost is 2^56 (which the rule never picks), and it is never used as a
+ *                          distance.
+ * The second call takes the first's d_widths without the host between them.  The rule that reads the costs (csrc/grid_rule.h) is
+ * glcLagProbeSegments' walk over thirteen candidates: its ten, then the grid filter at (2, w_2), (4, w_4) and (8, w_8) with the
+ * fold, under the same margin.  The first call costs the same for every segment length: about 1.6e9 (target, width) pairs where
+ * all three element sizes reach Wmax = 65536.  No output need be zeroed by the caller.  Both calls only enqueue on `stream`.  A
+ * bad argument (a null pointer with count > 0, d_sums or d_widths not 4-byte, d_costs not 8-byte or d_planes not 16-byte aligned,
+ * two of a call's arrays equal, a maxLen above GLC_FILTER_PROBE_MAX_LEN or a count above GLC_PROBE_MAX_COUNT) is
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_GRID_PROBE_SUMS (3 * 65537)
+CUDPPResult glcGridProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned int *d_sums, unsigned int *d_widths, void *stream);
+CUDPPResult glcGridPlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_widths, unsigned int *d_planes,
+                                  unsigned long long *d_costs, void *stream);
+
 /* {blocks given to the BWT codec, blocks given to the order-0 codec, frames written} of the plan's last successful container
  * compress, whatever its codec; with GLC_CONTAINER_CODEC_CHOOSE the first two are the rule's choices, counted before the record
  * rule stores a block raw.  {0, 0, 0} before the first. */
@@ -634,20 +664,48 @@ CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, 
  * elements and glcUnlagDeltaUnshuffleRangeDevice with the frame's lag and fold.  The setting is also the version the plan speaks:
  * with it on the plan reads versions 1 to 5, 7, 8, 10 and 13; every other plan, a filter-auto plan included, refuses a version-13
  * stream as a stream-header failure.  A lag word under a version-10 header, and any word outside the family above, is a
- * frame-table failure naming the frame.  The 2-D predictor's width, a lag above 16, the unfolded delta at lag > 1 as a candidate
- * of its own, a choice per block and a sampled probe are not offered. */
+ * frame-table failure naming the frame.  The 2-D predictor's width is glcPlanSetContainerFilterGrid's; a lag above 16, the
+ * unfolded delta at lag > 1 as a candidate of its own and a choice per block are not offered. */
 CUDPPResult glcPlanSetContainerFilterLag(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on);
 
+/* Filter-grid: filter-lag also finds the row width of the 2-D predictor per frame.  on = 1 writes format version 14: version 13
+ * whose frame word may also name glcGridDeltaShuffleDevice's filter.  A frame word with bit 31 clear is version 13's, unchanged; one
+ * with bit 31 set is elem | width << 8 | fold << 30 | 1 << 31 -- format version 12's header word 3 with the fold in bit 30 -- with
+ * elem 2, 4 or 8, width 2..65536 and bits 25..29 zero: that frame went through glcGridDeltaShuffleDevice(elem, width, fold) as one
+ * segment.  (Under version 13 every word with bit 31 set is illegal, so the two families cannot collide.)  The stream header's
+ * triple is (14, 0, 0); kinds, frames, tables, records and trailer are version 13's.  Per frame the writer enqueues the filter
+ * probe, the lag probe and the grid probe (glcGridProbeSegments and glcGridPlanesSegments, the widths staying in device memory
+ * between them), reads thirteen costs, three lags and three widths back with the one wait filter-auto has, and walks the thirteen
+ * candidates of csrc/grid_rule.h: filter-lag's ten in their order, then the grid filter at (2, w_2), (4, w_4) and (8, w_8) with the
+ * fold, under the same margin.  The writer makes only fold = 1 grid words; the reader takes fold 0 as well.  A stream whose every
+ * pick is among the first ten differs from the version-13 stream only in the header's version and its CRC.  A stream that holds
+ * images of different widths, 1-D series and text behind each other gets each frame's own filter (INTEGRATION.md 4b,
+ * "filter-grid: when").  The probe's cost is constant per frame, so small frames pay most.  on = 1 needs filter-lag on: on = 1
+ * without it, and any other value, are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; whatever switches
+ * filter-lag off switches this off.  0 (the default) writes every stream byte for byte as before.  All six container entry points
+ * write the same bytes, with pipelining on or off.  Range reads of a grid frame start at a band of that frame's width
+ * (2048 ceil(width / 64) elements) and use glcUngridDeltaUnshuffleRangeDevice.  The setting is also the version the plan speaks:
+ * with it on the plan reads versions 1 to 5, 7, 8, 10, 13 and 14; every other plan, a filter-lag plan included, refuses a
+ * version-14 stream as a stream-header failure.  A grid word under a version-13 or version-10 header, and any bit-31 word outside
+ * the family above, is a frame-table failure naming the frame.  Widths above 65536, a width per block, the unfolded grid as a
+ * candidate of its own and a 3-D predictor are not offered. */
+CUDPPResult glcPlanSetContainerFilterGrid(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on);
+
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.
- * With filter-auto off every frame counts for the plan's own filter; a frame that took a lag candidate of filter-lag counts in
- * out[7] only.  Zeros before the first. */
+ * With filter-auto off every frame counts for the plan's own filter; a frame that took a lag candidate of filter-lag or a grid
+ * candidate of filter-grid counts in out[7] only.  Zeros before the first. */
 CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8]);
 
 /* Frames of the plan's last successful container compress that took the lag candidate of elem 2, of elem 4 and of elem 8
  * (glcPlanSetContainerFilterLag), and their sum.  Zeros before the first and with the setting off. */
 CUDPPResult glcContainerLastLagFilters(CUDPPHandle plan, unsigned long long out[4]);
+
+/* Frames of the plan's last successful container compress that took the grid candidate of elem 2, of elem 4 and of elem 8
+ * (glcPlanSetContainerFilterGrid), and their sum.  Zeros before the first and with the setting off. */
+CUDPPResult glcContainerLastGridFilters(CUDPPHandle plan, unsigned long long out[4]);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -58,13 +58,15 @@ generated on the host and repeated --, or any typed kind; --rounds R, at least 1
 lag 1 -- the shuffle alone, the plain delta, with --fold the folded delta (format version 11) -- and the 2-D predictor of row width
 W (glcPlanSetContainerDeltaGrid, format version 12), interleaved, with the same output.
 
+--filter-grid (with --grid W [--fold] and the data of the grid section; --rounds R, at least 1) is the filter-grid section: the
+order-0 container under filter-lag, under filter-grid (format version 14) and with elem, W and the fold set by hand (version 12).
 --filter-lag (with --lag L [--fold] and the data of the lag section; --rounds R, at least 1) is the filter-lag section: the order-0
 codec with the auto mode on under filter-auto (format version 10), under filter-auto with lag (glcPlanSetContainerFilterLag, format
 version 13: the lag probe per frame, the lag picked per frame) and under the plan set by hand to the data's element size, lag L and
 the fold (format version 11), interleaved, with the filter-auto section's output and what glcContainerLastLagFilters reports.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
-                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold]]"""
+                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid]]"""
 import argparse
 import json
 import os
@@ -469,17 +471,19 @@ def filter_auto_section(torch, glc, plan, d_in, total, elem, delta, rounds, with
     return res
 
 
-def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
+def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
     """the order-0 container with the auto mode on under "filter_auto" (format version 10), "filter_lag" (format version 13: the
     filter probe and the lag probe per frame, one host wait, the filter and its lag picked per frame) and "hand" (format version 11:
     elem, lag and fold set by hand, no probe), interleaved: `rounds` rounds of one encode and one decode per setting after one
-    untimed round, each timed with device events on the plan's (the default) stream"""
+    untimed round, each timed with device events on the plan's (the default) stream.  With a row width `grid` the settings are
+    "filter_lag", "filter_grid" (format version 14: the grid probe behind the two, the row width found per frame) and "hand"
+    (format version 12: elem, `grid` and fold set by hand)"""
     n = plan.n
     cap = glc.container_bound(total, n)
     cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
     out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
     d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
-    settings = ["filter_auto", "filter_lag", "hand"]
+    settings = ["filter_lag", "filter_grid", "hand"] if grid else ["filter_auto", "filter_lag", "hand"]
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
     glc.container_set_auto(plan, 1)
 
@@ -499,10 +503,14 @@ def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
             if s == "hand":
                 glc.container_set_shuffle(plan, elem)
                 glc.container_set_delta(plan, 1)
-                glc.container_set_delta_lag(plan, lag, fold)
+                if grid:
+                    glc.container_set_delta_grid(plan, grid, fold)
+                else:
+                    glc.container_set_delta_lag(plan, lag, fold)
             else:
                 glc.container_set_filter_auto(plan, 1)
-                glc.container_set_filter_lag(plan, 1 if s == "filter_lag" else 0)
+                glc.container_set_filter_lag(plan, 0 if s == "filter_auto" else 1)
+                glc.container_set_filter_grid(plan, 1 if s == "filter_grid" else 0)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -514,6 +522,7 @@ def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds):
                 res[s]["version"] = int(cont[4].item()) | int(cont[5].item()) << 8
                 res[s]["frames_per_filter"] = list(glc.container_last_filters(plan))
                 res[s]["frames_per_lag_filter"] = list(glc.container_last_lag_filters(plan))
+                res[s]["frames_per_grid_filter"] = list(glc.container_last_grid_filters(plan))
                 continue
             res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
             res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
@@ -604,6 +613,8 @@ def main():
     ap.add_argument("--lag", type=int, default=0, metavar="L", help="the lag section (format version 11): the delta's lag, 1 to 16")
     ap.add_argument("--filter-lag", action="store_true",
                     help="the filter-lag section (format version 13): filter-auto, filter-auto with lag, and elem / --lag / --fold set by hand")
+    ap.add_argument("--filter-grid", action="store_true",
+                    help="the filter-grid section (format version 14): filter-lag, filter-lag with grid, and elem / --grid / --fold set by hand")
     ap.add_argument("--fold", action="store_true", help="the lag or grid section's delta folds its sign")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
     args = ap.parse_args()
@@ -675,6 +686,15 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if args.filter_grid:
+        assert args.grid, "--filter-grid compares with the plan set by hand: give its --grid (and --fold)"
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["filter_grid"] = filter_lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], 1, int(args.fold),
+                                                    max(1, args.rounds), args.grid)
         print(json.dumps(res))
         return
     if args.grid:

@@ -15,7 +15,14 @@ interleaved-channel inputs (adc16x8 and xyz32 of tests/lag_inputs.py, 32 MiB mad
   lag_planes  glcLagPlanesSegments at the winners: a memset of the rows, k_lp_planes, k_lp_cost
 with the winners and the candidate the ten-cost walk picks.
 
-python tools/bench_filter_probe.py [--gib 1] [--rounds 5] [--lag]"""
+--filter-grid (with --lag) adds the grid probe (csrc/grid_probe.hip) in the same way, and three gridded inputs (img16 at row width
+1024, field32 at 1800 and walk32 at 721 of tests/grid_inputs.py, 32 MiB of whole rows made on the host and repeated):
+  grid_sums    glcGridProbeSegments: k_gw_init, the two instances of k_gw_sums, k_gw_argmin
+  grid_planes  glcGridPlanesSegments at the winners: a memset of the rows, the three instances of k_gw_planes, k_lp_cost
+with the widths, the candidate the thirteen-cost walk picks and, because the first call costs the same for every length, both
+calls' medians in milliseconds as well.
+
+python tools/bench_filter_probe.py [--gib 1] [--rounds 5] [--lag [--filter-grid]]"""
 import argparse
 import importlib.util
 import json
@@ -34,7 +41,9 @@ def main():
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--lag", action="store_true", help="also the lag probe, and the interleaved-channel inputs")
+    ap.add_argument("--filter-grid", action="store_true", help="also the grid probe, and the gridded inputs (needs --lag)")
     args = ap.parse_args()
+    assert args.lag or not args.filter_grid, "--filter-grid adds to --lag"
     import torch
     spec = importlib.util.spec_from_file_location("glc_binding", os.path.join(ROOT, "gpu-lossless-compression_amd", "glc_binding.py"))
     glc = importlib.util.module_from_spec(spec)
@@ -56,6 +65,11 @@ def main():
     lp_lags = torch.empty((1, 3), dtype=torch.int32, device=dev)
     lp_planes = torch.empty((1, 14, 256), dtype=torch.int32, device=dev)
     lp_costs = torch.empty((1, 3), dtype=torch.int64, device=dev)
+    gw_sums = torch.empty((1, glc.GRID_PROBE_SUMS), dtype=torch.int32, device=dev)
+    gw_widths = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    gw_planes = torch.empty((1, 14, 256), dtype=torch.int32, device=dev)
+    gw_costs = torch.empty((1, 3), dtype=torch.int64, device=dev)
+    GRIDS = {"img16": 1024, "field32": 1800, "walk32": 721}
     L = glc._ct()
 
     def timed(fn):
@@ -67,7 +81,7 @@ def main():
         torch.cuda.synchronize()
         return a.elapsed_time(b) * 1e-3
 
-    for name in ("zeros", "ts64", "float32", "noise") + (("adc16x8", "xyz32") if args.lag else ()):
+    for name in ("zeros", "ts64", "float32", "noise") + (("adc16x8", "xyz32") if args.lag else ()) + (tuple(GRIDS) if args.filter_grid else ()):
         if name == "zeros":
             d_in = torch.zeros(total, dtype=torch.uint8, device=dev)
         elif name == "ts64":
@@ -76,6 +90,12 @@ def main():
             import lag_inputs
             import numpy as np
             piece = torch.from_numpy(np.array(lag_inputs.lag_bytes(name, min(total, 32 * MiB)), copy=True)).to(dev)
+            d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
+        elif name in GRIDS:
+            import grid_inputs
+            import numpy as np
+            row = GRIDS[name] * grid_inputs.KINDS[name]
+            piece = torch.from_numpy(grid_inputs.grid_bytes(name, max(row, min(total, 32 * MiB) // row * row), GRIDS[name])).to(dev)
             d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
         elif name == "float32":
             d_in = torch.randn(total // 4, dtype=torch.float32, device=dev, generator=g).view(torch.uint8)
@@ -101,8 +121,17 @@ def main():
             glc._chk("glcLagPlanesSegments", L.glcLagPlanesSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total, lp_lags.data_ptr(),
                                                                      lp_planes.data_ptr(), lp_costs.data_ptr(), None))
 
+        def grid_sums():
+            glc._chk("glcGridProbeSegments", L.glcGridProbeSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total,
+                                                                     gw_sums.data_ptr(), gw_widths.data_ptr(), None))
+
+        def grid_planes():
+            glc._chk("glcGridPlanesSegments", L.glcGridPlanesSegments(d_in.data_ptr(), off1.data_ptr(), ln1.data_ptr(), 1, total, gw_widths.data_ptr(),
+                                                                       gw_planes.data_ptr(), gw_costs.data_ptr(), None))
+
         calls = (("frame_GBps", frame), ("blocks_GBps", blocks), ("copy_GBps", copy)) + \
-                ((("lag_sums_GBps", lag_sums), ("lag_planes_GBps", lag_planes)) if args.lag else ())
+                ((("lag_sums_GBps", lag_sums), ("lag_planes_GBps", lag_planes)) if args.lag else ()) + \
+                ((("grid_sums_GBps", grid_sums), ("grid_planes_GBps", grid_planes)) if args.filter_grid else ())
         res = {k: [] for k, _ in calls}
         for r in range(args.rounds + 1):                        # round 0 is the warm-up
             for k, fn in calls:
@@ -121,9 +150,17 @@ def main():
             c10 = c + [int(v) for v in lp_costs[0].cpu().tolist()]
             assert int(lp_planes.sum(dtype=torch.int64).item()) == 3 * total
             rep.update({"lags": lags, "lag_costs_bytes": [v // 2048 for v in c10[7:]], "lag_pick": list(FL.cands(lags)[FL.pick(c10)])})
+        if args.filter_grid:
+            import filter_grid_model as Q
+            widths = [int(v) for v in gw_widths[0].cpu().tolist()]
+            c13 = c10 + [int(v) for v in gw_costs[0].cpu().tolist()]
+            assert int(gw_planes.sum(dtype=torch.int64).item()) == sum(total // 8 * 8 for w in widths if w)
+            rep.update({"widths": widths, "grid_costs_bytes": [v // 2048 for v in c13[10:]], "grid_pick": list(Q.cands(lags, widths)[Q.pick(c13)])})
         for k, v in res.items():
             s = sorted(v)
             rep[k], rep[k + "_median"], rep[k + "_spread"] = v, s[len(s) // 2], round(s[-1] - s[0], 2)
+            if k.startswith("grid_"):
+                rep[k[:-4] + "ms_median"] = round(total / (s[len(s) // 2] * 1e9) * 1e3, 4)
         print(json.dumps(rep))
         del d_in
 
