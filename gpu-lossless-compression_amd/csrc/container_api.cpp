@@ -5,7 +5,8 @@
 // Format.  A stream is a header, frames and a trailer.  Its header's triple (version, flags, elem) is a CtFormat, and a format says
 // two things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, the fused delta + shuffle of delta.hip, under version 11 that delta with the flags' lag and fold, lag.hip,
-// or under version 12 the 2-D predictor of grid.hip with the row width of the header's word 3),
+// under version 12 the 2-D predictor of grid.hip with the row width of the header's word 3, or under version 15 the byte predictor
+// of byte_delta.hip with the flags' lag and word 3's row stride),
 // and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always; 2 order-0 Huffman, 3 its sparse form (sparse.hip), 4 the BWT codec's zero-run form (zrun.hip), 5 the order-0
 // codec's rANS form (ans.hip) and 6 its dedup form (dedup.hip) where kind2_legal() .. kind6_legal() say so).  ct_legal() is the
@@ -1272,7 +1273,7 @@ CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &i
     const CUDPPResult r = walk_result(plan, end, stopped);
     if (r != CUDPP_SUCCESS) return r;
     ix->fmt = CtFormat();
-    (void)parse_header_format(ix->hdr, &ix->fmt);
+    (void)parse_container_format(ix->hdr, &ix->fmt);
     ix->block_len = ix->hdr[2];
     ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
     *index = ix.release();
@@ -1378,7 +1379,7 @@ std::vector<uint8_t> needed_blocks(const CtFormat &fmt, uint32_t nb, uint32_t bl
     const unsigned long long e = fmt.elem, q = F / e;
     const unsigned long long lo = a / e, hi = std::min(q, (b + e - 1) / e);
     if (lo < hi) {                                              // (a range inside the len % elem tail needs no element)
-        *i0 = fmt.grid() ? lo - lo % ct_grid_period(fmt.width) : fmt.delta() ? lo & ~2047ull : lo;   // (the band's, the run's start)
+        *i0 = fmt.bytes() ? lo - lo % ct_byte_step(fmt.width) : fmt.grid() ? lo - lo % ct_grid_period(fmt.width) : fmt.delta() ? lo & ~2047ull : lo;   // (the band's, the run's start)
         *i1 = hi;
         for (unsigned long long j = 0; j < e; j++) mark(j * q + *i0, j * q + *i1);
     }
@@ -1442,7 +1443,8 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
         if (i0 < i1) {                                          // elements [i0, i1) into the second staging, [a, min(b, q e)) out of them
             uint8_t *el = nullptr;
             CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
-            if (ff.grid()) CT_TRY(ungrid_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.width, ff.fold(), i0, i1 - i0));
+            if (ff.bytes()) CT_TRY(unbyte_delta_range_device(D.P.st, stage, el, q, ff.lag(), ff.width, i0, i1 - i0));
+            else if (ff.grid()) CT_TRY(ungrid_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.width, ff.fold(), i0, i1 - i0));
             else if (ff.delta()) CT_TRY(unlag_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.lag(), ff.fold(), i0, i1 - i0));
             else CT_TRY(unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
             const unsigned long long top = std::min(b, q * e);
@@ -1822,6 +1824,18 @@ CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, 
     if (!fold) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const CUDPPResult r = ct_get(plan, width, [](const CtSettings &s) { return s.grid_width; });
     return r != CUDPP_SUCCESS ? r : ct_get(plan, fold, [](const CtSettings &s) { return s.grid_fold; });
+}
+
+CUDPPResult glcPlanSetContainerByteDelta(CUDPPHandle plan, unsigned int lag, unsigned int stride)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_byte_delta(lag, stride); });
+}
+
+CUDPPResult glcPlanGetContainerByteDelta(CUDPPHandle plan, unsigned int *lag, unsigned int *stride)
+{
+    if (!stride) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const CUDPPResult r = ct_get(plan, lag, [](const CtSettings &s) { return s.byte_lag; });
+    return r != CUDPP_SUCCESS ? r : ct_get(plan, stride, [](const CtSettings &s) { return s.byte_stride; });
 }
 
 } // extern "C"

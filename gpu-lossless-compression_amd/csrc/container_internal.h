@@ -110,6 +110,13 @@ hipError_t grid_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, 
                                uint32_t fold, bool inverse);
 hipError_t ungrid_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
                                          uint32_t width, uint32_t fold, unsigned long long first, unsigned long long count);
+// the byte predictor and its inverses (byte_delta.hip): one-byte elements, the predecessor `lag` bytes back (1..16) over the
+// differences to the byte `stride` back (0 = none, else 2..65536: the row above) within bands of ct_grid_period(stride) bytes; no
+// planes, no fold: out has the length and the positions of in.  The range form gives bytes [first, first + count) of the inverse of
+// the len bytes at `in`; `first` a multiple of ct_byte_step(stride)
+hipError_t byte_delta_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t lag, uint32_t stride, bool inverse);
+hipError_t unbyte_delta_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t lag, uint32_t stride,
+                                     unsigned long long first, unsigned long long count);
 
 // Carves typed arrays out of one allocation.  The same sequence of calls runs twice: on a null base it measures (bytes()), on
 // the allocation it places, so the size and the pointers cannot disagree.
@@ -261,18 +268,34 @@ constexpr uint32_t CT_VERSION_FILTER_LAG = 13;
 // such word is illegal, so the two families cannot collide.  The stream header's triple is (14, 0, 0)
 constexpr uint32_t CT_VERSION_FILTER_GRID = 14;
 constexpr uint32_t CT_WORD_GRID = 1u << 31, CT_WORD_GRID_FOLD = 1u << 30, CT_WORD_GRID_WIDTH = 0x1FFFFu << CT_WIDTH_SHIFT;
-constexpr uint32_t CT_VERSION_MAX = CT_VERSION_FILTER_GRID;
+// 15: version 8's stream (its kinds, frame word 0) behind the byte predictor of byte_delta.hip, for one-byte elements: flags
+// 1 | (stride ? 4 : 0) | (lag - 1) << 8 (no fold bit: the fold permutes byte values) and the header's word 3 1 | stride << 8 with
+// the row stride 0 (none) or 2..65536 bytes.  (lag 1, stride 0) is legal here: no older version can say it of bytes
+constexpr uint32_t CT_VERSION_BYTE = 15;
+constexpr uint32_t CT_BYTE_MAX_LAG = 16;
+__host__ __device__ inline bool ct_byte_lag_ok(uint32_t lag) { return lag >= 1 && lag <= CT_BYTE_MAX_LAG; }
+__host__ __device__ inline bool ct_byte_stride_ok(uint32_t stride) { return stride == 0 || ct_grid_width_ok(stride); }
+// what a range read of the byte predictor's inverse starts at a multiple of: the run, with a stride the band
+__host__ __device__ inline uint32_t ct_byte_step(uint32_t stride) { return stride ? ct_grid_period(stride) : 2048u; }
+__host__ __device__ inline bool ct_byte_legal(uint32_t flags, uint32_t word3)
+{
+    const uint32_t stride = word3 >> CT_WIDTH_SHIFT;
+    return (word3 & 0xFFu) == 1 && ct_byte_stride_ok(stride) && (flags & CT_FLAG_DELTA) && !(flags & ~(CT_FLAG_DELTA | CT_FLAG_GRID | CT_LAG_MASK)) &&
+           ((flags & CT_FLAG_GRID) != 0) == (stride != 0);
+}
+constexpr uint32_t CT_VERSION_MAX = CT_VERSION_BYTE;
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
 // its filter-auto setting version 10, its delta-lag setting version 11, its grid setting version 12, its filter-lag setting
-// version 13 and its filter-grid setting version 14 (each is only ever on with the auto mode, so that mode's bits come with it;
-// filter-lag only with filter-auto, filter-grid only with filter-lag)
+// version 13, its filter-grid setting version 14 and its byte-delta setting version 15 (each is only ever on with the auto mode, so
+// that mode's bits come with it; filter-lag only with filter-auto, filter-grid only with filter-lag)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
 constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128, CT_READS_FILTER_LAG = 256, CT_READS_FILTER_GRID = 512;
+constexpr uint32_t CT_READS_BYTE = 1024;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
-    constexpr uint32_t K[CT_VERSION_MAX + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F, 0x2F, 0x2F, 0x2F};
+    constexpr uint32_t K[CT_VERSION_MAX + 1] = {0, 0x03, 0x03, 0x07, 0x07, 0x0F, 0x17, 0x27, 0x2F, 0x47, 0x2F, 0x2F, 0x2F, 0x2F, 0x2F, 0x2F};
     return version <= CT_VERSION_MAX ? K[version] : 0u;
 }
 // A stream's format is its header's triple.  It says the two things that differ between streams: the filter a frame's bytes
@@ -286,7 +309,9 @@ struct CtFormat {
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     // the delta's lag and fold: (1, 0) below version 11; under version 13 a FRAME's format (ct_frame_format) carries them
     __host__ __device__ bool frame_filters() const { return version == CT_VERSION_FILTER || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID; }
-    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID; }
+    // the byte predictor: version 15's streams; elem is 1, `width` the row stride in bytes (0 = none), the lag in the flags
+    __host__ __device__ bool bytes() const { return version == CT_VERSION_BYTE; }
+    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID || bytes(); }
     __host__ __device__ uint32_t lag() const { return lag_flags() ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
     __host__ __device__ uint32_t fold() const { return (lag_flags() || version == CT_VERSION_GRID) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
     // the 2-D predictor: version 12's streams, and under version 14 the format of a frame whose word names it
@@ -306,7 +331,8 @@ struct CtFormat {
                version == CT_VERSION_ANS ? CT_READS_ANS : version == CT_VERSION_AUTO ? CT_READS_AUTO :
                version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
                version == CT_VERSION_LAG ? CT_READS_LAG : version == CT_VERSION_GRID ? CT_READS_GRID :
-               version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : version == CT_VERSION_FILTER_GRID ? CT_READS_FILTER_GRID : 0u;
+               version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : version == CT_VERSION_FILTER_GRID ? CT_READS_FILTER_GRID :
+               version == CT_VERSION_BYTE ? CT_READS_BYTE : 0u;
     }
 };
 // a frame header's word 3.  Versions 1 to 9, 11 and 12 keep it 0; under versions 10, 13 and 14 it is the frame's filter.  ct_frame_word_legal() is the
@@ -346,6 +372,7 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
 // a format's filter over one segment, or its inverse
 inline hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
 {
+    if (f.bytes()) return byte_delta_device(st, in, out, len, f.lag(), f.width, inverse);
     if (f.grid()) return grid_shuffle_device(st, in, out, len, f.elem, f.width, f.fold(), inverse);
     if (f.delta()) return lag_shuffle_device(st, in, out, len, f.elem, f.lag(), f.fold(), inverse);   // ((1, 0): delta.hip's kernels)
     return shuffle_device(st, in, out, len, f.elem, inverse);
@@ -461,11 +488,22 @@ __host__ __device__ inline bool parse_header_format(const uint32_t h[8], CtForma
     return f->version == CT_VERSION_FILTER_GRID && f->flags == 0 && f->elem == 0 && f->width == 0;
 }
 
+// version 15's family beside it, accepted the way 13 and 14 were: parse_header_format() is pinned up to version 16 by
+// tools/filter_grid_rule_check.cpp, so this is the function the readers call; tools/byte_format_check.cpp pins it.  Word 3 is
+// split as under version 12: the element size 1 below the row stride
+__host__ __device__ inline bool parse_container_format(const uint32_t h[8], CtFormat *f)
+{
+    if (parse_header_format(h, f)) return true;
+    if (f->version != CT_VERSION_BYTE || !ct_byte_legal(f->flags, h[3])) return false;
+    f->elem = 1; f->width = h[3] >> CT_WIDTH_SHIFT;
+    return true;
+}
+
 // the checks on a stream header; false = refused
 __host__ __device__ inline bool check_stream_header(const CrcTables &C, const uint32_t h[8], CtFormat *fmt, uint32_t *block_len,
                                                     unsigned long long *total)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_header_format(h, fmt)) return false;
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_container_format(h, fmt)) return false;
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
     *block_len = h[2];
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
@@ -594,13 +632,26 @@ struct CtSettings {
     // them puts it back to off
     uint32_t grid_width = 0, grid_fold = 0;
     bool grid_on() const { return grid_width != 0; }
+    // byte-delta: every frame goes through the byte predictor at (byte_lag, byte_stride) (byte_delta.hip; the writer writes
+    // version 15); byte_lag 0 = off.  Only ever on with the order-0 codec, the auto mode on, the shuffle off and filter-auto off;
+    // a codec or mode change that ends one of them switches it off, and while it is on the shuffle and filter-auto are refused
+    uint32_t byte_lag = 0, byte_stride = 0;
+    bool byte_on() const { return byte_lag != 0; }
+    bool byte_fits() const { return codec == CT_CODEC_HUFF0 && mode == CT_MODE_AUTO && !shuffle && !filter_auto; }
     void lag_keep()
     {
         if (!lag_fits()) { lag = 1; fold = 0; grid_width = 0; grid_fold = 0; }
+        if (!byte_fits()) { byte_lag = 0; byte_stride = 0; }
+    }
+    bool set_byte_delta(uint32_t l, uint32_t s)
+    {
+        if (l && (!ct_byte_lag_ok(l) || !ct_byte_stride_ok(s) || !byte_fits())) return false;
+        byte_lag = l; byte_stride = l ? s : 0;
+        return true;
     }
     bool set_shuffle(uint32_t elem)
     {
-        if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE || filter_auto)) return false;
+        if (elem > 1 && (!shuffle_elem_ok(elem) || codec == CT_CODEC_CHOOSE || filter_auto || byte_on())) return false;
         shuffle = elem > 1 ? elem : 0;
         if (elem <= 1) delta = false;                         // (no delta without the shuffle)
         lag_keep();
@@ -647,7 +698,7 @@ struct CtSettings {
     }
     bool set_filter_auto(uint32_t on)
     {
-        if (on > 1 || (on && (codec != CT_CODEC_HUFF0 || mode != CT_MODE_AUTO || shuffle))) return false;
+        if (on > 1 || (on && (codec != CT_CODEC_HUFF0 || mode != CT_MODE_AUTO || shuffle || byte_on()))) return false;
         filter_auto = on != 0;
         filter_keep();
         lag_keep();                                           // (it needs the shuffle off and the lag needs it on: already (1, 0))
@@ -671,7 +722,7 @@ struct CtSettings {
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
                mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) |
-                                      (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) :
+                                      (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) | (byte_on() ? CT_READS_BYTE : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
@@ -689,6 +740,12 @@ inline CtFormat format_of(const CtSettings &s)
 {
     CtFormat f;
     if (s.filter_auto) { f.version = s.filter_grid ? CT_VERSION_FILTER_GRID : s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
+    if (s.byte_on()) {
+        f.version = CT_VERSION_BYTE;
+        f.flags = CT_FLAG_DELTA | (s.byte_stride ? CT_FLAG_GRID : 0u) | (s.byte_lag - 1) << CT_LAG_SHIFT;
+        f.elem = 1; f.width = s.byte_stride;
+        return f;
+    }
     f.elem = s.shuffle;
     f.flags = s.shuffle && s.delta ? CT_FLAG_DELTA : 0;
     if (s.lag_on()) {                                         // (what (1, 0) does, version 8 says)

@@ -153,6 +153,40 @@ CUDPPResult glcUngridDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, un
     return range_filter_api(d_in, d_out, len, elem, first, count, stream, true, 1, fold, &width);
 }
 
+// the byte predictor's three calls (byte_delta.hip): glcDeltaShuffleDevice's rules over one-byte elements
+static CUDPPResult byte_delta_api(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride, void *stream,
+                                  bool inverse)
+{
+    if (!ct_byte_lag_ok(lag) || !ct_byte_stride_ok(stride)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (len == 0) return CUDPP_SUCCESS;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (a < b ? b - a : a - b) < len) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_result(byte_delta_device(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out),
+                                     len, lag, stride, inverse));
+}
+
+CUDPPResult glcByteDeltaDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride, void *stream)
+{
+    return byte_delta_api(d_in, d_out, len, lag, stride, stream, false);
+}
+
+CUDPPResult glcUnbyteDeltaDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride, void *stream)
+{
+    return byte_delta_api(d_in, d_out, len, lag, stride, stream, true);
+}
+
+CUDPPResult glcUnbyteDeltaRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride,
+                                      unsigned long long first, unsigned long long count, void *stream)
+{
+    if (!ct_byte_lag_ok(lag) || !ct_byte_stride_ok(stride)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (first > len || count > len - first || first % ct_byte_step(stride)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
+    if (!d_in || !d_out || (a < b + count && b < a + len)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    return hip_result(unbyte_delta_range_device(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_in),
+                                             static_cast<uint8_t *>(d_out), len, lag, stride, first, count));
+}
+
 // the two sparse calls: a bad argument is refused before anything is enqueued
 static bool sparse_args_ok(const void *a, const void *b, const void *c, const void *d, const void *e, const void *f, size_t count, size_t maxLen)
 {

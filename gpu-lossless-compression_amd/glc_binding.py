@@ -724,6 +724,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerFilterLag", "glcPlanGetContainerFilterLag", "glcContainerLastLagFilters",
                      "glcGridProbeSegments", "glcGridPlanesSegments",
                      "glcPlanSetContainerFilterGrid", "glcPlanGetContainerFilterGrid", "glcContainerLastGridFilters",
+                     "glcByteDeltaDevice", "glcUnbyteDeltaDevice", "glcUnbyteDeltaRangeDevice",
+                     "glcPlanSetContainerByteDelta", "glcPlanGetContainerByteDelta",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -782,6 +784,11 @@ def _ct():
         for nm in ("glcGridDeltaShuffleDevice", "glcUngridDeltaUnshuffleDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, vp]
         L.glcUngridDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
+        L.glcPlanSetContainerByteDelta.argtypes = [sz, C.c_uint, C.c_uint]
+        L.glcPlanGetContainerByteDelta.argtypes = [sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+        for nm in ("glcByteDeltaDevice", "glcUnbyteDeltaDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, vp]
+        L.glcUnbyteDeltaRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, ull, ull, vp]
         for nm in CONTAINER_SYMBOLS[1:-1]:
             getattr(L, nm).restype = C.c_int
         L.glcContainerIndexFree.restype = None
@@ -1042,6 +1049,21 @@ def container_get_delta_grid(plan):
     width, fold = C.c_uint(0), C.c_uint(0)
     _chk("glcPlanGetContainerDeltaGrid", _ct().glcPlanGetContainerDeltaGrid(plan.handle, C.byref(width), C.byref(fold)))
     return int(width.value), int(fold.value)
+
+
+def container_set_byte_delta(plan, lag, stride):
+    """the lag and row stride of the byte predictor of the plan's container ENCODER (format version 15, for 8-bit sample data: the
+    predecessor `lag` bytes back, 1 to 16, the channel count, over the differences to the byte `stride` back, 0 for none or 2 to
+    65536, the row length in bytes); lag 0 is off.  On needs the order-0 codec, the auto mode on, the shuffle off and filter-auto
+    off; while it is on the shuffle and filter-auto are refused, and a codec change or the auto mode going off switches it off.  It
+    is also the version the plan reads: on, versions 1 to 5, 7, 8 and 15; off, a version-15 stream is a stream-header failure."""
+    _chk("glcPlanSetContainerByteDelta", _ct().glcPlanSetContainerByteDelta(plan.handle, int(lag), int(stride)))
+
+
+def container_get_byte_delta(plan):
+    lag, stride = C.c_uint(0), C.c_uint(0)
+    _chk("glcPlanGetContainerByteDelta", _ct().glcPlanGetContainerByteDelta(plan.handle, C.byref(lag), C.byref(stride)))
+    return int(lag.value), int(stride.value)
 
 
 def container_last_filters(plan):
@@ -1456,6 +1478,31 @@ def ungrid_delta_unshuffle(d_in, elem, width, fold, out=None, stream=None):
     return _lag_shuffle("glcUngridDeltaUnshuffleDevice", d_in, elem, width, fold, out, stream)
 
 
+def _byte_delta(fn, d_in, lag, stride, out, stream):
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(lag), int(stride),
+                                stream))
+    return out
+
+
+def byte_delta(d_in, lag, stride, out=None, stream=None):
+    """the byte predictor over a device uint8 tensor of 8-bit samples: every byte minus the byte `lag` back (1 to 16, the channel
+    count; restarting every 2048 bytes), taken over the differences to the byte `stride` back (0 for none, or 2 to 65536, the row
+    length in bytes) within bands of 2048 * ceil(stride / 64) bytes; modulo 256, same length and positions.  Into `out` (same
+    size, not overlapping) or a new tensor"""
+    return _byte_delta("glcByteDeltaDevice", d_in, lag, stride, out, stream)
+
+
+def unbyte_delta(d_in, lag, stride, out=None, stream=None):
+    """the inverse of byte_delta"""
+    return _byte_delta("glcUnbyteDeltaDevice", d_in, lag, stride, out, stream)
+
+
 def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):
     """shuffle (or unshuffle) the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in into the same ranges of d_out"""
     import torch
@@ -1634,4 +1681,18 @@ def ungrid_delta_unshuffle_range(d_in, elem, width, fold, first, count, out=None
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
     _chk("glcUngridDeltaUnshuffleRangeDevice", _ct().glcUngridDeltaUnshuffleRangeDevice(
         x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(fold), int(first), int(count), stream))
+    return out
+
+
+def unbyte_delta_range(d_in, lag, stride, first, count, out=None, stream=None):
+    """bytes [first, first + count) of unbyte_delta(d_in, lag, stride); first a multiple of 2048 at stride 0 and of the period,
+    2048 * ceil(stride / 64), otherwise"""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(int(count), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count)
+    _chk("glcUnbyteDeltaRangeDevice", _ct().glcUnbyteDeltaRangeDevice(
+        x.data_ptr(), out.data_ptr(), x.numel(), int(lag), int(stride), int(first), int(count), stream))
     return out

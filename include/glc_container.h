@@ -208,6 +208,21 @@ CUDPPResult glcUngridDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, un
                                                unsigned int width, unsigned int fold, unsigned long long first,
                                                unsigned long long count, void *stream);
 
+/* The byte predictor (csrc/byte_delta.hip), for 8-bit sample data -- greyscale, RGB and RGBA images, masks and label maps, 8-bit
+ * depth or detector frames, u8 audio: one-byte elements, so there are no planes, no tail and no fold, and out has the length and the
+ * positions of in.  With arithmetic modulo 256, `lag` 1..16 (the channel count), `stride` 0 (none) or 2..65536 (the row length in
+ * bytes, channels * width) and P = 2048 * ceil(stride / 64): v[i] = x[i] where stride == 0 or i mod P < stride and
+ * x[i] - x[i - stride] elsewhere; out[i] = v[i] where i mod 2048 < lag and v[i] - v[i - lag] elsewhere.  The rule is linear in i: a
+ * segment needs no row alignment.  The inverse sums down every chain (i, i - lag, ...) of a run of 2048 and then adds the row above
+ * up every band of P bytes.  The rules of glcDeltaShuffleDevice: any length and alignment, out of place, overlapping buffers
+ * refused, len 0 succeeds; a lag outside 1..16 and a stride of 1 or above 65536 are CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing
+ * written.  The range form writes bytes [first, first + count) of glcUnbyteDeltaDevice's output to d_out[0 .. count): first a
+ * multiple of 2048 with stride 0 and of P otherwise, first + count <= len. */
+CUDPPResult glcByteDeltaDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride, void *stream);
+CUDPPResult glcUnbyteDeltaDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride, void *stream);
+CUDPPResult glcUnbyteDeltaRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride,
+                                      unsigned long long first, unsigned long long count, void *stream);
+
 /* The two passes of the sparse mode as batched calls (csrc/sparse.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of
  * its base, cut into chunks of 64 bytes (the last may be short); d_fill[i] & 255 is its fill byte, given by the caller; its mask is
  * row i of d_mask, rows of ceil(ceil(maxLen / 64) / 32) words: bit c % 32 of word c / 32 is 1 when chunk c is kept, 0 when every
@@ -692,6 +707,18 @@ CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on);
  * candidate of its own and a 3-D predictor are not offered. */
 CUDPPResult glcPlanSetContainerFilterGrid(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on);
+
+/* The lag and row stride of the ENCODER's byte predictor (glcByteDeltaDevice); lag 0 = off, the default.  On needs the order-0
+ * codec, the auto mode on, the shuffle off (hence the delta, the delta-lag and the grid settings off) and filter-auto off; any other
+ * state, a lag above 16 and a stride of 1 or above 65536 are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.
+ * While it is on, glcPlanSetContainerShuffle with 2, 4 or 8 and glcPlanSetContainerFilterAuto(plan, 1) are refused; a codec change
+ * or switching the auto mode off switches it off.  The stream is format version 15: version 8's frames, the header's flags
+ * 1 | (stride ? 4 : 0) | (lag - 1) << 8 and its word 3 1 | stride << 8.  Decode, index and range reads take lag and stride from the
+ * stream header, never from the plan; a range read decodes from the run (stride 0) or the band that holds its first byte.  The
+ * setting is also the version the plan speaks: with it on the plan reads versions 1 to 5, 7, 8 and 15; every other plan refuses a
+ * version-15 stream as a stream-header failure.  With it off every stream is written as before. */
+CUDPPResult glcPlanSetContainerByteDelta(CUDPPHandle plan, unsigned int lag, unsigned int stride);
+CUDPPResult glcPlanGetContainerByteDelta(CUDPPHandle plan, unsigned int *lag, unsigned int *stride);
 
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.

@@ -64,9 +64,16 @@ order-0 container under filter-lag, under filter-grid (format version 14) and wi
 codec with the auto mode on under filter-auto (format version 10), under filter-auto with lag (glcPlanSetContainerFilterLag, format
 version 13: the lag probe per frame, the lag picked per frame) and under the plan set by hand to the data's element size, lag L and
 the fold (format version 11), interleaved, with the filter-auto section's output and what glcContainerLastLagFilters reports.
+
+--byte-delta LAG,STRIDE (with --data grey8 or rgb8 of tests/byte_delta_inputs.py -- about 32 MiB of whole rows of STRIDE bytes
+generated on the host and repeated; STRIDE 0: rows of 721 pixels --, or any other kind; --rounds R, at least 1) is the byte section:
+the order-0 codec with the auto mode on and no filter (format version 8) and with the byte predictor at (LAG, STRIDE)
+(glcPlanSetContainerByteDelta, format version 15), interleaved, with the same output as the lag section; LAG 0 runs the first only,
+which is also what a build without the setting can run.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
-                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid]]"""
+                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid] |
+                                 --byte-delta LAG,STRIDE]"""
 import argparse
 import json
 import os
@@ -78,7 +85,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
 DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0,
-             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4, "img16": 2, "field32": 4, "walk32": 4}
+             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4, "img16": 2, "field32": 4, "walk32": 4, "grey8": 0, "rgb8": 0}
 LAG_PIECE = 32 * MiB                                           # what tests/lag_inputs.py generates on the host; repeated on the device
 
 
@@ -589,6 +596,53 @@ def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
     return res
 
 
+def byte_section(torch, glc, plan, d_in, total, lag, stride, rounds):
+    """the order-0 container with the auto mode on under "off" (no filter, format version 8) and, unless lag is 0, "on" (the byte
+    predictor at (lag, stride), format version 15), interleaved: `rounds` rounds of one encode and one decode per setting after one
+    untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["off"] + (["on"] if lag else [])
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+    glc.container_set_auto(plan, 1)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            if lag:
+                glc.container_set_byte_delta(plan, lag if s == "on" else 0, stride)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["version"] = int(cont[4].item()) | int(cont[5].item()) << 8
+                res[s]["container_crc32"] = zlib.crc32(cont[:clen].cpu().numpy().tobytes())
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -617,7 +671,11 @@ def main():
                     help="the filter-grid section (format version 14): filter-lag, filter-lag with grid, and elem / --grid / --fold set by hand")
     ap.add_argument("--fold", action="store_true", help="the lag or grid section's delta folds its sign")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
+    ap.add_argument("--byte-delta", default=None, metavar="LAG,STRIDE",
+                    help="the byte section (format version 15): the byte predictor's lag, 0 (off only) to 16, and row stride, 0 or 2 to 65536")
     args = ap.parse_args()
+    byte_delta = tuple(int(v) for v in args.byte_delta.split(",")) if args.byte_delta else None
+    assert byte_delta is None or len(byte_delta) == 2, "--byte-delta LAG,STRIDE"
     import importlib.util
     import numpy as np
     import torch
@@ -645,6 +703,15 @@ def main():
         assert args.grid, "the grids are the grid section's"
         row = args.grid * grid_inputs.KINDS[args.data]
         piece = torch.from_numpy(grid_inputs.grid_bytes(args.data, max(row, min(total, LAG_PIECE) // row * row), args.grid)).to(dev)      # whole rows
+        d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
+    elif args.data in ("grey8", "rgb8"):
+        import byte_delta_inputs
+        assert byte_delta, "the 8-bit images are the byte section's"
+        ch = 3 if args.data == "rgb8" else 1
+        row = byte_delta[1] or 721 * ch
+        assert row % ch == 0, "a row of whole pixels"
+        gen = byte_delta_inputs.rgb8 if ch == 3 else byte_delta_inputs.grey8
+        piece = torch.from_numpy(gen(max(row, min(total, LAG_PIECE) // row * row), row // ch)).to(dev)      # whole rows
         d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
     elif args.data in ("zipf", "mix"):
         d_in = torch.empty(total, dtype=torch.uint8, device=dev)
@@ -686,6 +753,13 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if byte_delta:
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["byte_delta"] = byte_section(torch, glc, plan, d_in, total, byte_delta[0], byte_delta[1], max(1, args.rounds))
         print(json.dumps(res))
         return
     if args.filter_grid:

@@ -11,13 +11,17 @@
              glcGridDeltaShuffleDevice / glcUngridDeltaUnshuffleDevice (csrc/grid.hip) at row width W beside the lag kernels at
              (1, 1), which the grid's expectations are stated against; k_grid_vsum takes its 16-byte path when W * N and the
              destination's address (--offset) are multiples of 16, else its element path
+  byte L,S / unbyte L,S   (with --bytes)
+             glcByteDeltaDevice / glcUnbyteDeltaDevice (csrc/byte_delta.hip) at (lag, stride) = (1, 0), (3, 0), (1, 4096) and (3, 1281),
+             beside the kernels they are stated against on the same byte count: lag 3 2 / unlag 3 2 and grid 1281 2 / ungrid 1281 2
+             (the lag and grid kernels at elem 2, no fold)
 
 Every variant runs once per round, rounds repeat (--reps, after --warmup rounds); each run is bracketed by device events.  The
 table gives the median, the fastest and the slowest run of every variant, as GB/s of input bytes (the traffic is twice that)
 and relative to the copy's median.  The buffer (--gib, default 1) is larger than the 256 MiB Infinity Cache on purpose.
 --offset A B misaligns source and destination by A and B bytes.  One JSON line on stdout, the table on stderr or in --md FILE.
 
-python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--grid W] [--md FILE]"""
+python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--grid W] [--bytes] [--md FILE]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -46,6 +50,7 @@ def main():
     ap.add_argument("--offset", type=int, nargs=2, default=[0, 0])
     ap.add_argument("--lag", action="store_true", help="the lagged, folded delta kernels beside the others")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the 2-D predictor's kernels at row width W beside the lag kernels at (1, 1)")
+    ap.add_argument("--bytes", action="store_true", help="the byte predictor's kernels beside the lag and grid kernels at elem 2")
     ap.add_argument("--md", default=None)
     args = ap.parse_args()
     assert args.reps >= 20, "at least 20 timed repetitions"
@@ -104,6 +109,22 @@ def main():
             lagged(L.glcGridDeltaShuffleDevice, elem, args.grid, 1)()
             glc._chk("ungrid", L.glcUngridDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, args.grid, 1, None))
             assert torch.equal(back, src), (elem, args.grid)
+        del back
+    if args.bytes:
+        def byted(fn, lag, stride):
+            return lambda: glc._chk("byte", fn(src.data_ptr(), dst.data_ptr(), n, lag, stride, None))
+
+        back = torch.empty_like(src)                           # what is timed inverts itself
+        variants.append(("lag 3 2", lagged(L.glcLagDeltaShuffleDevice, 2, 3, 0)))
+        variants.append(("unlag 3 2", lagged(L.glcUnlagDeltaUnshuffleDevice, 2, 3, 0)))
+        variants.append(("grid 1281 2", lagged(L.glcGridDeltaShuffleDevice, 2, 1281, 0)))
+        variants.append(("ungrid 1281 2", lagged(L.glcUngridDeltaUnshuffleDevice, 2, 1281, 0)))
+        for lag, stride in ((1, 0), (3, 0), (1, 4096), (3, 1281)):
+            variants.append(("byte %d,%d" % (lag, stride), byted(L.glcByteDeltaDevice, lag, stride)))
+            variants.append(("unbyte %d,%d" % (lag, stride), byted(L.glcUnbyteDeltaDevice, lag, stride)))
+            byted(L.glcByteDeltaDevice, lag, stride)()
+            glc._chk("unbyte", L.glcUnbyteDeltaDevice(dst.data_ptr(), back.data_ptr(), n, lag, stride, None))
+            assert torch.equal(back, src), (lag, stride)
         del back
     # correctness of what is timed, once, at this size and alignment
     for elem in (2, 4, 8):
