@@ -18,7 +18,10 @@
 // carry version 11's lag and fold: the writer enqueues the lag probe behind the filter probe (lag_probe.hip, lag_rule.h) and
 // reads ten costs and three lags with the same one wait; its triple (13, 0, 0) is parse_stream_format()'s.  Format version 14
 // (filter-grid) is version 13 whose frame word may also name the 2-D predictor of version 12: the grid probe (grid_probe.hip,
-// grid_rule.h) is enqueued behind the lag probe, and the one wait brings thirteen costs, three lags and three widths.
+// grid_rule.h) is enqueued behind the lag probe, and the one wait brings thirteen costs, three lags and three widths.  With
+// glcPlanSetContainerFilterByte the stream is version 16: a frame word may also name the byte predictor at a lag and a row stride,
+// the byte probe (byte_probe.hip, byte_rule.h) is enqueued behind the grid probe, and the one wait brings fifteen costs, three
+// lags, three widths and the byte lag and stride.
 //
 // Encode (Encoder).  A filtered frame is staged through filter_device() into staging kept with the plan and encoded from there;
 // crc_all is taken over the original bytes.  With the BWT codec one hooked glcCompressBatchCompact per frame writes the Huffman
@@ -54,6 +57,7 @@
 #include "../../include/glc_container.h"
 #include "container_internal.h"
 #include "dedup_rule.h"
+#include "byte_rule.h"
 #include "filter_rule.h"
 #include "grid_rule.h"
 #include "lag_rule.h"
@@ -191,6 +195,11 @@ struct Encoder {
     // probe's, the lags behind those and the widths behind the lags: one copy brings all of it
     bool filter_grid = false;
     uint32_t *gw_sums = nullptr, *gw_widths = nullptr, *gw_planes = nullptr;
+    // filter-byte (format version 16): the byte probe's sums, winners and rows of the same frame; its two costs lie behind the grid
+    // probe's, and its lag and stride words behind the widths: one copy brings all of it
+    bool filter_byte = false;
+    unsigned long long *bp_lag_sums = nullptr;
+    uint32_t *bp_sums = nullptr, *bp_words = nullptr, *bp_planes = nullptr;
     unsigned long long *fp_costs = nullptr, *fp_seg = nullptr, *h_costs = nullptr;
 
     // everything of a runs frame is on the plan's stream in order, so one set serves pipelined calls as well
@@ -303,6 +312,7 @@ struct Encoder {
             fp_costs = c.take<unsigned long long>(FP_HOST_WORDS);
             lp_lags = reinterpret_cast<uint32_t *>(fp_costs + ncosts());
             gw_widths = lp_lags + 4;
+            bp_words = lp_lags + 8;
             fp_seg = c.take<unsigned long long>(2);
             if (filter_lag) {
                 lp_sums = c.take<unsigned long long>(LAG_SUMS);
@@ -313,6 +323,12 @@ struct Encoder {
                 c.align(16);
                 gw_planes = c.take<uint32_t>(LAG_ROWS * 256);
                 gw_sums = c.take<uint32_t>(GRID_SUMS);
+            }
+            if (filter_byte) {
+                c.align(16);
+                bp_planes = c.take<uint32_t>(BYTE_ROWS * 256);
+                bp_lag_sums = c.take<unsigned long long>(BYTE_LAGS);
+                bp_sums = c.take<uint32_t>(BYTE_SUM_ROW);
             }
         }
     }
@@ -326,6 +342,7 @@ struct Encoder {
         filter_auto = s.filter_auto;
         filter_lag = s.filter_lag;
         filter_grid = s.filter_grid;
+        filter_byte = s.filter_byte;
         for (uint32_t i = 0; i < FILTER_CANDS; i++) {             // the candidate that is the plan's own filter
             const FilterCand c = filter_cand(i);
             if (c.elem == (fmt.elem ? fmt.elem : 1u) && (c.delta != 0) == fmt.delta()) own_pick = i;
@@ -360,10 +377,11 @@ struct Encoder {
     // stats), and the rule on the host.  A frame beyond the probe's 2^31 bytes is judged by its first 2^31.  With filter-lag the
     // lag probe's sums, winners, rows and costs are enqueued behind it -- the winners never leave the device between them -- and
     // the same wait brings ten costs and three lags; the walk is lag_rule.h's.  With filter-grid the grid probe follows in the same
-    // way, and the walk is grid_rule.h's over thirteen costs.  *pick: the candidate (below GRID_CANDS), *lag: its lag, *width: its
-    // row width (0 but for a grid candidate).
-    static constexpr size_t FP_HOST_WORDS = GRID_CANDS + 4;   // up to thirteen costs, then the three lags and the three widths in two 64-bit words each
-    size_t ncosts() const { return filter_grid ? GRID_CANDS : LAG_CANDS; }
+    // way, and the walk is grid_rule.h's over thirteen costs; with filter-byte the byte probe follows, and the walk is byte_rule.h's
+    // over fifteen.  *pick: the candidate (below BYTE_CANDS), *lag: its lag, *width: its row width, for a byte candidate its row
+    // stride (0 but for a grid candidate and the strided byte candidate).
+    static constexpr size_t FP_HOST_WORDS = BYTE_CANDS + 5;   // up to fifteen costs, then the three lags and the three widths in two 64-bit words each, the byte lag and stride in one
+    size_t ncosts() const { return filter_byte ? BYTE_CANDS : filter_grid ? GRID_CANDS : LAG_CANDS; }
     CUDPPResult pick_filter(const uint8_t *d_in, unsigned long long frame_len, uint32_t *pick, uint32_t *lag, uint32_t *width)
     {
         const uint32_t max_len = (uint32_t)std::min<unsigned long long>(frame_len, GLC_FILTER_PROBE_MAX_LEN);
@@ -383,11 +401,18 @@ struct Encoder {
             CT_TRY(grid_probe_sums(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, gw_sums, gw_widths));
             CT_TRY(grid_probe_planes(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, gw_widths, gw_planes, fp_costs + LAG_CANDS));
         }
-        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * (ncosts() + 4), hipMemcpyDeviceToHost, P.st));
+        if (filter_byte) {
+            CT_TRY(byte_probe_sums(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, bp_lag_sums, bp_sums, bp_words));
+            CT_TRY(byte_probe_planes(P.st, d_in, fp_seg, fp_seg + 1, 1, max_len, bp_words, bp_planes, fp_costs + GRID_CANDS));
+        }
+        CT_TRY(hipMemcpyAsync(h_costs, fp_costs, 8 * (ncosts() + 5), hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
-        const uint32_t *words = reinterpret_cast<const uint32_t *>(h_costs + ncosts());      // three lags, a pad, three widths
-        *pick = filter_grid ? grid_pick(h_costs) : lag_pick(h_costs);
-        if (*pick >= LAG_CANDS) *width = grid_width_word(words[4 + *pick - LAG_CANDS]);      // (never 0: such a candidate costs GRID_NO_COST)
+        const uint32_t *words = reinterpret_cast<const uint32_t *>(h_costs + ncosts());      // three lags, a pad, three widths, a pad, the byte lag and stride
+        *pick = filter_byte ? byte_pick(h_costs) : filter_grid ? grid_pick(h_costs) : lag_pick(h_costs);
+        if (*pick >= GRID_CANDS) {                            // (a strided candidate without a stride costs GRID_NO_COST: never picked)
+            *lag = lag_clamp(words[8]);
+            *width = *pick == GRID_CANDS ? 0u : byte_stride_word(words[9]);
+        } else if (*pick >= LAG_CANDS) *width = grid_width_word(words[4 + *pick - LAG_CANDS]);      // (never 0: such a candidate costs GRID_NO_COST)
         else if (*pick >= FILTER_CANDS) *lag = lag_clamp(words[*pick - FILTER_CANDS]);
         return CUDPP_SUCCESS;
     }
@@ -409,14 +434,15 @@ struct Encoder {
             const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick, &lag, &width);
             if (r != CUDPP_SUCCESS) return r;
             const uint32_t lags[LAG_ELEMS] = {lag, lag, lag}, widths[LAG_ELEMS] = {width, width, width};
-            const GridCand c = grid_cand(pick, lags, widths); // (below FILTER_CANDS: filter_rule.h's candidate, lag 1 and no fold)
-            ff.elem = c.elem > 1 ? c.elem : 0;
+            const GridCand c = byte_cand(pick, lags, widths, lag, width);     // (below FILTER_CANDS: filter_rule.h's candidate, lag 1 and no fold)
+            ff.elem = c.elem > 1 || pick >= GRID_CANDS ? c.elem : 0;      // (a byte candidate's frame has elem 1: version 15's format)
             ff.flags = c.delta ? CT_FLAG_DELTA | (c.fold ? CT_FLAG_FOLD : 0u) | (c.lag - 1u) << CT_LAG_SHIFT | (c.width ? CT_FLAG_GRID : 0u) : 0;
             ff.width = c.width;                               // (the frame's format: ct_frame_format()'s of the word written below)
         }
         if (pick < FILTER_CANDS) rep.filters[pick]++;         // (a frame that took a lag or grid candidate counts among all frames only)
         else if (pick < LAG_CANDS) { rep.lag_filters[pick - FILTER_CANDS]++; rep.lag_filters[LAG_ELEMS]++; }
-        else { rep.grid_filters[pick - LAG_CANDS]++; rep.grid_filters[LAG_ELEMS]++; }
+        else if (pick < GRID_CANDS) { rep.grid_filters[pick - LAG_CANDS]++; rep.grid_filters[LAG_ELEMS]++; }
+        else { rep.byte_filters[pick - GRID_CANDS]++; rep.byte_filters[BYTE_ROWS]++; }
         rep.filters[FILTER_CANDS]++;
         if (ff.filtered()) {
             plan_wait_released(P.h);                          // (the frame that staged here two calls ago is through)
@@ -668,6 +694,7 @@ struct Encoder {
         memcpy(r.filters, rep.filters, sizeof r.filters);
         memcpy(r.lag_filters, rep.lag_filters, sizeof r.lag_filters);
         memcpy(r.grid_filters, rep.grid_filters, sizeof r.grid_filters);
+        memcpy(r.byte_filters, rep.byte_filters, sizeof r.byte_filters);
         set_error(P.h, CT_OK);
         return CUDPP_SUCCESS;
     }
@@ -1273,7 +1300,7 @@ CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &i
     const CUDPPResult r = walk_result(plan, end, stopped);
     if (r != CUDPP_SUCCESS) return r;
     ix->fmt = CtFormat();
-    (void)parse_container_format(ix->hdr, &ix->fmt);
+    (void)parse_frame_filter_format(ix->hdr, &ix->fmt);
     ix->block_len = ix->hdr[2];
     ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
     *index = ix.release();
@@ -1692,6 +1719,11 @@ CUDPPResult glcContainerLastGridFilters(CUDPPHandle plan, unsigned long long out
     return last_report(plan, false, out, LAG_ELEMS + 1, [](const CtReports &r) { return r.grid_filters; });
 }
 
+CUDPPResult glcContainerLastByteFilters(CUDPPHandle plan, unsigned long long out[3])
+{
+    return last_report(plan, false, out, BYTE_ROWS + 1, [](const CtReports &r) { return r.byte_filters; });
+}
+
 CUDPPResult glcPlanSetContainerShuffle(CUDPPHandle plan, unsigned int elem)
 {
     return ct_set(plan, [&](CtSettings &s) { return s.set_shuffle(elem); });
@@ -1747,6 +1779,11 @@ CUDPPResult glcPlanSetContainerFilterGrid(CUDPPHandle plan, unsigned int on)
     return ct_set(plan, [&](CtSettings &s) { return s.set_filter_grid(on); });
 }
 
+CUDPPResult glcPlanSetContainerFilterByte(CUDPPHandle plan, unsigned int on)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_filter_byte(on); });
+}
+
 CUDPPResult glcPlanGetContainerShuffle(CUDPPHandle plan, unsigned int *elem)
 {
     return ct_get(plan, elem, [](const CtSettings &s) { return s.shuffle; });
@@ -1800,6 +1837,11 @@ CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on)
 CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on)
 {
     return ct_get(plan, on, [](const CtSettings &s) { return s.filter_grid ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanGetContainerFilterByte(CUDPPHandle plan, unsigned int *on)
+{
+    return ct_get(plan, on, [](const CtSettings &s) { return s.filter_byte ? 1u : 0u; });
 }
 
 CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold)

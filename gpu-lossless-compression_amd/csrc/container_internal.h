@@ -284,14 +284,21 @@ __host__ __device__ inline bool ct_byte_legal(uint32_t flags, uint32_t word3)
            ((flags & CT_FLAG_GRID) != 0) == (stride != 0);
 }
 constexpr uint32_t CT_VERSION_MAX = CT_VERSION_BYTE;
+// 16: version 14 whose frame word may also name the byte predictor: a word with bit 31 set and the low byte 1 is
+// 1 | stride << 8 | (lag - 1) << 25 | 1 << 31 (stride 0 or 2..65536, lag 1..16, bits 29 and 30 zero); under version 14 every such
+// word is illegal (its elem is 1), so the families cannot collide.  The stream header's triple is (16, 0, 0).  It is no entry of
+// ct_kinds()'s table, which tools/byte_format_check.cpp pins: CtFormat::kinds() answers version 8's kinds for it
+constexpr uint32_t CT_VERSION_FILTER_BYTE = 16;
+constexpr uint32_t CT_WORD_BYTE_LAG_SHIFT = 25, CT_WORD_BYTE_LAG = 15u << CT_WORD_BYTE_LAG_SHIFT;
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
 // its filter-auto setting version 10, its delta-lag setting version 11, its grid setting version 12, its filter-lag setting
-// version 13, its filter-grid setting version 14 and its byte-delta setting version 15 (each is only ever on with the auto mode, so
-// that mode's bits come with it; filter-lag only with filter-auto, filter-grid only with filter-lag)
+// version 13, its filter-grid setting version 14, its byte-delta setting version 15 and its filter-byte setting version 16 (each is
+// only ever on with the auto mode, so that mode's bits come with it; filter-lag only with filter-auto, filter-grid only with
+// filter-lag, filter-byte only with filter-grid)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
 constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128, CT_READS_FILTER_LAG = 256, CT_READS_FILTER_GRID = 512;
-constexpr uint32_t CT_READS_BYTE = 1024;
+constexpr uint32_t CT_READS_BYTE = 1024, CT_READS_FILTER_BYTE = 2048;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
@@ -304,21 +311,22 @@ __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 // are a family of flags over it: the delta's lag and fold; version 12's a family of row widths, which ride in the element word).
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
-    uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12 and in a grid FRAME's format under version 14
+    uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12 and in a grid FRAME's format under versions 14 and 16
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     // the delta's lag and fold: (1, 0) below version 11; under version 13 a FRAME's format (ct_frame_format) carries them
-    __host__ __device__ bool frame_filters() const { return version == CT_VERSION_FILTER || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID; }
-    // the byte predictor: version 15's streams; elem is 1, `width` the row stride in bytes (0 = none), the lag in the flags
-    __host__ __device__ bool bytes() const { return version == CT_VERSION_BYTE; }
-    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID || bytes(); }
+    __host__ __device__ bool frame_filters() const { return version == CT_VERSION_FILTER || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID || version == CT_VERSION_FILTER_BYTE; }
+    // the byte predictor: version 15's streams, and under version 16 the format of a frame whose word names it (no other frame
+    // has elem 1); elem is 1, `width` the row stride in bytes (0 = none), the lag in the flags
+    __host__ __device__ bool bytes() const { return version == CT_VERSION_BYTE || (version == CT_VERSION_FILTER_BYTE && elem == 1); }
+    __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID || version == CT_VERSION_FILTER_BYTE || bytes(); }
     __host__ __device__ uint32_t lag() const { return lag_flags() ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
     __host__ __device__ uint32_t fold() const { return (lag_flags() || version == CT_VERSION_GRID) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
-    // the 2-D predictor: version 12's streams, and under version 14 the format of a frame whose word names it
-    __host__ __device__ bool grid() const { return version == CT_VERSION_GRID || (version == CT_VERSION_FILTER_GRID && width != 0); }
+    // the 2-D predictor: version 12's streams, and under versions 14 and 16 the format of a frame whose word names it
+    __host__ __device__ bool grid() const { return version == CT_VERSION_GRID || (version == CT_VERSION_FILTER_GRID && width != 0) || (version == CT_VERSION_FILTER_BYTE && width != 0 && elem != 1); }
     // the stream header's word 3: the element size, under version 12 with the row width above it
     __host__ __device__ uint32_t word3() const { return elem | width << CT_WIDTH_SHIFT; }
-    __host__ __device__ uint32_t kinds() const { return ct_kinds(version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4)
+    __host__ __device__ uint32_t kinds() const { return ct_kinds(version == CT_VERSION_FILTER_BYTE ? CT_VERSION_AUTO : version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4; 16: version 8's)
     __host__ __device__ bool kind2_legal() const { return (kinds() >> 2 & 1u) != 0; }
     __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
     __host__ __device__ bool kind4_legal() const { return (kinds() >> 4 & 1u) != 0; }
@@ -332,23 +340,27 @@ struct CtFormat {
                version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
                version == CT_VERSION_LAG ? CT_READS_LAG : version == CT_VERSION_GRID ? CT_READS_GRID :
                version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : version == CT_VERSION_FILTER_GRID ? CT_READS_FILTER_GRID :
-               version == CT_VERSION_BYTE ? CT_READS_BYTE : 0u;
+               version == CT_VERSION_BYTE ? CT_READS_BYTE : version == CT_VERSION_FILTER_BYTE ? CT_READS_FILTER_BYTE : 0u;
     }
 };
-// a frame header's word 3.  Versions 1 to 9, 11 and 12 keep it 0; under versions 10, 13 and 14 it is the frame's filter.  ct_frame_word_legal() is the
+// a frame header's word 3.  Versions 1 to 9, 11, 12 and 15 keep it 0; under versions 10, 13, 14 and 16 it is the frame's filter.  ct_frame_word_legal() is the
 // header's range check on it, ct_frame_format() the format whose filter a frame with a legal word went through: the stream's
 // below version 10, the word's under it
 __host__ __device__ inline uint32_t ct_frame_word(const CtFormat &f)
 {
+    if (f.version == CT_VERSION_FILTER_BYTE && f.elem == 1)   // version 16's byte word
+        return 1u | f.width << CT_WIDTH_SHIFT | (f.lag() - 1) << CT_WORD_BYTE_LAG_SHIFT | CT_WORD_GRID;
     if (f.width) return f.elem | f.width << CT_WIDTH_SHIFT | (f.fold() ? CT_WORD_GRID_FOLD : 0u) | CT_WORD_GRID;
     return f.elem | (f.flags << 16);
 }
 __host__ __device__ inline bool ct_frame_word_legal(const CtFormat &stream, uint32_t word)
 {
     if (!stream.frame_filters()) return word == 0;
-    if (word & CT_WORD_GRID) {                                // version 14's grid word
+    if (word & CT_WORD_GRID) {                                // version 14's grid word, version 16's byte word
         const uint32_t e = word & 0xFFu;
-        return stream.version == CT_VERSION_FILTER_GRID && !(word & ~(0xFFu | CT_WORD_GRID_WIDTH | CT_WORD_GRID_FOLD | CT_WORD_GRID)) &&
+        if (stream.version == CT_VERSION_FILTER_BYTE && e == 1)
+            return !(word & ~(0xFFu | CT_WORD_GRID_WIDTH | CT_WORD_BYTE_LAG | CT_WORD_GRID)) && ct_byte_stride_ok((word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT);
+        return (stream.version == CT_VERSION_FILTER_GRID || stream.version == CT_VERSION_FILTER_BYTE) && !(word & ~(0xFFu | CT_WORD_GRID_WIDTH | CT_WORD_GRID_FOLD | CT_WORD_GRID)) &&
                (e == 2 || e == 4 || e == 8) && ct_grid_width_ok((word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT);
     }
     const uint32_t elem = word & 0xFFFFu, flags = word >> 16;
@@ -360,7 +372,13 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
 {
     CtFormat f = stream;
     if (!stream.frame_filters()) return f;
-    if (word & CT_WORD_GRID) {                                // (legal under version 14 alone: version 12's filter for this frame)
+    if (word & CT_WORD_GRID) {                                // (legal under versions 14 and 16 alone: version 12's filter for this frame)
+        if (stream.version == CT_VERSION_FILTER_BYTE && (word & 0xFFu) == 1) {     // (version 15's filter for this frame, its flags)
+            f.elem = 1;
+            f.width = (word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT;
+            f.flags = CT_FLAG_DELTA | (f.width ? CT_FLAG_GRID : 0u) | ((word & CT_WORD_BYTE_LAG) >> CT_WORD_BYTE_LAG_SHIFT) << CT_LAG_SHIFT;
+            return f;
+        }
         f.elem = word & 0xFFu;
         f.width = (word & CT_WORD_GRID_WIDTH) >> CT_WIDTH_SHIFT;
         f.flags = CT_FLAG_DELTA | CT_FLAG_GRID | (word & CT_WORD_GRID_FOLD ? CT_FLAG_FOLD : 0u);
@@ -499,11 +517,21 @@ __host__ __device__ inline bool parse_container_format(const uint32_t h[8], CtFo
     return true;
 }
 
+// version 16's one triple (16, 0, 0) beside it, accepted the way 13, 14 and 15 were: parse_container_format() is pinned up to
+// version 17 by tools/byte_format_check.cpp, so this is the function the readers call; tools/filter_byte_rule_check.cpp pins it
+__host__ __device__ inline bool parse_frame_filter_format(const uint32_t h[8], CtFormat *f)
+{
+    if (parse_container_format(h, f)) return true;
+    if (f->version != CT_VERSION_FILTER_BYTE || f->flags != 0 || h[3] != 0) return false;
+    f->elem = 0; f->width = 0;
+    return true;
+}
+
 // the checks on a stream header; false = refused
 __host__ __device__ inline bool check_stream_header(const CrcTables &C, const uint32_t h[8], CtFormat *fmt, uint32_t *block_len,
                                                     unsigned long long *total)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_container_format(h, fmt)) return false;
+    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_frame_filter_format(h, fmt)) return false;
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
     *block_len = h[2];
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
@@ -615,11 +643,15 @@ struct CtSettings {
     // filter-grid: filter-lag also weighs the 2-D predictor at the row width it finds per frame (grid_rule.h) and writes version
     // 14.  Only ever on with filter-lag on; whatever switches that off switches this off
     bool filter_grid = false;
+    // filter-byte: filter-grid also weighs the byte predictor at the lag and the row stride it finds per frame (byte_rule.h) and
+    // writes version 16.  Only ever on with filter-grid on; whatever switches that off switches this off
+    bool filter_byte = false;
     void filter_keep()
     {
         if (mode != CT_MODE_AUTO) filter_auto = false;
         if (!filter_auto) filter_lag = false;
         if (!filter_lag) filter_grid = false;
+        if (!filter_grid) filter_byte = false;
     }
     // delta-lag: the delta's predecessor is `lag` elements back and its sign is folded where fold = 1 (lag.hip; the writer writes
     // version 11).  Anything but (1, 0) is only ever on with the order-0 codec, the auto mode, the shuffle and the delta on and
@@ -715,13 +747,20 @@ struct CtSettings {
     {
         if (on > 1 || (on && !filter_lag)) return false;
         filter_grid = on != 0;
+        filter_keep();
+        return true;
+    }
+    bool set_filter_byte(uint32_t on)
+    {
+        if (on > 1 || (on && !filter_grid)) return false;
+        filter_byte = on != 0;
         return true;
     }
     // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
-               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) |
+               mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) | (filter_byte ? CT_READS_FILTER_BYTE : 0u) |
                                       (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) | (byte_on() ? CT_READS_BYTE : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
@@ -739,7 +778,7 @@ struct CtSettings {
 inline CtFormat format_of(const CtSettings &s)
 {
     CtFormat f;
-    if (s.filter_auto) { f.version = s.filter_grid ? CT_VERSION_FILTER_GRID : s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
+    if (s.filter_auto) { f.version = s.filter_byte ? CT_VERSION_FILTER_BYTE : s.filter_grid ? CT_VERSION_FILTER_GRID : s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
     if (s.byte_on()) {
         f.version = CT_VERSION_BYTE;
         f.flags = CT_FLAG_DELTA | (s.byte_stride ? CT_FLAG_GRID : 0u) | (s.byte_lag - 1) << CT_LAG_SHIFT;
@@ -774,6 +813,7 @@ struct CtReports {
     unsigned long long filters[FILTER_CANDS + 1] = {};     // frames per candidate of filter_rule.h, then all frames, of the last successful compress
     unsigned long long lag_filters[4] = {};                // frames that took the lag candidate of elem 2, 4, 8 (lag_rule.h) and their sum, of the same compress
     unsigned long long grid_filters[4] = {};               // frames that took the grid candidate of elem 2, 4, 8 (grid_rule.h) and their sum, of the same compress
+    unsigned long long byte_filters[3] = {};               // frames that took byte (lag, 0), byte (lag, stride) (byte_rule.h) and their sum, of the same compress
 };
 CtReports &plan_container_reports(CUDPPHandle plan);
 // the plan's two frame staging buffers for the filter (grown on demand, never shrunk, freed with the plan; encoder: one per
@@ -935,6 +975,15 @@ hipError_t grid_probe_sums(hipStream_t st, const uint8_t *data, const unsigned l
                            uint32_t count, uint32_t max_len, uint32_t *sums, uint32_t *widths);
 hipError_t grid_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                              uint32_t count, uint32_t max_len, const uint32_t *widths, uint32_t *planes, unsigned long long *costs);
+// the byte probe (byte_probe.hip, byte_rule.h), the segments as the filter probe's: row i of lag_sums = the 16 sums A[l] of segment
+// i, row i of stride_sums its 65537 sums S[W] (0xFFFFFFFF where W is no candidate) and row i of winners {lag, stride} (stride 0: no
+// candidate); row i of planes = the two histograms of segment i at the {lag, stride} words of row i of `words` (device memory; the
+// lag used as ((v - 1) & 15) + 1, a stride outside 17..65536 names none: a zero row, GRID_NO_COST), row i of costs their two
+// costs (both GRID_NO_COST below 1024 counted bytes).  planes is 16-byte aligned; nothing need be zeroed.  Everything only enqueues.
+hipError_t byte_probe_sums(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                           uint32_t count, uint32_t max_len, unsigned long long *lag_sums, uint32_t *stride_sums, uint32_t *winners);
+hipError_t byte_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                             uint32_t count, uint32_t max_len, const uint32_t *words, uint32_t *planes, unsigned long long *costs);
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every
 // block from the statistics (kind 3 when 32 E >= nch, K's bytes, its counts into au.hist_s, the segment its table and encoder would
 // read into (in_off, in_len), sp.skip_table) and wA into au.wa.  Behind the tables of au.hist_s: wS, the choice (au.pick5), the

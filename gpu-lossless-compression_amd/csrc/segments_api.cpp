@@ -477,4 +477,32 @@ CUDPPResult glcGridPlanesSegments(const void *d_inBase, const unsigned long long
     return CUDPP_SUCCESS;
 }
 
+// the two byte probes: a bad argument is refused before anything is enqueued
+CUDPPResult glcByteProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned long long *d_lagSums, unsigned int *d_strideSums,
+                                 unsigned int *d_winners, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_lagSums, 8, d_strideSums, 4)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    if (!d_winners || (reinterpret_cast<uintptr_t>(d_winners) & 3) || static_cast<void *>(d_winners) == d_lagSums ||
+        d_winners == d_strideSums) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(byte_probe_sums(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                           (uint32_t)maxLen, d_lagSums, d_strideSums, d_winners));
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcBytePlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_words, unsigned int *d_planes,
+                                  unsigned long long *d_costs, void *stream)
+{
+    if (!lag_probe_args_ok(d_inBase, d_offsets, d_lengths, count, maxLen, d_planes, 16, d_costs, 8)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (count == 0) return CUDPP_SUCCESS;
+    // (the words are read while the outputs are written: neither output may be them)
+    if (!d_words || (reinterpret_cast<uintptr_t>(d_words) & 3) || static_cast<const void *>(d_words) == d_planes ||
+        static_cast<const void *>(d_words) == d_costs) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    CT_TRY(byte_probe_planes(reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t *>(d_inBase), d_offsets, d_lengths, (uint32_t)count,
+                             (uint32_t)maxLen, d_words, d_planes, d_costs));
+    return CUDPP_SUCCESS;
+}
+
 } // extern "C"

@@ -726,6 +726,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerFilterGrid", "glcPlanGetContainerFilterGrid", "glcContainerLastGridFilters",
                      "glcByteDeltaDevice", "glcUnbyteDeltaDevice", "glcUnbyteDeltaRangeDevice",
                      "glcPlanSetContainerByteDelta", "glcPlanGetContainerByteDelta",
+                     "glcByteProbeSegments", "glcBytePlanesSegments",
+                     "glcPlanSetContainerFilterByte", "glcPlanGetContainerFilterByte", "glcContainerLastByteFilters",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -809,6 +811,9 @@ def _ct():
         L.glcContainerLastGridFilters.argtypes = [sz, ullp]
         L.glcGridProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp]
         L.glcGridPlanesSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.glcContainerLastByteFilters.argtypes = [sz, ullp]
+        L.glcByteProbeSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
+        L.glcBytePlanesSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, vp, vp]
         L.glcDedupWorkBytes.argtypes = [sz, sz]
         L.glcDedupWorkBytes.restype = sz
         L.glcDedupMapSegments.argtypes = [vp, vp, vp, sz, sz, vp, vp, sz, vp]
@@ -1022,6 +1027,25 @@ def container_last_grid_filters(plan):
     return tuple(int(v) for v in a)
 
 
+def container_set_filter_byte(plan, on):
+    """filter-byte of the plan's container ENCODER (format version 16: filter-grid also weighs the byte predictor at the lag and the
+    row stride the byte probe finds per frame): True / 1 needs filter-grid on, and whatever switches filter-grid off switches it
+    off.  It is also the version the plan reads: on, versions 1 to 5, 7, 8, 10, 13, 14 and 16; off, a version-16 stream is a
+    stream-header failure."""
+    _chk("glcPlanSetContainerFilterByte", _ct().glcPlanSetContainerFilterByte(plan.handle, int(on)))
+
+
+def container_get_filter_byte(plan):
+    return _get_uint("glcPlanGetContainerFilterByte", plan)
+
+
+def container_last_byte_filters(plan):
+    """(frames that took the byte candidate at (lag, 0), at (lag, stride), their sum) of the plan's last successful compress"""
+    a = (C.c_ulonglong * 3)()
+    _chk("glcContainerLastByteFilters", _ct().glcContainerLastByteFilters(plan.handle, a))
+    return tuple(int(v) for v in a)
+
+
 def container_set_delta_lag(plan, lag, fold):
     """the lag and fold of the delta of the plan's container ENCODER (format version 11: the predecessor `lag` elements back, the
     sign folded into bit 0 where fold is 1); (1, 0) is off.  Anything else needs the order-0 codec, the auto mode, the shuffle
@@ -1227,6 +1251,47 @@ def grid_planes_segments(d_in, offsets, lengths, widths, max_len=None, planes=No
     assert widths.is_contiguous() and widths.dtype == torch.int32 and widths.numel() >= 3 * n
     assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
     _chk("glcGridPlanesSegments", _ct().glcGridPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, widths.data_ptr(),
+                                                               planes.data_ptr(), costs.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return planes[:n], costs[:n]
+
+
+BYTE_PROBE_LAGS, BYTE_PROBE_ROW, BYTE_PROBE_ROWS = 16, 65537, 2
+
+
+def byte_probe_segments(d_in, offsets, lengths, max_len=None, lag_sums=None, stride_sums=None, winners=None, stream=None):
+    """the byte probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (lag_sums,
+    stride_sums, winners) -- an int64 tensor [count, 16] of the magnitudes A[l] of the byte differences at lag l = 1 .. 16 over each
+    segment's first L - L % 8 bytes, an int32 tensor [count, 65537] whose word W is S[W] for the row strides 17 .. Wmax (the bit
+    pattern 0xFFFFFFFF, so -1, where W is no candidate), and an int32 tensor [count, 2] of the lag and the stride with the smallest
+    sums, the stride 0 where there is none (csrc/byte_rule.h).  The outputs need not be zeroed."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    lag_sums = torch.empty((max(1, n), BYTE_PROBE_LAGS), dtype=torch.int64, device=dev) if lag_sums is None else lag_sums
+    stride_sums = torch.empty((max(1, n), BYTE_PROBE_ROW), dtype=torch.int32, device=dev) if stride_sums is None else stride_sums
+    winners = torch.empty((max(1, n), 2), dtype=torch.int32, device=dev) if winners is None else winners
+    assert lag_sums.is_contiguous() and stride_sums.is_contiguous() and winners.is_contiguous()
+    assert lag_sums.dtype == torch.int64 and stride_sums.dtype == torch.int32 and winners.dtype == torch.int32
+    assert lag_sums.numel() >= BYTE_PROBE_LAGS * n and stride_sums.numel() >= BYTE_PROBE_ROW * n and winners.numel() >= 2 * n
+    _chk("glcByteProbeSegments", _ct().glcByteProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
+                                                             lag_sums.data_ptr(), stride_sums.data_ptr(), winners.data_ptr(), stream))
+    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    return lag_sums[:n], stride_sums[:n], winners[:n]
+
+
+def byte_planes_segments(d_in, offsets, lengths, words, max_len=None, planes=None, costs=None, stream=None):
+    """the plane probe of the byte rule over the same segments at the {lag, stride} words of the device int32 tensor `words`
+    [count, 2] (the lag used as ((v - 1) & 15) + 1; a stride outside 17..65536 names none: a zero row and the cost 2^56):
+    (planes, costs) -- an int32 tensor [count, 2, 256], the histograms of the byte predictor's output at (lag, 0) and at (lag,
+    stride), and an int64 tensor [count, 2].  planes / costs: tensors to write into (they need not be zeroed)."""
+    import torch
+    dev, off, ln, n, max_len = _lag_probe_args(d_in, offsets, lengths, max_len)
+    planes = torch.empty((max(1, n), BYTE_PROBE_ROWS, 256), dtype=torch.int32, device=dev) if planes is None else planes
+    costs = torch.empty((max(1, n), BYTE_PROBE_ROWS), dtype=torch.int64, device=dev) if costs is None else costs
+    assert planes.is_contiguous() and costs.is_contiguous() and costs.dtype == torch.int64
+    assert words.is_contiguous() and words.dtype == torch.int32 and words.numel() >= 2 * n
+    assert planes.numel() >= BYTE_PROBE_ROWS * 256 * n and costs.numel() >= BYTE_PROBE_ROWS * n
+    _chk("glcBytePlanesSegments", _ct().glcBytePlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, words.data_ptr(),
                                                                planes.data_ptr(), costs.data_ptr(), stream))
     torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
     return planes[:n], costs[:n]

@@ -560,6 +560,36 @@ CUDPPResult glcGridPlanesSegments(const void *d_inBase, const unsigned long long
                                   size_t count, size_t maxLen, const unsigned int *d_widths, unsigned int *d_planes,
                                   unsigned long long *d_costs, void *stream);
 
+/* The byte probe as two batched calls (csrc/byte_probe.hip, csrc/byte_rule.h): which lag and which row stride of glcByteDeltaDevice's
+ * byte predictor a segment wants, and what its output would cost.  The segments are those of glcFilterProbeSegments: with
+ * L = min(d_lengths[i], maxLen) only the first P = L - L % 8 bytes x[j] of segment i are counted.
+ *   glcByteProbeSegments   row i of d_lagSums is sixteen 64-bit words: at word l - 1 the sum over j < P of m((x[j] - p) mod 256)
+ *                          for the lag l = 1 .. 16, p = x[j - l] where j mod 2048 >= l and 0 elsewhere, m(d) = d below 128 and
+ *                          255 - d otherwise, exact.  Row i of d_strideSums is 65537 32-bit words (GLC_BYTE_PROBE_ROW): with
+ *                          P >= 1024, Wmax = min(65536, P / 2) and glcGridProbeSegments' 32 tiles of 256 targets at element size 1,
+ *                          at word W the sum of bitlen(fold((x[j] - x[j - W]) mod 256)) for W = 17 .. Wmax; 0xFFFFFFFF at every
+ *                          other word.  Row i of d_winners is two words: the lag with the smallest sum and the stride with the
+ *                          smallest sum, ties to the smallest, the stride 0 where P < 1024.
+ *   glcBytePlanesSegments  row i of d_planes is two histograms of 256 words: of the bytes glcByteDeltaDevice(lag, 0) and of the
+ *                          bytes glcByteDeltaDevice(lag, stride) write from the counted bytes, bands and run heads included,
+ *                          with {lag, stride} read from row i of d_words in device memory; row i of d_costs is two 64-bit words,
+ *                          the cost of glcFilterProbeSegments of each histogram.  The lag word is used as ((v - 1) & 15) + 1.  A
+ *                          stride word outside 17..65536 names no stride: its row is zero, its cost is 2^56 (which the rule never
+ *                          picks), and it is never used as a distance.  With P < 1024 both rows are zero and both costs 2^56.
+ * The second call takes the first's d_winners without the host between them.  The rule that reads the costs (csrc/byte_rule.h) is
+ * glcGridProbeSegments' walk over fifteen candidates: its thirteen, then the byte predictor at (lag, 0) and at (lag, stride), under
+ * the same margin.  No output need be zeroed by the caller.  Both calls only enqueue on `stream`.  A bad argument (a null pointer
+ * with count > 0, d_strideSums, d_winners or d_words not 4-byte, d_lagSums or d_costs not 8-byte or d_planes not 16-byte aligned, two
+ * of a call's arrays equal, a maxLen above GLC_FILTER_PROBE_MAX_LEN or a count above GLC_PROBE_MAX_COUNT) is
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION with nothing written. */
+#define GLC_BYTE_PROBE_ROW 65537
+CUDPPResult glcByteProbeSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                 size_t count, size_t maxLen, unsigned long long *d_lagSums, unsigned int *d_strideSums,
+                                 unsigned int *d_winners, void *stream);
+CUDPPResult glcBytePlanesSegments(const void *d_inBase, const unsigned long long *d_offsets, const unsigned long long *d_lengths,
+                                  size_t count, size_t maxLen, const unsigned int *d_words, unsigned int *d_planes,
+                                  unsigned long long *d_costs, void *stream);
+
 /* {blocks given to the BWT codec, blocks given to the order-0 codec, frames written} of the plan's last successful container
  * compress, whatever its codec; with GLC_CONTAINER_CODEC_CHOOSE the first two are the rule's choices, counted before the record
  * rule stores a block raw.  {0, 0, 0} before the first. */
@@ -708,6 +738,28 @@ CUDPPResult glcPlanGetContainerFilterLag(CUDPPHandle plan, unsigned int *on);
 CUDPPResult glcPlanSetContainerFilterGrid(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on);
 
+/* Filter-byte: filter-grid also finds the lag and the row stride of the byte predictor per frame, for 8-bit samples.  on = 1 writes
+ * format version 16: version 14 whose frame word may also name glcByteDeltaDevice's filter.  A frame word is version 14's,
+ * unchanged, or a byte word 1 | stride << 8 | (lag - 1) << 25 | 1 << 31: the low byte 1, stride 0 or 2..65536, lag 1..16, bits 29
+ * and 30 zero; that frame went through glcByteDeltaDevice(lag, stride) as one segment and is format version 15's frame of its
+ * bytes but for the word and the table CRC.  (Under version 14 every word with bit 31 set and the low byte 1 is illegal, so the
+ * families cannot collide.)  The stream header's triple is (16, 0, 0); kinds, frames, tables, records and trailer are version
+ * 14's.  Per frame the writer enqueues the byte probe behind the grid probe (glcByteProbeSegments and glcBytePlanesSegments, the
+ * winners staying in device memory between them), reads fifteen costs, three lags, three widths and the byte lag and stride back
+ * with the one wait filter-auto has, and walks the fifteen candidates of csrc/byte_rule.h: filter-grid's thirteen in their order,
+ * then the byte predictor at (lag, 0) and at (lag, stride), under the same margin.  The writer makes strides of 0 or at least 17;
+ * the reader takes version 15's whole family.  A stream whose every pick is among the first thirteen differs from the version-14
+ * stream only in the header's version and its CRC.  on = 1 needs filter-grid on: on = 1 without it, and any other value, are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was; whatever switches filter-grid off switches this off.
+ * 0 (the default) writes every stream byte for byte as before.  All six container entry points write the same bytes, with
+ * pipelining on or off.  Range reads of a byte frame start at a run, or at a band of that frame's stride, and use
+ * glcUnbyteDeltaRangeDevice.  The setting is also the version the plan speaks: with it on the plan reads versions 1 to 5, 7, 8, 10,
+ * 13, 14 and 16; every other plan, a filter-grid plan and a byte-delta plan included, refuses a version-16 stream as a
+ * stream-header failure.  A byte word under an older header, and any bit-31 word outside the two families, is a frame-table
+ * failure naming the frame.  glcPlanSetContainerByteDelta stays exclusive with filter-auto. */
+CUDPPResult glcPlanSetContainerFilterByte(CUDPPHandle plan, unsigned int on);
+CUDPPResult glcPlanGetContainerFilterByte(CUDPPHandle plan, unsigned int *on);
+
 /* The lag and row stride of the ENCODER's byte predictor (glcByteDeltaDevice); lag 0 = off, the default.  On needs the order-0
  * codec, the auto mode on, the shuffle off (hence the delta, the delta-lag and the grid settings off) and filter-auto off; any other
  * state, a lag above 16 and a stride of 1 or above 65536 are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.
@@ -722,8 +774,8 @@ CUDPPResult glcPlanGetContainerByteDelta(CUDPPHandle plan, unsigned int *lag, un
 
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.
- * With filter-auto off every frame counts for the plan's own filter; a frame that took a lag candidate of filter-lag or a grid
- * candidate of filter-grid counts in out[7] only.  Zeros before the first. */
+ * With filter-auto off every frame counts for the plan's own filter; a frame that took a lag candidate of filter-lag, a grid
+ * candidate of filter-grid or a byte candidate of filter-byte counts in out[7] only.  Zeros before the first. */
 CUDPPResult glcContainerLastFilters(CUDPPHandle plan, unsigned long long out[8]);
 
 /* Frames of the plan's last successful container compress that took the lag candidate of elem 2, of elem 4 and of elem 8
@@ -733,6 +785,10 @@ CUDPPResult glcContainerLastLagFilters(CUDPPHandle plan, unsigned long long out[
 /* Frames of the plan's last successful container compress that took the grid candidate of elem 2, of elem 4 and of elem 8
  * (glcPlanSetContainerFilterGrid), and their sum.  Zeros before the first and with the setting off. */
 CUDPPResult glcContainerLastGridFilters(CUDPPHandle plan, unsigned long long out[4]);
+
+/* Frames of the plan's last successful container compress that took the byte candidate at (lag, 0) and at (lag, stride)
+ * (glcPlanSetContainerFilterByte), and their sum.  Zeros before the first and with the setting off. */
+CUDPPResult glcContainerLastByteFilters(CUDPPHandle plan, unsigned long long out[3]);
 
 /* {what, frame, block} of the plan's last container failure (what = GlcContainerError; frame / block = ~0 where the
  * failure is not tied to one).  A successful call resets it to {0, ~0, ~0}. */

@@ -65,6 +65,8 @@ codec with the auto mode on under filter-auto (format version 10), under filter-
 version 13: the lag probe per frame, the lag picked per frame) and under the plan set by hand to the data's element size, lag L and
 the fold (format version 11), interleaved, with the filter-auto section's output and what glcContainerLastLagFilters reports.
 
+--filter-byte (with --byte-delta LAG,STRIDE and --data grey8 or rgb8; --rounds R, at least 1) is the filter-byte section: the order-0
+container under filter-grid (format version 14), under filter-byte (format version 16) and with LAG and STRIDE set by hand (version 15).
 --byte-delta LAG,STRIDE (with --data grey8 or rgb8 of tests/byte_delta_inputs.py -- about 32 MiB of whole rows of STRIDE bytes
 generated on the host and repeated; STRIDE 0: rows of 721 pixels --, or any other kind; --rounds R, at least 1) is the byte section:
 the order-0 codec with the auto mode on and no filter (format version 8) and with the byte predictor at (LAG, STRIDE)
@@ -73,7 +75,7 @@ which is also what a build without the setting can run.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
                                 [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid] |
-                                 --byte-delta LAG,STRIDE]"""
+                                 --byte-delta LAG,STRIDE [--filter-byte]]"""
 import argparse
 import json
 import os
@@ -643,6 +645,63 @@ def byte_section(torch, glc, plan, d_in, total, lag, stride, rounds):
     return res
 
 
+def filter_byte_section(torch, glc, plan, d_in, total, lag, stride, rounds):
+    """the order-0 container with the auto mode on under "filter_grid" (format version 14), "filter_byte" (format version 16: the
+    byte probe behind the grid probe, the byte predictor's lag and row stride found per frame) and "hand" (format version 15: the
+    byte predictor at (lag, stride) set by hand, no probe), interleaved: `rounds` rounds of one encode and one decode per setting
+    after one untimed round, each timed with device events on the plan's (the default) stream"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    settings = ["filter_grid", "filter_byte", "hand"]
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+    glc.container_set_auto(plan, 1)
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s in settings:
+            glc.container_set_filter_auto(plan, 0)             # (filter-lag, filter-grid and filter-byte go off with it)
+            glc.container_set_byte_delta(plan, 0, 0)
+            if s == "hand":
+                glc.container_set_byte_delta(plan, lag, stride)
+            else:
+                glc.container_set_filter_auto(plan, 1)
+                glc.container_set_filter_lag(plan, 1)
+                glc.container_set_filter_grid(plan, 1)
+                glc.container_set_filter_byte(plan, 1 if s == "filter_byte" else 0)
+            t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+                plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+                plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
+                res[s]["version"] = int(cont[4].item()) | int(cont[5].item()) << 8
+                res[s]["frames_per_filter"] = list(glc.container_last_filters(plan))
+                res[s]["frames_per_grid_filter"] = list(glc.container_last_grid_filters(plan))
+                res[s]["frames_per_byte_filter"] = list(glc.container_last_byte_filters(plan))
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    res["working_set_bytes"] = {"input": total, "container_capacity": cap, "output": total}
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gib", type=float, default=4.0)
@@ -673,6 +732,8 @@ def main():
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
     ap.add_argument("--byte-delta", default=None, metavar="LAG,STRIDE",
                     help="the byte section (format version 15): the byte predictor's lag, 0 (off only) to 16, and row stride, 0 or 2 to 65536")
+    ap.add_argument("--filter-byte", action="store_true",
+                    help="the filter-byte section (format version 16): filter-grid, filter-grid with bytes, and --byte-delta set by hand")
     args = ap.parse_args()
     byte_delta = tuple(int(v) for v in args.byte_delta.split(",")) if args.byte_delta else None
     assert byte_delta is None or len(byte_delta) == 2, "--byte-delta LAG,STRIDE"
@@ -753,6 +814,14 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             res["runs"] = runs_section(torch, glc, plan, d_in, total, max(1, args.rounds), args.runs)
+        print(json.dumps(res))
+        return
+    if args.filter_byte:
+        assert byte_delta and byte_delta[0], "--filter-byte compares with the plan set by hand: give its --byte-delta LAG,STRIDE"
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            glc.container_set_codec(plan, 1)
+            res["filter_byte"] = filter_byte_section(torch, glc, plan, d_in, total, byte_delta[0], byte_delta[1], max(1, args.rounds))
         print(json.dumps(res))
         return
     if byte_delta:
