@@ -349,28 +349,15 @@ struct Encoder {
         }
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
         if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
-        if (codec == CT_CODEC_CHOOSE) CT_HIP(glc_host_alloc((void **)&h_stats, 8 * CHOOSE_STATS * (size_t)P.rows));
-        if (filter_auto) CT_HIP(glc_host_alloc((void **)&h_costs, 8 * FP_HOST_WORDS));
+        if (codec == CT_CODEC_CHOOSE) CT_HIP(plan_pinned_scratch(P.h, CT_PIN_STATS, 8 * CHOOSE_STATS * (size_t)P.rows, (void **)&h_stats));
+        if (filter_auto) CT_HIP(plan_pinned_scratch(P.h, CT_PIN_COSTS, 8 * FP_HOST_WORDS, (void **)&h_costs));
         if (fmt.filtered() || filter_auto) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
             for (int i = 0; i < nstage; i++) CT_HIP(plan_stage(P.h, i, (size_t)P.rows * P.n, &stage[i]));
             if (nstage == 1) stage[1] = stage[0];
         }
-        CT_HIP(carve_on(
-            [&](size_t bytes, void **base) {
-                const hipError_t e = glc_dev_alloc(&mem, bytes);
-                if (e != hipSuccess) mem = nullptr;
-                *base = mem;
-                return e;
-            },
-            [&](Carver &c) { carve(c); }));
+        CT_HIP(carve_on(codec_scratch(P.h, CT_DEV_ENC_TABLES), [&](Carver &c) { carve(c); }));   // (the plan's: nothing is freed here)
         return filter_auto ? hipMemsetAsync(fp_seg, 0, 8, P.st) : hipSuccess;
-    }
-    ~Encoder()
-    {
-        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); }
-        if (h_stats) (void)hipHostFree(h_stats);
-        if (h_costs) (void)hipHostFree(h_costs);
     }
 
     // filter-auto: the probe of the frame where it lies, its seven costs read back with one wait (as the CHOOSE codec reads its
@@ -795,12 +782,6 @@ struct Decoder {
         return carve_on(codec_scratch(P.h, 1), [&](Carver &c) { carve_huff0(c, nb, blk_len); });
     }
 
-    ~Decoder()
-    {
-        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); }
-        if (state) { (void)hipStreamSynchronize(P.st); (void)hipFree(state); }
-        if (h_verdict) (void)hipHostFree(h_verdict);
-    }
     static size_t verdict_words(uint32_t nb) { return 2 + ((size_t)nb + 1) / 2; }
     void carve(Carver &c, uint32_t nb)
     {
@@ -813,13 +794,13 @@ struct Decoder {
     hipError_t reserve(uint32_t nb)
     {
         if (nb <= cap_nb && mem) return hipSuccess;
-        if (mem) { (void)hipStreamSynchronize(P.st); (void)hipFree(mem); mem = nullptr; }
-        if (h_verdict) { (void)hipHostFree(h_verdict); h_verdict = nullptr; }
+        // the plan's tables and pinned words (a larger frame in the same call: the plan waits for its stream before it lets the
+        // old ones go)
         CT_HIP(carve_on(
             [&](size_t bytes, void **base) {
-                hipError_t e = glc_dev_alloc(&mem, bytes);
+                hipError_t e = plan_codec_scratch(P.h, CT_DEV_DEC_TABLES, bytes, reinterpret_cast<uint8_t **>(&mem));
                 if (e != hipSuccess) { mem = nullptr; return e; }
-                e = glc_host_alloc((void **)&h_verdict, 8 * verdict_words(nb));
+                e = plan_pinned_scratch(P.h, CT_PIN_VERDICT, 8 * verdict_words(nb), (void **)&h_verdict);
                 if (e != hipSuccess) h_verdict = nullptr;
                 *base = mem;
                 return e;
@@ -830,7 +811,7 @@ struct Decoder {
     }
     hipError_t begin()
     {
-        hipError_t e = glc_dev_alloc((void **)&state, sizeof(CtDecState));
+        hipError_t e = plan_codec_scratch(P.h, CT_DEV_DEC_STATE, sizeof(CtDecState), reinterpret_cast<uint8_t **>(&state));
         if (e != hipSuccess) { state = nullptr; return e; }
         e = hipMemsetAsync(state, 0, sizeof(CtDecState), P.st);
         if (e == hipSuccess) e = hipMemsetAsync(&state->err, 0xFF, 8, P.st);
@@ -1016,29 +997,28 @@ struct FileSink : Sink {
     bool write(const void *src, size_t n) override { return fwrite(src, 1, n, f) == n; }
 };
 
+// staging of the host-pointer and file forms: views of the plan's grow-only slots (nothing is freed by a call)
 struct Pinned {
+    CUDPPHandle plan; uint32_t slot;
     void *p = nullptr; size_t n = 0;
-    ~Pinned() { if (p) (void)hipHostFree(p); }
+    Pinned(CUDPPHandle h, uint32_t s) : plan(h), slot(s) {}
     hipError_t reserve(size_t m)
     {
         if (m <= n) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = glc_host_alloc(&p, m);
-        if (e == hipSuccess) n = m;
+        const hipError_t e = plan_pinned_scratch(plan, slot, m, &p);
+        if (e == hipSuccess) n = m; else { p = nullptr; n = 0; }
         return e;
     }
 };
 struct DevBuf {
+    CUDPPHandle plan; uint32_t slot;
     void *p = nullptr; size_t n = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
+    DevBuf(CUDPPHandle h, uint32_t s) : plan(h), slot(s) {}
     hipError_t reserve(size_t m)
     {
         if (m <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; n = 0;
-        hipError_t e = glc_dev_alloc(&p, m);
-        if (e == hipSuccess) n = m;
+        const hipError_t e = plan_codec_scratch(plan, slot, m, reinterpret_cast<uint8_t **>(&p));
+        if (e == hipSuccess) n = m; else { p = nullptr; n = 0; }
         return e;
     }
 };
@@ -1051,8 +1031,8 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
     if (!E.P.ok(plan)) return CUDPP_ERROR_INVALID_PLAN;
     CT_TRY(E.init());
     const unsigned long long fmax = (unsigned long long)E.P.n * E.P.rows;
-    Pinned hin[2], hout;
-    DevBuf din[2], dout;
+    Pinned hin[2] = {{plan, CT_PIN_IN0}, {plan, CT_PIN_IN1}}, hout{plan, CT_PIN_OUT};
+    DevBuf din[2] = {{plan, CT_DEV_IN0}, {plan, CT_DEV_IN1}}, dout{plan, CT_DEV_OUT};
     const size_t inb = (size_t)std::min(fmax, std::max(len, 1ull));
     for (int i = 0; i < 2; i++) { CT_TRY(hin[i].reserve(inb)); CT_TRY(din[i].reserve(inb)); }
     // (a last chunk: blocks + tail; with the CHOOSE codec a chunk may come out as one frame per block)
@@ -1099,7 +1079,8 @@ CUDPPResult compress_stream(CUDPPHandle plan, Source &src, unsigned long long le
         CT_TRY(hipMemcpyAsync(&fb, &E.state->cursor, 8, hipMemcpyDeviceToHost, E.P.st));
         CT_TRY(hipStreamSynchronize(E.P.st));
         if (fb > ocap) return fail(plan, CT_CAPACITY);
-        CT_TRY(hipMemcpy(hout.p, dout.p, fb, hipMemcpyDeviceToHost));
+        CT_TRY(hipMemcpyAsync(hout.p, dout.p, fb, hipMemcpyDeviceToHost, E.P.st));   // (on the plan's stream: hipMemcpy goes through stream 0)
+        CT_TRY(hipStreamSynchronize(E.P.st));
         if (!out.write(hout.p, fb)) return fail(plan, CT_CAPACITY);
         total += fb;
     }
@@ -1195,7 +1176,8 @@ struct StreamFeed : Feed {
     Sink &sink;
     Pinned hf, ho;
     DevBuf df, dob;
-    StreamFeed(CUDPPHandle p, hipStream_t s, Source &i, Sink &o) : plan(p), st(s), src(i), sink(o) {}
+    StreamFeed(CUDPPHandle p, hipStream_t s, Source &i, Sink &o)
+        : plan(p), st(s), src(i), sink(o), hf(p, CT_PIN_IN0), ho(p, CT_PIN_OUT), df(p, CT_DEV_IN0), dob(p, CT_DEV_OUT) {}
     CUDPPResult header(void *dst, unsigned long long, size_t n, unsigned long long frame) override
     {
         return src.read(dst, n) ? CUDPP_SUCCESS : fail(plan, CT_TRUNCATED, frame);
@@ -1203,7 +1185,10 @@ struct StreamFeed : Feed {
     CUDPPResult frame(const uint32_t fh[8], unsigned long long, unsigned long long fb, unsigned long long, size_t ob, uint32_t fi,
                       const uint8_t **fr, uint8_t **o) override
     {
-        CT_TRY(hf.reserve(fb)); CT_TRY(df.reserve(fb));
+        // room for the worst frame of this one's shape (fh[1] blocks of fh[2] bytes, all stored raw), not for its own bytes alone:
+        // the next stream of the same shape, however it compresses, then finds the staging large enough and nothing is freed
+        const size_t room = (size_t)std::max(fb, frame_bound(fh[1], fh[2]));
+        CT_TRY(hf.reserve(room)); CT_TRY(df.reserve(room));
         CT_TRY(ho.reserve(ob)); CT_TRY(dob.reserve(ob));
         memcpy(hf.p, fh, CT_FRAME_HDR);
         if (!src.read(static_cast<uint8_t *>(hf.p) + CT_FRAME_HDR, fb - CT_FRAME_HDR)) return fail(plan, CT_TRUNCATED, fi);
@@ -1370,7 +1355,8 @@ struct HostRangeIO : RangeIO {
     uint8_t *out;
     Pinned hf, ho;
     DevBuf df;
-    HostRangeIO(hipStream_t s, RandomSource &i, void *o) : st(s), src(i), out(static_cast<uint8_t *>(o)) {}
+    HostRangeIO(CUDPPHandle p, hipStream_t s, RandomSource &i, void *o)
+        : st(s), src(i), out(static_cast<uint8_t *>(o)), hf(p, CT_PIN_IN0), ho(p, CT_PIN_OUT), df(p, CT_DEV_IN0) {}
     CUDPPResult small(void *dst, unsigned long long pos, size_t n) override { return src.at(dst, pos, n) ? CUDPP_SUCCESS : CUDPP_ERROR_UNKNOWN; }
     CUDPPResult frame(unsigned long long pos, unsigned long long fb, const uint8_t **fr, uint32_t fh[8]) override
     {
@@ -1602,7 +1588,7 @@ CUDPPResult glcContainerReadRange(CUDPPHandle plan, const GlcContainerIndex *ind
     if (const CUDPPResult bad = D.P.check(plan)) return bad;
     if (!in || (count && !out)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     MemRandom src(in, len);
-    HostRangeIO io(D.P.st, src, out);
+    HostRangeIO io(D.P.h, D.P.st, src, out);
     return read_range(D, index, io, len, offset, count);
 }
 
@@ -1613,7 +1599,7 @@ CUDPPResult glcContainerReadRangeFile(CUDPPHandle plan, const GlcContainerIndex 
     if (const CUDPPResult bad = D.P.check(plan)) return bad;
     FileRandom src(path);
     if (src.fd < 0 || (count && !out)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    HostRangeIO io(D.P.st, src, out);
+    HostRangeIO io(D.P.h, D.P.st, src, out);
     return read_range(D, index, io, src.len, offset, count);
 }
 

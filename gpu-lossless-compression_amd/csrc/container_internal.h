@@ -828,6 +828,13 @@ void plan_wait_released(CUDPPHandle plan);
 // by a plan that only uses the BWT codec), the plan's live kernel profile, and its stage events (i = 0 .. 3: the marks of
 // glcPlanLastTiming's four spans, recorded on the plan's stream; a no-op while timing is off)
 hipError_t plan_codec_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, uint8_t **out);
+// Grow-only memory the plan keeps for what a container call needs beside the codecs' scratch: a call that has run once on
+// inputs of its size allocates and frees nothing.  Device slots continue plan_codec_scratch's numbering; pinned slots are
+// plan_pinned_scratch's.  The encoder and the decoder never share a slot (a range read decodes while an index lives), the
+// host-pointer / file forms' staging is shared between the two directions (one call at a time on a plan).
+enum CtDevSlot : uint32_t { CT_DEV_ENC_TABLES = 3, CT_DEV_DEC_TABLES, CT_DEV_DEC_STATE, CT_DEV_IN0, CT_DEV_IN1, CT_DEV_OUT, CT_DEV_SLOTS };
+enum CtPinSlot : uint32_t { CT_PIN_STATS = 0, CT_PIN_COSTS, CT_PIN_VERDICT, CT_PIN_IN0, CT_PIN_IN1, CT_PIN_OUT, CT_PIN_SLOTS };
+hipError_t plan_pinned_scratch(CUDPPHandle plan, uint32_t which, size_t bytes, void **out);
 KernelProf *plan_prof(CUDPPHandle plan);
 void plan_stage_mark(CUDPPHandle plan, int i);
 // the runs mode's two ends of the plan's BWT codec, wholly on the plan's stream (the side stream is joined first).  Encode: the

@@ -125,6 +125,28 @@ struct GrowBuf {
     }
     ~GrowBuf() { if (mem) (void)hipFree(mem); }
 };
+// ... and the pinned host memory it keeps for the same path (readback words, the host-pointer and file forms' staging)
+struct GrowPinned {
+    void *mem = nullptr;
+    size_t bytes = 0;
+    hipError_t grow(PlanBase &p, size_t want, void **out)
+    {
+        if (want > bytes) {
+            if (mem) {                                         // (growing: a copy into or out of the old one finishes first)
+                p.join_side();
+                (void)hipStreamSynchronize(p.stream);
+                (void)hipHostFree(mem);
+                mem = nullptr; bytes = 0;
+            }
+            const hipError_t e = glc_host_alloc(&mem, want);
+            if (e != hipSuccess) { mem = nullptr; return e; }
+            bytes = want;
+        }
+        *out = mem;
+        return hipSuccess;
+    }
+    ~GrowPinned() { if (mem) (void)hipHostFree(mem); }
+};
 
 struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_plan.h:307-341)
     SaScratch sa;
@@ -148,7 +170,8 @@ struct CompressPlan : PlanBase {                 // CUDPPCompressPlan (cudpp_pla
     CtSettings ct;
     CtReports ct_reports;                        // what the glcContainerLast* entries report
     GrowBuf ct_stage[2];
-    GrowBuf ct_codec[3];                         // the order-0 container codec's scratch, its sparse and rANS modes' and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries
+    GrowBuf ct_codec[CT_DEV_SLOTS];              // the order-0 container codec's scratch, its sparse and rANS modes' and the runs mode's included: [0] the encoder's, [1] the decoder's; [2] the frame index walk's entries; from [3] on the slots of container_internal.h (CtDevSlot): what a container call used to allocate and free itself -- hipFree waits for the whole device, so a call that frees serialises against every stream of the caller's
+    GrowPinned ct_pinned[CT_PIN_SLOTS];          // CtPinSlot: the readback words and the host forms' staging
     SaScratch *sorter() override { return &sa; }
     void wire_prof() override { sa.prof = &prof; mtf.prof = &prof; huff.prof = &prof; dec.prof = &prof; }
     hipEvent_t side_span_start() override { return pipelined ? ev_s2 : nullptr; }
@@ -920,6 +943,12 @@ hipError_t plan_codec_scratch(CUDPPHandle planHandle, uint32_t which, size_t byt
 {
     CompressPlan *p = plan_from<CompressPlan>(planHandle);
     return p->ct_codec[which].grow(*p, bytes, out);
+}
+
+hipError_t plan_pinned_scratch(CUDPPHandle planHandle, uint32_t which, size_t bytes, void **out)
+{
+    CompressPlan *p = plan_from<CompressPlan>(planHandle);
+    return p->ct_pinned[which].grow(*p, bytes, out);
 }
 
 KernelProf *plan_prof(CUDPPHandle planHandle) { return &plan_from<CompressPlan>(planHandle)->prof; }

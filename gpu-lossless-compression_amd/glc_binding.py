@@ -579,7 +579,7 @@ def hd_decode_device(d_units, lens, codes, nsym, stream=None):
     work = torch.empty(lib().glcHdWorkBytes(nunits), dtype=torch.uint8, device=d_units.device)
     out = torch.empty(max(1, nsym), dtype=torch.uint8, device=d_units.device)
     ok = lib().glcHdDecodeDevice(d_units.data_ptr(), nunits, lens.ctypes.data, codes.ctypes.data,
-                                 out.data_ptr(), nsym, work.data_ptr(), stream)
+                                 out.data_ptr(), nsym, work.data_ptr(), _stream_ptr(stream))
     if not ok:
         raise HdError("glcHdDecodeDevice failed")
     return out[:nsym]
@@ -1109,14 +1109,47 @@ def container_get_dedup(plan):
     return _get_uint("glcPlanGetContainerDedup", plan)
 
 
-def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None, stream=None):
+# --- the segment helpers ------------------------------------------------------------------------------------------------------
+# The *Segments entries only enqueue on `stream` (None, a raw hipStream_t or a torch.cuda.Stream).  The helpers below upload the
+# segment lists and allocate work memory per call, so by default each ends with a wait for the whole device, behind which those
+# temporaries may die.  A caller that wants the entry's own behaviour -- nothing but the enqueue, on its stream -- passes
+# keep=[...]: the helper then does not wait and appends its temporaries to the list, which the caller holds until it has
+# synchronised; and it passes offsets / lengths / fills as SegmentList, uploaded ahead of the call, so that the helper copies
+# nothing either (a copy from pageable memory waits for the stream it is queued on).
+class SegmentList(list):
+    """a list of segment offsets, lengths or fill bytes together with its device copy (`tensor`), made here"""
+
+    def __init__(self, values, device, dtype=None):
+        import torch
+        super().__init__(int(v) for v in values)
+        self.tensor = torch.as_tensor(list(self), dtype=torch.int64 if dtype is None else dtype).to(device)
+
+
+def _seg_tensor(values, dtype, dev):
+    import torch
+    t = getattr(values, "tensor", None)
+    if t is None:
+        return torch.as_tensor(values, dtype=dtype).to(dev)
+    assert t.dtype == dtype and t.device == torch.device(dev), "a SegmentList of another type or device"
+    return t
+
+
+def _seg_done(dev, keep, *temps):
+    import torch
+    if keep is None:
+        torch.cuda.synchronize(dev)                            # (the temporaries of the call die behind it)
+    else:
+        keep.extend(temps)
+
+
+def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None, stream=None, keep=None):
     """the probe of the auto mode over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in:
     (hist, uniform), int32 tensors [count, 256] -- the byte counts, and per byte value the 64-byte chunks (cut from the segment's
     start) made of that byte alone.  hist / uniform: tensors to write into (they need not be zeroed)."""
     import torch
     dev = d_in.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     n = off.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
@@ -1124,26 +1157,26 @@ def probe_segments(d_in, offsets, lengths, max_len=None, hist=None, uniform=None
     uniform = torch.empty((max(1, n), 256), dtype=torch.int32, device=dev) if uniform is None else uniform
     assert hist.is_contiguous() and uniform.is_contiguous() and hist.numel() >= 256 * n and uniform.numel() >= 256 * n
     _chk("glcProbeSegments", _ct().glcProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, hist.data_ptr(),
-                                                     uniform.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                     uniform.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return hist[:n], uniform[:n]
 
 
-def bigram_probe_segments(d_in, offsets, lengths, max_len=None, stats=None, stream=None):
+def bigram_probe_segments(d_in, offsets, lengths, max_len=None, stats=None, stream=None, keep=None):
     """the bigram probe of CONTAINER_CODEC_CHOOSE over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8
     tensor d_in: an int64 tensor [count, 4] of rows {S2, SR, SC, M} (csrc/choose_rule.h).  stats: a tensor to write into."""
     import torch
     dev = d_in.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     n = off.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
     stats = torch.empty((max(1, n), 4), dtype=torch.int64, device=dev) if stats is None else stats
     assert stats.is_contiguous() and stats.dtype == torch.int64 and stats.numel() >= 4 * n
     _chk("glcBigramProbeSegments", _ct().glcBigramProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
-                                                                 stats.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                                 stats.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return stats[:n]
 
 
@@ -1151,15 +1184,15 @@ FILTER_PROBE_ROWS, FILTER_CANDIDATES, FILTER_PROBE_MAX_LEN = 22, 7, 1 << 31
 FILTER_CANDS = ((1, 0), (2, 0), (2, 1), (4, 0), (4, 1), (8, 0), (8, 1))     # (elem, delta) in the rule's order; (1, 0): no filter
 
 
-def filter_probe_segments(d_in, offsets, lengths, max_len=None, planes=None, costs=None, stream=None):
+def filter_probe_segments(d_in, offsets, lengths, max_len=None, planes=None, costs=None, stream=None, keep=None):
     """the filter probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (planes,
     costs) -- an int32 tensor [count, 22, 256] of the histograms A_0..7, D_2, D_4 and D_8 of each segment's first L - L % 8 bytes,
     and an int64 tensor [count, 7] of the candidates' costs in the order of FILTER_CANDS (csrc/filter_rule.h).  planes / costs:
     tensors to write into (they need not be zeroed)."""
     import torch
     dev = d_in.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     n = off.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
@@ -1168,8 +1201,8 @@ def filter_probe_segments(d_in, offsets, lengths, max_len=None, planes=None, cos
     assert planes.is_contiguous() and costs.is_contiguous() and costs.dtype == torch.int64
     assert planes.numel() >= FILTER_PROBE_ROWS * 256 * n and costs.numel() >= FILTER_CANDIDATES * n
     _chk("glcFilterProbeSegments", _ct().glcFilterProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
-                                                                 planes.data_ptr(), costs.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                                 planes.data_ptr(), costs.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return planes[:n], costs[:n]
 
 
@@ -1179,13 +1212,13 @@ LAG_PROBE_SUMS, LAG_PROBE_ROWS, LAG_PROBE_MAX_LAG = 48, 14, 16
 def _lag_probe_args(d_in, offsets, lengths, max_len):
     import torch
     dev = d_in.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     return dev, off, ln, off.numel(), int(max(lengths, default=0)) if max_len is None else int(max_len)
 
 
-def lag_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, lags=None, stream=None):
+def lag_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, lags=None, stream=None, keep=None):
     """the lag probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (sums, lags) --
     an int64 tensor [count, 48] of the bit lengths S[e][l] of the folded differences at element size e = 2, 4, 8 and lag
     l = 1 .. 16 (row (log2 e - 1) * 16 + l - 1) over each segment's first L - L % 8 bytes, and an int32 tensor [count, 3] of the
@@ -1197,12 +1230,12 @@ def lag_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, lags=Non
     assert sums.is_contiguous() and lags.is_contiguous() and sums.dtype == torch.int64 and lags.dtype == torch.int32
     assert sums.numel() >= LAG_PROBE_SUMS * n and lags.numel() >= 3 * n
     _chk("glcLagProbeSegments", _ct().glcLagProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
-                                                           sums.data_ptr(), lags.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                           sums.data_ptr(), lags.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return sums[:n], lags[:n]
 
 
-def lag_planes_segments(d_in, offsets, lengths, lags, max_len=None, planes=None, costs=None, stream=None):
+def lag_planes_segments(d_in, offsets, lengths, lags, max_len=None, planes=None, costs=None, stream=None, keep=None):
     """the plane probe of the lag rule over the same segments at the lags of the device int32 tensor `lags` [count, 3] (each word
     used as ((v - 1) & 15) + 1): (planes, costs) -- an int32 tensor [count, 14, 256] of the histograms E_2, E_4 and E_8 and an
     int64 tensor [count, 3] of their costs.  planes / costs: tensors to write into (they need not be zeroed)."""
@@ -1214,15 +1247,15 @@ def lag_planes_segments(d_in, offsets, lengths, lags, max_len=None, planes=None,
     assert lags.is_contiguous() and lags.dtype == torch.int32 and lags.numel() >= 3 * n
     assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
     _chk("glcLagPlanesSegments", _ct().glcLagPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, lags.data_ptr(),
-                                                             planes.data_ptr(), costs.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                             planes.data_ptr(), costs.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return planes[:n], costs[:n]
 
 
 GRID_PROBE_ROW, GRID_PROBE_SUMS = 65537, 3 * 65537
 
 
-def grid_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, widths=None, stream=None):
+def grid_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, widths=None, stream=None, keep=None):
     """the grid probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (sums, widths) --
     an int32 tensor [count, 3 * 65537] whose word k * 65537 + W is S_e[W] for e = 2 << k (the bit pattern 0xFFFFFFFF, so -1, where W
     is no candidate), and an int32 tensor [count, 3] of the width with the smallest sum per element size, 0 where there is none
@@ -1234,12 +1267,12 @@ def grid_probe_segments(d_in, offsets, lengths, max_len=None, sums=None, widths=
     assert sums.is_contiguous() and widths.is_contiguous() and sums.dtype == torch.int32 and widths.dtype == torch.int32
     assert sums.numel() >= GRID_PROBE_SUMS * n and widths.numel() >= 3 * n
     _chk("glcGridProbeSegments", _ct().glcGridProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
-                                                             sums.data_ptr(), widths.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                             sums.data_ptr(), widths.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return sums[:n], widths[:n]
 
 
-def grid_planes_segments(d_in, offsets, lengths, widths, max_len=None, planes=None, costs=None, stream=None):
+def grid_planes_segments(d_in, offsets, lengths, widths, max_len=None, planes=None, costs=None, stream=None, keep=None):
     """the plane probe of the grid rule over the same segments at the widths of the device int32 tensor `widths` [count, 3] (a
     word outside 2..65536 names no width: zero rows and the cost 2^56): (planes, costs) -- an int32 tensor [count, 14, 256] and an
     int64 tensor [count, 3].  planes / costs: tensors to write into (they need not be zeroed)."""
@@ -1251,15 +1284,15 @@ def grid_planes_segments(d_in, offsets, lengths, widths, max_len=None, planes=No
     assert widths.is_contiguous() and widths.dtype == torch.int32 and widths.numel() >= 3 * n
     assert planes.numel() >= LAG_PROBE_ROWS * 256 * n and costs.numel() >= 3 * n
     _chk("glcGridPlanesSegments", _ct().glcGridPlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, widths.data_ptr(),
-                                                               planes.data_ptr(), costs.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                               planes.data_ptr(), costs.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return planes[:n], costs[:n]
 
 
 BYTE_PROBE_LAGS, BYTE_PROBE_ROW, BYTE_PROBE_ROWS = 16, 65537, 2
 
 
-def byte_probe_segments(d_in, offsets, lengths, max_len=None, lag_sums=None, stride_sums=None, winners=None, stream=None):
+def byte_probe_segments(d_in, offsets, lengths, max_len=None, lag_sums=None, stride_sums=None, winners=None, stream=None, keep=None):
     """the byte probe over the segments [offsets[i], + min(lengths[i], max_len)) of the device uint8 tensor d_in: (lag_sums,
     stride_sums, winners) -- an int64 tensor [count, 16] of the magnitudes A[l] of the byte differences at lag l = 1 .. 16 over each
     segment's first L - L % 8 bytes, an int32 tensor [count, 65537] whose word W is S[W] for the row strides 17 .. Wmax (the bit
@@ -1274,12 +1307,12 @@ def byte_probe_segments(d_in, offsets, lengths, max_len=None, lag_sums=None, str
     assert lag_sums.dtype == torch.int64 and stride_sums.dtype == torch.int32 and winners.dtype == torch.int32
     assert lag_sums.numel() >= BYTE_PROBE_LAGS * n and stride_sums.numel() >= BYTE_PROBE_ROW * n and winners.numel() >= 2 * n
     _chk("glcByteProbeSegments", _ct().glcByteProbeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len,
-                                                             lag_sums.data_ptr(), stride_sums.data_ptr(), winners.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                             lag_sums.data_ptr(), stride_sums.data_ptr(), winners.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return lag_sums[:n], stride_sums[:n], winners[:n]
 
 
-def byte_planes_segments(d_in, offsets, lengths, words, max_len=None, planes=None, costs=None, stream=None):
+def byte_planes_segments(d_in, offsets, lengths, words, max_len=None, planes=None, costs=None, stream=None, keep=None):
     """the plane probe of the byte rule over the same segments at the {lag, stride} words of the device int32 tensor `words`
     [count, 2] (the lag used as ((v - 1) & 15) + 1; a stride outside 17..65536 names none: a zero row and the cost 2^56):
     (planes, costs) -- an int32 tensor [count, 2, 256], the histograms of the byte predictor's output at (lag, 0) and at (lag,
@@ -1292,8 +1325,8 @@ def byte_planes_segments(d_in, offsets, lengths, words, max_len=None, planes=Non
     assert words.is_contiguous() and words.dtype == torch.int32 and words.numel() >= 2 * n
     assert planes.numel() >= BYTE_PROBE_ROWS * 256 * n and costs.numel() >= BYTE_PROBE_ROWS * n
     _chk("glcBytePlanesSegments", _ct().glcBytePlanesSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, words.data_ptr(),
-                                                               planes.data_ptr(), costs.data_ptr(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+                                                               planes.data_ptr(), costs.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return planes[:n], costs[:n]
 
 
@@ -1309,60 +1342,62 @@ def ans_work_bytes(count, max_len):
 def _ans_args(d_base, offsets, lengths, max_len):
     import torch
     dev = d_base.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
     work = torch.empty(max(16, ans_work_bytes(off.numel(), max_len)), dtype=torch.uint8, device=dev)
     return off, ln, max_len, work
 
 
-def ans_encode_segments(d_in, offsets, lengths, max_len=None, stream=None):
+def ans_encode_segments(d_in, offsets, lengths, max_len=None, stream=None, keep=None, rec_off=None):
     """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in as rANS records (format version 7, kind 5).
     Returns (hist int32 tensor [count, 256], records int32 tensor, record word offsets (list), record words int64 tensor
     [count]); record i is records[rec_off[i] : rec_off[i] + words[i]]"""
     import torch
     off, ln, max_len, work = _ans_args(d_in, offsets, lengths, max_len)
     n = off.numel()
-    rec_off, total = [], 0
+    offs, total = [], 0
     for l in lengths:
-        rec_off.append(total)
+        offs.append(total)
         total += ans_bound_words(min(int(l), max_len))
-    ro = torch.as_tensor(rec_off, dtype=torch.int64).to(d_in.device)
+    assert rec_off is None or list(rec_off) == offs            # (rec_off: these offsets as a SegmentList, uploaded ahead of the call)
+    rec_off = offs if rec_off is None else rec_off
+    ro = _seg_tensor(rec_off, torch.int64, d_in.device)
     hist = torch.zeros((max(1, n), 256), dtype=torch.int32, device=d_in.device)
     rec = torch.zeros(max(1, total), dtype=torch.int32, device=d_in.device)
     words = torch.zeros(max(1, n), dtype=torch.int64, device=d_in.device)
     _chk("glcAnsEncodeSegments", _ct().glcAnsEncodeSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), n, max_len, hist.data_ptr(),
                                                              rec.data_ptr(), ro.data_ptr(), words.data_ptr(), work.data_ptr(),
-                                                             work.numel(), stream))
-    torch.cuda.synchronize(d_in.device)                        # (off / ln / ro / work are temporaries of this call)
+                                                             work.numel(), _stream_ptr(stream)))
+    _seg_done(d_in.device, keep, off, ln, ro, work)
     return hist[:n], rec, rec_off, words[:n]
 
 
-def ans_decode_segments(rec, rec_off, words, hist, d_out, offsets, lengths, max_len=None, stream=None):
+def ans_decode_segments(rec, rec_off, words, hist, d_out, offsets, lengths, max_len=None, stream=None, keep=None):
     """the inverse of ans_encode_segments into the device uint8 tensor d_out; tolerant of whatever rec and words hold"""
     import torch
     off, ln, max_len, work = _ans_args(d_out, offsets, lengths, max_len)
-    ro = torch.as_tensor(rec_off, dtype=torch.int64).to(d_out.device)
-    wd = torch.as_tensor(words, dtype=torch.int64).to(d_out.device)
+    ro = _seg_tensor(rec_off, torch.int64, d_out.device)
+    wd = _seg_tensor(words, torch.int64, d_out.device)
     h = hist.contiguous()
     assert ro.numel() == wd.numel() == off.numel() and h.numel() == 256 * off.numel()
     _chk("glcAnsDecodeSegments", _ct().glcAnsDecodeSegments(rec.data_ptr(), ro.data_ptr(), wd.data_ptr(), h.data_ptr(), off.data_ptr(),
                                                              ln.data_ptr(), off.numel(), max_len, d_out.data_ptr(), work.data_ptr(),
-                                                             work.numel(), stream))
-    torch.cuda.synchronize(d_out.device)
+                                                             work.numel(), _stream_ptr(stream)))
+    _seg_done(d_out.device, keep, off, ln, ro, wd, h, work)
     return d_out
 
 
 def _zerorun_args(d_base, offsets, lengths):
     import torch
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(d_base.device)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(d_base.device)
+    off = _seg_tensor(offsets, torch.int64, d_base.device)
+    ln = _seg_tensor(lengths, torch.int64, d_base.device)
     assert off.numel() == ln.numel()
     return off, ln
 
 
-def zerorun_split_segments(d_in, d_a, d_b, offsets, lengths, max_len=None, stream=None):
+def zerorun_split_segments(d_in, d_a, d_b, offsets, lengths, max_len=None, stream=None, keep=None):
     """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in split into A (non-zero bytes and one zero per run
     of zeros, a run ending at a 256-byte tile edge) at d_a + offsets[i] and B (run lengths minus one) at d_b + offsets[i].
     Returns (A lengths, B lengths), int64 tensors [count]"""
@@ -1372,22 +1407,22 @@ def zerorun_split_segments(d_in, d_a, d_b, offsets, lengths, max_len=None, strea
     alen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
     blen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
     _chk("glcZeroRunSplitSegments", _ct().glcZeroRunSplitSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
-                                                                   d_a.data_ptr(), d_b.data_ptr(), alen.data_ptr(), blen.data_ptr(), stream))
-    torch.cuda.synchronize(d_in.device)                        # (off / ln are temporaries of this call)
+                                                                   d_a.data_ptr(), d_b.data_ptr(), alen.data_ptr(), blen.data_ptr(), _stream_ptr(stream)))
+    _seg_done(d_in.device, keep, off, ln)
     return alen[:off.numel()], blen[:off.numel()]
 
 
-def zerorun_join_segments(d_a, d_b, d_out, offsets, a_lengths, b_lengths, lengths, max_len=None, stream=None):
+def zerorun_join_segments(d_a, d_b, d_out, offsets, a_lengths, b_lengths, lengths, max_len=None, stream=None, keep=None):
     """the inverse of zerorun_split_segments; tolerant of streams that do not fit each other (see include/glc_container.h)"""
     import torch
     off, ln = _zerorun_args(d_out, offsets, lengths)
-    al = torch.as_tensor(a_lengths, dtype=torch.int64).to(d_out.device)
-    bl = torch.as_tensor(b_lengths, dtype=torch.int64).to(d_out.device)
+    al = _seg_tensor(a_lengths, torch.int64, d_out.device)
+    bl = _seg_tensor(b_lengths, torch.int64, d_out.device)
     assert al.numel() == bl.numel() == off.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
     _chk("glcZeroRunJoinSegments", _ct().glcZeroRunJoinSegments(d_a.data_ptr(), d_b.data_ptr(), off.data_ptr(), al.data_ptr(), bl.data_ptr(),
-                                                                 ln.data_ptr(), off.numel(), max_len, d_out.data_ptr(), stream))
-    torch.cuda.synchronize(d_out.device)
+                                                                 ln.data_ptr(), off.numel(), max_len, d_out.data_ptr(), _stream_ptr(stream)))
+    _seg_done(d_out.device, keep, off, ln, al, bl)
     return d_out
 
 
@@ -1398,14 +1433,14 @@ def sparse_mask_words(max_len):
 def _sparse_args(d_base, offsets, lengths, fill):
     import torch
     dev = d_base.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
-    fl = torch.as_tensor(fill, dtype=torch.int32).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
+    fl = _seg_tensor(fill, torch.int32, dev)
     assert off.numel() == ln.numel() == fl.numel()
     return off, ln, fl
 
 
-def sparse_split_segments(d_in, d_kept, offsets, lengths, fill, max_len=None, stream=None):
+def sparse_split_segments(d_in, d_kept, offsets, lengths, fill, max_len=None, stream=None, keep=None):
     """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in, cut into 64-byte chunks: the chunks that are not
     all fill[i] go, in order, to d_kept at offsets[i].  Returns (mask int32 tensor [count, sparse_mask_words(max_len)], kept
     lengths int64 tensor [count])"""
@@ -1415,12 +1450,12 @@ def sparse_split_segments(d_in, d_kept, offsets, lengths, fill, max_len=None, st
     mask = torch.zeros((off.numel(), max(1, sparse_mask_words(max_len))), dtype=torch.int32, device=d_in.device)
     klen = torch.zeros(max(1, off.numel()), dtype=torch.int64, device=d_in.device)
     _chk("glcSparseSplitSegments", _ct().glcSparseSplitSegments(d_in.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
-                                                                 fl.data_ptr(), mask.data_ptr(), d_kept.data_ptr(), klen.data_ptr(), stream))
-    torch.cuda.synchronize(d_in.device)                        # (off / ln / fl are temporaries of this call)
+                                                                 fl.data_ptr(), mask.data_ptr(), d_kept.data_ptr(), klen.data_ptr(), _stream_ptr(stream)))
+    _seg_done(d_in.device, keep, off, ln, fl)
     return mask[:, :sparse_mask_words(max_len)], klen[:off.numel()]
 
 
-def sparse_join_segments(d_kept, d_out, offsets, lengths, fill, mask, max_len=None, stream=None):
+def sparse_join_segments(d_kept, d_out, offsets, lengths, fill, mask, max_len=None, stream=None, keep=None):
     """the inverse of sparse_split_segments: `mask` is its mask tensor (rows of sparse_mask_words(max_len) words)"""
     import torch
     off, ln, fl = _sparse_args(d_kept, offsets, lengths, fill)
@@ -1428,8 +1463,8 @@ def sparse_join_segments(d_kept, d_out, offsets, lengths, fill, mask, max_len=No
     m = mask.contiguous()
     assert m.numel() == off.numel() * sparse_mask_words(max_len) or sparse_mask_words(max_len) == 0
     _chk("glcSparseJoinSegments", _ct().glcSparseJoinSegments(d_kept.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
-                                                               fl.data_ptr(), m.data_ptr(), d_out.data_ptr(), stream))
-    torch.cuda.synchronize(d_kept.device)
+                                                               fl.data_ptr(), m.data_ptr(), d_out.data_ptr(), _stream_ptr(stream)))
+    _seg_done(d_kept.device, keep, off, ln, fl, m)
     return d_out
 
 
@@ -1440,38 +1475,38 @@ def dedup_chunks(max_len):
     return (int(max_len) + DEDUP_CHUNK - 1) // DEDUP_CHUNK
 
 
-def dedup_map_segments(d_base, offsets, lengths, max_len=None, stream=None):
+def dedup_map_segments(d_base, offsets, lengths, max_len=None, stream=None, keep=None):
     """the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_base as the blocks of one frame, cut into 512-byte
     chunks: an int32 tensor [count * dedup_chunks(max_len)] with, for chunk c of segment i at i * nch + c, the id of the earlier
     chunk it repeats under the writer's rule, or its own id"""
     import torch
     dev = d_base.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
     L = _ct()
     src = torch.zeros(max(1, off.numel() * dedup_chunks(max_len)), dtype=torch.int32, device=dev)
     work = torch.empty(max(16, int(L.glcDedupWorkBytes(off.numel(), max_len))), dtype=torch.uint8, device=dev)
     _chk("glcDedupMapSegments", L.glcDedupMapSegments(d_base.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len, src.data_ptr(),
-                                                      work.data_ptr(), work.numel(), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln / work are temporaries of this call)
+                                                      work.data_ptr(), work.numel(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln, work)
     return src[:off.numel() * dedup_chunks(max_len)]
 
 
-def dedup_fill_segments(d_out, offsets, lengths, src, max_len=None, stream=None):
+def dedup_fill_segments(d_out, offsets, lengths, src, max_len=None, stream=None, keep=None):
     """the inverse of dedup_map_segments, in place: every chunk whose entry of `src` is not its own id is copied from the chunk the
     entry names"""
     import torch
     dev = d_out.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     max_len = int(max(lengths, default=0)) if max_len is None else int(max_len)
     s = src.contiguous()
     assert s.numel() == off.numel() * dedup_chunks(max_len)
     _chk("glcDedupFillSegments", _ct().glcDedupFillSegments(d_out.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), max_len,
-                                                             s.data_ptr() if s.numel() else None, stream))
-    torch.cuda.synchronize(dev)
+                                                             s.data_ptr() if s.numel() else None, _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln, s)
     return d_out
 
 
@@ -1482,7 +1517,7 @@ def _shuffle(fn, d_in, elem, out, stream):
     if out is None:
         out = torch.empty_like(x)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
-    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), stream))
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), _stream_ptr(stream)))
     return out
 
 
@@ -1516,7 +1551,7 @@ def _lag_shuffle(fn, d_in, elem, lag, fold, out, stream):
         out = torch.empty_like(x)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
     _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), int(lag),
-                                int(fold), stream))
+                                int(fold), _stream_ptr(stream)))
     return out
 
 
@@ -1551,7 +1586,7 @@ def _byte_delta(fn, d_in, lag, stride, out, stream):
         out = torch.empty_like(x)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
     _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(lag), int(stride),
-                                stream))
+                                _stream_ptr(stream)))
     return out
 
 
@@ -1568,31 +1603,37 @@ def unbyte_delta(d_in, lag, stride, out=None, stream=None):
     return _byte_delta("glcUnbyteDeltaDevice", d_in, lag, stride, out, stream)
 
 
-def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None):
+def shuffle_segments(d_in, d_out, offsets, lengths, elem, inverse=False, stream=None, keep=None):
     """shuffle (or unshuffle) the segments [offsets[i], + lengths[i]) of the device uint8 tensor d_in into the same ranges of d_out"""
     import torch
     dev = d_in.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     fn = "glcUnshuffleSegments" if inverse else "glcShuffleSegments"
-    _chk(fn, getattr(_ct(), fn)(d_in.data_ptr(), d_out.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), int(elem), stream))
-    torch.cuda.synchronize(dev)                                # (off / ln are temporaries of this call)
+    _chk(fn, getattr(_ct(), fn)(d_in.data_ptr(), d_out.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(), int(elem), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
     return d_out
 
 
-def crc32_segments(d_base, offsets, lengths, stream=None):
-    """CRC-32 (zlib.crc32) of segments [offsets[i], + lengths[i]) of the device uint8 tensor d_base; returns a list of ints"""
+def crc32_segments_device(d_base, offsets, lengths, stream=None, keep=None):
+    """CRC-32 (zlib.crc32) of segments [offsets[i], + lengths[i]) of the device uint8 tensor d_base: an int32 device tensor
+    [count] (the sums' bit patterns)"""
     import torch
     dev = d_base.device
-    off = torch.as_tensor(offsets, dtype=torch.int64).to(dev)
-    ln = torch.as_tensor(lengths, dtype=torch.int64).to(dev)
+    off = _seg_tensor(offsets, torch.int64, dev)
+    ln = _seg_tensor(lengths, torch.int64, dev)
     assert off.numel() == ln.numel()
     out = torch.zeros(max(1, off.numel()), dtype=torch.int32, device=dev)
     _chk("glcCrc32Segments", _ct().glcCrc32Segments(d_base.data_ptr(), off.data_ptr(), ln.data_ptr(), off.numel(),
-                                                    out.data_ptr(), stream))
-    torch.cuda.synchronize(dev)
-    return [int(v) & 0xFFFFFFFF for v in out[:off.numel()].cpu().tolist()]
+                                                    out.data_ptr(), _stream_ptr(stream)))
+    _seg_done(dev, keep, off, ln)
+    return out[:off.numel()]
+
+
+def crc32_segments(d_base, offsets, lengths, stream=None):
+    """crc32_segments_device, waited for: a list of ints"""
+    return [int(v) & 0xFFFFFFFF for v in crc32_segments_device(d_base, offsets, lengths, stream).cpu().tolist()]
 
 
 def container_last_error(plan):
@@ -1708,7 +1749,7 @@ def _unshuffle_range(fn, d_in, elem, first, count, out, stream):
     if out is None:
         out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
-    _chk(fn, getattr(_ct(), fn)(x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(first), int(count), stream))
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(first), int(count), _stream_ptr(stream)))
     return out
 
 
@@ -1731,7 +1772,7 @@ def unlag_delta_unshuffle_range(d_in, elem, lag, fold, first, count, out=None, s
         out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
     _chk("glcUnlagDeltaUnshuffleRangeDevice", _ct().glcUnlagDeltaUnshuffleRangeDevice(
-        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(lag), int(fold), int(first), int(count), stream))
+        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(lag), int(fold), int(first), int(count), _stream_ptr(stream)))
     return out
 
 
@@ -1745,7 +1786,7 @@ def ungrid_delta_unshuffle_range(d_in, elem, width, fold, first, count, out=None
         out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
     _chk("glcUngridDeltaUnshuffleRangeDevice", _ct().glcUngridDeltaUnshuffleRangeDevice(
-        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(fold), int(first), int(count), stream))
+        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(fold), int(first), int(count), _stream_ptr(stream)))
     return out
 
 
@@ -1759,5 +1800,5 @@ def unbyte_delta_range(d_in, lag, stride, first, count, out=None, stream=None):
         out = torch.empty(int(count), dtype=torch.uint8, device=x.device)
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count)
     _chk("glcUnbyteDeltaRangeDevice", _ct().glcUnbyteDeltaRangeDevice(
-        x.data_ptr(), out.data_ptr(), x.numel(), int(lag), int(stride), int(first), int(count), stream))
+        x.data_ptr(), out.data_ptr(), x.numel(), int(lag), int(stride), int(first), int(count), _stream_ptr(stream)))
     return out

@@ -1,8 +1,14 @@
 """One small container input and every encoder setting of the container with the CPU model that writes its bytes, shared by
 test_gpu_scratch_fill.py and test_gpu_call_history.py.  The shape is the plain-C rigs' scaled down -- plan n = 4096, rows 4,
 nine blocks and a ragged tail of 1203 bytes: two full frames, a frame of one block, the tail -- and the blocks are chosen so
-that every mode writes the record kind it exists for.  Pure numpy and the models: no GPU."""
+that every mode writes the record kind it exists for.
+
+On that input the filter rules of formats 13, 14 and 16 pick what format 10 picks -- no lag above 1, no width, no byte
+candidate -- so those settings, and the hand-set byte predictor of format 15, have a second table, FILTERS: each entry with its own
+plan shape, the input its feature exists for and the expected container (the golden fixtures; the byte-delta model).
+entry(name) answers for the names of both tables.  Pure numpy and the models: no GPU."""
 import functools
+import os
 
 import numpy as np
 
@@ -12,7 +18,15 @@ import choose_model
 import container_model as M
 import datagen
 import dedup_model
+import byte_delta_inputs
+import byte_delta_model
 import filter_auto_model
+import filter_byte_inputs
+import filter_byte_model
+import filter_grid_inputs
+import filter_grid_model
+import filter_lag_inputs
+import filter_lag_model
 import grid_model
 import lag_model
 import runs_model
@@ -36,7 +50,8 @@ def data():
     return x
 
 
-def _settings(glc, plan, codec=0, elem=0, delta=False, mode=None, lag=None, grid=None, filter_auto=False):
+def _settings(glc, plan, codec=0, elem=0, delta=False, mode=None, lag=None, grid=None, filter_auto=False, filter_lag=False,
+              filter_grid=False, filter_byte=False, byte_delta=None):
     glc.container_set_shuffle(plan, elem)
     glc.container_set_codec(plan, codec)
     if mode:
@@ -49,6 +64,14 @@ def _settings(glc, plan, codec=0, elem=0, delta=False, mode=None, lag=None, grid
         glc.container_set_delta_grid(plan, *grid)
     if filter_auto:
         glc.container_set_filter_auto(plan, 1)
+    if filter_lag:
+        glc.container_set_filter_lag(plan, 1)
+    if filter_grid:
+        glc.container_set_filter_grid(plan, 1)
+    if filter_byte:
+        glc.container_set_filter_byte(plan, 1)
+    if byte_delta:
+        glc.container_set_byte_delta(plan, *byte_delta)
 
 
 # name -> (the settings of a plan that writes and reads it, the model's writer, a record kind the stream must hold or None)
@@ -71,9 +94,57 @@ CONFIGS = {
 }
 
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+BIG_N, BIG_ROWS, BIG_TAIL = 65536, 4, 3001                   # the shape of the 64 KiB entries; byte_delta: one full frame and this tail
+_FILTER_AUTO = dict(codec=1, mode="auto", filter_auto=True)
+
+
+def _fixture(name):
+    return lambda: open(os.path.join(GOLDEN, name), "rb").read()
+
+
+def _byte_delta_input(kind):
+    x = (byte_delta_inputs.rgb8(BIG_N * BIG_ROWS + BIG_TAIL, 427) if kind == "rgb8" else
+         byte_delta_inputs.grey8(BIG_N * BIG_ROWS + BIG_TAIL, 721))
+    return x
+
+
+# name -> (plan n, plan rows, the settings, the input, the expected container, the model's reader).  byte_delta is the hand-set
+# predictor at (lag 3, stride 1281) on an RGB image 427 wide, byte_delta_lag at (1, 0) on a greyscale image
+FILTERS = {
+    "filter_lag": (filter_lag_inputs.N, filter_lag_inputs.ROWS, dict(_FILTER_AUTO, filter_lag=True), filter_lag_inputs.mixed_stream,
+                   _fixture("filter_lag_v13_container.bin"), filter_lag_model.read),
+    "filter_grid": (filter_grid_inputs.N, filter_grid_inputs.ROWS, dict(_FILTER_AUTO, filter_lag=True, filter_grid=True),
+                    filter_grid_inputs.mixed_stream, _fixture("filter_grid_v14_container.bin"), filter_grid_model.read),
+    "filter_byte": (filter_byte_inputs.N, filter_byte_inputs.ROWS, dict(_FILTER_AUTO, filter_lag=True, filter_grid=True, filter_byte=True),
+                    filter_byte_inputs.mixed_stream, _fixture("filter_byte_v16_container.bin"), filter_byte_model.read),
+    "byte_delta": (BIG_N, BIG_ROWS, dict(codec=1, mode="auto", byte_delta=(3, 1281)), lambda: _byte_delta_input("rgb8"),
+                   lambda: byte_delta_model.write(_byte_delta_input("rgb8"), BIG_N, BIG_ROWS, 3, 1281), byte_delta_model.read),
+    "byte_delta_lag": (BIG_N, BIG_ROWS, dict(codec=1, mode="auto", byte_delta=(1, 0)), lambda: _byte_delta_input("grey8"),
+                       lambda: byte_delta_model.write(_byte_delta_input("grey8"), BIG_N, BIG_ROWS, 1, 0), byte_delta_model.read),
+}
+ALL = tuple(CONFIGS) + tuple(FILTERS)
+
+
+def reset(glc, plan):
+    """every container setting back to a new plan's, innermost first (off is always legal): what lets one plan go from one
+    name of the tables to another"""
+    glc.container_set_filter_byte(plan, 0)
+    glc.container_set_filter_grid(plan, 0)
+    glc.container_set_filter_lag(plan, 0)
+    glc.container_set_byte_delta(plan, 0, 0)
+    glc.container_set_filter_auto(plan, 0)
+    glc.container_set_delta_grid(plan, 0, 0)
+    glc.container_set_delta_lag(plan, 1, 0)
+    for off in (glc.container_set_dedup, glc.container_set_auto, glc.container_set_ans, glc.container_set_sparse,
+                glc.container_set_runs, glc.container_set_delta, glc.container_set_shuffle):
+        off(plan, 0)
+    glc.container_set_codec(plan, 0)
+
+
 def configure(glc, plan, name, pipelined=False):
     plan.set_pipelining(pipelined)
-    _settings(glc, plan, **CONFIGS[name][0])
+    _settings(glc, plan, **(CONFIGS[name][0] if name in CONFIGS else FILTERS[name][2]))
     return plan
 
 
@@ -81,3 +152,14 @@ def configure(glc, plan, name, pipelined=False):
 def want(name):
     """the model's container of data() under the setting `name`, computed once per process"""
     return CONFIGS[name][1](data())
+
+
+@functools.lru_cache(maxsize=None)
+def entry(name):
+    """(plan n, plan rows, the input, the expected container) of a name of either table, made once per process"""
+    if name in CONFIGS:
+        return N, ROWS, data(), want(name)
+    n, rows, _, make, expect, _ = FILTERS[name]
+    x = make()
+    x.setflags(write=False)
+    return n, rows, x, expect()

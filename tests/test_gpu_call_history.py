@@ -34,6 +34,10 @@ def _host(t):
 def _reset_container(glc, plan):
     """every container setting back to a new plan's, each by its own setter (off is always legal), innermost first; then the
     getters must all say so"""
+    glc.container_set_filter_byte(plan, 0)
+    glc.container_set_filter_grid(plan, 0)
+    glc.container_set_filter_lag(plan, 0)
+    glc.container_set_byte_delta(plan, 0, 0)
     glc.container_set_filter_auto(plan, 0)
     glc.container_set_delta_grid(plan, 0, 0)
     glc.container_set_delta_lag(plan, 1, 0)
@@ -43,8 +47,10 @@ def _reset_container(glc, plan):
     glc.container_set_codec(plan, glc.CONTAINER_CODEC_BWT)
     state = (glc.container_get_codec(plan), glc.container_get_shuffle(plan), glc.container_get_delta(plan), glc.container_get_runs(plan),
              glc.container_get_sparse(plan), glc.container_get_ans(plan), glc.container_get_auto(plan), glc.container_get_dedup(plan),
-             glc.container_get_filter_auto(plan), tuple(glc.container_get_delta_lag(plan)), tuple(glc.container_get_delta_grid(plan)))
-    assert state == (glc.CONTAINER_CODEC_BWT, 0, 0, 0, 0, 0, 0, 0, 0, (1, 0), (0, 0)), state
+             glc.container_get_filter_auto(plan), tuple(glc.container_get_delta_lag(plan)), tuple(glc.container_get_delta_grid(plan)),
+             glc.container_get_filter_byte(plan), glc.container_get_filter_grid(plan), glc.container_get_filter_lag(plan),
+             tuple(glc.container_get_byte_delta(plan)))
+    assert state == (glc.CONTAINER_CODEC_BWT, 0, 0, 0, 0, 0, 0, 0, 0, (1, 0), (0, 0), 0, 0, 0, (0, 0)), state
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,7 +143,7 @@ TARGETS = {"short_block": t_short_block, "container_bwt": t_container_bwt, "cont
 # --- the calls that go first: name -> (plan n, plan rows, the call, T's pipelining, a call behind T or None) --------------------
 @functools.lru_cache(maxsize=None)
 def _all_tiers_want():
-    return [O.compress(b) for b in T.all_tiers_blocks_1m()]
+    return list(T.all_tiers_compressed_1m())
 
 
 def p_all_tiers(glc, plan):
@@ -277,3 +283,115 @@ def test_target_call_behind_another_call(glc, cuda, previous, target):
             TARGETS[target](glc, plan, t_pipelined)
             if behind:
                 behind(glc, plan)
+
+
+# --- the second matrix: formats 13 to 16 on plans of (65536, 4) ---------------------------------------------------------------------
+# The filter probes of formats 13, 14 and 16 keep their winners in device memory between launches and read a wider pinned
+# record back; the hand-set byte predictor of format 15 carves the same staging its own way.  Inputs and expected bytes are
+# small_container.FILTERS' (the golden fixtures, the byte-delta model).
+BIG_N, BIG_ROWS = S.BIG_N, S.BIG_ROWS
+
+
+def _configured(glc, plan, name, pipelined):
+    _reset_container(glc, plan)
+    assert S.entry(name)[:2] == (plan.n, plan.rows)
+    return S.configure(glc, plan, name, pipelined)
+
+
+def _encode_equals(glc, plan, name, pipelined):
+    _configured(glc, plan, name, pipelined)
+    _, _, x, want = S.entry(name)
+    c = glc.container_compress(plan, _gpu(x))
+    assert _host(c).tobytes() == want, "%s: container bytes" % name
+
+
+def _decode_equals(glc, plan, name, pipelined):
+    _configured(glc, plan, name, pipelined)
+    _, _, x, want = S.entry(name)
+    assert np.array_equal(_host(glc.container_decompress(plan, _gpu(np.frombuffer(want, np.uint8)))), x), "%s: decode" % name
+    assert glc.container_last_error(plan) == (0, -1, -1)
+
+
+@functools.lru_cache(maxsize=None)
+def _bwt_text():
+    x = datagen.text_bytes(5 * BIG_N + S.TAIL, seed=31)        # a full frame, a frame of one block, a tail
+    return x, M.write(x, BIG_N, BIG_ROWS)
+
+
+@functools.lru_cache(maxsize=None)
+def _refused_v16():
+    """one case of filter_byte_model.refusal_cases: a flipped bit in a record, which the reader meets after it has started"""
+    import filter_byte_model as B
+    cases, _ = B.refusal_cases(S.entry("filter_byte")[3])
+    (cont, want), = [(c, w) for name, c, w, reads in cases if name == "a flipped record bit" and reads == B.READS]
+    assert want[0] == M.RECORD_CRC
+    return cont, want
+
+
+def p2_bwt_text(glc, plan):
+    """a BWT container of text: the sorter's arrays, the BWT codec's carving of the scratch"""
+    plan.set_pipelining(False)
+    _reset_container(glc, plan)
+    x, want = _bwt_text()
+    c = glc.container_compress(plan, _gpu(x))
+    assert _host(c).tobytes() == want
+    assert np.array_equal(_host(glc.container_decompress(plan, c)), x)
+
+
+def p2_v15_hand_set(glc, plan):
+    _encode_equals(glc, plan, "byte_delta", False)
+    _decode_equals(glc, plan, "byte_delta", False)
+
+
+def p2_v14_encode(glc, plan):
+    _encode_equals(glc, plan, "filter_grid", False)
+
+
+def p2_v16_decode(glc, plan):
+    """on a fresh plan its first call"""
+    _decode_equals(glc, plan, "filter_byte", False)
+
+
+def p2_v16_refused(glc, plan):
+    _configured(glc, plan, "filter_byte", False)
+    cont, want = _refused_v16()
+    with pytest.raises(glc.CudppError) as e:
+        glc.container_decompress(plan, _gpu(np.frombuffer(cont, np.uint8)), cap=S.entry("filter_byte")[2].size)
+    assert e.value.code == UNKNOWN and glc.container_last_error(plan) == want
+
+
+def t2_v16_encode(glc, plan, pipelined):
+    """the fixture's bytes, and the four reports of the picks its frame words name"""
+    import filter_auto_model as F
+    import filter_byte_model as B
+    _encode_equals(glc, plan, "filter_byte", pipelined)
+    picks = [B.word_format(w) for w in F.frame_words(S.entry("filter_byte")[3])]
+    assert glc.container_last_filters(plan) == B.last_filters(picks)
+    assert glc.container_last_lag_filters(plan) == B.last_lag_filters(picks)
+    assert glc.container_last_grid_filters(plan) == B.last_grid_filters(picks)
+    assert glc.container_last_byte_filters(plan) == B.last_byte_filters(picks)
+
+
+def t2_v16_decode(glc, plan, pipelined):
+    _decode_equals(glc, plan, "filter_byte", pipelined)
+
+
+def t2_v15(glc, plan, pipelined):
+    for name in ("byte_delta", "byte_delta_lag"):
+        _encode_equals(glc, plan, name, pipelined)
+        _decode_equals(glc, plan, name, pipelined)
+
+
+PREVIOUS2 = {"bwt_text": p2_bwt_text, "v15_hand_set": p2_v15_hand_set, "v14_encode": p2_v14_encode, "v16_decode_first": p2_v16_decode,
+             "v16_refused": p2_v16_refused}
+TARGETS2 = {"v16_encode": t2_v16_encode, "v16_decode": t2_v16_decode, "v15_encode_decode": t2_v15}
+
+
+@pytest.mark.parametrize("pipelined", [False, True], ids=["serial", "pipelined"])
+@pytest.mark.parametrize("target", list(TARGETS2))
+@pytest.mark.parametrize("previous", list(PREVIOUS2))
+def test_filter_target_behind_another_call(glc, cuda, previous, target, pipelined):
+    with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, BIG_N, rows=BIG_ROWS) as plan:
+        for rnd in range(2):
+            PREVIOUS2[previous](glc, plan)
+            TARGETS2[target](glc, plan, pipelined)

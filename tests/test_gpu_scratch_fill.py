@@ -67,6 +67,8 @@ def _want_bwt(key):
 
 @functools.lru_cache(maxsize=None)
 def _want_compress(key):
+    if key == "all_tiers":
+        return list(T.all_tiers_compressed_1m())               # (shared with the other modules that make this call)
     return [O.compress(b) for b in _blocks(key)]
 
 
@@ -301,26 +303,64 @@ def test_the_small_container_takes_every_path():
     assert M.HUFF in kinds and 2 in kinds                      # both codecs chosen
 
 
+def test_the_filter_inputs_pick_what_their_formats_add():
+    """CPU: from the frame words of the expected containers, the inputs of S.FILTERS between them pick a lag above 1 at each of
+    elem 2 and elem 4, a grid width, a byte candidate with a stride and one with a lag alone; the hand-set byte predictor's
+    header names its pair; and each model reads its container back to the input.  Without this the entries could go as hollow
+    as four more names in S.CONFIGS would be: on S.data() formats 13, 14 and 16 all pick what format 10 picks."""
+    import struct
+    import byte_delta_model as BD
+    import filter_auto_model as F
+    import filter_byte_model as B
+    import filter_grid_model as Q
+    import filter_lag_model as FL
+    picks = {name: [mod.word_format(w) for w in F.frame_words(S.entry(name)[3])]
+             for name, mod in (("filter_lag", FL), ("filter_grid", Q), ("filter_byte", B))}
+    for elem in (2, 4):
+        assert any(e == elem and d == 1 and lag > 1 for e, d, lag, _ in picks["filter_lag"]), (elem, picks["filter_lag"])
+    assert any(w > 0 and e > 1 for e, _, _, _, w in picks["filter_grid"]), picks["filter_grid"]
+    byte = [p for p in picks["filter_byte"] if B.is_byte(p)]
+    assert any(p[4] > 0 for p in byte), byte                   # a stride
+    assert any(p[4] == 0 and p[2] > 1 for p in byte), byte     # a lag alone
+    for name, (lag, stride) in (("byte_delta", (3, 1281)), ("byte_delta_lag", (1, 0))):
+        flags, _, word3 = struct.unpack("<HHII", S.entry(name)[3][4:16])[1:]
+        assert struct.unpack("<H", S.entry(name)[3][4:6])[0] == BD.VERSION and BD.lag_stride_of(flags, word3) == (lag, stride), name
+    versions = dict(filter_lag=13, filter_grid=14, filter_byte=16, byte_delta=15, byte_delta_lag=15)
+    for name, (n, rows, _, _, _, read) in S.FILTERS.items():
+        pn, prows, x, want = S.entry(name)
+        assert (pn, prows) == (n, rows) and struct.unpack("<H", want[4:6])[0] == versions[name], name
+        frames = [(f["nb"], f["blk_len"]) for f in M.layout(want)["frames"]]
+        assert frames[0] == (rows, n) and len(frames) >= 2 and frames[-1][0] == 1 and frames[-1][1] < n, (name, frames)   # a full frame, a ragged tail
+        assert np.array_equal(read(want), x), name
+
+
+# further range reads of an entry: filter_byte's first frame is a greyscale image 721 wide whose band is 24576 bytes, so this one
+# starts mid-band in it (test_gpu_container_filter_byte.py::test_range_reads)
+MORE_RANGES = {"filter_byte": ((30000, 3000),)}
+
+
 @gpu
 @fills
 @pytest.mark.parametrize("pipelined", [False, True], ids=["serial", "pipelined"])
-@pytest.mark.parametrize("name", list(S.CONFIGS))
+@pytest.mark.parametrize("name", list(S.ALL))
 def test_container_modes(glc, cuda, word, name, pipelined):
     """bytes equal the model's; the same plan and a fresh plan decode them; one range read across a frame boundary"""
-    x, want = S.data(), S.want(name)
+    n, rows, x, want = S.entry(name)
     with _filled(glc, word, "container %s%s" % (name, ", pipelined" if pipelined else "")):
         with glc.Cudpp() as ctx:
-            with S.configure(glc, glc.Plan(ctx, glc.CUDPP_COMPRESS, S.N, rows=S.ROWS), name, pipelined) as plan:
+            with S.configure(glc, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows), name, pipelined) as plan:
                 d_c = glc.container_compress(plan, _gpu(x))
                 assert _host(d_c).tobytes() == want, "container bytes"
                 assert np.array_equal(_host(glc.container_decompress(plan, d_c)), x), "decode on the plan that wrote it"
                 assert glc.container_last_error(plan) == (0, -1, -1)
-            with S.configure(glc, glc.Plan(ctx, glc.CUDPP_COMPRESS, S.N, rows=S.ROWS), name, pipelined) as fresh:
+            with S.configure(glc, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=rows), name, pipelined) as fresh:
                 d_w = _gpu(np.frombuffer(want, np.uint8))
                 assert np.array_equal(_host(glc.container_decompress(fresh, d_w)), x), "decode on a fresh plan"
-                off, count = 3 * S.N + 100, S.N + 500          # the last block of frame 0 and the first of frame 1
+                ranges = ((rows - 1) * n + 100, n + 500),      # the last block of frame 0 and the first of frame 1
                 with glc.container_index(fresh, d_w) as ix:
-                    assert np.array_equal(_host(glc.container_read_range(fresh, ix, d_w, off, count)), x[off:off + count]), "range read"
+                    for off, count in ranges + MORE_RANGES.get(name, ()):
+                        got = _host(glc.container_read_range(fresh, ix, d_w, off, count))
+                        assert np.array_equal(got, x[off:off + count]), "range read (%d, %d)" % (off, count)
 
 
 @gpu

@@ -65,3 +65,10 @@ def all_tiers_blocks_1m():
     for b in blocks:
         b.setflags(write=False)
     return tuple(blocks)
+
+
+@functools.lru_cache(maxsize=None)
+def all_tiers_compressed_1m():
+    """the oracle's compress of each block of all_tiers_blocks_1m(), once per process for every module that needs it"""
+    import oracle_lib
+    return tuple(oracle_lib.compress(b) for b in all_tiers_blocks_1m())
