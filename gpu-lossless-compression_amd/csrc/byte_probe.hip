@@ -416,6 +416,31 @@ hipError_t byte_probe_sums(hipStream_t st, const uint8_t *data, const unsigned l
     return hipGetLastError();
 }
 
+// grid: (ceil(segments / 256)); words: {the winner of the segment's lag sums, stride 0}
+__global__ __launch_bounds__(BP_THREADS) void k_bp_lag_words(const unsigned long long *__restrict__ lag_sums, uint32_t count, uint32_t *__restrict__ words)
+{
+    const uint32_t b = blockIdx.x * BP_THREADS + threadIdx.x;
+    if (b >= count) return;
+    words[(size_t)b * 2] = byte_lag_argmin(lag_sums + (size_t)b * BYTE_LAGS);
+    words[(size_t)b * 2 + 1] = 0;
+}
+
+hipError_t byte_probe_lags(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                           uint32_t count, uint32_t max_len, unsigned long long *lag_sums, uint32_t *words)
+{
+    if (count == 0) return hipSuccess;
+    hipError_t e = hipMemsetAsync(lag_sums, 0, (size_t)count * BYTE_LAGS * 8, st);
+    if (e != hipSuccess) return e;
+    if (max_len >= 8) {
+        uint32_t span;
+        const dim3 grid = bp_grid(count, max_len, &span);
+        hipLaunchKernelGGL(k_bp_lags, grid, dim3(BP_THREADS), 0, st, data, data_off, data_len, max_len, span, lag_sums);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(k_bp_lag_words, dim3((count + BP_THREADS - 1) / BP_THREADS), dim3(BP_THREADS), 0, st, lag_sums, count, words);
+    return hipGetLastError();
+}
+
 hipError_t byte_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                              uint32_t count, uint32_t max_len, const uint32_t *words, uint32_t *planes, unsigned long long *costs)
 {

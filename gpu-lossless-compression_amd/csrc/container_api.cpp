@@ -37,7 +37,11 @@
 // frames, one at the end.  With the CHOOSE codec (super_frame) the bigram probe of choose.hip runs over what is one frame
 // otherwise, its stats rows are read back (the one host read per such group), the rule of choose_rule.h picks the BWT or the
 // order-0 codec per block, and every maximal run of blocks of one choice becomes one frame by that codec's path above: format
-// version 3, kinds 0, 1 and 2, no reader change.
+// version 3, kinds 0, 1 and 2, no reader change.  With glcPlanSetContainerChooseFilters (class_rule.h) the order-0 frames take the
+// auto mode and the filter-auto ladder up to the level's step: from level 2 on the filter probe (at level 5 the byte probe's lag
+// sums and rows as well) runs over the same blocks as segments, the same one read brings their costs, a frame is cut wherever a
+// block's class -- BWT, or order-0 with the element size its costs pick -- changes, and an order-0 frame's filter is pick_filter's
+// over the whole frame; the stream is version 8, 10, 13, 14 or 16, whose readers take kind-0 runs already.
 //
 // Decode (Decoder).  decode_walk() runs ct_walk() (container_internal.h), the one loop over a stream's headers, fed either from
 // the caller's device buffers or from a Source through staging; the frame index (glcContainerIndex*) is the same walk without the
@@ -179,6 +183,13 @@ struct Encoder {
     CtEncDedup dd = {};                                       // the dedup mode's: the sparse mode's scratch (masks, compaction space) and its own
     uint8_t *stage[2] = {nullptr, nullptr};                   // the plan's frame staging, by call parity when pipelined
     unsigned long long *ch_stats = nullptr, *h_stats = nullptr;   // the CHOOSE codec's probe rows [rows][4]: device, pinned
+    // choose-filters (class_rule.h): the level; from level 2 on the filter probe's rows and seven costs of every block of a
+    // super-frame, at level 5 the byte probe's lag sums, {lag, 0} words, rows and two costs of every block as well.  The cost rows
+    // lie behind ch_stats ([rows][4], [rows][7], [rows][2]), so that one copy brings all of a super-frame's statistics
+    uint32_t level = 0;
+    uint32_t *cf_planes = nullptr, *cb_words = nullptr, *cb_planes = nullptr;
+    unsigned long long *cf_costs = nullptr, *cb_costs = nullptr, *cb_lag_sums = nullptr;
+    static constexpr size_t CLASS_HOST_WORDS = CHOOSE_STATS + FILTER_CANDS + BYTE_ROWS;       // 64-bit words a block, device and pinned
     CtReports rep;                                            // this call's choice and filters, committed when it succeeds
     // filter-auto (format version 10): the filter probe's rows and costs of one frame, the frame as its one segment {offset, length},
     // the costs on the host (pinned); rep.filters counts the frames each candidate got (the plan's own filter's candidate with the
@@ -307,6 +318,17 @@ struct Encoder {
             c.round(256);
         }
         if (codec == CT_CODEC_CHOOSE) ch_stats = c.take<unsigned long long>(CHOOSE_STATS * R);
+        if (level >= 2) {
+            cf_costs = c.take<unsigned long long>(FILTER_CANDS * R);
+            cb_costs = c.take<unsigned long long>(BYTE_ROWS * R);
+            c.align(16);
+            cf_planes = c.take<uint32_t>(FILTER_ROWS * 256 * R);
+        }
+        if (level >= 5) {
+            cb_planes = c.take<uint32_t>(BYTE_ROWS * 256 * R);
+            cb_lag_sums = c.take<unsigned long long>(BYTE_LAGS * R);
+            cb_words = c.take<uint32_t>(2 * R);
+        }
         if (filter_auto) {
             fp_planes = c.take<uint32_t>(FILTER_ROWS * 256);
             fp_costs = c.take<unsigned long long>(FP_HOST_WORDS);
@@ -343,13 +365,18 @@ struct Encoder {
         filter_lag = s.filter_lag;
         filter_grid = s.filter_grid;
         filter_byte = s.filter_byte;
+        level = s.choose_filters;
+        if (level) {                                          // the order-0 frames' settings: the level's, as an order-0 plan has them
+            mode = CT_MODE_AUTO;
+            filter_auto = level >= 2; filter_lag = level >= 3; filter_grid = level >= 4; filter_byte = level >= 5;
+        }
         for (uint32_t i = 0; i < FILTER_CANDS; i++) {             // the candidate that is the plan's own filter
             const FilterCand c = filter_cand(i);
             if (c.elem == (fmt.elem ? fmt.elem : 1u) && (c.delta != 0) == fmt.delta()) own_pick = i;
         }
         if (mode == CT_MODE_RUNS) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_runs(c); }));
         if (codec != CT_CODEC_BWT) CT_HIP(carve_on(codec_scratch(P.h, 0), [&](Carver &c) { carve_huff0(c); }));
-        if (codec == CT_CODEC_CHOOSE) CT_HIP(plan_pinned_scratch(P.h, CT_PIN_STATS, 8 * CHOOSE_STATS * (size_t)P.rows, (void **)&h_stats));
+        if (codec == CT_CODEC_CHOOSE) CT_HIP(plan_pinned_scratch(P.h, CT_PIN_STATS, 8 * (level >= 2 ? CLASS_HOST_WORDS : CHOOSE_STATS) * (size_t)P.rows, (void **)&h_stats));
         if (filter_auto) CT_HIP(plan_pinned_scratch(P.h, CT_PIN_COSTS, 8 * FP_HOST_WORDS, (void **)&h_costs));
         if (fmt.filtered() || filter_auto) {
             const int nstage = plan_pipelined(P.h) ? 2 : 1;
@@ -416,7 +443,7 @@ struct Encoder {
         const uint8_t *orig = nullptr;
         CtFormat ff = fmt;                                    // the format whose filter this frame goes through
         uint32_t pick = own_pick;
-        if (filter_auto) {
+        if (filter_auto && by == CT_CODEC_HUFF0) {             // (a BWT frame of the CHOOSE codec takes no filter: word 0)
             uint32_t lag = 1, width = 0;
             const CUDPPResult r = pick_filter(d_in, (unsigned long long)nb * blk_len, &pick, &lag, &width);
             if (r != CUDPP_SUCCESS) return r;
@@ -658,13 +685,33 @@ struct Encoder {
     {
         CT_TRY(ct_block_offsets(P.st, h0.blk_off, h0.blk_len, nb, blk_len));
         CT_TRY(bigram_probe_segments(P.st, d_in, h0.blk_off, h0.blk_len, nb, blk_len, ch_stats));
-        CT_TRY(hipMemcpyAsync(h_stats, ch_stats, 8 * CHOOSE_STATS * (size_t)nb, hipMemcpyDeviceToHost, P.st));
+        // choose-filters from level 2 on: the filter probe with the blocks as its segments, at level 5 the byte probe's lag sums and
+        // its rows at {best lag, stride 0} -- no stride, lag or width search per block: those are the frame's
+        const size_t R = P.rows;
+        if (level >= 2 && blk_len >= CHOOSE_MIN_LEN) {
+            CT_TRY(filter_probe_segments(P.st, d_in, h0.blk_off, h0.blk_len, nb, blk_len, cf_planes, cf_costs));
+            if (level >= 5) {
+                CT_TRY(byte_probe_lags(P.st, d_in, h0.blk_off, h0.blk_len, nb, blk_len, cb_lag_sums, cb_words));
+                CT_TRY(byte_probe_planes(P.st, d_in, h0.blk_off, h0.blk_len, nb, blk_len, cb_words, cb_planes, cb_costs));
+            }
+            CT_TRY(hipMemcpyAsync(h_stats, ch_stats, 8 * CLASS_HOST_WORDS * R, hipMemcpyDeviceToHost, P.st));
+        } else
+            CT_TRY(hipMemcpyAsync(h_stats, ch_stats, 8 * CHOOSE_STATS * (size_t)nb, hipMemcpyDeviceToHost, P.st));
         CT_TRY(hipStreamSynchronize(P.st));
-        auto by = [&](uint32_t b) { return choose_bwt(blk_len, h_stats + CHOOSE_STATS * (size_t)b) ? CT_CODEC_BWT : CT_CODEC_HUFF0; };
+        // the key of a block (class_rule.h): CLASS_BWT, or the order-0 codec with the block's element size
+        auto by = [&](uint32_t b) {
+            unsigned long long cost[CLASS_COSTS] = {};
+            const bool probed = level >= 2 && blk_len >= CHOOSE_MIN_LEN;
+            if (probed) {
+                memcpy(cost, h_stats + CHOOSE_STATS * R + FILTER_CANDS * (size_t)b, 8 * FILTER_CANDS);
+                cost[FILTER_CANDS] = level >= 5 ? h_stats[(CHOOSE_STATS + FILTER_CANDS) * R + BYTE_ROWS * (size_t)b] : GRID_NO_COST;
+            }
+            return class_key(probed ? level : 0u, blk_len, cost, h_stats + CHOOSE_STATS * (size_t)b);
+        };
         for (uint32_t a = 0; a < nb;) {
-            const uint32_t c = by(a);
+            const uint32_t key = by(a), c = key == CLASS_BWT ? CT_CODEC_BWT : CT_CODEC_HUFF0;
             uint32_t b = a + 1;
-            while (b < nb && by(b) == c) b++;
+            while (b < nb && by(b) == key) b++;
             if (c == CT_CODEC_HUFF0) plan_join(P.h);
             const CUDPPResult r = frame(d_in + (size_t)a * blk_len, b - a, blk_len, out, cap, c);
             if (r != CUDPP_SUCCESS) return r;
@@ -1828,6 +1875,16 @@ CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on)
 CUDPPResult glcPlanGetContainerFilterByte(CUDPPHandle plan, unsigned int *on)
 {
     return ct_get(plan, on, [](const CtSettings &s) { return s.filter_byte ? 1u : 0u; });
+}
+
+CUDPPResult glcPlanSetContainerChooseFilters(CUDPPHandle plan, unsigned int level)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_choose_filters(level); });
+}
+
+CUDPPResult glcPlanGetContainerChooseFilters(CUDPPHandle plan, unsigned int *level)
+{
+    return ct_get(plan, level, [](const CtSettings &s) { return s.choose_filters; });
 }
 
 CUDPPResult glcPlanSetContainerDeltaLag(CUDPPHandle plan, unsigned int lag, unsigned int fold)

@@ -7,6 +7,7 @@
 #include "ans_coder.h"
 #include "auto_rule.h"
 #include "choose_rule.h"
+#include "class_rule.h"
 #include "filter_rule.h"
 
 #include <functional>
@@ -708,10 +709,23 @@ struct CtSettings {
         grid_width = w; grid_fold = w ? f : 0;
         return true;
     }
+    // choose-filters: the CHOOSE codec's order-0 frames take the auto mode (level 1) and the filter-auto ladder up to filter-auto,
+    // filter-lag, filter-grid, filter-byte (levels 2 to 5), and the writer cuts its frames by class_rule.h; the stream is version 8,
+    // 10, 13, 14 or 16.  A field of its own: mode, filter_auto and the rest stay what they are under CHOOSE (off), and so do their
+    // getters and refusals.  Only ever non-zero with the CHOOSE codec; every codec call, one that sets CHOOSE again included, puts
+    // it back to 0
+    uint32_t choose_filters = 0;
+    bool set_choose_filters(uint32_t level)
+    {
+        if (level > CLASS_MAX_LEVEL || codec != CT_CODEC_CHOOSE) return false;
+        choose_filters = level;
+        return true;
+    }
     bool set_codec(uint32_t c)
     {
         if (c != CT_CODEC_BWT && c != CT_CODEC_HUFF0 && (c != CT_CODEC_CHOOSE || shuffle)) return false;
         codec = c;
+        choose_filters = 0;
         if (!ct_mode_fits(mode, codec)) mode = CT_MODE_PLAIN;  // (no mode without its codec)
         filter_keep();
         lag_keep();
@@ -759,6 +773,9 @@ struct CtSettings {
     // what the plan speaks as a reader: its mode's version, and with the auto mode the sparse and rANS modes' as well
     uint32_t reader() const
     {
+        if (choose_filters)                                   // (the order-0 plan's with the level's settings; under CHOOSE every mode is off)
+            return CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (choose_filters >= 2 ? CT_READS_FILTER : 0u) | (choose_filters >= 3 ? CT_READS_FILTER_LAG : 0u) |
+                   (choose_filters >= 4 ? CT_READS_FILTER_GRID : 0u) | (choose_filters >= 5 ? CT_READS_FILTER_BYTE : 0u);
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
                mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) | (filter_byte ? CT_READS_FILTER_BYTE : 0u) |
                                       (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) | (byte_on() ? CT_READS_BYTE : 0u) :
@@ -767,7 +784,7 @@ struct CtSettings {
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
     uint32_t kinds() const
     {
-        const bool k3 = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO, k5 = mode == CT_MODE_ANS || mode == CT_MODE_AUTO;
+        const bool k3 = mode == CT_MODE_SPARSE || mode == CT_MODE_AUTO || choose_filters, k5 = mode == CT_MODE_ANS || mode == CT_MODE_AUTO || choose_filters;
         return 1u << CT_KIND_RAW | (codec != CT_CODEC_HUFF0 ? 1u << CT_KIND_HUFF : 0u) | (codec != CT_CODEC_BWT ? 1u << CT_KIND_HUFF0 : 0u) |
                (k3 ? 1u << CT_KIND_SPARSE : 0u) |
                (mode == CT_MODE_RUNS ? 1u << CT_KIND_RUNS : 0u) | (k5 ? 1u << CT_KIND_ANS : 0u) |
@@ -778,6 +795,7 @@ struct CtSettings {
 inline CtFormat format_of(const CtSettings &s)
 {
     CtFormat f;
+    if (s.choose_filters) { f.version = class_version(s.choose_filters); return f; }      // (that version's own triple: (v, 0, 0))
     if (s.filter_auto) { f.version = s.filter_byte ? CT_VERSION_FILTER_BYTE : s.filter_grid ? CT_VERSION_FILTER_GRID : s.filter_lag ? CT_VERSION_FILTER_LAG : CT_VERSION_FILTER; return f; }   // (the filter is each frame's own)
     if (s.byte_on()) {
         f.version = CT_VERSION_BYTE;
@@ -989,6 +1007,10 @@ hipError_t grid_probe_planes(hipStream_t st, const uint8_t *data, const unsigned
 // costs (both GRID_NO_COST below 1024 counted bytes).  planes is 16-byte aligned; nothing need be zeroed.  Everything only enqueues.
 hipError_t byte_probe_sums(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                            uint32_t count, uint32_t max_len, unsigned long long *lag_sums, uint32_t *stride_sums, uint32_t *winners);
+// the lag sums alone and row i of words = {their winner, 0}: what byte_probe_planes takes to probe byte (best lag, stride 0) of
+// every segment without the stride search (class_rule.h's eighth candidate)
+hipError_t byte_probe_lags(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
+                           uint32_t count, uint32_t max_len, unsigned long long *lag_sums, uint32_t *words);
 hipError_t byte_probe_planes(hipStream_t st, const uint8_t *data, const unsigned long long *data_off, const unsigned long long *data_len,
                              uint32_t count, uint32_t max_len, const uint32_t *words, uint32_t *planes, unsigned long long *costs);
 // the auto mode's steps (auto.hip), in order.  Behind the probe, the fill bytes and the blocks' rANS tables: candidate S of every

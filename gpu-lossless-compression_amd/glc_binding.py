@@ -728,6 +728,7 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcPlanSetContainerByteDelta", "glcPlanGetContainerByteDelta",
                      "glcByteProbeSegments", "glcBytePlanesSegments",
                      "glcPlanSetContainerFilterByte", "glcPlanGetContainerFilterByte", "glcContainerLastByteFilters",
+                     "glcPlanSetContainerChooseFilters", "glcPlanGetContainerChooseFilters",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -1037,6 +1038,19 @@ def container_set_filter_byte(plan, on):
 
 def container_get_filter_byte(plan):
     return _get_uint("glcPlanGetContainerFilterByte", plan)
+
+
+def container_set_choose_filters(plan, level):
+    """glcPlanSetContainerChooseFilters: what the CHOOSE codec's order-0 frames take -- 0 (the default) today's CHOOSE, version 3;
+    1 the auto mode, version 8; 2 to 5 filter-auto, filter-lag, filter-grid and filter-byte on top, versions 10, 13, 14 and 16, the
+    frames cut by class (typed with an element size, BWT, order-0).  Legal only while the codec is CHOOSE; every
+    container_set_codec call puts it back to 0.  It is also what the plan reads: the level's version and what an order-0 plan
+    with the same settings reads."""
+    _chk("glcPlanSetContainerChooseFilters", _ct().glcPlanSetContainerChooseFilters(plan.handle, int(level)))
+
+
+def container_get_choose_filters(plan):
+    return _get_uint("glcPlanGetContainerChooseFilters", plan)
 
 
 def container_last_byte_filters(plan):

@@ -760,6 +760,18 @@ CUDPPResult glcPlanGetContainerFilterGrid(CUDPPHandle plan, unsigned int *on);
 CUDPPResult glcPlanSetContainerFilterByte(CUDPPHandle plan, unsigned int on);
 CUDPPResult glcPlanGetContainerFilterByte(CUDPPHandle plan, unsigned int *on);
 
+/* What the CHOOSE codec's order-0 frames take (INTEGRATION.md 4b "choose with filters"): level 0, the default, is CHOOSE as it is
+ * (version 3); level 1 gives those frames the auto mode (record kinds 2, 3 and 5; version 8); levels 2 to 5 add filter-auto,
+ * filter-lag, filter-grid and filter-byte (versions 10, 13, 14 and 16), and the writer then sorts every block into a class --
+ * typed with an element size (the filter rule picks a filter for the block), BWT (the bigram rule), or order-0 -- and cuts a
+ * frame wherever the class changes; an order-0 frame's filter is picked by the level's own probes over the whole frame, a BWT
+ * frame has none.  Legal only while the codec is GLC_CONTAINER_CODEC_CHOOSE (else CUDPP_ERROR_ILLEGAL_CONFIGURATION, nothing
+ * changed), level 0 to 5; every glcPlanSetContainerCodec call, one that sets CHOOSE again included, puts it back to 0.  The mode
+ * and filter settings keep answering as they do under CHOOSE: off, and refused.  The streams are those versions' own: an order-0
+ * plan with the level's settings reads them, and a plan with this level reads what that plan reads. */
+CUDPPResult glcPlanSetContainerChooseFilters(CUDPPHandle plan, unsigned int level);
+CUDPPResult glcPlanGetContainerChooseFilters(CUDPPHandle plan, unsigned int *level);
+
 /* The lag and row stride of the ENCODER's byte predictor (glcByteDeltaDevice); lag 0 = off, the default.  On needs the order-0
  * codec, the auto mode on, the shuffle off (hence the delta, the delta-lag and the grid settings off) and filter-auto off; any other
  * state, a lag above 16 and a stride of 1 or above 65536 are CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.

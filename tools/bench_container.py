@@ -72,6 +72,11 @@ generated on the host and repeated; STRIDE 0: rows of 721 pixels --, or any othe
 the order-0 codec with the auto mode on and no filter (format version 8) and with the byte predictor at (LAG, STRIDE)
 (glcPlanSetContainerByteDelta, format version 15), interleaved, with the same output as the lag section; LAG 0 runs the first only,
 which is also what a build without the setting can run.
+--choose-filters LEVEL [--block-kib K] (its own input: runs of 16 blocks of text-like bytes, float32 values, int64 timestamps, noise
+and an 8-bit greyscale image in turn; --rounds R, at least 1) is the choose-filters section: the BWT codec, the CHOOSE codec alone, the
+order-0 codec at the settings of every level up to LEVEL and the CHOOSE codec at every level up to it
+(glcPlanSetContainerChooseFilters), interleaved, with the filter-auto section's output.  --bigram-kernels times the bigram probe's
+one-pass kernel (segments of up to 64 KiB) against its two-pass kernel on the same blocks of 16 and 64 KiB.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
                                 [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid] |
@@ -317,6 +322,157 @@ def choose_section(torch, glc, plan, d_in, total, rounds):
     med = lambda fn: sorted(event_timed(fn) for _ in range(5))[2]
     res["probe"] = {"bytes": x.numel(), "bigram_probe_GBps": round(x.numel() / med(bigram) / 1e9, 1),
                     "auto_probe_GBps": round(x.numel() / med(probe) / 1e9, 1), "copy_GBps": round(x.numel() / med(lambda: y.copy_(x)) / 1e9, 1)}
+    return res
+
+
+ARCHIVE_KINDS = ("textlike", "float32", "ts64", "noise", "grey8")
+
+
+def archive_on_device(torch, L, dev, total, n, run_blocks=16):
+    """`total` bytes (whole blocks of n) of the mixed input of the choose-filters section: runs of run_blocks blocks of text-like
+    bytes, float32 values, int64 timestamps, noise and an 8-bit greyscale image 721 wide, in turn, each kind one stream cut into
+    its runs"""
+    import byte_delta_inputs
+    import numpy as np
+    run = run_blocks * n
+    nruns = total // run
+    assert nruns >= len(ARCHIVE_KINDS) and total % run == 0, "whole runs, at least one of each kind"
+    out = torch.empty(total, dtype=torch.uint8, device=dev).view(nruns, run)
+    for k, kind in enumerate(ARCHIVE_KINDS):
+        mine = list(range(k, nruns, len(ARCHIVE_KINDS)))
+        need = len(mine) * run
+        if kind == "textlike":
+            src = text_on_device(torch, dev, kind, need)
+        elif kind == "noise":
+            g = torch.Generator(device=dev)
+            g.manual_seed(0x5EED0030)
+            src = torch.randint(0, 256, (need,), dtype=torch.uint8, device=dev, generator=g)
+        elif kind == "grey8":
+            piece = torch.from_numpy(np.array(byte_delta_inputs.grey8(min(need, LAG_PIECE) // 721 * 721, 721), copy=True)).to(dev)
+            src = piece.repeat((need + piece.numel() - 1) // piece.numel())[:need]
+        else:
+            src = typed_on_device(torch, L, dev, kind, need)[:need]
+        out[mine] = src.contiguous().view(len(mine), run)
+    return out.view(-1)
+
+
+def choose_filters_section(torch, glc, plan, d_in, total, level, rounds):
+    """the container of the mixed input under the CHOOSE codec alone, under the order-0 codec with the settings of every level up to
+    `level` (the auto mode, filter-auto, filter-lag, filter-grid, filter-byte) and under the CHOOSE codec at every level up to it
+    (glcPlanSetContainerChooseFilters), interleaved as sparse_section does it: ratio, encode and decode GB/s per setting, the CRC-32
+    of the container, what glcContainerLastChoice and glcContainerLastFilters report"""
+    n = plan.n
+    cap = glc.container_bound(total, n)
+    cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
+    out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
+    d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
+    ladder = (glc.container_set_auto, glc.container_set_filter_auto, glc.container_set_filter_lag, glc.container_set_filter_grid,
+              glc.container_set_filter_byte)
+
+    def order0(k):
+        def go():
+            glc.container_set_codec(plan, 1)
+            for setter in ladder[:k]:
+                setter(plan, 1)
+        return go
+
+    def choose(k):
+        def go():
+            glc.container_set_codec(plan, glc.CONTAINER_CODEC_CHOOSE)      # (which puts the level back to 0)
+            if k:
+                glc.container_set_choose_filters(plan, k)
+        return go
+
+    settings = {"bwt": lambda: glc.container_set_codec(plan, 0), "order0": order0(0), "choose": choose(0)}
+    for k in range(1, level + 1):
+        settings["order0_level%d" % k] = order0(k)
+        settings["choose_filters_level%d" % k] = choose(k)
+    res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
+
+    def event_timed(fn):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        return a.elapsed_time(b) * 1e-3
+
+    def enc():
+        glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
+            plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr()))
+
+    def dec(clen):
+        glc._chk("glcContainerDecompressDevice", glc._ct().glcContainerDecompressDevice(
+            plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr()))
+
+    for r in range(rounds + 1):                                # round 0 is the warm-up (scratch allocation, code load)
+        for s, configure in settings.items():
+            configure()
+            t_enc = event_timed(enc)
+            clen = int(d_len.item())
+            t_dec = event_timed(lambda: dec(clen))
+            if r == 0:
+                assert torch.equal(out, d_in) and int(d_len.item()) == total
+                res[s]["container_bytes"], res[s]["ratio"] = clen, round(total / clen, 4)
+                res[s]["crc32"] = zlib.crc32(cont[:clen].cpu().numpy().tobytes())
+                res[s]["last_choice"] = list(glc.container_last_choice(plan))
+                res[s]["last_filters"] = list(glc.container_last_filters(plan))
+                continue
+            res[s]["encode_GBps"].append(round(total / t_enc / 1e9, 2))
+            res[s]["decode_GBps"].append(round(total / t_dec / 1e9, 2))
+    for s in settings:
+        for k in ("encode_GBps", "decode_GBps"):
+            v = sorted(res[s][k])
+            res[s][k + "_median"], res[s][k + "_spread"] = v[len(v) // 2], round(v[-1] - v[0], 2)
+    glc.container_set_codec(plan, 0)
+    return res
+
+
+def bigram_kernels_section(torch, glc, L, dev, rounds, launches=20, span=64 * MiB):
+    """k_ch_probe16 against k_ch_probe on the same segments: glcBigramProbeSegments picks the kernel by its maxLen, so the blocks of
+    16 KiB and of 64 KiB of text-like bytes, Zipf bytes and zeros are probed with maxLen = the block (the one-pass kernel) and with
+    maxLen = 65537 (the two-pass kernel, which the lengths keep to the same bytes), `rounds` interleaved rounds of `launches`
+    launches each, timed with device events; the stats rows of the two must be equal"""
+    import datagen
+    import numpy as np
+    data = {"textlike": text_on_device(torch, dev, "textlike", span), "zeros": torch.zeros(span, dtype=torch.uint8, device=dev)}
+    z = torch.empty(span, dtype=torch.uint8, device=dev)
+    thr = torch.from_numpy(datagen.zipf_thresholds().view(np.int32)).to(dev)
+    assert L.glcGenZipfPhilox(z.data_ptr(), span, 0, 0x5EED0002, thr.data_ptr(), None) == 1
+    data["zipf"] = z
+    C = glc._ct()
+    res = {}
+    for blk in (16384, 65536):
+        nseg = span // blk
+        off = torch.arange(nseg, dtype=torch.int64, device=dev) * blk
+        ln = torch.full((nseg,), blk, dtype=torch.int64, device=dev)
+        for kind, x in data.items():
+            stats = {k: torch.empty((nseg, 4), dtype=torch.int64, device=dev) for k in ("one_pass", "two_pass")}
+            max_len = {"one_pass": blk, "two_pass": 65537}
+
+            def run(k):
+                for _ in range(launches):
+                    glc._chk("glcBigramProbeSegments", C.glcBigramProbeSegments(x.data_ptr(), off.data_ptr(), ln.data_ptr(), nseg, max_len[k],
+                                                                                 stats[k].data_ptr(), None))
+            rates = {k: [] for k in stats}
+            for r in range(rounds + 1):                            # round 0 is the warm-up
+                for k in ("two_pass", "one_pass"):
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    a.record()
+                    run(k)
+                    b.record()
+                    torch.cuda.synchronize()
+                    if r:
+                        rates[k].append(round(launches * span / (a.elapsed_time(b) * 1e-3) / 1e9, 1))
+            assert torch.equal(stats["one_pass"], stats["two_pass"]), (blk, kind)
+            row = {}
+            for k, v in rates.items():
+                s = sorted(v)
+                row[k + "_GBps"], row[k + "_GBps_median"], row[k + "_GBps_spread"] = v, s[len(s) // 2], round(s[-1] - s[0], 1)
+            row["one_pass_min_over_two_pass_max"] = round(min(rates["one_pass"]) / max(rates["two_pass"]), 3)
+            res["%d KiB, %s" % (blk >> 10, kind)] = row
     return res
 
 
@@ -734,6 +890,10 @@ def main():
                     help="the byte section (format version 15): the byte predictor's lag, 0 (off only) to 16, and row stride, 0 or 2 to 65536")
     ap.add_argument("--filter-byte", action="store_true",
                     help="the filter-byte section (format version 16): filter-grid, filter-grid with bytes, and --byte-delta set by hand")
+    ap.add_argument("--choose-filters", type=int, default=None, choices=range(0, 6), metavar="LEVEL",
+                    help="the choose-filters section: the mixed input under CHOOSE, the order-0 codec at every level's settings and CHOOSE at every level up to LEVEL")
+    ap.add_argument("--block-kib", type=int, default=1024, help="the choose-filters section's block size in KiB (1 to 1024)")
+    ap.add_argument("--bigram-kernels", action="store_true", help="the bigram probe's one-pass kernel against its two-pass kernel at 16 and 64 KiB blocks")
     args = ap.parse_args()
     byte_delta = tuple(int(v) for v in args.byte_delta.split(",")) if args.byte_delta else None
     assert byte_delta is None or len(byte_delta) == 2, "--byte-delta LAG,STRIDE"
@@ -748,10 +908,25 @@ def main():
     import datagen
     L = glc.lib()
     dev = torch.device("cuda:0")
+    if args.bigram_kernels:
+        print(json.dumps({"workload": "bigram probe kernels, 64 MiB a kind", "bigram_kernels": bigram_kernels_section(torch, glc, L, dev, max(1, args.rounds))}))
+        return
+    if args.choose_filters is not None:
+        n = args.block_kib << 10
+        total = int(args.gib * 1024 * MiB) // (16 * n) * (16 * n)
+        d_in = archive_on_device(torch, L, dev, total, n)
+        torch.cuda.synchronize()
+        res = {"workload": "archive (runs of 16 blocks of %s): %d x %d KiB blocks, plan rows %d, pipelining %s"
+                           % (", ".join(ARCHIVE_KINDS), total // n, args.block_kib, args.rows, bool(args.pipelining))}
+        with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
+            plan.set_pipelining(bool(args.pipelining))
+            res["choose_filters"] = choose_filters_section(torch, glc, plan, d_in, total, args.choose_filters, max(1, args.rounds))
+        print(json.dumps(res))
+        return
     n = MiB
     nblocks = int(args.gib * 1024)
     total = nblocks * n
-    if args.data in ("pages", "pages_noise"):                  # the model's own generator, on the host
+    if args.data in ("pages", "pages_noise"):                 # the model's own generator, on the host
         import dedup_inputs
         d_in = torch.from_numpy(np.array(dedup_inputs.make(args.data, total), copy=True)).to(dev)
     elif args.data in ("stereo16", "adc16x8", "xyz32", "cplx64", "i32x4"):
