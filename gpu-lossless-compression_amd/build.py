@@ -19,7 +19,7 @@ _TAG = hashlib.sha1(" ".join(os.environ.get("GLC_CXXFLAGS", "").split()).encode(
 OBJ = os.path.join(HERE, "build_variant", _TAG) if _VARIANT else os.path.join(HERE, "build")
 LIB = os.environ.get("GLC_LIB_OUT") or os.path.join(HERE, "libglc_amd.so")
 SOURCES = ["cudpp_api.cpp", "bwt_tiers.cpp", "bwt_sa.hip", "bwt_bucket.hip", "bwt_sample.hip", "bwt_periodic.hip", "mtf.hip", "huffman.hip", "decode.hip", "culzss.hip",
-           "culzss_api.cpp", "hd_decode.hip", "hd_encode.hip", "hd_batch.hip", "probe.hip", "exchange.cpp", "container.hip", "container_api.cpp", "segments_api.cpp", "shuffle.hip", "delta.hip", "lag.hip", "grid.hip", "byte_delta.hip", "sparse.hip", "zrun.hip", "ans.hip", "auto.hip", "choose.hip", "dedup.hip", "filter_probe.hip", "lag_probe.hip", "grid_probe.hip", "byte_probe.hip"]
+           "culzss_api.cpp", "hd_decode.hip", "hd_encode.hip", "hd_batch.hip", "probe.hip", "exchange.cpp", "container.hip", "container_api.cpp", "segments_api.cpp", "shuffle.hip", "delta.hip", "lag.hip", "grid.hip", "vol.hip", "byte_delta.hip", "sparse.hip", "zrun.hip", "ans.hip", "auto.hip", "choose.hip", "dedup.hip", "filter_probe.hip", "lag_probe.hip", "grid_probe.hip", "byte_probe.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread"] + os.environ.get("GLC_CXXFLAGS", "").split()
 
 

@@ -6,7 +6,8 @@
 // two things: the FILTER every frame's bytes go through as one segment before the frame's blocks are cut (none, the byte-plane
 // shuffle of shuffle.hip, the fused delta + shuffle of delta.hip, under version 11 that delta with the flags' lag and fold, lag.hip,
 // under version 12 the 2-D predictor of grid.hip with the row width of the header's word 3, or under version 15 the byte predictor
-// of byte_delta.hip with the flags' lag and word 3's row stride),
+// of byte_delta.hip with the flags' lag and word 3's row stride, or under version 17 the 3-D predictor of vol.hip with word 3's row
+// width and the plane stride of the header's word 7),
 // and which record KINDS a frame may hold (0 BWT + Huffman and
 // 1 raw always; 2 order-0 Huffman, 3 its sparse form (sparse.hip), 4 the BWT codec's zero-run form (zrun.hip), 5 the order-0
 // codec's rANS form (ans.hip) and 6 its dedup form (dedup.hip) where kind2_legal() .. kind6_legal() say so).  ct_legal() is the
@@ -141,7 +142,8 @@ void make_header(uint32_t h[8], const CtFormat &f, uint32_t block_len, unsigned 
     h[0] = CT_MAGIC_STREAM; h[1] = f.version | (f.flags << 16);
     h[2] = block_len; h[3] = f.word3();
     h[4] = (uint32_t)total; h[5] = (uint32_t)(total >> 32);
-    h[6] = crc32_host(h, 24); h[7] = 0;
+    h[7] = f.plane;                                            // (0 but under version 17, whose CRC covers it)
+    h[6] = ct_header_crc(h, [](const uint32_t *w, size_t n) { return crc32_host(w, n); });
 }
 
 // measure with a null Carver, allocate (alloc(bytes, &base) -> hipError_t), carve again on the allocation
@@ -1332,7 +1334,7 @@ CUDPPResult index_result(CUDPPHandle plan, std::unique_ptr<GlcContainerIndex> &i
     const CUDPPResult r = walk_result(plan, end, stopped);
     if (r != CUDPP_SUCCESS) return r;
     ix->fmt = CtFormat();
-    (void)parse_frame_filter_format(ix->hdr, &ix->fmt);
+    (void)parse_volume_format(ix->hdr, &ix->fmt);
     ix->block_len = ix->hdr[2];
     ix->total = (unsigned long long)ix->hdr[4] | ((unsigned long long)ix->hdr[5] << 32);
     *index = ix.release();
@@ -1439,7 +1441,7 @@ std::vector<uint8_t> needed_blocks(const CtFormat &fmt, uint32_t nb, uint32_t bl
     const unsigned long long e = fmt.elem, q = F / e;
     const unsigned long long lo = a / e, hi = std::min(q, (b + e - 1) / e);
     if (lo < hi) {                                              // (a range inside the len % elem tail needs no element)
-        *i0 = fmt.bytes() ? lo - lo % ct_byte_step(fmt.width) : fmt.grid() ? lo - lo % ct_grid_period(fmt.width) : fmt.delta() ? lo & ~2047ull : lo;   // (the band's, the run's start)
+        *i0 = fmt.vol() ? lo - lo % ct_vol_slab(fmt.width, fmt.plane) : fmt.bytes() ? lo - lo % ct_byte_step(fmt.width) : fmt.grid() ? lo - lo % ct_grid_period(fmt.width) : fmt.delta() ? lo & ~2047ull : lo;   // (the slab's, the band's, the run's start)
         *i1 = hi;
         for (unsigned long long j = 0; j < e; j++) mark(j * q + *i0, j * q + *i1);
     }
@@ -1504,6 +1506,7 @@ CUDPPResult read_range(Decoder &D, const GlcContainerIndex *ix, RangeIO &io, uns
             uint8_t *el = nullptr;
             CT_TRY(plan_stage(plan, 1, (i1 - i0) * e, &el));
             if (ff.bytes()) CT_TRY(unbyte_delta_range_device(D.P.st, stage, el, q, ff.lag(), ff.width, i0, i1 - i0));
+            else if (ff.vol()) CT_TRY(unvol_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.width, ff.plane, ff.fold(), i0, i1 - i0));
             else if (ff.grid()) CT_TRY(ungrid_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.width, ff.fold(), i0, i1 - i0));
             else if (ff.delta()) CT_TRY(unlag_unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, ff.lag(), ff.fold(), i0, i1 - i0));
             else CT_TRY(unshuffle_range_device(D.P.st, stage, el, q, (uint32_t)e, i0, i1 - i0));
@@ -1615,6 +1618,13 @@ CUDPPResult glcContainerIndexInfo(const GlcContainerIndex *index, unsigned long 
     if (!index || !out) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     out[0] = index->total; out[1] = index->block_len; out[2] = index->frames.size();
     out[3] = index->fmt.version | ((unsigned long long)index->fmt.flags << 16) | ((unsigned long long)index->fmt.word3() << 32);
+    return CUDPP_SUCCESS;
+}
+
+CUDPPResult glcContainerIndexPlane(const GlcContainerIndex *index, unsigned int *plane)
+{
+    if (!index || !plane) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    *plane = index->fmt.plane;
     return CUDPP_SUCCESS;
 }
 
@@ -1909,6 +1919,16 @@ CUDPPResult glcPlanGetContainerDeltaGrid(CUDPPHandle plan, unsigned int *width, 
     if (!fold) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const CUDPPResult r = ct_get(plan, width, [](const CtSettings &s) { return s.grid_width; });
     return r != CUDPP_SUCCESS ? r : ct_get(plan, fold, [](const CtSettings &s) { return s.grid_fold; });
+}
+
+CUDPPResult glcPlanSetContainerDeltaVolume(CUDPPHandle plan, unsigned int plane)
+{
+    return ct_set(plan, [&](CtSettings &s) { return s.set_delta_volume(plane); });
+}
+
+CUDPPResult glcPlanGetContainerDeltaVolume(CUDPPHandle plan, unsigned int *plane)
+{
+    return ct_get(plan, plane, [](const CtSettings &s) { return s.vol_plane; });
 }
 
 CUDPPResult glcPlanSetContainerByteDelta(CUDPPHandle plan, unsigned int lag, unsigned int stride)

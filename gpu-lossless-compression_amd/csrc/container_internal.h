@@ -111,6 +111,17 @@ hipError_t grid_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, 
                                uint32_t fold, bool inverse);
 hipError_t ungrid_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
                                          uint32_t width, uint32_t fold, unsigned long long first, unsigned long long count);
+// k_grid_vsum's walk with the caller's (W, P): every element at P-relative place W or beyond gains the element W places back, in
+// place over `count` elements of v at `out`, the first of them the first of a band.  grid.hip calls it with (width, period),
+// vol.hip with (plane, slab)
+hipError_t grid_vsum_device(hipStream_t st, uint8_t *out, unsigned long long count, uint32_t elem, uint32_t W, uint32_t P);
+// the 3-D predictor + shuffle and its inverses (vol.hip): the 2-D predictor over the differences to the element `plane` places
+// back, the plane behind, within slabs of ct_vol_slab(width, plane) elements; the rules of the grid forms, the range form's
+// `first` a multiple of the slab
+hipError_t vol_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long len, uint32_t elem, uint32_t width,
+                              uint32_t plane, uint32_t fold, bool inverse);
+hipError_t unvol_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint8_t *out, unsigned long long q, uint32_t elem,
+                                        uint32_t width, uint32_t plane, uint32_t fold, unsigned long long first, unsigned long long count);
 // the byte predictor and its inverses (byte_delta.hip): one-byte elements, the predecessor `lag` bytes back (1..16) over the
 // differences to the byte `stride` back (0 = none, else 2..65536: the row above) within bands of ct_grid_period(stride) bytes; no
 // planes, no fold: out has the length and the positions of in.  The range form gives bytes [first, first + count) of the inverse of
@@ -291,15 +302,35 @@ constexpr uint32_t CT_VERSION_MAX = CT_VERSION_BYTE;
 // ct_kinds()'s table, which tools/byte_format_check.cpp pins: CtFormat::kinds() answers version 8's kinds for it
 constexpr uint32_t CT_VERSION_FILTER_BYTE = 16;
 constexpr uint32_t CT_WORD_BYTE_LAG_SHIFT = 25, CT_WORD_BYTE_LAG = 15u << CT_WORD_BYTE_LAG_SHIFT;
+// 17: version 12's stream behind the 3-D predictor of vol.hip: flags 1 | fold << 1 | 4 | 8 (bit 3 the volume flag), word 3 as
+// under version 12 and the header's word 7 the plane stride S in elements, width < S <= 2^24.  Under this version alone word 7 is
+// not 0 and word 6 is the CRC-32 of words 0..5 followed by word 7.  Like 16 it is no entry of ct_kinds()'s table: CtFormat::kinds()
+// answers version 8's kinds for it
+constexpr uint32_t CT_VERSION_VOL = 17;
+constexpr uint32_t CT_FLAG_VOL = 8, CT_VOL_MAX_PLANE = 1u << 24, CT_VOL_PLANES = 16;
+__host__ __device__ inline bool ct_vol_plane_ok(uint32_t width, uint32_t plane) { return plane > width && plane <= CT_VOL_MAX_PLANE; }
+// the slab of the predictor: the plane behind is subtracted only inside a slab of this many elements (about 16 planes, whole
+// bands).  At most 2^28 + 2^21; the product is taken in 64 bits
+__host__ __device__ inline uint32_t ct_vol_slab(uint32_t width, uint32_t plane)
+{
+    const unsigned long long P = ct_grid_period(width);
+    return (uint32_t)(P * (((unsigned long long)CT_VOL_PLANES * plane + P - 1) / P));
+}
+__host__ __device__ inline bool ct_vol_legal(uint32_t flags, uint32_t word3, uint32_t word7)
+{
+    const uint32_t e = word3 & 0xFFu, w = word3 >> CT_WIDTH_SHIFT;
+    return (flags & ~CT_FLAG_FOLD) == (CT_FLAG_DELTA | CT_FLAG_GRID | CT_FLAG_VOL) && (e == 2 || e == 4 || e == 8) && ct_grid_width_ok(w) &&
+           ct_vol_plane_ok(w, word7);
+}
 // what a reading plan speaks beyond versions 1 to 4 (ct_walk's `reader`): its sparse mode reads version 5, its runs mode version 6,
 // its rANS mode version 7, its auto mode version 8 (and, the sparse and rANS bits implied, versions 5 and 7), its dedup mode version 9,
 // its filter-auto setting version 10, its delta-lag setting version 11, its grid setting version 12, its filter-lag setting
 // version 13, its filter-grid setting version 14, its byte-delta setting version 15 and its filter-byte setting version 16 (each is
 // only ever on with the auto mode, so that mode's bits come with it; filter-lag only with filter-auto, filter-grid only with
-// filter-lag, filter-byte only with filter-grid)
+// filter-lag, filter-byte only with filter-grid); its volume setting version 17 (only ever on with the grid setting)
 constexpr uint32_t CT_READS_SPARSE = 1, CT_READS_RUNS = 2, CT_READS_ANS = 4, CT_READS_AUTO = 8, CT_READS_DEDUP = 16, CT_READS_FILTER = 32;
 constexpr uint32_t CT_READS_LAG = 64, CT_READS_GRID = 128, CT_READS_FILTER_LAG = 256, CT_READS_FILTER_GRID = 512;
-constexpr uint32_t CT_READS_BYTE = 1024, CT_READS_FILTER_BYTE = 2048;
+constexpr uint32_t CT_READS_BYTE = 1024, CT_READS_FILTER_BYTE = 2048, CT_READS_VOL = 4096;
 // the one description of a version's record kinds: bit k = kind k is legal under it (0 = no such version)
 __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 {
@@ -313,6 +344,7 @@ __host__ __device__ inline uint32_t ct_kinds(uint32_t version)
 struct CtFormat {
     uint32_t version = CT_VERSION, flags = 0, elem = 0;
     uint32_t width = 0;                                       // the 2-D predictor's row width: 0 but under version 12 and in a grid FRAME's format under versions 14 and 16
+    uint32_t plane = 0;                                       // the 3-D predictor's plane stride: 0 but under version 17
     __host__ __device__ bool filtered() const { return elem != 0; }
     __host__ __device__ bool delta() const { return (flags & CT_FLAG_DELTA) != 0; }
     // the delta's lag and fold: (1, 0) below version 11; under version 13 a FRAME's format (ct_frame_format) carries them
@@ -322,12 +354,14 @@ struct CtFormat {
     __host__ __device__ bool bytes() const { return version == CT_VERSION_BYTE || (version == CT_VERSION_FILTER_BYTE && elem == 1); }
     __host__ __device__ bool lag_flags() const { return version == CT_VERSION_LAG || version == CT_VERSION_FILTER_LAG || version == CT_VERSION_FILTER_GRID || version == CT_VERSION_FILTER_BYTE || bytes(); }
     __host__ __device__ uint32_t lag() const { return lag_flags() ? ((flags & CT_LAG_MASK) >> CT_LAG_SHIFT) + 1 : 1u; }
-    __host__ __device__ uint32_t fold() const { return (lag_flags() || version == CT_VERSION_GRID) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
+    __host__ __device__ uint32_t fold() const { return (lag_flags() || version == CT_VERSION_GRID || version == CT_VERSION_VOL) && (flags & CT_FLAG_FOLD) ? 1u : 0u; }
     // the 2-D predictor: version 12's streams, and under versions 14 and 16 the format of a frame whose word names it
     __host__ __device__ bool grid() const { return version == CT_VERSION_GRID || (version == CT_VERSION_FILTER_GRID && width != 0) || (version == CT_VERSION_FILTER_BYTE && width != 0 && elem != 1); }
-    // the stream header's word 3: the element size, under version 12 with the row width above it
+    // the 3-D predictor: version 17's streams (grid() is false of them: whoever asks both asks this first)
+    __host__ __device__ bool vol() const { return version == CT_VERSION_VOL; }
+    // the stream header's word 3: the element size, under versions 12 and 17 with the row width above it
     __host__ __device__ uint32_t word3() const { return elem | width << CT_WIDTH_SHIFT; }
-    __host__ __device__ uint32_t kinds() const { return ct_kinds(version == CT_VERSION_FILTER_BYTE ? CT_VERSION_AUTO : version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4; 16: version 8's)
+    __host__ __device__ uint32_t kinds() const { return ct_kinds(version == CT_VERSION_FILTER_BYTE || version == CT_VERSION_VOL ? CT_VERSION_AUTO : version); }      // (version 6: all but 3; 7: all but 3 and 4; 8: all but 4; 16, 17: version 8's)
     __host__ __device__ bool kind2_legal() const { return (kinds() >> 2 & 1u) != 0; }
     __host__ __device__ bool kind3_legal() const { return (kinds() >> 3 & 1u) != 0; }
     __host__ __device__ bool kind4_legal() const { return (kinds() >> 4 & 1u) != 0; }
@@ -341,7 +375,8 @@ struct CtFormat {
                version == CT_VERSION_DEDUP ? CT_READS_DEDUP : version == CT_VERSION_FILTER ? CT_READS_FILTER :
                version == CT_VERSION_LAG ? CT_READS_LAG : version == CT_VERSION_GRID ? CT_READS_GRID :
                version == CT_VERSION_FILTER_LAG ? CT_READS_FILTER_LAG : version == CT_VERSION_FILTER_GRID ? CT_READS_FILTER_GRID :
-               version == CT_VERSION_BYTE ? CT_READS_BYTE : version == CT_VERSION_FILTER_BYTE ? CT_READS_FILTER_BYTE : 0u;
+               version == CT_VERSION_BYTE ? CT_READS_BYTE : version == CT_VERSION_FILTER_BYTE ? CT_READS_FILTER_BYTE :
+               version == CT_VERSION_VOL ? CT_READS_VOL : 0u;
     }
 };
 // a frame header's word 3.  Versions 1 to 9, 11, 12 and 15 keep it 0; under versions 10, 13, 14 and 16 it is the frame's filter.  ct_frame_word_legal() is the
@@ -392,6 +427,7 @@ __host__ __device__ inline CtFormat ct_frame_format(const CtFormat &stream, uint
 inline hipError_t filter_device(hipStream_t st, const CtFormat &f, const uint8_t *in, uint8_t *out, unsigned long long len, bool inverse)
 {
     if (f.bytes()) return byte_delta_device(st, in, out, len, f.lag(), f.width, inverse);
+    if (f.vol()) return vol_shuffle_device(st, in, out, len, f.elem, f.width, f.plane, f.fold(), inverse);
     if (f.grid()) return grid_shuffle_device(st, in, out, len, f.elem, f.width, f.fold(), inverse);
     if (f.delta()) return lag_shuffle_device(st, in, out, len, f.elem, f.lag(), f.fold(), inverse);   // ((1, 0): delta.hip's kernels)
     return shuffle_device(st, in, out, len, f.elem, inverse);
@@ -528,11 +564,34 @@ __host__ __device__ inline bool parse_frame_filter_format(const uint32_t h[8], C
     return true;
 }
 
-// the checks on a stream header; false = refused
+// version 17's family beside it, accepted the way 13 to 16 were: parse_frame_filter_format() is pinned up to version 18 by
+// tools/filter_byte_rule_check.cpp, so this is the function the readers call; tools/vol_format_check.cpp pins it.  Word 3 is
+// split as under version 12, word 7 is the plane stride
+__host__ __device__ inline bool parse_volume_format(const uint32_t h[8], CtFormat *f)
+{
+    f->plane = 0;
+    if (parse_frame_filter_format(h, f)) return true;
+    if (f->version != CT_VERSION_VOL || !ct_vol_legal(f->flags, h[3], h[7])) return false;
+    f->elem = h[3] & 0xFFu; f->width = h[3] >> CT_WIDTH_SHIFT; f->plane = h[7];
+    return true;
+}
+
+// a stream header's word 6: the CRC-32 of words 0..5, under version 17 of words 0..5 followed by word 7 (28 bytes), so that the
+// plane stride is covered
+template <class Crc>
+__host__ __device__ inline uint32_t ct_header_crc(const uint32_t h[8], Crc crc)
+{
+    if ((h[1] & 0xFFFFu) != CT_VERSION_VOL) return crc(h, 24);
+    const uint32_t t[7] = {h[0], h[1], h[2], h[3], h[4], h[5], h[7]};
+    return crc(t, 28);
+}
+
+// the checks on a stream header; false = refused.  Word 7 is 0 under every version but 17
 __host__ __device__ inline bool check_stream_header(const CrcTables &C, const uint32_t h[8], CtFormat *fmt, uint32_t *block_len,
                                                     unsigned long long *total)
 {
-    if (h[0] != CT_MAGIC_STREAM || h[7] != 0 || h[6] != crc32_bytes(C, h, 24) || !parse_frame_filter_format(h, fmt)) return false;
+    if (h[0] != CT_MAGIC_STREAM || ((h[1] & 0xFFFFu) != CT_VERSION_VOL && h[7] != 0)) return false;
+    if (h[6] != ct_header_crc(h, [&](const uint32_t *w, size_t n) { return crc32_bytes(C, w, n); }) || !parse_volume_format(h, fmt)) return false;
     if (h[2] == 0 || h[2] > MAX_BLOCK_ELEMS) return false;
     *block_len = h[2];
     *total = (unsigned long long)h[4] | ((unsigned long long)h[5] << 32);
@@ -665,6 +724,10 @@ struct CtSettings {
     // them puts it back to off
     uint32_t grid_width = 0, grid_fold = 0;
     bool grid_on() const { return grid_width != 0; }
+    // volume: the 2-D predictor runs over the differences to the element vol_plane places back (0 = off; vol.hip; the writer
+    // writes version 17).  Only ever on with the grid setting on at a width below it; whatever switches that off switches this off
+    uint32_t vol_plane = 0;
+    bool vol_on() const { return vol_plane != 0; }
     // byte-delta: every frame goes through the byte predictor at (byte_lag, byte_stride) (byte_delta.hip; the writer writes
     // version 15); byte_lag 0 = off.  Only ever on with the order-0 codec, the auto mode on, the shuffle off and filter-auto off;
     // a codec or mode change that ends one of them switches it off, and while it is on the shuffle and filter-auto are refused
@@ -673,7 +736,7 @@ struct CtSettings {
     bool byte_fits() const { return codec == CT_CODEC_HUFF0 && mode == CT_MODE_AUTO && !shuffle && !filter_auto; }
     void lag_keep()
     {
-        if (!lag_fits()) { lag = 1; fold = 0; grid_width = 0; grid_fold = 0; }
+        if (!lag_fits()) { lag = 1; fold = 0; grid_width = 0; grid_fold = 0; vol_plane = 0; }
         if (!byte_fits()) { byte_lag = 0; byte_stride = 0; }
     }
     bool set_byte_delta(uint32_t l, uint32_t s)
@@ -705,8 +768,15 @@ struct CtSettings {
     }
     bool set_delta_grid(uint32_t w, uint32_t f)
     {
-        if (f > 1 || (w && (!ct_grid_width_ok(w) || !lag_fits() || lag_on()))) return false;
+        if (f > 1 || (w && (!ct_grid_width_ok(w) || !lag_fits() || lag_on())) || (w && vol_on() && w >= vol_plane)) return false;
         grid_width = w; grid_fold = w ? f : 0;
+        if (!w) vol_plane = 0;
+        return true;
+    }
+    bool set_delta_volume(uint32_t p)
+    {
+        if (p && (!grid_on() || !ct_vol_plane_ok(grid_width, p))) return false;
+        vol_plane = p;
         return true;
     }
     // choose-filters: the CHOOSE codec's order-0 frames take the auto mode (level 1) and the filter-auto ladder up to filter-auto,
@@ -778,7 +848,7 @@ struct CtSettings {
                    (choose_filters >= 4 ? CT_READS_FILTER_GRID : 0u) | (choose_filters >= 5 ? CT_READS_FILTER_BYTE : 0u);
         return mode == CT_MODE_SPARSE ? CT_READS_SPARSE : mode == CT_MODE_RUNS ? CT_READS_RUNS : mode == CT_MODE_ANS ? CT_READS_ANS :
                mode == CT_MODE_AUTO ? CT_READS_AUTO | CT_READS_SPARSE | CT_READS_ANS | (filter_auto ? CT_READS_FILTER : 0u) | (filter_lag ? CT_READS_FILTER_LAG : 0u) | (filter_grid ? CT_READS_FILTER_GRID : 0u) | (filter_byte ? CT_READS_FILTER_BYTE : 0u) |
-                                      (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) | (byte_on() ? CT_READS_BYTE : 0u) :
+                                      (lag_on() ? CT_READS_LAG : 0u) | (grid_on() ? CT_READS_GRID : 0u) | (vol_on() ? CT_READS_VOL : 0u) | (byte_on() ? CT_READS_BYTE : 0u) :
                mode == CT_MODE_DEDUP ? CT_READS_DEDUP : 0u;
     }
     // the record kinds the writer may emit (bit k = kind k, as ct_kinds())
@@ -811,9 +881,9 @@ inline CtFormat format_of(const CtSettings &s)
         return f;
     }
     if (s.grid_on()) {
-        f.version = CT_VERSION_GRID;
-        f.flags |= (s.grid_fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID;
-        f.width = s.grid_width;
+        f.version = s.vol_on() ? CT_VERSION_VOL : CT_VERSION_GRID;
+        f.flags |= (s.grid_fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID | (s.vol_on() ? CT_FLAG_VOL : 0u);
+        f.width = s.grid_width; f.plane = s.vol_plane;
         return f;
     }
     for (uint32_t i = 0; i < CT_NLEGAL; i++) {

@@ -22,24 +22,11 @@
 // the first W elements of a band are never written.
 //
 // LDS: forward 51264 bytes (two raw images of 16416, padded image 18432): three workgroups per CU; k_grid_vsum none.
-#include "lag_tile.h"
+#include "grid_tile.h"
 
 namespace glc {
 
-constexpr uint32_t GD_FRONT = 4;                               // words in front of a raw image (a read starts up to 8 bytes early)
-constexpr uint32_t GD_RAW_WORDS = GD_FRONT + 4 * SH_NGI;
 constexpr uint32_t GD_VSUM_ROWS = 4;                           // rows k_grid_vsum has in flight per lane
-
-// p with every element k zeroed for which keep(k) is false
-template <uint32_t ELEM, class Keep>
-__device__ __forceinline__ void gd_select(uint32_t (&p)[4], Keep keep)
-{
-#pragma unroll
-    for (uint32_t m = 0; m < 4; m++) {
-        if constexpr (ELEM == 2) p[m] &= (keep(2 * m) ? 0xFFFFu : 0u) | (keep(2 * m + 1) ? 0xFFFF0000u : 0u);
-        else p[m] = keep(ELEM == 8 ? m / 2 : m) ? p[m] : 0u;
-    }
-}
 
 // ---------------------------------------------------------------------------
 // forward: elements [i0, i0 + cnt) of a segment whose q whole elements start at `in`; i0 is a multiple of RUN
@@ -180,9 +167,8 @@ static hipError_t gd_launch_forward(hipStream_t st, uint32_t grid, const uint8_t
 }
 
 template <class T>
-static hipError_t gd_launch_vsum(hipStream_t st, uint8_t *out, unsigned long long count, uint32_t W)
+static hipError_t gd_launch_vsum(hipStream_t st, uint8_t *out, unsigned long long count, uint32_t W, uint32_t P)
 {
-    const uint32_t P = ct_grid_period(W);
     const bool fast = (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (W * sizeof(T)) % 16 == 0;
     const unsigned long long units = (count + P - 1) / P * (fast ? W / (16 / sizeof(T)) : W);
     const dim3 grid((uint32_t)std::min<unsigned long long>((units + SH_THREADS - 1) / SH_THREADS, 1u << 20)), block(SH_THREADS);
@@ -191,14 +177,16 @@ static hipError_t gd_launch_vsum(hipStream_t st, uint8_t *out, unsigned long lon
     return hipGetLastError();
 }
 
-// v -> x over `count` elements at `out`, the first of them the first of a band
-static hipError_t grid_vsum_device(hipStream_t st, uint8_t *out, unsigned long long count, uint32_t elem, uint32_t W)
+// v -> x over `count` elements at `out`, the first of them the first of a band: every element at P-relative place W or beyond
+// gains the element W places back.  vol.hip runs the same walk up its slabs, with (S, Q) for (W, P): the kernel's indices within a
+// band are 32-bit and stay below P + GD_VSUM_ROWS * W, which holds at Q <= 2^28 + 2^21 and S <= 2^24
+hipError_t grid_vsum_device(hipStream_t st, uint8_t *out, unsigned long long count, uint32_t elem, uint32_t W, uint32_t P)
 {
     if (count <= W) return hipSuccess;                         // (one row: nothing above anything)
     switch (elem) {
-    case 2: return gd_launch_vsum<uint16_t>(st, out, count, W);
-    case 4: return gd_launch_vsum<uint32_t>(st, out, count, W);
-    case 8: return gd_launch_vsum<unsigned long long>(st, out, count, W);
+    case 2: return gd_launch_vsum<uint16_t>(st, out, count, W, P);
+    case 4: return gd_launch_vsum<uint32_t>(st, out, count, W, P);
+    case 8: return gd_launch_vsum<unsigned long long>(st, out, count, W, P);
     default: return hipErrorInvalidValue;
     }
 }
@@ -210,7 +198,7 @@ hipError_t grid_shuffle_device(hipStream_t st, const uint8_t *in, uint8_t *out, 
     if (len == 0) return hipSuccess;
     if (inverse) {
         const hipError_t e = lag_shuffle_device(st, in, out, len, elem, 1, fold, true);
-        return e != hipSuccess ? e : grid_vsum_device(st, out, len / elem, elem, width);
+        return e != hipSuccess ? e : grid_vsum_device(st, out, len / elem, elem, width, ct_grid_period(width));
     }
     const unsigned long long tq = SH_TILE / elem, q = len / elem, nt = q ? (q + tq - 1) / tq : 1;
     const uint32_t grid = (uint32_t)std::min<unsigned long long>(nt, 1u << 24);     // (one workgroup per tile up to 256 GiB)
@@ -229,7 +217,7 @@ hipError_t ungrid_unshuffle_range_device(hipStream_t st, const uint8_t *in, uint
     if (count == 0) return hipSuccess;
     if (first % ct_grid_period(width)) return hipErrorInvalidValue;
     const hipError_t e = unlag_unshuffle_range_device(st, in, out, q, elem, 1, fold, first, count);
-    return e != hipSuccess ? e : grid_vsum_device(st, out, count, elem, width);
+    return e != hipSuccess ? e : grid_vsum_device(st, out, count, elem, width, ct_grid_period(width));
 }
 
 } // namespace glc

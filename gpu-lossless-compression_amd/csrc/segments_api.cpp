@@ -1,7 +1,7 @@
 // segments_api.cpp -- the plan-less calls of include/glc_container.h: each takes device segments (a base, offsets and lengths) or
 // one device buffer and a stream, refuses a bad argument before anything is enqueued, and enqueues the kernels of one pass -- the
 // CRC of segments (container.hip), the byte-plane shuffle, the delta + shuffle and its lagged, folded form with their range forms
-// (shuffle.hip, delta.hip, lag.hip) and the 2-D predictor over it (grid.hip),
+// (shuffle.hip, delta.hip, lag.hip), the 2-D predictor over it (grid.hip) and the 3-D predictor over that (vol.hip),
 // the sparse split and join (sparse.hip), the dedup map and fill (dedup.hip), the zero-run split and join (zrun.hip), the rANS
 // coder (ans.hip) and the probes (auto.hip, choose.hip, filter_probe.hip, lag_probe.hip, grid_probe.hip).  The container over a plan, which runs the same
 // passes inside its frames, is container_api.cpp.
@@ -16,17 +16,20 @@ bool lag_ok(unsigned int lag, unsigned int fold) { return lag >= 1 && lag <= 16 
 
 CUDPPResult range_filter_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned long long first,
                              unsigned long long count, void *stream, bool delta, unsigned int lag = 1, unsigned int fold = 0,
-                             const unsigned int *width = nullptr)
+                             const unsigned int *width = nullptr, const unsigned int *plane = nullptr)
 {
-    if (!shuffle_elem_ok(elem) || !lag_ok(lag, fold) || (width && !ct_grid_width_ok(*width))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (!shuffle_elem_ok(elem) || !lag_ok(lag, fold) || (width && !ct_grid_width_ok(*width)) || (plane && !ct_vol_plane_ok(*width, *plane)))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const unsigned long long q = len / elem;
-    if (first > q || count > q - first || (delta && first % (width ? ct_grid_period(*width) : 2048u))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    const uint32_t step = plane ? ct_vol_slab(*width, *plane) : width ? ct_grid_period(*width) : 2048u;
+    if (first > q || count > q - first || (delta && first % step)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     if (count == 0) return CUDPP_SUCCESS;
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
     if (!d_in || !d_out || (a < b + count * elem && b < a + len)) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const uint8_t *in = static_cast<const uint8_t *>(d_in);
     uint8_t *out = static_cast<uint8_t *>(d_out);
+    if (plane) return hip_result(unvol_unshuffle_range_device(st, in, out, q, elem, *width, *plane, fold, first, count));
     if (width) return hip_result(ungrid_unshuffle_range_device(st, in, out, q, elem, *width, fold, first, count));
     return hip_result(delta ? unlag_unshuffle_range_device(st, in, out, q, elem, lag, fold, first, count)      // ((1, 0): delta.hip's)
                             : unshuffle_range_device(st, in, out, q, elem, first, count));
@@ -57,12 +60,15 @@ static CUDPPResult shuffle_segments_api(const void *d_inBase, void *d_outBase, c
 }
 
 static CUDPPResult shuffle_device_api(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, void *stream, bool inverse,
-                                      bool delta = false, unsigned int lag = 1, unsigned int fold = 0, const unsigned int *width = nullptr)
+                                      bool delta = false, unsigned int lag = 1, unsigned int fold = 0, const unsigned int *width = nullptr,
+                                      const unsigned int *plane = nullptr)
 {
     CtFormat f;                                               // (only its filter matters here)
     f.flags = delta ? CT_FLAG_DELTA : 0; f.elem = elem;
-    if (!shuffle_elem_ok(elem) || !lag_ok(lag, fold) || (width && !ct_grid_width_ok(*width))) return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
-    if (width) { f.version = CT_VERSION_GRID; f.flags |= (fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID; f.width = *width; }
+    if (!shuffle_elem_ok(elem) || !lag_ok(lag, fold) || (width && !ct_grid_width_ok(*width)) || (plane && !ct_vol_plane_ok(*width, *plane)))
+        return CUDPP_ERROR_ILLEGAL_CONFIGURATION;
+    if (plane) { f.version = CT_VERSION_VOL; f.flags |= (fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID | CT_FLAG_VOL; f.width = *width; f.plane = *plane; }
+    else if (width) { f.version = CT_VERSION_GRID; f.flags |= (fold ? CT_FLAG_FOLD : 0u) | CT_FLAG_GRID; f.width = *width; }
     else if (lag != 1 || fold) { f.version = CT_VERSION_LAG; f.flags |= (fold ? CT_FLAG_FOLD : 0u) | (lag - 1) << CT_LAG_SHIFT; }
     if (len == 0) return CUDPP_SUCCESS;
     const uintptr_t a = reinterpret_cast<uintptr_t>(d_in), b = reinterpret_cast<uintptr_t>(d_out);
@@ -151,6 +157,25 @@ CUDPPResult glcUngridDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, un
                                                unsigned long long count, void *stream)
 {
     return range_filter_api(d_in, d_out, len, elem, first, count, stream, true, 1, fold, &width);
+}
+
+CUDPPResult glcVolDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                     unsigned int plane, unsigned int fold, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, false, true, 1, fold, &width, &plane);
+}
+
+CUDPPResult glcUnvolDeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                         unsigned int plane, unsigned int fold, void *stream)
+{
+    return shuffle_device_api(d_in, d_out, len, elem, stream, true, true, 1, fold, &width, &plane);
+}
+
+CUDPPResult glcUnvolDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                              unsigned int width, unsigned int plane, unsigned int fold, unsigned long long first,
+                                              unsigned long long count, void *stream)
+{
+    return range_filter_api(d_in, d_out, len, elem, first, count, stream, true, 1, fold, &width, &plane);
 }
 
 // the byte predictor's three calls (byte_delta.hip): glcDeltaShuffleDevice's rules over one-byte elements

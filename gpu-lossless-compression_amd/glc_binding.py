@@ -729,6 +729,8 @@ CONTAINER_SYMBOLS = ["glcContainerBound", "glcContainerCompressDevice", "glcCont
                      "glcByteProbeSegments", "glcBytePlanesSegments",
                      "glcPlanSetContainerFilterByte", "glcPlanGetContainerFilterByte", "glcContainerLastByteFilters",
                      "glcPlanSetContainerChooseFilters", "glcPlanGetContainerChooseFilters",
+                     "glcVolDeltaShuffleDevice", "glcUnvolDeltaUnshuffleDevice", "glcUnvolDeltaUnshuffleRangeDevice",
+                     "glcPlanSetContainerDeltaVolume", "glcPlanGetContainerDeltaVolume", "glcContainerIndexPlane",
                      "glcContainerIndexDevice", "glcContainerIndex", "glcContainerIndexFile", "glcContainerIndexInfo",
                      "glcContainerReadRangeDevice", "glcContainerReadRange", "glcContainerReadRangeFile", "glcContainerLastRangeStats",
                      "glcUnshuffleRangeDevice", "glcUndeltaUnshuffleRangeDevice", "glcContainerIndexFree"]
@@ -787,6 +789,12 @@ def _ct():
         for nm in ("glcGridDeltaShuffleDevice", "glcUngridDeltaUnshuffleDevice"):
             getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, vp]
         L.glcUngridDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
+        L.glcPlanSetContainerDeltaVolume.argtypes = [sz, C.c_uint]
+        L.glcPlanGetContainerDeltaVolume.argtypes = [sz, C.POINTER(C.c_uint)]
+        for nm in ("glcVolDeltaShuffleDevice", "glcUnvolDeltaUnshuffleDevice"):
+            getattr(L, nm).argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp]
+        L.glcUnvolDeltaUnshuffleRangeDevice.argtypes = [vp, vp, ull, C.c_uint, C.c_uint, C.c_uint, C.c_uint, ull, ull, vp]
+        L.glcContainerIndexPlane.argtypes = [vp, C.POINTER(C.c_uint)]
         L.glcPlanSetContainerByteDelta.argtypes = [sz, C.c_uint, C.c_uint]
         L.glcPlanGetContainerByteDelta.argtypes = [sz, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
         for nm in ("glcByteDeltaDevice", "glcUnbyteDeltaDevice"):
@@ -1102,6 +1110,21 @@ def container_get_byte_delta(plan):
     lag, stride = C.c_uint(0), C.c_uint(0)
     _chk("glcPlanGetContainerByteDelta", _ct().glcPlanGetContainerByteDelta(plan.handle, C.byref(lag), C.byref(stride)))
     return int(lag.value), int(stride.value)
+
+
+def container_set_delta_volume(plan, plane):
+    """the plane stride of the 3-D predictor of the plan's container ENCODER (format version 17: the 2-D predictor over the
+    differences to the element `plane` places back, the plane behind); 0 is off.  Any other plane (up to 2^24) needs the grid
+    setting on at a width below it; whatever switches that off switches this off, and while it is on a grid width >= plane is
+    refused.  It is also the version the plan reads: on, versions 1 to 5, 7, 8, 12 and 17; off, a version-17 stream is a
+    stream-header failure."""
+    _chk("glcPlanSetContainerDeltaVolume", _ct().glcPlanSetContainerDeltaVolume(plan.handle, int(plane)))
+
+
+def container_get_delta_volume(plan):
+    plane = C.c_uint(0)
+    _chk("glcPlanGetContainerDeltaVolume", _ct().glcPlanGetContainerDeltaVolume(plan.handle, C.byref(plane)))
+    return int(plane.value)
 
 
 def container_last_filters(plan):
@@ -1604,6 +1627,30 @@ def _byte_delta(fn, d_in, lag, stride, out, stream):
     return out
 
 
+def _vol_shuffle(fn, d_in, elem, width, plane, fold, out, stream):
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == x.numel()
+    _chk(fn, getattr(_ct(), fn)(x.data_ptr() if x.numel() else None, out.data_ptr() if x.numel() else None, x.numel(), int(elem), int(width),
+                                int(plane), int(fold), _stream_ptr(stream)))
+    return out
+
+
+def vol_delta_shuffle(d_in, elem, width, plane, fold, out=None, stream=None):
+    """grid_delta_shuffle over the differences to the element `plane` places back (the plane behind of a row-major volume,
+    width < plane <= 2^24 elements) within slabs of about 16 planes, P * ceil(16 plane / P) elements with P the grid's period.
+    The rules of shuffle"""
+    return _vol_shuffle("glcVolDeltaShuffleDevice", d_in, elem, width, plane, fold, out, stream)
+
+
+def unvol_delta_unshuffle(d_in, elem, width, plane, fold, out=None, stream=None):
+    """the inverse of vol_delta_shuffle"""
+    return _vol_shuffle("glcUnvolDeltaUnshuffleDevice", d_in, elem, width, plane, fold, out, stream)
+
+
 def byte_delta(d_in, lag, stride, out=None, stream=None):
     """the byte predictor over a device uint8 tensor of 8-bit samples: every byte minus the byte `lag` back (1 to 16, the channel
     count; restarting every 2048 bytes), taken over the differences to the byte `stride` back (0 for none, or 2 to 65536, the row
@@ -1669,6 +1716,12 @@ class ContainerIndex:
         a = (C.c_ulonglong * 4)()
         _chk("glcContainerIndexInfo", _ct().glcContainerIndexInfo(self.ptr, a))
         return int(a[0]), int(a[1]), int(a[2]), int(a[3]) & 0xFFFF, (int(a[3]) >> 16) & 0xFFFF, int(a[3]) >> 32
+
+    def plane(self):
+        """the plane stride of a version-17 stream's header (word 7); 0 of every other stream"""
+        p = C.c_uint(0)
+        _chk("glcContainerIndexPlane", _ct().glcContainerIndexPlane(self.ptr, C.byref(p)))
+        return int(p.value)
 
     def close(self):
         if self.ptr:
@@ -1801,6 +1854,20 @@ def ungrid_delta_unshuffle_range(d_in, elem, width, fold, first, count, out=None
     assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
     _chk("glcUngridDeltaUnshuffleRangeDevice", _ct().glcUngridDeltaUnshuffleRangeDevice(
         x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(fold), int(first), int(count), _stream_ptr(stream)))
+    return out
+
+
+def unvol_delta_unshuffle_range(d_in, elem, width, plane, fold, first, count, out=None, stream=None):
+    """elements [first, first + count) of unvol_delta_unshuffle(d_in, elem, width, plane, fold); first a multiple of the slab,
+    P * ceil(16 plane / P) with P = 2048 * ceil(width / 64)"""
+    import torch
+    x = d_in.reshape(-1)
+    assert x.dtype == torch.uint8 and x.is_contiguous()
+    if out is None:
+        out = torch.empty(int(count) * int(elem), dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= int(count) * int(elem)
+    _chk("glcUnvolDeltaUnshuffleRangeDevice", _ct().glcUnvolDeltaUnshuffleRangeDevice(
+        x.data_ptr(), out.data_ptr(), x.numel(), int(elem), int(width), int(plane), int(fold), int(first), int(count), _stream_ptr(stream)))
     return out
 
 

@@ -223,6 +223,22 @@ CUDPPResult glcUnbyteDeltaDevice(const void *d_in, void *d_out, unsigned long lo
 CUDPPResult glcUnbyteDeltaRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int lag, unsigned int stride,
                                       unsigned long long first, unsigned long long count, void *stream);
 
+/* The 3-D (plane-stride) predictor (csrc/vol.hip), for row-major volumes -- 3-D float32 or float64 fields, stacks of detector
+ * frames, CT and MRI stacks: the 2-D predictor over the differences to the element one plane behind.  With `width` and P as
+ * above, `plane` the plane stride S in elements, width < S <= 2^24, and the slab Q = P * ceil(16 S / P): w[i] = x[i] where
+ * i mod Q < S and x[i] - x[i - S] elsewhere; then glcGridDeltaShuffleDevice's rule on w.  The rule is linear in i: a segment needs
+ * no row or plane alignment and S need not be a multiple of width.  With S >= len / elem the output is glcGridDeltaShuffleDevice's.
+ * The inverse is glcUngridDeltaUnshuffleDevice's followed by the sums of the plane behind up every slab.  The rules of
+ * glcGridDeltaShuffleDevice; a plane <= width or above 2^24 is refused like a bad width, with nothing written.  The range form is
+ * glcUngridDeltaUnshuffleRangeDevice's with `first` a multiple of Q. */
+CUDPPResult glcVolDeltaShuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                     unsigned int plane, unsigned int fold, void *stream);
+CUDPPResult glcUnvolDeltaUnshuffleDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem, unsigned int width,
+                                         unsigned int plane, unsigned int fold, void *stream);
+CUDPPResult glcUnvolDeltaUnshuffleRangeDevice(const void *d_in, void *d_out, unsigned long long len, unsigned int elem,
+                                              unsigned int width, unsigned int plane, unsigned int fold, unsigned long long first,
+                                              unsigned long long count, void *stream);
+
 /* The two passes of the sparse mode as batched calls (csrc/sparse.hip).  Segment i is [d_offsets[i], + min(d_lengths[i], maxLen)) of
  * its base, cut into chunks of 64 bytes (the last may be short); d_fill[i] & 255 is its fill byte, given by the caller; its mask is
  * row i of d_mask, rows of ceil(ceil(maxLen / 64) / 32) words: bit c % 32 of word c / 32 is 1 when chunk c is kept, 0 when every
@@ -409,6 +425,8 @@ CUDPPResult glcContainerIndexFile(CUDPPHandle plan, const char *path, GlcContain
 void glcContainerIndexFree(GlcContainerIndex *index);
 /* out: total_len, block_len, frame count, version | flags << 16 | elem << 32 */
 CUDPPResult glcContainerIndexInfo(const GlcContainerIndex *index, unsigned long long out[4]);
+/* the plane stride the stream header's word 7 holds: 0 but of a version-17 stream (glcPlanSetContainerDeltaVolume) */
+CUDPPResult glcContainerIndexPlane(const GlcContainerIndex *index, unsigned int *plane);
 CUDPPResult glcContainerReadRangeDevice(CUDPPHandle plan, const GlcContainerIndex *index, const void *d_in, unsigned long long len,
                                         unsigned long long offset, unsigned long long count, void *d_out);
 CUDPPResult glcContainerReadRange(CUDPPHandle plan, const GlcContainerIndex *index, const void *in, unsigned long long len,
@@ -783,6 +801,19 @@ CUDPPResult glcPlanGetContainerChooseFilters(CUDPPHandle plan, unsigned int *lev
  * version-15 stream as a stream-header failure.  With it off every stream is written as before. */
 CUDPPResult glcPlanSetContainerByteDelta(CUDPPHandle plan, unsigned int lag, unsigned int stride);
 CUDPPResult glcPlanGetContainerByteDelta(CUDPPHandle plan, unsigned int *lag, unsigned int *stride);
+
+/* The plane stride of the ENCODER's 3-D predictor (glcVolDeltaShuffleDevice); 0 = off, the default.  Any other plane needs the
+ * grid setting (glcPlanSetContainerDeltaGrid) on at a width below it; any other state and a plane above 2^24 are
+ * CUDPP_ERROR_ILLEGAL_CONFIGURATION and leave the setting as it was.  While it is on, glcPlanSetContainerDeltaGrid with a width
+ * >= plane is refused.  Whatever switches the grid setting off switches this off; a change among elem 2, 4 and 8 keeps it.  The
+ * stream is format version 17: version 12's stream with the header's flags 1 | fold << 1 | 4 | 8, word 3 elem | width << 8 and
+ * word 7 the plane stride (0 under every other version); under version 17 the header's word 6 is the CRC-32 of words 0..5 followed
+ * by word 7.  Decode, index and range reads take width, plane and fold from the stream header, never from the plan; a range read
+ * starts at a slab.  The setting is also the version the plan speaks: with it on the plan reads versions 1 to 5, 7, 8, 12 and 17;
+ * every other plan refuses a version-17 stream as a stream-header failure.  With it off every stream is written as before.  Not
+ * offered: a stride chosen by the writer, the setting under filter-auto or CHOOSE, the byte predictor in 3-D. */
+CUDPPResult glcPlanSetContainerDeltaVolume(CUDPPHandle plan, unsigned int plane);
+CUDPPResult glcPlanGetContainerDeltaVolume(CUDPPHandle plan, unsigned int *plane);
 
 /* Frames per filter of the plan's last successful container compress: out[i], i < 7, counts the frames that went through candidate
  * i of glcFilterProbeSegments' order -- (1,0) (2,0) (2,1) (4,0) (4,1) (8,0) (8,1), (1,0) being no filter -- and out[7] all frames.

@@ -56,7 +56,10 @@ mode on under the shuffle alone, the plain delta (both format version 8) and the
 --grid W [--fold] (with --data img16, field32 or walk32 of tests/grid_inputs.py at row width W -- about 32 MiB of whole rows
 generated on the host and repeated --, or any typed kind; --rounds R, at least 1) is the grid section: the lag section's settings at
 lag 1 -- the shuffle alone, the plain delta, with --fold the folded delta (format version 11) -- and the 2-D predictor of row width
-W (glcPlanSetContainerDeltaGrid, format version 12), interleaved, with the same output.
+W (glcPlanSetContainerDeltaGrid, format version 12), interleaved, with the same output.  --volume S (with --grid W, and --data
+vol32, vol64, volr32, vol16 or vol16n -- smooth32, smooth64, round32, ct16 and ct16n of tests/vol_inputs.py at row width W and
+plane stride S, about 32 MiB of whole planes generated on the host and repeated --, or any typed kind) adds the 3-D predictor of
+plane stride S over it (glcPlanSetContainerDeltaVolume, format version 17) to the grid section's settings.
 
 --filter-grid (with --grid W [--fold] and the data of the grid section; --rounds R, at least 1) is the filter-grid section: the
 order-0 container under filter-lag, under filter-grid (format version 14) and with elem, W and the fold set by hand (version 12).
@@ -79,7 +82,7 @@ order-0 codec at the settings of every level up to LEVEL and the CHOOSE codec at
 one-pass kernel (segments of up to 64 KiB) against its two-pass kernel on the same blocks of 16 and 64 KiB.
 python tools/bench_container.py [--gib 4] [--rows 2048] [--iters 2] [--pipelining 1|0] [--data KIND] [--shuffle ELEM] [--delta] [--codec 0|1|4]
                                 [--rounds R] [--sparse] [--ans] [--auto] [--dedup] [--runs | --runs-off-only]
-                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--filter-grid] |
+                                [--filter-auto | --filter-auto-off-only] [--lag L [--fold] [--filter-lag] | --grid W [--fold] [--volume S] [--filter-grid] |
                                  --byte-delta LAG,STRIDE [--filter-byte]]"""
 import argparse
 import json
@@ -92,7 +95,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 MiB = 1 << 20
 DATA_ELEM = {"mix": 0, "textlike": 0, "loglike": 0, "zipf": 0, "float32": 4, "smooth32": 4, "smooth64": 8, "quant16": 2, "ts64": 8, "ids32": 4, "ctr32": 4, "adc16": 2, "skew90": 0, "pages": 0, "pages_noise": 0,
-             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4, "img16": 2, "field32": 4, "walk32": 4, "grey8": 0, "rgb8": 0}
+             "stereo16": 2, "adc16x8": 2, "xyz32": 4, "cplx64": 4, "i32x4": 4, "img16": 2, "field32": 4, "walk32": 4, "grey8": 0, "rgb8": 0,
+             "vol32": 4, "vol64": 8, "volr32": 4, "vol16": 2, "vol16n": 2}
+VOL_KINDS = {"vol32": "smooth32", "vol64": "smooth64", "volr32": "round32", "vol16": "ct16", "vol16n": "ct16n"}      # tests/vol_inputs.py's
 LAG_PIECE = 32 * MiB                                           # what tests/lag_inputs.py generates on the host; repeated on the device
 
 
@@ -699,17 +704,18 @@ def filter_lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, g
     return res
 
 
-def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
+def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0, volume=0):
     """the order-0 container with the auto mode on under "shuffle" (the shuffle alone), "delta" (the plain delta), "lag" (the
     delta with `lag` and `fold`, format version 11; left out at (1, 0)) and, with a row width `grid`, "grid" (the 2-D predictor
-    with `fold`, format version 12), interleaved: `rounds` rounds of one encode and one decode per setting after one untimed
-    round, each timed with device events on the plan's (the default) stream"""
+    with `fold`, format version 12) and, with a plane stride `volume` as well, "volume" (the 3-D predictor over it, format
+    version 17), interleaved: `rounds` rounds of one encode and one decode per setting after one untimed round, each timed with
+    device events on the plan's (the default) stream"""
     n = plan.n
     cap = glc.container_bound(total, n)
     cont = torch.empty(cap, dtype=torch.uint8, device=d_in.device)
     out = torch.empty(total, dtype=torch.uint8, device=d_in.device)
     d_len = torch.zeros(1, dtype=torch.int64, device=d_in.device)
-    settings = ["shuffle", "delta"] + (["lag"] if (lag, fold) != (1, 0) else []) + (["grid"] if grid else [])
+    settings = ["shuffle", "delta"] + (["lag"] if (lag, fold) != (1, 0) else []) + (["grid"] if grid else []) + (["volume"] if grid and volume else [])
     res = {s: {"encode_GBps": [], "decode_GBps": []} for s in settings}
     glc.container_set_auto(plan, 1)
     glc.container_set_shuffle(plan, elem)
@@ -728,8 +734,10 @@ def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
             glc.container_set_delta(plan, 0 if s == "shuffle" else 1)      # (off: the lag goes back to (1, 0) with it)
             if s == "lag":
                 glc.container_set_delta_lag(plan, lag, fold)
-            if s == "grid":
+            if s in ("grid", "volume"):
                 glc.container_set_delta_grid(plan, grid, fold)
+            if s == "volume":
+                glc.container_set_delta_volume(plan, volume)
             t_enc = event_timed(lambda: glc._chk("glcContainerCompressDevice", glc._ct().glcContainerCompressDevice(
                 plan.handle, d_in.data_ptr(), total, cont.data_ptr(), cap, d_len.data_ptr())))
             clen = int(d_len.item())
@@ -737,8 +745,8 @@ def lag_section(torch, glc, plan, d_in, total, elem, lag, fold, rounds, grid=0):
                 plan.handle, cont.data_ptr(), clen, out.data_ptr(), total, d_len.data_ptr())))
             if s == "lag":
                 glc.container_set_delta_lag(plan, 1, 0)
-            if s == "grid":
-                glc.container_set_delta_grid(plan, 0, 0)
+            if s in ("grid", "volume"):
+                glc.container_set_delta_grid(plan, 0, 0)       # (the volume goes off with it)
             if r == 0:
                 assert torch.equal(out, d_in) and int(d_len.item()) == total
                 res[s]["container_bytes"], res[s]["ratio"] = clen, total / clen
@@ -886,6 +894,7 @@ def main():
                     help="the filter-grid section (format version 14): filter-lag, filter-lag with grid, and elem / --grid / --fold set by hand")
     ap.add_argument("--fold", action="store_true", help="the lag or grid section's delta folds its sign")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the grid section (format version 12): the 2-D predictor's row width, 2 to 65536")
+    ap.add_argument("--volume", type=int, default=0, metavar="S", help="with --grid W: the 3-D predictor's plane stride (format version 17), above W, up to 2^24")
     ap.add_argument("--byte-delta", default=None, metavar="LAG,STRIDE",
                     help="the byte section (format version 15): the byte predictor's lag, 0 (off only) to 16, and row stride, 0 or 2 to 65536")
     ap.add_argument("--filter-byte", action="store_true",
@@ -939,6 +948,12 @@ def main():
         assert args.grid, "the grids are the grid section's"
         row = args.grid * grid_inputs.KINDS[args.data]
         piece = torch.from_numpy(grid_inputs.grid_bytes(args.data, max(row, min(total, LAG_PIECE) // row * row), args.grid)).to(dev)      # whole rows
+        d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
+    elif args.data in VOL_KINDS:
+        import vol_inputs
+        assert args.grid and args.volume > args.grid, "the volumes are the grid section's with --volume"
+        plane = args.volume * DATA_ELEM[args.data]
+        piece = torch.from_numpy(vol_inputs.vol_bytes(VOL_KINDS[args.data], max(plane, min(total, LAG_PIECE) // plane * plane), args.grid, args.volume)).to(dev)   # whole planes
         d_in = piece.repeat((total + piece.numel() - 1) // piece.numel())[:total].contiguous()
     elif args.data in ("grey8", "rgb8"):
         import byte_delta_inputs
@@ -1019,7 +1034,8 @@ def main():
         with glc.Cudpp() as ctx, glc.Plan(ctx, glc.CUDPP_COMPRESS, n, rows=args.rows) as plan:
             plan.set_pipelining(bool(args.pipelining))
             glc.container_set_codec(plan, 1)
-            res["grid"] = lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], 1, int(args.fold), max(1, args.rounds), args.grid)
+            res["grid"] = lag_section(torch, glc, plan, d_in, total, args.shuffle or DATA_ELEM[args.data], 1, int(args.fold), max(1, args.rounds), args.grid,
+                                      args.volume)
         print(json.dumps(res))
         return
     if args.filter_lag:

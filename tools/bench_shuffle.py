@@ -11,6 +11,10 @@
              glcGridDeltaShuffleDevice / glcUngridDeltaUnshuffleDevice (csrc/grid.hip) at row width W beside the lag kernels at
              (1, 1), which the grid's expectations are stated against; k_grid_vsum takes its 16-byte path when W * N and the
              destination's address (--offset) are multiples of 16, else its element path
+  vol W,Sf N / unvol W,Sf N   (with --grid W --volume S, the fold on)
+             glcVolDeltaShuffleDevice / glcUnvolDeltaUnshuffleDevice (csrc/vol.hip) at plane stride S beside the grid kernels at
+             W, which the volume's expectations are stated against; the inverse is the grid's followed by k_grid_vsum up the
+             slabs, whose rate alone is what "unvol" takes longer than "ungrid"
   byte L,S / unbyte L,S   (with --bytes)
              glcByteDeltaDevice / glcUnbyteDeltaDevice (csrc/byte_delta.hip) at (lag, stride) = (1, 0), (3, 0), (1, 4096) and (3, 1281),
              beside the kernels they are stated against on the same byte count: lag 3 2 / unlag 3 2 and grid 1281 2 / ungrid 1281 2
@@ -21,7 +25,7 @@ table gives the median, the fastest and the slowest run of every variant, as GB/
 and relative to the copy's median.  The buffer (--gib, default 1) is larger than the 256 MiB Infinity Cache on purpose.
 --offset A B misaligns source and destination by A and B bytes.  One JSON line on stdout, the table on stderr or in --md FILE.
 
-python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--grid W] [--bytes] [--md FILE]"""
+python tools/bench_shuffle.py [--gib 1] [--reps 30] [--warmup 3] [--offset 0 0] [--lag] [--grid W [--volume S]] [--bytes] [--md FILE]"""
 import argparse
 import ctypes as C
 import importlib.util
@@ -50,6 +54,7 @@ def main():
     ap.add_argument("--offset", type=int, nargs=2, default=[0, 0])
     ap.add_argument("--lag", action="store_true", help="the lagged, folded delta kernels beside the others")
     ap.add_argument("--grid", type=int, default=0, metavar="W", help="the 2-D predictor's kernels at row width W beside the lag kernels at (1, 1)")
+    ap.add_argument("--volume", type=int, default=0, metavar="S", help="with --grid W: the 3-D predictor's kernels at plane stride S beside the grid kernels")
     ap.add_argument("--bytes", action="store_true", help="the byte predictor's kernels beside the lag and grid kernels at elem 2")
     ap.add_argument("--md", default=None)
     args = ap.parse_args()
@@ -109,6 +114,15 @@ def main():
             lagged(L.glcGridDeltaShuffleDevice, elem, args.grid, 1)()
             glc._chk("ungrid", L.glcUngridDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, args.grid, 1, None))
             assert torch.equal(back, src), (elem, args.grid)
+            if args.volume:
+                def vol(fn, elem=elem):
+                    return lambda: glc._chk("vol", fn(src.data_ptr(), dst.data_ptr(), n, elem, args.grid, args.volume, 1, None))
+
+                variants.append(("vol %d,%df %d" % (args.grid, args.volume, elem), vol(L.glcVolDeltaShuffleDevice)))
+                variants.append(("unvol %d,%df %d" % (args.grid, args.volume, elem), vol(L.glcUnvolDeltaUnshuffleDevice)))
+                vol(L.glcVolDeltaShuffleDevice)()
+                glc._chk("unvol", L.glcUnvolDeltaUnshuffleDevice(dst.data_ptr(), back.data_ptr(), n, elem, args.grid, args.volume, 1, None))
+                assert torch.equal(back, src), (elem, args.grid, args.volume)
         del back
     if args.bytes:
         def byted(fn, lag, stride):
